@@ -25,7 +25,11 @@ and two ONE-process modes over N devices, no torch — what a cgo host calls (cs
   --mode router: cfg-2/3 replicas in one process: one coalescer per device behind pg_router_*, 768 x N host threads with one
       request outstanding each; the timed region is exactly steps x 256 x N requests.
 
-At N = 1 the same JSON line also carries (each a bounded, separately timed leg after the headline region):
+A plain run sets up, warms up, times exactly --steps steps and prints the headline line (metric, value, unit,
+higher_is_better, dtype, ms_per_step, config); --dump-outputs DIR also writes what the last timed step returned as
+DIR/<name>.npy.  Everything else runs only with --full: the oracle spot checks, the N > 1 parity preflight, the rooflines
+and their un-overlapped scan legs, device info, and at N = 1 (each a bounded, separately timed leg after the headline region)
+single-request latency, the rank stage per shape, the other precision modes, the batch sweep, and:
   "concurrent_callers"  the same table / model / k served through the request coalescer to --callers host threads
                         that each issue ONE request at a time (how pairec calls its plug-ins), items/s + p50/p99
   "gaussian_table"      the headline measurement repeated on N(0,1) rows (the int8 screen's less favourable case)
@@ -101,6 +105,13 @@ def parse_args():
     ap.add_argument("--page", type=int, default=100, help="entries each concurrent caller asks for (ctx.Size)")
     ap.add_argument("--latency-reqs", type=int, default=500,
                     help="single-request latency samples at N=1 (the first 10 %% are discarded as warm-up, SURVEY.md 8d)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: oracle spot checks, the N > 1 preflight, rooflines and their "
+                         "un-overlapped scan legs, latency, rank shapes, the other precisions, batch sweep, callers, power, other "
+                         "tables and configs, live rocprofv3 traffic, device info, the CPU baseline (the --no-* options prune it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB in all)")
     args = ap.parse_args()
     if args.rows is None:
         args.rows = 125_000_000 if args.mode in ("shard", "group") else 100_000_000
@@ -375,6 +386,41 @@ def power_leg(step_fn, drain_fn, seconds=3.0, sync_each=False):
     return {"seconds": el, "steps": n, "ms_per_step": el / n * 1e3, "readings": len(rd),
             "package_w": float(np.median([r_["package_w"] for r_ in rd])), "sclk_mhz": float(np.median([r_["sclk_mhz"] for r_ in rd])),
             "cap_w": rd[0]["cap_w"]}
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as path/<name>.npy, integers as float64 (exact), floats kept at their width.  All arrays
+    are [requests, ...]: above 64 MB in all, a fixed seeded sample of requests is written instead (the same rows of every
+    array; their indices as requests_sampled.npy)."""
+    os.makedirs(path, exist_ok=True)
+    conv = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        conv[name] = a.astype(np.float64 if a.dtype.kind in "iub" or a.dtype == np.float64 else np.float32)
+    total = sum(a.nbytes for a in conv.values())
+    if total > DUMP_LIMIT_BYTES:
+        n = min(a.shape[0] for a in conv.values())
+        keep = max(1, int(n * DUMP_LIMIT_BYTES // total) - 1)
+        idx = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        conv = {k_: a[idx] for k_, a in conv.items()}
+        conv["requests_sampled"] = idx.astype(np.float64)
+    for name, a in conv.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+
+
+def pipeline_outputs(pipe):
+    """What pg_recommend_end handed the caller for the last batch `pipe` issued, as [R, K] host arrays."""
+    b = pipe.bufs[(pipe.issued - 1) % pipe.depth]
+    R, K = pipe.R, pipe.K
+    out = {"rows": np.zeros((R, K), np.uint64), "recall_scores": np.zeros((R, K), np.float32),
+           "rank_scores": np.zeros((R, K), np.float32), "fused_scores": np.zeros((R, K), np.float64),
+           "order": np.zeros((R, K), np.uint32)}
+    for a_, p_ in zip(out.values(), b):
+        pipe.ctx.d2h(a_, p_)
+    return out
 
 
 def make_queries(o, step, R, dim):
@@ -1566,7 +1612,7 @@ def inprocess_main(args, R, K):
     devices = list(range(N)) if have.value >= N else [0] * N
     physical = len(set(devices))
     pf = None
-    if N > 1 and not args.no_preflight:
+    if N > 1 and args.full and not args.no_preflight:
         # before anything is timed: the group step on a small table over these devices against the oracle
         pf = preflight_group(pa, o, devices)
         if not pf["ok"]:
@@ -1589,13 +1635,14 @@ def inprocess_main(args, R, K):
         for s_ in range(max(args.warmup, 1)):                       # (the first step builds shadows and both lanes' scratch)
             g.recommend(expr, "gpu_dnn", qs[s_ % len(qs)], K, args.page, dpp_candidates=dpp_c, dpp_alpha=DPP_ALPHA,
                         dpp_window=DPP_WINDOW)
-        g.recommend(expr, "gpu_dnn", qs[0], K, args.page, dpp_candidates=dpp_c)
-        # per-shard scan stage of an un-overlapped step (HIP events on each shard's launch stream)
         scan = []
-        for sh in range(N):
-            ms, nbytes = C.c_double(), C.c_uint64()
-            _lib.check(L.pg_last_scan_kernel_ms(C.c_void_p(L.pg_group_ctx(g.h, sh)), C.byref(ms), C.byref(nbytes)))
-            scan.append(ms.value)
+        if args.full:
+            # per-shard scan stage of an un-overlapped step (HIP events on each shard's launch stream)
+            g.recommend(expr, "gpu_dnn", qs[0], K, args.page, dpp_candidates=dpp_c)
+            for sh in range(N):
+                ms, nbytes = C.c_double(), C.c_uint64()
+                _lib.check(L.pg_last_scan_kernel_ms(C.c_void_p(L.pg_group_ctx(g.h, sh)), C.byref(ms), C.byref(nbytes)))
+                scan.append(ms.value)
         import gc
         gc.collect()
         gc.disable()
@@ -1610,10 +1657,13 @@ def inprocess_main(args, R, K):
         elapsed = time.perf_counter() - t0
         gc.enable()
         assert int(page[4].min()) == args.page
-        scan_avg_ms = float(max(scan))
-        tv = _TableView(L, C.c_void_p(L.pg_group_ctx(g.h, 0)), C.c_void_p(L.pg_group_table(g.h, 0)))
-        rf = roofline_block(tv, R, args, args.rows, scan_avg_ms, None)
-        rf["per_shard_scan_ms"] = scan
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, dict(zip(("rows", "recall_scores", "rank_scores", "fused_scores", "count"), page)))
+        rf = None
+        if args.full:
+            tv = _TableView(L, C.c_void_p(L.pg_group_ctx(g.h, 0)), C.c_void_p(L.pg_group_table(g.h, 0)))
+            rf = roofline_block(tv, R, args, args.rows, float(max(scan)), None)
+            rf["per_shard_scan_ms"] = scan
         g.destroy()
         workload = ("configs[4]: %d x %d fp32 table in %d row-range shards (%d rows each), %d requests x top-%d -> merge -> "
                     "owner-computes DNN3 rank (%s) -> fuse -> sort -> DPPSort(%d candidates, page %d, window %d); one process, "
@@ -1651,16 +1701,18 @@ def inprocess_main(args, R, K):
         res = run(args.steps * R * N)
         elapsed = res.seconds
         served = router.served().tolist()
-        # the scan stage alone on replica 0, one caller-made batch at a time (per-kernel duration without overlap)
-        d_qs = [ctxs[0].to_device(make_queries(o, s_, R, args.dim)) for s_ in range(4)]
-        import copy
-        a1 = copy.copy(args)
-        a1.warmup, a1.steps = 1, 8
         router.destroy()
         for c_ in cos:
             c_.destroy()
-        _, _, scan_ms = run_headline(pa, ctxs[0], tables[0], models[0], expr, d_qs, a1, R, K, ctxs[0].synchronize)
-        rf = roofline_block(tables[0], R, args, args.rows, float(np.mean(scan_ms)), None, ctxs[0].last_scan_kernel()[1])
+        rf = None
+        if args.full:
+            # the scan stage alone on replica 0, one caller-made batch at a time (per-kernel duration without overlap)
+            d_qs = [ctxs[0].to_device(make_queries(o, s_, R, args.dim)) for s_ in range(4)]
+            import copy
+            a1 = copy.copy(args)
+            a1.warmup, a1.steps = 1, 8
+            _, _, scan_ms = run_headline(pa, ctxs[0], tables[0], models[0], expr, d_qs, a1, R, K, ctxs[0].synchronize)
+            rf = roofline_block(tables[0], R, args, args.rows, float(np.mean(scan_ms)), None, ctxs[0].last_scan_kernel()[1])
         out_extra = {"callers": callers, "requests": int(res.requests), "p50_ms": res.p50_ms, "p99_ms": res.p99_ms,
                      "served_per_replica": served}
         for m_ in models:
@@ -1681,7 +1733,7 @@ def inprocess_main(args, R, K):
         "dtype": args.prec, "data": "synthetic", "mode": args.mode,
         "config": {"workload": workload, "requests_per_step": R * (N if args.mode == "router" else 1),
                    "candidates_per_request": K, "table_rows_per_gpu": args.rows, "dim": args.dim, "parallelism": parallelism},
-        "roofline": rf, "cpu_baseline": None, "device": device_info(),
+        "roofline": rf, "cpu_baseline": None, "device": device_info() if args.full else None,
     }
     out.update(out_extra)
     out["preflight"] = pf
@@ -1689,7 +1741,7 @@ def inprocess_main(args, R, K):
         out["ranks"] = N
         out["dev_mode"] = "PG_BENCH_SHARE_GPU=1: %d logical %s on ONE device — a correctness run of the N > 1 code, not a measurement" \
                           % (N, "shards" if args.mode == "group" else "replicas")
-    if N == 1 and not args.no_cpu_baseline:
+    if N == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(o, args, R, K)
     print(json.dumps(out))
 
@@ -1701,6 +1753,8 @@ def main():
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     R, K = args.batch, args.k
     assert 1 <= R <= 256
+    if args.dump_outputs and args.mode == "router":
+        raise SystemExit("bench.py: --dump-outputs is not available in --mode router (the callers' results stay in the load generator)")
     if args.mode in ("group", "router"):
         # one process drives all N devices; under a launcher only rank 0 works (the others leave before touching a GPU)
         if rank == 0:
@@ -1745,7 +1799,7 @@ def main():
     coll = HostStagedCollectives(dist, torch) if share_gpu else dist
     preflight = None
     group_ok = True
-    if world > 1 and not args.no_preflight:
+    if world > 1 and args.full and not args.no_preflight:
         # the first thing N > 1 ranks do: prove the sharded step on this wire against the oracle (and pg_group_* over the
         # same devices), on every rank; a failure stops the run before a number exists
         preflight, pf_ok = preflight_ranks(pa, o, torch, dist, coll, rank, world, local_rank, share_gpu, ctl)
@@ -1793,7 +1847,7 @@ def main():
     total_steps = args.warmup + args.steps
     # replica mode: every rank serves different users
     qs = [make_queries(o, s * (1 if shard else world) + (0 if shard else rank), R, args.dim) for s in range(total_steps)]
-    measured_gbs = table.hbm_read_probe(3)           # measured streaming-read ceiling of this GPU's HBM
+    measured_gbs = table.hbm_read_probe(3) if args.full else None     # measured streaming-read ceiling of this GPU's HBM (rooflines)
     table.screen_info()                              # build the shadow outside the timed region
 
     if not shard:
@@ -1820,10 +1874,13 @@ def main():
         predicted0 = sum(c_.stats().recall_predicted for c_ in [ctx] + extra_ctxs)
         rescans0 = sum(c_.stats().recall_rescans for c_ in [ctx] + extra_ctxs)
         pipe, elapsed, scan_ms = run_headline(pa, ctx, table, model, expr, d_qs, args, R, K, sync, extra_ctxs)
-        spot = headline_spot_check(o, pipe, table, w, args.prec, qs[(total_steps - 1) % len(qs)], K) if rank == 0 else None
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, pipeline_outputs(pipe))
+        spot = headline_spot_check(o, pipe, table, w, args.prec, qs[(total_steps - 1) % len(qs)], K) \
+            if rank == 0 and args.full else None
         predicted_batches = sum(c_.stats().recall_predicted for c_ in [ctx] + extra_ctxs) - predicted0
         rescans = sum(c_.stats().recall_rescans for c_ in [ctx] + extra_ctxs) - rescans0
-        if extra_ctxs:
+        if extra_ctxs and args.full:
             # the roofline figure is a per-kernel property: with batches overlapping on two streams a kernel's event-timed
             # duration includes the other stream's work, so the scan-stage time is measured in a short un-overlapped leg
             # (one context, one batch at a time) right after the headline region
@@ -1852,12 +1909,17 @@ def main():
             scan_ms.append(ctx.last_scan_kernel()[0])
         sync()
         elapsed = time.perf_counter() - t0
-        # the last timed step's results: identical on every rank (checksums over the wire), every list in ItemRankScore order
-        with torch.cuda.stream(eng.stream):
-            shard_sanity = {"ranks_agree": ranks_agree(torch, coll, world, last),
-                            "lists_sorted": bool((torch.gather(last[1], 1, last[2].long()).diff(dim=1) <= 0).all().item())}
-        shard_sanity["ok"] = shard_sanity["ranks_agree"] and shard_sanity["lists_sorted"]
-        shard_sanity["exchange"] = dict(getattr(eng, "exchange_stats", None) or {}, unpruned_bytes_per_shard=R * K * 12)
+        if args.dump_outputs and rank == 0:
+            with torch.cuda.stream(eng.stream):
+                dump_outputs(args.dump_outputs, {nm: t_.cpu().numpy() for nm, t_ in zip(("rows", "fused_scores", "order", "page"), last)})
+        shard_sanity = None
+        if args.full:
+            # the last timed step's results: identical on every rank (checksums over the wire), every list in ItemRankScore order
+            with torch.cuda.stream(eng.stream):
+                shard_sanity = {"ranks_agree": ranks_agree(torch, coll, world, last),
+                                "lists_sorted": bool((torch.gather(last[1], 1, last[2].long()).diff(dim=1) <= 0).all().item())}
+            shard_sanity["ok"] = shard_sanity["ranks_agree"] and shard_sanity["lists_sorted"]
+            shard_sanity["exchange"] = dict(getattr(eng, "exchange_stats", None) or {}, unpruned_bytes_per_shard=R * K * 12)
     if os.environ.get("PG_BENCH_STEPTIMES"):          # developer aid
         print("scan ms:", " ".join("%.2f" % x for x in scan_ms), "| rescans", ctx.stats().recall_rescans, file=sys.stderr)
     st = ctx.stats()
@@ -1898,15 +1960,17 @@ def main():
                                    % (world, args.rows * world)) if shard else
                                   ("request-parallel x%d, table replicated per GPU, no data-path collective" % world
                                    if world > 1 else "1 GPU")},
-        "roofline": roofline_block(table, R, args, end - begin, scan_avg_ms, measured_gbs, ctx.last_scan_kernel()[1]),
-        "stages_ms": {"recall_device_ms": st.last_recall_ms, "rank_device_ms": st.last_rank_ms},
+        "roofline": roofline_block(table, R, args, end - begin, scan_avg_ms, measured_gbs, ctx.last_scan_kernel()[1])
+        if args.full else None,
+        # (--full only: there the un-overlapped scan leg has run last where the headline overlaps two batches)
+        "stages_ms": {"recall_device_ms": st.last_recall_ms, "rank_device_ms": st.last_rank_ms} if args.full else None,
         "oracle_spot_check": shard_sanity if shard else spot,
         "preflight": preflight,
         "rank_roofline": {"bound": "mfma", "kernel": "pg::dnn3_ws_kernel" if args.prec == "bf16" else "pg::dnn3_x3_kernel<512, 256>",
                           "achieved": rank_items * FLOPS_PER_ITEM / max(st.last_rank_ms, 1e-9) / 1e9,
                           "peak": MFMA_BF16_PEAK_TFLOPS, "unit": "TFLOP/s",
                           "frac": rank_items * FLOPS_PER_ITEM / max(st.last_rank_ms, 1e-9) / 1e9 / MFMA_BF16_PEAK_TFLOPS}
-        if args.prec != "f32" and st.last_rank_ms > 0 else None,
+        if args.full and args.prec != "f32" and st.last_rank_ms > 0 else None,
     }
 
     if share_gpu:
@@ -1914,7 +1978,8 @@ def main():
         out["dev_mode"] = ("PG_BENCH_SHARE_GPU=1: %d ranks on ONE device, gloo with host-staged exchanges — a correctness run "
                            "of the N > 1 code, not a measurement" % world)
     solo = world == 1
-    if solo and args.latency_reqs > 0:
+    full = args.full
+    if solo and full and args.latency_reqs > 0:
         # p50 single-request latency (R=1), same pipeline, inputs resident, one batch at a time
         lat = []
         lq = [ctx.to_device(make_queries(o, 7000 + i, 1, args.dim)) for i in range(min(args.latency_reqs, 1000))]
@@ -1940,7 +2005,7 @@ def main():
                                                                      "measured_peak", "frac_of_measured", "bytes_per_pass",
                                                                      "ms_per_pass", "traffic_from_profile")}
 
-    if solo and args.prec != "f32" and not args.no_rank_shapes:
+    if solo and full and args.prec != "f32" and not args.no_rank_shapes:
         # the rank stage alone, per hidden shape (bf16) and the benchmark's shape in the headline's precision: the rank roofline proper
         for c_ in [ctx] + list(extra_ctxs):
             c_.synchronize()
@@ -1960,7 +2025,7 @@ def main():
                                                 "note": "HIP events around the stage inside the headline loop, i.e. right behind the scan: the "
                                                         "clock the power cap leaves"}}
 
-    if solo and not args.no_f32_leg:
+    if solo and full and not args.no_f32_leg:
         # The same timed region in the other precision modes, and what separates each matrix-pipe mode from PG_PREC_F32 (the fp32
         # specification: scores within 2e-7 of the oracle's chains).  north_star's tolerance is 1e-5 on float scores against the
         # reference's fp32 path (algorithm/eas/easyrec_response.go:479-483, eas/tf_response.go:55-59): bf16x3 — the headline —
@@ -2003,9 +2068,9 @@ def main():
                 mm.destroy()
         if m32 is not model:
             m32.destroy()
-    if solo and not args.no_batch_sweep:
+    if solo and full and not args.no_batch_sweep:
         out["batch_sweep"] = batch_sweep_leg(pa, o, ctx, table, model, expr, args, K, extra_ctxs, measured_gbs)
-    extras = solo and not args.no_extras
+    extras = solo and full and not args.no_extras
     if extras and args.callers > 0:
         out["concurrent_callers"] = concurrent_callers_leg(pa, o, ctx, table, model, expr, args, K)
     if extras and not args.no_power:
@@ -2081,7 +2146,7 @@ def main():
             c4["roofline"]["traffic_detail"] = det4
             if tb4:
                 c4["roofline"]["traffic_bytes_per_item"] = tb4 / (R * K)
-    if world > 1 and not shard and not args.no_extras:
+    if world > 1 and not shard and full and not args.no_extras:
         # the default N > 1 line carries both §8(e) forms of configs[4] beside the replica headline: the sharded step over
         # RCCL (every rank) and pg_group_* in one process (rank 0, the others wait) — one driver command, both curves
         for c_ in extra_ctxs:
@@ -2102,8 +2167,8 @@ def main():
         cpu_barrier()
     failed = False
     if rank == 0:
-        out["device"] = device_info()
-        if solo and not args.no_cpu_baseline:
+        out["device"] = device_info() if full else None
+        if solo and full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(o, args, R, K)
         else:
             out["cpu_baseline"] = None

@@ -5,7 +5,7 @@ REPO=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$REPO/gpurun_out/ks_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT" -o t -- python3 "$REPO/bench.py" --steps 5 --warmup 2 --no-cpu-baseline --latency-reqs 0 "$@" > "$OUT/log.txt" 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT" -o t -- python3 "$REPO/bench.py" --full --steps 5 --warmup 2 --no-cpu-baseline --latency-reqs 0 "$@" > "$OUT/log.txt" 2>&1
 python3 - "$OUT" <<'PY'
 import sys, glob, csv, os
 for p in glob.glob(os.path.join(sys.argv[1], "**", "*kernel_stats.csv"), recursive=True):

@@ -6,7 +6,7 @@ set -u
 cd "$(dirname "$0")/.."
 mkdir -p gpurun_out/r6_multirank_dev
 export PG_BENCH_SHARE_GPU=1
-COMMON="--rows 3000000 --steps 3 --warmup 1 --calibrate 2 --no-cpu-baseline"
+COMMON="--full --rows 3000000 --steps 3 --warmup 1 --calibrate 2 --no-cpu-baseline"
 for spec in "replica 2" "shard 2" "group 4" "router 2"; do
   set -- $spec
   timeout 900 python bench.py --gpus $2 --mode $1 $COMMON > gpurun_out/r6_multirank_dev/$1_$2.json 2> gpurun_out/r6_multirank_dev/$1_$2.err

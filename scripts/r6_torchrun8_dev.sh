@@ -6,7 +6,7 @@ cd "$(dirname "$0")/.."
 mkdir -p gpurun_out/r6_torchrun8
 export PG_BENCH_SHARE_GPU=1
 timeout 1500 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29533 \
-  bench.py --gpus 8 --steps 3 --warmup 1 --rows 2000000 --calibrate 2 --no-cpu-baseline \
+  bench.py --full --gpus 8 --steps 3 --warmup 1 --rows 2000000 --calibrate 2 --no-cpu-baseline \
   > gpurun_out/r6_torchrun8/replica_8.json 2> gpurun_out/r6_torchrun8/replica_8.err
 echo "rc $?"
 tail -c 1500 gpurun_out/r6_torchrun8/replica_8.json

@@ -1,7 +1,7 @@
 # developer A/B runs of bench.py under different recall policies (environment switches of recall.hip)
 run() { # label, batch, env...
   label=$1; batch=$2; shift 2
-  env "$@" python bench.py --steps 10 --warmup 2 --batch $batch --no-cpu-baseline --latency-reqs 0 2>/dev/null | python -c "
+  env "$@" python bench.py --full --steps 10 --warmup 2 --batch $batch --no-cpu-baseline --latency-reqs 0 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -1,7 +1,8 @@
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
-OUT=$GRAFT_REPO_ROOT/gpurun_out/lat1
+OUT=${OUT:-$(mktemp -d)}/lat1
 mkdir -p $OUT
-rocprofv3 --kernel-trace --output-format csv -d $OUT -o t -- python3 $GRAFT_REPO_ROOT/bench.py --steps 4 --warmup 2 --no-cpu-baseline --latency-reqs 40 --no-extras --no-rank-shapes --contexts 1 --callers 0 --no-live-traffic > $OUT/log.txt 2>&1
+rocprofv3 --kernel-trace --output-format csv -d $OUT -o t -- python3 "$REPO/bench.py" --full --steps 4 --warmup 2 --no-cpu-baseline --latency-reqs 40 --no-extras --no-rank-shapes --contexts 1 --callers 0 --no-live-traffic > $OUT/log.txt 2>&1
 python3 - $OUT <<'PY'
 import sys, csv, glob, os
 rows=[]

@@ -112,3 +112,45 @@ def test_power_readings_parse_rocm_smi_text():
     assert bench.parse_smi(idle) == {"package_w": 247.0, "sclk_mhz": 95.0, "cap_w": 1400.0}
     assert bench.parse_smi(txt.replace("GPU[0]\t\t: Max Graphics Package Power (W): 1400.0\n", ""))["cap_w"] is None
     assert bench.parse_smi("rocm-smi: command not found") is None and bench.parse_smi("") is None
+
+
+def test_router_refuses_dump_outputs(tmp_path):
+    """--mode router has no outputs to hand back (the callers' results stay in the load generator): --dump-outputs is refused
+    before anything touches a device, and nothing is written."""
+    d = tmp_path / "dump"
+    r = _run(["--gpus", "1", "--mode", "router", "--steps", "1", "--dump-outputs", str(d)])
+    assert r.returncode != 0 and "--dump-outputs is not available in --mode router" in r.stderr
+    assert '"n_gpus"' not in r.stdout and not d.exists()
+
+
+def test_dump_outputs_writes_exact_floats_within_the_cap(tmp_path):
+    """--dump-outputs: integer outputs become float64 (exact), fp32 / fp64 keep their width; above 64 MB in all, the same fixed
+    sample of requests of every array is written, with the sampled indices."""
+    sys.path.insert(0, ROOT)
+    import bench
+    import numpy as np
+    R, K = 256, 5000
+    rng = np.random.default_rng(1)
+    arrays = {"rows": rng.integers(0, 100_000_000, (R, K)).astype(np.uint64),
+              "recall_scores": rng.random((R, K), dtype=np.float32), "rank_scores": rng.random((R, K), dtype=np.float32),
+              "fused_scores": rng.random((R, K)), "order": np.tile(np.arange(K, dtype=np.uint32), (R, 1))}
+    bench.dump_outputs(str(tmp_path / "a"), arrays)
+    got = {n: np.load(str(tmp_path / "a" / (n + ".npy"))) for n in arrays}
+    assert got["rows"].dtype == np.float64 and np.array_equal(got["rows"].astype(np.uint64), arrays["rows"])
+    assert got["order"].dtype == np.float64 and np.array_equal(got["order"], arrays["order"])
+    assert got["recall_scores"].dtype == np.float32 and np.array_equal(got["recall_scores"], arrays["recall_scores"])
+    assert got["fused_scores"].dtype == np.float64 and np.array_equal(got["fused_scores"], arrays["fused_scores"])
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    big = {n: np.repeat(a, 3, axis=1) for n, a in arrays.items()}
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), big)
+    files = sorted(os.listdir(str(tmp_path / "b")))
+    assert "requests_sampled.npy" in files
+    assert sum(os.path.getsize(str(tmp_path / "b" / f)) for f in files) <= 64 << 20
+    idx = np.load(str(tmp_path / "b" / "requests_sampled.npy")).astype(np.int64)
+    assert len(idx) > 0 and len(set(idx.tolist())) == len(idx)
+    for n, a in big.items():                              # every array keeps the same requests
+        got_n = np.load(str(tmp_path / "b" / (n + ".npy")))
+        assert got_n.shape == a[idx].shape and np.array_equal(got_n, a[idx].astype(got_n.dtype))
+    for f in files:
+        assert np.array_equal(np.load(str(tmp_path / "b" / f)), np.load(str(tmp_path / "c" / f)))
