@@ -70,7 +70,7 @@ int pg_shutdown(pg_ctx* ctx);
 int pg_synchronize(pg_ctx* ctx);
 /* Developer / test knobs of one context (defaults come from PG_* environment variables read once, in pg_init):
  * "no_pilot", "recall_exact", "screen_min", "pilot_fraction", "chunk_growth", "seed_rows", "pilot_growth",
- * "pilot_sigmas", "debug_scan", "rank_no_ws", "sort_lds", and for the 4-bit screen of batches of <= 4 queries
+ * "pilot_sigmas", "debug_scan", "rank_no_ws", and for the 4-bit screen of batches of <= 4 queries
  * (csrc/recall_i4.hip) "no_screen_i4", "i4_min_rows" (default 2^22), "i4_max_lambda", and for the threshold refinement inside the pilot plan's
  * full pass "no_refine", "refine_min_rows" (default 2^24), and for the threshold model that replaces the pilot sample
  * once a table has seen >= 1024 queries of one K (plan 0) "no_predict", "predict_sigmas" (default 4.5),

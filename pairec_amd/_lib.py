@@ -9,11 +9,7 @@ import ctypes as C
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# PG_LIB_VARIANT=dev selects libpairec_gpu_dev.so: what `make WS_EXTRA=… / SCAN_EXTRA=… / MLP_EXTRA=…` builds (profile marks,
-# ablations) — the product library is never one of those (pairec_amd/csrc/Makefile)
-LIB_PATH = os.path.join(_HERE, "libpairec_gpu_dev.so" if os.environ.get("PG_LIB_VARIANT") == "dev" else "libpairec_gpu.so")
-if os.environ.get("PG_LIB_PATH"):                  # developer A/B runs: an explicitly named build
-    LIB_PATH = os.environ["PG_LIB_PATH"]
+LIB_PATH = os.path.join(_HERE, "libpairec_gpu.so")
 
 # every symbol include/pairec_gpu.h declares (tests/test_abi.py checks the two stay in sync)
 EXPORTS = [

@@ -17,8 +17,6 @@ static void knobs_from_env(Knobs* k) {
     k->seed_rows = (uint32_t)num("PG_SEED_ROWS", 8192);
     k->pilot_growth = num("PG_PILOT_GROWTH", 0.0);
     k->debug_scan = flag("PG_DEBUG_SCAN");
-    k->screen_bf16 = flag("PG_SCREEN_BF16");
-    k->screen_i8 = flag("PG_SCREEN_I8");
     k->no_refine = flag("PG_NO_REFINE");
     k->refine_min_rows = (uint32_t)num("PG_REFINE_MIN_ROWS", (double)(1u << 24));
     k->no_screen_i4 = flag("PG_NO_SCREEN_I4");
@@ -33,9 +31,6 @@ static void knobs_from_env(Knobs* k) {
     k->rank_sort_max = (uint32_t)num("PG_RANK_SORT_MAX", 32);
     k->rank_sort_work = num("PG_RANK_SORT_WORK", 7e7);
     k->split_sort_max = (uint32_t)num("PG_SPLIT_SORT_MAX", 96);
-    k->sort_lds = flag("PG_SORT_LDS");
-    k->fm2t_irs = flag("PG_FM2T_IRS");
-    k->dpp_valu = flag("PG_DPP_VALU");
     k->max_rec_scale = (uint32_t)num("PG_MAX_REC_SCALE", 16);
     k->no_r2 = flag("PG_NO_R2");
     k->r2_min_factor = num("PG_R2_MIN_FACTOR", 3.0);
@@ -179,10 +174,7 @@ int pg_set_option(pg_ctx* ctx, const char* name, const char* value) {
     else if (n == "rank_sort_max") k.rank_sort_max = (uint32_t)v;
     else if (n == "split_sort_max") k.split_sort_max = (uint32_t)v;
     else if (n == "rank_sort_work") k.rank_sort_work = v;
-    else if (n == "sort_lds") k.sort_lds = b;
     else if (n == "stage_timers") ctx->timers_off = !b;      // (not a Knobs member: a coalescer's sibling context copies the knobs, its batches decide for themselves)
-    else if (n == "fm2t_irs") k.fm2t_irs = b;
-    else if (n == "dpp_valu") k.dpp_valu = b;
     else if (n == "no_r2") k.no_r2 = b;
     else if (n == "r2_min_factor") k.r2_min_factor = v;
     else if (n == "max_rec_scale") k.max_rec_scale = v >= 1 ? (uint32_t)v : 1u;

@@ -63,8 +63,6 @@ struct Knobs {
     uint32_t seed_rows = 8192;     // PG_SEED_ROWS: exact seed of the pilot sample
     double pilot_growth = 0.0;     // PG_PILOT_GROWTH: > 0 = geometric chunks over the sample instead of seed + one launch
     bool debug_scan = false;       // PG_DEBUG_SCAN: print per-launch times and suspect counts
-    bool screen_bf16 = false;      // PG_SCREEN_BF16: bf16 shadow for dim-128 tables too
-    bool screen_i8 = false;        // PG_SCREEN_I8: int8 shadow even for heavy-tailed tables
     bool no_refine = false;        // PG_NO_REFINE: the pilot plan's full pass keeps the sample's threshold throughout
     uint32_t refine_min_rows = 1u << 24;   // PG_REFINE_MIN_ROWS: smallest table whose full pass is split for the refinement
     bool no_screen_i4 = false;     // PG_NO_SCREEN_I4: small batches stay on the int8 screen
@@ -79,9 +77,6 @@ struct Knobs {
     uint32_t split_sort_max = 96;  // PG_SPLIT_SORT_MAX: up to this many lists (of 1025 … 8192 items, ~450 K items in all) per call are sorted run by run over the chip (split_sort.hpp; 0 = never)
     uint32_t rank_sort_max = 32;   // PG_RANK_SORT_MAX: up to this many lists per call are sorted by counting ranks (0 = never) ...
     double rank_sort_work = 7e7;   // PG_RANK_SORT_WORK: ... while lists x items^2 stays under this (lists of <= 8192 items; the top-K's final order, one compare per key, takes 1.5 x)
-    bool sort_lds = false;         // PG_SORT_LDS: LDS bitonic sort instead of the register-resident one
-    bool dpp_valu = false;         // PG_DPP_VALU: the DPP kernel matrix on the fp64 vector pipe (round-4 kernel) instead of the fp64 matrix pipe (A/B; same bits)
-    bool fm2t_irs = false;         // PG_FM2T_IRS: cfg 4's item-record rank on the producer / consumer kernel (rank_ir.hip) instead of rank_is.hip (A/B)
     bool no_r2 = false;            // PG_NO_R2: never refine the int8 screen's suspects on the residual shadow
     double r2_min_factor = 3.0;    // PG_R2_MIN_FACTOR: ... refine once a table's passes average more than this many suspects per answer (x K)
     uint32_t max_rec_scale = 16;   // PG_MAX_REC_SCALE: the 256-query pass's hit-record areas grow up to this many times their default size with a table

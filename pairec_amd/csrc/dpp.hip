@@ -20,9 +20,6 @@
 #include <type_traits>
 #include <vector>
 
-#ifndef DPP_ABL
-#define DPP_ABL 0
-#endif
 namespace pg {
 
 // Feature rows, one thread per candidate of one request (blockIdx.y = request), following KernelMatrix
@@ -147,7 +144,7 @@ __global__ __launch_bounds__(64) void dpp_prepare_table_kernel(DppPrep a) {
 // XCD has its own L2: with the tile pairs of a request dealt over the grid's x and the requests over z, the nt (nt + 1) / 2 tiles
 // that share a request's F rows ran on all eight XCDs, and each fetched its two 64-row panels from the fabric again —
 // FETCH_SIZE 1.75 GB per 256-request batch (profiles/r4_dpp_v2_pmc_summary.txt) for 132 MB of F, and 0.29 ms of the kernel's
-// 0.35 with the arithmetic removed (round 5 ablation, DPP_ABL).  Here XCD x serves requests x, x + 8, …, all tile pairs of one
+// 0.35 with the arithmetic removed (round 5 ablation).  Here XCD x serves requests x, x + 8, …, all tile pairs of one
 // request on consecutive workgroups of that XCD: a request's F (516 KB at 500 x 129) is fetched once and stays in the 4 MB L2
 // while its tiles run.  (Placement is a speed assumption only: any other assignment of workgroups to XCDs computes the same.)
 // Requests beyond the last full round of eight (and a batch of fewer than eight — one request of pg_dpp) are not left to one XCD
@@ -175,163 +172,21 @@ __host__ inline uint32_t dpp_km_blocks(uint32_t nt, uint32_t R) {
 }
 
 constexpr int kDppTile = 64, kDppKc = 16;
-// One WAVE per 64 x 64 tile of S = F F^T, upper triangle only (blockIdx.x walks the tile pairs ti <= tj): lane (ty, tx)
-// of an 8 x 8 grid owns the 8 x 8 patch rows {2ty, 2ty + 1} + 16a, columns {2tx, 2tx + 1} + 16b — 64 accumulators per
-// lane, and an operand pair is ONE 16-B LDS read: 8 reads per 64 fma (the round-2 kernel's 4 x 4 patches needed 8
-// reads per 16 fma and were LDS-bound at 28 % of the fp64 rate).  The panels are staged with 16 lanes per row (128
-// contiguous bytes per row and instruction).  Every element is its own k-ascending fma chain, as the specification
-// wants it; S is symmetric bit for bit (a product commutes), L is not — L_ij = (r_i S_ij) r_j and L_ji = (r_j S_ij) r_i
-// are both formed from the one S_ij.
-// Round 4 (profiles/r4_dpp_pmc_summary.txt, scripts/micro/fma64_rate.hip).  What the chip gives: v_fmac_f64 from 64
-// independent accumulators runs at 4.7 cycles per wave-instruction and SIMD with two waves per SIMD (6.2 with one) at the
-// 1.8 GHz it sustains under that load — 25 T fma/s, not the nominal 39: this kernel's 4.66 G fma cannot take less than
-// 0.19 ms.  Where it stood: one wave per SIMD (496 registers), every chunk's panel loads awaited at the top of the chunk,
-// VALU 38 % busy — 521 us.  Steps: next chunk's loads requested before the fma block (456 us); then TWO waves per SIMD —
-// possible once the epilogue's passes were compile-time code (with `mirror` / `half` as loop variables the compiler kept
-// the 64 accumulators in scratch and formed all 256 products in each of the four passes: 241 spilled dwords under a
-// 256-register budget) and the panel loads moved back inside the chunk (their 64 registers are dead during the fma
-// block; the other wave covers the wait): 365 us; panel loads without per-load arithmetic and a 17-wide last chunk
-// instead of a ninth staging round for one column: 356 us = VALU 50 % busy at 2.1 GHz, 0.53 of what the chip gives.
-// Tried and dropped: 8-column chunks double-buffered in LDS (700 us: a row's 64-B segments fetch every 128-B line twice);
-// the operands of step k + 1 read before the fma of step k (no gain).
-__global__ __launch_bounds__(64, 2) void dpp_kernel_matrix_kernel(const double* __restrict__ F,
-                                                                  uint32_t n, uint32_t d1, uint32_t nt, uint32_t R, uint32_t ld, double* __restrict__ S) {
-    typedef double f64x2 __attribute__((ext_vector_type(2)));
-    // the two panels [k][row], rows padded to a 16-B multiple (+ 1 column: the 17-wide tail); ONE array: the output staging
-    // below runs over both
-    __shared__ __attribute__((aligned(16))) double panels[2][kDppKc + 1][kDppTile + 2];
-    auto& sa = panels[0];
-    auto& sb = panels[1];
-    // (request, tile pair) of this workgroup: see dpp_tile_of_block
-    uint32_t q, p;
-    if (!dpp_tile_of_block(nt, R, &q, &p)) return;
-    // tile pair p → (ti, tj), ti <= tj: row ti holds nt - ti pairs
-    uint32_t ti = 0;
-    while (p >= nt - ti) {
-        p -= nt - ti;
-        ++ti;
-    }
-    const uint32_t tj = ti + p;
-    const uint32_t i0 = ti * kDppTile, j0 = tj * kDppTile;
-    const uint32_t lane = threadIdx.x, tx = lane & 7, ty = lane >> 3;
-    const uint32_t kk = lane & 15, rr = lane >> 4;             // staging: column kk of rows rr + 4 it
-    const double* Fq = F + (size_t)q * n * d1;
-    double acc[8][8];                                          // [2a + u][2b + v]: row 2ty + u + 16a, column 2tx + v + 16b
-#pragma unroll
-    for (int a = 0; a < 8; ++a)
-#pragma unroll
-        for (int b = 0; b < 8; ++b) acc[a][b] = 0.0;
-    double va[16], vb[16];
-    // Panel loads with NO per-load arithmetic: a lane's byte offset (row rr, column k0 + kk) is one register advanced per
-    // chunk, the sixteen row groups are wave-uniform bases (scalar registers).  Rows past n and columns past d1 are read
-    // — F carries 64 rows of slack behind the last request (dpp_run_locked) — but only feed accumulators that are never
-    // written / k-steps that are never taken.  (Clamped addresses cost 130 VALU instructions per chunk beside its 1 024 fma.)
-    const char* const Fb = reinterpret_cast<const char*>(Fq);
-    const uint32_t rowb = d1 * 8u;
-    uint32_t voff = rr * rowb + kk * 8u;
-    auto load_panels = [&]() {
-#pragma unroll
-        for (int it = 0; it < 16; ++it) {
-            const char* const ba = Fb + (size_t)(i0 + (uint32_t)it * 4) * rowb;      // (uniform)
-            const char* const bb = Fb + (size_t)(j0 + (uint32_t)it * 4) * rowb;
-            va[it] = *reinterpret_cast<const double*>(ba + voff);
-            vb[it] = *reinterpret_cast<const double*>(bb + voff);
-        }
-        voff += kDppKc * 8u;
-    };
-    // a width of 16 m + 1 (the embedding's 128 columns + the constant one) ends with a chunk of 17 instead of a ninth
-    // staging round for a single column
-    const bool tail17 = d1 > (uint32_t)kDppKc && d1 % kDppKc == 1;
-    for (uint32_t k0 = 0; k0 < d1; k0 += kDppKc) {
-        uint32_t kc = d1 - k0 < (uint32_t)kDppKc ? d1 - k0 : (uint32_t)kDppKc;
-        const bool last17 = tail17 && k0 + kDppKc + 1 == d1;
-        load_panels();
-        double xa = 0.0, xb = 0.0;
-        if (last17) {                                          // column k0 + 16 of rows `lane` of both panels
-            xa = *reinterpret_cast<const double*>(Fb + (size_t)(i0 + lane) * rowb + (size_t)(k0 + kDppKc) * 8u);
-            xb = *reinterpret_cast<const double*>(Fb + (size_t)(j0 + lane) * rowb + (size_t)(k0 + kDppKc) * 8u);
-        }
-        __syncthreads();                                       // the previous step's readers are done
-#pragma unroll
-        for (int it = 0; it < 16; ++it) {
-            sa[kk][it * 4 + rr] = va[it];
-            sb[kk][it * 4 + rr] = vb[it];
-        }
-        if (last17) {
-            sa[kDppKc][lane] = xa;
-            sb[kDppKc][lane] = xb;
-            kc = kDppKc + 1;
-        }
-        __syncthreads();
-        for (uint32_t k = 0; k < kc; ++k) {
-            f64x2 av[4], bv[4];
-#pragma unroll
-            for (int a = 0; a < 4; ++a) av[a] = *reinterpret_cast<const f64x2*>(&sa[k][2 * ty + 16 * a]);
-#pragma unroll
-            for (int b = 0; b < 4; ++b) bv[b] = *reinterpret_cast<const f64x2*>(&sb[k][2 * tx + 16 * b]);
-#pragma unroll
-            for (int a = 0; a < 4; ++a)
-#pragma unroll
-                for (int b = 0; b < 4; ++b) {
-                    acc[2 * a][2 * b] = fma(av[a].x, bv[b].x, acc[2 * a][2 * b]);
-                    acc[2 * a][2 * b + 1] = fma(av[a].x, bv[b].y, acc[2 * a][2 * b + 1]);
-                    acc[2 * a + 1][2 * b] = fma(av[a].y, bv[b].x, acc[2 * a + 1][2 * b]);
-                    acc[2 * a + 1][2 * b + 1] = fma(av[a].y, bv[b].y, acc[2 * a + 1][2 * b + 1]);
-                }
-        }
-        if (last17) break;
-    }
-    // The S tile and (off the diagonal) its mirror — its transpose; round 5: the r-scaling moved to the greedy kernels — written as whole 512-B rows: the patches go through LDS — half a tile
-    // (32 rows) at a time, in the panels' space — so that a store instruction covers one contiguous row of 64 doubles
-    // (patch-wise stores are 16-B runs scattered over eight rows: 512 MB of them per 256-request batch)
-    double* const stage = &panels[0][0][0];                     // 32 x 65 doubles fit the two panels (2 x 17 x 66)
-    static_assert(32 * 65 <= 2 * (kDppKc + 1) * (kDppTile + 2), "the output staging aliases the panels");
-    // (mirror and half as compile-time values: with runtime ones the compiler keeps the accumulators in scratch and forms
-    // every product in every pass)
-    auto pass = [&](auto mirror_c, auto half_c) {
-        constexpr int mirror = decltype(mirror_c)::value, half = decltype(half_c)::value;
-        __syncthreads();                                    // the panels' / the previous half's readers are done
-        // this lane's elements whose OUTPUT row falls into rows [32 half, 32 half + 32) of the (mirrored) tile
-#pragma unroll
-        for (int a = 0; a < 8; ++a)
-#pragma unroll
-            for (int b = 0; b < 8; ++b) {
-                const int row_t = 2 * (int)ty + (a & 1) + 16 * (a >> 1);        // row of the tile
-                const int col_t = 2 * (int)tx + (b & 1) + 16 * (b >> 1);
-                const int orow = mirror ? col_t : row_t, ocol = mirror ? row_t : col_t;
-                if (((mirror ? b : a) >> 2) != half) continue;                  // (orow >> 5: 2 t + (x & 1) < 16)
-                stage[(orow & 31) * 65 + ocol] = acc[a][b];
-            }
-        __syncthreads();
-        const uint32_t r0 = (mirror ? j0 : i0) + 32 * half, c0 = mirror ? i0 : j0;
-        const uint32_t rows = r0 < n ? (n - r0 < 32u ? n - r0 : 32u) : 0u;      // (uniform; the column test once per pass)
-        double* const rowp = S + ((size_t)q * n + r0) * ld + c0;                 // (uniform: stores with a scalar base)
-        if (c0 + lane < n)
-            for (uint32_t rr2 = 0; rr2 < rows; ++rr2)
-                __builtin_nontemporal_store(stage[rr2 * 65 + lane], rowp + (size_t)rr2 * ld + lane);   // (streams out: see the matrix-pipe kernel)
-    };
-    pass(std::integral_constant<int, 0>(), std::integral_constant<int, 0>());
-    pass(std::integral_constant<int, 0>(), std::integral_constant<int, 1>());
-    if (ti != tj) {
-        pass(std::integral_constant<int, 1>(), std::integral_constant<int, 0>());
-        pass(std::integral_constant<int, 1>(), std::integral_constant<int, 1>());
-    }
-}
-
-// Round 5: the same tile on the fp64 matrix pipe.  v_mfma_f64_16x16x4_f64 accumulates D = C + a_0 b_0 + … + a_3 b_3 as the
+// One WAVE per 64 x 64 tile of S = F F^T, upper triangle only (dpp_tile_of_block), on the fp64 matrix pipe.  (The round-4 kernel of
+// the same tile on the fp64 vector pipe, 0.356 ms per 256 x 500 x 129 batch, was retired; it is in git history.)  v_mfma_f64_16x16x4_f64 accumulates D = C + a_0 b_0 + … + a_3 b_3 as the
 // k-ascending fma chain the specification is (scripts/micro/mfma_f64.hip, profiles/r5_mfma_f64_microbench.txt: 256 of 256
 // outputs over K = 128 with exponents spread over 2^±20 bit-equal to the chain; 125 / 46 / 65 of 256 to the other candidate
-// orders), so S_ij keeps its bits (tests/test_gpu_parity.py::test_dpp_kernel_matrix_bits_on_both_pipes: this kernel, the vector
-// kernel and the oracle agree bit for bit) — and an instruction retires 1 024 fma for TWO 8-byte operand reads per lane where the
+// orders), so S_ij keeps its bits (tests/test_gpu_parity.py::test_dpp_kernel_matrix_bits_on_the_matrix_pipe: this kernel and
+// the oracle agree bit for bit) — and an instruction retires 1 024 fma for TWO 8-byte operand reads per lane where the
 // vector form needs 8 reads of 16 B per 64.  The instruction takes 64 cycles (16 fma per clock and SIMD = 38 T fma/s measured:
 // the chip's fp64 matrix peak IS its vector peak — the instructions execute on the SIMD's fp64 vector units), 33 k-steps x 16
 // blocks per tile = 0.136 ms of pipe time per 256 x 500 x 129 batch.  A wave owns the 64 x 64 tile as 4 x 4 blocks of 16 x 16:
-// block (a, b), register g, lane l = row 16a + (l >> 4) + 4g, column 16b + (l & 15).  The panels are staged as before, the next
+// block (a, b), register g, lane l = row 16a + (l >> 4) + 4g, column 16b + (l & 15).  The panels are staged through LDS, the next
 // chunk's requested before this chunk's instructions; a width that is not a multiple of four ends with zero operands written
 // into the panel (fma(0, 0, acc) = acc: the chain starts at +0 and cannot reach -0).  Epilogue: the tile of S and its mirror (its
 // transpose: S is symmetric bit for bit) as whole rows through LDS; L_ij = (r_i S_ij) r_j is formed by the greedy kernels for the
 // diagonal and the rows they pick — a fifth of the matrix — which took 1 024 multiplications per tile out of this epilogue.
-// Measured (profiles/r5_dpp_mfma_summary.txt): 0.343 ms as first built — exactly the vector kernel's time: neither pipe was the
+// Measured (profiles/r5_dpp_mfma_summary.txt): 0.343 ms as first built — exactly the vector-pipe kernel's time: neither pipe was the
 // bound.  FETCH_SIZE 1.75 GB for 132 MB of F: dpp_tile_of_block (one request's tiles on one XCD) → 135 MB, 0.304 ms; L's 512 MB as
 // non-temporal stores: 0.277 ms (matrix pipe 49 % busy); S instead of L, the stores' tests hoisted: 0.262 ms; panels staged with 16-byte
 // loads (eight lanes per row, half the load instructions): −5 % (0.258 against 0.274 on one box).  What is left is the pairing of two waves per SIMD on one fp64 unit: with
@@ -340,25 +195,13 @@ __global__ __launch_bounds__(64, 2) void dpp_kernel_matrix_kernel(const double* 
 // s_setprio does not change that, and one wave per SIMD (0.37 ms) leaves every load latency exposed.  Not done: a single wave
 // per SIMD that issues its LDS / global traffic between its own matrix instructions (hand-placed, as csrc/recall.hip does).
 __global__ __launch_bounds__(64, 2) void dpp_kernel_matrix_mfma_kernel(const double* __restrict__ F,
-                                                                       uint32_t n, uint32_t d1, uint32_t nt, uint32_t R, uint32_t ld, double* __restrict__ S
-#ifdef DPP_PROFILE
-                                                                       , unsigned long long* prof
-#endif
-                                                                       ) {
+                                                                       uint32_t n, uint32_t d1, uint32_t nt, uint32_t R, uint32_t ld, double* __restrict__ S) {
     typedef double f64x4 __attribute__((ext_vector_type(4)));
     __shared__ __attribute__((aligned(16))) double panels[2][kDppKc + 1][kDppTile + 2];
     auto& sa = panels[0];
     auto& sb = panels[1];
     uint32_t q, p;
     if (!dpp_tile_of_block(nt, R, &q, &p)) return;
-#ifdef DPP_PROFILE
-    // phases: 0 prologue (first panels requested), 1 waiting for a chunk's panels + their LDS writes, 2 requesting the next panels,
-    // 3 the chunk's matrix instructions (operand reads included), 4 epilogue
-    uint64_t ph[5] = {0, 0, 0, 0, 0}, tp = __builtin_readcyclecounter();
-#define DPP_MARK(i) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); const uint64_t tn = __builtin_readcyclecounter(); ph[i] += tn - tp; tp = tn; }
-#else
-#define DPP_MARK(i)
-#endif
     uint32_t ti = 0;
     while (p >= nt - ti) {
         p -= nt - ti;
@@ -387,7 +230,9 @@ __global__ __launch_bounds__(64, 2) void dpp_kernel_matrix_mfma_kernel(const dou
     const uint32_t rowb = d1 * 8u;
     const uint32_t kq = lane & 7, r8 = lane >> 3;
     uint32_t voff = r8 * rowb + kq * 16u;
-    auto load_panels = [&]() {                                  // (unclamped: see dpp_kernel_matrix_kernel)
+    // Panel loads unclamped: rows past n and columns past d1 are read — F carries 64 rows of slack behind the last request
+    // (dpp_run_locked) — but only feed accumulators that are never written / k-steps that are never taken.
+    auto load_panels = [&]() {
 #pragma unroll
         for (int it = 0; it < 8; ++it) {
             va[it] = *reinterpret_cast<const f64x2*>(Fb + (size_t)(i0 + (uint32_t)it * 8) * rowb + voff);
@@ -416,7 +261,6 @@ __global__ __launch_bounds__(64, 2) void dpp_kernel_matrix_mfma_kernel(const dou
                 asm volatile("v_mfma_f64_16x16x4_f64 %0, %1, %2, %0" : "+v"(acc[a][b]) : "v"(av[a]), "v"(bv[b]));
     };
     load_panels();
-    DPP_MARK(0)
     for (uint32_t k0 = 0; k0 < d1; k0 += kDppKc) {              // (the 129th column is a ninth chunk of one: its staging hides like the others')
         const uint32_t kc = d1 - k0 < (uint32_t)kDppKc ? d1 - k0 : (uint32_t)kDppKc;
 #pragma unroll
@@ -430,16 +274,10 @@ __global__ __launch_bounds__(64, 2) void dpp_kernel_matrix_mfma_kernel(const dou
             sa[z][lane] = 0.0;
             sb[z][lane] = 0.0;
         }
-        DPP_MARK(1)
         if (k0 + kDppKc < d1) load_panels();                    // the next chunk's, under this chunk's instructions
-        DPP_MARK(2)
-#if DPP_ABL == 2
-        if (d1 == 12345u)
-#endif
 #pragma unroll 1
         for (uint32_t s4 = 0; 4 * s4 < kc; ++s4) step(4 * s4 + rr);   // (one code path: the accumulators stay where they are)
         asm volatile("" ::: "memory");
-        DPP_MARK(3)
     }
     asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15" : DPP_ACCS);   // a 16-pass instruction's results, before anything else reads them
 #undef DPP_ACCS
@@ -462,11 +300,7 @@ __global__ __launch_bounds__(64, 2) void dpp_kernel_matrix_mfma_kernel(const dou
         const uint32_t r0 = (mirror ? j0 : i0) + 32 * half, c0 = mirror ? i0 : j0;
         const uint32_t rows = r0 < n ? (n - r0 < 32u ? n - r0 : 32u) : 0u;      // (uniform; the column test once per pass)
         double* const rowp = S + ((size_t)q * n + r0) * ld + c0;                 // (uniform: stores with a scalar base)
-#if DPP_ABL == 1
-        if (c0 + lane < n && stage[lane] == 1.2345e300)
-#else
         if (c0 + lane < n)
-#endif
             for (uint32_t rr2 = 0; rr2 < rows; ++rr2)
                 // (non-temporal: 2 MB per request stream out once; as ordinary stores they pass through the L2 the tiles' F rows live in)
                 __builtin_nontemporal_store(stage[rr2 * 65 + lane], rowp + (size_t)rr2 * ld + lane);
@@ -477,12 +311,6 @@ __global__ __launch_bounds__(64, 2) void dpp_kernel_matrix_mfma_kernel(const dou
         pass(std::integral_constant<int, 1>(), std::integral_constant<int, 0>());
         pass(std::integral_constant<int, 1>(), std::integral_constant<int, 1>());
     }
-#ifdef DPP_PROFILE
-    DPP_MARK(4)
-    if (lane == 0)
-        for (int i = 0; i < 5; ++i) atomicAdd(&prof[i], (unsigned long long)ph[i]);
-#endif
-#undef DPP_MARK
 }
 
 // L_ij = (r_i S_ij) r_j for the whole matrix (pg_dpp_kernel_matrix_dev; the greedy kernels form the elements they read themselves)
@@ -695,11 +523,6 @@ __global__ __launch_bounds__(64) void dpp_greedy_wave_kernel(const double* __res
         }
     };
     uint32_t done = 0;
-#ifdef DPP_PROFILE
-    uint64_t prof_wait = 0, prof_picks = 0, prof_arg = 0, prof_upd = 0;
-    const uint64_t prof_t0 = __builtin_readcyclecounter();
-    uint64_t prof_mark = prof_t0;
-#endif
     uint32_t n_calls, rem;
     if (topn_total <= window) { n_calls = 1; rem = 0; }
     else { n_calls = topn_total / window; rem = topn_total % window; }
@@ -751,14 +574,6 @@ __global__ __launch_bounds__(64) void dpp_greedy_wave_kernel(const double* __res
 #pragma unroll
             for (int s = 1; s < EPL; ++s) rsel = (j >> 6) == (uint32_t)s ? rn[s] : rsel;
             const double rj = __shfl(rsel, (int)(j & 63u), 64);
-#ifdef DPP_PROFILE
-            {                                                    // cycles from the row's requests to its arrival
-                const uint64_t t0 = __builtin_readcyclecounter();
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                prof_wait += __builtin_readcyclecounter() - t0;
-                ++prof_picks;
-            }
-#endif
 #pragma unroll
             for (int s = 0; s < EPL; ++s) {
                 const uint32_t n = (uint32_t)s * 64u + lane;
@@ -781,16 +596,7 @@ __global__ __launch_bounds__(64) void dpp_greedy_wave_kernel(const double* __res
                 if ((uint32_t)s * 64u + lane == j) d2[s] = nan;
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // one wave: orders the LDS column copy for the later picks
-#ifdef DPP_PROFILE
-            const uint64_t ta0 = __builtin_readcyclecounter();
-            prof_upd += ta0 - prof_mark;
-#endif
             argmax(j, dj);
-#ifdef DPP_PROFILE
-            asm volatile("" : "+v"(dj));
-            prof_mark = __builtin_readcyclecounter();
-            prof_arg += prof_mark - ta0;
-#endif
             if (lane == 0) out[done + ny] = j;
 #pragma unroll
             for (int s = 0; s < EPL; ++s) sel[s] = sel[s] || ((uint32_t)s * 64u + lane == j);
@@ -815,12 +621,6 @@ __global__ __launch_bounds__(64) void dpp_greedy_wave_kernel(const double* __res
         done += ny;
     }
     if (lane == 0) out_count[req] = done;
-#ifdef DPP_PROFILE
-    if (lane == 0 && req == 3)
-        printf("dpp greedy (request 3): %llu picks, %llu ticks in all, %llu waiting for the picked rows, %llu in the argmax, %llu from one argmax to the next (row wait included)\n",
-               (unsigned long long)prof_picks, (unsigned long long)(__builtin_readcyclecounter() - prof_t0), (unsigned long long)prof_wait,
-               (unsigned long long)prof_arg, (unsigned long long)prof_upd);
-#endif
 }
 
 // DPP for R independent requests of n candidates each, device-resident: d_emb32 [R][n][d] fp32 (NULL on the
@@ -860,26 +660,7 @@ int dpp_run_locked(pg_ctx* ctx, const float* d_emb32, const double* d_hook, cons
     else dpp_prepare_kernel<<<dim3((n + 63) / 64, R), 64, 0, ctx->stream>>>(a);
     const uint32_t nt = (n + kDppTile - 1) / kDppTile;
     const uint32_t km_blocks = dpp_km_blocks(nt, R);                            // (dpp_tile_of_block)
-    if (ctx->knobs.dpp_valu) dpp_kernel_matrix_kernel<<<km_blocks, 64, 0, ctx->stream>>>(F, n, d1, nt, R, ld, L);
-#ifdef DPP_PROFILE
-    else {
-        static unsigned long long* prof = nullptr;
-        if (!prof) hipMalloc(&prof, 5 * 8);
-        hipMemsetAsync(prof, 0, 5 * 8, ctx->stream);
-        dpp_kernel_matrix_mfma_kernel<<<km_blocks, 64, 0, ctx->stream>>>(F, n, d1, nt, R, ld, L, prof);
-        unsigned long long h[5];
-        hipStreamSynchronize(ctx->stream);
-        hipMemcpy(h, prof, sizeof h, hipMemcpyDeviceToHost);
-        static int calls = 0;
-        if (++calls == 5) {
-            const double tiles = (double)(nt * (nt + 1) / 2) * R;
-            fprintf(stderr, "dpp kernel matrix, s_memtime ticks per tile: prologue %.0f, panel wait + LDS writes %.0f, panel requests %.0f, matrix instructions %.0f, epilogue %.0f\n",
-                    h[0] / tiles, h[1] / tiles, h[2] / tiles, h[3] / tiles, h[4] / tiles);
-        }
-    }
-#else
-    else dpp_kernel_matrix_mfma_kernel<<<km_blocks, 64, 0, ctx->stream>>>(F, n, d1, nt, R, ld, L);
-#endif
+    dpp_kernel_matrix_mfma_kernel<<<km_blocks, 64, 0, ctx->stream>>>(F, n, d1, nt, R, ld, L);
     if (d_L_out) {                                              // KernelMatrix alone (pg_dpp_kernel_matrix_dev)
         PG_HIP(hipGetLastError());
         dpp_scale_kernel<<<dim3((n + 63) / 64, n, R), 64, 0, ctx->stream>>>(L, Rr, n, ld, d_L_out);

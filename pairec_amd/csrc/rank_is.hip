@@ -2,21 +2,17 @@
 // consumer split, no workgroup barrier in the loop, no activation tile in LDS).
 #include "rank_mlp.hpp"
 
-#include <cstdlib>
-
 namespace pg {
 
 // ---------------------------------------------------------------------------------------------
-// fm2t_isw_kernel: the same model, shape and arithmetic as fm2t_irs_kernel (rank_ir.hip; algorithm/eas/fm_request.go:29-79,
-// service/rank/rank_service.go:264-289) — 8 item fields x 16, item tower 128 -> 256 -> 64, bf16, 640-B item records.
+// fm2t_isw_kernel: FM + two-tower rank (algorithm/eas/fm_request.go:29-79, service/rank/rank_service.go:264-289) for the
+// benchmark's shape — 8 item fields x 16, item tower 128 -> 256 -> 64, bf16, 640-B item records.
 //
-// fm2t_irs_kernel keeps the towers in the registers of four consumer waves and feeds them through LDS tiles from four
-// producer waves: two barrier-coupled halves per 64-item tile, each as long as its slowest wave, 5 500 cycles per tile
-// against an HBM floor of 3 400.  Here the towers' 96 KB of MFMA fragments live in LDS, read-only, and a
-// wave owns a 32-item tile from its records to its scores:
+// The towers' 96 KB of MFMA fragments live in LDS, read-only, and a wave owns a 32-item tile from its records to its scores
+// (a split into producer and consumer waves, two barrier-coupled halves per 64-item tile, took 5 500 cycles per tile against
+// an HBM floor of 3 400: DESIGN.md 4.2):
 //   * gather: four adjacent lanes per record, two passes of sixteen records, straight into registers (eight 16-B quads +
-//     the linear quad per lane and pass); the FM chains run in the lane, in the specification's order, exactly as
-//     fm2t_irs_kernel's conversion does;
+//     the linear quad per lane and pass); the FM chains run in the lane, in the specification's order;
 //   * the X operand never exists as a tile: layer 1 is computed in swapped form (C^T = W^T X^T), whose B operand wants
 //     lane (item, h) to hold dims 16 f + 8 h .. + 7 of its item — the packed quads 2 h, 2 h + 1 of field f, which sit in
 //     lanes (item, 2 h), (item, 2 h + 1) of the gather layout: two `ds_bpermute` per dword (one per pass) and a select;
@@ -25,19 +21,19 @@ namespace pg {
 //     register pair turns (P_0, P_1) into the fragment of k-step 2 nb and (P_2, P_3) into that of 2 nb + 1;
 //   * the head's two 32-column chains cross the lane halves every four columns the same way (sixteen hand-overs);
 //   * per hidden block: 8 layer-1 MFMAs (one chain, k ascending, from the bias) and 4 layer-2 MFMAs (two output blocks,
-//     k-steps 2 nb, 2 nb + 1) — the accumulation orders of both layers are fm2t_irs_kernel's, hence mlp_kernel's, hence
-//     the per-field path's: scores are bit-identical (test_fm2t_materialised_item_records_are_bit_identical).
+//     k-steps 2 nb, 2 nb + 1) — the accumulation orders of both layers are mlp_kernel's, hence the per-field path's:
+//     scores are bit-identical (test_fm2t_materialised_item_records_are_bit_identical).
 // Eight waves per CU (two per SIMD, 246 registers) run out of phase by themselves: one's gather latency and VALU phases
 // lie under the others' MFMAs.  The records of a wave's NEXT tile are requested before its towers run (72 registers in
 // flight under the MFMAs), its candidate rows a trip earlier, its descriptor a trip before that; the request's FM prefix
 // and user-tower output sit in a wave-private LDS cache refilled when the request changes (~150 tiles).
 // Measured (256 x 5 000 random candidates of a 20 M-item catalogue, one MI355X): rank stage 0.226-0.230 ms against
-// fm2t_irs_kernel's 0.246-0.262 on the same box, 0.219-0.227 in bench.py's leg (0.241); with every candidate = row 0 0.15 ms
-// (0.19).  The gather + FM sums alone (-DPG_ISW_GATHER_ONLY) take 0.171 ms = 5.3 TB/s of record lines: the towers' LDS
+// 0.246-0.262 for the producer / consumer kernel on the same box, 0.219-0.227 in bench.py's leg (0.241); with every candidate
+// = row 0 0.15 ms (0.19).  The gather + FM sums alone take 0.171 ms = 5.3 TB/s of record lines: the towers' LDS
 // and MFMA traffic costs the memory side a quarter of that (waves wait 55 % of their lifetime for their records, all
 // 2 048 of them with 18 KB in flight).  Tried: twelve waves (168 registers: 99 spilled dwords with the prefetch, 0.28 ms
-// without it), whole-line fetches with eight lanes per record (probe: -2 % on the gather alone, nothing under the towers —
-// unlike fm2t_irs_kernel's LDS-DMAs, where it gave 16 %), non-temporal loads (nothing).
+// without it), whole-line fetches with eight lanes per record (probe: -2 % on the gather alone, nothing under the towers),
+// non-temporal loads (nothing).
 // ---------------------------------------------------------------------------------------------
 constexpr int kIsTH = 256, kIsTO = 64;
 constexpr size_t kIsW1 = (size_t)kDIN * kIsTH * 2;            // 64 KiB of layer-1 fragments [n-block][k-step][lane]
@@ -82,10 +78,7 @@ __device__ __forceinline__ float is_to_lower(float v) {
     return __builtin_bit_cast(float, z);
 }
 
-#ifndef PG_ISW_WAVES
-#define PG_ISW_WAVES 8
-#endif
-constexpr int kIsWaves = PG_ISW_WAVES;                         // per CU (one workgroup)
+constexpr int kIsWaves = 8;                                    // per CU (one workgroup)
 
 __global__ __launch_bounds__(64 * kIsWaves, 1) void fm2t_isw_kernel(MlpArgs a) {
     constexpr int KS1 = kDIN / 16, KS2 = kIsTH / 16, NB1 = kIsTH / 32;     // 8 k-steps / 16 k-steps / 8 hidden blocks
@@ -176,7 +169,7 @@ __global__ __launch_bounds__(64 * kIsWaves, 1) void fm2t_isw_kernel(MlpArgs a) {
         const float4 q4 = *reinterpret_cast<const float4*>(rq + kFmMaxK + 4 * gj);
         const float linu = rq[64];
 
-        // ---- FM terms and the packed quads (fm2t_irs_kernel's conversion, per pass)
+        // ---- FM terms and the packed quads (per pass)
         uint32_t qp[2][8][2];
         float fmt[2];
 #pragma unroll
@@ -235,20 +228,6 @@ __global__ __launch_bounds__(64 * kIsWaves, 1) void fm2t_isw_kernel(MlpArgs a) {
         if (t + kIsWaves < t_end) issue_gather(rows1);
         load_rows(d2, rows1);                                  // (tile t + 2 W's rows: requested behind the gather that used the old ones)
 
-#ifdef PG_ISW_GATHER_ONLY
-        {                                                      // (developer experiment: the gather + FM + permutes alone)
-            float v = fm_term;
-#pragma unroll
-            for (int f = 0; f < 8; ++f)
-#pragma unroll
-                for (int i = 0; i < 8; ++i) v += (float)xb[f][i];
-            if (bh == 1 && bi < cnt) a.out[item0 + bi] = v;
-            d0 = d1;
-            d1 = d2;
-            d2 = d3;
-            continue;
-        }
-#endif
         // ---- the towers: per hidden block 8 + 4 MFMAs
         f32x16 acc2[2];
 #pragma unroll
@@ -268,27 +247,15 @@ __global__ __launch_bounds__(64 * kIsWaves, 1) void fm2t_isw_kernel(MlpArgs a) {
             }
             bf16x8 wf[KS1];
 #pragma unroll
-#ifdef PG_ISW_NO_LDSW                                           // (developer experiment: the towers without their LDS traffic — wrong results)
-            for (int ks = 0; ks < KS1; ++ks) wf[ks] = xb[(ks + nb) & 7];
-#else
             for (int ks = 0; ks < KS1; ++ks) wf[ks] = *reinterpret_cast<const bf16x8*>(W1S + (size_t)(nb * KS1 + ks) * 1024 + l_ * 16);
-#endif
             bf16x8 w2f[2][2];
 #pragma unroll
             for (int u = 0; u < 2; ++u)
 #pragma unroll
                 for (int nb2 = 0; nb2 < 2; ++nb2)
-#ifdef PG_ISW_NO_LDSW
-                    w2f[u][nb2] = xb[(u * 2 + nb2 + nb) & 7];
-#else
                     w2f[u][nb2] = *reinterpret_cast<const bf16x8*>(W2S + (size_t)(nb2 * KS2 + 2 * nb + u) * 1024 + l_ * 16);
-#endif
 #pragma unroll
-#ifdef PG_ISW_NO_MFMA                                           // (developer experiment: the LDS traffic without the MFMAs — wrong results)
-            for (int ks = 0; ks < KS1; ++ks) acc[ks] += (float)wf[ks][0] * (float)xb[ks][1];
-#else
             for (int ks = 0; ks < KS1; ++ks) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[ks], xb[ks], acc, 0, 0, 0);
-#endif
             // relu -> bf16 -> the two k-steps' B fragments of layer 2
             uint32_t pk[4][2];
 #pragma unroll
@@ -303,11 +270,7 @@ __global__ __launch_bounds__(64 * kIsWaves, 1) void fm2t_isw_kernel(MlpArgs a) {
                 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
                 const bf16x8 hb = __builtin_bit_cast(bf16x8, u32x4{pk[2 * u][0], pk[2 * u][1], pk[2 * u + 1][0], pk[2 * u + 1][1]});
 #pragma unroll
-#ifdef PG_ISW_NO_MFMA
-                for (int nb2 = 0; nb2 < 2; ++nb2) acc2[nb2][u] += (float)w2f[u][nb2][0] * (float)hb[1];
-#else
                 for (int nb2 = 0; nb2 < 2; ++nb2) acc2[nb2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w2f[u][nb2], hb, acc2[nb2], 0, 0, 0);
-#endif
             }
         }
         // ---- head: chain 0 over output columns 0..31 (from the FM term), chain 1 over 32..63 (from 0), both ascending; a
@@ -338,31 +301,6 @@ __global__ __launch_bounds__(64 * kIsWaves, 1) void fm2t_isw_kernel(MlpArgs a) {
             c1 = b1;
         }
         const float z = c0 + c1;
-#ifdef PG_ISW_DEBUG
-        const int dbg = (int)a.b3;
-        if (dbg) {
-            float v = 0.0f;
-            if (dbg == 1) v = fm_term;
-            if (dbg == 2 || dbg == 3) {
-#pragma unroll
-                for (int f = 0; f < 8; ++f)
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) v += (float)xb[f][i];
-            }
-            if (dbg == 4 || dbg == 5) {
-#pragma unroll
-                for (int i = 0; i < 16; ++i) v += acc2[0][i];
-            }
-            if (dbg == 6) v = c0;
-            if (dbg == 7) v = c1;
-            const bool upper = dbg == 3 || dbg == 5 || dbg == 6 || dbg == 7;
-            if ((bh == 1) == upper && bi < cnt) a.out[item0 + bi] = v;
-            d0 = d1;
-            d1 = d2;
-            d2 = d3;
-            continue;
-        }
-#endif
         if (bh == 1 && bi < cnt) a.out[item0 + bi] = 1.0f / (1.0f + expf(-z));
         d0 = d1;
         d1 = d2;
@@ -376,12 +314,6 @@ int launch_fm2t_isw(pg_ctx* ctx, const MlpArgs& a) {
     constexpr size_t lds = is_lds_bytes(kIsWaves);
     int rc;
     if ((rc = ensure_dyn_lds(ctx, (const void*)fm2t_isw_kernel, lds))) return rc;
-#ifdef PG_ISW_DEBUG
-    MlpArgs b = a;
-    b.b3 = getenv("PG_ISW_DEBUG_MODE") ? (float)atoi(getenv("PG_ISW_DEBUG_MODE")) : 0.0f;
-    fm2t_isw_kernel<<<ctx->num_cus, 64 * kIsWaves, lds, ctx->stream>>>(b);
-    return PG_OK;
-#endif
     fm2t_isw_kernel<<<ctx->num_cus, 64 * kIsWaves, lds, ctx->stream>>>(a);
     return PG_OK;
 }

@@ -216,12 +216,6 @@ __global__ __launch_bounds__(256, OCC) void mlp_kernel(MlpArgs a) {
     constexpr bool PRE = PREC == 1 && OCC >= 2;        // preloaded B fragments (bf16, several workgroups per CU)
     bf16x8 b1f[PRE ? KG1 : 1][PRE ? L1NB : 1];
     bf16x8 b2f[PRE ? KGC : 1][PRE ? L2NB : 1];
-#ifdef PG_MLP_PROFILE
-    uint64_t prof[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tp = __builtin_readcyclecounter();
-#define MLP_MARK(i) { const uint64_t tn = __builtin_readcyclecounter(); prof[i] += tn - tp; tp = tn; }
-#else
-#define MLP_MARK(i)
-#endif
 
     // ---------------- gather prologue: 32 lanes x 16 B per item, 8 items per pass ------------
     {
@@ -388,9 +382,7 @@ __global__ __launch_bounds__(256, OCC) void mlp_kernel(MlpArgs a) {
             }
         }
     }
-    MLP_MARK(0)
     __syncthreads();
-    MLP_MARK(1)
 
     const int mrow0 = wm * MB * 32;
     f32x16 acc2[MB][L2NB];
@@ -443,7 +435,6 @@ __global__ __launch_bounds__(256, OCC) void mlp_kernel(MlpArgs a) {
             gemm_tile<PREC, MB, L1NB, kDIN, true>(acc1, XT, mrow0, reinterpret_cast<const char*>(a.w1p),
                                                   frag1(chunk), lane, X_LO, reinterpret_cast<const char*>(a.w1p_lo));
         }
-        MLP_MARK(2)
         // relu → P() → H1 chunk tile (A operand of layer 2): one packed store per 4 columns
 #pragma unroll
         for (int mb = 0; mb < MB; ++mb)
@@ -458,9 +449,7 @@ __global__ __launch_bounds__(256, OCC) void mlp_kernel(MlpArgs a) {
                     store_h_quad<PREC, CH>(H1T, row, col, v0 > 0.0f ? v0 : 0.0f, v1 > 0.0f ? v1 : 0.0f,
                                            v2 > 0.0f ? v2 : 0.0f, v3 > 0.0f ? v3 : 0.0f, H_LO);
                 }
-        MLP_MARK(3)
         __syncthreads();
-        MLP_MARK(4)
         // ---- layer 2 partial: acc2 += H1chunk · W2[chunk*CH .. +CH, :]
         if constexpr (PRE) {
             gemm_tile_pre<MB, L2NB, CH>(acc2, H1T, mrow0, b2f, lane);
@@ -470,9 +459,7 @@ __global__ __launch_bounds__(256, OCC) void mlp_kernel(MlpArgs a) {
             gemm_tile<PREC, MB, L2NB, CH, true>(acc2, H1T, mrow0, reinterpret_cast<const char*>(a.w2p),
                                                 frag2(chunk), lane, H_LO, reinterpret_cast<const char*>(a.w2p_lo));
         }
-        MLP_MARK(5)
         if (NH1 == 1 || chunk + 1 == NCHUNK) __syncthreads();
-        MLP_MARK(6)
     }
 
     // ---- layer-2 activation → H2 tile (fp32; rows padded by one 16-B quad: an odd number of quads per
@@ -587,15 +574,6 @@ __global__ __launch_bounds__(256, OCC) void mlp_kernel(MlpArgs a) {
         }
         if (tid < BM && (uint32_t)tid < cnt) a.out[item0 + tid] = 1.0f / (1.0f + expf(-(ph[0] + ph[1])));
     }
-#ifdef PG_MLP_PROFILE
-    if constexpr (MODEL == 3 && PREC == 1) {           // (field_emb is unused by this instance: the launcher points it at a buffer)
-        MLP_MARK(7)
-        if (lane == 0 && blockIdx.x >= 5000 && blockIdx.x < 5016) {
-            uint64_t* o = (uint64_t*)(a.field_emb) + ((blockIdx.x - 5000) * 4 + wave) * 8;
-            for (int i = 0; i < 8; ++i) o[i] = prof[i];
-        }
-    }
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -988,7 +966,6 @@ struct RankScratch {
     uint32_t *tile_req, *tile_item0, *tile_cnt, *n_tiles, *req_tile0;
     float* c1;       // [n_req][h1]  (DNN3) or uo [n_req][to] (two-tower)
     float* fm_user;  // [n_req][kFmUserStride]
-    float* sink;     // [1024] write-only
 };
 
 static int rank_scratch(pg_ctx* ctx, uint32_t n_req, uint32_t max_tiles, uint32_t per_req_floats,
@@ -996,7 +973,7 @@ static int rank_scratch(pg_ctx* ctx, uint32_t n_req, uint32_t max_tiles, uint32_
     void* p;
     int rc;
     const size_t ints = (size_t)3 * max_tiles + 64 + n_req;
-    const size_t bytes = ints * 4 + ((size_t)n_req * per_req_floats + (size_t)n_req * kFmUserStride) * 4 + 256 + 8192;
+    const size_t bytes = ints * 4 + ((size_t)n_req * per_req_floats + (size_t)n_req * kFmUserStride) * 4 + 256;
     if ((rc = scratch_reserve(ctx, 6, bytes, &p))) return rc;
     uint32_t* u = (uint32_t*)p;
     rs->tile_req = u;
@@ -1006,7 +983,6 @@ static int rank_scratch(pg_ctx* ctx, uint32_t n_req, uint32_t max_tiles, uint32_
     rs->req_tile0 = rs->n_tiles + 64;
     rs->c1 = (float*)(rs->req_tile0 + n_req);
     rs->fm_user = rs->c1 + (size_t)n_req * per_req_floats;
-    rs->sink = rs->fm_user + (size_t)n_req * kFmUserStride + 16;     // 1 024 floats nobody reads (rank_ir.hip's always-issued stores)
     return PG_OK;
 }
 
@@ -1048,25 +1024,6 @@ static int launch_fm2t_mlp(pg_ctx* ctx, const MlpArgs& a, uint32_t grid) {
         if constexpr (PREC == 1) {
             constexpr size_t lds = mlp_lds_bytes(1, TO, 128, 1, kFmBM);
             if ((rc = ensure_dyn_lds(ctx, (const void*)mlp_kernel<1, TH, TO, false, 2, 2, 3, 128, 1, 2, FK, kFmBM>, lds))) return rc;
-#ifdef PG_MLP_PROFILE
-            // developer aid (make MLP_EXTRA=-DPG_MLP_PROFILE): per-phase cycle counts of 16 mid-grid workgroups, printed once
-            static uint64_t* dbg = nullptr;
-            if (!dbg) (void)hipMalloc(&dbg, 16 * 4 * 8 * 8);
-            MlpArgs b = a;
-            b.field_emb = reinterpret_cast<const float* const*>(dbg);
-            mlp_kernel<1, TH, TO, false, 2, 2, 3, 128, 1, 2, FK, kFmBM><<<grid, 256, lds, ctx->stream>>>(b);
-            uint64_t hcyc[16 * 4 * 8];
-            (void)hipMemcpy(hcyc, dbg, sizeof hcyc, hipMemcpyDeviceToHost);
-            static int calls = 0;
-            if (++calls == 5) {
-                double av[8] = {0};
-                for (int w = 0; w < 64; ++w)
-                    for (int i = 0; i < 8; ++i) av[i] += (double)hcyc[w * 8 + i] / 64.0;
-                fprintf(stderr, "mlp model 3, mean cycles per wave and tile: gather+fm %.0f | barrier %.0f | L1 mfma %.0f | relu+store %.0f | barrier %.0f | L2 mfma %.0f | barrier %.0f | head %.0f\n",
-                        av[0], av[1], av[2], av[3], av[4], av[5], av[6], av[7]);
-            }
-            return PG_OK;
-#endif
             mlp_kernel<1, TH, TO, false, 2, 2, 3, 128, 1, 2, FK, kFmBM><<<grid, 256, lds, ctx->stream>>>(a);
         } else if constexpr (PREC == 2) {
             constexpr size_t lds = mlp_lds_bytes(2, TO, 128, 1, kFmBM);
@@ -1213,10 +1170,9 @@ static int rank_fm2t_dev_locked(pg_ctx* ctx, const pg_model* m, const float* d_u
                                 uint32_t n_req, uint32_t n_items, float* d_out, const pg_item_rows* ir = nullptr,
                                 const uint32_t* d_cand = nullptr) {
     if (n_items == 0 || n_req == 0) return PG_OK;
-    // the benchmark's shape over item records: the stationary-weights kernel (rank_ir.hip), 64-item tiles
-    const bool irs = ir && !ctx->knobs.rank_no_ws && fm2t_irs_shape(m->th, m->to, m->k, m->nif, m->prec);
-    const bool isw = irs && !ctx->knobs.fm2t_irs;
-    const uint32_t bm = isw ? (uint32_t)kIswItems : irs ? (uint32_t)kIrsItems : (m->prec ? (uint32_t)kFmBM : (uint32_t)kBM);
+    // the benchmark's shape over item records: the per-wave pipeline kernel (rank_is.hip), 32-item tiles
+    const bool isw = ir && !ctx->knobs.rank_no_ws && fm2t_isw_shape(m->th, m->to, m->k, m->nif, m->prec);
+    const uint32_t bm = isw ? (uint32_t)kIswItems : (m->prec ? (uint32_t)kFmBM : (uint32_t)kBM);
     const uint32_t max_tiles = n_items / bm + n_req;
     RankScratch rs;
     int rc;
@@ -1255,11 +1211,8 @@ static int rank_fm2t_dev_locked(pg_ctx* ctx, const pg_model* m, const float* d_u
     a.w1p_lo = m->w1p_lo;
     a.w2p_lo = m->w2p_lo;
     a.out = d_out;
-    a.sink = rs.sink;
     if (isw) {
         if ((rc = launch_fm2t_isw(ctx, a))) return rc;
-    } else if (irs) {
-        if ((rc = launch_fm2t_irs(ctx, a))) return rc;
     } else if ((rc = dispatch_fm2t_mlp(ctx, m, a, max_tiles))) {
         return rc;
     }

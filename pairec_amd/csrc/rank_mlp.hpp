@@ -106,7 +106,6 @@ struct MlpArgs {
     const void* w1p_lo;
     const void* w2p_lo;
     float* out;
-    float* sink;                     // >= 1024 floats nobody reads (fm2t_irs_kernel's always-issued stores)
 };
 
 // (PREC 2: the hi tile has the bf16 layout, the lo tile follows it `lo_off` bytes on)
@@ -187,12 +186,9 @@ int launch_dnn3_ls(pg_ctx* ctx, uint32_t h1, uint32_t h2, const MlpArgs& a);
 bool dnn3_x3_shape(uint32_t h1, uint32_t h2);
 int launch_dnn3_x3(pg_ctx* ctx, uint32_t h1, uint32_t h2, const MlpArgs& a);
 
-// rank_ir.hip: FM + two-tower over materialised item records for the benchmark's shape (towers 256-64, 8 fields x 16, bf16):
-// weights stationary in registers, records two tiles ahead; 64-item tiles
-constexpr int kIrsItems = 64;
-bool fm2t_irs_shape(uint32_t th, uint32_t to, uint32_t k, uint32_t nif, int prec);
-int launch_fm2t_irs(pg_ctx* ctx, const MlpArgs& a);
-// the same shape with every wave a whole pipeline over 32-item tiles (rank_is.hip)
+// rank_is.hip: FM + two-tower over materialised item records for the benchmark's shape (towers 256-64, 8 fields x 16, bf16),
+// every wave a whole pipeline over 32-item tiles
+bool fm2t_isw_shape(uint32_t th, uint32_t to, uint32_t k, uint32_t nif, int prec);
 constexpr int kIswItems = 32;
 int launch_fm2t_isw(pg_ctx* ctx, const MlpArgs& a);
 

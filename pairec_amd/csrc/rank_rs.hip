@@ -26,12 +26,6 @@ constexpr size_t rs_lds_bytes(uint32_t n_out) {
            (W1L ? (size_t)kDIN * H1 * 2 : 0);
 }
 
-// make WS_EXTRA=-DPG_RS_PROFILE: per-phase cycle counts of the first workgroups (developer aid)
-#ifdef PG_RS_PROFILE
-#define RS_MARK(i) { const uint64_t tn = __builtin_readcyclecounter(); ph[i] += tn - tp; tp = tn; }
-#else
-#define RS_MARK(i)
-#endif
 
 struct RsTile {
     uint32_t req, item0, cnt;
@@ -121,9 +115,6 @@ __global__ __launch_bounds__(256 * MSPLIT, WPC) void dnn3_rs_kernel(MlpArgs a) {
     constexpr int FPW = kWsItems / (4 * MSPLIT);           // items a wave finishes
     const uint32_t fin_item = (uint32_t)wave_id * FPW + (lane & (FPW - 1));
 
-#ifdef PG_RS_PROFILE
-    uint64_t ph[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tp = __builtin_readcyclecounter();
-#endif
     for (uint32_t tile = t_begin; tile < t_end; ++tile) {
         const RsTile d3 = load_desc(tile + 3);
         // (per-lane addresses from an opaque copy of the thread id: hoisted out of the tile loop they are spilled)
@@ -139,9 +130,7 @@ __global__ __launch_bounds__(256 * MSPLIT, WPC) void dnn3_rs_kernel(MlpArgs a) {
             c1_req = cur.req;
             if (tid < H1) c1s[tid] = a.c1[(size_t)cur.req * a.c1_stride + tid];
         }
-        RS_MARK(0)
         __syncthreads();
-        RS_MARK(1)
 
         // ---- layer 1: hidden columns of n-blocks wave * NB1 + nb, transposed accumulators (a lane owns 4 consecutive
         // columns of one item); MBG item blocks at a time (one where two workgroups share the CU's registers)
@@ -189,9 +178,7 @@ __global__ __launch_bounds__(256 * MSPLIT, WPC) void dnn3_rs_kernel(MlpArgs a) {
                                             fmaxf(acc[mb][nb][4 * g + 0], 0.0f), fmaxf(acc[mb][nb][4 * g + 1], 0.0f),
                                             fmaxf(acc[mb][nb][4 * g + 2], 0.0f), fmaxf(acc[mb][nb][4 * g + 3], 0.0f));
         }
-        RS_MARK(2)
         __syncthreads();
-        RS_MARK(3)
 
         // ---- layer 2 + head partials
 #pragma unroll 1
@@ -257,9 +244,7 @@ __global__ __launch_bounds__(256 * MSPLIT, WPC) void dnn3_rs_kernel(MlpArgs a) {
                 }
             }
         }
-        RS_MARK(4)
         __syncthreads();                                   // partials visible; everyone is done with X and H1
-        RS_MARK(5)
 
         // ---- scores: z = (((b3 + p0) + p1) + …) + p7, 16 items per wave; lane group g = lane / FPW takes heads g, g + 64 / FPW, …
         if (fin_item < cur.cnt) {
@@ -274,14 +259,7 @@ __global__ __launch_bounds__(256 * MSPLIT, WPC) void dnn3_rs_kernel(MlpArgs a) {
         nxt = nn;
         nn = uniform(d3);
         row_n1 = row_n2;
-        RS_MARK(6)
     }
-#ifdef PG_RS_PROFILE
-    if (lane == 0 && blockIdx.x < 4) {
-        uint64_t* o = (uint64_t*)(a.field_emb) + (blockIdx.x * 4 + (wave_id & 3)) * 8;
-        for (int i = 0; i < 8; ++i) o[i] = ph[i];
-    }
-#endif
 }
 
 // WPC workgroups per CU: 128-128 needs 206 registers, so two of them share a CU (one's barriers and LDS phases run
@@ -291,24 +269,7 @@ static int launch_rs(pg_ctx* ctx, const MlpArgs& a) {
     const size_t lds = rs_lds_bytes<H1, H2, W1L>(a.n_out);
     int rc;
     if ((rc = ensure_dyn_lds(ctx, (const void*)dnn3_rs_kernel<H1, H2, WPC, MBG, MSPLIT, W1L>, lds))) return rc;
-#ifdef PG_RS_PROFILE
-    static uint64_t* dbg = nullptr;
-    if (!dbg) hipMalloc(&dbg, 4 * 4 * 8 * 8);
-    MlpArgs b = a;
-    b.field_emb = reinterpret_cast<const float* const*>(dbg);
-    dnn3_rs_kernel<H1, H2, WPC, MBG, MSPLIT, W1L><<<ctx->num_cus * WPC, 256 * MSPLIT, lds, ctx->stream>>>(b);
-    uint64_t hcyc[128];
-    hipMemcpy(hcyc, dbg, sizeof hcyc, hipMemcpyDeviceToHost);
-    static int calls = 0;
-    if (++calls % 40 == 3)
-        for (int wv = 0; wv < 8; ++wv) {
-            fprintf(stderr, "rs<%d,%d> wg %d wave %d:", H1, H2, wv / 4, wv % 4);
-            for (int i = 0; i < 8; ++i) fprintf(stderr, " %8llu", (unsigned long long)hcyc[wv * 8 + i]);
-            fprintf(stderr, "\n");
-        }
-#else
     dnn3_rs_kernel<H1, H2, WPC, MBG, MSPLIT, W1L><<<ctx->num_cus * WPC, 256 * MSPLIT, lds, ctx->stream>>>(a);
-#endif
     return PG_OK;
 }
 
@@ -378,9 +339,6 @@ __global__ __launch_bounds__(512, 1) void dnn3_ls_kernel(MlpArgs a) {
     const int mb1 = wave & 3, nb1 = wave >> 2;
     uint32_t c1_req = 0xffffffffu;
 
-#ifdef PG_RS_PROFILE
-    uint64_t ph[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tp = __builtin_readcyclecounter();
-#endif
     for (uint32_t tile = t_begin; tile < t_end; ++tile) {
         const uint32_t req = a.tile_req[tile], item0 = a.tile_item0[tile], cnt = a.tile_cnt[tile];
         uint32_t tid_o = tid;
@@ -424,9 +382,7 @@ __global__ __launch_bounds__(512, 1) void dnn3_ls_kernel(MlpArgs a) {
             }
 #pragma unroll
         for (int mb = 0; mb < 4; ++mb) LS_MFMA_READY(acc2[mb][0], acc2[mb][1]);
-        RS_MARK(0)
         __syncthreads();
-        RS_MARK(1)
 
         // layer 1 of chunk `cl` → H1 buffer `buf`; then its fragments are re-requested for chunk cl + 1
         auto layer1 = [&](int cl, int buf) {
@@ -498,7 +454,7 @@ __global__ __launch_bounds__(512, 1) void dnn3_ls_kernel(MlpArgs a) {
         // Between two barriers a wave runs layer 1 of one chunk and layer 2 of another, and the two waves of a SIMD (w and
         // w + 4) are HALF AN INTERVAL APART: layer 1 is a chain of 8 dependent MFMAs between LDS reads, relu and stores
         // — latency, 1 300-2 000 cycles by itself — while layer 2 is 32 back-to-back MFMAs; in step, both waves idled the
-        // matrix pipe together and then competed for it (PG_RS_PROFILE: 5 000 cycles per chunk for 2 600 of MFMA work).
+        // matrix pipe together and then competed for it (per-phase cycle stamps: 5 000 cycles per chunk for 2 600 of MFMA work).
         //   waves 0-3:  L1(0) b0 | L1(1) L2(0) b1 | L1(2) L2(1) b2 | …
         //   waves 4-7:  L1(0) b0 L2(0) | L1(1) b1 L2(1) | L1(2) b2 L2(2) | …
         // ONE code path (the same loop body, the barrier before or after its layer 2): L2(k) runs behind b_k, by which
@@ -510,9 +466,7 @@ __global__ __launch_bounds__(512, 1) void dnn3_ls_kernel(MlpArgs a) {
         const int ahead = wave >> 2;                       // waves 4-7 run layer 2 half an interval ahead
         layer1(0, 0);
         first_w2f();
-        RS_MARK(2)
         __syncthreads();
-        RS_MARK(3)
         if (ahead) layer2(0, 1);
         const int n_it = NCH - ahead;
 #pragma unroll 1
@@ -520,13 +474,9 @@ __global__ __launch_bounds__(512, 1) void dnn3_ls_kernel(MlpArgs a) {
             const int c1 = c + 1 < NCH ? c + 1 : c;        // layer 1's chunk
             const int c2 = c + ahead;                      // layer 2's chunk
             layer1(c1, (c + 1) & 1);
-            RS_MARK(2)
             if (ahead) __syncthreads();
-            RS_MARK(3)
             layer2(c2, c2 + 1 < NCH ? c2 + 1 : c2);
-            RS_MARK(4)
             if (!ahead) __syncthreads();
-            RS_MARK(3)
         }
         if (ahead) __syncthreads();
 
@@ -575,14 +525,7 @@ __global__ __launch_bounds__(512, 1) void dnn3_ls_kernel(MlpArgs a) {
                 a.out[(size_t)o * a.out_stride + item0 + (tid_o & (M - 1))] = 1.0f / (1.0f + expf(-z));
             }
         }
-        RS_MARK(5)
     }
-#ifdef PG_RS_PROFILE
-    if ((tid & 63) == 0 && blockIdx.x < 2) {
-        uint64_t* o = (uint64_t*)(a.field_emb) + (blockIdx.x * 8 + wave) * 8;
-        for (int i = 0; i < 8; ++i) o[i] = ph[i];
-    }
-#endif
 }
 
 template <int H1, int H2>
@@ -590,24 +533,7 @@ static int launch_ls(pg_ctx* ctx, const MlpArgs& a) {
     const size_t lds = ls_lds_bytes<H1, H2>(a.n_out);
     int rc;
     if ((rc = ensure_dyn_lds(ctx, (const void*)dnn3_ls_kernel<H1, H2>, lds))) return rc;
-#ifdef PG_RS_PROFILE
-    static uint64_t* dbg = nullptr;
-    if (!dbg) hipMalloc(&dbg, 2 * 8 * 8 * 8);
-    MlpArgs b = a;
-    b.field_emb = reinterpret_cast<const float* const*>(dbg);
-    dnn3_ls_kernel<H1, H2><<<ctx->num_cus, 512, lds, ctx->stream>>>(b);
-    uint64_t hcyc[128];
-    hipMemcpy(hcyc, dbg, sizeof hcyc, hipMemcpyDeviceToHost);
-    static int calls = 0;
-    if (++calls == 43)
-        for (int wv = 0; wv < 16; ++wv) {
-            fprintf(stderr, "ls<%d,%d> wg %d wave %d:", H1, H2, wv / 8, wv % 8);
-            for (int i = 0; i < 8; ++i) fprintf(stderr, " %8llu", (unsigned long long)hcyc[wv * 8 + i]);
-            fprintf(stderr, "\n");
-        }
-#else
     dnn3_ls_kernel<H1, H2><<<ctx->num_cus, 512, lds, ctx->stream>>>(a);
-#endif
     return PG_OK;
 }
 

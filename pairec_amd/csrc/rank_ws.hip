@@ -120,16 +120,10 @@ __global__ __launch_bounds__(256, 1) void dnn3_ws_kernel(MlpArgs a) {
     WsTile cur = uniform(load_desc(t_begin)), nxt = uniform(load_desc(t_begin + 1));
     load_rows(load_rowid(cur, g_item), g_q0);
     uint32_t c1_req = 0xffffffffu;
-#ifdef PG_WS_PROFILE
-    uint64_t ph[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tp = __builtin_readcyclecounter();
-#define WS_MARK(i) { const uint64_t tn = __builtin_readcyclecounter(); ph[i] += tn - tp; tp = tn; }
-#else
-#define WS_MARK(i)
-#endif
 
     // the streamed layer-1 fragments (hidden columns 128w+64..128w+127, used by block B): requested a tile ahead, in
     // the head phase — a global load costs its wave ~40 issue cycles in a VALU phase, 60-90 between MFMAs, and at
-    // the top of the tile they were a pure stall in front of the barrier (measured with PG_WS_PROFILE)
+    // the top of the tile they were a pure stall in front of the barrier (measured with per-phase cycle stamps)
     bf16x8 w1g[KS1][2];
 #pragma unroll
     for (int ks = 0; ks < KS1; ++ks)
@@ -222,9 +216,7 @@ __global__ __launch_bounds__(256, 1) void dnn3_ws_kernel(MlpArgs a) {
             *reinterpret_cast<float2*>(c1s + 2 * tid_o) =
                 *reinterpret_cast<const float2*>(a.c1 + (size_t)cur.req * a.c1_stride + 2 * tid_o);
         }
-        WS_MARK(0)
         __syncthreads();
-        WS_MARK(1)
 
         // ---- layer 1: hidden columns [128*wave, +128) as two blocks of 64 (A: fragments from LDS, B: the
         // streamed ones), both 32-item blocks each; transposed accumulators (a lane owns 4 consecutive columns
@@ -305,11 +297,9 @@ __global__ __launch_bounds__(256, 1) void dnn3_ws_kernel(MlpArgs a) {
 #pragma unroll
             for (int q = 0; q < 16; ++q) store_h(accB, wave * 128 + 64, q >> 3, (q >> 2) & 1, q & 3);
         }
-        WS_MARK(2)
         finalize_read_multi();
         if (MULTI && n_out > 4) finalize_high_heads();
         __syncthreads();
-        WS_MARK(3)
 
         // ---- layer 2: output columns [64*wave, +64) for both item blocks, W2 from the AGPR half, A fragments
         // two k-steps ahead.  The next tile's candidate rows are requested first.
@@ -364,7 +354,6 @@ __global__ __launch_bounds__(256, 1) void dnn3_ws_kernel(MlpArgs a) {
             WS_MFMA_DONE4(acc2[0][0], acc2[0][1], acc2[1][0], acc2[1][1]);
         }
         finalize_write_multi();
-        WS_MARK(4)
 
         // next tile's streamed fragments (this tile's were last read by block B)
 #pragma unroll
@@ -427,10 +416,7 @@ __global__ __launch_bounds__(256, 1) void dnn3_ws_kernel(MlpArgs a) {
                 }
             }
         }
-        WS_MARK(5)
         __syncthreads();                                   // partials visible; also: everyone is done with H1
-        WS_MARK(6)
-        WS_MARK(7)
         fin = cur;                                         // its scores are finished under the next tile's layer 1
         cur = nxt;
         nxt = uniform(nn);
@@ -440,12 +426,6 @@ __global__ __launch_bounds__(256, 1) void dnn3_ws_kernel(MlpArgs a) {
     finalize_read_multi();
     finalize_write_multi();
     if (MULTI && n_out > 4) finalize_high_heads();
-#ifdef PG_WS_PROFILE
-    if (lane == 0 && blockIdx.x < 4) {
-        uint64_t* o = (uint64_t*)(a.field_emb) + (blockIdx.x * 4 + wave) * 8;
-        for (int i = 0; i < 8; ++i) o[i] = ph[i];
-    }
-#endif
 }
 
 int launch_dnn3_ws(pg_ctx* ctx, const MlpArgs& a) {
@@ -457,24 +437,7 @@ int launch_dnn3_ws(pg_ctx* ctx, const MlpArgs& a) {
         return PG_OK;
     }
     if ((rc = ensure_dyn_lds(ctx, (const void*)dnn3_ws_kernel<false>, lds))) return rc;
-#ifdef PG_WS_PROFILE
-    static uint64_t* dbg = nullptr;
-    if (!dbg) hipMalloc(&dbg, 4 * 4 * 8 * 8);
-    MlpArgs b = a;
-    b.field_emb = reinterpret_cast<const float* const*>(dbg);
-    dnn3_ws_kernel<false><<<ctx->num_cus, 256, lds, ctx->stream>>>(b);
-    uint64_t hcyc[128];
-    hipMemcpy(hcyc, dbg, sizeof hcyc, hipMemcpyDeviceToHost);
-    static int calls = 0;
-    if (++calls == 3)
-        for (int wv = 0; wv < 8; ++wv) {
-            fprintf(stderr, "ws wg %d wave %d:", wv / 4, wv % 4);
-            for (int i = 0; i < 8; ++i) fprintf(stderr, " %8llu", (unsigned long long)hcyc[wv * 8 + i]);
-            fprintf(stderr, "\n");
-        }
-#else
     dnn3_ws_kernel<false><<<ctx->num_cus, 256, lds, ctx->stream>>>(a);
-#endif
     return PG_OK;
 }
 

@@ -17,14 +17,14 @@
 //   One barrier per chunk.  The two waves of a SIMD run different code between the same barriers, so one's LDS reads, global
 //   loads and conversions sit under the other's MFMAs without any hand-made interleaving — and the matrix pipe sees
 //   48 + 96 MFMAs per SIMD and interval whichever wave issues them.
-// Where it stands (round 5, PG_X3_PROFILE-style cycle stamps and ablation builds on the dev library): the matrix pipe is 61 %
+// Where it stands (round 5, cycle stamps and ablation builds, since retired): the matrix pipe is 61 %
 // busy at the 1.95 GHz the chip holds under this kernel.  An interval is 6.3-6.7 K cycles for 4.6 K of MFMA issue per SIMD;
 // the layer-1 wave is its critical path (48 MFMAs + conversion: 2.9 K cycles with the pipe to itself, 5.4-6.8 K beside the
 // layer-2 wave's 96 MFMAs).  Tried and dropped, all bit-identical, none faster than 1.18-1.20 ms: the conversion of chunk
 // c under the MFMAs of chunk c + 1 (second accumulator set, layer-2 waves two intervals behind; as a block per k-step, and
 // cut into pieces between the individual MFMAs), weight fragments re-requested per k-step, weight fragments two k-steps
 // ahead in the layer-2 waves, priority to the layer-2 waves (-3 %).
-// Round 6 (same box, `scripts/dev/x3_time.py`, builds with `make WS_EXTRA=-DPG_X3_ABL=n`): 1.205 ms; X stored UNSPLIT (ablation 1 = the
+// Round 6 (same box, `scripts/dev/x3_time.py`, ablation builds, since retired): 1.205 ms; X stored UNSPLIT (ablation 1 = the
 // most a pre-split hi / lo shadow of the table rows could save): 1.23; H1 stored with NO relu / split at all (ablation 3): 1.19; X
 // fragments two k-steps ahead: 1.205.  The conversions are not what the kernel waits for, and neither is the matrix pipe's schedule:
 // rocm-smi beside a loop of this kernel reads 1 377-1 381 W of the 1 400 W package limit at 2.04-2.09 GHz of 2.4 (`scripts/dev/
@@ -59,24 +59,12 @@ __device__ __forceinline__ float x3_relu(float v) { return __builtin_amdgcn_fmed
 template <int LO>
 __device__ __forceinline__ void x3_store_h_quad(char* tile, int row, int col, float v0, float v1, float v2, float v3) {
     uint2 ph, pl;
-#if defined(PG_X3_ABL) && PG_X3_ABL == 3          // ablation (wrong results): H1 stored without relu / split — the conversion's whole cost
-    ph.x = __float_as_uint(v0); pl.x = __float_as_uint(v1); ph.y = __float_as_uint(v2); pl.y = __float_as_uint(v3);
-#else
     split_bf16x2(x3_relu(v0), x3_relu(v1), ph.x, pl.x);
     split_bf16x2(x3_relu(v2), x3_relu(v3), ph.y, pl.y);
-#endif
     char* const d = tile + row * 128 + ((((col >> 3) ^ ((row >> 1) & 7))) << 4) + (col & 7) * 2;
     *reinterpret_cast<uint2*>(d) = ph;
     *reinterpret_cast<uint2*>(d + LO) = pl;
 }
-
-#if defined(PG_X3_ABL) && PG_X3_ABL == 1
-__device__ __forceinline__ void store_x_quad_raw(char* tile, int row, int c, float4 v, int lo_off) {
-    char* const d = tile + row * 256 + ((((c >> 1) ^ (row & 15))) << 4) + (c & 1) * 8;
-    *reinterpret_cast<uint2*>(d) = make_uint2(__float_as_uint(v.x), __float_as_uint(v.y));
-    *reinterpret_cast<uint2*>(d + lo_off) = make_uint2(__float_as_uint(v.z), __float_as_uint(v.w));
-}
-#endif
 
 template <int H1, int H2>
 __global__ __launch_bounds__(512, 1) void dnn3_x3_kernel(MlpArgs a) {
@@ -148,11 +136,7 @@ __global__ __launch_bounds__(512, 1) void dnn3_x3_kernel(MlpArgs a) {
             for (int p = 0; p < 2; ++p)
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
-#if defined(PG_X3_ABL) && PG_X3_ABL == 1      // ablation (wrong results): X stored unsplit — what a pre-split shadow of the rows could save at most
-                    store_x_quad_raw(XH, p * 64 + (t_ >> 2), 4 * j + (t_ & 3), xq[p][j], X_B);
-#else
                     store_x_quad<2>(XH, p * 64 + (t_ >> 2), 4 * j + (t_ & 3), xq[p][j], X_B);
-#endif
                 }
             if (d.req != c1_req) {
                 c1_req = d.req;

@@ -134,7 +134,6 @@ __device__ __forceinline__ void wait_vmcnt() {
     asm volatile("s_waitcnt vmcnt(%0)" ::"i"(N) : "memory");
 }
 
-// VAR: developer ablations (0 = product; 1 = no threshold test; 2 = no MFMA; 3 = no DMA)
 // NQB = number of 32-query column blocks riding in the B operand (1: up to 32 queries, 2: up to 64).
 // With two blocks every A fragment feeds two independent accumulator chains and the kernel becomes
 // fp32-MFMA-bound instead of HBM-bound (2 x 64 cycles per 32 B of table per SIMD).
@@ -142,8 +141,10 @@ __device__ __forceinline__ void wait_vmcnt() {
 // inner products come out of the same MFMA chains; every accumulator is then turned into -d = fmaf(2, ip, -(|x|^2 + |q|^2))
 // — the block's 32 row norms arrive by scalar loads (the block's first row is wave-uniform; lgkmcnt, not the ring's vmcnt) —
 // and everything behind (threshold streaming, keys, select, final) works on -d unchanged.  HBM-bound like the exact scan.
+// (VAR is kept only so that the kernel's name stays the same)
 template <int DIM, int NQB = 1, int VAR = 0, bool L2 = false>
 __global__ __launch_bounds__(64 * kScanWaves, 2) void scan_kernel(ScanArgs a) {
+    static_assert(VAR == 0);
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int PPB = DIM / kPieceCols;       // pieces per 32-row block
     constexpr int NS = kRingSlots;
@@ -277,7 +278,7 @@ __global__ __launch_bounds__(64 * kScanWaves, 2) void scan_kernel(ScanArgs a) {
             const uint32_t t = b * PPB + pc;
             // pieces t..t+NS-2 are in flight (ND DMAs each); piece t+NS-1 is issued below, one DMA
             // every other quad, into the slot that piece t-1 just vacated
-            if (VAR != 3) wait_vmcnt<ND * (NS - 2)>();      // piece t has landed
+            wait_vmcnt<ND * (NS - 2)>();                    // piece t has landed
             const char* nb_src;
             uint32_t nb_dst;
             piece_addr(t + NS - 1, nb_src, nb_dst);
@@ -292,24 +293,15 @@ __global__ __launch_bounds__(64 * kScanWaves, 2) void scan_kernel(ScanArgs a) {
 #pragma unroll
             for (int g = 0; g < NQ; ++g) {
                 const f32x4 q = qv[g];
-                if (g < ND && VAR != 3) dma_one(nb_src, nb_dst + g * 1024, voff[g], q.x);
+                if (g < ND) dma_one(nb_src, nb_dst + g * 1024, voff[g], q.x);
                 const float a0 = h ? q.y : q.x;
                 const float a1 = h ? q.w : q.z;
                 const int s = pc * (kPieceCols / 2) + 2 * g;
-                if (VAR == 2) {
-                    acc[0][g] += a0 + a1;
-                } else {
 #pragma unroll
-                    for (int c = 0; c < NQB; ++c) acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, bq[c][s], acc[c], 0, 0, 0);
+                for (int c = 0; c < NQB; ++c) acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, bq[c][s], acc[c], 0, 0, 0);
 #pragma unroll
-                    for (int c = 0; c < NQB; ++c) acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, bq[c][s + 1], acc[c], 0, 0, 0);
-                }
+                for (int c = 0; c < NQB; ++c) acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, bq[c][s + 1], acc[c], 0, 0, 0);
             }
-        }
-        if (VAR == 1 || VAR == 3) {
-#pragma unroll
-            for (int c = 0; c < NQB; ++c) asm volatile("" ::"v"(acc[c][0]), "v"(acc[c][15]));   // keep the chain live
-            continue;
         }
         if constexpr (L2) {
             const uint32_t l2_row0 = __builtin_amdgcn_readfirstlane(
@@ -440,9 +432,6 @@ struct ScreenArgs {
     const float* blk_nxmin;   // [blocks] smallest |x|^2 of every physical 32-row block (pg_table::d_nxmin)
     const float* l2_b;        // [256]
     const float* nx_rows;     // L2 = 2 (per-row test: g = 2 s_x s_q I - |x|^2 >= C'_q, thr_screen = C'_q, l2_b = 2 s_x s_q): |x|^2 of every row
-#ifdef PG_SCREEN_PROFILE
-    unsigned long long* prof; // [waves][8]
-#endif
 };
 
 // Hit records (query halves).  A 32-row x 32-query tile with a suspect in it has, as a rule, exactly one: one lane, one of
@@ -458,31 +447,21 @@ struct ScreenArgs {
 // counted waits over-wait all the time and the ring runs one piece deep.)
 constexpr uint32_t kRecBytes = 80;
 constexpr uint32_t kRecOvfWord = 1 + kMaxQueries + 1;       // rs.overflow[kRecOvfWord]: the overflow was one of the hit-record areas (they can grow: pg_table::rec_scale)
-// make SCAN_EXTRA=-DPG_SCREEN_PROFILE: per-phase cycle counts of the query-halves loop, printed by launch_screen (developer aid)
-#ifdef PG_SCREEN_PROFILE
-#define SP_MARK(i) { const uint64_t tn = __builtin_readcyclecounter(); sp[i] += tn - sp_t; sp_t = tn; }
-#else
-#define SP_MARK(i)
-#endif
 
 // NQB query blocks of 32; WAVES waves per workgroup.  <=128 queries: 8 waves (2 per SIMD), ring of 4
 // pieces per wave; 256 queries: the 256 B-operand registers leave room for one wave per SIMD only, so
 // 4 waves with a ring of 8 pieces each.
-// SPLIT = 2: waves (2j, 2j+1) walk the SAME run of blocks, each against its own half of the queries
-// (NQB blocks each).  The table is then requested twice within a few microseconds; the second request
-// is served by L2 / Infinity Cache, so HBM traffic stays ≈ 1x while both waves keep their B operand in
-// 128 registers (two waves per SIMD) — 256 queries per pass without the one-wave-per-SIMD penalty.
-// VAR: developer ablations (PG_SCAN_VARIANTS builds only; 0 = product; 1 = no screen test; 2 = no MFMA and
-// no test; 3 = no DMA; 4 = test but never take the hit path) — they time the components, results are wrong
 // I8: the shadow and the queries are int8 and the bound is an exact int32 dot product on
 // v_mfma_i32_32x32x32_i8 — same issue rate as the bf16 MFMA at twice the k per instruction, over half the
 // bytes per row.
 // QH: query halves — the wave serves NQB x QH query blocks, QH groups of NQB one after the other on the same table
 // block, re-using the accumulators (int8, 256 queries: 2 x 4 blocks in 8 waves — two waves per SIMD, so one
 // wave's test, hit path and DMA issue run under the other's MFMAs; all 128 B-operand registers in the AGPR half).
+// (SPLIT and VAR are kept only so that the kernel's name stays the same)
 template <int DIM, int NQB, int WAVES, int SPLIT = 1, int VAR = 0, bool I8 = false, int QH = 1, int L2 = 0>
 __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void screen_kernel(ScreenArgs a) {
-    static_assert(!L2 || (I8 && QH == 1 && SPLIT == 1), "squared-Euclidean screen: the int8 kernels of <= 128 queries");
+    static_assert(SPLIT == 1 && VAR == 0);
+    static_assert(!L2 || (I8 && QH == 1), "squared-Euclidean screen: the int8 kernels of <= 128 queries");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // the kernel streams the table's shadow: a piece is 32 rows x one 128-B line per row (64 bf16 / 128 int8)
     constexpr int EB = I8 ? 1 : 2;               // bytes per shadow element
@@ -502,15 +481,13 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void screen_kernel(ScreenArg
     constexpr int kBLds = QH > 1 ? 2048 : 0;
     constexpr int kStageBytesW = (kScreenLds - kScanLdsRing - kBLds) / WAVES;
     constexpr int NQT = NQB * QH;                // query blocks of this wave
-    static_assert(QH == 1 || (PPB == 1 && SPLIT == 1), "query halves: one piece per block");
+    static_assert(QH == 1 || PPB == 1, "query halves: one piece per block");
     constexpr int kCap = (kStageBytesW - NQT * 256 - 16) / 8;       // staged (row, query) pairs per wave
     constexpr int kScanWaves = WAVES;            // (shadows the exact kernel's constant in this scope)
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t gw_raw = blockIdx.x * kScanWaves + wave;
-    const uint32_t gw = gw_raw / SPLIT;                          // block-run owner (shared by a wave group)
-    const uint32_t W = gridDim.x * kScanWaves / SPLIT;
-    const int qb0 = (int)(gw_raw % SPLIT) * NQT;                 // first query block of this wave
+    const uint32_t gw = blockIdx.x * kScanWaves + wave;
+    const uint32_t W = gridDim.x * kScanWaves;
     const int i32 = lane & 31;
     const int h = lane >> 5;
 
@@ -523,8 +500,8 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void screen_kernel(ScreenArg
     char* const b_lds = smem + kScreenLds - kBLds;
     if constexpr (QH > 1) {
         if (wave == 0) {
-            *reinterpret_cast<uint4*>(b_lds + lane * 16) = a.qb16[((qb0 + NQT - 1) * KS + KS - 2) * 64 + lane];
-            *reinterpret_cast<uint4*>(b_lds + 1024 + lane * 16) = a.qb16[((qb0 + NQT - 1) * KS + KS - 1) * 64 + lane];
+            *reinterpret_cast<uint4*>(b_lds + lane * 16) = a.qb16[((NQT - 1) * KS + KS - 2) * 64 + lane];
+            *reinterpret_cast<uint4*>(b_lds + 1024 + lane * 16) = a.qb16[((NQT - 1) * KS + KS - 1) * 64 + lane];
         }
         __syncthreads();
     }
@@ -533,15 +510,15 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void screen_kernel(ScreenArg
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
             if (QH > 1 && c == NQT - 1 && ks >= KS - 2) bfrag[c][ks] = make_uint4(0, 0, 0, 0);     // (in LDS; unused)
-            else bfrag[c][ks] = a.qb16[((qb0 + c) * KS + ks) * 64 + lane];
+            else bfrag[c][ks] = a.qb16[(c * KS + ks) * 64 + lane];
         }
-        active[c] = (uint32_t)((qb0 + c) * 32 + i32) < a.nq;
-        if constexpr (I8) thr_s[c] = active[c] ? __float_as_int(a.thr_screen[(qb0 + c) * 32 + i32]) : 0x7fffffff;
-        else thr_s[c] = active[c] ? a.thr_screen[(qb0 + c) * 32 + i32] : __builtin_inff();
-        eu[c] = (!I8 && active[c]) ? a.eps_unit[(qb0 + c) * 32 + i32] : 0.0f;
+        active[c] = (uint32_t)(c * 32 + i32) < a.nq;
+        if constexpr (I8) thr_s[c] = active[c] ? __float_as_int(a.thr_screen[c * 32 + i32]) : 0x7fffffff;
+        else thr_s[c] = active[c] ? a.thr_screen[c * 32 + i32] : __builtin_inff();
+        eu[c] = (!I8 && active[c]) ? a.eps_unit[c * 32 + i32] : 0.0f;
         if constexpr (L2 != 0) {                      // A_q in la, B_q in eu (L2 = 2: C'_q and 2 s_x s_q; inactive columns: never a suspect)
-            la[c] = active[c] ? a.thr_screen[(qb0 + c) * 32 + i32] : __builtin_inff();
-            eu[c] = active[c] ? a.l2_b[(qb0 + c) * 32 + i32] : 0.0f;
+            la[c] = active[c] ? a.thr_screen[c * 32 + i32] : __builtin_inff();
+            eu[c] = active[c] ? a.l2_b[c * 32 + i32] : 0.0f;
         }
     }
 #pragma unroll
@@ -574,7 +551,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void screen_kernel(ScreenArg
 
     const uint32_t total = a.rb_end - a.rb_begin;
     uint32_t first, nblk;
-    if (WAVES == 8 && SPLIT == 1 && a.early_share != 512) {
+    if (WAVES == 8 && a.early_share != 512) {
         // Two waves per SIMD (w and w + 4), and the SIMD's arbiter favours the older one: per-phase cycle counts of the
         // 256-query kernel had waves 0-3 finish an equal share in 78 % of the time of waves 4-7, which then ran the last fifth
         // of the launch alone — one wave per SIMD, nothing to overlap with.  So the pair's run of blocks is split unevenly
@@ -594,7 +571,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void screen_kernel(ScreenArg
         nblk = first < total ? (total - first < bpw ? total - first : bpw) : 0;
     }
     if (nblk == 0) {
-        if (QH > 1 && lane == 0) a.rec_cnt[gw_raw] = 0;
+        if (QH > 1 && lane == 0) a.rec_cnt[gw] = 0;
         return;
     }
 
@@ -660,7 +637,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void screen_kernel(ScreenArg
             const int q = lane + 64 * part;
             if (q < NQT * 32) {
                 const uint32_t c = st_cnt[q];
-                st_base[q] = c ? atomicAdd(&a.susp_cnt[qb0 * 32 + q], c) : 0u;
+                st_base[q] = c ? atomicAdd(&a.susp_cnt[q], c) : 0u;
                 st_cnt[q] = 0;
             }
         }
@@ -669,7 +646,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void screen_kernel(ScreenArg
             if (e < st_n) {
                 const uint32_t q = st_q[e];
                 const uint32_t pos = st_base[q] + atomicAdd(&st_cnt[q], 1u);
-                if (pos < a.cap) a.susp[(uint64_t)(qb0 * 32 + q) * a.cap + pos] = st_row[e];
+                if (pos < a.cap) a.susp[(uint64_t)q * a.cap + pos] = st_row[e];
                 else *a.overflow = 1u;
             }
         }
@@ -690,7 +667,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void screen_kernel(ScreenArg
         // hit records: staged in LDS (the area the other variants stage (row, query) pairs in), flushed to this wave's region
         constexpr uint32_t kRecStage = (uint32_t)kStageBytesW / kRecBytes;
         char* const rec_lds = smem + kScanLdsRing + wave * kStageBytesW;
-        char* const rec_glb = a.rec + (size_t)gw_raw * a.rec_cap * kRecBytes;
+        char* const rec_glb = a.rec + (size_t)gw * a.rec_cap * kRecBytes;
         uint32_t rec_st = 0, rec_total = 0;
         auto rec_flush = [&]() {
             if (rec_total + rec_st > a.rec_cap) {
@@ -714,12 +691,8 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void screen_kernel(ScreenArg
             }
             rec_st = 0;
         };
-#ifdef PG_SCREEN_PROFILE
-        uint64_t sp[8] = {0, 0, 0, 0, 0, 0, 0, 0}, sp_t = __builtin_readcyclecounter();
-#endif
         for (uint32_t b = 0; b < nblk; ++b) {
-            if (VAR != 3 && VAR != 5) wait_vmcnt<ND * (NS - 2)>();
-            SP_MARK(0)
+            wait_vmcnt<ND * (NS - 2)>();
             const char* nb_src;
             uint32_t nb_dst;
             piece_addr(NS - 1, b + NS - 1, nb_src, nb_dst);
@@ -730,8 +703,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void screen_kernel(ScreenArg
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int n = 0; n < ND; ++n)
-                if (VAR != 3 && VAR != 5) dma_one(nb_src, nb_dst + n * 1024, voff[n], q4[n].x);
-            SP_MARK(1)
+                dma_one(nb_src, nb_dst + n * 1024, voff[n], q4[n].x);
             const uint32_t cur_phys = phys[0];
 #pragma unroll
             for (int j = 0; j < D; ++j) phys[j] = phys[j + 1];
@@ -748,21 +720,12 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void screen_kernel(ScreenArg
                 for (int ksl = 0; ksl < 4; ++ksl)
 #pragma unroll
                     for (int c = 0; c < NQB; ++c) {
-                        if (VAR == 2) {                      // (ablation: stream only)
-                            asm volatile("" :: "v"(q4[ksl]));
-                            continue;
-                        }
                         uint4 bq;
                         if (half * NQB + c == NQT - 1 && ksl >= KS - 2) bq = *reinterpret_cast<const uint4*>(b_lds + (ksl - (KS - 2)) * 1024 + lane * 16);
                         else bq = bfrag[half * NQB + c][ksl];
                         acc[c] = __builtin_amdgcn_mfma_i32_32x32x32_i8(__builtin_bit_cast(i32x4, q4[ksl]),
                                                                        __builtin_bit_cast(i32x4, bq), acc[c], 0, 0, 0);
                     }
-                if (VAR == 1 || VAR == 2 || VAR == 5) {      // (ablation: no screen test)
-#pragma unroll
-                    for (int c = 0; c < NQB; ++c) asm volatile("" :: "v"(acc[c][0]), "v"(acc[c][15]));
-                    continue;
-                }
                 uint64_t cmask[NQB];
                 bool hit[NQB];
                 uint64_t any_mask = 0;
@@ -775,11 +738,6 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void screen_kernel(ScreenArg
                     cmask[c] = __builtin_amdgcn_ballot_w64(hit[c]);
                     any_mask |= cmask[c];
                 }
-                if (VAR == 4) {                              // (ablation: test, never the hit path)
-                    asm volatile("" :: "s"(any_mask));
-                    any_mask = 0;
-                }
-                SP_MARK(2 + 2 * half)
                 if (any_mask != 0) {
 #pragma unroll
                     for (int c = 0; c < NQB; ++c) {
@@ -799,7 +757,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void screen_kernel(ScreenArg
                                     const i32x4 v = {acc[c][4 * jj], acc[c][4 * jj + 1], acc[c][4 * jj + 2], acc[c][4 * jj + 3]};
                                     *reinterpret_cast<i32x4*>(r + 16 * jj) = v;
                                 }
-                                *reinterpret_cast<uint2*>(r + 64) = make_uint2(row0, (uint32_t)((qb0 + half * NQB + c) * 32 + i32) | ((uint32_t)h << 8));
+                                *reinterpret_cast<uint2*>(r + 64) = make_uint2(row0, (uint32_t)((half * NQB + c) * 32 + i32) | ((uint32_t)h << 8));
                             }
                             rec_st += n < kRecStage ? n : kRecStage;
                             if (n <= kRecStage) break;
@@ -808,15 +766,10 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void screen_kernel(ScreenArg
                         }
                     }
                 }
-                SP_MARK(3 + 2 * half)
             }
         }
         rec_flush();
-        if (lane == 0) a.rec_cnt[gw_raw] = rec_total;
-#ifdef PG_SCREEN_PROFILE
-        if (lane == 0 && a.prof)
-            for (int i = 0; i < 8; ++i) a.prof[gw_raw * 8 + i] = sp[i];
-#endif
+        if (lane == 0) a.rec_cnt[gw] = rec_total;
     } else {
     for (uint32_t b = 0; b < nblk; ++b) {
         AccT acc[NQB];
@@ -827,7 +780,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void screen_kernel(ScreenArg
 #pragma unroll
         for (int pc = 0; pc < PPB; ++pc) {
             const uint32_t t = b * PPB + pc;
-            if (VAR != 3) wait_vmcnt<ND * (NS - 2)>();
+            wait_vmcnt<ND * (NS - 2)>();
             const char* nb_src;
             uint32_t nb_dst;
             piece_addr(pc + NS - 1, t + NS - 1, nb_src, nb_dst);
@@ -843,15 +796,11 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void screen_kernel(ScreenArg
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int n = 0; n < ND; ++n)
-                if (VAR != 3) dma_one(nb_src, nb_dst + n * 1024, voff[n], q4[n].x);
+                dma_one(nb_src, nb_dst + n * 1024, voff[n], q4[n].x);
 #pragma unroll
             for (int ksl = 0; ksl < 4; ++ksl) {
                 const bf16x8 af = __builtin_bit_cast(bf16x8, q4[ksl]);
                 const int ks = pc * 4 + ksl;
-                if (VAR == 2) {
-                    asm volatile("" :: "v"(af));
-                    continue;
-                }
 #pragma unroll
                 for (int c = 0; c < NQB; ++c) {
                     if constexpr (I8)
@@ -869,11 +818,6 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void screen_kernel(ScreenArg
         // ---- screen test.  Each lane packs its hits into a bit set (bit c*16+r ↔ accumulator c,
         // register r); the slow path below only needs (row, query) — both follow from the bit index —
         // so the accumulators are never indexed dynamically.
-        if (VAR == 1 || VAR == 2) {
-#pragma unroll
-            for (int c = 0; c < NQB; ++c) asm volatile("" :: "v"(acc[c][0]), "v"(acc[c][15]));
-            continue;
-        }
         // Block reject: the largest of a lane's 16 bounds per query block against the screen threshold
         // (7 max3 + 1 max + 1 compare per query block).  fmaxf drops a NaN operand, which is safe: the
         // accumulators of a finite table and a finite, moderate query are finite, and every other query
@@ -938,7 +882,6 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void screen_kernel(ScreenArg
             }
             any_mask |= cmask[c];
         }
-        if (VAR == 4) any_mask = 0;
         if (any_mask != 0) {
             // the rare block with a hit: only the query blocks that have one are looked at again
             const uint32_t row0 = cur_phys * kPieceRows;
@@ -2058,16 +2001,16 @@ static uint32_t next_pow2(uint32_t x) {
     return p;
 }
 
-template <int DIM, int NQB = 1, int VAR = 0, bool L2 = false>
+template <int DIM, int NQB = 1, bool L2 = false>
 static int launch_scan(pg_ctx* ctx, const ScanArgs& a) {
     int rc_attr;
-    if ((rc_attr = ensure_dyn_lds(ctx, (const void*)scan_kernel<DIM, NQB, VAR, L2>, kScanLds))) return rc_attr;
+    if ((rc_attr = ensure_dyn_lds(ctx, (const void*)scan_kernel<DIM, NQB, 0, L2>, kScanLds))) return rc_attr;
     const uint32_t total = a.rb_end - a.rb_begin;
     uint32_t grid = (uint32_t)ctx->num_cus;
     const uint32_t need = (total + kScanWaves - 1) / kScanWaves;
     if (grid > need) grid = need;
     const uint32_t groups = a.group_q ? (a.nq + a.group_q - 1) / a.group_q : 1;
-    scan_kernel<DIM, NQB, VAR, L2><<<dim3(grid, groups), 64 * kScanWaves, kScanLds, ctx->stream>>>(a);
+    scan_kernel<DIM, NQB, 0, L2><<<dim3(grid, groups), 64 * kScanWaves, kScanLds, ctx->stream>>>(a);
     PG_HIP(hipGetLastError());
     return PG_OK;
 }
@@ -2075,22 +2018,14 @@ static int launch_scan(pg_ctx* ctx, const ScanArgs& a) {
 static int dispatch_scan(pg_ctx* ctx, uint32_t dim, const ScanArgs& a) {
     const bool wide = a.nq_launch > 32;          // two 32-query column blocks
     if (a.nx) {                                   // squared-Euclidean recall
-        if (dim == 64) return wide ? launch_scan<64, 2, 0, true>(ctx, a) : launch_scan<64, 1, 0, true>(ctx, a);
-        if (dim == 128) return wide ? launch_scan<128, 2, 0, true>(ctx, a) : launch_scan<128, 1, 0, true>(ctx, a);
+        if (dim == 64) return wide ? launch_scan<64, 2, true>(ctx, a) : launch_scan<64, 1, true>(ctx, a);
+        if (dim == 128) return wide ? launch_scan<128, 2, true>(ctx, a) : launch_scan<128, 1, true>(ctx, a);
         set_error("recall (squared Euclidean): dim=%u unsupported (64 or 128)", dim);
         return PG_ERR_UNSUPPORTED;
     }
     switch (dim) {
         case 64: return wide ? launch_scan<64, 2>(ctx, a) : launch_scan<64, 1>(ctx, a);
-        case 128: {
-#ifdef PG_SCAN_VARIANTS
-            const char* v = getenv("PG_SCAN_VAR");     // developer ablation builds only
-            if (v && v[0] == '1') return launch_scan<128, 1, 1>(ctx, a);
-            if (v && v[0] == '2') return launch_scan<128, 1, 2>(ctx, a);
-            if (v && v[0] == '3') return launch_scan<128, 1, 3>(ctx, a);
-#endif
-            return wide ? launch_scan<128, 2>(ctx, a) : launch_scan<128, 1>(ctx, a);
-        }
+        case 128: return wide ? launch_scan<128, 2>(ctx, a) : launch_scan<128, 1>(ctx, a);
         case 192:
         case 256:
             if (wide) {      // 2 x dim/2 B-operand registers no longer fit 2 waves per SIMD
@@ -2206,7 +2141,7 @@ int final_launch(pg_ctx* ctx, const uint64_t* cand, const uint32_t* cnt, uint32_
 }
 
 // statistics + shadow of a table (lazily, cached until the next upload / fill): int8 for dim 128 (two passes:
-// statistics, then quantisation with the table's scale), bf16 for dim 64 or when PG_SCREEN_BF16 is set (A/B runs).
+// statistics, then quantisation with the table's scale), bf16 for dim 64.
 // Tables the screen cannot serve (other dims, no memory for the shadow) keep stats_valid = false.
 static std::mutex g_stats_build_mu;   // a table is shared by the contexts of a device (a coalescer's sibling): one of them builds
 int ensure_table_stats(pg_ctx* ctx, const pg_table* tc) {
@@ -2221,8 +2156,7 @@ int ensure_table_stats(pg_ctx* ctx, const pg_table* tc) {
     t->pred_model = false;                            // ... and the threshold model
     t->prefix_failures = 0;
     if (t->dim != 64 && t->dim != 128) { t->shadow_failed = true; return PG_OK; }
-    const bool force_bf16 = ctx->knobs.screen_bf16;
-    bool i8 = t->dim == 128 && !force_bf16;
+    bool i8 = t->dim == 128;
     void* p;
     int rc;
     if ((rc = scratch_reserve(ctx, 4, 4096, &p))) return rc;
@@ -2249,8 +2183,7 @@ int ensure_table_stats(pg_ctx* ctx, const pg_table* tc) {
         // Heavy tails or outliers (a Student-t table: int8 margin 130 x the bf16 one, every row a suspect, 560 ms per
         // recall instead of 2.4) go to the bf16 shadow with per-block norms.
         const float rms_norm = sqrtf(sumsq / (float)(t->rows ? t->rows : 1));
-        const bool force_i8 = ctx->knobs.screen_i8;
-        if (t->all_finite && !force_i8 && t->s8 * sqrtf((float)t->dim / 12.0f) > 4.0f * kScreenEps * rms_norm) i8 = false;
+        if (t->all_finite && t->s8 * sqrtf((float)t->dim / 12.0f) > 4.0f * kScreenEps * rms_norm) i8 = false;
     }
     if (i8) {
         if (!t->d8) {
@@ -2374,33 +2307,15 @@ static int ensure_pred_model(pg_ctx* ctx, const pg_table* tc) {
     return PG_OK;
 }
 
-template <int DIM, int NQB, int WAVES, int SPLIT = 1, int VAR = 0, bool I8 = false, int QH = 1, int L2 = 0>
+template <int DIM, int NQB, int WAVES, bool I8 = false, int QH = 1, int L2 = 0>
 static int launch_screen(pg_ctx* ctx, const ScreenArgs& a) {
     int rc_attr;
-    if ((rc_attr = ensure_dyn_lds(ctx, (const void*)screen_kernel<DIM, NQB, WAVES, SPLIT, VAR, I8, QH, L2>, kScreenLds))) return rc_attr;
+    if ((rc_attr = ensure_dyn_lds(ctx, (const void*)screen_kernel<DIM, NQB, WAVES, 1, 0, I8, QH, L2>, kScreenLds))) return rc_attr;
     const uint32_t total = a.rb_end - a.rb_begin;
     uint32_t grid = (uint32_t)ctx->num_cus;
-    const uint32_t need = (total * SPLIT + WAVES - 1) / WAVES;
+    const uint32_t need = (total + WAVES - 1) / WAVES;
     if (grid > need) grid = need;
-#ifdef PG_SCREEN_PROFILE
-    if (QH > 1) {
-        static unsigned long long* dbg = nullptr;
-        if (!dbg) hipMalloc(&dbg, 4096 * 64);
-        ScreenArgs b = a;
-        b.prof = dbg;
-        screen_kernel<DIM, NQB, WAVES, SPLIT, VAR, I8, QH, L2><<<grid, 64 * WAVES, kScreenLds, ctx->stream>>>(b);
-        static int calls = 0;
-        if (total > 2000000 && ++calls == 12) {
-            std::vector<unsigned long long> h(4096 * 8);
-            hipMemcpy(h.data(), dbg, 4096 * 64, hipMemcpyDeviceToHost);
-            for (int w : {0, 1, 4, 5, 8 * 100, 8 * 100 + 4, 8 * 255 + 3})
-                fprintf(stderr, "[pg] screen wave %4d: wait %9llu lds+dma %9llu | half0 %9llu hit %9llu | half1 %9llu hit %9llu (cycles, %u blocks)\n", w,
-                        h[w * 8], h[w * 8 + 1], h[w * 8 + 2], h[w * 8 + 3], h[w * 8 + 4], h[w * 8 + 5], (total + grid * WAVES - 1) / (grid * WAVES));
-        }
-        return PG_OK;
-    }
-#endif
-    screen_kernel<DIM, NQB, WAVES, SPLIT, VAR, I8, QH, L2><<<grid, 64 * WAVES, kScreenLds, ctx->stream>>>(a);
+    screen_kernel<DIM, NQB, WAVES, 1, 0, I8, QH, L2><<<grid, 64 * WAVES, kScreenLds, ctx->stream>>>(a);
     PG_HIP(hipGetLastError());
     return PG_OK;
 }
@@ -2408,54 +2323,27 @@ static int launch_screen(pg_ctx* ctx, const ScreenArgs& a) {
 static int dispatch_screen(pg_ctx* ctx, uint32_t dim, bool i8, const ScreenArgs& a) {
     const bool wide = a.nq > 128;
     if (a.nx_rows) {                                 // squared-Euclidean recall, per-row test (rows of mixed norms)
-        if (a.nq <= 32) return launch_screen<128, 1, 8, 1, 0, true, 1, 2>(ctx, a);
-        if (a.nq <= 64) return launch_screen<128, 2, 8, 1, 0, true, 1, 2>(ctx, a);
-        return launch_screen<128, 4, 8, 1, 0, true, 1, 2>(ctx, a);
+        if (a.nq <= 32) return launch_screen<128, 1, 8, true, 1, 2>(ctx, a);
+        if (a.nq <= 64) return launch_screen<128, 2, 8, true, 1, 2>(ctx, a);
+        return launch_screen<128, 4, 8, true, 1, 2>(ctx, a);
     }
     if (a.blk_nxmin) {                               // squared-Euclidean recall: int8 shadow, <= 128 queries (recall_job_prepare)
-        if (a.nq <= 32) return launch_screen<128, 1, 8, 1, 0, true, 1, 1>(ctx, a);
-        if (a.nq <= 64) return launch_screen<128, 2, 8, 1, 0, true, 1, 1>(ctx, a);
-        return launch_screen<128, 4, 8, 1, 0, true, 1, 1>(ctx, a);
+        if (a.nq <= 32) return launch_screen<128, 1, 8, true, 1, 1>(ctx, a);
+        if (a.nq <= 64) return launch_screen<128, 2, 8, true, 1, 1>(ctx, a);
+        return launch_screen<128, 4, 8, true, 1, 1>(ctx, a);
     }
     if (i8) {                                        // int8 shadow (dim 128)
-#ifdef PG_SCAN_VARIANTS
-        const char* v = getenv("PG_SCREEN_VAR");     // developer ablation builds only
-        if (wide && v && v[0] == '1') return launch_screen<128, 4, 8, 1, 1, true, 2>(ctx, a);
-        if (wide && v && v[0] == '2') return launch_screen<128, 4, 8, 1, 2, true, 2>(ctx, a);
-        if (wide && v && v[0] == '4') return launch_screen<128, 4, 8, 1, 4, true, 2>(ctx, a);
-        if (wide && v && v[0] == '3') return launch_screen<128, 4, 8, 1, 3, true, 2>(ctx, a);     // no DMA (stale LDS): MFMA + tests
-        if (wide && v && v[0] == '5') return launch_screen<128, 4, 8, 1, 5, true, 2>(ctx, a);     // no DMA, no tests: MFMA only
-#endif
-        if (wide) return launch_screen<128, 4, 8, 1, 0, true, 2>(ctx, a);
-        if (a.nq <= 32) return launch_screen<128, 1, 8, 1, 0, true>(ctx, a);
-        if (a.nq <= 64) return launch_screen<128, 2, 8, 1, 0, true>(ctx, a);
-        return launch_screen<128, 4, 8, 1, 0, true>(ctx, a);
+        if (wide) return launch_screen<128, 4, 8, true, 2>(ctx, a);
+        if (a.nq <= 32) return launch_screen<128, 1, 8, true>(ctx, a);
+        if (a.nq <= 64) return launch_screen<128, 2, 8, true>(ctx, a);
+        return launch_screen<128, 4, 8, true>(ctx, a);
     }
-#ifdef PG_SCAN_VARIANTS
-    // PG_SCREEN_SPLIT=1 selects the wave-pair variant that fetches every block twice (measured slower: 8.3 vs
-    // 6.9 ms per 256-query pass — DESIGN.md "what did not work"); developer ablation builds only.
-    static const bool split = getenv("PG_SCREEN_SPLIT") != nullptr;
-    if (wide && split) return dim == 64 ? launch_screen<64, 4, 8, 2>(ctx, a) : launch_screen<128, 4, 8, 2>(ctx, a);
-#endif
     if (dim == 64) {
         if (wide) return launch_screen<64, 8, 4>(ctx, a);
         if (a.nq <= 32) return launch_screen<64, 1, 8>(ctx, a);
         if (a.nq <= 64) return launch_screen<64, 2, 8>(ctx, a);
         return launch_screen<64, 4, 8>(ctx, a);
     }
-#ifdef PG_SCAN_VARIANTS
-    {
-        const char* v = getenv("PG_SCREEN_VAR");     // developer ablation builds only
-        if (wide && v && v[0] == '1') return launch_screen<128, 8, 4, 1, 1>(ctx, a);
-        if (wide && v && v[0] == '2') return launch_screen<128, 8, 4, 1, 2>(ctx, a);
-        if (wide && v && v[0] == '3') return launch_screen<128, 8, 4, 1, 3>(ctx, a);
-        if (wide && v && v[0] == '4') return launch_screen<128, 8, 4, 1, 4>(ctx, a);
-        if (!wide && v && v[0] == '1') return launch_screen<128, 4, 8, 1, 1>(ctx, a);
-        if (!wide && v && v[0] == '2') return launch_screen<128, 4, 8, 1, 2>(ctx, a);
-        if (!wide && v && v[0] == '3') return launch_screen<128, 4, 8, 1, 3>(ctx, a);
-        if (!wide && v && v[0] == '4') return launch_screen<128, 4, 8, 1, 4>(ctx, a);
-    }
-#endif
     if (wide) return launch_screen<128, 8, 4>(ctx, a);
     if (a.nq <= 32) return launch_screen<128, 1, 8>(ctx, a);
     if (a.nq <= 64) return launch_screen<128, 2, 8>(ctx, a);

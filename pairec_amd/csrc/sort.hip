@@ -227,7 +227,7 @@ int sort_dev_locked(pg_ctx* ctx, const double* d_scores, const uint32_t* d_seg, 
     } else if (split_sort_applies(ctx, n_seg, max_seg)) {
         int rc;
         if ((rc = split_sort_launch(ctx, ScoreSortPolicy{d_scores, d_seg, desc, d_out}, n_seg, max_seg))) return rc;
-    } else if (max_seg <= kSortLdsMax && !ctx->knobs.sort_lds)
+    } else if (max_seg <= kSortLdsMax)
         sort_kernel_reg<<<n_seg, 1024, 0, ctx->stream>>>(d_scores, d_seg, desc, d_out);
     else
         sort_kernel<<<n_seg, 1024, lds, ctx->stream>>>(d_scores, d_seg, desc, g_keys, g_idx, stride, d_out);

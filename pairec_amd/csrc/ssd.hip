@@ -21,7 +21,6 @@
 
 #include <cfloat>
 #include <cmath>
-#include <cstring>
 
 namespace pg {
 
@@ -566,12 +565,9 @@ int ssd_run_locked(pg_ctx* ctx, const pg_table* t, const uint32_t* d_cand, const
     const size_t bMail = al(sizeof(SsdMail)), bEbuf = al((size_t)2 * (G + 1) * d1 * 8);
     // Kernel choice: the multi-workgroup kernel (embeddings pinned in registers, device-wide barrier) for the usual
     // widths (dim 64 / 128, with or without the appended 1) and windows <= 16; the one-workgroup kernels otherwise
-    // (PG_SSD_KERNEL=generic|reg forces them, for A/B runs; single requests only).
-    const char* force = getenv("PG_SSD_KERNEL");
+    // (single requests only).
     const bool known_d1 = d1 == 64 || d1 == 65 || d1 == 128 || d1 == 129;
-    int kind = ssd_batchable(d1, window) ? 2 : ((known_d1 && n <= kSsdRegMaxN) ? 1 : 0);
-    if (R == 1 && force && !strcmp(force, "generic")) kind = 0;
-    if (R == 1 && force && !strcmp(force, "reg") && known_d1 && n <= kSsdRegMaxN) kind = 1;
+    const int kind = ssd_batchable(d1, window) ? 2 : ((known_d1 && n <= kSsdRegMaxN) ? 1 : 0);
     if (R > 1 && kind != 2) {
         set_error("ssd: a batch of %u requests needs dim 64 / 128 and a window <= 16 (d1 = %u, window %u)", R, d1, window);
         return PG_ERR_UNSUPPORTED;

@@ -1,5 +1,5 @@
 """Developer aid: the split-bf16 rank stage alone (dnn3_x3_kernel, 256 x 5000 random candidate rows of a 100 M-row table), ms per
-call; PG_LIB_PATH selects the build (ablations compute wrong results by design: the check line says so).  GPU box."""
+call.  GPU box."""
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np
@@ -31,7 +31,6 @@ for _ in range(700 if loop else 5):
     res.append((time.perf_counter() - t0) / 10 * 1e3)
 out = np.empty(nI, dtype=np.float32)
 ctx.d2h(out, d_out)
-# (cheap fingerprint only: an ablation build shows a different one)
+# (cheap fingerprint only)
 msg = " | scores finite %s, mean %.6f, first %s" % (bool(np.all(np.isfinite(out))), float(out.mean()), out[:3])
-print("%s: x3 rank stage ms per call: %s (device %.3f)%s" % (os.environ.get("PG_LIB_PATH", "product"), " ".join("%.3f" % x for x in res),
-                                                            ctx.stats().last_rank_ms, msg))
+print("x3 rank stage ms per call: %s (device %.3f)%s" % (" ".join("%.3f" % x for x in res), ctx.stats().last_rank_ms, msg))
