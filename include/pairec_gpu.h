@@ -85,7 +85,10 @@ int pg_synchronize(pg_ctx* ctx);
  * lists) with "rank_sort_work" (lists x items^2 <= 7e7: counting ranks), "split_sort_max" (default 96 lists of 1025 … 8192 items:
  * runs sorted wave by wave over the chip; 0 = never); "stage_timers" (default 1; 0: this context's direct calls record no HIP events
  * around the recall plan, its scan launches and the rank stage — pg_stats' last_*_ms and pg_last_scan_kernel_ms stop moving, a
- * small batch's step gets 40-60 us shorter; a coalescer's batches never record them, see there).  value is parsed as a number. */
+ * small batch's step gets 40-60 us shorter; a coalescer's batches never record them, see there); for recalls through a pg_index
+ * "index_dense_fraction" (default 0.01: a batch of nq queries whose live (row, query) pairs exceed this x rows x nq^0.6 takes
+ * the table's pass).
+ * value is parsed as a number. */
 int pg_set_option(pg_ctx* ctx, const char* name, const char* value);
 int pg_device_malloc(pg_ctx* ctx, size_t bytes, void** out);
 int pg_device_free(pg_ctx* ctx, void* p);
@@ -387,6 +390,61 @@ int pg_recall_topk_where(pg_ctx* ctx, const pg_table* t, const pg_features* fs, 
  * recommend calls, and a view as i2i TRIGGER table, are refused (PG_ERR_UNSUPPORTED / PG_ERR_INVALID); rank / DPP / SSD calls take the
  * source table and the recalled ids.  PG_ERR_EMPTY when no row passes (PG_ERR_INVALID is a bad column / operator / feature store).  Destroyed with pg_table_destroy. */
 int pg_table_view_create(pg_ctx* ctx, const pg_table* t, const pg_features* fs, int column, int op, long long value, pg_table** out_view);
+
+/* ---- exact IVF-partitioned index ------------------------------------------------------------------
+ * The partition index behind the reference's remote vector services (the FAISS service of algorithm/faiss/
+ * vectorretrieval.proto:11-20, the Proxima index of HologresVectorRecall(V2), service/recall/hologres_vector_recall.go:23,
+ * _v2.go:23), kept EXACT: k-means lists over the table's rows, a rigorous per-(query, list) bound of every score in the list
+ * (DESIGN.md 4.1f), and only lists that provably cannot reach the query's K-th score are skipped.
+ *   Outputs   bit for bit those of pg_recall_topk[_l2][_dev] on the same table and queries: ids (row_offset + local), order, score
+ *             bits, tail padding (UINT64_MAX with -inf / +inf) and out_count.  Limits and error codes are the same too:
+ *             1 <= k <= 16384, nq <= 256 (<= 32 when dim > 128); squared Euclidean at dim 64 / 128.
+ *   Lifetime  the index references its table and holds no copy of the rows (4 B per row plus n_lists x (dim + 4) x 4 B); the
+ *             table must outlive the index.  Read-only after build: recalls from several contexts may run at once, each with
+ *             its own context's scratch.
+ *   Stale     after pg_table_upload, _fill_* or _swap the table's generation differs from the one the index was built against;
+ *             a recall through it is then served by the table's own pass (exact, counted as `stale`).  Rebuilding is the caller's job.
+ *   Refusals  a view as the source, and tables of >= 2^32 rows, return PG_ERR_UNSUPPORTED.
+ *   Fallbacks a table with non-finite values builds, every recall through it is served by the table's pass (`nonfinite`, also
+ *             counted for a batch with a non-finite query); a batch of nq queries whose live (row, query) pairs would exceed
+ *             index_dense_fraction x rows x nq^0.6 (pg_set_option, default 0.01) goes to the table's pass (`dense`); so does one whose candidate
+ *             lists overflow or whose per-call scratch cannot be allocated (`overflow`).  None of these is an error.
+ *   Build     PG_ERR_NOMEM when an allocation fails; nothing stays allocated then.
+ * params: n_lists 0 = round(4 sqrt(rows)) clamped to [1, 65536] and to rows / 64; train_rows 0 = min(rows, 64 n_lists) (the
+ * k-means sample); iters 0 = 8 Lloyd iterations; seed picks the sample and the initial centroids.  NULL = all defaults. */
+typedef struct pg_index pg_index;
+typedef struct {
+    uint32_t n_lists;
+    uint32_t train_rows;
+    uint32_t iters;
+    uint64_t seed;
+} pg_index_params;
+int pg_index_build(pg_ctx* ctx, const pg_table* t, const pg_index_params* p, pg_index** out);
+int pg_index_destroy(pg_ctx* ctx, pg_index* ix);
+int pg_index_recall_topk(pg_ctx* ctx, const pg_index* ix, const float* queries, uint32_t nq, uint32_t k, uint64_t* out_rows,
+                         float* out_scores, uint32_t* out_count);
+int pg_index_recall_topk_dev(pg_ctx* ctx, const pg_index* ix, const float* d_queries, uint32_t nq, uint32_t k, uint64_t* d_out_rows,
+                             float* d_out_scores, uint32_t* out_count);
+int pg_index_recall_topk_l2(pg_ctx* ctx, const pg_index* ix, const float* queries, uint32_t nq, uint32_t k, uint64_t* out_rows,
+                            float* out_dist, uint32_t* out_count);
+int pg_index_recall_topk_l2_dev(pg_ctx* ctx, const pg_index* ix, const float* d_queries, uint32_t nq, uint32_t k, uint64_t* d_out_rows,
+                                float* d_out_dist, uint32_t* out_count);
+typedef struct {
+    uint32_t n_lists, dim;
+    uint64_t rows, generation;          /* the table's rows and the generation the index was built against */
+    float    max_radius, mean_radius;   /* r_L >= max ||x - c_L|| over the rows of list L (mean over non-empty lists) */
+    uint32_t largest_list;              /* rows of the largest list */
+    uint32_t empty_lists;
+    double   build_ms;
+    /* recalls through the index: calls, queries, row loads and (row, query) scores of the exact re-scoring (one row load per pair:
+     * the scan gathers every pair's row), and the batches served by the table's pass, by reason */
+    uint64_t calls, queries, rows_scored, pairs_scored;
+    uint64_t fallback_dense, fallback_stale, fallback_nonfinite, fallback_overflow;
+    /* rows of the lists live for at least one query of a batch (the union; what a scan loading each live list once would read),
+     * summed over the batches scored through the index; the most rows one query's scan (outside its probe) scored in one batch */
+    uint64_t rows_live, max_query_scan_rows;
+} pg_index_stats_t;
+int pg_index_stats(const pg_index* ix, pg_index_stats_t* out);
 /* FM + two-tower rank straight from candidate rows: the model's item field ids are the integer columns
  * item_field_cols[n_item_fields] of `fs` (out-of-vocabulary ids are clamped as in pg_rank_fm2t_dev) */
 int pg_rank_fm2t_rows_dev(pg_ctx* ctx, const pg_model* m, const pg_features* fs, const int32_t* item_field_cols,

@@ -38,6 +38,8 @@ EXPORTS = [
     "pg_group_table_fill_synthetic", "pg_group_table_upload", "pg_group_model_load", "pg_group_recommend",
     "pg_group_recommend_begin", "pg_group_recommend_end", "pg_group_info", "pg_coalescer_create_group",
     "pg_router_create", "pg_router_destroy", "pg_router_recommend", "pg_router_recall", "pg_router_stats",
+    "pg_index_build", "pg_index_destroy", "pg_index_recall_topk", "pg_index_recall_topk_dev", "pg_index_recall_topk_l2",
+    "pg_index_recall_topk_l2_dev", "pg_index_stats",
 ]
 
 
@@ -50,6 +52,19 @@ class PgStats(C.Structure):
                 ("recall_suspects", C.c_uint64), ("recall_suspect_queries", C.c_uint64), ("recall_i4m_pairs", C.c_uint64),
                 ("recall_screen_overflows", C.c_uint64), ("recall_record_growths", C.c_uint64),
                 ("recall_rescored", C.c_uint64), ("sort_split_calls", C.c_uint64)]
+
+
+class PgIndexParams(C.Structure):
+    _fields_ = [("n_lists", C.c_uint32), ("train_rows", C.c_uint32), ("iters", C.c_uint32), ("seed", C.c_uint64)]
+
+
+class PgIndexStats(C.Structure):
+    _fields_ = [("n_lists", C.c_uint32), ("dim", C.c_uint32), ("rows", C.c_uint64), ("generation", C.c_uint64),
+                ("max_radius", C.c_float), ("mean_radius", C.c_float), ("largest_list", C.c_uint32), ("empty_lists", C.c_uint32),
+                ("build_ms", C.c_double), ("calls", C.c_uint64), ("queries", C.c_uint64), ("rows_scored", C.c_uint64),
+                ("pairs_scored", C.c_uint64), ("fallback_dense", C.c_uint64), ("fallback_stale", C.c_uint64),
+                ("fallback_nonfinite", C.c_uint64), ("fallback_overflow", C.c_uint64),
+                ("rows_live", C.c_uint64), ("max_query_scan_rows", C.c_uint64)]
 
 
 class PgDppOptions(C.Structure):
@@ -128,6 +143,13 @@ def load():
         "pg_recall_topk_l2_dev": [vp, vp, vp, u32, u32, vp, vp, vp],
         "pg_recall_topk_where": [vp, vp, vp, i32, i32, C.c_longlong, i32, vp, u32, u32, vp, vp, vp],
         "pg_table_view_create": [vp, vp, vp, i32, i32, C.c_longlong, vp],
+        "pg_index_build": [vp, vp, P(PgIndexParams), P(vp)],
+        "pg_index_destroy": [vp, vp],
+        "pg_index_recall_topk": [vp, vp, vp, u32, u32, vp, vp, vp],
+        "pg_index_recall_topk_dev": [vp, vp, vp, u32, u32, vp, vp, vp],
+        "pg_index_recall_topk_l2": [vp, vp, vp, u32, u32, vp, vp, vp],
+        "pg_index_recall_topk_l2_dev": [vp, vp, vp, u32, u32, vp, vp, vp],
+        "pg_index_stats": [vp, P(PgIndexStats)],
         "pg_topk_merge_dev": [vp, vp, vp, u32, u32, u32, u32, vp, vp],
         "pg_model_load": [vp, i32, i32, vp, sz, P(vp)],
         "pg_model_destroy": [vp, vp],

@@ -46,6 +46,7 @@ static void knobs_from_env(Knobs* k) {
     k->where_compact_max_rows = (uint32_t)num("PG_WHERE_COMPACT_MAX_ROWS", (double)(8u << 20));
     k->where_compact_min_ratio = (uint32_t)num("PG_WHERE_COMPACT_MIN_RATIO", 8);
     k->screen_early_share_narrow = (uint32_t)num("PG_SCREEN_EARLY_SHARE_NARROW", 512);
+    k->index_dense_fraction = num("PG_INDEX_DENSE_FRACTION", 0.01);
 }
 
 static thread_local std::string g_err;
@@ -190,6 +191,7 @@ int pg_set_option(pg_ctx* ctx, const char* name, const char* value) {
     else if (n == "where_compact_max_rows") k.where_compact_max_rows = (uint32_t)v;
     else if (n == "where_compact_min_ratio") k.where_compact_min_ratio = v >= 1 ? (uint32_t)v : 1u;
     else if (n == "screen_early_share_narrow") k.screen_early_share_narrow = (uint32_t)v;
+    else if (n == "index_dense_fraction") k.index_dense_fraction = v >= 0 ? v : 0.0;
     else {
         pg::set_error("pg_set_option: unknown option \"%s\"", name);
         return PG_ERR_INVALID;

@@ -93,6 +93,7 @@ struct Knobs {
     uint32_t where_compact_min_ratio = 8;         // PG_WHERE_COMPACT_MIN_RATIO: ... and at most 1/ratio of the table is served from a compact copy of them
     double l2_max_slack = 1.0;              // PG_L2_MAX_SLACK: largest pg_table::l2_slack the per-BLOCK cutoff is used for (above: the per-row test)
     uint32_t screen_early_share = 604;      // PG_SCREEN_EARLY_SHARE: share (x 1024) of a SIMD's blocks given to its older wave (256-query screen)
+    double index_dense_fraction = 0.01;     // PG_INDEX_DENSE_FRACTION: an index recall of nq queries whose (row, query) pairs exceed this x rows x nq^0.6 is served by the table's pass
 };
 
 }  // namespace pg
@@ -228,8 +229,8 @@ struct pg_ctx {
     //   6 rank tile table + request partials   7 sort / dpp / ssd work areas   8 recommend pipeline intermediates (post_scratch)
     //   9 group.hip   10 re-rank stage (DPP candidates)   11 recall.hip: the screened pass's record regions
     //   12, 13 recall.hip   14 rank_mlp.hip: head partials of the weights-stationary multi-head kernel   15 pg_fuse_scores_dev
-    //   16 pg_features_eval_dev: the bound variables
-    pg::Scratch scratch[17];
+    //   16 pg_features_eval_dev: the bound variables   17 index.hip: bounds, probe thresholds and list counts of an index recall
+    pg::Scratch scratch[18];
     std::mutex pool_mu;          // guards pipe_free
     std::vector<pg::PipeRun*> pipe_free;     // per-batch status blocks / events of the device-resident pipelines
     std::map<const void*, size_t> dyn_lds;   // kernels whose dynamic-LDS limit was raised on this device
@@ -401,6 +402,14 @@ int launch_select(pg_ctx* ctx, uint32_t nq, const uint64_t* in, uint64_t* out, u
 int final_launch(pg_ctx* ctx, const uint64_t* cand, const uint32_t* cnt, uint32_t cap, uint32_t nq, uint32_t k,
                  uint64_t row_offset, uint64_t* d_out_rows, float* d_out_scores, uint32_t* d_out_count);
 int ensure_table_stats(pg_ctx* ctx, const pg_table* tc);
+int ensure_table_nx(pg_ctx* ctx, const pg_table* tc);
+// recall.hip's exact re-scoring (rescore_kernel) over per-query suspect lists susp[q * scap + i] of local rows, appending the keys of
+// rows whose score reaches thr[q] to cand[q * cap + ...]; the squared-Euclidean |q|^2 chain and the final sign flip (index.hip)
+int rescore_launch(pg_ctx* ctx, uint32_t dim, bool l2, const float* tab, const float* d_queries, const float* thr, const uint32_t* susp,
+                   const uint32_t* susp_cnt, uint32_t scap, uint32_t* cnt, uint64_t* cand, uint32_t* overflow, uint32_t cap, uint32_t nq,
+                   uint32_t n_rows, const float* nx, const float* nqv, uint32_t blocks);
+int query_norm2_launch(pg_ctx* ctx, const float* d_queries, uint32_t nq, uint32_t dim, float* d_out);
+int negate_launch(pg_ctx* ctx, float* d_v, uint64_t n);
 // recall_i4.hip (caller holds ctx->mu)
 constexpr uint32_t kI4MaxQueries = 4;
 int ensure_table_i4(pg_ctx* ctx, const pg_table* tc);

@@ -1,0 +1,932 @@
+// index.hip — an exact IVF-partitioned index over a table.
+//
+// Build (all on the device): k-means over a sample of the rows (Lloyd, deterministic centroid sums in fp64), every row assigned
+// to its nearest centroid, a stable sort by list into a uint32 permutation (rows of one list in ascending source order) with the
+// lists' offsets, a per-list radius r_L >= max ||x - c_L|| over the rows actually assigned (fp64, rounded up) and ||c_L||.
+//
+// Search, per batch of queries:
+//   bound    U[q][L] >= every chain score of list L's rows (squared Euclidean: >= every -d), from q.c_L, ||q||, r_L and the
+//            chain's rounding error (the slack derived in DESIGN.md 4.1f)
+//   probe    per query, the lists of largest bound until >= K rows are covered (a weighted radix select over the bounds), scored
+//            exactly: the K-th best score is thr_q, a lower bound of the final K-th best
+//   scan     the lists that are not in the probe and whose bound reaches thr_q (inclusive), scored exactly; a row joins the
+//            query's candidates when its score reaches the running threshold
+//   select   recall.hip's select / final kernels: the same keys (score totalOrder descending, then row ascending) as the table pass
+// Every row is scored by recall.hip's rescore_kernel — the specification's k-ascending fmaf chain — so its bits are the table
+// pass's bits; pruning drops only lists whose bound proves that none of their rows can reach thr_q.
+#include "common.hpp"
+
+#include <hipcub/hipcub.hpp>
+
+#include <chrono>
+#include <cmath>
+
+struct pg_index {
+    const pg_table* t = nullptr;
+    uint64_t gen = 0;
+    uint64_t rows = 0;
+    uint32_t dim = 0, n_lists = 0;
+    bool nonfinite = false;
+    uint32_t* d_perm = nullptr;   // [rows] source rows, list by list
+    uint32_t* d_off = nullptr;    // [n_lists + 1] list offsets into d_perm
+    float* d_cent = nullptr;      // [n_lists][dim] centroids
+    float* d_cnorm = nullptr;     // [n_lists] ||c_L||, rounded up
+    float* d_rad = nullptr;       // [n_lists] r_L, rounded up
+    void* d_small = nullptr;      // the allocation behind d_off / d_cent / d_cnorm / d_rad
+    std::mutex mu;                // guards st
+    pg_index_stats_t st{};
+};
+
+namespace pg {
+namespace {
+
+constexpr uint32_t kMaxLists = 65536;
+constexpr uint32_t kSlices = 256;        // list slices of the count / expand kernels (per query)
+constexpr uint32_t kBoundQ = 8;          // queries per bound-kernel block
+
+__device__ __forceinline__ uint32_t ukey(float f) {      // order-preserving bits (totalOrder for non-NaN)
+    const uint32_t b = __float_as_uint(f);
+    if (f != f) return 0u;
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
+// the smallest float >= v
+__device__ __forceinline__ float round_up_f(double v) {
+    float f = (float)v;
+    if ((double)f < v) f = nextafterf(f, __builtin_inff());
+    return f;
+}
+
+// ---- build ---------------------------------------------------------------------------------------------------
+__global__ void sample_gather_kernel(const float* __restrict__ tab, uint64_t rows, uint32_t dim, uint64_t mul, uint64_t add,
+                                     float* __restrict__ out) {
+    const uint64_t i = blockIdx.x;
+    const uint64_t r = (mul * i + add) % rows;               // mul coprime to rows: distinct rows for i < rows
+    for (uint32_t c = threadIdx.x; c < dim; c += blockDim.x) out[i * dim + c] = tab[r * dim + c];
+}
+
+__global__ void iota_kernel(uint32_t* __restrict__ v, uint64_t n) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) v[i] = (uint32_t)i;
+}
+
+__global__ void cnorm2_kernel(const float* __restrict__ c, uint32_t nl, uint32_t dim, float* __restrict__ out) {
+    const uint32_t L = blockIdx.x * blockDim.x + threadIdx.x;
+    if (L >= nl) return;
+    float s = 0.0f;
+    for (uint32_t k = 0; k < dim; ++k) s = __fmaf_rn(c[(size_t)L * dim + k], c[(size_t)L * dim + k], s);
+    out[L] = s;
+}
+
+// nearest centroid (smallest ||c||^2 - 2 x.c, ties to the lower list) of rows [0, n) of X: 64 rows x 64 centroids per step, every
+// thread 4 x 4 of them.  Only speed depends on this arithmetic: the radius is measured over the assignment it makes.
+template <int DIM>
+__global__ __launch_bounds__(256) void assign_kernel(const float* __restrict__ X, uint64_t n, const float* __restrict__ C,
+                                                     const float* __restrict__ cn2, uint32_t nl, uint32_t* __restrict__ out,
+                                                     uint32_t* __restrict__ nonfinite) {
+    extern __shared__ float sm[];
+    float* const Xs = sm;                    // [DIM][65]
+    float* const Cs = sm + DIM * 65;         // [DIM][65]
+    const uint64_t r0 = (uint64_t)blockIdx.x * 64;
+    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+    bool bad = false;
+    for (int e = tid; e < 64 * DIM; e += 256) {
+        const int r = e / DIM, c = e % DIM;
+        const float v = r0 + r < n ? X[(r0 + r) * DIM + c] : 0.0f;
+        bad |= !isfinite(v);
+        Xs[c * 65 + r] = v;
+    }
+    if (bad) atomicOr(nonfinite, 1u);
+    float best[4];
+    uint32_t bi[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { best[i] = __builtin_inff(); bi[i] = 0xFFFFFFFFu; }
+    for (uint32_t c0 = 0; c0 < nl; c0 += 64) {
+        __syncthreads();
+        for (int e = tid; e < 64 * DIM; e += 256) {
+            const int cc = e / DIM, c = e % DIM;
+            Cs[c * 65 + cc] = c0 + cc < nl ? C[(size_t)(c0 + cc) * DIM + c] : 0.0f;
+        }
+        __syncthreads();
+        float acc[4][4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[i][j] = 0.0f;
+        for (int k = 0; k < DIM; ++k) {
+            float a[4], b[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) { a[i] = Xs[k * 65 + ty + 16 * i]; b[i] = Cs[k * 65 + tx + 16 * i]; }
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc[i][j] = __fmaf_rn(a[i], b[j], acc[i][j]);
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const uint32_t ci = c0 + tx + 16 * j;
+            if (ci >= nl) continue;
+            const float cc = cn2[ci];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const float d = cc - 2.0f * acc[i][j];
+                if (d < best[i]) { best[i] = d; bi[i] = ci; }
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        for (int off = 8; off > 0; off >>= 1) {
+            const float ob = __shfl_xor(best[i], off);
+            const uint32_t oi = (uint32_t)__shfl_xor((int)bi[i], off);
+            if (ob < best[i] || (ob == best[i] && oi < bi[i])) { best[i] = ob; bi[i] = oi; }
+        }
+        const uint64_t r = r0 + ty + 16 * i;
+        if (tx == 0 && r < n) out[r] = bi[i] < nl ? bi[i] : 0u;      // (a NaN row: list 0)
+    }
+}
+
+// offsets of a sorted key array: off[L] = first position whose key is >= L, off[nl] = n
+__global__ void list_offsets_kernel(const uint32_t* __restrict__ keys, uint64_t n, uint32_t nl, uint32_t* __restrict__ off) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > n) return;
+    const uint32_t lo = i == 0 ? 0u : keys[i - 1] + 1u;
+    const uint32_t hi = i == n ? nl : keys[i];
+    for (uint32_t L = lo; L <= hi && L <= nl; ++L) off[L] = (uint32_t)i;
+}
+
+// Lloyd update: centroid L = mean of its sample rows (summed in fp64, in sorted order: deterministic); an empty list is re-seeded
+// with a sample row
+__global__ void centroid_update_kernel(const float* __restrict__ S, uint32_t n_sample, uint32_t dim, const uint32_t* __restrict__ sorted_idx,
+                                       const uint32_t* __restrict__ off, float* __restrict__ C, uint64_t salt) {
+    const uint32_t L = blockIdx.x;
+    const uint32_t b = off[L], e = off[L + 1];
+    if (b == e) {
+        const uint32_t r = (uint32_t)((((uint64_t)L + 1) * 0x9E3779B97F4A7C15ull + salt) % n_sample);
+        for (uint32_t c = threadIdx.x; c < dim; c += blockDim.x) C[(size_t)L * dim + c] = S[(size_t)r * dim + c];
+        return;
+    }
+    for (uint32_t c = threadIdx.x; c < dim; c += blockDim.x) {
+        double s = 0.0;
+        for (uint32_t j = b; j < e; ++j) s += (double)S[(size_t)sorted_idx[j] * dim + c];
+        C[(size_t)L * dim + c] = (float)(s / (double)(e - b));
+    }
+}
+
+// r_L >= max ||x - c_L|| over the rows assigned to L: fp64 distances, a relative margin for their rounding, rounded up to fp32
+__global__ void radius_kernel(const float* __restrict__ tab, uint64_t rows, uint32_t dim, const uint32_t* __restrict__ assign,
+                              const float* __restrict__ C, uint32_t* __restrict__ rad_bits) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= rows) return;
+    const uint32_t L = assign[i];
+    double s = 0.0;
+    for (uint32_t k = 0; k < dim; ++k) {
+        const double d = (double)tab[i * dim + k] - (double)C[(size_t)L * dim + k];
+        s = fma(d, d, s);
+    }
+    const float r = round_up_f(sqrt(s) * (1.0 + 0x1p-40));
+    atomicMax(&rad_bits[L], __float_as_uint(r));             // (non-negative floats order as their bits)
+}
+
+__global__ void cnorm_kernel(const float* __restrict__ C, uint32_t nl, uint32_t dim, float* __restrict__ out) {
+    const uint32_t L = blockIdx.x * blockDim.x + threadIdx.x;
+    if (L >= nl) return;
+    double s = 0.0;
+    for (uint32_t k = 0; k < dim; ++k) s = fma((double)C[(size_t)L * dim + k], (double)C[(size_t)L * dim + k], s);
+    out[L] = round_up_f(sqrt(s) * (1.0 + 0x1p-40));
+}
+
+// ---- search --------------------------------------------------------------------------------------------------
+// per query: an upper bound of ||q|| (fp64) and whether every element is finite
+__global__ void qinfo_kernel(const float* __restrict__ Q, uint32_t dim, double* __restrict__ qn, uint32_t* __restrict__ flag) {
+    const uint32_t q = blockIdx.x;
+    double s = 0.0;
+    bool bad = false;
+    for (uint32_t c = threadIdx.x; c < dim; c += 64) {
+        const float v = Q[(size_t)q * dim + c];
+        bad |= !isfinite(v);
+        s = fma((double)v, (double)v, s);
+    }
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+    if (bad) atomicOr(flag, 1u);
+    if (threadIdx.x == 0) qn[q] = sqrt(s) * (1.0 + 0x1p-40);
+}
+
+__global__ void index_init_kernel(float* __restrict__ thr, uint32_t* __restrict__ cnt, uint32_t* __restrict__ overflow, uint32_t* __restrict__ flag) {
+    const uint32_t i = threadIdx.x;
+    thr[i] = -__builtin_inff();
+    cnt[i] = 0u;
+    if (i == 0) { *overflow = 0u; *flag = 0u; }
+}
+
+// U[q][L].  Inner product: fl(x.q) <= q.c + r ||q|| + gamma_d (||c|| + r) ||q|| (+ underflow and fp64 terms).
+// Squared Euclidean (ranked by -d): -fl(d) <= -(max(0, ||q - c|| - r))^2 + gamma_{d+3} (||c|| + r + ||q||)^2 (+ the same).
+// Where a partial sum could overflow fp32 the bound is +inf (the list is always scanned).
+template <bool L2>
+__global__ __launch_bounds__(256) void bound_kernel(const float* __restrict__ Q, uint32_t nq, uint32_t dim, const double* __restrict__ qn,
+                                                    const float* __restrict__ C, const float* __restrict__ cnorm, const float* __restrict__ rad,
+                                                    uint32_t nl, float* __restrict__ U) {
+    extern __shared__ double qs[];           // [kBoundQ][dim]
+    const uint32_t q0 = blockIdx.y * kBoundQ;
+    for (uint32_t e = threadIdx.x; e < kBoundQ * dim; e += blockDim.x) {
+        const uint32_t j = e / dim, c = e % dim;
+        qs[e] = q0 + j < nq ? (double)Q[(size_t)(q0 + j) * dim + c] : 0.0;
+    }
+    __syncthreads();
+    const uint32_t L = blockIdx.x * blockDim.x + threadIdx.x;
+    if (L >= nl) return;
+    double acc[kBoundQ];
+#pragma unroll
+    for (int j = 0; j < (int)kBoundQ; ++j) acc[j] = 0.0;
+    for (uint32_t c = 0; c < dim; ++c) {
+        const double cv = (double)C[(size_t)L * dim + c];
+#pragma unroll
+        for (int j = 0; j < (int)kBoundQ; ++j) {
+            if (L2) {
+                const double d = qs[j * dim + c] - cv;
+                acc[j] = fma(d, d, acc[j]);
+            } else {
+                acc[j] = fma(cv, qs[j * dim + c], acc[j]);
+            }
+        }
+    }
+    const double u = 0x1p-24;
+    const double dd = (double)dim + (L2 ? 3.0 : 0.0);
+    const double gam = dd * u / (1.0 - dd * u);
+    const double r = (double)rad[L], cn = (double)cnorm[L];
+#pragma unroll
+    for (int j = 0; j < (int)kBoundQ; ++j) {
+        const uint32_t q = q0 + j;
+        if (q >= nq) break;
+        const double qv = qn[q];
+        float out;
+        if (L2) {
+            const double b = cn + r + qv;
+            if (!(b * b * 2.0 < 0x1p126)) {
+                out = __builtin_inff();
+            } else {
+                const double s = sqrt(acc[j]) * (1.0 - 0x1p-40);
+                const double lb = s > r ? s - r : 0.0;
+                const double lb2 = lb * lb * (1.0 - 0x1p-40);
+                const double err = gam * b * b * (1.0 + 0x1p-20) + 0x1p-40 * b * b + (double)dim * 0x1p-146;
+                out = round_up_f(err - lb2);
+            }
+        } else {
+            const double a = (cn + r) * qv;
+            if (!(a * (1.0 + gam) * 2.0 < 0x1p127)) {
+                out = __builtin_inff();
+            } else {
+                const double slack = gam * a * (1.0 + 0x1p-20) + 0x1p-40 * a + (double)dim * 0x1p-148;
+                out = round_up_f(acc[j] + r * qv + slack);
+            }
+        }
+        U[(size_t)q * nl + L] = out;
+    }
+}
+
+// per query: the largest bound key B with sum(size of lists with key >= B) >= K (a radix select weighted by list size); the
+// probe is those lists, probe_rows[q] their rows.  A table of <= K rows probes everything (B = 0).
+__global__ __launch_bounds__(1024) void probe_kernel(const float* __restrict__ U, uint32_t nl, const uint32_t* __restrict__ off,
+                                                     uint64_t rows, uint32_t K, uint32_t* __restrict__ Bkey, uint32_t* __restrict__ probe_rows) {
+    __shared__ uint32_t hist[256];
+    __shared__ uint32_t s_digit, s_need;
+    __shared__ unsigned long long s_tot;
+    const uint32_t q = blockIdx.x, tid = threadIdx.x;
+    const float* u = U + (size_t)q * nl;
+    uint32_t prefix = 0, mask = 0, need = K;
+    if (rows > K) {
+        for (int shift = 24; shift >= 0; shift -= 8) {
+            if (tid < 256) hist[tid] = 0;
+            __syncthreads();
+            for (uint32_t L = tid; L < nl; L += 1024) {
+                const uint32_t sz = off[L + 1] - off[L];
+                const uint32_t key = ukey(u[L]);
+                if (sz && (key & mask) == prefix) atomicAdd(&hist[(key >> shift) & 255u], sz);
+            }
+            __syncthreads();
+            if (tid < 256) {
+                uint32_t above = 0;
+                for (int d = 255; d > (int)tid; --d) above += hist[d];
+                if (above < need && need <= above + hist[tid]) { s_digit = tid; s_need = need - above; }
+            }
+            __syncthreads();
+            prefix |= s_digit << shift;
+            mask |= 255u << shift;
+            need = s_need;
+            __syncthreads();
+        }
+    }
+    if (tid == 0) s_tot = 0;
+    __syncthreads();
+    unsigned long long mine = 0;
+    for (uint32_t L = tid; L < nl; L += 1024)
+        if (ukey(u[L]) >= prefix) mine += off[L + 1] - off[L];
+    atomicAdd(&s_tot, mine);
+    __syncthreads();
+    if (tid == 0) {
+        Bkey[q] = prefix;
+        probe_rows[q] = (uint32_t)s_tot;
+    }
+}
+
+// mode 0 (probe): key(U) >= B;  mode 1 (scan): U reaches thr (inclusive; a NaN threshold admits everything) and key(U) < B
+__device__ __forceinline__ bool list_selected(int mode, float u, uint32_t B, float thr) {
+    const uint32_t key = ukey(u);
+    return mode == 0 ? key >= B : (!(u < thr) && key < B);
+}
+
+__device__ __forceinline__ void slice_of(uint32_t nl, uint32_t g, uint32_t& lo, uint32_t& hi) {
+    const uint32_t per = (nl + kSlices - 1) / kSlices;
+    lo = g * per < nl ? g * per : nl;
+    hi = lo + per < nl ? lo + per : nl;
+}
+
+// rows of the selected lists per (query, slice)
+__global__ __launch_bounds__(256) void count_kernel(const float* __restrict__ U, uint32_t nl, const uint32_t* __restrict__ off,
+                                                    const uint32_t* __restrict__ Bkey, const float* __restrict__ thr, int mode,
+                                                    uint32_t* __restrict__ cnt) {
+    __shared__ uint32_t wsum[4];
+    const uint32_t q = blockIdx.y, g = blockIdx.x;
+    uint32_t lo, hi;
+    slice_of(nl, g, lo, hi);
+    const float* u = U + (size_t)q * nl;
+    const uint32_t B = Bkey[q];
+    const float th = thr[q];
+    uint32_t s = 0;
+    for (uint32_t L = lo + threadIdx.x; L < hi; L += 256)
+        if (list_selected(mode, u[L], B, th)) s += off[L + 1] - off[L];
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) cnt[(size_t)q * kSlices + g] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+}
+
+// the rows of the selected lists, in (slice, list) order, positions [skip, skip + scap) of that sequence → susp[q][0, scap)
+__global__ __launch_bounds__(256) void expand_kernel(const float* __restrict__ U, uint32_t nl, const uint32_t* __restrict__ off,
+                                                     const uint32_t* __restrict__ perm, const uint32_t* __restrict__ Bkey,
+                                                     const float* __restrict__ thr, int mode, const uint32_t* __restrict__ cnt,
+                                                     uint64_t skip, uint32_t scap, uint32_t* __restrict__ susp,
+                                                     uint32_t* __restrict__ susp_cnt) {
+    __shared__ uint32_t sc[256];
+    __shared__ uint32_t e_start[256], e_len[256];
+    __shared__ long long e_dst[256];
+    __shared__ uint32_t s_n;
+    __shared__ long long s_base;
+    const uint32_t q = blockIdx.y, g = blockIdx.x, tid = threadIdx.x;
+    if (tid == 0) {
+        unsigned long long before = 0, total = 0;
+        for (uint32_t i = 0; i < kSlices; ++i) {
+            const uint32_t c = cnt[(size_t)q * kSlices + i];
+            if (i < g) before += c;
+            total += c;
+        }
+        s_base = (long long)before - (long long)skip;
+        s_n = 0;
+        if (g == 0) {
+            const long long rem = (long long)total - (long long)skip;
+            susp_cnt[q] = rem <= 0 ? 0u : (rem < (long long)scap ? (uint32_t)rem : scap);
+        }
+    }
+    __syncthreads();
+    uint32_t lo, hi;
+    slice_of(nl, g, lo, hi);
+    const float* u = U + (size_t)q * nl;
+    const uint32_t B = Bkey[q];
+    const float th = thr[q];
+    uint32_t* const out = susp + (size_t)q * scap;
+    long long base = s_base;
+    for (uint32_t c0 = lo; c0 < hi; c0 += 256) {
+        const uint32_t L = c0 + tid;
+        const bool sel = L < hi && list_selected(mode, u[L], B, th);
+        const uint32_t b = sel ? off[L] : 0u;
+        const uint32_t sz = sel ? off[L + 1] - b : 0u;
+        sc[tid] = sz;
+        __syncthreads();
+        for (uint32_t o = 1; o < 256; o <<= 1) {            // inclusive scan of the sizes
+            const uint32_t v = tid >= o ? sc[tid - o] : 0u;
+            __syncthreads();
+            sc[tid] += v;
+            __syncthreads();
+        }
+        const long long dst = base + (long long)(sc[tid] - sz);
+        if (sz && dst < (long long)scap && dst + (long long)sz > 0) {
+            const uint32_t e = atomicAdd(&s_n, 1u);
+            e_start[e] = b;
+            e_len[e] = sz;
+            e_dst[e] = dst;
+        }
+        const uint32_t chunk = sc[255];
+        __syncthreads();
+        const uint32_t n_e = s_n;
+        for (uint32_t e = 0; e < n_e; ++e) {
+            const uint32_t st = e_start[e], len = e_len[e];
+            const long long d0 = e_dst[e];
+            for (uint32_t j = tid; j < len; j += 256) {
+                const long long p = d0 + (long long)j;
+                if (p >= 0 && p < (long long)scap) out[p] = perm[st + j];
+            }
+        }
+        base += chunk;
+        __syncthreads();
+        if (tid == 0) s_n = 0;
+        __syncthreads();
+    }
+}
+
+// rows of the lists that are live for at least one query of the batch (probe or scan): what a scan that loads every live list
+// once for all its queries would read
+__global__ __launch_bounds__(256) void union_kernel(const float* __restrict__ U, uint32_t nl, uint32_t nq, const uint32_t* __restrict__ off,
+                                                    const uint32_t* __restrict__ Bkey, const float* __restrict__ thr,
+                                                    unsigned long long* __restrict__ out) {
+    const uint32_t L = blockIdx.x * blockDim.x + threadIdx.x;
+    unsigned long long s = 0;
+    if (L < nl) {
+        bool live = false;
+        for (uint32_t q = 0; q < nq && !live; ++q) {
+            const float u = U[(size_t)q * nl + L];
+            live = list_selected(0, u, Bkey[q], thr[q]) || list_selected(1, u, Bkey[q], thr[q]);
+        }
+        if (live) s = off[L + 1] - off[L];
+    }
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    if ((threadIdx.x & 63) == 0 && s) atomicAdd(out, s);
+}
+
+// ---- host ----------------------------------------------------------------------------------------------------
+// device allocation that reports failure as PG_ERR_NOMEM (and clears the runtime's last error)
+int dalloc(void** p, size_t bytes, std::vector<void*>& owned) {
+    if (hipMalloc(p, bytes ? bytes : 16) != hipSuccess) {
+        (void)hipGetLastError();
+        *p = nullptr;
+        return PG_ERR_NOMEM;
+    }
+    owned.push_back(*p);
+    return PG_OK;
+}
+
+void free_all(std::vector<void*>& owned) {
+    for (void* p : owned) (void)hipFree(p);
+    owned.clear();
+}
+
+template <int DIM>
+int assign_launch(pg_ctx* ctx, const float* X, uint64_t n, const float* C, const float* cn2, uint32_t nl, uint32_t* out, uint32_t* flag) {
+    const size_t lds = (size_t)2 * DIM * 65 * 4;
+    int rc;
+    if ((rc = ensure_dyn_lds(ctx, (const void*)assign_kernel<DIM>, lds))) return rc;
+    assign_kernel<DIM><<<(uint32_t)((n + 63) / 64), 256, lds, ctx->stream>>>(X, n, C, cn2, nl, out, flag);
+    PG_HIP(hipGetLastError());
+    return PG_OK;
+}
+
+int assign_dispatch(pg_ctx* ctx, uint32_t dim, const float* X, uint64_t n, const float* C, const float* cn2, uint32_t nl, uint32_t* out,
+                    uint32_t* flag) {
+    cnorm2_kernel<<<(nl + 255) / 256, 256, 0, ctx->stream>>>(C, nl, dim, const_cast<float*>(cn2));
+    PG_HIP(hipGetLastError());
+    switch (dim) {
+        case 64: return assign_launch<64>(ctx, X, n, C, cn2, nl, out, flag);
+        case 128: return assign_launch<128>(ctx, X, n, C, cn2, nl, out, flag);
+        case 192: return assign_launch<192>(ctx, X, n, C, cn2, nl, out, flag);
+        case 256: return assign_launch<256>(ctx, X, n, C, cn2, nl, out, flag);
+    }
+    set_error("pg_index_build: dim=%u unsupported", dim);
+    return PG_ERR_UNSUPPORTED;
+}
+
+// stable sort of keys (list ids) with their positions: sorted keys, positions in source order within a key, offsets
+int sort_end_bit(uint32_t nl) {
+    int end_bit = 1;
+    while (end_bit < 32 && (1ull << end_bit) < (uint64_t)nl) ++end_bit;
+    return end_bit;
+}
+
+// temp storage of the largest sort of a build (hipcub's radix sort; the item count is 64-bit)
+int sort_temp_bytes(uint64_t n, uint32_t nl, size_t* out) {
+    *out = 0;
+    PG_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, *out, (const uint32_t*)nullptr, (uint32_t*)nullptr, (const uint32_t*)nullptr,
+                                              (uint32_t*)nullptr, n, 0, sort_end_bit(nl), (hipStream_t)0));
+    return PG_OK;
+}
+
+// (tmp: sort_temp_bytes of the build's largest n, allocated once)
+int sort_by_list(pg_ctx* ctx, const uint32_t* keys, uint64_t n, uint32_t nl, uint32_t* keys_out, uint32_t* vals_in, uint32_t* vals_out,
+                 uint32_t* off, void* tmp, size_t tmp_bytes) {
+    iota_kernel<<<(uint32_t)((n + 255) / 256), 256, 0, ctx->stream>>>(vals_in, n);
+    PG_HIP(hipGetLastError());
+    PG_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, keys, keys_out, vals_in, vals_out, n, 0, sort_end_bit(nl), ctx->stream));
+    list_offsets_kernel<<<(uint32_t)((n + 1 + 255) / 256), 256, 0, ctx->stream>>>(keys_out, n, nl, off);
+    PG_HIP(hipGetLastError());
+    return PG_OK;
+}
+
+uint64_t gcd64(uint64_t a, uint64_t b) {
+    while (b) { const uint64_t t = a % b; a = b; b = t; }
+    return a;
+}
+
+uint64_t splitmix(uint64_t& x) {
+    uint64_t z = (x += 0x9E3779B97F4A7C15ull);
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+int index_build_locked(pg_ctx* ctx, const pg_table* t, const pg_index_params& p, pg_index* ix, std::vector<void*>& owned,
+                       std::vector<void*>& temp) {
+    const uint64_t rows = t->rows;
+    const uint32_t dim = t->dim;
+    uint32_t nl = p.n_lists;
+    if (nl == 0) nl = (uint32_t)std::llround(4.0 * std::sqrt((double)rows));
+    if (nl > kMaxLists) nl = kMaxLists;
+    if (nl > rows / 64) nl = (uint32_t)(rows / 64);
+    if (nl < 1) nl = 1;
+    uint64_t ns = p.train_rows ? p.train_rows : std::min<uint64_t>(rows, 64ull * nl);
+    if (ns > rows) ns = rows;
+    if (ns < nl) ns = nl;
+    const uint32_t iters = p.iters ? p.iters : 8;
+    ix->n_lists = nl;
+    int rc;
+    // index memory: the permutation and the per-list arrays (one allocation)
+    if ((rc = dalloc((void**)&ix->d_perm, rows * 4, owned))) return rc;
+    const size_t off_b = ((size_t)(nl + 1) * 4 + 255) & ~(size_t)255, cent_b = (size_t)nl * dim * 4, lists_b = ((size_t)nl * 4 + 255) & ~(size_t)255;
+    if ((rc = dalloc(&ix->d_small, off_b + cent_b + 2 * lists_b, owned))) return rc;
+    ix->d_off = (uint32_t*)ix->d_small;
+    ix->d_cent = (float*)((char*)ix->d_small + off_b);
+    ix->d_cnorm = (float*)((char*)ix->d_cent + cent_b);
+    ix->d_rad = (float*)((char*)ix->d_cnorm + lists_b);
+    // build temporaries
+    float *S, *cn2;
+    uint32_t *assign, *keys_s, *vals_in, *vals_s, *soff, *flag;
+    if ((rc = dalloc((void**)&S, ns * dim * 4, temp))) return rc;
+    if ((rc = dalloc((void**)&cn2, (size_t)nl * 4, temp))) return rc;
+    if ((rc = dalloc((void**)&assign, rows * 4, temp))) return rc;
+    if ((rc = dalloc((void**)&keys_s, rows * 4, temp))) return rc;
+    if ((rc = dalloc((void**)&vals_in, rows * 4, temp))) return rc;
+    if ((rc = dalloc((void**)&soff, ((size_t)nl + 1) * 4, temp))) return rc;
+    if ((rc = dalloc((void**)&flag, 16, temp))) return rc;
+    size_t tmp_bytes = 0, tmp_small = 0;
+    void* tmp;
+    if ((rc = sort_temp_bytes(rows, nl, &tmp_bytes)) || (rc = sort_temp_bytes(ns, nl, &tmp_small))) return rc;
+    tmp_bytes = std::max(tmp_bytes, tmp_small);
+    if ((rc = dalloc(&tmp, tmp_bytes, temp))) return rc;
+    vals_s = ix->d_perm;                     // (the sample's sort uses the permutation's memory before the table's does)
+    PG_HIP(hipMemsetAsync(flag, 0, 16, ctx->stream));
+    // 1. the sample: rows (mul * i + add) mod rows, mul coprime to rows; the first n_lists of them seed the centroids
+    uint64_t sx = p.seed ^ 0x1D8E4E27C47D124Full;
+    uint64_t mul = rows > 1 ? 1 + splitmix(sx) % (rows - 1) : 1;
+    while (gcd64(mul, rows) != 1) mul = mul + 1 < rows ? mul + 1 : 1;
+    const uint64_t add = splitmix(sx) % rows;
+    sample_gather_kernel<<<(uint32_t)ns, 64, 0, ctx->stream>>>(t->d, rows, dim, mul, add, S);
+    PG_HIP(hipGetLastError());
+    PG_HIP(hipMemcpyAsync(ix->d_cent, S, (size_t)nl * dim * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    // 2. Lloyd iterations over the sample
+    for (uint32_t it = 0; it < iters; ++it) {
+        if ((rc = assign_dispatch(ctx, dim, S, ns, ix->d_cent, cn2, nl, assign, flag + 1))) return rc;
+        if ((rc = sort_by_list(ctx, assign, ns, nl, keys_s, vals_in, vals_s, soff, tmp, tmp_bytes))) return rc;
+        centroid_update_kernel<<<nl, 64, 0, ctx->stream>>>(S, (uint32_t)ns, dim, vals_s, soff, ix->d_cent, splitmix(sx));
+        PG_HIP(hipGetLastError());
+    }
+    // 3. every row to its nearest centroid; the stable sort by list is the permutation
+    if ((rc = assign_dispatch(ctx, dim, t->d, rows, ix->d_cent, cn2, nl, assign, flag))) return rc;
+    if ((rc = sort_by_list(ctx, assign, rows, nl, keys_s, vals_in, ix->d_perm, ix->d_off, tmp, tmp_bytes))) return rc;
+    // 4. radii over the rows actually assigned, 5. centroid norms
+    PG_HIP(hipMemsetAsync(ix->d_rad, 0, (size_t)nl * 4, ctx->stream));
+    radius_kernel<<<(uint32_t)((rows + 255) / 256), 256, 0, ctx->stream>>>(t->d, rows, dim, assign, ix->d_cent, (uint32_t*)ix->d_rad);
+    PG_HIP(hipGetLastError());
+    cnorm_kernel<<<(nl + 255) / 256, 256, 0, ctx->stream>>>(ix->d_cent, nl, dim, ix->d_cnorm);
+    PG_HIP(hipGetLastError());
+    std::vector<float> rad(nl);
+    std::vector<uint32_t> off(nl + 1);
+    uint32_t h_flag = 0;
+    PG_HIP(hipMemcpyAsync(rad.data(), ix->d_rad, (size_t)nl * 4, hipMemcpyDeviceToHost, ctx->stream));
+    PG_HIP(hipMemcpyAsync(off.data(), ix->d_off, ((size_t)nl + 1) * 4, hipMemcpyDeviceToHost, ctx->stream));
+    PG_HIP(hipMemcpyAsync(&h_flag, flag, 4, hipMemcpyDeviceToHost, ctx->stream));
+    PG_HIP(hipStreamSynchronize(ctx->stream));
+    ix->nonfinite = h_flag != 0;
+    double sum_r = 0.0;
+    float max_r = 0.0f;
+    uint32_t largest = 0, empty = 0;
+    for (uint32_t L = 0; L < nl; ++L) {
+        const uint32_t sz = off[L + 1] - off[L];
+        if (!sz) { ++empty; continue; }
+        largest = std::max(largest, sz);
+        sum_r += rad[L];
+        max_r = std::max(max_r, rad[L]);
+    }
+    ix->st.n_lists = nl;
+    ix->st.dim = dim;
+    ix->st.rows = rows;
+    ix->st.max_radius = max_r;
+    ix->st.mean_radius = nl > empty ? (float)(sum_r / (nl - empty)) : 0.0f;
+    ix->st.largest_list = largest;
+    ix->st.empty_lists = empty;
+    return PG_OK;
+}
+
+// per-call scratch of an index recall (slot 17); NOMEM instead of a device error
+int index_scratch(pg_ctx* ctx, size_t bytes, void** out) {
+    Scratch& s = ctx->scratch[17];
+    if (s.cap < bytes) {
+        if (s.p) {
+            PG_HIP(hipStreamSynchronize(ctx->stream));
+            PG_HIP(hipFree(s.p));
+            s.p = nullptr;
+            s.cap = 0;
+        }
+        const size_t cap = (bytes + (1u << 20) - 1) & ~((size_t)(1u << 20) - 1);
+        if (hipMalloc(&s.p, cap) != hipSuccess) {
+            (void)hipGetLastError();
+            s.p = nullptr;
+            return PG_ERR_NOMEM;
+        }
+        s.cap = cap;
+    }
+    *out = s.p;
+    return PG_OK;
+}
+
+enum Fallback { kNone = 0, kDense, kStale, kNonfinite, kOverflow };
+
+int table_pass_locked(pg_ctx* ctx, const pg_table* t, const float* d_q, uint32_t nq, uint32_t k, uint64_t* d_rows, float* d_sc,
+                      uint32_t* h_counts, bool l2) {
+    if (!l2) return recall_dev_locked(ctx, t, d_q, nq, k, d_rows, d_sc, h_counts, nullptr);
+    for (uint32_t q0 = 0; q0 < nq; q0 += 128) {       // (as pg_recall_topk_l2_dev: at most 128 queries per job)
+        const uint32_t n = nq - q0 < 128 ? nq - q0 : 128;
+        const int rc = recall_dev_locked(ctx, t, d_q + (size_t)q0 * t->dim, n, k, d_rows + (size_t)q0 * k, d_sc + (size_t)q0 * k,
+                                         h_counts + q0, nullptr, false, true);
+        if (rc) return rc;
+    }
+    return PG_OK;
+}
+
+// one batch (caller holds ctx->mu and the table's shared lock); h_counts: host [nq]
+int index_recall_locked(pg_ctx* ctx, pg_index* ix, const float* d_q, uint32_t nq, uint32_t k, uint64_t* d_rows, float* d_sc,
+                        uint32_t* h_counts, bool l2) {
+    const pg_table* t = ix->t;
+    const uint32_t nl = ix->n_lists, dim = t->dim;
+    uint64_t pairs = 0, union_rows = 0, max_scan = 0;
+    Fallback fb = kNone;
+    int rc = PG_OK;
+    auto tally = [&]() {
+        std::lock_guard<std::mutex> g(ix->mu);
+        ix->st.calls++;
+        ix->st.queries += nq;
+        ix->st.pairs_scored += pairs;
+        ix->st.rows_scored += pairs;
+        ix->st.rows_live += union_rows;
+        ix->st.max_query_scan_rows = std::max<uint64_t>(ix->st.max_query_scan_rows, max_scan);
+        if (fb == kDense) ix->st.fallback_dense++;
+        if (fb == kStale) ix->st.fallback_stale++;
+        if (fb == kNonfinite) ix->st.fallback_nonfinite++;
+        if (fb == kOverflow) ix->st.fallback_overflow++;
+    };
+    if (t->generation.load(std::memory_order_relaxed) != ix->gen) fb = kStale;
+    else if (ix->nonfinite) fb = kNonfinite;
+    else if (l2 && dim != 64 && dim != 128) fb = kDense;    // (the table's pass answers with its own error)
+    if (fb == kNone) rc = [&]() -> int {
+        RecallScratch rs;
+        int rc2;
+        if ((rc2 = recall_scratch(ctx, dim, k, &rs))) return rc2;
+        if (l2 && (rc2 = ensure_table_nx(ctx, t))) return rc2;
+        // slot 17: U [nq][nl] | qn [nq] f64 | nqv [nq] | Bkey [nq] | probe rows [nq] | counts [nq] | flag, union [16] |
+        //          slice counts [nq][kSlices] | scan threshold [nq]
+        const size_t u_b = ((size_t)nq * nl * 4 + 255) & ~(size_t)255;
+        void* base;
+        if (index_scratch(ctx, u_b + (size_t)nq * (8 + 4 + 4 + 4 + 4 + 4) + (size_t)nq * kSlices * 4 + 1024, &base)) {
+            fb = kOverflow;
+            return PG_OK;
+        }
+        float* U = (float*)base;
+        double* qn = (double*)((char*)base + u_b);
+        float* nqv = (float*)(qn + nq);
+        uint32_t* Bkey = (uint32_t*)(nqv + nq);
+        uint32_t* probe = Bkey + nq;
+        uint32_t* dcount = probe + nq;
+        uint32_t* flag = dcount + nq;
+        unsigned long long* d_union = (unsigned long long*)(flag + 2);
+        uint32_t* cntg = flag + 16;
+        float* thr_scan = (float*)(cntg + (size_t)nq * kSlices);   // the probe's K-th scores, frozen for the scan's list selection
+        hipStream_t s = ctx->stream;
+        index_init_kernel<<<1, kMaxQueries, 0, s>>>(rs.thr, rs.cnt, rs.overflow, flag);
+        qinfo_kernel<<<nq, 64, 0, s>>>(d_q, dim, qn, flag);
+        PG_HIP(hipGetLastError());
+        if (l2 && (rc2 = query_norm2_launch(ctx, d_q, nq, dim, nqv))) return rc2;
+        const dim3 bg((nl + 255) / 256, (nq + kBoundQ - 1) / kBoundQ);
+        const size_t blds = (size_t)kBoundQ * dim * 8;
+        if (l2) bound_kernel<true><<<bg, 256, blds, s>>>(d_q, nq, dim, qn, ix->d_cent, ix->d_cnorm, ix->d_rad, nl, U);
+        else bound_kernel<false><<<bg, 256, blds, s>>>(d_q, nq, dim, qn, ix->d_cent, ix->d_cnorm, ix->d_rad, nl, U);
+        probe_kernel<<<nq, 1024, 0, s>>>(U, nl, ix->d_off, ix->rows, k, Bkey, probe);
+        count_kernel<<<dim3(kSlices, nq), 256, 0, s>>>(U, nl, ix->d_off, Bkey, rs.thr, 0, cntg);
+        PG_HIP(hipGetLastError());
+        std::vector<uint32_t> h_cnt((size_t)nq * kSlices);
+        uint32_t h_flag = 0;
+        PG_HIP(hipMemcpyAsync(h_cnt.data(), cntg, h_cnt.size() * 4, hipMemcpyDeviceToHost, s));
+        PG_HIP(hipMemcpyAsync(&h_flag, flag, 4, hipMemcpyDeviceToHost, s));
+        PG_HIP(hipStreamSynchronize(s));
+        if (h_flag) { fb = kNonfinite; return PG_OK; }
+        // the scan gathers a full row per pair, the table's pass streams a shadow whose cost grows slowly with the batch: at 100 M
+        // rows the index breaks even at about 0.010 / 0.038 / 0.085 / 0.16 / 0.3-0.5 x rows pairs for 1 / 8 / 32 / 64 / 256 queries
+        // (profiles/index_breakeven.json with profiles/index_sweep_10k.json) — 0.01 x rows x nq^0.6
+        const double limit = ctx->knobs.index_dense_fraction * (double)ix->rows * std::pow((double)nq, 0.6);
+        const uint32_t scap = rs.cap - k;
+        uint64_t tot_probe = 0;
+        auto sum_counts = [&](uint64_t& total, uint64_t& most) {
+            total = 0;
+            most = 0;
+            for (uint32_t q = 0; q < nq; ++q) {
+                uint64_t v = 0;
+                for (uint32_t g = 0; g < kSlices; ++g) v += h_cnt[(size_t)q * kSlices + g];
+                total += v;
+                most = std::max(most, v);
+            }
+        };
+        uint64_t most = 0;
+        sum_counts(tot_probe, most);
+        if ((double)tot_probe > limit) { fb = kDense; return PG_OK; }
+        int cur = 0;
+        // score the selected lists' rows in rounds of scap per query, keeping each query's best K between rounds
+        auto run = [&](int mode, uint64_t most_q) -> int {
+            for (uint64_t skip = 0; skip < most_q; skip += scap) {
+                const uint64_t this_round = std::min<uint64_t>(most_q - skip, scap);
+                expand_kernel<<<dim3(kSlices, nq), 256, 0, s>>>(U, nl, ix->d_off, ix->d_perm, Bkey, thr_scan, mode, cntg, skip, scap,
+                                                                 rs.susp, rs.susp_cnt);
+                PG_HIP(hipGetLastError());
+                uint32_t blocks = (uint32_t)((this_round + 1023) / 1024);
+                const uint32_t most_blocks = std::max<uint32_t>(16u, 4096u / nq);
+                blocks = std::max<uint32_t>(1u, std::min(blocks, most_blocks));
+                int rc3;
+                if ((rc3 = rescore_launch(ctx, dim, l2, t->d, d_q, rs.thr, rs.susp, rs.susp_cnt, scap, rs.cnt, rs.cand[cur], rs.overflow,
+                                          rs.cap, nq, (uint32_t)ix->rows, l2 ? t->d_nx : nullptr, l2 ? nqv : nullptr, blocks)))
+                    return rc3;
+                if ((rc3 = launch_select(ctx, nq, rs.cand[cur], rs.cand[cur ^ 1], rs.cnt, rs.thr, rs.cap, k, 0))) return rc3;
+                cur ^= 1;
+            }
+            return PG_OK;
+        };
+        if ((rc2 = run(0, most))) return rc2;
+        pairs += tot_probe;
+        // the scan: lists outside the probe whose bound reaches the probe's K-th score.  The selection is made ONCE against that
+        // threshold (thr_scan): the per-slice counts and every round's expansion must see the same lists, while rs.thr keeps
+        // rising with the select between rounds and serves only the re-scoring's candidate test.
+        PG_HIP(hipMemcpyAsync(thr_scan, rs.thr, (size_t)nq * 4, hipMemcpyDeviceToDevice, s));
+        PG_HIP(hipMemsetAsync(d_union, 0, 8, s));
+        count_kernel<<<dim3(kSlices, nq), 256, 0, s>>>(U, nl, ix->d_off, Bkey, thr_scan, 1, cntg);
+        union_kernel<<<(nl + 255) / 256, 256, 0, s>>>(U, nl, nq, ix->d_off, Bkey, thr_scan, d_union);
+        PG_HIP(hipGetLastError());
+        unsigned long long h_union = 0;
+        PG_HIP(hipMemcpyAsync(h_cnt.data(), cntg, h_cnt.size() * 4, hipMemcpyDeviceToHost, s));
+        PG_HIP(hipMemcpyAsync(&h_union, d_union, 8, hipMemcpyDeviceToHost, s));
+        PG_HIP(hipStreamSynchronize(s));
+        union_rows = h_union;
+        uint64_t tot_scan = 0;
+        sum_counts(tot_scan, most);
+        max_scan = most;
+        if ((double)(tot_probe + tot_scan) > limit) { fb = kDense; return PG_OK; }
+        if ((rc2 = run(1, most))) return rc2;
+        pairs += tot_scan;
+        if ((rc2 = final_launch(ctx, rs.cand[cur], rs.cnt, rs.cap, nq, k, t->row_offset, d_rows, d_sc, dcount))) return rc2;
+        if (l2 && (rc2 = negate_launch(ctx, d_sc, (uint64_t)nq * k))) return rc2;
+        uint32_t h_ovf = 0;
+        PG_HIP(hipMemcpyAsync(&h_ovf, rs.overflow, 4, hipMemcpyDeviceToHost, s));
+        PG_HIP(hipMemcpyAsync(h_counts, dcount, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
+        PG_HIP(hipStreamSynchronize(s));
+        if (h_ovf) fb = kOverflow;
+        return PG_OK;
+    }();
+    if (rc == PG_OK && fb != kNone) rc = table_pass_locked(ctx, t, d_q, nq, k, d_rows, d_sc, h_counts, l2);
+    if (rc == PG_OK) tally();
+    return rc;
+}
+
+int index_check(const char* who, pg_ctx* ctx, const pg_index* ix, const void* q, const void* rows, const void* sc, uint32_t nq,
+                uint32_t k, bool l2) {
+    PG_REQUIRE(ctx && ix && q && rows && sc, "%s: NULL argument", who);
+    PG_REQUIRE(nq >= 1 && nq <= (uint32_t)kMaxQueries, "%s: nq=%u must be in [1,%d]", who, nq, kMaxQueries);
+    PG_REQUIRE(l2 || ix->dim <= 128 || nq <= 32, "%s: dim %u supports at most 32 queries per call", who, ix->dim);
+    if (k < 1 || k > 16384) {
+        set_error("%s: k=%u unsupported (1..16384)", who, k);
+        return PG_ERR_UNSUPPORTED;
+    }
+    return PG_OK;
+}
+
+int index_dev(const char* who, pg_ctx* ctx, const pg_index* ixc, const float* d_q, uint32_t nq, uint32_t k, uint64_t* d_rows, float* d_sc,
+              uint32_t* out_count, bool l2) {
+    int rc;
+    if ((rc = index_check(who, ctx, ixc, d_q, d_rows, d_sc, nq, k, l2))) return rc;
+    pg_index* ix = const_cast<pg_index*>(ixc);          // (only the statistics change)
+    std::lock_guard<std::mutex> g(ctx->mu);
+    TableRead tr(ix->t->rw);
+    uint32_t counts[kMaxQueries];
+    if ((rc = index_recall_locked(ctx, ix, d_q, nq, k, d_rows, d_sc, counts, l2))) return rc;
+    if (out_count) memcpy(out_count, counts, (size_t)nq * 4);
+    return PG_OK;
+}
+
+int index_host(const char* who, pg_ctx* ctx, const pg_index* ixc, const float* queries, uint32_t nq, uint32_t k, uint64_t* out_rows,
+               float* out_sc, uint32_t* out_count, bool l2) {
+    int rc;
+    if ((rc = index_check(who, ctx, ixc, queries, out_rows, out_sc, nq, k, l2))) return rc;
+    pg_index* ix = const_cast<pg_index*>(ixc);
+    std::lock_guard<std::mutex> g(ctx->mu);
+    TableRead tr(ix->t->rw);
+    void* buf;
+    const size_t qb = (size_t)nq * ix->dim * 4, rb = (size_t)nq * k * 8, sb = (size_t)nq * k * 4;
+    if ((rc = scratch_reserve(ctx, 5, qb + rb + sb + 64, &buf))) return rc;
+    float* d_q = (float*)buf;
+    uint64_t* d_rows = (uint64_t*)((char*)buf + ((qb + 15) & ~(size_t)15));
+    float* d_sc = (float*)((char*)d_rows + rb);
+    PG_HIP(hipMemcpyAsync(d_q, queries, qb, hipMemcpyHostToDevice, ctx->stream));
+    uint32_t counts[kMaxQueries];
+    if ((rc = index_recall_locked(ctx, ix, d_q, nq, k, d_rows, d_sc, counts, l2))) return rc;
+    PG_HIP(hipMemcpyAsync(out_rows, d_rows, rb, hipMemcpyDeviceToHost, ctx->stream));
+    PG_HIP(hipMemcpyAsync(out_sc, d_sc, sb, hipMemcpyDeviceToHost, ctx->stream));
+    PG_HIP(hipStreamSynchronize(ctx->stream));
+    if (out_count) memcpy(out_count, counts, (size_t)nq * 4);
+    return PG_OK;
+}
+
+}  // namespace
+}  // namespace pg
+
+extern "C" {
+
+int pg_index_build(pg_ctx* ctx, const pg_table* t, const pg_index_params* p, pg_index** out) {
+    PG_REQUIRE(ctx && t && out, "pg_index_build: NULL argument");
+    if (t->d_row_map) {
+        pg::set_error("pg_index_build: a view cannot be indexed (build the index over the source table)");
+        return PG_ERR_UNSUPPORTED;
+    }
+    if (t->rows >= (1ull << 32)) {
+        pg::set_error("pg_index_build: %llu rows unsupported (row ids are 32-bit)", (unsigned long long)t->rows);
+        return PG_ERR_UNSUPPORTED;
+    }
+    const pg_index_params params = p ? *p : pg_index_params{0, 0, 0, 0};
+    std::lock_guard<std::mutex> g(ctx->mu);
+    pg::TableRead tr(t->rw);
+    const auto t0 = std::chrono::steady_clock::now();
+    pg_index* ix = new pg_index();
+    ix->t = t;
+    ix->gen = t->generation.load(std::memory_order_relaxed);
+    ix->rows = t->rows;
+    ix->dim = t->dim;
+    std::vector<void*> owned, temp;
+    int rc = pg::index_build_locked(ctx, t, params, ix, owned, temp);
+    if (rc == PG_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) {
+        pg::set_error("pg_index_build: %s", hipGetErrorString(hipGetLastError()));
+        rc = PG_ERR_DEVICE;
+    }
+    if (rc != PG_OK) (void)hipStreamSynchronize(ctx->stream);
+    pg::free_all(temp);
+    if (rc != PG_OK) {
+        if (rc == PG_ERR_NOMEM) pg::set_error("pg_index_build: device allocation failed (%llu rows x %u)", (unsigned long long)t->rows, t->dim);
+        pg::free_all(owned);
+        delete ix;
+        return rc;
+    }
+    ix->st.generation = ix->gen;
+    ix->st.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    *out = ix;
+    return PG_OK;
+}
+
+int pg_index_destroy(pg_ctx* ctx, pg_index* ix) {
+    PG_REQUIRE(ctx, "pg_index_destroy: ctx is NULL");
+    if (!ix) return PG_OK;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    PG_HIP(hipStreamSynchronize(ctx->stream));
+    if (ix->d_perm) PG_HIP(hipFree(ix->d_perm));
+    if (ix->d_small) PG_HIP(hipFree(ix->d_small));
+    delete ix;
+    return PG_OK;
+}
+
+int pg_index_recall_topk(pg_ctx* ctx, const pg_index* ix, const float* queries, uint32_t nq, uint32_t k, uint64_t* out_rows,
+                         float* out_scores, uint32_t* out_count) {
+    return pg::index_host("pg_index_recall_topk", ctx, ix, queries, nq, k, out_rows, out_scores, out_count, false);
+}
+
+int pg_index_recall_topk_dev(pg_ctx* ctx, const pg_index* ix, const float* d_queries, uint32_t nq, uint32_t k, uint64_t* d_out_rows,
+                             float* d_out_scores, uint32_t* out_count) {
+    return pg::index_dev("pg_index_recall_topk_dev", ctx, ix, d_queries, nq, k, d_out_rows, d_out_scores, out_count, false);
+}
+
+int pg_index_recall_topk_l2(pg_ctx* ctx, const pg_index* ix, const float* queries, uint32_t nq, uint32_t k, uint64_t* out_rows,
+                            float* out_dist, uint32_t* out_count) {
+    return pg::index_host("pg_index_recall_topk_l2", ctx, ix, queries, nq, k, out_rows, out_dist, out_count, true);
+}
+
+int pg_index_recall_topk_l2_dev(pg_ctx* ctx, const pg_index* ix, const float* d_queries, uint32_t nq, uint32_t k, uint64_t* d_out_rows,
+                                float* d_out_dist, uint32_t* out_count) {
+    return pg::index_dev("pg_index_recall_topk_l2_dev", ctx, ix, d_queries, nq, k, d_out_rows, d_out_dist, out_count, true);
+}
+
+int pg_index_stats(const pg_index* ixc, pg_index_stats_t* out) {
+    PG_REQUIRE(ixc && out, "pg_index_stats: NULL argument");
+    pg_index* ix = const_cast<pg_index*>(ixc);
+    std::lock_guard<std::mutex> g(ix->mu);
+    *out = ix->st;
+    return PG_OK;
+}
+
+}  // extern "C"

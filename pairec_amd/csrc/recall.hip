@@ -3415,6 +3415,44 @@ int topk_merge_locked(pg_ctx* ctx, const uint64_t* d_rows, const float* d_scores
     return topk_merge_strided_locked(ctx, d_rows, d_scores, nq, nlists, per_list, ls, qs, ls, qs, k, d_out_rows, d_out_scores, d_out_count);
 }
 
+// The exact re-scoring and the squared-Euclidean helpers for callers outside this file (index.hip): the same kernels, so a
+// row scored there carries the bits the table's own pass gives it.
+int rescore_launch(pg_ctx* ctx, uint32_t dim, bool l2, const float* tab, const float* d_queries, const float* thr, const uint32_t* susp,
+                   const uint32_t* susp_cnt, uint32_t scap, uint32_t* cnt, uint64_t* cand, uint32_t* overflow, uint32_t cap, uint32_t nq,
+                   uint32_t n_rows, const float* nx, const float* nqv, uint32_t blocks) {
+    const dim3 g(blocks, nq);
+    if (l2 && dim == 64)
+        rescore_kernel<64, true><<<g, 256, 0, ctx->stream>>>(tab, d_queries, thr, susp, susp_cnt, cap, cnt, cand, overflow, scap, n_rows, nx, nqv);
+    else if (l2 && dim == 128)
+        rescore_kernel<128, true><<<g, 256, 0, ctx->stream>>>(tab, d_queries, thr, susp, susp_cnt, cap, cnt, cand, overflow, scap, n_rows, nx, nqv);
+    else if (!l2 && dim == 64)
+        rescore_kernel<64><<<g, 256, 0, ctx->stream>>>(tab, d_queries, thr, susp, susp_cnt, cap, cnt, cand, overflow, scap, n_rows);
+    else if (!l2 && dim == 128)
+        rescore_kernel<128><<<g, 256, 0, ctx->stream>>>(tab, d_queries, thr, susp, susp_cnt, cap, cnt, cand, overflow, scap, n_rows);
+    else if (!l2 && dim == 192)
+        rescore_kernel<192><<<g, 256, 0, ctx->stream>>>(tab, d_queries, thr, susp, susp_cnt, cap, cnt, cand, overflow, scap, n_rows);
+    else if (!l2 && dim == 256)
+        rescore_kernel<256><<<g, 256, 0, ctx->stream>>>(tab, d_queries, thr, susp, susp_cnt, cap, cnt, cand, overflow, scap, n_rows);
+    else {
+        set_error("rescore: dim=%u unsupported%s", dim, l2 ? " (squared Euclidean: 64 or 128)" : "");
+        return PG_ERR_UNSUPPORTED;
+    }
+    PG_HIP(hipGetLastError());
+    return PG_OK;
+}
+
+int query_norm2_launch(pg_ctx* ctx, const float* d_queries, uint32_t nq, uint32_t dim, float* d_out) {
+    query_norm2_kernel<<<1, nq, 0, ctx->stream>>>(d_queries, dim, d_out);
+    PG_HIP(hipGetLastError());
+    return PG_OK;
+}
+
+int negate_launch(pg_ctx* ctx, float* d_v, uint64_t n) {
+    negate_kernel<<<(uint32_t)((n + 255) / 256), 256, 0, ctx->stream>>>(d_v, n);
+    PG_HIP(hipGetLastError());
+    return PG_OK;
+}
+
 }  // namespace pg
 
 extern "C" {

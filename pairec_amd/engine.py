@@ -242,6 +242,57 @@ class Table:
         return counts
 
 
+class Index:
+    """Exact IVF-partitioned index over a table (pg_index_*): the same results as the table's own recalls, bit for bit, with
+    the lists that provably cannot reach a query's K-th score skipped.  The table must outlive the index."""
+
+    def __init__(self, ctx: Context, table: Table, n_lists: int = 0, train_rows: int = 0, iters: int = 0, seed: int = 0):
+        self.ctx, self.table = ctx, table
+        p = _lib.PgIndexParams(n_lists, train_rows, iters, seed)
+        h = C.c_void_p()
+        _lib.check(ctx.L.pg_index_build(ctx.h, table.h, C.byref(p), C.byref(h)))
+        self.h = h
+
+    def _recall(self, fn, queries: np.ndarray, k: int):
+        dim = self.table.dim
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, dim)
+        nq = q.shape[0]
+        rows = np.empty((nq, k), dtype=np.uint64)
+        scores = np.empty((nq, k), dtype=np.float32)
+        counts = np.zeros(nq, dtype=np.uint32)
+        per_pass = MAX_QUERIES if dim <= 128 else 32
+        for s in range(0, nq, per_pass):             # batches split as Table.recall_topk splits them
+            e = min(nq, s + per_pass)
+            r_, s_, c_ = rows[s:e], scores[s:e], counts[s:e]
+            _lib.check(fn(self.ctx.h, self.h, _ptr(q[s:e]), e - s, k, _ptr(r_), _ptr(s_), _ptr(c_)))
+        return rows, scores, counts
+
+    def recall_topk(self, queries: np.ndarray, k: int):
+        """as Table.recall_topk → (rows [nq][k] uint64 global ids, scores [nq][k] f32, counts [nq])"""
+        return self._recall(self.ctx.L.pg_index_recall_topk, queries, k)
+
+    def recall_topk_l2(self, queries: np.ndarray, k: int):
+        """as Table.recall_topk_l2 → (rows, squared Euclidean distances ascending, counts)"""
+        return self._recall(self.ctx.L.pg_index_recall_topk_l2, queries, k)
+
+    def recall_topk_dev(self, d_queries: int, nq: int, k: int, d_out_rows: int, d_out_scores: int, l2: bool = False):
+        counts = np.zeros(nq, dtype=np.uint32)
+        fn = self.ctx.L.pg_index_recall_topk_l2_dev if l2 else self.ctx.L.pg_index_recall_topk_dev
+        _lib.check(fn(self.ctx.h, self.h, C.c_void_p(d_queries), nq, k, C.c_void_p(d_out_rows), C.c_void_p(d_out_scores),
+                      _ptr(counts)))
+        return counts
+
+    def stats(self) -> dict:
+        st = _lib.PgIndexStats()
+        _lib.check(self.ctx.L.pg_index_stats(self.h, C.byref(st)))
+        return {name: getattr(st, name) for name, _ in st._fields_}
+
+    def destroy(self):
+        if self.h:
+            _lib.check(self.ctx.L.pg_index_destroy(self.ctx.h, self.h))
+            self.h = None
+
+
 def pack_dnn3(w1, b1, w2, b2, w3, b3, d_user: int) -> bytes:
     w1 = np.ascontiguousarray(w1, dtype=np.float32)
     w2 = np.ascontiguousarray(w2, dtype=np.float32)
