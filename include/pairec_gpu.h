@@ -87,7 +87,7 @@ int pg_synchronize(pg_ctx* ctx);
  * around the recall plan, its scan launches and the rank stage — pg_stats' last_*_ms and pg_last_scan_kernel_ms stop moving, a
  * small batch's step gets 40-60 us shorter; a coalescer's batches never record them, see there); for recalls through a pg_index
  * "index_dense_fraction" (default 0.01: a batch of nq queries whose live (row, query) pairs exceed this x rows x nq^0.6 takes
- * the table's pass).
+ * the table's pass), and for an attached index "index_plan_rounds" / "index_skip_batches" (see pg_index_attach).
  * value is parsed as a number. */
 int pg_set_option(pg_ctx* ctx, const char* name, const char* value);
 int pg_device_malloc(pg_ctx* ctx, size_t bytes, void** out);
@@ -445,6 +445,29 @@ typedef struct {
     uint64_t rows_live, max_query_scan_rows;
 } pg_index_stats_t;
 int pg_index_stats(const pg_index* ix, pg_index_stats_t* out);
+
+/* Serving through an index.  pg_index_attach routes every recall of ix's table that runs as a recall job through ix first: the
+ * plain calls pg_recall_topk[_l2][_dev], pg_i2i_recall and pg_online_vector_recall, a coalescer's recall / l2 / i2i / online /
+ * recommend batches, and pg_recommend_dnn3_dev / _begin / _end.  Not routed: pg_recall_topk_where (filtered), views, the shard
+ * group, and pg_index_recall_topk* (whose own fallback is the table's pass).  The index's plan is enqueued without a host
+ * synchronisation and verified with the job's status words afterwards; when it does not hold — the batch is dense, needs more
+ * rounds than "index_plan_rounds" (pg_set_option, default 2), has a non-finite query or overflows its candidate lists — the
+ * table's own plans serve the whole batch.  Outputs are bit for bit the table's.  A stale index (the table changed since the
+ * build) is skipped.  After a dense or rounds re-plan, batches of that size band (1, 2-8, 9-32, 33-64, 65-256 queries) skip
+ * the index for "index_skip_batches" batches (default 64), then try it once more.
+ *   attach   at most one index per table (a second replaces the first); PG_ERR_INVALID for a view.  Neither call bumps the
+ *            table's generation or drops its statistics; both wait until nothing enqueued reads a replaced index any more.
+ *   detach   PG_ERR_INVALID when ix is not attached.  pg_index_destroy refuses an attached index (PG_ERR_INVALID).
+ *   stats    plans tried, held and their queries; re-plans by reason; batches that never tried the plan (stale index, or the
+ *            size band switched off).  pg_index_stats' calls, queries, pairs, rows_live and fallbacks include the plans. */
+int pg_index_attach(pg_ctx* ctx, pg_index* ix);
+int pg_index_detach(pg_ctx* ctx, pg_index* ix);
+typedef struct {
+    uint64_t plans, plans_held, queries_held;
+    uint64_t replan_dense, replan_rounds, replan_overflow, replan_nonfinite;
+    uint64_t skipped_stale, skipped_switch;   /* batches that never tried the index plan */
+} pg_index_serving_stats_t;
+int pg_index_serving_stats(const pg_index* ix, pg_index_serving_stats_t* out);
 /* FM + two-tower rank straight from candidate rows: the model's item field ids are the integer columns
  * item_field_cols[n_item_fields] of `fs` (out-of-vocabulary ids are clamped as in pg_rank_fm2t_dev) */
 int pg_rank_fm2t_rows_dev(pg_ctx* ctx, const pg_model* m, const pg_features* fs, const int32_t* item_field_cols,

@@ -39,7 +39,7 @@ EXPORTS = [
     "pg_group_recommend_begin", "pg_group_recommend_end", "pg_group_info", "pg_coalescer_create_group",
     "pg_router_create", "pg_router_destroy", "pg_router_recommend", "pg_router_recall", "pg_router_stats",
     "pg_index_build", "pg_index_destroy", "pg_index_recall_topk", "pg_index_recall_topk_dev", "pg_index_recall_topk_l2",
-    "pg_index_recall_topk_l2_dev", "pg_index_stats",
+    "pg_index_recall_topk_l2_dev", "pg_index_stats", "pg_index_attach", "pg_index_detach", "pg_index_serving_stats",
 ]
 
 
@@ -65,6 +65,12 @@ class PgIndexStats(C.Structure):
                 ("pairs_scored", C.c_uint64), ("fallback_dense", C.c_uint64), ("fallback_stale", C.c_uint64),
                 ("fallback_nonfinite", C.c_uint64), ("fallback_overflow", C.c_uint64),
                 ("rows_live", C.c_uint64), ("max_query_scan_rows", C.c_uint64)]
+
+
+class PgIndexServingStats(C.Structure):
+    _fields_ = [("plans", C.c_uint64), ("plans_held", C.c_uint64), ("queries_held", C.c_uint64),
+                ("replan_dense", C.c_uint64), ("replan_rounds", C.c_uint64), ("replan_overflow", C.c_uint64),
+                ("replan_nonfinite", C.c_uint64), ("skipped_stale", C.c_uint64), ("skipped_switch", C.c_uint64)]
 
 
 class PgDppOptions(C.Structure):
@@ -150,6 +156,9 @@ def load():
         "pg_index_recall_topk_l2": [vp, vp, vp, u32, u32, vp, vp, vp],
         "pg_index_recall_topk_l2_dev": [vp, vp, vp, u32, u32, vp, vp, vp],
         "pg_index_stats": [vp, P(PgIndexStats)],
+        "pg_index_attach": [vp, vp],
+        "pg_index_detach": [vp, vp],
+        "pg_index_serving_stats": [vp, P(PgIndexServingStats)],
         "pg_topk_merge_dev": [vp, vp, vp, u32, u32, u32, u32, vp, vp],
         "pg_model_load": [vp, i32, i32, vp, sz, P(vp)],
         "pg_model_destroy": [vp, vp],

@@ -47,6 +47,8 @@ static void knobs_from_env(Knobs* k) {
     k->where_compact_min_ratio = (uint32_t)num("PG_WHERE_COMPACT_MIN_RATIO", 8);
     k->screen_early_share_narrow = (uint32_t)num("PG_SCREEN_EARLY_SHARE_NARROW", 512);
     k->index_dense_fraction = num("PG_INDEX_DENSE_FRACTION", 0.01);
+    k->index_plan_rounds = (uint32_t)num("PG_INDEX_PLAN_ROUNDS", 2);
+    k->index_skip_batches = (uint32_t)num("PG_INDEX_SKIP_BATCHES", 64);
 }
 
 static thread_local std::string g_err;
@@ -192,6 +194,8 @@ int pg_set_option(pg_ctx* ctx, const char* name, const char* value) {
     else if (n == "where_compact_min_ratio") k.where_compact_min_ratio = v >= 1 ? (uint32_t)v : 1u;
     else if (n == "screen_early_share_narrow") k.screen_early_share_narrow = (uint32_t)v;
     else if (n == "index_dense_fraction") k.index_dense_fraction = v >= 0 ? v : 0.0;
+    else if (n == "index_plan_rounds") k.index_plan_rounds = v >= 1 ? (uint32_t)v : 1u;
+    else if (n == "index_skip_batches") k.index_skip_batches = v >= 0 ? (uint32_t)v : 0u;
     else {
         pg::set_error("pg_set_option: unknown option \"%s\"", name);
         return PG_ERR_INVALID;

@@ -9,6 +9,7 @@
 #include <cstring>
 #include <map>
 #include <atomic>
+#include <memory>
 #include <mutex>
 #include <shared_mutex>
 #include <string>
@@ -94,6 +95,8 @@ struct Knobs {
     double l2_max_slack = 1.0;              // PG_L2_MAX_SLACK: largest pg_table::l2_slack the per-BLOCK cutoff is used for (above: the per-row test)
     uint32_t screen_early_share = 604;      // PG_SCREEN_EARLY_SHARE: share (x 1024) of a SIMD's blocks given to its older wave (256-query screen)
     double index_dense_fraction = 0.01;     // PG_INDEX_DENSE_FRACTION: an index recall of nq queries whose (row, query) pairs exceed this x rows x nq^0.6 is served by the table's pass
+    uint32_t index_plan_rounds = 2;         // PG_INDEX_PLAN_ROUNDS: expand / rescore / select rounds of an attached index's plan, for the probe and for the scan each
+    uint32_t index_skip_batches = 64;       // PG_INDEX_SKIP_BATCHES: after a dense or rounds re-plan, batches of that size band that skip the index plan
 };
 
 }  // namespace pg
@@ -107,6 +110,9 @@ struct pg_table {
     // bumped by every exclusive section (upload, fill, swap): a recall job remembers the value it was prepared against, and a
     // re-plan or a patch that finds another one restarts the whole batch on the new rows instead of mixing generations
     mutable std::atomic<uint64_t> generation{0};
+    // pg_index_attach: the index that every RecallJob on this table tries first (index.hip).  Written under the exclusive lock
+    // with the device drained, read under the shared lock by recall_job_prepare; neither bumps the generation.
+    mutable std::atomic<pg_index*> index{nullptr};
     float* d = nullptr;          // [rows][dim] fp32 row-major
     uint64_t rows = 0;
     uint32_t dim = 0;
@@ -305,6 +311,7 @@ struct RecallScratch {
     uint32_t* cnt_seen;      // [kMaxQueries] the candidates each query had collected when the last select kept K of them
 };
 constexpr uint32_t kRecallStatusWords = 640;
+constexpr uint32_t kIndexStatAt = 260;      // an index plan's words in a job's status block ([0, 1 + nq) as every plan's; index.hip)
 // A predicate over an integer feature column that restricts a recall's candidates (HologresVectorConf.WhereClause of the
 // reference, hologres_vector_recall.go:49-62, in the one shape the device serves: `column OP constant`).  Rows that fail it
 // never become candidates — it is applied where candidates are made (exact re-scoring, the exact scan's hit path), so every
@@ -329,6 +336,7 @@ __host__ __device__ inline bool row_filter_pass(const RowFilter& f, uint32_t row
     }
 }
 
+struct IndexServe;   // index.hip: an attached index's serving counters and switch (outlives the index while a job holds it)
 struct RecallJob {
     // set by the caller
     pg_ctx* ctx = nullptr;
@@ -346,6 +354,7 @@ struct RecallJob {
     RowFilter filter{};                     // restrict the candidates to the rows that pass (col = nullptr: none)
     uint32_t rows_qualified = 0;            // ... how many rows do (counted in recall_job_prepare)
     bool exact_only = false;                // no statistics, no shadow: the exact scan (the compact table of a selective filter)
+    bool no_index = false;                  // never through the table's attached index (its own fallback, the shard group)
     // state (recall_job_*)
     RecallScratch rs{};
     uint32_t* d_count = nullptr;
@@ -354,7 +363,7 @@ struct RecallJob {
     bool screen4 = false;                   // the pilot plan's full pass streams the 4-bit shadow (nq <= kI4MaxQueries)
     bool stage2 = false;                    // the int8 screen's suspects pass the two-digit refinement (recall_r2.hip) before the exact re-scoring
     bool screen4m = false;                  // ... through the matrix pipe, suspects thinned on the int8 shadow (kI4MaxQueries < nq <= kI4mMaxQueries)
-    int plans[4] = {0, 0, 0, 0};
+    int plans[5] = {0, 0, 0, 0, 0};
     bool predict = false;                   // plans[0] takes its first thresholds from the table's threshold model
     bool pred_observe = false;              // the table has a model: this job contributes its observed quantiles
     bool observed = false;                  // ... and the enqueued plan did
@@ -374,7 +383,11 @@ struct RecallJob {
     // sample threshold was too high).  A handful can be re-run one by one instead of re-running the whole batch.
     std::vector<uint32_t> failed;
     uint64_t table_gen = 0;                 // t->generation when the job was prepared (the statistics, shadow and plans are that version's)
+    // plans[0] = kIndexPlan: the attached index (read under the shared lock of the enqueue) and its counters (read by the check)
+    const pg_index* ix = nullptr;
+    std::shared_ptr<IndexServe> ix_serve;
 };
+constexpr int kIndexPlan = 100;             // the plan id of an attached index's plan (recall.hip's own plans are 0 .. 3)
 constexpr size_t kMaxPatchQueries = 8;
 // All four: caller holds ctx->mu.  prepare may synchronise once (a table's statistics / shadow on first use).
 int recall_job_prepare(RecallJob* j);
@@ -383,7 +396,13 @@ int recall_job_check(RecallJob* j, bool* ok);         // after the stream passed
 void recall_job_finish(RecallJob* j);                 // publish timing / counters into ctx
 int recall_dev_locked(pg_ctx* ctx, const pg_table* t, const float* d_queries, uint32_t nq, uint32_t k,
                       uint64_t* d_out_rows, float* d_out_scores, uint32_t* out_count, uint32_t* d_out_count,
-                      bool skip_pilot = false, bool l2 = false, const RowFilter* filter = nullptr, bool exact_only = false);
+                      bool skip_pilot = false, bool l2 = false, const RowFilter* filter = nullptr, bool exact_only = false,
+                      bool no_index = false);
+// index.hip: the attached index's plan in front of the table's plans (recall_job_prepare, after the table's plans are made), its
+// enqueue-only launches and status copy (recall_job_enqueue) and its verdict (recall_job_check; *ok = false: the table's plans follow)
+int index_plan_prepare(RecallJob* j);
+int index_plan_enqueue(RecallJob* j, uint32_t status_words);
+int index_plan_check(RecallJob* j, bool* ok);
 // re-run the failed queries of `j` (at most kMaxPatchQueries) one by one, synchronously, writing into their slices of
 // the job's outputs and their valid counts into counts[q]; caller holds ctx->mu
 int recall_patch_failed_locked(RecallJob* j, uint32_t* counts);

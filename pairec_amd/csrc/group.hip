@@ -436,6 +436,7 @@ int step_enqueue(pg_group* g, pg_group_ticket* tk, uint32_t attempt) {
             j.d_out_scores = (float*)(l.d_own + rb);
             j.h_status = l.run->h_status;
             j.events = &l.run->events;
+            j.no_index = true;                 // (the shard group serves through no index)
             if ((rc = recall_job_prepare(&j))) return rc;
         }
         if ((rc = recall_job_enqueue(&j))) return rc;

@@ -14,12 +14,30 @@
 //   select   recall.hip's select / final kernels: the same keys (score totalOrder descending, then row ascending) as the table pass
 // Every row is scored by recall.hip's rescore_kernel — the specification's k-ascending fmaf chain — so its bits are the table
 // pass's bits; pruning drops only lists whose bound proves that none of their rows can reach thr_q.
+//
+// Serving (pg_index_attach): the same search as a RecallJob plan that is only enqueued.  What the synchronous
+// path decides on the host between its launches — the dense fallback, the number of rounds, a non-finite query — a plan kernel
+// decides on the device; every round's kernels read its verdict and return at once when there is nothing (more) to do, and
+// recall_job_check reads it with the job's status words and moves to the table's own plans when a flag is set.
 #include "common.hpp"
 
 #include <hipcub/hipcub.hpp>
 
 #include <chrono>
 #include <cmath>
+
+namespace pg {
+// an attached index's serving counters and its switch, shared with the jobs that tried it (a job's check may come after a
+// detach and destroy: the jobs keep this alive, not the index)
+constexpr int kBands = 5;                  // batch sizes 1, 2-8, 9-32, 33-64, 65-256
+struct IndexServe {
+    std::atomic<uint64_t> plans{0}, plans_held{0}, queries_held{0};
+    std::atomic<uint64_t> replan_dense{0}, replan_rounds{0}, replan_overflow{0}, replan_nonfinite{0};
+    std::atomic<uint64_t> skipped_stale{0}, skipped_switch{0};
+    std::atomic<uint64_t> queries{0}, pairs{0}, rows_live{0}, max_scan{0};
+    std::atomic<int32_t> skip[kBands] = {};   // batches of the band that skip the index plan before it is tried again
+};
+}  // namespace pg
 
 struct pg_index {
     const pg_table* t = nullptr;
@@ -34,7 +52,8 @@ struct pg_index {
     float* d_rad = nullptr;       // [n_lists] r_L, rounded up
     void* d_small = nullptr;      // the allocation behind d_off / d_cent / d_cnorm / d_rad
     std::mutex mu;                // guards st
-    pg_index_stats_t st{};
+    pg_index_stats_t st{};        // the synchronous pg_index_recall_topk* calls (the attached plans count in serve)
+    std::shared_ptr<pg::IndexServe> serve = std::make_shared<pg::IndexServe>();
 };
 
 namespace pg {
@@ -43,6 +62,19 @@ namespace {
 constexpr uint32_t kMaxLists = 65536;
 constexpr uint32_t kSlices = 256;        // list slices of the count / expand kernels (per query)
 constexpr uint32_t kBoundQ = 8;          // queries per bound-kernel block
+
+// the verdict of an index plan, written by the device (index_plan_kernel) and read by every later launch of the plan, then
+// copied into the job's status words at kIndexStatAt
+struct IndexPlanWords {
+    uint32_t flags;                      // kPlanNonfinite | kPlanDense | kPlanRounds: the table's plans serve the batch
+    uint32_t need[2];                    // rounds the probe (0) and the scan (1) take
+    uint32_t pad;
+    unsigned long long pairs[2];         // (row, query) pairs of the probe and the scan
+    unsigned long long union_rows;       // rows of the lists live for some query (union_kernel)
+    unsigned long long max_scan;         // the most rows one query's scan scores
+};
+static_assert(sizeof(IndexPlanWords) == 48, "12 status words");
+constexpr uint32_t kPlanNonfinite = 1u, kPlanDense = 2u, kPlanRounds = 4u;
 
 __device__ __forceinline__ uint32_t ukey(float f) {      // order-preserving bits (totalOrder for non-NaN)
     const uint32_t b = __float_as_uint(f);
@@ -361,18 +393,25 @@ __global__ __launch_bounds__(256) void count_kernel(const float* __restrict__ U,
     if (threadIdx.x == 0) cnt[(size_t)q * kSlices + g] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
 }
 
-// the rows of the selected lists, in (slice, list) order, positions [skip, skip + scap) of that sequence → susp[q][0, scap)
+// the rows of the selected lists, in (slice, list) order, positions [round x scap, (round + 1) x scap) of that sequence →
+// susp[q][0, scap).  pw (an index plan): nothing to do once a flag is set or past the rounds the plan kernel counted — the round's
+// suspect lists are left empty, so its re-scoring returns at once.
 __global__ __launch_bounds__(256) void expand_kernel(const float* __restrict__ U, uint32_t nl, const uint32_t* __restrict__ off,
                                                      const uint32_t* __restrict__ perm, const uint32_t* __restrict__ Bkey,
                                                      const float* __restrict__ thr, int mode, const uint32_t* __restrict__ cnt,
-                                                     uint64_t skip, uint32_t scap, uint32_t* __restrict__ susp,
-                                                     uint32_t* __restrict__ susp_cnt) {
+                                                     uint32_t round, uint32_t scap, uint32_t* __restrict__ susp,
+                                                     uint32_t* __restrict__ susp_cnt, const IndexPlanWords* __restrict__ pw) {
     __shared__ uint32_t sc[256];
     __shared__ uint32_t e_start[256], e_len[256];
     __shared__ long long e_dst[256];
     __shared__ uint32_t s_n;
     __shared__ long long s_base;
     const uint32_t q = blockIdx.y, g = blockIdx.x, tid = threadIdx.x;
+    if (pw && (pw->flags != 0u || round >= pw->need[mode])) {        // (the same for the whole block)
+        if (g == 0 && tid == 0) susp_cnt[q] = 0u;
+        return;
+    }
+    const uint64_t skip = (uint64_t)round * scap;
     if (tid == 0) {
         unsigned long long before = 0, total = 0;
         for (uint32_t i = 0; i < kSlices; ++i) {
@@ -450,6 +489,58 @@ __global__ __launch_bounds__(256) void union_kernel(const float* __restrict__ U,
     }
     for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
     if ((threadIdx.x & 63) == 0 && s) atomicAdd(out, s);
+}
+
+// an index plan: thresholds, counts and the overflow word as index_init_kernel, and the plan's words cleared
+__global__ void index_plan_init_kernel(float* __restrict__ thr, uint32_t* __restrict__ cnt, uint32_t* __restrict__ overflow,
+                                       IndexPlanWords* __restrict__ pw) {
+    const uint32_t i = threadIdx.x;
+    thr[i] = -__builtin_inff();
+    cnt[i] = 0u;
+    if (i == 0) *overflow = 0u;
+    if (i < sizeof(IndexPlanWords) / 4) reinterpret_cast<uint32_t*>(pw)[i] = 0u;
+}
+
+// the host decisions of index_recall_locked, on the device (launched <<<1, kMaxQueries>>> after the count of `mode`): the
+// (row, query) pairs of the batch, the dense rule against `limit` (the probe's pairs, then probe + scan), and the rounds of
+// scap suspects the query with the most rows needs — more than `budget` of them is a flag too
+__global__ __launch_bounds__(256) void index_plan_kernel(const uint32_t* __restrict__ cnt, uint32_t nq, int mode, uint32_t scap,
+                                                         uint32_t budget, double limit, IndexPlanWords* __restrict__ pw) {
+    __shared__ unsigned long long s_tot[4], s_max[4];
+    const uint32_t q = threadIdx.x;
+    unsigned long long v = 0;
+    if (q < nq)
+        for (uint32_t g = 0; g < kSlices; ++g) v += cnt[(size_t)q * kSlices + g];
+    unsigned long long tot = v, mx = v;
+    for (int o = 32; o > 0; o >>= 1) {
+        tot += __shfl_xor(tot, o);
+        const unsigned long long om = __shfl_xor(mx, o);
+        mx = om > mx ? om : mx;
+    }
+    if ((q & 63) == 0) { s_tot[q >> 6] = tot; s_max[q >> 6] = mx; }
+    __syncthreads();
+    if (q != 0) return;
+    tot = s_tot[0] + s_tot[1] + s_tot[2] + s_tot[3];
+    mx = s_max[0];
+    for (int w = 1; w < 4; ++w) mx = s_max[w] > mx ? s_max[w] : mx;
+    const unsigned long long need = (mx + scap - 1) / scap;
+    uint32_t f = 0;
+    if ((double)(mode == 0 ? tot : pw->pairs[0] + tot) > limit) f |= kPlanDense;
+    if (need > budget) f |= kPlanRounds;
+    pw->pairs[mode] = tot;
+    pw->need[mode] = (uint32_t)(need < budget ? need : budget);
+    if (mode == 1) pw->max_scan = mx;
+    if (f) pw->flags |= f;
+}
+
+// the status block of an index plan (<<<1, kMaxQueries>>>): [0] the re-scoring's overflow flag, [1 + q] valid counts (as every
+// plan's), [kIndexStatAt, + 12) the plan's words
+__global__ void index_status_kernel(const uint32_t* __restrict__ overflow, uint32_t nq, const IndexPlanWords* __restrict__ pw,
+                                    uint32_t* __restrict__ out) {
+    const uint32_t t = threadIdx.x;
+    out[1 + t] = t < nq ? overflow[1 + t] : 0u;
+    if (t < sizeof(IndexPlanWords) / 4) out[kIndexStatAt + t] = reinterpret_cast<const uint32_t*>(pw)[t];
+    if (t == 0) out[0] = overflow[0];
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------
@@ -645,15 +736,45 @@ int index_scratch(pg_ctx* ctx, size_t bytes, void** out) {
     return PG_OK;
 }
 
+// slot 17 of one batch: U [nq][nl] | qn [nq] f64 | nqv [nq] | Bkey [nq] | probe rows [nq] | counts [nq] | flag, union / the plan's
+//          words [16] | slice counts [nq][kSlices] | scan threshold [nq]
+struct SearchBufs {
+    float* U;
+    double* qn;
+    float* nqv;
+    uint32_t *Bkey, *probe, *dcount, *flag, *cntg;
+    float* thr_scan;                     // the probe's K-th scores, frozen for the scan's list selection
+};
+size_t search_bytes(uint32_t nq, uint32_t nl) {
+    const size_t u_b = ((size_t)nq * nl * 4 + 255) & ~(size_t)255;
+    return u_b + (size_t)nq * (8 + 4 + 4 + 4 + 4 + 4) + (size_t)nq * kSlices * 4 + 1024;
+}
+int search_bufs(pg_ctx* ctx, uint32_t nq, uint32_t nl, SearchBufs* b) {
+    const size_t u_b = ((size_t)nq * nl * 4 + 255) & ~(size_t)255;
+    void* base;
+    if (index_scratch(ctx, search_bytes(nq, nl), &base)) return PG_ERR_NOMEM;
+    b->U = (float*)base;
+    b->qn = (double*)((char*)base + u_b);
+    b->nqv = (float*)(b->qn + nq);
+    b->Bkey = (uint32_t*)(b->nqv + nq);
+    b->probe = b->Bkey + nq;
+    b->dcount = b->probe + nq;
+    b->flag = b->dcount + nq;            // (8-byte aligned: u_b + 24 nq)
+    b->cntg = b->flag + 16;
+    b->thr_scan = (float*)(b->cntg + (size_t)nq * kSlices);
+    return PG_OK;
+}
+
 enum Fallback { kNone = 0, kDense, kStale, kNonfinite, kOverflow };
 
 int table_pass_locked(pg_ctx* ctx, const pg_table* t, const float* d_q, uint32_t nq, uint32_t k, uint64_t* d_rows, float* d_sc,
                       uint32_t* h_counts, bool l2) {
-    if (!l2) return recall_dev_locked(ctx, t, d_q, nq, k, d_rows, d_sc, h_counts, nullptr);
+    // (never through an attached index: this is the index's own fallback)
+    if (!l2) return recall_dev_locked(ctx, t, d_q, nq, k, d_rows, d_sc, h_counts, nullptr, false, false, nullptr, false, true);
     for (uint32_t q0 = 0; q0 < nq; q0 += 128) {       // (as pg_recall_topk_l2_dev: at most 128 queries per job)
         const uint32_t n = nq - q0 < 128 ? nq - q0 : 128;
         const int rc = recall_dev_locked(ctx, t, d_q + (size_t)q0 * t->dim, n, k, d_rows + (size_t)q0 * k, d_sc + (size_t)q0 * k,
-                                         h_counts + q0, nullptr, false, true);
+                                         h_counts + q0, nullptr, false, true, nullptr, false, true);
         if (rc) return rc;
     }
     return PG_OK;
@@ -688,24 +809,17 @@ int index_recall_locked(pg_ctx* ctx, pg_index* ix, const float* d_q, uint32_t nq
         int rc2;
         if ((rc2 = recall_scratch(ctx, dim, k, &rs))) return rc2;
         if (l2 && (rc2 = ensure_table_nx(ctx, t))) return rc2;
-        // slot 17: U [nq][nl] | qn [nq] f64 | nqv [nq] | Bkey [nq] | probe rows [nq] | counts [nq] | flag, union [16] |
-        //          slice counts [nq][kSlices] | scan threshold [nq]
-        const size_t u_b = ((size_t)nq * nl * 4 + 255) & ~(size_t)255;
-        void* base;
-        if (index_scratch(ctx, u_b + (size_t)nq * (8 + 4 + 4 + 4 + 4 + 4) + (size_t)nq * kSlices * 4 + 1024, &base)) {
+        SearchBufs sb;
+        if (search_bufs(ctx, nq, nl, &sb)) {
             fb = kOverflow;
             return PG_OK;
         }
-        float* U = (float*)base;
-        double* qn = (double*)((char*)base + u_b);
-        float* nqv = (float*)(qn + nq);
-        uint32_t* Bkey = (uint32_t*)(nqv + nq);
-        uint32_t* probe = Bkey + nq;
-        uint32_t* dcount = probe + nq;
-        uint32_t* flag = dcount + nq;
+        float* U = sb.U;
+        double* qn = sb.qn;
+        float* nqv = sb.nqv;
+        uint32_t *Bkey = sb.Bkey, *probe = sb.probe, *dcount = sb.dcount, *flag = sb.flag, *cntg = sb.cntg;
         unsigned long long* d_union = (unsigned long long*)(flag + 2);
-        uint32_t* cntg = flag + 16;
-        float* thr_scan = (float*)(cntg + (size_t)nq * kSlices);   // the probe's K-th scores, frozen for the scan's list selection
+        float* thr_scan = sb.thr_scan;
         hipStream_t s = ctx->stream;
         index_init_kernel<<<1, kMaxQueries, 0, s>>>(rs.thr, rs.cnt, rs.overflow, flag);
         qinfo_kernel<<<nq, 64, 0, s>>>(d_q, dim, qn, flag);
@@ -748,8 +862,8 @@ int index_recall_locked(pg_ctx* ctx, pg_index* ix, const float* d_q, uint32_t nq
         auto run = [&](int mode, uint64_t most_q) -> int {
             for (uint64_t skip = 0; skip < most_q; skip += scap) {
                 const uint64_t this_round = std::min<uint64_t>(most_q - skip, scap);
-                expand_kernel<<<dim3(kSlices, nq), 256, 0, s>>>(U, nl, ix->d_off, ix->d_perm, Bkey, thr_scan, mode, cntg, skip, scap,
-                                                                 rs.susp, rs.susp_cnt);
+                expand_kernel<<<dim3(kSlices, nq), 256, 0, s>>>(U, nl, ix->d_off, ix->d_perm, Bkey, thr_scan, mode, cntg,
+                                                                 (uint32_t)(skip / scap), scap, rs.susp, rs.susp_cnt, nullptr);
                 PG_HIP(hipGetLastError());
                 uint32_t blocks = (uint32_t)((this_round + 1023) / 1024);
                 const uint32_t most_blocks = std::max<uint32_t>(16u, 4096u / nq);
@@ -846,7 +960,155 @@ int index_host(const char* who, pg_ctx* ctx, const pg_index* ixc, const float* q
     return PG_OK;
 }
 
+int band_of(uint32_t nq) { return nq <= 1 ? 0 : nq <= 8 ? 1 : nq <= 32 ? 2 : nq <= 64 ? 3 : 4; }
+
 }  // namespace
+
+// ---- an attached index as a RecallJob plan ------------------------------------------------------------------------
+// In front of the table's plans when the table has an attachment that is current and finite, and the job is one the index
+// serves (no filter, not exact_only, not a view, not the index's own fallback or the shard group); the batch's size band may
+// be switched off for a while (index_plan_check).  Caller holds ctx->mu and the table's shared lock.
+int index_plan_prepare(RecallJob* j) {
+    const pg_table* t = j->t;
+    j->ix = nullptr;
+    j->ix_serve.reset();
+    pg_index* ix = t->index.load(std::memory_order_acquire);
+    if (!ix || j->no_index || j->filter.col || j->exact_only || j->skip_pilot || t->d_row_map) return PG_OK;
+    IndexServe& sv = *ix->serve;
+    if (t->generation.load(std::memory_order_relaxed) != ix->gen) {
+        sv.skipped_stale++;
+        return PG_OK;
+    }
+    if (ix->nonfinite || j->k > 16384 || (j->l2 && t->dim != 64 && t->dim != 128) || (!j->l2 && t->dim > 128 && j->nq > 32)) return PG_OK;
+    std::atomic<int32_t>& sw = sv.skip[band_of(j->nq)];
+    int32_t left = sw.load(std::memory_order_relaxed);
+    while (left > 0 && !sw.compare_exchange_weak(left, left - 1, std::memory_order_relaxed)) {}
+    if (left > 0) {
+        sv.skipped_switch++;
+        return PG_OK;
+    }
+    void* base;
+    if (index_scratch(j->ctx, search_bytes(j->nq, ix->n_lists), &base)) return PG_OK;     // (no memory: the table's plans)
+    for (int i = j->n_plans; i > 0; --i) j->plans[i] = j->plans[i - 1];
+    j->plans[0] = kIndexPlan;
+    j->n_plans++;
+    j->next_plan = 0;
+    j->ix = ix;
+    j->ix_serve = ix->serve;
+    return PG_OK;
+}
+
+// index_recall_locked's launches without its three synchronisations: a fixed number of rounds (index_plan_rounds) for the probe
+// and for the scan, whose kernels read the plan kernel's verdict; the outputs, the status block and its copy as any plan's
+int index_plan_enqueue(RecallJob* j, uint32_t status_words) {
+    pg_ctx* ctx = j->ctx;
+    const pg_table* t = j->t;
+    const pg_index* ix = j->ix;
+    const uint32_t nq = j->nq, k = j->k, nl = ix->n_lists, dim = t->dim;
+    const bool l2 = j->l2;
+    const float* d_q = j->d_queries;
+    RecallScratch& rs = j->rs;
+    hipStream_t s = ctx->stream;
+    int rc;
+    SearchBufs sb;
+    if ((rc = search_bufs(ctx, nq, nl, &sb))) return rc;      // (reserved by index_plan_prepare: only grows)
+    IndexPlanWords* pw = reinterpret_cast<IndexPlanWords*>(sb.flag);
+    while (j->events->size() < 2) {
+        hipEvent_t e;
+        PG_HIP(hipEventCreate(&e));
+        j->events->push_back(e);
+    }
+    j->timers = !ctx->timers_off;
+    if (j->timers) PG_HIP(hipEventRecord((*j->events)[0], s));
+    index_plan_init_kernel<<<1, kMaxQueries, 0, s>>>(rs.thr, rs.cnt, rs.overflow, pw);
+    qinfo_kernel<<<nq, 64, 0, s>>>(d_q, dim, sb.qn, &pw->flags);
+    PG_HIP(hipGetLastError());
+    if (l2 && (rc = query_norm2_launch(ctx, d_q, nq, dim, sb.nqv))) return rc;
+    const dim3 bg((nl + 255) / 256, (nq + kBoundQ - 1) / kBoundQ);
+    const size_t blds = (size_t)kBoundQ * dim * 8;
+    if (l2) bound_kernel<true><<<bg, 256, blds, s>>>(d_q, nq, dim, sb.qn, ix->d_cent, ix->d_cnorm, ix->d_rad, nl, sb.U);
+    else bound_kernel<false><<<bg, 256, blds, s>>>(d_q, nq, dim, sb.qn, ix->d_cent, ix->d_cnorm, ix->d_rad, nl, sb.U);
+    probe_kernel<<<nq, 1024, 0, s>>>(sb.U, nl, ix->d_off, ix->rows, k, sb.Bkey, sb.probe);
+    count_kernel<<<dim3(kSlices, nq), 256, 0, s>>>(sb.U, nl, ix->d_off, sb.Bkey, rs.thr, 0, sb.cntg);
+    PG_HIP(hipGetLastError());
+    // (the limit of index_recall_locked, computed the same way)
+    const double limit = ctx->knobs.index_dense_fraction * (double)ix->rows * std::pow((double)nq, 0.6);
+    const uint32_t budget = ctx->knobs.index_plan_rounds ? ctx->knobs.index_plan_rounds : 1u;
+    const uint32_t scap = rs.cap - k;
+    // one grid for every round: as many blocks as the largest round needs (the blocks past a round's suspects return at once)
+    const uint32_t blocks = std::max<uint32_t>(1u, std::min<uint32_t>(std::max<uint32_t>(16u, 4096u / nq), (scap + 1023) / 1024));
+    int cur = 0;
+    auto rounds = [&](int mode) -> int {
+        index_plan_kernel<<<1, kMaxQueries, 0, s>>>(sb.cntg, nq, mode, scap, budget, limit, pw);
+        PG_HIP(hipGetLastError());
+        for (uint32_t r = 0; r < budget; ++r) {
+            expand_kernel<<<dim3(kSlices, nq), 256, 0, s>>>(sb.U, nl, ix->d_off, ix->d_perm, sb.Bkey, sb.thr_scan, mode, sb.cntg, r, scap,
+                                                             rs.susp, rs.susp_cnt, pw);
+            PG_HIP(hipGetLastError());
+            int rc3;
+            if ((rc3 = rescore_launch(ctx, dim, l2, t->d, d_q, rs.thr, rs.susp, rs.susp_cnt, scap, rs.cnt, rs.cand[cur], rs.overflow, rs.cap,
+                                      nq, (uint32_t)ix->rows, l2 ? t->d_nx : nullptr, l2 ? sb.nqv : nullptr, blocks)))
+                return rc3;
+            // (a round without suspects selects the kept list again: the same K keys, the same threshold)
+            if ((rc3 = launch_select(ctx, nq, rs.cand[cur], rs.cand[cur ^ 1], rs.cnt, rs.thr, rs.cap, k, 0))) return rc3;
+            cur ^= 1;
+        }
+        return PG_OK;
+    };
+    if ((rc = rounds(0))) return rc;
+    // the scan's lists, chosen once against the probe's thresholds (thr_scan)
+    PG_HIP(hipMemcpyAsync(sb.thr_scan, rs.thr, (size_t)nq * 4, hipMemcpyDeviceToDevice, s));
+    count_kernel<<<dim3(kSlices, nq), 256, 0, s>>>(sb.U, nl, ix->d_off, sb.Bkey, sb.thr_scan, 1, sb.cntg);
+    union_kernel<<<(nl + 255) / 256, 256, 0, s>>>(sb.U, nl, nq, ix->d_off, sb.Bkey, sb.thr_scan, &pw->union_rows);
+    PG_HIP(hipGetLastError());
+    if ((rc = rounds(1))) return rc;
+    if ((rc = final_launch(ctx, rs.cand[cur], rs.cnt, rs.cap, nq, k, t->row_offset, j->d_out_rows, j->d_out_scores, j->d_count))) return rc;
+    if (l2 && (rc = negate_launch(ctx, j->d_out_scores, (uint64_t)nq * k))) return rc;
+    if (j->timers) PG_HIP(hipEventRecord((*j->events)[1], s));
+    index_status_kernel<<<1, kMaxQueries, 0, s>>>(rs.overflow, nq, pw, rs.status);
+    PG_HIP(hipGetLastError());
+    if (j->d_out_count) PG_HIP(hipMemcpyAsync(j->d_out_count, j->d_count, 4 * (size_t)nq, hipMemcpyDeviceToDevice, s));
+    PG_HIP(hipMemcpyAsync(j->h_status, rs.status, 4 * (size_t)status_words, hipMemcpyDeviceToHost, s));
+    j->n_ev = 1;
+    j->refined = j->observed = j->susp_stat = j->stat_wide = false;
+    j->enqueued_plan = kIndexPlan;
+    j->next_plan++;
+    return PG_OK;
+}
+
+// the verdict of an enqueued index plan (its status words have arrived): held, or a reason to let the table's first plan serve
+// the whole batch — dense and rounds also switch the batch's size band off for index_skip_batches batches
+int index_plan_check(RecallJob* j, bool* ok) {
+    IndexServe& sv = *j->ix_serve;
+    IndexPlanWords w;
+    memcpy(&w, j->h_status + kIndexStatAt, sizeof w);
+    sv.plans++;
+    sv.queries += j->nq;
+    j->failed.clear();
+    *ok = false;
+    if (w.flags & kPlanNonfinite) {
+        sv.replan_nonfinite++;
+    } else if (w.flags & (kPlanDense | kPlanRounds)) {
+        if (w.flags & kPlanDense) sv.replan_dense++;
+        else sv.replan_rounds++;
+        sv.skip[band_of(j->nq)].store((int32_t)std::min<uint32_t>(j->ctx->knobs.index_skip_batches, 0x7FFFFFFFu), std::memory_order_relaxed);
+    } else if (j->h_status[0] != 0) {
+        sv.replan_overflow++;
+    } else {
+        *ok = true;
+        sv.plans_held++;
+        sv.queries_held += j->nq;
+        sv.pairs += w.pairs[0] + w.pairs[1];
+        sv.rows_live += w.union_rows;
+        uint64_t m = sv.max_scan.load(std::memory_order_relaxed);
+        while (w.max_scan > m && !sv.max_scan.compare_exchange_weak(m, w.max_scan, std::memory_order_relaxed)) {}
+    }
+    if (j->ctx->knobs.debug_scan)
+        fprintf(stderr, "[pg] index plan %s: flags %u, rounds %u + %u, pairs %llu + %llu\n", *ok ? "held" : "re-planned", w.flags, w.need[0],
+                w.need[1], w.pairs[0], w.pairs[1]);
+    return PG_OK;
+}
+
 }  // namespace pg
 
 extern "C" {
@@ -893,6 +1155,7 @@ int pg_index_build(pg_ctx* ctx, const pg_table* t, const pg_index_params* p, pg_
 int pg_index_destroy(pg_ctx* ctx, pg_index* ix) {
     PG_REQUIRE(ctx, "pg_index_destroy: ctx is NULL");
     if (!ix) return PG_OK;
+    PG_REQUIRE(ix->t->index.load(std::memory_order_acquire) != ix, "pg_index_destroy: the index is attached to its table (pg_index_detach first)");
     std::lock_guard<std::mutex> g(ctx->mu);
     PG_HIP(hipStreamSynchronize(ctx->stream));
     if (ix->d_perm) PG_HIP(hipFree(ix->d_perm));
@@ -926,6 +1189,61 @@ int pg_index_stats(const pg_index* ixc, pg_index_stats_t* out) {
     pg_index* ix = const_cast<pg_index*>(ixc);
     std::lock_guard<std::mutex> g(ix->mu);
     *out = ix->st;
+    // (+ the batches that tried the attached plan; `rounds` re-plans have no field of their own here)
+    const pg::IndexServe& sv = *ix->serve;
+    const uint64_t pairs = sv.pairs.load();
+    out->calls += sv.plans.load();
+    out->queries += sv.queries.load();
+    out->rows_scored += pairs;
+    out->pairs_scored += pairs;
+    out->rows_live += sv.rows_live.load();
+    out->max_query_scan_rows = std::max<uint64_t>(out->max_query_scan_rows, sv.max_scan.load());
+    out->fallback_dense += sv.replan_dense.load();
+    out->fallback_nonfinite += sv.replan_nonfinite.load();
+    out->fallback_overflow += sv.replan_overflow.load();
+    return PG_OK;
+}
+
+// Attach / detach change no rows: the table's lock is taken exclusively WITHOUT a generation bump (TableWrite's), and the
+// device is drained so that nothing enqueued still reads a previous attachment's arrays.
+int pg_index_attach(pg_ctx* ctx, pg_index* ix) {
+    PG_REQUIRE(ctx && ix, "pg_index_attach: NULL argument");
+    PG_REQUIRE(!ix->t->d_row_map, "pg_index_attach: the table is a view");
+    std::lock_guard<std::mutex> g(ctx->mu);
+    std::unique_lock<std::shared_mutex> w(ix->t->rw);
+    pg_index* prev = ix->t->index.load(std::memory_order_acquire);
+    if (prev == ix) return PG_OK;
+    if (prev) {
+        PG_HIP(hipSetDevice(ctx->device));
+        PG_HIP(hipDeviceSynchronize());
+    }
+    ix->t->index.store(ix, std::memory_order_release);
+    return PG_OK;
+}
+
+int pg_index_detach(pg_ctx* ctx, pg_index* ix) {
+    PG_REQUIRE(ctx && ix, "pg_index_detach: NULL argument");
+    std::lock_guard<std::mutex> g(ctx->mu);
+    std::unique_lock<std::shared_mutex> w(ix->t->rw);
+    PG_REQUIRE(ix->t->index.load(std::memory_order_acquire) == ix, "pg_index_detach: the index is not attached");
+    PG_HIP(hipSetDevice(ctx->device));
+    PG_HIP(hipDeviceSynchronize());
+    ix->t->index.store(nullptr, std::memory_order_release);
+    return PG_OK;
+}
+
+int pg_index_serving_stats(const pg_index* ix, pg_index_serving_stats_t* out) {
+    PG_REQUIRE(ix && out, "pg_index_serving_stats: NULL argument");
+    const pg::IndexServe& sv = *ix->serve;
+    out->plans = sv.plans.load();
+    out->plans_held = sv.plans_held.load();
+    out->queries_held = sv.queries_held.load();
+    out->replan_dense = sv.replan_dense.load();
+    out->replan_rounds = sv.replan_rounds.load();
+    out->replan_overflow = sv.replan_overflow.load();
+    out->replan_nonfinite = sv.replan_nonfinite.load();
+    out->skipped_stale = sv.skipped_stale.load();
+    out->skipped_switch = sv.skipped_switch.load();
     return PG_OK;
 }
 

@@ -2251,6 +2251,8 @@ constexpr uint32_t kI4mStatAt = 272;          // [272] the (row, query) pairs th
                                               // [+3] pairs that reached the exact re-scoring, [+4] candidates the pass collected
 constexpr uint32_t kStatusCopyWords = kI4mStatAt + 5;
 static_assert(kStatusCopyWords <= 300 && kStatusCopyWords <= kRecallStatusWords, "the status block ends in front of the words other calls keep in ctx->h_status");
+// (an index plan has none of the words above: its own twelve take their place, index.hip)
+static_assert(kIndexStatAt > kMaxQueries && kIndexStatAt + 12 <= kStatusCopyWords, "an index plan's status words");
 
 // (launched <<<1, kMaxQueries>>>; null pointers = words that stay zero)
 __global__ void status_pack_kernel(const uint32_t* __restrict__ overflow, uint32_t nq, uint32_t rec_ovf_word,
@@ -2681,6 +2683,7 @@ int recall_job_prepare(RecallJob* j) {
     j->plans[j->n_plans++] = kGrow;
     j->plans[j->n_plans++] = kSafe;
     if (j->skip_pilot && j->plans[0] == kPilot) j->next_plan = 1;    // the re-run of a query a sampled threshold failed
+    static_assert(kIndexPlan != kPilot && kIndexPlan != kGrow && kIndexPlan != kSafe && kIndexPlan != kPredict, "plan ids");
     // small batches: the pilot plan's full pass is HBM-bound on the shadow it streams — use the 4-bit one (recall_i4.hip)
     if (screen && t->dim == 128 && j->nq <= kI4MaxQueries && j->plans[0] == kPilot && !kn.no_screen_i4 &&
         rows >= kn.i4_min_rows && (uint64_t)kMaxQueries * rs_cap_bound(j->k) / kI4MaxQueries < 0xFFFFFFFFull) {
@@ -2747,7 +2750,9 @@ int recall_job_prepare(RecallJob* j) {
             }
         }
     }
-    return PG_OK;
+    // a table with an attached index: its plan goes in front of everything above (index.hip; the plans above stay as they are
+    // and serve the batch when it does not hold)
+    return index_plan_prepare(j);
 }
 
 namespace {
@@ -3001,6 +3006,7 @@ int recall_job_enqueue(RecallJob* j) {
     // here long after it): fetch the pointers again rather than trust the cached ones
     if ((rc = recall_scratch(ctx, t->dim, j->k, &j->rs))) return rc;
     j->d_count = j->rs.overflow + 1;
+    if (plan == kIndexPlan) return index_plan_enqueue(j, kStatusCopyWords);
     PlanRun r(j);
     RecallScratch& rs = j->rs;
     recall_init_kernel<<<(kMaxQueries * t->dim + 255) / 256, 256, 0, ctx->stream>>>(
@@ -3198,6 +3204,7 @@ int recall_job_check(RecallJob* j, bool* ok_out) {
         }
     }
     j->scan_launches += j->n_ev - 1;
+    if (plan == kIndexPlan) return index_plan_check(j, ok_out);
     bool ok = j->h_status[0] == 0;
     j->failed.clear();
     if (ok && (plan == kPilot || plan == kPredict)) {
@@ -3332,7 +3339,7 @@ int recall_patch_failed_locked(RecallJob* j, uint32_t* counts) {
         int rc;
         if ((rc = recall_dev_locked(ctx, j->t, j->d_queries + (size_t)q * j->t->dim, 1, j->k, j->d_out_rows + (size_t)q * j->k,
                                     j->d_out_scores + (size_t)q * j->k, &cnt, j->d_out_count ? j->d_out_count + q : nullptr, true, j->l2,
-                                    j->filter.col ? &j->filter : nullptr, j->exact_only)))
+                                    j->filter.col ? &j->filter : nullptr, j->exact_only, j->no_index)))
             return rc;
         counts[q] = cnt;
     }
@@ -3343,9 +3350,11 @@ int recall_patch_failed_locked(RecallJob* j, uint32_t* counts) {
 // the whole recall for one batch of queries, verified before it returns; all pointers are device pointers
 int recall_dev_locked(pg_ctx* ctx, const pg_table* t, const float* d_queries, uint32_t nq,
                       uint32_t k, uint64_t* d_out_rows, float* d_out_scores,
-                      uint32_t* out_count, uint32_t* d_out_count, bool skip_pilot, bool l2, const RowFilter* filter, bool exact_only) {
+                      uint32_t* out_count, uint32_t* d_out_count, bool skip_pilot, bool l2, const RowFilter* filter, bool exact_only,
+                      bool no_index) {
     RecallJob j;
     j.exact_only = exact_only;
+    j.no_index = no_index;
     j.skip_pilot = skip_pilot;
     j.l2 = l2;
     if (filter) j.filter = *filter;

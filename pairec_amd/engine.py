@@ -287,6 +287,21 @@ class Index:
         _lib.check(self.ctx.L.pg_index_stats(self.h, C.byref(st)))
         return {name: getattr(st, name) for name, _ in st._fields_}
 
+    def attach(self, ctx: Context = None):
+        """Route every recall job of the table (plain recalls, coalescer batches, recommend pipelines) through this index first
+        (pg_index_attach); a second attached index replaces the first."""
+        _lib.check(self.ctx.L.pg_index_attach((ctx or self.ctx).h, self.h))
+
+    def detach(self, ctx: Context = None):
+        """Stop routing the table's recalls through this index; returns once nothing enqueued reads it (pg_index_detach)."""
+        _lib.check(self.ctx.L.pg_index_detach((ctx or self.ctx).h, self.h))
+
+    def serving_stats(self) -> dict:
+        """plans tried / held, re-plans by reason and skipped batches of the attached plan (pg_index_serving_stats)"""
+        st = _lib.PgIndexServingStats()
+        _lib.check(self.ctx.L.pg_index_serving_stats(self.h, C.byref(st)))
+        return {name: getattr(st, name) for name, _ in st._fields_}
+
     def destroy(self):
         if self.h:
             _lib.check(self.ctx.L.pg_index_destroy(self.ctx.h, self.h))
