@@ -468,6 +468,16 @@ typedef struct {
     uint64_t skipped_stale, skipped_switch;   /* batches that never tried the index plan */
 } pg_index_serving_stats_t;
 int pg_index_serving_stats(const pg_index* ix, pg_index_serving_stats_t* out);
+/* Diagnostics of an index's device state (what the search prunes with).
+ *   read     copies the build's arrays to host memory: offsets [n_lists + 1] (list L holds perm[offsets[L], offsets[L+1])),
+ *            perm [rows] (source rows, ascending within a list), centroids [n_lists][dim], cnorm [n_lists] (>= ||c_L||) and
+ *            radius [n_lists] (>= max ||x - c_L|| over the list's rows; 0 for an empty list).  Any output pointer may be NULL.
+ *   bounds   U[q][L] for host queries [nq][dim], 1 <= nq <= 256, as the search computes it (the same launch): an upper bound of
+ *            every chain score of list L's rows (l2 != 0: of every -d, d the squared Euclidean distance); +inf where a partial
+ *            sum could overflow.  out: [nq][n_lists].  Neither needs a current generation.  PG_ERR_INVALID on a NULL ctx or
+ *            index (or, for bounds, NULL queries / out or nq out of range). */
+int pg_index_read(pg_ctx* ctx, const pg_index* ix, uint32_t* offsets, uint32_t* perm, float* centroids, float* cnorm, float* radius);
+int pg_index_bounds(pg_ctx* ctx, const pg_index* ix, const float* queries, uint32_t nq, int l2, float* out);
 /* FM + two-tower rank straight from candidate rows: the model's item field ids are the integer columns
  * item_field_cols[n_item_fields] of `fs` (out-of-vocabulary ids are clamped as in pg_rank_fm2t_dev) */
 int pg_rank_fm2t_rows_dev(pg_ctx* ctx, const pg_model* m, const pg_features* fs, const int32_t* item_field_cols,

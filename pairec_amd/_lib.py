@@ -40,6 +40,7 @@ EXPORTS = [
     "pg_router_create", "pg_router_destroy", "pg_router_recommend", "pg_router_recall", "pg_router_stats",
     "pg_index_build", "pg_index_destroy", "pg_index_recall_topk", "pg_index_recall_topk_dev", "pg_index_recall_topk_l2",
     "pg_index_recall_topk_l2_dev", "pg_index_stats", "pg_index_attach", "pg_index_detach", "pg_index_serving_stats",
+    "pg_index_read", "pg_index_bounds",
 ]
 
 
@@ -159,6 +160,8 @@ def load():
         "pg_index_attach": [vp, vp],
         "pg_index_detach": [vp, vp],
         "pg_index_serving_stats": [vp, P(PgIndexServingStats)],
+        "pg_index_read": [vp, vp, vp, vp, vp, vp, vp],
+        "pg_index_bounds": [vp, vp, vp, u32, i32, vp],
         "pg_topk_merge_dev": [vp, vp, vp, u32, u32, u32, u32, vp, vp],
         "pg_model_load": [vp, i32, i32, vp, sz, P(vp)],
         "pg_model_destroy": [vp, vp],

@@ -765,6 +765,20 @@ int search_bufs(pg_ctx* ctx, uint32_t nq, uint32_t nl, SearchBufs* b) {
     return PG_OK;
 }
 
+// the bounds of a batch: qn[q] >= ||q|| (and *flag |= 1 for a non-finite query), then U[q][L] — the one launch of the
+// synchronous search, the attached plan and pg_index_bounds
+int bounds_launch(pg_ctx* ctx, const pg_index* ix, const float* d_q, uint32_t nq, bool l2, double* qn, uint32_t* flag, float* U) {
+    const uint32_t nl = ix->n_lists, dim = ix->dim;
+    hipStream_t s = ctx->stream;
+    qinfo_kernel<<<nq, 64, 0, s>>>(d_q, dim, qn, flag);
+    const dim3 bg((nl + 255) / 256, (nq + kBoundQ - 1) / kBoundQ);
+    const size_t blds = (size_t)kBoundQ * dim * 8;
+    if (l2) bound_kernel<true><<<bg, 256, blds, s>>>(d_q, nq, dim, qn, ix->d_cent, ix->d_cnorm, ix->d_rad, nl, U);
+    else bound_kernel<false><<<bg, 256, blds, s>>>(d_q, nq, dim, qn, ix->d_cent, ix->d_cnorm, ix->d_rad, nl, U);
+    PG_HIP(hipGetLastError());
+    return PG_OK;
+}
+
 enum Fallback { kNone = 0, kDense, kStale, kNonfinite, kOverflow };
 
 int table_pass_locked(pg_ctx* ctx, const pg_table* t, const float* d_q, uint32_t nq, uint32_t k, uint64_t* d_rows, float* d_sc,
@@ -822,13 +836,9 @@ int index_recall_locked(pg_ctx* ctx, pg_index* ix, const float* d_q, uint32_t nq
         float* thr_scan = sb.thr_scan;
         hipStream_t s = ctx->stream;
         index_init_kernel<<<1, kMaxQueries, 0, s>>>(rs.thr, rs.cnt, rs.overflow, flag);
-        qinfo_kernel<<<nq, 64, 0, s>>>(d_q, dim, qn, flag);
         PG_HIP(hipGetLastError());
         if (l2 && (rc2 = query_norm2_launch(ctx, d_q, nq, dim, nqv))) return rc2;
-        const dim3 bg((nl + 255) / 256, (nq + kBoundQ - 1) / kBoundQ);
-        const size_t blds = (size_t)kBoundQ * dim * 8;
-        if (l2) bound_kernel<true><<<bg, 256, blds, s>>>(d_q, nq, dim, qn, ix->d_cent, ix->d_cnorm, ix->d_rad, nl, U);
-        else bound_kernel<false><<<bg, 256, blds, s>>>(d_q, nq, dim, qn, ix->d_cent, ix->d_cnorm, ix->d_rad, nl, U);
+        if ((rc2 = bounds_launch(ctx, ix, d_q, nq, l2, qn, flag, U))) return rc2;
         probe_kernel<<<nq, 1024, 0, s>>>(U, nl, ix->d_off, ix->rows, k, Bkey, probe);
         count_kernel<<<dim3(kSlices, nq), 256, 0, s>>>(U, nl, ix->d_off, Bkey, rs.thr, 0, cntg);
         PG_HIP(hipGetLastError());
@@ -1021,13 +1031,9 @@ int index_plan_enqueue(RecallJob* j, uint32_t status_words) {
     j->timers = !ctx->timers_off;
     if (j->timers) PG_HIP(hipEventRecord((*j->events)[0], s));
     index_plan_init_kernel<<<1, kMaxQueries, 0, s>>>(rs.thr, rs.cnt, rs.overflow, pw);
-    qinfo_kernel<<<nq, 64, 0, s>>>(d_q, dim, sb.qn, &pw->flags);
     PG_HIP(hipGetLastError());
     if (l2 && (rc = query_norm2_launch(ctx, d_q, nq, dim, sb.nqv))) return rc;
-    const dim3 bg((nl + 255) / 256, (nq + kBoundQ - 1) / kBoundQ);
-    const size_t blds = (size_t)kBoundQ * dim * 8;
-    if (l2) bound_kernel<true><<<bg, 256, blds, s>>>(d_q, nq, dim, sb.qn, ix->d_cent, ix->d_cnorm, ix->d_rad, nl, sb.U);
-    else bound_kernel<false><<<bg, 256, blds, s>>>(d_q, nq, dim, sb.qn, ix->d_cent, ix->d_cnorm, ix->d_rad, nl, sb.U);
+    if ((rc = bounds_launch(ctx, ix, d_q, nq, l2, sb.qn, &pw->flags, sb.U))) return rc;
     probe_kernel<<<nq, 1024, 0, s>>>(sb.U, nl, ix->d_off, ix->rows, k, sb.Bkey, sb.probe);
     count_kernel<<<dim3(kSlices, nq), 256, 0, s>>>(sb.U, nl, ix->d_off, sb.Bkey, rs.thr, 0, sb.cntg);
     PG_HIP(hipGetLastError());
@@ -1201,6 +1207,39 @@ int pg_index_stats(const pg_index* ixc, pg_index_stats_t* out) {
     out->fallback_dense += sv.replan_dense.load();
     out->fallback_nonfinite += sv.replan_nonfinite.load();
     out->fallback_overflow += sv.replan_overflow.load();
+    return PG_OK;
+}
+
+int pg_index_read(pg_ctx* ctx, const pg_index* ix, uint32_t* offsets, uint32_t* perm, float* centroids, float* cnorm, float* radius) {
+    PG_REQUIRE(ctx && ix, "pg_index_read: NULL argument");
+    std::lock_guard<std::mutex> g(ctx->mu);
+    hipStream_t s = ctx->stream;
+    const size_t nl = ix->n_lists;
+    if (offsets) PG_HIP(hipMemcpyAsync(offsets, ix->d_off, (nl + 1) * 4, hipMemcpyDeviceToHost, s));
+    if (perm) PG_HIP(hipMemcpyAsync(perm, ix->d_perm, (size_t)ix->rows * 4, hipMemcpyDeviceToHost, s));
+    if (centroids) PG_HIP(hipMemcpyAsync(centroids, ix->d_cent, nl * ix->dim * 4, hipMemcpyDeviceToHost, s));
+    if (cnorm) PG_HIP(hipMemcpyAsync(cnorm, ix->d_cnorm, nl * 4, hipMemcpyDeviceToHost, s));
+    if (radius) PG_HIP(hipMemcpyAsync(radius, ix->d_rad, nl * 4, hipMemcpyDeviceToHost, s));
+    PG_HIP(hipStreamSynchronize(s));
+    return PG_OK;
+}
+
+int pg_index_bounds(pg_ctx* ctx, const pg_index* ix, const float* queries, uint32_t nq, int l2, float* out) {
+    PG_REQUIRE(ctx && ix && queries && out, "pg_index_bounds: NULL argument");
+    PG_REQUIRE(nq >= 1 && nq <= (uint32_t)pg::kMaxQueries, "pg_index_bounds: nq=%u must be in [1,%d]", nq, pg::kMaxQueries);
+    std::lock_guard<std::mutex> g(ctx->mu);
+    hipStream_t s = ctx->stream;
+    const size_t qb = (size_t)nq * ix->dim * 4;
+    void* buf;
+    int rc;
+    if ((rc = pg::scratch_reserve(ctx, 5, qb, &buf))) return rc;
+    pg::SearchBufs sb;
+    if ((rc = pg::search_bufs(ctx, nq, ix->n_lists, &sb))) return rc;
+    PG_HIP(hipMemcpyAsync(buf, queries, qb, hipMemcpyHostToDevice, s));
+    PG_HIP(hipMemsetAsync(sb.flag, 0, 4, s));
+    if ((rc = pg::bounds_launch(ctx, ix, (const float*)buf, nq, l2 != 0, sb.qn, sb.flag, sb.U))) return rc;
+    PG_HIP(hipMemcpyAsync(out, sb.U, (size_t)nq * ix->n_lists * 4, hipMemcpyDeviceToHost, s));
+    PG_HIP(hipStreamSynchronize(s));
     return PG_OK;
 }
 

@@ -1118,14 +1118,32 @@ __global__ __launch_bounds__(256) void rescore_kernel(const float* __restrict__ 
         float s = 0.0f;
         // (phases written out: with `v[ph & 1]` inside a loop the buffers stayed in scratch at DIM = 128; past the
         // last chunk row_next is 0 — a harmless gather of row 0 instead of a conditional one)
-        if constexpr (NPH == 2) {
+        // (every phase is walked in column order: the chain is k-ascending over all DIM columns)
+        if constexpr (NPH == 1) {
+            rescore_gather<DIM>(vb, tab, row_next, 0, lane);
+            rescore_walk<kRowB>(va, my, qs, 0, lane, s);
+        } else if constexpr (NPH == 2) {
             rescore_gather<DIM>(vb, tab, row, 1, lane);
             rescore_walk<kRowB>(va, my, qs, 0, lane, s);
             rescore_gather<DIM>(va, tab, row_next, 0, lane);
             rescore_walk<kRowB>(vb, my, qs, 1, lane, s);
-        } else {
-            rescore_gather<DIM>(vb, tab, row_next, 0, lane);
+        } else if constexpr (NPH == 3) {
+            rescore_gather<DIM>(vb, tab, row, 1, lane);
             rescore_walk<kRowB>(va, my, qs, 0, lane, s);
+            rescore_gather<DIM>(va, tab, row, 2, lane);
+            rescore_walk<kRowB>(vb, my, qs, 1, lane, s);
+            rescore_gather<DIM>(vb, tab, row_next, 0, lane);
+            rescore_walk<kRowB>(va, my, qs, 2, lane, s);
+        } else {
+            static_assert(NPH == 4, "rescore_kernel: DIM 64, 128, 192 or 256");
+            rescore_gather<DIM>(vb, tab, row, 1, lane);
+            rescore_walk<kRowB>(va, my, qs, 0, lane, s);
+            rescore_gather<DIM>(va, tab, row, 2, lane);
+            rescore_walk<kRowB>(vb, my, qs, 1, lane, s);
+            rescore_gather<DIM>(vb, tab, row, 3, lane);
+            rescore_walk<kRowB>(va, my, qs, 2, lane, s);
+            rescore_gather<DIM>(va, tab, row_next, 0, lane);
+            rescore_walk<kRowB>(vb, my, qs, 3, lane, s);
         }
         if (NPH & 1) {                                   // odd phase count: the prefetched unit sits in v[1], the loop reads v[0]
 #pragma unroll

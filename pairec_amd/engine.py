@@ -287,6 +287,24 @@ class Index:
         _lib.check(self.ctx.L.pg_index_stats(self.h, C.byref(st)))
         return {name: getattr(st, name) for name, _ in st._fields_}
 
+    def read(self) -> dict:
+        """the build's device arrays (pg_index_read): offsets [n_lists + 1] and perm [rows] uint32, centroids [n_lists][dim],
+        cnorm and radius [n_lists] f32"""
+        st = self.stats()
+        nl, rows, dim = st["n_lists"], st["rows"], st["dim"]
+        out = {"offsets": np.empty(nl + 1, np.uint32), "perm": np.empty(rows, np.uint32),
+               "centroids": np.empty((nl, dim), np.float32), "cnorm": np.empty(nl, np.float32), "radius": np.empty(nl, np.float32)}
+        _lib.check(self.ctx.L.pg_index_read(self.ctx.h, self.h, *(_ptr(out[n]) for n in ("offsets", "perm", "centroids", "cnorm",
+                                                                                          "radius"))))
+        return out
+
+    def bounds(self, queries: np.ndarray, l2: bool = False) -> np.ndarray:
+        """U [nq][n_lists] f32 as the search computes it (pg_index_bounds): >= every chain score of a list's rows (l2: of -d)"""
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.table.dim)
+        out = np.empty((q.shape[0], self.stats()["n_lists"]), np.float32)
+        _lib.check(self.ctx.L.pg_index_bounds(self.ctx.h, self.h, _ptr(q), q.shape[0], int(l2), _ptr(out)))
+        return out
+
     def attach(self, ctx: Context = None):
         """Route every recall job of the table (plain recalls, coalescer batches, recommend pipelines) through this index first
         (pg_index_attach); a second attached index replaces the first."""

@@ -36,6 +36,42 @@ def delta(ix, before):
                                               "fallback_nonfinite", "fallback_overflow")}
 
 
+FALLBACKS = ("fallback_dense", "fallback_stale", "fallback_nonfinite", "fallback_overflow")
+
+
+class lifted:
+    """the dense rule lifted for a block: it is a cost decision calibrated at 100 M rows that sends most batches
+    on these small tables to the table's pass, so that without this the search itself would not see the data"""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+
+    def __enter__(self):
+        self.ctx.set_option("index_dense_fraction", 1e6)
+
+    def __exit__(self, *a):
+        self.ctx.set_option("index_dense_fraction", DENSE_DEFAULT)
+
+
+def assert_served(d, calls=1):
+    """every batch of the call was answered by the index search: no fallback of any kind, and pairs were scored"""
+    assert d["calls"] == calls and d["pairs_scored"] > 0 and all(d[f] == 0 for f in FALLBACKS), d
+
+
+def both_rules(ctx, ix, call, ref, l2=False, seen=None):
+    """the call under the default dense rule, then again with the rule lifted: exact both times, and the second time served by
+    the search.  seen (a list) collects whether the default-rule call reached the search."""
+    b = ix.stats()
+    assert_same(call(), *ref, l2=l2)
+    d = delta(ix, b)
+    if seen is not None:
+        seen.append(all(d[f] == 0 for f in FALLBACKS))
+    b = ix.stats()
+    with lifted(ctx):
+        assert_same(call(), *ref, l2=l2)
+    assert_served(delta(ix, b))
+
+
 @pytest.fixture(scope="module", params=[0.03, 0.1, 0.3])
 def mixture(request, ctx):
     sigma = request.param
@@ -57,9 +93,9 @@ def test_mixture_exact_and_pruned(ctx, mixture):
     assert st["n_lists"] == round(4 * np.sqrt(N)) and st["rows"] == N and st["max_radius"] >= st["mean_radius"] > 0
     for nq in (1, 8, 33, 64, 256):
         for k in (1, 100, 1000, 5000):
-            assert_same(ix.recall_topk(q[:nq], k), orow[:nq, :k], osc[:nq, :k])
+            both_rules(ctx, ix, lambda: ix.recall_topk(q[:nq], k), (orow[:nq, :k], osc[:nq, :k]))
     for nq, k in ((1, 5000), (33, 100), (256, 1000)):
-        assert_same(ix.recall_topk_l2(q[:nq], k), lrow[:nq, :k], lsc[:nq, :k], l2=True)
+        both_rules(ctx, ix, lambda: ix.recall_topk_l2(q[:nq], k), (lrow[:nq, :k], lsc[:nq, :k]), l2=True)
     # the _dev variants
     nq, k = 33, 1000
     dq = ctx.to_device(q[:nq])
@@ -135,8 +171,8 @@ def test_uniform_table_exact(ctx):
     q = o.synth_rows(o.SEED_QUERY, 0, 64, d)
     ix = pa.Index(ctx, t)
     for nq, k in ((1, 1000), (64, 100)):
-        assert_same(ix.recall_topk(q[:nq], k), *o.recall_topk(tab, q[:nq], k))
-    assert_same(ix.recall_topk_l2(q[:8], 500), *o.recall_topk_l2(tab, q[:8], 500), l2=True)
+        both_rules(ctx, ix, lambda: ix.recall_topk(q[:nq], k), o.recall_topk(tab, q[:nq], k))
+    both_rules(ctx, ix, lambda: ix.recall_topk_l2(q[:8], 500), o.recall_topk_l2(tab, q[:8], 500), l2=True)
     ix.destroy()
     t.destroy()
 
@@ -148,16 +184,19 @@ def _table(ctx, tab, row_offset=0):
 
 
 def test_hostile_data(ctx):
+    """Every case under the default dense rule (which sends most of them to the table's pass) and again with the rule lifted,
+    where the search itself must serve it; the two cases that fall back on purpose assert their own outcome."""
     rng = np.random.default_rng(11)
     d = 128
+    seen = []
     # all-equal rows (radius 0, every score tied), rows not a multiple of 64, K > rows
     same = np.tile(rng.standard_normal(d).astype(np.float32), (5003, 1))
     t = _table(ctx, same)
     ix = pa.Index(ctx, t)
     q = rng.standard_normal((4, d)).astype(np.float32)
     for k in (1, 100, 8000):
-        assert_same(ix.recall_topk(q, k), *o.recall_topk(same, q, k))
-        assert_same(ix.recall_topk_l2(q, k), *o.recall_topk_l2(same, q, k), l2=True)
+        both_rules(ctx, ix, lambda: ix.recall_topk(q, k), o.recall_topk(same, q, k), seen=seen)
+        both_rules(ctx, ix, lambda: ix.recall_topk_l2(q, k), o.recall_topk_l2(same, q, k), l2=True, seen=seen)
     ix.destroy()
     t.destroy()
     # duplicates and scores tied at the threshold: small-integer rows, many exact ties; zero / one-hot / negated-centroid /
@@ -175,22 +214,33 @@ def test_hostile_data(ctx):
         ix = pa.Index(ctx, t, n_lists=nl)
         assert ix.stats()["n_lists"] == nl
         for k in (1, 50, 2000):
-            assert_same(ix.recall_topk(qs, k), *o.recall_topk(tab, qs, k, row_offset=off))
-        assert_same(ix.recall_topk_l2(qs[:3], 300), *o.recall_topk_l2(tab, qs[:3], 300, row_offset=off), l2=True)
+            both_rules(ctx, ix, lambda: ix.recall_topk(qs, k), o.recall_topk(tab, qs, k, row_offset=off), seen=seen)
+        both_rules(ctx, ix, lambda: ix.recall_topk_l2(qs[:3], 300), o.recall_topk_l2(tab, qs[:3], 300, row_offset=off), l2=True,
+                   seen=seen)
         ix.destroy()
     t.destroy()
-    # dim 64 and 256 (<= 32 queries per call at 256)
-    for dd, nq in ((64, 40), (256, 32)):
+    # dim 64, 192 and 256 (<= 32 queries per call above 128)
+    for dd, nq in ((64, 40), (192, 32), (256, 32)):
         tab = o.synth_mixture_rows(5, 0, 20_011, dd, 20, 0.1)
         q = o.synth_mixture_rows(5, 1, nq, dd, 20, 0.1, stream=1)
         t = _table(ctx, tab)
         ix = pa.Index(ctx, t)
-        assert_same(ix.recall_topk(q, 700), *o.recall_topk(tab, q, 700))
+        both_rules(ctx, ix, lambda: ix.recall_topk(q, 700), o.recall_topk(tab, q, 700), seen=seen)
         if dd == 64:
-            assert_same(ix.recall_topk_l2(q, 700), *o.recall_topk_l2(tab, q, 700), l2=True)
+            both_rules(ctx, ix, lambda: ix.recall_topk_l2(q, 700), o.recall_topk_l2(tab, q, 700), l2=True, seen=seen)
+        else:
+            # squared Euclidean above dim 128 is always `dense` (index.hip: the search has no kernel for it): the table's pass
+            # refuses it as it refuses the table's own call, and nothing is counted
+            b = ix.stats()
+            with lifted(ctx):
+                for fn in (lambda: ix.recall_topk_l2(q, 700), lambda: t.recall_topk_l2(q, 700)):
+                    with pytest.raises(pa._lib.PgError) as e:
+                        fn()
+                    assert e.value.code == -4
+            assert all(v == 0 for v in delta(ix, b).values())
         ix.destroy()
         t.destroy()
-    # a NaN / inf row: builds, every recall is the table's pass (counted)
+    # a NaN / inf row: builds, every recall is the table's pass (counted), with or without the dense rule
     tab = o.synth_rows(o.SEED_TABLE, 0, 10_000, d)
     tab[17, 3] = np.nan
     tab[9000, 0] = np.inf
@@ -200,7 +250,90 @@ def test_hostile_data(ctx):
     b = ix.stats()
     assert_same(ix.recall_topk(q, 100), *t.recall_topk(q, 100)[:2])
     assert delta(ix, b)["fallback_nonfinite"] == 1
+    b = ix.stats()
+    with lifted(ctx):
+        assert_same(ix.recall_topk(q, 100), *t.recall_topk(q, 100)[:2])
+    dd = delta(ix, b)
+    assert dd["calls"] == 1 and dd["fallback_nonfinite"] == 1 and dd["pairs_scored"] == 0, dd
     ix.destroy()
+    t.destroy()
+    print("test_hostile_data: %d of %d cases reached the search under the default dense rule, %d of %d with it lifted"
+          % (sum(seen), len(seen), len(seen), len(seen)))
+
+
+def test_outlier_rows_only_the_radius_keeps_live(ctx):
+    """Tight clusters; into a few far clusters one row at c + rho q_hat for a query q, so that the row is q's top-1 while its
+    list's centroid ranks far down for q.  Only r_L (the outlier widens it) keeps that list live: a bound that under-counts the
+    radius prunes the list and loses the top-1.  Exact for IP and L2 with the dense rule lifted, no fallback, and at K = 1 the
+    pairs scored show that most of the table was pruned."""
+    rng = np.random.default_rng(0x0071)
+    d, n_c, per, nq = 128, 64, 4096, 8
+    cent = rng.standard_normal((n_c, d))
+    cent /= np.linalg.norm(cent, axis=1, keepdims=True)
+    tab = (np.repeat(cent, per, axis=0) + 0.02 * rng.standard_normal((n_c * per, d)) / np.sqrt(d)).astype(np.float32)
+    q = rng.standard_normal((nq, d))
+    q /= np.linalg.norm(q, axis=1, keepdims=True)
+    cq = q @ cent.T                                          # [nq][n_c]
+    far = []
+    for j in range(nq):                                      # a distinct far cluster per query: among the lowest c.q
+        far.append(next(c for c in np.argsort(cq[j]) if c not in far))
+    rho = cq.max(axis=1) - cq[np.arange(nq), far] + 0.3
+    out_rows = np.array([f * per + 17 for f in far])
+    tab[out_rows] = (cent[far] + rho[:, None] * q).astype(np.float32)
+    q = q.astype(np.float32)
+    t = _table(ctx, tab)
+    ix = pa.Index(ctx, t, n_lists=4 * n_c, iters=16)          # (several lists per cluster: few lists span two clusters)
+    try:
+        st = ix.read()
+        list_of = np.empty(tab.shape[0], np.int64)
+        list_of[st["perm"].astype(np.int64)] = np.repeat(np.arange(4 * n_c), np.diff(st["offsets"].astype(np.int64)))
+        crank = np.argsort(np.argsort(-(q.astype(np.float64) @ st["centroids"].T.astype(np.float64)), axis=1), axis=1)
+        for j in range(nq):
+            assert crank[j, list_of[out_rows[j]]] >= 2 * n_c, "the outlier's list must rank far down for its query"
+        ip = o.recall_topk(tab, q, 5000)
+        assert np.array_equal(ip[0][:, 0], out_rows.astype(np.uint64)), "the outlier must be its query's top-1"
+        l2 = o.recall_topk_l2(tab, q, 5000)
+        with lifted(ctx):
+            # (pruning is measured at K = 1: at larger K the wide outlier lists, whose bounds are the highest, fill the probe
+            # and set a low threshold — exact, but most of the table is scanned)
+            for k in (1, 100, 5000):
+                b = ix.stats()
+                assert_same(ix.recall_topk(q, k), ip[0][:, :k], ip[1][:, :k])
+                dd = delta(ix, b)
+                assert_served(dd)
+                assert k > 1 or dd["pairs_scored"] <= 0.2 * tab.shape[0] * nq, dd
+                b = ix.stats()
+                assert_same(ix.recall_topk_l2(q, k), l2[0][:, :k], l2[1][:, :k], l2=True)
+                dd = delta(ix, b)
+                assert_served(dd)
+                assert k > 1 or dd["pairs_scored"] <= 0.2 * tab.shape[0] * nq, dd
+    finally:
+        ix.destroy()
+        t.destroy()
+
+
+def test_k_above_rows_with_a_row_offset(ctx):
+    """K above the table's row count through the search (the dense rule lifted): every row, padded with UINT64_MAX and -inf
+    (+inf for L2), counts = rows, global ids offset"""
+    n, d, off = 5_003, 64, 4_000_000_007              # (global ids are 32-bit)
+    tab = o.synth_mixture_rows(13, 0, n, d, 16, 0.05)
+    q = o.synth_mixture_rows(13, 2, 6, d, 16, 0.05, stream=1)
+    t = _table(ctx, tab, off)
+    for nl in (1, 9, n // 64):
+        ix = pa.Index(ctx, t, n_lists=nl)
+        try:
+            with lifted(ctx):
+                for k in (n, n + 1, 8000):
+                    b = ix.stats()
+                    got = ix.recall_topk(q, k)
+                    assert_same(got, *o.recall_topk(tab, q, k, row_offset=off))
+                    assert got[2].tolist() == [n] * q.shape[0]
+                    assert_served(delta(ix, b))
+                    b = ix.stats()
+                    assert_same(ix.recall_topk_l2(q, k), *o.recall_topk_l2(tab, q, k, row_offset=off), l2=True)
+                    assert_served(delta(ix, b))
+        finally:
+            ix.destroy()
     t.destroy()
 
 

@@ -352,6 +352,96 @@ def test_round_budget_replans_and_several_rounds_hold(ctx):
     t.destroy()
 
 
+def _hostile_tables(rng):
+    """the tables of test_gpu_index.py::test_hostile_data: (table rows, row offset, n_lists values, queries, IP cases, L2 cases),
+    a case being (queries, k)"""
+    d = 128
+    same = np.tile(rng.standard_normal(d).astype(np.float32), (5003, 1))
+    q = rng.standard_normal((4, d)).astype(np.float32)
+    yield same, 0, (0,), [(q, k) for k in (1, 100, 8000)], [(q, k) for k in (1, 100, 8000)]
+    base = rng.integers(-2, 3, size=(3000, d)).astype(np.float32)
+    tab = np.concatenate([base, base[::-1], base[:77]]).astype(np.float32)
+    onehot = np.zeros((1, d), np.float32)
+    onehot[0, 5] = 1
+    qs = np.concatenate([np.zeros((1, d), np.float32), onehot, -tab.mean(0, keepdims=True).astype(np.float32),
+                         np.float32(1e30) * np.sign(rng.standard_normal((1, d))).astype(np.float32),
+                         rng.integers(-1, 2, size=(4, d)).astype(np.float32)]).astype(np.float32)
+    yield tab, 1_000_003, (1, tab.shape[0] // 64, 17), [(qs, k) for k in (1, 50, 2000)], [(qs[:3], 300)]
+    for dd, nq in ((64, 40), (192, 32), (256, 32)):
+        tab = o.synth_mixture_rows(5, 0, 20_011, dd, 20, 0.1)
+        q = o.synth_mixture_rows(5, 1, nq, dd, 20, 0.1, stream=1)
+        yield tab, 0, (0,), [(q, 700)], ([(q, 700)] if dd == 64 else [])
+
+
+def _like_oracle_padded(got, ref, l2):
+    n = ref[0].shape[1]
+    like_oracle((got[0][:, :n], got[1][:, :n]), *ref)
+    assert np.asarray(got[2]).tolist() == [n] * got[0].shape[0]
+    assert np.all(got[0][:, n:] == np.uint64(0xFFFFFFFFFFFFFFFF))
+    assert np.all(got[1][:, n:] == (np.inf if l2 else -np.inf))
+
+
+def test_hostile_tables_through_the_attached_plan(ctx):
+    """test_gpu_index.py's hostile tables through t.recall_topk[_l2] with the index attached (dense rule lifted, a raised round
+    budget): bit for bit the detached call and the oracle, and every batch held by the plan.  A table with a NaN / inf row is
+    never tried (the plan is not prepared for a non-finite index): the table's plans answer and no counter moves."""
+    rng = np.random.default_rng(11)
+    for tab, off, n_lists, ip_cases, l2_cases in _hostile_tables(rng):
+        t = pa.Table(ctx, tab.shape[0], tab.shape[1], off)
+        t.upload(tab)
+        cases = [(False, qq, k) for qq, k in ip_cases] + [(True, qq, k) for qq, k in l2_cases]
+        detached = [(t.recall_topk_l2 if l2 else t.recall_topk)(qq, k) for l2, qq, k in cases]
+        refs = [(o.recall_topk_l2 if l2 else o.recall_topk)(tab, qq, k, row_offset=off) for l2, qq, k in cases]
+        for nl in n_lists:
+            ix = pa.Index(ctx, t, n_lists=nl)
+            with wide(ctx), options(ctx, index_plan_rounds=(8, 2)):
+                ix.attach()
+                try:
+                    for (l2, qq, k), det, ref in zip(cases, detached, refs):
+                        s0 = serving(ix)
+                        got = (t.recall_topk_l2 if l2 else t.recall_topk)(qq, k)
+                        dd = serving(ix, s0)
+                        same(got, det)
+                        _like_oracle_padded(got, ref, l2)
+                        assert dd["plans"] == 1 and dd["plans_held"] == 1 and dd["queries_held"] == qq.shape[0], (tab.shape, nl, l2, k, dd)
+                        assert all(dd[c] == 0 for c in ("replan_dense", "replan_rounds", "replan_overflow", "replan_nonfinite",
+                                                        "skipped_stale", "skipped_switch")), (tab.shape, nl, l2, k, dd)
+                finally:
+                    ix.detach()
+            ix.destroy()
+        if tab.shape[1] > 128:
+            # squared Euclidean above dim 128: not routed (no kernel for it), refused by the table as before attaching
+            ix = pa.Index(ctx, t)
+            with wide(ctx):
+                ix.attach()
+                s0 = serving(ix)
+                with pytest.raises(pa._lib.PgError) as e:
+                    t.recall_topk_l2(ip_cases[0][0], 700)
+                assert e.value.code == -4
+                assert all(v == 0 for v in serving(ix, s0).values())
+                ix.detach()
+            ix.destroy()
+        t.destroy()
+    # a NaN / inf row
+    tab = o.synth_rows(o.SEED_TABLE, 0, 10_000, 128)
+    tab[17, 3] = np.nan
+    tab[9000, 0] = np.inf
+    t = pa.Table(ctx, tab.shape[0], tab.shape[1])
+    t.upload(tab)
+    q = o.synth_rows(o.SEED_QUERY, 0, 3, 128)
+    det = t.recall_topk(q, 100)
+    ix = pa.Index(ctx, t)
+    with wide(ctx), options(ctx, index_plan_rounds=(8, 2)):
+        ix.attach()
+        s0, p0 = serving(ix), ix.stats()
+        same(t.recall_topk(q, 100), det)
+        assert all(v == 0 for v in serving(ix, s0).values())
+        assert ix.stats()["calls"] == p0["calls"]
+        ix.detach()
+    ix.destroy()
+    t.destroy()
+
+
 def test_edge_cases(ctx, world):
     t, tab, q, (orow, osc), _, ix = world
     k = 100

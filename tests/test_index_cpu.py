@@ -9,6 +9,7 @@ import pytest
 import pairec_amd as pa
 from pairec_amd import _lib
 from oracle import oracle as o
+from index_bound_ref import _adversarial, _bound_ip, _bound_neg_l2, _list_side
 
 PG_ERR_INVALID = -1
 
@@ -33,72 +34,16 @@ def test_index_abi_exported_and_refuses_nulls():
     st = _lib.PgIndexStats()
     assert L.pg_index_stats(None, C.byref(st)) == PG_ERR_INVALID
     assert L.pg_index_destroy(None, None) == PG_ERR_INVALID
-
-
-# ---- the bound, restated (index.hip: bound_kernel; all fp64, every table-side input rounded up to fp32 first) -------------
-def _up32(v):
-    """the smallest float32 >= v (elementwise, v float64)"""
-    f = np.asarray(v, dtype=np.float64).astype(np.float32)
-    low = f.astype(np.float64) < v
-    return np.where(low, np.nextafter(f, np.float32(np.inf)), f)
-
-
-def _list_side(x, c):
-    """r_L and ||c_L|| as the build measures them: fp64, a 2^-40 relative margin, rounded up to fp32"""
-    d = x.astype(np.float64) - c.astype(np.float64)
-    r = _up32(np.sqrt(np.max(np.sum(d * d, axis=1))) * (1 + 2.0 ** -40))
-    cn = _up32(np.sqrt(np.sum(c.astype(np.float64) ** 2)) * (1 + 2.0 ** -40))
-    return float(r), float(cn)
-
-
-def _bound_ip(q, c, r, cn):
-    dim = q.shape[1]
-    u = 2.0 ** -24
-    gam = dim * u / (1 - dim * u)
-    qn = np.sqrt(np.sum(q.astype(np.float64) ** 2, axis=1)) * (1 + 2.0 ** -40)
-    cq = q.astype(np.float64) @ c.astype(np.float64)
-    a = (cn + r) * qn
-    slack = gam * a * (1 + 2.0 ** -20) + 2.0 ** -40 * a + dim * 2.0 ** -148
-    out = _up32(cq + r * qn + slack)
-    return np.where(a * (1 + gam) * 2 < 2.0 ** 127, out, np.inf)
-
-
-def _bound_neg_l2(q, c, r, cn):
-    """upper bound of -d (the search ranks squared Euclidean recalls by -d)"""
-    dim = q.shape[1]
-    u = 2.0 ** -24
-    gam = (dim + 3) * u / (1 - (dim + 3) * u)
-    qn = np.sqrt(np.sum(q.astype(np.float64) ** 2, axis=1)) * (1 + 2.0 ** -40)
-    s = np.sqrt(np.sum((q.astype(np.float64) - c.astype(np.float64)) ** 2, axis=1)) * (1 - 2.0 ** -40)
-    lb = np.maximum(s - r, 0.0)
-    lb2 = lb * lb * (1 - 2.0 ** -40)
-    b = cn + r + qn
-    err = gam * b * b * (1 + 2.0 ** -20) + 2.0 ** -40 * b * b + dim * 2.0 ** -146
-    out = _up32(err - lb2)
-    return np.where(b * b * 2 < 2.0 ** 126, out, np.inf)
-
-
-def _adversarial(dim, scale, rng):
-    """a list: centroid c and rows around it — some exactly on the sphere of the measured radius, sign patterns that line up
-    every term of the chain (maximal rounding), near-duplicates of the centroid; queries: aligned, opposite, one-hot, zero,
-    sign-matched"""
-    c = (rng.standard_normal(dim) * scale).astype(np.float32)
-    signs = np.sign(rng.standard_normal((8, dim))).astype(np.float32)
-    dirs = rng.standard_normal((24, dim))
-    dirs /= np.linalg.norm(dirs, axis=1, keepdims=True)
-    rad = 0.3 * np.linalg.norm(c.astype(np.float64)) + 1e-30
-    on_sphere = (c.astype(np.float64) + rad * dirs).astype(np.float32)        # rows at (about) the measured radius
-    aligned = (c.astype(np.float64) + rad * signs / np.sqrt(dim)).astype(np.float32)
-    near = (c + np.float32(scale) * np.float32(1e-6) * signs[:2]).astype(np.float32)
-    x = np.concatenate([on_sphere, aligned, near, c[None, :]]).astype(np.float32)
-    onehot = np.zeros((2, dim), dtype=np.float32)
-    onehot[0, 0] = 1.0
-    onehot[1, dim - 1] = -np.float32(scale)
-    q = np.concatenate([
-        c[None, :], -c[None, :], signs[:3] * np.float32(scale), aligned[:2], onehot, np.zeros((1, dim), np.float32),
-        (rng.standard_normal((3, dim)) * scale).astype(np.float32),
-    ]).astype(np.float32)
-    return x, c, q
+    # the diagnostics: NULL ctx or index refused (every output pointer may be NULL, but not the handles)
+    for name in ("pg_index_read", "pg_index_bounds"):
+        assert hasattr(L, name) and name in _lib.EXPORTS
+    off = np.zeros(2, dtype=np.uint32)
+    assert L.pg_index_read(None, None, off.ctypes.data, None, None, None, None) == PG_ERR_INVALID
+    assert b"NULL" in L.pg_last_error()
+    assert L.pg_index_read(None, None, None, None, None, None, None) == PG_ERR_INVALID
+    assert L.pg_index_bounds(None, None, q.ctypes.data, 1, 0, sc.ctypes.data) == PG_ERR_INVALID
+    assert b"NULL" in L.pg_last_error()
+    assert L.pg_index_bounds(None, None, q.ctypes.data, 1, 1, sc.ctypes.data) == PG_ERR_INVALID
 
 
 @pytest.mark.parametrize("dim", [64, 128, 256])
