@@ -394,10 +394,21 @@ int recall_job_prepare(RecallJob* j);
 int recall_job_enqueue(RecallJob* j);                 // enqueue the next plan + the status copy into h_status
 int recall_job_check(RecallJob* j, bool* ok);         // after the stream passed the status copy: did the plan hold?
 void recall_job_finish(RecallJob* j);                 // publish timing / counters into ctx
+// how a recall job runs besides its table and queries (a default-constructed struct: an inner-product recall of every row)
+struct RecallOpts {
+    bool skip_pilot = false;                // no pilot plan (a re-run of a failed query)
+    bool l2 = false;                        // squared Euclidean, ascending
+    const RowFilter* filter = nullptr;      // only the rows the filter admits
+    bool exact_only = false;                // the exact plan only
+    bool no_index = false;                  // never through an attached index (the index's own fallback)
+};
 int recall_dev_locked(pg_ctx* ctx, const pg_table* t, const float* d_queries, uint32_t nq, uint32_t k,
                       uint64_t* d_out_rows, float* d_out_scores, uint32_t* out_count, uint32_t* d_out_count,
-                      bool skip_pilot = false, bool l2 = false, const RowFilter* filter = nullptr, bool exact_only = false,
-                      bool no_index = false);
+                      const RecallOpts& o = RecallOpts());
+// recall_dev_locked for up to kMaxQueries queries: one job, or for squared Euclidean jobs of at most 128 queries (the screened
+// pass serves up to 128; the exact scan runs groups of 64 either way)
+int recall_batches_locked(pg_ctx* ctx, const pg_table* t, const float* d_queries, uint32_t nq, uint32_t k, uint64_t* d_out_rows,
+                          float* d_out_scores, uint32_t* out_count, const RecallOpts& o);
 // index.hip: the attached index's plan in front of the table's plans (recall_job_prepare, after the table's plans are made), its
 // enqueue-only launches and status copy (recall_job_enqueue) and its verdict (recall_job_check; *ok = false: the table's plans follow)
 int index_plan_prepare(RecallJob* j);
@@ -503,6 +514,38 @@ int sort_dev_locked(pg_ctx* ctx, const double* d_scores, const uint32_t* d_seg, 
 
 void pipe_pool_destroy(pg_ctx* ctx);      // pipeline.hip
 int scratch_reserve(pg_ctx* ctx, int slot, size_t bytes, void** out);
+// the checks of the pg_recall_topk* and pg_index_recall_topk* entry points, in this order, named after the entry point `who`;
+// `over` is the table or index searched (its dim)
+template <class T>
+int recall_check(const char* who, const pg_ctx* ctx, const T* over, const void* queries, const void* rows, const void* scores, uint32_t nq,
+                 uint32_t k, bool l2) {
+    PG_REQUIRE(ctx && over && queries && rows && scores, "%s: NULL argument", who);
+    PG_REQUIRE(nq >= 1 && nq <= (uint32_t)kMaxQueries, "%s: nq=%u must be in [1,%d]", who, nq, kMaxQueries);
+    PG_REQUIRE(l2 || over->dim <= 128 || nq <= 32, "%s: dim %u supports at most 32 queries per call", who, over->dim);
+    if (k < 1 || k > 16384) {
+        set_error("%s: k=%u unsupported (1..16384)", who, k);
+        return PG_ERR_UNSUPPORTED;
+    }
+    return PG_OK;
+}
+// a recall of host queries into host outputs: the queries copied into scratch slot 5, run(d_queries, d_rows, d_scores) on the
+// device, the rows and scores copied out; caller holds ctx->mu
+template <class Run>
+int recall_staged(pg_ctx* ctx, uint32_t dim, const float* queries, uint32_t nq, uint32_t k, uint64_t* out_rows, float* out_scores, Run&& run) {
+    void* buf;
+    int rc;
+    const size_t qb = (size_t)nq * dim * 4, rb = (size_t)nq * k * 8, sb = (size_t)nq * k * 4;
+    if ((rc = scratch_reserve(ctx, 5, qb + rb + sb + 64, &buf))) return rc;
+    float* d_q = (float*)buf;
+    uint64_t* d_rows = (uint64_t*)((char*)buf + ((qb + 15) & ~(size_t)15));
+    float* d_sc = (float*)((char*)d_rows + rb);
+    PG_HIP(hipMemcpyAsync(d_q, queries, qb, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = run(d_q, d_rows, d_sc))) return rc;
+    PG_HIP(hipMemcpyAsync(out_rows, d_rows, rb, hipMemcpyDeviceToHost, ctx->stream));
+    PG_HIP(hipMemcpyAsync(out_scores, d_sc, sb, hipMemcpyDeviceToHost, ctx->stream));
+    PG_HIP(hipStreamSynchronize(ctx->stream));
+    return PG_OK;
+}
 // raise a kernel's dynamic-LDS limit once per context (the attribute is per device: a process may hold
 // contexts on several GPUs); caller holds ctx->mu
 int ensure_dyn_lds(pg_ctx* ctx, const void* kernel, size_t bytes);

@@ -15,10 +15,14 @@
 // Every row is scored by recall.hip's rescore_kernel — the specification's k-ascending fmaf chain — so its bits are the table
 // pass's bits; pruning drops only lists whose bound proves that none of their rows can reach thr_q.
 //
-// Serving (pg_index_attach): the same search as a RecallJob plan that is only enqueued.  What the synchronous
-// path decides on the host between its launches — the dense fallback, the number of rounds, a non-finite query — a plan kernel
-// decides on the device; every round's kernels read its verdict and return at once when there is nothing (more) to do, and
-// recall_job_check reads it with the job's status words and moves to the table's own plans when a flag is set.
+// One launch sequence (index_search) serves both callers.  After each stage's count a plan kernel writes the verdict — the dense
+// rule, a non-finite query, the rounds the stage takes — into the plan words, and every round's expansion reads it.  The two
+// callers differ only in their round policy:
+//   pg_index_recall_topk*   the host reads the words after each stage, falls back to the table's pass on a flag, and runs exactly
+//                           the rounds counted (no budget)
+//   an attached index       (pg_index_attach) a RecallJob plan that is only enqueued: index_plan_rounds rounds per
+//                           stage, rounds past the verdict's do nothing; recall_job_check reads the words with the job's status
+//                           words and moves to the table's own plans when a flag is set
 #include "common.hpp"
 
 #include <hipcub/hipcub.hpp>
@@ -68,7 +72,7 @@ constexpr uint32_t kBoundQ = 8;          // queries per bound-kernel block
 struct IndexPlanWords {
     uint32_t flags;                      // kPlanNonfinite | kPlanDense | kPlanRounds: the table's plans serve the batch
     uint32_t need[2];                    // rounds the probe (0) and the scan (1) take
-    uint32_t pad;
+    uint32_t max_probe;                  // the most rows one query's probe scores
     unsigned long long pairs[2];         // (row, query) pairs of the probe and the scan
     unsigned long long union_rows;       // rows of the lists live for some query (union_kernel)
     unsigned long long max_scan;         // the most rows one query's scan scores
@@ -242,13 +246,6 @@ __global__ void qinfo_kernel(const float* __restrict__ Q, uint32_t dim, double* 
     for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
     if (bad) atomicOr(flag, 1u);
     if (threadIdx.x == 0) qn[q] = sqrt(s) * (1.0 + 0x1p-40);
-}
-
-__global__ void index_init_kernel(float* __restrict__ thr, uint32_t* __restrict__ cnt, uint32_t* __restrict__ overflow, uint32_t* __restrict__ flag) {
-    const uint32_t i = threadIdx.x;
-    thr[i] = -__builtin_inff();
-    cnt[i] = 0u;
-    if (i == 0) { *overflow = 0u; *flag = 0u; }
 }
 
 // U[q][L].  Inner product: fl(x.q) <= q.c + r ||q|| + gamma_d (||c|| + r) ||q|| (+ underflow and fp64 terms).
@@ -491,7 +488,7 @@ __global__ __launch_bounds__(256) void union_kernel(const float* __restrict__ U,
     if ((threadIdx.x & 63) == 0 && s) atomicAdd(out, s);
 }
 
-// an index plan: thresholds, counts and the overflow word as index_init_kernel, and the plan's words cleared
+// a search's start: thresholds -inf, candidate counts and the overflow word 0, the plan's words cleared
 __global__ void index_plan_init_kernel(float* __restrict__ thr, uint32_t* __restrict__ cnt, uint32_t* __restrict__ overflow,
                                        IndexPlanWords* __restrict__ pw) {
     const uint32_t i = threadIdx.x;
@@ -501,9 +498,9 @@ __global__ void index_plan_init_kernel(float* __restrict__ thr, uint32_t* __rest
     if (i < sizeof(IndexPlanWords) / 4) reinterpret_cast<uint32_t*>(pw)[i] = 0u;
 }
 
-// the host decisions of index_recall_locked, on the device (launched <<<1, kMaxQueries>>> after the count of `mode`): the
-// (row, query) pairs of the batch, the dense rule against `limit` (the probe's pairs, then probe + scan), and the rounds of
-// scap suspects the query with the most rows needs — more than `budget` of them is a flag too
+// a stage's verdict (launched <<<1, kMaxQueries>>> after the count of `mode`): the (row, query) pairs of the batch, the dense
+// rule against `limit` (the probe's pairs, then probe + scan), the most rows one query scores and the rounds of scap suspects
+// that takes — more than `budget` of them is a flag too
 __global__ __launch_bounds__(256) void index_plan_kernel(const uint32_t* __restrict__ cnt, uint32_t nq, int mode, uint32_t scap,
                                                          uint32_t budget, double limit, IndexPlanWords* __restrict__ pw) {
     __shared__ unsigned long long s_tot[4], s_max[4];
@@ -529,7 +526,8 @@ __global__ __launch_bounds__(256) void index_plan_kernel(const uint32_t* __restr
     if (need > budget) f |= kPlanRounds;
     pw->pairs[mode] = tot;
     pw->need[mode] = (uint32_t)(need < budget ? need : budget);
-    if (mode == 1) pw->max_scan = mx;
+    if (mode == 0) pw->max_probe = (uint32_t)mx;
+    else pw->max_scan = mx;
     if (f) pw->flags |= f;
 }
 
@@ -736,13 +734,15 @@ int index_scratch(pg_ctx* ctx, size_t bytes, void** out) {
     return PG_OK;
 }
 
-// slot 17 of one batch: U [nq][nl] | qn [nq] f64 | nqv [nq] | Bkey [nq] | probe rows [nq] | counts [nq] | flag, union / the plan's
-//          words [16] | slice counts [nq][kSlices] | scan threshold [nq]
+// slot 17 of one batch: U [nq][nl] | qn [nq] f64 | nqv [nq] | Bkey [nq] | probe rows [nq] | counts [nq] | the plan's words [16] |
+//          slice counts [nq][kSlices] | scan threshold [nq]
 struct SearchBufs {
     float* U;
     double* qn;
     float* nqv;
-    uint32_t *Bkey, *probe, *dcount, *flag, *cntg;
+    uint32_t *Bkey, *probe, *dcount;
+    IndexPlanWords* pw;
+    uint32_t* cntg;
     float* thr_scan;                     // the probe's K-th scores, frozen for the scan's list selection
 };
 size_t search_bytes(uint32_t nq, uint32_t nl) {
@@ -759,14 +759,14 @@ int search_bufs(pg_ctx* ctx, uint32_t nq, uint32_t nl, SearchBufs* b) {
     b->Bkey = (uint32_t*)(b->nqv + nq);
     b->probe = b->Bkey + nq;
     b->dcount = b->probe + nq;
-    b->flag = b->dcount + nq;            // (8-byte aligned: u_b + 24 nq)
-    b->cntg = b->flag + 16;
+    b->pw = (IndexPlanWords*)(b->dcount + nq);         // (8-byte aligned: u_b + 24 nq)
+    b->cntg = (uint32_t*)b->pw + 16;
     b->thr_scan = (float*)(b->cntg + (size_t)nq * kSlices);
     return PG_OK;
 }
 
 // the bounds of a batch: qn[q] >= ||q|| (and *flag |= 1 for a non-finite query), then U[q][L] — the one launch of the
-// synchronous search, the attached plan and pg_index_bounds
+// search and pg_index_bounds
 int bounds_launch(pg_ctx* ctx, const pg_index* ix, const float* d_q, uint32_t nq, bool l2, double* qn, uint32_t* flag, float* U) {
     const uint32_t nl = ix->n_lists, dim = ix->dim;
     hipStream_t s = ctx->stream;
@@ -779,193 +779,148 @@ int bounds_launch(pg_ctx* ctx, const pg_index* ix, const float* d_q, uint32_t nq
     return PG_OK;
 }
 
-enum Fallback { kNone = 0, kDense, kStale, kNonfinite, kOverflow };
+// The search of one batch, enqueued on ctx->stream: plan init, the L2 query norms, bounds, probe, the probe's count, plan kernel
+// and rounds, the frozen scan threshold, the scan's count and union, plan kernel and rounds, final, the negation for L2.  The
+// device writes its verdict into sb.pw and every round's expansion reads it.  Two round policies:
+//   h_pw null   an attached plan: `budget` rounds per stage on one grid, no host reads (rounds past the verdict's do nothing)
+//   h_pw        the synchronous call (budget unlimited): after each stage's plan kernel the host reads the words into *h_pw; a
+//               flag ends the search there (that stage's pairs cleared: not scored), else the stage runs exactly its rounds,
+//               each on a grid sized to its suspects
+int index_search(pg_ctx* ctx, const pg_index* ix, const float* d_q, uint32_t nq, uint32_t k, bool l2, RecallScratch& rs,
+                 const SearchBufs& sb, uint64_t* d_rows, float* d_sc, uint32_t* d_count, uint32_t budget, IndexPlanWords* h_pw) {
+    const pg_table* t = ix->t;
+    const uint32_t nl = ix->n_lists, dim = t->dim;
+    hipStream_t s = ctx->stream;
+    int rc;
+    index_plan_init_kernel<<<1, kMaxQueries, 0, s>>>(rs.thr, rs.cnt, rs.overflow, sb.pw);
+    PG_HIP(hipGetLastError());
+    if (l2 && (rc = query_norm2_launch(ctx, d_q, nq, dim, sb.nqv))) return rc;
+    if ((rc = bounds_launch(ctx, ix, d_q, nq, l2, sb.qn, &sb.pw->flags, sb.U))) return rc;
+    probe_kernel<<<nq, 1024, 0, s>>>(sb.U, nl, ix->d_off, ix->rows, k, sb.Bkey, sb.probe);
+    count_kernel<<<dim3(kSlices, nq), 256, 0, s>>>(sb.U, nl, ix->d_off, sb.Bkey, rs.thr, 0, sb.cntg);
+    PG_HIP(hipGetLastError());
+    // the dense rule: the scan gathers a full row per pair, the table's pass streams a shadow whose cost grows slowly with the
+    // batch: at 100 M rows the index breaks even at about 0.010 / 0.038 / 0.085 / 0.16 / 0.3-0.5 x rows pairs for 1 / 8 / 32 / 64 /
+    // 256 queries (profiles/index_breakeven.json with profiles/index_sweep_10k.json) — 0.01 x rows x nq^0.6
+    const double limit = ctx->knobs.index_dense_fraction * (double)ix->rows * std::pow((double)nq, 0.6);
+    const uint32_t scap = rs.cap - k;
+    // a round of n suspects per query: one block per 1024, at most max(16, 4096 / nq) (the blocks past a query's suspects return)
+    auto grid = [&](uint64_t n) {
+        return std::max<uint32_t>(1u, (uint32_t)std::min<uint64_t>((n + 1023) / 1024, std::max<uint32_t>(16u, 4096u / nq)));
+    };
+    int cur = 0;
+    // score the stage's lists' rows in rounds of scap per query, keeping each query's best K between rounds
+    auto stage = [&](int mode) -> int {
+        index_plan_kernel<<<1, kMaxQueries, 0, s>>>(sb.cntg, nq, mode, scap, budget, limit, sb.pw);
+        PG_HIP(hipGetLastError());
+        uint32_t rounds = budget;
+        uint64_t most = 0;
+        if (h_pw) {
+            PG_HIP(hipMemcpyAsync(h_pw, sb.pw, sizeof *h_pw, hipMemcpyDeviceToHost, s));
+            PG_HIP(hipStreamSynchronize(s));
+            if (h_pw->flags) {
+                h_pw->pairs[mode] = 0;
+                return PG_OK;
+            }
+            rounds = h_pw->need[mode];
+            most = mode == 0 ? h_pw->max_probe : h_pw->max_scan;
+        }
+        for (uint32_t r = 0; r < rounds; ++r) {
+            expand_kernel<<<dim3(kSlices, nq), 256, 0, s>>>(sb.U, nl, ix->d_off, ix->d_perm, sb.Bkey, sb.thr_scan, mode, sb.cntg, r, scap,
+                                                             rs.susp, rs.susp_cnt, sb.pw);
+            PG_HIP(hipGetLastError());
+            const uint32_t blocks = grid(h_pw ? std::min<uint64_t>(most - (uint64_t)r * scap, scap) : scap);
+            int rc3;
+            if ((rc3 = rescore_launch(ctx, dim, l2, t->d, d_q, rs.thr, rs.susp, rs.susp_cnt, scap, rs.cnt, rs.cand[cur], rs.overflow, rs.cap,
+                                      nq, (uint32_t)ix->rows, l2 ? t->d_nx : nullptr, l2 ? sb.nqv : nullptr, blocks)))
+                return rc3;
+            // (a round without suspects selects the kept list again: the same K keys, the same threshold)
+            if ((rc3 = launch_select(ctx, nq, rs.cand[cur], rs.cand[cur ^ 1], rs.cnt, rs.thr, rs.cap, k, 0))) return rc3;
+            cur ^= 1;
+        }
+        return PG_OK;
+    };
+    if ((rc = stage(0)) || (h_pw && h_pw->flags)) return rc;
+    // the scan: lists outside the probe whose bound reaches the probe's K-th score.  The selection is made ONCE against that
+    // threshold (thr_scan): the per-slice counts and every round's expansion must see the same lists, while rs.thr keeps
+    // rising with the select between rounds and serves only the re-scoring's candidate test.
+    PG_HIP(hipMemcpyAsync(sb.thr_scan, rs.thr, (size_t)nq * 4, hipMemcpyDeviceToDevice, s));
+    count_kernel<<<dim3(kSlices, nq), 256, 0, s>>>(sb.U, nl, ix->d_off, sb.Bkey, sb.thr_scan, 1, sb.cntg);
+    union_kernel<<<(nl + 255) / 256, 256, 0, s>>>(sb.U, nl, nq, ix->d_off, sb.Bkey, sb.thr_scan, &sb.pw->union_rows);
+    PG_HIP(hipGetLastError());
+    if ((rc = stage(1)) || (h_pw && h_pw->flags)) return rc;
+    if ((rc = final_launch(ctx, rs.cand[cur], rs.cnt, rs.cap, nq, k, t->row_offset, d_rows, d_sc, d_count))) return rc;
+    if (l2 && (rc = negate_launch(ctx, d_sc, (uint64_t)nq * k))) return rc;
+    return PG_OK;
+}
 
 int table_pass_locked(pg_ctx* ctx, const pg_table* t, const float* d_q, uint32_t nq, uint32_t k, uint64_t* d_rows, float* d_sc,
                       uint32_t* h_counts, bool l2) {
-    // (never through an attached index: this is the index's own fallback)
-    if (!l2) return recall_dev_locked(ctx, t, d_q, nq, k, d_rows, d_sc, h_counts, nullptr, false, false, nullptr, false, true);
-    for (uint32_t q0 = 0; q0 < nq; q0 += 128) {       // (as pg_recall_topk_l2_dev: at most 128 queries per job)
-        const uint32_t n = nq - q0 < 128 ? nq - q0 : 128;
-        const int rc = recall_dev_locked(ctx, t, d_q + (size_t)q0 * t->dim, n, k, d_rows + (size_t)q0 * k, d_sc + (size_t)q0 * k,
-                                         h_counts + q0, nullptr, false, true, nullptr, false, true);
-        if (rc) return rc;
-    }
-    return PG_OK;
+    RecallOpts o;
+    o.l2 = l2;
+    o.no_index = true;                   // (never through an attached index: this is the index's own fallback)
+    return recall_batches_locked(ctx, t, d_q, nq, k, d_rows, d_sc, h_counts, o);
 }
 
-// one batch (caller holds ctx->mu and the table's shared lock); h_counts: host [nq]
+// one batch, synchronously (caller holds ctx->mu and the table's shared lock); h_counts: host [nq].  A stale, non-finite, dense
+// or overflowing batch is answered by the table's pass.
 int index_recall_locked(pg_ctx* ctx, pg_index* ix, const float* d_q, uint32_t nq, uint32_t k, uint64_t* d_rows, float* d_sc,
                         uint32_t* h_counts, bool l2) {
     const pg_table* t = ix->t;
-    const uint32_t nl = ix->n_lists, dim = t->dim;
-    uint64_t pairs = 0, union_rows = 0, max_scan = 0;
-    Fallback fb = kNone;
+    const uint32_t dim = t->dim;
+    IndexPlanWords w{};                  // the plan words as the host read them last (the pairs of the stages scored)
+    uint64_t pg_index_stats_t::*fb = nullptr;          // the fallback the batch takes
     int rc = PG_OK;
-    auto tally = [&]() {
-        std::lock_guard<std::mutex> g(ix->mu);
-        ix->st.calls++;
-        ix->st.queries += nq;
-        ix->st.pairs_scored += pairs;
-        ix->st.rows_scored += pairs;
-        ix->st.rows_live += union_rows;
-        ix->st.max_query_scan_rows = std::max<uint64_t>(ix->st.max_query_scan_rows, max_scan);
-        if (fb == kDense) ix->st.fallback_dense++;
-        if (fb == kStale) ix->st.fallback_stale++;
-        if (fb == kNonfinite) ix->st.fallback_nonfinite++;
-        if (fb == kOverflow) ix->st.fallback_overflow++;
-    };
-    if (t->generation.load(std::memory_order_relaxed) != ix->gen) fb = kStale;
-    else if (ix->nonfinite) fb = kNonfinite;
-    else if (l2 && dim != 64 && dim != 128) fb = kDense;    // (the table's pass answers with its own error)
-    if (fb == kNone) rc = [&]() -> int {
+    if (t->generation.load(std::memory_order_relaxed) != ix->gen) fb = &pg_index_stats_t::fallback_stale;
+    else if (ix->nonfinite) fb = &pg_index_stats_t::fallback_nonfinite;
+    else if (l2 && dim != 64 && dim != 128) fb = &pg_index_stats_t::fallback_dense;   // (the table's pass answers with its own error)
+    else rc = [&]() -> int {
         RecallScratch rs;
+        SearchBufs sb;
         int rc2;
         if ((rc2 = recall_scratch(ctx, dim, k, &rs))) return rc2;
         if (l2 && (rc2 = ensure_table_nx(ctx, t))) return rc2;
-        SearchBufs sb;
-        if (search_bufs(ctx, nq, nl, &sb)) {
-            fb = kOverflow;
+        if (search_bufs(ctx, nq, ix->n_lists, &sb)) {
+            fb = &pg_index_stats_t::fallback_overflow;
             return PG_OK;
         }
-        float* U = sb.U;
-        double* qn = sb.qn;
-        float* nqv = sb.nqv;
-        uint32_t *Bkey = sb.Bkey, *probe = sb.probe, *dcount = sb.dcount, *flag = sb.flag, *cntg = sb.cntg;
-        unsigned long long* d_union = (unsigned long long*)(flag + 2);
-        float* thr_scan = sb.thr_scan;
-        hipStream_t s = ctx->stream;
-        index_init_kernel<<<1, kMaxQueries, 0, s>>>(rs.thr, rs.cnt, rs.overflow, flag);
-        PG_HIP(hipGetLastError());
-        if (l2 && (rc2 = query_norm2_launch(ctx, d_q, nq, dim, nqv))) return rc2;
-        if ((rc2 = bounds_launch(ctx, ix, d_q, nq, l2, qn, flag, U))) return rc2;
-        probe_kernel<<<nq, 1024, 0, s>>>(U, nl, ix->d_off, ix->rows, k, Bkey, probe);
-        count_kernel<<<dim3(kSlices, nq), 256, 0, s>>>(U, nl, ix->d_off, Bkey, rs.thr, 0, cntg);
-        PG_HIP(hipGetLastError());
-        std::vector<uint32_t> h_cnt((size_t)nq * kSlices);
-        uint32_t h_flag = 0;
-        PG_HIP(hipMemcpyAsync(h_cnt.data(), cntg, h_cnt.size() * 4, hipMemcpyDeviceToHost, s));
-        PG_HIP(hipMemcpyAsync(&h_flag, flag, 4, hipMemcpyDeviceToHost, s));
-        PG_HIP(hipStreamSynchronize(s));
-        if (h_flag) { fb = kNonfinite; return PG_OK; }
-        // the scan gathers a full row per pair, the table's pass streams a shadow whose cost grows slowly with the batch: at 100 M
-        // rows the index breaks even at about 0.010 / 0.038 / 0.085 / 0.16 / 0.3-0.5 x rows pairs for 1 / 8 / 32 / 64 / 256 queries
-        // (profiles/index_breakeven.json with profiles/index_sweep_10k.json) — 0.01 x rows x nq^0.6
-        const double limit = ctx->knobs.index_dense_fraction * (double)ix->rows * std::pow((double)nq, 0.6);
-        const uint32_t scap = rs.cap - k;
-        uint64_t tot_probe = 0;
-        auto sum_counts = [&](uint64_t& total, uint64_t& most) {
-            total = 0;
-            most = 0;
-            for (uint32_t q = 0; q < nq; ++q) {
-                uint64_t v = 0;
-                for (uint32_t g = 0; g < kSlices; ++g) v += h_cnt[(size_t)q * kSlices + g];
-                total += v;
-                most = std::max(most, v);
-            }
-        };
-        uint64_t most = 0;
-        sum_counts(tot_probe, most);
-        if ((double)tot_probe > limit) { fb = kDense; return PG_OK; }
-        int cur = 0;
-        // score the selected lists' rows in rounds of scap per query, keeping each query's best K between rounds
-        auto run = [&](int mode, uint64_t most_q) -> int {
-            for (uint64_t skip = 0; skip < most_q; skip += scap) {
-                const uint64_t this_round = std::min<uint64_t>(most_q - skip, scap);
-                expand_kernel<<<dim3(kSlices, nq), 256, 0, s>>>(U, nl, ix->d_off, ix->d_perm, Bkey, thr_scan, mode, cntg,
-                                                                 (uint32_t)(skip / scap), scap, rs.susp, rs.susp_cnt, nullptr);
-                PG_HIP(hipGetLastError());
-                uint32_t blocks = (uint32_t)((this_round + 1023) / 1024);
-                const uint32_t most_blocks = std::max<uint32_t>(16u, 4096u / nq);
-                blocks = std::max<uint32_t>(1u, std::min(blocks, most_blocks));
-                int rc3;
-                if ((rc3 = rescore_launch(ctx, dim, l2, t->d, d_q, rs.thr, rs.susp, rs.susp_cnt, scap, rs.cnt, rs.cand[cur], rs.overflow,
-                                          rs.cap, nq, (uint32_t)ix->rows, l2 ? t->d_nx : nullptr, l2 ? nqv : nullptr, blocks)))
-                    return rc3;
-                if ((rc3 = launch_select(ctx, nq, rs.cand[cur], rs.cand[cur ^ 1], rs.cnt, rs.thr, rs.cap, k, 0))) return rc3;
-                cur ^= 1;
-            }
-            return PG_OK;
-        };
-        if ((rc2 = run(0, most))) return rc2;
-        pairs += tot_probe;
-        // the scan: lists outside the probe whose bound reaches the probe's K-th score.  The selection is made ONCE against that
-        // threshold (thr_scan): the per-slice counts and every round's expansion must see the same lists, while rs.thr keeps
-        // rising with the select between rounds and serves only the re-scoring's candidate test.
-        PG_HIP(hipMemcpyAsync(thr_scan, rs.thr, (size_t)nq * 4, hipMemcpyDeviceToDevice, s));
-        PG_HIP(hipMemsetAsync(d_union, 0, 8, s));
-        count_kernel<<<dim3(kSlices, nq), 256, 0, s>>>(U, nl, ix->d_off, Bkey, thr_scan, 1, cntg);
-        union_kernel<<<(nl + 255) / 256, 256, 0, s>>>(U, nl, nq, ix->d_off, Bkey, thr_scan, d_union);
-        PG_HIP(hipGetLastError());
-        unsigned long long h_union = 0;
-        PG_HIP(hipMemcpyAsync(h_cnt.data(), cntg, h_cnt.size() * 4, hipMemcpyDeviceToHost, s));
-        PG_HIP(hipMemcpyAsync(&h_union, d_union, 8, hipMemcpyDeviceToHost, s));
-        PG_HIP(hipStreamSynchronize(s));
-        union_rows = h_union;
-        uint64_t tot_scan = 0;
-        sum_counts(tot_scan, most);
-        max_scan = most;
-        if ((double)(tot_probe + tot_scan) > limit) { fb = kDense; return PG_OK; }
-        if ((rc2 = run(1, most))) return rc2;
-        pairs += tot_scan;
-        if ((rc2 = final_launch(ctx, rs.cand[cur], rs.cnt, rs.cap, nq, k, t->row_offset, d_rows, d_sc, dcount))) return rc2;
-        if (l2 && (rc2 = negate_launch(ctx, d_sc, (uint64_t)nq * k))) return rc2;
+        if ((rc2 = index_search(ctx, ix, d_q, nq, k, l2, rs, sb, d_rows, d_sc, sb.dcount, ~0u, &w))) return rc2;
+        if (w.flags & kPlanNonfinite) fb = &pg_index_stats_t::fallback_nonfinite;
+        else if (w.flags & kPlanDense) fb = &pg_index_stats_t::fallback_dense;
+        if (fb) return PG_OK;
         uint32_t h_ovf = 0;
-        PG_HIP(hipMemcpyAsync(&h_ovf, rs.overflow, 4, hipMemcpyDeviceToHost, s));
-        PG_HIP(hipMemcpyAsync(h_counts, dcount, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
-        PG_HIP(hipStreamSynchronize(s));
-        if (h_ovf) fb = kOverflow;
+        PG_HIP(hipMemcpyAsync(&h_ovf, rs.overflow, 4, hipMemcpyDeviceToHost, ctx->stream));
+        PG_HIP(hipMemcpyAsync(h_counts, sb.dcount, (size_t)nq * 4, hipMemcpyDeviceToHost, ctx->stream));
+        PG_HIP(hipStreamSynchronize(ctx->stream));
+        if (h_ovf) fb = &pg_index_stats_t::fallback_overflow;
         return PG_OK;
     }();
-    if (rc == PG_OK && fb != kNone) rc = table_pass_locked(ctx, t, d_q, nq, k, d_rows, d_sc, h_counts, l2);
-    if (rc == PG_OK) tally();
-    return rc;
-}
-
-int index_check(const char* who, pg_ctx* ctx, const pg_index* ix, const void* q, const void* rows, const void* sc, uint32_t nq,
-                uint32_t k, bool l2) {
-    PG_REQUIRE(ctx && ix && q && rows && sc, "%s: NULL argument", who);
-    PG_REQUIRE(nq >= 1 && nq <= (uint32_t)kMaxQueries, "%s: nq=%u must be in [1,%d]", who, nq, kMaxQueries);
-    PG_REQUIRE(l2 || ix->dim <= 128 || nq <= 32, "%s: dim %u supports at most 32 queries per call", who, ix->dim);
-    if (k < 1 || k > 16384) {
-        set_error("%s: k=%u unsupported (1..16384)", who, k);
-        return PG_ERR_UNSUPPORTED;
-    }
+    if (rc == PG_OK && fb) rc = table_pass_locked(ctx, t, d_q, nq, k, d_rows, d_sc, h_counts, l2);
+    if (rc != PG_OK) return rc;
+    std::lock_guard<std::mutex> g(ix->mu);
+    ix->st.calls++;
+    ix->st.queries += nq;
+    ix->st.pairs_scored += w.pairs[0] + w.pairs[1];
+    ix->st.rows_scored += w.pairs[0] + w.pairs[1];
+    ix->st.rows_live += w.union_rows;
+    ix->st.max_query_scan_rows = std::max<uint64_t>(ix->st.max_query_scan_rows, w.max_scan);
+    if (fb) ix->st.*fb += 1;
     return PG_OK;
 }
 
-int index_dev(const char* who, pg_ctx* ctx, const pg_index* ixc, const float* d_q, uint32_t nq, uint32_t k, uint64_t* d_rows, float* d_sc,
-              uint32_t* out_count, bool l2) {
+// pg_index_recall_topk[_l2][_dev]: host, the queries and outputs are host memory (staged through scratch slot 5)
+int index_entry(const char* who, pg_ctx* ctx, const pg_index* ixc, const float* q, uint32_t nq, uint32_t k, uint64_t* rows, float* sc,
+                uint32_t* out_count, bool l2, bool host) {
     int rc;
-    if ((rc = index_check(who, ctx, ixc, d_q, d_rows, d_sc, nq, k, l2))) return rc;
+    if ((rc = recall_check(who, ctx, ixc, q, rows, sc, nq, k, l2))) return rc;
     pg_index* ix = const_cast<pg_index*>(ixc);          // (only the statistics change)
     std::lock_guard<std::mutex> g(ctx->mu);
     TableRead tr(ix->t->rw);
     uint32_t counts[kMaxQueries];
-    if ((rc = index_recall_locked(ctx, ix, d_q, nq, k, d_rows, d_sc, counts, l2))) return rc;
-    if (out_count) memcpy(out_count, counts, (size_t)nq * 4);
-    return PG_OK;
-}
-
-int index_host(const char* who, pg_ctx* ctx, const pg_index* ixc, const float* queries, uint32_t nq, uint32_t k, uint64_t* out_rows,
-               float* out_sc, uint32_t* out_count, bool l2) {
-    int rc;
-    if ((rc = index_check(who, ctx, ixc, queries, out_rows, out_sc, nq, k, l2))) return rc;
-    pg_index* ix = const_cast<pg_index*>(ixc);
-    std::lock_guard<std::mutex> g(ctx->mu);
-    TableRead tr(ix->t->rw);
-    void* buf;
-    const size_t qb = (size_t)nq * ix->dim * 4, rb = (size_t)nq * k * 8, sb = (size_t)nq * k * 4;
-    if ((rc = scratch_reserve(ctx, 5, qb + rb + sb + 64, &buf))) return rc;
-    float* d_q = (float*)buf;
-    uint64_t* d_rows = (uint64_t*)((char*)buf + ((qb + 15) & ~(size_t)15));
-    float* d_sc = (float*)((char*)d_rows + rb);
-    PG_HIP(hipMemcpyAsync(d_q, queries, qb, hipMemcpyHostToDevice, ctx->stream));
-    uint32_t counts[kMaxQueries];
-    if ((rc = index_recall_locked(ctx, ix, d_q, nq, k, d_rows, d_sc, counts, l2))) return rc;
-    PG_HIP(hipMemcpyAsync(out_rows, d_rows, rb, hipMemcpyDeviceToHost, ctx->stream));
-    PG_HIP(hipMemcpyAsync(out_sc, d_sc, sb, hipMemcpyDeviceToHost, ctx->stream));
-    PG_HIP(hipStreamSynchronize(ctx->stream));
+    auto run = [&](const float* d_q, uint64_t* d_rows, float* d_sc) {
+        return index_recall_locked(ctx, ix, d_q, nq, k, d_rows, d_sc, counts, l2);
+    };
+    if ((rc = host ? recall_staged(ctx, ix->dim, q, nq, k, rows, sc, run) : run(q, rows, sc))) return rc;
     if (out_count) memcpy(out_count, counts, (size_t)nq * 4);
     return PG_OK;
 }
@@ -1008,21 +963,16 @@ int index_plan_prepare(RecallJob* j) {
     return PG_OK;
 }
 
-// index_recall_locked's launches without its three synchronisations: a fixed number of rounds (index_plan_rounds) for the probe
-// and for the scan, whose kernels read the plan kernel's verdict; the outputs, the status block and its copy as any plan's
+// index_search with the attached plan's round policy (index_plan_rounds per stage, no host reads) between the job's events; the
+// outputs, the status block and its copy as any plan's
 int index_plan_enqueue(RecallJob* j, uint32_t status_words) {
     pg_ctx* ctx = j->ctx;
-    const pg_table* t = j->t;
-    const pg_index* ix = j->ix;
-    const uint32_t nq = j->nq, k = j->k, nl = ix->n_lists, dim = t->dim;
-    const bool l2 = j->l2;
-    const float* d_q = j->d_queries;
+    const uint32_t nq = j->nq;
     RecallScratch& rs = j->rs;
     hipStream_t s = ctx->stream;
     int rc;
     SearchBufs sb;
-    if ((rc = search_bufs(ctx, nq, nl, &sb))) return rc;      // (reserved by index_plan_prepare: only grows)
-    IndexPlanWords* pw = reinterpret_cast<IndexPlanWords*>(sb.flag);
+    if ((rc = search_bufs(ctx, nq, j->ix->n_lists, &sb))) return rc;      // (reserved by index_plan_prepare: only grows)
     while (j->events->size() < 2) {
         hipEvent_t e;
         PG_HIP(hipEventCreate(&e));
@@ -1030,48 +980,11 @@ int index_plan_enqueue(RecallJob* j, uint32_t status_words) {
     }
     j->timers = !ctx->timers_off;
     if (j->timers) PG_HIP(hipEventRecord((*j->events)[0], s));
-    index_plan_init_kernel<<<1, kMaxQueries, 0, s>>>(rs.thr, rs.cnt, rs.overflow, pw);
-    PG_HIP(hipGetLastError());
-    if (l2 && (rc = query_norm2_launch(ctx, d_q, nq, dim, sb.nqv))) return rc;
-    if ((rc = bounds_launch(ctx, ix, d_q, nq, l2, sb.qn, &pw->flags, sb.U))) return rc;
-    probe_kernel<<<nq, 1024, 0, s>>>(sb.U, nl, ix->d_off, ix->rows, k, sb.Bkey, sb.probe);
-    count_kernel<<<dim3(kSlices, nq), 256, 0, s>>>(sb.U, nl, ix->d_off, sb.Bkey, rs.thr, 0, sb.cntg);
-    PG_HIP(hipGetLastError());
-    // (the limit of index_recall_locked, computed the same way)
-    const double limit = ctx->knobs.index_dense_fraction * (double)ix->rows * std::pow((double)nq, 0.6);
     const uint32_t budget = ctx->knobs.index_plan_rounds ? ctx->knobs.index_plan_rounds : 1u;
-    const uint32_t scap = rs.cap - k;
-    // one grid for every round: as many blocks as the largest round needs (the blocks past a round's suspects return at once)
-    const uint32_t blocks = std::max<uint32_t>(1u, std::min<uint32_t>(std::max<uint32_t>(16u, 4096u / nq), (scap + 1023) / 1024));
-    int cur = 0;
-    auto rounds = [&](int mode) -> int {
-        index_plan_kernel<<<1, kMaxQueries, 0, s>>>(sb.cntg, nq, mode, scap, budget, limit, pw);
-        PG_HIP(hipGetLastError());
-        for (uint32_t r = 0; r < budget; ++r) {
-            expand_kernel<<<dim3(kSlices, nq), 256, 0, s>>>(sb.U, nl, ix->d_off, ix->d_perm, sb.Bkey, sb.thr_scan, mode, sb.cntg, r, scap,
-                                                             rs.susp, rs.susp_cnt, pw);
-            PG_HIP(hipGetLastError());
-            int rc3;
-            if ((rc3 = rescore_launch(ctx, dim, l2, t->d, d_q, rs.thr, rs.susp, rs.susp_cnt, scap, rs.cnt, rs.cand[cur], rs.overflow, rs.cap,
-                                      nq, (uint32_t)ix->rows, l2 ? t->d_nx : nullptr, l2 ? sb.nqv : nullptr, blocks)))
-                return rc3;
-            // (a round without suspects selects the kept list again: the same K keys, the same threshold)
-            if ((rc3 = launch_select(ctx, nq, rs.cand[cur], rs.cand[cur ^ 1], rs.cnt, rs.thr, rs.cap, k, 0))) return rc3;
-            cur ^= 1;
-        }
-        return PG_OK;
-    };
-    if ((rc = rounds(0))) return rc;
-    // the scan's lists, chosen once against the probe's thresholds (thr_scan)
-    PG_HIP(hipMemcpyAsync(sb.thr_scan, rs.thr, (size_t)nq * 4, hipMemcpyDeviceToDevice, s));
-    count_kernel<<<dim3(kSlices, nq), 256, 0, s>>>(sb.U, nl, ix->d_off, sb.Bkey, sb.thr_scan, 1, sb.cntg);
-    union_kernel<<<(nl + 255) / 256, 256, 0, s>>>(sb.U, nl, nq, ix->d_off, sb.Bkey, sb.thr_scan, &pw->union_rows);
-    PG_HIP(hipGetLastError());
-    if ((rc = rounds(1))) return rc;
-    if ((rc = final_launch(ctx, rs.cand[cur], rs.cnt, rs.cap, nq, k, t->row_offset, j->d_out_rows, j->d_out_scores, j->d_count))) return rc;
-    if (l2 && (rc = negate_launch(ctx, j->d_out_scores, (uint64_t)nq * k))) return rc;
+    if ((rc = index_search(ctx, j->ix, j->d_queries, nq, j->k, j->l2, rs, sb, j->d_out_rows, j->d_out_scores, j->d_count, budget, nullptr)))
+        return rc;
     if (j->timers) PG_HIP(hipEventRecord((*j->events)[1], s));
-    index_status_kernel<<<1, kMaxQueries, 0, s>>>(rs.overflow, nq, pw, rs.status);
+    index_status_kernel<<<1, kMaxQueries, 0, s>>>(rs.overflow, nq, sb.pw, rs.status);
     PG_HIP(hipGetLastError());
     if (j->d_out_count) PG_HIP(hipMemcpyAsync(j->d_out_count, j->d_count, 4 * (size_t)nq, hipMemcpyDeviceToDevice, s));
     PG_HIP(hipMemcpyAsync(j->h_status, rs.status, 4 * (size_t)status_words, hipMemcpyDeviceToHost, s));
@@ -1172,22 +1085,22 @@ int pg_index_destroy(pg_ctx* ctx, pg_index* ix) {
 
 int pg_index_recall_topk(pg_ctx* ctx, const pg_index* ix, const float* queries, uint32_t nq, uint32_t k, uint64_t* out_rows,
                          float* out_scores, uint32_t* out_count) {
-    return pg::index_host("pg_index_recall_topk", ctx, ix, queries, nq, k, out_rows, out_scores, out_count, false);
+    return pg::index_entry("pg_index_recall_topk", ctx, ix, queries, nq, k, out_rows, out_scores, out_count, false, true);
 }
 
 int pg_index_recall_topk_dev(pg_ctx* ctx, const pg_index* ix, const float* d_queries, uint32_t nq, uint32_t k, uint64_t* d_out_rows,
                              float* d_out_scores, uint32_t* out_count) {
-    return pg::index_dev("pg_index_recall_topk_dev", ctx, ix, d_queries, nq, k, d_out_rows, d_out_scores, out_count, false);
+    return pg::index_entry("pg_index_recall_topk_dev", ctx, ix, d_queries, nq, k, d_out_rows, d_out_scores, out_count, false, false);
 }
 
 int pg_index_recall_topk_l2(pg_ctx* ctx, const pg_index* ix, const float* queries, uint32_t nq, uint32_t k, uint64_t* out_rows,
                             float* out_dist, uint32_t* out_count) {
-    return pg::index_host("pg_index_recall_topk_l2", ctx, ix, queries, nq, k, out_rows, out_dist, out_count, true);
+    return pg::index_entry("pg_index_recall_topk_l2", ctx, ix, queries, nq, k, out_rows, out_dist, out_count, true, true);
 }
 
 int pg_index_recall_topk_l2_dev(pg_ctx* ctx, const pg_index* ix, const float* d_queries, uint32_t nq, uint32_t k, uint64_t* d_out_rows,
                                 float* d_out_dist, uint32_t* out_count) {
-    return pg::index_dev("pg_index_recall_topk_l2_dev", ctx, ix, d_queries, nq, k, d_out_rows, d_out_dist, out_count, true);
+    return pg::index_entry("pg_index_recall_topk_l2_dev", ctx, ix, d_queries, nq, k, d_out_rows, d_out_dist, out_count, true, false);
 }
 
 int pg_index_stats(const pg_index* ixc, pg_index_stats_t* out) {
@@ -1236,8 +1149,8 @@ int pg_index_bounds(pg_ctx* ctx, const pg_index* ix, const float* queries, uint3
     pg::SearchBufs sb;
     if ((rc = pg::search_bufs(ctx, nq, ix->n_lists, &sb))) return rc;
     PG_HIP(hipMemcpyAsync(buf, queries, qb, hipMemcpyHostToDevice, s));
-    PG_HIP(hipMemsetAsync(sb.flag, 0, 4, s));
-    if ((rc = pg::bounds_launch(ctx, ix, (const float*)buf, nq, l2 != 0, sb.qn, sb.flag, sb.U))) return rc;
+    PG_HIP(hipMemsetAsync(&sb.pw->flags, 0, 4, s));
+    if ((rc = pg::bounds_launch(ctx, ix, (const float*)buf, nq, l2 != 0, sb.qn, &sb.pw->flags, sb.U))) return rc;
     PG_HIP(hipMemcpyAsync(out, sb.U, (size_t)nq * ix->n_lists * 4, hipMemcpyDeviceToHost, s));
     PG_HIP(hipStreamSynchronize(s));
     return PG_OK;

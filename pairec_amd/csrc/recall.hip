@@ -3352,12 +3352,17 @@ void recall_job_finish(RecallJob* j) {
 int recall_patch_failed_locked(RecallJob* j, uint32_t* counts) {
     pg_ctx* ctx = j->ctx;
     const std::vector<uint32_t> failed = j->failed;
+    RecallOpts o;
+    o.skip_pilot = true;
+    o.l2 = j->l2;
+    o.filter = j->filter.col ? &j->filter : nullptr;
+    o.exact_only = j->exact_only;
+    o.no_index = j->no_index;
     for (uint32_t q : failed) {
         uint32_t cnt = 0;
         int rc;
         if ((rc = recall_dev_locked(ctx, j->t, j->d_queries + (size_t)q * j->t->dim, 1, j->k, j->d_out_rows + (size_t)q * j->k,
-                                    j->d_out_scores + (size_t)q * j->k, &cnt, j->d_out_count ? j->d_out_count + q : nullptr, true, j->l2,
-                                    j->filter.col ? &j->filter : nullptr, j->exact_only, j->no_index)))
+                                    j->d_out_scores + (size_t)q * j->k, &cnt, j->d_out_count ? j->d_out_count + q : nullptr, o)))
             return rc;
         counts[q] = cnt;
     }
@@ -3368,14 +3373,13 @@ int recall_patch_failed_locked(RecallJob* j, uint32_t* counts) {
 // the whole recall for one batch of queries, verified before it returns; all pointers are device pointers
 int recall_dev_locked(pg_ctx* ctx, const pg_table* t, const float* d_queries, uint32_t nq,
                       uint32_t k, uint64_t* d_out_rows, float* d_out_scores,
-                      uint32_t* out_count, uint32_t* d_out_count, bool skip_pilot, bool l2, const RowFilter* filter, bool exact_only,
-                      bool no_index) {
+                      uint32_t* out_count, uint32_t* d_out_count, const RecallOpts& o) {
     RecallJob j;
-    j.exact_only = exact_only;
-    j.no_index = no_index;
-    j.skip_pilot = skip_pilot;
-    j.l2 = l2;
-    if (filter) j.filter = *filter;
+    j.exact_only = o.exact_only;
+    j.no_index = o.no_index;
+    j.skip_pilot = o.skip_pilot;
+    j.l2 = o.l2;
+    if (o.filter) j.filter = *o.filter;
     j.ctx = ctx;
     j.t = t;
     j.d_queries = d_queries;
@@ -3407,6 +3411,33 @@ int recall_dev_locked(pg_ctx* ctx, const pg_table* t, const float* d_queries, ui
         for (uint32_t q = 0; q < nq; ++q) out_count[q] = counts[q];
     recall_job_finish(&j);
     return PG_OK;
+}
+
+int recall_batches_locked(pg_ctx* ctx, const pg_table* t, const float* d_queries, uint32_t nq, uint32_t k, uint64_t* d_out_rows,
+                          float* d_out_scores, uint32_t* out_count, const RecallOpts& o) {
+    const uint32_t step = o.l2 ? 128u : (uint32_t)kMaxQueries;
+    for (uint32_t q0 = 0; q0 < nq; q0 += step) {
+        const uint32_t n = nq - q0 < step ? nq - q0 : step;
+        const int rc = recall_dev_locked(ctx, t, d_queries + (size_t)q0 * t->dim, n, k, d_out_rows + (size_t)q0 * k,
+                                         d_out_scores + (size_t)q0 * k, out_count ? out_count + q0 : nullptr, nullptr, o);
+        if (rc) return rc;
+    }
+    return PG_OK;
+}
+
+// pg_recall_topk[_l2][_dev]: host, the queries and outputs are host memory (staged through scratch slot 5)
+int recall_entry(const char* who, pg_ctx* ctx, const pg_table* t, const float* q, uint32_t nq, uint32_t k, uint64_t* rows, float* sc,
+                 uint32_t* out_count, bool l2, bool host) {
+    int rc;
+    if ((rc = recall_check(who, ctx, t, q, rows, sc, nq, k, l2))) return rc;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    TableRead tr(t->rw);
+    RecallOpts o;
+    o.l2 = l2;
+    auto run = [&](const float* d_q, uint64_t* d_rows, float* d_sc) {
+        return recall_batches_locked(ctx, t, d_q, nq, k, d_rows, d_sc, out_count, o);
+    };
+    return host ? recall_staged(ctx, t->dim, q, nq, k, rows, sc, run) : run(q, rows, sc);
 }
 
 int topk_merge_strided_locked(pg_ctx* ctx, const uint64_t* d_rows, const float* d_scores, uint32_t nq, uint32_t nlists,
@@ -3498,42 +3529,12 @@ int pg_table_screen_info(pg_ctx* ctx, const pg_table* t, int* out_elem_bytes, fl
 
 int pg_recall_topk_dev(pg_ctx* ctx, const pg_table* t, const float* d_queries, uint32_t nq,
                        uint32_t k, uint64_t* d_out_rows, float* d_out_scores, uint32_t* out_count) {
-    PG_REQUIRE(ctx && t && d_queries && d_out_rows && d_out_scores, "pg_recall_topk_dev: NULL argument");
-    PG_REQUIRE(nq >= 1 && nq <= (uint32_t)pg::kMaxQueries, "pg_recall_topk_dev: nq=%u must be in [1,%d]", nq, pg::kMaxQueries);
-    PG_REQUIRE(t->dim <= 128 || nq <= 32, "pg_recall_topk_dev: dim %u supports at most 32 queries per call", t->dim);
-    if (k < 1 || k > 16384) {
-        pg::set_error("pg_recall_topk_dev: k=%u unsupported (1..16384)", k);
-        return PG_ERR_UNSUPPORTED;
-    }
-    std::lock_guard<std::mutex> g(ctx->mu);
-    pg::TableRead tr(t->rw);
-    return pg::recall_dev_locked(ctx, t, d_queries, nq, k, d_out_rows, d_out_scores, out_count, nullptr);
+    return pg::recall_entry("pg_recall_topk_dev", ctx, t, d_queries, nq, k, d_out_rows, d_out_scores, out_count, false, false);
 }
 
 int pg_recall_topk(pg_ctx* ctx, const pg_table* t, const float* queries, uint32_t nq, uint32_t k,
                    uint64_t* out_rows, float* out_scores, uint32_t* out_count) {
-    PG_REQUIRE(ctx && t && queries && out_rows && out_scores, "pg_recall_topk: NULL argument");
-    PG_REQUIRE(nq >= 1 && nq <= (uint32_t)pg::kMaxQueries, "pg_recall_topk: nq=%u must be in [1,%d]", nq, pg::kMaxQueries);
-    PG_REQUIRE(t->dim <= 128 || nq <= 32, "pg_recall_topk: dim %u supports at most 32 queries per call", t->dim);
-    if (k < 1 || k > 16384) {
-        pg::set_error("pg_recall_topk: k=%u unsupported (1..16384)", k);
-        return PG_ERR_UNSUPPORTED;
-    }
-    std::lock_guard<std::mutex> g(ctx->mu);
-    pg::TableRead tr(t->rw);
-    void* buf;
-    int rc;
-    const size_t qb = (size_t)nq * t->dim * 4, rb = (size_t)nq * k * 8, sb = (size_t)nq * k * 4;
-    if ((rc = pg::scratch_reserve(ctx, 5, qb + rb + sb + 64, &buf))) return rc;
-    float* d_q = (float*)buf;
-    uint64_t* d_rows = (uint64_t*)((char*)buf + ((qb + 15) & ~(size_t)15));
-    float* d_sc = (float*)((char*)d_rows + rb);
-    PG_HIP(hipMemcpyAsync(d_q, queries, qb, hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = pg::recall_dev_locked(ctx, t, d_q, nq, k, d_rows, d_sc, out_count, nullptr))) return rc;
-    PG_HIP(hipMemcpyAsync(out_rows, d_rows, rb, hipMemcpyDeviceToHost, ctx->stream));
-    PG_HIP(hipMemcpyAsync(out_scores, d_sc, sb, hipMemcpyDeviceToHost, ctx->stream));
-    PG_HIP(hipStreamSynchronize(ctx->stream));
-    return PG_OK;
+    return pg::recall_entry("pg_recall_topk", ctx, t, queries, nq, k, out_rows, out_scores, out_count, false, true);
 }
 
 // HologresVectorRecallV2 (service/recall/hologres_vector_recall_v2.go:23,96-206): "SELECT id, pm_approx_squared_euclidean_distance
@@ -3542,52 +3543,12 @@ int pg_recall_topk(pg_ctx* ctx, const pg_table* t, const float* queries, uint32_
 // every sum a k-ascending fp32 fmaf chain; ties by row ascending; slots beyond the table's rows: row UINT64_MAX, distance +inf.
 int pg_recall_topk_l2_dev(pg_ctx* ctx, const pg_table* t, const float* d_queries, uint32_t nq, uint32_t k, uint64_t* d_out_rows,
                           float* d_out_dist, uint32_t* out_count) {
-    PG_REQUIRE(ctx && t && d_queries && d_out_rows && d_out_dist, "pg_recall_topk_l2_dev: NULL argument");
-    PG_REQUIRE(nq >= 1 && nq <= (uint32_t)pg::kMaxQueries, "pg_recall_topk_l2_dev: nq=%u must be in [1,%d]", nq, pg::kMaxQueries);
-    if (k < 1 || k > 16384) {
-        pg::set_error("pg_recall_topk_l2_dev: k=%u unsupported (1..16384)", k);
-        return PG_ERR_UNSUPPORTED;
-    }
-    std::lock_guard<std::mutex> g(ctx->mu);
-    pg::TableRead tr(t->rw);
-    // (the screened pass serves up to 128 queries; the exact scan runs groups of 64 either way: at most 128 per job)
-    for (uint32_t q0 = 0; q0 < nq; q0 += 128) {
-        const uint32_t n = nq - q0 < 128 ? nq - q0 : 128;
-        const int rc = pg::recall_dev_locked(ctx, t, d_queries + (size_t)q0 * t->dim, n, k, d_out_rows + (size_t)q0 * k,
-                                             d_out_dist + (size_t)q0 * k, out_count ? out_count + q0 : nullptr, nullptr, false, true);
-        if (rc) return rc;
-    }
-    return PG_OK;
+    return pg::recall_entry("pg_recall_topk_l2_dev", ctx, t, d_queries, nq, k, d_out_rows, d_out_dist, out_count, true, false);
 }
 
 int pg_recall_topk_l2(pg_ctx* ctx, const pg_table* t, const float* queries, uint32_t nq, uint32_t k, uint64_t* out_rows,
                       float* out_dist, uint32_t* out_count) {
-    PG_REQUIRE(ctx && t && queries && out_rows && out_dist, "pg_recall_topk_l2: NULL argument");
-    PG_REQUIRE(nq >= 1 && nq <= (uint32_t)pg::kMaxQueries, "pg_recall_topk_l2: nq=%u must be in [1,%d]", nq, pg::kMaxQueries);
-    if (k < 1 || k > 16384) {
-        pg::set_error("pg_recall_topk_l2: k=%u unsupported (1..16384)", k);
-        return PG_ERR_UNSUPPORTED;
-    }
-    std::lock_guard<std::mutex> g(ctx->mu);
-    pg::TableRead tr(t->rw);
-    void* buf;
-    int rc;
-    const size_t qb = (size_t)nq * t->dim * 4, rb = (size_t)nq * k * 8, sb = (size_t)nq * k * 4;
-    if ((rc = pg::scratch_reserve(ctx, 5, qb + rb + sb + 64, &buf))) return rc;
-    float* d_q = (float*)buf;
-    uint64_t* d_rows = (uint64_t*)((char*)buf + ((qb + 15) & ~(size_t)15));
-    float* d_sc = (float*)((char*)d_rows + rb);
-    PG_HIP(hipMemcpyAsync(d_q, queries, qb, hipMemcpyHostToDevice, ctx->stream));
-    for (uint32_t q0 = 0; q0 < nq; q0 += 128) {
-        const uint32_t n = nq - q0 < 128 ? nq - q0 : 128;
-        if ((rc = pg::recall_dev_locked(ctx, t, d_q + (size_t)q0 * t->dim, n, k, d_rows + (size_t)q0 * k, d_sc + (size_t)q0 * k,
-                                        out_count ? out_count + q0 : nullptr, nullptr, false, true)))
-            return rc;
-    }
-    PG_HIP(hipMemcpyAsync(out_rows, d_rows, rb, hipMemcpyDeviceToHost, ctx->stream));
-    PG_HIP(hipMemcpyAsync(out_dist, d_sc, sb, hipMemcpyDeviceToHost, ctx->stream));
-    PG_HIP(hipStreamSynchronize(ctx->stream));
-    return PG_OK;
+    return pg::recall_entry("pg_recall_topk_l2", ctx, t, queries, nq, k, out_rows, out_dist, out_count, true, true);
 }
 
 // A Hologres vector recall WITH its WhereClause (HologresVectorConf.WhereClause, recconf.go:492-497; the SQL of
@@ -3633,7 +3594,6 @@ int pg_recall_topk_where(pg_ctx* ctx, const pg_table* t, const pg_features* fs, 
     uint32_t *d_blk, *d_grp, cblocks, admitted;
     if ((rc = pg::filter_count_locked(ctx, f, t->rows, &d_blk, &d_grp, &cblocks, &admitted))) return rc;
     f.admitted = admitted;
-    const uint32_t step = metric == 1 ? 128u : (uint32_t)pg::kMaxQueries;
     if (admitted == 0) {
         // nothing passes: every slot is padding (row UINT64_MAX, score -inf / distance +inf), every count 0
         pg::recall_pad_kernel<<<(uint32_t)(((size_t)nq * k + 255) / 256), 256, 0, ctx->stream>>>(d_rows, d_sc, (size_t)nq * k, metric == 1);
@@ -3670,23 +3630,19 @@ int pg_recall_topk_where(pg_ctx* ctx, const pg_table* t, const pg_features* fs, 
             ct.nx_valid = true;
         }
         PG_HIP(hipGetLastError());
-        for (uint32_t q0 = 0; q0 < nq; q0 += step) {
-            const uint32_t n = nq - q0 < step ? nq - q0 : step;
-            if ((rc = pg::recall_dev_locked(ctx, &ct, d_q + (size_t)q0 * t->dim, n, k, d_rows + (size_t)q0 * k, d_sc + (size_t)q0 * k,
-                                            out_count ? out_count + q0 : nullptr, nullptr, false, metric == 1, nullptr, true)))
-                return rc;
-        }
+        pg::RecallOpts o;
+        o.l2 = metric == 1;
+        o.exact_only = true;
+        if ((rc = pg::recall_batches_locked(ctx, &ct, d_q, nq, k, d_rows, d_sc, out_count, o))) return rc;
         pg::compact_map_rows_kernel<<<(uint32_t)(((size_t)nq * k + 255) / 256), 256, 0, ctx->stream>>>(d_rows, (uint64_t)nq * k, d_ids, t->row_offset, admitted);
         PG_HIP(hipGetLastError());
         ct.d = nullptr;
         ct.d_nx = nullptr;
     } else {
-        for (uint32_t q0 = 0; q0 < nq; q0 += step) {
-            const uint32_t n = nq - q0 < step ? nq - q0 : step;
-            if ((rc = pg::recall_dev_locked(ctx, t, d_q + (size_t)q0 * t->dim, n, k, d_rows + (size_t)q0 * k, d_sc + (size_t)q0 * k,
-                                            out_count ? out_count + q0 : nullptr, nullptr, false, metric == 1, &f)))
-                return rc;
-        }
+        pg::RecallOpts o;
+        o.l2 = metric == 1;
+        o.filter = &f;
+        if ((rc = pg::recall_batches_locked(ctx, t, d_q, nq, k, d_rows, d_sc, out_count, o))) return rc;
     }
     PG_HIP(hipMemcpyAsync(out_rows, d_rows, rb, hipMemcpyDeviceToHost, ctx->stream));
     PG_HIP(hipMemcpyAsync(out_scores, d_sc, sb, hipMemcpyDeviceToHost, ctx->stream));

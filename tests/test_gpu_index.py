@@ -137,7 +137,8 @@ def test_mixture_exact_and_pruned(ctx, mixture):
 
 def test_scan_in_several_rounds(ctx):
     """A query whose live lists hold more rows than one round of suspects (2^19 per query): the scan runs in rounds with a select
-    between them, the running threshold rises, and the lists chosen for the scan must stay the ones counted after the probe."""
+    between them, the running threshold rises, and the lists chosen for the scan must stay the ones counted after the probe.
+    The synchronous call's rounds are not bounded by index_plan_rounds (an attached plan's budget): at 1 it still serves."""
     n, d = 3_000_000, 64
     t = pa.Table(ctx, n, d)
     t.fill_synthetic(o.SEED_TABLE)
@@ -146,19 +147,21 @@ def test_scan_in_several_rounds(ctx):
     ix = pa.Index(ctx, t, n_lists=12)
     ctx.set_option("index_dense_fraction", 1e6)          # wide lists: every batch would otherwise take the table's pass
     try:
-        for nq, k in ((1, 5000), (4, 3000)):
+        for plan_rounds in (1, 2):                       # (2: the default)
+            ctx.set_option("index_plan_rounds", plan_rounds)
+            for nq, k in ((1, 5000), (4, 3000)):
+                b = ix.stats()
+                assert_same(ix.recall_topk(q[:nq], k), *o.recall_topk(tab, q[:nq], k))
+                assert_served(delta(ix, b))
             b = ix.stats()
-            assert_same(ix.recall_topk(q[:nq], k), *o.recall_topk(tab, q[:nq], k))
-            dd = delta(ix, b)
-            assert dd["fallback_dense"] == 0 and dd["fallback_overflow"] == 0, dd
-        b = ix.stats()
-        assert_same(ix.recall_topk_l2(q, 2000), *o.recall_topk_l2(tab, q, 2000), l2=True)
-        assert delta(ix, b)["fallback_dense"] == 0
+            assert_same(ix.recall_topk_l2(q, 2000), *o.recall_topk_l2(tab, q, 2000), l2=True)
+            assert_served(delta(ix, b))
+            st = ix.stats()
+            assert st["max_query_scan_rows"] > 2 ** 19, st
+            assert st["rows_live"] > 0
     finally:
         ctx.set_option("index_dense_fraction", DENSE_DEFAULT)
-    st = ix.stats()
-    assert st["max_query_scan_rows"] > 2 ** 19, st
-    assert st["rows_live"] > 0
+        ctx.set_option("index_plan_rounds", 2)
     ix.destroy()
     t.destroy()
 
