@@ -87,7 +87,10 @@ int pg_synchronize(pg_ctx* ctx);
  * around the recall plan, its scan launches and the rank stage — pg_stats' last_*_ms and pg_last_scan_kernel_ms stop moving, a
  * small batch's step gets 40-60 us shorter; a coalescer's batches never record them, see there); for recalls through a pg_index
  * "index_dense_fraction" (default 0.01: a batch of nq queries whose live (row, query) pairs exceed this x rows x nq^0.6 takes
- * the table's pass), and for an attached index "index_plan_rounds" / "index_skip_batches" (see pg_index_attach).
+ * the table's pass), and for an attached index "index_plan_rounds" / "index_skip_batches" (see pg_index_attach); for filtered
+ * recalls through an index (pg_index_recall_topk_where) "index_where_cache" (default 4 filtered lists kept per index; 0 = built
+ * per call and freed after it) and "index_route_where" (default 0; 1: pg_recall_topk_where on a table whose attached index is
+ * current searches that index, synchronously).
  * value is parsed as a number. */
 int pg_set_option(pg_ctx* ctx, const char* name, const char* value);
 int pg_device_malloc(pg_ctx* ctx, size_t bytes, void** out);
@@ -449,7 +452,8 @@ int pg_index_stats(const pg_index* ix, pg_index_stats_t* out);
 /* Serving through an index.  pg_index_attach routes every recall of ix's table that runs as a recall job through ix first: the
  * plain calls pg_recall_topk[_l2][_dev], pg_i2i_recall and pg_online_vector_recall, a coalescer's recall / l2 / i2i / online /
  * recommend batches, and pg_recommend_dnn3_dev / _begin / _end.  Not routed: pg_recall_topk_where (filtered), views, the shard
- * group, and pg_index_recall_topk* (whose own fallback is the table's pass).  The index's plan is enqueued without a host
+ * group, and pg_index_recall_topk* (whose own fallback is the table's pass).  pg_recall_topk_where goes through the attached index
+ * only with the option "index_route_where" set (as pg_index_recall_topk_where, synchronously).  The index's plan is enqueued without a host
  * synchronisation and verified with the job's status words afterwards; when it does not hold — the batch is dense, needs more
  * rounds than "index_plan_rounds" (pg_set_option, default 2), has a non-finite query or overflows its candidate lists — the
  * table's own plans serve the whole batch.  Outputs are bit for bit the table's.  A stale index (the table changed since the
@@ -478,6 +482,34 @@ int pg_index_serving_stats(const pg_index* ix, pg_index_serving_stats_t* out);
  *            index (or, for bounds, NULL queries / out or nq out of range). */
 int pg_index_read(pg_ctx* ctx, const pg_index* ix, uint32_t* offsets, uint32_t* perm, float* centroids, float* cnorm, float* radius);
 int pg_index_bounds(pg_ctx* ctx, const pg_index* ix, const float* queries, uint32_t nq, int l2, float* out);
+
+/* A filtered recall through an index: pg_recall_topk_where (WhereClause `column OP value`) with the index in place of the table
+ * (DESIGN.md 4.1h).  Argument checks, error codes and outputs are pg_recall_topk_where's on ix's table, bit for bit: only admitted
+ * rows are candidates, out_count[q] = min(k, admitted), padding UINT64_MAX with -inf (metric 1: +inf, distances ascending), no
+ * admitted row gives padding and zero counts; at most 32 queries at dim > 128.
+ *   Search   the index's search over the filter's lists — each list restricted to the rows the filter admits — the probe
+ *            covering min(K, admitted) admitted rows; lists without an admitted row are never probed or scanned.
+ *   Lists    built on the device (the predicate as a bitmap in row order, per-list counts, a stable compaction of the index's
+ *            permutation) and kept per index, keyed by feature store, column, the column's version (every
+ *            pg_features_set_column is a new one), op, value and the index's generation: "index_where_cache" entries (default
+ *            4, least recently used evicted; 0 = built per call and freed after it), each admitted x 4 B + (n_lists + 1) x 4 B
+ *            of device memory (plus a bitmap of rows / 8 bytes while it is built).  Contexts may share one index.
+ *   Fallbacks a stale index, a non-finite table or query, a dense batch (pairs above index_dense_fraction x min(rows, 150 x
+ *            admitted) x nq^0.6) and an overflow are answered by pg_recall_topk_where's own search, counted in
+ *            pg_index_stats' fallback fields; every call counts in calls, queries, pairs, rows_scored and rows_live.
+ * where_read copies a filter's lists (built or from the cache): offsets [n_lists + 1] (list L: perm[offsets[L], offsets[L+1])),
+ * perm [admitted] (at most the index's rows), *admitted; any output may be NULL.  where_stats: the cache's builds, hits,
+ * evictions, entries held and their device bytes. */
+int pg_index_recall_topk_where(pg_ctx* ctx, const pg_index* ix, const pg_features* fs, int column, int op, long long value,
+                               int metric, const float* queries, uint32_t nq, uint32_t k, uint64_t* out_rows,
+                               float* out_scores, uint32_t* out_count);
+int pg_index_where_read(pg_ctx* ctx, const pg_index* ix, const pg_features* fs, int column, int op, long long value,
+                        uint32_t* offsets, uint32_t* perm, uint64_t* admitted);
+typedef struct {
+    uint64_t builds, hits, evictions;
+    uint64_t entries, bytes;            /* the entries the cache holds and their device bytes */
+} pg_index_where_stats_t;
+int pg_index_where_stats(const pg_index* ix, pg_index_where_stats_t* out);
 /* FM + two-tower rank straight from candidate rows: the model's item field ids are the integer columns
  * item_field_cols[n_item_fields] of `fs` (out-of-vocabulary ids are clamped as in pg_rank_fm2t_dev) */
 int pg_rank_fm2t_rows_dev(pg_ctx* ctx, const pg_model* m, const pg_features* fs, const int32_t* item_field_cols,

@@ -40,7 +40,7 @@ EXPORTS = [
     "pg_router_create", "pg_router_destroy", "pg_router_recommend", "pg_router_recall", "pg_router_stats",
     "pg_index_build", "pg_index_destroy", "pg_index_recall_topk", "pg_index_recall_topk_dev", "pg_index_recall_topk_l2",
     "pg_index_recall_topk_l2_dev", "pg_index_stats", "pg_index_attach", "pg_index_detach", "pg_index_serving_stats",
-    "pg_index_read", "pg_index_bounds",
+    "pg_index_read", "pg_index_bounds", "pg_index_recall_topk_where", "pg_index_where_read", "pg_index_where_stats",
 ]
 
 
@@ -72,6 +72,11 @@ class PgIndexServingStats(C.Structure):
     _fields_ = [("plans", C.c_uint64), ("plans_held", C.c_uint64), ("queries_held", C.c_uint64),
                 ("replan_dense", C.c_uint64), ("replan_rounds", C.c_uint64), ("replan_overflow", C.c_uint64),
                 ("replan_nonfinite", C.c_uint64), ("skipped_stale", C.c_uint64), ("skipped_switch", C.c_uint64)]
+
+
+class PgIndexWhereStats(C.Structure):
+    _fields_ = [("builds", C.c_uint64), ("hits", C.c_uint64), ("evictions", C.c_uint64), ("entries", C.c_uint64),
+                ("bytes", C.c_uint64)]
 
 
 class PgDppOptions(C.Structure):
@@ -160,6 +165,9 @@ def load():
         "pg_index_attach": [vp, vp],
         "pg_index_detach": [vp, vp],
         "pg_index_serving_stats": [vp, P(PgIndexServingStats)],
+        "pg_index_recall_topk_where": [vp, vp, vp, i32, i32, C.c_longlong, i32, vp, u32, u32, vp, vp, vp],
+        "pg_index_where_read": [vp, vp, vp, i32, i32, C.c_longlong, vp, vp, vp],
+        "pg_index_where_stats": [vp, P(PgIndexWhereStats)],
         "pg_index_read": [vp, vp, vp, vp, vp, vp, vp],
         "pg_index_bounds": [vp, vp, vp, u32, i32, vp],
         "pg_topk_merge_dev": [vp, vp, vp, u32, u32, u32, u32, vp, vp],

@@ -49,6 +49,8 @@ static void knobs_from_env(Knobs* k) {
     k->index_dense_fraction = num("PG_INDEX_DENSE_FRACTION", 0.01);
     k->index_plan_rounds = (uint32_t)num("PG_INDEX_PLAN_ROUNDS", 2);
     k->index_skip_batches = (uint32_t)num("PG_INDEX_SKIP_BATCHES", 64);
+    k->index_where_cache = (uint32_t)num("PG_INDEX_WHERE_CACHE", 4);
+    k->index_route_where = flag("PG_INDEX_ROUTE_WHERE");
 }
 
 static thread_local std::string g_err;
@@ -196,6 +198,8 @@ int pg_set_option(pg_ctx* ctx, const char* name, const char* value) {
     else if (n == "index_dense_fraction") k.index_dense_fraction = v >= 0 ? v : 0.0;
     else if (n == "index_plan_rounds") k.index_plan_rounds = v >= 1 ? (uint32_t)v : 1u;
     else if (n == "index_skip_batches") k.index_skip_batches = v >= 0 ? (uint32_t)v : 0u;
+    else if (n == "index_where_cache") k.index_where_cache = v >= 0 ? (uint32_t)v : 0u;
+    else if (n == "index_route_where") k.index_route_where = b;
     else {
         pg::set_error("pg_set_option: unknown option \"%s\"", name);
         return PG_ERR_INVALID;

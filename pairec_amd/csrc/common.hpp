@@ -97,6 +97,8 @@ struct Knobs {
     double index_dense_fraction = 0.01;     // PG_INDEX_DENSE_FRACTION: an index recall of nq queries whose (row, query) pairs exceed this x rows x nq^0.6 is served by the table's pass
     uint32_t index_plan_rounds = 2;         // PG_INDEX_PLAN_ROUNDS: expand / rescore / select rounds of an attached index's plan, for the probe and for the scan each
     uint32_t index_skip_batches = 64;       // PG_INDEX_SKIP_BATCHES: after a dense or rounds re-plan, batches of that size band that skip the index plan
+    uint32_t index_where_cache = 4;         // PG_INDEX_WHERE_CACHE: filtered lists an index keeps per filter (0: built per call, freed after it)
+    bool index_route_where = false;         // PG_INDEX_ROUTE_WHERE: pg_recall_topk_where on a table with a current attached index searches it
 };
 
 }  // namespace pg
@@ -208,6 +210,7 @@ struct pg_features {
         int dtype = 0;
         void* d = nullptr;          // [rows] of the column type
         double def = 0.0;           // default for rows outside the store
+        uint64_t version = 0;       // pg::next_column_version() at every write of the values (a cache key: never reused)
     };
     std::vector<Column> cols;
 };
@@ -414,6 +417,21 @@ int recall_batches_locked(pg_ctx* ctx, const pg_table* t, const float* d_queries
 int index_plan_prepare(RecallJob* j);
 int index_plan_enqueue(RecallJob* j, uint32_t status_words);
 int index_plan_check(RecallJob* j, bool* ok);
+// recall.hip: the checks of pg_recall_topk_where and pg_index_recall_topk_where, in this order, named after `who` (t: the table
+// searched); on success *f is the filter.  recall_where_locked: its search, never through an index (caller holds ctx->mu and the
+// table's shared lock; device queries and outputs, host counts [nq] or NULL); where_pad_launch: an answer of no admitted row.
+int where_check(const char* who, const pg_ctx* ctx, const pg_table* t, const pg_features* fs, int column, int op, long long value,
+                int metric, const void* queries, const void* rows, const void* scores, uint32_t nq, uint32_t k, RowFilter* f);
+int recall_where_locked(pg_ctx* ctx, const pg_table* t, RowFilter f, int metric, const float* d_q, uint32_t nq, uint32_t k,
+                        uint64_t* d_rows, float* d_sc, uint32_t* out_count);
+int where_pad_launch(pg_ctx* ctx, uint64_t* d_rows, float* d_sc, size_t n, bool l2);
+// index.hip: the attached index pg_recall_topk_where searches ("index_route_where" set and the index current), or NULL; the
+// filtered search itself (a stale, non-finite, dense or overflowing batch: recall_where_locked)
+pg_index* index_route_where(const pg_ctx* ctx, const pg_table* t);
+int index_where_locked(pg_ctx* ctx, pg_index* ix, const pg_features* fs, int column, const RowFilter& f, bool l2, const float* d_q,
+                       uint32_t nq, uint32_t k, uint64_t* d_rows, float* d_sc, uint32_t* h_counts);
+// features.hip: a process-wide counter, so a column's version never repeats (not even for a store reallocated at one address)
+uint64_t next_column_version();
 // re-run the failed queries of `j` (at most kMaxPatchQueries) one by one, synchronously, writing into their slices of
 // the job's outputs and their valid counts into counts[q]; caller holds ctx->mu
 int recall_patch_failed_locked(RecallJob* j, uint32_t* counts);

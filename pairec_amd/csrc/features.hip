@@ -162,6 +162,13 @@ int features_gather_i32_locked(pg_ctx* ctx, const pg_features* fs, const int32_t
 
 }  // namespace pg
 
+namespace pg {
+uint64_t next_column_version() {
+    static std::atomic<uint64_t> counter{0};
+    return counter.fetch_add(1, std::memory_order_relaxed) + 1;
+}
+}  // namespace pg
+
 extern "C" {
 
 int pg_features_create(pg_ctx* ctx, uint64_t rows, pg_features** out) {
@@ -205,6 +212,7 @@ int pg_features_set_column(pg_ctx* ctx, pg_features* fs, const char* name, int d
     }
     col->dtype = dtype;
     col->def = default_value;
+    col->version = pg::next_column_version();      // (before the write: a cached filter of the old values never matches again)
     if (!col->d) {
         hipError_t e = hipMalloc(&col->d, fs->rows * es);
         if (e != hipSuccess) {

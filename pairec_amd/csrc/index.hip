@@ -29,6 +29,7 @@
 
 #include <chrono>
 #include <cmath>
+#include <list>
 
 namespace pg {
 // an attached index's serving counters and its switch, shared with the jobs that tried it (a job's check may come after a
@@ -40,6 +41,30 @@ struct IndexServe {
     std::atomic<uint64_t> skipped_stale{0}, skipped_switch{0};
     std::atomic<uint64_t> queries{0}, pairs{0}, rows_live{0}, max_scan{0};
     std::atomic<int32_t> skip[kBands] = {};   // batches of the band that skip the index plan before it is tried again
+};
+
+// The lists of an index restricted to the rows a filter admits: list L holds perm[off[L], off[L + 1]), the
+// index's rows of L that pass, in the same (ascending source) order.  One allocation, freed with the last reference: a call that
+// searches an entry holds it until its stream has synchronised, so an eviction by another context never frees it under a search.
+struct WhereKey {
+    const pg_features* fs;
+    int column;
+    uint64_t version;                    // the column's (process-wide counter: a rewritten or reallocated column never matches)
+    int op;
+    long long value;
+    uint64_t gen;                        // the index's table generation
+    bool operator==(const WhereKey& o) const {
+        return fs == o.fs && column == o.column && version == o.version && op == o.op && value == o.value && gen == o.gen;
+    }
+};
+struct WhereLists {
+    WhereKey key{};
+    void* d = nullptr;
+    uint32_t* off = nullptr;             // [n_lists + 1]
+    uint32_t* perm = nullptr;            // [admitted]
+    uint64_t admitted = 0;
+    size_t bytes = 0;                    // admitted x 4 + (n_lists + 1) x 4 (the offsets padded to 256 B)
+    ~WhereLists() { if (d) (void)hipFree(d); }
 };
 }  // namespace pg
 
@@ -58,6 +83,11 @@ struct pg_index {
     std::mutex mu;                // guards st
     pg_index_stats_t st{};        // the synchronous pg_index_recall_topk* calls (the attached plans count in serve)
     std::shared_ptr<pg::IndexServe> serve = std::make_shared<pg::IndexServe>();
+    // filtered lists: at most "index_where_cache" entries, most recently used first.  where_mu is taken after
+    // ctx->mu and the table's shared lock; it also guards where_st.
+    std::mutex where_mu;
+    std::list<std::shared_ptr<pg::WhereLists>> where_cache;
+    pg_index_where_stats_t where_st{};
 };
 
 namespace pg {
@@ -66,6 +96,10 @@ namespace {
 constexpr uint32_t kMaxLists = 65536;
 constexpr uint32_t kSlices = 256;        // list slices of the count / expand kernels (per query)
 constexpr uint32_t kBoundQ = 8;          // queries per bound-kernel block
+// the dense rule of a filter's lists: the filtered pass costs about as much as the table's pass (rows) or, when
+// it gathers a compact copy, this many table-pass rows per admitted row (profiles/index_where.json: the breakevens at 0.1 % and
+// 1 % admitted put it at ~140 and ~80)
+constexpr double kWhereGatherWeight = 150.0;
 
 // the verdict of an index plan, written by the device (index_plan_kernel) and read by every later launch of the plan, then
 // copied into the job's status words at kIndexStatAt
@@ -541,6 +575,47 @@ __global__ void index_status_kernel(const uint32_t* __restrict__ overflow, uint3
     if (t == 0) out[0] = overflow[0];
 }
 
+// ---- filtered lists -------------------------------------------------------------------------
+// bit r of bits: row r passes the filter.  Rows in order (the column is read coalesced); a wave's 64 rows are two words.
+__global__ __launch_bounds__(256) void where_bits_kernel(RowFilter f, uint64_t rows, uint32_t* __restrict__ bits) {
+    const uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    const bool pass = r < rows && row_filter_pass(f, (uint32_t)r);
+    const uint64_t m = __builtin_amdgcn_ballot_w64(pass);
+    if ((threadIdx.x & 63) == 0 && r < rows) {
+        bits[r >> 5] = (uint32_t)m;
+        if (r + 32 < rows) bits[(r >> 5) + 1] = (uint32_t)(m >> 32);
+    }
+}
+
+// one block per list: the positions of list L whose row passes (bits[perm[p]], a gather from a bitmap of rows / 8 bytes).
+// COUNT: cnt[L] = how many.  Else the stable compaction: perm_f[off_f[L] + rank] = perm[p], ranks in position order.
+template <bool COUNT>
+__global__ __launch_bounds__(256) void where_lists_kernel(const uint32_t* __restrict__ perm, const uint32_t* __restrict__ off,
+                                                          const uint32_t* __restrict__ bits, uint32_t* __restrict__ cnt_off,
+                                                          uint32_t* __restrict__ perm_f) {
+    __shared__ uint32_t wsum[4];
+    const uint32_t L = blockIdx.x;
+    const uint32_t b = off[L], e = off[L + 1];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    uint32_t base = COUNT ? 0u : cnt_off[L];
+    for (uint32_t p0 = b; p0 < e; p0 += 256) {
+        const uint32_t p = p0 + threadIdx.x;
+        const uint32_t row = p < e ? perm[p] : 0u;
+        const bool pass = p < e && ((bits[row >> 5] >> (row & 31)) & 1u);
+        const uint64_t m = __builtin_amdgcn_ballot_w64(pass);
+        if (lane == 0) wsum[w] = (uint32_t)__popcll(m);
+        __syncthreads();
+        if (!COUNT && pass) {
+            uint32_t pos = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+            for (int j = 0; j < w; ++j) pos += wsum[j];
+            perm_f[pos] = row;
+        }
+        base += wsum[0] + wsum[1] + wsum[2] + wsum[3];
+        __syncthreads();
+    }
+    if (COUNT && threadIdx.x == 0) cnt_off[L] = base;
+}
+
 // ---- host ----------------------------------------------------------------------------------------------------
 // device allocation that reports failure as PG_ERR_NOMEM (and clears the runtime's last error)
 int dalloc(void** p, size_t bytes, std::vector<void*>& owned) {
@@ -779,6 +854,16 @@ int bounds_launch(pg_ctx* ctx, const pg_index* ix, const float* d_q, uint32_t nq
     return PG_OK;
 }
 
+// The lists a search walks: the index's own, or a filter's — the same sequence over either.  rows: the rows
+// the lists hold (the probe covers min(K, rows) of them); dense_rows: the rows the dense rule weighs the batch's pairs against.
+struct SearchLists {
+    const uint32_t* perm;
+    const uint32_t* off;
+    uint64_t rows;
+    double dense_rows;
+};
+SearchLists own_lists(const pg_index* ix) { return SearchLists{ix->d_perm, ix->d_off, ix->rows, (double)ix->rows}; }
+
 // The search of one batch, enqueued on ctx->stream: plan init, the L2 query norms, bounds, probe, the probe's count, plan kernel
 // and rounds, the frozen scan threshold, the scan's count and union, plan kernel and rounds, final, the negation for L2.  The
 // device writes its verdict into sb.pw and every round's expansion reads it.  Two round policies:
@@ -786,7 +871,7 @@ int bounds_launch(pg_ctx* ctx, const pg_index* ix, const float* d_q, uint32_t nq
 //   h_pw        the synchronous call (budget unlimited): after each stage's plan kernel the host reads the words into *h_pw; a
 //               flag ends the search there (that stage's pairs cleared: not scored), else the stage runs exactly its rounds,
 //               each on a grid sized to its suspects
-int index_search(pg_ctx* ctx, const pg_index* ix, const float* d_q, uint32_t nq, uint32_t k, bool l2, RecallScratch& rs,
+int index_search(pg_ctx* ctx, const pg_index* ix, const SearchLists& li, const float* d_q, uint32_t nq, uint32_t k, bool l2, RecallScratch& rs,
                  const SearchBufs& sb, uint64_t* d_rows, float* d_sc, uint32_t* d_count, uint32_t budget, IndexPlanWords* h_pw) {
     const pg_table* t = ix->t;
     const uint32_t nl = ix->n_lists, dim = t->dim;
@@ -796,13 +881,14 @@ int index_search(pg_ctx* ctx, const pg_index* ix, const float* d_q, uint32_t nq,
     PG_HIP(hipGetLastError());
     if (l2 && (rc = query_norm2_launch(ctx, d_q, nq, dim, sb.nqv))) return rc;
     if ((rc = bounds_launch(ctx, ix, d_q, nq, l2, sb.qn, &sb.pw->flags, sb.U))) return rc;
-    probe_kernel<<<nq, 1024, 0, s>>>(sb.U, nl, ix->d_off, ix->rows, k, sb.Bkey, sb.probe);
-    count_kernel<<<dim3(kSlices, nq), 256, 0, s>>>(sb.U, nl, ix->d_off, sb.Bkey, rs.thr, 0, sb.cntg);
+    probe_kernel<<<nq, 1024, 0, s>>>(sb.U, nl, li.off, li.rows, k, sb.Bkey, sb.probe);
+    count_kernel<<<dim3(kSlices, nq), 256, 0, s>>>(sb.U, nl, li.off, sb.Bkey, rs.thr, 0, sb.cntg);
     PG_HIP(hipGetLastError());
     // the dense rule: the scan gathers a full row per pair, the table's pass streams a shadow whose cost grows slowly with the
     // batch: at 100 M rows the index breaks even at about 0.010 / 0.038 / 0.085 / 0.16 / 0.3-0.5 x rows pairs for 1 / 8 / 32 / 64 /
-    // 256 queries (profiles/index_breakeven.json with profiles/index_sweep_10k.json) — 0.01 x rows x nq^0.6
-    const double limit = ctx->knobs.index_dense_fraction * (double)ix->rows * std::pow((double)nq, 0.6);
+    // 256 queries (profiles/index_breakeven.json with profiles/index_sweep_10k.json) — 0.01 x rows x nq^0.6 (a
+    // filter's lists: dense_rows)
+    const double limit = ctx->knobs.index_dense_fraction * li.dense_rows * std::pow((double)nq, 0.6);
     const uint32_t scap = rs.cap - k;
     // a round of n suspects per query: one block per 1024, at most max(16, 4096 / nq) (the blocks past a query's suspects return)
     auto grid = [&](uint64_t n) {
@@ -826,13 +912,13 @@ int index_search(pg_ctx* ctx, const pg_index* ix, const float* d_q, uint32_t nq,
             most = mode == 0 ? h_pw->max_probe : h_pw->max_scan;
         }
         for (uint32_t r = 0; r < rounds; ++r) {
-            expand_kernel<<<dim3(kSlices, nq), 256, 0, s>>>(sb.U, nl, ix->d_off, ix->d_perm, sb.Bkey, sb.thr_scan, mode, sb.cntg, r, scap,
+            expand_kernel<<<dim3(kSlices, nq), 256, 0, s>>>(sb.U, nl, li.off, li.perm, sb.Bkey, sb.thr_scan, mode, sb.cntg, r, scap,
                                                              rs.susp, rs.susp_cnt, sb.pw);
             PG_HIP(hipGetLastError());
             const uint32_t blocks = grid(h_pw ? std::min<uint64_t>(most - (uint64_t)r * scap, scap) : scap);
             int rc3;
             if ((rc3 = rescore_launch(ctx, dim, l2, t->d, d_q, rs.thr, rs.susp, rs.susp_cnt, scap, rs.cnt, rs.cand[cur], rs.overflow, rs.cap,
-                                      nq, (uint32_t)ix->rows, l2 ? t->d_nx : nullptr, l2 ? sb.nqv : nullptr, blocks)))
+                                      nq, (uint32_t)ix->rows /* the gather's bound: the table's rows */, l2 ? t->d_nx : nullptr, l2 ? sb.nqv : nullptr, blocks)))
                 return rc3;
             // (a round without suspects selects the kept list again: the same K keys, the same threshold)
             if ((rc3 = launch_select(ctx, nq, rs.cand[cur], rs.cand[cur ^ 1], rs.cnt, rs.thr, rs.cap, k, 0))) return rc3;
@@ -845,8 +931,8 @@ int index_search(pg_ctx* ctx, const pg_index* ix, const float* d_q, uint32_t nq,
     // threshold (thr_scan): the per-slice counts and every round's expansion must see the same lists, while rs.thr keeps
     // rising with the select between rounds and serves only the re-scoring's candidate test.
     PG_HIP(hipMemcpyAsync(sb.thr_scan, rs.thr, (size_t)nq * 4, hipMemcpyDeviceToDevice, s));
-    count_kernel<<<dim3(kSlices, nq), 256, 0, s>>>(sb.U, nl, ix->d_off, sb.Bkey, sb.thr_scan, 1, sb.cntg);
-    union_kernel<<<(nl + 255) / 256, 256, 0, s>>>(sb.U, nl, nq, ix->d_off, sb.Bkey, sb.thr_scan, &sb.pw->union_rows);
+    count_kernel<<<dim3(kSlices, nq), 256, 0, s>>>(sb.U, nl, li.off, sb.Bkey, sb.thr_scan, 1, sb.cntg);
+    union_kernel<<<(nl + 255) / 256, 256, 0, s>>>(sb.U, nl, nq, li.off, sb.Bkey, sb.thr_scan, &sb.pw->union_rows);
     PG_HIP(hipGetLastError());
     if ((rc = stage(1)) || (h_pw && h_pw->flags)) return rc;
     if ((rc = final_launch(ctx, rs.cand[cur], rs.cnt, rs.cap, nq, k, t->row_offset, d_rows, d_sc, d_count))) return rc;
@@ -884,7 +970,7 @@ int index_recall_locked(pg_ctx* ctx, pg_index* ix, const float* d_q, uint32_t nq
             fb = &pg_index_stats_t::fallback_overflow;
             return PG_OK;
         }
-        if ((rc2 = index_search(ctx, ix, d_q, nq, k, l2, rs, sb, d_rows, d_sc, sb.dcount, ~0u, &w))) return rc2;
+        if ((rc2 = index_search(ctx, ix, own_lists(ix), d_q, nq, k, l2, rs, sb, d_rows, d_sc, sb.dcount, ~0u, &w))) return rc2;
         if (w.flags & kPlanNonfinite) fb = &pg_index_stats_t::fallback_nonfinite;
         else if (w.flags & kPlanDense) fb = &pg_index_stats_t::fallback_dense;
         if (fb) return PG_OK;
@@ -927,7 +1013,161 @@ int index_entry(const char* who, pg_ctx* ctx, const pg_index* ixc, const float* 
 
 int band_of(uint32_t nq) { return nq <= 1 ? 0 : nq <= 8 ? 1 : nq <= 32 ? 2 : nq <= 64 ? 3 : 4; }
 
+// A filter's lists over the index, built on ctx->stream: the predicate's bitmap in row order, the admitted rows per list, their
+// exclusive scan (the offsets), then the stable compaction of the permutation.  Synchronises (the total sizes the allocation).
+int where_lists_build(pg_ctx* ctx, const pg_index* ix, const RowFilter& f, std::shared_ptr<WhereLists>* out) {
+    const uint32_t nl = ix->n_lists;
+    const uint64_t rows = ix->rows;
+    hipStream_t s = ctx->stream;
+    std::vector<void*> temp;
+    auto done = [&](int rc) {
+        (void)hipStreamSynchronize(s);
+        free_all(temp);
+        return rc;
+    };
+    int rc;
+    uint32_t *bits, *cnt, *off;
+    const size_t words = (size_t)((rows + 31) / 32);
+    if ((rc = dalloc((void**)&bits, words * 4, temp)) || (rc = dalloc((void**)&cnt, ((size_t)nl + 1) * 4, temp)) ||
+        (rc = dalloc((void**)&off, ((size_t)nl + 1) * 4, temp)))
+        return done(rc);
+    size_t scan_b = 0;
+    void* scan_tmp;
+    if (hipcub::DeviceScan::ExclusiveSum(nullptr, scan_b, cnt, off, nl + 1, s) != hipSuccess) return done(PG_ERR_DEVICE);
+    if ((rc = dalloc(&scan_tmp, scan_b, temp))) return done(rc);
+    where_bits_kernel<<<(uint32_t)((rows + 255) / 256), 256, 0, s>>>(f, rows, bits);
+    if (hipMemsetAsync(cnt + nl, 0, 4, s) != hipSuccess) return done(PG_ERR_DEVICE);
+    where_lists_kernel<true><<<nl, 256, 0, s>>>(ix->d_perm, ix->d_off, bits, cnt, nullptr);
+    if (hipGetLastError() != hipSuccess || hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_b, cnt, off, nl + 1, s) != hipSuccess)
+        return done(PG_ERR_DEVICE);
+    uint32_t admitted = 0;
+    if (hipMemcpyAsync(&admitted, off + nl, 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+        return done(PG_ERR_DEVICE);
+    auto wl = std::make_shared<WhereLists>();
+    const size_t off_b = (((size_t)nl + 1) * 4 + 255) & ~(size_t)255;
+    if (hipMalloc(&wl->d, off_b + (size_t)admitted * 4 + 16) != hipSuccess) {
+        (void)hipGetLastError();
+        wl->d = nullptr;
+        return done(PG_ERR_NOMEM);
+    }
+    wl->off = (uint32_t*)wl->d;
+    wl->perm = (uint32_t*)((char*)wl->d + off_b);
+    wl->admitted = admitted;
+    wl->bytes = (size_t)admitted * 4 + ((size_t)nl + 1) * 4;
+    if (hipMemcpyAsync(wl->off, off, ((size_t)nl + 1) * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) return done(PG_ERR_DEVICE);
+    where_lists_kernel<false><<<nl, 256, 0, s>>>(ix->d_perm, ix->d_off, bits, wl->off, wl->perm);
+    if (hipGetLastError() != hipSuccess) return done(PG_ERR_DEVICE);
+    rc = done(PG_OK);
+    if (rc == PG_OK) *out = std::move(wl);
+    return rc;
+}
+
+// the filter's lists from the index's cache, or built (and kept while "index_where_cache" of the calling context allows); caller
+// holds ctx->mu and the table's shared lock
+int where_lists_get(pg_ctx* ctx, pg_index* ix, const pg_features* fs, int column, const RowFilter& f, std::shared_ptr<WhereLists>* out) {
+    const WhereKey key{fs, column, fs->cols[(size_t)column].version, f.op, f.val, ix->gen};
+    std::lock_guard<std::mutex> g(ix->where_mu);
+    pg_index_where_stats_t& st = ix->where_st;
+    const uint32_t cap = ctx->knobs.index_where_cache;
+    auto trim = [&]() {                      // (to the calling context's capacity: at 0 every call builds)
+        while (ix->where_cache.size() > cap) {
+            st.evictions++;
+            st.bytes -= ix->where_cache.back()->bytes;
+            ix->where_cache.pop_back();      // (a search that still holds the entry keeps it alive)
+        }
+        st.entries = ix->where_cache.size();
+    };
+    trim();
+    for (auto it = ix->where_cache.begin(); it != ix->where_cache.end(); ++it) {
+        if (!((*it)->key == key)) continue;
+        ix->where_cache.splice(ix->where_cache.begin(), ix->where_cache, it);
+        st.hits++;
+        *out = ix->where_cache.front();
+        return PG_OK;
+    }
+    int rc;
+    if ((rc = where_lists_build(ctx, ix, f, out))) {
+        if (rc == PG_ERR_DEVICE) set_error("index filtered lists: %s", hipGetErrorString(hipGetLastError()));
+        else set_error("index filtered lists: device allocation failed (%llu rows)", (unsigned long long)ix->rows);
+        return rc;
+    }
+    (*out)->key = key;
+    st.builds++;
+    if (cap) {
+        ix->where_cache.push_front(*out);
+        st.bytes += (*out)->bytes;
+    }
+    trim();
+    return PG_OK;
+}
+
 }  // namespace
+
+pg_index* index_route_where(const pg_ctx* ctx, const pg_table* t) {
+    if (!ctx->knobs.index_route_where || t->d_row_map) return nullptr;
+    pg_index* ix = t->index.load(std::memory_order_acquire);
+    return ix && t->generation.load(std::memory_order_relaxed) == ix->gen ? ix : nullptr;
+}
+
+// one filtered batch, synchronously (caller holds ctx->mu and the table's shared lock); h_counts: host [nq].  The search of
+// index_recall_locked over the filter's lists; a stale, non-finite, dense or overflowing batch is answered by the filtered pass.
+int index_where_locked(pg_ctx* ctx, pg_index* ix, const pg_features* fs, int column, const RowFilter& f, bool l2, const float* d_q,
+                       uint32_t nq, uint32_t k, uint64_t* d_rows, float* d_sc, uint32_t* h_counts) {
+    const pg_table* t = ix->t;
+    const uint32_t dim = t->dim;
+    IndexPlanWords w{};
+    uint64_t pg_index_stats_t::*fb = nullptr;
+    std::shared_ptr<WhereLists> wl;      // (released after the stream has synchronised: every path below ends synchronised)
+    int rc = PG_OK;
+    if (t->generation.load(std::memory_order_relaxed) != ix->gen) fb = &pg_index_stats_t::fallback_stale;
+    else if (ix->nonfinite) fb = &pg_index_stats_t::fallback_nonfinite;
+    else if (l2 && dim != 64 && dim != 128) fb = &pg_index_stats_t::fallback_dense;   // (the filtered pass answers with its own error)
+    else rc = [&]() -> int {
+        int rc2;
+        if ((rc2 = where_lists_get(ctx, ix, fs, column, f, &wl))) return rc2;
+        if (wl->admitted == 0) {
+            // nothing passes: padding, every count 0 (as pg_recall_topk_where)
+            if ((rc2 = where_pad_launch(ctx, d_rows, d_sc, (size_t)nq * k, l2))) return rc2;
+            for (uint32_t q = 0; q < nq; ++q) h_counts[q] = 0;
+            PG_HIP(hipStreamSynchronize(ctx->stream));
+            return PG_OK;
+        }
+        RecallScratch rs;
+        SearchBufs sb;
+        if ((rc2 = recall_scratch(ctx, dim, k, &rs))) return rc2;
+        if (l2 && (rc2 = ensure_table_nx(ctx, t))) return rc2;
+        if (search_bufs(ctx, nq, ix->n_lists, &sb)) {
+            fb = &pg_index_stats_t::fallback_overflow;
+            return PG_OK;
+        }
+        // the dense rule weighs the pairs against the filtered pass, which streams the table or gathers a compact copy of the
+        // admitted rows, whichever is less
+        const SearchLists li{wl->perm, wl->off, wl->admitted, std::min((double)ix->rows, kWhereGatherWeight * (double)wl->admitted)};
+        if ((rc2 = index_search(ctx, ix, li, d_q, nq, k, l2, rs, sb, d_rows, d_sc, sb.dcount, ~0u, &w))) return rc2;
+        if (w.flags & kPlanNonfinite) fb = &pg_index_stats_t::fallback_nonfinite;
+        else if (w.flags & kPlanDense) fb = &pg_index_stats_t::fallback_dense;
+        if (fb) return PG_OK;
+        uint32_t h_ovf = 0;
+        PG_HIP(hipMemcpyAsync(&h_ovf, rs.overflow, 4, hipMemcpyDeviceToHost, ctx->stream));
+        PG_HIP(hipMemcpyAsync(h_counts, sb.dcount, (size_t)nq * 4, hipMemcpyDeviceToHost, ctx->stream));
+        PG_HIP(hipStreamSynchronize(ctx->stream));
+        if (h_ovf) fb = &pg_index_stats_t::fallback_overflow;
+        return PG_OK;
+    }();
+    if (rc != PG_OK && wl) (void)hipStreamSynchronize(ctx->stream);
+    wl.reset();
+    if (rc == PG_OK && fb) rc = recall_where_locked(ctx, t, f, l2 ? 1 : 0, d_q, nq, k, d_rows, d_sc, h_counts);
+    if (rc != PG_OK) return rc;
+    std::lock_guard<std::mutex> g(ix->mu);
+    ix->st.calls++;
+    ix->st.queries += nq;
+    ix->st.pairs_scored += w.pairs[0] + w.pairs[1];
+    ix->st.rows_scored += w.pairs[0] + w.pairs[1];
+    ix->st.rows_live += w.union_rows;
+    ix->st.max_query_scan_rows = std::max<uint64_t>(ix->st.max_query_scan_rows, w.max_scan);
+    if (fb) ix->st.*fb += 1;
+    return PG_OK;
+}
 
 // ---- an attached index as a RecallJob plan ------------------------------------------------------------------------
 // In front of the table's plans when the table has an attachment that is current and finite, and the job is one the index
@@ -981,7 +1221,7 @@ int index_plan_enqueue(RecallJob* j, uint32_t status_words) {
     j->timers = !ctx->timers_off;
     if (j->timers) PG_HIP(hipEventRecord((*j->events)[0], s));
     const uint32_t budget = ctx->knobs.index_plan_rounds ? ctx->knobs.index_plan_rounds : 1u;
-    if ((rc = index_search(ctx, j->ix, j->d_queries, nq, j->k, j->l2, rs, sb, j->d_out_rows, j->d_out_scores, j->d_count, budget, nullptr)))
+    if ((rc = index_search(ctx, j->ix, own_lists(j->ix), j->d_queries, nq, j->k, j->l2, rs, sb, j->d_out_rows, j->d_out_scores, j->d_count, budget, nullptr)))
         return rc;
     if (j->timers) PG_HIP(hipEventRecord((*j->events)[1], s));
     index_status_kernel<<<1, kMaxQueries, 0, s>>>(rs.overflow, nq, sb.pw, rs.status);
@@ -1101,6 +1341,66 @@ int pg_index_recall_topk_l2(pg_ctx* ctx, const pg_index* ix, const float* querie
 int pg_index_recall_topk_l2_dev(pg_ctx* ctx, const pg_index* ix, const float* d_queries, uint32_t nq, uint32_t k, uint64_t* d_out_rows,
                                 float* d_out_dist, uint32_t* out_count) {
     return pg::index_entry("pg_index_recall_topk_l2_dev", ctx, ix, d_queries, nq, k, d_out_rows, d_out_dist, out_count, true, false);
+}
+
+// the filtered recall through the index: pg_recall_topk_where's checks and contract, over ix's table
+int pg_index_recall_topk_where(pg_ctx* ctx, const pg_index* ixc, const pg_features* fs, int column, int op, long long value, int metric,
+                               const float* queries, uint32_t nq, uint32_t k, uint64_t* out_rows, float* out_scores, uint32_t* out_count) {
+    PG_REQUIRE(ixc, "pg_index_recall_topk_where: NULL argument");
+    pg::RowFilter f;
+    int rc;
+    if ((rc = pg::where_check("pg_index_recall_topk_where", ctx, ixc->t, fs, column, op, value, metric, queries, out_rows, out_scores, nq, k,
+                              &f)))
+        return rc;
+    pg_index* ix = const_cast<pg_index*>(ixc);          // (only the statistics and the filtered lists' cache change)
+    std::lock_guard<std::mutex> g(ctx->mu);
+    pg::TableRead tr(ix->t->rw);
+    uint32_t counts[pg::kMaxQueries];
+    auto run = [&](const float* d_q, uint64_t* d_rows, float* d_sc) {
+        return pg::index_where_locked(ctx, ix, fs, column, f, metric == 1, d_q, nq, k, d_rows, d_sc, counts);
+    };
+    if ((rc = pg::recall_staged(ctx, ix->dim, queries, nq, k, out_rows, out_scores, run))) return rc;
+    if (out_count) memcpy(out_count, counts, (size_t)nq * 4);
+    return PG_OK;
+}
+
+int pg_index_where_read(pg_ctx* ctx, const pg_index* ixc, const pg_features* fs, int column, int op, long long value, uint32_t* offsets,
+                        uint32_t* perm, uint64_t* admitted) {
+    PG_REQUIRE(ctx && ixc && fs, "pg_index_where_read: NULL argument");
+    PG_REQUIRE(column >= 0 && (size_t)column < fs->cols.size(), "pg_index_where_read: column %d out of range", column);
+    PG_REQUIRE(op >= 0 && op <= 5, "pg_index_where_read: op %d unknown (0 >, 1 >=, 2 <, 3 <=, 4 ==, 5 !=)", op);
+    PG_REQUIRE(fs->rows >= ixc->rows, "pg_index_where_read: the feature store holds %llu rows, the index %llu", (unsigned long long)fs->rows,
+               (unsigned long long)ixc->rows);
+    const pg_features::Column& c = fs->cols[(size_t)column];
+    if ((c.dtype != PG_F_I32 && c.dtype != PG_F_I64) || !c.d) {
+        pg::set_error("pg_index_where_read: column \"%s\" must be an int32 / int64 column with values", c.name.c_str());
+        return PG_ERR_UNSUPPORTED;
+    }
+    pg::RowFilter f;
+    f.col = c.d;
+    f.dtype = c.dtype;
+    f.op = op;
+    f.val = value;
+    pg_index* ix = const_cast<pg_index*>(ixc);
+    std::lock_guard<std::mutex> g(ctx->mu);
+    pg::TableRead tr(ix->t->rw);
+    std::shared_ptr<pg::WhereLists> wl;
+    int rc;
+    if ((rc = pg::where_lists_get(ctx, ix, fs, column, f, &wl))) return rc;
+    hipStream_t s = ctx->stream;
+    if (offsets) PG_HIP(hipMemcpyAsync(offsets, wl->off, ((size_t)ix->n_lists + 1) * 4, hipMemcpyDeviceToHost, s));
+    if (perm && wl->admitted) PG_HIP(hipMemcpyAsync(perm, wl->perm, (size_t)wl->admitted * 4, hipMemcpyDeviceToHost, s));
+    PG_HIP(hipStreamSynchronize(s));
+    if (admitted) *admitted = wl->admitted;
+    return PG_OK;
+}
+
+int pg_index_where_stats(const pg_index* ixc, pg_index_where_stats_t* out) {
+    PG_REQUIRE(ixc && out, "pg_index_where_stats: NULL argument");
+    pg_index* ix = const_cast<pg_index*>(ixc);
+    std::lock_guard<std::mutex> g(ix->where_mu);
+    *out = ix->where_st;
+    return PG_OK;
 }
 
 int pg_index_stats(const pg_index* ixc, pg_index_stats_t* out) {

@@ -3511,6 +3511,97 @@ int negate_launch(pg_ctx* ctx, float* d_v, uint64_t n) {
     return PG_OK;
 }
 
+int where_check(const char* who, const pg_ctx* ctx, const pg_table* t, const pg_features* fs, int column, int op, long long value,
+                int metric, const void* queries, const void* rows, const void* scores, uint32_t nq, uint32_t k, RowFilter* f) {
+    PG_REQUIRE(ctx && t && fs && queries && rows && scores, "%s: NULL argument", who);
+    PG_REQUIRE(nq >= 1 && nq <= (uint32_t)kMaxQueries, "%s: nq=%u must be in [1,%d]", who, nq, kMaxQueries);
+    PG_REQUIRE(t->dim <= 128 || nq <= 32, "%s: dim %u supports at most 32 queries per call", who, t->dim);
+    PG_REQUIRE(column >= 0 && (size_t)column < fs->cols.size(), "%s: column %d out of range", who, column);
+    PG_REQUIRE(op >= 0 && op <= 5, "%s: op %d unknown (0 >, 1 >=, 2 <, 3 <=, 4 ==, 5 !=)", who, op);
+    PG_REQUIRE(metric == 0 || metric == 1, "%s: metric %d unknown (0 inner product, 1 squared Euclidean)", who, metric);
+    PG_REQUIRE(fs->rows >= t->rows, "%s: the feature store holds %llu rows, the table %llu", who, (unsigned long long)fs->rows,
+               (unsigned long long)t->rows);
+    const pg_features::Column& c = fs->cols[(size_t)column];
+    if ((c.dtype != PG_F_I32 && c.dtype != PG_F_I64) || !c.d) {
+        set_error("%s: column \"%s\" must be an int32 / int64 column with values", who, c.name.c_str());
+        return PG_ERR_UNSUPPORTED;
+    }
+    if (k < 1 || k > 16384) {
+        set_error("%s: k=%u unsupported (1..16384)", who, k);
+        return PG_ERR_UNSUPPORTED;
+    }
+    *f = RowFilter();
+    f->col = c.d;
+    f->dtype = c.dtype;
+    f->op = op;
+    f->val = value;
+    return PG_OK;
+}
+
+int where_pad_launch(pg_ctx* ctx, uint64_t* d_rows, float* d_sc, size_t n, bool l2) {
+    recall_pad_kernel<<<(uint32_t)((n + 255) / 256), 256, 0, ctx->stream>>>(d_rows, d_sc, n, l2);
+    PG_HIP(hipGetLastError());
+    return PG_OK;
+}
+
+int recall_where_locked(pg_ctx* ctx, const pg_table* t, RowFilter f, int metric, const float* d_q, uint32_t nq, uint32_t k,
+                        uint64_t* d_rows, float* d_sc, uint32_t* out_count) {
+    int rc;
+    uint32_t *d_blk, *d_grp, cblocks, admitted;
+    if ((rc = filter_count_locked(ctx, f, t->rows, &d_blk, &d_grp, &cblocks, &admitted))) return rc;
+    f.admitted = admitted;
+    if (admitted == 0) {
+        // nothing passes: every slot is padding (row UINT64_MAX, score -inf / distance +inf), every count 0
+        if ((rc = where_pad_launch(ctx, d_rows, d_sc, (size_t)nq * k, metric == 1))) return rc;
+        if (out_count) for (uint32_t q = 0; q < nq; ++q) out_count[q] = 0;
+    } else if (admitted <= (nq <= 4 ? ctx->knobs.where_compact_max_rows / 2 : ctx->knobs.where_compact_max_rows) &&
+               (uint64_t)admitted * ctx->knobs.where_compact_min_ratio <= t->rows &&
+               (metric == 0 || t->dim == 64 || t->dim == 128)) {
+        // A selective filter: the thresholds the scan plans estimate from samples of the table say little about the few rows
+        // that pass (1 % admitted of 100 M rows, 128 queries: 180 ms of re-planned passes).  Gather the admitted rows, in row
+        // order, into a compact table and run the exact scan over that: its rows are the candidates, its row order the tie
+        // order, and the answer's local rows map back through the id list.  (The gather is 1 KB of traffic per admitted row: at
+        // 100 M x 128 the copy wins below ~4 M rows for a lone query — in place 2.2 ms at 4 % — and below ~8 M for 16+ queries.)
+        const size_t idb = (((size_t)admitted + 64) * 4 + 255) & ~(size_t)255;
+        const size_t tabb = (((size_t)admitted + 64) * t->dim * 4 + 255) & ~(size_t)255;
+        const size_t nxb = metric == 1 ? (((size_t)admitted + 64) * 4 + 255) & ~(size_t)255 : 0;
+        void* gbuf;
+        if ((rc = scratch_reserve(ctx, 13, idb + tabb + nxb, &gbuf))) return rc;
+        uint32_t* d_ids = (uint32_t*)gbuf;
+        float* d_tab = (float*)((char*)gbuf + idb);
+        float* d_cnx = nxb ? (float*)((char*)gbuf + idb + tabb) : nullptr;
+        filter_scatter_kernel<<<cblocks, 256, 0, ctx->stream>>>(f, t->rows, d_blk, d_grp, d_ids);
+        const uint64_t quads = (uint64_t)admitted * (t->dim / 4);
+        compact_gather_kernel<<<(uint32_t)((quads + 255) / 256), 256, 0, ctx->stream>>>(t->d, d_ids, admitted, t->dim, d_tab);
+        PG_HIP(hipMemsetAsync(d_tab + (size_t)admitted * t->dim, 0, (size_t)64 * t->dim * 4, ctx->stream));
+        pg_table ct;
+        ct.d = d_tab;
+        ct.rows = admitted;
+        ct.dim = t->dim;
+        if (metric == 1) {
+            if ((rc = ensure_table_nx(ctx, t))) return rc;
+            compact_gather_nx_kernel<<<(admitted + 64 + 255) / 256, 256, 0, ctx->stream>>>(t->d_nx, d_ids, admitted, d_cnx);
+            ct.d_nx = d_cnx;
+            ct.nx_valid = true;
+        }
+        PG_HIP(hipGetLastError());
+        RecallOpts o;
+        o.l2 = metric == 1;
+        o.exact_only = true;
+        if ((rc = recall_batches_locked(ctx, &ct, d_q, nq, k, d_rows, d_sc, out_count, o))) return rc;
+        compact_map_rows_kernel<<<(uint32_t)(((size_t)nq * k + 255) / 256), 256, 0, ctx->stream>>>(d_rows, (uint64_t)nq * k, d_ids, t->row_offset, admitted);
+        PG_HIP(hipGetLastError());
+        ct.d = nullptr;
+        ct.d_nx = nullptr;
+    } else {
+        RecallOpts o;
+        o.l2 = metric == 1;
+        o.filter = &f;
+        if ((rc = recall_batches_locked(ctx, t, d_q, nq, k, d_rows, d_sc, out_count, o))) return rc;
+    }
+    return PG_OK;
+}
+
 }  // namespace pg
 
 extern "C" {
@@ -3559,94 +3650,20 @@ int pg_recall_topk_l2(pg_ctx* ctx, const pg_table* t, const float* queries, uint
 // is applied where candidates are made, so the plans' thresholds are thresholds of the filtered top-K.
 int pg_recall_topk_where(pg_ctx* ctx, const pg_table* t, const pg_features* fs, int column, int op, long long value, int metric,
                          const float* queries, uint32_t nq, uint32_t k, uint64_t* out_rows, float* out_scores, uint32_t* out_count) {
-    PG_REQUIRE(ctx && t && fs && queries && out_rows && out_scores, "pg_recall_topk_where: NULL argument");
-    PG_REQUIRE(nq >= 1 && nq <= (uint32_t)pg::kMaxQueries, "pg_recall_topk_where: nq=%u must be in [1,%d]", nq, pg::kMaxQueries);
-    PG_REQUIRE(t->dim <= 128 || nq <= 32, "pg_recall_topk_where: dim %u supports at most 32 queries per call", t->dim);
-    PG_REQUIRE(column >= 0 && (size_t)column < fs->cols.size(), "pg_recall_topk_where: column %d out of range", column);
-    PG_REQUIRE(op >= 0 && op <= 5, "pg_recall_topk_where: op %d unknown (0 >, 1 >=, 2 <, 3 <=, 4 ==, 5 !=)", op);
-    PG_REQUIRE(metric == 0 || metric == 1, "pg_recall_topk_where: metric %d unknown (0 inner product, 1 squared Euclidean)", metric);
-    PG_REQUIRE(fs->rows >= t->rows, "pg_recall_topk_where: the feature store holds %llu rows, the table %llu",
-               (unsigned long long)fs->rows, (unsigned long long)t->rows);
-    const pg_features::Column& c = fs->cols[(size_t)column];
-    if ((c.dtype != PG_F_I32 && c.dtype != PG_F_I64) || !c.d) {
-        pg::set_error("pg_recall_topk_where: column \"%s\" must be an int32 / int64 column with values", c.name.c_str());
-        return PG_ERR_UNSUPPORTED;
-    }
-    if (k < 1 || k > 16384) {
-        pg::set_error("pg_recall_topk_where: k=%u unsupported (1..16384)", k);
-        return PG_ERR_UNSUPPORTED;
-    }
     pg::RowFilter f;
-    f.col = c.d;
-    f.dtype = c.dtype;
-    f.op = op;
-    f.val = value;
+    int rc;
+    if ((rc = pg::where_check("pg_recall_topk_where", ctx, t, fs, column, op, value, metric, queries, out_rows, out_scores, nq, k, &f)))
+        return rc;
     std::lock_guard<std::mutex> g(ctx->mu);
     pg::TableRead tr(t->rw);
-    void* buf;
-    int rc;
-    const size_t qb = (size_t)nq * t->dim * 4, rb = (size_t)nq * k * 8, sb = (size_t)nq * k * 4;
-    if ((rc = pg::scratch_reserve(ctx, 5, qb + rb + sb + 64, &buf))) return rc;
-    float* d_q = (float*)buf;
-    uint64_t* d_rows = (uint64_t*)((char*)buf + ((qb + 15) & ~(size_t)15));
-    float* d_sc = (float*)((char*)d_rows + rb);
-    PG_HIP(hipMemcpyAsync(d_q, queries, qb, hipMemcpyHostToDevice, ctx->stream));
-    uint32_t *d_blk, *d_grp, cblocks, admitted;
-    if ((rc = pg::filter_count_locked(ctx, f, t->rows, &d_blk, &d_grp, &cblocks, &admitted))) return rc;
-    f.admitted = admitted;
-    if (admitted == 0) {
-        // nothing passes: every slot is padding (row UINT64_MAX, score -inf / distance +inf), every count 0
-        pg::recall_pad_kernel<<<(uint32_t)(((size_t)nq * k + 255) / 256), 256, 0, ctx->stream>>>(d_rows, d_sc, (size_t)nq * k, metric == 1);
-        PG_HIP(hipGetLastError());
-        if (out_count) for (uint32_t q = 0; q < nq; ++q) out_count[q] = 0;
-    } else if (admitted <= (nq <= 4 ? ctx->knobs.where_compact_max_rows / 2 : ctx->knobs.where_compact_max_rows) &&
-               (uint64_t)admitted * ctx->knobs.where_compact_min_ratio <= t->rows &&
-               (metric == 0 || t->dim == 64 || t->dim == 128)) {
-        // A selective filter: the thresholds the scan plans estimate from samples of the table say little about the few rows
-        // that pass (1 % admitted of 100 M rows, 128 queries: 180 ms of re-planned passes).  Gather the admitted rows, in row
-        // order, into a compact table and run the exact scan over that: its rows are the candidates, its row order the tie
-        // order, and the answer's local rows map back through the id list.  (The gather is 1 KB of traffic per admitted row: at
-        // 100 M x 128 the copy wins below ~4 M rows for a lone query — in place 2.2 ms at 4 % — and below ~8 M for 16+ queries.)
-        const size_t idb = (((size_t)admitted + 64) * 4 + 255) & ~(size_t)255;
-        const size_t tabb = (((size_t)admitted + 64) * t->dim * 4 + 255) & ~(size_t)255;
-        const size_t nxb = metric == 1 ? (((size_t)admitted + 64) * 4 + 255) & ~(size_t)255 : 0;
-        void* gbuf;
-        if ((rc = pg::scratch_reserve(ctx, 13, idb + tabb + nxb, &gbuf))) return rc;
-        uint32_t* d_ids = (uint32_t*)gbuf;
-        float* d_tab = (float*)((char*)gbuf + idb);
-        float* d_cnx = nxb ? (float*)((char*)gbuf + idb + tabb) : nullptr;
-        pg::filter_scatter_kernel<<<cblocks, 256, 0, ctx->stream>>>(f, t->rows, d_blk, d_grp, d_ids);
-        const uint64_t quads = (uint64_t)admitted * (t->dim / 4);
-        pg::compact_gather_kernel<<<(uint32_t)((quads + 255) / 256), 256, 0, ctx->stream>>>(t->d, d_ids, admitted, t->dim, d_tab);
-        PG_HIP(hipMemsetAsync(d_tab + (size_t)admitted * t->dim, 0, (size_t)64 * t->dim * 4, ctx->stream));
-        pg_table ct;
-        ct.d = d_tab;
-        ct.rows = admitted;
-        ct.dim = t->dim;
-        if (metric == 1) {
-            if ((rc = pg::ensure_table_nx(ctx, t))) return rc;
-            pg::compact_gather_nx_kernel<<<(admitted + 64 + 255) / 256, 256, 0, ctx->stream>>>(t->d_nx, d_ids, admitted, d_cnx);
-            ct.d_nx = d_cnx;
-            ct.nx_valid = true;
-        }
-        PG_HIP(hipGetLastError());
-        pg::RecallOpts o;
-        o.l2 = metric == 1;
-        o.exact_only = true;
-        if ((rc = pg::recall_batches_locked(ctx, &ct, d_q, nq, k, d_rows, d_sc, out_count, o))) return rc;
-        pg::compact_map_rows_kernel<<<(uint32_t)(((size_t)nq * k + 255) / 256), 256, 0, ctx->stream>>>(d_rows, (uint64_t)nq * k, d_ids, t->row_offset, admitted);
-        PG_HIP(hipGetLastError());
-        ct.d = nullptr;
-        ct.d_nx = nullptr;
-    } else {
-        pg::RecallOpts o;
-        o.l2 = metric == 1;
-        o.filter = &f;
-        if ((rc = pg::recall_batches_locked(ctx, t, d_q, nq, k, d_rows, d_sc, out_count, o))) return rc;
-    }
-    PG_HIP(hipMemcpyAsync(out_rows, d_rows, rb, hipMemcpyDeviceToHost, ctx->stream));
-    PG_HIP(hipMemcpyAsync(out_scores, d_sc, sb, hipMemcpyDeviceToHost, ctx->stream));
-    PG_HIP(hipStreamSynchronize(ctx->stream));
+    pg_index* ix = pg::index_route_where(ctx, t);          // ("index_route_where": the attached index, when it is current)
+    uint32_t counts[pg::kMaxQueries];
+    auto run = [&](const float* d_q, uint64_t* d_rows, float* d_sc) {
+        return ix ? pg::index_where_locked(ctx, ix, fs, column, f, metric == 1, d_q, nq, k, d_rows, d_sc, counts)
+                  : pg::recall_where_locked(ctx, t, f, metric, d_q, nq, k, d_rows, d_sc, counts);
+    };
+    if ((rc = pg::recall_staged(ctx, t->dim, queries, nq, k, out_rows, out_scores, run))) return rc;
+    if (out_count) memcpy(out_count, counts, (size_t)nq * 4);
     return PG_OK;
 }
 

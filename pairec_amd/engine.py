@@ -305,6 +305,43 @@ class Index:
         _lib.check(self.ctx.L.pg_index_bounds(self.ctx.h, self.h, _ptr(q), q.shape[0], int(l2), _ptr(out)))
         return out
 
+    def recall_topk_where(self, feats: "Features", column: str, op: str, value: int, queries: np.ndarray, k: int, l2: bool = False):
+        """as Table.recall_topk_where, through the index over the filter's lists (pg_index_recall_topk_where)
+        → (rows, scores or distances, counts)"""
+        ops = {">": 0, ">=": 1, "<": 2, "<=": 3, "==": 4, "!=": 5}
+        dim = self.table.dim
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, dim)
+        nq = q.shape[0]
+        rows = np.empty((nq, k), dtype=np.uint64)
+        scores = np.empty((nq, k), dtype=np.float32)
+        counts = np.zeros(nq, dtype=np.uint32)
+        col = self.ctx.L.pg_features_column_index(feats.h, column.encode())
+        for s in range(0, nq, MAX_QUERIES):          # batches split as Table.recall_topk_where splits them
+            e = min(nq, s + MAX_QUERIES)
+            r_, s_, c_ = rows[s:e], scores[s:e], counts[s:e]
+            _lib.check(self.ctx.L.pg_index_recall_topk_where(self.ctx.h, self.h, feats.h, col, ops[op], int(value), 1 if l2 else 0,
+                                                             _ptr(q[s:e]), e - s, k, _ptr(r_), _ptr(s_), _ptr(c_)))
+        return rows, scores, counts
+
+    def where_read(self, feats: "Features", column: str, op: str, value: int) -> dict:
+        """a filter's lists over the index (pg_index_where_read, built or from the cache): offsets [n_lists + 1] and perm
+        [admitted] uint32 — list L holds perm[offsets[L]:offsets[L + 1]], the index's rows of L that pass, in order"""
+        ops = {">": 0, ">=": 1, "<": 2, "<=": 3, "==": 4, "!=": 5}
+        st = self.stats()
+        col = self.ctx.L.pg_features_column_index(feats.h, column.encode())
+        offsets = np.empty(st["n_lists"] + 1, np.uint32)
+        perm = np.empty(max(st["rows"], 1), np.uint32)
+        admitted = C.c_uint64()
+        _lib.check(self.ctx.L.pg_index_where_read(self.ctx.h, self.h, feats.h, col, ops[op], int(value), _ptr(offsets), _ptr(perm),
+                                                  C.byref(admitted)))
+        return {"offsets": offsets, "perm": perm[:admitted.value].copy(), "admitted": admitted.value}
+
+    def where_stats(self) -> dict:
+        """the filtered lists' cache: builds, hits, evictions, entries held and their device bytes (pg_index_where_stats)"""
+        st = _lib.PgIndexWhereStats()
+        _lib.check(self.ctx.L.pg_index_where_stats(self.h, C.byref(st)))
+        return {name: getattr(st, name) for name, _ in st._fields_}
+
     def attach(self, ctx: Context = None):
         """Route every recall job of the table (plain recalls, coalescer batches, recommend pipelines) through this index first
         (pg_index_attach); a second attached index replaces the first."""
