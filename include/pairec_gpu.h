@@ -90,7 +90,8 @@ int pg_synchronize(pg_ctx* ctx);
  * the table's pass), and for an attached index "index_plan_rounds" / "index_skip_batches" (see pg_index_attach); for filtered
  * recalls through an index (pg_index_recall_topk_where) "index_where_cache" (default 4 filtered lists kept per index; 0 = built
  * per call and freed after it) and "index_route_where" (default 0; 1: pg_recall_topk_where on a table whose attached index is
- * current searches that index, synchronously).
+ * current searches that index, synchronously); for pg_index_refresh "index_refresh_full_fraction" (default 0.1: in auto mode
+ * more written rows than this share of the table are refreshed in full; a table's write log is dropped past it too).
  * value is parsed as a number. */
 int pg_set_option(pg_ctx* ctx, const char* name, const char* value);
 int pg_device_malloc(pg_ctx* ctx, size_t bytes, void** out);
@@ -406,7 +407,7 @@ int pg_table_view_create(pg_ctx* ctx, const pg_table* t, const pg_features* fs, 
  *             table must outlive the index.  Read-only after build: recalls from several contexts may run at once, each with
  *             its own context's scratch.
  *   Stale     after pg_table_upload, _fill_* or _swap the table's generation differs from the one the index was built against;
- *             a recall through it is then served by the table's own pass (exact, counted as `stale`).  Rebuilding is the caller's job.
+ *             a recall through it is then served by the table's own pass (exact, counted as `stale`) until pg_index_refresh.
  *   Refusals  a view as the source, and tables of >= 2^32 rows, return PG_ERR_UNSUPPORTED.
  *   Fallbacks a table with non-finite values builds, every recall through it is served by the table's pass (`nonfinite`, also
  *             counted for a batch with a non-finite query); a batch of nq queries whose live (row, query) pairs would exceed
@@ -510,6 +511,56 @@ typedef struct {
     uint64_t entries, bytes;            /* the entries the cache holds and their device bytes */
 } pg_index_where_stats_t;
 int pg_index_where_stats(const pg_index* ix, pg_index_where_stats_t* out);
+
+/* Refresh: bring an existing index back to its table's current rows KEEPING ITS CENTROIDS — cheap when few
+ * rows were written, several times cheaper than pg_index_build when all of them were (nothing is trained).  Nothing changes
+ * until it is called: a written table still makes its index stale.
+ *   Exact     after a refresh every recall through the index, attached or not, filtered or not, is bit for bit the table's pass
+ *             on the current rows, as after a build: every radius is measured anew over the rows of the new lists.
+ *   Rule      a row's list is the one the build's assignment gives it for the kept centroids (the smallest cn2[L] - 2 x.c_L in
+ *             the build's fp32 chains, ties to the lower list, a NaN row to list 0), whichever mode ran: pg_index_read afterwards
+ *             equals what the build's sort, offsets and radius steps produce for these centroids and rows; centroids and cnorm are
+ *             unchanged; a forced full refresh of an unchanged table reproduces the built arrays.
+ *   Modes     incremental: only the rows in the table's write log are re-assigned (the log: at most 64 disjoint row ranges that
+ *             pg_table_upload wrote since some generation; pg_table_fill_*, pg_table_swap, a 65th range and more than
+ *             "index_refresh_full_fraction" of the rows — the option of the context that uploads — reset it).  full: every row, on the bf16 matrix pipe as a rigorous screen
+ *             with the surviving lists confirmed by the rule's own chain (dim 64 / 128; rows it cannot settle, and dim 192 / 256,
+ *             go through the build's fp32 kernel).  mode 0 picks incremental when the log covers every write since the index's
+ *             generation and holds at most that fraction of the rows, else full; mode 1 is full; mode 2 is incremental, or
+ *             PG_ERR_UNSUPPORTED (the index unchanged) when the log does not reach back.  A current index is left alone
+ *             (`noop`) unless force != 0 (then mode 0 / 1 refresh in full).
+ *   Install   the new arrays are built in new device memory under the table's shared lock (other contexts keep serving through
+ *             the table's pass), then exchanged as pg_index_attach replaces an index: the table's lock exclusively, no generation
+ *             bump, the device drained.  The index then describes the generation read under the shared lock: a write in
+ *             between leaves it stale again.  Its filtered lists' cache is dropped.  An attached index stays attached, its
+ *             counters go on.  Any context may call it; refreshes of one index are serialised.
+ *   Context   the calling context is busy for the whole refresh (seconds at 100 M rows: every other call on it, a coalescer
+ *             created on it included, waits): refresh from the loader's context, not from the one that serves.
+ *   Errors    PG_ERR_INVALID for a NULL ctx / ix or an unknown mode; PG_ERR_NOMEM / PG_ERR_DEVICE leave the index as it was,
+ *             stale and valid.  A refresh holds about 24 B per row of device memory beside the index while it runs (the new
+ *             permutation, three row-sized work arrays, the sort's 8 B per row: 2.4 GB at 100 M rows) plus a 128 MB gather buffer.
+ * pg_index_stats reports the refreshed generation, radii, largest_list and empty_lists afterwards; build_ms stays the build's. */
+typedef struct {
+    int      mode;        /* 0 = auto, 1 = full, 2 = incremental or PG_ERR_UNSUPPORTED */
+    int      force;       /* != 0: refresh even when the index is current */
+} pg_index_refresh_params;                       /* NULL = {0, 0} */
+int pg_index_refresh(pg_ctx* ctx, pg_index* ix, const pg_index_refresh_params* p);
+typedef struct {
+    uint64_t refreshes, full, incremental, noop;  /* calls by what they did (noop: the index was current and force == 0) */
+    uint64_t rows_reassigned;                     /* rows whose list was recomputed, summed */
+    uint64_t rows_moved;                          /* ... of which the list changed */
+    uint64_t rows_confirmed_wide;                 /* full refreshes: rows that left the matrix-pipe screen for the fp32 kernel */
+    uint64_t last_generation;                     /* the table generation the index describes now */
+    double   last_ms, last_assign_ms;             /* wall time of the last refresh, device time of its assignment */
+} pg_index_refresh_stats_t;
+int pg_index_refresh_stats(const pg_index* ix, pg_index_refresh_stats_t* out);
+/* Diagnostic of the full refresh's matrix-pipe screen: for host rows [n][dim] and centroids [n_lists][dim]
+ * (dim 64 / 128, n and n_lists <= 65536) out_s[row][L] is the screen's distance — the same loads, MFMA sequence and formulas as
+ * the assignment — and out_e[row][L] the bound e(x, L) the kernel applies to it, +inf where the row or the centroid lies
+ * outside the range the bound is claimed for.  |out_s - (cn2[L] - 2 x.c_L in the build's fp32 chains)| <= out_e is what the
+ * equality of the two refresh modes rests on; tests check it on the device.  PG_ERR_INVALID for NULLs, dim or sizes. */
+int pg_index_screen_probe(pg_ctx* ctx, uint32_t dim, const float* rows, uint32_t n, const float* centroids, uint32_t n_lists,
+                          float* out_s, float* out_e);
 /* FM + two-tower rank straight from candidate rows: the model's item field ids are the integer columns
  * item_field_cols[n_item_fields] of `fs` (out-of-vocabulary ids are clamped as in pg_rank_fm2t_dev) */
 int pg_rank_fm2t_rows_dev(pg_ctx* ctx, const pg_model* m, const pg_features* fs, const int32_t* item_field_cols,

@@ -41,6 +41,7 @@ EXPORTS = [
     "pg_index_build", "pg_index_destroy", "pg_index_recall_topk", "pg_index_recall_topk_dev", "pg_index_recall_topk_l2",
     "pg_index_recall_topk_l2_dev", "pg_index_stats", "pg_index_attach", "pg_index_detach", "pg_index_serving_stats",
     "pg_index_read", "pg_index_bounds", "pg_index_recall_topk_where", "pg_index_where_read", "pg_index_where_stats",
+    "pg_index_refresh", "pg_index_refresh_stats", "pg_index_screen_probe",
 ]
 
 
@@ -77,6 +78,16 @@ class PgIndexServingStats(C.Structure):
 class PgIndexWhereStats(C.Structure):
     _fields_ = [("builds", C.c_uint64), ("hits", C.c_uint64), ("evictions", C.c_uint64), ("entries", C.c_uint64),
                 ("bytes", C.c_uint64)]
+
+
+class PgIndexRefreshParams(C.Structure):
+    _fields_ = [("mode", C.c_int), ("force", C.c_int)]
+
+
+class PgIndexRefreshStats(C.Structure):
+    _fields_ = [("refreshes", C.c_uint64), ("full", C.c_uint64), ("incremental", C.c_uint64), ("noop", C.c_uint64),
+                ("rows_reassigned", C.c_uint64), ("rows_moved", C.c_uint64), ("rows_confirmed_wide", C.c_uint64),
+                ("last_generation", C.c_uint64), ("last_ms", C.c_double), ("last_assign_ms", C.c_double)]
 
 
 class PgDppOptions(C.Structure):
@@ -168,6 +179,9 @@ def load():
         "pg_index_recall_topk_where": [vp, vp, vp, i32, i32, C.c_longlong, i32, vp, u32, u32, vp, vp, vp],
         "pg_index_where_read": [vp, vp, vp, i32, i32, C.c_longlong, vp, vp, vp],
         "pg_index_where_stats": [vp, P(PgIndexWhereStats)],
+        "pg_index_refresh": [vp, vp, P(PgIndexRefreshParams)],
+        "pg_index_refresh_stats": [vp, P(PgIndexRefreshStats)],
+        "pg_index_screen_probe": [vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, vp, vp],
         "pg_index_read": [vp, vp, vp, vp, vp, vp, vp],
         "pg_index_bounds": [vp, vp, vp, u32, i32, vp],
         "pg_topk_merge_dev": [vp, vp, vp, u32, u32, u32, u32, vp, vp],

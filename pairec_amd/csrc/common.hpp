@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -99,6 +100,7 @@ struct Knobs {
     uint32_t index_skip_batches = 64;       // PG_INDEX_SKIP_BATCHES: after a dense or rounds re-plan, batches of that size band that skip the index plan
     uint32_t index_where_cache = 4;         // PG_INDEX_WHERE_CACHE: filtered lists an index keeps per filter (0: built per call, freed after it)
     bool index_route_where = false;         // PG_INDEX_ROUTE_WHERE: pg_recall_topk_where on a table with a current attached index searches it
+    double index_refresh_full_fraction = 0.1;   // PG_INDEX_REFRESH_FULL_FRACTION: pg_index_refresh in auto mode re-assigns every row once the written rows exceed this share of the table
 };
 
 }  // namespace pg
@@ -115,6 +117,14 @@ struct pg_table {
     // pg_index_attach: the index that every RecallJob on this table tries first (index.hip).  Written under the exclusive lock
     // with the device drained, read under the shared lock by recall_job_prepare; neither bumps the generation.
     mutable std::atomic<pg_index*> index{nullptr};
+    // The write log: every row written by a write that produced a generation in (log_since, generation] lies in
+    // one of the log_n disjoint, ascending, non-adjacent ranges [log_lo[i], log_hi[i]).  Written under the exclusive lock the
+    // writers hold (TableWrite, table_log_add), read under the shared lock (pg_index_refresh: several indexes of one table at
+    // different generations read the same log).  The set only grows between resets.
+    static constexpr uint32_t kLogRanges = 64;
+    mutable uint64_t log_lo[kLogRanges], log_hi[kLogRanges];
+    mutable uint32_t log_n = 0;
+    mutable uint64_t log_since = 0;
     float* d = nullptr;          // [rows][dim] fp32 row-major
     uint64_t rows = 0;
     uint32_t dim = 0;
@@ -269,16 +279,56 @@ struct TableRead2 {
         if (y && y != x) b = TableRead(y->rw);
     }
 };
-// exclusive access to one or two tables (address order) with nothing in flight on the device
+// the write log of a table whose every row may have changed: empty, complete from the generation just produced (caller holds
+// the table's lock exclusively and has bumped the generation)
+inline void table_log_reset(const pg_table* t) {
+    t->log_n = 0;
+    t->log_since = t->generation.load(std::memory_order_relaxed);
+}
+// rows [row0, row0 + n) join the log (merged with the ranges they touch); a 65th range, or more than `full_fraction` of the
+// table in the log (the uploading context's "index_refresh_full_fraction"), resets it instead (caller as above)
+inline void table_log_add(const pg_table* t, uint64_t row0, uint64_t n, double full_fraction) {
+    uint64_t lo = row0, hi = row0 + n;
+    uint32_t w = 0, at = 0;
+    uint64_t total = 0;
+    bool placed = false;
+    uint64_t nlo[pg_table::kLogRanges + 1], nhi[pg_table::kLogRanges + 1];
+    for (uint32_t i = 0; i < t->log_n; ++i) {
+        if (t->log_hi[i] >= lo && t->log_lo[i] <= hi) {          // overlapping or adjacent: absorbed
+            lo = std::min(lo, t->log_lo[i]);
+            hi = std::max(hi, t->log_hi[i]);
+            continue;
+        }
+        if (!placed && t->log_lo[i] > hi) { at = w++; placed = true; }
+        nlo[w] = t->log_lo[i];
+        nhi[w] = t->log_hi[i];
+        total += nhi[w] - nlo[w];
+        ++w;
+    }
+    if (!placed) at = w++;
+    nlo[at] = lo;
+    nhi[at] = hi;
+    total += hi - lo;
+    if (w > pg_table::kLogRanges || (double)total > full_fraction * (double)t->rows) {
+        table_log_reset(t);
+        return;
+    }
+    for (uint32_t i = 0; i < w; ++i) { t->log_lo[i] = nlo[i]; t->log_hi[i] = nhi[i]; }
+    t->log_n = w;
+}
+// exclusive access to one or two tables (address order) with nothing in flight on the device.  Every row may change: the write
+// log is reset, unless the caller logs the rows it writes itself (keep_log: pg_table_upload, table_log_add)
 struct TableWrite {
     std::unique_lock<std::shared_mutex> a, b;
-    TableWrite(const pg_table* x, const pg_table* y = nullptr) {
+    TableWrite(const pg_table* x, const pg_table* y = nullptr, bool keep_log = false) {
         if (y && y < x) std::swap(x, y);
         a = std::unique_lock<std::shared_mutex>(x->rw);
         x->generation.fetch_add(1, std::memory_order_relaxed);
+        if (!keep_log) table_log_reset(x);
         if (y && y != x) {
             b = std::unique_lock<std::shared_mutex>(y->rw);
             y->generation.fetch_add(1, std::memory_order_relaxed);
+            if (!keep_log) table_log_reset(y);
         }
     }
 };
@@ -430,6 +480,15 @@ int where_pad_launch(pg_ctx* ctx, uint64_t* d_rows, float* d_sc, size_t n, bool 
 pg_index* index_route_where(const pg_ctx* ctx, const pg_table* t);
 int index_where_locked(pg_ctx* ctx, pg_index* ix, const pg_features* fs, int column, const RowFilter& f, bool l2, const float* d_q,
                        uint32_t nq, uint32_t k, uint64_t* d_rows, float* d_sc, uint32_t* h_counts);
+// index_assign.hip: the matrix-pipe assignment of pg_index_refresh's full path (dim 64 / 128).  The split bf16
+// screen over all lists with the survivors confirmed by the rule's chain: out[r] = the rule's list of row r, except for the
+// rows the screen could not settle (more survivors than slots, a row outside the range the bound is proven for), whose ids are
+// appended to wide[*wide_n ...] in no particular order.  *flag |= 1 for a non-finite row element.  ws: assign_screen_ws_bytes()
+// of device memory.  Returns PG_ERR_UNSUPPORTED (nothing enqueued beyond the workspace's preparation, which synchronises) when
+// a centroid lies outside that range: the caller assigns with the fp32 kernel.
+size_t assign_screen_ws_bytes(uint32_t nl, uint32_t dim);
+int assign_screen_launch(pg_ctx* ctx, uint32_t dim, const float* X, uint64_t n, const float* C, uint32_t nl, void* ws, uint32_t* out,
+                         uint32_t* wide, uint32_t* wide_n, uint32_t* flag);
 // features.hip: a process-wide counter, so a column's version never repeats (not even for a store reallocated at one address)
 uint64_t next_column_version();
 // re-run the failed queries of `j` (at most kMaxPatchQueries) one by one, synchronously, writing into their slices of

@@ -88,6 +88,10 @@ struct pg_index {
     std::mutex where_mu;
     std::list<std::shared_ptr<pg::WhereLists>> where_cache;
     pg_index_where_stats_t where_st{};
+    // pg_index_refresh: one refresh of an index at a time (taken after ctx->mu, before the table's lock); the
+    // counters are guarded by mu
+    std::mutex refresh_mu;
+    pg_index_refresh_stats_t rst{};
 };
 
 namespace pg {
@@ -264,6 +268,57 @@ __global__ void cnorm_kernel(const float* __restrict__ C, uint32_t nl, uint32_t 
     double s = 0.0;
     for (uint32_t k = 0; k < dim; ++k) s = fma((double)C[(size_t)L * dim + k], (double)C[(size_t)L * dim + k], s);
     out[L] = round_up_f(sqrt(s) * (1.0 + 0x1p-40));
+}
+
+// ---- refresh ----------------------------------------------------------------------------------
+// the per-row list recovered from the index: position p of the permutation lies in list L with off[L] <= p < off[L + 1]
+__global__ void list_of_row_kernel(const uint32_t* __restrict__ perm, const uint32_t* __restrict__ off, uint64_t rows, uint32_t nl,
+                                   uint32_t* __restrict__ assign) {
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= rows) return;
+    uint32_t lo = 0, hi = nl;                // the last L with off[L] <= p (off[0] = 0, off[nl] = rows > p)
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (off[mid] <= (uint32_t)p) lo = mid;
+        else hi = mid;
+    }
+    const uint32_t row = perm[p];
+    if (row < rows) assign[row] = lo;
+}
+
+__global__ void iota_from_kernel(uint32_t* __restrict__ v, uint64_t n, uint32_t first) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) v[i] = first + (uint32_t)i;
+}
+
+// assign[ids[i]] = vals[i]; moved (may be null: assign holds nothing to compare with) += the rows whose list changes
+__global__ void patch_kernel(const uint32_t* __restrict__ ids, const uint32_t* __restrict__ vals, uint32_t n, uint64_t rows,
+                             uint32_t* __restrict__ assign, unsigned long long* __restrict__ moved) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    bool m = false;
+    if (i < n && ids[i] < rows) {
+        m = moved && assign[ids[i]] != vals[i];
+        assign[ids[i]] = vals[i];
+    }
+    if (!moved) return;                      // (uniform)
+    const unsigned long long c = __popcll(__builtin_amdgcn_ballot_w64(m));
+    if ((threadIdx.x & 63) == 0 && c) atomicAdd(moved, c);
+}
+
+__global__ void count_moved_kernel(const uint32_t* __restrict__ a, const uint32_t* __restrict__ b, uint64_t rows,
+                                   unsigned long long* __restrict__ moved) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool m = i < rows && a[i] != b[i];
+    const unsigned long long c = __popcll(__builtin_amdgcn_ballot_w64(m));
+    if ((threadIdx.x & 63) == 0 && c) atomicAdd(moved, c);
+}
+
+// *flag |= 1 when an element of the table is not finite
+__global__ void finite_kernel(const float* __restrict__ tab, uint64_t n_elems, uint32_t* __restrict__ flag) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    bool bad = false;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_elems; i += stride) bad |= !isfinite(tab[i]);
+    if (bad) atomicOr(flag, 1u);
 }
 
 // ---- search --------------------------------------------------------------------------------------------------
@@ -695,6 +750,25 @@ uint64_t splitmix(uint64_t& x) {
     return z ^ (z >> 31);
 }
 
+// the lists' figures of pg_index_stats from their radii and offsets (the build's and every refresh's)
+void list_summary(const std::vector<float>& rad, const std::vector<uint32_t>& off, pg_index_stats_t* st) {
+    const uint32_t nl = (uint32_t)rad.size();
+    double sum_r = 0.0;
+    float max_r = 0.0f;
+    uint32_t largest = 0, empty = 0;
+    for (uint32_t L = 0; L < nl; ++L) {
+        const uint32_t sz = off[L + 1] - off[L];
+        if (!sz) { ++empty; continue; }
+        largest = std::max(largest, sz);
+        sum_r += rad[L];
+        max_r = std::max(max_r, rad[L]);
+    }
+    st->max_radius = max_r;
+    st->mean_radius = nl > empty ? (float)(sum_r / (nl - empty)) : 0.0f;
+    st->largest_list = largest;
+    st->empty_lists = empty;
+}
+
 int index_build_locked(pg_ctx* ctx, const pg_table* t, const pg_index_params& p, pg_index* ix, std::vector<void*>& owned,
                        std::vector<void*>& temp) {
     const uint64_t rows = t->rows;
@@ -767,23 +841,144 @@ int index_build_locked(pg_ctx* ctx, const pg_table* t, const pg_index_params& p,
     PG_HIP(hipMemcpyAsync(&h_flag, flag, 4, hipMemcpyDeviceToHost, ctx->stream));
     PG_HIP(hipStreamSynchronize(ctx->stream));
     ix->nonfinite = h_flag != 0;
-    double sum_r = 0.0;
-    float max_r = 0.0f;
-    uint32_t largest = 0, empty = 0;
-    for (uint32_t L = 0; L < nl; ++L) {
-        const uint32_t sz = off[L + 1] - off[L];
-        if (!sz) { ++empty; continue; }
-        largest = std::max(largest, sz);
-        sum_r += rad[L];
-        max_r = std::max(max_r, rad[L]);
-    }
     ix->st.n_lists = nl;
     ix->st.dim = dim;
     ix->st.rows = rows;
-    ix->st.max_radius = max_r;
-    ix->st.mean_radius = nl > empty ? (float)(sum_r / (nl - empty)) : 0.0f;
-    ix->st.largest_list = largest;
-    ix->st.empty_lists = empty;
+    list_summary(rad, off, &ix->st);
+    return PG_OK;
+}
+
+// ---- refresh: host --------------------------------------------------------------------------------
+constexpr uint32_t kReassignChunk = 1u << 18;        // rows gathered per assign_kernel launch (128 MB at dim 128)
+
+// the rule's list of the rows ids[0, count) (device), computed by assign_kernel over a gathered copy of them and patched into
+// assign; xg: [kReassignChunk][dim], vals: [kReassignChunk]
+int reassign_rows(pg_ctx* ctx, const pg_table* t, const float* C, float* cn2, uint32_t nl, const uint32_t* ids, uint64_t count, float* xg,
+                  uint32_t* vals, uint32_t* assign, uint32_t* flag, unsigned long long* moved) {
+    int rc;
+    for (uint64_t at = 0; at < count; at += kReassignChunk) {
+        const uint32_t m = (uint32_t)std::min<uint64_t>(kReassignChunk, count - at);
+        if ((rc = table_gather_locked(ctx, t, ids + at, m, xg))) return rc;
+        if ((rc = assign_dispatch(ctx, t->dim, xg, m, C, cn2, nl, vals, flag))) return rc;
+        patch_kernel<<<(m + 255) / 256, 256, 0, ctx->stream>>>(ids + at, vals, m, t->rows, assign, moved);
+        PG_HIP(hipGetLastError());
+    }
+    return PG_OK;
+}
+
+struct RefreshOut {                      // what a refresh built (owned until installed) and counted
+    uint32_t* perm = nullptr;
+    void* small = nullptr;
+    bool nonfinite = false;
+    uint64_t reassigned = 0, moved = 0, wide = 0;
+    double assign_ms = 0.0;
+    std::vector<float> rad;
+    std::vector<uint32_t> off;
+};
+
+// The new permutation, offsets and radii of ix for the table's current rows and ix's centroids, in new buffers; caller holds
+// ctx->mu and the table's shared lock.  incremental: only the rows of the table's write log are re-assigned.
+int index_refresh_locked(pg_ctx* ctx, const pg_index* ix, bool incremental, RefreshOut* o, std::vector<void*>& owned,
+                         std::vector<void*>& temp, hipEvent_t ev0, hipEvent_t ev1) {
+    const pg_table* t = ix->t;
+    const uint64_t rows = ix->rows;
+    const uint32_t dim = ix->dim, nl = ix->n_lists;
+    hipStream_t s = ctx->stream;
+    int rc;
+    if ((rc = dalloc((void**)&o->perm, rows * 4, owned))) return rc;
+    const size_t off_b = ((size_t)(nl + 1) * 4 + 255) & ~(size_t)255, cent_b = (size_t)nl * dim * 4, lists_b = ((size_t)nl * 4 + 255) & ~(size_t)255;
+    if ((rc = dalloc(&o->small, off_b + cent_b + 2 * lists_b, owned))) return rc;
+    uint32_t* const n_off = (uint32_t*)o->small;
+    float* const n_cent = (float*)((char*)o->small + off_b);
+    float* const n_cnorm = (float*)((char*)n_cent + cent_b);
+    float* const n_rad = (float*)((char*)n_cnorm + lists_b);
+    float *cn2, *xg;
+    uint32_t *assign, *keys_s, *vals_in, *vals, *flag;
+    if ((rc = dalloc((void**)&cn2, (size_t)nl * 4, temp))) return rc;
+    if ((rc = dalloc((void**)&assign, rows * 4, temp))) return rc;
+    if ((rc = dalloc((void**)&keys_s, rows * 4, temp))) return rc;
+    if ((rc = dalloc((void**)&vals_in, rows * 4, temp))) return rc;
+    if ((rc = dalloc((void**)&flag, 32, temp))) return rc;
+    const uint64_t chunk = std::min<uint64_t>(kReassignChunk, rows);
+    if ((rc = dalloc((void**)&xg, chunk * dim * 4, temp))) return rc;
+    if ((rc = dalloc((void**)&vals, chunk * 4, temp))) return rc;
+    size_t tmp_bytes = 0;
+    void* tmp;
+    if ((rc = sort_temp_bytes(rows, nl, &tmp_bytes))) return rc;
+    if ((rc = dalloc(&tmp, tmp_bytes, temp))) return rc;
+    unsigned long long* const moved = (unsigned long long*)(flag + 2);        // flag[0] non-finite, flag[1] wide rows, [2, 4) moved
+    PG_HIP(hipMemsetAsync(flag, 0, 32, s));
+    // the centroids and their norms stay: bit copies
+    PG_HIP(hipMemcpyAsync(n_cent, ix->d_cent, cent_b, hipMemcpyDeviceToDevice, s));
+    PG_HIP(hipMemcpyAsync(n_cnorm, ix->d_cnorm, (size_t)nl * 4, hipMemcpyDeviceToDevice, s));
+    // the lists the index holds now, per row (the full path counts the moved rows against them)
+    uint32_t* const old_assign = incremental ? assign : vals_in;
+    list_of_row_kernel<<<(uint32_t)((rows + 255) / 256), 256, 0, s>>>(ix->d_perm, ix->d_off, rows, nl, old_assign);
+    PG_HIP(hipGetLastError());
+    PG_HIP(hipEventRecord(ev0, s));
+    if (incremental) {
+        // the log's rows, gathered and re-assigned by the rule's own kernel, patched into the recovered lists
+        uint64_t d_rows = 0;
+        for (uint32_t i = 0; i < t->log_n; ++i) d_rows += t->log_hi[i] - t->log_lo[i];
+        uint32_t* ids = keys_s;              // (free until the sort)
+        uint64_t at = 0;
+        for (uint32_t i = 0; i < t->log_n; ++i) {
+            const uint64_t m = t->log_hi[i] - t->log_lo[i];
+            iota_from_kernel<<<(uint32_t)((m + 255) / 256), 256, 0, s>>>(ids + at, m, (uint32_t)t->log_lo[i]);
+            PG_HIP(hipGetLastError());
+            at += m;
+        }
+        if ((rc = reassign_rows(ctx, t, ix->d_cent, cn2, nl, ids, d_rows, xg, vals, assign, flag, moved))) return rc;
+        o->reassigned = d_rows;
+        if (ix->nonfinite) {                 // (which rows were not finite is not recorded: look at all of them)
+            PG_HIP(hipMemsetAsync(flag, 0, 4, s));
+            finite_kernel<<<(uint32_t)ctx->num_cus * 8, 256, 0, s>>>(t->d, rows * dim, flag);
+            PG_HIP(hipGetLastError());
+        }
+    } else {
+        bool screened = false;
+        if (dim == 64 || dim == 128) {
+            void* ws;
+            uint32_t* const wide = keys_s;   // (free until the sort)
+            if ((rc = dalloc(&ws, assign_screen_ws_bytes(nl, dim), temp))) return rc;
+            rc = assign_screen_launch(ctx, dim, t->d, rows, ix->d_cent, nl, ws, assign, wide, flag + 1, flag);
+            if (rc == PG_OK) {
+                screened = true;
+                uint32_t h_wide = 0;
+                PG_HIP(hipMemcpyAsync(&h_wide, flag + 1, 4, hipMemcpyDeviceToHost, s));
+                PG_HIP(hipStreamSynchronize(s));
+                // the rows the screen left open: the fp32 kernel against all lists (`assign` holds nothing for them yet: the
+                // moved rows are counted against old_assign below)
+                if ((rc = reassign_rows(ctx, t, ix->d_cent, cn2, nl, wide, h_wide, xg, vals, assign, flag, nullptr))) return rc;
+                o->wide = h_wide;
+            } else if (rc != PG_ERR_UNSUPPORTED) {
+                return rc;
+            }
+        }
+        // (a centroid outside the screen's range, dim 192 / 256: the fp32 kernel for every row)
+        if (!screened && (rc = assign_dispatch(ctx, dim, t->d, rows, ix->d_cent, cn2, nl, assign, flag))) return rc;
+        count_moved_kernel<<<(uint32_t)((rows + 255) / 256), 256, 0, s>>>(old_assign, assign, rows, moved);
+        PG_HIP(hipGetLastError());
+        o->reassigned = rows;
+    }
+    PG_HIP(hipEventRecord(ev1, s));
+    // the build's steps: the stable sort by list is the permutation, offsets, radii over the rows actually assigned
+    if ((rc = sort_by_list(ctx, assign, rows, nl, keys_s, vals_in, o->perm, n_off, tmp, tmp_bytes))) return rc;
+    PG_HIP(hipMemsetAsync(n_rad, 0, (size_t)nl * 4, s));
+    radius_kernel<<<(uint32_t)((rows + 255) / 256), 256, 0, s>>>(t->d, rows, dim, assign, ix->d_cent, (uint32_t*)n_rad);
+    PG_HIP(hipGetLastError());
+    o->rad.resize(nl);
+    o->off.resize((size_t)nl + 1);
+    uint32_t h_flag[4] = {0, 0, 0, 0};
+    PG_HIP(hipMemcpyAsync(o->rad.data(), n_rad, (size_t)nl * 4, hipMemcpyDeviceToHost, s));
+    PG_HIP(hipMemcpyAsync(o->off.data(), n_off, ((size_t)nl + 1) * 4, hipMemcpyDeviceToHost, s));
+    PG_HIP(hipMemcpyAsync(h_flag, flag, 16, hipMemcpyDeviceToHost, s));
+    PG_HIP(hipStreamSynchronize(s));
+    o->nonfinite = h_flag[0] != 0;
+    memcpy(&o->moved, h_flag + 2, 8);
+    float ms = 0.0f;
+    PG_HIP(hipEventElapsedTime(&ms, ev0, ev1));
+    o->assign_ms = ms;
     return PG_OK;
 }
 
@@ -1311,6 +1506,113 @@ int pg_index_build(pg_ctx* ctx, const pg_table* t, const pg_index_params* p, pg_
     return PG_OK;
 }
 
+int pg_index_refresh(pg_ctx* ctx, pg_index* ix, const pg_index_refresh_params* p) {
+    PG_REQUIRE(ctx && ix, "pg_index_refresh: NULL argument");
+    const pg_index_refresh_params prm = p ? *p : pg_index_refresh_params{0, 0};
+    PG_REQUIRE(prm.mode >= 0 && prm.mode <= 2, "pg_index_refresh: mode %d unknown (0 auto, 1 full, 2 incremental)", prm.mode);
+    const pg_table* t = ix->t;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    std::lock_guard<std::mutex> gr(ix->refresh_mu);
+    const auto t0 = std::chrono::steady_clock::now();
+    pg::TableRead tr(t->rw);
+    const uint64_t gen = t->generation.load(std::memory_order_relaxed);
+    if (gen == ix->gen && !prm.force) {
+        std::lock_guard<std::mutex> gs(ix->mu);
+        ix->rst.refreshes++;
+        ix->rst.noop++;
+        return PG_OK;
+    }
+    // the write log covers every write since the index's generation?
+    const bool covered = ix->gen >= t->log_since;
+    uint64_t logged = 0;
+    for (uint32_t i = 0; i < t->log_n; ++i) logged += t->log_hi[i] - t->log_lo[i];
+    bool incremental;
+    if (prm.mode == 2) {
+        if (!covered) {
+            pg::set_error("pg_index_refresh: the table's write log starts at generation %llu, the index describes %llu (refresh in full)",
+                          (unsigned long long)t->log_since, (unsigned long long)ix->gen);
+            return PG_ERR_UNSUPPORTED;
+        }
+        incremental = true;
+    } else if (prm.mode == 1 || gen == ix->gen) {
+        incremental = false;
+    } else {
+        incremental = covered && (double)logged <= ctx->knobs.index_refresh_full_fraction * (double)ix->rows;
+    }
+    PG_HIP(hipSetDevice(ctx->device));
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    PG_HIP(hipEventCreate(&ev[0]));
+    if (hipEventCreate(&ev[1]) != hipSuccess) {
+        (void)hipEventDestroy(ev[0]);
+        pg::set_error("pg_index_refresh: %s", hipGetErrorString(hipGetLastError()));
+        return PG_ERR_DEVICE;
+    }
+    pg::RefreshOut o;
+    std::vector<void*> owned, temp;
+    int rc = pg::index_refresh_locked(ctx, ix, incremental, &o, owned, temp, ev[0], ev[1]);
+    if (rc != PG_OK) (void)hipStreamSynchronize(ctx->stream);
+    pg::free_all(temp);
+    (void)hipEventDestroy(ev[0]);
+    (void)hipEventDestroy(ev[1]);
+    if (rc != PG_OK) {
+        if (rc == PG_ERR_NOMEM) pg::set_error("pg_index_refresh: device allocation failed (%llu rows x %u)", (unsigned long long)ix->rows, ix->dim);
+        pg::free_all(owned);
+        return rc;                           // (the index as it was: stale and valid)
+    }
+    // install as pg_index_attach replaces an index: the table exclusively (no generation bump), the device drained so that no
+    // enqueued index plan reads the old arrays, then the exchange.  A write between the two locks leaves the index stale again.
+    tr.unlock();
+    uint32_t* const old_perm = ix->d_perm;
+    void* const old_small = ix->d_small;
+    {
+        std::unique_lock<std::shared_mutex> w(t->rw);
+        if (hipDeviceSynchronize() != hipSuccess) {
+            pg::set_error("pg_index_refresh: %s", hipGetErrorString(hipGetLastError()));
+            pg::free_all(owned);
+            return PG_ERR_DEVICE;
+        }
+        const uint32_t nl = ix->n_lists;
+        const size_t off_b = ((size_t)(nl + 1) * 4 + 255) & ~(size_t)255, cent_b = (size_t)nl * ix->dim * 4, lists_b = ((size_t)nl * 4 + 255) & ~(size_t)255;
+        ix->d_perm = o.perm;
+        ix->d_small = o.small;
+        ix->d_off = (uint32_t*)ix->d_small;
+        ix->d_cent = (float*)((char*)ix->d_small + off_b);
+        ix->d_cnorm = (float*)((char*)ix->d_cent + cent_b);
+        ix->d_rad = (float*)((char*)ix->d_cnorm + lists_b);
+        ix->gen = gen;
+        ix->nonfinite = o.nonfinite;
+        {
+            std::lock_guard<std::mutex> gw(ix->where_mu);       // (the cached filters' keys carry the old generation)
+            ix->where_cache.clear();
+            ix->where_st.entries = 0;
+            ix->where_st.bytes = 0;
+        }
+        std::lock_guard<std::mutex> gs(ix->mu);
+        ix->st.generation = gen;
+        pg::list_summary(o.rad, o.off, &ix->st);
+        pg_index_refresh_stats_t& r = ix->rst;
+        r.refreshes++;
+        (incremental ? r.incremental : r.full)++;
+        r.rows_reassigned += o.reassigned;
+        r.rows_moved += o.moved;
+        r.rows_confirmed_wide += o.wide;
+        r.last_generation = gen;
+        r.last_assign_ms = o.assign_ms;
+        r.last_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    (void)hipFree(old_perm);
+    (void)hipFree(old_small);
+    return PG_OK;
+}
+
+int pg_index_refresh_stats(const pg_index* ixc, pg_index_refresh_stats_t* out) {
+    PG_REQUIRE(ixc && out, "pg_index_refresh_stats: NULL argument");
+    pg_index* ix = const_cast<pg_index*>(ixc);
+    std::lock_guard<std::mutex> g(ix->mu);
+    *out = ix->rst;
+    return PG_OK;
+}
+
 int pg_index_destroy(pg_ctx* ctx, pg_index* ix) {
     PG_REQUIRE(ctx, "pg_index_destroy: ctx is NULL");
     if (!ix) return PG_OK;
@@ -1426,6 +1728,7 @@ int pg_index_stats(const pg_index* ixc, pg_index_stats_t* out) {
 int pg_index_read(pg_ctx* ctx, const pg_index* ix, uint32_t* offsets, uint32_t* perm, float* centroids, float* cnorm, float* radius) {
     PG_REQUIRE(ctx && ix, "pg_index_read: NULL argument");
     std::lock_guard<std::mutex> g(ctx->mu);
+    pg::TableRead tr(ix->t->rw);             // (pg_index_refresh exchanges the arrays under the exclusive lock)
     hipStream_t s = ctx->stream;
     const size_t nl = ix->n_lists;
     if (offsets) PG_HIP(hipMemcpyAsync(offsets, ix->d_off, (nl + 1) * 4, hipMemcpyDeviceToHost, s));
@@ -1441,6 +1744,7 @@ int pg_index_bounds(pg_ctx* ctx, const pg_index* ix, const float* queries, uint3
     PG_REQUIRE(ctx && ix && queries && out, "pg_index_bounds: NULL argument");
     PG_REQUIRE(nq >= 1 && nq <= (uint32_t)pg::kMaxQueries, "pg_index_bounds: nq=%u must be in [1,%d]", nq, pg::kMaxQueries);
     std::lock_guard<std::mutex> g(ctx->mu);
+    pg::TableRead tr(ix->t->rw);
     hipStream_t s = ctx->stream;
     const size_t qb = (size_t)nq * ix->dim * 4;
     void* buf;

@@ -251,9 +251,10 @@ int pg_table_upload(pg_ctx* ctx, pg_table* t, uint64_t row0, uint64_t nrows, con
                (unsigned long long)row0, (unsigned long long)(row0 + nrows), (unsigned long long)t->rows);
     std::lock_guard<std::mutex> g(ctx->mu);
     if (nrows == 0) return PG_OK;
-    pg::TableWrite w(t);                             // no enqueue reads the table's pointers meanwhile (rows of a table that is
+    pg::TableWrite w(t, nullptr, true);              // no enqueue reads the table's pointers meanwhile (rows of a table that is
                                                      // being served change under batches already in flight: load into a
                                                      // second table and pg_table_swap for an atomic change-over)
+    pg::table_log_add(t, row0, nrows, ctx->knobs.index_refresh_full_fraction);
     PG_HIP(hipMemcpyAsync(t->d + row0 * t->dim, host_rows, nrows * (size_t)t->dim * sizeof(float),
                           hipMemcpyHostToDevice, ctx->stream));
     PG_HIP(hipStreamSynchronize(ctx->stream));

@@ -342,6 +342,20 @@ class Index:
         _lib.check(self.ctx.L.pg_index_where_stats(self.h, C.byref(st)))
         return {name: getattr(st, name) for name, _ in st._fields_}
 
+    def refresh(self, mode: str = "auto", force: bool = False, ctx: Context = None):
+        """Bring the index back to the table's current rows, keeping its centroids (pg_index_refresh): "incremental" re-assigns
+        the rows the table's write log holds, "full" every row (on the matrix pipe), "auto" picks; a current index is left
+        alone unless force.  Results stay bit for bit the table's."""
+        p = _lib.PgIndexRefreshParams({"auto": 0, "full": 1, "incremental": 2}[mode], int(force))
+        _lib.check(self.ctx.L.pg_index_refresh((ctx or self.ctx).h, self.h, C.byref(p)))
+
+    def refresh_stats(self) -> dict:
+        """refreshes by kind, rows re-assigned / moved / sent to the fp32 kernel, the generation described, the last refresh's
+        wall and assignment times (pg_index_refresh_stats)"""
+        st = _lib.PgIndexRefreshStats()
+        _lib.check(self.ctx.L.pg_index_refresh_stats(self.h, C.byref(st)))
+        return {name: getattr(st, name) for name, _ in st._fields_}
+
     def attach(self, ctx: Context = None):
         """Route every recall job of the table (plain recalls, coalescer batches, recommend pipelines) through this index first
         (pg_index_attach); a second attached index replaces the first."""
@@ -361,6 +375,18 @@ class Index:
         if self.h:
             _lib.check(self.ctx.L.pg_index_destroy(self.ctx.h, self.h))
             self.h = None
+
+
+def index_screen_probe(ctx: Context, rows: np.ndarray, centroids: np.ndarray):
+    """the matrix-pipe screen of Index.refresh's full mode on host rows and centroids (pg_index_screen_probe)
+    → (s [n][n_lists] the screen's distances, e [n][n_lists] its bound; +inf outside the range the bound is claimed for)"""
+    rows = np.ascontiguousarray(rows, dtype=np.float32)
+    cent = np.ascontiguousarray(centroids, dtype=np.float32).reshape(-1, rows.shape[1])
+    s = np.empty((rows.shape[0], cent.shape[0]), np.float32)
+    e = np.empty_like(s)
+    _lib.check(ctx.L.pg_index_screen_probe(ctx.h, rows.shape[1], _ptr(rows), rows.shape[0], _ptr(cent), cent.shape[0], _ptr(s),
+                                           _ptr(e)))
+    return s, e
 
 
 def pack_dnn3(w1, b1, w2, b2, w3, b3, d_user: int) -> bytes:

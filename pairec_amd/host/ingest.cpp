@@ -12,7 +12,9 @@
 //                built, pg_table_swap exchanges the two tables (exclusive against every enqueue, device drained) and the
 //                dictionaries change over in the same critical section of the engine's version lock, which every
 //                request holds shared from its first plug-in call to its last label lookup: a request sees ONE
-//                generation of rows and ids.
+//                generation of rows and ids.  A pg_index over the live table is stale after the commit (its recalls take
+//                the table's pass): the caller brings it to the new rows with pg_index_refresh, from any context, after
+//                commit() has returned and while requests go on (include/pairec_gpu.h).
 #include <algorithm>
 #include <atomic>
 #include <cstdio>
