@@ -31,6 +31,7 @@ typedef struct pg_ctx pg_ctx;
 typedef struct pg_table pg_table;      /* HBM-resident embedding table  (module.VectorDao backend) */
 typedef struct pg_model pg_model;      /* rank model weights            (algorithm/eas model)      */
 typedef struct pg_expr pg_expr;        /* compiled RankScore expression (utils/ast)                */
+typedef struct pg_where pg_where;      /* compiled compound WhereClause (HologresVectorConf.WhereClause) */
 
 typedef enum {
     PG_OK = 0,
@@ -511,6 +512,67 @@ typedef struct {
     uint64_t entries, bytes;            /* the entries the cache holds and their device bytes */
 } pg_index_where_stats_t;
 int pg_index_where_stats(const pg_index* ix, pg_index_where_stats_t* out);
+
+/* ---- compound WhereClauses ----------------------------------------------------------
+ * The clauses deployments write in HologresVectorConf.WhereClause are conjunctions ("status = 1 AND create_time > ${time}",
+ * "cat_id IN (3, 7, 12) AND stock > 0"); pg_where serves them everywhere the single `column OP constant` is served.
+ *   Grammar   expr  := and ( OR and )*          and := unary ( AND unary )*        unary := NOT unary | '(' expr ')' | term
+ *             term  := column OP integer        OP: > >= < <= = == != <>
+ *                    | column [NOT] IN '(' integer ( ',' integer )* ')'
+ *                    | column [NOT] BETWEEN integer AND integer          (both bounds inclusive, as SQL)
+ *             Keywords in any case; columns [A-Za-z_][A-Za-z0-9_]*; integers signed decimal that fit long long (the caller
+ *             substitutes "${time}" before compiling).  Columns compare as long long, the logic is two-valued (no NULL).
+ *   Limits    16 distinct columns, 64 terms, 1024 IN constants in total (as written), 64 levels of '(' and NOT nesting.
+ *   compile   parses only and needs no GPU; column names are kept and resolved against a feature store at each use.  NULL
+ *             arguments are PG_ERR_INVALID; everything else that is refused — strings, floats, functions, arithmetic, trailing
+ *             text, an integer that overflows, a limit exceeded, hostile nesting — is PG_ERR_PARSE with pg_last_error() naming
+ *             the 0-based byte position ("... at position N").
+ *   columns   pg_where_num_columns / _column_name: the distinct columns in order of first appearance (NULL out of range).
+ *   eval_host evaluates the compiled program on host arrays — cols[i] / dtypes[i] (PG_F_I32 or PG_F_I64) belong to column i
+ *             of pg_where_column_name — into out_bits[(rows + 31) / 32]: bit r & 31 of word r >> 5 is set when row r passes,
+ *             bits beyond `rows` are zero.  It states what the device kernel reproduces word for word.
+ *   Binding   a call that takes a pg_where resolves its columns by name in `fs`: a column the store lacks, one that is not
+ *             int32 / int64 or has no values, and a store of fewer rows than the table are PG_ERR_INVALID.  This is the one
+ *             error code that differs from the calls the _ex calls extend, which answer a float or value-less column with
+ *             PG_ERR_UNSUPPORTED; it holds for a one-comparison clause too (its search, not its binding, is today's path).
+ *   Bitmap    a clause of more than one plain comparison is evaluated on the device into a bitmap of rows / 8 bytes (one kernel,
+ *             every referenced column read once) that the pg_where keeps: its key is the store, the version of every referenced
+ *             column (pg_features_set_column makes a new one), the row count and the device, so a changed column rebuilds it on
+ *             the next use.  One bitmap is kept; contexts and threads may share a pg_where (builds are serialised), and a
+ *             rebuild never frees a bitmap under a search that still reads it.  A clause that IS one plain comparison
+ *             ("stock > 0", also negated or parenthesised) takes pg_recall_topk_where's path unchanged and builds nothing.
+ *   _ex calls pg_recall_topk_where_ex, pg_index_recall_topk_where_ex and pg_table_view_create_ex are pg_recall_topk_where,
+ *             pg_index_recall_topk_where and pg_table_view_create with the clause in place of (column, op, value): the same
+ *             argument checks in the same order, error codes (but for Binding's), padding, out_count, "index_route_where"
+ *             routing, fallbacks and counters.  The index keeps a compound clause's filtered lists under the pg_where's identity and its bitmap's epoch
+ *             beside the index generation; "index_where_cache" governs eviction as before.
+ *   bits      a diagnostic: the device's bitmap for `rows` rows of `fs` (built, or from the cache; a plain comparison too)
+ *             into out_bits[(rows + 31) / 32] and the rows it admits; either output may be NULL.  `rows` is the caller's
+ *             (at most the store's) and part of the kept bitmap's key: asking for another row count than the table's replaces
+ *             the bitmap the recalls use, and their next call rebuilds it.
+ *   stats     bitmap builds and cache hits, the last build's device milliseconds, the device bytes held (program + bitmap), the
+ *             kept bitmap's epoch and the rows it admits.
+ * pg_where_free must not run while a call uses the clause. */
+int pg_where_compile(const char* clause, pg_where** out);
+int pg_where_free(pg_where* w);
+int pg_where_num_columns(const pg_where* w);
+const char* pg_where_column_name(const pg_where* w, int i);
+int pg_where_eval_host(const pg_where* w, const void* const* cols, const int* dtypes, uint64_t rows, uint32_t* out_bits);
+int pg_recall_topk_where_ex(pg_ctx* ctx, const pg_table* t, const pg_features* fs, const pg_where* w, int metric,
+                            const float* queries, uint32_t nq, uint32_t k, uint64_t* out_rows, float* out_scores,
+                            uint32_t* out_count);
+int pg_index_recall_topk_where_ex(pg_ctx* ctx, const pg_index* ix, const pg_features* fs, const pg_where* w, int metric,
+                                  const float* queries, uint32_t nq, uint32_t k, uint64_t* out_rows, float* out_scores,
+                                  uint32_t* out_count);
+int pg_table_view_create_ex(pg_ctx* ctx, const pg_table* t, const pg_features* fs, const pg_where* w, pg_table** out_view);
+int pg_where_bits(pg_ctx* ctx, const pg_where* w, const pg_features* fs, uint64_t rows, uint32_t* out_bits, uint64_t* out_admitted);
+typedef struct {
+    uint64_t builds, hits;              /* bitmap builds, and uses that found the kept bitmap current */
+    double   last_build_ms;             /* the last build's kernel, device time */
+    uint64_t bytes;                     /* device bytes the kept bitmap and its program hold */
+    uint64_t epoch, admitted;           /* the kept bitmap's epoch (process-wide, never reused) and the rows it admits */
+} pg_where_stats_t;
+int pg_where_stats(const pg_where* w, pg_where_stats_t* out);
 
 /* Refresh: bring an existing index back to its table's current rows KEEPING ITS CENTROIDS — cheap when few
  * rows were written, several times cheaper than pg_index_build when all of them were (nothing is trained).  Nothing changes

@@ -42,6 +42,8 @@ EXPORTS = [
     "pg_index_recall_topk_l2_dev", "pg_index_stats", "pg_index_attach", "pg_index_detach", "pg_index_serving_stats",
     "pg_index_read", "pg_index_bounds", "pg_index_recall_topk_where", "pg_index_where_read", "pg_index_where_stats",
     "pg_index_refresh", "pg_index_refresh_stats", "pg_index_screen_probe",
+    "pg_where_compile", "pg_where_free", "pg_where_num_columns", "pg_where_column_name", "pg_where_eval_host",
+    "pg_recall_topk_where_ex", "pg_index_recall_topk_where_ex", "pg_table_view_create_ex", "pg_where_bits", "pg_where_stats",
 ]
 
 
@@ -54,6 +56,11 @@ class PgStats(C.Structure):
                 ("recall_suspects", C.c_uint64), ("recall_suspect_queries", C.c_uint64), ("recall_i4m_pairs", C.c_uint64),
                 ("recall_screen_overflows", C.c_uint64), ("recall_record_growths", C.c_uint64),
                 ("recall_rescored", C.c_uint64), ("sort_split_calls", C.c_uint64)]
+
+
+class PgWhereStats(C.Structure):
+    _fields_ = [("builds", C.c_uint64), ("hits", C.c_uint64), ("last_build_ms", C.c_double), ("bytes", C.c_uint64),
+                ("epoch", C.c_uint64), ("admitted", C.c_uint64)]
 
 
 class PgIndexParams(C.Structure):
@@ -179,6 +186,15 @@ def load():
         "pg_index_recall_topk_where": [vp, vp, vp, i32, i32, C.c_longlong, i32, vp, u32, u32, vp, vp, vp],
         "pg_index_where_read": [vp, vp, vp, i32, i32, C.c_longlong, vp, vp, vp],
         "pg_index_where_stats": [vp, P(PgIndexWhereStats)],
+        "pg_where_compile": [C.c_char_p, P(vp)],
+        "pg_where_free": [vp],
+        "pg_where_num_columns": [vp],
+        "pg_where_eval_host": [vp, P(vp), P(i32), C.c_uint64, vp],
+        "pg_recall_topk_where_ex": [vp, vp, vp, vp, i32, vp, u32, u32, vp, vp, vp],
+        "pg_index_recall_topk_where_ex": [vp, vp, vp, vp, i32, vp, u32, u32, vp, vp, vp],
+        "pg_table_view_create_ex": [vp, vp, vp, vp, P(vp)],
+        "pg_where_bits": [vp, vp, vp, C.c_uint64, vp, P(C.c_uint64)],
+        "pg_where_stats": [vp, P(PgWhereStats)],
         "pg_index_refresh": [vp, vp, P(PgIndexRefreshParams)],
         "pg_index_refresh_stats": [vp, P(PgIndexRefreshStats)],
         "pg_index_screen_probe": [vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, vp, vp],
@@ -294,6 +310,8 @@ def load():
     L.pg_group_table.restype = vp
     L.pg_expr_var_name.argtypes = [vp, i32]
     L.pg_expr_var_name.restype = C.c_char_p
+    L.pg_where_column_name.argtypes = [vp, i32]
+    L.pg_where_column_name.restype = C.c_char_p
     _lib = L
     return L
 

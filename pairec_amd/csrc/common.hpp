@@ -369,15 +369,19 @@ constexpr uint32_t kIndexStatAt = 260;      // an index plan's words in a job's 
 // reference, hologres_vector_recall.go:49-62, in the one shape the device serves: `column OP constant`).  Rows that fail it
 // never become candidates — it is applied where candidates are made (exact re-scoring, the exact scan's hit path), so every
 // threshold the plans derive is a threshold of the FILTERED top-K and the answers stay exact.
+// Its second form serves a compound clause (pg_where, where.hip): dtype = kFilterBits and col the clause's row
+// bitmap (bit r & 31 of word r >> 5: row r passes), built once per version of the clause's columns; op and val are unused.
+constexpr int kFilterBits = 100;
 struct RowFilter {
-    const void* col = nullptr;   // [rows] int32 / int64 device column; nullptr = no filter
-    int dtype = 0;               // PG_F_I32 or PG_F_I64
+    const void* col = nullptr;   // [rows] int32 / int64 device column, or the bitmap; nullptr = no filter
+    int dtype = 0;               // PG_F_I32, PG_F_I64 or kFilterBits
     int op = 0;                  // pg_where_op: 0 >, 1 >=, 2 <, 3 <=, 4 ==, 5 !=
     long long val = 0;
     long long admitted = -1;     // host side: rows the filter admits when the caller has counted them already (-1: not yet)
 };
 __host__ __device__ inline bool row_filter_pass(const RowFilter& f, uint32_t row) {
     if (!f.col) return true;
+    if (f.dtype == kFilterBits) return (reinterpret_cast<const uint32_t*>(f.col)[row >> 5] >> (row & 31u)) & 1u;
     const long long v = f.dtype == 2 ? reinterpret_cast<const long long*>(f.col)[row] : (long long)reinterpret_cast<const int32_t*>(f.col)[row];
     switch (f.op) {
         case 0: return v > f.val;
@@ -472,14 +476,25 @@ int index_plan_check(RecallJob* j, bool* ok);
 // table's shared lock; device queries and outputs, host counts [nq] or NULL); where_pad_launch: an answer of no admitted row.
 int where_check(const char* who, const pg_ctx* ctx, const pg_table* t, const pg_features* fs, int column, int op, long long value,
                 int metric, const void* queries, const void* rows, const void* scores, uint32_t nq, uint32_t k, RowFilter* f);
+// what a filter is to the caches that key on it (the index's filtered lists): a column of a store, or a compound clause and the
+// epoch of its bitmap (where.hip: process-wide, never reused)
+struct WhereId {
+    const pg_features* fs = nullptr;
+    int column = -1;
+    const pg_where* w = nullptr;
+    uint64_t epoch = 0;
+};
+// recall.hip: pg_table_view_create behind its checks (caller holds ctx->mu and the table's shared lock; synchronises)
+int view_create_locked(const char* who, pg_ctx* ctx, const pg_table* t, const RowFilter& f, pg_table** out_view);
 int recall_where_locked(pg_ctx* ctx, const pg_table* t, RowFilter f, int metric, const float* d_q, uint32_t nq, uint32_t k,
                         uint64_t* d_rows, float* d_sc, uint32_t* out_count);
 int where_pad_launch(pg_ctx* ctx, uint64_t* d_rows, float* d_sc, size_t n, bool l2);
 // index.hip: the attached index pg_recall_topk_where searches ("index_route_where" set and the index current), or NULL; the
 // filtered search itself (a stale, non-finite, dense or overflowing batch: recall_where_locked)
 pg_index* index_route_where(const pg_ctx* ctx, const pg_table* t);
-int index_where_locked(pg_ctx* ctx, pg_index* ix, const pg_features* fs, int column, const RowFilter& f, bool l2, const float* d_q,
+int index_where_locked(pg_ctx* ctx, pg_index* ix, const WhereId& id, const RowFilter& f, bool l2, const float* d_q,
                        uint32_t nq, uint32_t k, uint64_t* d_rows, float* d_sc, uint32_t* h_counts);
+const pg_table* index_table(const pg_index* ix);
 // index_assign.hip: the matrix-pipe assignment of pg_index_refresh's full path (dim 64 / 128).  The split bf16
 // screen over all lists with the survivors confirmed by the rule's chain: out[r] = the rule's list of row r, except for the
 // rows the screen could not settle (more survivors than slots, a row outside the range the bound is proven for), whose ids are

@@ -53,8 +53,13 @@ struct WhereKey {
     int op;
     long long value;
     uint64_t gen;                        // the index's table generation
+    // a compound clause: its identity and its bitmap's epoch (column -1; version, op and value 0) — a bitmap
+    // rebuilt after a column changed has a new epoch, and no two builds in a process share one
+    const pg_where* w;
+    uint64_t epoch;
     bool operator==(const WhereKey& o) const {
-        return fs == o.fs && column == o.column && version == o.version && op == o.op && value == o.value && gen == o.gen;
+        return fs == o.fs && column == o.column && version == o.version && op == o.op && value == o.value && gen == o.gen && w == o.w &&
+               epoch == o.epoch;
     }
 };
 struct WhereLists {
@@ -1221,16 +1226,18 @@ int where_lists_build(pg_ctx* ctx, const pg_index* ix, const RowFilter& f, std::
         return rc;
     };
     int rc;
-    uint32_t *bits, *cnt, *off;
+    uint32_t *bits = nullptr, *cnt, *off;
     const size_t words = (size_t)((rows + 31) / 32);
-    if ((rc = dalloc((void**)&bits, words * 4, temp)) || (rc = dalloc((void**)&cnt, ((size_t)nl + 1) * 4, temp)) ||
+    const bool have_bits = f.dtype == kFilterBits;       // (a compound clause's filter IS the bitmap in row order)
+    if ((!have_bits && (rc = dalloc((void**)&bits, words * 4, temp))) || (rc = dalloc((void**)&cnt, ((size_t)nl + 1) * 4, temp)) ||
         (rc = dalloc((void**)&off, ((size_t)nl + 1) * 4, temp)))
         return done(rc);
     size_t scan_b = 0;
     void* scan_tmp;
     if (hipcub::DeviceScan::ExclusiveSum(nullptr, scan_b, cnt, off, nl + 1, s) != hipSuccess) return done(PG_ERR_DEVICE);
     if ((rc = dalloc(&scan_tmp, scan_b, temp))) return done(rc);
-    where_bits_kernel<<<(uint32_t)((rows + 255) / 256), 256, 0, s>>>(f, rows, bits);
+    if (have_bits) bits = const_cast<uint32_t*>(reinterpret_cast<const uint32_t*>(f.col));
+    else where_bits_kernel<<<(uint32_t)((rows + 255) / 256), 256, 0, s>>>(f, rows, bits);
     if (hipMemsetAsync(cnt + nl, 0, 4, s) != hipSuccess) return done(PG_ERR_DEVICE);
     where_lists_kernel<true><<<nl, 256, 0, s>>>(ix->d_perm, ix->d_off, bits, cnt, nullptr);
     if (hipGetLastError() != hipSuccess || hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_b, cnt, off, nl + 1, s) != hipSuccess)
@@ -1259,8 +1266,9 @@ int where_lists_build(pg_ctx* ctx, const pg_index* ix, const RowFilter& f, std::
 
 // the filter's lists from the index's cache, or built (and kept while "index_where_cache" of the calling context allows); caller
 // holds ctx->mu and the table's shared lock
-int where_lists_get(pg_ctx* ctx, pg_index* ix, const pg_features* fs, int column, const RowFilter& f, std::shared_ptr<WhereLists>* out) {
-    const WhereKey key{fs, column, fs->cols[(size_t)column].version, f.op, f.val, ix->gen};
+int where_lists_get(pg_ctx* ctx, pg_index* ix, const WhereId& id, const RowFilter& f, std::shared_ptr<WhereLists>* out) {
+    const WhereKey key = id.w ? WhereKey{id.fs, -1, 0, 0, 0, ix->gen, id.w, id.epoch}
+                              : WhereKey{id.fs, id.column, id.fs->cols[(size_t)id.column].version, f.op, f.val, ix->gen, nullptr, 0};
     std::lock_guard<std::mutex> g(ix->where_mu);
     pg_index_where_stats_t& st = ix->where_st;
     const uint32_t cap = ctx->knobs.index_where_cache;
@@ -1298,6 +1306,8 @@ int where_lists_get(pg_ctx* ctx, pg_index* ix, const pg_features* fs, int column
 
 }  // namespace
 
+const pg_table* index_table(const pg_index* ix) { return ix->t; }
+
 pg_index* index_route_where(const pg_ctx* ctx, const pg_table* t) {
     if (!ctx->knobs.index_route_where || t->d_row_map) return nullptr;
     pg_index* ix = t->index.load(std::memory_order_acquire);
@@ -1306,7 +1316,7 @@ pg_index* index_route_where(const pg_ctx* ctx, const pg_table* t) {
 
 // one filtered batch, synchronously (caller holds ctx->mu and the table's shared lock); h_counts: host [nq].  The search of
 // index_recall_locked over the filter's lists; a stale, non-finite, dense or overflowing batch is answered by the filtered pass.
-int index_where_locked(pg_ctx* ctx, pg_index* ix, const pg_features* fs, int column, const RowFilter& f, bool l2, const float* d_q,
+int index_where_locked(pg_ctx* ctx, pg_index* ix, const WhereId& id, const RowFilter& f, bool l2, const float* d_q,
                        uint32_t nq, uint32_t k, uint64_t* d_rows, float* d_sc, uint32_t* h_counts) {
     const pg_table* t = ix->t;
     const uint32_t dim = t->dim;
@@ -1319,7 +1329,7 @@ int index_where_locked(pg_ctx* ctx, pg_index* ix, const pg_features* fs, int col
     else if (l2 && dim != 64 && dim != 128) fb = &pg_index_stats_t::fallback_dense;   // (the filtered pass answers with its own error)
     else rc = [&]() -> int {
         int rc2;
-        if ((rc2 = where_lists_get(ctx, ix, fs, column, f, &wl))) return rc2;
+        if ((rc2 = where_lists_get(ctx, ix, id, f, &wl))) return rc2;
         if (wl->admitted == 0) {
             // nothing passes: padding, every count 0 (as pg_recall_topk_where)
             if ((rc2 = where_pad_launch(ctx, d_rows, d_sc, (size_t)nq * k, l2))) return rc2;
@@ -1659,7 +1669,7 @@ int pg_index_recall_topk_where(pg_ctx* ctx, const pg_index* ixc, const pg_featur
     pg::TableRead tr(ix->t->rw);
     uint32_t counts[pg::kMaxQueries];
     auto run = [&](const float* d_q, uint64_t* d_rows, float* d_sc) {
-        return pg::index_where_locked(ctx, ix, fs, column, f, metric == 1, d_q, nq, k, d_rows, d_sc, counts);
+        return pg::index_where_locked(ctx, ix, pg::WhereId{fs, column, nullptr, 0}, f, metric == 1, d_q, nq, k, d_rows, d_sc, counts);
     };
     if ((rc = pg::recall_staged(ctx, ix->dim, queries, nq, k, out_rows, out_scores, run))) return rc;
     if (out_count) memcpy(out_count, counts, (size_t)nq * 4);
@@ -1688,7 +1698,7 @@ int pg_index_where_read(pg_ctx* ctx, const pg_index* ixc, const pg_features* fs,
     pg::TableRead tr(ix->t->rw);
     std::shared_ptr<pg::WhereLists> wl;
     int rc;
-    if ((rc = pg::where_lists_get(ctx, ix, fs, column, f, &wl))) return rc;
+    if ((rc = pg::where_lists_get(ctx, ix, pg::WhereId{fs, column, nullptr, 0}, f, &wl))) return rc;
     hipStream_t s = ctx->stream;
     if (offsets) PG_HIP(hipMemcpyAsync(offsets, wl->off, ((size_t)ix->n_lists + 1) * 4, hipMemcpyDeviceToHost, s));
     if (perm && wl->admitted) PG_HIP(hipMemcpyAsync(perm, wl->perm, (size_t)wl->admitted * 4, hipMemcpyDeviceToHost, s));

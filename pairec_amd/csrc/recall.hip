@@ -2414,9 +2414,10 @@ __device__ __forceinline__ bool filter_cmp(int op, long long v, long long val) {
         default: return v != val;
     }
 }
-// bit i: row r0 + i passes (r0 a multiple of 4: one 16-B load of an int32 column, two of an int64 one)
+// bit i: row r0 + i passes (r0 a multiple of 4: one 16-B load of an int32 column, two of an int64 one, four bits of a bitmap)
 __device__ __forceinline__ uint32_t row_filter_mask4(const RowFilter& f, uint64_t r0, uint64_t rows) {
     uint32_t m = 0;
+    if (f.dtype == kFilterBits) return (reinterpret_cast<const uint32_t*>(f.col)[r0 >> 5] >> (uint32_t)(r0 & 31u)) & 0xFu;   // (zero bits beyond the rows)
     if (r0 + 4 <= rows) {
         if (f.dtype == PG_F_I64) {
             const longlong2 a = reinterpret_cast<const longlong2*>(reinterpret_cast<const long long*>(f.col) + r0)[0];
@@ -3602,6 +3603,39 @@ int recall_where_locked(pg_ctx* ctx, const pg_table* t, RowFilter f, int metric,
     return PG_OK;
 }
 
+int view_create_locked(const char* who, pg_ctx* ctx, const pg_table* t, const RowFilter& f, pg_table** out_view) {
+    PG_HIP(hipSetDevice(ctx->device));
+    int rc;
+    uint32_t *d_blk, *d_grp, cblocks, admitted;
+    if ((rc = filter_count_locked(ctx, f, t->rows, &d_blk, &d_grp, &cblocks, &admitted))) return rc;
+    if (admitted == 0) {
+        set_error("%s: no row passes the filter", who);
+        return PG_ERR_EMPTY;
+    }
+    pg_table* v = new pg_table();
+    v->rows = admitted;
+    v->dim = t->dim;
+    v->row_offset = 0;
+    v->map_offset = t->row_offset;
+    hipError_t e = hipMalloc((void**)&v->d, ((size_t)admitted + 64) * t->dim * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&v->d_row_map, ((size_t)admitted + 64) * sizeof(uint32_t));
+    if (e != hipSuccess) {
+        set_error("%s: hipMalloc(%.1f GB) failed: %s", who, (double)admitted * t->dim * 4 / 1e9, hipGetErrorString(e));
+        if (v->d) (void)hipFree(v->d);
+        delete v;
+        return PG_ERR_NOMEM;
+    }
+    filter_scatter_kernel<<<cblocks, 256, 0, ctx->stream>>>(f, t->rows, d_blk, d_grp, v->d_row_map);
+    const uint64_t quads = (uint64_t)admitted * (t->dim / 4);
+    compact_gather_kernel<<<(uint32_t)((quads + 255) / 256), 256, 0, ctx->stream>>>(t->d, v->d_row_map, admitted, t->dim, v->d);
+    PG_HIP(hipGetLastError());
+    PG_HIP(hipMemsetAsync(v->d + (size_t)admitted * t->dim, 0, (size_t)64 * t->dim * sizeof(float), ctx->stream));
+    PG_HIP(hipMemsetAsync(v->d_row_map + admitted, 0, 64 * sizeof(uint32_t), ctx->stream));
+    PG_HIP(hipStreamSynchronize(ctx->stream));
+    *out_view = v;
+    return PG_OK;
+}
+
 }  // namespace pg
 
 extern "C" {
@@ -3659,7 +3693,7 @@ int pg_recall_topk_where(pg_ctx* ctx, const pg_table* t, const pg_features* fs, 
     pg_index* ix = pg::index_route_where(ctx, t);          // ("index_route_where": the attached index, when it is current)
     uint32_t counts[pg::kMaxQueries];
     auto run = [&](const float* d_q, uint64_t* d_rows, float* d_sc) {
-        return ix ? pg::index_where_locked(ctx, ix, fs, column, f, metric == 1, d_q, nq, k, d_rows, d_sc, counts)
+        return ix ? pg::index_where_locked(ctx, ix, pg::WhereId{fs, column, nullptr, 0}, f, metric == 1, d_q, nq, k, d_rows, d_sc, counts)
                   : pg::recall_where_locked(ctx, t, f, metric, d_q, nq, k, d_rows, d_sc, counts);
     };
     if ((rc = pg::recall_staged(ctx, t->dim, queries, nq, k, out_rows, out_scores, run))) return rc;
@@ -3692,36 +3726,7 @@ int pg_table_view_create(pg_ctx* ctx, const pg_table* t, const pg_features* fs, 
     f.val = value;
     std::lock_guard<std::mutex> g(ctx->mu);
     pg::TableRead tr(t->rw);
-    PG_HIP(hipSetDevice(ctx->device));
-    int rc;
-    uint32_t *d_blk, *d_grp, cblocks, admitted;
-    if ((rc = pg::filter_count_locked(ctx, f, t->rows, &d_blk, &d_grp, &cblocks, &admitted))) return rc;
-    if (admitted == 0) {
-        pg::set_error("pg_table_view_create: no row passes the filter");
-        return PG_ERR_EMPTY;
-    }
-    pg_table* v = new pg_table();
-    v->rows = admitted;
-    v->dim = t->dim;
-    v->row_offset = 0;
-    v->map_offset = t->row_offset;
-    hipError_t e = hipMalloc((void**)&v->d, ((size_t)admitted + 64) * t->dim * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&v->d_row_map, ((size_t)admitted + 64) * sizeof(uint32_t));
-    if (e != hipSuccess) {
-        pg::set_error("pg_table_view_create: hipMalloc(%.1f GB) failed: %s", (double)admitted * t->dim * 4 / 1e9, hipGetErrorString(e));
-        if (v->d) (void)hipFree(v->d);
-        delete v;
-        return PG_ERR_NOMEM;
-    }
-    pg::filter_scatter_kernel<<<cblocks, 256, 0, ctx->stream>>>(f, t->rows, d_blk, d_grp, v->d_row_map);
-    const uint64_t quads = (uint64_t)admitted * (t->dim / 4);
-    pg::compact_gather_kernel<<<(uint32_t)((quads + 255) / 256), 256, 0, ctx->stream>>>(t->d, v->d_row_map, admitted, t->dim, v->d);
-    PG_HIP(hipGetLastError());
-    PG_HIP(hipMemsetAsync(v->d + (size_t)admitted * t->dim, 0, (size_t)64 * t->dim * sizeof(float), ctx->stream));
-    PG_HIP(hipMemsetAsync(v->d_row_map + admitted, 0, 64 * sizeof(uint32_t), ctx->stream));
-    PG_HIP(hipStreamSynchronize(ctx->stream));
-    *out_view = v;
-    return PG_OK;
+    return pg::view_create_locked("pg_table_view_create", ctx, t, f, out_view);
 }
 
 // I2IVectorRecall (service/recall/item_2_item_vector_racall.go:51-152): the trigger item's own embedding

@@ -223,6 +223,21 @@ class Table:
         v.rows = rows.value
         return v
 
+    def recall_topk_where_ex(self, feats: "Features", where: "Where", queries: np.ndarray, k: int, l2: bool = False):
+        """as recall_topk_where with a compiled compound clause (pg_recall_topk_where_ex) → (rows, scores or distances, counts)"""
+        return where._recall(self.ctx, self.ctx.L.pg_recall_topk_where_ex, self.h, self.dim, feats, queries, k, l2)
+
+    def view_where(self, feats: "Features", where: "Where") -> "Table":
+        """as view with a compiled compound clause (pg_table_view_create_ex)"""
+        h = C.c_void_p()
+        _lib.check(self.ctx.L.pg_table_view_create_ex(self.ctx.h, self.h, feats.h, where.h, C.byref(h)))
+        v = Table.__new__(Table)
+        v.ctx, v.dim, v.row_offset, v.h = self.ctx, self.dim, 0, h
+        rows = C.c_uint64()
+        _lib.check(self.ctx.L.pg_table_info(h, C.byref(rows), None, None))
+        v.rows = rows.value
+        return v
+
     def i2i_recall(self, trigger_rows, k: int, trigger_table: Optional["Table"] = None):
         """I2IVectorRecall: rows of `trigger_table` (default: this table) are the queries."""
         tr = np.ascontiguousarray(trigger_rows, dtype=np.uint32)
@@ -322,6 +337,10 @@ class Index:
             _lib.check(self.ctx.L.pg_index_recall_topk_where(self.ctx.h, self.h, feats.h, col, ops[op], int(value), 1 if l2 else 0,
                                                              _ptr(q[s:e]), e - s, k, _ptr(r_), _ptr(s_), _ptr(c_)))
         return rows, scores, counts
+
+    def recall_topk_where_ex(self, feats: "Features", where: "Where", queries: np.ndarray, k: int, l2: bool = False):
+        """as Table.recall_topk_where_ex, through the index over the clause's lists (pg_index_recall_topk_where_ex)"""
+        return where._recall(self.ctx, self.ctx.L.pg_index_recall_topk_where_ex, self.h, self.table.dim, feats, queries, k, l2)
 
     def where_read(self, feats: "Features", column: str, op: str, value: int) -> dict:
         """a filter's lists over the index (pg_index_where_read, built or from the cache): offsets [n_lists + 1] and perm
@@ -558,6 +577,64 @@ def rank_fm2t_rows_host(model: "RankModel", feats: "Features", item_field_names,
     _lib.check(ctx.L.pg_rank_fm2t_rows(ctx.h, model.h, feats.h, _ptr(cols), _ptr(u), _ptr(uf), _ptr(cr), _ptr(ro),
                                        ro.shape[0] - 1, _ptr(out)))
     return out
+
+
+class Where:
+    """A compiled compound WhereClause (pg_where_*): AND / OR / NOT / IN / BETWEEN over the integer columns of a Features store.
+    Compiling needs no GPU; the columns are resolved by name at each use."""
+
+    def __init__(self, clause: str):
+        self.L = _lib.load()
+        h = C.c_void_p()
+        _lib.check(self.L.pg_where_compile(clause.encode("utf-8"), C.byref(h)))
+        self.h = h
+        self.columns = [self.L.pg_where_column_name(h, i).decode("utf-8") for i in range(self.L.pg_where_num_columns(h))]
+
+    def free(self):
+        if self.h:
+            self.L.pg_where_free(self.h)
+            self.h = None
+
+    def eval_host(self, cols: dict, rows: Optional[int] = None) -> np.ndarray:
+        """cols: {column name: int32 or int64 array} → the bitmap [(rows + 31) // 32] uint32 (pg_where_eval_host): bit r & 31 of
+        word r >> 5 is set when row r passes"""
+        arrs = []
+        for n in self.columns:
+            a = np.asarray(cols[n])
+            if a.dtype not in (np.int32, np.int64):
+                raise TypeError("Where.eval_host: column %r is %s, not int32 / int64" % (n, a.dtype))
+            arrs.append(np.ascontiguousarray(a))
+        if rows is None:
+            rows = arrs[0].shape[0]
+        ptrs = (C.c_void_p * max(len(arrs), 1))(*[a.ctypes.data for a in arrs])
+        dts = (C.c_int * max(len(arrs), 1))(*[F_I64 if a.dtype == np.int64 else F_I32 for a in arrs])
+        out = np.zeros((rows + 31) // 32, dtype=np.uint32)
+        _lib.check(self.L.pg_where_eval_host(self.h, ptrs, dts, rows, _ptr(out)))
+        return out
+
+    def bits(self, ctx: "Context", feats: "Features", rows: int):
+        """the device's bitmap for `rows` rows of `feats`, built or from the cache (pg_where_bits) → (bitmap uint32, admitted)"""
+        out = np.zeros((rows + 31) // 32, dtype=np.uint32)
+        n = C.c_uint64()
+        _lib.check(self.L.pg_where_bits(ctx.h, self.h, feats.h, rows, _ptr(out), C.byref(n)))
+        return out, n.value
+
+    def stats(self) -> dict:
+        st = _lib.PgWhereStats()
+        _lib.check(self.L.pg_where_stats(self.h, C.byref(st)))
+        return {name: getattr(st, name) for name, _ in st._fields_}
+
+    def _recall(self, ctx, fn, over, dim: int, feats: "Features", queries: np.ndarray, k: int, l2: bool):
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, dim)
+        nq = q.shape[0]
+        rows = np.empty((nq, k), dtype=np.uint64)
+        scores = np.empty((nq, k), dtype=np.float32)
+        counts = np.zeros(nq, dtype=np.uint32)
+        for s in range(0, nq, MAX_QUERIES):          # batches split as Table.recall_topk_where splits them
+            e = min(nq, s + MAX_QUERIES)
+            r_, s_, c_ = rows[s:e], scores[s:e], counts[s:e]
+            _lib.check(fn(ctx.h, over, feats.h, self.h, 1 if l2 else 0, _ptr(q[s:e]), e - s, k, _ptr(r_), _ptr(s_), _ptr(c_)))
+        return rows, scores, counts
 
 
 class Expr:
