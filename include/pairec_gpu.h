@@ -92,7 +92,9 @@ int pg_synchronize(pg_ctx* ctx);
  * recalls through an index (pg_index_recall_topk_where) "index_where_cache" (default 4 filtered lists kept per index; 0 = built
  * per call and freed after it) and "index_route_where" (default 0; 1: pg_recall_topk_where on a table whose attached index is
  * current searches that index, synchronously); for pg_index_refresh "index_refresh_full_fraction" (default 0.1: in auto mode
- * more written rows than this share of the table are refreshed in full; a table's write log is dropped past it too).
+ * more written rows than this share of the table are refreshed in full; a table's write log is dropped past it too); for
+ * coalescers created afterwards "coalescer_max_exclude" (default 0, 0..4096: the longest list pg_coalescer_recall_exclude takes;
+ * a value outside the range is PG_ERR_INVALID).
  * value is parsed as a number. */
 int pg_set_option(pg_ctx* ctx, const char* name, const char* value);
 int pg_device_malloc(pg_ctx* ctx, size_t bytes, void** out);
@@ -574,6 +576,61 @@ typedef struct {
 } pg_where_stats_t;
 int pg_where_stats(const pg_where* w, pg_where_stats_t* out);
 
+/* Per-request exclusion lists: the items THIS user has already been shown, taken out inside the vector recall.
+ * In the reference that filter is part of the recall: BeVectorRecall.GetItems (service/recall/be_vector_recall.go:63-95) asks its
+ * BeFilterNames for query parameters, and berecall.User2ItemExposureFilter.BuildQueryParams (service/recall/berecall/
+ * user_item_exposure_filter.go:22-33) puts the user's exposure_list into the vector query, so the engine returns returnCount
+ * UNSEEN items.  Deployments without BE run filter/user_item_exposure_filter.go:34-49 (FilterByHistory) behind the recall and
+ * are left with fewer than RecallCount candidates for rank.  Here the answer is exact and full: a recall's answer is totally
+ * ordered (score, then row), so the first k entries outside a list of n ids lie within the first k + n; one ordinary pass at
+ * depth k + (the longest list of the call) holds every request's answer, and one order-preserving compaction on the device cuts
+ * it out.
+ *   Lists     request q excludes excl_rows[excl_offsets[q] .. excl_offsets[q + 1]): GLOBAL row ids as recalls return them
+ *             (row_offset + local row; for a view the source's ids), unsorted, duplicates allowed, at most 4096 per request
+ *             (more: PG_ERR_UNSUPPORTED).  An id that cannot occur in the answer — UINT64_MAX, a row outside the table, a row
+ *             the clause does not admit — matches nothing.  excl_offsets is host memory [nq + 1] in every call but
+ *             pg_exclude_compact_dev; NULL or non-monotone offsets are PG_ERR_INVALID.
+ *   compact   pg_exclude_compact_dev is the kernel alone: d_rows / d_scores [nq][k_in] in a recall's output order (they may end
+ *             in UINT64_MAX padding), lists and offsets on the device; output slot j of request q is its j-th input entry that
+ *             is neither padding nor in its list — relative order and score bits untouched — the slots from the kept count on
+ *             carry UINT64_MAX / pad_score, d_out_count[q] (optional) = min(k_out, kept).  1 <= k_out <= k_in <= 16384 and
+ *             nq <= 256 (else PG_ERR_UNSUPPORTED / PG_ERR_INVALID); at most 4096 ids per request is a PRECONDITION here (the
+ *             offsets are device memory: the caller keeps it; of a longer list the first 4096 ids count).  Outputs must not overlap the inputs.  One launch on the
+ *             context's stream, no synchronisation; an empty list costs a copy of the head.  A sharded host (the shard
+ *             group, dist.py) has no exclude call of its own: it over-asks its merge by the longest list and calls this after
+ *             pg_topk_merge_lists_dev.
+ *   recalls   pg_recall_topk_exclude[_dev] return the exact top-k — order, padding (UINT64_MAX with -inf; +inf for metric 1) and
+ *             argument checks of the call they extend, in its order: pg_recall_topk[_l2][_dev], or with opts->fs / opts->where
+ *             pg_recall_topk_where_ex — over the rows of `t` (the rows the clause admits) that are not in the request's list;
+ *             out_count[q] = min(k, candidates - excluded candidates).  opts = NULL is {0, NULL, NULL}; fs without where or
+ *             where without fs is PG_ERR_INVALID.  The inner recall runs at k + the longest list through the very search the
+ *             plain call uses, so an attached index, "index_route_where", the compact route of a selective clause and views
+ *             serve it unchanged and count it as usual; k + the longest list > 16384 is PG_ERR_UNSUPPORTED.  With every list
+ *             empty the pass runs at k and the outputs are bit for bit the plain call's.  _dev: queries, lists and outputs
+ *             are device memory, offsets and out_count host; both forms return synchronised.
+ *   i2i       pg_i2i_recall_exclude is pg_i2i_recall (its checks, in its order) with lists; exclude_trigger != 0 appends each
+ *             request's own trigger row to its list — the hole pg_i2i_recall documents — and needs trigger_table == t
+ *             (PG_ERR_INVALID otherwise); excl_rows / excl_offsets may then be NULL.  The list with the trigger row holds at
+ *             most 4096 ids.
+ *   coalescer pg_coalescer_recall_exclude, below. */
+typedef struct {
+    int metric;                /* 0 inner product (descending), 1 squared Euclidean (ascending) */
+    const pg_features* fs;     /* with `where`: candidates restricted to the clause's rows; both NULL = every row */
+    const pg_where* where;
+} pg_recall_exclude_opts;
+int pg_exclude_compact_dev(pg_ctx* ctx, const uint64_t* d_rows, const float* d_scores, uint32_t nq, uint32_t k_in,
+                           const uint64_t* d_excl_rows, const uint32_t* d_excl_offsets, uint32_t k_out, float pad_score,
+                           uint64_t* d_out_rows, float* d_out_scores, uint32_t* d_out_count);
+int pg_recall_topk_exclude(pg_ctx* ctx, const pg_table* t, const float* queries, uint32_t nq, uint32_t k,
+                           const uint64_t* excl_rows, const uint32_t* excl_offsets, const pg_recall_exclude_opts* opts,
+                           uint64_t* out_rows, float* out_scores, uint32_t* out_count);
+int pg_recall_topk_exclude_dev(pg_ctx* ctx, const pg_table* t, const float* d_queries, uint32_t nq, uint32_t k,
+                               const uint64_t* d_excl_rows, const uint32_t* excl_offsets, const pg_recall_exclude_opts* opts,
+                               uint64_t* d_out_rows, float* d_out_scores, uint32_t* out_count);
+int pg_i2i_recall_exclude(pg_ctx* ctx, const pg_table* trigger_table, const uint32_t* trigger_rows, uint32_t n, const pg_table* t,
+                          uint32_t k, int exclude_trigger, const uint64_t* excl_rows, const uint32_t* excl_offsets,
+                          uint64_t* out_rows, float* out_scores, uint32_t* out_count);
+
 /* Refresh: bring an existing index back to its table's current rows KEEPING ITS CENTROIDS — cheap when few
  * rows were written, several times cheaper than pg_index_build when all of them were (nothing is trained).  Nothing changes
  * until it is called: a written table still makes its index stale.
@@ -853,6 +910,18 @@ int pg_coalescer_recall(pg_coalescer* c, const float* query, uint64_t* out_rows,
 /* HologresVectorRecallV2 through the coalescer: one request per call, up to 128 share one screened pass (32 one pass of the
  * exact scan, where the table needs that: pg_recall_topk_l2); out_dist ascending. */
 int pg_coalescer_recall_l2(pg_coalescer* c, const float* query, uint64_t* out_rows, float* out_dist, uint32_t* out_count);
+/* pg_recall_topk_exclude for ONE request (BeVectorRecall with the User2ItemExposureFilter, be_vector_recall.go:63-95 /
+ * berecall/user_item_exposure_filter.go:22-33): query [dim] and the n_excl global row ids this user has seen.  Enabled by the
+ * context option "coalescer_max_exclude" (0..4096, default 0), read once when the coalescer is created; with it positive,
+ * k + coalescer_max_exclude > 16384 fails the creation with PG_ERR_UNSUPPORTED, and every slot holds the over-fetched answer
+ * ([max_batch][k + coalescer_max_exclude] rows and scores) and the lists — nothing is allocated without the option.
+ * PG_ERR_UNSUPPORTED when the coalescer was created with 0, when n_excl exceeds the option, and for a group coalescer.  Such
+ * requests wait in a queue of their own (as the squared-Euclidean recalls do); one batch is one recall job at the FIXED depth
+ * k + coalescer_max_exclude — one depth, so the table's per-K threshold model does not alternate — the compaction, and the
+ * usual [nq][k] copy-out; plain batches are untouched.  Counted under flavour 0.  The answer is bit for bit
+ * pg_recall_topk_exclude's for the same request alone. */
+int pg_coalescer_recall_exclude(pg_coalescer* c, const float* query, const uint64_t* excl_rows, uint32_t n_excl,
+                                uint64_t* out_rows, float* out_scores, uint32_t* out_count);
 int pg_coalescer_i2i_recall(pg_coalescer* c, uint32_t trigger_row, uint64_t* out_rows, float* out_scores,
                             uint32_t* out_count);
 /* OnlineVectorRecall.GetCandidateItems for ONE user (pg_online_vector_recall with n_req = 1): user_vec[d_user] goes

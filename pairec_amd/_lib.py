@@ -44,6 +44,8 @@ EXPORTS = [
     "pg_index_refresh", "pg_index_refresh_stats", "pg_index_screen_probe",
     "pg_where_compile", "pg_where_free", "pg_where_num_columns", "pg_where_column_name", "pg_where_eval_host",
     "pg_recall_topk_where_ex", "pg_index_recall_topk_where_ex", "pg_table_view_create_ex", "pg_where_bits", "pg_where_stats",
+    "pg_exclude_compact_dev", "pg_recall_topk_exclude", "pg_recall_topk_exclude_dev", "pg_i2i_recall_exclude",
+    "pg_coalescer_recall_exclude",
 ]
 
 
@@ -85,6 +87,10 @@ class PgIndexServingStats(C.Structure):
 class PgIndexWhereStats(C.Structure):
     _fields_ = [("builds", C.c_uint64), ("hits", C.c_uint64), ("evictions", C.c_uint64), ("entries", C.c_uint64),
                 ("bytes", C.c_uint64)]
+
+
+class PgRecallExcludeOpts(C.Structure):
+    _fields_ = [("metric", C.c_int), ("fs", C.c_void_p), ("where", C.c_void_p)]
 
 
 class PgIndexRefreshParams(C.Structure):
@@ -195,6 +201,11 @@ def load():
         "pg_table_view_create_ex": [vp, vp, vp, vp, P(vp)],
         "pg_where_bits": [vp, vp, vp, C.c_uint64, vp, P(C.c_uint64)],
         "pg_where_stats": [vp, P(PgWhereStats)],
+        "pg_exclude_compact_dev": [vp, vp, vp, u32, u32, vp, vp, u32, C.c_float, vp, vp, vp],
+        "pg_recall_topk_exclude": [vp, vp, vp, u32, u32, vp, vp, P(PgRecallExcludeOpts), vp, vp, vp],
+        "pg_recall_topk_exclude_dev": [vp, vp, vp, u32, u32, vp, vp, P(PgRecallExcludeOpts), vp, vp, vp],
+        "pg_i2i_recall_exclude": [vp, vp, vp, u32, vp, u32, i32, vp, vp, vp, vp, vp],
+        "pg_coalescer_recall_exclude": [vp, vp, vp, u32, vp, vp, P(u32)],
         "pg_index_refresh": [vp, vp, P(PgIndexRefreshParams)],
         "pg_index_refresh_stats": [vp, P(PgIndexRefreshStats)],
         "pg_index_screen_probe": [vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, vp, vp],

@@ -51,6 +51,7 @@ static void knobs_from_env(Knobs* k) {
     k->index_skip_batches = (uint32_t)num("PG_INDEX_SKIP_BATCHES", 64);
     k->index_where_cache = (uint32_t)num("PG_INDEX_WHERE_CACHE", 4);
     k->index_route_where = flag("PG_INDEX_ROUTE_WHERE");
+    k->coalescer_max_exclude = (uint32_t)std::min(std::max(num("PG_COALESCER_MAX_EXCLUDE", 0), 0.0), (double)kMaxExclude);
     k->index_refresh_full_fraction = num("PG_INDEX_REFRESH_FULL_FRACTION", 0.1);
 }
 
@@ -201,6 +202,10 @@ int pg_set_option(pg_ctx* ctx, const char* name, const char* value) {
     else if (n == "index_skip_batches") k.index_skip_batches = v >= 0 ? (uint32_t)v : 0u;
     else if (n == "index_where_cache") k.index_where_cache = v >= 0 ? (uint32_t)v : 0u;
     else if (n == "index_route_where") k.index_route_where = b;
+    else if (n == "coalescer_max_exclude") {
+        PG_REQUIRE(v >= 0 && v <= (double)pg::kMaxExclude, "pg_set_option: coalescer_max_exclude %s outside 0..%u", value, pg::kMaxExclude);
+        k.coalescer_max_exclude = (uint32_t)v;
+    }
     else if (n == "index_refresh_full_fraction") k.index_refresh_full_fraction = v >= 0 ? (v <= 1 ? v : 1.0) : 0.0;
     else {
         pg::set_error("pg_set_option: unknown option \"%s\"", name);

@@ -51,7 +51,7 @@ namespace {
 using Clock = std::chrono::steady_clock;
 
 enum Flavour { kRecall = 0, kRank = 1, kRecommend = 2, kDpp = 3, kSsd = 4 };      // statistics index
-enum Queue { kQRecall = 0, kQRecommend = 1, kQDpp = 2, kQRecallL2 = 3, kQRank0 = 4 };     // kQRank0 + algorithm index
+enum Queue { kQRecall = 0, kQRecommend = 1, kQDpp = 2, kQRecallL2 = 3, kQRecallEx = 4, kQRank0 = 5 };     // kQRecallEx: recalls with an exclusion list; kQRank0 + algorithm index
 constexpr uint32_t kL2Batch = 32;      // squared-Euclidean recalls per pass: the exact scan serves 32 queries at the price of one;
                                        // 128 when the table has an int8 shadow (the screened pass)
 inline uint32_t l2_batch_limit(const pg_coalescer* c);
@@ -82,7 +82,8 @@ struct Req {
     uint32_t qkind = kVector;              // recall: what `vec` / `trigger_row` is
     uint32_t trigger_row = 0;
     const uint32_t* cand = nullptr;        // rank / dpp: candidate rows
-    uint32_t n = 0;                        // rank / dpp: candidates; recommend: top_n
+    uint32_t n = 0;                        // rank / dpp: candidates; recommend: top_n; recall with exclusions: ids in `excl`
+    const uint64_t* excl = nullptr;        // recall with exclusions: the request's list (global row ids)
     const double* hook = nullptr;          // dpp: hook embeddings
     std::vector<double> rel;               // dpp: relevance scores as KernelMatrix uses them (normalised by the caller's thread)
     DppKey key;
@@ -137,6 +138,13 @@ struct Slot {
     double* d_fused = nullptr;
     uint32_t* d_order = nullptr;
     uint32_t* d_count = nullptr;           // [max_batch]
+    // recalls with exclusion lists ("coalescer_max_exclude" > 0): the lists, their offsets, and the job's answer at depth k + max_exclude
+    uint64_t* h_xlist = nullptr;           // [max_batch][max_exclude] packed request by request
+    uint32_t* h_xoff = nullptr;            // [max_batch + 1]
+    uint64_t* d_xlist = nullptr;
+    uint32_t* d_xoff = nullptr;
+    uint64_t* d_xrows = nullptr;           // [max_batch][k + max_exclude]
+    float* d_xsc = nullptr;
     uint32_t* d_pick = nullptr;            // re-rank: [max_batch][max_top_n]
     uint32_t* d_pick_cnt = nullptr;
     char* d_page = nullptr;                // recommend: the pages, layout as h_out
@@ -212,6 +220,7 @@ struct pg_coalescer {
     std::string grank_var;
     std::atomic<uint32_t> outstanding{0};            // requests between submit and return (the router's load measure)
     uint32_t k = 0, max_batch = 0, max_wait_us = 0, depth = 0, max_top_n = 0, max_rank_items = 0, timeout_us = 0;
+    uint32_t max_exclude = 0;        // the context's "coalescer_max_exclude" at creation: longest list of pg_coalescer_recall_exclude (0: off)
     // arrival statistics per queue (under mu): a request that arrives at an idle device only waits for company when company is likely —
     // when the recent inter-arrival gap (EWMA) is below max_wait_us; a lone caller is dispatched at once
     pg::Clock::time_point last_arrival[pg::kNumQueues];
@@ -258,7 +267,7 @@ inline uint32_t l2_batch_limit(const pg_coalescer* c) {
     return std::min(c->max_batch, screened ? 128u : kL2Batch);
 }
 int flavour_of(int queue) {
-    return (queue == kQRecall || queue == kQRecallL2) ? kRecall : (queue == kQRecommend ? kRecommend : (queue == kQDpp ? kDpp : kRank));
+    return (queue == kQRecall || queue == kQRecallL2 || queue == kQRecallEx) ? kRecall : (queue == kQRecommend ? kRecommend : (queue == kQDpp ? kDpp : kRank));
 }
 
 size_t page_bytes(const pg_coalescer* c) { return (size_t)c->max_batch * c->max_top_n * page_entry_bytes(std::max(c->n_planes, 1)); }
@@ -317,6 +326,15 @@ int alloc_slot(pg_coalescer* c, Slot* s) {
     PG_HIP(hipMalloc((void**)&s->d_rows, nb * k * 8));
     PG_HIP(hipMalloc((void**)&s->d_recall, nb * k * 4));
     PG_HIP(hipMalloc((void**)&s->d_count, nb * 4));
+    if (c->max_exclude) {
+        const size_t kx = k + c->max_exclude;
+        PG_HIP(hipHostMalloc((void**)&s->h_xlist, nb * c->max_exclude * 8));
+        PG_HIP(hipHostMalloc((void**)&s->h_xoff, (nb + 1) * 4));
+        PG_HIP(hipMalloc((void**)&s->d_xlist, nb * c->max_exclude * 8));
+        PG_HIP(hipMalloc((void**)&s->d_xoff, (nb + 1) * 4));
+        PG_HIP(hipMalloc((void**)&s->d_xrows, nb * kx * 8));
+        PG_HIP(hipMalloc((void**)&s->d_xsc, nb * kx * 4));
+    }
     if (rank) PG_HIP(hipMalloc((void**)&s->d_rank, (size_t)std::max(c->n_planes, (int)c->max_heads) * c->rank_stride * 4));
     if (c->e) {
         PG_HIP(hipMalloc((void**)&s->d_fused, nb * k * 8));
@@ -360,12 +378,12 @@ void free_slot(pg_coalescer* c, Slot* s) {
     if (s->done) hipEventDestroy(s->done);
     if (s->computed) hipEventDestroy(s->computed);
     for (void* p : {(void*)s->h_vec, (void*)s->h_ufid, (void*)s->h_qk, (void*)s->h_uq, (void*)s->h_cand, (void*)s->h_off, (void*)s->h_out,
-                    (void*)s->h_dcand, (void*)s->h_drel, (void*)s->h_dhook, (void*)s->h_dout})
+                    (void*)s->h_dcand, (void*)s->h_drel, (void*)s->h_dhook, (void*)s->h_dout, (void*)s->h_xlist, (void*)s->h_xoff})
         if (p) hipHostFree(p);
     for (void* p : {(void*)s->d_vec, (void*)s->d_ufid, (void*)s->d_qk, (void*)s->d_uq, (void*)s->d_qemb, (void*)s->d_cand, (void*)s->d_off,
                     (void*)s->d_rows, (void*)s->d_recall, (void*)s->d_rank, (void*)s->d_fused, (void*)s->d_order, (void*)s->d_count,
                     (void*)s->d_pick, (void*)s->d_pick_cnt, (void*)s->d_page, (void*)s->d_dcand, (void*)s->d_drel, (void*)s->d_dhook,
-                    (void*)s->d_demb, (void*)s->d_dout})
+                    (void*)s->d_demb, (void*)s->d_dout, (void*)s->d_xlist, (void*)s->d_xoff, (void*)s->d_xrows, (void*)s->d_xsc})
         if (p) hipFree(p);
     delete s;
 }
@@ -397,6 +415,8 @@ int slot_copy_out(pg_coalescer* c, Slot* s) {
         const size_t nk = (size_t)nq * c->k;
         PG_HIP(hipMemcpyAsync(s->h_out, s->d_rows, nk * 8, hipMemcpyDeviceToHost, c->copy_stream));
         PG_HIP(hipMemcpyAsync(s->h_out + (size_t)c->max_batch * c->k * 8, s->d_recall, nk * 4, hipMemcpyDeviceToHost, c->copy_stream));
+        if (s->queue == kQRecallEx)            // (the counts after the exclusions: the job's status words count the over-fetched answer)
+            PG_HIP(hipMemcpyAsync(s->h_out + (size_t)c->max_batch * c->k * 12, s->d_count, (size_t)nq * 4, hipMemcpyDeviceToHost, c->copy_stream));
     } else if (fl == kDpp) {
         const size_t np = (size_t)nq * s->key.topn;
         PG_HIP(hipMemcpyAsync(s->h_dout, s->d_dout, np * 4, hipMemcpyDeviceToHost, c->copy_stream));
@@ -413,6 +433,13 @@ int slot_copy_out(pg_coalescer* c, Slot* s) {
     return PG_OK;
 }
 
+// a batch of recalls with exclusion lists: every request's first k entries outside its list, out of the job's answer at depth
+// k + max_exclude (behind the job's plan, and again behind a patch of single requests; caller holds the slot's ctx->mu)
+int exclude_batch_compact_locked(pg_coalescer* c, Slot* s) {
+    return exclude_compact_locked(s->ctx, s->d_xrows, s->d_xsc, s->n_req, c->k + c->max_exclude, s->d_xlist, s->d_xoff, c->k,
+                                  -__builtin_inff(), s->d_rows, s->d_recall, s->d_count);
+}
+
 // the recall job of a recall-flavour batch, with its queries put together in front of it
 int enqueue_recall_batch(pg_coalescer* c, Slot* s, bool first) {
     pg_ctx* ctx = s->ctx;
@@ -426,7 +453,12 @@ int enqueue_recall_batch(pg_coalescer* c, Slot* s, bool first) {
     // a swap / upload between this batch's first pass and its re-plan: the job's statistics and plans are the old version's —
     // the whole batch starts over on the new rows (one version per batch)
     if (!first && j.table_gen != c->t->generation.load(std::memory_order_relaxed)) first = true;
+    const bool ex = s->queue == kQRecallEx;
     if (first) {
+        if (ex) {
+            PG_HIP(hipMemcpyAsync(s->d_xoff, s->h_xoff, ((size_t)nq + 1) * 4, hipMemcpyHostToDevice, st));
+            if (s->h_xoff[nq]) PG_HIP(hipMemcpyAsync(s->d_xlist, s->h_xlist, (size_t)s->h_xoff[nq] * 8, hipMemcpyHostToDevice, st));
+        }
         bool any_trigger = false, any_online = false;
         for (uint32_t q = 0; q < nq; ++q) {
             any_trigger = any_trigger || s->h_qk[2 * q] == kTrigger;
@@ -446,9 +478,9 @@ int enqueue_recall_batch(pg_coalescer* c, Slot* s, bool first) {
         j.t = c->t;
         j.d_queries = s->d_vec;
         j.nq = nq;
-        j.k = c->k;
-        j.d_out_rows = s->d_rows;
-        j.d_out_scores = s->d_recall;
+        j.k = ex ? c->k + c->max_exclude : c->k;          // (one depth for every such batch, whatever its lists hold)
+        j.d_out_rows = ex ? s->d_xrows : s->d_rows;
+        j.d_out_scores = ex ? s->d_xsc : s->d_recall;
         j.d_out_count = nullptr;
         j.h_status = s->run->h_status;
         j.events = &s->run->events;
@@ -456,7 +488,8 @@ int enqueue_recall_batch(pg_coalescer* c, Slot* s, bool first) {
         if ((rc = recall_job_prepare(&j))) return rc;
     }
     s->run->patched = false;
-    return recall_job_enqueue(&j);
+    if ((rc = recall_job_enqueue(&j))) return rc;
+    return ex ? exclude_batch_compact_locked(c, s) : PG_OK;
 }
 
 int enqueue_rank_batch(pg_coalescer* c, Slot* s) {
@@ -669,12 +702,17 @@ void stage_batch(pg_coalescer* c, Slot* s) {
                 else if (c->query_model) memset(s->h_uq + (size_t)i * c->query_model->d_user, 0, (size_t)c->query_model->d_user * 4);
             } else {
                 memcpy(s->h_vec + (size_t)i * w, r->vec, (size_t)w * 4);
-                if (kind == kQRecallL2) {              // plain vector queries (enqueue_recall_batch looks at the kinds)
+                if (kind == kQRecallL2 || kind == kQRecallEx) {              // plain vector queries (enqueue_recall_batch looks at the kinds)
                     s->h_qk[2 * i] = kVector;
                     s->h_qk[2 * i + 1] = 0;
                 }
+                if (kind == kQRecallEx) {
+                    if (i == 0) s->h_xoff[0] = 0;
+                    if (r->n) memcpy(s->h_xlist + s->h_xoff[i], r->excl, (size_t)r->n * 8);
+                    s->h_xoff[i + 1] = s->h_xoff[i] + r->n;
+                }
             }
-            if (uw && kind != kQRecall && kind != kQRecallL2) {
+            if (uw && kind != kQRecall && kind != kQRecallL2 && kind != kQRecallEx) {
                 if (r->ufids) memcpy(s->h_ufid + (size_t)i * uw, r->ufids, (size_t)uw * 4);
                 else memset(s->h_ufid + (size_t)i * uw, 0, (size_t)uw * 4);
             }
@@ -819,6 +857,10 @@ void completer_main(pg_coalescer* c) {
             if (ok && s->run->patched) {                 // device outputs changed after the copy-out: copy again
                 s->run->patched = false;
                 replanned = true;
+                if (s->queue == kQRecallEx) {            // (the patched requests' slices of the over-fetched answer changed)
+                    std::lock_guard<std::mutex> g(s->ctx->mu);
+                    if ((rc = exclude_batch_compact_locked(c, s))) break;
+                }
                 if ((rc = slot_copy_out(c, s))) break;
                 continue;
             }
@@ -1092,6 +1134,15 @@ int pg_coalescer_create_scene(pg_ctx* ctx, const pg_table* t, const pg_scene_con
     c->rerank.candidates = sc->rerank_candidates;
     c->rerank.dpp = sc->dpp;
     c->k = cfg->k;
+    {
+        std::lock_guard<std::mutex> g(ctx->mu);
+        c->max_exclude = ctx->knobs.coalescer_max_exclude;
+    }
+    if (c->max_exclude && cfg->k + c->max_exclude > 16384) {
+        pg::set_error("pg_coalescer_create: k=%u plus coalescer_max_exclude=%u exceeds the recalls' depth of 16384", cfg->k, c->max_exclude);
+        delete c;
+        return PG_ERR_UNSUPPORTED;
+    }
     c->max_batch = cfg->max_batch ? cfg->max_batch : max_q;
     c->max_wait_us = cfg->max_wait_us ? cfg->max_wait_us : 100;
     for (double& sc : c->rejoin_score) sc = 1.0;     // (optimistic: callers are closed loops until they show otherwise)
@@ -1240,6 +1291,35 @@ int pg_coalescer_recall_l2(pg_coalescer* c, const float* query, uint64_t* out_ro
         memcpy(out_rows, s->h_out + (size_t)r->index * k * 8, k * 8);
         memcpy(out_dist, s->h_out + (size_t)c->max_batch * k * 8 + (size_t)r->index * k * 4, k * 4);
         if (out_count) *out_count = s->run->h_status[1 + r->index];
+    }
+    return pg::finish_call(c, r);
+}
+
+int pg_coalescer_recall_exclude(pg_coalescer* c, const float* query, const uint64_t* excl_rows, uint32_t n_excl, uint64_t* out_rows,
+                                float* out_scores, uint32_t* out_count) {
+    PG_REQUIRE(c && query && out_rows && out_scores && (excl_rows || n_excl == 0), "pg_coalescer_recall_exclude: NULL argument");
+    if (c->group) {
+        pg::set_error("pg_coalescer: a coalescer over a shard group serves pg_coalescer_recommend only");
+        return PG_ERR_UNSUPPORTED;
+    }
+    if (!c->max_exclude || n_excl > c->max_exclude) {
+        pg::set_error("pg_coalescer_recall_exclude: a list of %u ids; the coalescer was created with coalescer_max_exclude = %u", n_excl, c->max_exclude);
+        return PG_ERR_UNSUPPORTED;
+    }
+    pg::Req* r = new pg::Req();
+    r->vec = query;
+    r->qkind = pg::kVector;
+    r->excl = excl_rows;
+    r->n = n_excl;
+    r->queue = pg::kQRecallEx;
+    int rc;
+    if ((rc = pg::submit_and_wait(c, r))) return rc;
+    pg::Slot* s = r->slot;
+    if (r->rc == PG_OK) {
+        const size_t k = c->k;
+        memcpy(out_rows, s->h_out + (size_t)r->index * k * 8, k * 8);
+        memcpy(out_scores, s->h_out + (size_t)c->max_batch * k * 8 + (size_t)r->index * k * 4, k * 4);
+        if (out_count) memcpy(out_count, s->h_out + (size_t)c->max_batch * k * 12 + (size_t)r->index * 4, 4);
     }
     return pg::finish_call(c, r);
 }

@@ -98,6 +98,7 @@ struct Knobs {
     double index_dense_fraction = 0.01;     // PG_INDEX_DENSE_FRACTION: an index recall of nq queries whose (row, query) pairs exceed this x rows x nq^0.6 is served by the table's pass
     uint32_t index_plan_rounds = 2;         // PG_INDEX_PLAN_ROUNDS: expand / rescore / select rounds of an attached index's plan, for the probe and for the scan each
     uint32_t index_skip_batches = 64;       // PG_INDEX_SKIP_BATCHES: after a dense or rounds re-plan, batches of that size band that skip the index plan
+    uint32_t coalescer_max_exclude = 0;     // PG_COALESCER_MAX_EXCLUDE: longest list of pg_coalescer_recall_exclude (0..4096; 0: the entry is off), read when a coalescer is created
     uint32_t index_where_cache = 4;         // PG_INDEX_WHERE_CACHE: filtered lists an index keeps per filter (0: built per call, freed after it)
     bool index_route_where = false;         // PG_INDEX_ROUTE_WHERE: pg_recall_topk_where on a table with a current attached index searches it
     double index_refresh_full_fraction = 0.1;   // PG_INDEX_REFRESH_FULL_FRACTION: pg_index_refresh in auto mode re-assigns every row once the written rows exceed this share of the table
@@ -249,7 +250,8 @@ struct pg_ctx {
     //   9 group.hip   10 re-rank stage (DPP candidates)   11 recall.hip: the screened pass's record regions
     //   12, 13 recall.hip   14 rank_mlp.hip: head partials of the weights-stationary multi-head kernel   15 pg_fuse_scores_dev
     //   16 pg_features_eval_dev: the bound variables   17 index.hip: bounds, probe thresholds and list counts of an index recall
-    pg::Scratch scratch[18];
+    //   18 recall.hip: the over-fetched answer, lists and counts of a recall with exclusion lists
+    pg::Scratch scratch[19];
     std::mutex pool_mu;          // guards pipe_free
     std::vector<pg::PipeRun*> pipe_free;     // per-batch status blocks / events of the device-resident pipelines
     std::map<const void*, size_t> dyn_lds;   // kernels whose dynamic-LDS limit was raised on this device
@@ -489,6 +491,22 @@ int view_create_locked(const char* who, pg_ctx* ctx, const pg_table* t, const Ro
 int recall_where_locked(pg_ctx* ctx, const pg_table* t, RowFilter f, int metric, const float* d_q, uint32_t nq, uint32_t k,
                         uint64_t* d_rows, float* d_sc, uint32_t* out_count);
 int where_pad_launch(pg_ctx* ctx, uint64_t* d_rows, float* d_sc, size_t n, bool l2);
+// where.hip: a compound clause for a search outside that file (pg_recall_topk_exclude).  where_clause_check: the checks of
+// pg_recall_topk_where_ex in its order (no lock needed); where_clause_bind: the filter, its identity and the reference that keeps
+// its bitmap alive until the caller's stream has synchronised (caller holds ctx->mu and the table's shared lock).
+struct WhereServe {
+    RowFilter f{};
+    WhereId id{};
+    std::shared_ptr<void> hold;
+};
+int where_clause_check(const char* who, const pg_ctx* ctx, const pg_table* t, const pg_features* fs, const pg_where* w, int metric,
+                       const void* queries, const void* rows, const void* scores, uint32_t nq, uint32_t k);
+int where_clause_bind(const char* who, pg_ctx* ctx, const pg_table* t, const pg_features* fs, const pg_where* w, WhereServe* out);
+// exclude.hip: pg_exclude_compact_dev behind its checks (caller holds ctx->mu; enqueues one kernel, nothing synchronises)
+constexpr uint32_t kMaxExclude = 4096;      // ids in one request's list
+int exclude_compact_locked(pg_ctx* ctx, const uint64_t* d_rows, const float* d_scores, uint32_t nq, uint32_t k_in,
+                           const uint64_t* d_excl_rows, const uint32_t* d_excl_offsets, uint32_t k_out, float pad_score,
+                           uint64_t* d_out_rows, float* d_out_scores, uint32_t* d_out_count);
 // index.hip: the attached index pg_recall_topk_where searches ("index_route_where" set and the index current), or NULL; the
 // filtered search itself (a stale, non-finite, dense or overflowing batch: recall_where_locked)
 pg_index* index_route_where(const pg_ctx* ctx, const pg_table* t);

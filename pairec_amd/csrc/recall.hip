@@ -3441,6 +3441,112 @@ int recall_entry(const char* who, pg_ctx* ctx, const pg_table* t, const float* q
     return host ? recall_staged(ctx, t->dim, q, nq, k, rows, sc, run) : run(q, rows, sc);
 }
 
+// ---- recalls with per-request exclusion lists (the kernel: exclude.hip) ----------------------------------------
+// The offsets of nq lists (`extra` more ids join every list: the request's own trigger row): monotone, at most kMaxExclude ids
+// each, k + the longest within the recalls' 16384.
+int exclude_lists_check(const char* who, const uint32_t* off, uint32_t nq, uint32_t k, uint32_t extra, uint32_t* nmax_out) {
+    uint32_t nmax = extra;
+    for (uint32_t q = 0; off && q < nq; ++q) {
+        PG_REQUIRE(off[q + 1] >= off[q], "%s: excl_offsets[%u] = %u is below excl_offsets[%u] = %u", who, q + 1, off[q + 1], q, off[q]);
+        if (off[q + 1] - off[q] > kMaxExclude) {
+            set_error("%s: request %u excludes %u ids (at most %u per request)", who, q, off[q + 1] - off[q], kMaxExclude);
+            return PG_ERR_UNSUPPORTED;
+        }
+        nmax = std::max(nmax, off[q + 1] - off[q] + extra);
+    }
+    if (nmax > kMaxExclude) {
+        set_error("%s: a list of %u ids with the trigger row (at most %u per request)", who, nmax, kMaxExclude);
+        return PG_ERR_UNSUPPORTED;
+    }
+    if ((uint64_t)k + nmax > 16384) {
+        set_error("%s: k=%u plus the longest exclusion list of %u ids exceeds the recalls' depth of 16384", who, k, nmax);
+        return PG_ERR_UNSUPPORTED;
+    }
+    *nmax_out = nmax;
+    return PG_OK;
+}
+
+// One recall of nq device queries at depth k + nmax through `inner` — the plain call's own search — into scratch slot 18, then
+// the compaction into d_rows / d_sc [nq][k].  excl: the lists' ids, host (staged here, off rebased) or device (indexed by off
+// as given); off: host [nq + 1].  nmax = 0: `inner` at k straight into the outputs.  Caller holds ctx->mu and the table's
+// shared lock; ends synchronised (out_count: host [nq] or NULL).
+template <class Inner>
+int recall_exclude_locked(pg_ctx* ctx, uint32_t nq, uint32_t k, uint32_t nmax, bool l2, const uint64_t* excl, bool excl_on_host,
+                          const uint32_t* off, uint64_t* d_rows, float* d_sc, uint32_t* out_count, Inner&& inner) {
+    int rc;
+    uint32_t counts[kMaxQueries];
+    if (nmax == 0) {
+        if ((rc = inner(k, d_rows, d_sc, counts))) return rc;
+        if (out_count) memcpy(out_count, counts, (size_t)nq * 4);
+        return PG_OK;
+    }
+    const uint32_t kx = k + nmax;
+    const uint32_t total = excl_on_host ? off[nq] - off[0] : 0;
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t ob = al(((size_t)nq + 1) * 4), cb = al((size_t)nq * 4), lb = al((size_t)total * 8), rb = al((size_t)nq * kx * 8);
+    void* buf;
+    if ((rc = scratch_reserve(ctx, 18, ob + cb + lb + rb + (size_t)nq * kx * 4, &buf))) return rc;
+    uint32_t* d_off = (uint32_t*)buf;
+    uint32_t* d_cnt = (uint32_t*)((char*)buf + ob);
+    uint64_t* d_list = (uint64_t*)((char*)buf + ob + cb);
+    uint64_t* d_xrows = (uint64_t*)((char*)buf + ob + cb + lb);
+    float* d_xsc = (float*)((char*)d_xrows + rb);
+    uint32_t h_off[kMaxQueries + 1];
+    for (uint32_t q = 0; q <= nq; ++q) h_off[q] = excl_on_host ? off[q] - off[0] : off[q];
+    PG_HIP(hipMemcpyAsync(d_off, h_off, ((size_t)nq + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (total) PG_HIP(hipMemcpyAsync(d_list, excl + off[0], (size_t)total * 8, hipMemcpyHostToDevice, ctx->stream));
+    PG_HIP(hipStreamSynchronize(ctx->stream));          // (h_off lives on this frame, and the inner recall may reuse pageable staging)
+    if ((rc = inner(kx, d_xrows, d_xsc, counts))) return rc;
+    if ((rc = exclude_compact_locked(ctx, d_xrows, d_xsc, nq, kx, excl_on_host ? d_list : excl, d_off, k,
+                                     l2 ? __builtin_inff() : -__builtin_inff(), d_rows, d_sc, d_cnt)))
+        return rc;
+    PG_HIP(hipMemcpyAsync(ctx->h_status, d_cnt, (size_t)nq * 4, hipMemcpyDeviceToHost, ctx->stream));
+    PG_HIP(hipStreamSynchronize(ctx->stream));
+    if (out_count) memcpy(out_count, ctx->h_status, (size_t)nq * 4);
+    return PG_OK;
+}
+
+// pg_recall_topk_exclude[_dev]: the checks of the call it extends (pg_recall_topk[_l2][_dev], or pg_recall_topk_where_ex with a
+// clause), then the lists'
+int recall_exclude_entry(const char* who, pg_ctx* ctx, const pg_table* t, const float* q, uint32_t nq, uint32_t k, const uint64_t* excl,
+                         const uint32_t* off, const pg_recall_exclude_opts* opts, uint64_t* rows, float* sc, uint32_t* out_count, bool host) {
+    const int metric = opts ? opts->metric : 0;
+    const pg_features* fs = opts ? opts->fs : nullptr;
+    const pg_where* w = opts ? opts->where : nullptr;
+    PG_REQUIRE((fs != nullptr) == (w != nullptr), "%s: opts->fs and opts->where come together", who);
+    int rc;
+    if (w) {
+        if ((rc = where_clause_check(who, ctx, t, fs, w, metric, q, rows, sc, nq, k))) return rc;
+    } else {
+        PG_REQUIRE(metric == 0 || metric == 1, "%s: metric %d unknown (0 inner product, 1 squared Euclidean)", who, metric);
+        if ((rc = recall_check(who, ctx, t, q, rows, sc, nq, k, metric == 1))) return rc;
+    }
+    PG_REQUIRE(off, "%s: excl_offsets is NULL", who);
+    uint32_t nmax = 0;
+    if ((rc = exclude_lists_check(who, off, nq, k, 0, &nmax))) return rc;
+    PG_REQUIRE(excl || off[nq] == off[0], "%s: excl_rows is NULL", who);
+    std::lock_guard<std::mutex> g(ctx->mu);
+    TableRead tr(t->rw);
+    WhereServe ws;
+    if (w && (rc = where_clause_bind(who, ctx, t, fs, w, &ws))) return rc;
+    pg_index* ix = w ? index_route_where(ctx, t) : nullptr;
+    auto run = [&](const float* d_q, uint64_t* d_rows, float* d_sc) {
+        auto inner = [&](uint32_t kk, uint64_t* r, float* s, uint32_t* counts) {
+            if (!w) {
+                RecallOpts o;
+                o.l2 = metric == 1;
+                return recall_batches_locked(ctx, t, d_q, nq, kk, r, s, counts, o);
+            }
+            return ix ? index_where_locked(ctx, ix, ws.id, ws.f, metric == 1, d_q, nq, kk, r, s, counts)
+                      : recall_where_locked(ctx, t, ws.f, metric, d_q, nq, kk, r, s, counts);
+        };
+        return recall_exclude_locked(ctx, nq, k, nmax, metric == 1, excl, host, off, d_rows, d_sc, out_count, inner);
+    };
+    rc = host ? recall_staged(ctx, t->dim, q, nq, k, rows, sc, run) : run(q, rows, sc);
+    if (rc != PG_OK && w) (void)hipStreamSynchronize(ctx->stream);      // (nothing enqueued reads the bitmap once ws lets go of it)
+    return rc;
+}
+
 int topk_merge_strided_locked(pg_ctx* ctx, const uint64_t* d_rows, const float* d_scores, uint32_t nq, uint32_t nlists,
                               uint32_t per_list, size_t row_ls, size_t row_qs, size_t sc_ls, size_t sc_qs, uint32_t k,
                               uint64_t* d_out_rows, float* d_out_scores, uint32_t* d_out_count) {
@@ -3759,6 +3865,69 @@ int pg_i2i_recall(pg_ctx* ctx, const pg_table* trigger_table, const uint32_t* tr
         PG_HIP(hipMemcpyAsync(d_q + (size_t)i * t->dim, trigger_table->d + (size_t)trigger_rows[i] * t->dim, (size_t)t->dim * 4,
                               hipMemcpyDeviceToDevice, ctx->stream));
     if ((rc = pg::recall_dev_locked(ctx, t, d_q, n, k, d_rows, d_sc, out_count, nullptr))) return rc;
+    PG_HIP(hipMemcpyAsync(out_rows, d_rows, rb, hipMemcpyDeviceToHost, ctx->stream));
+    PG_HIP(hipMemcpyAsync(out_scores, d_sc, sb, hipMemcpyDeviceToHost, ctx->stream));
+    PG_HIP(hipStreamSynchronize(ctx->stream));
+    return PG_OK;
+}
+
+int pg_recall_topk_exclude(pg_ctx* ctx, const pg_table* t, const float* queries, uint32_t nq, uint32_t k, const uint64_t* excl_rows,
+                           const uint32_t* excl_offsets, const pg_recall_exclude_opts* opts, uint64_t* out_rows, float* out_scores,
+                           uint32_t* out_count) {
+    return pg::recall_exclude_entry("pg_recall_topk_exclude", ctx, t, queries, nq, k, excl_rows, excl_offsets, opts, out_rows, out_scores,
+                                    out_count, true);
+}
+
+int pg_recall_topk_exclude_dev(pg_ctx* ctx, const pg_table* t, const float* d_queries, uint32_t nq, uint32_t k, const uint64_t* d_excl_rows,
+                               const uint32_t* excl_offsets, const pg_recall_exclude_opts* opts, uint64_t* d_out_rows, float* d_out_scores,
+                               uint32_t* out_count) {
+    return pg::recall_exclude_entry("pg_recall_topk_exclude_dev", ctx, t, d_queries, nq, k, d_excl_rows, excl_offsets, opts, d_out_rows,
+                                    d_out_scores, out_count, false);
+}
+
+// pg_i2i_recall without the items the request has seen — and, with exclude_trigger, without the trigger item itself (the hole
+// pg_i2i_recall documents): its checks in its order, then the lists'
+int pg_i2i_recall_exclude(pg_ctx* ctx, const pg_table* trigger_table, const uint32_t* trigger_rows, uint32_t n, const pg_table* t,
+                          uint32_t k, int exclude_trigger, const uint64_t* excl_rows, const uint32_t* excl_offsets, uint64_t* out_rows,
+                          float* out_scores, uint32_t* out_count) {
+    PG_REQUIRE(ctx && trigger_table && t && trigger_rows && out_rows && out_scores, "pg_i2i_recall_exclude: NULL argument");
+    PG_REQUIRE(trigger_table->dim == t->dim, "pg_i2i_recall_exclude: trigger table dim %u != searched table dim %u", trigger_table->dim, t->dim);
+    PG_REQUIRE(!trigger_table->d_row_map, "pg_i2i_recall_exclude: the trigger table is a filtered view (trigger rows are rows of the source)");
+    PG_REQUIRE(n >= 1 && n <= (uint32_t)pg::kMaxQueries && (t->dim <= 128 || n <= 32), "pg_i2i_recall_exclude: %u trigger items per call unsupported", n);
+    if (k < 1 || k > 16384) {
+        pg::set_error("pg_i2i_recall_exclude: k=%u unsupported (1..16384)", k);
+        return PG_ERR_UNSUPPORTED;
+    }
+    for (uint32_t i = 0; i < n; ++i)
+        PG_REQUIRE(trigger_rows[i] < trigger_table->rows, "pg_i2i_recall_exclude: trigger row %u outside table of %llu rows", trigger_rows[i],
+                   (unsigned long long)trigger_table->rows);
+    PG_REQUIRE(!exclude_trigger || trigger_table == t, "pg_i2i_recall_exclude: exclude_trigger needs the trigger table to be the searched table");
+    PG_REQUIRE(excl_offsets || exclude_trigger, "pg_i2i_recall_exclude: excl_offsets is NULL");
+    uint32_t nmax = 0;
+    int rc;
+    if ((rc = pg::exclude_lists_check("pg_i2i_recall_exclude", excl_offsets, n, k, exclude_trigger ? 1u : 0u, &nmax))) return rc;
+    PG_REQUIRE(excl_rows || !excl_offsets || excl_offsets[n] == excl_offsets[0], "pg_i2i_recall_exclude: excl_rows is NULL");
+    // every request's list with its trigger row behind it
+    std::vector<uint64_t> lists;
+    std::vector<uint32_t> off(n + 1, 0);
+    for (uint32_t i = 0; i < n; ++i) {
+        if (excl_offsets) lists.insert(lists.end(), excl_rows + excl_offsets[i], excl_rows + excl_offsets[i + 1]);
+        if (exclude_trigger) lists.push_back(t->row_offset + trigger_rows[i]);
+        off[i + 1] = (uint32_t)lists.size();
+    }
+    std::lock_guard<std::mutex> g(ctx->mu);
+    pg::TableRead2 tr(t, trigger_table);
+    void* buf;
+    const size_t qb = (size_t)n * t->dim * 4, rb = (size_t)n * k * 8, sb = (size_t)n * k * 4;
+    if ((rc = pg::scratch_reserve(ctx, 5, qb + rb + sb + 64, &buf))) return rc;
+    float* d_q = (float*)buf;
+    uint64_t* d_rows = (uint64_t*)((char*)buf + ((qb + 15) & ~(size_t)15));
+    float* d_sc = (float*)((char*)d_rows + rb);
+    for (uint32_t i = 0; i < n; ++i)
+        PG_HIP(hipMemcpyAsync(d_q + (size_t)i * t->dim, trigger_table->d + (size_t)trigger_rows[i] * t->dim, (size_t)t->dim * 4,
+                              hipMemcpyDeviceToDevice, ctx->stream));
+    auto inner = [&](uint32_t kk, uint64_t* r, float* s, uint32_t* counts) { return pg::recall_dev_locked(ctx, t, d_q, n, kk, r, s, counts, nullptr); };
+    if ((rc = pg::recall_exclude_locked(ctx, n, k, nmax, false, lists.data(), true, off.data(), d_rows, d_sc, out_count, inner))) return rc;
     PG_HIP(hipMemcpyAsync(out_rows, d_rows, rb, hipMemcpyDeviceToHost, ctx->stream));
     PG_HIP(hipMemcpyAsync(out_scores, d_sc, sb, hipMemcpyDeviceToHost, ctx->stream));
     PG_HIP(hipStreamSynchronize(ctx->stream));

@@ -651,6 +651,24 @@ int where_ex_recall(const char* who, pg_ctx* ctx, const pg_table* t, pg_index* i
 }
 }  // namespace
 
+int where_clause_check(const char* who, const pg_ctx* ctx, const pg_table* t, const pg_features* fs, const pg_where* w, int metric,
+                       const void* queries, const void* rows, const void* scores, uint32_t nq, uint32_t k) {
+    int cols[kMaxCols];
+    return where_ex_check(who, ctx, t, fs, w, metric, queries, rows, scores, nq, k, cols);
+}
+
+int where_clause_bind(const char* who, pg_ctx* ctx, const pg_table* t, const pg_features* fs, const pg_where* w, WhereServe* out) {
+    int cols[kMaxCols];
+    int rc;
+    if ((rc = where_resolve(who, w, fs, t->rows, cols))) return rc;
+    WhereBound b;
+    if ((rc = where_bind(who, ctx, w, fs, t->rows, cols, false, &b))) return rc;
+    out->f = b.f;
+    out->id = b.id;
+    out->hold = b.hold;
+    return PG_OK;
+}
+
 }  // namespace pg
 
 extern "C" {

@@ -22,6 +22,19 @@ def _ptr(a: np.ndarray):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def _pack_lists(lists, nq: int):
+    """one exclusion list per request → (ids uint64 [total], offsets uint32 [nq + 1]); None = every list empty"""
+    if lists is None:
+        lists = [()] * nq
+    if len(lists) != nq:
+        raise ValueError("%d exclusion lists for %d requests" % (len(lists), nq))
+    arrs = [np.asarray(l, dtype=np.uint64).reshape(-1) for l in lists]
+    off = np.zeros(nq + 1, dtype=np.uint32)
+    off[1:] = np.cumsum([a.shape[0] for a in arrs])
+    ids = np.ascontiguousarray(np.concatenate(arrs)) if nq else np.zeros(0, dtype=np.uint64)
+    return ids, off
+
+
 class Context:
     def __init__(self, device: int = 0, stream: Optional[int] = None):
         self.L = _lib.load()
@@ -90,6 +103,33 @@ class Context:
         ms, b = C.c_double(), C.c_uint64()
         _lib.check(self.L.pg_last_scan_kernel_ms(self.h, C.byref(ms), C.byref(b)))
         return ms.value, b.value
+
+    def exclude_compact(self, rows: np.ndarray, scores: np.ndarray, lists, k_out: int, pad_score: float = -np.inf):
+        """The compaction kernel alone (pg_exclude_compact_dev): rows / scores [nq][k_in] in a recall's output order and one
+        exclusion list of global row ids per request → (rows [nq][k_out], scores [nq][k_out], counts [nq])."""
+        r = np.ascontiguousarray(rows, dtype=np.uint64)
+        sc = np.ascontiguousarray(scores, dtype=np.float32)
+        nq, k_in = r.shape
+        ids, off = _pack_lists(lists, nq)
+        if nq and int(np.diff(off.astype(np.int64)).max()) > 4096:       # (the C call cannot check it: its offsets are device memory)
+            raise ValueError("exclude_compact: at most 4096 ids per request")
+        bufs = [self.to_device(r), self.to_device(sc), self.to_device(ids), self.to_device(off),
+                self.malloc(nq * k_out * 8), self.malloc(nq * k_out * 4), self.malloc(nq * 4)]
+        try:
+            _lib.check(self.L.pg_exclude_compact_dev(self.h, C.c_void_p(bufs[0]), C.c_void_p(bufs[1]), nq, k_in, C.c_void_p(bufs[2]),
+                                                     C.c_void_p(bufs[3]), k_out, float(pad_score), C.c_void_p(bufs[4]),
+                                                     C.c_void_p(bufs[5]), C.c_void_p(bufs[6])))
+            self.synchronize()
+            out_r = np.empty((nq, k_out), dtype=np.uint64)
+            out_s = np.empty((nq, k_out), dtype=np.float32)
+            cnt = np.empty(nq, dtype=np.uint32)
+            self.d2h(out_r, bufs[4])
+            self.d2h(out_s, bufs[5])
+            self.d2h(cnt, bufs[6])
+        finally:
+            for b in bufs:
+                self.free(b)
+        return out_r, out_s, cnt
 
     # ---- sort / expr (context-level ops) ----------------------------------------------------
     def sort_scores(self, scores: np.ndarray, seg_offsets: Optional[Sequence[int]] = None,
@@ -238,13 +278,36 @@ class Table:
         v.rows = rows.value
         return v
 
-    def i2i_recall(self, trigger_rows, k: int, trigger_table: Optional["Table"] = None):
-        """I2IVectorRecall: rows of `trigger_table` (default: this table) are the queries."""
+    def recall_topk_exclude(self, queries: np.ndarray, k: int, lists, l2: bool = False, feats: Optional["Features"] = None,
+                            where: Optional["Where"] = None):
+        """recall_topk / recall_topk_l2 / recall_topk_where_ex (feats + where) over the rows that are not in the request's
+        exclusion list (pg_recall_topk_exclude): lists[q] = the global row ids request q has seen.
+        → (rows, scores or distances, counts)."""
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dim)
+        nq = q.shape[0]
+        ids, off = _pack_lists(lists, nq)
+        opts = _lib.PgRecallExcludeOpts(1 if l2 else 0, feats.h if feats is not None else None, where.h if where is not None else None)
+        rows = np.empty((nq, k), dtype=np.uint64)
+        scores = np.empty((nq, k), dtype=np.float32)
+        counts = np.zeros(nq, dtype=np.uint32)
+        _lib.check(self.ctx.L.pg_recall_topk_exclude(self.ctx.h, self.h, _ptr(q), nq, k, _ptr(ids), _ptr(off), C.byref(opts),
+                                                     _ptr(rows), _ptr(scores), _ptr(counts)))
+        return rows, scores, counts
+
+    def i2i_recall(self, trigger_rows, k: int, trigger_table: Optional["Table"] = None, exclude_trigger: bool = False, lists=None):
+        """I2IVectorRecall: rows of `trigger_table` (default: this table) are the queries.  exclude_trigger / lists: without
+        the trigger item itself / the request's seen items (pg_i2i_recall_exclude)."""
         tr = np.ascontiguousarray(trigger_rows, dtype=np.uint32)
         n = tr.shape[0]
         rows = np.empty((n, k), dtype=np.uint64)
         scores = np.empty((n, k), dtype=np.float32)
         counts = np.zeros(n, dtype=np.uint32)
+        if exclude_trigger or lists is not None:
+            ids, off = _pack_lists(lists, n)
+            _lib.check(self.ctx.L.pg_i2i_recall_exclude(self.ctx.h, (trigger_table or self).h, _ptr(tr), n, self.h, k,
+                                                        int(exclude_trigger), _ptr(ids), _ptr(off), _ptr(rows), _ptr(scores),
+                                                        _ptr(counts)))
+            return rows, scores, counts
         _lib.check(self.ctx.L.pg_i2i_recall(self.ctx.h, (trigger_table or self).h, _ptr(tr), n, self.h, k,
                                             _ptr(rows), _ptr(scores), _ptr(counts)))
         return rows, scores, counts
@@ -801,6 +864,15 @@ class Coalescer:
         rows, dist, cnt = self._recall_out()
         _lib.check(self.ctx.L.pg_coalescer_recall_l2(self.h, _ptr(q), _ptr(rows), _ptr(dist), C.byref(cnt)))
         return rows, dist, cnt.value
+
+    def recall_exclude(self, query: np.ndarray, ids):
+        """one request without the global row ids it has seen (pg_coalescer_recall_exclude; the context option
+        "coalescer_max_exclude" must be set when the coalescer is created)"""
+        q = np.ascontiguousarray(query, dtype=np.float32).reshape(self.table.dim)
+        x = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
+        rows, scores, cnt = self._recall_out()
+        _lib.check(self.ctx.L.pg_coalescer_recall_exclude(self.h, _ptr(q), _ptr(x), x.shape[0], _ptr(rows), _ptr(scores), C.byref(cnt)))
+        return rows, scores, cnt.value
 
     def i2i_recall(self, trigger_row: int):
         rows, scores, cnt = self._recall_out()
