@@ -51,8 +51,25 @@ typedef enum {
  *   PG_PREC_F32    fp32 MFMA, bit-defined (a k-ordered fmaf chain): the specification.
  *   PG_PREC_BF16   operands rounded to bf16, fp32 accumulation: fastest; scores within ~4e-5 of the fp32 path.
  *   PG_PREC_BF16X3 "split bf16": every operand as hi + lo bf16, three products per term into the fp32 accumulator, nothing
- *                  else rounded: scores within 1e-5 of PG_PREC_F32 (observed ~1e-6) at the bf16 matrix pipe's speed / 3. */
-typedef enum { PG_PREC_F32 = 0, PG_PREC_BF16 = 1, PG_PREC_BF16X3 = 2 } pg_prec;
+ *                  else rounded: scores within 1e-5 of PG_PREC_F32 (observed ~1e-6) at the bf16 matrix pipe's speed / 3.
+ *   PG_PREC_F16X2  PG_MODEL_DNN3[_MULTI] only.  Activations rounded once to fp16 (RNE), weights as hi + lo fp16, two products
+ *                  per term into the fp32 accumulator.
+ *   PG_PREC_F16    the same with the weights rounded once too: one product per term.
+ *                  Both carry PG_PREC_BF16X3's contract — scores within 1e-5 of PG_PREC_F32 — and keep it by range
+ *                  handling, not by luck.  Scaling rule (every factor an exact power of two, fixed at pg_model_load): with
+ *                  E_k = floor(log2 max_j |W1[k][j]|) per item input column and F_i = floor(log2 max_j |W2[i][j]|) per
+ *                  hidden unit (0 for an all-zero row), the kernel converts x_k * 2^(E_k + G) and relu(z1_i) * 2^(F_i + G)
+ *                  to fp16 against weights scaled by 2^(-E_k - G + S) and 2^(-F_i - G + S); G = 11, S = 23 (undone
+ *                  exactly where the accumulators are read).  A scaled activation that underflows fp16's normal range
+ *                  costs at most 2^-24 per term in units where the weight row's maximum is in [1, 2), i.e. at most
+ *                  fan_in * 2^-24 per pre-activation; one that overflows (a single term of order 2^5 in those units), or
+ *                  is not finite, sends its 128-item tile to the PG_PREC_BF16X3 kernel, enqueued behind the fp16 one — the
+ *                  tile's scores are then exactly a PG_PREC_BF16X3 model's.  A call the fp16 kernel does not cover
+ *                  (hidden widths 1024-512, a table of dim != 128, the rank_no_ws option) is served whole by the
+ *                  PG_PREC_BF16X3 path, bit for bit.  Never an error, never a silently worse score; pg_model_f16_stats counts.
+ *                  Refused at load (PG_ERR_UNSUPPORTED): PG_MODEL_FM_TWOTOWER; a non-finite weight; a scaled weight or
+ *                  scale factor outside fp32's normal range. */
+typedef enum { PG_PREC_F32 = 0, PG_PREC_BF16 = 1, PG_PREC_BF16X3 = 2, PG_PREC_F16X2 = 3, PG_PREC_F16 = 4 } pg_prec;
 typedef enum { PG_MODEL_DNN3 = 1, PG_MODEL_FM_TWOTOWER = 2, PG_MODEL_DNN3_MULTI = 3 } pg_model_kind;
 
 const char* pg_last_error(void);
@@ -212,6 +229,11 @@ int pg_model_load(pg_ctx* ctx, pg_model_kind kind, pg_prec prec, const void* blo
 int pg_model_destroy(pg_ctx* ctx, pg_model* m);
 /* outputs per item: 1, or n_out of a PG_MODEL_DNN3_MULTI */
 int pg_model_num_outputs(const pg_model* m, uint32_t* out);
+/* PG_PREC_F16X2 / PG_PREC_F16 models: out = {rank calls, 128-item tiles the fp16 kernel took, tiles of those re-served by the
+ * PG_PREC_BF16X3 kernel (out of range / non-finite data), calls served whole by the PG_PREC_BF16X3 path}.  Zeros for a model
+ * of another precision.  Waits for the model's context to drain (the tile counts live on the device; nothing on the rank
+ * path reads them back). */
+int pg_model_f16_stats(const pg_model* m, uint64_t out[4]);
 
 /* DNN3: R requests; request r has user vector user_vecs[r][d_user] and candidates
  * cand_rows[req_offsets[r] .. req_offsets[r+1]) (local row indices into `t`).  out_scores is fp32

@@ -204,6 +204,17 @@ struct pg_model {
     void* w2p = nullptr;    // packed layer 2
     void* w1p_lo = nullptr; // PG_PREC_BF16X3: the lo fragments (inside the w1p / w2p allocations)
     void* w2p_lo = nullptr;
+    // PG_PREC_F16X2 / PG_PREC_F16: prec is 2 (every BF16X3 buffer above is kept: the fallback) and f16_nprod 2 / 1
+    int f16_nprod = 0;
+    void* h_w1p = nullptr;  // scaled fp16 fragments (rank_h2.hip); the lo planes inside the same allocations
+    void* h_w2p = nullptr;
+    void* h_w1p_lo = nullptr;
+    void* h_w2p_lo = nullptr;
+    float* h_xs = nullptr;  // [kDIN] input-column factors
+    float* h_hs = nullptr;  // [h1] hidden-unit factors
+    unsigned long long* h_stats = nullptr;   // device [2]: tiles taken by the fp16 kernel, tiles re-served in BF16X3
+    mutable uint64_t f16_calls = 0, f16_calls_whole = 0;   // under the context's lock
+    pg_ctx* ctx = nullptr;
     float* c1_shared = nullptr;   // two-tower: ib1
     float* b2 = nullptr;
     float* w3 = nullptr;    // DNN3 head(s): [n_out][h2]

@@ -941,6 +941,84 @@ static std::vector<uint8_t> pack_weights(const float* w, uint32_t K, uint32_t N,
     return out;
 }
 
+// PG_PREC_F16X2 / PG_PREC_F16 (rank_h2.hip): the bf16 fragment layout in fp16 — every hi fragment (RNE), then, with two
+// products per term, every lo fragment (lo = RNE(w - hi))
+static std::vector<uint8_t> pack_weights_f16(const float* w, uint32_t K, uint32_t N, int nprod) {
+    const uint32_t kg = K / 16;
+    const size_t plane = (size_t)(N / 32) * kg * 1024;
+    std::vector<uint8_t> out(plane * nprod);
+    for (uint32_t nbg = 0; nbg < N / 32; ++nbg)
+        for (uint32_t g = 0; g < kg; ++g) {
+            uint8_t* frag = out.data() + ((size_t)nbg * kg + g) * 1024;
+            for (uint32_t lane = 0; lane < 64; ++lane) {
+                const uint32_t j = lane & 31, hh = lane >> 5;
+                _Float16 hi[8], lo[8];
+                for (uint32_t e = 0; e < 8; ++e) {
+                    const float v = w[(size_t)(g * 16 + 8 * hh + e) * N + nbg * 32 + j];
+                    hi[e] = (_Float16)v;
+                    lo[e] = (_Float16)(v - (float)hi[e]);
+                }
+                memcpy(frag + lane * 16, hi, 16);
+                if (nprod == 2) memcpy(frag + plane + lane * 16, lo, 16);
+            }
+        }
+    return out;
+}
+
+// floor(log2 max_j |row[j]|), 0 for an all-zero row; false for a non-finite entry
+static bool row_exponent(const float* row, size_t n, int* e) {
+    float mx = 0.0f;
+    for (size_t j = 0; j < n; ++j) {
+        if (!std::isfinite(row[j])) return false;
+        mx = std::max(mx, std::fabs(row[j]));
+    }
+    *e = mx > 0.0f ? std::ilogb(mx) : 0;
+    return true;
+}
+static bool f32_normal_or_zero(float v) { return v == 0.0f || std::isnormal(v); }
+
+// The fp16 modes' operands (the scaling rule is in rank_h2.hip's header): W1's item half [kDIN][h1] and W2 [h1][h2] scaled
+// per row, the activations' factors beside them.  PG_ERR_UNSUPPORTED for weights the rule cannot carry.
+static int build_f16_operands(const float* w1i, const float* w2, uint32_t h1, uint32_t h2, int nprod,
+                              std::vector<uint8_t>* w1p, std::vector<uint8_t>* w2p, std::vector<float>* xs,
+                              std::vector<float>* hs) {
+    auto scale_rows = [&](const float* w, uint32_t K, uint32_t N, int act_bias, std::vector<float>* ws,
+                          std::vector<float>* fs, const char* what) {
+        ws->assign((size_t)K * N, 0.0f);
+        fs->assign(K, 0.0f);
+        for (uint32_t k = 0; k < K; ++k) {
+            int e;
+            if (!row_exponent(w + (size_t)k * N, N, &e)) {
+                set_error("pg_model_load: %s row %u holds a non-finite weight: not representable in an fp16 mode", what, k);
+                return PG_ERR_UNSUPPORTED;
+            }
+            // act_bias: G for x (accumulator scale S comes from the weights), G - S for h1 (whose accumulators carry 2^S)
+            const float f = std::ldexp(1.0f, e + act_bias), g = std::ldexp(1.0f, -e - kH2G + kH2S);
+            bool ok = std::isnormal(f) && std::isnormal(g);
+            for (uint32_t j = 0; j < N && ok; ++j) {
+                const float v = w[(size_t)k * N + j] * g;
+                // (a weight 2^-100 of its row's maximum may vanish: it is under every bound here)
+                ok = std::isfinite(v);
+                (*ws)[(size_t)k * N + j] = v;
+            }
+            if (!ok) {
+                set_error("pg_model_load: %s row %u (largest weight 2^%d) leaves fp32's normal range once scaled for an fp16 mode",
+                          what, k, e);
+                return PG_ERR_UNSUPPORTED;
+            }
+            (*fs)[k] = f;
+        }
+        return PG_OK;
+    };
+    std::vector<float> w1s, w2s;
+    int rc;
+    if ((rc = scale_rows(w1i, kDIN, h1, kH2G, &w1s, xs, "W1 (item half)"))) return rc;
+    if ((rc = scale_rows(w2, h1, h2, kH2G - kH2S, &w2s, hs, "W2"))) return rc;
+    *w1p = pack_weights_f16(w1s.data(), kDIN, h1, nprod);
+    *w2p = pack_weights_f16(w2s.data(), h1, h2, nprod);
+    return PG_OK;
+}
+
 static int upload(pg_ctx* ctx, pg_model* m, const void* src, size_t bytes, void** dst) {
     void* d = nullptr;
     hipError_t e = hipMalloc(&d, bytes ? bytes : 16);
@@ -1106,6 +1184,13 @@ int rank_dnn3_dev_locked(pg_ctx* ctx, const pg_model* m, const pg_table* t,
     const bool ls_k = m->prec == 1 && !no_ws && t->dim == 128 && dnn3_ls_shape(m->h1, m->h2);
     // split bf16: the two-role kernel (rank_x3.hip), 128-item tiles; 1024-512 and 64-wide tables take the general form
     const bool x3_k = m->prec == 2 && !no_ws && t->dim == 128 && dnn3_x3_shape(m->h1, m->h2);
+    // the fp16 modes: rank_h2.hip where the two-role kernel would run, its out-of-range tiles re-served by that kernel;
+    // every other call whole on the split-bf16 path (the model's prec is 2)
+    const bool h2_k = m->f16_nprod && x3_k;
+    if (m->f16_nprod) {
+        m->f16_calls++;
+        if (!h2_k) m->f16_calls_whole++;
+    }
     const uint32_t grid128 = n_items / kBM + n_req;
     if (!ctx->timers_off) PG_HIP(hipEventRecord(ctx->ev[2], ctx->stream));
     if ((rc = build_tiles_launch(ctx, d_off, n_req, max_tiles, ws || rs_k ? (uint32_t)kWsItems : (uint32_t)kBM, rs.tile_req, rs.tile_item0,
@@ -1150,6 +1235,31 @@ int rank_dnn3_dev_locked(pg_ctx* ctx, const pg_model* m, const pg_table* t,
         if ((rc = launch_dnn3_rs(ctx, m->h1, m->h2, a))) return rc;
     } else if (ls_k) {
         if ((rc = launch_dnn3_ls(ctx, m->h1, m->h2, a))) return rc;
+    } else if (h2_k) {
+        void* fbp;
+        if ((rc = scratch_reserve(ctx, 17, ((size_t)3 * max_tiles + 64) * 4, &fbp))) return rc;
+        MlpArgs h = a;
+        h.w1p = m->h_w1p;
+        h.w2p = m->h_w2p;
+        h.w1p_lo = m->h_w1p_lo;
+        h.w2p_lo = m->h_w2p_lo;
+        h.f16_xs = m->h_xs;
+        h.f16_hs = m->h_hs;
+        h.f16_scale = std::ldexp(1.0f, kH2S);
+        h.f16_unscale = std::ldexp(1.0f, -kH2S);
+        h.fb_tile_req = (uint32_t*)fbp;
+        h.fb_tile_item0 = h.fb_tile_req + max_tiles;
+        h.fb_tile_cnt = h.fb_tile_req + 2 * (size_t)max_tiles;
+        h.fb_n_tiles = h.fb_tile_req + 3 * (size_t)max_tiles;
+        h.f16_stats = m->h_stats;
+        PG_HIP(hipMemsetAsync(h.fb_n_tiles, 0, 4, ctx->stream));
+        if ((rc = launch_dnn3_h2(ctx, m->h1, m->h2, m->f16_nprod, h))) return rc;
+        // the marked tiles again, in split bf16: the list's length stays on the device (zero tiles return at once)
+        a.tile_req = h.fb_tile_req;
+        a.tile_item0 = h.fb_tile_item0;
+        a.tile_cnt = h.fb_tile_cnt;
+        a.n_tiles = h.fb_n_tiles;
+        if ((rc = launch_dnn3_x3(ctx, m->h1, m->h2, a))) return rc;
     } else if (x3_k) {
         if ((rc = launch_dnn3_x3(ctx, m->h1, m->h2, a))) return rc;
     } else if ((rc = dispatch_dnn3_mlp(ctx, m, a, grid128))) {
@@ -1334,13 +1444,23 @@ extern "C" {
 int pg_model_load(pg_ctx* ctx, pg_model_kind kind, pg_prec prec, const void* blob, size_t len,
                   pg_model** out) {
     PG_REQUIRE(ctx && blob && out, "pg_model_load: NULL argument");
-    PG_REQUIRE(prec == PG_PREC_F32 || prec == PG_PREC_BF16 || prec == PG_PREC_BF16X3, "pg_model_load: bad precision %d", (int)prec);
+    PG_REQUIRE(prec == PG_PREC_F32 || prec == PG_PREC_BF16 || prec == PG_PREC_BF16X3 || prec == PG_PREC_F16X2 || prec == PG_PREC_F16,
+               "pg_model_load: bad precision %d", (int)prec);
+    const int f16_nprod = prec == PG_PREC_F16X2 ? 2 : (prec == PG_PREC_F16 ? 1 : 0);
+    if (f16_nprod && kind == PG_MODEL_FM_TWOTOWER) {
+        pg::set_error("pg_model_load: PG_PREC_F16X2 / PG_PREC_F16 serve PG_MODEL_DNN3 and PG_MODEL_DNN3_MULTI; load a "
+                      "PG_MODEL_FM_TWOTOWER in PG_PREC_BF16X3");
+        return PG_ERR_UNSUPPORTED;
+    }
     std::lock_guard<std::mutex> g(ctx->mu);
     PG_HIP(hipSetDevice(ctx->device));
     const uint8_t* p = (const uint8_t*)blob;
     pg_model* m = new pg_model();
     m->kind = kind;
-    m->prec = (int)prec;
+    // an fp16 mode is the split-bf16 model (its whole-call and per-tile fallback) plus the fp16 operands
+    m->prec = f16_nprod ? (int)PG_PREC_BF16X3 : (int)prec;
+    m->f16_nprod = f16_nprod;
+    m->ctx = ctx;
     int rc = PG_OK;
     auto fail = [&](int code) {
         for (void* a : m->allocs) hipFree(a);
@@ -1394,6 +1514,26 @@ int pg_model_load(pg_ctx* ctx, pg_model_kind kind, pg_prec prec, const void* blo
         if ((rc = pg::upload(ctx, m, b2, m->h2 * 4, (void**)&m->b2))) return fail(rc);
         if ((rc = pg::upload(ctx, m, w3t.data(), w3t.size() * 4, (void**)&m->w3))) return fail(rc);
         if ((rc = pg::upload(ctx, m, b3, m->n_out * 4, (void**)&m->b3v))) return fail(rc);
+        if (f16_nprod) {
+            std::vector<uint8_t> hw1, hw2;
+            std::vector<float> xs, hs;
+            const unsigned long long zeros[2] = {0, 0};
+            for (size_t i = 0; i < (len - hb) / 4; ++i)
+                if (!std::isfinite(w1[i])) {
+                    pg::set_error("pg_model_load: the blob holds a non-finite weight (float %zu): not representable in an fp16 mode", i);
+                    return fail(PG_ERR_UNSUPPORTED);
+                }
+            if ((rc = pg::build_f16_operands(w1i.data(), w2, m->h1, m->h2, f16_nprod, &hw1, &hw2, &xs, &hs))) return fail(rc);
+            if ((rc = pg::upload(ctx, m, hw1.data(), hw1.size(), &m->h_w1p))) return fail(rc);
+            if ((rc = pg::upload(ctx, m, hw2.data(), hw2.size(), &m->h_w2p))) return fail(rc);
+            if (f16_nprod == 2) {
+                m->h_w1p_lo = (char*)m->h_w1p + hw1.size() / 2;
+                m->h_w2p_lo = (char*)m->h_w2p + hw2.size() / 2;
+            }
+            if ((rc = pg::upload(ctx, m, xs.data(), xs.size() * 4, (void**)&m->h_xs))) return fail(rc);
+            if ((rc = pg::upload(ctx, m, hs.data(), hs.size() * 4, (void**)&m->h_hs))) return fail(rc);
+            if ((rc = pg::upload(ctx, m, zeros, sizeof zeros, (void**)&m->h_stats))) return fail(rc);
+        }
     } else if (kind == PG_MODEL_FM_TWOTOWER) {
         if (len < 32) { pg::set_error("pg_model_load: blob too short"); return fail(PG_ERR_INVALID); }
         uint32_t hdr[7];
@@ -1458,6 +1598,23 @@ int pg_model_load(pg_ctx* ctx, pg_model_kind kind, pg_prec prec, const void* blo
 int pg_model_num_outputs(const pg_model* m, uint32_t* out) {
     PG_REQUIRE(m && out, "pg_model_num_outputs: NULL argument");
     *out = m->n_out;
+    return PG_OK;
+}
+
+int pg_model_f16_stats(const pg_model* m, uint64_t out[4]) {
+    PG_REQUIRE(m && out, "pg_model_f16_stats: NULL argument");
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (!m->f16_nprod) return PG_OK;
+    pg_ctx* ctx = m->ctx;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    PG_HIP(hipSetDevice(ctx->device));
+    unsigned long long dev[2] = {0, 0};
+    PG_HIP(hipMemcpyAsync(dev, m->h_stats, sizeof dev, hipMemcpyDeviceToHost, ctx->stream));
+    PG_HIP(hipStreamSynchronize(ctx->stream));
+    out[0] = m->f16_calls;
+    out[1] = dev[0];
+    out[2] = dev[1];
+    out[3] = m->f16_calls_whole;
     return PG_OK;
 }
 

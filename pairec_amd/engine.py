@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _lib
 
-PREC_F32, PREC_BF16, PREC_BF16X3 = 0, 1, 2
+PREC_F32, PREC_BF16, PREC_BF16X3, PREC_F16X2, PREC_F16 = 0, 1, 2, 3, 4
 MODEL_DNN3, MODEL_FM_TWOTOWER, MODEL_DNN3_MULTI = 1, 2, 3
 MAX_QUERIES = 256         # per table pass (32 when dim > 128)
 
@@ -525,6 +525,14 @@ class RankModel:
         if self.h:
             _lib.check(self.ctx.L.pg_model_destroy(self.ctx.h, self.h))
             self.h = None
+
+    def f16_stats(self) -> dict:
+        """PREC_F16X2 / PREC_F16: how much of the model's work the fp16 kernel took and how much went back to BF16X3
+        (waits for the context to drain)."""
+        out = (C.c_uint64 * 4)()
+        _lib.check(self.ctx.L.pg_model_f16_stats(self.h, out))
+        return {"calls": int(out[0]), "tiles": int(out[1]), "tiles_served_bf16x3": int(out[2]),
+                "calls_served_bf16x3_whole": int(out[3])}
 
     def rank_dnn3(self, table: Table, user_vecs: np.ndarray, cand_rows: np.ndarray,
                   req_offsets: Sequence[int]) -> np.ndarray:

@@ -1881,11 +1881,13 @@ Engine* Engine::Create(const std::string& config_json, std::string* err) {
         const std::string name = a.s("Name"), kind = a.s("Kind");
         if (a.has("Precision")) {
             // the rank model's matrix layers: "f32" (bit-defined), "bf16" (fastest), "bf16x3" (split bf16: the fp32 scores of
-            // the reference's model servers — eas/easyrec_response.go:479-483 — at matrix-pipe speed)
+            // the reference's model servers — eas/easyrec_response.go:479-483 — at matrix-pipe speed), "f16x2" / "f16" (dnn3 only: the same 1e-5 of the fp32 scores on scaled fp16 operands,
+            // out-of-range tiles re-served in bf16x3)
             const std::string pr = a.s("Precision");
-            const int pv = pr == "f32" ? PG_PREC_F32 : pr == "bf16" ? PG_PREC_BF16 : pr == "bf16x3" ? PG_PREC_BF16X3 : -1;
+            const int pv = pr == "f32" ? PG_PREC_F32 : pr == "bf16" ? PG_PREC_BF16 : pr == "bf16x3" ? PG_PREC_BF16X3
+                           : pr == "f16x2" ? PG_PREC_F16X2 : pr == "f16" ? PG_PREC_F16 : -1;
             if (pv < 0) {
-                if (err) *err = "pairec_gpu.Algorithms: " + name + ": Precision \"" + pr + "\" (f32, bf16 or bf16x3)";
+                if (err) *err = "pairec_gpu.Algorithms: " + name + ": Precision \"" + pr + "\" (f32, bf16, bf16x3, f16x2 or f16)";
                 return nullptr;
             }
             e->algo_precision[name] = pv;

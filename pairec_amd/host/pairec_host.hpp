@@ -441,7 +441,7 @@ public:
     pg_table* table = nullptr;
     pg_model* model = nullptr;
     std::map<std::string, pg_model*> named_models;      // multi-output rank algorithms: "<algo>/<output>" → DNN3 model
-    // pairec_gpu.Algorithms[].Precision ("f32" | "bf16" | "bf16x3", default bf16): what a loader passing prec < 0 gets
+    // pairec_gpu.Algorithms[].Precision ("f32" | "bf16" | "bf16x3" | "f16x2" | "f16", default bf16): what a loader passing prec < 0 gets
     std::map<std::string, int> algo_precision;
     int default_dnn_precision = PG_PREC_BF16, default_fm2t_precision = PG_PREC_BF16;
     int PrecisionOf(const std::string& algo, int fallback) const {
