@@ -206,7 +206,7 @@ struct pg_model {
     void* w2p_lo = nullptr;
     // PG_PREC_F16X2 / PG_PREC_F16: prec is 2 (every BF16X3 buffer above is kept: the fallback) and f16_nprod 2 / 1
     int f16_nprod = 0;
-    void* h_w1p = nullptr;  // scaled fp16 fragments (rank_h2.hip); the lo planes inside the same allocations
+    void* h_w1p = nullptr;  // scaled fp16 fragments (rank_2r.hip); the lo planes inside the same allocations
     void* h_w2p = nullptr;
     void* h_w1p_lo = nullptr;
     void* h_w2p_lo = nullptr;

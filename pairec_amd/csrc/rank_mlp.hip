@@ -941,7 +941,7 @@ static std::vector<uint8_t> pack_weights(const float* w, uint32_t K, uint32_t N,
     return out;
 }
 
-// PG_PREC_F16X2 / PG_PREC_F16 (rank_h2.hip): the bf16 fragment layout in fp16 — every hi fragment (RNE), then, with two
+// PG_PREC_F16X2 / PG_PREC_F16 (rank_2r.hip): the bf16 fragment layout in fp16 — every hi fragment (RNE), then, with two
 // products per term, every lo fragment (lo = RNE(w - hi))
 static std::vector<uint8_t> pack_weights_f16(const float* w, uint32_t K, uint32_t N, int nprod) {
     const uint32_t kg = K / 16;
@@ -977,7 +977,7 @@ static bool row_exponent(const float* row, size_t n, int* e) {
 }
 static bool f32_normal_or_zero(float v) { return v == 0.0f || std::isnormal(v); }
 
-// The fp16 modes' operands (the scaling rule is in rank_h2.hip's header): W1's item half [kDIN][h1] and W2 [h1][h2] scaled
+// The fp16 modes' operands (the scaling rule is in rank_2r.hip's header): W1's item half [kDIN][h1] and W2 [h1][h2] scaled
 // per row, the activations' factors beside them.  PG_ERR_UNSUPPORTED for weights the rule cannot carry.
 static int build_f16_operands(const float* w1i, const float* w2, uint32_t h1, uint32_t h2, int nprod,
                               std::vector<uint8_t>* w1p, std::vector<uint8_t>* w2p, std::vector<float>* xs,
@@ -1077,7 +1077,7 @@ static int launch_dnn3_mlp(pg_ctx* ctx, const MlpArgs& a, uint32_t grid) {
         if ((rc = ensure_dyn_lds(ctx, (const void*)mlp_kernel<1, H1, H2, true, 2, 2, 1, 64, 2, OCC>, lds))) return rc;
         mlp_kernel<1, H1, H2, true, 2, 2, 1, 64, 2, OCC><<<grid, 256, lds, ctx->stream>>>(a);
     } else if constexpr (PREC == 2) {
-        // split bf16, the general form (the benchmark's shape has a kernel of its own, rank_x3.hip): the bf16 tiling with
+        // split bf16, the general form (the benchmark's shape has a kernel of its own, rank_2r.hip): the bf16 tiling with
         // a hi and a lo operand tile, one workgroup per CU's worth of registers
         constexpr size_t lds = mlp_lds_bytes(2, H2, 64, 2);
         if ((rc = ensure_dyn_lds(ctx, (const void*)mlp_kernel<2, H1, H2, true, 2, 2, 1, 64, 2, 1>, lds))) return rc;
@@ -1182,9 +1182,9 @@ int rank_dnn3_dev_locked(pg_ctx* ctx, const pg_model* m, const pg_table* t,
     // the small shapes, gather-bound: the whole model in registers (rank_rs.hip)
     const bool rs_k = m->prec == 1 && !no_ws && t->dim == 128 && dnn3_rs_shape(m->h1, m->h2);
     const bool ls_k = m->prec == 1 && !no_ws && t->dim == 128 && dnn3_ls_shape(m->h1, m->h2);
-    // split bf16: the two-role kernel (rank_x3.hip), 128-item tiles; 1024-512 and 64-wide tables take the general form
+    // split bf16: the two-role kernel (rank_2r.hip), 128-item tiles; 1024-512 and 64-wide tables take the general form
     const bool x3_k = m->prec == 2 && !no_ws && t->dim == 128 && dnn3_x3_shape(m->h1, m->h2);
-    // the fp16 modes: rank_h2.hip where the two-role kernel would run, its out-of-range tiles re-served by that kernel;
+    // the fp16 modes: rank_2r.hip where the two-role kernel would run, its out-of-range tiles re-served by that kernel;
     // every other call whole on the split-bf16 path (the model's prec is 2)
     const bool h2_k = m->f16_nprod && x3_k;
     if (m->f16_nprod) {

@@ -106,7 +106,7 @@ struct MlpArgs {
     const void* w1p_lo;
     const void* w2p_lo;
     float* out;
-    // PG_PREC_F16X2 / PG_PREC_F16 (rank_h2.hip): w1p / w2p (and the lo pointers) are then the scaled fp16 fragments
+    // PG_PREC_F16X2 / PG_PREC_F16 (rank_2r.hip): w1p / w2p (and the lo pointers) are then the scaled fp16 fragments
     const float* f16_xs;             // [kDIN] 2^(E_k + G): factor of input column k in front of the fp16 convert
     const float* f16_hs;             // [h1]   2^(F_i + G - S): factor of hidden unit i
     float f16_scale, f16_unscale;    // 2^S, 2^-S
@@ -191,12 +191,13 @@ int launch_dnn3_rs(pg_ctx* ctx, uint32_t h1, uint32_t h2, const MlpArgs& a);
 bool dnn3_ls_shape(uint32_t h1, uint32_t h2);
 int launch_dnn3_ls(pg_ctx* ctx, uint32_t h1, uint32_t h2, const MlpArgs& a);
 
-// rank_x3.hip: DNN3 in PG_PREC_BF16X3 (split bf16) — 128-item tiles, layer-1 and layer-2 waves sharing each SIMD
+// rank_2r.hip, the two-role kernel: DNN3 in PG_PREC_BF16X3 (split bf16) — 128-item tiles, layer-1 and layer-2 waves sharing
+// each SIMD
 bool dnn3_x3_shape(uint32_t h1, uint32_t h2);
 int launch_dnn3_x3(pg_ctx* ctx, uint32_t h1, uint32_t h2, const MlpArgs& a);
 
-// rank_h2.hip: DNN3 in PG_PREC_F16X2 / PG_PREC_F16 (nprod 2 / 1) — rank_x3.hip's structure on the fp16 MFMA, operands scaled
-// by exact powers of two, out-of-range tiles listed for the BF16X3 kernel; same shapes as dnn3_x3_shape
+// ... and in PG_PREC_F16X2 / PG_PREC_F16 (nprod 2 / 1) — the same body on the fp16 MFMA, operands scaled by exact powers of
+// two, out-of-range tiles listed for the BF16X3 kernel; same shapes as dnn3_x3_shape
 constexpr int kH2G = 11;       // activations: 2^G on top of the row normalisation
 constexpr int kH2S = 23;       // accumulators hold 2^S x the pre-activation; weights carry 2^(S - G)
 int launch_dnn3_h2(pg_ctx* ctx, uint32_t h1, uint32_t h2, int nprod, const MlpArgs& a);

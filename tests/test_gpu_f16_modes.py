@@ -1,4 +1,4 @@
-"""GPU tests of PG_PREC_F16X2 / PG_PREC_F16 (pairec_amd/csrc/rank_h2.hip): the DNN3 matrix layers on the fp16 MFMA with
+"""GPU tests of PG_PREC_F16X2 / PG_PREC_F16 (pairec_amd/csrc/rank_2r.hip): the DNN3 matrix layers on the fp16 MFMA with
 operands scaled by exact powers of two, against the FP32 oracle (prec = 0, nothing mirrored).
 
 Bars: |score - fp32 oracle| <= 1e-5 (north_star), and, as a regression bar, <= 2 x the mode's emulated error
@@ -245,7 +245,7 @@ def test_calls_outside_the_kernel_are_served_whole_by_the_bf16x3_path(ctx, world
 
 
 def test_recommend_step_and_coalescer_inherit_the_mode(ctx):
-    """pg_recommend_dnn3 and a coalescer rank call reach rank_h2.hip through the same entry: the direct call's bits"""
+    """pg_recommend_dnn3 and a coalescer rank call reach rank_2r.hip through the same entry: the direct call's bits"""
     n, R, K = 300_000, 3, 200
     t = pa.Table(ctx, n, 128)
     t.fill_synthetic(o.SEED_TABLE)
