@@ -111,7 +111,8 @@ int pg_synchronize(pg_ctx* ctx);
  * current searches that index, synchronously); for pg_index_refresh "index_refresh_full_fraction" (default 0.1: in auto mode
  * more written rows than this share of the table are refreshed in full; a table's write log is dropped past it too); for
  * coalescers created afterwards "coalescer_max_exclude" (default 0, 0..4096: the longest list pg_coalescer_recall_exclude takes;
- * a value outside the range is PG_ERR_INVALID).
+ * a value outside the range is PG_ERR_INVALID); for pg_cf_recall "cf_lds_max_pairs" (default and largest value 6144: a request
+ * of at most this many (trigger, neighbour) pairs keeps its table in LDS, a larger one in global memory; 0 = always global).
  * value is parsed as a number. */
 int pg_set_option(pg_ctx* ctx, const char* name, const char* value);
 int pg_device_malloc(pg_ctx* ctx, size_t bytes, void** out);
@@ -652,6 +653,68 @@ int pg_recall_topk_exclude_dev(pg_ctx* ctx, const pg_table* t, const float* d_qu
 int pg_i2i_recall_exclude(pg_ctx* ctx, const pg_table* trigger_table, const uint32_t* trigger_rows, uint32_t n, const pg_table* t,
                           uint32_t k, int exclude_trigger, const uint64_t* excl_rows, const uint32_t* excl_offsets,
                           uint64_t* out_rows, float* out_scores, uint32_t* out_count);
+
+/* Collaborative-filter recall (U2I2I) over a similarity table resident in HBM (csrc/cf.hip).
+ * UserCollaborativeFilterRecall.GetCandidateItems (service/recall/user_collaborative_filter_recall.go:31-80) reads the user's
+ * trigger items with their preference scores, expands them into their similar-item lists (swing / etrec) with four goroutines
+ * of SELECT ... WHERE item_id IN (...) under a 200 ms timeout (module/user_collaborative_hologres_dao.go:58-216), multiplies
+ * every similarity by the trigger's preference (:179-192), sums the products per distinct item in float64
+ * (module/user_collaborative_dao.go:38-51), divides by the largest sum unless Normalization is "off" (:61-68), sorts
+ * descending and cuts to RecallCount.  ItemCollaborativeFilterRecall (service/recall/item_collaborative_filter_recall.go:40-90)
+ * is the one-trigger case with prefer = 1 and normalize = 0.  RealTimeU2IRecall's trigger-weight expression stays on the host:
+ * its output is this call's (trigger_rows, trigger_prefer).
+ *   Table     CSR over the LOCAL rows of an item table `t`: offsets uint64[rows + 1], neighbours uint32[pairs] (local rows of
+ *             `t`), similarities float[pairs].  The reference parses similarities from text as float64; here they are stored
+ *             fp32, like every table of this engine, and widened exactly when used.  `t` must outlive the similarity table,
+ *             must not be a view, and holds at most 2^32 - 1 rows.  A table whose rows were never uploaded has empty lists.
+ *   upload    pg_simtable_upload appends the lists of `nrows` consecutive rows from row0; rows arrive in ascending order (row0
+ *             at or behind the end of the previous upload; rows skipped keep empty lists); offsets[nrows + 1] are relative to
+ *             the call's nbr_rows / sims.  PG_ERR_INVALID, the table left as it was, for a list longer than 1024, a neighbour
+ *             >= rows, a non-finite similarity, or a neighbour that appears twice in one list (duplicate-free lists are what
+ *             makes the sums deterministic without floating-point atomics).  Synchronous; recalls of other contexts wait.
+ *   stale     the table records t's generation at create: after pg_table_swap (or any other write) of `t` a recall returns
+ *             PG_ERR_INVALID with a message that names both generations — there is nothing to fall back to.
+ *   recall    request q's triggers are trigger_rows / trigger_prefer [trigger_offsets[q] .. trigger_offsets[q + 1]) (local rows
+ *             of `t`; at most 256 per request, nq <= 256, 1 <= k <= 16384; else PG_ERR_UNSUPPORTED / PG_ERR_INVALID as the
+ *             vector recalls).  The answer is DEFINED, bit for bit:
+ *               - triggers j in the order given, within a trigger the list's entries e in stored order;
+ *                 term = (double)sim_e * prefer_j (one rounding); the first term of an item IS its score, every later one is
+ *                 score = score + term — the order a single goroutine of the reference would take;
+ *               - a trigger row of UINT32_MAX or >= rows contributes nothing (an id the reference's SQL does not return); a
+ *                 trigger that occurs twice contributes twice; trigger items are not removed from the answer;
+ *               - m = the largest score, found with > from 0; with normalize != 0 and m > 0 every score becomes score / m;
+ *               - order: score descending, then local row ascending (-0.0 ranks as 0.0); out_rows are global ids (row_offset +
+ *                 local row), the first k of that order; slots past the distinct count carry UINT64_MAX and -inf;
+ *                 out_count[q] = the valid count; a request without triggers answers 0.
+ *             trigger_prefer must be finite: pg_cf_recall checks it (PG_ERR_INVALID), for pg_cf_recall_dev it is a
+ *             precondition.  A request whose lists hold more than 65536 pairs in all is never cut: the call returns
+ *             PG_ERR_UNSUPPORTED and names the request (the other requests' outputs are written).
+ *   opts      NULL = {1, NULL, NULL}.  normalize: the reference's default ("on" unless "off", recconf.go:579).  excl_rows /
+ *             excl_offsets: per-request exclusion lists with the meaning, limits and errors they have in
+ *             pg_recall_topk_exclude (global ids, at most 4096 per request, k + the longest list <= 16384): the answer is the
+ *             first k entries of the same order that are not in the request's list.
+ *   _dev      trigger_rows, trigger_prefer, opts->excl_rows and the outputs are device memory; both offset arrays and
+ *             out_count (optional) are host memory.  Both forms return synchronised.
+ *   Memory    scratch of about 40 B x min(65536, rows) per request of the batch (the global tier's tables and the items to
+ *             order: 0.7 GB for 256 requests on a table of >= 65536 rows), kept by the context. */
+typedef struct pg_simtable pg_simtable;
+typedef struct {
+    int normalize;                 /* != 0: divide by the largest score when it is positive */
+    const uint64_t* excl_rows;     /* with excl_offsets: per-request exclusion lists; both NULL = none */
+    const uint32_t* excl_offsets;  /* host [nq + 1] */
+} pg_cf_opts;
+int pg_simtable_create(pg_ctx* ctx, const pg_table* t, pg_simtable** out);
+int pg_simtable_upload(pg_ctx* ctx, pg_simtable* s, uint64_t row0, uint64_t nrows, const uint64_t* offsets, const uint32_t* nbr_rows,
+                       const float* sims);
+/* any of the outputs may be NULL; generation = the item table's generation the lists belong to */
+int pg_simtable_info(const pg_simtable* s, uint64_t* rows, uint64_t* pairs, uint64_t* rows_uploaded, uint64_t* generation);
+int pg_simtable_destroy(pg_ctx* ctx, pg_simtable* s);
+int pg_cf_recall(pg_ctx* ctx, const pg_simtable* s, const uint32_t* trigger_rows, const double* trigger_prefer,
+                 const uint32_t* trigger_offsets, uint32_t nq, uint32_t k, const pg_cf_opts* opts, uint64_t* out_rows, double* out_scores,
+                 uint32_t* out_count);
+int pg_cf_recall_dev(pg_ctx* ctx, const pg_simtable* s, const uint32_t* d_trigger_rows, const double* d_trigger_prefer,
+                     const uint32_t* trigger_offsets, uint32_t nq, uint32_t k, const pg_cf_opts* opts, uint64_t* d_out_rows,
+                     double* d_out_scores, uint32_t* out_count);
 
 /* Refresh: bring an existing index back to its table's current rows KEEPING ITS CENTROIDS — cheap when few
  * rows were written, several times cheaper than pg_index_build when all of them were (nothing is trained).  Nothing changes

@@ -46,6 +46,7 @@ EXPORTS = [
     "pg_recall_topk_where_ex", "pg_index_recall_topk_where_ex", "pg_table_view_create_ex", "pg_where_bits", "pg_where_stats",
     "pg_exclude_compact_dev", "pg_recall_topk_exclude", "pg_recall_topk_exclude_dev", "pg_i2i_recall_exclude",
     "pg_coalescer_recall_exclude",
+    "pg_simtable_create", "pg_simtable_upload", "pg_simtable_info", "pg_simtable_destroy", "pg_cf_recall", "pg_cf_recall_dev",
 ]
 
 
@@ -91,6 +92,10 @@ class PgIndexWhereStats(C.Structure):
 
 class PgRecallExcludeOpts(C.Structure):
     _fields_ = [("metric", C.c_int), ("fs", C.c_void_p), ("where", C.c_void_p)]
+
+
+class PgCfOpts(C.Structure):
+    _fields_ = [("normalize", C.c_int), ("excl_rows", C.c_void_p), ("excl_offsets", C.c_void_p)]
 
 
 class PgIndexRefreshParams(C.Structure):
@@ -207,6 +212,12 @@ def load():
         "pg_recall_topk_exclude_dev": [vp, vp, vp, u32, u32, vp, vp, P(PgRecallExcludeOpts), vp, vp, vp],
         "pg_i2i_recall_exclude": [vp, vp, vp, u32, vp, u32, i32, vp, vp, vp, vp, vp],
         "pg_coalescer_recall_exclude": [vp, vp, vp, u32, vp, vp, P(u32)],
+        "pg_simtable_create": [vp, vp, P(vp)],
+        "pg_simtable_upload": [vp, vp, u64, u64, vp, vp, vp],
+        "pg_simtable_info": [vp, P(u64), P(u64), P(u64), P(u64)],
+        "pg_simtable_destroy": [vp, vp],
+        "pg_cf_recall": [vp, vp, vp, vp, vp, u32, u32, P(PgCfOpts), vp, vp, vp],
+        "pg_cf_recall_dev": [vp, vp, vp, vp, vp, u32, u32, P(PgCfOpts), vp, vp, vp],
         "pg_index_refresh": [vp, vp, P(PgIndexRefreshParams)],
         "pg_index_refresh_stats": [vp, P(PgIndexRefreshStats)],
         "pg_index_screen_probe": [vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, vp, vp],

@@ -1,0 +1,649 @@
+// cf.hip — collaborative-filter recall (U2I2I) over an HBM similarity table.
+//
+// UserCollaborativeFilterRecall (service/recall/user_collaborative_filter_recall.go:31-80) expands a user's trigger items into
+// their similar-item lists (module/user_collaborative_hologres_dao.go:58-216: four goroutines of SELECT ... WHERE item_id IN),
+// multiplies every similarity by the trigger's preference (:179-192), sums the products per distinct item in float64
+// (module/user_collaborative_dao.go:38-51), optionally divides by the largest sum (:61-65), sorts descending and cuts to
+// RecallCount.  Here the lists are CSR over the local rows of an item table and one workgroup serves one request: a sparse
+// gather, a keyed fp64 reduction in an open-addressed table, and an ordered cut.
+//
+// Storage: offsets uint64[rows + 1], neighbours uint32[pairs] (local rows of the item table), similarities float[pairs].  The
+// reference parses similarities from text as float64; here they are stored fp32, like every table of this engine, and widened
+// exactly when used (term = (double)sim * prefer: one rounding).
+//
+// Determinism without floating-point atomics: triggers are processed one after the other with a barrier between them, a
+// trigger's list is spread over the lanes, and a list holds no neighbour twice (pg_simtable_upload refuses it), so no two
+// lanes of one trigger touch one slot.  Every item's additions happen in trigger order with a plain read-modify-write; only
+// the slot's uint32 key is claimed by compare-and-swap.
+#include "common.hpp"
+
+#include <cmath>
+
+struct pg_simtable {
+    // recalls share this lock, pg_simtable_upload takes it exclusively.  Lock order: ctx->mu, the item table, then this.
+    mutable std::shared_mutex rw;
+    const pg_table* t = nullptr;
+    uint64_t gen = 0;              // t->generation at create: a recall on another generation is refused
+    uint64_t rows = 0;
+    uint64_t* d_off = nullptr;     // [rows + 1]
+    uint32_t* d_nbr = nullptr;     // [cap], pairs used
+    float* d_sim = nullptr;
+    uint64_t pairs = 0, cap = 0;
+    uint64_t rows_uploaded = 0;    // the next upload starts at or behind this row
+};
+
+namespace pg {
+namespace {
+
+constexpr uint32_t kCfThreads = 1024;            // one workgroup per request; a list of at most kCfMaxList entries is one entry per lane
+constexpr uint32_t kCfMaxTriggers = 256;
+constexpr uint32_t kCfMaxList = 1024;
+constexpr uint32_t kCfMaxPairs = 65536;          // a request beyond it is reported, never cut
+// LDS tier: 12288 slots of (fp64 accumulator, uint32 key) in two planes = 144 KiB; load factor <= 0.5 serves 6144 pairs.  The
+// planes keep the 8-byte accumulators of neighbouring slots on neighbouring bank pairs and the keys' probes (4-byte reads,
+// 32-bank modulus) apart from them; a 16-byte record per slot would hold a third less.
+constexpr uint32_t kCfLdsSlots = 12288;
+constexpr uint32_t kCfLdsMaxPairs = kCfLdsSlots / 2;
+constexpr uint32_t kCfSortChunk = 8192;          // 16-byte sort records ordered in LDS at a time (128 KiB, the table's bytes reused)
+constexpr size_t kCfTableBytes = (size_t)kCfLdsSlots * 12;
+static_assert((size_t)kCfSortChunk * 16 <= kCfTableBytes, "the sort reuses the table's LDS");
+constexpr size_t kCfLds = kCfTableBytes + kCfMaxTriggers * (8 + 8 + 4) + 64;
+static_assert(kCfLds <= 160 * 1024, "one workgroup's LDS");
+constexpr uint32_t kCfEmpty = 0xFFFFFFFFu;       // never a neighbour: neighbours are < rows <= UINT32_MAX
+constexpr uint32_t kCfMaxDepth = 16384;
+
+struct CfArgs {
+    const uint64_t* off;
+    const uint32_t* nbr;
+    const float* sim;
+    uint32_t rows;
+    uint64_t row_offset;
+    const uint32_t* trig;
+    const double* pref;
+    const uint32_t* trig_off;      // [nq + 1]
+    uint32_t lds_max_pairs;
+    uint32_t gslots;               // slots of one request's slice of the global tables (a power of two >= 2 min(65536, rows))
+    uint32_t* gkeys;               // [nq][gslots]
+    double* gacc;
+    ulonglong2* cand;              // [nq][cand_cap] compacted items, then sort records
+    uint32_t cand_cap;             // a power of two >= min(65536, rows)
+    int normalize;
+    uint32_t kd;                   // output depth
+    uint64_t* out_rows;            // [nq][kd]
+    double* out_scores;
+    float* out_idx;                // [nq][kd] or NULL: slot j's own index as bits (the plane pg_exclude_compact_dev carries)
+    uint32_t* out_count;           // [nq]
+    uint32_t* status;              // the smallest request beyond kCfMaxPairs (UINT32_MAX: none)
+};
+
+// (the multiplicative hash of exclude.hip on 32-bit rows, scaled to any slot count: rows that share their low bits, or are
+// multiples of the slot count, spread over the table)
+__device__ inline uint32_t cf_slot(uint32_t row, uint32_t slots) {
+    return (uint32_t)(((uint64_t)(row * 0x9E3779B1u) * slots) >> 32);
+}
+
+__device__ inline bool cf_less(const ulonglong2& a, const ulonglong2& b) { return a.x < b.x || (a.x == b.x && a.y < b.y); }
+
+// The accumulation over one request's staged triggers and the compaction of its occupied slots into cand[0 .. *n_items), in
+// no particular order (the order is made by the sort); *max_bits = the largest positive score's bits.  One body for both
+// tiers: keys / acc are LDS or the request's slice of the global tables, `slots` a multiple of kCfThreads.
+template <bool kLds>
+__device__ void cf_accumulate(const CfArgs& a, uint32_t* keys, double* acc, uint32_t slots, uint32_t nt, const uint64_t* tb_begin,
+                              const double* tb_pref, const uint32_t* tb_len, ulonglong2* cand, uint32_t* n_items,
+                              unsigned long long* max_bits) {
+    const uint32_t tid = threadIdx.x;
+    for (uint32_t i = tid; i < slots; i += kCfThreads) keys[i] = kCfEmpty;
+    // the next trigger's list is loaded while the current one is accumulated
+    uint32_t nb_next = kCfEmpty;
+    float sm_next = 0.0f;
+    if (nt && tid < tb_len[0]) {
+        nb_next = a.nbr[tb_begin[0] + tid];
+        sm_next = a.sim[tb_begin[0] + tid];
+    }
+    __syncthreads();
+    for (uint32_t j = 0; j < nt; ++j) {
+        uint32_t nb = nb_next;
+        float sm = sm_next;
+        const uint32_t len = tb_len[j];
+        const uint64_t begin = tb_begin[j];
+        const double pf = tb_pref[j];
+        if (j + 1 < nt && tid < tb_len[j + 1]) {
+            nb_next = a.nbr[tb_begin[j + 1] + tid];
+            sm_next = a.sim[tb_begin[j + 1] + tid];
+        }
+        for (uint32_t i = tid; i < len; i += kCfThreads) {
+            if (i != tid) {                              // (lists are at most kCfThreads long: never taken for an uploaded table)
+                nb = a.nbr[begin + i];
+                sm = a.sim[begin + i];
+            }
+            if (nb >= a.rows) continue;
+            const double term = (double)sm * pf;
+            for (uint32_t h = cf_slot(nb, slots);; h = h + 1 == slots ? 0 : h + 1) {
+                uint32_t cur = __hip_atomic_load(&keys[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                bool mine = false;
+                if (cur == kCfEmpty) {
+                    cur = atomicCAS(&keys[h], kCfEmpty, nb);
+                    mine = cur == kCfEmpty;
+                }
+                if (mine) {
+                    acc[h] = term;                       // the first term of an item IS its score
+                    break;
+                }
+                if (cur == nb) {
+                    acc[h] = acc[h] + term;
+                    break;
+                }
+            }
+        }
+        __syncthreads();                                 // trigger j's additions are done, and visible, before trigger j + 1's
+    }
+    double lmax = 0.0;
+    for (uint32_t i = tid; i < slots; i += kCfThreads) {
+        const uint32_t key = keys[i];
+        const bool occ = key != kCfEmpty;
+        const unsigned long long m = __ballot(occ);
+        if (m == 0) continue;
+        const uint32_t before = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+        const int leader = __ffsll((long long)m) - 1;
+        uint32_t base = 0;
+        if (occ && before == 0) base = atomicAdd(n_items, (uint32_t)__popcll(m));
+        base = __shfl(base, leader);
+        if (occ) {
+            const double sc = acc[i];
+            if (sc > lmax) lmax = sc;
+            const uint32_t pos = base + before;
+            if (pos < a.cand_cap) cand[pos] = make_ulonglong2((unsigned long long)__double_as_longlong(sc), key);
+        }
+    }
+    for (int d = kWave / 2; d > 0; d >>= 1) {
+        const double o = __shfl_xor(lmax, d);
+        if (o > lmax) lmax = o;
+    }
+    // (positive doubles order as their bits)
+    if ((tid & (kWave - 1)) == 0 && lmax > 0.0) atomicMax(max_bits, (unsigned long long)__double_as_longlong(lmax));
+    __syncthreads();
+}
+
+// g[base .. base + n) through LDS: the bitonic network's steps of the merges k_lo .. k_hi whose partner distance is below n
+// (n a power of two <= kCfSortChunk; directions follow the global index).
+__device__ void cf_sort_lds(ulonglong2* g, ulonglong2* s, uint32_t base, uint32_t n, uint32_t k_lo, uint32_t k_hi) {
+    const uint32_t tid = threadIdx.x;
+    for (uint32_t i = tid; i < n; i += kCfThreads) s[i] = g[base + i];
+    __syncthreads();
+    for (uint32_t k = k_lo; k <= k_hi && k; k <<= 1) {
+        for (uint32_t j = min(k >> 1, n >> 1); j > 0; j >>= 1) {
+            for (uint32_t p = tid; p < (n >> 1); p += kCfThreads) {
+                const uint32_t i = ((p & ~(j - 1)) << 1) | (p & (j - 1)), l = i | j;
+                const bool up = ((base + i) & k) == 0;
+                const ulonglong2 x = s[i], y = s[l];
+                if (cf_less(y, x) == up) {
+                    s[i] = y;
+                    s[l] = x;
+                }
+            }
+            __syncthreads();
+        }
+    }
+    for (uint32_t i = tid; i < n; i += kCfThreads) g[base + i] = s[i];
+    __syncthreads();
+}
+
+// ascending sort of g[0 .. n), n a power of two: chunks of kCfSortChunk in LDS, the wider steps in place
+__device__ void cf_sort(ulonglong2* g, ulonglong2* s, uint32_t n) {
+    const uint32_t tid = threadIdx.x;
+    if (n <= kCfSortChunk) {
+        cf_sort_lds(g, s, 0, n, 2, n);
+        return;
+    }
+    for (uint32_t base = 0; base < n; base += kCfSortChunk) cf_sort_lds(g, s, base, kCfSortChunk, 2, kCfSortChunk);
+    for (uint32_t k = kCfSortChunk << 1; k <= n; k <<= 1) {
+        for (uint32_t j = k >> 1; j >= kCfSortChunk; j >>= 1) {
+            for (uint32_t p = tid; p < (n >> 1); p += kCfThreads) {
+                const uint32_t i = ((p & ~(j - 1)) << 1) | (p & (j - 1)), l = i | j;
+                const bool up = (i & k) == 0;
+                const ulonglong2 x = g[i], y = g[l];
+                if (cf_less(y, x) == up) {
+                    g[i] = y;
+                    g[l] = x;
+                }
+            }
+            __syncthreads();
+        }
+        for (uint32_t base = 0; base < n; base += kCfSortChunk) cf_sort_lds(g, s, base, kCfSortChunk, k, k);
+    }
+}
+
+__device__ inline void cf_pad(const CfArgs& a, uint32_t q, uint32_t from) {
+    for (uint32_t j = from + threadIdx.x; j < a.kd; j += kCfThreads) {
+        const size_t o = (size_t)q * a.kd + j;
+        a.out_rows[o] = ~0ull;
+        a.out_scores[o] = -__builtin_inf();
+        if (a.out_idx) a.out_idx[o] = __uint_as_float(j);
+    }
+}
+
+// Request q = blockIdx.x.  trigger_prefer must be finite (the host entry point checks it).
+__global__ __launch_bounds__(kCfThreads) void cf_recall_kernel(CfArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char cf_lds[];
+    uint64_t* tb_begin = reinterpret_cast<uint64_t*>(cf_lds + kCfTableBytes);
+    double* tb_pref = reinterpret_cast<double*>(tb_begin + kCfMaxTriggers);
+    uint32_t* tb_len = reinterpret_cast<uint32_t*>(tb_pref + kCfMaxTriggers);
+    unsigned long long* max_bits = reinterpret_cast<unsigned long long*>(tb_len + kCfMaxTriggers);
+    uint32_t* n_pairs = reinterpret_cast<uint32_t*>(max_bits + 1);
+    uint32_t* n_items = n_pairs + 1;
+    const uint32_t q = blockIdx.x, tid = threadIdx.x;
+    const uint32_t t0 = a.trig_off[q];
+    const uint32_t nt = min(a.trig_off[q + 1] - t0, kCfMaxTriggers);
+    if (tid == 0) {
+        *max_bits = 0;
+        *n_pairs = 0;
+        *n_items = 0;
+    }
+    __syncthreads();
+    if (tid < nt) {
+        // a trigger of UINT32_MAX or >= rows contributes nothing: the id the reference's SQL does not return
+        const uint32_t r = a.trig[t0 + tid];
+        uint64_t b = 0;
+        uint32_t len = 0;
+        if (r < a.rows) {
+            b = a.off[r];
+            len = (uint32_t)(a.off[r + 1] - b);
+        }
+        tb_begin[tid] = b;
+        tb_len[tid] = len;
+        tb_pref[tid] = a.pref[t0 + tid];
+        if (len) atomicAdd(n_pairs, len);
+    }
+    __syncthreads();
+    const uint32_t pairs = *n_pairs;
+    if (pairs > kCfMaxPairs) {
+        if (tid == 0) {
+            atomicMin(a.status, q);
+            a.out_count[q] = 0;
+        }
+        cf_pad(a, q, 0);
+        return;
+    }
+    ulonglong2* cand = a.cand + (size_t)q * a.cand_cap;
+    // the tier is the kernel's own decision, from the lists' offsets: no host read-back before the launch
+    if (pairs <= min(a.lds_max_pairs, kCfLdsMaxPairs)) {
+        double* acc = reinterpret_cast<double*>(cf_lds);
+        uint32_t* keys = reinterpret_cast<uint32_t*>(cf_lds + (size_t)kCfLdsSlots * 8);
+        cf_accumulate<true>(a, keys, acc, kCfLdsSlots, nt, tb_begin, tb_pref, tb_len, cand, n_items, max_bits);
+    } else {
+        uint32_t slots = kCfThreads;
+        while (slots < 2 * pairs) slots <<= 1;
+        slots = min(slots, a.gslots);                    // (distinct items <= min(pairs, rows) <= gslots / 2 either way)
+        cf_accumulate<false>(a, a.gkeys + (size_t)q * a.gslots, a.gacc + (size_t)q * a.gslots, slots, nt, tb_begin, tb_pref, tb_len,
+                             cand, n_items, max_bits);
+    }
+    const uint32_t n = min(*n_items, a.cand_cap);
+    if (n == 0) {
+        if (tid == 0) a.out_count[q] = 0;
+        cf_pad(a, q, 0);
+        return;
+    }
+    // m: the largest score, found with > from 0; divided by only when it is positive
+    const double m = __longlong_as_double((long long)*max_bits);
+    const bool divide = a.normalize && m > 0.0;
+    uint32_t np2 = 1;
+    while (np2 < n) np2 <<= 1;
+    // sort records: x = the score's bits mapped so that ascending x is descending score (-0.0 ranks as 0.0), y = row << 1 | (the
+    // score is -0.0): ascending (x, y) is score descending, then row ascending
+    for (uint32_t i = tid; i < np2; i += kCfThreads) {
+        ulonglong2 e = make_ulonglong2(~0ull, ~0ull);
+        if (i < n) {
+            const ulonglong2 c = cand[i];
+            double sc = __longlong_as_double((long long)c.x);
+            if (divide) sc = sc / m;
+            unsigned long long b = (unsigned long long)__double_as_longlong(sc);
+            const unsigned long long negzero = b == 0x8000000000000000ull ? 1ull : 0ull;
+            if (negzero) b = 0;
+            const unsigned long long asc = (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+            e = make_ulonglong2(~asc, (c.y << 1) | negzero);
+        }
+        cand[i] = e;
+    }
+    __syncthreads();
+    cf_sort(cand, reinterpret_cast<ulonglong2*>(cf_lds), np2);
+    const uint32_t kept = min(n, a.kd);
+    for (uint32_t j = tid; j < kept; j += kCfThreads) {
+        const ulonglong2 e = cand[j];
+        const unsigned long long asc = ~e.x;
+        unsigned long long b = (asc >> 63) ? (asc & 0x7FFFFFFFFFFFFFFFull) : ~asc;
+        if (e.y & 1ull) b = 0x8000000000000000ull;
+        const size_t o = (size_t)q * a.kd + j;
+        a.out_rows[o] = a.row_offset + (e.y >> 1);
+        a.out_scores[o] = __longlong_as_double((long long)b);
+        if (a.out_idx) a.out_idx[o] = __uint_as_float(j);
+    }
+    cf_pad(a, q, kept);
+    if (tid == 0) a.out_count[q] = kept;
+}
+
+// out[q][j] = scores[q][the index idx[q][j] carries] for the kept slots, -inf behind them
+__global__ void cf_gather_scores_kernel(const double* __restrict__ scores, const float* __restrict__ idx, const uint32_t* __restrict__ count,
+                                        uint32_t kd, uint32_t k, double* __restrict__ out) {
+    const uint32_t q = blockIdx.y, j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= k) return;
+    double v = -__builtin_inf();
+    if (j < count[q]) {
+        const uint32_t src = __float_as_uint(idx[(size_t)q * k + j]);
+        if (src < kd) v = scores[(size_t)q * kd + src];
+    }
+    out[(size_t)q * k + j] = v;
+}
+
+__global__ void cf_fill_u64_kernel(uint64_t* __restrict__ p, uint64_t n, uint64_t v) {
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) p[i] = v;
+}
+
+inline size_t cf_al(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// the arguments every form of the recall checks, in this order
+int cf_check(const char* who, const pg_ctx* ctx, const pg_simtable* s, const void* trig, const void* pref, const uint32_t* off, uint32_t nq,
+             uint32_t k, const pg_cf_opts* opts, const void* rows, const void* scores, uint32_t* nmax_out) {
+    PG_REQUIRE(ctx && s && off && rows && scores, "%s: NULL argument", who);
+    PG_REQUIRE(nq >= 1 && nq <= (uint32_t)kMaxQueries, "%s: nq=%u must be in [1,%d]", who, nq, kMaxQueries);
+    if (k < 1 || k > kCfMaxDepth) {
+        set_error("%s: k=%u unsupported (1..%u)", who, k, kCfMaxDepth);
+        return PG_ERR_UNSUPPORTED;
+    }
+    for (uint32_t q = 0; q < nq; ++q) {
+        PG_REQUIRE(off[q + 1] >= off[q], "%s: trigger_offsets[%u] = %u is below trigger_offsets[%u] = %u", who, q + 1, off[q + 1], q, off[q]);
+        if (off[q + 1] - off[q] > kCfMaxTriggers) {
+            set_error("%s: request %u has %u triggers (at most %u per request)", who, q, off[q + 1] - off[q], kCfMaxTriggers);
+            return PG_ERR_UNSUPPORTED;
+        }
+    }
+    PG_REQUIRE((trig && pref) || off[nq] == off[0], "%s: NULL argument", who);
+    uint32_t nmax = 0;
+    const uint32_t* xo = opts ? opts->excl_offsets : nullptr;
+    if (xo) {
+        for (uint32_t q = 0; q < nq; ++q) {
+            PG_REQUIRE(xo[q + 1] >= xo[q], "%s: excl_offsets[%u] = %u is below excl_offsets[%u] = %u", who, q + 1, xo[q + 1], q, xo[q]);
+            if (xo[q + 1] - xo[q] > kMaxExclude) {
+                set_error("%s: request %u excludes %u ids (at most %u per request)", who, q, xo[q + 1] - xo[q], kMaxExclude);
+                return PG_ERR_UNSUPPORTED;
+            }
+            nmax = std::max(nmax, xo[q + 1] - xo[q]);
+        }
+        PG_REQUIRE(opts->excl_rows || xo[nq] == xo[0], "%s: excl_rows is NULL", who);
+        if ((uint64_t)k + nmax > kCfMaxDepth) {
+            set_error("%s: k=%u plus the longest exclusion list of %u ids exceeds the depth of %u", who, k, nmax, kCfMaxDepth);
+            return PG_ERR_UNSUPPORTED;
+        }
+    } else {
+        PG_REQUIRE(!opts || !opts->excl_rows, "%s: excl_rows without excl_offsets", who);
+    }
+    *nmax_out = nmax;
+    return PG_OK;
+}
+
+// The recall of nq requests whose triggers are device memory (indexed by the host offsets `off` as given) into device outputs
+// [nq][k]; lists: host ids (staged here) or device ids, host offsets.  Caller holds ctx->mu, the item table's shared lock and
+// the similarity table's; ends synchronised.
+int cf_recall_locked(const char* who, pg_ctx* ctx, const pg_simtable* s, const uint32_t* d_trig, const double* d_pref, const uint32_t* off,
+                     uint32_t nq, uint32_t k, int normalize, const uint64_t* excl, bool excl_on_host, const uint32_t* xoff, uint32_t nmax,
+                     uint64_t* d_out_rows, double* d_out_scores, uint32_t* out_count) {
+    int rc;
+    const uint32_t rows_eff = (uint32_t)std::min<uint64_t>(kCfMaxPairs, s->rows);
+    uint32_t gslots = kCfThreads, cand_cap = 1;
+    while (gslots < 2 * rows_eff) gslots <<= 1;
+    while (cand_cap < rows_eff) cand_cap <<= 1;
+    const uint32_t kd = k + nmax;
+    const uint32_t xtotal = nmax && excl_on_host ? xoff[nq] - xoff[0] : 0;
+    const size_t b_stat = cf_al((1 + (size_t)kMaxQueries) * 4), b_off = cf_al(((size_t)nq + 1) * 4), b_list = cf_al((size_t)xtotal * 8);
+    const size_t b_keys = cf_al((size_t)nq * gslots * 4), b_acc = cf_al((size_t)nq * gslots * 8), b_cand = cf_al((size_t)nq * cand_cap * 16);
+    const size_t b_xr = nmax ? cf_al((size_t)nq * kd * 8) : 0, b_xi = nmax ? cf_al((size_t)nq * kd * 4) : 0, b_oi = nmax ? cf_al((size_t)nq * k * 4) : 0;
+    void* buf;
+    if ((rc = scratch_reserve(ctx, 19, b_stat + 2 * b_off + b_list + b_keys + b_acc + b_cand + 2 * b_xr + b_xi + b_oi, &buf))) return rc;
+    char* p = (char*)buf;
+    uint32_t* d_status = (uint32_t*)p;   p += b_stat;        // [0] the status word, [1 + q] request q's count
+    uint32_t* d_off = (uint32_t*)p;      p += b_off;
+    uint32_t* d_xoff = (uint32_t*)p;     p += b_off;
+    uint64_t* d_list = (uint64_t*)p;     p += b_list;
+    uint32_t* d_keys = (uint32_t*)p;     p += b_keys;
+    double* d_acc = (double*)p;          p += b_acc;
+    ulonglong2* d_cand = (ulonglong2*)p; p += b_cand;
+    uint64_t* d_xrows = (uint64_t*)p;    p += b_xr;
+    double* d_xsc = (double*)p;          p += b_xr;
+    float* d_xidx = (float*)p;           p += b_xi;
+    float* d_oidx = (float*)p;
+    uint32_t h_xoff[kMaxQueries + 1];
+    PG_HIP(hipMemsetAsync(d_status, 0xFF, 4, ctx->stream));
+    PG_HIP(hipMemcpyAsync(d_off, off, ((size_t)nq + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (nmax) {
+        for (uint32_t q = 0; q <= nq; ++q) h_xoff[q] = excl_on_host ? xoff[q] - xoff[0] : xoff[q];
+        PG_HIP(hipMemcpyAsync(d_xoff, h_xoff, ((size_t)nq + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+        if (xtotal) PG_HIP(hipMemcpyAsync(d_list, excl + xoff[0], (size_t)xtotal * 8, hipMemcpyHostToDevice, ctx->stream));
+    }
+    PG_HIP(hipStreamSynchronize(ctx->stream));           // (the staged offsets live on the callers' frames)
+    CfArgs a;
+    a.off = s->d_off;
+    a.nbr = s->d_nbr;
+    a.sim = s->d_sim;
+    a.rows = (uint32_t)s->rows;
+    a.row_offset = s->t->row_offset;
+    a.trig = d_trig;
+    a.pref = d_pref;
+    a.trig_off = d_off;
+    a.lds_max_pairs = std::min(ctx->knobs.cf_lds_max_pairs, kCfLdsMaxPairs);
+    a.gslots = gslots;
+    a.gkeys = d_keys;
+    a.gacc = d_acc;
+    a.cand = d_cand;
+    a.cand_cap = cand_cap;
+    a.normalize = normalize;
+    a.kd = kd;
+    a.out_rows = nmax ? d_xrows : d_out_rows;
+    a.out_scores = nmax ? d_xsc : d_out_scores;
+    a.out_idx = nmax ? d_xidx : nullptr;
+    a.out_count = d_status + 1;
+    a.status = d_status;
+    if ((rc = ensure_dyn_lds(ctx, (const void*)cf_recall_kernel, kCfLds))) return rc;
+    cf_recall_kernel<<<nq, kCfThreads, kCfLds, ctx->stream>>>(a);
+    PG_HIP(hipGetLastError());
+    if (nmax) {
+        // the existing compaction on the row plane; its fp32 score plane carries each entry's index into the fp64 scores
+        if ((rc = exclude_compact_locked(ctx, d_xrows, d_xidx, nq, kd, excl_on_host ? d_list : excl, d_xoff, k, 0.0f, d_out_rows, d_oidx,
+                                         d_status + 1)))
+            return rc;
+        cf_gather_scores_kernel<<<dim3((k + 255) / 256, nq), 256, 0, ctx->stream>>>(d_xsc, d_oidx, d_status + 1, kd, k, d_out_scores);
+        PG_HIP(hipGetLastError());
+    }
+    PG_HIP(hipMemcpyAsync(ctx->h_status, d_status, (1 + (size_t)nq) * 4, hipMemcpyDeviceToHost, ctx->stream));
+    PG_HIP(hipStreamSynchronize(ctx->stream));
+    if (ctx->h_status[0] != 0xFFFFFFFFu) {
+        set_error("%s: request %u expands to more than %u (trigger, neighbour) pairs", who, ctx->h_status[0], kCfMaxPairs);
+        return PG_ERR_UNSUPPORTED;
+    }
+    if (out_count) memcpy(out_count, ctx->h_status + 1, (size_t)nq * 4);
+    return PG_OK;
+}
+
+int cf_entry(const char* who, pg_ctx* ctx, const pg_simtable* s, const uint32_t* trig, const double* pref, const uint32_t* off, uint32_t nq,
+             uint32_t k, const pg_cf_opts* opts, uint64_t* rows, double* scores, uint32_t* out_count, bool host) {
+    int rc;
+    uint32_t nmax = 0;
+    if ((rc = cf_check(who, ctx, s, trig, pref, off, nq, k, opts, rows, scores, &nmax))) return rc;
+    const uint32_t total = off[nq] - off[0];
+    if (host)
+        for (uint32_t i = 0; i < total; ++i)
+            PG_REQUIRE(std::isfinite(pref[off[0] + i]), "%s: trigger_prefer[%u] is not finite", who, off[0] + i);
+    const int normalize = opts ? opts->normalize : 1;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    PG_HIP(hipSetDevice(ctx->device));
+    TableRead tr(s->t->rw);
+    std::shared_lock<std::shared_mutex> sr(s->rw);
+    const uint64_t gen = s->t->generation.load(std::memory_order_relaxed);
+    PG_REQUIRE(gen == s->gen, "%s: the similarity table describes generation %llu of its item table, which is at generation %llu (stale)",
+               who, (unsigned long long)s->gen, (unsigned long long)gen);
+    const uint64_t* excl = opts ? opts->excl_rows : nullptr;
+    const uint32_t* xoff = opts ? opts->excl_offsets : nullptr;
+    if (!host) return cf_recall_locked(who, ctx, s, trig, pref, off, nq, k, normalize, excl, false, xoff, nmax, rows, scores, out_count);
+    // host buffers: triggers and preferences in, rows and scores out, through scratch slot 5
+    const size_t tb = cf_al((size_t)total * 4), pb = cf_al((size_t)total * 8), ob = cf_al((size_t)nq * k * 8);
+    void* buf;
+    if ((rc = scratch_reserve(ctx, 5, tb + pb + 2 * ob, &buf))) return rc;
+    uint32_t* d_trig = (uint32_t*)buf;
+    double* d_pref = (double*)((char*)buf + tb);
+    uint64_t* d_rows = (uint64_t*)((char*)buf + tb + pb);
+    double* d_sc = (double*)((char*)buf + tb + pb + ob);
+    uint32_t h_off[kMaxQueries + 1];
+    for (uint32_t q = 0; q <= nq; ++q) h_off[q] = off[q] - off[0];
+    if (total) {
+        PG_HIP(hipMemcpyAsync(d_trig, trig + off[0], (size_t)total * 4, hipMemcpyHostToDevice, ctx->stream));
+        PG_HIP(hipMemcpyAsync(d_pref, pref + off[0], (size_t)total * 8, hipMemcpyHostToDevice, ctx->stream));
+    }
+    rc = cf_recall_locked(who, ctx, s, d_trig, d_pref, h_off, nq, k, normalize, excl, true, xoff, nmax, d_rows, d_sc, out_count);
+    if (rc) return rc;
+    PG_HIP(hipMemcpyAsync(rows, d_rows, (size_t)nq * k * 8, hipMemcpyDeviceToHost, ctx->stream));
+    PG_HIP(hipMemcpyAsync(scores, d_sc, (size_t)nq * k * 8, hipMemcpyDeviceToHost, ctx->stream));
+    PG_HIP(hipStreamSynchronize(ctx->stream));
+    return PG_OK;
+}
+
+}  // namespace
+}  // namespace pg
+
+extern "C" {
+
+int pg_simtable_create(pg_ctx* ctx, const pg_table* t, pg_simtable** out) {
+    PG_REQUIRE(ctx && t && out, "pg_simtable_create: NULL argument");
+    PG_REQUIRE(t->rows >= 1 && t->rows <= 0xFFFFFFFFull, "pg_simtable_create: a table of %llu rows (1 .. 2^32 - 1)", (unsigned long long)t->rows);
+    PG_REQUIRE(!t->d_row_map, "pg_simtable_create: a filtered view has no similarity table (its rows are not the source's)");
+    std::lock_guard<std::mutex> g(ctx->mu);
+    PG_HIP(hipSetDevice(ctx->device));
+    pg::TableRead tr(t->rw);
+    pg_simtable* s = new pg_simtable();
+    s->t = t;
+    s->gen = t->generation.load(std::memory_order_relaxed);
+    s->rows = t->rows;
+    const hipError_t e = hipMalloc((void**)&s->d_off, (s->rows + 1) * 8);
+    if (e != hipSuccess) {
+        pg::set_error("pg_simtable_create: hipMalloc(%.1f MB) failed: %s", (double)((s->rows + 1) * 8) / 1e6, hipGetErrorString(e));
+        delete s;
+        return PG_ERR_NOMEM;
+    }
+    // a table whose rows were never uploaded has empty lists
+    if (hipMemsetAsync(s->d_off, 0, (s->rows + 1) * 8, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) {
+        pg::set_error("pg_simtable_create: clearing the offsets failed");
+        (void)hipFree(s->d_off);
+        delete s;
+        return PG_ERR_DEVICE;
+    }
+    *out = s;
+    return PG_OK;
+}
+
+int pg_simtable_upload(pg_ctx* ctx, pg_simtable* s, uint64_t row0, uint64_t nrows, const uint64_t* offsets, const uint32_t* nbr_rows,
+                       const float* sims) {
+    PG_REQUIRE(ctx && s && offsets, "pg_simtable_upload: NULL argument");
+    PG_REQUIRE(row0 <= s->rows && nrows <= s->rows - row0, "pg_simtable_upload: rows [%llu, %llu) outside the table's %llu",
+               (unsigned long long)row0, (unsigned long long)(row0 + nrows), (unsigned long long)s->rows);
+    std::lock_guard<std::mutex> g(ctx->mu);
+    std::unique_lock<std::shared_mutex> sw(s->rw);
+    PG_REQUIRE(row0 >= s->rows_uploaded, "pg_simtable_upload: row %llu after rows up to %llu were uploaded (rows arrive in ascending order)",
+               (unsigned long long)row0, (unsigned long long)s->rows_uploaded);
+    const uint64_t total = offsets[nrows] - offsets[0];
+    PG_REQUIRE(offsets[nrows] >= offsets[0] && (total == 0 || (nbr_rows && sims)), "pg_simtable_upload: NULL argument");
+    // every refusal comes before the first change: a refused upload leaves the table as it was
+    std::vector<uint32_t> seen;
+    for (uint64_t r = 0; r < nrows; ++r) {
+        PG_REQUIRE(offsets[r + 1] >= offsets[r], "pg_simtable_upload: offsets[%llu] is below offsets[%llu]", (unsigned long long)(r + 1),
+                   (unsigned long long)r);
+        const uint64_t b = offsets[r], len = offsets[r + 1] - b;
+        PG_REQUIRE(len <= pg::kCfMaxList, "pg_simtable_upload: the list of row %llu has %llu entries (at most %u)", (unsigned long long)(row0 + r),
+                   (unsigned long long)len, pg::kCfMaxList);
+        for (uint64_t i = 0; i < len; ++i) {
+            PG_REQUIRE(nbr_rows[b + i] < s->rows, "pg_simtable_upload: neighbour %u of row %llu is outside the table's %llu rows", nbr_rows[b + i],
+                       (unsigned long long)(row0 + r), (unsigned long long)s->rows);
+            PG_REQUIRE(std::isfinite(sims[b + i]), "pg_simtable_upload: a similarity of row %llu is not finite", (unsigned long long)(row0 + r));
+        }
+        seen.assign(nbr_rows + b, nbr_rows + b + len);
+        std::sort(seen.begin(), seen.end());
+        for (uint64_t i = 1; i < len; ++i)
+            PG_REQUIRE(seen[i] != seen[i - 1], "pg_simtable_upload: neighbour %u appears twice in the list of row %llu", seen[i],
+                       (unsigned long long)(row0 + r));
+    }
+    if (nrows == 0) return PG_OK;
+    PG_HIP(hipSetDevice(ctx->device));
+    if (s->pairs + total > s->cap) {
+        const uint64_t cap = std::max<uint64_t>(s->pairs + total, s->cap + s->cap / 2);
+        uint32_t* nn = nullptr;
+        float* ns = nullptr;
+        if (hipMalloc((void**)&nn, cap * 4) != hipSuccess || hipMalloc((void**)&ns, cap * 4) != hipSuccess) {
+            if (nn) (void)hipFree(nn);
+            pg::set_error("pg_simtable_upload: hipMalloc(%.1f MB) failed", (double)(cap * 8) / 1e6);
+            return PG_ERR_NOMEM;
+        }
+        PG_HIP(hipDeviceSynchronize());                  // (no other context's recall still reads the old arrays: they hold the shared lock until they are synchronised)
+        if (s->pairs) {
+            PG_HIP(hipMemcpyAsync(nn, s->d_nbr, s->pairs * 4, hipMemcpyDeviceToDevice, ctx->stream));
+            PG_HIP(hipMemcpyAsync(ns, s->d_sim, s->pairs * 4, hipMemcpyDeviceToDevice, ctx->stream));
+            PG_HIP(hipStreamSynchronize(ctx->stream));
+        }
+        if (s->d_nbr) (void)hipFree(s->d_nbr);
+        if (s->d_sim) (void)hipFree(s->d_sim);
+        s->d_nbr = nn;
+        s->d_sim = ns;
+        s->cap = cap;
+    }
+    std::vector<uint64_t> abs(nrows);
+    for (uint64_t r = 0; r < nrows; ++r) abs[r] = s->pairs + (offsets[r] - offsets[0]);
+    PG_HIP(hipMemcpyAsync(s->d_off + row0, abs.data(), nrows * 8, hipMemcpyHostToDevice, ctx->stream));
+    // (the rows between the last upload and row0 already end at the old total: their lists stay empty)
+    const uint64_t tail = s->rows + 1 - (row0 + nrows);
+    pg::cf_fill_u64_kernel<<<(unsigned)std::min<uint64_t>((tail + 255) / 256, 4096), 256, 0, ctx->stream>>>(s->d_off + row0 + nrows, tail,
+                                                                                                          s->pairs + total);
+    PG_HIP(hipGetLastError());
+    if (total) {
+        PG_HIP(hipMemcpyAsync(s->d_nbr + s->pairs, nbr_rows + offsets[0], total * 4, hipMemcpyHostToDevice, ctx->stream));
+        PG_HIP(hipMemcpyAsync(s->d_sim + s->pairs, sims + offsets[0], total * 4, hipMemcpyHostToDevice, ctx->stream));
+    }
+    PG_HIP(hipStreamSynchronize(ctx->stream));
+    s->pairs += total;
+    s->rows_uploaded = row0 + nrows;
+    return PG_OK;
+}
+
+int pg_simtable_info(const pg_simtable* s, uint64_t* rows, uint64_t* pairs, uint64_t* rows_uploaded, uint64_t* generation) {
+    PG_REQUIRE(s, "pg_simtable_info: table is NULL");
+    std::shared_lock<std::shared_mutex> sr(s->rw);
+    if (rows) *rows = s->rows;
+    if (pairs) *pairs = s->pairs;
+    if (rows_uploaded) *rows_uploaded = s->rows_uploaded;
+    if (generation) *generation = s->gen;
+    return PG_OK;
+}
+
+int pg_simtable_destroy(pg_ctx* ctx, pg_simtable* s) {
+    PG_REQUIRE(ctx, "pg_simtable_destroy: ctx is NULL");
+    if (!s) return PG_OK;
+    {
+        std::lock_guard<std::mutex> g(ctx->mu);
+        std::unique_lock<std::shared_mutex> sw(s->rw);
+        PG_HIP(hipSetDevice(ctx->device));
+        PG_HIP(hipDeviceSynchronize());
+        if (s->d_off) (void)hipFree(s->d_off);
+        if (s->d_nbr) (void)hipFree(s->d_nbr);
+        if (s->d_sim) (void)hipFree(s->d_sim);
+    }
+    delete s;
+    return PG_OK;
+}
+
+int pg_cf_recall(pg_ctx* ctx, const pg_simtable* s, const uint32_t* trigger_rows, const double* trigger_prefer, const uint32_t* trigger_offsets,
+                 uint32_t nq, uint32_t k, const pg_cf_opts* opts, uint64_t* out_rows, double* out_scores, uint32_t* out_count) {
+    return pg::cf_entry("pg_cf_recall", ctx, s, trigger_rows, trigger_prefer, trigger_offsets, nq, k, opts, out_rows, out_scores, out_count, true);
+}
+
+int pg_cf_recall_dev(pg_ctx* ctx, const pg_simtable* s, const uint32_t* d_trigger_rows, const double* d_trigger_prefer,
+                     const uint32_t* trigger_offsets, uint32_t nq, uint32_t k, const pg_cf_opts* opts, uint64_t* d_out_rows,
+                     double* d_out_scores, uint32_t* out_count) {
+    return pg::cf_entry("pg_cf_recall_dev", ctx, s, d_trigger_rows, d_trigger_prefer, trigger_offsets, nq, k, opts, d_out_rows, d_out_scores,
+                        out_count, false);
+}
+
+}  // extern "C"

@@ -101,6 +101,7 @@ struct Knobs {
     uint32_t coalescer_max_exclude = 0;     // PG_COALESCER_MAX_EXCLUDE: longest list of pg_coalescer_recall_exclude (0..4096; 0: the entry is off), read when a coalescer is created
     uint32_t index_where_cache = 4;         // PG_INDEX_WHERE_CACHE: filtered lists an index keeps per filter (0: built per call, freed after it)
     bool index_route_where = false;         // PG_INDEX_ROUTE_WHERE: pg_recall_topk_where on a table with a current attached index searches it
+    uint32_t cf_lds_max_pairs = 6144;           // PG_CF_LDS_MAX_PAIRS: a collaborative-filter request of at most this many (trigger, neighbour) pairs keeps its table in LDS (cf.hip: 12288 slots in 144 KiB, load factor <= 0.5; larger values are cut to that); above, in global memory
     double index_refresh_full_fraction = 0.1;   // PG_INDEX_REFRESH_FULL_FRACTION: pg_index_refresh in auto mode re-assigns every row once the written rows exceed this share of the table
 };
 
@@ -262,7 +263,8 @@ struct pg_ctx {
     //   12, 13 recall.hip   14 rank_mlp.hip: head partials of the weights-stationary multi-head kernel   15 pg_fuse_scores_dev
     //   16 pg_features_eval_dev: the bound variables   17 index.hip: bounds, probe thresholds and list counts of an index recall
     //   18 recall.hip: the over-fetched answer, lists and counts of a recall with exclusion lists
-    pg::Scratch scratch[19];
+    //   19 cf.hip: status and counts, staged offsets and lists, the global tier's tables, the items to order, the over-fetched answer
+    pg::Scratch scratch[20];
     std::mutex pool_mu;          // guards pipe_free
     std::vector<pg::PipeRun*> pipe_free;     // per-batch status blocks / events of the device-resident pipelines
     std::map<const void*, size_t> dyn_lds;   // kernels whose dynamic-LDS limit was raised on this device

@@ -320,6 +320,77 @@ class Table:
         return counts
 
 
+class SimTable:
+    """Item-to-item similarity lists over the local rows of `table`, resident in HBM (pg_simtable_*), and the
+    collaborative-filter recall over them (pg_cf_recall).  The table must outlive it."""
+
+    def __init__(self, ctx: Context, table: Table):
+        self.ctx, self.table = ctx, table
+        h = C.c_void_p()
+        _lib.check(ctx.L.pg_simtable_create(ctx.h, table.h, C.byref(h)))
+        self.h = h
+
+    def destroy(self):
+        if self.h:
+            _lib.check(self.ctx.L.pg_simtable_destroy(self.ctx.h, self.h))
+            self.h = None
+
+    def info(self) -> dict:
+        v = [C.c_uint64() for _ in range(4)]
+        _lib.check(self.ctx.L.pg_simtable_info(self.h, *[C.byref(x) for x in v]))
+        return dict(zip(("rows", "pairs", "rows_uploaded", "generation"), (x.value for x in v)))
+
+    def upload(self, offsets, nbr_rows, sims, row0: int = 0):
+        """append the lists of len(offsets) - 1 consecutive rows from row0: row row0 + i has the neighbours
+        nbr_rows[offsets[i]:offsets[i + 1]] (local rows of the table) with the similarities sims[...]"""
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        nb = np.ascontiguousarray(nbr_rows, dtype=np.uint32)
+        sm = np.ascontiguousarray(sims, dtype=np.float32)
+        if off.shape[0] < 1 or nb.shape != sm.shape or nb.ndim != 1 or int(off.max()) > nb.shape[0]:
+            raise ValueError("SimTable.upload: offsets must index nbr_rows / sims of one length")
+        _lib.check(self.ctx.L.pg_simtable_upload(self.ctx.h, self.h, int(row0), off.shape[0] - 1, _ptr(off), _ptr(nb), _ptr(sm)))
+
+    def cf_recall(self, triggers, prefer, k: int, normalize: bool = True, lists=None):
+        """UserCollaborativeFilterRecall: triggers[q] / prefer[q] = request q's trigger rows and preference scores;
+        lists[q] = the global row ids request q has seen (None: none).
+        → (rows [nq][k] uint64 global ids, scores [nq][k] f64, counts [nq])."""
+        nq = len(triggers)
+        if len(prefer) != nq:
+            raise ValueError("cf_recall: %d preference lists for %d requests" % (len(prefer), nq))
+        tr = [np.asarray(t, dtype=np.uint32).reshape(-1) for t in triggers]
+        pf = [np.asarray(p, dtype=np.float64).reshape(-1) for p in prefer]
+        if any(a.shape != b.shape for a, b in zip(tr, pf)):
+            raise ValueError("cf_recall: every trigger needs one preference score")
+        off = np.zeros(nq + 1, dtype=np.uint32)
+        off[1:] = np.cumsum([a.shape[0] for a in tr])
+        trc = np.ascontiguousarray(np.concatenate(tr)) if nq else np.zeros(0, dtype=np.uint32)
+        pfc = np.ascontiguousarray(np.concatenate(pf)) if nq else np.zeros(0, dtype=np.float64)
+        opts = _lib.PgCfOpts(int(bool(normalize)), None, None)
+        if lists is not None:
+            ids, xoff = _pack_lists(lists, nq)
+            opts.excl_rows, opts.excl_offsets = ids.ctypes.data, xoff.ctypes.data
+        rows = np.empty((nq, k), dtype=np.uint64)
+        scores = np.empty((nq, k), dtype=np.float64)
+        counts = np.zeros(nq, dtype=np.uint32)
+        _lib.check(self.ctx.L.pg_cf_recall(self.ctx.h, self.h, _ptr(trc), _ptr(pfc), _ptr(off), nq, k, C.byref(opts),
+                                           _ptr(rows), _ptr(scores), _ptr(counts)))
+        return rows, scores, counts
+
+    def cf_recall_dev(self, d_triggers: int, d_prefer: int, trigger_offsets, k: int, d_out_rows: int, d_out_scores: int,
+                      normalize: bool = True, d_excl_rows: int = 0, excl_offsets=None):
+        """pg_cf_recall_dev: triggers, preferences, lists and outputs are device addresses, the offsets host arrays → counts"""
+        off = np.ascontiguousarray(trigger_offsets, dtype=np.uint32)
+        nq = off.shape[0] - 1
+        opts = _lib.PgCfOpts(int(bool(normalize)), None, None)
+        if excl_offsets is not None:
+            xoff = np.ascontiguousarray(excl_offsets, dtype=np.uint32)
+            opts.excl_rows, opts.excl_offsets = d_excl_rows or None, xoff.ctypes.data
+        counts = np.zeros(nq, dtype=np.uint32)
+        _lib.check(self.ctx.L.pg_cf_recall_dev(self.ctx.h, self.h, C.c_void_p(d_triggers), C.c_void_p(d_prefer), _ptr(off), nq, k,
+                                               C.byref(opts), C.c_void_p(d_out_rows), C.c_void_p(d_out_scores), _ptr(counts)))
+        return counts
+
+
 class Index:
     """Exact IVF-partitioned index over a table (pg_index_*): the same results as the table's own recalls, bit for bit, with
     the lists that provably cannot reach a query's K-th score skipped.  The table must outlive the index."""
