@@ -361,11 +361,18 @@ int pg_dpp_ex(pg_ctx* ctx, const pg_table* t, const uint32_t* cand_rows, const d
  * norm_quality_score is the ssd_norm_quality_score experiment parameter (0 none, 1 z-score, 2 min-max).
  * out_idx (capacity n) receives min(topn, n) indices into the candidate list; when the reference would
  * return the items unchanged ("all item score are zeros") it receives 0..n-1 and *out_count = n.
- * out_quality (optional, [n]) receives the normalised quality scores ("ssd_quality_score"). */
+ * out_quality (optional, [n]) receives the normalised quality scores ("ssd_quality_score").
+ * PG_ERR_UNSUPPORTED, the context left usable: n > 8192, dim + ensure_pos_similarity > 320, a candidate row outside `t`. */
 int pg_ssd(pg_ctx* ctx, const pg_table* t, const uint32_t* cand_rows, const double* rel, uint32_t n,
            double gamma, uint32_t topn, uint32_t window, int normalize_emb, int ensure_pos_similarity,
            int norm_quality_score, int use_ssd_star, uint32_t* out_idx, uint32_t* out_count,
            double* out_quality);
+/* pg_ssd over embeddings the caller holds — emb: [n][dim] fp32 on the host, candidate i's item embedding as loadEmbeddingCache
+ * parses it from the item's properties, of any dim with dim + ensure_pos_similarity <= 320 (a table holds 64 / 128 / 192 / 256
+ * only).  Everything else as pg_ssd; PG_ERR_UNSUPPORTED for n > 8192 or a wider embedding. */
+int pg_ssd_emb(pg_ctx* ctx, const float* emb, uint32_t dim, const double* rel, uint32_t n, double gamma, uint32_t topn,
+               uint32_t window, int normalize_emb, int ensure_pos_similarity, int norm_quality_score, int use_ssd_star,
+               uint32_t* out_idx, uint32_t* out_count, double* out_quality);
 
 /* ---- item features: typed columns in HBM, assembled by row ----------------------------------
  * Replaces the per-request host boxing of EasyrecAlgoDataGenerator.AddFeatures / GeneratorAlgoData
@@ -1099,6 +1106,11 @@ typedef struct {
                                            crowded rows switched the two-digit refinement stage on, csrc/recall_r2.hip) */
     uint64_t sort_split_calls;          /* score sorts and top-K final orders that took the split sort (few lists of 1025 … 8192
                                            items: runs sorted wave by wave over the chip, csrc/split_sort.hpp) */
+    /* SSD calls by the kernel that served them (csrc/ssd.hip; d1 = table dim + ensure_pos_similarity; one count per launch
+     * sequence, so a coalesced batch of R requests counts once): the multi-workgroup kernel (d1 64 / 65 / 128 / 129 and
+     * window <= 16), the one-workgroup register kernel (those widths, window > 16, n <= 2048), the one-workgroup generic kernel
+     * (everything else up to 8192 x 320) */
+    uint64_t ssd_grid_calls, ssd_reg_calls, ssd_generic_calls;
 } pg_stats_t;
 int pg_stats(pg_ctx* ctx, pg_stats_t* out);
 /* time (ms) of the dominant kernel of the last pg_recall_* call, measured with HIP events on the

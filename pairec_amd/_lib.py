@@ -21,7 +21,7 @@ EXPORTS = [
     "pg_rank_fm2t", "pg_rank_fm2t_dev", "pg_expr_compile", "pg_expr_free", "pg_expr_num_vars", "pg_expr_set_score_rewrites", "pg_expr_compile_typed", "pg_expr_is_antlr", "pg_fuse_scores_dev",
     "pg_expr_var_name", "pg_expr_eval", "pg_expr_eval_dev", "pg_sort_scores", "pg_sort_scores_dev",
     "pg_dpp", "pg_stats", "pg_last_scan_kernel_ms", "pg_rows_to_local_dev", "pg_widen_f32_dev",
-    "pg_hbm_read_probe", "pg_table_screen_info", "pg_ssd", "pg_features_create", "pg_features_destroy", "pg_features_set_column",
+    "pg_hbm_read_probe", "pg_table_screen_info", "pg_ssd", "pg_ssd_emb", "pg_features_create", "pg_features_destroy", "pg_features_set_column",
     "pg_features_column_index", "pg_features_num_columns", "pg_features_gather_i32_dev",
     "pg_features_gather_f32_dev", "pg_rank_fm2t_rows_dev", "pg_rank_fm2t_rows", "pg_recommend_dnn3_dev", "pg_set_option",
     "pg_table_fill_gaussian", "pg_table_fill_mixture", "pg_group_exchange_stats", "pg_dpp_ex", "pg_i2i_recall", "pg_online_vector_recall", "pg_fm2t_user_embedding",
@@ -58,7 +58,8 @@ class PgStats(C.Structure):
                 ("last_sort_ms", C.c_double), ("recall_predicted", C.c_uint64),
                 ("recall_suspects", C.c_uint64), ("recall_suspect_queries", C.c_uint64), ("recall_i4m_pairs", C.c_uint64),
                 ("recall_screen_overflows", C.c_uint64), ("recall_record_growths", C.c_uint64),
-                ("recall_rescored", C.c_uint64), ("sort_split_calls", C.c_uint64)]
+                ("recall_rescored", C.c_uint64), ("sort_split_calls", C.c_uint64),
+                ("ssd_grid_calls", C.c_uint64), ("ssd_reg_calls", C.c_uint64), ("ssd_generic_calls", C.c_uint64)]
 
 
 class PgWhereStats(C.Structure):
@@ -244,6 +245,7 @@ def load():
         "pg_dpp": [vp, vp, vp, vp, u32, C.c_double, u32, u32, i32, vp, vp],
         "pg_dpp_ex": [vp, vp, vp, vp, u32, P(PgDppOptions), vp, vp, vp, vp],
         "pg_ssd": [vp, vp, vp, vp, u32, C.c_double, u32, u32, i32, i32, i32, i32, vp, vp, vp],
+        "pg_ssd_emb": [vp, vp, u32, vp, u32, C.c_double, u32, u32, i32, i32, i32, i32, vp, vp, vp],
         "pg_features_create": [vp, u64, P(vp)],
         "pg_features_destroy": [vp, vp],
         "pg_features_set_column": [vp, vp, C.c_char_p, i32, vp, C.c_double],

@@ -26,15 +26,14 @@ namespace pg {
 
 // one thread per candidate: gather the fp32 row, widen, optionally L2-normalise (floats.Norm /
 // floats.Scale(1/norm), ssd_sort.go:246-249), optionally append 1 (ensurePosSimilarity, :250-252);
-// stored transposed Et[k][n]
+// stored transposed Et[k][n].  cand == nullptr: candidate i is row i (pg_ssd_emb).
 __global__ void ssd_prepare_kernel(const float* __restrict__ tab, uint32_t tab_rows, uint32_t d,
                                    const uint32_t* __restrict__ cand, uint32_t n, int normalize,
                                    int append_one, double* __restrict__ Et) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    cand += (size_t)blockIdx.y * n;                               // request blockIdx.y of a batch
-    Et += (size_t)blockIdx.y * n * (d + (append_one ? 1u : 0u));
-    uint32_t row = cand[i];
+    Et += (size_t)blockIdx.y * n * (d + (append_one ? 1u : 0u));   // request blockIdx.y of a batch
+    uint32_t row = cand ? cand[(size_t)blockIdx.y * n + i] : i;
     row = row < tab_rows ? row : tab_rows - 1;
     const float* x = tab + (size_t)row * d;
     double inv = 1.0;
@@ -552,13 +551,14 @@ bool ssd_batchable(uint32_t d1, uint32_t window) { return (d1 == 64 || d1 == 65 
 // SSDWithSlidingWindow for R requests of n candidates each, device-resident: d_cand [R][n] rows of `t`, d_rel [R][n]
 // quality scores (normalised already), d_out [R][T] picks.  R > 1 needs the multi-workgroup kernel's shapes
 // (ssd_batchable): every request is its own set of G single-wave workgroups with its own mailbox and barrier; a launch
-// carries as many requests as are co-resident (4 single-wave workgroups per CU).  Caller holds ctx->mu.
-int ssd_run_locked(pg_ctx* ctx, const pg_table* t, const uint32_t* d_cand, const double* d_rel, uint32_t R, uint32_t n,
-                   double gamma, uint32_t T, uint32_t window, int normalize_emb, int ensure_pos_similarity, int use_ssd_star,
-                   uint32_t* d_out) {
+// carries as many requests as are co-resident (4 single-wave workgroups per CU).  The embeddings are rows d_cand of the
+// device array d_tab [tab_rows][dim] (d_cand == nullptr: rows 0..n-1).  Caller holds ctx->mu.
+static int ssd_run_rows_locked(pg_ctx* ctx, const float* d_tab, uint32_t tab_rows, uint32_t dim, const uint32_t* d_cand,
+                               const double* d_rel, uint32_t R, uint32_t n, double gamma, uint32_t T, uint32_t window,
+                               int normalize_emb, int ensure_pos_similarity, int use_ssd_star, uint32_t* d_out) {
     if (R == 0 || n == 0 || T == 0) return PG_OK;
     if (window <= 1) window = 5;                          // ssd_sort.go:357-360
-    const uint32_t d1 = t->dim + (ensure_pos_similarity ? 1u : 0u);
+    const uint32_t d1 = dim + (ensure_pos_similarity ? 1u : 0u);
     const uint32_t G = (n + 63) / 64;
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t bE = al((size_t)n * d1 * 8), bP = al((size_t)window * n * 8), bN = al((size_t)n * 8), bSel = al((size_t)n * 4);
@@ -572,6 +572,9 @@ int ssd_run_locked(pg_ctx* ctx, const pg_table* t, const uint32_t* d_cand, const
         set_error("ssd: a batch of %u requests needs dim 64 / 128 and a window <= 16 (d1 = %u, window %u)", R, d1, window);
         return PG_ERR_UNSUPPORTED;
     }
+    if (kind == 2) ctx->stats.ssd_grid_calls++;
+    else if (kind == 1) ctx->stats.ssd_reg_calls++;
+    else ctx->stats.ssd_generic_calls++;
     void* buf;
     int rc;
     if (kind == 2) {
@@ -581,7 +584,7 @@ int ssd_run_locked(pg_ctx* ctx, const pg_table* t, const uint32_t* d_cand, const
         // (requests are strided by their exact sizes inside the kernels: n * d1 doubles, one SsdMail, 2 (G + 1) d1 doubles)
         SsdMail* mail = (SsdMail*)p; p += (size_t)R * bMail;
         double* ebuf = (double*)p;
-        ssd_prepare_kernel<<<dim3((n + 63) / 64, R), 64, 0, ctx->stream>>>(t->d, (uint32_t)t->rows, t->dim, d_cand, n, normalize_emb,
+        ssd_prepare_kernel<<<dim3((n + 63) / 64, R), 64, 0, ctx->stream>>>(d_tab, tab_rows, dim, d_cand, n, normalize_emb,
                                                                            ensure_pos_similarity, Et);
         PG_HIP(hipMemsetAsync(mail, 0, (size_t)R * sizeof(SsdMail), ctx->stream));
         // as many requests per launch as are certainly co-resident: 4 single-wave workgroups (one per SIMD) per CU
@@ -612,7 +615,7 @@ int ssd_run_locked(pg_ctx* ctx, const pg_table* t, const uint32_t* d_cand, const
     double* ssq = (double*)p; p += bN;
     double* q = (double*)p; p += bN;
     uint32_t* d_sel = (uint32_t*)p;
-    ssd_prepare_kernel<<<dim3((n + 63) / 64, 1), 64, 0, ctx->stream>>>(t->d, (uint32_t)t->rows, t->dim, d_cand, n, normalize_emb,
+    ssd_prepare_kernel<<<dim3((n + 63) / 64, 1), 64, 0, ctx->stream>>>(d_tab, tab_rows, dim, d_cand, n, normalize_emb,
                                                                        ensure_pos_similarity, Et);
     if (kind == 1) {
         switch (d1) {
@@ -625,6 +628,52 @@ int ssd_run_locked(pg_ctx* ctx, const pg_table* t, const uint32_t* d_cand, const
         ssd_kernel<<<1, 1024, 0, ctx->stream>>>(Et, n, d1, d_rel, gamma, T, window, use_ssd_star, P, nrm, ssq, q, d_sel, d_out);
     }
     PG_HIP(hipGetLastError());
+    return PG_OK;
+}
+
+int ssd_run_locked(pg_ctx* ctx, const pg_table* t, const uint32_t* d_cand, const double* d_rel, uint32_t R, uint32_t n,
+                   double gamma, uint32_t T, uint32_t window, int normalize_emb, int ensure_pos_similarity, int use_ssd_star,
+                   uint32_t* d_out) {
+    return ssd_run_rows_locked(ctx, t->d, (uint32_t)t->rows, t->dim, d_cand, d_rel, R, n, gamma, T, window, normalize_emb,
+                               ensure_pos_similarity, use_ssd_star, d_out);
+}
+
+// pg_ssd (t, cand_rows) and pg_ssd_emb (emb [n][dim], the candidates' own embeddings on the host) behind their checks
+static int ssd_one(pg_ctx* ctx, const pg_table* t, const uint32_t* cand_rows, const float* emb, uint32_t dim, const double* rel,
+                   uint32_t n, double gamma, uint32_t topn, uint32_t window, int normalize_emb, int ensure_pos_similarity,
+                   int norm_quality_score, int use_ssd_star, uint32_t* out_idx, uint32_t* out_count, double* out_quality) {
+    std::vector<double> quality(n);
+    const bool bail = !ssd_norm_quality_host(rel, n, norm_quality_score, quality.data());
+    if (bail) {        // "all item score are zeros": the reference returns the items unchanged
+        for (uint32_t i = 0; i < n; ++i) out_idx[i] = i;
+        *out_count = n;
+        if (out_quality) for (uint32_t i = 0; i < n; ++i) out_quality[i] = rel[i];
+        return PG_OK;
+    }
+    if (out_quality) for (uint32_t i = 0; i < n; ++i) out_quality[i] = quality[i];
+
+    const uint32_t T = n < topn ? n : topn;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    TableRead tr;
+    if (t) tr = TableRead(t->rw);
+    void* io;
+    int rc;
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t bIn = t ? al((size_t)n * 4) : al((size_t)n * dim * 4);      // candidate rows, or the embeddings themselves
+    if ((rc = scratch_reserve(ctx, 5, bIn + al((size_t)n * 8) + al((size_t)T * 4), &io))) return rc;
+    double* d_rel = (double*)((char*)io + bIn);
+    uint32_t* d_out = (uint32_t*)((char*)io + bIn + al((size_t)n * 8));
+    if (t) PG_HIP(hipMemcpyAsync(io, cand_rows, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+    else PG_HIP(hipMemcpyAsync(io, emb, (size_t)n * dim * 4, hipMemcpyHostToDevice, ctx->stream));
+    PG_HIP(hipMemcpyAsync(d_rel, quality.data(), (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (t) rc = ssd_run_rows_locked(ctx, t->d, (uint32_t)t->rows, t->dim, (const uint32_t*)io, d_rel, 1, n, gamma, T, window,
+                                    normalize_emb, ensure_pos_similarity, use_ssd_star, d_out);
+    else rc = ssd_run_rows_locked(ctx, (const float*)io, n, dim, nullptr, d_rel, 1, n, gamma, T, window, normalize_emb,
+                                  ensure_pos_similarity, use_ssd_star, d_out);
+    if (rc) return rc;
+    PG_HIP(hipMemcpyAsync(out_idx, d_out, (size_t)T * 4, hipMemcpyDeviceToHost, ctx->stream));
+    PG_HIP(hipStreamSynchronize(ctx->stream));
+    *out_count = T;
     return PG_OK;
 }
 
@@ -648,36 +697,32 @@ int pg_ssd(pg_ctx* ctx, const pg_table* t, const uint32_t* cand_rows, const doub
         return PG_ERR_UNSUPPORTED;
     }
     for (uint32_t i = 0; i < n; ++i)
-        PG_REQUIRE(cand_rows[i] < t->rows, "pg_ssd: candidate row %u outside table", cand_rows[i]);
+        if (cand_rows[i] >= t->rows) {
+            pg::set_error("pg_ssd: candidate row %u outside table", cand_rows[i]);
+            return PG_ERR_UNSUPPORTED;
+        }
 
-    std::vector<double> quality(n);
-    const bool bail = !pg::ssd_norm_quality_host(rel, n, norm_quality_score, quality.data());
-    if (bail) {        // "all item score are zeros": the reference returns the items unchanged
-        for (uint32_t i = 0; i < n; ++i) out_idx[i] = i;
-        *out_count = n;
-        if (out_quality) for (uint32_t i = 0; i < n; ++i) out_quality[i] = rel[i];
-        return PG_OK;
+    return pg::ssd_one(ctx, t, cand_rows, nullptr, t->dim, rel, n, gamma, topn, window, normalize_emb, ensure_pos_similarity,
+                       norm_quality_score, use_ssd_star, out_idx, out_count, out_quality);
+}
+
+int pg_ssd_emb(pg_ctx* ctx, const float* emb, uint32_t dim, const double* rel, uint32_t n, double gamma, uint32_t topn,
+               uint32_t window, int normalize_emb, int ensure_pos_similarity, int norm_quality_score, int use_ssd_star,
+               uint32_t* out_idx, uint32_t* out_count, double* out_quality) {
+    PG_REQUIRE(ctx && out_count, "pg_ssd_emb: NULL argument");
+    *out_count = 0;
+    if (n == 0 || topn == 0) return PG_OK;
+    PG_REQUIRE(emb && rel && out_idx, "pg_ssd_emb: NULL argument");
+    PG_REQUIRE(dim >= 1, "pg_ssd_emb: dim must be >= 1");
+    PG_REQUIRE(norm_quality_score >= 0 && norm_quality_score <= 2, "pg_ssd_emb: norm_quality_score must be 0, 1 or 2");
+    // (dim first: dim + 1 must not wrap)
+    if (n > 8192 || dim > pg::kSsdMaxDim || dim + (ensure_pos_similarity ? 1u : 0u) > pg::kSsdMaxDim) {
+        pg::set_error("pg_ssd_emb: %u candidates x %u dims%s unsupported (<= 8192 x %u)", n, dim, ensure_pos_similarity ? " + 1" : "",
+                      pg::kSsdMaxDim);
+        return PG_ERR_UNSUPPORTED;
     }
-    if (out_quality) for (uint32_t i = 0; i < n; ++i) out_quality[i] = quality[i];
-
-    const uint32_t T = n < topn ? n : topn;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    pg::TableRead tr(t->rw);
-    void* io;
-    int rc;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    if ((rc = pg::scratch_reserve(ctx, 5, al((size_t)n * 4) + al((size_t)n * 8) + al((size_t)T * 4), &io))) return rc;
-    uint32_t* d_cand = (uint32_t*)io;
-    double* d_rel = (double*)((char*)io + al((size_t)n * 4));
-    uint32_t* d_out = (uint32_t*)((char*)io + al((size_t)n * 4) + al((size_t)n * 8));
-    PG_HIP(hipMemcpyAsync(d_cand, cand_rows, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-    PG_HIP(hipMemcpyAsync(d_rel, quality.data(), (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = pg::ssd_run_locked(ctx, t, d_cand, d_rel, 1, n, gamma, T, window, normalize_emb, ensure_pos_similarity, use_ssd_star, d_out)))
-        return rc;
-    PG_HIP(hipMemcpyAsync(out_idx, d_out, (size_t)T * 4, hipMemcpyDeviceToHost, ctx->stream));
-    PG_HIP(hipStreamSynchronize(ctx->stream));
-    *out_count = T;
-    return PG_OK;
+    return pg::ssd_one(ctx, nullptr, nullptr, emb, dim, rel, n, gamma, topn, window, normalize_emb, ensure_pos_similarity,
+                       norm_quality_score, use_ssd_star, out_idx, out_count, out_quality);
 }
 
 }  // extern "C"

@@ -1236,6 +1236,22 @@ def ssd(ctx: Context, table: Table, cand_rows, rel, gamma: float, topn: int, win
     return out[:cnt.value], qual[:c.shape[0]]
 
 
+def ssd_emb(ctx: Context, emb, rel, gamma: float, topn: int, window: int, normalize_emb: bool = True,
+            ensure_pos_similarity: bool = True, norm_quality_score: int = 0, use_ssd_star: bool = False):
+    """pg_ssd_emb: pg_ssd over the candidates' own fp32 embeddings [n][dim] (any dim).  Returns (picked indices, quality scores)."""
+    e = np.ascontiguousarray(emb, dtype=np.float32)
+    r = np.ascontiguousarray(rel, dtype=np.float64)
+    n = r.shape[0]
+    e = e.reshape(n, -1)
+    out = np.zeros(max(n, 1), dtype=np.uint32)
+    qual = np.zeros(max(n, 1), dtype=np.float64)
+    cnt = C.c_uint32()
+    _lib.check(ctx.L.pg_ssd_emb(ctx.h, _ptr(e), e.shape[1], _ptr(r), n, gamma, topn, window, int(normalize_emb),
+                                int(ensure_pos_similarity), int(norm_quality_score), int(use_ssd_star), _ptr(out),
+                                C.byref(cnt), _ptr(qual)))
+    return out[:cnt.value], qual[:n]
+
+
 F_I32, F_I64, F_F32, F_F64 = 1, 2, 3, 4
 _F_NP = {F_I32: np.int32, F_I64: np.int64, F_F32: np.float32, F_F64: np.float64}
 

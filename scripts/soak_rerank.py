@@ -1,4 +1,5 @@
-"""Soak: DPPSort / SSDSort on the device against the oracle over random candidate sets — sizes 2..1500, dims 64 / 128, clustered
+"""Soak: DPPSort / SSDSort on the device against the oracle over random candidate sets — sizes 2..1500, dims 64 / 128 (SSD also: dim 192,
+which only its generic kernel serves, and 5000 candidates, where its multi-workgroup kernel reduces over more than 64 workgroups), clustered
 embeddings, exact duplicates among the candidates, relevance with ties / negative values / a wide range, every option switch,
 random topn / window / alpha / gamma.  Pick sequences must be identical.
 Usage: soak_rerank.py [seconds] [seed]"""
@@ -34,7 +35,7 @@ ctx = pa.Context(0)
 t_end = time.time() + seconds
 cases = bad = skipped = noise = 0
 while time.time() < t_end:
-    d = int(rng.choice([64, 128]))
+    d = int(rng.choice([64, 128, 192]))
     n_tab = int(rng.choice([2000, 20000]))
     nc = int(rng.choice([1, 3, 12, 200]))
     centers = rng.standard_normal((nc, d)).astype(np.float32)
@@ -42,7 +43,8 @@ while time.time() < t_end:
     t = pa.Table(ctx, n_tab, d)
     t.upload(tab)
     for _ in range(12):
-        n = int(rng.choice([2, 5, 17, 100, 500, 800, 1500]))
+        is_dpp = d != 192 and rng.random() < 0.5
+        n = int(rng.choice([2, 5, 17, 100, 500, 800, 1500] + ([] if is_dpp else [5000])))
         cand = rng.choice(n_tab, n, replace=n > n_tab // 2).astype(np.uint32)
         dups = bool(n >= 5 and rng.random() < 0.4)            # exact duplicates among the candidates
         if dups:
@@ -52,10 +54,12 @@ while time.time() < t_end:
         rel = rng.random(n) if rk == 0 else (np.round(rng.random(n), 1) if rk == 1 else (rng.standard_normal(n) if rk == 2 else rng.random(n) * 5))
         rel = np.sort(rel)[::-1].copy()
         topn = int(rng.choice([1, 10, 37, 100, n, n + 5]))
+        if n > 1500:
+            topn = min(topn, 100)                                # (thousands of picks over 5000 candidates are seconds of oracle time)
         window = int(rng.choice([1, 2, 5, 10, 30]))
         desc = dict(d=d, n=n, topn=topn, window=window, dups=dups, rel_max=float(np.abs(rel).max()))
         try:
-            if rng.random() < 0.5:
+            if is_dpp:
                 alpha = float(rng.choice([0.05, 0.5, 1.0, 2.0]))
                 norm, pos, mode = bool(rng.integers(0, 2)), bool(rng.integers(0, 2)), int(rng.integers(0, 3))
                 hk = rng.standard_normal((n, int(rng.choice([8, 48])))) if rng.random() < 0.3 else None
