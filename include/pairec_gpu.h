@@ -112,7 +112,9 @@ int pg_synchronize(pg_ctx* ctx);
  * more written rows than this share of the table are refreshed in full; a table's write log is dropped past it too); for
  * coalescers created afterwards "coalescer_max_exclude" (default 0, 0..4096: the longest list pg_coalescer_recall_exclude takes;
  * a value outside the range is PG_ERR_INVALID); for pg_cf_recall "cf_lds_max_pairs" (default and largest value 6144: a request
- * of at most this many (trigger, neighbour) pairs keeps its table in LDS, a larger one in global memory; 0 = always global).
+ * of at most this many (trigger, neighbour) pairs keeps its table in LDS, a larger one in global memory; 0 = always global);
+ * for pg_fanin_merge_dev "fanin_lds_max_cap" (default and largest value 8192 = PG_FANIN_LDS_MAX_CAP: a merge of at most this
+ * many candidates per request keeps its table in LDS, a larger one in context scratch; 0 = always scratch).
  * value is parsed as a number. */
 int pg_set_option(pg_ctx* ctx, const char* name, const char* value);
 int pg_device_malloc(pg_ctx* ctx, size_t bytes, void** out);
@@ -723,6 +725,57 @@ int pg_cf_recall_dev(pg_ctx* ctx, const pg_simtable* s, const uint32_t* d_trigge
                      const uint32_t* trigger_offsets, uint32_t nq, uint32_t k, const pg_cf_opts* opts, uint64_t* d_out_rows,
                      double* d_out_scores, uint32_t* out_count);
 
+/* Fan-in + UniqueFilter on the device (csrc/fanin.hip): the answers of a request's recalls merged into one
+ * candidate list without leaving device memory.  RecallService.GetItems (service/recall.go:53-153; the fan-in :126-150) runs
+ * every recall of the scene's category and concatenates what they return; UniqueFilter (filter/unique_filter.go:26-49) dedups
+ * by item id: the first occurrence wins, a later one only leaves its score in RecallScores[its RetrieveId].
+ *   Sources   1 .. PG_FANIN_MAX_SOURCES per call, nq <= 256 requests.  Source s: d_rows uint64 [nq][k] — global row ids of ONE
+ *             item table (every id of the call belongs to it), UINT64_MAX = padding, anywhere in a list — and d_scores [nq][k],
+ *             float (score_f64 = 0: the vector recalls, pg_i2i_recall) or double (score_f64 != 0: pg_cf_recall_dev).  1 <= k and
+ *             cap = the sum of the sources' k <= PG_FANIN_MAX_CAP (pg_recommend_dnn3_dev's limit for k); anything else is
+ *             PG_ERR_UNSUPPORTED / PG_ERR_INVALID as in pg_exclude_compact_dev, the context left usable.  The k are host values,
+ *             every pointer is device memory; outputs must not overlap inputs.
+ *   Answer    DEFINED bit for bit: UniqueFilter over the concatenation "sources as given, entries in list order, padding
+ *             dropped" (the reference's source order is goroutine completion order; here it is the order given).  No score is
+ *             touched by arithmetic: doubles travel as bits (NaN payloads, -0.0, infinities, subnormals survive), floats are
+ *             widened exactly as vector_recall.go:98 does (a signalling NaN comes out quiet, as from any conversion).
+ *               d_out_rows [nq][cap]            the distinct ids in order of first occurrence, then UINT64_MAX
+ *               d_out_score [nq][cap] fp64      the FIRST occurrence's score (Item.Score); padding -inf
+ *               d_out_source [nq][cap] uint8    the first occurrence's source (RetrieveId); padding 0xFF
+ *               d_out_recall_scores [n_sources][nq][cap] fp64 (optional)
+ *                                               per slot and source that source's score for the item
+ *                                               (RecallScores[RetrieveId]); where a source holds the id more than once, its LAST
+ *                                               occurrence's (unique_filter.go:43 overwrites) — Item.Score stays the first's;
+ *                                               where it does not hold the item, and in padding slots, the quiet NaN
+ *                                               0x7FF8000000000000
+ *               d_out_source_mask [nq][cap] uint32 (optional)
+ *                                               bit s set iff source s holds the item; padding 0.  The reference creates
+ *                                               RecallScores only once a duplicate is seen: a mask with more than one bit is
+ *                                               that condition for duplicates across recalls (for an id repeated inside one
+ *                                               recall only, the reference also creates the map, with that recall's last
+ *                                               score alone — which is what the plane carries either way)
+ *               d_out_count [nq]                the number of distinct ids
+ *             AlgoScores are not merged: recalls carry none.
+ *   Tiers     one workgroup per request and an open-addressed table keyed by id; the walk takes PG_FANIN_CHUNK positions at a
+ *             time.  cap <= PG_FANIN_LDS_MAX_CAP ("fanin_lds_max_cap") and ids that span less than 2^32 - 1 keep the table in
+ *             LDS, keyed on the 32-bit distance to the request's smallest id; everything else — a larger cap, ids further apart
+ *             — uses context scratch with full 64-bit keys (12 B x the power of two >= 2 cap, per request).  Two ids that differ
+ *             only above bit 32 are never merged.
+ *   Stream    one launch on the context's stream, no synchronisation (pg_synchronize, or any later call that does). */
+#define PG_FANIN_MAX_SOURCES 8
+#define PG_FANIN_MAX_CAP 16384
+#define PG_FANIN_LDS_MAX_CAP 8192
+#define PG_FANIN_CHUNK 1024
+typedef struct {
+    const uint64_t* d_rows;    /* [nq][k] */
+    const void*     d_scores;  /* [nq][k] float, or double with score_f64 != 0 */
+    uint32_t        k;
+    int             score_f64;
+} pg_fanin_source;
+int pg_fanin_merge_dev(pg_ctx* ctx, const pg_fanin_source* sources, uint32_t n_sources, uint32_t nq, uint64_t* d_out_rows,
+                       double* d_out_score, uint8_t* d_out_source, double* d_out_recall_scores, uint32_t* d_out_source_mask,
+                       uint32_t* d_out_count);
+
 /* Refresh: bring an existing index back to its table's current rows KEEPING ITS CENTROIDS — cheap when few
  * rows were written, several times cheaper than pg_index_build when all of them were (nothing is trained).  Nothing changes
  * until it is called: a written table still makes its index stale.
@@ -835,6 +888,26 @@ int pg_recommend_dnn3_begin(pg_ctx* ctx, const pg_table* t, const pg_model* m, c
                             uint32_t* d_out_order, uint32_t* d_out_count, pg_ticket** out);
 /* scan_ms (optional): the batch's scan-stage launches, HIP-event timed (what pg_last_scan_kernel_ms reports) */
 int pg_recommend_end(pg_ctx* ctx, pg_ticket* ticket, double* scan_ms);
+
+/* The stages behind the recall for candidate lists the caller made — the merged answer of several recalls
+ * (pg_fanin_merge_dev: service/recall.go:126-150 + filter/unique_filter.go:26-49), or any other [nq][cap] lists: rank every
+ * candidate with the DNN3 `m` → ScoreRewrite / RankScore fusion → ItemRankScore sort, as pg_recommend_dnn3_dev runs them
+ * behind its vector recall, with one version of the table for the whole call.
+ *   In        d_rows [nq][cap] global row ids of `t` (UINT64_MAX = padding; a row outside `t` counts as padding), d_score
+ *             [nq][cap] fp64 — Item.Score, what "current_score" binds to, with all 64 bits — d_count [nq] (optional: slots from
+ *             d_count[q] on are padding whatever they hold), d_user_vecs [nq][dim]; 1 <= nq <= 256, 1 <= cap <= 16384; model,
+ *             expression and rank_var as pg_recommend_dnn3_dev.  These are pg_fanin_merge_dev's d_out_rows / d_out_score /
+ *             d_out_count as they are.
+ *   Out       all [nq][cap]: the model's scores, the fused fp64 scores, d_out_order = each request's positions sorted by fused
+ *             score, descending.  Padding slots: model score 0, fused NaN, last in the order.  Fed one vector recall's [nq][k]
+ *             answer with its scores widened, the three outputs are bit for bit pg_recommend_dnn3_dev's.
+ *   Errors    a filtered view is refused (PG_ERR_UNSUPPORTED) as there; PG_ERR_ARITH when the RankScore divides by zero.  The
+ *             call returns synchronised.
+ * Not served here yet: the coalescer, scenes, the shard group, a DPP stage behind the sort and the _begin / _end ticket form. */
+int pg_recommend_candidates_dnn3_dev(pg_ctx* ctx, const pg_table* t, const pg_model* m, const pg_expr* e, const char* rank_var,
+                                     const float* d_user_vecs, uint32_t nq, uint32_t cap, const uint64_t* d_rows,
+                                     const double* d_score, const uint32_t* d_count, float* d_out_rank_scores,
+                                     double* d_out_fused, uint32_t* d_out_order);
 
 /* ---- shard group: one process, several GPUs --------------------------------------------------------
  * BASELINE.json configs[4] / SURVEY.md 8e behind the C ABI (a cgo host cannot join a torch.distributed job): the item

@@ -47,6 +47,7 @@ EXPORTS = [
     "pg_exclude_compact_dev", "pg_recall_topk_exclude", "pg_recall_topk_exclude_dev", "pg_i2i_recall_exclude",
     "pg_coalescer_recall_exclude",
     "pg_simtable_create", "pg_simtable_upload", "pg_simtable_info", "pg_simtable_destroy", "pg_cf_recall", "pg_cf_recall_dev",
+    "pg_fanin_merge_dev", "pg_recommend_candidates_dnn3_dev",
 ]
 
 
@@ -97,6 +98,10 @@ class PgRecallExcludeOpts(C.Structure):
 
 class PgCfOpts(C.Structure):
     _fields_ = [("normalize", C.c_int), ("excl_rows", C.c_void_p), ("excl_offsets", C.c_void_p)]
+
+
+class PgFaninSource(C.Structure):
+    _fields_ = [("d_rows", C.c_void_p), ("d_scores", C.c_void_p), ("k", C.c_uint32), ("score_f64", C.c_int)]
 
 
 class PgIndexRefreshParams(C.Structure):
@@ -219,6 +224,8 @@ def load():
         "pg_simtable_destroy": [vp, vp],
         "pg_cf_recall": [vp, vp, vp, vp, vp, u32, u32, P(PgCfOpts), vp, vp, vp],
         "pg_cf_recall_dev": [vp, vp, vp, vp, vp, u32, u32, P(PgCfOpts), vp, vp, vp],
+        "pg_fanin_merge_dev": [vp, P(PgFaninSource), u32, u32, vp, vp, vp, vp, vp, vp],
+        "pg_recommend_candidates_dnn3_dev": [vp, vp, vp, vp, C.c_char_p, vp, u32, u32, vp, vp, vp, vp, vp, vp],
         "pg_index_refresh": [vp, vp, P(PgIndexRefreshParams)],
         "pg_index_refresh_stats": [vp, P(PgIndexRefreshStats)],
         "pg_index_screen_probe": [vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, vp, vp],

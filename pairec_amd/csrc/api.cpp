@@ -54,6 +54,7 @@ static void knobs_from_env(Knobs* k) {
     k->coalescer_max_exclude = (uint32_t)std::min(std::max(num("PG_COALESCER_MAX_EXCLUDE", 0), 0.0), (double)kMaxExclude);
     k->index_refresh_full_fraction = num("PG_INDEX_REFRESH_FULL_FRACTION", 0.1);
     k->cf_lds_max_pairs = (uint32_t)std::min(std::max(num("PG_CF_LDS_MAX_PAIRS", 6144), 0.0), 6144.0);
+    k->fanin_lds_max_cap = (uint32_t)std::min(std::max(num("PG_FANIN_LDS_MAX_CAP", 8192), 0.0), 8192.0);
 }
 
 static thread_local std::string g_err;
@@ -208,6 +209,7 @@ int pg_set_option(pg_ctx* ctx, const char* name, const char* value) {
         k.coalescer_max_exclude = (uint32_t)v;
     }
     else if (n == "cf_lds_max_pairs") k.cf_lds_max_pairs = v >= 0 ? (v <= 6144 ? (uint32_t)v : 6144u) : 0u;
+    else if (n == "fanin_lds_max_cap") k.fanin_lds_max_cap = v >= 0 ? (v <= 8192 ? (uint32_t)v : 8192u) : 0u;
     else if (n == "index_refresh_full_fraction") k.index_refresh_full_fraction = v >= 0 ? (v <= 1 ? v : 1.0) : 0.0;
     else {
         pg::set_error("pg_set_option: unknown option \"%s\"", name);

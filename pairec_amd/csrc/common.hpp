@@ -102,6 +102,7 @@ struct Knobs {
     uint32_t index_where_cache = 4;         // PG_INDEX_WHERE_CACHE: filtered lists an index keeps per filter (0: built per call, freed after it)
     bool index_route_where = false;         // PG_INDEX_ROUTE_WHERE: pg_recall_topk_where on a table with a current attached index searches it
     uint32_t cf_lds_max_pairs = 6144;           // PG_CF_LDS_MAX_PAIRS: a collaborative-filter request of at most this many (trigger, neighbour) pairs keeps its table in LDS (cf.hip: 12288 slots in 144 KiB, load factor <= 0.5; larger values are cut to that); above, in global memory
+    uint32_t fanin_lds_max_cap = 8192;          // PG_FANIN_LDS_MAX_CAP: a fan-in merge of at most this many candidates per request keeps its table in LDS (fanin.hip: 16384 slots of 8 B, load factor <= 0.5; larger values are cut to that); above, in context scratch
     double index_refresh_full_fraction = 0.1;   // PG_INDEX_REFRESH_FULL_FRACTION: pg_index_refresh in auto mode re-assigns every row once the written rows exceed this share of the table
 };
 
@@ -264,7 +265,7 @@ struct pg_ctx {
     //   16 pg_features_eval_dev: the bound variables   17 index.hip: bounds, probe thresholds and list counts of an index recall
     //   18 recall.hip: the over-fetched answer, lists and counts of a recall with exclusion lists
     //   19 cf.hip: status and counts, staged offsets and lists, the global tier's tables, the items to order, the over-fetched answer
-    pg::Scratch scratch[20];
+    pg::Scratch scratch[21];
     std::mutex pool_mu;          // guards pipe_free
     std::vector<pg::PipeRun*> pipe_free;     // per-batch status blocks / events of the device-resident pipelines
     std::map<const void*, size_t> dyn_lds;   // kernels whose dynamic-LDS limit was raised on this device
@@ -520,6 +521,9 @@ constexpr uint32_t kMaxExclude = 4096;      // ids in one request's list
 int exclude_compact_locked(pg_ctx* ctx, const uint64_t* d_rows, const float* d_scores, uint32_t nq, uint32_t k_in,
                            const uint64_t* d_excl_rows, const uint32_t* d_excl_offsets, uint32_t k_out, float pad_score,
                            uint64_t* d_out_rows, float* d_out_scores, uint32_t* d_out_count);
+// fanin.hip: the merge of n_src recall answers per request (one launch, no synchronisation; arguments as pg_fanin_merge_dev, checked by the caller)
+int fanin_merge_locked(pg_ctx* ctx, const pg_fanin_source* src, uint32_t n_src, uint32_t nq, uint64_t* d_out_rows, double* d_out_score,
+                       uint8_t* d_out_source, double* d_out_recall_scores, uint32_t* d_out_source_mask, uint32_t* d_out_count);
 // index.hip: the attached index pg_recall_topk_where searches ("index_route_where" set and the index current), or NULL; the
 // filtered search itself (a stale, non-finite, dense or overflowing batch: recall_where_locked)
 pg_index* index_route_where(const pg_ctx* ctx, const pg_table* t);

@@ -19,13 +19,14 @@ namespace pg {
 // decoder of the reference performs (algorithm/eas/easyrec_response.go:479-483), for all variables of the expression
 struct VarSrc { int8_t src[32]; };
 // (src >= 0: score plane; -1: Item.Score; <= -2: the f64 result of score rewrite -2 - src, rw [n_rewrites][n])
-__global__ void bind_vars_kernel(const float* __restrict__ recall, const float* __restrict__ rank, size_t rank_stride,
-                                 uint32_t n, uint32_t nv, VarSrc vs, double* __restrict__ vars, uint32_t* __restrict__ err,
-                                 const double* __restrict__ rw, int zero_err) {
+// Item.Score is the recall's fp32 score widened, or — recall64 != NULL, candidates the caller made — an fp64 score as it is
+__global__ void bind_vars_kernel(const float* __restrict__ recall, const double* __restrict__ recall64, const float* __restrict__ rank,
+                                 size_t rank_stride, uint32_t n, uint32_t nv, VarSrc vs, double* __restrict__ vars,
+                                 uint32_t* __restrict__ err, const double* __restrict__ rw, int zero_err) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (zero_err && i < (uint32_t)kMaxQueries) err[i] = 0; // the RankScore flags of the evaluations behind this launch
     if (i >= n) return;
-    const double a = (double)recall[i];
+    const double a = recall64 ? recall64[i] : (double)recall[i];
     for (uint32_t v = 0; v < nv; ++v) {
         const int sa = vs.src[v];
         vars[(size_t)v * n + i] = sa >= 0 ? (double)rank[(size_t)sa * rank_stride + i] : (sa == -1 ? a : rw[(size_t)(-2 - sa) * n + i]);
@@ -35,10 +36,17 @@ __global__ void bind_vars_kernel(const float* __restrict__ recall, const float* 
 // A table with fewer than k rows leaves padding slots (row = UINT64_MAX, recall score = -inf) at the end of every
 // request.  They are not items: their model scores are reported as 0 and their fused score as NaN, which the sort
 // places last in either direction, so a page never starts with them.
+// In lists the caller made (cand != 0: k entries per request, count optional) a row outside the table [row_off, row_off + nrows)
+// and every slot from the request's count on are padding too.
 __global__ void mask_pads_kernel(const uint64_t* __restrict__ rows, uint32_t n, float* __restrict__ rank, size_t rank_stride,
-                                 int n_algos, double* __restrict__ fused) {
+                                 int n_algos, double* __restrict__ fused, int cand, uint64_t row_off, uint64_t nrows,
+                                 const uint32_t* __restrict__ count, uint32_t k) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n || rows[i] != ~0ull) return;
+    if (i >= n) return;
+    const uint64_t r = rows[i];
+    bool pad = r == ~0ull;
+    if (cand) pad = pad || r < row_off || r - row_off >= nrows || (count && i % k >= count[i / k]);
+    if (!pad) return;
     for (int a = 0; a < n_algos; ++a) rank[(size_t)a * rank_stride + i] = 0.0f;
     fused[i] = __longlong_as_double(0x7FF8000000000000ll);
 }
@@ -161,7 +169,8 @@ int post_scratch(pg_ctx* ctx, const RecommendCall& c, uint32_t nq, PostScratch* 
 // The fusion itself: ScoreRewrite sources first, then RankScore, over n items whose planes lie rank_stride apart; d_vars holds
 // (widest expression's variables + number of rewrites) x n doubles; d_err kMaxQueries flags (one per items_per_flag items)
 int fuse_scores_enqueue_locked(pg_ctx* ctx, const pg_expr* e, const int* var_src, int nv, const float* d_recall, const float* d_rank,
-                               size_t rank_stride, uint32_t n, uint32_t items_per_flag, double* d_vars, uint32_t* d_err, double* d_fused) {
+                               size_t rank_stride, uint32_t n, uint32_t items_per_flag, double* d_vars, uint32_t* d_err, double* d_fused,
+                               const double* d_recall64) {
     hipStream_t st = ctx->stream;
     int rc;
     VarSrc vs;
@@ -178,7 +187,7 @@ int fuse_scores_enqueue_locked(pg_ctx* ctx, const pg_expr* e, const int* var_src
         for (int i = 0; i < 32; ++i) vs.src[i] = i < nvr ? (int8_t)var_src[at + i] : (int8_t)-1;
         at += nvr;
         if (nvr > 0 || !zeroed) {
-            bind_vars_kernel<<<bind_grid, 256, 0, st>>>(d_recall, d_rank, rank_stride, n, (uint32_t)nvr, vs, d_vars, d_err, nullptr, zeroed ? 0 : 1);
+            bind_vars_kernel<<<bind_grid, 256, 0, st>>>(d_recall, d_recall64, d_rank, rank_stride, n, (uint32_t)nvr, vs, d_vars, d_err, nullptr, zeroed ? 0 : 1);
             PG_HIP(hipGetLastError());
             zeroed = true;
         }
@@ -186,7 +195,7 @@ int fuse_scores_enqueue_locked(pg_ctx* ctx, const pg_expr* e, const int* var_src
     }
     for (int i = 0; i < 32; ++i) vs.src[i] = i < nv ? (int8_t)var_src[i] : (int8_t)-1;
     if (nv > 0) {
-        bind_vars_kernel<<<bind_grid, 256, 0, st>>>(d_recall, d_rank, rank_stride, n, (uint32_t)nv, vs, d_vars, d_err, d_rw, zeroed ? 0 : 1);
+        bind_vars_kernel<<<bind_grid, 256, 0, st>>>(d_recall, d_recall64, d_rank, rank_stride, n, (uint32_t)nv, vs, d_vars, d_err, d_rw, zeroed ? 0 : 1);
         PG_HIP(hipGetLastError());
     } else if (!zeroed) {
         PG_HIP(hipMemsetAsync(d_err, 0, (size_t)kMaxQueries * 4, st));
@@ -201,11 +210,12 @@ int post_fuse_sort_locked(pg_ctx* ctx, const RecommendCall& c, uint32_t q0, uint
     const size_t o = (size_t)q0 * c.k;
     hipStream_t st = ctx->stream;
     int rc;
-    if ((rc = fuse_scores_enqueue_locked(ctx, c.e, c.var_src, c.nv, c.d_recall + o, c.d_rank + o, c.rank_stride, n, c.k, ps.d_vars, ps.d_err,
-                                         c.d_fused + o)))
+    if ((rc = fuse_scores_enqueue_locked(ctx, c.e, c.var_src, c.nv, c.d_recall ? c.d_recall + o : nullptr, c.d_rank + o, c.rank_stride, n, c.k,
+                                         ps.d_vars, ps.d_err, c.d_fused + o, c.d_score64 ? c.d_score64 + o : nullptr)))
         return rc;
-    if (c.pads) {
-        mask_pads_kernel<<<(n + 255) / 256, 256, 0, st>>>(c.d_rows + o, n, c.d_rank + o, c.rank_stride, c.planes(), c.d_fused + o);
+    if (c.pads || c.cand) {
+        mask_pads_kernel<<<(n + 255) / 256, 256, 0, st>>>(c.d_rows + o, n, c.d_rank + o, c.rank_stride, c.planes(), c.d_fused + o, c.cand ? 1 : 0,
+                                                          c.t->row_offset, c.t->rows, c.d_cand_count ? c.d_cand_count + q0 : nullptr, c.k);
         PG_HIP(hipGetLastError());
     }
     return sort_dev_locked(ctx, c.d_fused + o, ps.d_off, nq, n, c.k, 1, c.d_order + o);
@@ -440,6 +450,49 @@ int pg_fuse_scores_dev(pg_ctx* ctx, const pg_expr* e, const char* const* plane_n
         pg::set_expr_arith_error(e);
         return PG_ERR_ARITH;
     }
+    return PG_OK;
+}
+
+int pg_recommend_candidates_dnn3_dev(pg_ctx* ctx, const pg_table* t, const pg_model* m, const pg_expr* e, const char* rank_var,
+                                     const float* d_user_vecs, uint32_t nq, uint32_t cap, const uint64_t* d_rows,
+                                     const double* d_score, const uint32_t* d_count, float* d_out_rank_scores,
+                                     double* d_out_fused, uint32_t* d_out_order) {
+    PG_REQUIRE(ctx && t && m && e && rank_var && d_user_vecs && d_rows && d_score && d_out_rank_scores && d_out_fused && d_out_order,
+               "pg_recommend_candidates_dnn3_dev: NULL argument");
+    PG_REQUIRE(nq > 0 && nq <= (uint32_t)pg::kMaxQueries && cap > 0 && cap <= 16384, "pg_recommend_candidates_dnn3_dev: bad nq / cap");
+    PG_REQUIRE(m->kind == PG_MODEL_DNN3 && t->dim == m->d_item && m->d_user == t->dim,
+               "pg_recommend_candidates_dnn3_dev: the model must be DNN3 with d_user = d_item = the table's dim");
+    PG_REQUIRE(m->n_out == 1, "pg_recommend_candidates_dnn3_dev: a multi-output model needs its output names (a scene)");
+    if (t->d_row_map) {                  // as recommend_enqueue: the rank stage gathers the rows from this table, a view reports its source's ids
+        pg::set_error("pg_recommend_candidates_dnn3_dev: the table is a filtered view (pg_table_view_create) — views serve the recall calls only");
+        return PG_ERR_UNSUPPORTED;
+    }
+    pg::ExprHold hold;
+    hold.take(e);
+    std::vector<int> var_src;
+    int rc;
+    if ((rc = pg::recommend_bind_vars(e, &rank_var, 1, &var_src, "pg_recommend_candidates_dnn3_dev"))) return rc;
+    pg::RecommendCall c;
+    c.t = t; c.algos[0].m = m; c.n_algos = 1; c.e = e; c.var_src = var_src.data(); c.nv = pg_expr_num_vars(e);
+    c.d_queries = d_user_vecs; c.nq = nq; c.k = cap;
+    c.d_rows = const_cast<uint64_t*>(d_rows);        // (the stages behind the recall only read the rows)
+    c.d_score64 = d_score; c.d_cand_count = d_count; c.cand = true;
+    c.d_rank = d_out_rank_scores; c.rank_stride = (size_t)nq * cap; c.d_fused = d_out_fused; c.d_order = d_out_order;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    PG_HIP(hipSetDevice(ctx->device));
+    pg::TimersScope quiet(ctx, c.timers);
+    pg::TableRead tr(t->rw);             // rank and the padding test read one version of the table
+    pg::PostScratch ps;
+    if ((rc = pg::post_scratch(ctx, c, nq, &ps))) return rc;
+    if ((rc = pg::recommend_post_locked(ctx, c, 0, nq, ps))) return rc;
+    uint32_t* const h_flags = ctx->h_status + pg::kExprFlagAt;
+    PG_HIP(hipMemcpyAsync(h_flags, ps.d_err, (size_t)nq * 4, hipMemcpyDeviceToHost, ctx->stream));
+    PG_HIP(hipStreamSynchronize(ctx->stream));
+    for (uint32_t q = 0; q < nq; ++q)
+        if (h_flags[q]) {
+            pg::set_expr_arith_error(e);
+            return PG_ERR_ARITH;
+        }
     return PG_OK;
 }
 

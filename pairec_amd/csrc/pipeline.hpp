@@ -63,6 +63,11 @@ struct RecommendCall {
     uint32_t nq = 0, k = 0;
     uint64_t* d_rows = nullptr;
     float* d_recall = nullptr;
+    // candidates the caller made instead of a recall's answer (pg_recommend_candidates_dnn3_dev): Item.Score is d_score64, fp64,
+    // d_recall NULL; rows outside the table and slots from d_cand_count[q] (optional) on are padding, masked like `pads`
+    bool cand = false;
+    const double* d_score64 = nullptr;
+    const uint32_t* d_cand_count = nullptr;
     float* d_rank = nullptr;           // planes() planes of rank_stride floats, each [nq][k]
     size_t rank_stride = 0;
     // score planes: algorithm a writes planes plane0[a] .. plane0[a] + (its model's outputs) - 1; n_planes = 0 means
@@ -104,7 +109,8 @@ struct PostScratch {
 int post_scratch(pg_ctx* ctx, const RecommendCall& c, uint32_t nq, PostScratch* ps);
 int post_fuse_sort_locked(pg_ctx* ctx, const RecommendCall& c, uint32_t q0, uint32_t nq, const PostScratch& ps);
 int fuse_scores_enqueue_locked(pg_ctx* ctx, const pg_expr* e, const int* var_src, int nv, const float* d_recall, const float* d_rank,
-                               size_t rank_stride, uint32_t n, uint32_t items_per_flag, double* d_vars, uint32_t* d_err, double* d_fused);
+                               size_t rank_stride, uint32_t n, uint32_t items_per_flag, double* d_vars, uint32_t* d_err, double* d_fused,
+                               const double* d_recall64 = nullptr);
 int rerank_select_locked(pg_ctx* ctx, const RecommendCall& c, uint32_t q0, uint32_t nq, const PostScratch& ps);
 int rerank_run_locked(pg_ctx* ctx, const RecommendCall& c, uint32_t q0, uint32_t nq, const PostScratch& ps);
 

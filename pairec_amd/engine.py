@@ -131,6 +131,59 @@ class Context:
                 self.free(b)
         return out_r, out_s, cnt
 
+    def fanin_merge_dev(self, sources, nq: int, d_out_rows: int, d_out_score: int, d_out_source: int, d_out_recall_scores: int,
+                        d_out_source_mask: int, d_out_count: int) -> None:
+        """pg_fanin_merge_dev: sources = [(d_rows, d_scores, k, score_f64)] of device addresses, outputs device addresses
+        ([nq][cap] with cap = the sum of the k; d_out_recall_scores [n_sources][nq][cap] and d_out_source_mask may be 0 = not
+        wanted).  Enqueued on the context's stream: synchronize() before reading."""
+        arr = (_lib.PgFaninSource * max(len(sources), 1))()
+        for i, (r, sc, k, f64) in enumerate(sources):
+            arr[i] = _lib.PgFaninSource(r or None, sc or None, int(k), int(bool(f64)))
+        _lib.check(self.L.pg_fanin_merge_dev(self.h, arr, len(sources), nq, C.c_void_p(d_out_rows or None), C.c_void_p(d_out_score or None),
+                                             C.c_void_p(d_out_source or None), C.c_void_p(d_out_recall_scores or None),
+                                             C.c_void_p(d_out_source_mask or None), C.c_void_p(d_out_count or None)))
+
+    def fanin_merge(self, sources, recall_scores: bool = True, source_mask: bool = True):
+        """Fan-in + UniqueFilter of a request batch's recall answers on host arrays (pg_fanin_merge_dev): sources = [(rows
+        [nq][k_s] uint64, scores [nq][k_s] float32 or float64)] in the order the reference would concatenate them →
+        (rows [nq][cap] u64, score [nq][cap] f64, source [nq][cap] u8, recall_scores [n][nq][cap] f64 or None,
+        source_mask [nq][cap] u32 or None, count [nq] u32)."""
+        src = []
+        for r, sc in sources:
+            r = np.ascontiguousarray(r, dtype=np.uint64)
+            sc = np.ascontiguousarray(sc)
+            if sc.dtype != np.float64:
+                sc = np.ascontiguousarray(sc, dtype=np.float32)
+            if r.ndim != 2 or sc.shape != r.shape:
+                raise ValueError("fanin_merge: every source is (rows [nq][k], scores [nq][k])")
+            src.append((r, sc))
+        nq = src[0][0].shape[0] if src else 0
+        if any(r.shape[0] != nq for r, _ in src):
+            raise ValueError("fanin_merge: every source holds the same requests")
+        cap, n = sum(r.shape[1] for r, _ in src), len(src)
+        bufs, dev = [], []
+        try:
+            for r, sc in src:
+                bufs += [self.to_device(r), self.to_device(sc)]
+                dev.append((bufs[-2], bufs[-1], r.shape[1], sc.dtype == np.float64))
+            outs = [np.empty((nq, cap), np.uint64), np.empty((nq, cap), np.float64), np.empty((nq, cap), np.uint8),
+                    np.empty((n, nq, cap), np.float64) if recall_scores else None,
+                    np.empty((nq, cap), np.uint32) if source_mask else None, np.empty(nq, np.uint32)]
+            d_out = []
+            for a in outs:
+                d_out.append(self.malloc(max(a.nbytes, 16)) if a is not None else 0)
+                bufs.append(d_out[-1])
+            self.fanin_merge_dev(dev, nq, *d_out)
+            self.synchronize()
+            for a, p_ in zip(outs, d_out):
+                if a is not None and a.nbytes:
+                    self.d2h(a, p_)
+        finally:
+            for b in bufs:
+                if b:
+                    self.free(b)
+        return tuple(outs)
+
     # ---- sort / expr (context-level ops) ----------------------------------------------------
     def sort_scores(self, scores: np.ndarray, seg_offsets: Optional[Sequence[int]] = None,
                     descending: bool = True) -> np.ndarray:
@@ -849,6 +902,33 @@ def recommend_dnn3(ctx: Context, table: Table, model: "RankModel", expr: "Expr",
             ctx.free(p_)
     return tuple(outs)
 
+
+def recommend_candidates_dnn3(ctx: Context, table: Table, model: "RankModel", expr: "Expr", rank_var: str, user_vecs: np.ndarray,
+                              rows: np.ndarray, score: np.ndarray, count=None):
+    """pg_recommend_candidates_dnn3_dev on host arrays: the stages behind the recall for candidate lists the caller made
+    (Context.fanin_merge's rows / score / count): user_vecs [R][dim], rows [R][cap] u64, score [R][cap] f64, count [R] or None →
+    model scores [R][cap] f32, fused [R][cap] f64, order [R][cap] u32."""
+    u = np.ascontiguousarray(user_vecs, dtype=np.float32).reshape(-1, table.dim)
+    r = np.ascontiguousarray(rows, dtype=np.uint64)
+    sc = np.ascontiguousarray(score, dtype=np.float64)
+    R, cap = r.shape
+    if sc.shape != r.shape or u.shape[0] != R:
+        raise ValueError("recommend_candidates_dnn3: rows and score are [R][cap], user_vecs [R][dim]")
+    n = R * cap
+    ins = [ctx.to_device(u), ctx.to_device(r), ctx.to_device(sc),
+           ctx.to_device(np.ascontiguousarray(count, dtype=np.uint32)) if count is not None else 0]
+    bufs = [ctx.malloc(max(n * 4, 16)), ctx.malloc(max(n * 8, 16)), ctx.malloc(max(n * 4, 16))]
+    try:
+        _lib.check(ctx.L.pg_recommend_candidates_dnn3_dev(ctx.h, table.h, model.h, expr.h, rank_var.encode(), ins[0], R, cap, ins[1], ins[2],
+                                                          ins[3] or None, *bufs))
+        outs = [np.zeros((R, cap), np.float32), np.zeros((R, cap), np.float64), np.zeros((R, cap), np.uint32)]
+        for a, p_ in zip(outs, bufs):
+            ctx.d2h(a, p_)
+    finally:
+        for p_ in ins + bufs:
+            if p_:
+                ctx.free(p_)
+    return tuple(outs)
 
 class Coalescer:
     """Cross-request batching (pg_coalescer_*): every method serves ONE request and may be called from any number
