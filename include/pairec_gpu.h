@@ -776,6 +776,66 @@ int pg_fanin_merge_dev(pg_ctx* ctx, const pg_fanin_source* sources, uint32_t n_s
                        double* d_out_score, uint8_t* d_out_source, double* d_out_recall_scores, uint32_t* d_out_source_mask,
                        uint32_t* d_out_count);
 
+/* Recall quotas and the coarse-rank cut on the device (csrc/trim.hip): the merged candidates of a request cut
+ * down between UniqueFilter and RankService.Rank (service/user_recommend.go:105-137) without leaving device memory.
+ * PriorityAdjustCountFilter (filter/priority_adjust_count_filter.go:80-251, recconf.AdjustCountConfig) sorts the union by
+ * Item.Score, groups it by RetrieveId and keeps a quota per recall in the order the config names them; GeneralRank's actions
+ * (service/general_rank/action.go:61-83) sort by the coarse score and keep the first RetainNum (AdjustCountFilter with
+ * ShuffleItem false, filter/adjust_count_filter.go:58-71).  Both are: order by a score, keep the first n_c entries of each class
+ * of sources, class after class.
+ *   In        pg_fanin_merge_dev's outputs as they are, nq <= 256 requests of cap <= PG_TRIM_MAX_CAP entries: d_rows [nq][cap]
+ *             uint64, d_score [nq][cap] fp64, d_source [nq][cap] uint8 (optional when the single rule is PG_TRIM_ANY), d_count
+ *             [nq] (optional), and what is carried along: d_planes_f64 [n_f64][nq][cap] (optional: the per-recall scores),
+ *             d_source_mask [nq][cap] (optional), d_planes_f32 [n_f32][nq][cap] (optional: algorithm scores); at most
+ *             PG_TRIM_MAX_PLANES planes each.  An entry is padding if its row is UINT64_MAX or its position is >= d_count[q];
+ *             padding may sit anywhere, is dropped and never counted.
+ *   Rules     host values, 1 .. PG_TRIM_MAX_RULES of {source, type, count}: type PG_TRIM_FIX or PG_TRIM_ACCUMULATE
+ *             (AdjustCountConfig.Type "fix" / "accumulator"), source < PG_TRIM_MAX_SOURCES, or PG_TRIM_ANY = every source,
+ *             valid only as the single rule (the AdjustCountFilter / top-N case).
+ *   Answer    DEFINED bit for bit — priority_adjust_count_filter.go:92-203 with ensureDiversity == false:
+ *               1. a request's real entries are ordered by d_score descending exactly as pg_sort_scores_dev orders them:
+ *                  -0.0 equals +0.0, NaN sorts last, ties keep input position.  (The reference shuffles the first half of the
+ *                  list and sorts unstably, :88-92, which only randomises the order among equal scores; here it is fixed.)
+ *               2. they are grouped by source in that order (:103-104); entries whose source no rule names are dropped;
+ *               3. rules apply in the order given (:143-203): FIX takes the first min(len, count) entries of its source and
+ *                  leaves the accumulator alone (:145-150); ACCUMULATE takes the first min(len, count - acc) and adds what it
+ *                  took to acc (:193-200);
+ *               4. the output is the takes concatenated in rule order, then padding: row UINT64_MAX, score -inf, source 0xFF,
+ *                  fp64 planes the quiet NaN 0x7FF8000000000000, mask 0, fp32 planes 0; d_out_count[q] = the number taken.
+ *             Every carried array is gathered through the same permutation; no value meets arithmetic, doubles and floats
+ *             travel as bits.  Outputs are [nq][out_cap] (planes [n][nq][out_cap]) with out_cap from pg_trim_out_cap; an output
+ *             is required exactly where its input is given; outputs must not overlap inputs.
+ *   Refused   on the host, the context left usable (PG_ERR_INVALID): no rules (the reference indexes configs[len - 1], :123);
+ *             ACCUMULATE counts that decrease along the list (the reference slices with a negative bound and panics, :193-195); a
+ *             source named twice (the reference emits its items twice); PG_TRIM_ANY beside other rules; a source >=
+ *             PG_TRIM_MAX_SOURCES; an unknown type; rules that name sources without d_source.  More than PG_TRIM_MAX_RULES rules
+ *             and cap outside [1, PG_TRIM_MAX_CAP] are PG_ERR_UNSUPPORTED.
+ *   Width     pg_trim_out_cap: a pure host function (no context, no device) that validates the rules as above and returns
+ *             out_cap = min(cap, the sum of the FIX counts + the largest ACCUMULATE count) — no request can keep more.
+ *   Kernel    one workgroup of PG_TRIM_CHUNK lanes per request: count the classes, plan takes and bases, walk the sorted order
+ *             PG_TRIM_CHUNK positions at a time (an entry's rank within its class from wave ballots and per-wave class counts),
+ *             pad.  Every output element is written exactly once.
+ *   Stream    the score sort and one launch on the context's stream, no synchronisation (as pg_fanin_merge_dev). */
+#define PG_TRIM_FIX 0
+#define PG_TRIM_ACCUMULATE 1
+#define PG_TRIM_ANY 0xFF
+#define PG_TRIM_MAX_RULES 8
+#define PG_TRIM_MAX_SOURCES 8
+#define PG_TRIM_MAX_PLANES 8
+#define PG_TRIM_MAX_CAP 16384
+#define PG_TRIM_CHUNK 1024
+typedef struct {
+    uint8_t  source;   /* < PG_TRIM_MAX_SOURCES, or PG_TRIM_ANY */
+    uint8_t  type;     /* PG_TRIM_FIX / PG_TRIM_ACCUMULATE */
+    uint32_t count;
+} pg_trim_rule;
+int pg_trim_out_cap(const pg_trim_rule* rules, uint32_t n_rules, uint32_t cap, uint32_t* out_cap);
+int pg_candidates_trim_dev(pg_ctx* ctx, const pg_trim_rule* rules, uint32_t n_rules, uint32_t nq, uint32_t cap, const uint64_t* d_rows,
+                           const double* d_score, const uint8_t* d_source, const uint32_t* d_count, const double* d_planes_f64,
+                           uint32_t n_f64, const uint32_t* d_source_mask, const float* d_planes_f32, uint32_t n_f32, uint64_t* d_out_rows,
+                           double* d_out_score, uint8_t* d_out_source, double* d_out_planes_f64, uint32_t* d_out_source_mask,
+                           float* d_out_planes_f32, uint32_t* d_out_count);
+
 /* Refresh: bring an existing index back to its table's current rows KEEPING ITS CENTROIDS — cheap when few
  * rows were written, several times cheaper than pg_index_build when all of them were (nothing is trained).  Nothing changes
  * until it is called: a written table still makes its index stale.
@@ -908,6 +968,44 @@ int pg_recommend_candidates_dnn3_dev(pg_ctx* ctx, const pg_table* t, const pg_mo
                                      const float* d_user_vecs, uint32_t nq, uint32_t cap, const uint64_t* d_rows,
                                      const double* d_score, const uint32_t* d_count, float* d_out_rank_scores,
                                      double* d_out_fused, uint32_t* d_out_order);
+
+/* The coarse-rank cascade over candidate lists the caller made: GeneralRank
+ * (service/general_rank/base_general_rank.go:66-238, action.go:61-83) in front of RankService.Rank, as
+ * service/user_recommend.go:105-137 runs them, in one call with one version of the table:
+ *   1. the coarse DNN3 `m_coarse` scores all cap candidates of every request;
+ *   2. the `e_coarse` fusion: variables `coarse_var` and/or "current_score" (d_score); its fp64 result becomes Item.Score
+ *      (base_general_rank.go:221-227);
+ *   3. ItemRankScore sorts each request by it, descending;
+ *   4. pg_candidates_trim_dev's kernel with the single rule {PG_TRIM_ANY, PG_TRIM_FIX, n_keep} keeps the first n_keep
+ *      (AdjustCountFilter, ShuffleItem false), carrying rows, the coarse fused score, the source and the coarse model score;
+ *   5. the fine DNN3 `m_fine` scores the survivors;
+ *   6. the `e_fine` fusion: variables `fine_var`, `coarse_var` — the carried coarse model score, still in the item's
+ *      algoScores (module/item.go:168-212) — and/or "current_score", now the coarse fused fp64 score;
+ *   7. ItemRankScore sorts the survivors by the fine fused score, descending.
+ *   In        as pg_recommend_candidates_dnn3_dev (d_rows, d_score, d_count optional, d_user_vecs; padding = row UINT64_MAX, a
+ *             row outside `t`, a slot from d_count[q] on) plus d_source [nq][cap] uint8 (optional); 1 <= n_keep <= cap <= 16384;
+ *             both models DNN3 with one output and d_user = d_item = the table's dim; fine_var and coarse_var must differ
+ *             (PG_ERR_INVALID).
+ *   Out       [nq][n_keep]: d_out_rows, d_out_coarse_fused (fp64), d_out_source (required iff d_source is given),
+ *             d_out_model_scores [2][nq][n_keep] float — plane 0 the fine model's scores, plane 1 the coarse model's —,
+ *             d_out_fused (fp64, the fine fusion), d_out_order = each request's positions 0 .. n_keep - 1 sorted by d_out_fused;
+ *             d_out_count [nq] = the survivors.  The coarse stage leaves padding with a NaN score, which sorts last: survivors are
+ *             real candidates as long as there are any, then rows outside `t` (counted, and padding again for the fine stage),
+ *             never UINT64_MAX rows or slots beyond d_count.  Slots behind d_out_count[q]: row UINT64_MAX, coarse fused -inf,
+ *             source 0xFF; padding of the fine stage has model scores 0, fused NaN and is last in the order, as in
+ *             pg_recommend_candidates_dnn3_dev.
+ *   Same as   the stages run one by one: pg_recommend_candidates_dnn3_dev with the coarse model, the trim, pg_rank_dnn3 on the
+ *             surviving rows (model scores and everything carried are bit-identical).
+ *   Errors    a filtered view is refused (PG_ERR_UNSUPPORTED); PG_ERR_ARITH when either RankScore divides by zero.  The call
+ *             returns synchronised.
+ * Not served here yet: what pg_recommend_candidates_dnn3_dev does not serve, an FM + two-tower coarse model, the filter's
+ * diversity branch (ensureDiversity, DiversityDao) and PriorityAdjustCountFilterV2's Expression / Weight. */
+int pg_recommend_cascade_dnn3_dev(pg_ctx* ctx, const pg_table* t, const pg_model* m_coarse, const pg_expr* e_coarse,
+                                  const char* coarse_var, const pg_model* m_fine, const pg_expr* e_fine, const char* fine_var,
+                                  const float* d_user_vecs, uint32_t nq, uint32_t cap, const uint64_t* d_rows, const double* d_score,
+                                  const uint8_t* d_source, const uint32_t* d_count, uint32_t n_keep, uint64_t* d_out_rows,
+                                  double* d_out_coarse_fused, uint8_t* d_out_source, float* d_out_model_scores, double* d_out_fused,
+                                  uint32_t* d_out_order, uint32_t* d_out_count);
 
 /* ---- shard group: one process, several GPUs --------------------------------------------------------
  * BASELINE.json configs[4] / SURVEY.md 8e behind the C ABI (a cgo host cannot join a torch.distributed job): the item

@@ -48,6 +48,7 @@ EXPORTS = [
     "pg_coalescer_recall_exclude",
     "pg_simtable_create", "pg_simtable_upload", "pg_simtable_info", "pg_simtable_destroy", "pg_cf_recall", "pg_cf_recall_dev",
     "pg_fanin_merge_dev", "pg_recommend_candidates_dnn3_dev",
+    "pg_trim_out_cap", "pg_candidates_trim_dev", "pg_recommend_cascade_dnn3_dev",
 ]
 
 
@@ -102,6 +103,10 @@ class PgCfOpts(C.Structure):
 
 class PgFaninSource(C.Structure):
     _fields_ = [("d_rows", C.c_void_p), ("d_scores", C.c_void_p), ("k", C.c_uint32), ("score_f64", C.c_int)]
+
+
+class PgTrimRule(C.Structure):
+    _fields_ = [("source", C.c_uint8), ("type", C.c_uint8), ("count", C.c_uint32)]
 
 
 class PgIndexRefreshParams(C.Structure):
@@ -226,6 +231,10 @@ def load():
         "pg_cf_recall_dev": [vp, vp, vp, vp, vp, u32, u32, P(PgCfOpts), vp, vp, vp],
         "pg_fanin_merge_dev": [vp, P(PgFaninSource), u32, u32, vp, vp, vp, vp, vp, vp],
         "pg_recommend_candidates_dnn3_dev": [vp, vp, vp, vp, C.c_char_p, vp, u32, u32, vp, vp, vp, vp, vp, vp],
+        "pg_trim_out_cap": [P(PgTrimRule), u32, u32, P(C.c_uint32)],
+        "pg_candidates_trim_dev": [vp, P(PgTrimRule), u32, u32, u32, vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp],
+        "pg_recommend_cascade_dnn3_dev": [vp, vp, vp, vp, C.c_char_p, vp, vp, C.c_char_p, vp, u32, u32, vp, vp, vp, vp, u32,
+                                          vp, vp, vp, vp, vp, vp, vp],
         "pg_index_refresh": [vp, vp, P(PgIndexRefreshParams)],
         "pg_index_refresh_stats": [vp, P(PgIndexRefreshStats)],
         "pg_index_screen_probe": [vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, vp, vp],

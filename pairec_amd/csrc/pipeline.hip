@@ -496,6 +496,83 @@ int pg_recommend_candidates_dnn3_dev(pg_ctx* ctx, const pg_table* t, const pg_mo
     return PG_OK;
 }
 
+int pg_recommend_cascade_dnn3_dev(pg_ctx* ctx, const pg_table* t, const pg_model* m_coarse, const pg_expr* e_coarse,
+                                  const char* coarse_var, const pg_model* m_fine, const pg_expr* e_fine, const char* fine_var,
+                                  const float* d_user_vecs, uint32_t nq, uint32_t cap, const uint64_t* d_rows, const double* d_score,
+                                  const uint8_t* d_source, const uint32_t* d_count, uint32_t n_keep, uint64_t* d_out_rows,
+                                  double* d_out_coarse_fused, uint8_t* d_out_source, float* d_out_model_scores, double* d_out_fused,
+                                  uint32_t* d_out_order, uint32_t* d_out_count) {
+    const char* const who = "pg_recommend_cascade_dnn3_dev";
+    PG_REQUIRE(ctx && t && m_coarse && e_coarse && coarse_var && m_fine && e_fine && fine_var && d_user_vecs && d_rows && d_score &&
+                   d_out_rows && d_out_coarse_fused && d_out_model_scores && d_out_fused && d_out_order && d_out_count,
+               "%s: NULL argument", who);
+    PG_REQUIRE(!d_source == !d_out_source, "%s: d_source and d_out_source come as a pair", who);
+    PG_REQUIRE(nq > 0 && nq <= (uint32_t)pg::kMaxQueries && cap > 0 && cap <= 16384 && n_keep > 0 && n_keep <= cap, "%s: bad nq / cap / n_keep", who);
+    for (const pg_model* m : {m_coarse, m_fine}) {
+        PG_REQUIRE(m->kind == PG_MODEL_DNN3 && t->dim == m->d_item && m->d_user == t->dim,
+                   "%s: both models must be DNN3 with d_user = d_item = the table's dim", who);
+        PG_REQUIRE(m->n_out == 1, "%s: a multi-output model needs its output names (a scene)", who);
+    }
+    PG_REQUIRE(strcmp(fine_var, coarse_var) != 0, "%s: the fine and the coarse model share the name \"%s\"", who, fine_var);
+    if (t->d_row_map) {                  // as recommend_enqueue: both rank stages gather the rows from this table
+        pg::set_error("%s: the table is a filtered view (pg_table_view_create) — views serve the recall calls only", who);
+        return PG_ERR_UNSUPPORTED;
+    }
+    pg::ExprHold hold_c, hold_f;
+    hold_c.take(e_coarse);
+    hold_f.take(e_fine);
+    std::vector<int> src_c, src_f;
+    const char* const fine_names[2] = {fine_var, coarse_var};        // score planes 0 and 1 of the fine stage
+    int rc;
+    if ((rc = pg::recommend_bind_vars(e_coarse, &coarse_var, 1, &src_c, who))) return rc;
+    if ((rc = pg::recommend_bind_vars(e_fine, fine_names, 2, &src_f, who))) return rc;
+    const size_t n = (size_t)nq * cap, nk = (size_t)nq * n_keep;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    PG_HIP(hipSetDevice(ctx->device));
+    pg::TableRead tr(t->rw);             // both rank stages and their padding tests read one version of the table
+    // the coarse stage's own outputs: model scores, fused scores, order — all [nq][cap]
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    void* buf;
+    if ((rc = pg::scratch_reserve(ctx, 22, al(n * 8) + al(n * 4) + n * 4, &buf))) return rc;
+    double* const c_fused = (double*)buf;
+    float* const c_rank = (float*)((char*)buf + al(n * 8));
+    uint32_t* const c_order = (uint32_t*)((char*)buf + al(n * 8) + al(n * 4));
+    pg::RecommendCall cc, cf;
+    cc.t = t; cc.algos[0].m = m_coarse; cc.n_algos = 1; cc.e = e_coarse; cc.var_src = src_c.data(); cc.nv = pg_expr_num_vars(e_coarse);
+    cc.d_queries = d_user_vecs; cc.nq = nq; cc.k = cap;
+    cc.d_rows = const_cast<uint64_t*>(d_rows);       // (the stages behind the recall only read the rows)
+    cc.d_score64 = d_score; cc.d_cand_count = d_count; cc.cand = true;
+    cc.d_rank = c_rank; cc.rank_stride = n; cc.d_fused = c_fused; cc.d_order = c_order;
+    // the fine stage over the survivors: Item.Score is the coarse fused score, the carried coarse model score one more plane
+    cf.t = t; cf.algos[0].m = m_fine; cf.n_algos = 1; cf.n_planes = 2; cf.e = e_fine; cf.var_src = src_f.data(); cf.nv = pg_expr_num_vars(e_fine);
+    cf.d_queries = d_user_vecs; cf.nq = nq; cf.k = n_keep;
+    cf.d_rows = d_out_rows; cf.d_score64 = d_out_coarse_fused; cf.d_cand_count = d_out_count; cf.cand = true;
+    cf.d_rank = d_out_model_scores; cf.rank_stride = nk; cf.d_fused = d_out_fused; cf.d_order = d_out_order;
+    pg::TimersScope quiet(ctx, cc.timers);
+    // (one post-stage scratch serves both stages in turn: sized for the larger before anything is enqueued, so that the second
+    // reservation cannot move it under the first stage's work)
+    pg::PostScratch ps;
+    if ((rc = pg::post_scratch(ctx, cf, nq, &ps)) || (rc = pg::post_scratch(ctx, cc, nq, &ps))) return rc;
+    if ((rc = pg::recommend_post_locked(ctx, cc, 0, nq, ps))) return rc;
+    uint32_t* const h_flags = ctx->h_status + pg::kExprFlagAt;       // [0, 256) the coarse RankScore's flags, [256, 512) the fine one's
+    PG_HIP(hipMemcpyAsync(h_flags, ps.d_err, (size_t)nq * 4, hipMemcpyDeviceToHost, ctx->stream));
+    const pg_trim_rule keep = {PG_TRIM_ANY, PG_TRIM_FIX, n_keep};
+    if ((rc = pg::candidates_trim_locked(ctx, &keep, 1, nq, cap, n_keep, d_rows, c_fused, d_source, d_count, nullptr, 0, nullptr, c_rank, 1,
+                                         c_order, d_out_rows, d_out_coarse_fused, d_out_source, nullptr, nullptr, d_out_model_scores + nk,
+                                         d_out_count)))
+        return rc;
+    if ((rc = pg::post_scratch(ctx, cf, nq, &ps))) return rc;
+    if ((rc = pg::recommend_post_locked(ctx, cf, 0, nq, ps))) return rc;
+    PG_HIP(hipMemcpyAsync(h_flags + pg::kMaxQueries, ps.d_err, (size_t)nq * 4, hipMemcpyDeviceToHost, ctx->stream));
+    PG_HIP(hipStreamSynchronize(ctx->stream));
+    for (uint32_t q = 0; q < nq; ++q)
+        if (h_flags[q] || h_flags[pg::kMaxQueries + q]) {
+            pg::set_expr_arith_error(h_flags[q] ? e_coarse : e_fine);
+            return PG_ERR_ARITH;
+        }
+    return PG_OK;
+}
+
 int pg_recommend_end_timed(pg_ctx* ctx, pg_ticket* tk, uint32_t timeout_us, double* scan_ms) {
     PG_REQUIRE(ctx && tk, "pg_recommend_end_timed: NULL argument");
     if (timeout_us) {

@@ -35,6 +35,24 @@ def _pack_lists(lists, nq: int):
     return ids, off
 
 
+TRIM_FIX, TRIM_ACCUMULATE, TRIM_ANY = 0, 1, 0xFF
+
+
+def _trim_rules(rules):
+    arr = (_lib.PgTrimRule * max(len(rules), 1))()
+    for i, (source, type_, count) in enumerate(rules):
+        arr[i] = _lib.PgTrimRule(int(source), int(type_), int(count))
+    return arr
+
+
+def trim_out_cap(rules, cap: int) -> int:
+    """pg_trim_out_cap: rules = [(source, TRIM_FIX | TRIM_ACCUMULATE, count)] → min(cap, the FIX counts + the largest ACCUMULATE
+    count); raises PgError for a rule set the trim refuses.  A host function: no context, no device."""
+    out = C.c_uint32()
+    _lib.check(_lib.load().pg_trim_out_cap(_trim_rules(rules), len(rules), int(cap), C.byref(out)))
+    return out.value
+
+
 class Context:
     def __init__(self, device: int = 0, stream: Optional[int] = None):
         self.L = _lib.load()
@@ -174,6 +192,75 @@ class Context:
                 d_out.append(self.malloc(max(a.nbytes, 16)) if a is not None else 0)
                 bufs.append(d_out[-1])
             self.fanin_merge_dev(dev, nq, *d_out)
+            self.synchronize()
+            for a, p_ in zip(outs, d_out):
+                if a is not None and a.nbytes:
+                    self.d2h(a, p_)
+        finally:
+            for b in bufs:
+                if b:
+                    self.free(b)
+        return tuple(outs)
+
+    @staticmethod
+    def trim_out_cap(rules, cap: int) -> int:
+        """pg_trim_out_cap: the width of what the rules can keep of `cap` entries (validates them; needs no device)."""
+        return trim_out_cap(rules, cap)
+
+    def candidates_trim_dev(self, rules, nq: int, cap: int, d_rows: int, d_score: int, d_source: int, d_count: int, d_planes_f64: int,
+                            n_f64: int, d_source_mask: int, d_planes_f32: int, n_f32: int, d_out_rows: int, d_out_score: int,
+                            d_out_source: int, d_out_planes_f64: int, d_out_source_mask: int, d_out_planes_f32: int,
+                            d_out_count: int) -> None:
+        """pg_candidates_trim_dev: rules = [(source, type, count)], everything else device addresses (0 = absent; an output is
+        required exactly where its input is given), outputs [nq][trim_out_cap(rules, cap)].  Enqueued on the context's stream:
+        synchronize() before reading."""
+        arr = _trim_rules(rules)
+        v = lambda p: C.c_void_p(p or None)                                          # noqa: E731
+        _lib.check(self.L.pg_candidates_trim_dev(self.h, arr, len(rules), nq, cap, v(d_rows), v(d_score), v(d_source), v(d_count),
+                                                 v(d_planes_f64), n_f64, v(d_source_mask), v(d_planes_f32), n_f32, v(d_out_rows),
+                                                 v(d_out_score), v(d_out_source), v(d_out_planes_f64), v(d_out_source_mask),
+                                                 v(d_out_planes_f32), v(d_out_count)))
+
+    def candidates_trim(self, rules, rows, score, source=None, count=None, planes_f64=None, source_mask=None, planes_f32=None):
+        """Recall quotas / the top-N cut on host arrays (pg_candidates_trim_dev): fanin_merge's rows [nq][cap] u64, score
+        [nq][cap] f64, source [nq][cap] u8, count [nq], recall_scores [n][nq][cap] f64 and source_mask, plus planes_f32
+        [n][nq][cap] →  (rows, score, source, planes_f64, source_mask, planes_f32, count), [nq][out_cap] each, None where the
+        input was None."""
+        r = np.ascontiguousarray(rows, dtype=np.uint64)
+        sc = np.ascontiguousarray(score, dtype=np.float64)
+        if r.ndim != 2 or sc.shape != r.shape:
+            raise ValueError("candidates_trim: rows and score are [nq][cap]")
+        nq, cap = r.shape
+        out_cap = trim_out_cap(rules, cap)
+        opt = [None if source is None else np.ascontiguousarray(source, dtype=np.uint8),
+               None if count is None else np.ascontiguousarray(count, dtype=np.uint32),
+               None if planes_f64 is None else np.ascontiguousarray(planes_f64, dtype=np.float64),
+               None if source_mask is None else np.ascontiguousarray(source_mask, dtype=np.uint32),
+               None if planes_f32 is None else np.ascontiguousarray(planes_f32, dtype=np.float32)]
+        for a, shape in ((opt[0], (nq, cap)), (opt[1], (nq,)), (opt[3], (nq, cap))):
+            if a is not None and a.shape != shape:
+                raise ValueError("candidates_trim: source and source_mask are [nq][cap], count [nq]")
+        for a in (opt[2], opt[4]):
+            if a is not None and (a.ndim != 3 or a.shape[1:] != (nq, cap)):
+                raise ValueError("candidates_trim: planes are [n][nq][cap]")
+        n64 = opt[2].shape[0] if opt[2] is not None else 0
+        n32 = opt[4].shape[0] if opt[4] is not None else 0
+        outs = [np.empty((nq, out_cap), np.uint64), np.empty((nq, out_cap), np.float64),
+                None if opt[0] is None else np.empty((nq, out_cap), np.uint8),
+                None if opt[2] is None else np.empty((n64, nq, out_cap), np.float64),
+                None if opt[3] is None else np.empty((nq, out_cap), np.uint32),
+                None if opt[4] is None else np.empty((n32, nq, out_cap), np.float32), np.empty(nq, np.uint32)]
+        bufs = []
+        try:
+            d_in = []
+            for a in [r, sc] + opt:
+                d_in.append(self.to_device(a) if a is not None and a.nbytes else (self.malloc(16) if a is not None else 0))
+                bufs.append(d_in[-1])
+            d_out = []
+            for a in outs:
+                d_out.append(self.malloc(max(a.nbytes, 16)) if a is not None else 0)
+                bufs.append(d_out[-1])
+            self.candidates_trim_dev(rules, nq, cap, d_in[0], d_in[1], d_in[2], d_in[3], d_in[4], n64, d_in[5], d_in[6], n32, *d_out)
             self.synchronize()
             for a, p_ in zip(outs, d_out):
                 if a is not None and a.nbytes:
@@ -929,6 +1016,44 @@ def recommend_candidates_dnn3(ctx: Context, table: Table, model: "RankModel", ex
             if p_:
                 ctx.free(p_)
     return tuple(outs)
+
+
+def recommend_cascade_dnn3(ctx: Context, table: Table, coarse: "RankModel", e_coarse: "Expr", coarse_var: str, fine: "RankModel",
+                           e_fine: "Expr", fine_var: str, user_vecs: np.ndarray, rows: np.ndarray, score: np.ndarray, n_keep: int,
+                           source=None, count=None):
+    """pg_recommend_cascade_dnn3_dev on host arrays: coarse rank → fusion → sort → keep n_keep → fine rank → fusion → sort over
+    candidate lists the caller made (inputs as recommend_candidates_dnn3, plus source [R][cap] u8 or None) → rows [R][n_keep] u64,
+    coarse fused [R][n_keep] f64, coarse model scores f32, source u8 or None, fine model scores f32, fine fused f64, order u32,
+    count [R] u32."""
+    u = np.ascontiguousarray(user_vecs, dtype=np.float32).reshape(-1, table.dim)
+    r = np.ascontiguousarray(rows, dtype=np.uint64)
+    sc = np.ascontiguousarray(score, dtype=np.float64)
+    R, cap = r.shape
+    if sc.shape != r.shape or u.shape[0] != R:
+        raise ValueError("recommend_cascade_dnn3: rows and score are [R][cap], user_vecs [R][dim]")
+    nk = R * max(int(n_keep), 0)
+    ins = [ctx.to_device(u), ctx.to_device(r), ctx.to_device(sc),
+           ctx.to_device(np.ascontiguousarray(source, dtype=np.uint8)) if source is not None else 0,
+           ctx.to_device(np.ascontiguousarray(count, dtype=np.uint32)) if count is not None else 0]
+    # rows, coarse fused, source, model scores [2], fused, order, count
+    sizes = [nk * 8, nk * 8, nk if source is not None else 0, 2 * nk * 4, nk * 8, nk * 4, R * 4]
+    bufs = [ctx.malloc(max(b, 16)) if b or i != 2 else 0 for i, b in enumerate(sizes)]
+    try:
+        _lib.check(ctx.L.pg_recommend_cascade_dnn3_dev(ctx.h, table.h, coarse.h, e_coarse.h, coarse_var.encode(), fine.h, e_fine.h,
+                                                       fine_var.encode(), ins[0], R, cap, ins[1], ins[2], ins[3] or None, ins[4] or None,
+                                                       int(n_keep), bufs[0], bufs[1], bufs[2] or None, *bufs[3:]))
+        outs = [np.zeros((R, n_keep), np.uint64), np.zeros((R, n_keep), np.float64),
+                np.zeros((R, n_keep), np.uint8) if source is not None else None, np.zeros((2, R, n_keep), np.float32),
+                np.zeros((R, n_keep), np.float64), np.zeros((R, n_keep), np.uint32), np.zeros(R, np.uint32)]
+        for a, p_ in zip(outs, bufs):
+            if a is not None:
+                ctx.d2h(a, p_)
+    finally:
+        for p_ in ins + bufs:
+            if p_:
+                ctx.free(p_)
+    rows_o, c_fused, src_o, ms, fused, order, cnt = outs
+    return rows_o, c_fused, ms[1], src_o, ms[0], fused, order, cnt
 
 class Coalescer:
     """Cross-request batching (pg_coalescer_*): every method serves ONE request and may be called from any number
