@@ -1282,6 +1282,11 @@ typedef struct {
      * window <= 16), the one-workgroup register kernel (those widths, window > 16, n <= 2048), the one-workgroup generic kernel
      * (everything else up to 8192 x 320) */
     uint64_t ssd_grid_calls, ssd_reg_calls, ssd_generic_calls;
+    /* DPP calls by the greedy kernel that served them (csrc/dpp.hip:dpp_run_locked; one count per launch sequence, so a batch of
+     * R requests counts once; pg_dpp_kernel_matrix_dev runs no greedy kernel and counts nothing; window 0 means 10 before the
+     * rule is applied): the one-wave kernel with eight items per lane (n <= 512 and window <= 16), the one-wave kernel with
+     * sixteen (otherwise n <= 1024 and window <= 10), the one-workgroup kernel (everything else up to 8192 candidates) */
+    uint64_t dpp_wave8_calls, dpp_wave16_calls, dpp_block_calls;
 } pg_stats_t;
 int pg_stats(pg_ctx* ctx, pg_stats_t* out);
 /* time (ms) of the dominant kernel of the last pg_recall_* call, measured with HIP events on the

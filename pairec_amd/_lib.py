@@ -61,7 +61,8 @@ class PgStats(C.Structure):
                 ("recall_suspects", C.c_uint64), ("recall_suspect_queries", C.c_uint64), ("recall_i4m_pairs", C.c_uint64),
                 ("recall_screen_overflows", C.c_uint64), ("recall_record_growths", C.c_uint64),
                 ("recall_rescored", C.c_uint64), ("sort_split_calls", C.c_uint64),
-                ("ssd_grid_calls", C.c_uint64), ("ssd_reg_calls", C.c_uint64), ("ssd_generic_calls", C.c_uint64)]
+                ("ssd_grid_calls", C.c_uint64), ("ssd_reg_calls", C.c_uint64), ("ssd_generic_calls", C.c_uint64),
+                ("dpp_wave8_calls", C.c_uint64), ("dpp_wave16_calls", C.c_uint64), ("dpp_block_calls", C.c_uint64)]
 
 
 class PgWhereStats(C.Structure):

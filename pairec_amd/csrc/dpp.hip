@@ -671,12 +671,15 @@ int dpp_run_locked(pg_ctx* ctx, const float* d_emb32, const double* d_hook, cons
         const size_t lds = (size_t)wrows * 512 * 8;
         if ((rc = ensure_dyn_lds(ctx, (const void*)dpp_greedy_wave_kernel<8, 16>, lds))) return rc;
         dpp_greedy_wave_kernel<8, 16><<<R, 64, lds, ctx->stream>>>(L, Rr, n, ld, topn, window, d_out, d_out_count);
+        ctx->stats.dpp_wave8_calls++;
     } else if (n <= 1024 && window <= 10) {
         const size_t lds = (size_t)wrows * 1024 * 8;
         if ((rc = ensure_dyn_lds(ctx, (const void*)dpp_greedy_wave_kernel<16, 10>, lds))) return rc;
         dpp_greedy_wave_kernel<16, 10><<<R, 64, lds, ctx->stream>>>(L, Rr, n, ld, topn, window, d_out, d_out_count);
+        ctx->stats.dpp_wave16_calls++;
     } else {
         dpp_greedy_kernel<<<R, 1024, 0, ctx->stream>>>(L, Rr, n, ld, topn, window, D2, Cm, d_out, d_out_count);
+        ctx->stats.dpp_block_calls++;
     }
     PG_HIP(hipGetLastError());
     return PG_OK;
