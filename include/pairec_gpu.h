@@ -1287,6 +1287,13 @@ typedef struct {
      * rule is applied): the one-wave kernel with eight items per lane (n <= 512 and window <= 16), the one-wave kernel with
      * sixteen (otherwise n <= 1024 and window <= 10), the one-workgroup kernel (everything else up to 8192 candidates) */
     uint64_t dpp_wave8_calls, dpp_wave16_calls, dpp_block_calls;
+    /* rank calls by the kernel that served them (csrc/rank_mlp.hip: rank_dnn3_dev_locked, rank_fm2t_dev_locked; one count per
+     * launch sequence; the seven sum to rank_calls): the weights-stationary DNN3 kernel (512-256, bf16), the register-stationary
+     * ones (128-128, 256-128, 256-256, bf16), the LDS-stationary one (1024-512, bf16), the two-role kernel in split bf16, the
+     * two-role kernel in an fp16 mode (its split-bf16 pass over the marked tiles belongs to the same sequence and is not counted
+     * as x3), the per-wave two-tower kernel over item records, and the general mlp_kernel (every other DNN3 or two-tower call:
+     * fp32, 64-wide tables, rank_no_ws, shapes without a kernel of their own) */
+    uint64_t rank_ws_calls, rank_rs_calls, rank_ls_calls, rank_x3_calls, rank_h2_calls, rank_isw_calls, rank_mlp_calls;
 } pg_stats_t;
 int pg_stats(pg_ctx* ctx, pg_stats_t* out);
 /* time (ms) of the dominant kernel of the last pg_recall_* call, measured with HIP events on the

@@ -62,7 +62,10 @@ class PgStats(C.Structure):
                 ("recall_screen_overflows", C.c_uint64), ("recall_record_growths", C.c_uint64),
                 ("recall_rescored", C.c_uint64), ("sort_split_calls", C.c_uint64),
                 ("ssd_grid_calls", C.c_uint64), ("ssd_reg_calls", C.c_uint64), ("ssd_generic_calls", C.c_uint64),
-                ("dpp_wave8_calls", C.c_uint64), ("dpp_wave16_calls", C.c_uint64), ("dpp_block_calls", C.c_uint64)]
+                ("dpp_wave8_calls", C.c_uint64), ("dpp_wave16_calls", C.c_uint64), ("dpp_block_calls", C.c_uint64),
+                ("rank_ws_calls", C.c_uint64), ("rank_rs_calls", C.c_uint64), ("rank_ls_calls", C.c_uint64),
+                ("rank_x3_calls", C.c_uint64), ("rank_h2_calls", C.c_uint64), ("rank_isw_calls", C.c_uint64),
+                ("rank_mlp_calls", C.c_uint64)]
 
 
 class PgWhereStats(C.Structure):

@@ -1231,10 +1231,13 @@ int rank_dnn3_dev_locked(pg_ctx* ctx, const pg_model* m, const pg_table* t,
     if (ws) {
         // bf16: weights-stationary persistent kernel over 64-item tiles
         if ((rc = launch_dnn3_ws(ctx, a))) return rc;
+        ctx->stats.rank_ws_calls++;
     } else if (rs_k) {
         if ((rc = launch_dnn3_rs(ctx, m->h1, m->h2, a))) return rc;
+        ctx->stats.rank_rs_calls++;
     } else if (ls_k) {
         if ((rc = launch_dnn3_ls(ctx, m->h1, m->h2, a))) return rc;
+        ctx->stats.rank_ls_calls++;
     } else if (h2_k) {
         void* fbp;
         if ((rc = scratch_reserve(ctx, 17, ((size_t)3 * max_tiles + 64) * 4, &fbp))) return rc;
@@ -1260,10 +1263,13 @@ int rank_dnn3_dev_locked(pg_ctx* ctx, const pg_model* m, const pg_table* t,
         a.tile_cnt = h.fb_tile_cnt;
         a.n_tiles = h.fb_n_tiles;
         if ((rc = launch_dnn3_x3(ctx, m->h1, m->h2, a))) return rc;
+        ctx->stats.rank_h2_calls++;                     // (not also an x3 call: that pass is part of this sequence)
     } else if (x3_k) {
         if ((rc = launch_dnn3_x3(ctx, m->h1, m->h2, a))) return rc;
-    } else if ((rc = dispatch_dnn3_mlp(ctx, m, a, grid128))) {
-        return rc;
+        ctx->stats.rank_x3_calls++;
+    } else {
+        if ((rc = dispatch_dnn3_mlp(ctx, m, a, grid128))) return rc;
+        ctx->stats.rank_mlp_calls++;
     }
     PG_HIP(hipGetLastError());
     if (!ctx->timers_off) {
@@ -1323,8 +1329,10 @@ static int rank_fm2t_dev_locked(pg_ctx* ctx, const pg_model* m, const float* d_u
     a.out = d_out;
     if (isw) {
         if ((rc = launch_fm2t_isw(ctx, a))) return rc;
-    } else if ((rc = dispatch_fm2t_mlp(ctx, m, a, max_tiles))) {
-        return rc;
+        ctx->stats.rank_isw_calls++;
+    } else {
+        if ((rc = dispatch_fm2t_mlp(ctx, m, a, max_tiles))) return rc;
+        ctx->stats.rank_mlp_calls++;
     }
     PG_HIP(hipGetLastError());
     if (!ctx->timers_off) {

@@ -94,7 +94,7 @@ def test_cfg4_fm_twotower_with_million_row_field_tables(ctx):
         m.destroy()
 
 
-@pytest.mark.parametrize("d_user,d_item,h1,h2", [(128, 128, 128, 128), (64, 64, 256, 128), (128, 128, 256, 256),
+@pytest.mark.parametrize("d_user,d_item,h1,h2", [(128, 128, 128, 128), (64, 64, 256, 128), (128, 128, 256, 128), (128, 128, 256, 256),
                                                  (200, 128, 1024, 512), (128, 64, 512, 256)])
 def test_dnn3_shapes_match_oracle(ctx, d_user, d_item, h1, h2):
     """EAS-shaped DNN predict beyond the benchmark's 256-512-256-1 (algorithm/eas/model.go:197-222 serves whatever
