@@ -1007,6 +1007,110 @@ int pg_recommend_cascade_dnn3_dev(pg_ctx* ctx, const pg_table* t, const pg_model
                                   double* d_out_coarse_fused, uint8_t* d_out_source, float* d_out_model_scores, double* d_out_fused,
                                   uint32_t* d_out_order, uint32_t* d_out_count);
 
+/* DiversityRuleSort on the device (csrc/diversity.hip): the windowed scatter rules that follow ItemRankScore
+ * in most scenes (sort/diversity_rule_sort.go:116-283, sort/diversity_rule.go:50-92, sort/diversity_exclusion_rule.go:37-56),
+ * for nq <= 256 requests of cap <= PG_DIV_MAX_N candidates each, without leaving device memory.
+ *   In        a request's candidates in the order the previous sort left them; position 0 .. n - 1 is an entry's identity.
+ *             (The reference's alreadyMatchItems, :156, is keyed by item id; after UniqueFilter ids are unique, so a "taken"
+ *             flag per position is the same thing.)  dims [n_cols][nq][cap] int64: column c of the entry at position i of
+ *             request q is dims[(c * nq + q) * cap + i] — dictionary codes or integer features; source [nq][cap] uint8
+ *             (Item.RetrieveId as fan-in numbers it; optional), count [nq] (optional: cap), enable [nq] bytes (optional: the
+ *             sort's Conditions gate, :74-85, evaluated by the caller; 0 = the request's order is the identity).
+ *   Config    host values: size = ctx.Size, diversity_size / explore_item_size (<= 0: off, :46-48) / exclude_source_mask (bit s:
+ *             source s is among ExcludeRecalls; sources >= 32 are never excluded), 0 .. PG_DIV_MAX_RULES rules {1 ..
+ *             PG_DIV_MAX_DIMS column indices, interval, window, frequency, weight} and 0 .. PG_DIV_MAX_EXCL exclusion rules
+ *             {1-based positions, 1 .. PG_DIV_MAX_TERMS terms `column OP value` (pg_where_op), all ANDed}.
+ *   Values    a rule's value for an entry is the TUPLE of its dimension columns; two values are equal iff every column is.
+ *             The reference joins the columns' strings with "_" (diversity_rule.go:45), so ("a_b", "c") equals ("a", "b_c")
+ *             there and not here; a caller who wants that encodes the joined string as one column.
+ *   Match     (diversity_rule.go:50-92) with s results so far, an entry FAILS rule r when interval > 0, s >= interval and the
+ *             last `interval` results all carry its value (:54-69), or when window > 0, frequency > 0, window > frequency and
+ *             1 + the results in [max(0, s - window + 1), s) that carry its value > frequency (:71-90).
+ *             An exclusion rule matches (position, entry) iff the position is among its positions and every term holds.
+ *   Answer    DEFINED bit for bit (doSort, :116-283): no rules, enable == 0 or nothing left after the set-aside → identity.
+ *             Else the entries whose source is in exclude_source_mask are set aside in order (:127-138; the m others are
+ *             renumbered 0 .. m - 1 in order, and distances below are in that numbering); D = size, or min(diversity_size, m)
+ *             when diversity_size > 0 (:146-153).  First pick: the first entry no exclusion rule matches at position 1, entry
+ *             0 if all match or there are no exclusion rules (:158-184).  Then while len(result) <= D — note <=: up to D + 1
+ *             greedy picks, :197 — and picks != m (:198): walk the untaken entries in order, skipping those an exclusion rule
+ *             matches at position len(result) + 1 (:210-221); f = the first entry not skipped; the walk stops at an entry i
+ *             with explore_item_size > 0 and i - f >= explore_item_size (:226, taken entries count); if any rule has weight >
+ *             0 every rule is evaluated and w = the sum of the weights of the rules that do not fail (:231-238), else the
+ *             entry passes iff no rule fails; the first entry that passes every rule is taken (:246-250); if none does, the
+ *             evaluated entry with the largest w, the first one on ties (:256-265, :302-310; without weights: the first
+ *             evaluated entry); if every untaken entry was skipped the loop ends (:266).  Output: the result, the untaken
+ *             entries in order (:271-276), the set-aside entries in order (:278) — a permutation of 0 .. n - 1 as uint32
+ *             positions; slots at positions >= count receive UINT32_MAX.
+ *   Refused   on the host, the context left usable.  PG_ERR_INVALID: a rule's n_dims 0 or > PG_DIV_MAX_DIMS, a column index >=
+ *             n_cols, a negative interval / window / frequency, an unknown operator, a position of 0, an exclusion rule with
+ *             no term or no position, exclude_source_mask without source.  No rules is NOT an error (identity, :121-123).
+ *             PG_ERR_UNSUPPORTED: more rules / exclusion rules / terms / columns than the limits, cap > PG_DIV_MAX_N, nq >
+ *             256, more than PG_DIV_MAX_POSITIONS reachable positions (<= PG_DIV_MAX_N + 1) in one exclusion rule, and
+ *             n_multi_value > 0: MultiValueDimensionConf (list-valued dimensions, diversity_rule.go:101-210) is not served.
+ *             Exclusion terms that are not integer comparisons cannot be expressed here; the host mirror refuses them by name.
+ *   host      pg_diversity_rules_host: a pure host function (no context, no device) that validates the config and states
+ *             what the kernel reproduces; tests compare the kernel with it.  The library falls back to it for nothing.
+ *   dev       pg_diversity_rules_dev: the same over device arrays, one launch on the context's stream, no synchronisation.
+ *   features  pg_diversity_rules_features_dev: column c is the int32 / int64 column col_names[c] of fs at the candidates'
+ *             rows d_rows [nq][cap] uint64 (a row outside the store reads the column default), gathered into planes in context
+ *             scratch; then the same kernel.  A float column, a column without values or an unknown name is PG_ERR_INVALID.
+ *   one       pg_diversity_rules: host arrays of one request, dims [n_cols][n] (upload, run, download, synchronise).
+ *   Kernel    one workgroup of PG_DIV_CHUNK lanes per request.  Prepare: the set-aside compaction; per rule an exact key per
+ *             entry = the first entry with an equal tuple, through an open-addressed table in which tuples themselves are
+ *             compared (no hash ever stands for a tuple); one bit per (exclusion rule, entry).  Greedy: the taken bitmap, the
+ *             result, the run of equal values at its tail and the count of every value inside the window per rule; a step
+ *             scans PG_DIV_CHUNK entries at a time, one lane per entry against all rules, wave ballots and a scan of the
+ *             waves' masks give the first passing entry, (largest w, first position) is carried across chunks, the explore
+ *             bound ends the scan.  Every output element is written exactly once. */
+#define PG_DIV_MAX_N 8192
+#define PG_DIV_MAX_RULES 8
+#define PG_DIV_MAX_DIMS 4
+#define PG_DIV_MAX_COLS 16
+#define PG_DIV_MAX_EXCL 8
+#define PG_DIV_MAX_TERMS 4
+#define PG_DIV_MAX_POSITIONS 64
+#define PG_DIV_CHUNK 1024
+typedef struct {
+    uint32_t n_dims;                    /* 1 .. PG_DIV_MAX_DIMS (DiversityRuleConfig.Dimensions) */
+    uint32_t dims[PG_DIV_MAX_DIMS];     /* column indices < n_cols */
+    int32_t  interval;                  /* IntervalSize */
+    int32_t  window;                    /* WindowSize */
+    int32_t  frequency;                 /* FrequencySize */
+    int32_t  weight;                    /* Weight */
+} pg_div_rule;
+typedef struct {
+    uint32_t  column;                   /* < n_cols */
+    int32_t   op;                       /* pg_where_op */
+    long long value;
+} pg_div_term;
+typedef struct {
+    const uint32_t* positions;          /* ExclusionRuleConfig.Positions, 1-based */
+    uint32_t        n_positions;
+    uint32_t        n_terms;            /* 1 .. PG_DIV_MAX_TERMS (Conditions), all ANDed */
+    pg_div_term     terms[PG_DIV_MAX_TERMS];
+} pg_div_exclusion;
+typedef struct {
+    int32_t          size;              /* ctx.Size */
+    int32_t          diversity_size;    /* DiversitySize; <= 0: off */
+    int32_t          explore_item_size; /* ExploreItemSize; <= 0: off */
+    uint32_t         exclude_source_mask;
+    uint32_t         n_cols;            /* planes in dims, <= PG_DIV_MAX_COLS */
+    uint32_t         n_rules;
+    uint32_t         n_excl;
+    uint32_t         n_multi_value;     /* MultiValueDimensionConf entries: anything but 0 is refused */
+    pg_div_rule      rules[PG_DIV_MAX_RULES];
+    pg_div_exclusion excl[PG_DIV_MAX_EXCL];
+} pg_div_config;
+int pg_diversity_rules_host(const pg_div_config* cfg, uint32_t nq, uint32_t cap, const uint32_t* count, const int64_t* dims,
+                            const uint8_t* source, const uint8_t* enable, uint32_t* order);
+int pg_diversity_rules_dev(pg_ctx* ctx, const pg_div_config* cfg, uint32_t nq, uint32_t cap, const uint32_t* d_count,
+                           const int64_t* d_dims, const uint8_t* d_source, const uint8_t* d_enable, uint32_t* d_order);
+int pg_diversity_rules_features_dev(pg_ctx* ctx, const pg_div_config* cfg, const pg_features* fs, const char* const* col_names,
+                                    uint32_t nq, uint32_t cap, const uint64_t* d_rows, const uint32_t* d_count,
+                                    const uint8_t* d_source, const uint8_t* d_enable, uint32_t* d_order);
+int pg_diversity_rules(pg_ctx* ctx, const pg_div_config* cfg, uint32_t n, const int64_t* dims, const uint8_t* source,
+                       uint32_t* order);
+
 /* ---- shard group: one process, several GPUs --------------------------------------------------------
  * BASELINE.json configs[4] / SURVEY.md 8e behind the C ABI (a cgo host cannot join a torch.distributed job): the item
  * table in contiguous row ranges [g*N/G, (g+1)*N/G), one context per shard, model weights replicated.  devices[] may

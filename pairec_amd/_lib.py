@@ -49,6 +49,7 @@ EXPORTS = [
     "pg_simtable_create", "pg_simtable_upload", "pg_simtable_info", "pg_simtable_destroy", "pg_cf_recall", "pg_cf_recall_dev",
     "pg_fanin_merge_dev", "pg_recommend_candidates_dnn3_dev",
     "pg_trim_out_cap", "pg_candidates_trim_dev", "pg_recommend_cascade_dnn3_dev",
+    "pg_diversity_rules_host", "pg_diversity_rules_dev", "pg_diversity_rules_features_dev", "pg_diversity_rules",
 ]
 
 
@@ -111,6 +112,26 @@ class PgFaninSource(C.Structure):
 
 class PgTrimRule(C.Structure):
     _fields_ = [("source", C.c_uint8), ("type", C.c_uint8), ("count", C.c_uint32)]
+
+
+class PgDivRule(C.Structure):
+    _fields_ = [("n_dims", C.c_uint32), ("dims", C.c_uint32 * 4), ("interval", C.c_int32), ("window", C.c_int32),
+                ("frequency", C.c_int32), ("weight", C.c_int32)]
+
+
+class PgDivTerm(C.Structure):
+    _fields_ = [("column", C.c_uint32), ("op", C.c_int32), ("value", C.c_longlong)]
+
+
+class PgDivExclusion(C.Structure):
+    _fields_ = [("positions", C.POINTER(C.c_uint32)), ("n_positions", C.c_uint32), ("n_terms", C.c_uint32),
+                ("terms", PgDivTerm * 4)]
+
+
+class PgDivConfig(C.Structure):
+    _fields_ = [("size", C.c_int32), ("diversity_size", C.c_int32), ("explore_item_size", C.c_int32),
+                ("exclude_source_mask", C.c_uint32), ("n_cols", C.c_uint32), ("n_rules", C.c_uint32), ("n_excl", C.c_uint32),
+                ("n_multi_value", C.c_uint32), ("rules", PgDivRule * 8), ("excl", PgDivExclusion * 8)]
 
 
 class PgIndexRefreshParams(C.Structure):
@@ -239,6 +260,10 @@ def load():
         "pg_candidates_trim_dev": [vp, P(PgTrimRule), u32, u32, u32, vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp],
         "pg_recommend_cascade_dnn3_dev": [vp, vp, vp, vp, C.c_char_p, vp, vp, C.c_char_p, vp, u32, u32, vp, vp, vp, vp, u32,
                                           vp, vp, vp, vp, vp, vp, vp],
+        "pg_diversity_rules_host": [P(PgDivConfig), u32, u32, vp, vp, vp, vp, vp],
+        "pg_diversity_rules_dev": [vp, P(PgDivConfig), u32, u32, vp, vp, vp, vp, vp],
+        "pg_diversity_rules_features_dev": [vp, P(PgDivConfig), vp, P(C.c_char_p), u32, u32, vp, vp, vp, vp, vp],
+        "pg_diversity_rules": [vp, P(PgDivConfig), u32, vp, vp, vp],
         "pg_index_refresh": [vp, vp, P(PgIndexRefreshParams)],
         "pg_index_refresh_stats": [vp, P(PgIndexRefreshStats)],
         "pg_index_screen_probe": [vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, vp, vp],

@@ -265,7 +265,8 @@ struct pg_ctx {
     //   16 pg_features_eval_dev: the bound variables   17 index.hip: bounds, probe thresholds and list counts of an index recall
     //   18 recall.hip: the over-fetched answer, lists and counts of a recall with exclusion lists
     //   19 cf.hip: status and counts, staged offsets and lists, the global tier's tables, the items to order, the over-fetched answer
-    pg::Scratch scratch[23];
+    //   23 diversity.hip: keys, window counts and tuple tables   24 diversity.hip: the dimension planes gathered from a feature store
+    pg::Scratch scratch[25];
     std::mutex pool_mu;          // guards pipe_free
     std::vector<pg::PipeRun*> pipe_free;     // per-batch status blocks / events of the device-resident pipelines
     std::map<const void*, size_t> dyn_lds;   // kernels whose dynamic-LDS limit was raised on this device

@@ -53,6 +53,65 @@ def trim_out_cap(rules, cap: int) -> int:
     return out.value
 
 
+DIV_MAX_N, DIV_MAX_RULES, DIV_MAX_DIMS, DIV_MAX_COLS, DIV_MAX_EXCL, DIV_MAX_TERMS, DIV_MAX_POSITIONS, DIV_CHUNK = 8192, 8, 4, 16, 8, 4, 64, 1024
+WHERE_GT, WHERE_GE, WHERE_LT, WHERE_LE, WHERE_EQ, WHERE_NE = range(6)
+
+
+def _div_config(cfg, n_cols: int):
+    """a DiversityRuleSort config → (pg_div_config, the arrays it points to).  cfg: {"size", "diversity_size", "explore_item_size",
+    "exclude_source_mask", "rules": [{"dims": [column indices], "interval", "window", "frequency", "weight"}], "exclusions":
+    [{"positions": [1-based], "terms": [(column, WHERE_*, value)]}], "multi_value": MultiValueDimensionConf entries}; absent keys
+    are 0 / empty.  More entries than the C arrays hold are cut here and still counted, so the C side refuses them."""
+    c = _lib.PgDivConfig()
+    c.size, c.diversity_size = int(cfg.get("size", 0)), int(cfg.get("diversity_size", 0))
+    c.explore_item_size, c.exclude_source_mask = int(cfg.get("explore_item_size", 0)), int(cfg.get("exclude_source_mask", 0))
+    c.n_cols, c.n_multi_value = int(cfg.get("n_cols", n_cols)), int(cfg.get("multi_value", 0))
+    rules, excl, keep = list(cfg.get("rules", ())), list(cfg.get("exclusions", ())), []
+    c.n_rules, c.n_excl = len(rules), len(excl)
+    for i, r in enumerate(rules[:DIV_MAX_RULES]):
+        dims = list(r.get("dims", ()))
+        c.rules[i].n_dims = len(dims)
+        for k, d in enumerate(dims[:DIV_MAX_DIMS]):
+            c.rules[i].dims[k] = int(d)
+        c.rules[i].interval, c.rules[i].window = int(r.get("interval", 0)), int(r.get("window", 0))
+        c.rules[i].frequency, c.rules[i].weight = int(r.get("frequency", 0)), int(r.get("weight", 0))
+    for i, e in enumerate(excl[:DIV_MAX_EXCL]):
+        pos = np.ascontiguousarray(list(e.get("positions", ())), dtype=np.uint32)
+        keep.append(pos)
+        c.excl[i].positions = pos.ctypes.data_as(C.POINTER(C.c_uint32)) if pos.size else None
+        c.excl[i].n_positions = pos.size
+        terms = list(e.get("terms", ()))
+        c.excl[i].n_terms = len(terms)
+        for k, (col, op, value) in enumerate(terms[:DIV_MAX_TERMS]):
+            c.excl[i].terms[k] = _lib.PgDivTerm(int(col), int(op), int(value))
+    return c, keep
+
+
+def _div_planes(dims, count, source, enable):
+    d = np.ascontiguousarray(dims, dtype=np.int64)
+    if d.ndim != 3:
+        raise ValueError("diversity_rules: dims is [n_cols][nq][cap]")
+    n_cols, nq, cap = d.shape
+    cnt = None if count is None else np.ascontiguousarray(count, dtype=np.uint32)
+    src = None if source is None else np.ascontiguousarray(source, dtype=np.uint8)
+    en = None if enable is None else np.ascontiguousarray(enable, dtype=np.uint8)
+    if (cnt is not None and cnt.shape != (nq,)) or (en is not None and en.shape != (nq,)) or (src is not None and src.shape != (nq, cap)):
+        raise ValueError("diversity_rules: count and enable are [nq], source [nq][cap]")
+    return d, n_cols, nq, cap, cnt, src, en
+
+
+def diversity_rules_host(cfg, dims, count=None, source=None, enable=None) -> np.ndarray:
+    """pg_diversity_rules_host: DiversityRuleSort of nq requests on the host — the statement the kernel reproduces (no context, no
+    device).  dims [n_cols][nq][cap] int64 → order [nq][cap] uint32 (UINT32_MAX behind count)."""
+    d, n_cols, nq, cap, cnt, src, en = _div_planes(dims, count, source, enable)
+    c, keep = _div_config(cfg, n_cols)
+    out = np.empty((nq, cap), dtype=np.uint32)
+    o = lambda a: None if a is None else _ptr(a)                                     # noqa: E731
+    _lib.check(_lib.load().pg_diversity_rules_host(C.byref(c), nq, cap, o(cnt), _ptr(d), o(src), o(en), _ptr(out)))
+    del keep
+    return out
+
+
 class Context:
     def __init__(self, device: int = 0, stream: Optional[int] = None):
         self.L = _lib.load()
@@ -270,6 +329,76 @@ class Context:
                 if b:
                     self.free(b)
         return tuple(outs)
+
+    def diversity_rules_dev(self, cfg, n_cols: int, nq: int, cap: int, d_count: int, d_dims: int, d_source: int, d_enable: int,
+                            d_order: int) -> None:
+        """pg_diversity_rules_dev: device addresses (0 = absent), d_dims [n_cols][nq][cap] int64, d_order [nq][cap] uint32.
+        Enqueued on the context's stream: synchronize() before reading."""
+        c, keep = _div_config(cfg, n_cols)
+        v = lambda p: C.c_void_p(p or None)                                          # noqa: E731
+        _lib.check(self.L.pg_diversity_rules_dev(self.h, C.byref(c), nq, cap, v(d_count), v(d_dims), v(d_source), v(d_enable), v(d_order)))
+        del keep
+
+    def diversity_rules_features_dev(self, cfg, fs, col_names, nq: int, cap: int, d_rows: int, d_count: int, d_source: int,
+                                     d_enable: int, d_order: int) -> None:
+        """pg_diversity_rules_features_dev: column c of the config is fs's integer column col_names[c] at d_rows [nq][cap] uint64."""
+        c, keep = _div_config(cfg, len(col_names))
+        names = (C.c_char_p * max(len(col_names), 1))(*[n.encode() for n in col_names])
+        v = lambda p: C.c_void_p(p or None)                                          # noqa: E731
+        _lib.check(self.L.pg_diversity_rules_features_dev(self.h, C.byref(c), getattr(fs, "h", fs), names, nq, cap, v(d_rows), v(d_count),
+                                                          v(d_source), v(d_enable), v(d_order)))
+        del keep
+
+    def _diversity_run(self, nq, cap, arrays, launch):
+        out = np.empty((nq, cap), dtype=np.uint32)
+        bufs = []
+        try:
+            dev = []
+            for a in arrays:
+                dev.append(self.to_device(a) if a is not None else 0)
+                bufs.append(dev[-1])
+            d_out = self.malloc(max(out.nbytes, 16))
+            bufs.append(d_out)
+            launch(dev, d_out)
+            self.synchronize()
+            if out.nbytes:
+                self.d2h(out, d_out)
+        finally:
+            for b in bufs:
+                if b:
+                    self.free(b)
+        return out
+
+    def diversity_rules(self, cfg, dims, count=None, source=None, enable=None) -> np.ndarray:
+        """DiversityRuleSort of nq requests on host arrays (pg_diversity_rules_dev): dims [n_cols][nq][cap] int64, count [nq],
+        source [nq][cap] uint8, enable [nq] bytes → order [nq][cap] uint32 (UINT32_MAX behind count)."""
+        d, n_cols, nq, cap, cnt, src, en = _div_planes(dims, count, source, enable)
+        return self._diversity_run(nq, cap, [cnt, d, src, en], lambda dev, d_out: self.diversity_rules_dev(
+            cfg, n_cols, nq, cap, dev[0], dev[1], dev[2], dev[3], d_out))
+
+    def diversity_rules_features(self, cfg, fs, col_names, rows, count=None, source=None, enable=None) -> np.ndarray:
+        """The same with the dimension columns read from a feature store (pg_diversity_rules_features_dev): rows [nq][cap] uint64."""
+        r = np.ascontiguousarray(rows, dtype=np.uint64)
+        if r.ndim != 2:
+            raise ValueError("diversity_rules_features: rows is [nq][cap]")
+        nq, cap = r.shape
+        cnt = None if count is None else np.ascontiguousarray(count, dtype=np.uint32)
+        src = None if source is None else np.ascontiguousarray(source, dtype=np.uint8)
+        en = None if enable is None else np.ascontiguousarray(enable, dtype=np.uint8)
+        return self._diversity_run(nq, cap, [r, cnt, src, en], lambda dev, d_out: self.diversity_rules_features_dev(
+            cfg, fs, list(col_names), nq, cap, dev[0], dev[1], dev[2], dev[3], d_out))
+
+    def diversity_rules_one(self, cfg, dims, source=None) -> np.ndarray:
+        """pg_diversity_rules: one request on host arrays, dims [n_cols][n] int64 → order [n] uint32 (what the host mirror calls)."""
+        d = np.ascontiguousarray(dims, dtype=np.int64)
+        if d.ndim != 2:
+            raise ValueError("diversity_rules_one: dims is [n_cols][n]")
+        src = None if source is None else np.ascontiguousarray(source, dtype=np.uint8)
+        c, keep = _div_config(cfg, d.shape[0])
+        out = np.empty(d.shape[1], dtype=np.uint32)
+        _lib.check(self.L.pg_diversity_rules(self.h, C.byref(c), d.shape[1], _ptr(d), None if src is None else _ptr(src), _ptr(out)))
+        del keep
+        return out
 
     # ---- sort / expr (context-level ops) ----------------------------------------------------
     def sort_scores(self, scores: np.ndarray, seg_offsets: Optional[Sequence[int]] = None,

@@ -266,7 +266,68 @@ bool RecommendConfig::Parse(const std::string& text, RecommendConfig* out, std::
         }
         out->GpuRecalls.push_back(c);
     }
-    for (const auto& sc : out->UserDefineConfs.at("pairec_gpu").at("Sorts").arr) out->GpuSorts.push_back(parse_sort(sc));
+    // DiversityRuleSort on the device (sort/diversity_rule_sort.go:25-67): what pg_diversity_rules cannot serve is refused here, by name
+    auto parse_diversity = [&](const json::Value& sc, SortConfig* c) {
+        auto refuse = [&](const std::string& what) {
+            if (err) *err = "pairec_gpu.Sorts: " + c->Name + ": DiversityRuleSort: " + what;
+            return false;
+        };
+        DiversityRuleSortConfig& dc = c->DiversityConf;
+        dc.DiversitySize = (int)sc.n("DiversitySize");
+        dc.ExploreItemSize = (int)sc.n("ExploreItemSize");
+        dc.ExcludeRecalls = str_list(sc.at("ExcludeRecalls"));
+        if (!sc.at("MultiValueDimensionConf").arr.empty()) return refuse("MultiValueDimensionConf (list-valued dimensions) is not supported");
+        if (!sc.at("Conditions").arr.empty()) return refuse("Conditions (the sort's user-level gate) is not supported");
+        if (sc.at("DiversityRules").arr.size() > PG_DIV_MAX_RULES) return refuse("more than " + std::to_string(PG_DIV_MAX_RULES) + " DiversityRules");
+        if (sc.at("ExclusionRules").arr.size() > PG_DIV_MAX_EXCL) return refuse("more than " + std::to_string(PG_DIV_MAX_EXCL) + " ExclusionRules");
+        for (const auto& r : sc.at("DiversityRules").arr) {
+            DiversityRuleConfig rc;
+            rc.Dimensions = str_list(r.at("Dimensions"));
+            if (rc.Dimensions.empty() || rc.Dimensions.size() > PG_DIV_MAX_DIMS)
+                return refuse("a rule needs 1.." + std::to_string(PG_DIV_MAX_DIMS) + " Dimensions");
+            rc.WindowSize = (int)r.n("WindowSize"); rc.FrequencySize = (int)r.n("FrequencySize");
+            rc.IntervalSize = (int)r.n("IntervalSize"); rc.Weight = (int)r.n("Weight");
+            if (rc.WindowSize < 0 || rc.FrequencySize < 0 || rc.IntervalSize < 0) return refuse("a negative WindowSize, FrequencySize or IntervalSize");
+            dc.DiversityRules.push_back(rc);
+        }
+        for (const auto& x : sc.at("ExclusionRules").arr) {
+            ExclusionRuleConfig xc;
+            for (const auto& p : x.at("Positions").arr) {
+                if (p.type != json::Value::Number || p.num < 1 || p.num != std::floor(p.num)) return refuse("a position that is not a 1-based integer");
+                xc.Positions.push_back((long long)p.num);
+            }
+            if (xc.Positions.empty() || x.at("Conditions").arr.empty()) continue;          // (never matches: diversity_exclusion_rule.go:38-43)
+            if (x.at("Conditions").arr.size() > PG_DIV_MAX_TERMS) return refuse("more than " + std::to_string(PG_DIV_MAX_TERMS) + " Conditions in an exclusion rule");
+            for (const auto& f : x.at("Conditions").arr) {
+                ExclusionCondition ec;
+                ec.Name = f.s("Name");
+                const std::string op = f.s("Operator"), type = f.s("Type"), domain = f.s("Domain");
+                const json::Value& v = f.at("Value");
+                static const std::map<std::string, int> ops = {{"greater", PG_WHERE_GT}, {"greaterThan", PG_WHERE_GE}, {"less", PG_WHERE_LT},
+                                                               {"lessThan", PG_WHERE_LE}, {"equal", PG_WHERE_EQ}, {"not_equal", PG_WHERE_NE}};
+                const auto o = ops.find(op);
+                ec.IsString = type == "string" && v.type == json::Value::String;
+                const bool is_int = (type == "int" || type == "int64") && v.type == json::Value::Number && v.num == std::floor(v.num) && std::fabs(v.num) < 9e15;
+                const bool served = o != ops.end() && !ec.Name.empty() && (domain.empty() || domain == "item") &&
+                                    (is_int || (ec.IsString && (o->second == PG_WHERE_EQ || o->second == PG_WHERE_NE)));
+                if (!served)
+                    return refuse("exclusion condition on \"" + ec.Name + "\" (Operator \"" + op + "\", Type \"" + type +
+                                  "\") is not an integer comparison: the device serves item properties under equal / not_equal / greater / "
+                                  "greaterThan / less / lessThan against an integer literal, and strings under equal / not_equal");
+                ec.Op = o->second;
+                ec.Int = is_int ? (long long)v.num : 0;
+                ec.Str = v.str;
+                xc.Conditions.push_back(ec);
+            }
+            dc.ExclusionRules.push_back(xc);
+        }
+        return true;
+    };
+    for (const auto& sc : out->UserDefineConfs.at("pairec_gpu").at("Sorts").arr) {
+        SortConfig c = parse_sort(sc);
+        if (c.SortType == "DiversityRuleSort" && !parse_diversity(sc, &c)) return false;
+        out->GpuSorts.push_back(c);
+    }
     return true;
 }
 }  // namespace recconf
@@ -1317,6 +1378,105 @@ struct GpuCustomFieldSort : sort::ISort {
     }
 };
 
+// DiversityRuleSort (sort/diversity_rule_sort.go:116-283) through pg_diversity_rules: the items' dimension strings
+// (Item.StringProperty, a missing property = "") are dictionary-encoded per call — equal strings, equal codes — and so are the
+// string conditions' literals; integer conditions read the property's integer.  What cannot be served leaves Data untouched and
+// returns an error, which the caller ignores as it ignores every sort's error (sort/sort.go:123).
+struct GpuDiversityRuleSort : sort::ISort {
+    Engine* e;
+    recconf::DiversityRuleSortConfig conf;
+    GpuDiversityRuleSort(Engine* eng, recconf::DiversityRuleSortConfig c) : e(eng), conf(std::move(c)) {}
+    bool Sort(sort::SortData* d, std::string* err) override {
+        const size_t n = d->Data.size();
+        if (n == 0 || conf.DiversityRules.empty()) return true;                    // :121-123
+        if (n > PG_DIV_MAX_N) {
+            if (err) *err = "DiversityRuleSort: " + std::to_string(n) + " items (the device serves up to " + std::to_string(PG_DIV_MAX_N) + ")";
+            return false;
+        }
+        // columns: one per distinct dimension name (codes), one per distinct condition (integers, or codes of the same dictionary)
+        std::vector<std::string> col_names;
+        std::vector<bool> col_is_int;
+        auto column = [&](const std::string& name, bool is_int) {
+            for (size_t c = 0; c < col_names.size(); ++c)
+                if (col_names[c] == name && col_is_int[c] == is_int) return (uint32_t)c;
+            col_names.push_back(name);
+            col_is_int.push_back(is_int);
+            return (uint32_t)(col_names.size() - 1);
+        };
+        pg_div_config cfg;
+        memset(&cfg, 0, sizeof cfg);
+        cfg.size = d->Context ? d->Context->Size : 10;
+        cfg.diversity_size = conf.DiversitySize;
+        cfg.explore_item_size = conf.ExploreItemSize;
+        cfg.n_rules = (uint32_t)conf.DiversityRules.size();
+        for (size_t r = 0; r < conf.DiversityRules.size(); ++r) {
+            const auto& rc = conf.DiversityRules[r];
+            cfg.rules[r].n_dims = (uint32_t)rc.Dimensions.size();
+            for (size_t k = 0; k < rc.Dimensions.size(); ++k) cfg.rules[r].dims[k] = column(rc.Dimensions[k], false);
+            cfg.rules[r].interval = rc.IntervalSize; cfg.rules[r].window = rc.WindowSize;
+            cfg.rules[r].frequency = rc.FrequencySize; cfg.rules[r].weight = rc.Weight;
+        }
+        std::vector<std::vector<uint32_t>> positions(conf.ExclusionRules.size());
+        cfg.n_excl = (uint32_t)conf.ExclusionRules.size();
+        for (size_t x = 0; x < conf.ExclusionRules.size(); ++x) {
+            const auto& xc = conf.ExclusionRules[x];
+            for (long long p : xc.Positions) positions[x].push_back((uint32_t)std::min<long long>(p, 0xFFFFFFFFll));
+            cfg.excl[x].positions = positions[x].data();
+            cfg.excl[x].n_positions = (uint32_t)positions[x].size();
+            cfg.excl[x].n_terms = (uint32_t)xc.Conditions.size();
+            for (size_t t = 0; t < xc.Conditions.size(); ++t)
+                cfg.excl[x].terms[t] = pg_div_term{column(xc.Conditions[t].Name, !xc.Conditions[t].IsString), xc.Conditions[t].Op, xc.Conditions[t].Int};
+        }
+        if (col_names.size() > PG_DIV_MAX_COLS) {
+            if (err) *err = "DiversityRuleSort: " + std::to_string(col_names.size()) + " distinct columns (the device serves up to " + std::to_string(PG_DIV_MAX_COLS) + ")";
+            return false;
+        }
+        cfg.n_cols = (uint32_t)col_names.size();
+        std::vector<int64_t> dims(col_names.size() * n);
+        std::vector<std::map<std::string, int64_t>> dict(col_names.size());
+        for (size_t c = 0; c < col_names.size(); ++c)
+            for (size_t i = 0; i < n; ++i) {
+                const module::Item& it = *d->Data[i];
+                if (col_is_int[c]) {
+                    const auto p = it.Properties.find(col_names[c]);
+                    const bool num = p != it.Properties.end() && p->second.type == json::Value::Number && p->second.num == std::floor(p->second.num);
+                    if (!num) {
+                        if (err) *err = "DiversityRuleSort: item " + it.Id + " has no integer property \"" + col_names[c] + "\" for an exclusion condition";
+                        return false;
+                    }
+                    dims[c * n + i] = p->second.is_int ? p->second.i : (long long)p->second.num;
+                } else {
+                    const auto ins = dict[c].emplace(feature::ItemStringProperty(it, col_names[c]), (int64_t)dict[c].size());
+                    dims[c * n + i] = ins.first->second;
+                }
+            }
+        for (size_t x = 0; x < conf.ExclusionRules.size(); ++x)                      // a literal no item carries: a code no item has
+            for (size_t t = 0; t < conf.ExclusionRules[x].Conditions.size(); ++t) {
+                const auto& ec = conf.ExclusionRules[x].Conditions[t];
+                if (!ec.IsString) continue;
+                const auto& dc = dict[cfg.excl[x].terms[t].column];
+                const auto f = dc.find(ec.Str);
+                cfg.excl[x].terms[t].value = f == dc.end() ? -1 : f->second;
+            }
+        std::vector<uint8_t> source;
+        if (!conf.ExcludeRecalls.empty()) {                                           // :127-138
+            source.resize(n);
+            for (size_t i = 0; i < n; ++i)
+                source[i] = std::find(conf.ExcludeRecalls.begin(), conf.ExcludeRecalls.end(), d->Data[i]->RetrieveId) != conf.ExcludeRecalls.end() ? 0 : 1;
+            cfg.exclude_source_mask = 1u;
+        }
+        std::vector<uint32_t> order(n);
+        if (pg_diversity_rules(e->ctx, &cfg, (uint32_t)n, dims.data(), source.empty() ? nullptr : source.data(), order.data()) != PG_OK) {
+            if (err) *err = pg_err("pg_diversity_rules");
+            return false;
+        }
+        std::vector<module::ItemPtr> out(n);
+        for (size_t i = 0; i < n; ++i) out[i] = d->Data[order[i]];
+        d->Data.swap(out);
+        return true;
+    }
+};
+
 struct GpuSSDSort : sort::ISort {                        // sort/ssd_sort.go:110-343 (embedding table = item table)
     Engine* e;
     recconf::SSDSortConfig conf;
@@ -1873,6 +2033,7 @@ Engine* Engine::Create(const std::string& config_json, std::string* err) {
         else if (sc.SortType == "CustomFieldSort") e->sorts.RegisterSort(sc.Name, std::make_shared<GpuCustomFieldSort>(e.get(), sc), nullptr);
         else if (sc.SortType == "ItemRankScore") e->sorts.RegisterSort(sc.Name, std::make_shared<GpuItemRankScoreSort>(e.get()), nullptr);
         else if (sc.SortType == "ItemScore") e->sorts.RegisterSort(sc.Name, std::make_shared<GpuItemScoreSort>(e.get()), nullptr);
+        else if (sc.SortType == "DiversityRuleSort") e->sorts.RegisterSort(sc.Name, std::make_shared<GpuDiversityRuleSort>(e.get(), sc.DiversityConf), nullptr);
         else { if (err) *err = "pairec_gpu.Sorts: unknown SortType " + sc.SortType; return nullptr; }
     }
     // algorithms by name (the shim's start hook does the same with algorithm.RegisterAlgorithm)

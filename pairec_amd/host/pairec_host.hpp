@@ -129,6 +129,18 @@ struct SSDSortConfig {                     // recconf.go:980-1000 (the fields th
     double MinScorePercent = 0.0;
     std::vector<std::string> FilterRetrieveIds;
 };
+// DiversityRuleSort (recconf.go SortConfig.DiversityRules / ExclusionRules / DiversitySize / ExploreItemSize / ExcludeRecalls), in
+// the form the device serves: a condition is `item property OP literal` — integers under every comparison, strings under
+// equal / not_equal (a dictionary code compares like the string)
+struct DiversityRuleConfig { std::vector<std::string> Dimensions; int WindowSize = 0, FrequencySize = 0, IntervalSize = 0, Weight = 0; };
+struct ExclusionCondition { std::string Name; int Op = 0; bool IsString = false; long long Int = 0; std::string Str; };   // Op: pg_where_op
+struct ExclusionRuleConfig { std::vector<long long> Positions; std::vector<ExclusionCondition> Conditions; };
+struct DiversityRuleSortConfig {
+    int DiversitySize = 0, ExploreItemSize = 0;
+    std::vector<std::string> ExcludeRecalls;
+    std::vector<DiversityRuleConfig> DiversityRules;
+    std::vector<ExclusionRuleConfig> ExclusionRules;
+};
 struct SortConfig {                        // recconf.go:820-838: Name, SortType, nested DPPConf / SSDConf
     std::string Name, SortType;
     std::string SortByField;               // AlgoScoreSort (sort/algo_score_sort.go:17-27), CustomFieldSort (custom_field_sort.go:21-38)
@@ -137,6 +149,7 @@ struct SortConfig {                        // recconf.go:820-838: Name, SortType
     std::string HologresName;              // DPPConf / SSDConf .DaoConf.HologresName: what NewDPPSort / NewSSDSort open first
     DPPSortConfig DPPConf;
     SSDSortConfig SSDConf;
+    DiversityRuleSortConfig DiversityConf; // pairec_gpu.Sorts entries of SortType DiversityRuleSort only
 };
 struct FeatureConfig {                      // recconf.go:256-265
     std::string FeatureType, FeatureName, FeatureSource, FeatureValue, FeatureStore, Normalizer, Expression;
