@@ -278,6 +278,18 @@ int pg_expr_num_vars(const pg_expr* e);
  * ExprASTResultByAntlr's error rule — an item that lacks ANY variable of the expression scores 0 (ast.go:374-383) — is the
  * caller's to apply (pg_expr_is_antlr tells it to). */
 int pg_expr_compile_typed(const char* source, const char* ast_type, pg_expr** out);
+/* The arithmetic subset of govaluate that BoostScoreSort expressions use (sort/boost_score_sort.go:20-36,
+ * NewEvaluableExpressionWithFunctions with utils.GovaluateFunctions), compiled to the same program: float64 literals (digits and
+ * '.'), bare and [bracketed] names, + - * / % **, unary minus, parentheses, round(x) = math.Round and round(x, n) =
+ * math.Trunc(x * Pow(10, n)) / Pow(10, n) (utils/govaluate_functions.go:63-75).  Every number is a float64; `/` is Go's float
+ * division (±Inf / NaN, no error); `%` is math.Mod; `**` is math.Pow as the `^` of the default grammar states it; precedence
+ * + -  <  * / %  <  **  <  prefix minus (so -a ** 2 is (-a) ** 2), as the feature normalizer's govaluate evaluator has it.
+ * Refused by name (PG_ERR_UNSUPPORTED): comparators, the ternary, && ||, ! ~ and the bitwise operators, strings, booleans,
+ * accessors, arrays, a chained **, every other function.  "" compiles to the empty expression.
+ * pg_expr_eval_host evaluates any compiled expression on host arrays (vars [n_vars][n_items], as pg_expr_eval): the program's
+ * host statement, no context, no device; PG_ERR_ARITH as pg_expr_eval. */
+int pg_expr_compile_govaluate(const char* source, pg_expr** out);
+int pg_expr_eval_host(const pg_expr* e, const double* vars, uint32_t n_items, double* out_scores);
 int pg_expr_is_antlr(const pg_expr* e);
 /* RankConfig.ScoreRewrite (recconf/recconf.go:743; service/rank/rank_service.go:296-306,343-353): a map source → expression.
  * Per item the reference evaluates EVERY source's expression over the item as the algorithms left it, collects the results
@@ -1110,6 +1122,145 @@ int pg_diversity_rules_features_dev(pg_ctx* ctx, const pg_div_config* cfg, const
                                     const uint8_t* d_source, const uint8_t* d_enable, uint32_t* d_order);
 int pg_diversity_rules(pg_ctx* ctx, const pg_div_config* cfg, uint32_t n, const int64_t* dims, const uint8_t* source,
                        uint32_t* order);
+
+/* module.FilterParam as a compiled condition set, ItemStateFilter and BoostScoreSort on the device (DESIGN.md 4.1p;
+ * csrc/cond.hip).  ItemStateFilter (filter/item_state_filter.go:47-57, module/item_state_filter_hologres_dao.go:86-357) keeps, in
+ * order, the candidates whose state columns pass one FilterParam; BoostScoreSort (sort/boost_score_sort.go:73-104) rewrites
+ * Item.Score by the expression of the first BoostScoreCondition whose FilterParam matches, or of every matching one in sequence
+ * (BoostScoreConditionsFilterAll).  Both are one small program of `name OP value` operators (module/filter_op.go:453-540) per
+ * candidate over columns keyed by item row.
+ *   Rules     1 .. PG_COND_MAX_RULES rules; a rule is one FilterParam: 0 .. PG_COND_MAX_TERMS operators in the order given, all
+ *             ANDed (EvaluateByDomain, :507-540; none: true, :539).  A `bool` operator (one level, :1679-1756) is followed by
+ *             its children, which carry depth 1 and count among the rule's operators: bool_and == 0 (Type "" / "or") → any
+ *             child, no children false; bool_and != 0 → every child, no children true.
+ *   Terms     {name, domain "item" | "user" ("" = item, as the constructors do), op, type, right-hand side}.  Types: int and
+ *             int64 on int32 / int64 columns (compared as int64: Go's int is 64-bit), float on any numeric column (compared as
+ *             float64(value)), string for equal / not_equal / in / not_in over dictionary ids the caller encoded (integer
+ *             columns).  Right-hand side: a constant (i, or f for float), user.<rhs_name>, item.<rhs_name> (another column), or
+ *             for in / not_in a constant list of <= PG_COND_MAX_LIST values (sorted here, searched on the device).
+ *   Binding   item names are columns DECLARED at compile {name, dtype} and bound by name to a pg_features store at run time
+ *             (the store's dtype must be the declared one: PG_ERR_INVALID); only referenced columns are read, at most
+ *             PG_COND_MAX_COLS.  User names become user slots in order of first use (pg_cond_user_slot_name), at most
+ *             PG_COND_MAX_SLOTS: per request one 8-byte value per slot — int64, or fp64 when the terms that read it are float
+ *             (pg_cond_user_slot_is_float; both is PG_ERR_INVALID) — and one presence bit per slot.
+ *   Missing   the reference's "property missing from the map" branch is taken for a candidate whose row is outside the store
+ *             (row >= the store's rows: the ItemStateFilter item absent from the state table, :313-340 of the DAO with empty
+ *             defaultFieldValues — column defaults are NOT read) and for a user slot whose presence bit is clear.  Answers,
+ *             from the form EvaluateByDomain dispatches to (DomainEvaluate; Evaluate for is_null / is_not_null):
+ *               left missing      not_equal → true (:231-234), is_null → true (:1588-1596), every other operator false
+ *                                 (:85-88, :356-359, :597-600, :771-774, :945-948, :1119-1122, :1492-1495, :1621-1626)
+ *               type not listed   equal / not_equal with float → false (:167-169, :310-312); in / not_in with int64 or float
+ *                                 → false (:420, :1562), whether the property is there or not
+ *               user.x missing    equal false (:98-101), not_equal true (:244-247), ordered comparisons false (:610-613 ...)
+ *               item.x missing    equal false (:106-109), not_equal true (:252-255), ordered comparisons TRUE for float
+ *                                 (:618-621, :792-795, :966-969, :1140-1143) and false for int / int64 (:643-646 ...)
+ *   Refused   by name at compile, nothing allocated.  PG_ERR_UNSUPPORTED: contains / not_contains (list-valued properties);
+ *             expression (expr-lang); ordered comparisons on string; int / int64 / string terms on float columns (utils.ToInt
+ *             has no float32 case and truncates float64); in / not_in against user.x / item.x and PG_COND_RHS_USER_LIST
+ *             (list-valued properties); a bool below a bool; a domain other than item / user (:533-535); more rules, operators,
+ *             list values, referenced columns or user slots than the limits; in a boost rule set an item term or item.x named
+ *             `score` (the reference's clone gains a score key in the middle of the walk, boost_score_sort.go:81) and an
+ *             expression over PG_COND_MAX_EXPR_OPS operations or PG_COND_MAX_EXPR_DEPTH stack slots.  PG_ERR_INVALID: unknown
+ *             enum values, a name that is not declared, a boost rule without an expression (a nil dereference in the
+ *             reference when its condition matches, :22-29,:82), an expression in a set that is not a boost set.
+ *   Boost     (boost = 1) every rule carries a govaluate expression (pg_expr_compile_govaluate's subset) over `score` — the
+ *             entry's current fp64 score — and declared columns as float64.  Per candidate, rules in order; on a match the
+ *             expression's value replaces the score; without filter_all the walk ends at the first match, with it later rules
+ *             see the rewritten score.  An expression that errors — a column variable of a candidate outside the store —
+ *             leaves the score and still is the match (the break at :95-97 is outside the else).  out_rule: the last rule that
+ *             matched, 0xFF for none.  Padding entries keep their score bits and get 0xFF.
+ *   host      pg_cond_match_host / pg_boost_scores_host: pure host functions (no context, no device), the same answer stated
+ *             item by item over candidate-aligned arrays: cols[d] = the n values of declared column d in its dtype (NULL for
+ *             columns nothing references), item_in[i] = 0 for a candidate outside the store (NULL: all inside), user_vals
+ *             [n slots] / user_present for the one request.  They validate configs and are what tests compare the kernels
+ *             with; the library falls back to them for nothing.
+ *   filter    pg_item_state_filter_dev evaluates rule 0 and compacts in ONE launch on the context's stream, no synchronisation
+ *             (the first device call with a set uploads its lists and programs once, synchronously).  In: pg_fanin_merge_dev's
+ *             outputs as they are, nq <= 256, cap <= PG_TRIM_MAX_CAP: d_rows uint64 [nq][cap], d_score fp64, optional d_source
+ *             uint8, d_count [nq], d_source_mask uint32 and up to PG_TRIM_MAX_PLANES fp64 and fp32 planes [n][nq][cap]; an entry
+ *             is padding if its row is UINT64_MAX or its position is >= d_count[q]: dropped, never counted.  d_user_vals
+ *             [nq][PG_COND_MAX_SLOTS] 8-byte values, d_user_present [nq] bit s = slot s present (both may be NULL when the set
+ *             has no user slots).  Out [nq][cap]: the kept entries in order with everything carried, d_out_count[q], and
+ *             padding behind the count: UINT64_MAX rows, NaN scores and fp64 planes, source 0xFF, mask 0, fp32 planes 0 —
+ *             accepted by pg_candidates_trim_dev unchanged.  Every output element is written exactly once; an output that
+ *             overlaps its input is PG_ERR_INVALID.
+ *   boost     pg_boost_scores_dev: d_out_score [nq][cap] and optionally d_out_rule [nq][cap] uint8; order untouched
+ *             (pg_sort_scores_dev runs next); one launch, no synchronisation.  d_out_score may be d_score itself (a lane reads
+ *             its entry, then writes it); any other overlap of the two is undefined.  A score an expression rewrites to NaN is
+ *             "a NaN": the sign and payload of a generated or propagated NaN are the platform's (x86 and gfx950 differ); a
+ *             score no rule rewrote keeps its bits, NaN payloads included.
+ *   Sharing   a compiled set may be used by several contexts of ONE device, also concurrently (the upload of its table is
+ *             guarded inside the set); a second device is PG_ERR_INVALID.  pg_cond_free waits for that device.
+ *   one       host arrays of one request (upload, run, download, synchronise).  pg_item_state_filter: rows / score / source of
+ *             the request against a store.  pg_boost_scores: pg_boost_scores_host's arguments — the candidates' own values,
+ *             as a sort holds them in its items' properties — which become a store of n rows in context scratch.  n = 0 is an empty
+ *             answer (PG_OK, count 0), not an error.
+ *   Kernels   one lane per candidate: its row, then every referenced column's raw value — all loads issued before the first
+ *             use — then the term list, a by-value kernel argument; lists and programs are read at wave-uniform addresses;
+ *             the expression stack is 8 registers deep.  The filter: one workgroup of 1 024 lanes per request walks cap in
+ *             chunks, wave ballots + per-wave counts in LDS give each kept entry its slot. */
+#define PG_COND_MAX_RULES 8
+#define PG_COND_MAX_TERMS 8
+#define PG_COND_MAX_COLS 16
+#define PG_COND_MAX_SLOTS 8
+#define PG_COND_MAX_LIST 64
+#define PG_COND_MAX_EXPR_OPS 64
+#define PG_COND_MAX_EXPR_DEPTH 8
+typedef enum {
+    PG_COND_EQUAL = 0, PG_COND_NOT_EQUAL = 1, PG_COND_GREATER = 2, PG_COND_GREATER_THAN = 3, PG_COND_LESS = 4, PG_COND_LESS_THAN = 5,
+    PG_COND_IN = 6, PG_COND_NOT_IN = 7, PG_COND_IS_NULL = 8, PG_COND_IS_NOT_NULL = 9, PG_COND_BOOL = 10,
+    PG_COND_CONTAINS = 11, PG_COND_NOT_CONTAINS = 12, PG_COND_EXPRESSION = 13      /* the last three: refused by name */
+} pg_cond_op;      /* "greater" is >, "greaterThan" is >=, "less" is <, "lessThan" is <= (filter_op.go:627, :801, :975, :1149) */
+typedef enum { PG_COND_INT = 0, PG_COND_INT64 = 1, PG_COND_FLOAT = 2, PG_COND_STRING = 3 } pg_cond_type;
+typedef enum { PG_COND_RHS_CONST = 0, PG_COND_RHS_USER = 1, PG_COND_RHS_ITEM = 2, PG_COND_RHS_USER_LIST = 3 /* refused */ } pg_cond_rhs;
+typedef struct {
+    const char*      name;      /* the left property (unused for PG_COND_BOOL) */
+    const char*      domain;    /* "item", "user"; NULL or "" = item */
+    int32_t          op;        /* pg_cond_op */
+    int32_t          type;      /* pg_cond_type (ignored by is_null / is_not_null / bool) */
+    int32_t          rhs;       /* pg_cond_rhs */
+    uint32_t         depth;     /* 0, or 1 for a child of the bool in front */
+    uint32_t         bool_and;  /* PG_COND_BOOL: 0 = or, else and */
+    uint32_t         n_list;    /* in / not_in */
+    long long        i;         /* the constant of int / int64 / string terms */
+    double           f;         /* the constant of float terms */
+    const char*      rhs_name;  /* PG_COND_RHS_USER / _ITEM: the name behind "user." / "item." */
+    const long long* list;      /* in / not_in: n_list values */
+} pg_cond_term;
+typedef struct {
+    const pg_cond_term* terms;
+    uint32_t            n_terms;
+    const char*         expression;   /* boost rule sets: BoostScoreCondition.Expression; else NULL */
+} pg_cond_rule;
+typedef struct {
+    const char* name;
+    int32_t     dtype;                /* pg_feature_dtype */
+} pg_cond_col;
+typedef struct pg_cond pg_cond;
+int pg_cond_compile(const pg_cond_rule* rules, uint32_t n_rules, const pg_cond_col* cols, uint32_t n_cols, uint32_t boost, pg_cond** out);
+int pg_cond_free(pg_cond* c);
+int pg_cond_num_rules(const pg_cond* c);
+int pg_cond_num_user_slots(const pg_cond* c);
+const char* pg_cond_user_slot_name(const pg_cond* c, int i);
+int pg_cond_user_slot_is_float(const pg_cond* c, int i);
+int pg_cond_match_host(const pg_cond* c, uint32_t rule, uint32_t n, const uint8_t* item_in, const void* const* cols, const uint64_t* user_vals,
+                       uint32_t user_present, uint8_t* out_match);
+int pg_boost_scores_host(const pg_cond* c, uint32_t filter_all, uint32_t n, const uint8_t* item_in, const void* const* cols,
+                         const uint64_t* user_vals, uint32_t user_present, const double* score, double* out_score, uint8_t* out_rule);
+int pg_item_state_filter_dev(pg_ctx* ctx, pg_cond* c, const pg_features* fs, uint32_t nq, uint32_t cap, const uint64_t* d_rows,
+                             const double* d_score, const uint8_t* d_source, const uint32_t* d_count, const double* d_planes_f64,
+                             uint32_t n_f64, const uint32_t* d_source_mask, const float* d_planes_f32, uint32_t n_f32,
+                             const uint64_t* d_user_vals, const uint32_t* d_user_present, uint64_t* d_out_rows, double* d_out_score,
+                             uint8_t* d_out_source, double* d_out_planes_f64, uint32_t* d_out_source_mask, float* d_out_planes_f32,
+                             uint32_t* d_out_count);
+int pg_boost_scores_dev(pg_ctx* ctx, pg_cond* c, const pg_features* fs, uint32_t filter_all, uint32_t nq, uint32_t cap, const uint64_t* d_rows,
+                        const double* d_score, const uint32_t* d_count, const uint64_t* d_user_vals, const uint32_t* d_user_present,
+                        double* d_out_score, uint8_t* d_out_rule);
+int pg_item_state_filter(pg_ctx* ctx, pg_cond* c, const pg_features* fs, uint32_t n, const uint64_t* rows, const double* score,
+                         const uint8_t* source, const uint64_t* user_vals, uint32_t user_present, uint64_t* out_rows, double* out_score,
+                         uint8_t* out_source, uint32_t* out_count);
+int pg_boost_scores(pg_ctx* ctx, pg_cond* c, uint32_t filter_all, uint32_t n, const uint8_t* item_in, const void* const* cols,
+                    const uint64_t* user_vals, uint32_t user_present, const double* score, double* out_score, uint8_t* out_rule);
 
 /* ---- shard group: one process, several GPUs --------------------------------------------------------
  * BASELINE.json configs[4] / SURVEY.md 8e behind the C ABI (a cgo host cannot join a torch.distributed job): the item

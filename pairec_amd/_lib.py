@@ -50,6 +50,10 @@ EXPORTS = [
     "pg_fanin_merge_dev", "pg_recommend_candidates_dnn3_dev",
     "pg_trim_out_cap", "pg_candidates_trim_dev", "pg_recommend_cascade_dnn3_dev",
     "pg_diversity_rules_host", "pg_diversity_rules_dev", "pg_diversity_rules_features_dev", "pg_diversity_rules",
+    "pg_expr_compile_govaluate", "pg_expr_eval_host",
+    "pg_cond_compile", "pg_cond_free", "pg_cond_num_rules", "pg_cond_num_user_slots", "pg_cond_user_slot_name",
+    "pg_cond_user_slot_is_float", "pg_cond_match_host", "pg_boost_scores_host", "pg_item_state_filter_dev", "pg_boost_scores_dev",
+    "pg_item_state_filter", "pg_boost_scores",
 ]
 
 
@@ -132,6 +136,20 @@ class PgDivConfig(C.Structure):
     _fields_ = [("size", C.c_int32), ("diversity_size", C.c_int32), ("explore_item_size", C.c_int32),
                 ("exclude_source_mask", C.c_uint32), ("n_cols", C.c_uint32), ("n_rules", C.c_uint32), ("n_excl", C.c_uint32),
                 ("n_multi_value", C.c_uint32), ("rules", PgDivRule * 8), ("excl", PgDivExclusion * 8)]
+
+
+class PgCondTerm(C.Structure):
+    _fields_ = [("name", C.c_char_p), ("domain", C.c_char_p), ("op", C.c_int32), ("type", C.c_int32), ("rhs", C.c_int32),
+                ("depth", C.c_uint32), ("bool_and", C.c_uint32), ("n_list", C.c_uint32), ("i", C.c_longlong), ("f", C.c_double),
+                ("rhs_name", C.c_char_p), ("list", C.POINTER(C.c_longlong))]
+
+
+class PgCondRule(C.Structure):
+    _fields_ = [("terms", C.POINTER(PgCondTerm)), ("n_terms", C.c_uint32), ("expression", C.c_char_p)]
+
+
+class PgCondCol(C.Structure):
+    _fields_ = [("name", C.c_char_p), ("dtype", C.c_int32)]
 
 
 class PgIndexRefreshParams(C.Structure):
@@ -264,6 +282,19 @@ def load():
         "pg_diversity_rules_dev": [vp, P(PgDivConfig), u32, u32, vp, vp, vp, vp, vp],
         "pg_diversity_rules_features_dev": [vp, P(PgDivConfig), vp, P(C.c_char_p), u32, u32, vp, vp, vp, vp, vp],
         "pg_diversity_rules": [vp, P(PgDivConfig), u32, vp, vp, vp],
+        "pg_expr_compile_govaluate": [C.c_char_p, P(vp)],
+        "pg_expr_eval_host": [vp, vp, u32, vp],
+        "pg_cond_compile": [P(PgCondRule), u32, P(PgCondCol), u32, u32, P(vp)],
+        "pg_cond_free": [vp],
+        "pg_cond_num_rules": [vp],
+        "pg_cond_num_user_slots": [vp],
+        "pg_cond_user_slot_is_float": [vp, i32],
+        "pg_cond_match_host": [vp, u32, u32, vp, P(vp), vp, u32, vp],
+        "pg_boost_scores_host": [vp, u32, u32, vp, P(vp), vp, u32, vp, vp, vp],
+        "pg_item_state_filter_dev": [vp, vp, vp, u32, u32, vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+        "pg_boost_scores_dev": [vp, vp, vp, u32, u32, u32, vp, vp, vp, vp, vp, vp, vp],
+        "pg_item_state_filter": [vp, vp, vp, u32, vp, vp, vp, vp, u32, vp, vp, vp, vp],
+        "pg_boost_scores": [vp, vp, u32, u32, vp, P(vp), vp, u32, vp, vp, vp],
         "pg_index_refresh": [vp, vp, P(PgIndexRefreshParams)],
         "pg_index_refresh_stats": [vp, P(PgIndexRefreshStats)],
         "pg_index_screen_probe": [vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, vp, vp],
@@ -382,6 +413,8 @@ def load():
     L.pg_expr_var_name.restype = C.c_char_p
     L.pg_where_column_name.argtypes = [vp, i32]
     L.pg_where_column_name.restype = C.c_char_p
+    L.pg_cond_user_slot_name.argtypes = [vp, i32]
+    L.pg_cond_user_slot_name.restype = C.c_char_p
     _lib = L
     return L
 

@@ -1,0 +1,965 @@
+// cond.hip — module.FilterParam as a compiled object with one device evaluator, and the two stages that are nothing but it
+// (DESIGN.md 4.1p): ItemStateFilter (filter/item_state_filter.go:47-57, module/item_state_filter_hologres_dao.go:86-357: keep, in
+// order, the candidates whose state columns pass one FilterParam) and BoostScoreSort (sort/boost_score_sort.go:73-104: the first
+// BoostScoreCondition whose FilterParam matches rewrites Item.Score by a govaluate expression; with
+// BoostScoreConditionsFilterAll every matching one does, in sequence).
+//
+// A FilterParam (module/filter_op.go:453-540) is a list of `name OP value` operators, all ANDed by EvaluateByDomain (:507-540).
+// Here a rule is that list compiled against declared columns; the reference's "property missing from the map" branch is taken
+// for a candidate whose row lies outside the feature store (item properties) and for a user slot whose presence bit is clear
+// (user properties).  What every operator answers, transcribed operator by operator from the form EvaluateByDomain dispatches to
+// (DomainEvaluate for all but is_null / is_not_null, which only have Evaluate):
+//   left missing        not_equal → true (:231-234); is_null → true (:1588-1596); every other operator → false
+//                       (:85-88, :356-359, :597-600, :771, :945, :1119, :1492-1495, :1621-1626)
+//   type not listed     equal / not_equal with float → false (:167-169, :310-312); in / not_in with int64 or float → false
+//                       (:420, :1562: their switches list "string" and "int" only); left present or not
+//   `user.x` missing    equal → false (:98-101), not_equal → true (:244-247), the four ordered comparisons → false (:610-613 …)
+//   `item.x` missing    equal → false (:106-109), not_equal → true (:252-255); ordered comparisons: true for float
+//                       (:618-621, :792-795, :966-969, :1140-1143) and false for int / int64 (:643-646, :667-670 …).  With one
+//                       store per rule set this is reached by user-domain terms only: an item-domain term of such a candidate
+//                       has already answered for its missing left side.
+//   values              int / int64 compare as int64 (utils.ToInt / ToInt64 of an integer column; Go's int is 64-bit); float
+//                       compares float64(value) (utils.ToFloat); string compares dictionary ids the caller encoded
+//   bool                one level (:1679-1756): Type "" / "or" → any child (no children: false), anything else → every child
+//                       (no children: true); its own domain is always item (:1758-1760)
+//   no operators        true (:539)
+// in lists are sorted at compile time and searched.  Everything the evaluator does not state exactly is refused by name at
+// compile (pg_cond_compile in include/pairec_gpu.h lists it).
+//
+// Kernels: one lane per candidate.  The lane loads its row, then every referenced column's value (raw bits, <= 16 loads issued
+// before the first use), then walks the terms, which travel as a by-value kernel argument; in lists and expression programs lie
+// in a small device table uploaded once per compiled set and are read with wave-uniform addresses.  The expression walk keeps
+// an 8-deep stack in registers (constant indices only: the top is always slot 0).
+//   item_state_filter_kernel   one workgroup per request walks cap in chunks of 1 024: ballot + mbcnt within a wave, per-wave
+//                              counts in LDS (two sets: a wave one chunk ahead writes the other), every lane adds up the counts
+//                              itself, so one barrier per chunk; kept entries move to the front with everything carried.
+//   boost_scores_kernel        256 lanes per workgroup, grid (cap / 256, nq).
+#include "pipeline.hpp"
+#include "expr_prog.hpp"
+
+#include <algorithm>
+#include <cstdarg>
+#include <cstring>
+#include <memory>
+
+namespace pg {
+namespace {
+
+constexpr uint32_t kCondMaxRules = 8, kCondMaxTerms = 8, kCondMaxCols = 16, kCondMaxSlots = 8, kCondMaxList = 64;
+constexpr uint32_t kCondMaxExprOps = 64, kCondMaxExprDepth = 8;
+constexpr uint32_t kCondMaxPlanes = 8, kCondMaxCap = 16384, kCondChunk = 1024, kCondWaves = kCondChunk / kWave;
+static_assert(kCondMaxRules == PG_COND_MAX_RULES && kCondMaxTerms == PG_COND_MAX_TERMS && kCondMaxCols == PG_COND_MAX_COLS &&
+                  kCondMaxSlots == PG_COND_MAX_SLOTS && kCondMaxList == PG_COND_MAX_LIST && kCondMaxExprOps == PG_COND_MAX_EXPR_OPS &&
+                  kCondMaxExprDepth == PG_COND_MAX_EXPR_DEPTH,
+              "include/pairec_gpu.h repeats these");
+static_assert(kCondMaxPlanes == PG_TRIM_MAX_PLANES && kCondMaxCap == PG_TRIM_MAX_CAP && kCondMaxCap == PG_FANIN_MAX_CAP,
+              "the filter takes the fan-in's outputs and feeds the trim");
+constexpr unsigned long long kCondPad = ~0ull;
+constexpr unsigned long long kCondNan = 0x7FF8000000000000ull;
+constexpr uint32_t kVarScore = 0xFFFFu;           // Instr.arg of the variable `score`
+
+struct CondTerm {                                 // 24 bytes
+    uint8_t op, type, rhs, user_left;             // pg_cond_op, pg_cond_type, pg_cond_rhs; left side: 0 = column `left`, 1 = user slot `left`
+    uint8_t left, rhs_idx, depth, is_and;         // rhs_idx: user slot or referenced column; depth 1: a child of the bool in front
+    union { long long i; double f; } c;           // the constant
+    uint16_t list_off, list_n;                    // in / not_in: values [list_off, list_off + list_n) of the table, ascending
+    uint32_t pad;
+};
+struct CondRule { uint8_t term_off, n_terms; uint16_t prog_off, prog_n, pad; };
+struct CondCol { const void* base; int32_t dtype; int32_t pad; };
+struct CondProgram {                              // what both kernels and the host statement walk
+    CondCol cols[kCondMaxCols];                   // the referenced columns (host statement: base = the caller's candidate-aligned array)
+    CondTerm terms[kCondMaxRules * kCondMaxTerms];
+    CondRule rules[kCondMaxRules];
+    const long long* lists;
+    const Instr* progs;
+    uint32_t n_used, n_rules;
+    uint64_t store_rows;
+};
+
+// the candidate as the evaluator sees it: raw bits of every referenced column (meaningful iff item_in), the request's user slots
+struct CondItem {
+    unsigned long long raw[kCondMaxCols];
+    bool item_in;
+};
+struct CondUser {
+    const unsigned long long* vals;               // [kCondMaxSlots] bits: int64 or fp64 by the slot's type
+    uint32_t present;
+};
+
+// r[k] for a wave-uniform k as a chain of selects over constant indices: the values stay in registers.  (Left to itself the
+// optimiser folds the chain back into one indexed read, which puts the array in scratch; the empty asm keeps the links apart.)
+template <int N>
+__host__ __device__ __forceinline__ unsigned long long cond_pick(const unsigned long long (&r)[N], uint32_t k) {
+    unsigned long long v = r[0];
+#pragma unroll
+    for (int j = 1; j < N; ++j) {
+        v = k == (uint32_t)j ? r[j] : v;
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm volatile("" : "+v"(v));
+#endif
+    }
+    return v;
+}
+__host__ __device__ __forceinline__ double cond_bits_f64(unsigned long long b) {
+    double d;
+    memcpy(&d, &b, 8);
+    return d;
+}
+__host__ __device__ __forceinline__ long long cond_col_i64(const CondProgram& p, const CondItem& it, uint32_t k) {
+    const unsigned long long b = cond_pick(it.raw, k);
+    return p.cols[k].dtype == PG_F_I32 ? (long long)(int32_t)(uint32_t)b : (long long)b;          // (integer columns: the compiler checked)
+}
+__host__ __device__ __forceinline__ double cond_col_f64(const CondProgram& p, const CondItem& it, uint32_t k) {
+    const unsigned long long b = cond_pick(it.raw, k);
+    switch (p.cols[k].dtype) {
+        case PG_F_I32: return (double)(int32_t)(uint32_t)b;
+        case PG_F_I64: return (double)(long long)b;
+        case PG_F_F32: {
+            const uint32_t w = (uint32_t)b;
+            float f;
+            memcpy(&f, &w, 4);
+            return (double)f;
+        }
+        default: return cond_bits_f64(b);
+    }
+}
+
+// one operator that is not a bool (see the file header for where every answer comes from)
+__host__ __device__ __forceinline__ bool cond_term(const CondProgram& p, const CondTerm& t, const CondItem& it, const CondUser& u) {
+    const bool left_in = t.user_left ? ((u.present >> t.left) & 1u) != 0 : it.item_in;
+    if (t.op == PG_COND_IS_NULL) return !left_in;
+    if (t.op == PG_COND_IS_NOT_NULL) return left_in;
+    if (!left_in) return t.op == PG_COND_NOT_EQUAL;
+    const bool is_float = t.type == PG_COND_FLOAT;
+    if (t.op == PG_COND_EQUAL || t.op == PG_COND_NOT_EQUAL) {
+        if (is_float) return false;
+    } else if (t.op == PG_COND_IN || t.op == PG_COND_NOT_IN) {
+        if (is_float || t.type == PG_COND_INT64) return false;
+        const long long v = t.user_left ? (long long)u.vals[t.left] : cond_col_i64(p, it, t.left);
+        uint32_t lo = 0, hi = t.list_n;                               // the first value >= v
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (p.lists[t.list_off + mid] < v) lo = mid + 1; else hi = mid;
+        }
+        const bool found = lo < t.list_n && p.lists[t.list_off + lo] == v;
+        return t.op == PG_COND_IN ? found : !found;
+    }
+    // the right-hand side
+    if (t.rhs == PG_COND_RHS_USER && !((u.present >> t.rhs_idx) & 1u)) return t.op == PG_COND_NOT_EQUAL;
+    if (t.rhs == PG_COND_RHS_ITEM && !it.item_in) return t.op == PG_COND_NOT_EQUAL || (t.op >= PG_COND_GREATER && is_float);
+    if (is_float) {
+        const double l = t.user_left ? cond_bits_f64(u.vals[t.left]) : cond_col_f64(p, it, t.left);
+        const double r = t.rhs == PG_COND_RHS_USER ? cond_bits_f64(u.vals[t.rhs_idx])
+                         : t.rhs == PG_COND_RHS_ITEM ? cond_col_f64(p, it, t.rhs_idx) : t.c.f;
+        switch (t.op) {
+            case PG_COND_GREATER: return l > r;
+            case PG_COND_GREATER_THAN: return l >= r;
+            case PG_COND_LESS: return l < r;
+            default: return l <= r;
+        }
+    }
+    const long long l = t.user_left ? (long long)u.vals[t.left] : cond_col_i64(p, it, t.left);
+    const long long r = t.rhs == PG_COND_RHS_USER ? (long long)u.vals[t.rhs_idx] : t.rhs == PG_COND_RHS_ITEM ? cond_col_i64(p, it, t.rhs_idx) : t.c.i;
+    switch (t.op) {
+        case PG_COND_EQUAL: return l == r;
+        case PG_COND_NOT_EQUAL: return l != r;
+        case PG_COND_GREATER: return l > r;
+        case PG_COND_GREATER_THAN: return l >= r;
+        case PG_COND_LESS: return l < r;
+        default: return l <= r;
+    }
+}
+
+// FilterParam.EvaluateByDomain of rule r (filter_op.go:507-540; a bool's children: :1679-1756)
+__host__ __device__ __forceinline__ bool cond_rule(const CondProgram& p, uint32_t r, const CondItem& it, const CondUser& u) {
+    const uint32_t t0 = p.rules[r].term_off, t1 = t0 + p.rules[r].n_terms;
+    bool all = true;
+    uint32_t i = t0;
+    while (i < t1) {
+        const CondTerm& t = p.terms[i];
+        bool v;
+        if (t.op == PG_COND_BOOL) {
+            bool any = false, every = true;
+            for (++i; i < t1 && p.terms[i].depth == 1; ++i) {
+                const bool c = cond_term(p, p.terms[i], it, u);
+                any = any || c;
+                every = every && c;
+            }
+            v = t.is_and ? every : any;
+        } else {
+            v = cond_term(p, t, it, u);
+            ++i;
+        }
+        all = all && v;
+    }
+    return all;
+}
+
+// rule r's expression on the candidate (boost_score_sort.go:81-94): false = govaluate errors (a column of a candidate outside the
+// store: "No parameter found"), the score stays.  The stack's top is st[0]; a push moves everything down one slot.
+__host__ __device__ __forceinline__ bool cond_expr(const CondProgram& p, uint32_t r, const CondItem& it, double score, double* out) {
+    double st[kCondMaxExprDepth];
+#pragma unroll
+    for (uint32_t j = 0; j < kCondMaxExprDepth; ++j) st[j] = 0.0;
+    bool ok = true;
+    const Instr* prog = p.progs + p.rules[r].prog_off;
+    const uint32_t n = p.rules[r].prog_n;
+    for (uint32_t pc = 0; pc < n; ++pc) {
+        const Instr in = prog[pc];
+        if (in.op == OP_CONST || in.op == OP_VAR) {
+            double v = in.val;
+            if (in.op == OP_VAR) {
+                if (in.arg == kVarScore) v = score;
+                else if (it.item_in) v = cond_col_f64(p, it, in.arg);
+                else ok = false;
+            }
+#pragma unroll
+            for (uint32_t j = kCondMaxExprDepth - 1; j > 0; --j) st[j] = st[j - 1];
+            st[0] = v;
+        } else if (in.op == OP_NEG) {
+            st[0] = -st[0];
+        } else if (in.op == OP_ROUND) {
+            st[0] = round(st[0]);
+        } else {
+            double v;
+            expr_binop(in.op, st[1], st[0], &v);            // (the govaluate front end emits no operator that panics)
+            st[0] = v;
+#pragma unroll
+            for (uint32_t j = 1; j + 1 < kCondMaxExprDepth; ++j) st[j] = st[j + 1];
+        }
+    }
+    *out = st[0];
+    return ok;
+}
+
+// BoostScoreSort.doSort's inner loop for one item (:79-99): returns the last rule that matched (0xFF: none)
+__host__ __device__ __forceinline__ uint32_t cond_boost(const CondProgram& p, bool filter_all, const CondItem& it, const CondUser& u, double* score) {
+    uint32_t last = 0xFFu;
+    for (uint32_t r = 0; r < p.n_rules; ++r) {
+        if (!cond_rule(p, r, it, u)) continue;
+        double v;
+        if (cond_expr(p, r, it, *score, &v)) *score = v;
+        last = r;
+        if (!filter_all) break;                          // (outside the else: an expression that errors still ends the walk)
+    }
+    return last;
+}
+
+// ---- kernels ---------------------------------------------------------------------------------------------------------------
+// the referenced columns of `row`, every load issued before anything uses one
+__device__ __forceinline__ void cond_load(const CondProgram& p, unsigned long long row, CondItem* it) {
+    it->item_in = row < p.store_rows;
+#pragma unroll
+    for (uint32_t k = 0; k < kCondMaxCols; ++k) {
+        unsigned long long b = 0;
+        if (k < p.n_used && it->item_in) {
+            const int dt = p.cols[k].dtype;
+            if (dt == PG_F_I32 || dt == PG_F_F32) b = ((const uint32_t*)p.cols[k].base)[row];
+            else b = ((const unsigned long long*)p.cols[k].base)[row];
+        }
+        it->raw[k] = b;
+    }
+}
+
+struct FilterArgs {
+    const uint64_t* rows;                        // [nq][cap]
+    const unsigned long long* score;             // fp64 bits
+    const uint8_t* source;                       // [nq][cap] or NULL
+    const uint32_t* count;                       // [nq] or NULL
+    const unsigned long long* planes64;          // [n_f64][nq][cap] or NULL
+    const uint32_t* mask;                        // [nq][cap] or NULL
+    const uint32_t* planes32;                    // [n_f32][nq][cap] or NULL
+    const unsigned long long* user_vals;         // [nq][kCondMaxSlots] or NULL
+    const uint32_t* user_present;                // [nq] or NULL
+    uint64_t* out_rows;
+    unsigned long long* out_score;
+    uint8_t* out_source;
+    unsigned long long* out_planes64;
+    uint32_t* out_mask;
+    uint32_t* out_planes32;
+    uint32_t* out_count;
+    uint32_t nq, cap, n_f64, n_f32;
+};
+
+// Request q = blockIdx.x.
+__global__ __launch_bounds__(kCondChunk) void item_state_filter_kernel(CondProgram p, FilterArgs a) {
+    __shared__ uint32_t wcnt[2][kCondWaves];
+    const uint32_t q = blockIdx.x, tid = threadIdx.x, wave = tid / kWave, lane = tid & (kWave - 1);
+    const uint32_t cap = a.cap;
+    const size_t q0 = (size_t)q * cap, plane = (size_t)a.nq * cap;
+    const uint32_t n_valid = a.count ? min(a.count[q], cap) : cap;
+    CondUser u;
+    u.vals = a.user_vals ? a.user_vals + (size_t)q * kCondMaxSlots : nullptr;
+    u.present = a.user_present ? a.user_present[q] : 0u;
+    uint32_t run = 0;                                                // the entries kept so far: every lane counts along
+    for (uint32_t c0 = 0, it = 0; c0 < n_valid; c0 += kCondChunk, ++it) {
+        const uint32_t pos = c0 + tid;
+        bool keep = false;
+        if (pos < n_valid) {
+            const unsigned long long row = a.rows[q0 + pos];
+            if (row != kCondPad) {
+                CondItem item;
+                cond_load(p, row, &item);
+                keep = cond_rule(p, 0, item, u);
+            }
+        }
+        const unsigned long long m = __ballot(keep);
+        const uint32_t before = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+        uint32_t* wc = wcnt[it & 1u];
+        if (lane == 0) wc[wave] = (uint32_t)__popcll(m);
+        __syncthreads();
+        uint32_t below = 0, total = 0;
+#pragma unroll
+        for (uint32_t w = 0; w < kCondWaves; ++w) {
+            const uint32_t c = wc[w];
+            below += w < wave ? c : 0u;
+            total += c;
+        }
+        if (keep) {
+            const size_t src = q0 + pos, o = q0 + run + below + before;      // (run + below + before <= pos < cap)
+            a.out_rows[o] = a.rows[src];
+            a.out_score[o] = a.score[src];
+            if (a.out_source) a.out_source[o] = a.source[src];
+            if (a.out_mask) a.out_mask[o] = a.mask[src];
+            for (uint32_t f = 0; f < a.n_f64; ++f) a.out_planes64[f * plane + o] = a.planes64[f * plane + src];
+            for (uint32_t f = 0; f < a.n_f32; ++f) a.out_planes32[f * plane + o] = a.planes32[f * plane + src];
+        }
+        run += total;
+    }
+    for (uint32_t j = run + tid; j < cap; j += kCondChunk) {              // padding behind the count
+        const size_t o = q0 + j;
+        a.out_rows[o] = kCondPad;
+        a.out_score[o] = kCondNan;
+        if (a.out_source) a.out_source[o] = 0xFFu;
+        if (a.out_mask) a.out_mask[o] = 0u;
+        for (uint32_t f = 0; f < a.n_f64; ++f) a.out_planes64[f * plane + o] = kCondNan;
+        for (uint32_t f = 0; f < a.n_f32; ++f) a.out_planes32[f * plane + o] = 0u;
+    }
+    if (tid == 0) a.out_count[q] = run;
+}
+
+constexpr uint32_t kBoostThreads = 256;
+// Request q = blockIdx.y, positions blockIdx.x * 256 ...
+__global__ __launch_bounds__(kBoostThreads) void boost_scores_kernel(CondProgram p, const uint64_t* __restrict__ rows,
+                                                                     const unsigned long long* score, const uint32_t* __restrict__ count,
+                                                                     const unsigned long long* __restrict__ user_vals,
+                                                                     const uint32_t* __restrict__ user_present, uint32_t cap, uint32_t filter_all,
+                                                                     unsigned long long* out_score, uint8_t* __restrict__ out_rule) {      // (out_score may be score: a lane reads its entry, then writes it)
+    const uint32_t q = blockIdx.y, pos = blockIdx.x * kBoostThreads + threadIdx.x;
+    if (pos >= cap) return;
+    const size_t i = (size_t)q * cap + pos;
+    const uint32_t n_valid = count ? min(count[q], cap) : cap;
+    unsigned long long bits = score[i];
+    uint32_t last = 0xFFu;
+    const unsigned long long row = rows[i];
+    if (pos < n_valid && row != kCondPad) {
+        CondUser u;
+        u.vals = user_vals ? user_vals + (size_t)q * kCondMaxSlots : nullptr;
+        u.present = user_present ? user_present[q] : 0u;
+        CondItem item;
+        cond_load(p, row, &item);
+        double s = cond_bits_f64(bits);
+        last = cond_boost(p, filter_all != 0, item, u, &s);
+        memcpy(&bits, &s, 8);                                            // (moves only: an untouched score keeps its bits)
+    }
+    out_score[i] = bits;                                                 // padding entries keep their score bits
+    if (out_rule) out_rule[i] = (uint8_t)last;
+}
+
+}  // namespace
+}  // namespace pg
+
+// ---- the compiled object ------------------------------------------------------------------------------------------------------
+struct pg_cond {
+    bool boost = false;
+    std::vector<std::string> col_names;           // as declared
+    std::vector<int> col_dtypes;
+    std::vector<int> used;                        // referenced columns → declared index (<= kCondMaxCols)
+    std::vector<std::string> slot_names;          // user slots in order of first use
+    std::vector<uint8_t> slot_float;
+    std::vector<pg::CondTerm> terms;
+    std::vector<pg::CondRule> rules;
+    std::vector<long long> lists;
+    std::vector<pg::Instr> progs;
+    // the device table (lists, programs): uploaded at the first device call, owned until pg_cond_free
+    std::mutex table_mu;                          // the upload below: contexts on one device may share a set
+    int device = -1;
+    void* d_table = nullptr;
+    size_t progs_off = 0;
+};
+
+namespace pg {
+namespace {
+
+const char* const kCondOpNames[] = {"equal", "not_equal", "greater", "greaterThan", "less", "lessThan", "in", "not_in",
+                                    "is_null", "is_not_null", "bool", "contains", "not_contains", "expression"};
+
+struct CondCompiler {
+    pg_cond* c;
+    const pg_cond_col* cols;
+    uint32_t n_cols;
+    int refuse(int code, const char* fmt, ...) __attribute__((format(printf, 3, 4))) {
+        char buf[512];
+        va_list ap;
+        va_start(ap, fmt);
+        vsnprintf(buf, sizeof buf, fmt, ap);
+        va_end(ap);
+        set_error("pg_cond_compile: %s", buf);
+        return code;
+    }
+    // a column by name → its index among the referenced ones; need_int: the value is read as an integer
+    int column(const char* name, bool need_int, uint32_t rule, const char* what, uint8_t* out) {
+        uint32_t d = 0;
+        for (; d < n_cols; ++d)
+            if (!strcmp(cols[d].name, name)) break;
+        if (d == n_cols) return refuse(PG_ERR_INVALID, "rule %u: %s \"%s\" is not among the declared columns", rule, what, name);
+        if (need_int && cols[d].dtype != PG_F_I32 && cols[d].dtype != PG_F_I64)
+            return refuse(PG_ERR_UNSUPPORTED, "rule %u: %s \"%s\" is a float column read by an int / int64 / string term (utils.ToInt has no "
+                          "float32 case and truncates float64): not served", rule, what, name);
+        size_t k = 0;
+        for (; k < c->used.size(); ++k)
+            if (c->used[k] == (int)d) break;
+        if (k == c->used.size()) {
+            if (k == kCondMaxCols) return refuse(PG_ERR_UNSUPPORTED, "more than %u referenced columns (\"%s\")", kCondMaxCols, name);
+            c->used.push_back((int)d);
+        }
+        *out = (uint8_t)k;
+        return PG_OK;
+    }
+    // kind: 0 read as an integer, 1 read as a float, 2 only its presence is read
+    int slot(const char* name, uint8_t kind, uint32_t rule, uint8_t* out) {
+        size_t k = 0;
+        for (; k < c->slot_names.size(); ++k)
+            if (c->slot_names[k] == name) break;
+        if (k == c->slot_names.size()) {
+            if (k == kCondMaxSlots) return refuse(PG_ERR_UNSUPPORTED, "more than %u user slots (\"%s\")", kCondMaxSlots, name);
+            c->slot_names.push_back(name);
+            c->slot_float.push_back(kind);
+        } else if (c->slot_float[k] == 2) {
+            c->slot_float[k] = kind;
+        } else if (kind != 2 && c->slot_float[k] != kind) {
+            return refuse(PG_ERR_INVALID, "rule %u: user property \"%s\" is read both as a float and as an integer: a slot holds one 8-byte value", rule, name);
+        }
+        *out = (uint8_t)k;
+        return PG_OK;
+    }
+    int term(const pg_cond_term& s, uint32_t rule, uint32_t idx, bool in_bool) {
+        int rc;
+        if (s.op < 0 || s.op > PG_COND_EXPRESSION) return refuse(PG_ERR_INVALID, "rule %u term %u: unknown operator %d", rule, idx, s.op);
+        const char* opn = kCondOpNames[s.op];
+        if (s.op == PG_COND_CONTAINS || s.op == PG_COND_NOT_CONTAINS)
+            return refuse(PG_ERR_UNSUPPORTED, "rule %u term %u: operator \"%s\" (list-valued properties) is not served", rule, idx, opn);
+        if (s.op == PG_COND_EXPRESSION)
+            return refuse(PG_ERR_UNSUPPORTED, "rule %u term %u: operator \"expression\" (expr-lang) is not served", rule, idx);
+        if (s.depth > 1 || (s.depth == 1 && s.op == PG_COND_BOOL))
+            return refuse(PG_ERR_UNSUPPORTED, "rule %u term %u: operator \"%s\" nested deeper than one bool is not served", rule, idx, opn);
+        if (s.depth == 1 && !in_bool) return refuse(PG_ERR_INVALID, "rule %u term %u: a child term (\"%s\") without a bool in front", rule, idx, opn);
+        CondTerm t{};
+        t.op = (uint8_t)s.op;
+        t.depth = (uint8_t)s.depth;
+        if (s.op == PG_COND_BOOL) {
+            t.is_and = s.bool_and ? 1 : 0;
+            c->terms.push_back(t);
+            return PG_OK;
+        }
+        const char* dom = s.domain && s.domain[0] ? s.domain : "item";
+        if (strcmp(dom, "item") && strcmp(dom, "user"))
+            return refuse(PG_ERR_UNSUPPORTED, "rule %u term %u: domain \"%s\" (EvaluateByDomain serves item and user, filter_op.go:533-535)", rule, idx, dom);
+        if (!s.name || !s.name[0]) return refuse(PG_ERR_INVALID, "rule %u term %u: operator \"%s\" without a property name", rule, idx, opn);
+        t.user_left = !strcmp(dom, "user");
+        const bool nullish = s.op == PG_COND_IS_NULL || s.op == PG_COND_IS_NOT_NULL;
+        if (!nullish && (s.type < 0 || s.type > PG_COND_STRING)) return refuse(PG_ERR_INVALID, "rule %u term %u (\"%s\"): unknown type %d", rule, idx, s.name, s.type);
+        t.type = nullish ? (uint8_t)PG_COND_INT : (uint8_t)s.type;
+        const bool ordered = s.op >= PG_COND_GREATER && s.op <= PG_COND_LESS_THAN;
+        const bool listed = s.op == PG_COND_IN || s.op == PG_COND_NOT_IN;
+        if (ordered && s.type == PG_COND_STRING)
+            return refuse(PG_ERR_UNSUPPORTED, "rule %u term %u: \"%s\" on the string property \"%s\": ordered comparisons of strings are not served", rule, idx, opn, s.name);
+        // does this term ever read a value?  (equal / not_equal with float and in / not_in with int64 / float answer from the
+        // presence alone: their switches do not list the type)
+        const bool reads = !nullish && !((s.op <= PG_COND_NOT_EQUAL && s.type == PG_COND_FLOAT) || (listed && (s.type == PG_COND_FLOAT || s.type == PG_COND_INT64)));
+        const bool as_float = s.type == PG_COND_FLOAT;
+        if (c->boost && !t.user_left && !strcmp(s.name, "score"))
+            return refuse(PG_ERR_UNSUPPORTED, "rule %u term %u: an item term named \"score\" in a boost rule set (the reference's clone gains a "
+                          "score key in the middle of the walk, boost_score_sort.go:81)", rule, idx);
+        if (t.user_left) {
+            if ((rc = slot(s.name, !reads ? 2 : as_float ? 1 : 0, rule, &t.left))) return rc;
+        } else if (reads) {
+            if ((rc = column(s.name, !as_float, rule, "property", &t.left))) return rc;
+        } else {
+            uint8_t dummy;                                     // named, never read: it must still exist
+            if ((rc = column(s.name, false, rule, "property", &dummy))) return rc;
+            t.left = dummy;
+        }
+        if (nullish) {
+            c->terms.push_back(t);
+            return PG_OK;
+        }
+        if (listed) {
+            if (s.rhs != PG_COND_RHS_CONST)
+                return refuse(PG_ERR_UNSUPPORTED, "rule %u term %u: \"%s\" on \"%s\" against the list-valued property %s%s is not served", rule, idx, opn,
+                              s.name, s.rhs == PG_COND_RHS_ITEM ? "item." : "user.", s.rhs_name ? s.rhs_name : "");
+            if (s.n_list > kCondMaxList) return refuse(PG_ERR_UNSUPPORTED, "rule %u term %u: \"%s\" on \"%s\" with %u values (at most %u)", rule, idx, opn, s.name, s.n_list, kCondMaxList);
+            if (s.n_list && !s.list) return refuse(PG_ERR_INVALID, "rule %u term %u: \"%s\" on \"%s\": NULL list", rule, idx, opn, s.name);
+            t.list_off = (uint16_t)c->lists.size();
+            t.list_n = (uint16_t)s.n_list;
+            c->lists.insert(c->lists.end(), s.list, s.list + s.n_list);
+            std::sort(c->lists.begin() + t.list_off, c->lists.end());
+            c->terms.push_back(t);
+            return PG_OK;
+        }
+        if (s.rhs == PG_COND_RHS_USER_LIST)
+            return refuse(PG_ERR_UNSUPPORTED, "rule %u term %u: the list-valued right-hand side user.%s is not served", rule, idx, s.rhs_name ? s.rhs_name : "");
+        if (s.rhs < 0 || s.rhs > PG_COND_RHS_ITEM) return refuse(PG_ERR_INVALID, "rule %u term %u (\"%s\"): unknown right-hand side kind %d", rule, idx, s.name, s.rhs);
+        t.rhs = (uint8_t)s.rhs;
+        if (s.rhs == PG_COND_RHS_CONST) {
+            if (as_float) t.c.f = s.f; else t.c.i = s.i;
+        } else {
+            if (!s.rhs_name || !s.rhs_name[0]) return refuse(PG_ERR_INVALID, "rule %u term %u (\"%s\"): the right-hand side has no name", rule, idx, s.name);
+            if (s.rhs == PG_COND_RHS_USER) {
+                if ((rc = slot(s.rhs_name, !reads ? 2 : as_float ? 1 : 0, rule, &t.rhs_idx))) return rc;
+            } else {
+                if (c->boost && !strcmp(s.rhs_name, "score"))
+                    return refuse(PG_ERR_UNSUPPORTED, "rule %u term %u: item.score in a boost rule set (the reference's clone gains a score key in "
+                                  "the middle of the walk, boost_score_sort.go:81)", rule, idx);
+                if (reads) {
+                    if ((rc = column(s.rhs_name, !as_float, rule, "right-hand side item.", &t.rhs_idx))) return rc;
+                } else {
+                    uint8_t dummy;
+                    if ((rc = column(s.rhs_name, false, rule, "right-hand side item.", &dummy))) return rc;
+                    t.rhs_idx = dummy;
+                }
+            }
+        }
+        c->terms.push_back(t);
+        return PG_OK;
+    }
+};
+
+int cond_compile(const pg_cond_rule* rules, uint32_t n_rules, const pg_cond_col* cols, uint32_t n_cols, uint32_t boost, pg_cond* c) {
+    CondCompiler cc{c, cols, n_cols};
+    if (!rules || n_rules < 1) return cc.refuse(PG_ERR_INVALID, "no rules");
+    if (n_rules > kCondMaxRules) return cc.refuse(PG_ERR_UNSUPPORTED, "%u rules (at most %u)", n_rules, kCondMaxRules);
+    if (n_cols && !cols) return cc.refuse(PG_ERR_INVALID, "NULL column declarations");
+    for (uint32_t d = 0; d < n_cols; ++d) {
+        if (!cols[d].name || !cols[d].name[0]) return cc.refuse(PG_ERR_INVALID, "declared column %u has no name", d);
+        if (cols[d].dtype < PG_F_I32 || cols[d].dtype > PG_F_F64) return cc.refuse(PG_ERR_INVALID, "declared column \"%s\" has unknown dtype %d", cols[d].name, cols[d].dtype);
+        for (uint32_t e = 0; e < d; ++e)
+            if (!strcmp(cols[e].name, cols[d].name)) return cc.refuse(PG_ERR_INVALID, "column \"%s\" is declared twice", cols[d].name);
+        c->col_names.push_back(cols[d].name);
+        c->col_dtypes.push_back(cols[d].dtype);
+    }
+    c->boost = boost != 0;
+    int rc;
+    for (uint32_t r = 0; r < n_rules; ++r) {
+        const pg_cond_rule& ru = rules[r];
+        if (ru.n_terms > kCondMaxTerms) return cc.refuse(PG_ERR_UNSUPPORTED, "rule %u has %u operators, a bool's children counted (at most %u)", r, ru.n_terms, kCondMaxTerms);
+        if (ru.n_terms && !ru.terms) return cc.refuse(PG_ERR_INVALID, "rule %u: NULL terms", r);
+        CondRule out{};
+        out.term_off = (uint8_t)c->terms.size();
+        out.n_terms = (uint8_t)ru.n_terms;
+        bool in_bool = false;
+        for (uint32_t i = 0; i < ru.n_terms; ++i) {
+            if (ru.terms[i].depth == 0) in_bool = false;
+            if ((rc = cc.term(ru.terms[i], r, i, in_bool))) return rc;
+            if (ru.terms[i].op == PG_COND_BOOL) in_bool = true;
+        }
+        if (c->boost) {
+            // an empty Expression leaves evaluableExpression nil and a matching condition dereferences it (boost_score_sort.go:22-29,82)
+            if (!ru.expression || !ru.expression[0]) return cc.refuse(PG_ERR_INVALID, "rule %u: a boost rule without an expression (the reference dereferences nil when its condition matches)", r);
+            pg_expr* e = nullptr;
+            if ((rc = pg_expr_compile_govaluate(ru.expression, &e))) return rc;
+            std::unique_ptr<pg_expr> hold(e);
+            if (e->prog.size() > kCondMaxExprOps || (uint32_t)e->max_depth > kCondMaxExprDepth)
+                return cc.refuse(PG_ERR_UNSUPPORTED, "rule %u: expression '%.200s' has %zu operations at depth %d (at most %u at depth %u)", r, ru.expression,
+                                 e->prog.size(), e->max_depth, kCondMaxExprOps, kCondMaxExprDepth);
+            out.prog_off = (uint16_t)c->progs.size();
+            out.prog_n = (uint16_t)e->prog.size();
+            for (Instr in : e->prog) {
+                if (in.op == OP_VAR) {
+                    const std::string& name = e->vars[in.arg];
+                    if (name == "score") {
+                        in.arg = kVarScore;
+                    } else {
+                        uint8_t k;
+                        if ((rc = cc.column(name.c_str(), false, r, "expression variable", &k))) return rc;
+                        in.arg = k;
+                    }
+                }
+                c->progs.push_back(in);
+            }
+        } else if (ru.expression && ru.expression[0]) {
+            return cc.refuse(PG_ERR_INVALID, "rule %u carries an expression but the set is not a boost rule set", r);
+        }
+        c->rules.push_back(out);
+    }
+    return PG_OK;
+}
+
+// the kernel argument / the host statement's program; cols_base[k]: the base of referenced column k
+void cond_program(const pg_cond* c, const void* const* declared_base, const long long* lists, const Instr* progs, uint64_t store_rows, CondProgram* p) {
+    memset(p, 0, sizeof *p);
+    for (size_t k = 0; k < c->used.size(); ++k) p->cols[k] = CondCol{declared_base[c->used[k]], c->col_dtypes[(size_t)c->used[k]], 0};
+    std::copy(c->terms.begin(), c->terms.end(), p->terms);
+    std::copy(c->rules.begin(), c->rules.end(), p->rules);
+    p->lists = lists;
+    p->progs = progs;
+    p->n_used = (uint32_t)c->used.size();
+    p->n_rules = (uint32_t)c->rules.size();
+    p->store_rows = store_rows;
+}
+
+// host statement: the candidate's values from candidate-aligned arrays
+void cond_host_item(const pg_cond* c, const void* const* cols, const uint8_t* item_in, uint32_t i, CondItem* it) {
+    it->item_in = item_in ? item_in[i] != 0 : true;
+    for (uint32_t k = 0; k < kCondMaxCols; ++k) {
+        unsigned long long b = 0;
+        if (k < c->used.size() && it->item_in) {
+            const int d = c->used[k], dt = c->col_dtypes[(size_t)d];
+            if (dt == PG_F_I32 || dt == PG_F_F32) b = ((const uint32_t*)cols[d])[i];
+            else b = ((const unsigned long long*)cols[d])[i];
+        }
+        it->raw[k] = b;
+    }
+}
+
+int cond_host_check(const pg_cond* c, const void* const* cols, const uint64_t* user_vals, const char* who) {
+    for (int d : c->used)
+        if (!cols || !cols[d]) {
+            set_error("%s: the values of column \"%s\" are missing", who, c->col_names[(size_t)d].c_str());
+            return PG_ERR_INVALID;
+        }
+    if (!c->slot_names.empty() && !user_vals) {
+        set_error("%s: the set reads user property \"%s\" but user_vals is NULL", who, c->slot_names[0].c_str());
+        return PG_ERR_INVALID;
+    }
+    return PG_OK;
+}
+
+// binds the set to a store by name and makes sure its table is on the context's device; caller holds ctx->mu
+int cond_bind_locked(pg_ctx* ctx, pg_cond* c, const pg_features* fs, const char* who, CondProgram* p) {
+    std::vector<const void*> declared(c->col_names.size(), nullptr);
+    for (int d : c->used) {
+        const pg_features::Column* col = nullptr;
+        for (const auto& x : fs->cols)
+            if (x.name == c->col_names[(size_t)d]) { col = &x; break; }
+        if (!col || !col->d) {
+            set_error("%s: column \"%s\" is not a column of the feature store", who, c->col_names[(size_t)d].c_str());
+            return PG_ERR_INVALID;
+        }
+        if (col->dtype != c->col_dtypes[(size_t)d]) {
+            set_error("%s: column \"%s\" has dtype %d in the feature store, the set was compiled for dtype %d", who, col->name.c_str(), col->dtype,
+                      c->col_dtypes[(size_t)d]);
+            return PG_ERR_INVALID;
+        }
+        declared[(size_t)d] = col->d;
+    }
+    std::lock_guard<std::mutex> table_guard(c->table_mu);
+    if (c->device >= 0 && c->device != ctx->device) {
+        set_error("%s: the set's table lives on device %d, the context on device %d", who, c->device, ctx->device);
+        return PG_ERR_INVALID;
+    }
+    if (c->device < 0) {
+        // once per set: the in lists and the expression programs (the only synchronous step; every later call only launches)
+        const size_t lb = (c->lists.size() * 8 + 255) & ~(size_t)255, pb = c->progs.size() * sizeof(Instr);
+        void* d = nullptr;
+        PG_HIP(hipMalloc(&d, lb + pb + 256));
+        hipError_t e = hipSuccess;
+        if (!c->lists.empty()) e = hipMemcpy(d, c->lists.data(), c->lists.size() * 8, hipMemcpyHostToDevice);
+        if (e == hipSuccess && pb) e = hipMemcpy((char*)d + lb, c->progs.data(), pb, hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            hipFree(d);
+            set_error("%s: uploading the set's table failed: %s", who, hipGetErrorString(e));
+            return PG_ERR_DEVICE;
+        }
+        c->d_table = d;
+        c->progs_off = lb;
+        c->device = ctx->device;
+    }
+    cond_program(c, declared.data(), (const long long*)c->d_table, (const Instr*)((const char*)c->d_table + c->progs_off), fs->rows, p);
+    return PG_OK;
+}
+
+int cond_check_shape(uint32_t nq, uint32_t cap, const char* who) {
+    PG_REQUIRE(nq >= 1 && nq <= (uint32_t)kMaxQueries, "%s: nq=%u must be in [1,%d]", who, nq, kMaxQueries);
+    if (cap < 1 || cap > kCondMaxCap) {
+        set_error("%s: cap=%u unsupported (1..%u)", who, cap, kCondMaxCap);
+        return PG_ERR_UNSUPPORTED;
+    }
+    return PG_OK;
+}
+
+inline size_t cond_al(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// [a, a + an) and [b, b + bn) share a byte
+inline bool cond_overlap(const void* a, size_t an, const void* b, size_t bn) {
+    if (!a || !b) return false;
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + bn && y < x + an;
+}
+
+int item_state_filter_locked(pg_ctx* ctx, pg_cond* c, const pg_features* fs, uint32_t nq, uint32_t cap, const uint64_t* d_rows, const double* d_score,
+                             const uint8_t* d_source, const uint32_t* d_count, const double* d_planes_f64, uint32_t n_f64,
+                             const uint32_t* d_source_mask, const float* d_planes_f32, uint32_t n_f32, const uint64_t* d_user_vals,
+                             const uint32_t* d_user_present, uint64_t* d_out_rows, double* d_out_score, uint8_t* d_out_source,
+                             double* d_out_planes_f64, uint32_t* d_out_source_mask, float* d_out_planes_f32, uint32_t* d_out_count) {
+    CondProgram p;
+    int rc;
+    if ((rc = cond_bind_locked(ctx, c, fs, "pg_item_state_filter_dev", &p))) return rc;
+    FilterArgs a{};
+    a.rows = d_rows;
+    a.score = reinterpret_cast<const unsigned long long*>(d_score);
+    a.source = d_source;
+    a.count = d_count;
+    a.planes64 = reinterpret_cast<const unsigned long long*>(d_planes_f64);
+    a.mask = d_source_mask;
+    a.planes32 = reinterpret_cast<const uint32_t*>(d_planes_f32);
+    a.user_vals = reinterpret_cast<const unsigned long long*>(d_user_vals);
+    a.user_present = d_user_present;
+    a.out_rows = d_out_rows;
+    a.out_score = reinterpret_cast<unsigned long long*>(d_out_score);
+    a.out_source = d_source ? d_out_source : nullptr;
+    a.out_planes64 = reinterpret_cast<unsigned long long*>(d_out_planes_f64);
+    a.out_mask = d_source_mask ? d_out_source_mask : nullptr;
+    a.out_planes32 = reinterpret_cast<uint32_t*>(d_out_planes_f32);
+    a.out_count = d_out_count;
+    a.nq = nq;
+    a.cap = cap;
+    a.n_f64 = d_planes_f64 ? n_f64 : 0;
+    a.n_f32 = d_planes_f32 ? n_f32 : 0;
+    item_state_filter_kernel<<<nq, kCondChunk, 0, ctx->stream>>>(p, a);
+    PG_HIP(hipGetLastError());
+    return PG_OK;
+}
+
+int boost_scores_locked(pg_ctx* ctx, pg_cond* c, const pg_features* fs, uint32_t filter_all, uint32_t nq, uint32_t cap, const uint64_t* d_rows,
+                        const double* d_score, const uint32_t* d_count, const uint64_t* d_user_vals, const uint32_t* d_user_present,
+                        double* d_out_score, uint8_t* d_out_rule) {
+    CondProgram p;
+    int rc;
+    if ((rc = cond_bind_locked(ctx, c, fs, "pg_boost_scores_dev", &p))) return rc;
+    boost_scores_kernel<<<dim3((cap + kBoostThreads - 1) / kBoostThreads, nq), kBoostThreads, 0, ctx->stream>>>(
+        p, d_rows, reinterpret_cast<const unsigned long long*>(d_score), d_count, reinterpret_cast<const unsigned long long*>(d_user_vals),
+        d_user_present, cap, filter_all, reinterpret_cast<unsigned long long*>(d_out_score), d_out_rule);
+    PG_HIP(hipGetLastError());
+    return PG_OK;
+}
+
+}  // namespace
+}  // namespace pg
+
+extern "C" {
+
+int pg_cond_compile(const pg_cond_rule* rules, uint32_t n_rules, const pg_cond_col* cols, uint32_t n_cols, uint32_t boost, pg_cond** out) {
+    PG_REQUIRE(out, "pg_cond_compile: NULL argument");
+    if (n_cols > 256) {
+        pg::set_error("pg_cond_compile: %u declared columns (at most 256)", n_cols);
+        return PG_ERR_UNSUPPORTED;
+    }
+    std::unique_ptr<pg_cond> c(new pg_cond());
+    const int rc = pg::cond_compile(rules, n_rules, cols, n_cols, boost, c.get());
+    if (rc) return rc;
+    *out = c.release();
+    return PG_OK;
+}
+
+int pg_cond_free(pg_cond* c) {
+    if (!c) return PG_OK;
+    if (c->d_table) {
+        int cur = 0;
+        hipGetDevice(&cur);
+        hipSetDevice(c->device);
+        hipDeviceSynchronize();                     // (a launch that reads the table may still be in flight)
+        hipFree(c->d_table);
+        hipSetDevice(cur);
+    }
+    delete c;
+    return PG_OK;
+}
+
+int pg_cond_num_rules(const pg_cond* c) { return c ? (int)c->rules.size() : 0; }
+int pg_cond_num_user_slots(const pg_cond* c) { return c ? (int)c->slot_names.size() : 0; }
+const char* pg_cond_user_slot_name(const pg_cond* c, int i) { return c && i >= 0 && i < (int)c->slot_names.size() ? c->slot_names[(size_t)i].c_str() : ""; }
+int pg_cond_user_slot_is_float(const pg_cond* c, int i) { return c && i >= 0 && i < (int)c->slot_float.size() && c->slot_float[(size_t)i] == 1 ? 1 : 0; }
+
+int pg_cond_match_host(const pg_cond* c, uint32_t rule, uint32_t n, const uint8_t* item_in, const void* const* cols, const uint64_t* user_vals,
+                       uint32_t user_present, uint8_t* out_match) {
+    PG_REQUIRE(c && (n == 0 || out_match), "pg_cond_match_host: NULL argument");
+    PG_REQUIRE(rule < c->rules.size(), "pg_cond_match_host: rule %u of %zu", rule, c->rules.size());
+    int rc;
+    if (n && (rc = pg::cond_host_check(c, cols, user_vals, "pg_cond_match_host"))) return rc;
+    pg::CondProgram p;
+    std::vector<const void*> none(c->col_names.size(), nullptr);
+    pg::cond_program(c, none.data(), c->lists.data(), c->progs.data(), 0, &p);
+    const pg::CondUser u{reinterpret_cast<const unsigned long long*>(user_vals), user_present};
+    for (uint32_t i = 0; i < n; ++i) {
+        pg::CondItem it;
+        pg::cond_host_item(c, cols, item_in, i, &it);
+        out_match[i] = pg::cond_rule(p, rule, it, u) ? 1 : 0;
+    }
+    return PG_OK;
+}
+
+int pg_boost_scores_host(const pg_cond* c, uint32_t filter_all, uint32_t n, const uint8_t* item_in, const void* const* cols,
+                         const uint64_t* user_vals, uint32_t user_present, const double* score, double* out_score, uint8_t* out_rule) {
+    PG_REQUIRE(c && (n == 0 || (score && out_score)), "pg_boost_scores_host: NULL argument");
+    PG_REQUIRE(c->boost, "pg_boost_scores_host: the set was not compiled as a boost rule set");
+    int rc;
+    if (n && (rc = pg::cond_host_check(c, cols, user_vals, "pg_boost_scores_host"))) return rc;
+    pg::CondProgram p;
+    std::vector<const void*> none(c->col_names.size(), nullptr);
+    pg::cond_program(c, none.data(), c->lists.data(), c->progs.data(), 0, &p);
+    const pg::CondUser u{reinterpret_cast<const unsigned long long*>(user_vals), user_present};
+    for (uint32_t i = 0; i < n; ++i) {
+        pg::CondItem it;
+        pg::cond_host_item(c, cols, item_in, i, &it);
+        double s = score[i];
+        const uint32_t last = pg::cond_boost(p, filter_all != 0, it, u, &s);
+        memcpy(&out_score[i], &s, 8);                    // (moves only: an untouched score keeps its bits)
+        if (out_rule) out_rule[i] = (uint8_t)last;
+    }
+    return PG_OK;
+}
+
+int pg_item_state_filter_dev(pg_ctx* ctx, pg_cond* c, const pg_features* fs, uint32_t nq, uint32_t cap, const uint64_t* d_rows,
+                             const double* d_score, const uint8_t* d_source, const uint32_t* d_count, const double* d_planes_f64,
+                             uint32_t n_f64, const uint32_t* d_source_mask, const float* d_planes_f32, uint32_t n_f32,
+                             const uint64_t* d_user_vals, const uint32_t* d_user_present, uint64_t* d_out_rows, double* d_out_score,
+                             uint8_t* d_out_source, double* d_out_planes_f64, uint32_t* d_out_source_mask, float* d_out_planes_f32,
+                             uint32_t* d_out_count) {
+    PG_REQUIRE(ctx && c && fs && d_rows && d_score && d_out_rows && d_out_score && d_out_count, "pg_item_state_filter_dev: NULL argument");
+    PG_REQUIRE(!c->boost, "pg_item_state_filter_dev: the set was compiled as a boost rule set");
+    int rc;
+    if ((rc = pg::cond_check_shape(nq, cap, "pg_item_state_filter_dev"))) return rc;
+    PG_REQUIRE(c->slot_names.empty() || (d_user_vals && d_user_present), "pg_item_state_filter_dev: the set reads user properties: d_user_vals and d_user_present are needed");
+    PG_REQUIRE(!d_source == !d_out_source && !d_source_mask == !d_out_source_mask,
+               "pg_item_state_filter_dev: d_source / d_source_mask and their outputs come in pairs");
+    PG_REQUIRE(!d_planes_f64 == !d_out_planes_f64 && !d_planes_f32 == !d_out_planes_f32,
+               "pg_item_state_filter_dev: a carried plane set and its output come in pairs");
+    PG_REQUIRE((!d_planes_f64 || (n_f64 >= 1 && n_f64 <= pg::kCondMaxPlanes)) && (!d_planes_f32 || (n_f32 >= 1 && n_f32 <= pg::kCondMaxPlanes)),
+               "pg_item_state_filter_dev: a carried plane set holds 1..%u planes", pg::kCondMaxPlanes);
+    const size_t e = (size_t)nq * cap;
+    PG_REQUIRE(!pg::cond_overlap(d_rows, e * 8, d_out_rows, e * 8) && !pg::cond_overlap(d_score, e * 8, d_out_score, e * 8) &&
+                   !pg::cond_overlap(d_source, e, d_out_source, e) && !pg::cond_overlap(d_source_mask, e * 4, d_out_source_mask, e * 4) &&
+                   !pg::cond_overlap(d_planes_f64, e * 8 * n_f64, d_out_planes_f64, e * 8 * n_f64) &&
+                   !pg::cond_overlap(d_planes_f32, e * 4 * n_f32, d_out_planes_f32, e * 4 * n_f32),
+               "pg_item_state_filter_dev: an output overlaps its input");
+    std::lock_guard<std::mutex> g(ctx->mu);
+    PG_HIP(hipSetDevice(ctx->device));
+    return pg::item_state_filter_locked(ctx, c, fs, nq, cap, d_rows, d_score, d_source, d_count, d_planes_f64, n_f64, d_source_mask, d_planes_f32,
+                                        n_f32, d_user_vals, d_user_present, d_out_rows, d_out_score, d_out_source, d_out_planes_f64,
+                                        d_out_source_mask, d_out_planes_f32, d_out_count);
+}
+
+int pg_boost_scores_dev(pg_ctx* ctx, pg_cond* c, const pg_features* fs, uint32_t filter_all, uint32_t nq, uint32_t cap, const uint64_t* d_rows,
+                        const double* d_score, const uint32_t* d_count, const uint64_t* d_user_vals, const uint32_t* d_user_present,
+                        double* d_out_score, uint8_t* d_out_rule) {
+    PG_REQUIRE(ctx && c && fs && d_rows && d_score && d_out_score, "pg_boost_scores_dev: NULL argument");
+    PG_REQUIRE(c->boost, "pg_boost_scores_dev: the set was not compiled as a boost rule set");
+    int rc;
+    if ((rc = pg::cond_check_shape(nq, cap, "pg_boost_scores_dev"))) return rc;
+    PG_REQUIRE(c->slot_names.empty() || (d_user_vals && d_user_present), "pg_boost_scores_dev: the set reads user properties: d_user_vals and d_user_present are needed");
+    std::lock_guard<std::mutex> g(ctx->mu);
+    PG_HIP(hipSetDevice(ctx->device));
+    return pg::boost_scores_locked(ctx, c, fs, filter_all, nq, cap, d_rows, d_score, d_count, d_user_vals, d_user_present, d_out_score, d_out_rule);
+}
+
+// ---- one request on host arrays: upload, run, download, synchronise --------------------------------------------------------
+int pg_item_state_filter(pg_ctx* ctx, pg_cond* c, const pg_features* fs, uint32_t n, const uint64_t* rows, const double* score, const uint8_t* source,
+                         const uint64_t* user_vals, uint32_t user_present, uint64_t* out_rows, double* out_score, uint8_t* out_source,
+                         uint32_t* out_count) {
+    PG_REQUIRE(ctx && c && fs && out_count && (n == 0 || (rows && score && out_rows && out_score)), "pg_item_state_filter: NULL argument");
+    PG_REQUIRE(!c->boost, "pg_item_state_filter: the set was compiled as a boost rule set");
+    PG_REQUIRE(!source == !out_source, "pg_item_state_filter: source and out_source come in pairs");
+    PG_REQUIRE(c->slot_names.empty() || user_vals, "pg_item_state_filter: the set reads user properties: user_vals is needed");
+    int rc;
+    if (n == 0) {                                    // an empty request: an empty answer
+        *out_count = 0;
+        return PG_OK;
+    }
+    if ((rc = pg::cond_check_shape(1, n, "pg_item_state_filter"))) return rc;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    PG_HIP(hipSetDevice(ctx->device));
+    const size_t b8 = pg::cond_al((size_t)n * 8), b1 = pg::cond_al(n);
+    void* buf;
+    if ((rc = pg::scratch_reserve(ctx, 25, 4 * b8 + 2 * b1 + 3 * 256, &buf))) return rc;
+    char* at = (char*)buf;
+    uint64_t* d_rows = (uint64_t*)at; at += b8;
+    double* d_score = (double*)at; at += b8;
+    uint64_t* d_orows = (uint64_t*)at; at += b8;
+    double* d_oscore = (double*)at; at += b8;
+    uint8_t* d_src = (uint8_t*)at; at += b1;
+    uint8_t* d_osrc = (uint8_t*)at; at += b1;
+    uint64_t* d_uv = (uint64_t*)at; at += 256;
+    uint32_t* d_up = (uint32_t*)at; at += 256;
+    uint32_t* d_cnt = (uint32_t*)at;
+    uint64_t uv[pg::kCondMaxSlots] = {0};
+    if (user_vals) memcpy(uv, user_vals, c->slot_names.size() * 8);
+    PG_HIP(hipMemcpyAsync(d_rows, rows, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+    PG_HIP(hipMemcpyAsync(d_score, score, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (source) PG_HIP(hipMemcpyAsync(d_src, source, n, hipMemcpyHostToDevice, ctx->stream));
+    PG_HIP(hipMemcpyAsync(d_uv, uv, sizeof uv, hipMemcpyHostToDevice, ctx->stream));
+    PG_HIP(hipMemcpyAsync(d_up, &user_present, 4, hipMemcpyHostToDevice, ctx->stream));
+    PG_HIP(hipStreamSynchronize(ctx->stream));       // (uv and user_present are this frame's)
+    if ((rc = pg::item_state_filter_locked(ctx, c, fs, 1, n, d_rows, d_score, source ? d_src : nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, d_uv,
+                                           d_up, d_orows, d_oscore, source ? d_osrc : nullptr, nullptr, nullptr, nullptr, d_cnt)))
+        return rc;
+    PG_HIP(hipMemcpyAsync(out_rows, d_orows, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
+    PG_HIP(hipMemcpyAsync(out_score, d_oscore, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (source) PG_HIP(hipMemcpyAsync(out_source, d_osrc, n, hipMemcpyDeviceToHost, ctx->stream));
+    PG_HIP(hipMemcpyAsync(out_count, d_cnt, 4, hipMemcpyDeviceToHost, ctx->stream));
+    PG_HIP(hipStreamSynchronize(ctx->stream));
+    return PG_OK;
+}
+
+int pg_boost_scores(pg_ctx* ctx, pg_cond* c, uint32_t filter_all, uint32_t n, const uint8_t* item_in, const void* const* cols,
+                    const uint64_t* user_vals, uint32_t user_present, const double* score, double* out_score, uint8_t* out_rule) {
+    PG_REQUIRE(ctx && c && (n == 0 || (score && out_score)), "pg_boost_scores: NULL argument");
+    PG_REQUIRE(c->boost, "pg_boost_scores: the set was not compiled as a boost rule set");
+    int rc;
+    if (n == 0) return PG_OK;                        // an empty request: nothing to rewrite
+    if ((rc = pg::cond_check_shape(1, n, "pg_boost_scores"))) return rc;
+    if ((rc = pg::cond_host_check(c, cols, user_vals, "pg_boost_scores"))) return rc;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    PG_HIP(hipSetDevice(ctx->device));
+    // the candidates' values become a store of n rows in scratch: candidate i reads row i, one outside the store row n
+    const size_t b8 = pg::cond_al((size_t)n * 8), b1 = pg::cond_al(n), nu = c->used.size();
+    void* buf;
+    if ((rc = pg::scratch_reserve(ctx, 25, (3 + nu) * b8 + b1 + 2 * 256, &buf))) return rc;
+    char* at = (char*)buf;
+    uint64_t* d_rows = (uint64_t*)at; at += b8;
+    double* d_score = (double*)at; at += b8;
+    double* d_oscore = (double*)at; at += b8;
+    uint8_t* d_rule = (uint8_t*)at; at += b1;
+    uint64_t* d_uv = (uint64_t*)at; at += 256;
+    uint32_t* d_up = (uint32_t*)at; at += 256;
+    std::vector<uint64_t> rows(n);
+    for (uint32_t i = 0; i < n; ++i) rows[i] = !item_in || item_in[i] ? i : n;
+    uint64_t uv[pg::kCondMaxSlots] = {0};
+    if (user_vals) memcpy(uv, user_vals, c->slot_names.size() * 8);
+    pg_features tmp;                                  // (never owns: the columns point into scratch)
+    tmp.rows = n;
+    for (size_t k = 0; k < nu; ++k) {
+        const int d = c->used[k], dt = c->col_dtypes[(size_t)d];
+        const size_t es = dt == PG_F_I32 || dt == PG_F_F32 ? 4 : 8;
+        PG_HIP(hipMemcpyAsync(at, cols[d], (size_t)n * es, hipMemcpyHostToDevice, ctx->stream));
+        pg_features::Column col;
+        col.name = c->col_names[(size_t)d];
+        col.dtype = dt;
+        col.d = at;
+        tmp.cols.push_back(col);
+        at += b8;
+    }
+    PG_HIP(hipMemcpyAsync(d_rows, rows.data(), (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+    PG_HIP(hipMemcpyAsync(d_score, score, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+    PG_HIP(hipMemcpyAsync(d_uv, uv, sizeof uv, hipMemcpyHostToDevice, ctx->stream));
+    PG_HIP(hipMemcpyAsync(d_up, &user_present, 4, hipMemcpyHostToDevice, ctx->stream));
+    PG_HIP(hipStreamSynchronize(ctx->stream));       // (rows, uv and user_present are this frame's)
+    if ((rc = pg::boost_scores_locked(ctx, c, &tmp, filter_all, 1, n, d_rows, d_score, nullptr, d_uv, d_up, d_oscore, d_rule))) return rc;
+    PG_HIP(hipMemcpyAsync(out_score, d_oscore, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (out_rule) PG_HIP(hipMemcpyAsync(out_rule, d_rule, n, hipMemcpyDeviceToHost, ctx->stream));
+    PG_HIP(hipStreamSynchronize(ctx->stream));
+    return PG_OK;
+}
+
+}  // extern "C"

@@ -16,46 +16,11 @@
 // ${name}, and the registered functions maxIndex(${v}) / maxValue(${v}) over a list property (antlr_functions.go:34-66) —
 // compiled to the same device program; anything else is refused BY NAME (PG_ERR_UNSUPPORTED), never evaluated differently.
 #include "common.hpp"
+#include "expr_prog.hpp"
 
 #include <cmath>
 #include <string>
 #include <vector>
-
-namespace pg {
-
-enum OpCode : uint32_t { OP_CONST = 0, OP_VAR, OP_ADD, OP_SUB, OP_MUL, OP_DIV, OP_MOD, OP_POW, OP_FNZ,
-                         OP_DIVF,   // antlr subset: float division as Go's `/` on float64 (no panic: ±Inf / NaN)
-                         OP_NEG };  // antlr subset: unary minus
-
-struct Instr {
-    uint32_t op;
-    uint32_t arg;     // variable index
-    double val;       // constant
-};
-
-constexpr int kMaxStack = 32;
-constexpr int kMaxProg = 128;
-
-}  // namespace pg
-
-struct pg_expr {
-    std::string source;
-    std::vector<pg::Instr> prog;
-    std::vector<std::string> vars;
-    int max_depth = 0;
-    bool empty = false;       // "" → no expression (GetExpAST returns nil)
-    bool antlr = false;       // compiled by pg_expr_compile_typed(…, "antlr"): the evaluation-error rule of ExprASTResultByAntlr applies on the host
-    // RankConfig.ScoreRewrite of the scene this RankScore belongs to (pg_expr_set_score_rewrites): evaluated by the
-    // recommend pipelines' fusion stage before the RankScore itself (pipeline.hip: post_fuse_sort_locked)
-    struct Rewrite {
-        std::string source;
-        bool failed = false;  // the source's expression did not compile in the reference: the score is 0 (rank_service.go:349-351)
-        std::vector<pg::Instr> prog;
-        std::vector<std::string> vars;
-    };
-    std::vector<Rewrite> rewrites;
-    mutable std::atomic<int> holders{0};     // bindings made from this expression that are still alive (pg::ExprHold)
-};
 
 namespace pg {
 
@@ -277,52 +242,6 @@ struct ExprDev {
     uint32_t n;
 };
 
-// math.Pow as `^` sees it (utils/ast/ast.go:246; Go stdlib math/pow.go, go 1.24 per the reference's go.mod).  Go does not call a
-// libm pow: Pow(x, 1) = x and Pow(x, +-0.5) = Sqrt(x), 1 / Sqrt(x) are exact special cases, and the INTEGER part of the exponent
-// is applied by repeated squaring of Frexp(x)'s mantissa with the binary exponent carried on the side — so 400^4 is exactly
-// 25 600 000 000 where pow() is an ulp off (and that ulp decides whether the power is an integer-valued exponent of the next
-// `^`, or what an integer `%` of it leaves: found by scripts/soak_expr.py).  Integer-valued exponents therefore take Go's loop
-// here, bit for bit (the oracle restates the same loop); fractional ones stay on pow(), within 2 ulp of Go's Exp(yf Log(x)) form.
-__device__ __forceinline__ double go_pow(double x, double y) {
-    if (y == 1.0) return x;
-    const bool xfin = x == x && fabs(x) != __builtin_inf();
-    if (y == 0.5 && xfin && x != 0.0) return sqrt(x);
-    if (y == -0.5 && xfin && x != 0.0) return 1.0 / sqrt(x);
-    const double ay = fabs(y);
-    if (xfin && x != 0.0 && x != 1.0 && y != 0.0 && ay < 9223372036854775808.0 && ay == trunc(ay)) {
-        double a1 = 1.0;
-        long long ae = 0;
-        int xe_i;
-        double x1 = frexp(x, &xe_i);
-        long long xe = xe_i;
-        for (long long i = (long long)ay; i != 0; i >>= 1) {
-            if (xe < -(1ll << 12) || (1ll << 12) < xe) {
-                // overflow / underflow of the result: catch the exponent, stop
-                ae += xe;
-                break;
-            }
-            if (i & 1) {
-                a1 *= x1;
-                ae += xe;
-            }
-            x1 *= x1;
-            xe <<= 1;
-            if (x1 < 0.5) {
-                x1 += x1;
-                xe--;
-            }
-        }
-        if (y < 0.0) {
-            a1 = 1.0 / a1;
-            ae = -ae;
-        }
-        if (ae > 4096) ae = 4096;                     // ldexp's int argument: far beyond the format either way
-        if (ae < -4096) ae = -4096;
-        return ldexp(a1, (int)ae);
-    }
-    return pow(x, y);
-}
-
 __global__ void expr_eval_kernel(ExprDev e, const double* __restrict__ vars, uint32_t n_items,
                                  double* __restrict__ out, uint32_t* __restrict__ err, uint32_t items_per_flag) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -341,29 +260,14 @@ __global__ void expr_eval_kernel(ExprDev e, const double* __restrict__ vars, uin
                 st[sp - 1] = -st[sp - 1];
                 continue;
             }
+            if (in.op == OP_ROUND) {
+                st[sp - 1] = round(st[sp - 1]);
+                continue;
+            }
             const double r = st[--sp];
             const double l = st[--sp];
-            double v = 0.0;
-            switch (in.op) {
-                case OP_DIVF: v = l / r; break;
-                case OP_ADD: v = l + r; break;
-                case OP_SUB: v = l - r; break;
-                case OP_MUL: v = l * r; break;
-                case OP_DIV:
-                    if (r == 0.0) bad = true; else v = l / r;
-                    break;
-                case OP_MOD: {
-                    // float64(int(l) % int(r)); Go's float→int of NaN/out-of-range gives MinInt64 on amd64
-                    const long long li = (l == l && fabs(l) < 9223372036854775808.0) ? (long long)l : (long long)0x8000000000000000ull;
-                    const long long ri = (r == r && fabs(r) < 9223372036854775808.0) ? (long long)r : (long long)0x8000000000000000ull;
-                    if (ri == 0) bad = true;
-                    else if (ri == -1) v = 0.0;
-                    else v = (double)(li % ri);
-                    break;
-                }
-                case OP_POW: v = go_pow(l, r); break;
-                case OP_FNZ: v = (l != 0.0) ? l : r; break;
-            }
+            double v;
+            if (!expr_binop(in.op, l, r, &v)) bad = true;
             st[sp++] = v;
         }
     }
@@ -720,6 +624,249 @@ int pg_expr_compile_typed(const char* source, const char* ast_type, pg_expr** ou
     }
     e->max_depth = p.max_depth;
     *out = e;
+    return PG_OK;
+}
+
+// ---- the govaluate arithmetic subset (BoostScoreSort expressions, sort/boost_score_sort.go:20-36) -------------------------------
+// Knetic/govaluate as the reference builds it (NewEvaluableExpressionWithFunctions with utils.GovaluateFunctions): every number is
+// a float64; precedence  + -  <  * / %  <  **  <  prefix -  <  value, as host/feature.cpp states it for the feature normalizer
+// (so -a ** 2 is (-a) ** 2); `/` is Go's float division (OP_DIVF), `%` math.Mod (OP_FMOD), `**` math.Pow (OP_POW); names are bare
+// or [bracketed]; round(x) / round(x, n) are utils/govaluate_functions.go:63-75.  Comparators, the ternary, && ||, strings,
+// booleans, every other function and a chained ** are refused by name: never evaluated differently.
+namespace pg {
+namespace {
+struct GvParser {
+    const std::string& s;
+    size_t i = 0;
+    pg_expr* e;
+    int depth = 0, max_depth = 0, nest = 0;
+    std::string err;
+    GvParser(const std::string& src, pg_expr* out) : s(src), e(out) {}
+    void ws() { while (i < s.size() && (s[i] == ' ' || s[i] == '\t' || s[i] == '\n' || s[i] == '\r')) ++i; }
+    bool fail(const std::string& m) { if (err.empty()) err = m; return false; }
+    bool at(const char* t) { ws(); return s.compare(i, strlen(t), t) == 0; }
+    void push(uint32_t op, uint32_t arg, double val) {
+        e->prog.push_back({op, arg, val});
+        if (op == OP_CONST || op == OP_VAR) max_depth = std::max(max_depth, ++depth);
+        else if (op != OP_NEG && op != OP_ROUND) --depth;
+    }
+    uint32_t var(const std::string& name) {
+        uint32_t idx = 0;
+        for (; idx < e->vars.size(); ++idx)
+            if (e->vars[idx] == name) break;
+        if (idx == e->vars.size()) e->vars.push_back(name);
+        return idx;
+    }
+    static bool is_alpha(char c) { return (c >= 'a' && c <= 'z') || (c >= 'A' && c <= 'Z') || c == '_'; }
+    static bool is_digit(char c) { return c >= '0' && c <= '9'; }
+    bool value() {
+        ws();
+        if (i >= s.size()) return fail("unexpected end of the expression");
+        if (++nest > 64) return fail("nesting deeper than 64");
+        const bool ok = value_inner();
+        --nest;
+        return ok;
+    }
+    bool value_inner() {
+        const char c = s[i];
+        if (c == '(') {
+            ++i;
+            if (!add()) return false;
+            ws();
+            if (i < s.size() && s[i] == ',') return fail("',' (an array) is not in the served subset");
+            if (i >= s.size() || s[i] != ')') return unexpected("missing ')'");
+            ++i;
+            return true;
+        }
+        if (is_digit(c) || c == '.') {
+            if (c == '0' && i + 1 < s.size() && (s[i + 1] == 'x' || s[i + 1] == 'X')) return fail("a hexadecimal literal is not in the served subset");
+            size_t j = i;
+            while (j < s.size() && (is_digit(s[j]) || s[j] == '.')) ++j;      // govaluate's isNumeric: digits and '.'
+            const std::string lit = s.substr(i, j - i);
+            size_t dots = 0, digits = 0;
+            for (char d : lit) (d == '.' ? dots : digits)++;
+            if (dots > 1 || digits == 0) return fail("malformed number '" + lit + "'");
+            if (j < s.size() && is_alpha(s[j])) return fail("malformed number '" + lit + s[j] + "…' (govaluate reads digits and '.' only)");
+            i = j;
+            push(OP_CONST, 0, strtod(lit.c_str(), nullptr));
+            return true;
+        }
+        if (c == '[') {
+            const size_t close = s.find(']', i + 1);
+            if (close == std::string::npos || close == i + 1) return fail("unterminated or empty [name]");
+            push(OP_VAR, var(s.substr(i + 1, close - i - 1)), 0.0);
+            i = close + 1;
+            return true;
+        }
+        if (c == '\'' || c == '"') return fail("a string literal is not in the served subset");
+        if (is_alpha(c)) {
+            size_t j = i;
+            while (j < s.size() && (is_alpha(s[j]) || is_digit(s[j]) || s[j] == '.')) ++j;
+            const std::string name = s.substr(i, j - i);
+            if (name.find('.') != std::string::npos) return fail("the accessor \"" + name + "\" is not in the served subset");
+            if (name == "true" || name == "false") return fail("the boolean \"" + name + "\" is not in the served subset");
+            if (name == "in" || name == "IN") return fail("the comparator \"in\" is not in the served subset");
+            i = j;
+            ws();
+            if (i < s.size() && s[i] == '(') {
+                if (name != "round") return fail("the function \"" + name + "\" is not in the served subset (functions: round)");
+                ++i;
+                if (!add()) return false;
+                ws();
+                if (i < s.size() && s[i] == ',') {
+                    ++i;
+                    if (!add()) return false;
+                    ws();
+                    if (i < s.size() && s[i] == ',') return fail("round: wrong number of arguments");
+                    if (i >= s.size() || s[i] != ')') return unexpected("round: missing ')'");
+                    ++i;
+                    push(OP_ROUND2, 0, 0.0);
+                    return true;
+                }
+                if (i >= s.size() || s[i] != ')') return unexpected("round: missing ')'");
+                ++i;
+                push(OP_ROUND, 0, 0.0);
+                return true;
+            }
+            if (name == "round") return fail("the function \"round\" needs its argument list");
+            push(OP_VAR, var(name), 0.0);
+            return true;
+        }
+        return unexpected("unexpected");
+    }
+    // names what stands at the cursor: an operator of the language outside the subset, or the character
+    bool unexpected(const std::string& what) {
+        ws();
+        if (i >= s.size()) return fail(what + ": end of the expression");
+        static const char* const ops[] = {"==", "!=", ">=", "<=", "&&", "||", "=~", "!~", "<<", ">>", "??", ">", "<", "?", ":", "!", "~", "&", "|", "^"};
+        for (const char* o : ops)
+            if (s.compare(i, strlen(o), o) == 0) return fail(std::string("the operator '") + o + "' is not in the served subset");
+        if (is_alpha(s[i])) {
+            size_t j = i;
+            while (j < s.size() && (is_alpha(s[j]) || is_digit(s[j]))) ++j;
+            const std::string w = s.substr(i, j - i);
+            if (w == "in" || w == "IN") return fail("the comparator \"in\" is not in the served subset");
+            return fail(what + " \"" + w + "\"");
+        }
+        return fail(what + " '" + s[i] + "'");
+    }
+    bool prefix() {
+        ws();
+        if (i < s.size() && s[i] == '-') {
+            ++i;
+            if (++nest > 64) return fail("nesting deeper than 64");
+            const bool ok = prefix();
+            --nest;
+            if (!ok) return false;
+            push(OP_NEG, 0, 0.0);
+            return true;
+        }
+        return value();
+    }
+    bool power() {
+        if (!prefix()) return false;
+        if (at("**")) {
+            i += 2;
+            if (!prefix()) return false;
+            push(OP_POW, 0, 0.0);
+            if (at("**")) return fail("a chained '**' is not in the served subset (write the parentheses)");
+        }
+        return true;
+    }
+    bool mul() {
+        if (!power()) return false;
+        for (;;) {
+            ws();
+            if (i >= s.size() || (s[i] != '*' && s[i] != '/' && s[i] != '%')) return true;
+            const char op = s[i++];
+            if (!power()) return false;
+            push(op == '*' ? OP_MUL : op == '/' ? OP_DIVF : OP_FMOD, 0, 0.0);
+        }
+    }
+    bool add() {
+        if (!mul()) return false;
+        for (;;) {
+            ws();
+            if (i >= s.size() || (s[i] != '+' && s[i] != '-')) return true;
+            const char op = s[i++];
+            if (!mul()) return false;
+            push(op == '+' ? OP_ADD : OP_SUB, 0, 0.0);
+        }
+    }
+};
+}  // namespace
+
+// the program on host values, one item: vars[v] is variable v; false where the reference panics (OP_DIV / OP_MOD by zero)
+bool expr_run_host(const std::vector<Instr>& prog, const double* vars, double* out) {
+    double st[kMaxStack];
+    int sp = 0;
+    bool ok = true;
+    for (const Instr& in : prog) {
+        if (in.op == OP_CONST) st[sp++] = in.val;
+        else if (in.op == OP_VAR) st[sp++] = vars[in.arg];
+        else if (in.op == OP_NEG) st[sp - 1] = -st[sp - 1];
+        else if (in.op == OP_ROUND) st[sp - 1] = round(st[sp - 1]);
+        else {
+            const double r = st[--sp];
+            const double l = st[--sp];
+            double v;
+            if (!expr_binop(in.op, l, r, &v)) ok = false;
+            st[sp++] = v;
+        }
+    }
+    *out = sp > 0 ? st[sp - 1] : 0.0;
+    return ok;
+}
+}  // namespace pg
+
+int pg_expr_compile_govaluate(const char* source, pg_expr** out) {
+    PG_REQUIRE(source && out, "pg_expr_compile_govaluate: NULL argument");
+    pg_expr* e = new pg_expr();
+    e->source = source;
+    if (e->source.empty()) {                                 // BoostScoreCondition.Expression "": no expression is built
+        e->empty = true;
+        *out = e;
+        return PG_OK;
+    }
+    bool ok = e->source.size() <= 16384;
+    pg::GvParser p(e->source, e);
+    if (!ok) p.fail("expression too large");
+    if (ok) ok = p.add();
+    if (ok) {
+        p.ws();
+        if (p.i != e->source.size()) ok = p.unexpected("unexpected");
+    }
+    if (!ok) {
+        pg::set_error("pg_expr_compile_govaluate: %s at byte %zu of '%.200s' — the engine serves the arithmetic subset of govaluate "
+                      "(float64 numbers, names, [names], + - * / %% **, unary minus, parentheses, round) and refuses the rest rather "
+                      "than evaluate it differently", p.err.c_str(), p.i, source);
+        delete e;
+        return PG_ERR_UNSUPPORTED;
+    }
+    if (e->prog.size() > (size_t)pg::kMaxProg || p.max_depth > pg::kMaxStack) {
+        pg::set_error("pg_expr_compile_govaluate: expression too large (%zu operations, depth %d)", e->prog.size(), p.max_depth);
+        delete e;
+        return PG_ERR_UNSUPPORTED;
+    }
+    e->max_depth = p.max_depth;
+    *out = e;
+    return PG_OK;
+}
+
+int pg_expr_eval_host(const pg_expr* e, const double* vars, uint32_t n_items, double* out_scores) {
+    PG_REQUIRE(e && out_scores, "pg_expr_eval_host: NULL argument");
+    PG_REQUIRE(e->vars.empty() || vars || n_items == 0, "pg_expr_eval_host: vars is NULL but the expression has parameters");
+    std::vector<double> v(e->vars.size());
+    bool ok = true;
+    for (uint32_t i = 0; i < n_items; ++i) {
+        for (size_t k = 0; k < v.size(); ++k) v[k] = vars[k * (size_t)n_items + i];
+        if (e->empty) out_scores[i] = 0.0;
+        else if (!pg::expr_run_host(e->prog, v.data(), &out_scores[i])) ok = false;
+    }
+    if (!ok) {
+        pg::set_expr_arith_error(e);
+        return PG_ERR_ARITH;
+    }
     return PG_OK;
 }
 

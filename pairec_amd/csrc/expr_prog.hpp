@@ -1,0 +1,132 @@
+// expr_prog.hpp — the postfix program the expression front ends compile to (expr.hip) and the pieces other evaluators of it
+// share (cond.hip walks such programs per candidate with a register stack).
+#pragma once
+#include "common.hpp"
+
+#include <atomic>
+#include <cmath>
+#include <string>
+#include <vector>
+
+namespace pg {
+
+enum OpCode : uint32_t { OP_CONST = 0, OP_VAR, OP_ADD, OP_SUB, OP_MUL, OP_DIV, OP_MOD, OP_POW, OP_FNZ,
+                         OP_DIVF,   // antlr subset: float division as Go's `/` on float64 (no panic: ±Inf / NaN)
+                         OP_NEG,    // antlr subset: unary minus
+                         OP_FMOD,   // govaluate subset: `%` = math.Mod on float64 (no panic: NaN for a zero divisor)
+                         OP_ROUND,  // govaluate subset: round(x) = math.Round (unary)
+                         OP_ROUND2 };  // govaluate subset: round(x, n) = math.Trunc(x * Pow(10, n)) / Pow(10, n) (binary)
+
+struct Instr {
+    uint32_t op;
+    uint32_t arg;     // variable index
+    double val;       // constant
+};
+
+constexpr int kMaxStack = 32;
+constexpr int kMaxProg = 128;
+
+}  // namespace pg
+
+struct pg_expr {
+    std::string source;
+    std::vector<pg::Instr> prog;
+    std::vector<std::string> vars;
+    int max_depth = 0;
+    bool empty = false;       // "" → no expression (GetExpAST returns nil)
+    bool antlr = false;       // compiled by pg_expr_compile_typed(…, "antlr"): the evaluation-error rule of ExprASTResultByAntlr applies on the host
+    // RankConfig.ScoreRewrite of the scene this RankScore belongs to (pg_expr_set_score_rewrites): evaluated by the
+    // recommend pipelines' fusion stage before the RankScore itself (pipeline.hip: post_fuse_sort_locked)
+    struct Rewrite {
+        std::string source;
+        bool failed = false;  // the source's expression did not compile in the reference: the score is 0 (rank_service.go:349-351)
+        std::vector<pg::Instr> prog;
+        std::vector<std::string> vars;
+    };
+    std::vector<Rewrite> rewrites;
+    mutable std::atomic<int> holders{0};     // bindings made from this expression that are still alive (pg::ExprHold)
+};
+
+namespace pg {
+
+// math.Pow as `^` sees it (utils/ast/ast.go:246; Go stdlib math/pow.go, go 1.24 per the reference's go.mod).  Go does not call a
+// libm pow: Pow(x, 1) = x and Pow(x, +-0.5) = Sqrt(x), 1 / Sqrt(x) are exact special cases, and the INTEGER part of the exponent
+// is applied by repeated squaring of Frexp(x)'s mantissa with the binary exponent carried on the side — so 400^4 is exactly
+// 25 600 000 000 where pow() is an ulp off (and that ulp decides whether the power is an integer-valued exponent of the next
+// `^`, or what an integer `%` of it leaves: found by scripts/soak_expr.py).  Integer-valued exponents therefore take Go's loop
+// here, bit for bit (the oracle restates the same loop); fractional ones stay on pow(), within 2 ulp of Go's Exp(yf Log(x)) form.
+__host__ __device__ __forceinline__ double go_pow(double x, double y) {
+    if (y == 1.0) return x;
+    const bool xfin = x == x && fabs(x) != __builtin_inf();
+    if (y == 0.5 && xfin && x != 0.0) return sqrt(x);
+    if (y == -0.5 && xfin && x != 0.0) return 1.0 / sqrt(x);
+    const double ay = fabs(y);
+    if (xfin && x != 0.0 && x != 1.0 && y != 0.0 && ay < 9223372036854775808.0 && ay == trunc(ay)) {
+        double a1 = 1.0;
+        long long ae = 0;
+        int xe_i;
+        double x1 = frexp(x, &xe_i);
+        long long xe = xe_i;
+        for (long long i = (long long)ay; i != 0; i >>= 1) {
+            if (xe < -(1ll << 12) || (1ll << 12) < xe) {
+                // overflow / underflow of the result: catch the exponent, stop
+                ae += xe;
+                break;
+            }
+            if (i & 1) {
+                a1 *= x1;
+                ae += xe;
+            }
+            x1 *= x1;
+            xe <<= 1;
+            if (x1 < 0.5) {
+                x1 += x1;
+                xe--;
+            }
+        }
+        if (y < 0.0) {
+            a1 = 1.0 / a1;
+            ae = -ae;
+        }
+        if (ae > 4096) ae = 4096;                     // ldexp's int argument: far beyond the format either way
+        if (ae < -4096) ae = -4096;
+        return ldexp(a1, (int)ae);
+    }
+    return pow(x, y);
+}
+
+// one binary operation of the program; false: the reference panics here (a zero divisor of OP_DIV / OP_MOD)
+__host__ __device__ __forceinline__ bool expr_binop(uint32_t op, double l, double r, double* out) {
+    double v = 0.0;
+    bool ok = true;
+    switch (op) {
+        case OP_DIVF: v = l / r; break;
+        case OP_ADD: v = l + r; break;
+        case OP_SUB: v = l - r; break;
+        case OP_MUL: v = l * r; break;
+        case OP_DIV:
+            if (r == 0.0) ok = false; else v = l / r;
+            break;
+        case OP_MOD: {
+            // float64(int(l) % int(r)); Go's float→int of NaN/out-of-range gives MinInt64 on amd64
+            const long long li = (l == l && fabs(l) < 9223372036854775808.0) ? (long long)l : (long long)0x8000000000000000ull;
+            const long long ri = (r == r && fabs(r) < 9223372036854775808.0) ? (long long)r : (long long)0x8000000000000000ull;
+            if (ri == 0) ok = false;
+            else if (ri == -1) v = 0.0;
+            else v = (double)(li % ri);
+            break;
+        }
+        case OP_POW: v = go_pow(l, r); break;
+        case OP_FNZ: v = (l != 0.0) ? l : r; break;
+        case OP_FMOD: v = fmod(l, r); break;
+        case OP_ROUND2: {
+            const double m = go_pow(10.0, r);
+            v = trunc(l * m) / m;
+            break;
+        }
+    }
+    *out = v;
+    return ok;
+}
+
+}  // namespace pg

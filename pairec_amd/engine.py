@@ -112,6 +112,174 @@ def diversity_rules_host(cfg, dims, count=None, source=None, enable=None) -> np.
     return out
 
 
+COND_MAX_RULES, COND_MAX_TERMS, COND_MAX_COLS, COND_MAX_SLOTS, COND_MAX_LIST = 8, 8, 16, 8, 64
+_COND_OPS = {"equal": 0, "not_equal": 1, "greater": 2, "greaterThan": 3, "less": 4, "lessThan": 5, "in": 6, "not_in": 7,
+             "is_null": 8, "is_not_null": 9, "bool": 10, "contains": 11, "not_contains": 12, "expression": 13}
+_COND_TYPES = {"int": 0, "int64": 1, "float": 2, "string": 3}
+_F_NP = {1: np.int32, 2: np.int64, 3: np.float32, 4: np.float64}
+
+
+def _cond_const(value, type_, strings):
+    """a FilterParamConfig.Value as the term's constant: utils.ToInt / ToInt64 / ToFloat of a JSON value (numbers, numeric strings),
+    the dictionary id of a string"""
+    if type_ == "string":
+        if isinstance(value, str):
+            if value not in strings:
+                strings[value] = -2 - len(strings)          # a value no item carries: an id no dictionary hands out
+            return int(strings[value]), 0.0
+        return int(value), 0.0                              # already a dictionary id
+    if type_ == "float":
+        return 0, float(value)
+    return int(float(value)) if isinstance(value, (float, str)) else int(value), 0.0
+
+
+def _cond_terms(configs, strings, keep, depth=0):
+    """[FilterParamConfig] (the reference's JSON keys: Name, Domain, Operator, Type, Value, Configs) → [PgCondTerm], a bool
+    followed by its children.  As NewFilterParamWithConfig (filter_op.go:457-495) an unknown Operator adds nothing."""
+    out = []
+    for cfg in configs:
+        op = cfg.get("Operator", "")
+        if op not in _COND_OPS:
+            continue
+        t = _lib.PgCondTerm()
+        t.op, t.depth = _COND_OPS[op], depth
+        keep.append((cfg.get("Name", "") or "").encode("utf-8"))
+        t.name = keep[-1]
+        keep.append((cfg.get("Domain", "") or "").encode("utf-8"))
+        t.domain = keep[-1]
+        if op == "bool":
+            ty = str(cfg.get("Type", "") or "")
+            t.bool_and = 0 if ty == "" or ty.lower() == "or" else 1           # NewBoolFilterOp, :1640-1651
+            out.append(t)
+            out.extend(_cond_terms(cfg.get("Configs", ()) or (), strings, keep, depth + 1))
+            continue
+        ty = cfg.get("Type", "")
+        if op in ("is_null", "is_not_null"):
+            out.append(t)
+            continue
+        if ty not in _COND_TYPES:
+            raise ValueError("FilterParam: Type %r of %r is not served (int, int64, float, string)" % (ty, cfg.get("Name")))
+        t.type = _COND_TYPES[ty]
+        v = cfg.get("Value")
+        if isinstance(v, str) and (v.startswith("user.") or v.startswith("item.")):
+            t.rhs = 1 if v.startswith("user.") else 2
+            keep.append(v[5:].encode("utf-8"))
+            t.rhs_name = keep[-1]
+        elif op in ("in", "not_in"):
+            vals = [] if v is None or isinstance(v, str) else [_cond_const(x, "int" if ty != "string" else ty, strings)[0] for x in v]
+            arr = (C.c_longlong * max(len(vals), 1))(*vals)
+            keep.append(arr)
+            t.list, t.n_list = arr, len(vals)
+        elif op not in ("contains", "not_contains", "expression"):
+            t.i, t.f = _cond_const(v, ty, strings)
+        out.append(t)
+    return out
+
+
+class Cond:
+    """A compiled condition set (pg_cond_compile): 1..8 FilterParams over declared columns, optionally each with a govaluate
+    expression (a BoostScoreSort rule set).  rules: [{"Conditions": [FilterParamConfig], "Expression": str}] with the
+    reference's JSON keys; cols: [(name, F_I32 | F_I64 | F_F32 | F_F64)]; strings: {value: dictionary id} for string terms
+    (a value it lacks gets an id no item carries).  A host object until a device entry first uses it."""
+
+    def __init__(self, rules, cols, boost: bool = False, strings: Optional[dict] = None):
+        self.L = _lib.load()
+        self.cols = [(str(n), int(d)) for n, d in cols]
+        self.boost = bool(boost)
+        self.strings = dict(strings or {})
+        keep = []
+        arr = (_lib.PgCondRule * max(len(rules), 1))()
+        for i, r in enumerate(rules):
+            terms = _cond_terms(r.get("Conditions", ()) or (), self.strings, keep)
+            ta = (_lib.PgCondTerm * max(len(terms), 1))(*terms)
+            keep.append(ta)
+            arr[i].terms, arr[i].n_terms = ta, len(terms)
+            if r.get("Expression") is not None:
+                keep.append(str(r["Expression"]).encode("utf-8"))
+                arr[i].expression = keep[-1]
+        ca = (_lib.PgCondCol * max(len(self.cols), 1))()
+        for i, (n, d) in enumerate(self.cols):
+            keep.append(n.encode("utf-8"))
+            ca[i].name, ca[i].dtype = keep[-1], d
+        h = C.c_void_p()
+        _lib.check(self.L.pg_cond_compile(arr, len(rules), ca, len(self.cols), 1 if boost else 0, C.byref(h)))
+        del keep
+        self.h = h
+        self.n_rules = self.L.pg_cond_num_rules(h)
+        self.user_slots = [(self.L.pg_cond_user_slot_name(h, i).decode("utf-8"), bool(self.L.pg_cond_user_slot_is_float(h, i)))
+                           for i in range(self.L.pg_cond_num_user_slots(h))]
+
+    def free(self):
+        if self.h:
+            self.L.pg_cond_free(self.h)
+            self.h = None
+
+    def pack_user(self, users):
+        """one {name: value} per request (a name it lacks: the slot is absent) → (vals [nq][8] uint64 bits, present [nq] uint32)"""
+        vals = np.zeros((len(users), COND_MAX_SLOTS), dtype=np.uint64)
+        present = np.zeros(len(users), dtype=np.uint32)
+        for q, u in enumerate(users):
+            for s, (name, is_float) in enumerate(self.user_slots):
+                if u is not None and name in u:
+                    present[q] |= np.uint32(1 << s)
+                    vals[q, s] = np.array([u[name]], dtype=np.float64 if is_float else np.int64).view(np.uint64)[0]
+        return vals, present
+
+    def _host_args(self, cols, item_in, user):
+        n, arrs = None, []
+        ptrs = (C.c_void_p * max(len(self.cols), 1))()
+        for i, (name, dt) in enumerate(self.cols):
+            if cols is not None and name in cols:
+                a = np.ascontiguousarray(cols[name], dtype=_F_NP[dt]).reshape(-1)
+                arrs.append(a)
+                ptrs[i] = a.ctypes.data
+                n = a.shape[0] if n is None else n
+                if a.shape[0] != n:
+                    raise ValueError("Cond: the columns' arrays differ in length")
+        inn = None if item_in is None else np.ascontiguousarray(item_in, dtype=np.uint8).reshape(-1)
+        if inn is not None:
+            n = inn.shape[0] if n is None else n
+        vals, present = self.pack_user([user])
+        return n, arrs, ptrs, inn, vals, int(present[0])
+
+    def match_host(self, cols=None, item_in=None, user=None, rule: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """pg_cond_match_host: rule `rule` on n candidates given as candidate-aligned arrays {column name: [n]}; item_in [n]:
+        0 = the candidate's row is outside the store; user {name: value} of the one request → [n] bool."""
+        m, arrs, ptrs, inn, vals, present = self._host_args(cols, item_in, user)
+        n = m if n is None else n
+        out = np.zeros(n or 0, dtype=np.uint8)
+        _lib.check(self.L.pg_cond_match_host(self.h, rule, n or 0, None if inn is None else _ptr(inn), ptrs, _ptr(vals), present, _ptr(out)))
+        del arrs
+        return out.astype(bool)
+
+    def boost_host(self, score, cols=None, item_in=None, user=None, filter_all: bool = False):
+        """pg_boost_scores_host: BoostScoreSort's walk on n candidates → (scores [n] fp64, last matching rule [n] uint8, 0xFF none)"""
+        sc = np.ascontiguousarray(score, dtype=np.float64).reshape(-1)
+        m, arrs, ptrs, inn, vals, present = self._host_args(cols, item_in, user)
+        if m is not None and m != sc.shape[0]:
+            raise ValueError("Cond.boost_host: score and the columns differ in length")
+        out, rule = np.empty_like(sc), np.empty(sc.shape[0], dtype=np.uint8)
+        _lib.check(self.L.pg_boost_scores_host(self.h, 1 if filter_all else 0, sc.shape[0], None if inn is None else _ptr(inn), ptrs, _ptr(vals),
+                                               present, _ptr(sc), _ptr(out), _ptr(rule)))
+        del arrs
+        return out, rule
+
+
+def cond_compile(rules, cols, boost: bool = False, strings: Optional[dict] = None) -> Cond:
+    """pg_cond_compile (see Cond)."""
+    return Cond(rules, cols, boost, strings)
+
+
+def cond_match_host(cond: Cond, cols=None, item_in=None, user=None, rule: int = 0, n: Optional[int] = None) -> np.ndarray:
+    """pg_cond_match_host (see Cond.match_host): a host function, no context, no device."""
+    return cond.match_host(cols, item_in, user, rule, n)
+
+
+def expr_compile_govaluate(source: str) -> "Expr":
+    """pg_expr_compile_govaluate: the arithmetic subset of govaluate that BoostScoreSort expressions use."""
+    return Expr(source, govaluate=True)
+
+
 class Context:
     def __init__(self, device: int = 0, stream: Optional[int] = None):
         self.L = _lib.load()
@@ -399,6 +567,138 @@ class Context:
         _lib.check(self.L.pg_diversity_rules(self.h, C.byref(c), d.shape[1], _ptr(d), None if src is None else _ptr(src), _ptr(out)))
         del keep
         return out
+
+    # ---- FilterParam stages: ItemStateFilter, BoostScoreSort ------------------------------------------
+    def item_state_filter_dev(self, cond, fs, nq: int, cap: int, d_rows: int, d_score: int, d_source: int, d_count: int,
+                              d_planes_f64: int, n_f64: int, d_source_mask: int, d_planes_f32: int, n_f32: int, d_user_vals: int,
+                              d_user_present: int, d_out_rows: int, d_out_score: int, d_out_source: int, d_out_planes_f64: int,
+                              d_out_source_mask: int, d_out_planes_f32: int, d_out_count: int) -> None:
+        """pg_item_state_filter_dev: device addresses (0 = absent; an output is required exactly where its input is given),
+        outputs [nq][cap].  Enqueued on the context's stream: synchronize() before reading."""
+        v = lambda p: C.c_void_p(p or None)                                          # noqa: E731
+        _lib.check(self.L.pg_item_state_filter_dev(self.h, cond.h, getattr(fs, "h", fs), nq, cap, v(d_rows), v(d_score), v(d_source),
+                                                   v(d_count), v(d_planes_f64), n_f64, v(d_source_mask), v(d_planes_f32), n_f32,
+                                                   v(d_user_vals), v(d_user_present), v(d_out_rows), v(d_out_score), v(d_out_source),
+                                                   v(d_out_planes_f64), v(d_out_source_mask), v(d_out_planes_f32), v(d_out_count)))
+
+    def boost_scores_dev(self, cond, fs, filter_all: bool, nq: int, cap: int, d_rows: int, d_score: int, d_count: int, d_user_vals: int,
+                         d_user_present: int, d_out_score: int, d_out_rule: int) -> None:
+        """pg_boost_scores_dev: device addresses (0 = absent).  Enqueued on the context's stream: synchronize() before reading."""
+        v = lambda p: C.c_void_p(p or None)                                          # noqa: E731
+        _lib.check(self.L.pg_boost_scores_dev(self.h, cond.h, getattr(fs, "h", fs), 1 if filter_all else 0, nq, cap, v(d_rows), v(d_score),
+                                              v(d_count), v(d_user_vals), v(d_user_present), v(d_out_score), v(d_out_rule)))
+
+    def _cond_user(self, cond, users, nq):
+        if users is None:
+            users = [None] * nq
+        if len(users) != nq:
+            raise ValueError("%d user maps for %d requests" % (len(users), nq))
+        return cond.pack_user(users)
+
+    def item_state_filter(self, cond, fs, rows, score, source=None, count=None, planes_f64=None, source_mask=None, planes_f32=None,
+                          users=None):
+        """ItemStateFilter on host arrays (pg_item_state_filter_dev): fanin_merge's rows [nq][cap] u64, score [nq][cap] f64,
+        source [nq][cap] u8, count [nq], planes [n][nq][cap], source_mask [nq][cap] u32; users: one {name: value} per request →
+        (rows, score, source, planes_f64, source_mask, planes_f32, count), [nq][cap] each, None where the input was None."""
+        r = np.ascontiguousarray(rows, dtype=np.uint64)
+        sc = np.ascontiguousarray(score, dtype=np.float64)
+        if r.ndim != 2 or sc.shape != r.shape:
+            raise ValueError("item_state_filter: rows and score are [nq][cap]")
+        nq, cap = r.shape
+        opt = [None if source is None else np.ascontiguousarray(source, dtype=np.uint8),
+               None if count is None else np.ascontiguousarray(count, dtype=np.uint32),
+               None if planes_f64 is None else np.ascontiguousarray(planes_f64, dtype=np.float64),
+               None if source_mask is None else np.ascontiguousarray(source_mask, dtype=np.uint32),
+               None if planes_f32 is None else np.ascontiguousarray(planes_f32, dtype=np.float32)]
+        for a, shape in ((opt[0], (nq, cap)), (opt[1], (nq,)), (opt[3], (nq, cap))):
+            if a is not None and a.shape != shape:
+                raise ValueError("item_state_filter: source and source_mask are [nq][cap], count [nq]")
+        for a in (opt[2], opt[4]):
+            if a is not None and (a.ndim != 3 or a.shape[1:] != (nq, cap)):
+                raise ValueError("item_state_filter: planes are [n][nq][cap]")
+        n64 = opt[2].shape[0] if opt[2] is not None else 0
+        n32 = opt[4].shape[0] if opt[4] is not None else 0
+        uv, up = self._cond_user(cond, users, nq)
+        outs = [np.empty((nq, cap), np.uint64), np.empty((nq, cap), np.float64),
+                None if opt[0] is None else np.empty((nq, cap), np.uint8),
+                None if opt[2] is None else np.empty((n64, nq, cap), np.float64),
+                None if opt[3] is None else np.empty((nq, cap), np.uint32),
+                None if opt[4] is None else np.empty((n32, nq, cap), np.float32), np.empty(nq, np.uint32)]
+        bufs = []
+        try:
+            d_in = []
+            for a in [r, sc] + opt + [uv, up]:
+                d_in.append(self.to_device(a) if a is not None else 0)
+                bufs.append(d_in[-1])
+            d_out = []
+            for a in outs:
+                d_out.append(self.malloc(max(a.nbytes, 16)) if a is not None else 0)
+                bufs.append(d_out[-1])
+            self.item_state_filter_dev(cond, fs, nq, cap, d_in[0], d_in[1], d_in[2], d_in[3], d_in[4], n64, d_in[5], d_in[6], n32,
+                                       d_in[7], d_in[8], *d_out)
+            self.synchronize()
+            for a, p_ in zip(outs, d_out):
+                if a is not None and a.nbytes:
+                    self.d2h(a, p_)
+        finally:
+            for b in bufs:
+                if b:
+                    self.free(b)
+        return tuple(outs)
+
+    def boost_scores(self, cond, fs, rows, score, count=None, users=None, filter_all: bool = False):
+        """BoostScoreSort's rewrite on host arrays (pg_boost_scores_dev): rows [nq][cap] u64, score [nq][cap] f64, count [nq],
+        users: one {name: value} per request → (scores [nq][cap] f64, last matching rule [nq][cap] u8, 0xFF = none)."""
+        r = np.ascontiguousarray(rows, dtype=np.uint64)
+        sc = np.ascontiguousarray(score, dtype=np.float64)
+        if r.ndim != 2 or sc.shape != r.shape:
+            raise ValueError("boost_scores: rows and score are [nq][cap]")
+        nq, cap = r.shape
+        cnt = None if count is None else np.ascontiguousarray(count, dtype=np.uint32)
+        uv, up = self._cond_user(cond, users, nq)
+        out, rule = np.empty((nq, cap), np.float64), np.empty((nq, cap), np.uint8)
+        bufs = []
+        try:
+            dev = []
+            for a in (r, sc, cnt, uv, up):
+                dev.append(self.to_device(a) if a is not None else 0)
+                bufs.append(dev[-1])
+            d_out, d_rule = self.malloc(max(out.nbytes, 16)), self.malloc(max(rule.nbytes, 16))
+            bufs += [d_out, d_rule]
+            self.boost_scores_dev(cond, fs, filter_all, nq, cap, dev[0], dev[1], dev[2], dev[3], dev[4], d_out, d_rule)
+            self.synchronize()
+            self.d2h(out, d_out)
+            self.d2h(rule, d_rule)
+        finally:
+            for b in bufs:
+                if b:
+                    self.free(b)
+        return out, rule
+
+    def item_state_filter_one(self, cond, fs, rows, score, source=None, user=None):
+        """pg_item_state_filter: one request on host arrays (what the host mirror calls) → (rows [n], score [n], source [n] | None, count)"""
+        r = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1)
+        sc = np.ascontiguousarray(score, dtype=np.float64).reshape(-1)
+        src = None if source is None else np.ascontiguousarray(source, dtype=np.uint8).reshape(-1)
+        uv, up = cond.pack_user([user])
+        o_r, o_s, o_src, cnt = np.empty_like(r), np.empty_like(sc), None if src is None else np.empty_like(src), C.c_uint32()
+        _lib.check(self.L.pg_item_state_filter(self.h, cond.h, getattr(fs, "h", fs), r.shape[0], _ptr(r), _ptr(sc),
+                                               None if src is None else _ptr(src), _ptr(uv), int(up[0]), _ptr(o_r), _ptr(o_s),
+                                               None if src is None else _ptr(o_src), C.byref(cnt)))
+        return o_r, o_s, o_src, cnt.value
+
+    def boost_scores_one(self, cond, score, cols=None, item_in=None, user=None, filter_all: bool = False):
+        """pg_boost_scores: one request on host arrays, Cond.boost_host's arguments (what the host mirror calls) →
+        (scores [n], last matching rule [n])"""
+        sc = np.ascontiguousarray(score, dtype=np.float64).reshape(-1)
+        m, arrs, ptrs, inn, vals, present = cond._host_args(cols, item_in, user)
+        if m is not None and m != sc.shape[0]:
+            raise ValueError("boost_scores_one: score and the columns differ in length")
+        out, rule = np.empty_like(sc), np.empty(sc.shape[0], dtype=np.uint8)
+        _lib.check(self.L.pg_boost_scores(self.h, cond.h, 1 if filter_all else 0, sc.shape[0], None if inn is None else _ptr(inn), ptrs,
+                                          _ptr(vals), present, _ptr(sc), _ptr(out), _ptr(rule)))
+        del arrs
+        return out, rule
 
     # ---- sort / expr (context-level ops) ----------------------------------------------------
     def sort_scores(self, scores: np.ndarray, seg_offsets: Optional[Sequence[int]] = None,
@@ -1051,11 +1351,14 @@ class Where:
 class Expr:
     """Compiled RankConfig.RankScore expression (utils/ast replacement)."""
 
-    def __init__(self, source: str, ast_type: str = ""):
-        """ast_type "antlr": the subset of the reference's second evaluator (pg_expr_compile_typed)."""
+    def __init__(self, source: str, ast_type: str = "", govaluate: bool = False):
+        """ast_type "antlr": the subset of the reference's second evaluator (pg_expr_compile_typed); govaluate: the arithmetic
+        subset of govaluate that BoostScoreSort expressions use (pg_expr_compile_govaluate)."""
         self.L = _lib.load()
         h = C.c_void_p()
-        if ast_type:
+        if govaluate:
+            _lib.check(self.L.pg_expr_compile_govaluate(source.encode("utf-8"), C.byref(h)))
+        elif ast_type:
             _lib.check(self.L.pg_expr_compile_typed(source.encode("utf-8"), ast_type.encode("utf-8"), C.byref(h)))
         else:
             _lib.check(self.L.pg_expr_compile(source.encode("utf-8"), C.byref(h)))
@@ -1086,6 +1389,15 @@ class Expr:
             for x in exprs:
                 if x is not None:
                     x.free()
+
+    def eval_host(self, vars_: np.ndarray) -> np.ndarray:
+        """pg_expr_eval_host: the program on host arrays (no context, no device); vars_ as eval."""
+        v = np.ascontiguousarray(vars_, dtype=np.float64).reshape(len(self.var_names), -1) \
+            if len(self.var_names) else np.zeros((0, int(np.shape(vars_)[-1])), dtype=np.float64)
+        n = v.shape[1]
+        out = np.empty(n, dtype=np.float64)
+        _lib.check(self.L.pg_expr_eval_host(self.h, _ptr(v) if v.size else None, n, _ptr(out)))
+        return out
 
     def eval(self, ctx: Context, vars_: np.ndarray) -> np.ndarray:
         """vars_: [n_vars][n_items] fp64 in var_names order → fused scores [n_items] fp64."""

@@ -8,6 +8,7 @@
 #include <cmath>
 #include <cstring>
 #include <ctime>
+#include <deque>
 #include <thread>
 
 namespace pairec {
@@ -134,6 +135,131 @@ std::shared_ptr<Cache> NewCache(const std::string& adapter, const std::string&, 
 }  // namespace cache
 
 // ---- recconf -------------------------------------------------------------------------------------
+// ---- module.FilterParam → pg_cond_term ---------------------------------------------------------------------------
+// [FilterParamConfig] (recconf.go:884-891) as pg_cond_compile takes it: a bool is followed by its children; an Operator that
+// NewFilterParamWithConfig does not know adds nothing (filter_op.go:457-495).  Strings — literals, item properties, user
+// properties — are dictionary-encoded per call through one map (equal strings, equal ids); without a map (a filter over the
+// engine's integer columns) a string term is refused by name.  What pg_cond_compile refuses it refuses by name itself.
+namespace {
+struct CondBuild {
+    std::map<std::string, long long>* dict = nullptr;
+    std::deque<std::string> strs;
+    std::deque<std::vector<long long>> lists;
+    std::vector<std::string> item_names;                  // referenced item properties, in order of first use
+    std::map<std::string, int> item_kind, user_kind;       // bit 0: read as a string, bit 1: read as a number
+    std::string err;
+
+    const char* keep(const std::string& x) { strs.push_back(x); return strs.back().c_str(); }
+    void item(const std::string& name, int kind) {
+        if (!item_kind.count(name)) item_names.push_back(name);
+        item_kind[name] |= kind;
+    }
+    long long code(const std::string& x) { return dict->emplace(x, (long long)dict->size()).first->second; }
+    bool constant(const json::Value& v, const std::string& type, const std::string& name, long long* i, double* f) {
+        if (type == "string") {
+            if (!dict) { err = "string term on \"" + name + "\": the store's columns are integers (encode the literal and use Type int)"; return false; }
+            *i = code(v.type == json::Value::String ? v.str : v.type == json::Value::Number ? json::NumToString(v.num) : std::string());
+            return true;
+        }
+        if (type == "float") { *f = ToFloat(v, 0.0); return true; }
+        if (v.type == json::Value::Number) { *i = v.is_int ? v.i : (long long)v.num; return true; }      // utils.ToInt: int(float64)
+        if (v.type == json::Value::String) {
+            char* end = nullptr;
+            errno = 0;
+            const long long x = strtoll(v.str.c_str(), &end, 10);
+            if (!v.str.empty() && end && !*end && errno == 0) { *i = x; return true; }
+        }
+        err = "Value of \"" + name + "\" is not an integer";
+        return false;
+    }
+    bool build(const json::Value& configs, uint32_t depth, std::vector<pg_cond_term>* out) {
+        static const std::map<std::string, int> ops = {{"equal", PG_COND_EQUAL}, {"not_equal", PG_COND_NOT_EQUAL}, {"greater", PG_COND_GREATER},
+            {"greaterThan", PG_COND_GREATER_THAN}, {"less", PG_COND_LESS}, {"lessThan", PG_COND_LESS_THAN}, {"in", PG_COND_IN}, {"not_in", PG_COND_NOT_IN},
+            {"is_null", PG_COND_IS_NULL}, {"is_not_null", PG_COND_IS_NOT_NULL}, {"bool", PG_COND_BOOL}, {"contains", PG_COND_CONTAINS},
+            {"not_contains", PG_COND_NOT_CONTAINS}, {"expression", PG_COND_EXPRESSION}};
+        static const std::map<std::string, int> types = {{"int", PG_COND_INT}, {"int64", PG_COND_INT64}, {"float", PG_COND_FLOAT}, {"string", PG_COND_STRING}};
+        for (const auto& f : configs.arr) {
+            const auto o = ops.find(f.s("Operator"));
+            if (o == ops.end()) continue;
+            pg_cond_term t;
+            memset(&t, 0, sizeof t);
+            t.op = o->second;
+            t.depth = depth;
+            if (t.op == PG_COND_BOOL) {
+                std::string ty = f.s("Type");
+                std::transform(ty.begin(), ty.end(), ty.begin(), [](unsigned char c) { return (char)std::tolower(c); });
+                t.bool_and = ty.empty() || ty == "or" ? 0u : 1u;                                            // NewBoolFilterOp, :1640-1651
+                out->push_back(t);
+                if (!build(f.at("Configs"), depth + 1, out)) return false;
+                continue;
+            }
+            const std::string name = f.s("Name"), domain = f.s("Domain"), type = f.s("Type");
+            const bool user = domain == "user";
+            t.name = keep(name);
+            t.domain = keep(domain);
+            const bool nullish = t.op == PG_COND_IS_NULL || t.op == PG_COND_IS_NOT_NULL;
+            const auto ty = types.find(type);
+            if (!nullish && ty == types.end()) { err = "Type \"" + type + "\" of \"" + name + "\" is not served (int, int64, float, string)"; return false; }
+            if (!nullish) t.type = ty->second;
+            const int kind = nullish ? 0 : type == "string" ? 1 : 2;
+            if (user) user_kind[name] |= kind; else if (domain.empty() || domain == "item") item(name, kind);
+            if (nullish || t.op >= PG_COND_CONTAINS) { out->push_back(t); continue; }
+            const json::Value& v = f.at("Value");
+            const bool listed = t.op == PG_COND_IN || t.op == PG_COND_NOT_IN;
+            if (v.type == json::Value::String && (v.str.compare(0, 5, "user.") == 0 || v.str.compare(0, 5, "item.") == 0)) {
+                const bool ru = v.str[0] == 'u';
+                t.rhs = ru ? (listed ? PG_COND_RHS_USER_LIST : PG_COND_RHS_USER) : PG_COND_RHS_ITEM;
+                t.rhs_name = keep(v.str.substr(5));
+                if (ru) user_kind[v.str.substr(5)] |= kind; else if (!listed) item(v.str.substr(5), kind);
+            } else if (listed) {
+                lists.emplace_back();
+                // (utils.ToStringArray drops empty strings from a []any; ToIntArray keeps every element)
+                for (const auto& x : v.arr) {
+                    if (type == "string" && x.type == json::Value::String && x.str.empty()) continue;
+                    long long i = 0;
+                    double d = 0.0;
+                    if (type == "float" || type == "int64") continue;                                       // (never read: the switches list string and int)
+                    if (!constant(x, type, name, &i, &d)) return false;
+                    lists.back().push_back(i);
+                }
+                t.list = lists.back().data();
+                t.n_list = (uint32_t)lists.back().size();
+            } else if (!constant(v, type, name, &t.i, &t.f)) {
+                return false;
+            }
+            out->push_back(t);
+        }
+        return true;
+    }
+};
+}  // namespace
+
+namespace recconf {
+// a FilterParams list that the builder accepts (what pg_cond_compile refuses shows at the first request; this names the rest at load)
+bool CheckFilterParams(const json::Value& params, bool strings, std::string* why) {
+    std::map<std::string, long long> dict;
+    CondBuild b;
+    b.dict = strings ? &dict : nullptr;
+    std::vector<pg_cond_term> terms;
+    if (!b.build(params, 0, &terms)) { *why = b.err; return false; }
+    if (terms.size() > PG_COND_MAX_TERMS) { *why = std::to_string(terms.size()) + " operators in one FilterParam (at most " + std::to_string(PG_COND_MAX_TERMS) + ")"; return false; }
+    return true;
+}
+bool CheckBoostScoreConf(const json::Value& sc, std::string* why) {
+    const auto& conds = sc.at("BoostScoreConditions").arr;
+    if (conds.size() > PG_COND_MAX_RULES) { *why = "more than " + std::to_string(PG_COND_MAX_RULES) + " BoostScoreConditions"; return false; }
+    for (const auto& c : conds) {
+        if (!CheckFilterParams(c.at("Conditions"), true, why)) return false;
+        // an empty Expression is a nil dereference in the reference when the condition matches (boost_score_sort.go:22-29,82)
+        if (c.s("Expression").empty()) { *why = "a BoostScoreCondition without an Expression"; return false; }
+        pg_expr* e = nullptr;
+        if (pg_expr_compile_govaluate(c.s("Expression").c_str(), &e) != PG_OK) { *why = pg_last_error(); return false; }
+        pg_expr_free(e);
+    }
+    return true;
+}
+}  // namespace recconf
+
 namespace recconf {
 static std::vector<std::string> str_list(const json::Value& v) {
     std::vector<std::string> out;
@@ -326,8 +452,32 @@ bool RecommendConfig::Parse(const std::string& text, RecommendConfig* out, std::
     for (const auto& sc : out->UserDefineConfs.at("pairec_gpu").at("Sorts").arr) {
         SortConfig c = parse_sort(sc);
         if (c.SortType == "DiversityRuleSort" && !parse_diversity(sc, &c)) return false;
+        if (c.SortType == "BoostScoreSort") {
+            c.BoostConf = sc;
+            std::string why;
+            if (!CheckBoostScoreConf(sc, &why)) {
+                if (err) *err = "pairec_gpu.Sorts: " + c.Name + ": BoostScoreSort: " + why;
+                return false;
+            }
+        }
         out->GpuSorts.push_back(c);
     }
+    for (const auto& fc : out->UserDefineConfs.at("pairec_gpu").at("Filters").arr) {
+        GpuFilterConfig c;
+        c.Name = fc.s("Name"); c.FilterType = fc.s("FilterType"); c.FeatureStore = fc.s("FeatureStore");
+        c.FilterParams = fc.at("FilterParams");
+        std::string why;
+        if (c.FilterType != "ItemStateFilter") why = "unknown FilterType \"" + c.FilterType + "\" (the device serves ItemStateFilter)";
+        else if (!c.FeatureStore.empty() && c.FeatureStore != "item_features")
+            why = "FeatureStore \"" + c.FeatureStore + "\" (the engine holds one store of item columns, \"item_features\")";
+        else CheckFilterParams(c.FilterParams, false, &why);
+        if (!why.empty()) {
+            if (err) *err = "pairec_gpu.Filters: " + c.Name + ": " + why;
+            return false;
+        }
+        out->GpuFilters.push_back(c);
+    }
+    for (const auto& kv : out->UserDefineConfs.at("pairec_gpu").at("FilterNames").obj) out->GpuFilterNames[kv.first] = str_list(kv.second);
     return true;
 }
 }  // namespace recconf
@@ -1477,6 +1627,166 @@ struct GpuDiversityRuleSort : sort::ISort {
     }
 };
 
+// BoostScoreSort (sort/boost_score_sort.go:73-104) through pg_boost_scores: the properties the conditions and expressions name
+// become candidate-aligned columns — strings dictionary-encoded per call together with the conditions' literals and the user's
+// string properties, numbers as int64 where every item holds an integer and fp64 otherwise — and the user's properties the user
+// slots.  An item without a named property, a property of the wrong kind, a list over the device's cap or a condition set
+// pg_cond_compile refuses leave Data untouched and return an error, which the caller ignores as it ignores every sort's error.
+namespace {
+// fills the user slots of a compiled set from User.Properties; false: a property that is neither a number nor an encodable string
+bool cond_user_slots(pg_cond* c, const module::User* user, CondBuild* b, uint64_t* vals, uint32_t* present, std::string* err) {
+    *present = 0;
+    for (int s = 0; s < pg_cond_num_user_slots(c); ++s) {
+        const std::string name = pg_cond_user_slot_name(c, s);
+        vals[s] = 0;
+        if (!user) continue;
+        const auto p = user->Properties.find(name);
+        if (p == user->Properties.end()) continue;
+        const json::Value& v = p->second;
+        const bool as_string = (b->user_kind[name] & 1) != 0;
+        if (as_string && b->dict) {
+            const long long id = b->code(v.type == json::Value::String ? v.str : v.type == json::Value::Number ? json::NumToString(v.num) : std::string());
+            memcpy(&vals[s], &id, 8);
+        } else if (v.type == json::Value::Number || (v.type == json::Value::String && !v.str.empty())) {
+            if (pg_cond_user_slot_is_float(c, s)) {
+                const double d = ToFloat(v, 0.0);
+                memcpy(&vals[s], &d, 8);
+            } else {
+                long long i = 0;
+                double d = 0.0;
+                if (!b->constant(v, "int", name, &i, &d)) { if (err) *err = "user property \"" + name + "\" is not an integer"; return false; }
+                memcpy(&vals[s], &i, 8);
+            }
+        } else {
+            if (err) *err = "user property \"" + name + "\" is not a number";
+            return false;
+        }
+        *present |= 1u << s;
+    }
+    return true;
+}
+}  // namespace
+
+struct GpuBoostScoreSort : sort::ISort {
+    Engine* e;
+    json::Value conf;
+    GpuBoostScoreSort(Engine* eng, json::Value c) : e(eng), conf(std::move(c)) {}
+    bool Sort(sort::SortData* d, std::string* err) override {
+        const size_t n = d->Data.size();
+        const auto& conds = conf.at("BoostScoreConditions").arr;
+        if (n == 0 || conds.empty()) return true;
+        auto fail = [&](const std::string& what) { if (err) *err = "BoostScoreSort: " + what; return false; };
+        if (n > PG_TRIM_MAX_CAP) return fail(std::to_string(n) + " items (the device serves up to " + std::to_string(PG_TRIM_MAX_CAP) + ")");
+        std::map<std::string, long long> dict;
+        CondBuild b;
+        b.dict = &dict;
+        std::vector<std::vector<pg_cond_term>> terms(conds.size());
+        std::vector<pg_cond_rule> rules(conds.size());
+        for (size_t r = 0; r < conds.size(); ++r) {
+            if (!b.build(conds[r].at("Conditions"), 0, &terms[r])) return fail(b.err);
+            rules[r].terms = terms[r].data();
+            rules[r].n_terms = (uint32_t)terms[r].size();
+            rules[r].expression = b.keep(conds[r].s("Expression"));
+            pg_expr* x = nullptr;                                                  // the expression's variables are columns too
+            if (pg_expr_compile_govaluate(rules[r].expression, &x) != PG_OK) return fail(pg_last_error());
+            for (int v = 0; v < pg_expr_num_vars(x); ++v)
+                if (strcmp(pg_expr_var_name(x, v), "score") != 0) b.item(pg_expr_var_name(x, v), 2);
+            pg_expr_free(x);
+        }
+        // the columns
+        const size_t nc = b.item_names.size();
+        std::vector<std::vector<long long>> ints(nc);
+        std::vector<std::vector<double>> floats(nc);
+        std::vector<pg_cond_col> cols(nc);
+        std::vector<const void*> col_ptr(nc);
+        for (size_t c = 0; c < nc; ++c) {
+            const std::string& name = b.item_names[c];
+            const int kind = b.item_kind[name];
+            if ((kind & 1) && (kind & 2)) return fail("property \"" + name + "\" is read both as a string and as a number");
+            bool whole = true;
+            for (size_t i = 0; i < n; ++i) {
+                const auto p = d->Data[i]->Properties.find(name);
+                if (p == d->Data[i]->Properties.end()) return fail("item " + d->Data[i]->Id + " has no property \"" + name + "\"");
+                if (kind & 1) continue;
+                if (p->second.type != json::Value::Number) return fail("item " + d->Data[i]->Id + ": property \"" + name + "\" is not a number");
+                whole = whole && (p->second.is_int || (p->second.num == std::floor(p->second.num) && std::fabs(p->second.num) < 9e15));
+            }
+            cols[c].name = name.c_str();
+            if ((kind & 1) || whole) {
+                ints[c].resize(n);
+                for (size_t i = 0; i < n; ++i) {
+                    const json::Value& v = d->Data[i]->Properties.find(name)->second;
+                    ints[c][i] = (kind & 1) ? b.code(feature::ItemStringProperty(*d->Data[i], name)) : (v.is_int ? v.i : (long long)v.num);
+                }
+                cols[c].dtype = PG_F_I64;
+                col_ptr[c] = ints[c].data();
+            } else {
+                floats[c].resize(n);
+                for (size_t i = 0; i < n; ++i) floats[c][i] = d->Data[i]->Properties.find(name)->second.num;
+                cols[c].dtype = PG_F_F64;
+                col_ptr[c] = floats[c].data();
+            }
+        }
+        pg_cond* c = nullptr;
+        if (pg_cond_compile(rules.data(), (uint32_t)rules.size(), cols.data(), (uint32_t)nc, 1, &c) != PG_OK) return fail(pg_last_error());
+        uint64_t uv[PG_COND_MAX_SLOTS] = {0};
+        uint32_t present = 0;
+        std::vector<double> score(n), out(n);
+        for (size_t i = 0; i < n; ++i) score[i] = d->Data[i]->Score;
+        std::string uerr;
+        const bool ok = cond_user_slots(c, d->User, &b, uv, &present, &uerr) &&
+                        pg_boost_scores(e->ctx, c, conf.at("BoostScoreConditionsFilterAll").b ? 1u : 0u, (uint32_t)n, nullptr, col_ptr.data(), uv, present,
+                                        score.data(), out.data(), nullptr) == PG_OK;
+        const std::string why = ok ? std::string() : (uerr.empty() ? pg_err("pg_boost_scores") : uerr);
+        pg_cond_free(c);
+        if (!ok) return fail(why);
+        for (size_t i = 0; i < n; ++i) d->Data[i]->Score = out[i];
+        return true;
+    }
+};
+
+// ItemStateFilter (filter/item_state_filter.go:47-57; the DAO's keep, module/item_state_filter_hologres_dao.go:313-357) through
+// pg_item_state_filter over the engine's feature columns: an item whose id the table does not know is the item absent from the
+// state table.  The position rides in the score plane, so the kept items come back by position, in order.
+bool item_state_filter(Engine* self, const recconf::GpuFilterConfig& conf, const module::User* user, std::vector<module::ItemPtr>* items, std::string* err) {
+    const size_t n = items->size();
+    if (n == 0) return true;
+    auto fail = [&](const std::string& what) { if (err) *err = "ItemStateFilter " + conf.Name + ": " + what; return false; };
+    if (n > PG_TRIM_MAX_CAP) return fail(std::to_string(n) + " items (the device serves up to " + std::to_string(PG_TRIM_MAX_CAP) + ")");
+    if (!self->feats) return fail("the engine has no feature columns");
+    CondBuild b;
+    std::vector<pg_cond_term> terms;
+    if (!b.build(conf.FilterParams, 0, &terms)) return fail(b.err);
+    std::vector<pg_cond_col> cols(b.item_names.size());
+    for (size_t c = 0; c < cols.size(); ++c) {
+        if (pg_features_column_index(self->feats, b.item_names[c].c_str()) < 0) return fail("\"" + b.item_names[c] + "\" is not a feature column");
+        cols[c] = pg_cond_col{b.item_names[c].c_str(), PG_F_I32};
+    }
+    pg_cond_rule rule{terms.data(), (uint32_t)terms.size(), nullptr};
+    pg_cond* c = nullptr;
+    if (pg_cond_compile(&rule, 1, cols.data(), (uint32_t)cols.size(), 0, &c) != PG_OK) return fail(pg_last_error());
+    std::vector<uint64_t> rows(n), out_rows(n);
+    std::vector<double> pos(n), out_pos(n);
+    for (size_t i = 0; i < n; ++i) {
+        uint32_t row;
+        rows[i] = self->RowOfId((*items)[i]->Id, &row) ? row : self->table_rows;
+        pos[i] = (double)i;
+    }
+    uint64_t uv[PG_COND_MAX_SLOTS] = {0};
+    uint32_t present = 0, count = 0;
+    std::string uerr;
+    const bool ok = cond_user_slots(c, user, &b, uv, &present, &uerr) &&
+                    pg_item_state_filter(self->ctx, c, self->feats, (uint32_t)n, rows.data(), pos.data(), nullptr, uv, present, out_rows.data(), out_pos.data(), nullptr,
+                                         &count) == PG_OK;
+    const std::string why = ok ? std::string() : (uerr.empty() ? pg_err("pg_item_state_filter") : uerr);
+    pg_cond_free(c);
+    if (!ok) return fail(why);
+    std::vector<module::ItemPtr> kept(count);
+    for (uint32_t k = 0; k < count; ++k) kept[k] = (*items)[(size_t)out_pos[k]];
+    items->swap(kept);
+    return true;
+}
+
 struct GpuSSDSort : sort::ISort {                        // sort/ssd_sort.go:110-343 (embedding table = item table)
     Engine* e;
     recconf::SSDSortConfig conf;
@@ -2034,8 +2344,10 @@ Engine* Engine::Create(const std::string& config_json, std::string* err) {
         else if (sc.SortType == "ItemRankScore") e->sorts.RegisterSort(sc.Name, std::make_shared<GpuItemRankScoreSort>(e.get()), nullptr);
         else if (sc.SortType == "ItemScore") e->sorts.RegisterSort(sc.Name, std::make_shared<GpuItemScoreSort>(e.get()), nullptr);
         else if (sc.SortType == "DiversityRuleSort") e->sorts.RegisterSort(sc.Name, std::make_shared<GpuDiversityRuleSort>(e.get(), sc.DiversityConf), nullptr);
+        else if (sc.SortType == "BoostScoreSort") e->sorts.RegisterSort(sc.Name, std::make_shared<GpuBoostScoreSort>(e.get(), sc.BoostConf), nullptr);
         else { if (err) *err = "pairec_gpu.Sorts: unknown SortType " + sc.SortType; return nullptr; }
     }
+    for (const auto& fc : e->config.GpuFilters) e->gpu_filters[fc.Name] = fc;
     // algorithms by name (the shim's start hook does the same with algorithm.RegisterAlgorithm)
     bool first_dnn = true, first_fm = true;
     for (const auto& a : g.at("Algorithms").arr) {
@@ -2095,6 +2407,10 @@ Engine* Engine::Create(const std::string& config_json, std::string* err) {
     return e.release();
 }
 
+bool Engine::ItemStateFilter(const recconf::GpuFilterConfig& conf, const module::User* user, std::vector<module::ItemPtr>* items, std::string* err) {
+    return item_state_filter(this, conf, user, items, err);
+}
+
 bool Engine::Recommend(const std::string& uid, int size, const std::string& scene,
                        std::vector<module::ItemPtr>* out, std::string* err) {
     return Recommend(uid, size, scene, json::Value(), out, err);
@@ -2141,6 +2457,15 @@ bool Engine::Recommend(const std::string& uid, int size, const std::string& scen
                 items.insert(items.end(), got.begin(), got.end());
             }
     items = filter::UniqueFilter(items);
+    {   // FilterService.Filter (user_recommend.go:105-127): the scene's device filters, in order; an error leaves the items as they are
+        auto fn = config.GpuFilterNames.find(scene);
+        if (fn != config.GpuFilterNames.end())
+            for (const auto& name : fn->second) {
+                auto f = gpu_filters.find(name);
+                std::string ferr;
+                if (f != gpu_filters.end()) ItemStateFilter(f->second, &user, &items, &ferr);
+            }
+    }
     {   // FeatureService.LoadFeatures (user_recommend.go:129; feature_service.go:77-131): "features.scene.name" of the experiment first
         std::string fscene = ctx.HasExperiment() ? ctx.ExperimentParamsJson.s("features.scene.name") : "";
         if (fscene.empty()) fscene = scene;
@@ -2444,6 +2769,57 @@ const char* ph_engine_sort(void* h, const char* sort_name, const char* items_jso
     for (size_t i = 0; i < sd.Data.size(); ++i) { if (i) o += ","; json::Escape(sd.Data[i]->Id, &o); }
     o += "]";
     return o.c_str();
+}
+
+// one registered sort over caller-made items, as ph_engine_sort, with the user's properties (a JSON object or NULL); the answer
+// carries the scores: {"items":[{"item_id","score",…}]}
+const char* ph_engine_sort_scored(void* h, const char* sort_name, const char* items_json, const char* user_json, int size) {
+    if (!h) { g_ph_err = "ph_engine_sort_scored: NULL engine"; return nullptr; }
+    Engine* e = (Engine*)h;
+    json::Value root, uroot;
+    std::string err;
+    const std::string text = items_json ? items_json : "", utext = user_json ? user_json : "{}";
+    if (!json::Parser(text).Parse(&root, &err) || !json::Parser(utext).Parse(&uroot, &err)) { g_ph_err = err; return nullptr; }
+    auto s = e->sorts.Get(sort_name ? sort_name : "");
+    if (!s) { g_ph_err = std::string("Sort:not find, name:") + (sort_name ? sort_name : ""); return nullptr; }
+    sort::SortData sd;
+    context::RecommendContext ctx;
+    module::User user("u");
+    for (const auto& kv : uroot.obj) user.Properties[kv.first] = kv.second;
+    ctx.Size = size;
+    sd.Context = &ctx;
+    sd.User = &user;
+    for (const auto& it : root.arr) {
+        auto item = std::make_shared<module::Item>(it.s("id"));
+        item->Score = it.d("score");
+        item->Properties = it.at("properties").obj;
+        sd.Data.push_back(item);
+    }
+    if (!s->Sort(&sd, &err)) { g_ph_err = err; return nullptr; }
+    return items_to_json(sd.Data);
+}
+
+// one pairec_gpu.Filters entry over caller-made items [{"id","score"}] → the kept items, in order
+const char* ph_engine_filter(void* h, const char* filter_name, const char* items_json, const char* user_json) {
+    if (!h) { g_ph_err = "ph_engine_filter: NULL engine"; return nullptr; }
+    Engine* e = (Engine*)h;
+    json::Value root, uroot;
+    std::string err;
+    const std::string text = items_json ? items_json : "", utext = user_json ? user_json : "{}";
+    if (!json::Parser(text).Parse(&root, &err) || !json::Parser(utext).Parse(&uroot, &err)) { g_ph_err = err; return nullptr; }
+    auto f = e->gpu_filters.find(filter_name ? filter_name : "");
+    if (f == e->gpu_filters.end()) { g_ph_err = std::string("Filter:not find, name:") + (filter_name ? filter_name : ""); return nullptr; }
+    module::User user("u");
+    for (const auto& kv : uroot.obj) user.Properties[kv.first] = kv.second;
+    std::vector<module::ItemPtr> items;
+    for (const auto& it : root.arr) {
+        auto item = std::make_shared<module::Item>(it.s("id"));
+        item->Score = it.d("score");
+        items.push_back(item);
+    }
+    VersionLock::Read generation_guard(e->version);
+    if (!e->ItemStateFilter(f->second, &user, &items, &err)) { g_ph_err = err; return nullptr; }
+    return items_to_json(items);
 }
 
 const char* ph_recommend(void* h, const char* uid, int size, const char* scene) {

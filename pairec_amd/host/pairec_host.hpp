@@ -150,6 +150,13 @@ struct SortConfig {                        // recconf.go:820-838: Name, SortType
     DPPSortConfig DPPConf;
     SSDSortConfig SSDConf;
     DiversityRuleSortConfig DiversityConf; // pairec_gpu.Sorts entries of SortType DiversityRuleSort only
+    json::Value BoostConf;                 // pairec_gpu.Sorts entries of SortType BoostScoreSort only: the entry itself (BoostScoreConditions[]
+                                           // {Conditions, Expression}, BoostScoreConditionsFilterAll: recconf.go:843-844,892-895)
+};
+// pairec_gpu.Filters: FilterType "ItemStateFilter" (filter/item_state_filter.go:47-57) over the engine's feature columns
+struct GpuFilterConfig {
+    std::string Name, FilterType, FeatureStore;
+    json::Value FilterParams;              // [FilterParamConfig] (recconf.go:884-891)
 };
 struct FeatureConfig {                      // recconf.go:256-265
     std::string FeatureType, FeatureName, FeatureSource, FeatureValue, FeatureStore, Normalizer, Expression;
@@ -168,6 +175,8 @@ struct RecommendConfig {
     std::vector<SortConfig> SortConfs;                                       // recconf.go:86
     std::vector<RecallConfig> GpuRecalls;                                    // UserDefineConfs.pairec_gpu.Recalls
     std::vector<SortConfig> GpuSorts;                                        // UserDefineConfs.pairec_gpu.Sorts
+    std::vector<GpuFilterConfig> GpuFilters;                                 // UserDefineConfs.pairec_gpu.Filters
+    std::map<std::string, std::vector<std::string>> GpuFilterNames;           // UserDefineConfs.pairec_gpu.FilterNames, by scene (recconf.go FilterNames)
     json::Value UserDefineConfs;                                              // recconf.go:92
     static bool Parse(const std::string& text, RecommendConfig* out, std::string* err);
 };
@@ -462,6 +471,10 @@ public:
         return it == algo_precision.end() ? fallback : it->second;
     }
     pg_features* feats = nullptr;                       // item "context features" as device columns (EasyRec request flavour)
+    // pairec_gpu.Filters by name; FilterNames[scene] run between UniqueFilter and the feature transforms (user_recommend.go:105-129).
+    // A filter that cannot be served leaves the items as they are and reports an error, which Recommend ignores like a sort's.
+    std::map<std::string, recconf::GpuFilterConfig> gpu_filters;
+    bool ItemStateFilter(const recconf::GpuFilterConfig& conf, const module::User* user, std::vector<module::ItemPtr>* items, std::string* err);
     std::map<std::string, std::vector<int32_t>> user_fields;   // uid → dictionary-encoded user categorical features
     pg_model* fm2t = nullptr;                           // FM + two-tower model: rank algorithm "fm2t", and the vector model of the online recall
     pg_table* item_emb = nullptr;                       // … and the item-tower outputs it searches
