@@ -664,7 +664,7 @@ def pow_last_ulp_explains(evaluate, device_value) -> bool:
 def go_pow(x: float, y: float) -> float:
     """math.Pow (Go stdlib `math/pow.go`, go 1.24 per reference go.mod:3).  Go applies the INTEGER part of the exponent by
     repeated squaring of Frexp(x)'s mantissa with the binary exponent carried on the side (exact where the products are, e.g.
-    400^4); integer-valued exponents follow that loop here bit for bit.  Fractional exponents (Go: Exp(yf Log(x)) times the
+    400^4); integer-valued exponents follow that loop here bit for bit, and y = +-0.5 takes Go's Sqrt case.  Other fractional exponents (Go: Exp(yf Log(x)) times the
     integer part, with a platform-specific Exp on amd64) and the special cases are mapped onto C pow(): within 1-2 ulp of Go,
     so fused scores with a fractional `^` are compared with rel 1e-14."""
     ay = abs(y)
@@ -695,6 +695,11 @@ def go_pow(x: float, y: float) -> float:
             return math.ldexp(a1, ae)
         except OverflowError:
             return math.copysign(math.inf, a1)
+    if ay == 0.5 and math.isfinite(x) and x != 0.0:
+        # pow.go's `case y == 0.5: return Sqrt(x)` / `case y == -0.5: return 1 / Sqrt(x)`: they stand behind the y == 0 || x == 1,
+        # y == 1, NaN, x == 0, Inf(y) and Inf(x) cases, so they see a finite non-zero x only; Sqrt of a negative x is NaN
+        r = math.sqrt(x) if x > 0.0 else math.nan
+        return r if y > 0.0 else 1.0 / r
     try:
         return math.pow(x, y)
     except OverflowError:

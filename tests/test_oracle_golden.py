@@ -540,6 +540,22 @@ def test_expr_pow_follows_gos_integer_power_loop():
     assert o.expr_eval(o.expr_parse("4e2^4e0%1000"), lambda name: None) == 0.0
 
 
+def test_expr_pow_takes_gos_sqrt_case_for_half_exponents():
+    """math.Pow(x, 0.5) = Sqrt(x) and Pow(x, -0.5) = 1 / Sqrt(x) for a finite non-zero x (math/pow.go, behind the zero, NaN and
+    infinity cases).  The eight pairs are those of the evaluator's hostile grid where a libm pow is an ulp away from the square
+    root's form; the expected values come from math.sqrt."""
+    big, up, down = 2.0 ** 63, 1.0 + 2.0 ** -52, 1.0 - 2.0 ** -53
+    for x, y in ((0.5, -0.5), (2.0, -0.5), (3.0, -0.5), (7.0, -0.5), (big, -0.5), (up, -0.5), (down, 0.5), (down, -0.5)):
+        want = math.sqrt(x) if y > 0 else 1.0 / math.sqrt(x)
+        assert o.go_pow(x, y).hex() == want.hex(), (x, y)
+        assert o.expr_eval(o.expr_parse("${x}^${y}"), {"x": x, "y": y}.get).hex() == want.hex(), (x, y)
+    # only a finite non-zero x reaches the case: the zero, infinity and NaN cases in front of it keep their answers
+    assert math.isnan(o.go_pow(-4.0, 0.5)) and math.isnan(o.go_pow(-4.0, -0.5)) and math.isnan(o.go_pow(math.nan, 0.5))
+    assert o.go_pow(0.0, -0.5) == math.inf and o.go_pow(-0.0, -0.5) == math.inf
+    assert o.go_pow(-0.0, 0.5).hex() == (0.0).hex() and o.go_pow(math.inf, -0.5) == 0.0
+    assert o.go_pow(-math.inf, 0.5) == math.inf and o.go_pow(-math.inf, -0.5) == 0.0 and o.go_pow(1.0, -0.5) == 1.0
+
+
 def test_pow_last_ulp_classifier():
     """oracle.pow_last_ulp_explains (the soaks' classifier): a power inside the exponent of a negative base — the inner pow's last ulp
     decides whether the outer exponent is an integer, i.e. a number or NaN — is explained; an arbitrary wrong value is not."""
