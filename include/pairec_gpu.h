@@ -848,6 +848,82 @@ int pg_candidates_trim_dev(pg_ctx* ctx, const pg_trim_rule* rules, uint32_t n_ru
                            double* d_out_score, uint8_t* d_out_source, double* d_out_planes_f64, uint32_t* d_out_source_mask,
                            float* d_out_planes_f32, uint32_t* d_out_count);
 
+/* SnakeFilter and CompletelyFairCountFilter on the device (csrc/blend.hip): the two reference filters that sit in
+ * the trim's slot, between UniqueFilter and RankService.Rank (service/user_recommend.go:105-137), and interleave the recalls
+ * instead of cutting them.  SnakeFilter (filter/snake_filter.go:173-241) orders every configured recall by its own score and
+ * deals them out round after round by weight; an item reached through a recall other than its first takes that recall's name
+ * and score (:83-88) — the one filter that consumes RecallScores, i.e. the fan-in's per-recall score planes and source mask.
+ * CompletelyFairCountFilter (filter/completely_fair_count_filter.go:34-94) sorts the merged list by score and deals the recalls
+ * out one item at a time.
+ *   In        pg_fanin_merge_dev's outputs as they are, in pg_candidates_trim_dev's argument order and optionality: nq <= 256
+ *             requests of cap in [1, PG_BLEND_MAX_CAP] entries; d_rows, d_score, optional d_source, d_count, d_planes_f64
+ *             [n_f64][nq][cap] (planes 0.. are the per-recall scores by source index), d_source_mask, d_planes_f32; at most
+ *             PG_BLEND_MAX_PLANES planes each.  An entry is padding if its row is UINT64_MAX, its position is >= d_count[q] or
+ *             its source is >= PG_BLEND_MAX_SOURCES; padding may sit anywhere, is dropped and never counted.  Without d_source
+ *             every real entry belongs to one source (SNAKE: the single entry's).
+ *   Conf      host values: mode, retain_num, and for the SNAKE modes n_entries <= PG_BLEND_MAX_SOURCES of {source, weight} in
+ *             AdjustCountConfs order (source = the fan-in source index RecallName resolves to).  FAIR ignores the entries.
+ *   Answer    DEFINED bit for bit.  "Score order" is pg_sort_scores_dev's: descending, -0.0 equals +0.0, NaN last, ties keep
+ *             input position (the reference sorts unstably: only the order among equal keys is being fixed).
+ *             SNAKE   entry i names source s_i; its list holds the real entries e with source[e] == s_i, key d_score[e]
+ *                     (:63-67), and — with a mask — those with popcount(mask[e]) > 1, bit s_i of mask[e] set and source[e] !=
+ *                     s_i, key planes_f64[s_i][e] (:188-200; the reference's len(RecallScores) > 1), each list in score order
+ *                     of its key.  Entries of sources no entry names are dropped.  While size < retain_num a round runs
+ *                     (:212-231): entry i = 0 .. n_entries - 1 advances through its list from its cursor and stops after
+ *                     weight[i] slots (Next, :76-109); an entry nobody took yet is picked and costs a slot, one already taken
+ *                     costs no slot under PG_BLEND_SNAKE_REFILL and one under PG_BLEND_SNAKE_SKIP, the cursor advances either
+ *                     way; size += the round's picks; a round without a pick ends the walk (under SKIP even where fresh
+ *                     entries lie further down: the reference's quirk, kept).  The output is the picks in pick order cut to
+ *                     retain_num (:229-231).  A pick carries its row, score = its key in the picking list, source = s_i and
+ *                     every carried plane, mask and fp32 plane unchanged.
+ *             FAIR    retain = min(retain_num, the real entries); they are put in score order of d_score and grouped by
+ *                     source, the names in order of first appearance (:59-65); while count < retain, slot count % len(names)
+ *                     gives its next entry, and a name that has given its last entry is replaced by the last name, the list
+ *                     shrinking by one (:80-83).  Scores and sources are unchanged.
+ *             d_out_count[q] = the entries kept; behind them padding as the trim's: row UINT64_MAX, score -inf, source 0xFF,
+ *             fp64 planes the quiet NaN 0x7FF8000000000000, mask 0, fp32 planes 0.  Outputs are [nq][out_cap] (planes
+ *             [n][nq][out_cap]) with out_cap from pg_blend_out_cap; an output is required exactly where its input is given;
+ *             outputs must not overlap inputs.  No value meets arithmetic: doubles and floats travel as bits.
+ *   Refused   on the host, the context left usable (PG_ERR_INVALID): an unknown mode; retain_num == 0; SNAKE with no entries, a
+ *             source >= PG_BLEND_MAX_SOURCES, a source named twice (the reference's map keeps only the later iterator) or every
+ *             weight 0 (the reference divides 0 by 0 for its counts; one weight of 0 is legal: that recall never gives, and a
+ *             weight above the list's length drains the list); a mask without the planes it needs (SNAKE: n_f64 must exceed
+ *             every named source); SNAKE naming more than one source without d_source.  n_entries > PG_BLEND_MAX_SOURCES and
+ *             cap outside [1, PG_BLEND_MAX_CAP] are PG_ERR_UNSUPPORTED.
+ *   Width     pg_blend_out_cap: a pure host function (no context, no device) that validates the conf and returns out_cap =
+ *             min(cap, retain_num).
+ *   Host      pg_candidates_blend_host: the same answer computed on the host over host arrays (no context, no device) — the
+ *             statement the device path is tested against, and the path of a host that holds the merged list already.
+ *   Kernel    one workgroup per request.  FAIR: the trim's score sort, then counts and first appearances per source, a plan of
+ *             at most 8 phases between exhaustions by one lane, and every entry's output position from its rank within its
+ *             source — no loop over retain.  SNAKE: one sorted order per entry (keys built per entry, non-members NaN), each
+ *             list compacted to its members in order, then one wave walks (round, entry) steps 64 list entries at a time
+ *             against a bitmap of taken positions in LDS and records the picks, which the whole workgroup gathers.  Every
+ *             output element is written exactly once.  The snake_filter debug property (:89-99,232-236) is not built.
+ *   Stream    the sorts and the launches on the context's stream, no synchronisation (as pg_candidates_trim_dev). */
+#define PG_BLEND_SNAKE_REFILL 0   /* SnakeType default, REFILL_ON_DUPLICATE */
+#define PG_BLEND_SNAKE_SKIP   1   /* SnakeType "SKIP_ON_DUPLICATE" */
+#define PG_BLEND_FAIR         2   /* CompletelyFairCountFilter */
+#define PG_BLEND_MAX_SOURCES  8   /* == PG_FANIN_MAX_SOURCES */
+#define PG_BLEND_MAX_PLANES   8
+#define PG_BLEND_MAX_CAP      16384   /* == PG_FANIN_MAX_CAP */
+typedef struct {
+    uint32_t mode, retain_num, n_entries;          /* n_entries: SNAKE only (AdjustCountConfs, in config order) */
+    uint8_t  source[PG_BLEND_MAX_SOURCES];         /* the fan-in source index entry i names */
+    uint32_t weight[PG_BLEND_MAX_SOURCES];
+} pg_blend_conf;
+int pg_blend_out_cap(const pg_blend_conf* conf, uint32_t cap, uint32_t* out_cap);
+int pg_candidates_blend_dev(pg_ctx* ctx, const pg_blend_conf* conf, uint32_t nq, uint32_t cap, const uint64_t* d_rows,
+                            const double* d_score, const uint8_t* d_source, const uint32_t* d_count, const double* d_planes_f64,
+                            uint32_t n_f64, const uint32_t* d_source_mask, const float* d_planes_f32, uint32_t n_f32, uint64_t* d_out_rows,
+                            double* d_out_score, uint8_t* d_out_source, double* d_out_planes_f64, uint32_t* d_out_source_mask,
+                            float* d_out_planes_f32, uint32_t* d_out_count);
+int pg_candidates_blend_host(const pg_blend_conf* conf, uint32_t nq, uint32_t cap, const uint64_t* rows, const double* score,
+                             const uint8_t* source, const uint32_t* count, const double* planes_f64, uint32_t n_f64,
+                             const uint32_t* source_mask, const float* planes_f32, uint32_t n_f32, uint64_t* out_rows, double* out_score,
+                             uint8_t* out_source, double* out_planes_f64, uint32_t* out_source_mask, float* out_planes_f32,
+                             uint32_t* out_count);
+
 /* Refresh: bring an existing index back to its table's current rows KEEPING ITS CENTROIDS — cheap when few
  * rows were written, several times cheaper than pg_index_build when all of them were (nothing is trained).  Nothing changes
  * until it is called: a written table still makes its index stale.

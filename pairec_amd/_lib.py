@@ -49,6 +49,7 @@ EXPORTS = [
     "pg_simtable_create", "pg_simtable_upload", "pg_simtable_info", "pg_simtable_destroy", "pg_cf_recall", "pg_cf_recall_dev",
     "pg_fanin_merge_dev", "pg_recommend_candidates_dnn3_dev",
     "pg_trim_out_cap", "pg_candidates_trim_dev", "pg_recommend_cascade_dnn3_dev",
+    "pg_blend_out_cap", "pg_candidates_blend_dev", "pg_candidates_blend_host",
     "pg_diversity_rules_host", "pg_diversity_rules_dev", "pg_diversity_rules_features_dev", "pg_diversity_rules",
     "pg_expr_compile_govaluate", "pg_expr_eval_host",
     "pg_cond_compile", "pg_cond_free", "pg_cond_num_rules", "pg_cond_num_user_slots", "pg_cond_user_slot_name",
@@ -116,6 +117,11 @@ class PgFaninSource(C.Structure):
 
 class PgTrimRule(C.Structure):
     _fields_ = [("source", C.c_uint8), ("type", C.c_uint8), ("count", C.c_uint32)]
+
+
+class PgBlendConf(C.Structure):
+    _fields_ = [("mode", C.c_uint32), ("retain_num", C.c_uint32), ("n_entries", C.c_uint32), ("source", C.c_uint8 * 8),
+                ("weight", C.c_uint32 * 8)]
 
 
 class PgDivRule(C.Structure):
@@ -276,6 +282,9 @@ def load():
         "pg_recommend_candidates_dnn3_dev": [vp, vp, vp, vp, C.c_char_p, vp, u32, u32, vp, vp, vp, vp, vp, vp],
         "pg_trim_out_cap": [P(PgTrimRule), u32, u32, P(C.c_uint32)],
         "pg_candidates_trim_dev": [vp, P(PgTrimRule), u32, u32, u32, vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp],
+        "pg_blend_out_cap": [P(PgBlendConf), u32, P(C.c_uint32)],
+        "pg_candidates_blend_dev": [vp, P(PgBlendConf), u32, u32, vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp],
+        "pg_candidates_blend_host": [P(PgBlendConf), u32, u32, vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp],
         "pg_recommend_cascade_dnn3_dev": [vp, vp, vp, vp, C.c_char_p, vp, vp, C.c_char_p, vp, u32, u32, vp, vp, vp, vp, u32,
                                           vp, vp, vp, vp, vp, vp, vp],
         "pg_diversity_rules_host": [P(PgDivConfig), u32, u32, vp, vp, vp, vp, vp],

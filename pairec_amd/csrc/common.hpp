@@ -267,7 +267,8 @@ struct pg_ctx {
     //   19 cf.hip: status and counts, staged offsets and lists, the global tier's tables, the items to order, the over-fetched answer
     //   23 diversity.hip: keys, window counts and tuple tables   24 diversity.hip: the dimension planes gathered from a feature store
     //   25 cond.hip: the one-request entries' staging (pg_item_state_filter, pg_boost_scores: inputs, outputs, the temporary store)
-    pg::Scratch scratch[26];
+    //   26 blend.hip: segment offsets, per-entry keys and orders, the compacted lists and the pick records
+    pg::Scratch scratch[27];
     std::mutex pool_mu;          // guards pipe_free
     std::vector<pg::PipeRun*> pipe_free;     // per-batch status blocks / events of the device-resident pipelines
     std::map<const void*, size_t> dyn_lds;   // kernels whose dynamic-LDS limit was raised on this device

@@ -119,6 +119,13 @@ int candidates_trim_locked(pg_ctx* ctx, const pg_trim_rule* rules, uint32_t n_ru
                            const double* d_planes_f64, uint32_t n_f64, const uint32_t* d_source_mask, const float* d_planes_f32, uint32_t n_f32,
                            const uint32_t* d_order, uint64_t* d_out_rows, double* d_out_score, uint8_t* d_out_source, double* d_out_planes_f64,
                            uint32_t* d_out_source_mask, float* d_out_planes_f32, uint32_t* d_out_count);
+// blend.hip: SnakeFilter / CompletelyFairCountFilter over the same arrays (arguments as pg_candidates_blend_dev, checked by the
+// caller; out_cap from pg_blend_out_cap).  Caller holds ctx->mu; no synchronisation.
+int candidates_blend_locked(pg_ctx* ctx, const pg_blend_conf* conf, uint32_t nq, uint32_t cap, uint32_t out_cap, const uint64_t* d_rows,
+                            const double* d_score, const uint8_t* d_source, const uint32_t* d_count, const double* d_planes_f64,
+                            uint32_t n_f64, const uint32_t* d_source_mask, const float* d_planes_f32, uint32_t n_f32, uint64_t* d_out_rows,
+                            double* d_out_score, uint8_t* d_out_source, double* d_out_planes_f64, uint32_t* d_out_source_mask,
+                            float* d_out_planes_f32, uint32_t* d_out_count);
 int rerank_select_locked(pg_ctx* ctx, const RecommendCall& c, uint32_t q0, uint32_t nq, const PostScratch& ps);
 int rerank_run_locked(pg_ctx* ctx, const RecommendCall& c, uint32_t q0, uint32_t nq, const PostScratch& ps);
 

@@ -53,6 +53,70 @@ def trim_out_cap(rules, cap: int) -> int:
     return out.value
 
 
+BLEND_SNAKE_REFILL, BLEND_SNAKE_SKIP, BLEND_FAIR = 0, 1, 2
+
+
+def _blend_conf(conf):
+    """conf = (mode, retain_num, [(source, weight)]) → pg_blend_conf (entries the struct cannot hold are left to the library's
+    n_entries check)"""
+    mode, retain_num, entries = conf
+    entries = list(entries or ())
+    c = _lib.PgBlendConf(int(mode), int(retain_num), len(entries))
+    for i, (source, weight) in enumerate(entries[:8]):
+        c.source[i] = int(source)
+        c.weight[i] = int(weight)
+    return c
+
+
+def blend_out_cap(conf, cap: int) -> int:
+    """pg_blend_out_cap: conf = (BLEND_SNAKE_REFILL | BLEND_SNAKE_SKIP | BLEND_FAIR, retain_num, [(source, weight)]) →
+    min(cap, retain_num); raises PgError for a conf the blend refuses.  A host function: no context, no device."""
+    out = C.c_uint32()
+    _lib.check(_lib.load().pg_blend_out_cap(C.byref(_blend_conf(conf)), int(cap), C.byref(out)))
+    return out.value
+
+
+def _blend_arrays(who, conf, rows, score, source, count, planes_f64, source_mask, planes_f32):
+    """the blend's host arrays, checked and made contiguous → (nq, cap, out_cap, [rows, score, source, count, planes_f64,
+    source_mask, planes_f32], outs, n64, n32)"""
+    r = np.ascontiguousarray(rows, dtype=np.uint64)
+    sc = np.ascontiguousarray(score, dtype=np.float64)
+    if r.ndim != 2 or sc.shape != r.shape:
+        raise ValueError("%s: rows and score are [nq][cap]" % who)
+    nq, cap = r.shape
+    out_cap = blend_out_cap(conf, cap)
+    opt = [None if source is None else np.ascontiguousarray(source, dtype=np.uint8),
+           None if count is None else np.ascontiguousarray(count, dtype=np.uint32),
+           None if planes_f64 is None else np.ascontiguousarray(planes_f64, dtype=np.float64),
+           None if source_mask is None else np.ascontiguousarray(source_mask, dtype=np.uint32),
+           None if planes_f32 is None else np.ascontiguousarray(planes_f32, dtype=np.float32)]
+    for a, shape in ((opt[0], (nq, cap)), (opt[1], (nq,)), (opt[3], (nq, cap))):
+        if a is not None and a.shape != shape:
+            raise ValueError("%s: source and source_mask are [nq][cap], count [nq]" % who)
+    for a in (opt[2], opt[4]):
+        if a is not None and (a.ndim != 3 or a.shape[1:] != (nq, cap)):
+            raise ValueError("%s: planes are [n][nq][cap]" % who)
+    n64 = opt[2].shape[0] if opt[2] is not None else 0
+    n32 = opt[4].shape[0] if opt[4] is not None else 0
+    outs = [np.empty((nq, out_cap), np.uint64), np.empty((nq, out_cap), np.float64),
+            None if opt[0] is None else np.empty((nq, out_cap), np.uint8),
+            None if opt[2] is None else np.empty((n64, nq, out_cap), np.float64),
+            None if opt[3] is None else np.empty((nq, out_cap), np.uint32),
+            None if opt[4] is None else np.empty((n32, nq, out_cap), np.float32), np.empty(nq, np.uint32)]
+    return nq, cap, out_cap, [r, sc] + opt, outs, n64, n32
+
+
+def candidates_blend_host(conf, rows, score, source=None, count=None, planes_f64=None, source_mask=None, planes_f32=None):
+    """pg_candidates_blend_host: SnakeFilter / CompletelyFairCountFilter on host arrays by the library's host statement (no
+    context, no device); arguments and result as Context.candidates_blend."""
+    nq, cap, _, ins, outs, n64, n32 = _blend_arrays("candidates_blend_host", conf, rows, score, source, count, planes_f64, source_mask,
+                                                    planes_f32)
+    v = lambda a: None if a is None else _ptr(a)                                     # noqa: E731
+    _lib.check(_lib.load().pg_candidates_blend_host(C.byref(_blend_conf(conf)), nq, cap, v(ins[0]), v(ins[1]), v(ins[2]), v(ins[3]),
+                                                    v(ins[4]), n64, v(ins[5]), v(ins[6]), n32, *[v(a) for a in outs]))
+    return tuple(outs)
+
+
 DIV_MAX_N, DIV_MAX_RULES, DIV_MAX_DIMS, DIV_MAX_COLS, DIV_MAX_EXCL, DIV_MAX_TERMS, DIV_MAX_POSITIONS, DIV_CHUNK = 8192, 8, 4, 16, 8, 4, 64, 1024
 WHERE_GT, WHERE_GE, WHERE_LT, WHERE_LE, WHERE_EQ, WHERE_NE = range(6)
 
@@ -488,6 +552,51 @@ class Context:
                 d_out.append(self.malloc(max(a.nbytes, 16)) if a is not None else 0)
                 bufs.append(d_out[-1])
             self.candidates_trim_dev(rules, nq, cap, d_in[0], d_in[1], d_in[2], d_in[3], d_in[4], n64, d_in[5], d_in[6], n32, *d_out)
+            self.synchronize()
+            for a, p_ in zip(outs, d_out):
+                if a is not None and a.nbytes:
+                    self.d2h(a, p_)
+        finally:
+            for b in bufs:
+                if b:
+                    self.free(b)
+        return tuple(outs)
+
+    @staticmethod
+    def blend_out_cap(conf, cap: int) -> int:
+        """pg_blend_out_cap: min(cap, retain_num) (validates the conf; needs no device)."""
+        return blend_out_cap(conf, cap)
+
+    def candidates_blend_dev(self, conf, nq: int, cap: int, d_rows: int, d_score: int, d_source: int, d_count: int, d_planes_f64: int,
+                             n_f64: int, d_source_mask: int, d_planes_f32: int, n_f32: int, d_out_rows: int, d_out_score: int,
+                             d_out_source: int, d_out_planes_f64: int, d_out_source_mask: int, d_out_planes_f32: int,
+                             d_out_count: int) -> None:
+        """pg_candidates_blend_dev: conf = (mode, retain_num, [(source, weight)]), everything else device addresses as
+        candidates_trim_dev (0 = absent; an output is required exactly where its input is given), outputs
+        [nq][blend_out_cap(conf, cap)].  Enqueued on the context's stream: synchronize() before reading."""
+        v = lambda p: C.c_void_p(p or None)                                          # noqa: E731
+        _lib.check(self.L.pg_candidates_blend_dev(self.h, C.byref(_blend_conf(conf)), nq, cap, v(d_rows), v(d_score), v(d_source),
+                                                  v(d_count), v(d_planes_f64), n_f64, v(d_source_mask), v(d_planes_f32), n_f32,
+                                                  v(d_out_rows), v(d_out_score), v(d_out_source), v(d_out_planes_f64),
+                                                  v(d_out_source_mask), v(d_out_planes_f32), v(d_out_count)))
+
+    def candidates_blend(self, conf, rows, score, source=None, count=None, planes_f64=None, source_mask=None, planes_f32=None):
+        """SnakeFilter / CompletelyFairCountFilter on host arrays (pg_candidates_blend_dev): the arrays of candidates_trim, conf =
+        (BLEND_SNAKE_REFILL | BLEND_SNAKE_SKIP | BLEND_FAIR, retain_num, [(source, weight)]) → (rows, score, source, planes_f64,
+        source_mask, planes_f32, count), [nq][out_cap] each, None where the input was None."""
+        nq, cap, _, ins, outs, n64, n32 = _blend_arrays("candidates_blend", conf, rows, score, source, count, planes_f64, source_mask,
+                                                        planes_f32)
+        bufs = []
+        try:
+            d_in = []
+            for a in ins:
+                d_in.append(self.to_device(a) if a is not None and a.nbytes else (self.malloc(16) if a is not None else 0))
+                bufs.append(d_in[-1])
+            d_out = []
+            for a in outs:
+                d_out.append(self.malloc(max(a.nbytes, 16)) if a is not None else 0)
+                bufs.append(d_out[-1])
+            self.candidates_blend_dev(conf, nq, cap, d_in[0], d_in[1], d_in[2], d_in[3], d_in[4], n64, d_in[5], d_in[6], n32, *d_out)
             self.synchronize()
             for a, p_ in zip(outs, d_out):
                 if a is not None and a.nbytes:

@@ -467,7 +467,41 @@ bool RecommendConfig::Parse(const std::string& text, RecommendConfig* out, std::
         c.Name = fc.s("Name"); c.FilterType = fc.s("FilterType"); c.FeatureStore = fc.s("FeatureStore");
         c.FilterParams = fc.at("FilterParams");
         std::string why;
-        if (c.FilterType != "ItemStateFilter") why = "unknown FilterType \"" + c.FilterType + "\" (the device serves ItemStateFilter)";
+        if (c.IsBlend()) {
+            // NewSnakeFilter (snake_filter.go:118-164) / NewCompletelyFairCountFilter (completely_fair_count_filter.go:18-25): what
+            // pg_blend_out_cap refuses is refused here, by name
+            const bool snake = c.FilterType == "SnakeFilter";
+            for (const auto& r : out->GpuRecalls) c.BlendSources.push_back(r.Name);
+            const double retain = fc.d("RetainNum");
+            c.Blend.mode = !snake ? PG_BLEND_FAIR : (fc.s("SnakeType") == "SKIP_ON_DUPLICATE" ? PG_BLEND_SNAKE_SKIP : PG_BLEND_SNAKE_REFILL);
+            c.Blend.retain_num = retain >= 1 && retain <= 4294967295.0 ? (uint32_t)retain : 0u;
+            const auto& confs = fc.at("AdjustCountConfs").arr;
+            if (snake && confs.size() > PG_BLEND_MAX_SOURCES)
+                why = std::to_string(confs.size()) + " AdjustCountConfs (the device serves up to " + std::to_string(PG_BLEND_MAX_SOURCES) + ")";
+            for (size_t i = 0; snake && why.empty() && i < confs.size(); ++i) {
+                const std::string name = confs[i].s("RecallName");
+                const double weight = confs[i].d("Weight");
+                const auto at = std::find(c.BlendSources.begin(), c.BlendSources.end(), name);
+                if (at == c.BlendSources.end()) why = "RecallName \"" + name + "\" is no recall of pairec_gpu.Recalls";
+                else if (at - c.BlendSources.begin() >= PG_BLEND_MAX_SOURCES)
+                    why = "RecallName \"" + name + "\" is recall " + std::to_string(at - c.BlendSources.begin()) + " (the device serves the first " +
+                          std::to_string(PG_BLEND_MAX_SOURCES) + " recalls)";
+                else if (weight < 0 || weight > 4294967295.0 || weight != std::floor(weight)) why = "Weight of \"" + name + "\" is not a count";
+                else {
+                    c.Blend.source[i] = (uint8_t)(at - c.BlendSources.begin());
+                    c.Blend.weight[i] = (uint32_t)weight;
+                    c.Blend.n_entries = (uint32_t)i + 1;
+                }
+            }
+            uint32_t width = 0;
+            if (why.empty() && pg_blend_out_cap(&c.Blend, 1, &width) != PG_OK) {
+                why = pg_last_error();
+                const size_t colon = why.find(": ");                     // (the entry point's name says nothing here)
+                if (colon != std::string::npos) why = why.substr(colon + 2);
+                why = c.FilterType + ": " + why;
+            }
+        }
+        else if (c.FilterType != "ItemStateFilter") why = "unknown FilterType \"" + c.FilterType + "\" (the device serves ItemStateFilter)";
         else if (!c.FeatureStore.empty() && c.FeatureStore != "item_features")
             why = "FeatureStore \"" + c.FeatureStore + "\" (the engine holds one store of item columns, \"item_features\")";
         else CheckFilterParams(c.FilterParams, false, &why);
@@ -1787,6 +1821,82 @@ bool item_state_filter(Engine* self, const recconf::GpuFilterConfig& conf, const
     return true;
 }
 
+// SnakeFilter (filter/snake_filter.go:173-241) and CompletelyFairCountFilter (filter/completely_fair_count_filter.go:34-94) through
+// pg_candidates_blend_dev: the items become the arrays a fan-in leaves — the position as the row, Score, the index of RetrieveId
+// among the engine's recalls as the source, RecallScores as the per-recall planes and the source mask — and the kept positions
+// come back in order; an item picked through another recall's list takes that recall's name and score (:83-88).
+bool blend_filter(Engine* self, const recconf::GpuFilterConfig& conf, std::vector<module::ItemPtr>* items, std::string* err) {
+    const size_t n = items->size();
+    if (n == 0) return true;
+    auto fail = [&](const std::string& what) { if (err) *err = conf.FilterType + " " + conf.Name + ": " + what; return false; };
+    if (n > PG_BLEND_MAX_CAP) return fail(std::to_string(n) + " items (the device serves up to " + std::to_string(PG_BLEND_MAX_CAP) + ")");
+    const bool snake = conf.Blend.mode != PG_BLEND_FAIR;
+    // a fair filter deals out whatever names the items carry: those that are no recall of the engine get the indices behind
+    std::vector<std::string> names = conf.BlendSources;
+    if (names.size() > PG_BLEND_MAX_SOURCES) names.resize(PG_BLEND_MAX_SOURCES);
+    const uint32_t n_planes = (uint32_t)std::max<size_t>(names.size(), 1);
+    const uint32_t cap = (uint32_t)n;
+    uint32_t out_cap = 0;
+    if (pg_blend_out_cap(&conf.Blend, cap, &out_cap) != PG_OK) return fail(pg_last_error());
+    std::vector<uint64_t> rows(n), out_rows(out_cap);
+    std::vector<double> score(n), out_score(out_cap), planes((size_t)PG_BLEND_MAX_PLANES * n, std::nan(""));
+    std::vector<uint8_t> source(n), out_source(out_cap);
+    std::vector<uint32_t> mask(n);
+    for (size_t i = 0; i < n; ++i) {
+        const module::Item& it = *(*items)[i];
+        auto at = std::find(names.begin(), names.end(), it.RetrieveId);
+        if (at == names.end() && !snake) {
+            if (names.size() >= PG_BLEND_MAX_SOURCES) return fail("more than " + std::to_string(PG_BLEND_MAX_SOURCES) + " recall names among the items");
+            names.push_back(it.RetrieveId);
+            at = names.end() - 1;
+        }
+        rows[i] = i;
+        score[i] = it.Score;
+        source[i] = at == names.end() ? 0xFF : (uint8_t)(at - names.begin());        // (a snake drops what no entry names)
+        mask[i] = source[i] < 32 ? 1u << source[i] : 0u;
+        if (it.hasRecallScores)
+            for (const auto& kv : it.RecallScores) {
+                const auto r = std::find(names.begin(), names.end(), kv.first);
+                if (r == names.end() || r - names.begin() >= (long)n_planes) continue;
+                mask[i] |= 1u << (r - names.begin());
+                planes[(size_t)(r - names.begin()) * n + i] = kv.second;
+            }
+    }
+    const size_t b_in = n * 8, b_out = (size_t)out_cap * 8;
+    // one device buffer: rows | score | planes | mask | source | out rows | out score | out planes | out mask | out source | count
+    const size_t o_score = b_in, o_planes = 2 * b_in, o_mask = o_planes + n_planes * b_in, o_source = o_mask + n * 4;
+    const size_t o_orows = (o_source + n + 255) & ~(size_t)255, o_oscore = o_orows + b_out, o_oplanes = o_oscore + b_out;
+    const size_t o_omask = o_oplanes + n_planes * b_out, o_osource = o_omask + (size_t)out_cap * 4, o_count = (o_osource + out_cap + 255) & ~(size_t)255;
+    void* d = nullptr;
+    if (pg_device_malloc(self->ctx, o_count + 256, &d) != PG_OK) return fail(pg_last_error());
+    char* b = (char*)d;
+    uint32_t count = 0;
+    const bool ok = pg_memcpy_h2d(self->ctx, b, rows.data(), b_in) == PG_OK && pg_memcpy_h2d(self->ctx, b + o_score, score.data(), b_in) == PG_OK &&
+                    pg_memcpy_h2d(self->ctx, b + o_planes, planes.data(), n_planes * b_in) == PG_OK &&
+                    pg_memcpy_h2d(self->ctx, b + o_mask, mask.data(), n * 4) == PG_OK && pg_memcpy_h2d(self->ctx, b + o_source, source.data(), n) == PG_OK &&
+                    pg_candidates_blend_dev(self->ctx, &conf.Blend, 1, cap, (const uint64_t*)b, (const double*)(b + o_score), (const uint8_t*)(b + o_source),
+                                            nullptr, (const double*)(b + o_planes), n_planes, (const uint32_t*)(b + o_mask), nullptr, 0,
+                                            (uint64_t*)(b + o_orows), (double*)(b + o_oscore), (uint8_t*)(b + o_osource), (double*)(b + o_oplanes),
+                                            (uint32_t*)(b + o_omask), nullptr, (uint32_t*)(b + o_count)) == PG_OK &&
+                    pg_synchronize(self->ctx) == PG_OK && pg_memcpy_d2h(self->ctx, out_rows.data(), b + o_orows, b_out) == PG_OK &&
+                    pg_memcpy_d2h(self->ctx, out_score.data(), b + o_oscore, b_out) == PG_OK &&
+                    pg_memcpy_d2h(self->ctx, out_source.data(), b + o_osource, out_cap) == PG_OK &&
+                    pg_memcpy_d2h(self->ctx, &count, b + o_count, 4) == PG_OK;
+    const std::string why = ok ? std::string() : pg_last_error();
+    pg_device_free(self->ctx, d);
+    if (!ok) return fail(why);
+    std::vector<module::ItemPtr> kept(std::min(count, out_cap));
+    for (size_t k = 0; k < kept.size(); ++k) {
+        kept[k] = (*items)[(size_t)out_rows[k]];
+        if (snake && out_source[k] != source[(size_t)out_rows[k]]) {                  // (:83-88)
+            kept[k]->RetrieveId = names[out_source[k]];
+            kept[k]->Score = out_score[k];
+        }
+    }
+    items->swap(kept);
+    return true;
+}
+
 struct GpuSSDSort : sort::ISort {                        // sort/ssd_sort.go:110-343 (embedding table = item table)
     Engine* e;
     recconf::SSDSortConfig conf;
@@ -2411,6 +2521,10 @@ bool Engine::ItemStateFilter(const recconf::GpuFilterConfig& conf, const module:
     return item_state_filter(this, conf, user, items, err);
 }
 
+bool Engine::BlendFilter(const recconf::GpuFilterConfig& conf, std::vector<module::ItemPtr>* items, std::string* err) {
+    return blend_filter(this, conf, items, err);
+}
+
 bool Engine::Recommend(const std::string& uid, int size, const std::string& scene,
                        std::vector<module::ItemPtr>* out, std::string* err) {
     return Recommend(uid, size, scene, json::Value(), out, err);
@@ -2463,7 +2577,7 @@ bool Engine::Recommend(const std::string& uid, int size, const std::string& scen
             for (const auto& name : fn->second) {
                 auto f = gpu_filters.find(name);
                 std::string ferr;
-                if (f != gpu_filters.end()) ItemStateFilter(f->second, &user, &items, &ferr);
+                if (f != gpu_filters.end()) RunGpuFilter(f->second, &user, &items, &ferr);
             }
     }
     {   // FeatureService.LoadFeatures (user_recommend.go:129; feature_service.go:77-131): "features.scene.name" of the experiment first
@@ -2799,7 +2913,8 @@ const char* ph_engine_sort_scored(void* h, const char* sort_name, const char* it
     return items_to_json(sd.Data);
 }
 
-// one pairec_gpu.Filters entry over caller-made items [{"id","score"}] → the kept items, in order
+// one pairec_gpu.Filters entry over caller-made items [{"id","score"}, optionally "retrieve_id" and "recall_scores" {recall: score}
+// as UniqueFilter leaves them] → the kept items, in order
 const char* ph_engine_filter(void* h, const char* filter_name, const char* items_json, const char* user_json) {
     if (!h) { g_ph_err = "ph_engine_filter: NULL engine"; return nullptr; }
     Engine* e = (Engine*)h;
@@ -2815,10 +2930,16 @@ const char* ph_engine_filter(void* h, const char* filter_name, const char* items
     for (const auto& it : root.arr) {
         auto item = std::make_shared<module::Item>(it.s("id"));
         item->Score = it.d("score");
+        item->RetrieveId = it.s("retrieve_id");
+        for (const auto& kv : it.at("recall_scores").obj)
+            if (kv.second.type == json::Value::Number) {
+                item->RecallScores[kv.first] = kv.second.num;
+                item->hasRecallScores = true;
+            }
         items.push_back(item);
     }
     VersionLock::Read generation_guard(e->version);
-    if (!e->ItemStateFilter(f->second, &user, &items, &err)) { g_ph_err = err; return nullptr; }
+    if (!e->RunGpuFilter(f->second, &user, &items, &err)) { g_ph_err = err; return nullptr; }
     return items_to_json(items);
 }
 

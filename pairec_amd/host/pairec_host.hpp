@@ -154,9 +154,16 @@ struct SortConfig {                        // recconf.go:820-838: Name, SortType
                                            // {Conditions, Expression}, BoostScoreConditionsFilterAll: recconf.go:843-844,892-895)
 };
 // pairec_gpu.Filters: FilterType "ItemStateFilter" (filter/item_state_filter.go:47-57) over the engine's feature columns
+// … "SnakeFilter" (filter/snake_filter.go:118-241: AdjustCountConfs[{RecallName, Weight}], RetainNum, SnakeType) and
+// "CompletelyFairCountFilter" (filter/completely_fair_count_filter.go:18-94: RetainNum) through pg_candidates_blend_dev
 struct GpuFilterConfig {
     std::string Name, FilterType, FeatureStore;
     json::Value FilterParams;              // [FilterParamConfig] (recconf.go:884-891)
+    // the blend filters: the conf as the device takes it — a RecallName resolved to the recall's index in pairec_gpu.Recalls, which
+    // is the fan-in source index of its items — and those recall names in index order
+    pg_blend_conf Blend{};
+    std::vector<std::string> BlendSources;
+    bool IsBlend() const { return FilterType == "SnakeFilter" || FilterType == "CompletelyFairCountFilter"; }
 };
 struct FeatureConfig {                      // recconf.go:256-265
     std::string FeatureType, FeatureName, FeatureSource, FeatureValue, FeatureStore, Normalizer, Expression;
@@ -475,6 +482,11 @@ public:
     // A filter that cannot be served leaves the items as they are and reports an error, which Recommend ignores like a sort's.
     std::map<std::string, recconf::GpuFilterConfig> gpu_filters;
     bool ItemStateFilter(const recconf::GpuFilterConfig& conf, const module::User* user, std::vector<module::ItemPtr>* items, std::string* err);
+    bool BlendFilter(const recconf::GpuFilterConfig& conf, std::vector<module::ItemPtr>* items, std::string* err);   // SnakeFilter, CompletelyFairCountFilter
+    // one pairec_gpu.Filters entry, whatever its FilterType
+    bool RunGpuFilter(const recconf::GpuFilterConfig& conf, const module::User* user, std::vector<module::ItemPtr>* items, std::string* err) {
+        return conf.IsBlend() ? BlendFilter(conf, items, err) : ItemStateFilter(conf, user, items, err);
+    }
     std::map<std::string, std::vector<int32_t>> user_fields;   // uid → dictionary-encoded user categorical features
     pg_model* fm2t = nullptr;                           // FM + two-tower model: rank algorithm "fm2t", and the vector model of the online recall
     pg_table* item_emb = nullptr;                       // … and the item-tower outputs it searches
