@@ -76,7 +76,7 @@ int ensure_dyn_lds(pg_ctx* ctx, const void* kernel, size_t bytes) {
     return PG_OK;
 }
 
-int scratch_reserve(pg_ctx* ctx, int slot, size_t bytes, void** out) {
+int scratch_reserve(pg_ctx* ctx, ScratchSlot slot, size_t bytes, void** out, bool soft) {
     Scratch& s = ctx->scratch[slot];
     if (s.cap < bytes) {
         if (s.p) {
@@ -85,13 +85,22 @@ int scratch_reserve(pg_ctx* ctx, int slot, size_t bytes, void** out) {
             s.p = nullptr;
             s.cap = 0;
         }
-        size_t cap = (bytes + (1u << 20) - 1) & ~((size_t)(1u << 20) - 1);
-        PG_HIP(hipMalloc(&s.p, cap));
+        const size_t cap = align_up(bytes, (size_t)1 << 20);
+        if (soft) {
+            if (hipMalloc(&s.p, cap) != hipSuccess) {
+                (void)hipGetLastError();
+                s.p = nullptr;
+                return PG_ERR_NOMEM;
+            }
+        } else {
+            PG_HIP(hipMalloc(&s.p, cap));
+        }
         s.cap = cap;
     }
     *out = s.p;
     return PG_OK;
 }
+const void* scratch_peek(const pg_ctx* ctx, ScratchSlot slot) { return ctx->scratch[slot].p; }
 
 }  // namespace pg
 

@@ -452,8 +452,6 @@ int blend_check_call(const pg_blend_conf* c, uint32_t nq, uint32_t cap, const vo
     return PG_OK;
 }
 
-inline size_t blend_al(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // pg_sort_scores_dev's order on the host: descending, -0.0 equal to +0.0, NaN last, ties by input position
 inline bool blend_before(double x, double y) { return x == x && (y != y || x > y); }
 
@@ -550,15 +548,14 @@ int candidates_blend_locked(pg_ctx* ctx, const pg_blend_conf* conf, uint32_t nq,
     const bool fair = conf->mode == PG_BLEND_FAIR;
     const uint32_t n_e = fair ? 1u : conf->n_entries, n_seg = nq * n_e;
     // scratch: segment offsets | orders | (SNAKE) keys | lists | pick records
-    const size_t b_off = blend_al((size_t)(n_seg + 1) * 4), b_ord = blend_al((size_t)n_seg * cap * 4);
-    const size_t b_keys = fair ? 0 : blend_al((size_t)n_seg * cap * 8), b_pick = fair ? 0 : blend_al((size_t)nq * out_cap * 4);
-    void* buf;
-    if ((rc = scratch_reserve(ctx, 26, b_off + b_ord + b_keys + (fair ? 0 : b_ord) + b_pick, &buf))) return rc;
-    uint32_t* d_off = (uint32_t*)buf;
-    uint32_t* d_ord = (uint32_t*)((char*)buf + b_off);
-    unsigned long long* d_keys = (unsigned long long*)((char*)d_ord + b_ord);
-    uint32_t* d_lists = (uint32_t*)((char*)d_keys + b_keys);
-    uint32_t* d_picks = (uint32_t*)((char*)d_lists + b_ord);
+    uint32_t *d_off, *d_ord, *d_lists, *d_picks; unsigned long long* d_keys;
+    if ((rc = scratch_carve(ctx, kSlotBlend, [&](Carve& c) {
+            d_off = c.take<uint32_t>((size_t)n_seg + 1);
+            d_ord = c.take<uint32_t>((size_t)n_seg * cap);
+            d_keys = c.take<unsigned long long>(fair ? 0 : (size_t)n_seg * cap);
+            d_lists = c.take<uint32_t>(fair ? 0 : (size_t)n_seg * cap);
+            d_picks = c.take<uint32_t>(fair ? 0 : (size_t)nq * out_cap);
+        }))) return rc;
     BlendArgs a{};
     a.rows = d_rows;
     a.score = reinterpret_cast<const unsigned long long*>(d_score);

@@ -338,8 +338,6 @@ __global__ void cf_fill_u64_kernel(uint64_t* __restrict__ p, uint64_t n, uint64_
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) p[i] = v;
 }
 
-inline size_t cf_al(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // the arguments every form of the recall checks, in this order
 int cf_check(const char* who, const pg_ctx* ctx, const pg_simtable* s, const void* trig, const void* pref, const uint32_t* off, uint32_t nq,
              uint32_t k, const pg_cf_opts* opts, const void* rows, const void* scores, uint32_t* nmax_out) {
@@ -393,23 +391,20 @@ int cf_recall_locked(const char* who, pg_ctx* ctx, const pg_simtable* s, const u
     while (cand_cap < rows_eff) cand_cap <<= 1;
     const uint32_t kd = k + nmax;
     const uint32_t xtotal = nmax && excl_on_host ? xoff[nq] - xoff[0] : 0;
-    const size_t b_stat = cf_al((1 + (size_t)kMaxQueries) * 4), b_off = cf_al(((size_t)nq + 1) * 4), b_list = cf_al((size_t)xtotal * 8);
-    const size_t b_keys = cf_al((size_t)nq * gslots * 4), b_acc = cf_al((size_t)nq * gslots * 8), b_cand = cf_al((size_t)nq * cand_cap * 16);
-    const size_t b_xr = nmax ? cf_al((size_t)nq * kd * 8) : 0, b_xi = nmax ? cf_al((size_t)nq * kd * 4) : 0, b_oi = nmax ? cf_al((size_t)nq * k * 4) : 0;
-    void* buf;
-    if ((rc = scratch_reserve(ctx, 19, b_stat + 2 * b_off + b_list + b_keys + b_acc + b_cand + 2 * b_xr + b_xi + b_oi, &buf))) return rc;
-    char* p = (char*)buf;
-    uint32_t* d_status = (uint32_t*)p;   p += b_stat;        // [0] the status word, [1 + q] request q's count
-    uint32_t* d_off = (uint32_t*)p;      p += b_off;
-    uint32_t* d_xoff = (uint32_t*)p;     p += b_off;
-    uint64_t* d_list = (uint64_t*)p;     p += b_list;
-    uint32_t* d_keys = (uint32_t*)p;     p += b_keys;
-    double* d_acc = (double*)p;          p += b_acc;
-    ulonglong2* d_cand = (ulonglong2*)p; p += b_cand;
-    uint64_t* d_xrows = (uint64_t*)p;    p += b_xr;
-    double* d_xsc = (double*)p;          p += b_xr;
-    float* d_xidx = (float*)p;           p += b_xi;
-    float* d_oidx = (float*)p;
+    uint32_t *d_status, *d_off, *d_xoff, *d_keys; uint64_t *d_list, *d_xrows; double *d_acc, *d_xsc; ulonglong2* d_cand; float *d_xidx, *d_oidx;
+    if ((rc = scratch_carve(ctx, kSlotCf, [&](Carve& c) {
+            d_status = c.take<uint32_t>(1 + (size_t)kMaxQueries);      // ONE region, copied out together: [0] the status word, [1 + q] request q's count
+            d_off = c.take<uint32_t>((size_t)nq + 1);
+            d_xoff = c.take<uint32_t>((size_t)nq + 1);
+            d_list = c.take<uint64_t>(xtotal);
+            d_keys = c.take<uint32_t>((size_t)nq * gslots);
+            d_acc = c.take<double>((size_t)nq * gslots);
+            d_cand = c.take<ulonglong2>((size_t)nq * cand_cap);
+            d_xrows = c.take<uint64_t>(nmax ? (size_t)nq * kd : 0);
+            d_xsc = c.take<double>(nmax ? (size_t)nq * kd : 0);
+            d_xidx = c.take<float>(nmax ? (size_t)nq * kd : 0);
+            d_oidx = c.take<float>(nmax ? (size_t)nq * k : 0);
+        }))) return rc;
     uint32_t h_xoff[kMaxQueries + 1];
     PG_HIP(hipMemsetAsync(d_status, 0xFF, 4, ctx->stream));
     PG_HIP(hipMemcpyAsync(d_off, off, ((size_t)nq + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
@@ -482,14 +477,14 @@ int cf_entry(const char* who, pg_ctx* ctx, const pg_simtable* s, const uint32_t*
     const uint64_t* excl = opts ? opts->excl_rows : nullptr;
     const uint32_t* xoff = opts ? opts->excl_offsets : nullptr;
     if (!host) return cf_recall_locked(who, ctx, s, trig, pref, off, nq, k, normalize, excl, false, xoff, nmax, rows, scores, out_count);
-    // host buffers: triggers and preferences in, rows and scores out, through scratch slot 5
-    const size_t tb = cf_al((size_t)total * 4), pb = cf_al((size_t)total * 8), ob = cf_al((size_t)nq * k * 8);
-    void* buf;
-    if ((rc = scratch_reserve(ctx, 5, tb + pb + 2 * ob, &buf))) return rc;
-    uint32_t* d_trig = (uint32_t*)buf;
-    double* d_pref = (double*)((char*)buf + tb);
-    uint64_t* d_rows = (uint64_t*)((char*)buf + tb + pb);
-    double* d_sc = (double*)((char*)buf + tb + pb + ob);
+    // host buffers: triggers and preferences in, rows and scores out, through the staging slot
+    uint32_t* d_trig; double *d_pref, *d_sc; uint64_t* d_rows;
+    if ((rc = scratch_carve(ctx, kSlotStaging, [&](Carve& c) {
+            d_trig = c.take<uint32_t>(total);
+            d_pref = c.take<double>(total);
+            d_rows = c.take<uint64_t>((size_t)nq * k);
+            d_sc = c.take<double>((size_t)nq * k);
+        }))) return rc;
     uint32_t h_off[kMaxQueries + 1];
     for (uint32_t q = 0; q <= nq; ++q) h_off[q] = off[q] - off[0];
     if (total) {

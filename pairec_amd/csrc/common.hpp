@@ -8,6 +8,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <atomic>
 #include <memory>
@@ -17,6 +18,7 @@
 #include <vector>
 
 #include "../../include/pairec_gpu.h"
+#include "scratch_layout.hpp"
 
 namespace pg {
 
@@ -50,6 +52,38 @@ constexpr int kMaxQueries = 256;       // screened scan (int8 or bf16 filter + e
 struct Scratch {
     void* p = nullptr;
     size_t cap = 0;
+};
+// The arena's slots.  A slot's contents are valid until the next reserve of the same slot on this context; users that share a
+// slot are stages that never hold it at the same time on the context's one stream.  The values are only array positions.
+enum ScratchSlot : int {
+    kSlotRows = 0,           // table.hip: the row ids of a gather from host rows; rank_mlp.hip: fm2t rows' gathered field ids (separate entry points, neither calls the other)
+    kSlotHostStage = 1,      // table.hip: the gathered rows on their way to the host; features.hip: column descriptors and pointers of a gather (separate entry points)
+    kSlotRecallSmall = 2,    // recall.hip recall_scratch: padded queries, thresholds, counts, screen fragments, status words
+    kSlotRecallCand = 3,     // recall.hip recall_scratch: the candidate and suspect lists
+    kSlotStatus = 4,         // 4096 bytes of status words (expr, misc, recall, recall_i4, recall_r2): each user writes, copies out and synchronises inside one step of its call
+    kSlotStaging = 5,        // staging of every host-buffer entry point (rank, recall, sort, dpp, ssd, expr, cf, index, diversity): one per call under ctx->mu, synchronised before it returns
+    kSlotRankTiles = 6,      // rank_mlp.hip: tile table + request partials
+    kSlotWork = 7,           // work area of sort, split sort, dpp and ssd: each is one stage of a step, done with it before the next stage is enqueued on the stream
+    kSlotPipe = 8,           // pipeline.hip post_scratch: the recommend pipeline's intermediates
+    kSlotGroup = 9,          // group.hip pg_owned_compact_dev: the per-request counts of owned rows
+    kSlotRerank = 10,        // pipeline.hip: the re-rank stage's DPP candidates
+    kSlotHitRecords = 11,    // recall.hip: the screened pass's record regions
+    kSlotFilterCount = 12,   // recall.hip filter_count_locked: per-block and per-group counts of the rows a filter admits
+    kSlotFilterGather = 13,  // recall.hip: the admitted rows' ids, compacted table and norms of a filtered recall
+    kSlotRankHeads = 14,     // rank_mlp.hip: head partials of the weights-stationary multi-head kernel
+    kSlotFuse = 15,          // pipeline.hip pg_fuse_scores_dev: the bound variables and error flags
+    kSlotExprVars = 16,      // expr.hip pg_features_eval_dev: the bound variables
+    kSlotIndexSearch = 17,   // index.hip: bounds, probe thresholds and list counts of an index recall; rank_mlp.hip: the fp16 split kernel's fallback tile tables (separate calls)
+    kSlotRecallExclude = 18, // recall.hip: the over-fetched answer, lists and counts of a recall with exclusion lists
+    kSlotCf = 19,            // cf.hip: status and counts, staged offsets and lists, the global tier's tables, the items to order, the over-fetched answer
+    kSlotFanin = 20,         // fanin.hip: the merge's keys, values and masks
+    kSlotTrim = 21,          // trim.hip: segment offsets and the order of a coarse-rank cut
+    kSlotCoarse = 22,        // pipeline.hip: the coarse stage's own outputs of a two-stage rank (fused scores, model scores, order)
+    kSlotDiversity = 23,     // diversity.hip: keys, window counts and tuple tables
+    kSlotDiversityPlanes = 24,  // diversity.hip: the dimension planes gathered from a feature store
+    kSlotCond = 25,          // cond.hip: the one-request entries' staging (pg_item_state_filter, pg_boost_scores: inputs, outputs, the temporary store)
+    kSlotBlend = 26,         // blend.hip: segment offsets, per-entry keys and orders, the compacted lists and the pick records
+    kSlotCount
 };
 
 // Developer / tuning knobs.  Read from the environment ONCE, in pg_init (a serving process must not change
@@ -254,21 +288,7 @@ struct pg_ctx {
     bool own_stream = false;
     int num_cus = 256;
     std::mutex mu;               // serialises calls on this context
-    // named scratch slots (transient: a slot's contents are valid until the next reserve of the same slot on this context;
-    // users that share a slot are stages that never overlap on the context's one stream):
-    //   0 table upload staging / fm2t rows' gathered field ids     1 table / features host staging
-    //   2, 3 recall.hip candidate lists and thresholds             4 small status words (expr, misc, recall, recall_i4)
-    //   5 host-buffer entry points' staging (rank, recall, sort, dpp, ssd, expr)
-    //   6 rank tile table + request partials   7 sort / dpp / ssd work areas   8 recommend pipeline intermediates (post_scratch)
-    //   9 group.hip   10 re-rank stage (DPP candidates)   11 recall.hip: the screened pass's record regions
-    //   12, 13 recall.hip   14 rank_mlp.hip: head partials of the weights-stationary multi-head kernel   15 pg_fuse_scores_dev
-    //   16 pg_features_eval_dev: the bound variables   17 index.hip: bounds, probe thresholds and list counts of an index recall
-    //   18 recall.hip: the over-fetched answer, lists and counts of a recall with exclusion lists
-    //   19 cf.hip: status and counts, staged offsets and lists, the global tier's tables, the items to order, the over-fetched answer
-    //   23 diversity.hip: keys, window counts and tuple tables   24 diversity.hip: the dimension planes gathered from a feature store
-    //   25 cond.hip: the one-request entries' staging (pg_item_state_filter, pg_boost_scores: inputs, outputs, the temporary store)
-    //   26 blend.hip: segment offsets, per-entry keys and orders, the compacted lists and the pick records
-    pg::Scratch scratch[27];
+    pg::Scratch scratch[pg::kSlotCount];   // the arena (pg::ScratchSlot); touched only by the scratch_* functions and pg_shutdown
     std::mutex pool_mu;          // guards pipe_free
     std::vector<pg::PipeRun*> pipe_free;     // per-batch status blocks / events of the device-resident pipelines
     std::map<const void*, size_t> dyn_lds;   // kernels whose dynamic-LDS limit was raised on this device
@@ -643,7 +663,20 @@ int sort_dev_locked(pg_ctx* ctx, const double* d_scores, const uint32_t* d_seg, 
                     uint32_t max_seg, int desc, uint32_t* d_out);
 
 void pipe_pool_destroy(pg_ctx* ctx);      // pipeline.hip
-int scratch_reserve(pg_ctx* ctx, int slot, size_t bytes, void** out);
+// the arena (api.cpp): at least `bytes` of the slot; growing it synchronises the stream, frees and reallocates.  A failed
+// allocation is a device error — or, when `soft`, PG_ERR_NOMEM with the sticky HIP error cleared and the slot left empty
+int scratch_reserve(pg_ctx* ctx, ScratchSlot slot, size_t bytes, void** out, bool soft = false);
+const void* scratch_peek(const pg_ctx* ctx, ScratchSlot slot);     // what the slot holds now (nullptr: never reserved), for diagnostics
+// reserve a slot for the layout `lay(Carve&)` states: run once to measure, once more over the reserved buffer
+template <class Layout>
+int scratch_carve(pg_ctx* ctx, ScratchSlot slot, Layout&& lay, bool soft = false) {
+    Carve c;
+    lay(c);
+    void* buf;
+    const int rc = scratch_reserve(ctx, slot, c.total(), &buf, soft);
+    if (rc == PG_OK) lay(c = Carve{(char*)buf});
+    return rc;
+}
 // the checks of the pg_recall_topk* and pg_index_recall_topk* entry points, in this order, named after the entry point `who`;
 // `over` is the table or index searched (its dim)
 template <class T>
@@ -658,21 +691,22 @@ int recall_check(const char* who, const pg_ctx* ctx, const T* over, const void* 
     }
     return PG_OK;
 }
-// a recall of host queries into host outputs: the queries copied into scratch slot 5, run(d_queries, d_rows, d_scores) on the
-// device, the rows and scores copied out; caller holds ctx->mu
+// a recall into host outputs through the staging slot: the queries copied from the host — or, with `queries` NULL, brought by
+// fill(d_queries) —, run(d_queries, d_rows, d_scores) on the device, then the rows and scores copied out; caller holds ctx->mu
 template <class Run>
-int recall_staged(pg_ctx* ctx, uint32_t dim, const float* queries, uint32_t nq, uint32_t k, uint64_t* out_rows, float* out_scores, Run&& run) {
-    void* buf;
-    int rc;
-    const size_t qb = (size_t)nq * dim * 4, rb = (size_t)nq * k * 8, sb = (size_t)nq * k * 4;
-    if ((rc = scratch_reserve(ctx, 5, qb + rb + sb + 64, &buf))) return rc;
-    float* d_q = (float*)buf;
-    uint64_t* d_rows = (uint64_t*)((char*)buf + ((qb + 15) & ~(size_t)15));
-    float* d_sc = (float*)((char*)d_rows + rb);
-    PG_HIP(hipMemcpyAsync(d_q, queries, qb, hipMemcpyHostToDevice, ctx->stream));
+int recall_staged(pg_ctx* ctx, uint32_t dim, const float* queries, uint32_t nq, uint32_t k, uint64_t* out_rows, float* out_scores, Run&& run,
+                  const std::function<int(float*)>& fill = nullptr) {
+    float *d_q, *d_sc; uint64_t* d_rows; int rc;
+    if ((rc = scratch_carve(ctx, kSlotStaging, [&](Carve& c) {
+            d_q = c.take<float>((size_t)nq * dim);
+            d_rows = c.take<uint64_t>((size_t)nq * k);
+            d_sc = c.take<float>((size_t)nq * k);
+        }))) return rc;
+    if (queries) PG_HIP(hipMemcpyAsync(d_q, queries, (size_t)nq * dim * 4, hipMemcpyHostToDevice, ctx->stream));
+    else if ((rc = fill(d_q))) return rc;
     if ((rc = run(d_q, d_rows, d_sc))) return rc;
-    PG_HIP(hipMemcpyAsync(out_rows, d_rows, rb, hipMemcpyDeviceToHost, ctx->stream));
-    PG_HIP(hipMemcpyAsync(out_scores, d_sc, sb, hipMemcpyDeviceToHost, ctx->stream));
+    PG_HIP(hipMemcpyAsync(out_rows, d_rows, (size_t)nq * k * 8, hipMemcpyDeviceToHost, ctx->stream));
+    PG_HIP(hipMemcpyAsync(out_scores, d_sc, (size_t)nq * k * 4, hipMemcpyDeviceToHost, ctx->stream));
     PG_HIP(hipStreamSynchronize(ctx->stream));
     return PG_OK;
 }

@@ -661,7 +661,7 @@ int cond_bind_locked(pg_ctx* ctx, pg_cond* c, const pg_features* fs, const char*
     }
     if (c->device < 0) {
         // once per set: the in lists and the expression programs (the only synchronous step; every later call only launches)
-        const size_t lb = (c->lists.size() * 8 + 255) & ~(size_t)255, pb = c->progs.size() * sizeof(Instr);
+        const size_t lb = align_up(c->lists.size() * 8), pb = c->progs.size() * sizeof(Instr);
         void* d = nullptr;
         PG_HIP(hipMalloc(&d, lb + pb + 256));
         hipError_t e = hipSuccess;
@@ -688,8 +688,6 @@ int cond_check_shape(uint32_t nq, uint32_t cap, const char* who) {
     }
     return PG_OK;
 }
-
-inline size_t cond_al(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // [a, a + an) and [b, b + bn) share a byte
 inline bool cond_overlap(const void* a, size_t an, const void* b, size_t bn) {
@@ -880,19 +878,18 @@ int pg_item_state_filter(pg_ctx* ctx, pg_cond* c, const pg_features* fs, uint32_
     if ((rc = pg::cond_check_shape(1, n, "pg_item_state_filter"))) return rc;
     std::lock_guard<std::mutex> g(ctx->mu);
     PG_HIP(hipSetDevice(ctx->device));
-    const size_t b8 = pg::cond_al((size_t)n * 8), b1 = pg::cond_al(n);
-    void* buf;
-    if ((rc = pg::scratch_reserve(ctx, 25, 4 * b8 + 2 * b1 + 3 * 256, &buf))) return rc;
-    char* at = (char*)buf;
-    uint64_t* d_rows = (uint64_t*)at; at += b8;
-    double* d_score = (double*)at; at += b8;
-    uint64_t* d_orows = (uint64_t*)at; at += b8;
-    double* d_oscore = (double*)at; at += b8;
-    uint8_t* d_src = (uint8_t*)at; at += b1;
-    uint8_t* d_osrc = (uint8_t*)at; at += b1;
-    uint64_t* d_uv = (uint64_t*)at; at += 256;
-    uint32_t* d_up = (uint32_t*)at; at += 256;
-    uint32_t* d_cnt = (uint32_t*)at;
+    uint64_t *d_rows, *d_orows, *d_uv; double *d_score, *d_oscore; uint8_t *d_src, *d_osrc; uint32_t *d_up, *d_cnt;
+    if ((rc = pg::scratch_carve(ctx, pg::kSlotCond, [&](pg::Carve& s) {
+            d_rows = s.take<uint64_t>(n);
+            d_score = s.take<double>(n);
+            d_orows = s.take<uint64_t>(n);
+            d_oscore = s.take<double>(n);
+            d_src = s.take<uint8_t>(n);
+            d_osrc = s.take<uint8_t>(n);
+            d_uv = s.take<uint64_t>(pg::kCondMaxSlots);
+            d_up = s.take<uint32_t>(1);
+            d_cnt = s.take<uint32_t>(1);
+        }))) return rc;
     uint64_t uv[pg::kCondMaxSlots] = {0};
     if (user_vals) memcpy(uv, user_vals, c->slot_names.size() * 8);
     PG_HIP(hipMemcpyAsync(d_rows, rows, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
@@ -923,16 +920,18 @@ int pg_boost_scores(pg_ctx* ctx, pg_cond* c, uint32_t filter_all, uint32_t n, co
     std::lock_guard<std::mutex> g(ctx->mu);
     PG_HIP(hipSetDevice(ctx->device));
     // the candidates' values become a store of n rows in scratch: candidate i reads row i, one outside the store row n
-    const size_t b8 = pg::cond_al((size_t)n * 8), b1 = pg::cond_al(n), nu = c->used.size();
-    void* buf;
-    if ((rc = pg::scratch_reserve(ctx, 25, (3 + nu) * b8 + b1 + 2 * 256, &buf))) return rc;
-    char* at = (char*)buf;
-    uint64_t* d_rows = (uint64_t*)at; at += b8;
-    double* d_score = (double*)at; at += b8;
-    double* d_oscore = (double*)at; at += b8;
-    uint8_t* d_rule = (uint8_t*)at; at += b1;
-    uint64_t* d_uv = (uint64_t*)at; at += 256;
-    uint32_t* d_up = (uint32_t*)at; at += 256;
+    const size_t nu = c->used.size();
+    uint64_t *d_rows, *d_uv; double *d_score, *d_oscore; uint8_t* d_rule; uint32_t* d_up;
+    std::vector<void*> d_col(nu);                     // a column of up to 8-byte values each
+    if ((rc = pg::scratch_carve(ctx, pg::kSlotCond, [&](pg::Carve& s) {
+            d_rows = s.take<uint64_t>(n);
+            d_score = s.take<double>(n);
+            d_oscore = s.take<double>(n);
+            d_rule = s.take<uint8_t>(n);
+            d_uv = s.take<uint64_t>(pg::kCondMaxSlots);
+            d_up = s.take<uint32_t>(1);
+            for (size_t k = 0; k < nu; ++k) d_col[k] = s.bytes((size_t)n * 8);
+        }))) return rc;
     std::vector<uint64_t> rows(n);
     for (uint32_t i = 0; i < n; ++i) rows[i] = !item_in || item_in[i] ? i : n;
     uint64_t uv[pg::kCondMaxSlots] = {0};
@@ -942,13 +941,12 @@ int pg_boost_scores(pg_ctx* ctx, pg_cond* c, uint32_t filter_all, uint32_t n, co
     for (size_t k = 0; k < nu; ++k) {
         const int d = c->used[k], dt = c->col_dtypes[(size_t)d];
         const size_t es = dt == PG_F_I32 || dt == PG_F_F32 ? 4 : 8;
-        PG_HIP(hipMemcpyAsync(at, cols[d], (size_t)n * es, hipMemcpyHostToDevice, ctx->stream));
+        PG_HIP(hipMemcpyAsync(d_col[k], cols[d], (size_t)n * es, hipMemcpyHostToDevice, ctx->stream));
         pg_features::Column col;
         col.name = c->col_names[(size_t)d];
         col.dtype = dt;
-        col.d = at;
+        col.d = d_col[k];
         tmp.cols.push_back(col);
-        at += b8;
     }
     PG_HIP(hipMemcpyAsync(d_rows, rows.data(), (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
     PG_HIP(hipMemcpyAsync(d_score, score, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));

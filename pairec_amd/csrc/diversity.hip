@@ -572,8 +572,6 @@ void div_host_one(const DivCfg& c, uint32_t n, uint32_t cap, const int64_t* dims
     for (uint32_t p : aside) order[at++] = p;
 }
 
-inline size_t div_al(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // caller holds ctx->mu; no synchronisation
 int div_launch_locked(pg_ctx* ctx, const DivCfg& c, uint32_t nq, uint32_t cap, const uint32_t* d_count, const int64_t* d_dims,
                       const uint8_t* d_source, const uint8_t* d_enable, uint32_t* d_order) {
@@ -581,21 +579,20 @@ int div_launch_locked(pg_ctx* ctx, const DivCfg& c, uint32_t nq, uint32_t cap, c
     uint32_t bits = 0;
     while ((1u << bits) < std::max(2u * cap, kDivMinSlots)) ++bits;
     const uint32_t nr = std::max(c.n_rules, 1u);
-    const size_t b_keys = div_al((size_t)nq * nr * cap * 4), b_tbl = div_al(((size_t)nq << bits) * 4);
-    void* buf;
-    int rc;
-    if ((rc = scratch_reserve(ctx, 23, 2 * b_keys + b_tbl, &buf))) return rc;
     DivArgs a;
     memset(&a, 0, sizeof a);
+    int rc;
+    if ((rc = scratch_carve(ctx, kSlotDiversity, [&](Carve& s) {
+            a.keys = s.take<uint32_t>((size_t)nq * nr * cap);
+            a.cnt = s.take<uint32_t>((size_t)nq * nr * cap);
+            a.tbl = s.take<uint32_t>((size_t)nq << bits);
+        }))) return rc;
     a.c = c;
     a.dims = reinterpret_cast<const long long*>(d_dims);
     a.source = d_source;
     a.count = d_count;
     a.enable = d_enable;
     a.order = d_order;
-    a.keys = (uint32_t*)buf;
-    a.cnt = (uint32_t*)((char*)buf + b_keys);
-    a.tbl = (uint32_t*)((char*)buf + 2 * b_keys);
     a.nq = nq;
     a.cap = cap;
     a.slot_bits = bits;
@@ -698,7 +695,7 @@ int pg_diversity_rules_features_dev(pg_ctx* ctx, const pg_div_config* cfg, const
     PG_HIP(hipSetDevice(ctx->device));
     const size_t n = (size_t)nq * cap;
     void* planes;
-    if ((rc = pg::scratch_reserve(ctx, 24, std::max<size_t>((size_t)c.n_cols * n * 8, 256), &planes))) return rc;
+    if ((rc = pg::scratch_reserve(ctx, pg::kSlotDiversityPlanes, std::max<size_t>((size_t)c.n_cols * n * 8, 256), &planes))) return rc;
     if (c.n_cols) {
         pg::diversity_gather_kernel<<<(unsigned)((n + 255) / 256), 256, 0, ctx->stream>>>(cols, d_rows, n, (long long*)planes);
         PG_HIP(hipGetLastError());
@@ -715,12 +712,12 @@ int pg_diversity_rules(pg_ctx* ctx, const pg_div_config* cfg, uint32_t n, const 
     PG_REQUIRE(order && (dims || c.n_cols == 0), "pg_diversity_rules: NULL argument");
     std::lock_guard<std::mutex> g(ctx->mu);
     PG_HIP(hipSetDevice(ctx->device));
-    const size_t b_dims = pg::div_al((size_t)c.n_cols * n * 8), b_src = pg::div_al(n), b_out = pg::div_al((size_t)n * 4);
-    void* buf;
-    if ((rc = pg::scratch_reserve(ctx, 5, b_dims + b_src + b_out + 256, &buf))) return rc;
-    int64_t* d_dims = (int64_t*)buf;
-    uint8_t* d_src = (uint8_t*)buf + b_dims;
-    uint32_t* d_out = (uint32_t*)((char*)buf + b_dims + b_src);
+    int64_t* d_dims; uint8_t* d_src; uint32_t* d_out;
+    if ((rc = pg::scratch_carve(ctx, pg::kSlotStaging, [&](pg::Carve& s) {
+            d_dims = s.take<int64_t>((size_t)c.n_cols * n);
+            d_src = s.take<uint8_t>(n);
+            d_out = s.take<uint32_t>(n);
+        }))) return rc;
     if (c.n_cols) PG_HIP(hipMemcpyAsync(d_dims, dims, (size_t)c.n_cols * n * 8, hipMemcpyHostToDevice, ctx->stream));
     if (source) PG_HIP(hipMemcpyAsync(d_src, source, n, hipMemcpyHostToDevice, ctx->stream));
     if ((rc = pg::div_launch_locked(ctx, c, 1, n, nullptr, d_dims, source ? d_src : nullptr, nullptr, d_out))) return rc;

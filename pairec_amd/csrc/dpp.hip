@@ -633,23 +633,18 @@ int dpp_run_locked(pg_ctx* ctx, const float* d_emb32, const double* d_hook, cons
     if (R == 0 || n == 0 || (topn == 0 && !d_L_out)) return PG_OK;
     if (window == 0) window = 10;                        // NewDPPSort default (dpp_sort.go:89-91)
     const uint32_t d1 = hook_dim + (has_table ? d : 0u) + 1;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     // L's rows are padded to whole 128-byte lines: a tile's 512-byte row segments then cover four lines each — with rows of n = 500
     // doubles every segment began and ended inside a line that a workgroup of another XCD completes, and the 512 MB of a
     // 256-request batch left the chip as partial-line writes at 1.46 TB/s (0.35 ms whatever the arithmetic pipe did)
     const uint32_t ld = (n + 15u) & ~15u;
-    // (F: 64 rows of slack behind the last request — the kernel matrix's panel loads are not clamped)
-    const size_t bF = al(((size_t)R * n + kDppTile) * d1 * 8), bR = al((size_t)R * n * 8), bL = al((size_t)R * n * ld * 8);
-    const size_t bD2 = al((size_t)R * n * 8), bC = al((size_t)R * std::min(window, n) * n * 8);
-    void* buf;
-    int rc;
-    if ((rc = scratch_reserve(ctx, 7, bF + bR + bL + bD2 + bC, &buf))) return rc;
-    char* p = (char*)buf;
-    double* F = (double*)p; p += bF;
-    double* Rr = (double*)p; p += bR;
-    double* L = (double*)p; p += bL;
-    double* D2 = (double*)p; p += bD2;
-    double* Cm = (double*)p;
+    double *F, *Rr, *L, *D2, *Cm; int rc;
+    if ((rc = scratch_carve(ctx, kSlotWork, [&](Carve& c) {
+            F = c.take<double>(((size_t)R * n + kDppTile) * d1);      // (64 rows of slack behind the last request — the kernel matrix's panel loads are not clamped)
+            Rr = c.take<double>((size_t)R * n);
+            L = c.take<double>((size_t)R * n * ld);
+            D2 = c.take<double>((size_t)R * n);
+            Cm = c.take<double>((size_t)R * std::min(window, n) * n);
+        }))) return rc;
     DppPrep a;
     a.emb32 = d_emb32; a.hook = d_hook; a.rel = d_rel;
     a.n = n; a.d = d; a.hook_dim = hook_dim; a.alpha = alpha;
@@ -807,18 +802,14 @@ int pg_dpp_ex(pg_ctx* ctx, const pg_table* t, const uint32_t* cand_rows, const d
     std::lock_guard<std::mutex> g(ctx->mu);
     pg::TableRead tr;
     if (o->has_table) tr = pg::TableRead(t->rw);
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t bCand = al((size_t)n * 4), bRel = al((size_t)n * 8), bEmb = al((size_t)n * std::max(dim, 1u) * 4);
-    const size_t bHook = al((size_t)n * std::max(o->hook_dim, 1u) * 8), bOut = al((size_t)(topn + 1) * 4 + 16);
-    void* buf;
-    int rc;
-    if ((rc = pg::scratch_reserve(ctx, 5, bCand + bRel + bEmb + bHook + bOut, &buf))) return rc;
-    char* p = (char*)buf;
-    uint32_t* d_cand = (uint32_t*)p; p += bCand;
-    double* d_rel = (double*)p; p += bRel;
-    float* d_emb = (float*)p; p += bEmb;
-    double* d_hook = (double*)p; p += bHook;
-    uint32_t* d_out = (uint32_t*)p;
+    uint32_t *d_cand, *d_out; double *d_rel, *d_hook; float* d_emb; int rc;
+    if ((rc = pg::scratch_carve(ctx, pg::kSlotStaging, [&](pg::Carve& c) {
+            d_cand = c.take<uint32_t>(n);
+            d_rel = c.take<double>(n);
+            d_emb = c.take<float>((size_t)n * std::max(dim, 1u));
+            d_hook = c.take<double>((size_t)n * std::max(o->hook_dim, 1u));
+            d_out = c.take<uint32_t>((size_t)topn + 1 + 4);      // ONE region: the picks, their count behind them
+        }))) return rc;
     uint32_t* d_cnt = d_out + topn;
     PG_HIP(hipMemcpyAsync(d_rel, rs.data(), (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
     if (o->has_table) {

@@ -320,7 +320,7 @@ static int expr_eval_locked(pg_ctx* ctx, const pg_expr* e, const double* d_vars,
                             double* d_out) {
     void* p;
     int rc;
-    if ((rc = scratch_reserve(ctx, 4, 4096, &p))) return rc;
+    if ((rc = scratch_reserve(ctx, kSlotStatus, 4096, &p))) return rc;
     uint32_t* d_err = (uint32_t*)p + 320;
     PG_HIP(hipMemsetAsync(d_err, 0, 4, ctx->stream));
     if ((rc = expr_eval_enqueue_locked(ctx, e, d_vars, n_items, d_out, d_err, 0))) return rc;
@@ -390,7 +390,7 @@ int pg_features_eval_dev(pg_ctx* ctx, const pg_features* fs, const pg_expr* e, c
     if (nv) {
         void* buf;
         int rc;
-        if ((rc = pg::scratch_reserve(ctx, 16, (size_t)n * nv * 8, &buf))) return rc;
+        if ((rc = pg::scratch_reserve(ctx, pg::kSlotExprVars, (size_t)n * nv * 8, &buf))) return rc;
         d_vars = (double*)buf;
         const uint32_t total = n * (uint32_t)nv;
         pg::features_bind_f64_kernel<<<(total + 255) / 256, 256, 0, ctx->stream>>>(h, (uint32_t)nv, fs->rows, d_rows, n, d_vars);
@@ -933,12 +933,13 @@ int pg_expr_eval(pg_ctx* ctx, const pg_expr* e, const double* vars, uint32_t n_i
     PG_REQUIRE(e->vars.empty() || vars, "pg_expr_eval: vars is NULL but the expression has parameters");
     if (n_items == 0) return PG_OK;
     std::lock_guard<std::mutex> g(ctx->mu);
-    void* buf;
+    double *d_v, *d_o;
     int rc;
     const size_t vb = e->vars.size() * (size_t)n_items * 8, ob = (size_t)n_items * 8;
-    if ((rc = pg::scratch_reserve(ctx, 5, vb + ob + 256, &buf))) return rc;
-    double* d_v = (double*)buf;
-    double* d_o = (double*)((char*)buf + ((vb + 255) & ~(size_t)255));
+    if ((rc = pg::scratch_carve(ctx, pg::kSlotStaging, [&](pg::Carve& c) {
+            d_v = c.take<double>(e->vars.size() * (size_t)n_items);
+            d_o = c.take<double>(n_items);
+        }))) return rc;
     if (vb) PG_HIP(hipMemcpyAsync(d_v, vars, vb, hipMemcpyHostToDevice, ctx->stream));
     if ((rc = pg::expr_eval_locked(ctx, e, d_v, n_items, d_o))) return rc;     // scores untouched on error
     PG_HIP(hipMemcpyAsync(out_scores, d_o, ob, hipMemcpyDeviceToHost, ctx->stream));

@@ -320,8 +320,6 @@ __global__ __launch_bounds__(kFaninThreads) void fanin_merge_kernel(FaninArgs a)
     }
 }
 
-inline size_t fanin_al(size_t x) { return (x + 255) & ~(size_t)255; }
-
 }  // namespace
 
 // caller holds ctx->mu; one launch on the context's stream, no synchronisation
@@ -347,13 +345,12 @@ int fanin_merge_locked(pg_ctx* ctx, const pg_fanin_source* src, uint32_t n_src, 
     a.slot_bits = bits;
     a.lds_max_cap = std::min(ctx->knobs.fanin_lds_max_cap, kFaninLdsMaxCap);
     const size_t slots = (size_t)1 << bits;
-    const size_t b_keys = fanin_al((size_t)nq * slots * 8), b_val = fanin_al((size_t)nq * slots * 4), b_mask = fanin_al((size_t)nq * cap * 4);
-    void* buf;
     int rc;
-    if ((rc = scratch_reserve(ctx, 20, b_keys + b_val + b_mask, &buf))) return rc;
-    a.gkeys = (unsigned long long*)buf;
-    a.gval = (uint32_t*)((char*)buf + b_keys);
-    a.gmask = (uint32_t*)((char*)buf + b_keys + b_val);
+    if ((rc = scratch_carve(ctx, kSlotFanin, [&](Carve& c) {
+            a.gkeys = c.take<unsigned long long>((size_t)nq * slots);
+            a.gval = c.take<uint32_t>((size_t)nq * slots);
+            a.gmask = c.take<uint32_t>((size_t)nq * cap);
+        }))) return rc;
     a.out_rows = d_out_rows;
     a.out_score = reinterpret_cast<unsigned long long*>(d_out_score);
     a.out_source = d_out_source;

@@ -73,7 +73,7 @@ static size_t dtype_size(int dt) {
     return 0;
 }
 
-// descriptors of the requested columns (+ optional per-column scale / bias) → device scratch slot 1
+// descriptors of the requested columns (+ optional per-column scale / bias) → kSlotHostStage
 static int stage_descs(pg_ctx* ctx, const pg_features* fs, const int32_t* col_idx, uint32_t F, bool ints_only,
                        const char* who, const float* scale, const float* bias, ColDesc** d_desc,
                        float** d_scale, float** d_bias) {
@@ -90,12 +90,14 @@ static int stage_descs(pg_ctx* ctx, const pg_features* fs, const int32_t* col_id
         }
         h[f] = ColDesc{c.d, c.dtype, 0, c.def};
     }
-    const size_t desc_bytes = ((size_t)F * sizeof(ColDesc) + 255) & ~(size_t)255;
-    void* p;
+    ColDesc* p;
+    float* aux;                                       // scales [F], biases [F]
     int rc;
-    if ((rc = scratch_reserve(ctx, 1, desc_bytes + (size_t)F * 8 + 256, &p))) return rc;
+    if ((rc = scratch_carve(ctx, kSlotHostStage, [&](Carve& c) {
+            p = c.take<ColDesc>(F);
+            aux = c.take<float>((size_t)2 * F);
+        }))) return rc;
     PG_HIP(hipMemcpyAsync(p, h.data(), (size_t)F * sizeof(ColDesc), hipMemcpyHostToDevice, ctx->stream));
-    float* aux = (float*)((char*)p + desc_bytes);
     *d_scale = nullptr;
     *d_bias = nullptr;
     if (scale) {
@@ -107,7 +109,7 @@ static int stage_descs(pg_ctx* ctx, const pg_features* fs, const int32_t* col_id
         PG_HIP(hipMemcpyAsync(aux + F, bias, (size_t)F * 4, hipMemcpyHostToDevice, ctx->stream));
     }
     PG_HIP(hipStreamSynchronize(ctx->stream));       // the host staging buffers go out of scope
-    *d_desc = (ColDesc*)p;
+    *d_desc = p;
     return PG_OK;
 }
 

@@ -274,8 +274,8 @@ void shard_range(uint64_t total, uint32_t G, uint32_t g, uint64_t* b, uint64_t* 
     *e = *b + base + (g < rem ? 1 : 0);
 }
 
-size_t blk_rows_bytes(size_t n) { return (n * 8 + 255) & ~(size_t)255; }
-size_t blk_bytes(size_t n) { return blk_rows_bytes(n) + ((n * 4 + 255) & ~(size_t)255); }
+size_t blk_rows_bytes(size_t n) { return align_up(n * 8); }
+size_t blk_bytes(size_t n) { return blk_rows_bytes(n) + align_up(n * 4); }
 
 void free_lane_buffers(Lane& l) {
     if (!l.ctx) return;
@@ -593,7 +593,7 @@ int pg_owned_compact_dev(pg_ctx* ctx, const pg_table* t, const uint64_t* d_rows,
     std::lock_guard<std::mutex> g(ctx->mu);
     void* p;
     int rc;
-    if ((rc = pg::scratch_reserve(ctx, 9, 4096, &p))) return rc;
+    if ((rc = pg::scratch_reserve(ctx, pg::kSlotGroup, 4096, &p))) return rc;
     uint32_t* d_cnt = (uint32_t*)p;
     pg::owned_count_kernel<<<nq, 256, 0, ctx->stream>>>(d_rows, k, t->row_offset, t->rows, d_cnt);
     pg::owned_scan_kernel<<<1, 256, 0, ctx->stream>>>(d_cnt, nq, d_req_offsets);

@@ -791,7 +791,7 @@ int index_build_locked(pg_ctx* ctx, const pg_table* t, const pg_index_params& p,
     int rc;
     // index memory: the permutation and the per-list arrays (one allocation)
     if ((rc = dalloc((void**)&ix->d_perm, rows * 4, owned))) return rc;
-    const size_t off_b = ((size_t)(nl + 1) * 4 + 255) & ~(size_t)255, cent_b = (size_t)nl * dim * 4, lists_b = ((size_t)nl * 4 + 255) & ~(size_t)255;
+    const size_t off_b = align_up((size_t)(nl + 1) * 4), cent_b = (size_t)nl * dim * 4, lists_b = align_up((size_t)nl * 4);
     if ((rc = dalloc(&ix->d_small, off_b + cent_b + 2 * lists_b, owned))) return rc;
     ix->d_off = (uint32_t*)ix->d_small;
     ix->d_cent = (float*)((char*)ix->d_small + off_b);
@@ -891,7 +891,7 @@ int index_refresh_locked(pg_ctx* ctx, const pg_index* ix, bool incremental, Refr
     hipStream_t s = ctx->stream;
     int rc;
     if ((rc = dalloc((void**)&o->perm, rows * 4, owned))) return rc;
-    const size_t off_b = ((size_t)(nl + 1) * 4 + 255) & ~(size_t)255, cent_b = (size_t)nl * dim * 4, lists_b = ((size_t)nl * 4 + 255) & ~(size_t)255;
+    const size_t off_b = align_up((size_t)(nl + 1) * 4), cent_b = (size_t)nl * dim * 4, lists_b = align_up((size_t)nl * 4);
     if ((rc = dalloc(&o->small, off_b + cent_b + 2 * lists_b, owned))) return rc;
     uint32_t* const n_off = (uint32_t*)o->small;
     float* const n_cent = (float*)((char*)o->small + off_b);
@@ -987,29 +987,7 @@ int index_refresh_locked(pg_ctx* ctx, const pg_index* ix, bool incremental, Refr
     return PG_OK;
 }
 
-// per-call scratch of an index recall (slot 17); NOMEM instead of a device error
-int index_scratch(pg_ctx* ctx, size_t bytes, void** out) {
-    Scratch& s = ctx->scratch[17];
-    if (s.cap < bytes) {
-        if (s.p) {
-            PG_HIP(hipStreamSynchronize(ctx->stream));
-            PG_HIP(hipFree(s.p));
-            s.p = nullptr;
-            s.cap = 0;
-        }
-        const size_t cap = (bytes + (1u << 20) - 1) & ~((size_t)(1u << 20) - 1);
-        if (hipMalloc(&s.p, cap) != hipSuccess) {
-            (void)hipGetLastError();
-            s.p = nullptr;
-            return PG_ERR_NOMEM;
-        }
-        s.cap = cap;
-    }
-    *out = s.p;
-    return PG_OK;
-}
-
-// slot 17 of one batch: U [nq][nl] | qn [nq] f64 | nqv [nq] | Bkey [nq] | probe rows [nq] | counts [nq] | the plan's words [16] |
+// kSlotIndexSearch of one batch (NOMEM instead of a device error when it cannot grow): U [nq][nl] | qn [nq] f64 | nqv [nq] | Bkey [nq] | probe rows [nq] | counts [nq] | the plan's words [16] |
 //          slice counts [nq][kSlices] | scan threshold [nq]
 struct SearchBufs {
     float* U;
@@ -1020,24 +998,20 @@ struct SearchBufs {
     uint32_t* cntg;
     float* thr_scan;                     // the probe's K-th scores, frozen for the scan's list selection
 };
-size_t search_bytes(uint32_t nq, uint32_t nl) {
-    const size_t u_b = ((size_t)nq * nl * 4 + 255) & ~(size_t)255;
-    return u_b + (size_t)nq * (8 + 4 + 4 + 4 + 4 + 4) + (size_t)nq * kSlices * 4 + 1024;
-}
 int search_bufs(pg_ctx* ctx, uint32_t nq, uint32_t nl, SearchBufs* b) {
-    const size_t u_b = ((size_t)nq * nl * 4 + 255) & ~(size_t)255;
-    void* base;
-    if (index_scratch(ctx, search_bytes(nq, nl), &base)) return PG_ERR_NOMEM;
-    b->U = (float*)base;
-    b->qn = (double*)((char*)base + u_b);
-    b->nqv = (float*)(b->qn + nq);
-    b->Bkey = (uint32_t*)(b->nqv + nq);
-    b->probe = b->Bkey + nq;
-    b->dcount = b->probe + nq;
-    b->pw = (IndexPlanWords*)(b->dcount + nq);         // (8-byte aligned: u_b + 24 nq)
-    b->cntg = (uint32_t*)b->pw + 16;
-    b->thr_scan = (float*)(b->cntg + (size_t)nq * kSlices);
-    return PG_OK;
+    const int rc = scratch_carve(ctx, kSlotIndexSearch, [&](Carve& c) {
+        b->U = c.take<float>((size_t)nq * nl);
+        b->qn = c.take<double>(nq);
+        b->nqv = c.take<float>(nq);
+        b->Bkey = c.take<uint32_t>(nq);
+        b->probe = c.take<uint32_t>(nq);
+        b->dcount = c.take<uint32_t>(nq);
+        uint32_t* words = c.take<uint32_t>(16 + (size_t)nq * kSlices);      // ONE region: the plan's 16 words, the slice counts behind them
+        b->pw = (IndexPlanWords*)words;
+        b->cntg = words + 16;
+        b->thr_scan = c.take<float>(nq);
+    }, true);
+    return rc ? PG_ERR_NOMEM : PG_OK;
 }
 
 // the bounds of a batch: qn[q] >= ||q|| (and *flag |= 1 for a non-finite query), then U[q][L] — the one launch of the
@@ -1194,7 +1168,7 @@ int index_recall_locked(pg_ctx* ctx, pg_index* ix, const float* d_q, uint32_t nq
     return PG_OK;
 }
 
-// pg_index_recall_topk[_l2][_dev]: host, the queries and outputs are host memory (staged through scratch slot 5)
+// pg_index_recall_topk[_l2][_dev]: host, the queries and outputs are host memory (staged through kSlotStaging)
 int index_entry(const char* who, pg_ctx* ctx, const pg_index* ixc, const float* q, uint32_t nq, uint32_t k, uint64_t* rows, float* sc,
                 uint32_t* out_count, bool l2, bool host) {
     int rc;
@@ -1246,7 +1220,7 @@ int where_lists_build(pg_ctx* ctx, const pg_index* ix, const RowFilter& f, std::
     if (hipMemcpyAsync(&admitted, off + nl, 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
         return done(PG_ERR_DEVICE);
     auto wl = std::make_shared<WhereLists>();
-    const size_t off_b = (((size_t)nl + 1) * 4 + 255) & ~(size_t)255;
+    const size_t off_b = align_up(((size_t)nl + 1) * 4);
     if (hipMalloc(&wl->d, off_b + (size_t)admitted * 4 + 16) != hipSuccess) {
         (void)hipGetLastError();
         wl->d = nullptr;
@@ -1397,8 +1371,8 @@ int index_plan_prepare(RecallJob* j) {
         sv.skipped_switch++;
         return PG_OK;
     }
-    void* base;
-    if (index_scratch(j->ctx, search_bytes(j->nq, ix->n_lists), &base)) return PG_OK;     // (no memory: the table's plans)
+    SearchBufs room;
+    if (search_bufs(j->ctx, j->nq, ix->n_lists, &room)) return PG_OK;     // (no memory: the table's plans)
     for (int i = j->n_plans; i > 0; --i) j->plans[i] = j->plans[i - 1];
     j->plans[0] = kIndexPlan;
     j->n_plans++;
@@ -1582,7 +1556,7 @@ int pg_index_refresh(pg_ctx* ctx, pg_index* ix, const pg_index_refresh_params* p
             return PG_ERR_DEVICE;
         }
         const uint32_t nl = ix->n_lists;
-        const size_t off_b = ((size_t)(nl + 1) * 4 + 255) & ~(size_t)255, cent_b = (size_t)nl * ix->dim * 4, lists_b = ((size_t)nl * 4 + 255) & ~(size_t)255;
+        const size_t off_b = pg::align_up((size_t)(nl + 1) * 4), cent_b = (size_t)nl * ix->dim * 4, lists_b = pg::align_up((size_t)nl * 4);
         ix->d_perm = o.perm;
         ix->d_small = o.small;
         ix->d_off = (uint32_t*)ix->d_small;
@@ -1759,7 +1733,7 @@ int pg_index_bounds(pg_ctx* ctx, const pg_index* ix, const float* queries, uint3
     const size_t qb = (size_t)nq * ix->dim * 4;
     void* buf;
     int rc;
-    if ((rc = pg::scratch_reserve(ctx, 5, qb, &buf))) return rc;
+    if ((rc = pg::scratch_reserve(ctx, pg::kSlotStaging, qb, &buf))) return rc;
     pg::SearchBufs sb;
     if ((rc = pg::search_bufs(ctx, nq, ix->n_lists, &sb))) return rc;
     PG_HIP(hipMemcpyAsync(buf, queries, qb, hipMemcpyHostToDevice, s));

@@ -424,14 +424,15 @@ extern "C" int pg_index_screen_probe(pg_ctx* ctx, uint32_t dim, const float* row
     hipStream_t s = ctx->stream;
     const size_t xb = (size_t)n * dim * 4, cb = (size_t)n_lists * dim * 4, ob = (size_t)n * n_lists * 4;
     const size_t wb = pg::assign_screen_ws_bytes(n_lists, dim);
-    void* buf;
-    int rc;
-    if ((rc = pg::scratch_reserve(ctx, 5, xb + cb + 2 * ob + wb + 1024, &buf))) return rc;
-    float* const d_x = (float*)buf;
-    float* const d_c = (float*)((char*)buf + xb);
-    float* const d_s = (float*)((char*)d_c + cb);
-    float* const d_e = (float*)((char*)d_s + ob);
-    const pg::ScreenWs w = pg::screen_ws((char*)buf + ((xb + cb + 2 * ob + 255) & ~(size_t)255), n_lists, dim);
+    float *d_x, *d_c, *d_s, *d_e; void* ws; int rc;
+    if ((rc = pg::scratch_carve(ctx, pg::kSlotStaging, [&](pg::Carve& c) {
+            d_x = c.take<float>((size_t)n * dim);
+            d_c = c.take<float>((size_t)n_lists * dim);
+            d_s = c.take<float>((size_t)n * n_lists);
+            d_e = c.take<float>((size_t)n * n_lists);
+            ws = c.bytes(wb);
+        }))) return rc;
+    const pg::ScreenWs w = pg::screen_ws(ws, n_lists, dim);
     PG_HIP(hipMemcpyAsync(d_x, rows, xb, hipMemcpyHostToDevice, s));
     PG_HIP(hipMemcpyAsync(d_c, centroids, cb, hipMemcpyHostToDevice, s));
     bool in_range;

@@ -173,7 +173,7 @@ int pg_hbm_read_probe(pg_ctx* ctx, const pg_table* t, int reps, double* out_gbps
     std::lock_guard<std::mutex> g(ctx->mu);
     void* sink;
     int rc;
-    if ((rc = pg::scratch_reserve(ctx, 4, 4096, &sink))) return rc;
+    if ((rc = pg::scratch_reserve(ctx, pg::kSlotStatus, 4096, &sink))) return rc;
     const uint64_t n16 = bytes / 16;
     const int grid = ctx->num_cus * 8;
     double best = 0.0;

@@ -139,29 +139,26 @@ int recommend_bind_vars(const pg_expr* e, const char* const* names, int n_algos,
 
 int post_scratch(pg_ctx* ctx, const RecommendCall& c, uint32_t nq, PostScratch* ps) {
     const uint32_t n = nq * c.k;
-    void* buf;
     int rc;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t b_local = al((size_t)n * 4), b_off = al((size_t)(nq + 1) * 4), b_err = al((size_t)kMaxQueries * 4);
     // variables of the widest expression + one f64 result per score rewrite
     int wide = std::max(c.nv, 1);
     const int n_rw = expr_num_rewrites(c.e);
     for (int r = 0; r < n_rw; ++r) wide = std::max(wide, expr_rewrite_num_vars(c.e, r));
-    const size_t b_vars = al((size_t)(wide + n_rw) * n * 8);
-    if ((rc = scratch_reserve(ctx, 8, b_local + b_off + b_err + b_vars, &buf))) return rc;
-    ps->d_local = (uint32_t*)buf;
-    ps->d_off = (uint32_t*)((char*)buf + b_local);
-    ps->d_err = (uint32_t*)((char*)buf + b_local + b_off);
-    ps->d_vars = (double*)((char*)buf + b_local + b_off + b_err);
+    if ((rc = scratch_carve(ctx, kSlotPipe, [&](Carve& s) {
+            ps->d_local = s.take<uint32_t>(n);
+            ps->d_off = s.take<uint32_t>((size_t)nq + 1);
+            ps->d_err = s.take<uint32_t>(kMaxQueries);
+            ps->d_vars = s.take<double>((size_t)(wide + n_rw) * n);      // ONE region: the variables, the rewrites' results behind them
+        }))) return rc;
     ps->c_rows = nullptr; ps->c_rel = nullptr; ps->c_emb = nullptr; ps->c_bail = nullptr;
     if (c.rerank.kind) {
         const size_t nc = (size_t)nq * c.rerank.candidates;
-        const size_t b_rows = al(nc * 8), b_rel = al(nc * 8), b_emb = al(nc * c.t->dim * 4), b_bail = al((size_t)kMaxQueries * 4);
-        if ((rc = scratch_reserve(ctx, 10, b_rows + b_rel + b_emb + b_bail, &buf))) return rc;
-        ps->c_rows = (uint64_t*)buf;
-        ps->c_rel = (double*)((char*)buf + b_rows);
-        ps->c_emb = (float*)((char*)buf + b_rows + b_rel);
-        ps->c_bail = (uint32_t*)((char*)buf + b_rows + b_rel + b_emb);
+        if ((rc = scratch_carve(ctx, kSlotRerank, [&](Carve& s) {
+                ps->c_rows = s.take<uint64_t>(nc);
+                ps->c_rel = s.take<double>(nc);
+                ps->c_emb = s.take<float>(nc * c.t->dim);
+                ps->c_bail = s.take<uint32_t>(kMaxQueries);
+            }))) return rc;
     }
     return PG_OK;
 }
@@ -437,11 +434,11 @@ int pg_fuse_scores_dev(pg_ctx* ctx, const pg_expr* e, const char* const* plane_n
     int wide = std::max(nv, 1);
     for (int r = 0; r < n_rw; ++r) wide = std::max(wide, pg::expr_rewrite_num_vars(e, r));
     std::lock_guard<std::mutex> g(ctx->mu);
-    void* buf;
-    const size_t b_vars = (((size_t)(wide + n_rw) * n * 8) + 255) & ~(size_t)255;
-    if ((rc = pg::scratch_reserve(ctx, 15, b_vars + (size_t)pg::kMaxQueries * 4, &buf))) return rc;
-    double* const d_vars = (double*)buf;
-    uint32_t* const d_err = (uint32_t*)((char*)buf + b_vars);
+    double* d_vars; uint32_t* d_err;
+    if ((rc = pg::scratch_carve(ctx, pg::kSlotFuse, [&](pg::Carve& c) {
+            d_vars = c.take<double>((size_t)(wide + n_rw) * n);
+            d_err = c.take<uint32_t>(pg::kMaxQueries);
+        }))) return rc;
     if ((rc = pg::fuse_scores_enqueue_locked(ctx, e, var_src.data(), nv, d_recall, d_rank, rank_stride, n, 0u, d_vars, d_err, d_fused))) return rc;
     // (items_per_flag = 0: one flag for the call; read through the context's pinned status words)
     PG_HIP(hipMemcpyAsync(ctx->h_status + 321, d_err, 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -531,12 +528,12 @@ int pg_recommend_cascade_dnn3_dev(pg_ctx* ctx, const pg_table* t, const pg_model
     PG_HIP(hipSetDevice(ctx->device));
     pg::TableRead tr(t->rw);             // both rank stages and their padding tests read one version of the table
     // the coarse stage's own outputs: model scores, fused scores, order — all [nq][cap]
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    void* buf;
-    if ((rc = pg::scratch_reserve(ctx, 22, al(n * 8) + al(n * 4) + n * 4, &buf))) return rc;
-    double* const c_fused = (double*)buf;
-    float* const c_rank = (float*)((char*)buf + al(n * 8));
-    uint32_t* const c_order = (uint32_t*)((char*)buf + al(n * 8) + al(n * 4));
+    double* c_fused; float* c_rank; uint32_t* c_order;
+    if ((rc = pg::scratch_carve(ctx, pg::kSlotCoarse, [&](pg::Carve& c) {
+            c_fused = c.take<double>(n);
+            c_rank = c.take<float>(n);
+            c_order = c.take<uint32_t>(n);
+        }))) return rc;
     pg::RecommendCall cc, cf;
     cc.t = t; cc.algos[0].m = m_coarse; cc.n_algos = 1; cc.e = e_coarse; cc.var_src = src_c.data(); cc.nv = pg_expr_num_vars(e_coarse);
     cc.d_queries = d_user_vecs; cc.nq = nq; cc.k = cap;

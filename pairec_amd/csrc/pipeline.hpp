@@ -100,7 +100,7 @@ int recommend_verify(pg_ctx* ctx, PipeRun* r, bool* ok, const RecommendCall* c =
 struct PostScratch {
     uint32_t *d_local, *d_off, *d_err;
     double* d_vars;
-    // re-rank stage (scratch slot 10)
+    // re-rank stage (kSlotRerank)
     uint64_t* c_rows;
     double* c_rel;
     float* c_emb;

@@ -1048,20 +1048,15 @@ struct RankScratch {
 
 static int rank_scratch(pg_ctx* ctx, uint32_t n_req, uint32_t max_tiles, uint32_t per_req_floats,
                         RankScratch* rs) {
-    void* p;
-    int rc;
-    const size_t ints = (size_t)3 * max_tiles + 64 + n_req;
-    const size_t bytes = ints * 4 + ((size_t)n_req * per_req_floats + (size_t)n_req * kFmUserStride) * 4 + 256;
-    if ((rc = scratch_reserve(ctx, 6, bytes, &p))) return rc;
-    uint32_t* u = (uint32_t*)p;
-    rs->tile_req = u;
-    rs->tile_item0 = u + max_tiles;
-    rs->tile_cnt = u + 2 * (size_t)max_tiles;
-    rs->n_tiles = u + 3 * (size_t)max_tiles;
-    rs->req_tile0 = rs->n_tiles + 64;
-    rs->c1 = (float*)(rs->req_tile0 + n_req);
-    rs->fm_user = rs->c1 + (size_t)n_req * per_req_floats;
-    return PG_OK;
+    return scratch_carve(ctx, kSlotRankTiles, [&](Carve& c) {
+        rs->tile_req = c.take<uint32_t>(max_tiles);
+        rs->tile_item0 = c.take<uint32_t>(max_tiles);
+        rs->tile_cnt = c.take<uint32_t>(max_tiles);
+        rs->n_tiles = c.take<uint32_t>(64);
+        rs->req_tile0 = c.take<uint32_t>(n_req);
+        rs->c1 = c.take<float>((size_t)n_req * per_req_floats);
+        rs->fm_user = c.take<float>((size_t)n_req * kFmUserStride);
+    });
 }
 
 // ---- shapes the fused kernel is instantiated for ----------------------------------------------------------------
@@ -1225,7 +1220,7 @@ int rank_dnn3_dev_locked(pg_ctx* ctx, const pg_model* m, const pg_table* t,
     if (ws && m->n_out > 1) {
         // the weights-stationary kernel's partials of heads 1..: a block per workgroup (its LDS is full)
         void* hp;
-        if ((rc = scratch_reserve(ctx, 14, (size_t)ctx->num_cus * (kMaxHeads - 1) * 4 * kWsItems * 4, &hp))) return rc;
+        if ((rc = scratch_reserve(ctx, kSlotRankHeads, (size_t)ctx->num_cus * (kMaxHeads - 1) * 4 * kWsItems * 4, &hp))) return rc;
         a.head_part = (float*)hp;
     }
     if (ws) {
@@ -1239,9 +1234,13 @@ int rank_dnn3_dev_locked(pg_ctx* ctx, const pg_model* m, const pg_table* t,
         if ((rc = launch_dnn3_ls(ctx, m->h1, m->h2, a))) return rc;
         ctx->stats.rank_ls_calls++;
     } else if (h2_k) {
-        void* fbp;
-        if ((rc = scratch_reserve(ctx, 17, ((size_t)3 * max_tiles + 64) * 4, &fbp))) return rc;
         MlpArgs h = a;
+        if ((rc = scratch_carve(ctx, kSlotIndexSearch, [&](Carve& c) {
+                h.fb_tile_req = c.take<uint32_t>(max_tiles);
+                h.fb_tile_item0 = c.take<uint32_t>(max_tiles);
+                h.fb_tile_cnt = c.take<uint32_t>(max_tiles);
+                h.fb_n_tiles = c.take<uint32_t>(64);
+            }))) return rc;
         h.w1p = m->h_w1p;
         h.w2p = m->h_w2p;
         h.w1p_lo = m->h_w1p_lo;
@@ -1250,10 +1249,6 @@ int rank_dnn3_dev_locked(pg_ctx* ctx, const pg_model* m, const pg_table* t,
         h.f16_hs = m->h_hs;
         h.f16_scale = std::ldexp(1.0f, kH2S);
         h.f16_unscale = std::ldexp(1.0f, -kH2S);
-        h.fb_tile_req = (uint32_t*)fbp;
-        h.fb_tile_item0 = h.fb_tile_req + max_tiles;
-        h.fb_tile_cnt = h.fb_tile_req + 2 * (size_t)max_tiles;
-        h.fb_n_tiles = h.fb_tile_req + 3 * (size_t)max_tiles;
         h.f16_stats = m->h_stats;
         PG_HIP(hipMemsetAsync(h.fb_n_tiles, 0, 4, ctx->stream));
         if ((rc = launch_dnn3_h2(ctx, m->h1, m->h2, m->f16_nprod, h))) return rc;
@@ -1422,7 +1417,7 @@ int rank_fm2t_rows_dev_locked(pg_ctx* ctx, const pg_model* m, const pg_features*
     if (n_items == 0 || n_req == 0) return PG_OK;
     void* ids;
     int rc;
-    if ((rc = scratch_reserve(ctx, 0, (size_t)n_items * m->nif * 4, &ids))) return rc;
+    if ((rc = scratch_reserve(ctx, kSlotRows, (size_t)n_items * m->nif * 4, &ids))) return rc;
     if ((rc = features_gather_i32_locked(ctx, fs, item_field_cols, m->nif, d_cand, n_items, (int32_t*)ids, "rank_fm2t_rows"))) return rc;
     return rank_fm2t_dev_locked(ctx, m, d_user, d_ufids, (const int32_t*)ids, d_off, n_req, n_items, d_out);
 }
@@ -1669,17 +1664,17 @@ int pg_rank_dnn3(pg_ctx* ctx, const pg_model* m, const pg_table* t, const float*
                    cand_rows[i], (unsigned long long)t->rows);
     std::lock_guard<std::mutex> g(ctx->mu);
     pg::TableRead tr(t->rw);
-    void* buf;
+    float *d_u, *d_s;
+    uint32_t *d_c, *d_o;
     int rc;
     const size_t ub = (size_t)n_req * m->d_user * 4, cb = (size_t)n_items * 4, ob = (size_t)(n_req + 1) * 4;
     const size_t sb = (size_t)n_items * 4 * m->n_out;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    if ((rc = pg::scratch_reserve(ctx, 5, al(ub) + al(cb) + al(ob) + al(sb), &buf))) return rc;
-    char* b = (char*)buf;
-    float* d_u = (float*)b;
-    uint32_t* d_c = (uint32_t*)(b + al(ub));
-    uint32_t* d_o = (uint32_t*)(b + al(ub) + al(cb));
-    float* d_s = (float*)(b + al(ub) + al(cb) + al(ob));
+    if ((rc = pg::scratch_carve(ctx, pg::kSlotStaging, [&](pg::Carve& c) {
+            d_u = c.take<float>(ub / 4);
+            d_c = c.take<uint32_t>(cb / 4);
+            d_o = c.take<uint32_t>(ob / 4);
+            d_s = c.take<float>(sb / 4);
+        }))) return rc;
     PG_HIP(hipMemcpyAsync(d_u, user_vecs, ub, hipMemcpyHostToDevice, ctx->stream));
     PG_HIP(hipMemcpyAsync(d_c, cand_rows, cb, hipMemcpyHostToDevice, ctx->stream));
     PG_HIP(hipMemcpyAsync(d_o, req_offsets, ob, hipMemcpyHostToDevice, ctx->stream));
@@ -1700,12 +1695,13 @@ int pg_fm2t_user_embedding(pg_ctx* ctx, const pg_model* m, const float* user_vec
     PG_REQUIRE(m->kind == PG_MODEL_FM_TWOTOWER, "pg_fm2t_user_embedding: model is not FM_TWOTOWER");
     if (n_req == 0) return PG_OK;
     std::lock_guard<std::mutex> g(ctx->mu);
-    void* buf;
+    float *d_u, *d_o;
     int rc;
-    const size_t ub = ((size_t)n_req * m->d_user * 4 + 255) & ~(size_t)255, ob = (size_t)n_req * m->to * 4;
-    if ((rc = pg::scratch_reserve(ctx, 5, ub + ob, &buf))) return rc;
-    float* d_u = (float*)buf;
-    float* d_o = (float*)((char*)buf + ub);
+    const size_t ob = (size_t)n_req * m->to * 4;
+    if ((rc = pg::scratch_carve(ctx, pg::kSlotStaging, [&](pg::Carve& c) {
+            d_u = c.take<float>((size_t)n_req * m->d_user);
+            d_o = c.take<float>(ob / 4);
+        }))) return rc;
     PG_HIP(hipMemcpyAsync(d_u, user_vecs, (size_t)n_req * m->d_user * 4, hipMemcpyHostToDevice, ctx->stream));
     if ((rc = pg::fm2t_user_embedding_locked(ctx, m, d_u, n_req, d_o))) return rc;
     PG_HIP(hipMemcpyAsync(out, d_o, ob, hipMemcpyDeviceToHost, ctx->stream));
@@ -1759,19 +1755,20 @@ int pg_rank_fm2t_rows(pg_ctx* ctx, const pg_model* m, const pg_features* fs, con
         PG_REQUIRE(user_field_ids[i] >= 0 && (uint32_t)user_field_ids[i] < m->vocab,
                    "pg_rank_fm2t_rows: user field id %d outside vocab %u", user_field_ids[i], m->vocab);
     std::lock_guard<std::mutex> g(ctx->mu);
-    void* buf;
+    float *d_u, *d_s;
+    int32_t *d_uf, *d_if;
+    uint32_t *d_c, *d_o;
     int rc;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t ub = (size_t)n_req * m->d_user * 4, ufb = (size_t)n_req * m->nuf * 4, cb = (size_t)n_items * 4;
     const size_t ifb = (size_t)n_items * m->nif * 4, ob = (size_t)(n_req + 1) * 4, sb = (size_t)n_items * 4;
-    if ((rc = pg::scratch_reserve(ctx, 5, al(ub) + al(ufb) + al(cb) + al(ifb) + al(ob) + al(sb), &buf))) return rc;
-    char* b = (char*)buf;
-    float* d_u = (float*)b; b += al(ub);
-    int32_t* d_uf = (int32_t*)b; b += al(ufb);
-    uint32_t* d_c = (uint32_t*)b; b += al(cb);
-    int32_t* d_if = (int32_t*)b; b += al(ifb);
-    uint32_t* d_o = (uint32_t*)b; b += al(ob);
-    float* d_s = (float*)b;
+    if ((rc = pg::scratch_carve(ctx, pg::kSlotStaging, [&](pg::Carve& c) {
+            d_u = c.take<float>(ub / 4);
+            d_uf = c.take<int32_t>(ufb / 4);
+            d_c = c.take<uint32_t>(cb / 4);
+            d_if = c.take<int32_t>(ifb / 4);
+            d_o = c.take<uint32_t>(ob / 4);
+            d_s = c.take<float>(sb / 4);
+        }))) return rc;
     PG_HIP(hipMemcpyAsync(d_u, user_vecs, ub, hipMemcpyHostToDevice, ctx->stream));
     PG_HIP(hipMemcpyAsync(d_uf, user_field_ids, ufb, hipMemcpyHostToDevice, ctx->stream));
     PG_HIP(hipMemcpyAsync(d_c, cand_rows, cb, hipMemcpyHostToDevice, ctx->stream));
@@ -1802,18 +1799,19 @@ int pg_rank_fm2t(pg_ctx* ctx, const pg_model* m, const float* user_vecs, const i
         PG_REQUIRE(item_field_ids[i] >= 0 && (uint32_t)item_field_ids[i] < m->vocab,
                    "pg_rank_fm2t: item field id %d outside vocab %u", item_field_ids[i], m->vocab);
     std::lock_guard<std::mutex> g(ctx->mu);
-    void* buf;
+    float *d_u, *d_s;
+    int32_t *d_uf, *d_if;
+    uint32_t* d_o;
     int rc;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t ub = (size_t)n_req * m->d_user * 4, ufb = (size_t)n_req * m->nuf * 4;
     const size_t ifb = (size_t)n_items * m->nif * 4, ob = (size_t)(n_req + 1) * 4, sb = (size_t)n_items * 4;
-    if ((rc = pg::scratch_reserve(ctx, 5, al(ub) + al(ufb) + al(ifb) + al(ob) + al(sb), &buf))) return rc;
-    char* b = (char*)buf;
-    float* d_u = (float*)b; b += al(ub);
-    int32_t* d_uf = (int32_t*)b; b += al(ufb);
-    int32_t* d_if = (int32_t*)b; b += al(ifb);
-    uint32_t* d_o = (uint32_t*)b; b += al(ob);
-    float* d_s = (float*)b;
+    if ((rc = pg::scratch_carve(ctx, pg::kSlotStaging, [&](pg::Carve& c) {
+            d_u = c.take<float>(ub / 4);
+            d_uf = c.take<int32_t>(ufb / 4);
+            d_if = c.take<int32_t>(ifb / 4);
+            d_o = c.take<uint32_t>(ob / 4);
+            d_s = c.take<float>(sb / 4);
+        }))) return rc;
     PG_HIP(hipMemcpyAsync(d_u, user_vecs, ub, hipMemcpyHostToDevice, ctx->stream));
     PG_HIP(hipMemcpyAsync(d_uf, user_field_ids, ufb, hipMemcpyHostToDevice, ctx->stream));
     PG_HIP(hipMemcpyAsync(d_if, item_field_ids, ifb, hipMemcpyHostToDevice, ctx->stream));
@@ -1905,18 +1903,19 @@ int pg_rank_fm2t_irows(pg_ctx* ctx, const pg_model* m, const pg_item_rows* ir, c
         PG_REQUIRE(user_field_ids[i] >= 0 && (uint32_t)user_field_ids[i] < m->vocab,
                    "pg_rank_fm2t_irows: user field id %d outside vocab %u", user_field_ids[i], m->vocab);
     std::lock_guard<std::mutex> g(ctx->mu);
-    void* buf;
+    float *d_u, *d_s;
+    int32_t* d_uf;
+    uint32_t *d_c, *d_o;
     int rc;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t ub = (size_t)n_req * m->d_user * 4, ufb = (size_t)n_req * m->nuf * 4, cb = (size_t)n_items * 4;
     const size_t ob = (size_t)(n_req + 1) * 4, sb = (size_t)n_items * 4;
-    if ((rc = pg::scratch_reserve(ctx, 5, al(ub) + al(ufb) + al(cb) + al(ob) + al(sb), &buf))) return rc;
-    char* b = (char*)buf;
-    float* d_u = (float*)b; b += al(ub);
-    int32_t* d_uf = (int32_t*)b; b += al(ufb);
-    uint32_t* d_c = (uint32_t*)b; b += al(cb);
-    uint32_t* d_o = (uint32_t*)b; b += al(ob);
-    float* d_s = (float*)b;
+    if ((rc = pg::scratch_carve(ctx, pg::kSlotStaging, [&](pg::Carve& c) {
+            d_u = c.take<float>(ub / 4);
+            d_uf = c.take<int32_t>(ufb / 4);
+            d_c = c.take<uint32_t>(cb / 4);
+            d_o = c.take<uint32_t>(ob / 4);
+            d_s = c.take<float>(sb / 4);
+        }))) return rc;
     PG_HIP(hipMemcpyAsync(d_u, user_vecs, ub, hipMemcpyHostToDevice, ctx->stream));
     PG_HIP(hipMemcpyAsync(d_uf, user_field_ids, ufb, hipMemcpyHostToDevice, ctx->stream));
     PG_HIP(hipMemcpyAsync(d_c, cand_rows, cb, hipMemcpyHostToDevice, ctx->stream));

@@ -2062,36 +2062,35 @@ constexpr uint32_t kCandSlack = 1u << 19;      // candidate capacity beyond K pe
 
 int recall_scratch(pg_ctx* ctx, uint32_t dim, uint32_t k, RecallScratch* rs) {
     const uint32_t cap = k + kCandSlack;
-    void* small;
     int rc;
-    const size_t qb16_bytes = (size_t)kScreenMaxNQB * (dim / 16) * 64 * 16;
-    const size_t small_bytes = (size_t)kMaxQueries * dim * 4 + qb16_bytes + (size_t)kMaxQueries * 40 + 2048 + (size_t)kQ4mWords * 4 + 256 + 64 +
-                               (size_t)kMaxQueries * (2 * 128 + 16 + 4) + 192 + (size_t)(kRecallStatusWords + kMaxQueries) * 4 + 64;
-    if ((rc = scratch_reserve(ctx, 2, small_bytes, &small))) return rc;
-    rs->qpad = (float*)small;
-    rs->qb16 = (uint4*)((char*)small + (size_t)kMaxQueries * dim * 4);
-    rs->thr = (float*)((char*)rs->qb16 + qb16_bytes);
-    rs->eps = rs->thr + kMaxQueries;
-    rs->thr_screen = rs->eps + kMaxQueries;
-    rs->cnt = (uint32_t*)(rs->thr_screen + kMaxQueries);
-    rs->susp_cnt = rs->cnt + kMaxQueries;
-    rs->overflow = rs->susp_cnt + kMaxQueries;
-    rs->qscale = (float*)(rs->overflow + 64 + kMaxQueries);      // overflow word, the valid counts [kMaxQueries] right behind it (+ 1), padding
-    rs->q4 = (uint32_t*)(rs->qscale + kMaxQueries);      // 4 x 128 B + 4 x 16 B
-    rs->thr_ref = (float*)(rs->q4 + 160);                // [kMaxQueries]
-    rs->pred_ms = rs->thr_ref + kMaxQueries;             // [kMaxQueries][2]
-    rs->susp2_cnt = (uint32_t*)(rs->pred_ms + 2 * kMaxQueries);                       // [kI4mMaxQueries] + two statistics words
-    rs->q4m = (uint32_t*)(((uintptr_t)(rs->susp2_cnt + kI4mMaxQueries + 2) + 63) & ~(uintptr_t)63);   // (16-byte fragment loads)
-    rs->q16 = (uint32_t*)(((uintptr_t)(rs->q4m + kQ4mWords) + 63) & ~(uintptr_t)63);              // [256][32] Qh | [256][32] Ql | [256][4]
-    rs->susp2w_cnt = rs->q16 + (size_t)kMaxQueries * (2 * 32 + 4);
-    rs->status = (uint32_t*)(((uintptr_t)(rs->susp2w_cnt + kMaxQueries + 2) + 63) & ~(uintptr_t)63);
-    rs->cnt_seen = rs->status + kRecallStatusWords;
-    void* c;
-    if ((rc = scratch_reserve(ctx, 3, (size_t)kMaxQueries * cap * (2 * 8 + 4) + (size_t)kMaxQueries * cap * 4, &c))) return rc;
-    rs->cand[0] = (uint64_t*)c;
-    rs->cand[1] = rs->cand[0] + (size_t)kMaxQueries * cap;
-    rs->susp = (uint32_t*)(rs->cand[1] + (size_t)kMaxQueries * cap);
-    rs->susp2 = rs->susp + (size_t)kMaxQueries * cap;
+    // the small regions stay packed as they always were (alignment = the element's own), but for the 64-byte fragment loads
+    if ((rc = scratch_carve(ctx, kSlotRecallSmall, [&](Carve& c) {
+            rs->qpad = c.take<float>((size_t)kMaxQueries * dim);
+            rs->qb16 = c.take<uint4>((size_t)kScreenMaxNQB * (dim / 16) * 64, 16);
+            rs->thr = c.take<float>(kMaxQueries, 4);
+            rs->eps = c.take<float>(kMaxQueries, 4);
+            rs->thr_screen = c.take<float>(kMaxQueries, 4);
+            rs->cnt = c.take<uint32_t>(kMaxQueries, 4);
+            rs->susp_cnt = c.take<uint32_t>(kMaxQueries, 4);
+            rs->overflow = c.take<uint32_t>(64 + kMaxQueries, 4);      // ONE region: the overflow word, the valid counts [kMaxQueries] right behind it (+ 1), padding
+            rs->qscale = c.take<float>(kMaxQueries, 4);
+            rs->q4 = c.take<uint32_t>(160, 4);                         // 4 x 128 B + 4 x 16 B
+            rs->thr_ref = c.take<float>(kMaxQueries, 4);
+            rs->pred_ms = c.take<float>(2 * (size_t)kMaxQueries, 4);
+            rs->susp2_cnt = c.take<uint32_t>(kI4mMaxQueries + 2, 4);   // + two statistics words
+            rs->q4m = c.take<uint32_t>(kQ4mWords, 64);                 // (16-byte fragment loads)
+            rs->q16 = c.take<uint32_t>((size_t)kMaxQueries * (2 * 32 + 4), 64);   // [256][32] Qh | [256][32] Ql | [256][4]
+            rs->susp2w_cnt = c.take<uint32_t>(kMaxQueries + 2, 4);
+            rs->status = c.take<uint32_t>(kRecallStatusWords + kMaxQueries, 64);  // ONE region, copied out together: the status words, then cnt_seen
+            rs->cnt_seen = rs->status + kRecallStatusWords;
+        }))) return rc;
+    const size_t lists = (size_t)kMaxQueries * cap;
+    if ((rc = scratch_carve(ctx, kSlotRecallCand, [&](Carve& c) {
+            rs->cand[0] = c.take<uint64_t>(lists);
+            rs->cand[1] = c.take<uint64_t>(lists);
+            rs->susp = c.take<uint32_t>(lists);
+            rs->susp2 = c.take<uint32_t>(lists);
+        }))) return rc;
     rs->cap = cap;
     return PG_OK;
 }
@@ -2177,7 +2176,7 @@ int ensure_table_stats(pg_ctx* ctx, const pg_table* tc) {
     bool i8 = t->dim == 128;
     void* p;
     int rc;
-    if ((rc = scratch_reserve(ctx, 4, 4096, &p))) return rc;
+    if ((rc = scratch_reserve(ctx, kSlotStatus, 4096, &p))) return rc;
     float* d_max = (float*)p + 300;                   // [300] max norm^2, [301] non-finite flag, [302] max |x|, [303] max residual^2, [304] sum of norm^2
     uint32_t* d_bad = (uint32_t*)p + 301;
     PG_HIP(hipMemsetAsync(d_max, 0, 20, ctx->stream));
@@ -2543,7 +2542,7 @@ __global__ void compact_map_rows_kernel(uint64_t* __restrict__ rows, uint64_t n,
 }
 
 // Count the rows `f` admits per 1024-row block (one pass over the column) and scan the counts — the scan is also the compaction's
-// map (filter_scatter_kernel); buffers in scratch slot 12.  Synchronises the stream (the count comes back to the host).
+// map (filter_scatter_kernel); buffers in kSlotFilterCount.  Synchronises the stream (the count comes back to the host).
 int filter_count_locked(pg_ctx* ctx, const RowFilter& f, uint64_t rows, uint32_t** d_blk_out, uint32_t** d_grp_out, uint32_t* cblocks_out,
                         uint32_t* admitted_out) {
     const uint32_t cblocks = (uint32_t)((rows + kCompactBlockRows - 1) / kCompactBlockRows);
@@ -2552,11 +2551,11 @@ int filter_count_locked(pg_ctx* ctx, const RowFilter& f, uint64_t rows, uint32_t
         set_error("filtered recall: table of %llu rows too large", (unsigned long long)rows);
         return PG_ERR_UNSUPPORTED;
     }
-    void* cbuf;
-    int rc;
-    if ((rc = scratch_reserve(ctx, 12, ((size_t)cblocks + cgroups + 2) * 4, &cbuf))) return rc;
-    uint32_t* d_blk = (uint32_t*)cbuf;
-    uint32_t* d_grp = d_blk + cblocks;
+    uint32_t *d_blk, *d_grp; int rc;
+    if ((rc = scratch_carve(ctx, kSlotFilterCount, [&](Carve& c) {
+            d_blk = c.take<uint32_t>(cblocks);
+            d_grp = c.take<uint32_t>((size_t)cgroups + 2);      // the groups' scan, the total behind it
+        }))) return rc;
     uint32_t admitted = 0;
     if (cblocks) {
         filter_block_count_kernel<<<cblocks, 256, 0, ctx->stream>>>(f, rows, d_blk);
@@ -2587,7 +2586,7 @@ int ensure_table_nx(pg_ctx* ctx, const pg_table* tc) {
     row_norm2_kernel<<<(uint32_t)((t->rows + 255) / 256), 256, 0, ctx->stream>>>(t->d, t->rows, t->dim, t->d_nx);
     void* p;
     int rc;
-    if ((rc = scratch_reserve(ctx, 4, 4096, &p))) return rc;
+    if ((rc = scratch_reserve(ctx, kSlotStatus, 4096, &p))) return rc;
     double* d_st = reinterpret_cast<double*>((char*)p + 2048);
     PG_HIP(hipMemsetAsync(d_st, 0, 16, ctx->stream));
     block_nxmin_kernel<<<(nblocks + 255) / 256, 256, 0, ctx->stream>>>(t->d_nx, t->rows, t->d_nxmin, nblocks, d_st);
@@ -2625,7 +2624,7 @@ int recall_job_prepare(RecallJob* j) {
         // how many rows the filter admits: the plan check needs it (a filtered list may rightly be shorter than K), and the
         // pilot plan is only worth its launches when the sample holds enough of them
         void* p;
-        if ((rc = scratch_reserve(ctx, 4, 4096, &p))) return rc;
+        if ((rc = scratch_reserve(ctx, kSlotStatus, 4096, &p))) return rc;
         unsigned long long* d_n = reinterpret_cast<unsigned long long*>((char*)p + 3072);
         PG_HIP(hipMemsetAsync(d_n, 0, 8, ctx->stream));
         filter_count_kernel<<<(uint32_t)ctx->num_cus * 8, 256, 0, ctx->stream>>>(j->filter, t->rows, d_n);
@@ -2857,11 +2856,10 @@ struct PlanRun {                     // the launches of one plan (helper of reca
                 if (cap_w < floor_w) cap_w = floor_w;
                 // + a spill pool for tables whose best rows sit together: room for all of 256 x 2 K suspects
                 const uint32_t pool_cap = (uint32_t)(((uint64_t)kMaxQueries * j->k * 2 * rsc + kRecPoolSlice - 1) / kRecPoolSlice * kRecPoolSlice);
-                const size_t head = ((size_t)(rec_waves + 1) * 4 + 255) & ~(size_t)255;
-                void* p;
-                if ((rc2 = scratch_reserve(ctx, 11, head + ((size_t)rec_waves * cap_w + pool_cap) * kRecBytes, &p))) return rc2;
-                sa.rec_cnt = (uint32_t*)p;
-                sa.rec = (char*)p + head;
+                if ((rc2 = scratch_carve(ctx, kSlotHitRecords, [&](Carve& c) {
+                        sa.rec_cnt = c.take<uint32_t>((size_t)rec_waves + 1);
+                        sa.rec = (char*)c.bytes(((size_t)rec_waves * cap_w + pool_cap) * kRecBytes);      // the wave regions, then the spill pool
+                    }))) return rc2;
                 sa.rec_cap = cap_w;
                 sa.rec_pool = sa.rec + (size_t)rec_waves * cap_w * kRecBytes;
                 sa.rec_pool_cap = pool_cap;
@@ -3211,10 +3209,10 @@ int recall_job_check(RecallJob* j, bool* ok_out) {
         uint32_t sc[4] = {0, 0, 0, 0};
         PG_HIP(hipMemcpy(sc, j->rs.susp_cnt, sizeof sc, hipMemcpyDeviceToHost));
         fprintf(stderr, "[pg] plan %d last screened launch: suspects of queries 0-3: %u %u %u %u (K = %u)\n", plan, sc[0], sc[1], sc[2], sc[3], j->k);
-        if (j->t->shadow_is_i8 && j->nq > 128 && ctx->scratch[11].p) {     // hit records: the fullest wave region, the spill pool
+        if (j->t->shadow_is_i8 && j->nq > 128 && scratch_peek(ctx, kSlotHitRecords)) {     // hit records: the fullest wave region, the spill pool
             const uint32_t waves = (uint32_t)ctx->num_cus * 8u;
             std::vector<uint32_t> rc(waves + 1);
-            PG_HIP(hipMemcpy(rc.data(), ctx->scratch[11].p, rc.size() * 4, hipMemcpyDeviceToHost));
+            PG_HIP(hipMemcpy(rc.data(), scratch_peek(ctx, kSlotHitRecords), rc.size() * 4, hipMemcpyDeviceToHost));
             uint32_t mx = 0;
             uint64_t sum = 0;
             for (uint32_t w = 0; w < waves; ++w) { mx = rc[w] > mx ? rc[w] : mx; sum += rc[w]; }
@@ -3426,7 +3424,7 @@ int recall_batches_locked(pg_ctx* ctx, const pg_table* t, const float* d_queries
     return PG_OK;
 }
 
-// pg_recall_topk[_l2][_dev]: host, the queries and outputs are host memory (staged through scratch slot 5)
+// pg_recall_topk[_l2][_dev]: host, the queries and outputs are host memory (staged through kSlotStaging)
 int recall_entry(const char* who, pg_ctx* ctx, const pg_table* t, const float* q, uint32_t nq, uint32_t k, uint64_t* rows, float* sc,
                  uint32_t* out_count, bool l2, bool host) {
     int rc;
@@ -3466,7 +3464,7 @@ int exclude_lists_check(const char* who, const uint32_t* off, uint32_t nq, uint3
     return PG_OK;
 }
 
-// One recall of nq device queries at depth k + nmax through `inner` — the plain call's own search — into scratch slot 18, then
+// One recall of nq device queries at depth k + nmax through `inner` — the plain call's own search — into kSlotRecallExclude, then
 // the compaction into d_rows / d_sc [nq][k].  excl: the lists' ids, host (staged here, off rebased) or device (indexed by off
 // as given); off: host [nq + 1].  nmax = 0: `inner` at k straight into the outputs.  Caller holds ctx->mu and the table's
 // shared lock; ends synchronised (out_count: host [nq] or NULL).
@@ -3482,15 +3480,14 @@ int recall_exclude_locked(pg_ctx* ctx, uint32_t nq, uint32_t k, uint32_t nmax, b
     }
     const uint32_t kx = k + nmax;
     const uint32_t total = excl_on_host ? off[nq] - off[0] : 0;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t ob = al(((size_t)nq + 1) * 4), cb = al((size_t)nq * 4), lb = al((size_t)total * 8), rb = al((size_t)nq * kx * 8);
-    void* buf;
-    if ((rc = scratch_reserve(ctx, 18, ob + cb + lb + rb + (size_t)nq * kx * 4, &buf))) return rc;
-    uint32_t* d_off = (uint32_t*)buf;
-    uint32_t* d_cnt = (uint32_t*)((char*)buf + ob);
-    uint64_t* d_list = (uint64_t*)((char*)buf + ob + cb);
-    uint64_t* d_xrows = (uint64_t*)((char*)buf + ob + cb + lb);
-    float* d_xsc = (float*)((char*)d_xrows + rb);
+    uint32_t *d_off, *d_cnt; uint64_t *d_list, *d_xrows; float* d_xsc;
+    if ((rc = scratch_carve(ctx, kSlotRecallExclude, [&](Carve& c) {
+            d_off = c.take<uint32_t>((size_t)nq + 1);
+            d_cnt = c.take<uint32_t>(nq);
+            d_list = c.take<uint64_t>(total);
+            d_xrows = c.take<uint64_t>((size_t)nq * kx);
+            d_xsc = c.take<float>((size_t)nq * kx);
+        }))) return rc;
     uint32_t h_off[kMaxQueries + 1];
     for (uint32_t q = 0; q <= nq; ++q) h_off[q] = excl_on_host ? off[q] - off[0] : off[q];
     PG_HIP(hipMemcpyAsync(d_off, h_off, ((size_t)nq + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
@@ -3503,6 +3500,15 @@ int recall_exclude_locked(pg_ctx* ctx, uint32_t nq, uint32_t k, uint32_t nmax, b
     PG_HIP(hipMemcpyAsync(ctx->h_status, d_cnt, (size_t)nq * 4, hipMemcpyDeviceToHost, ctx->stream));
     PG_HIP(hipStreamSynchronize(ctx->stream));
     if (out_count) memcpy(out_count, ctx->h_status, (size_t)nq * 4);
+    return PG_OK;
+}
+
+// the queries of an item-to-item recall arrive as rows of the trigger table: the trigger rows are few, one small
+// device-to-device copy each (coalesced 512-B rows)
+int trigger_fill(pg_ctx* ctx, const pg_table* trigger_table, const uint32_t* trigger_rows, uint32_t n, float* d_q) {
+    const size_t dim = trigger_table->dim;
+    for (uint32_t i = 0; i < n; ++i)
+        PG_HIP(hipMemcpyAsync(d_q + i * dim, trigger_table->d + trigger_rows[i] * dim, dim * 4, hipMemcpyDeviceToDevice, ctx->stream));
     return PG_OK;
 }
 
@@ -3669,14 +3675,13 @@ int recall_where_locked(pg_ctx* ctx, const pg_table* t, RowFilter f, int metric,
         // order, into a compact table and run the exact scan over that: its rows are the candidates, its row order the tie
         // order, and the answer's local rows map back through the id list.  (The gather is 1 KB of traffic per admitted row: at
         // 100 M x 128 the copy wins below ~4 M rows for a lone query — in place 2.2 ms at 4 % — and below ~8 M for 16+ queries.)
-        const size_t idb = (((size_t)admitted + 64) * 4 + 255) & ~(size_t)255;
-        const size_t tabb = (((size_t)admitted + 64) * t->dim * 4 + 255) & ~(size_t)255;
-        const size_t nxb = metric == 1 ? (((size_t)admitted + 64) * 4 + 255) & ~(size_t)255 : 0;
-        void* gbuf;
-        if ((rc = scratch_reserve(ctx, 13, idb + tabb + nxb, &gbuf))) return rc;
-        uint32_t* d_ids = (uint32_t*)gbuf;
-        float* d_tab = (float*)((char*)gbuf + idb);
-        float* d_cnx = nxb ? (float*)((char*)gbuf + idb + tabb) : nullptr;
+        uint32_t* d_ids;
+        float *d_tab, *d_cnx = nullptr;
+        if ((rc = scratch_carve(ctx, kSlotFilterGather, [&](Carve& c) {
+                d_ids = c.take<uint32_t>((size_t)admitted + 64);
+                d_tab = c.take<float>(((size_t)admitted + 64) * t->dim);
+                if (metric == 1) d_cnx = c.take<float>((size_t)admitted + 64);
+            }))) return rc;
         filter_scatter_kernel<<<cblocks, 256, 0, ctx->stream>>>(f, t->rows, d_blk, d_grp, d_ids);
         const uint64_t quads = (uint64_t)admitted * (t->dim / 4);
         compact_gather_kernel<<<(uint32_t)((quads + 255) / 256), 256, 0, ctx->stream>>>(t->d, d_ids, admitted, t->dim, d_tab);
@@ -3853,22 +3858,10 @@ int pg_i2i_recall(pg_ctx* ctx, const pg_table* trigger_table, const uint32_t* tr
                    (unsigned long long)trigger_table->rows);
     std::lock_guard<std::mutex> g(ctx->mu);
     pg::TableRead2 tr(t, trigger_table);
-    void* buf;
-    int rc;
-    const size_t qb = (size_t)n * t->dim * 4, rb = (size_t)n * k * 8, sb = (size_t)n * k * 4;
-    if ((rc = pg::scratch_reserve(ctx, 5, qb + rb + sb + 64, &buf))) return rc;
-    float* d_q = (float*)buf;
-    uint64_t* d_rows = (uint64_t*)((char*)buf + ((qb + 15) & ~(size_t)15));
-    float* d_sc = (float*)((char*)d_rows + rb);
-    // the trigger rows are few: one small device-to-device copy each (coalesced 512-B rows)
-    for (uint32_t i = 0; i < n; ++i)
-        PG_HIP(hipMemcpyAsync(d_q + (size_t)i * t->dim, trigger_table->d + (size_t)trigger_rows[i] * t->dim, (size_t)t->dim * 4,
-                              hipMemcpyDeviceToDevice, ctx->stream));
-    if ((rc = pg::recall_dev_locked(ctx, t, d_q, n, k, d_rows, d_sc, out_count, nullptr))) return rc;
-    PG_HIP(hipMemcpyAsync(out_rows, d_rows, rb, hipMemcpyDeviceToHost, ctx->stream));
-    PG_HIP(hipMemcpyAsync(out_scores, d_sc, sb, hipMemcpyDeviceToHost, ctx->stream));
-    PG_HIP(hipStreamSynchronize(ctx->stream));
-    return PG_OK;
+    auto fill = [&](float* d_q) { return pg::trigger_fill(ctx, trigger_table, trigger_rows, n, d_q); };
+    return pg::recall_staged(ctx, t->dim, nullptr, n, k, out_rows, out_scores, [&](const float* d_q, uint64_t* d_rows, float* d_sc) {
+        return pg::recall_dev_locked(ctx, t, d_q, n, k, d_rows, d_sc, out_count, nullptr);
+    }, fill);
 }
 
 int pg_recall_topk_exclude(pg_ctx* ctx, const pg_table* t, const float* queries, uint32_t nq, uint32_t k, const uint64_t* excl_rows,
@@ -3917,21 +3910,11 @@ int pg_i2i_recall_exclude(pg_ctx* ctx, const pg_table* trigger_table, const uint
     }
     std::lock_guard<std::mutex> g(ctx->mu);
     pg::TableRead2 tr(t, trigger_table);
-    void* buf;
-    const size_t qb = (size_t)n * t->dim * 4, rb = (size_t)n * k * 8, sb = (size_t)n * k * 4;
-    if ((rc = pg::scratch_reserve(ctx, 5, qb + rb + sb + 64, &buf))) return rc;
-    float* d_q = (float*)buf;
-    uint64_t* d_rows = (uint64_t*)((char*)buf + ((qb + 15) & ~(size_t)15));
-    float* d_sc = (float*)((char*)d_rows + rb);
-    for (uint32_t i = 0; i < n; ++i)
-        PG_HIP(hipMemcpyAsync(d_q + (size_t)i * t->dim, trigger_table->d + (size_t)trigger_rows[i] * t->dim, (size_t)t->dim * 4,
-                              hipMemcpyDeviceToDevice, ctx->stream));
-    auto inner = [&](uint32_t kk, uint64_t* r, float* s, uint32_t* counts) { return pg::recall_dev_locked(ctx, t, d_q, n, kk, r, s, counts, nullptr); };
-    if ((rc = pg::recall_exclude_locked(ctx, n, k, nmax, false, lists.data(), true, off.data(), d_rows, d_sc, out_count, inner))) return rc;
-    PG_HIP(hipMemcpyAsync(out_rows, d_rows, rb, hipMemcpyDeviceToHost, ctx->stream));
-    PG_HIP(hipMemcpyAsync(out_scores, d_sc, sb, hipMemcpyDeviceToHost, ctx->stream));
-    PG_HIP(hipStreamSynchronize(ctx->stream));
-    return PG_OK;
+    auto fill = [&](float* d_q) { return pg::trigger_fill(ctx, trigger_table, trigger_rows, n, d_q); };
+    return pg::recall_staged(ctx, t->dim, nullptr, n, k, out_rows, out_scores, [&](const float* d_q, uint64_t* d_rows, float* d_sc) {
+        auto inner = [&](uint32_t kk, uint64_t* r, float* s, uint32_t* counts) { return pg::recall_dev_locked(ctx, t, d_q, n, kk, r, s, counts, nullptr); };
+        return pg::recall_exclude_locked(ctx, n, k, nmax, false, lists.data(), true, off.data(), d_rows, d_sc, out_count, inner);
+    }, fill);
 }
 
 // OnlineVectorRecall (service/recall/online_vector_recall.go:73-155): the model server turns the user's features
@@ -3950,15 +3933,16 @@ int pg_online_vector_recall(pg_ctx* ctx, const pg_model* m, const pg_table* item
     }
     std::lock_guard<std::mutex> g(ctx->mu);
     pg::TableRead tr(item_emb->rw);
-    void* buf;
+    float *d_u, *d_q, *d_sc;
+    uint64_t* d_rows;
     int rc;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t ub = al((size_t)n_req * m->d_user * 4), qb = al((size_t)n_req * m->to * 4), rb = (size_t)n_req * k * 8, sb = (size_t)n_req * k * 4;
-    if ((rc = pg::scratch_reserve(ctx, 5, ub + qb + rb + sb + 64, &buf))) return rc;
-    float* d_u = (float*)buf;
-    float* d_q = (float*)((char*)buf + ub);
-    uint64_t* d_rows = (uint64_t*)((char*)buf + ub + qb);
-    float* d_sc = (float*)((char*)d_rows + rb);
+    const size_t rb = (size_t)n_req * k * 8, sb = (size_t)n_req * k * 4;
+    if ((rc = pg::scratch_carve(ctx, pg::kSlotStaging, [&](pg::Carve& c) {
+            d_u = c.take<float>((size_t)n_req * m->d_user);
+            d_q = c.take<float>((size_t)n_req * m->to);
+            d_rows = c.take<uint64_t>((size_t)n_req * k);
+            d_sc = c.take<float>((size_t)n_req * k);
+        }))) return rc;
     PG_HIP(hipMemcpyAsync(d_u, user_vecs, (size_t)n_req * m->d_user * 4, hipMemcpyHostToDevice, ctx->stream));
     if ((rc = pg::fm2t_user_embedding_locked(ctx, m, d_u, n_req, d_q))) return rc;
     if ((rc = pg::recall_dev_locked(ctx, item_emb, d_q, n_req, k, d_rows, d_sc, out_count, nullptr))) return rc;

@@ -285,7 +285,7 @@ int ensure_table_i4(pg_ctx* ctx, const pg_table* tc) {
     if (t->dim != 128 || !t->stats_valid || !t->all_finite) { t->i4_failed = true; return PG_OK; }
     void* p;
     int rc;
-    if ((rc = scratch_reserve(ctx, 4, 4096, &p))) return rc;
+    if ((rc = scratch_reserve(ctx, kSlotStatus, 4096, &p))) return rc;
     float* d_st = (float*)p + 320;
     if (!t->d4) {
         if (hipMalloc((void**)&t->d4, (t->rows + 64) * (size_t)64) != hipSuccess ||

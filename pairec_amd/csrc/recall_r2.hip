@@ -258,7 +258,7 @@ int ensure_table_r2(pg_ctx* ctx, const pg_table* tc) {
     if (t->dim != 128 || !t->stats_valid || !t->all_finite || !t->shadow_is_i8 || !t->d8) { t->r2_failed = true; return PG_OK; }
     void* p;
     int rc;
-    if ((rc = scratch_reserve(ctx, 4, 4096, &p))) return rc;
+    if ((rc = scratch_reserve(ctx, kSlotStatus, 4096, &p))) return rc;
     float* d_st = (float*)p + 340;
     if (!t->d8r) {
         if (hipMalloc((void**)&t->d8r, (t->rows + 64) * (size_t)128) != hipSuccess) {

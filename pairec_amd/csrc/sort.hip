@@ -209,11 +209,11 @@ int sort_dev_locked(pg_ctx* ctx, const double* d_scores, const uint32_t* d_seg, 
     if (max_seg > kSortLdsMax) {
         stride = 2;
         while (stride < max_seg) stride <<= 1;
-        void* p;
         int rc;
-        if ((rc = scratch_reserve(ctx, 7, (size_t)n_seg * stride * 12, &p))) return rc;
-        g_keys = (uint64_t*)p;
-        g_idx = (uint32_t*)(g_keys + (size_t)n_seg * stride);
+        if ((rc = scratch_carve(ctx, kSlotWork, [&](Carve& c) {
+                g_keys = c.take<uint64_t>((size_t)n_seg * stride);
+                g_idx = c.take<uint32_t>((size_t)n_seg * stride);
+            }))) return rc;
     }
     if (rank_sort_applies(ctx, n_seg, max_seg)) {
         const size_t rl = (size_t)((max_seg + 31u) & ~31u) * 8;
@@ -264,14 +264,12 @@ int pg_sort_scores(pg_ctx* ctx, const double* scores, const uint32_t* seg_offset
     if (n == 0) return PG_OK;
     PG_REQUIRE(scores && out_order, "pg_sort_scores: NULL argument");
     std::lock_guard<std::mutex> g(ctx->mu);
-    void* buf;
-    int rc;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    if ((rc = pg::scratch_reserve(ctx, 5, al((size_t)n * 8) + al((size_t)(n_seg + 1) * 4) + al((size_t)n * 4), &buf)))
-        return rc;
-    double* d_s = (double*)buf;
-    uint32_t* d_o = (uint32_t*)((char*)buf + al((size_t)n * 8));
-    uint32_t* d_r = (uint32_t*)((char*)d_o + al((size_t)(n_seg + 1) * 4));
+    double* d_s; uint32_t *d_o, *d_r; int rc;
+    if ((rc = pg::scratch_carve(ctx, pg::kSlotStaging, [&](pg::Carve& c) {
+            d_s = c.take<double>(n);
+            d_o = c.take<uint32_t>((size_t)n_seg + 1);
+            d_r = c.take<uint32_t>(n);
+        }))) return rc;
     PG_HIP(hipMemcpyAsync(d_s, scores, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
     PG_HIP(hipMemcpyAsync(d_o, seg_offsets, (size_t)(n_seg + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
     PG_HIP(hipEventRecord(ctx->ev[4], ctx->stream));

@@ -135,15 +135,15 @@ __global__ __launch_bounds__(256) void split_sort_merge_kernel(Policy pol, const
         if (real[s]) pol.store(seg, rank[s], mine[s], my_ix[s]);
 }
 
-// host side: both launches on the context's stream; the runs live in scratch slot 7 (transient, as the other users of the slot)
+// host side: both launches on the context's stream; the runs live in kSlotWork (transient, as the other users of the slot)
 template <class Policy>
 int split_sort_launch(pg_ctx* ctx, const Policy& pol, uint32_t n_lists, uint32_t max_items) {
     const uint32_t parts = (max_items + kSplitRun - 1) / kSplitRun, stride = parts * kSplitRun;
-    void* p;
-    int rc;
-    if ((rc = scratch_reserve(ctx, 7, (size_t)n_lists * stride * 12, &p))) return rc;
-    uint64_t* const keys = (uint64_t*)p;
-    uint32_t* const idx = (uint32_t*)(keys + (size_t)n_lists * stride);
+    uint64_t* keys; uint32_t* idx; int rc;
+    if ((rc = scratch_carve(ctx, kSlotWork, [&](Carve& c) {
+            keys = c.take<uint64_t>((size_t)n_lists * stride);
+            idx = c.take<uint32_t>((size_t)n_lists * stride);
+        }))) return rc;
     const size_t lds = (size_t)stride * 8;
     if ((rc = ensure_dyn_lds(ctx, (const void*)split_sort_merge_kernel<Policy>, lds))) return rc;
     split_sort_runs_kernel<Policy><<<dim3(parts, n_lists), 64, 0, ctx->stream>>>(pol, keys, idx, stride);

@@ -560,9 +560,6 @@ static int ssd_run_rows_locked(pg_ctx* ctx, const float* d_tab, uint32_t tab_row
     if (window <= 1) window = 5;                          // ssd_sort.go:357-360
     const uint32_t d1 = dim + (ensure_pos_similarity ? 1u : 0u);
     const uint32_t G = (n + 63) / 64;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t bE = al((size_t)n * d1 * 8), bP = al((size_t)window * n * 8), bN = al((size_t)n * 8), bSel = al((size_t)n * 4);
-    const size_t bMail = al(sizeof(SsdMail)), bEbuf = al((size_t)2 * (G + 1) * d1 * 8);
     // Kernel choice: the multi-workgroup kernel (embeddings pinned in registers, device-wide barrier) for the usual
     // widths (dim 64 / 128, with or without the appended 1) and windows <= 16; the one-workgroup kernels otherwise
     // (single requests only).
@@ -575,15 +572,16 @@ static int ssd_run_rows_locked(pg_ctx* ctx, const float* d_tab, uint32_t tab_row
     if (kind == 2) ctx->stats.ssd_grid_calls++;
     else if (kind == 1) ctx->stats.ssd_reg_calls++;
     else ctx->stats.ssd_generic_calls++;
-    void* buf;
     int rc;
     if (kind == 2) {
-        if ((rc = scratch_reserve(ctx, 7, (size_t)R * (bE + bMail + bEbuf), &buf))) return rc;
-        char* p = (char*)buf;
-        double* Et = (double*)p; p += (size_t)R * bE;
+        double *Et, *ebuf;
+        SsdMail* mail;
         // (requests are strided by their exact sizes inside the kernels: n * d1 doubles, one SsdMail, 2 (G + 1) d1 doubles)
-        SsdMail* mail = (SsdMail*)p; p += (size_t)R * bMail;
-        double* ebuf = (double*)p;
+        if ((rc = scratch_carve(ctx, kSlotWork, [&](Carve& c) {
+                Et = c.take<double>((size_t)R * n * d1);
+                mail = c.take<SsdMail>(R);
+                ebuf = c.take<double>((size_t)R * 2 * (G + 1) * d1);
+            }))) return rc;
         ssd_prepare_kernel<<<dim3((n + 63) / 64, R), 64, 0, ctx->stream>>>(d_tab, tab_rows, dim, d_cand, n, normalize_emb,
                                                                            ensure_pos_similarity, Et);
         PG_HIP(hipMemsetAsync(mail, 0, (size_t)R * sizeof(SsdMail), ctx->stream));
@@ -607,14 +605,15 @@ static int ssd_run_rows_locked(pg_ctx* ctx, const float* d_tab, uint32_t tab_row
         PG_HIP(hipGetLastError());
         return PG_OK;
     }
-    if ((rc = scratch_reserve(ctx, 7, bE + bP + 3 * bN + bSel, &buf))) return rc;
-    char* p = (char*)buf;
-    double* Et = (double*)p; p += bE;
-    double* P = (double*)p; p += bP;
-    double* nrm = (double*)p; p += bN;
-    double* ssq = (double*)p; p += bN;
-    double* q = (double*)p; p += bN;
-    uint32_t* d_sel = (uint32_t*)p;
+    double *Et, *P, *nrm, *ssq, *q; uint32_t* d_sel;
+    if ((rc = scratch_carve(ctx, kSlotWork, [&](Carve& c) {
+            Et = c.take<double>((size_t)n * d1);
+            P = c.take<double>((size_t)window * n);
+            nrm = c.take<double>(n);
+            ssq = c.take<double>(n);
+            q = c.take<double>(n);
+            d_sel = c.take<uint32_t>(n);
+        }))) return rc;
     ssd_prepare_kernel<<<dim3((n + 63) / 64, 1), 64, 0, ctx->stream>>>(d_tab, tab_rows, dim, d_cand, n, normalize_emb,
                                                                        ensure_pos_similarity, Et);
     if (kind == 1) {
@@ -656,13 +655,12 @@ static int ssd_one(pg_ctx* ctx, const pg_table* t, const uint32_t* cand_rows, co
     std::lock_guard<std::mutex> g(ctx->mu);
     TableRead tr;
     if (t) tr = TableRead(t->rw);
-    void* io;
-    int rc;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t bIn = t ? al((size_t)n * 4) : al((size_t)n * dim * 4);      // candidate rows, or the embeddings themselves
-    if ((rc = scratch_reserve(ctx, 5, bIn + al((size_t)n * 8) + al((size_t)T * 4), &io))) return rc;
-    double* d_rel = (double*)((char*)io + bIn);
-    uint32_t* d_out = (uint32_t*)((char*)io + bIn + al((size_t)n * 8));
+    void* io; double* d_rel; uint32_t* d_out; int rc;
+    if ((rc = scratch_carve(ctx, kSlotStaging, [&](Carve& c) {
+            io = c.bytes(t ? (size_t)n * 4 : (size_t)n * dim * 4);      // candidate rows, or the embeddings themselves
+            d_rel = c.take<double>(n);
+            d_out = c.take<uint32_t>(T);
+        }))) return rc;
     if (t) PG_HIP(hipMemcpyAsync(io, cand_rows, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
     else PG_HIP(hipMemcpyAsync(io, emb, (size_t)n * dim * 4, hipMemcpyHostToDevice, ctx->stream));
     PG_HIP(hipMemcpyAsync(d_rel, quality.data(), (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));

@@ -350,8 +350,8 @@ int pg_table_gather(pg_ctx* ctx, const pg_table* t, const uint32_t* rows, uint32
     pg::TableRead tr(t->rw);
     void *d_rows, *d_out;
     int rc;
-    if ((rc = pg::scratch_reserve(ctx, 0, (size_t)n * 4, &d_rows))) return rc;
-    if ((rc = pg::scratch_reserve(ctx, 1, (size_t)n * t->dim * 4, &d_out))) return rc;
+    if ((rc = pg::scratch_reserve(ctx, pg::kSlotRows, (size_t)n * 4, &d_rows))) return rc;
+    if ((rc = pg::scratch_reserve(ctx, pg::kSlotHostStage, (size_t)n * t->dim * 4, &d_out))) return rc;
     PG_HIP(hipMemcpyAsync(d_rows, rows, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
     const uint64_t threads = (uint64_t)n * (t->dim / 4);
     pg::table_gather_kernel<<<(uint32_t)((threads + 255) / 256), 256, 0, ctx->stream>>>(

@@ -218,8 +218,6 @@ int trim_check_rules(const pg_trim_rule* rules, uint32_t n_rules, uint32_t cap, 
     return PG_OK;
 }
 
-inline size_t trim_al(size_t x) { return (x + 255) & ~(size_t)255; }
-
 }  // namespace
 
 // caller holds ctx->mu and has checked the arguments (trim_check_rules, the pointers); d_order: each request's positions in score
@@ -235,11 +233,11 @@ int candidates_trim_locked(pg_ctx* ctx, const pg_trim_rule* rules, uint32_t n_ru
         return PG_OK;
     }
     if (!d_order) {
-        const size_t b_off = trim_al((size_t)(nq + 1) * 4);
-        void* buf;
-        if ((rc = scratch_reserve(ctx, 21, b_off + (size_t)nq * cap * 4, &buf))) return rc;
-        uint32_t* d_off = (uint32_t*)buf;
-        uint32_t* d_ord = (uint32_t*)((char*)buf + b_off);
+        uint32_t *d_off, *d_ord;
+        if ((rc = scratch_carve(ctx, kSlotTrim, [&](Carve& c) {
+                d_off = c.take<uint32_t>((size_t)nq + 1);
+                d_ord = c.take<uint32_t>((size_t)nq * cap);
+            }))) return rc;
         if ((rc = uniform_offsets_locked(ctx, nq, cap, d_off))) return rc;
         // (what the sort makes of padding does not matter: the kernel skips padding wherever it lies in the order)
         if ((rc = sort_dev_locked(ctx, d_score, d_off, nq, nq * cap, cap, 1, d_ord))) return rc;

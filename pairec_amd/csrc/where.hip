@@ -495,7 +495,7 @@ int where_build(pg_ctx* ctx, const pg_where* w, const pg_features* fs, uint64_t 
     const size_t words = (size_t)((rows + 31) / 32);
     // program: [16 column pointers][terms][IN constants][ops][count], then the bitmap at a 256-B boundary
     const size_t o_terms = kMaxCols * 8, o_in = o_terms + nt * sizeof(WhereTerm), o_ops = o_in + ni * 8, o_cnt = (o_ops + no * 4 + 7) & ~(size_t)7;
-    const size_t o_bits = (o_cnt + 8 + 255) & ~(size_t)255;
+    const size_t o_bits = align_up(o_cnt + 8);
     const size_t total = o_bits + words * 4 + 256;
     std::vector<unsigned char> h(o_bits, 0);
     uint32_t is64 = 0;
