@@ -34,36 +34,20 @@ constexpr uint32_t kBlendMaxPlanes = 8;
 constexpr uint32_t kBlendMaxCap = 16384;
 static_assert(kBlendMaxSources == PG_BLEND_MAX_SOURCES && kBlendMaxPlanes == PG_BLEND_MAX_PLANES && kBlendMaxCap == PG_BLEND_MAX_CAP,
               "include/pairec_gpu.h repeats these");
-static_assert(kBlendMaxSources == PG_FANIN_MAX_SOURCES && kBlendMaxCap == PG_FANIN_MAX_CAP && kBlendMaxPlanes == PG_TRIM_MAX_PLANES,
-              "the blend takes the fan-in's outputs as they are, in the trim's place");
+static_assert(kBlendMaxSources == kCandMaxSources && kBlendMaxPlanes == kCandMaxPlanes && kBlendMaxCap == kCandMaxCap,
+              "the header names the limits per stage; cand_lists.hpp holds them together");
 constexpr uint32_t kBlendThreads = 1024;         // positions walked at a time
 constexpr uint32_t kBlendWaves = kBlendThreads / kWave;
 constexpr uint32_t kBlendLdsList = 2064;         // entries of every compacted list kept in LDS (uint16 positions): 8 x 2064 x 2 B = 33 KB
 constexpr uint32_t kBlendNone = 0xFFu;           // the source of padding
-constexpr unsigned long long kBlendPad = ~0ull;
-constexpr unsigned long long kBlendNan = 0x7FF8000000000000ull;
-constexpr unsigned long long kBlendNegInf = 0xFFF0000000000000ull;
 static_assert(kBlendMaxCap <= 65536 && kBlendMaxCap % 32 == 0, "positions fit uint16 and the pick records' low half; the bitmap is whole words");
 
 struct BlendArgs {
-    const uint64_t* rows;                        // [nq][cap]
-    const unsigned long long* score;             // fp64 bits
-    const uint8_t* source;                       // NULL: every real entry belongs to one source
-    const uint32_t* count;                       // [nq] or NULL
-    const unsigned long long* planes64;          // [n_f64][nq][cap] fp64 bits or NULL
-    const uint32_t* mask;                        // [nq][cap] or NULL
-    const uint32_t* planes32;                    // [n_f32][nq][cap] fp32 bits or NULL
+    CandIn in;                                   // (source NULL: every real entry belongs to one source)
+    CandOut out;
     const uint32_t* order;                       // FAIR [nq][cap], SNAKE [nq][n_entries][cap]: positions in score order
     uint32_t* lists;                             // SNAKE [nq][n_entries][cap]: every entry's members in order
     uint32_t* picks;                             // SNAKE [nq][out_cap]: position | entry << 16, in pick order
-    uint64_t* out_rows;                          // [nq][out_cap] ...
-    unsigned long long* out_score;
-    uint8_t* out_source;
-    unsigned long long* out_planes64;
-    uint32_t* out_mask;
-    uint32_t* out_planes32;
-    uint32_t* out_count;                         // [nq]
-    uint32_t nq, cap, out_cap, n_f64, n_f32;
     uint32_t skip, retain, n_entries;
     uint32_t e_weight[kBlendMaxSources];
     uint8_t e_source[kBlendMaxSources];
@@ -71,9 +55,9 @@ struct BlendArgs {
 
 // the source of the entry at position p of the request, kBlendNone for padding
 __device__ inline uint32_t blend_source(const BlendArgs& a, size_t in0, uint32_t p, uint32_t n_valid) {
-    if (p >= n_valid || a.rows[in0 + p] == kBlendPad) return kBlendNone;
-    if (!a.source) return a.e_source[0];         // (FAIR: 0)
-    const uint32_t s = a.source[in0 + p];
+    if (p >= n_valid || a.in.rows[in0 + p] == kCandPad) return kBlendNone;
+    if (!a.in.source) return a.e_source[0];      // (FAIR: 0)
+    const uint32_t s = a.in.source[in0 + p];
     return s < kBlendMaxSources ? s : kBlendNone;
 }
 
@@ -82,46 +66,25 @@ __device__ inline uint32_t blend_source(const BlendArgs& a, size_t in0, uint32_t
 __device__ inline bool blend_member(const BlendArgs& a, size_t in0, uint32_t p, uint32_t s, uint32_t si, bool* own) {
     *own = s == si;
     if (s == si) return true;
-    if (!a.mask) return false;
-    const uint32_t m = a.mask[in0 + p];
+    if (!a.in.mask) return false;
+    const uint32_t m = a.in.mask[in0 + p];
     return __popc(m) > 1 && ((m >> si) & 1u);
-}
-
-__device__ inline void blend_pad(const BlendArgs& a, size_t out0, uint32_t total, uint32_t tid) {
-    const size_t out_plane = (size_t)a.nq * a.out_cap;
-    for (uint32_t j = total + tid; j < a.out_cap; j += kBlendThreads) {
-        const size_t o = out0 + j;
-        a.out_rows[o] = kBlendPad;
-        a.out_score[o] = kBlendNegInf;
-        if (a.out_source) a.out_source[o] = 0xFFu;
-        if (a.out_mask) a.out_mask[o] = 0u;
-        for (uint32_t f = 0; f < a.n_f64; ++f) a.out_planes64[f * out_plane + o] = kBlendNan;
-        for (uint32_t f = 0; f < a.n_f32; ++f) a.out_planes32[f * out_plane + o] = 0u;
-    }
-}
-
-// everything of the entry at input position src but its score and source, which the two modes write themselves
-__device__ inline void blend_carry(const BlendArgs& a, size_t src, size_t o) {
-    a.out_rows[o] = a.rows[src];
-    if (a.out_mask) a.out_mask[o] = a.mask[src];
-    const size_t in_plane = (size_t)a.nq * a.cap, out_plane = (size_t)a.nq * a.out_cap;
-    for (uint32_t f = 0; f < a.n_f64; ++f) a.out_planes64[f * out_plane + o] = a.planes64[f * in_plane + src];
-    for (uint32_t f = 0; f < a.n_f32; ++f) a.out_planes32[f * out_plane + o] = a.planes32[f * in_plane + src];
 }
 
 // SNAKE keys: key[q][i][p] = the key of position p in entry i's list, NaN where it is no member (it sorts behind every number; the
 // walk kernel drops it again)
 __global__ __launch_bounds__(256) void blend_keys_kernel(BlendArgs a, unsigned long long* keys) {
     const uint32_t p = blockIdx.x * 256u + threadIdx.x, i = blockIdx.y, q = blockIdx.z;
-    if (p >= a.cap) return;
-    const size_t in0 = (size_t)q * a.cap;
-    const uint32_t n_valid = a.count ? min(a.count[q], a.cap) : a.cap;
+    const uint32_t cap = a.in.cap;
+    if (p >= cap) return;
+    const size_t in0 = (size_t)q * cap;
+    const uint32_t n_valid = cand_n_valid(a.in, q);
     const uint32_t s = blend_source(a, in0, p, n_valid), si = a.e_source[i];
-    unsigned long long k = kBlendNan;
+    unsigned long long k = kCandNan;
     bool own;
     if (s != kBlendNone && blend_member(a, in0, p, s, si, &own))
-        k = own ? a.score[in0 + p] : a.planes64[(size_t)si * a.nq * a.cap + in0 + p];
-    keys[((size_t)q * a.n_entries + i) * a.cap + p] = k;
+        k = own ? a.in.score[in0 + p] : a.in.planes64[(size_t)si * a.in.nq * cap + in0 + p];
+    keys[((size_t)q * a.n_entries + i) * cap + p] = k;
 }
 
 // SNAKE, request q = blockIdx.x.
@@ -132,9 +95,9 @@ __global__ __launch_bounds__(kBlendThreads) void blend_snake_kernel(BlendArgs a)
     __shared__ uint32_t wcnt[2][kBlendWaves];
     __shared__ uint32_t total_s;
     const uint32_t q = blockIdx.x, tid = threadIdx.x, wave = tid / kWave, lane = tid & (kWave - 1);
-    const uint32_t cap = a.cap, out_cap = a.out_cap, n_e = a.n_entries;
+    const uint32_t cap = a.in.cap, out_cap = a.out.out_cap, n_e = a.n_entries;
     const size_t in0 = (size_t)q * cap, out0 = (size_t)q * out_cap;
-    const uint32_t n_valid = a.count ? min(a.count[q], cap) : cap;
+    const uint32_t n_valid = cand_n_valid(a.in, q);
     for (uint32_t w = tid; w < kBlendMaxCap / 32; w += kBlendThreads) taken[w] = 0u;
     if (tid < kBlendMaxSources) {
         llen[tid] = 0;
@@ -179,7 +142,12 @@ __global__ __launch_bounds__(kBlendThreads) void blend_snake_kernel(BlendArgs a)
         }
     }
     __syncthreads();
-    // walk (snake_filter.go:212-231; Next :76-109): one wave, every quantity that steers it is the same in all its lanes
+    // walk (snake_filter.go:212-231; Next :76-109): one wave, every quantity that steers it is the same in all its lanes.
+    // One wave alone waits for its instruction fetches: where the loops below fall in the 64-byte instruction lines moves REFILL
+    // and SKIP by 1 to 1.5 % each (profiles/cand_lists_refactor.json, "placement"), so the walk starts at a fixed place in a line,
+    // the one of three measured at which both run as they did before the lists moved to cand_lists.hpp, whatever the code before
+    // it comes to.
+    asm volatile(".p2align 6\n\ts_nop 0");
     if (wave == 0) {
         const uint32_t retain = a.retain;
         uint32_t size = 0, outp = 0;
@@ -238,13 +206,13 @@ __global__ __launch_bounds__(kBlendThreads) void blend_snake_kernel(BlendArgs a)
         const uint32_t rec = a.picks[out0 + j], pos = rec & 0xFFFFu, i = rec >> 16;
         const uint32_t si = a.e_source[i];
         const size_t src = in0 + pos, o = out0 + j;
-        const bool own = !a.source || a.source[src] == si;
-        blend_carry(a, src, o);
-        a.out_score[o] = own ? a.score[src] : a.planes64[(size_t)si * a.nq * cap + src];
-        if (a.out_source) a.out_source[o] = (uint8_t)si;
+        const bool own = !a.in.source || a.in.source[src] == si;
+        cand_carry(a.in, a.out, src, o, false);
+        a.out.score[o] = own ? a.in.score[src] : a.in.planes64[(size_t)si * a.in.nq * cap + src];
+        if (a.out.source) a.out.source[o] = (uint8_t)si;
     }
-    blend_pad(a, out0, total, tid);
-    if (tid == 0) a.out_count[q] = total;
+    cand_pad(a.in, a.out, q, total + tid, kBlendThreads, kCandNegInf);
+    if (tid == 0) a.out.count[q] = total;
 }
 
 // FAIR, request q = blockIdx.x.
@@ -256,9 +224,9 @@ __global__ __launch_bounds__(kBlendThreads) void blend_fair_kernel(BlendArgs a) 
         ph_g[kBlendMaxSources][kBlendMaxSources], ph_k[kBlendMaxSources];
     __shared__ uint32_t n_ph_s, total_s;
     const uint32_t q = blockIdx.x, tid = threadIdx.x, wave = tid / kWave, lane = tid & (kWave - 1);
-    const uint32_t cap = a.cap, out_cap = a.out_cap;
+    const uint32_t cap = a.in.cap, out_cap = a.out.out_cap;
     const size_t in0 = (size_t)q * cap, out0 = (size_t)q * out_cap;
-    const uint32_t n_valid = a.count ? min(a.count[q], cap) : cap;
+    const uint32_t n_valid = cand_n_valid(a.in, q);
     if (tid < kBlendMaxSources) {
         cnt[tid] = 0;
         run[tid] = 0;
@@ -359,9 +327,9 @@ __global__ __launch_bounds__(kBlendThreads) void blend_fair_kernel(BlendArgs a) 
                 if (rank >= ph_r0[p][s] && rank - ph_r0[p][s] < ph_g[p][s]) dst = ph_first[p][s] + (rank - ph_r0[p][s]) * ph_k[p];
             if (dst < out_cap) {
                 const size_t src = in0 + pos, o = out0 + dst;
-                blend_carry(a, src, o);
-                a.out_score[o] = a.score[src];
-                if (a.out_source) a.out_source[o] = a.source[src];
+                cand_carry(a.in, a.out, src, o, false);
+                a.out.score[o] = a.in.score[src];
+                if (a.out.source) a.out.source[o] = a.in.source[src];
             }
         }
         __syncthreads();
@@ -373,8 +341,8 @@ __global__ __launch_bounds__(kBlendThreads) void blend_fair_kernel(BlendArgs a) 
         }
     }
     const uint32_t total = total_s;
-    blend_pad(a, out0, total, tid);
-    if (tid == 0) a.out_count[q] = total;
+    cand_pad(a.in, a.out, q, total + tid, kBlendThreads, kCandNegInf);
+    if (tid == 0) a.out.count[q] = total;
 }
 
 // the conf as the reference can run it, and the width of what it keeps
@@ -436,10 +404,9 @@ int blend_check_call(const pg_blend_conf* c, uint32_t nq, uint32_t cap, const vo
     PG_REQUIRE(nq >= 1 && nq <= (uint32_t)kMaxQueries, "%s: nq=%u must be in [1,%d]", who, nq, kMaxQueries);
     int rc;
     if ((rc = blend_check_conf(c, cap, out_cap, who))) return rc;
-    PG_REQUIRE(!source == !out_source && !mask == !out_mask, "%s: d_source / d_source_mask and their outputs come in pairs", who);
-    PG_REQUIRE(!planes_f64 == !out_planes_f64 && !planes_f32 == !out_planes_f32, "%s: a carried plane set and its output come in pairs", who);
-    PG_REQUIRE((!planes_f64 || (n_f64 >= 1 && n_f64 <= kBlendMaxPlanes)) && (!planes_f32 || (n_f32 >= 1 && n_f32 <= kBlendMaxPlanes)),
-               "%s: a carried plane set holds 1..%u planes", who, kBlendMaxPlanes);
+    if ((rc = cand_lists_check(who, source, planes_f64, n_f64, mask, planes_f32, n_f32, out_source, out_planes_f64, out_mask, out_planes_f32,
+                               kBlendMaxPlanes)))
+        return rc;
     if (c->mode != PG_BLEND_FAIR) {
         PG_REQUIRE(source || c->n_entries == 1, "%s: a snake that names more than one source needs d_source", who);
         if (mask) {
@@ -539,11 +506,8 @@ void blend_request_host(const pg_blend_conf& c, uint32_t cap, const uint64_t* ro
 
 }  // namespace
 
-int candidates_blend_locked(pg_ctx* ctx, const pg_blend_conf* conf, uint32_t nq, uint32_t cap, uint32_t out_cap, const uint64_t* d_rows,
-                            const double* d_score, const uint8_t* d_source, const uint32_t* d_count, const double* d_planes_f64,
-                            uint32_t n_f64, const uint32_t* d_source_mask, const float* d_planes_f32, uint32_t n_f32, uint64_t* d_out_rows,
-                            double* d_out_score, uint8_t* d_out_source, double* d_out_planes_f64, uint32_t* d_out_source_mask,
-                            float* d_out_planes_f32, uint32_t* d_out_count) {
+int candidates_blend_locked(pg_ctx* ctx, const pg_blend_conf* conf, const CandIn& in, const CandOut& out) {
+    const uint32_t nq = in.nq, cap = in.cap;
     int rc;
     const bool fair = conf->mode == PG_BLEND_FAIR;
     const uint32_t n_e = fair ? 1u : conf->n_entries, n_seg = nq * n_e;
@@ -554,31 +518,14 @@ int candidates_blend_locked(pg_ctx* ctx, const pg_blend_conf* conf, uint32_t nq,
             d_ord = c.take<uint32_t>((size_t)n_seg * cap);
             d_keys = c.take<unsigned long long>(fair ? 0 : (size_t)n_seg * cap);
             d_lists = c.take<uint32_t>(fair ? 0 : (size_t)n_seg * cap);
-            d_picks = c.take<uint32_t>(fair ? 0 : (size_t)nq * out_cap);
+            d_picks = c.take<uint32_t>(fair ? 0 : (size_t)nq * out.out_cap);
         }))) return rc;
     BlendArgs a{};
-    a.rows = d_rows;
-    a.score = reinterpret_cast<const unsigned long long*>(d_score);
-    a.source = d_source;
-    a.count = d_count;
-    a.planes64 = reinterpret_cast<const unsigned long long*>(d_planes_f64);
-    a.mask = d_source_mask;
-    a.planes32 = reinterpret_cast<const uint32_t*>(d_planes_f32);
+    a.in = in;
+    a.out = out;
     a.order = d_ord;
     a.lists = fair ? nullptr : d_lists;
     a.picks = fair ? nullptr : d_picks;
-    a.out_rows = d_out_rows;
-    a.out_score = reinterpret_cast<unsigned long long*>(d_out_score);
-    a.out_source = d_source ? d_out_source : nullptr;
-    a.out_planes64 = reinterpret_cast<unsigned long long*>(d_out_planes_f64);
-    a.out_mask = d_source_mask ? d_out_source_mask : nullptr;
-    a.out_planes32 = reinterpret_cast<uint32_t*>(d_out_planes_f32);
-    a.out_count = d_out_count;
-    a.nq = nq;
-    a.cap = cap;
-    a.out_cap = out_cap;
-    a.n_f64 = d_planes_f64 ? n_f64 : 0;
-    a.n_f32 = d_planes_f32 ? n_f32 : 0;
     a.skip = conf->mode == PG_BLEND_SNAKE_SKIP ? 1u : 0u;
     a.retain = conf->retain_num;
     a.n_entries = n_e;
@@ -589,7 +536,7 @@ int candidates_blend_locked(pg_ctx* ctx, const pg_blend_conf* conf, uint32_t nq,
     if ((rc = uniform_offsets_locked(ctx, n_seg, cap, d_off))) return rc;
     // (what the sorts make of padding and of non-members does not matter: the kernels skip them wherever they lie in the order)
     if (fair) {
-        if ((rc = sort_dev_locked(ctx, d_score, d_off, n_seg, n_seg * cap, cap, 1, d_ord))) return rc;
+        if ((rc = sort_dev_locked(ctx, reinterpret_cast<const double*>(in.score), d_off, n_seg, n_seg * cap, cap, 1, d_ord))) return rc;
         blend_fair_kernel<<<nq, kBlendThreads, 0, ctx->stream>>>(a);
     } else {
         blend_keys_kernel<<<dim3((cap + 255) / 256, n_e, nq), 256, 0, ctx->stream>>>(a, d_keys);
@@ -622,11 +569,13 @@ int pg_candidates_blend_dev(pg_ctx* ctx, const pg_blend_conf* conf, uint32_t nq,
                                    d_out_rows, d_out_score, d_out_source, d_out_planes_f64, d_out_source_mask, d_out_planes_f32,
                                    d_out_count, &out_cap, "pg_candidates_blend_dev")))
         return rc;
+    pg::CandIn in;
+    pg::CandOut out;
+    pg::cand_lists_bind(nq, cap, out_cap, d_rows, d_score, d_source, d_count, d_planes_f64, n_f64, d_source_mask, d_planes_f32, n_f32,
+                        d_out_rows, d_out_score, d_out_source, d_out_planes_f64, d_out_source_mask, d_out_planes_f32, d_out_count, &in, &out);
     std::lock_guard<std::mutex> g(ctx->mu);
     PG_HIP(hipSetDevice(ctx->device));
-    return pg::candidates_blend_locked(ctx, conf, nq, cap, out_cap, d_rows, d_score, d_source, d_count, d_planes_f64, n_f64, d_source_mask,
-                                       d_planes_f32, n_f32, d_out_rows, d_out_score, d_out_source, d_out_planes_f64, d_out_source_mask,
-                                       d_out_planes_f32, d_out_count);
+    return pg::candidates_blend_locked(ctx, conf, in, out);
 }
 
 int pg_candidates_blend_host(const pg_blend_conf* conf, uint32_t nq, uint32_t cap, const uint64_t* rows, const double* score,
@@ -640,48 +589,27 @@ int pg_candidates_blend_host(const pg_blend_conf* conf, uint32_t nq, uint32_t ca
                                    out_score, out_source, out_planes_f64, out_source_mask, out_planes_f32, out_count, &out_cap,
                                    "pg_candidates_blend_host")))
         return rc;
-    if (!planes_f64) n_f64 = 0;
-    if (!planes_f32) n_f32 = 0;
-    const unsigned long long* sbits = reinterpret_cast<const unsigned long long*>(score);
-    const unsigned long long* p64 = reinterpret_cast<const unsigned long long*>(planes_f64);
-    const uint32_t* p32 = reinterpret_cast<const uint32_t*>(planes_f32);
-    unsigned long long* o_sbits = reinterpret_cast<unsigned long long*>(out_score);
-    unsigned long long* o_p64 = reinterpret_cast<unsigned long long*>(out_planes_f64);
-    uint32_t* o_p32 = reinterpret_cast<uint32_t*>(out_planes_f32);
-    const size_t in_plane = (size_t)nq * cap, out_plane = (size_t)nq * out_cap;
+    pg::CandIn in;
+    pg::CandOut out;
+    pg::cand_lists_bind(nq, cap, out_cap, rows, score, source, count, planes_f64, n_f64, source_mask, planes_f32, n_f32, out_rows, out_score,
+                        out_source, out_planes_f64, out_source_mask, out_planes_f32, out_count, &in, &out);
     std::vector<pg::BlendPick> picks;
     for (uint32_t q = 0; q < nq; ++q) {
         const size_t in0 = (size_t)q * cap, out0 = (size_t)q * out_cap;
-        const uint32_t n_valid = count ? std::min(count[q], cap) : cap;
-        pg::blend_request_host(*conf, cap, rows + in0, score + in0, source ? source + in0 : nullptr, n_valid,
-                               planes_f64 ? planes_f64 + in0 : nullptr, in_plane, source_mask ? source_mask + in0 : nullptr, &picks);
+        pg::blend_request_host(*conf, cap, rows + in0, score + in0, source ? source + in0 : nullptr, pg::cand_n_valid(in, q),
+                               planes_f64 ? planes_f64 + in0 : nullptr, (size_t)nq * cap, source_mask ? source_mask + in0 : nullptr, &picks);
         const uint32_t n = (uint32_t)std::min<size_t>(picks.size(), out_cap);
-        for (uint32_t j = 0; j < out_cap; ++j) {
-            const size_t o = out0 + j;
-            if (j < n) {
-                const size_t src = in0 + picks[j].pos;
-                out_rows[o] = rows[src];
-                if (conf->mode == PG_BLEND_FAIR) {
-                    o_sbits[o] = sbits[src];
-                    if (out_source) out_source[o] = source[src];
-                } else {
-                    const uint32_t si = conf->source[picks[j].entry];
-                    const bool own = !source || source[src] == si;
-                    o_sbits[o] = own ? sbits[src] : p64[si * in_plane + src];
-                    if (out_source) out_source[o] = (uint8_t)si;
-                }
-                if (out_source_mask) out_source_mask[o] = source_mask[src];
-                for (uint32_t f = 0; f < n_f64; ++f) o_p64[f * out_plane + o] = p64[f * in_plane + src];
-                for (uint32_t f = 0; f < n_f32; ++f) o_p32[f * out_plane + o] = p32[f * in_plane + src];
-            } else {
-                out_rows[o] = ~0ull;
-                o_sbits[o] = pg::kBlendNegInf;
-                if (out_source) out_source[o] = 0xFFu;
-                if (out_source_mask) out_source_mask[o] = 0u;
-                for (uint32_t f = 0; f < n_f64; ++f) o_p64[f * out_plane + o] = pg::kBlendNan;
-                for (uint32_t f = 0; f < n_f32; ++f) o_p32[f * out_plane + o] = 0u;
+        for (uint32_t j = 0; j < n; ++j) {
+            const size_t src = in0 + picks[j].pos, o = out0 + j;
+            pg::cand_carry(in, out, src, o, conf->mode == PG_BLEND_FAIR);
+            if (conf->mode != PG_BLEND_FAIR) {
+                const uint32_t si = conf->source[picks[j].entry];
+                const bool own = !source || source[src] == si;
+                out.score[o] = own ? in.score[src] : in.planes64[si * ((size_t)nq * cap) + src];
+                if (out.source) out.source[o] = (uint8_t)si;
             }
         }
+        pg::cand_pad(in, out, q, n, 1, pg::kCandNegInf);
         out_count[q] = n;
     }
     return PG_OK;

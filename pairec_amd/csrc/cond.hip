@@ -47,15 +47,11 @@ namespace {
 
 constexpr uint32_t kCondMaxRules = 8, kCondMaxTerms = 8, kCondMaxCols = 16, kCondMaxSlots = 8, kCondMaxList = 64;
 constexpr uint32_t kCondMaxExprOps = 64, kCondMaxExprDepth = 8;
-constexpr uint32_t kCondMaxPlanes = 8, kCondMaxCap = 16384, kCondChunk = 1024, kCondWaves = kCondChunk / kWave;
+constexpr uint32_t kCondChunk = 1024, kCondWaves = kCondChunk / kWave;
 static_assert(kCondMaxRules == PG_COND_MAX_RULES && kCondMaxTerms == PG_COND_MAX_TERMS && kCondMaxCols == PG_COND_MAX_COLS &&
                   kCondMaxSlots == PG_COND_MAX_SLOTS && kCondMaxList == PG_COND_MAX_LIST && kCondMaxExprOps == PG_COND_MAX_EXPR_OPS &&
                   kCondMaxExprDepth == PG_COND_MAX_EXPR_DEPTH,
               "include/pairec_gpu.h repeats these");
-static_assert(kCondMaxPlanes == PG_TRIM_MAX_PLANES && kCondMaxCap == PG_TRIM_MAX_CAP && kCondMaxCap == PG_FANIN_MAX_CAP,
-              "the filter takes the fan-in's outputs and feeds the trim");
-constexpr unsigned long long kCondPad = ~0ull;
-constexpr unsigned long long kCondNan = 0x7FF8000000000000ull;
 constexpr uint32_t kVarScore = 0xFFFFu;           // Instr.arg of the variable `score`
 
 struct CondTerm {                                 // 24 bytes
@@ -263,32 +259,18 @@ __device__ __forceinline__ void cond_load(const CondProgram& p, unsigned long lo
 }
 
 struct FilterArgs {
-    const uint64_t* rows;                        // [nq][cap]
-    const unsigned long long* score;             // fp64 bits
-    const uint8_t* source;                       // [nq][cap] or NULL
-    const uint32_t* count;                       // [nq] or NULL
-    const unsigned long long* planes64;          // [n_f64][nq][cap] or NULL
-    const uint32_t* mask;                        // [nq][cap] or NULL
-    const uint32_t* planes32;                    // [n_f32][nq][cap] or NULL
+    CandIn in;
+    CandOut out;                                 // (out_cap = cap: the kept entries move to the front of their own list)
     const unsigned long long* user_vals;         // [nq][kCondMaxSlots] or NULL
     const uint32_t* user_present;                // [nq] or NULL
-    uint64_t* out_rows;
-    unsigned long long* out_score;
-    uint8_t* out_source;
-    unsigned long long* out_planes64;
-    uint32_t* out_mask;
-    uint32_t* out_planes32;
-    uint32_t* out_count;
-    uint32_t nq, cap, n_f64, n_f32;
 };
 
 // Request q = blockIdx.x.
 __global__ __launch_bounds__(kCondChunk) void item_state_filter_kernel(CondProgram p, FilterArgs a) {
     __shared__ uint32_t wcnt[2][kCondWaves];
     const uint32_t q = blockIdx.x, tid = threadIdx.x, wave = tid / kWave, lane = tid & (kWave - 1);
-    const uint32_t cap = a.cap;
-    const size_t q0 = (size_t)q * cap, plane = (size_t)a.nq * cap;
-    const uint32_t n_valid = a.count ? min(a.count[q], cap) : cap;
+    const size_t q0 = (size_t)q * a.in.cap;
+    const uint32_t n_valid = cand_n_valid(a.in, q);
     CondUser u;
     u.vals = a.user_vals ? a.user_vals + (size_t)q * kCondMaxSlots : nullptr;
     u.present = a.user_present ? a.user_present[q] : 0u;
@@ -297,8 +279,8 @@ __global__ __launch_bounds__(kCondChunk) void item_state_filter_kernel(CondProgr
         const uint32_t pos = c0 + tid;
         bool keep = false;
         if (pos < n_valid) {
-            const unsigned long long row = a.rows[q0 + pos];
-            if (row != kCondPad) {
+            const unsigned long long row = a.in.rows[q0 + pos];
+            if (row != kCandPad) {
                 CondItem item;
                 cond_load(p, row, &item);
                 keep = cond_rule(p, 0, item, u);
@@ -316,27 +298,11 @@ __global__ __launch_bounds__(kCondChunk) void item_state_filter_kernel(CondProgr
             below += w < wave ? c : 0u;
             total += c;
         }
-        if (keep) {
-            const size_t src = q0 + pos, o = q0 + run + below + before;      // (run + below + before <= pos < cap)
-            a.out_rows[o] = a.rows[src];
-            a.out_score[o] = a.score[src];
-            if (a.out_source) a.out_source[o] = a.source[src];
-            if (a.out_mask) a.out_mask[o] = a.mask[src];
-            for (uint32_t f = 0; f < a.n_f64; ++f) a.out_planes64[f * plane + o] = a.planes64[f * plane + src];
-            for (uint32_t f = 0; f < a.n_f32; ++f) a.out_planes32[f * plane + o] = a.planes32[f * plane + src];
-        }
+        if (keep) cand_carry(a.in, a.out, q0 + pos, q0 + run + below + before, true);      // (run + below + before <= pos < cap)
         run += total;
     }
-    for (uint32_t j = run + tid; j < cap; j += kCondChunk) {              // padding behind the count
-        const size_t o = q0 + j;
-        a.out_rows[o] = kCondPad;
-        a.out_score[o] = kCondNan;
-        if (a.out_source) a.out_source[o] = 0xFFu;
-        if (a.out_mask) a.out_mask[o] = 0u;
-        for (uint32_t f = 0; f < a.n_f64; ++f) a.out_planes64[f * plane + o] = kCondNan;
-        for (uint32_t f = 0; f < a.n_f32; ++f) a.out_planes32[f * plane + o] = 0u;
-    }
-    if (tid == 0) a.out_count[q] = run;
+    cand_pad(a.in, a.out, q, run + tid, kCondChunk, kCandNan);          // padding behind the count
+    if (tid == 0) a.out.count[q] = run;
 }
 
 constexpr uint32_t kBoostThreads = 256;
@@ -349,11 +315,11 @@ __global__ __launch_bounds__(kBoostThreads) void boost_scores_kernel(CondProgram
     const uint32_t q = blockIdx.y, pos = blockIdx.x * kBoostThreads + threadIdx.x;
     if (pos >= cap) return;
     const size_t i = (size_t)q * cap + pos;
-    const uint32_t n_valid = count ? min(count[q], cap) : cap;
+    const uint32_t n_valid = count ? min(count[q], cap) : cap;      // (a score rewrite in place: no lists move, no CandIn)
     unsigned long long bits = score[i];
     uint32_t last = 0xFFu;
     const unsigned long long row = rows[i];
-    if (pos < n_valid && row != kCondPad) {
+    if (pos < n_valid && row != kCandPad) {
         CondUser u;
         u.vals = user_vals ? user_vals + (size_t)q * kCondMaxSlots : nullptr;
         u.present = user_present ? user_present[q] : 0u;
@@ -682,8 +648,8 @@ int cond_bind_locked(pg_ctx* ctx, pg_cond* c, const pg_features* fs, const char*
 
 int cond_check_shape(uint32_t nq, uint32_t cap, const char* who) {
     PG_REQUIRE(nq >= 1 && nq <= (uint32_t)kMaxQueries, "%s: nq=%u must be in [1,%d]", who, nq, kMaxQueries);
-    if (cap < 1 || cap > kCondMaxCap) {
-        set_error("%s: cap=%u unsupported (1..%u)", who, cap, kCondMaxCap);
+    if (cap < 1 || cap > kCandMaxCap) {
+        set_error("%s: cap=%u unsupported (1..%u)", who, cap, kCandMaxCap);
         return PG_ERR_UNSUPPORTED;
     }
     return PG_OK;
@@ -696,36 +662,17 @@ inline bool cond_overlap(const void* a, size_t an, const void* b, size_t bn) {
     return x < y + bn && y < x + an;
 }
 
-int item_state_filter_locked(pg_ctx* ctx, pg_cond* c, const pg_features* fs, uint32_t nq, uint32_t cap, const uint64_t* d_rows, const double* d_score,
-                             const uint8_t* d_source, const uint32_t* d_count, const double* d_planes_f64, uint32_t n_f64,
-                             const uint32_t* d_source_mask, const float* d_planes_f32, uint32_t n_f32, const uint64_t* d_user_vals,
-                             const uint32_t* d_user_present, uint64_t* d_out_rows, double* d_out_score, uint8_t* d_out_source,
-                             double* d_out_planes_f64, uint32_t* d_out_source_mask, float* d_out_planes_f32, uint32_t* d_out_count) {
+int item_state_filter_locked(pg_ctx* ctx, pg_cond* c, const pg_features* fs, const CandIn& in, const CandOut& out, const uint64_t* d_user_vals,
+                             const uint32_t* d_user_present) {
     CondProgram p;
     int rc;
     if ((rc = cond_bind_locked(ctx, c, fs, "pg_item_state_filter_dev", &p))) return rc;
     FilterArgs a{};
-    a.rows = d_rows;
-    a.score = reinterpret_cast<const unsigned long long*>(d_score);
-    a.source = d_source;
-    a.count = d_count;
-    a.planes64 = reinterpret_cast<const unsigned long long*>(d_planes_f64);
-    a.mask = d_source_mask;
-    a.planes32 = reinterpret_cast<const uint32_t*>(d_planes_f32);
+    a.in = in;
+    a.out = out;
     a.user_vals = reinterpret_cast<const unsigned long long*>(d_user_vals);
     a.user_present = d_user_present;
-    a.out_rows = d_out_rows;
-    a.out_score = reinterpret_cast<unsigned long long*>(d_out_score);
-    a.out_source = d_source ? d_out_source : nullptr;
-    a.out_planes64 = reinterpret_cast<unsigned long long*>(d_out_planes_f64);
-    a.out_mask = d_source_mask ? d_out_source_mask : nullptr;
-    a.out_planes32 = reinterpret_cast<uint32_t*>(d_out_planes_f32);
-    a.out_count = d_out_count;
-    a.nq = nq;
-    a.cap = cap;
-    a.n_f64 = d_planes_f64 ? n_f64 : 0;
-    a.n_f32 = d_planes_f32 ? n_f32 : 0;
-    item_state_filter_kernel<<<nq, kCondChunk, 0, ctx->stream>>>(p, a);
+    item_state_filter_kernel<<<in.nq, kCondChunk, 0, ctx->stream>>>(p, a);
     PG_HIP(hipGetLastError());
     return PG_OK;
 }
@@ -830,23 +777,22 @@ int pg_item_state_filter_dev(pg_ctx* ctx, pg_cond* c, const pg_features* fs, uin
     int rc;
     if ((rc = pg::cond_check_shape(nq, cap, "pg_item_state_filter_dev"))) return rc;
     PG_REQUIRE(c->slot_names.empty() || (d_user_vals && d_user_present), "pg_item_state_filter_dev: the set reads user properties: d_user_vals and d_user_present are needed");
-    PG_REQUIRE(!d_source == !d_out_source && !d_source_mask == !d_out_source_mask,
-               "pg_item_state_filter_dev: d_source / d_source_mask and their outputs come in pairs");
-    PG_REQUIRE(!d_planes_f64 == !d_out_planes_f64 && !d_planes_f32 == !d_out_planes_f32,
-               "pg_item_state_filter_dev: a carried plane set and its output come in pairs");
-    PG_REQUIRE((!d_planes_f64 || (n_f64 >= 1 && n_f64 <= pg::kCondMaxPlanes)) && (!d_planes_f32 || (n_f32 >= 1 && n_f32 <= pg::kCondMaxPlanes)),
-               "pg_item_state_filter_dev: a carried plane set holds 1..%u planes", pg::kCondMaxPlanes);
+    if ((rc = pg::cand_lists_check("pg_item_state_filter_dev", d_source, d_planes_f64, n_f64, d_source_mask, d_planes_f32, n_f32, d_out_source,
+                                   d_out_planes_f64, d_out_source_mask, d_out_planes_f32, pg::kCandMaxPlanes)))
+        return rc;
     const size_t e = (size_t)nq * cap;
     PG_REQUIRE(!pg::cond_overlap(d_rows, e * 8, d_out_rows, e * 8) && !pg::cond_overlap(d_score, e * 8, d_out_score, e * 8) &&
                    !pg::cond_overlap(d_source, e, d_out_source, e) && !pg::cond_overlap(d_source_mask, e * 4, d_out_source_mask, e * 4) &&
                    !pg::cond_overlap(d_planes_f64, e * 8 * n_f64, d_out_planes_f64, e * 8 * n_f64) &&
                    !pg::cond_overlap(d_planes_f32, e * 4 * n_f32, d_out_planes_f32, e * 4 * n_f32),
                "pg_item_state_filter_dev: an output overlaps its input");
+    pg::CandIn in;
+    pg::CandOut out;
+    pg::cand_lists_bind(nq, cap, cap, d_rows, d_score, d_source, d_count, d_planes_f64, n_f64, d_source_mask, d_planes_f32, n_f32, d_out_rows,
+                        d_out_score, d_out_source, d_out_planes_f64, d_out_source_mask, d_out_planes_f32, d_out_count, &in, &out);
     std::lock_guard<std::mutex> g(ctx->mu);
     PG_HIP(hipSetDevice(ctx->device));
-    return pg::item_state_filter_locked(ctx, c, fs, nq, cap, d_rows, d_score, d_source, d_count, d_planes_f64, n_f64, d_source_mask, d_planes_f32,
-                                        n_f32, d_user_vals, d_user_present, d_out_rows, d_out_score, d_out_source, d_out_planes_f64,
-                                        d_out_source_mask, d_out_planes_f32, d_out_count);
+    return pg::item_state_filter_locked(ctx, c, fs, in, out, d_user_vals, d_user_present);
 }
 
 int pg_boost_scores_dev(pg_ctx* ctx, pg_cond* c, const pg_features* fs, uint32_t filter_all, uint32_t nq, uint32_t cap, const uint64_t* d_rows,
@@ -898,9 +844,19 @@ int pg_item_state_filter(pg_ctx* ctx, pg_cond* c, const pg_features* fs, uint32_
     PG_HIP(hipMemcpyAsync(d_uv, uv, sizeof uv, hipMemcpyHostToDevice, ctx->stream));
     PG_HIP(hipMemcpyAsync(d_up, &user_present, 4, hipMemcpyHostToDevice, ctx->stream));
     PG_HIP(hipStreamSynchronize(ctx->stream));       // (uv and user_present are this frame's)
-    if ((rc = pg::item_state_filter_locked(ctx, c, fs, 1, n, d_rows, d_score, source ? d_src : nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, d_uv,
-                                           d_up, d_orows, d_oscore, source ? d_osrc : nullptr, nullptr, nullptr, nullptr, d_cnt)))
-        return rc;
+    pg::CandIn in{};
+    in.rows = d_rows;
+    in.score = reinterpret_cast<const unsigned long long*>(d_score);
+    in.source = source ? d_src : nullptr;
+    in.nq = 1;
+    in.cap = n;
+    pg::CandOut out{};
+    out.rows = d_orows;
+    out.score = reinterpret_cast<unsigned long long*>(d_oscore);
+    out.source = source ? d_osrc : nullptr;
+    out.count = d_cnt;
+    out.out_cap = n;
+    if ((rc = pg::item_state_filter_locked(ctx, c, fs, in, out, d_uv, d_up))) return rc;
     PG_HIP(hipMemcpyAsync(out_rows, d_orows, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
     PG_HIP(hipMemcpyAsync(out_score, d_oscore, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
     if (source) PG_HIP(hipMemcpyAsync(out_source, d_osrc, n, hipMemcpyDeviceToHost, ctx->stream));

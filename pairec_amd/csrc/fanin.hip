@@ -19,7 +19,7 @@
 // Two tiers, chosen per request by the kernel itself: cap <= kFaninLdsMaxCap and ids that span less than 2^32 - 1 keep the
 // table in LDS, keyed on the 32-bit distance to the request's smallest id (8 B per slot: 16384 slots = 128 KiB); everything
 // else uses the request's slice of context scratch with full 64-bit keys.  Either way two ids that differ anywhere are two ids.
-#include "common.hpp"
+#include "cand_lists.hpp"
 
 #include <type_traits>
 
@@ -41,9 +41,6 @@ constexpr uint32_t kFaninLdsSlots = 2 * kFaninLdsMaxCap;
 constexpr size_t kFaninLdsTable = (size_t)kFaninLdsSlots * 8 + kFaninLdsMaxCap;
 constexpr size_t kFaninLds = kFaninLdsTable + 2 * kFaninWaves * 4 + 16;
 static_assert(kFaninLds + 256 <= 160 * 1024, "one workgroup's LDS (the source descriptors are static LDS beside it)");
-constexpr unsigned long long kFaninPad = ~0ull;
-constexpr unsigned long long kFaninNan = 0x7FF8000000000000ull;
-constexpr unsigned long long kFaninNegInf = 0xFFF0000000000000ull;
 // a slot's value: the smallest position (< 2^14) until the walk, then kFaninSlotFlag | output slot, then
 // (source + 1) << 28 | index in the source << 14 | output slot
 constexpr uint32_t kFaninSlotFlag = 1u << 14, kFaninSlotMask = kFaninSlotFlag - 1;
@@ -153,7 +150,7 @@ __device__ void fanin_run(const FaninArgs& a, const FaninDesc& d, uint32_t q, ty
     for (uint32_t p = tid; p < cap; p += kFaninThreads) {
         const uint32_t s = fanin_source_of(d, n_src, p);
         const unsigned long long id = d.rows[s][(size_t)q * d.k[s] + (p - d.base[s])];
-        if (id == kFaninPad) continue;
+        if (id == kCandPad) continue;
         const Key key = (Key)(id - id0);
         uint32_t h = fanin_slot((unsigned long long)key, bits);
         for (;; h = (h + 1) & smask) {
@@ -172,14 +169,14 @@ __device__ void fanin_run(const FaninArgs& a, const FaninDesc& d, uint32_t q, ty
     uint32_t base = 0;
     for (uint32_t c0 = 0, it = 0; c0 < cap; c0 += kFaninChunk, ++it) {
         const uint32_t p = c0 + tid;
-        unsigned long long id = kFaninPad;
+        unsigned long long id = kCandPad;
         uint32_t s = 0, j = 0, h = 0;
         bool first = false;
         if (p < cap) {
             s = fanin_source_of(d, n_src, p);
             j = p - d.base[s];
             id = d.rows[s][(size_t)q * d.k[s] + j];
-            if (id != kFaninPad) {
+            if (id != kCandPad) {
                 h = fanin_find<kLds, Key>(keys, (Key)(id - id0), bits);
                 first = tab_load<kLds>(&val[h]) == p;
             }
@@ -216,7 +213,7 @@ __device__ void fanin_run(const FaninArgs& a, const FaninDesc& d, uint32_t q, ty
             const uint64_t* rows = d.rows[s] + (size_t)q * ks;
             for (uint32_t j = tid; j < ks; j += kFaninThreads) {
                 const unsigned long long id = rows[j];
-                if (id == kFaninPad) continue;
+                if (id == kCandPad) continue;
                 const uint32_t h = fanin_find<kLds, Key>(keys, (Key)(id - id0), bits);
                 // (the value's low bits are the output slot whoever wrote it last)
                 const uint32_t slot = tab_load<kLds>(&val[h]) & kFaninSlotMask;
@@ -225,7 +222,7 @@ __device__ void fanin_run(const FaninArgs& a, const FaninDesc& d, uint32_t q, ty
             __syncthreads();
             for (uint32_t j = tid; j < ks; j += kFaninThreads) {
                 const unsigned long long id = rows[j];
-                if (id == kFaninPad) continue;
+                if (id == kCandPad) continue;
                 const uint32_t h = fanin_find<kLds, Key>(keys, (Key)(id - id0), bits);
                 const uint32_t v = tab_load<kLds>(&val[h]);
                 if ((v >> 14) != (((s + 1u) << 14) | j)) continue;
@@ -246,8 +243,8 @@ __device__ void fanin_run(const FaninArgs& a, const FaninDesc& d, uint32_t q, ty
     // padding behind the distinct ids, the mask, and NaN wherever a source does not hold the slot's item
     for (uint32_t jj = tid; jj < cap; jj += kFaninThreads) {
         if (jj >= count) {
-            out_rows[jj] = kFaninPad;
-            out_score[jj] = kFaninNegInf;
+            out_rows[jj] = kCandPad;
+            out_score[jj] = kCandNegInf;
             out_source[jj] = 0xFFu;
         }
         if (!want_planes) continue;
@@ -259,7 +256,7 @@ __device__ void fanin_run(const FaninArgs& a, const FaninDesc& d, uint32_t q, ty
         if (a.out_mask) a.out_mask[(size_t)q * cap + jj] = mk;
         if (a.out_planes)
             for (uint32_t s = 0; s < n_src; ++s)
-                if (!((mk >> s) & 1u)) a.out_planes[((size_t)s * a.nq + q) * cap + jj] = kFaninNan;
+                if (!((mk >> s) & 1u)) a.out_planes[((size_t)s * a.nq + q) * cap + jj] = kCandNan;
     }
     if (tid == 0) a.out_count[q] = count;
 }
@@ -290,7 +287,7 @@ __global__ __launch_bounds__(kFaninThreads) void fanin_merge_kernel(FaninArgs a)
         for (uint32_t p = tid; p < a.cap; p += kFaninThreads) {
             const uint32_t s = fanin_source_of(d, a.n_src, p);
             const unsigned long long id = d.rows[s][(size_t)q * d.k[s] + (p - d.base[s])];
-            if (id == kFaninPad) continue;
+            if (id == kCandPad) continue;
             lo = id < lo ? id : lo;
             hi = id > hi ? id : hi;
         }

@@ -554,10 +554,24 @@ int pg_recommend_cascade_dnn3_dev(pg_ctx* ctx, const pg_table* t, const pg_model
     uint32_t* const h_flags = ctx->h_status + pg::kExprFlagAt;       // [0, 256) the coarse RankScore's flags, [256, 512) the fine one's
     PG_HIP(hipMemcpyAsync(h_flags, ps.d_err, (size_t)nq * 4, hipMemcpyDeviceToHost, ctx->stream));
     const pg_trim_rule keep = {PG_TRIM_ANY, PG_TRIM_FIX, n_keep};
-    if ((rc = pg::candidates_trim_locked(ctx, &keep, 1, nq, cap, n_keep, d_rows, c_fused, d_source, d_count, nullptr, 0, nullptr, c_rank, 1,
-                                         c_order, d_out_rows, d_out_coarse_fused, d_out_source, nullptr, nullptr, d_out_model_scores + nk,
-                                         d_out_count)))
-        return rc;
+    // the survivors carry the coarse fused score as their score and the coarse model score as one f32 plane
+    pg::CandIn in{};
+    in.rows = d_rows;
+    in.score = reinterpret_cast<const unsigned long long*>(c_fused);
+    in.source = d_source;
+    in.count = d_count;
+    in.planes32 = reinterpret_cast<const uint32_t*>(c_rank);
+    in.nq = nq;
+    in.cap = cap;
+    in.n_f32 = 1;
+    pg::CandOut out{};
+    out.rows = d_out_rows;
+    out.score = reinterpret_cast<unsigned long long*>(d_out_coarse_fused);
+    out.source = d_out_source;
+    out.planes32 = reinterpret_cast<uint32_t*>(d_out_model_scores + nk);
+    out.count = d_out_count;
+    out.out_cap = n_keep;
+    if ((rc = pg::candidates_trim_locked(ctx, &keep, 1, in, out, c_order))) return rc;
     if ((rc = pg::post_scratch(ctx, cf, nq, &ps))) return rc;
     if ((rc = pg::recommend_post_locked(ctx, cf, 0, nq, ps))) return rc;
     PG_HIP(hipMemcpyAsync(h_flags + pg::kMaxQueries, ps.d_err, (size_t)nq * 4, hipMemcpyDeviceToHost, ctx->stream));

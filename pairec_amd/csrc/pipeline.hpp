@@ -3,6 +3,7 @@
 // coalescer (coalescer.hip) and the shard group (group.hip).
 #pragma once
 #include "common.hpp"
+#include "cand_lists.hpp"
 
 namespace pg {
 
@@ -111,21 +112,14 @@ int post_fuse_sort_locked(pg_ctx* ctx, const RecommendCall& c, uint32_t q0, uint
 int fuse_scores_enqueue_locked(pg_ctx* ctx, const pg_expr* e, const int* var_src, int nv, const float* d_recall, const float* d_rank,
                                size_t rank_stride, uint32_t n, uint32_t items_per_flag, double* d_vars, uint32_t* d_err, double* d_fused,
                                const double* d_recall64 = nullptr);
-// trim.hip: quotas per source class over each request's score order (arguments as pg_candidates_trim_dev, checked by the caller;
-// out_cap from pg_trim_out_cap); d_order = each request's positions in score order where the caller has sorted already, else NULL.
+// trim.hip: quotas per source class over each request's score order (the lists as cand_lists.hpp states them, checked by the caller;
+// out.out_cap from pg_trim_out_cap); d_order = each request's positions in score order where the caller has sorted already, else
+// NULL.  Caller holds ctx->mu; no synchronisation.
+int candidates_trim_locked(pg_ctx* ctx, const pg_trim_rule* rules, uint32_t n_rules, const CandIn& in, const CandOut& out,
+                           const uint32_t* d_order);
+// blend.hip: SnakeFilter / CompletelyFairCountFilter over the same lists (checked by the caller; out.out_cap from pg_blend_out_cap).
 // Caller holds ctx->mu; no synchronisation.
-int candidates_trim_locked(pg_ctx* ctx, const pg_trim_rule* rules, uint32_t n_rules, uint32_t nq, uint32_t cap, uint32_t out_cap,
-                           const uint64_t* d_rows, const double* d_score, const uint8_t* d_source, const uint32_t* d_count,
-                           const double* d_planes_f64, uint32_t n_f64, const uint32_t* d_source_mask, const float* d_planes_f32, uint32_t n_f32,
-                           const uint32_t* d_order, uint64_t* d_out_rows, double* d_out_score, uint8_t* d_out_source, double* d_out_planes_f64,
-                           uint32_t* d_out_source_mask, float* d_out_planes_f32, uint32_t* d_out_count);
-// blend.hip: SnakeFilter / CompletelyFairCountFilter over the same arrays (arguments as pg_candidates_blend_dev, checked by the
-// caller; out_cap from pg_blend_out_cap).  Caller holds ctx->mu; no synchronisation.
-int candidates_blend_locked(pg_ctx* ctx, const pg_blend_conf* conf, uint32_t nq, uint32_t cap, uint32_t out_cap, const uint64_t* d_rows,
-                            const double* d_score, const uint8_t* d_source, const uint32_t* d_count, const double* d_planes_f64,
-                            uint32_t n_f64, const uint32_t* d_source_mask, const float* d_planes_f32, uint32_t n_f32, uint64_t* d_out_rows,
-                            double* d_out_score, uint8_t* d_out_source, double* d_out_planes_f64, uint32_t* d_out_source_mask,
-                            float* d_out_planes_f32, uint32_t* d_out_count);
+int candidates_blend_locked(pg_ctx* ctx, const pg_blend_conf* conf, const CandIn& in, const CandOut& out);
 int rerank_select_locked(pg_ctx* ctx, const RecommendCall& c, uint32_t q0, uint32_t nq, const PostScratch& ps);
 int rerank_run_locked(pg_ctx* ctx, const RecommendCall& c, uint32_t q0, uint32_t nq, const PostScratch& ps);
 

@@ -28,31 +28,17 @@ constexpr uint32_t kTrimChunk = 1024;            // positions walked at a time =
 static_assert(kTrimMaxRules == PG_TRIM_MAX_RULES && kTrimMaxSources == PG_TRIM_MAX_SOURCES && kTrimMaxPlanes == PG_TRIM_MAX_PLANES &&
                   kTrimMaxCap == PG_TRIM_MAX_CAP && kTrimChunk == PG_TRIM_CHUNK,
               "include/pairec_gpu.h repeats these");
-static_assert(kTrimMaxSources == PG_FANIN_MAX_SOURCES && kTrimMaxCap == PG_FANIN_MAX_CAP, "the trim takes the fan-in's outputs as they are");
+static_assert(kTrimMaxSources == kCandMaxSources && kTrimMaxPlanes == kCandMaxPlanes && kTrimMaxCap == kCandMaxCap,
+              "the header names the limits per stage; cand_lists.hpp holds them together");
 constexpr uint32_t kTrimThreads = kTrimChunk;
 constexpr uint32_t kTrimWaves = kTrimThreads / kWave;
 constexpr uint32_t kTrimNone = 0xFFu;            // the class of padding and of entries whose source no rule names
-constexpr unsigned long long kTrimPad = ~0ull;
-constexpr unsigned long long kTrimNan = 0x7FF8000000000000ull;
-constexpr unsigned long long kTrimNegInf = 0xFFF0000000000000ull;
 
 struct TrimArgs {
-    const uint64_t* rows;                        // [nq][cap]
-    const unsigned long long* score;             // fp64 bits
-    const uint8_t* source;                       // NULL: the single rule matches every source
-    const uint32_t* count;                       // [nq] or NULL
-    const unsigned long long* planes64;          // [n_f64][nq][cap] fp64 bits or NULL
-    const uint32_t* mask;                        // [nq][cap] or NULL
-    const uint32_t* planes32;                    // [n_f32][nq][cap] fp32 bits or NULL
+    CandIn in;                                   // (source NULL: the single rule matches every source)
+    CandOut out;
     const uint32_t* order;                       // [nq][cap]: each request's positions in score order
-    uint64_t* out_rows;                          // [nq][out_cap] ...
-    unsigned long long* out_score;
-    uint8_t* out_source;
-    unsigned long long* out_planes64;
-    uint32_t* out_mask;
-    uint32_t* out_planes32;
-    uint32_t* out_count;                         // [nq]
-    uint32_t nq, cap, out_cap, n_f64, n_f32, n_rules;
+    uint32_t n_rules;
     uint32_t any;                                // the single rule is PG_TRIM_ANY
     uint32_t r_count[kTrimMaxRules];
     uint8_t r_source[kTrimMaxRules], r_type[kTrimMaxRules];
@@ -60,9 +46,9 @@ struct TrimArgs {
 
 // the class (= rule index) of the entry at position p of the request, kTrimNone for padding and for sources no rule names
 __device__ inline uint32_t trim_class(const TrimArgs& a, const uint32_t* cls_of, size_t in0, uint32_t p, uint32_t n_valid) {
-    if (p >= n_valid || a.rows[in0 + p] == kTrimPad) return kTrimNone;
+    if (p >= n_valid || a.in.rows[in0 + p] == kCandPad) return kTrimNone;
     if (a.any) return 0u;
-    const uint32_t s = a.source[in0 + p];
+    const uint32_t s = a.in.source[in0 + p];
     return s < kTrimMaxSources ? cls_of[s] : kTrimNone;
 }
 
@@ -72,9 +58,9 @@ __global__ __launch_bounds__(kTrimThreads) void candidates_trim_kernel(TrimArgs 
     __shared__ uint32_t wcnt[2][kTrimMaxRules][kTrimWaves];
     __shared__ uint32_t total_s;
     const uint32_t q = blockIdx.x, tid = threadIdx.x, wave = tid / kWave, lane = tid & (kWave - 1);
-    const uint32_t cap = a.cap, out_cap = a.out_cap, n_rules = a.n_rules;
+    const uint32_t cap = a.in.cap, out_cap = a.out.out_cap, n_rules = a.n_rules;
     const size_t in0 = (size_t)q * cap, out0 = (size_t)q * out_cap;
-    const uint32_t n_valid = a.count ? min(a.count[q], cap) : cap;
+    const uint32_t n_valid = cand_n_valid(a.in, q);
     if (tid < kTrimMaxSources) cls_of[tid] = kTrimNone;
     if (tid < kTrimMaxRules) {
         ccnt[tid] = 0;
@@ -133,16 +119,7 @@ __global__ __launch_bounds__(kTrimThreads) void candidates_trim_kernel(TrimArgs 
             uint32_t rank = run[c] + before;
             for (uint32_t w = 0; w < wave; ++w) rank += wc[c][w];
             const uint32_t dst = base[c] + rank;
-            if (rank < take[c] && dst < out_cap) {
-                const size_t src = in0 + pos, o = out0 + dst;
-                a.out_rows[o] = a.rows[src];
-                a.out_score[o] = a.score[src];
-                if (a.out_source) a.out_source[o] = a.source[src];
-                if (a.out_mask) a.out_mask[o] = a.mask[src];
-                const size_t in_plane = (size_t)a.nq * cap, out_plane = (size_t)a.nq * out_cap;
-                for (uint32_t f = 0; f < a.n_f64; ++f) a.out_planes64[f * out_plane + o] = a.planes64[f * in_plane + src];
-                for (uint32_t f = 0; f < a.n_f32; ++f) a.out_planes32[f * out_plane + o] = a.planes32[f * in_plane + src];
-            }
+            if (rank < take[c] && dst < out_cap) cand_carry(a.in, a.out, in0 + pos, out0 + dst, true);
         }
         __syncthreads();
         // (the running counts move between this chunk's reads and the next chunk's, which lie behind its barrier)
@@ -154,17 +131,8 @@ __global__ __launch_bounds__(kTrimThreads) void candidates_trim_kernel(TrimArgs 
     }
     // pad: every slot behind the takes
     const uint32_t total = total_s;
-    const size_t out_plane = (size_t)a.nq * out_cap;
-    for (uint32_t j = total + tid; j < out_cap; j += kTrimThreads) {
-        const size_t o = out0 + j;
-        a.out_rows[o] = kTrimPad;
-        a.out_score[o] = kTrimNegInf;
-        if (a.out_source) a.out_source[o] = 0xFFu;
-        if (a.out_mask) a.out_mask[o] = 0u;
-        for (uint32_t f = 0; f < a.n_f64; ++f) a.out_planes64[f * out_plane + o] = kTrimNan;
-        for (uint32_t f = 0; f < a.n_f32; ++f) a.out_planes32[f * out_plane + o] = 0u;
-    }
-    if (tid == 0) a.out_count[q] = total;
+    cand_pad(a.in, a.out, q, total + tid, kTrimThreads, kCandNegInf);
+    if (tid == 0) a.out.count[q] = total;
 }
 
 // the rules as the reference can run them (priority_adjust_count_filter.go:123,193-195) and the width of what they keep
@@ -222,14 +190,12 @@ int trim_check_rules(const pg_trim_rule* rules, uint32_t n_rules, uint32_t cap, 
 
 // caller holds ctx->mu and has checked the arguments (trim_check_rules, the pointers); d_order: each request's positions in score
 // order if the caller has them already, else NULL (the score sort runs here); no synchronisation
-int candidates_trim_locked(pg_ctx* ctx, const pg_trim_rule* rules, uint32_t n_rules, uint32_t nq, uint32_t cap, uint32_t out_cap,
-                           const uint64_t* d_rows, const double* d_score, const uint8_t* d_source, const uint32_t* d_count,
-                           const double* d_planes_f64, uint32_t n_f64, const uint32_t* d_source_mask, const float* d_planes_f32, uint32_t n_f32,
-                           const uint32_t* d_order, uint64_t* d_out_rows, double* d_out_score, uint8_t* d_out_source, double* d_out_planes_f64,
-                           uint32_t* d_out_source_mask, float* d_out_planes_f32, uint32_t* d_out_count) {
+int candidates_trim_locked(pg_ctx* ctx, const pg_trim_rule* rules, uint32_t n_rules, const CandIn& in, const CandOut& out,
+                           const uint32_t* d_order) {
+    const uint32_t nq = in.nq, cap = in.cap;
     int rc;
-    if (out_cap == 0) {                          // every count is 0: nothing is kept, nothing but the counts is written
-        PG_HIP(hipMemsetAsync(d_out_count, 0, (size_t)nq * 4, ctx->stream));
+    if (out.out_cap == 0) {                      // every count is 0: nothing is kept, nothing but the counts is written
+        PG_HIP(hipMemsetAsync(out.count, 0, (size_t)nq * 4, ctx->stream));
         return PG_OK;
     }
     if (!d_order) {
@@ -240,30 +206,13 @@ int candidates_trim_locked(pg_ctx* ctx, const pg_trim_rule* rules, uint32_t n_ru
             }))) return rc;
         if ((rc = uniform_offsets_locked(ctx, nq, cap, d_off))) return rc;
         // (what the sort makes of padding does not matter: the kernel skips padding wherever it lies in the order)
-        if ((rc = sort_dev_locked(ctx, d_score, d_off, nq, nq * cap, cap, 1, d_ord))) return rc;
+        if ((rc = sort_dev_locked(ctx, reinterpret_cast<const double*>(in.score), d_off, nq, nq * cap, cap, 1, d_ord))) return rc;
         d_order = d_ord;
     }
     TrimArgs a{};
-    a.rows = d_rows;
-    a.score = reinterpret_cast<const unsigned long long*>(d_score);
-    a.source = d_source;
-    a.count = d_count;
-    a.planes64 = reinterpret_cast<const unsigned long long*>(d_planes_f64);
-    a.mask = d_source_mask;
-    a.planes32 = reinterpret_cast<const uint32_t*>(d_planes_f32);
+    a.in = in;
+    a.out = out;
     a.order = d_order;
-    a.out_rows = d_out_rows;
-    a.out_score = reinterpret_cast<unsigned long long*>(d_out_score);
-    a.out_source = d_source ? d_out_source : nullptr;
-    a.out_planes64 = reinterpret_cast<unsigned long long*>(d_out_planes_f64);
-    a.out_mask = d_source_mask ? d_out_source_mask : nullptr;
-    a.out_planes32 = reinterpret_cast<uint32_t*>(d_out_planes_f32);
-    a.out_count = d_out_count;
-    a.nq = nq;
-    a.cap = cap;
-    a.out_cap = out_cap;
-    a.n_f64 = d_planes_f64 ? n_f64 : 0;
-    a.n_f32 = d_planes_f32 ? n_f32 : 0;
     a.n_rules = n_rules;
     a.any = rules[0].source == PG_TRIM_ANY ? 1u : 0u;
     for (uint32_t r = 0; r < n_rules; ++r) {
@@ -296,17 +245,16 @@ int pg_candidates_trim_dev(pg_ctx* ctx, const pg_trim_rule* rules, uint32_t n_ru
     int rc;
     if ((rc = pg::trim_check_rules(rules, n_rules, cap, &out_cap, "pg_candidates_trim_dev"))) return rc;
     PG_REQUIRE(d_source || rules[0].source == PG_TRIM_ANY, "pg_candidates_trim_dev: rules that name sources need d_source");
-    PG_REQUIRE(!d_source == !d_out_source && !d_source_mask == !d_out_source_mask,
-               "pg_candidates_trim_dev: d_source / d_source_mask and their outputs come in pairs");
-    PG_REQUIRE(!d_planes_f64 == !d_out_planes_f64 && !d_planes_f32 == !d_out_planes_f32,
-               "pg_candidates_trim_dev: a carried plane set and its output come in pairs");
-    PG_REQUIRE((!d_planes_f64 || (n_f64 >= 1 && n_f64 <= pg::kTrimMaxPlanes)) && (!d_planes_f32 || (n_f32 >= 1 && n_f32 <= pg::kTrimMaxPlanes)),
-               "pg_candidates_trim_dev: a carried plane set holds 1..%u planes", pg::kTrimMaxPlanes);
+    if ((rc = pg::cand_lists_check("pg_candidates_trim_dev", d_source, d_planes_f64, n_f64, d_source_mask, d_planes_f32, n_f32, d_out_source,
+                                   d_out_planes_f64, d_out_source_mask, d_out_planes_f32, pg::kTrimMaxPlanes)))
+        return rc;
+    pg::CandIn in;
+    pg::CandOut out;
+    pg::cand_lists_bind(nq, cap, out_cap, d_rows, d_score, d_source, d_count, d_planes_f64, n_f64, d_source_mask, d_planes_f32, n_f32,
+                        d_out_rows, d_out_score, d_out_source, d_out_planes_f64, d_out_source_mask, d_out_planes_f32, d_out_count, &in, &out);
     std::lock_guard<std::mutex> g(ctx->mu);
     PG_HIP(hipSetDevice(ctx->device));
-    return pg::candidates_trim_locked(ctx, rules, n_rules, nq, cap, out_cap, d_rows, d_score, d_source, d_count, d_planes_f64, n_f64,
-                                      d_source_mask, d_planes_f32, n_f32, nullptr, d_out_rows, d_out_score, d_out_source, d_out_planes_f64,
-                                      d_out_source_mask, d_out_planes_f32, d_out_count);
+    return pg::candidates_trim_locked(ctx, rules, n_rules, in, out, nullptr);
 }
 
 }  // extern "C"

@@ -76,15 +76,15 @@ def blend_out_cap(conf, cap: int) -> int:
     return out.value
 
 
-def _blend_arrays(who, conf, rows, score, source, count, planes_f64, source_mask, planes_f32):
-    """the blend's host arrays, checked and made contiguous → (nq, cap, out_cap, [rows, score, source, count, planes_f64,
-    source_mask, planes_f32], outs, n64, n32)"""
+def _cand_arrays(who, out_cap_of, rows, score, source, count, planes_f64, source_mask, planes_f32):
+    """a request batch's candidate lists on host arrays, checked and made contiguous; out_cap_of: cap → the outputs' width →
+    (nq, cap, [rows, score, source, count, planes_f64, source_mask, planes_f32], outs, n64, n32)"""
     r = np.ascontiguousarray(rows, dtype=np.uint64)
     sc = np.ascontiguousarray(score, dtype=np.float64)
     if r.ndim != 2 or sc.shape != r.shape:
         raise ValueError("%s: rows and score are [nq][cap]" % who)
     nq, cap = r.shape
-    out_cap = blend_out_cap(conf, cap)
+    out_cap = out_cap_of(cap)
     opt = [None if source is None else np.ascontiguousarray(source, dtype=np.uint8),
            None if count is None else np.ascontiguousarray(count, dtype=np.uint32),
            None if planes_f64 is None else np.ascontiguousarray(planes_f64, dtype=np.float64),
@@ -103,14 +103,14 @@ def _blend_arrays(who, conf, rows, score, source, count, planes_f64, source_mask
             None if opt[2] is None else np.empty((n64, nq, out_cap), np.float64),
             None if opt[3] is None else np.empty((nq, out_cap), np.uint32),
             None if opt[4] is None else np.empty((n32, nq, out_cap), np.float32), np.empty(nq, np.uint32)]
-    return nq, cap, out_cap, [r, sc] + opt, outs, n64, n32
+    return nq, cap, [r, sc] + opt, outs, n64, n32
 
 
 def candidates_blend_host(conf, rows, score, source=None, count=None, planes_f64=None, source_mask=None, planes_f32=None):
     """pg_candidates_blend_host: SnakeFilter / CompletelyFairCountFilter on host arrays by the library's host statement (no
     context, no device); arguments and result as Context.candidates_blend."""
-    nq, cap, _, ins, outs, n64, n32 = _blend_arrays("candidates_blend_host", conf, rows, score, source, count, planes_f64, source_mask,
-                                                    planes_f32)
+    nq, cap, ins, outs, n64, n32 = _cand_arrays("candidates_blend_host", lambda cap: blend_out_cap(conf, cap), rows, score, source, count,
+                                                planes_f64, source_mask, planes_f32)
     v = lambda a: None if a is None else _ptr(a)                                     # noqa: E731
     _lib.check(_lib.load().pg_candidates_blend_host(C.byref(_blend_conf(conf)), nq, cap, v(ins[0]), v(ins[1]), v(ins[2]), v(ins[3]),
                                                     v(ins[4]), n64, v(ins[5]), v(ins[6]), n32, *[v(a) for a in outs]))
@@ -517,41 +517,25 @@ class Context:
         [nq][cap] f64, source [nq][cap] u8, count [nq], recall_scores [n][nq][cap] f64 and source_mask, plus planes_f32
         [n][nq][cap] →  (rows, score, source, planes_f64, source_mask, planes_f32, count), [nq][out_cap] each, None where the
         input was None."""
-        r = np.ascontiguousarray(rows, dtype=np.uint64)
-        sc = np.ascontiguousarray(score, dtype=np.float64)
-        if r.ndim != 2 or sc.shape != r.shape:
-            raise ValueError("candidates_trim: rows and score are [nq][cap]")
-        nq, cap = r.shape
-        out_cap = trim_out_cap(rules, cap)
-        opt = [None if source is None else np.ascontiguousarray(source, dtype=np.uint8),
-               None if count is None else np.ascontiguousarray(count, dtype=np.uint32),
-               None if planes_f64 is None else np.ascontiguousarray(planes_f64, dtype=np.float64),
-               None if source_mask is None else np.ascontiguousarray(source_mask, dtype=np.uint32),
-               None if planes_f32 is None else np.ascontiguousarray(planes_f32, dtype=np.float32)]
-        for a, shape in ((opt[0], (nq, cap)), (opt[1], (nq,)), (opt[3], (nq, cap))):
-            if a is not None and a.shape != shape:
-                raise ValueError("candidates_trim: source and source_mask are [nq][cap], count [nq]")
-        for a in (opt[2], opt[4]):
-            if a is not None and (a.ndim != 3 or a.shape[1:] != (nq, cap)):
-                raise ValueError("candidates_trim: planes are [n][nq][cap]")
-        n64 = opt[2].shape[0] if opt[2] is not None else 0
-        n32 = opt[4].shape[0] if opt[4] is not None else 0
-        outs = [np.empty((nq, out_cap), np.uint64), np.empty((nq, out_cap), np.float64),
-                None if opt[0] is None else np.empty((nq, out_cap), np.uint8),
-                None if opt[2] is None else np.empty((n64, nq, out_cap), np.float64),
-                None if opt[3] is None else np.empty((nq, out_cap), np.uint32),
-                None if opt[4] is None else np.empty((n32, nq, out_cap), np.float32), np.empty(nq, np.uint32)]
+        nq, cap, ins, outs, n64, n32 = _cand_arrays("candidates_trim", lambda cap: trim_out_cap(rules, cap), rows, score, source, count,
+                                                    planes_f64, source_mask, planes_f32)
+        return self._cand_run(ins, outs, lambda d_in, d_out: self.candidates_trim_dev(
+            rules, nq, cap, d_in[0], d_in[1], d_in[2], d_in[3], d_in[4], n64, d_in[5], d_in[6], n32, *d_out))
+
+    def _cand_run(self, ins, outs, launch):
+        """upload ins, allocate outs, launch(d_in, d_out), synchronise, download, free → outs as a tuple (None stays None and
+        travels as address 0; an empty array still gets an allocation, so that it is not taken for an absent one)"""
         bufs = []
         try:
             d_in = []
-            for a in [r, sc] + opt:
+            for a in ins:
                 d_in.append(self.to_device(a) if a is not None and a.nbytes else (self.malloc(16) if a is not None else 0))
                 bufs.append(d_in[-1])
             d_out = []
             for a in outs:
                 d_out.append(self.malloc(max(a.nbytes, 16)) if a is not None else 0)
                 bufs.append(d_out[-1])
-            self.candidates_trim_dev(rules, nq, cap, d_in[0], d_in[1], d_in[2], d_in[3], d_in[4], n64, d_in[5], d_in[6], n32, *d_out)
+            launch(d_in, d_out)
             self.synchronize()
             for a, p_ in zip(outs, d_out):
                 if a is not None and a.nbytes:
@@ -584,28 +568,10 @@ class Context:
         """SnakeFilter / CompletelyFairCountFilter on host arrays (pg_candidates_blend_dev): the arrays of candidates_trim, conf =
         (BLEND_SNAKE_REFILL | BLEND_SNAKE_SKIP | BLEND_FAIR, retain_num, [(source, weight)]) → (rows, score, source, planes_f64,
         source_mask, planes_f32, count), [nq][out_cap] each, None where the input was None."""
-        nq, cap, _, ins, outs, n64, n32 = _blend_arrays("candidates_blend", conf, rows, score, source, count, planes_f64, source_mask,
-                                                        planes_f32)
-        bufs = []
-        try:
-            d_in = []
-            for a in ins:
-                d_in.append(self.to_device(a) if a is not None and a.nbytes else (self.malloc(16) if a is not None else 0))
-                bufs.append(d_in[-1])
-            d_out = []
-            for a in outs:
-                d_out.append(self.malloc(max(a.nbytes, 16)) if a is not None else 0)
-                bufs.append(d_out[-1])
-            self.candidates_blend_dev(conf, nq, cap, d_in[0], d_in[1], d_in[2], d_in[3], d_in[4], n64, d_in[5], d_in[6], n32, *d_out)
-            self.synchronize()
-            for a, p_ in zip(outs, d_out):
-                if a is not None and a.nbytes:
-                    self.d2h(a, p_)
-        finally:
-            for b in bufs:
-                if b:
-                    self.free(b)
-        return tuple(outs)
+        nq, cap, ins, outs, n64, n32 = _cand_arrays("candidates_blend", lambda cap: blend_out_cap(conf, cap), rows, score, source, count,
+                                                    planes_f64, source_mask, planes_f32)
+        return self._cand_run(ins, outs, lambda d_in, d_out: self.candidates_blend_dev(
+            conf, nq, cap, d_in[0], d_in[1], d_in[2], d_in[3], d_in[4], n64, d_in[5], d_in[6], n32, *d_out))
 
     def diversity_rules_dev(self, cfg, n_cols: int, nq: int, cap: int, d_count: int, d_dims: int, d_source: int, d_enable: int,
                             d_order: int) -> None:
@@ -709,51 +675,11 @@ class Context:
         """ItemStateFilter on host arrays (pg_item_state_filter_dev): fanin_merge's rows [nq][cap] u64, score [nq][cap] f64,
         source [nq][cap] u8, count [nq], planes [n][nq][cap], source_mask [nq][cap] u32; users: one {name: value} per request →
         (rows, score, source, planes_f64, source_mask, planes_f32, count), [nq][cap] each, None where the input was None."""
-        r = np.ascontiguousarray(rows, dtype=np.uint64)
-        sc = np.ascontiguousarray(score, dtype=np.float64)
-        if r.ndim != 2 or sc.shape != r.shape:
-            raise ValueError("item_state_filter: rows and score are [nq][cap]")
-        nq, cap = r.shape
-        opt = [None if source is None else np.ascontiguousarray(source, dtype=np.uint8),
-               None if count is None else np.ascontiguousarray(count, dtype=np.uint32),
-               None if planes_f64 is None else np.ascontiguousarray(planes_f64, dtype=np.float64),
-               None if source_mask is None else np.ascontiguousarray(source_mask, dtype=np.uint32),
-               None if planes_f32 is None else np.ascontiguousarray(planes_f32, dtype=np.float32)]
-        for a, shape in ((opt[0], (nq, cap)), (opt[1], (nq,)), (opt[3], (nq, cap))):
-            if a is not None and a.shape != shape:
-                raise ValueError("item_state_filter: source and source_mask are [nq][cap], count [nq]")
-        for a in (opt[2], opt[4]):
-            if a is not None and (a.ndim != 3 or a.shape[1:] != (nq, cap)):
-                raise ValueError("item_state_filter: planes are [n][nq][cap]")
-        n64 = opt[2].shape[0] if opt[2] is not None else 0
-        n32 = opt[4].shape[0] if opt[4] is not None else 0
+        nq, cap, ins, outs, n64, n32 = _cand_arrays("item_state_filter", lambda cap: cap, rows, score, source, count, planes_f64,
+                                                    source_mask, planes_f32)
         uv, up = self._cond_user(cond, users, nq)
-        outs = [np.empty((nq, cap), np.uint64), np.empty((nq, cap), np.float64),
-                None if opt[0] is None else np.empty((nq, cap), np.uint8),
-                None if opt[2] is None else np.empty((n64, nq, cap), np.float64),
-                None if opt[3] is None else np.empty((nq, cap), np.uint32),
-                None if opt[4] is None else np.empty((n32, nq, cap), np.float32), np.empty(nq, np.uint32)]
-        bufs = []
-        try:
-            d_in = []
-            for a in [r, sc] + opt + [uv, up]:
-                d_in.append(self.to_device(a) if a is not None else 0)
-                bufs.append(d_in[-1])
-            d_out = []
-            for a in outs:
-                d_out.append(self.malloc(max(a.nbytes, 16)) if a is not None else 0)
-                bufs.append(d_out[-1])
-            self.item_state_filter_dev(cond, fs, nq, cap, d_in[0], d_in[1], d_in[2], d_in[3], d_in[4], n64, d_in[5], d_in[6], n32,
-                                       d_in[7], d_in[8], *d_out)
-            self.synchronize()
-            for a, p_ in zip(outs, d_out):
-                if a is not None and a.nbytes:
-                    self.d2h(a, p_)
-        finally:
-            for b in bufs:
-                if b:
-                    self.free(b)
-        return tuple(outs)
+        return self._cand_run(ins + [uv, up], outs, lambda d_in, d_out: self.item_state_filter_dev(
+            cond, fs, nq, cap, d_in[0], d_in[1], d_in[2], d_in[3], d_in[4], n64, d_in[5], d_in[6], n32, d_in[7], d_in[8], *d_out))
 
     def boost_scores(self, cond, fs, rows, score, count=None, users=None, filter_all: bool = False):
         """BoostScoreSort's rewrite on host arrays (pg_boost_scores_dev): rows [nq][cap] u64, score [nq][cap] f64, count [nq],

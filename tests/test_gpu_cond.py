@@ -306,6 +306,21 @@ def test_filter_sizes(ctx, world, cap):
         trim_ref.same(run_filter(ctx, world, full, [USERS[0]] * 3), want_filter(world, full, [0, 0, 0]))
 
 
+@pytest.mark.parametrize("cap", (65, 1025))
+def test_filter_optional_arrays_one_at_a_time(ctx, world, cap):
+    """every optional array absent, then each present alone, at one lane past a wave and one position past a chunk: what binds the
+    ABI's pointers decides per array what the kernel carries and pads"""
+    rng = np.random.default_rng(7000 + cap)
+    rows, score, source, count, p64, mask, p32 = make_case(rng, 3, cap, ("mixed", "all", "none"), n64=2, n32=3)
+    users = [USERS[0]] * 3
+    for case in ((rows, score, None, None, None, None, None), (rows, score, source, None, None, None, None),
+                 (rows, score, None, count, None, None, None), (rows, score, None, None, p64, None, None),
+                 (rows, score, None, None, None, mask, None), (rows, score, None, None, None, None, p32)):
+        got = run_filter(ctx, world, case, users)
+        trim_ref.same(got, want_filter(world, case, [0, 0, 0]))
+        assert 0 < got[6][0] < cap and got[6][1] == cap and got[6][2] == 0
+
+
 def test_filter_256_requests_users_and_flavours(ctx, world):
     rng = np.random.default_rng(256)
     nq, cap = 256, 65
@@ -366,6 +381,27 @@ def test_filter_refusals_leave_the_context_usable(ctx, world):
     with pytest.raises(PgError) as ei:
         ctx.item_state_filter_dev(world.filter, world.fs, 1, 16, 4096, 8192, 0, 0, 0, 0, 0, 0, 0, 8, 8, 4096 + 64, 16384, 0, 0, 0, 0, 32768)
     assert ei.value.code == -1 and "overlaps" in str(ei.value)
+    # what the checks of the candidate lists answer, code and text (recorded from the build before cand_lists.hpp stated them once);
+    # every address is made up: the calls are refused before anything reaches the stream
+    d = 1 << 16
+
+    def call(nq=1, cap=16, **kw):
+        a = dict(d_rows=d, d_score=2 * d, d_source=3 * d, d_count=0, d_planes_f64=0, n_f64=0, d_source_mask=0, d_planes_f32=0, n_f32=0,
+                 d_user_vals=8, d_user_present=8, d_out_rows=4 * d, d_out_score=5 * d, d_out_source=6 * d, d_out_planes_f64=0,
+                 d_out_source_mask=0, d_out_planes_f32=0, d_out_count=7 * d)
+        a.update(kw)
+        ctx.item_state_filter_dev(world.filter, world.fs, nq, cap, **a)
+
+    for kw, code, text in ((dict(d_out_source=0), -1, "d_source / d_source_mask and their outputs come in pairs"),
+                           (dict(d_source_mask=8 * d), -1, "d_source / d_source_mask and their outputs come in pairs"),
+                           (dict(d_planes_f64=8 * d, n_f64=1), -1, "a carried plane set and its output come in pairs"),
+                           (dict(d_planes_f64=8 * d, d_out_planes_f64=9 * d, n_f64=0), -1, "a carried plane set holds 1..8 planes"),
+                           (dict(d_planes_f64=8 * d, d_out_planes_f64=9 * d, n_f64=9), -1, "a carried plane set holds 1..8 planes"),
+                           (dict(d_rows=0), -1, "NULL argument"), (dict(nq=0), -1, "nq=0 must be in [1,256]"),
+                           (dict(cap=0), -4, "cap=0 unsupported (1..16384)")):
+        with pytest.raises(PgError) as ei:
+            call(**kw)
+        assert ei.value.code == code and str(ei.value).endswith(": pg_item_state_filter_dev: " + text), kw
     trim_ref.same(run_filter(ctx, world, case, [USERS[0]]), want_filter(world, case, [0]))
 
 

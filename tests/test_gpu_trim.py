@@ -223,6 +223,17 @@ def test_argument_errors_leave_the_context_usable(ctx):
         with pytest.raises(PgError) as ei:
             call(**kw)
         assert ei.value.code in (-1, -4) and "pg_candidates_trim_dev" in str(ei.value), kw
+    # what the checks of the candidate lists answer, code and text (recorded from the build before cand_lists.hpp stated them once)
+    for kw, code, text in ((dict(d_out_source=0), -1, "d_source / d_source_mask and their outputs come in pairs"),
+                           (dict(d_source_mask=d), -1, "d_source / d_source_mask and their outputs come in pairs"),
+                           (dict(d_planes_f64=d, n_f64=1), -1, "a carried plane set and its output come in pairs"),
+                           (dict(d_planes_f64=d, d_out_planes_f64=d, n_f64=0), -1, "a carried plane set holds 1..8 planes"),
+                           (dict(d_planes_f64=d, d_out_planes_f64=d, n_f64=9), -1, "a carried plane set holds 1..8 planes"),
+                           (dict(d_rows=0), -1, "NULL argument"), (dict(nq=0), -1, "nq=0 must be in [1,256]"),
+                           (dict(cap=0), -4, "cap=0 unsupported (1..16384)")):
+        with pytest.raises(PgError) as ei:
+            call(**kw)
+        assert ei.value.code == code and str(ei.value).endswith(": pg_candidates_trim_dev: " + text), kw
     ctx.free(d)
     check(ctx, ok, random_case(np.random.default_rng(15), 2, 16, 2))
 
