@@ -49,13 +49,20 @@ def exchange_width(k: int, world: int) -> int:
 
 def tail_needed(torch, g_rows, g_scores, m_rows, m_scores, k: int):
     """[G] bool: shard g's LAST SENT entry of some request ranks strictly inside that request's merged top-k, so an entry it
-    did not send could too.  Order = the recall's: score descending, row ascending; anything odd (NaN scores, padding rows in the
-    last sent position or in the k-th merged one) counts as needed — the full exchange is always right."""
-    s_k, r_k = m_scores[:, k - 1], m_rows[:, k - 1]                        # [nq]
-    s_m, r_m = g_scores[:, :, -1], g_rows[:, :, -1]                        # [G, nq]
-    inside = (s_m > s_k[None]) | ((s_m == s_k[None]) & (r_m < r_k[None]))
-    odd = torch.isnan(s_m) | torch.isnan(s_k)[None] | (r_m < 0) | (r_k < 0)[None]
-    return (inside | odd).any(dim=1)
+    did not send could too.  Order = the recall's, the merge's and tail_needed_kernel's (csrc/group.hip): score descending BY
+    ORDERED BITS — IEEE totalOrder, so +0.0 ranks before -0.0 although they compare equal as floats, and every NaN ranks last —
+    then row ascending.  A float compare here would call (5, +0.0) and (0, -0.0) a tie that row 0 wins, while the merge puts row 5
+    first: the two statements of one criterion have to order scores the same way.  A padding row in the last sent position means
+    the list ended there (nothing was left unsent); a k-th merged entry that is padding (the merged list is short of k) makes
+    every list that did not end suspect."""
+    def ordered(s):
+        b = s.contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+        ob = torch.where((b & 0x80000000) != 0, b ^ 0xFFFFFFFF, b | 0x80000000)
+        return torch.where(torch.isnan(s), torch.zeros_like(ob), ob)
+    a, r_m = ordered(g_scores[:, :, -1]), g_rows[:, :, -1]                 # [G, nq]
+    b, r_k = ordered(m_scores[:, k - 1]), m_rows[:, k - 1]                 # [nq]
+    inside = (a > b[None]) | ((a == b[None]) & (r_m < r_k[None]))
+    return ((r_m >= 0) & ((r_k < 0)[None] | inside)).any(dim=1)
 
 
 def shard_range(total_rows: int, world: int, rank: int) -> Tuple[int, int]:
@@ -259,14 +266,15 @@ class GpuShardEngine:
         return self.torch.cuda.stream(self.stream)
 
     def recall_local(self, queries, nq, k):
-        rows, scores = self.t_rows[:nq, :k], self.t_scores[:nq, :k]
-        assert rows.is_contiguous()
+        # dense [nq, k] over the leading elements of the [nq_max, k_max] buffers: the C side reads a plain pointer, and a
+        # [:nq, :k] slice with k < k_max would be strided
+        rows, scores = self.t_rows.view(-1)[:nq * k].view(nq, k), self.t_scores.view(-1)[:nq * k].view(nq, k)
         self.table.recall_topk_dev(queries.data_ptr(), nq, k, rows.data_ptr(), scores.data_ptr())
         return rows, scores
 
     def merge(self, g_rows, g_scores, k):
         G, nq, per = g_rows.shape                                   # list-major, as all-gathered
-        rows, scores = self.m_rows[:nq, :k], self.m_scores[:nq, :k]
+        rows, scores = self.m_rows.view(-1)[:nq * k].view(nq, k), self.m_scores.view(-1)[:nq * k].view(nq, k)
         self._check(self.ctx.L.pg_topk_merge_lists_dev(self.ctx.h, g_rows.data_ptr(), g_scores.data_ptr(), nq, G,
                                                        per, 1, k, rows.data_ptr(), scores.data_ptr()))
         return rows, scores

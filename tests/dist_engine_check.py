@@ -43,8 +43,11 @@ else:
 w = o.Dnn3Weights()
 m = pa.RankModel(ctx, pa.MODEL_DNN3, prec, pa.pack_dnn3(w.w1, w.b1, w.w2, w.b2, w.w3, w.b3, 128))
 ex = pa.Expr(EXPR)
-eng = GpuShardEngine(torch, ctx, t, m, ex, k, R)
-for step, (user0, nq) in enumerate(((77, R), (500, R - 2))):      # two steps: the buffers are reused
+k_max = k
+eng = GpuShardEngine(torch, ctx, t, m, ex, k_max, R)
+# three steps: the buffers are reused; the third with fewer requests AND k < k_max (dense [nq, k] views over the engine's
+# [nq_max, k_max] buffers, fuse_sort's own segment offsets)
+for step, (user0, nq, k) in enumerate(((77, R, k_max), (500, R - 2, k_max), (900, R - 1, k_max - 61))):
     q = o.synth_rows(o.SEED_QUERY, user0, nq, d)
     tq = torch.from_numpy(q).to("cuda:0")
     torch.cuda.synchronize()                            # the upload ran on the default stream
