@@ -1338,6 +1338,109 @@ int pg_item_state_filter(pg_ctx* ctx, pg_cond* c, const pg_features* fs, uint32_
 int pg_boost_scores(pg_ctx* ctx, pg_cond* c, uint32_t filter_all, uint32_t n, const uint8_t* item_in, const void* const* cols,
                     const uint64_t* user_vals, uint32_t user_present, const double* score, double* out_score, uint8_t* out_rule);
 
+/* DiversityAdjustCountFilter on the device: quotas per expression class (csrc/classcut.hip).  The fourth reference
+ * filter of the slot between UniqueFilter and RankService.Rank (service/user_recommend.go:105-137): every AdjustCountConfig gives
+ * its quota not to a recall but to the items for which a govaluate expression over the item's features is true
+ * (filter/diversity_adjust_count_filter.go:75-143), e.g. recall_name == 'u2i' && category == 3.  Classes may overlap; an item an
+ * earlier class took is skipped by later ones.
+ *   In        pg_fanin_merge_dev's outputs as they are, in pg_candidates_trim_dev's argument order and optionality (nq <= 256, cap
+ *             in [1, PG_TRIM_MAX_CAP]), + the compiled set and the pg_features store its columns are bound to by name (NULL only for a set that reads no
+ *             column).  An entry
+ *             is padding if its row is UINT64_MAX or its position is >= d_count[q]; padding may sit anywhere, is dropped and
+ *             never counted.
+ *   Answer    DEFINED bit for bit (doFilter, :75-143; only the order among equal scores is being fixed, as for the trim):
+ *               1. a request's real entries are put in pg_sort_scores_dev's order of d_score: descending, -0.0 equals +0.0,
+ *                  NaN last, ties keep input position (the reference shuffles the first half and sorts unstably, :83-87);
+ *               2. class c (rule c, c < n <= PG_CLASSCUT_MAX_CLASSES) holds, in that order, the entries for which expression c
+ *                  evaluates to true (:92-103: an evaluation error or any other result is "not a member");
+ *               3. classes apply in rule order with acc = 0 (:115-140): limit_c = count_c for PG_TRIM_FIX, max(0, count_c -
+ *                  acc) for PG_TRIM_ACCUMULATE; the window of class c is its first limit_c members (the reference's `i < count`
+ *                  indexes the class's list: a member an earlier class took still uses up a place); its picks are the window's
+ *                  members no earlier class picked, in order; an ACCUMULATE class then adds its picks to acc;
+ *               4. the output is the picks concatenated in class order, then the trim's padding: row UINT64_MAX, score -inf,
+ *                  source 0xFF, fp64 planes 0x7FF8000000000000, mask 0, fp32 planes 0; d_out_count[q] = the number of picks.
+ *             Every carried array is gathered through the same permutation; score and source are unchanged; no value meets
+ *             arithmetic, doubles and floats travel as bits.  Outputs are [nq][out_cap] with out_cap from pg_classcut_out_cap;
+ *             an output is required exactly where its input is given; an output that overlaps its input is PG_ERR_INVALID.
+ *   Language  govaluate at the version the reference pins (go.mod: v3.0.1-0.20171022003610), as a STATICALLY TYPED boolean subset
+ *             compiled to the postfix program of pg_expr_compile_govaluate (parity is unpinned: the library is Go).
+ *             Numbers: everything pg_expr_compile_govaluate accepts — float64 literals, bare and [bracketed] names, + - * / % **,
+ *             unary minus, parentheses, round — with its precedence.  Comparators == != > >= < <= on two numbers, IEEE (NaN ==
+ *             x false, NaN != x true), looser than arithmetic; x in (a, b, …) over 2 .. PG_COND_MAX_LIST constant numbers,
+ *             tested by ==; && looser than the comparators, || looser still, both left-associative; prefix ! on a bool.
+ *             Variables: DECLARED item columns {name, dtype}, bound by name to the store at run time as pg_cond binds them and
+ *             read as float64(value) (only referenced columns are loaded; dictionary-coded strings compare as their codes);
+ *             recall_score = the entry's d_score (module/item.go:229-248); recall_name = the entry's source as a string through
+ *             recall_names[n_recalls] (n_recalls <= PG_CLASSCUT_MAX_RECALLS), legal only as recall_name == 'lit', != 'lit' and
+ *             in ('a', 'b', …) with ' or " quotes and literals of the shape [A-Za-z_][A-Za-z0-9_]* (govaluate tries every string
+ *             as a date first; this shape never is one); a literal that names no recall equals nothing, a source >= n_recalls
+ *             has a name equal to no literal.
+ *   Errors    a candidate whose row is >= the store's rows has every declared column missing (recall_name and recall_score are
+ *             still there); reading one is govaluate's "No parameter found".  An error propagates through arithmetic,
+ *             comparators, in and !; a && b is a's error, false if a is false (b is not looked at), else b; a || b the same with
+ *             true; a final error means "not a member" (:95-98).
+ *   Refused   by name at compile, nothing allocated.  PG_ERR_UNSUPPORTED: the ternary and ??; bitwise operators, =~ and !~; true /
+ *             false; == / != between bools; ordered comparisons on, or arithmetic with, recall_name; any other string literal; a
+ *             top-level expression that is a number; a bool where a number is needed or a number where a bool is (errors on every
+ *             item in govaluate); a one-element in list; every other function, accessors, a chained **; more than
+ *             PG_COND_MAX_EXPR_OPS operations, PG_COND_MAX_EXPR_DEPTH stack slots, PG_COND_MAX_COLS referenced columns or 4096
+ *             in-list values per set; more than PG_CLASSCUT_MAX_CLASSES classes; anything malformed.  PG_ERR_INVALID: no classes
+ *             (the reference indexes configs[len - 1], :115); an ACCUMULATE class directly after an ACCUMULATE class with a larger
+ *             count (the reference panics in its constructor, :56-61); a type other than FIX / ACCUMULATE; a name that is neither
+ *             declared nor a built-in (that includes the reference's per-recall Properties key).  At a call, on the host and with
+ *             the context left usable: an expression that reads recall_name while d_source is absent (PG_ERR_INVALID); cap outside
+ *             [1, PG_TRIM_MAX_CAP] (PG_ERR_UNSUPPORTED).
+ *   Width     pg_classcut_out_cap: a pure host function; out_cap = min(cap, the sum of the FIX counts + the largest ACCUMULATE
+ *             count) — no request keeps more.
+ *   host      pg_classcut_masks_host (n candidates → one byte each, bit c = member of class c) and pg_candidates_classcut_host
+ *             (the whole answer): pure host functions over candidate-aligned arrays as pg_cond_match_host takes them — cols[d] =
+ *             the values of declared column d in its dtype (NULL for columns nothing references), item_in[i] = 0 for a candidate
+ *             outside the store (NULL: all inside); for the whole answer both are [nq * cap].  The statements the kernels are
+ *             tested against; the library falls back to them for nothing.
+ *   Kernels   pg_classcut_masks_dev: ONE launch, one lane per candidate — its row, every referenced column's raw value (all loads
+ *             issued before the first use), then each class's program on an 8-deep register stack with one error bit beside each
+ *             slot; programs and lists are read at wave-uniform addresses; every byte of [nq][cap] is written, padding gets 0.
+ *             pg_candidates_classcut_dev: that launch, the trim's score sort, and one workgroup of PG_TRIM_CHUNK lanes per
+ *             request: classes one after another, each walking the sorted order PG_TRIM_CHUNK positions at a time (a member's
+ *             rank from wave ballots, per-wave counts in LDS and the running count; picked iff in the window and its bit in a
+ *             2 KB LDS bitmap of input positions is clear) up to the chunk in which the rank reaches the limit; then the padding.
+ *             Every output element is written exactly once.
+ *   Stream    the device calls enqueue on the context's stream and do not synchronise (the first device call with a set uploads
+ *             its lists and programs once, synchronously).  Sharing and free: as pg_cond — several contexts of ONE device may
+ *             use a set, also concurrently; pg_classcut_free waits for that device.
+ *   one       pg_candidates_classcut: one request on host arrays against a store (upload, run, download, synchronise), outputs
+ *             [pg_classcut_out_cap(n)]; n = 0 is an empty answer. */
+#define PG_CLASSCUT_MAX_CLASSES 8
+#define PG_CLASSCUT_MAX_RECALLS 32
+typedef struct {
+    const char* expression;   /* AdjustCountConfig.Expression */
+    uint8_t     type;         /* PG_TRIM_FIX | PG_TRIM_ACCUMULATE (AdjustCountConfig.Type "fix" / "accumulator") */
+    uint32_t    count;
+} pg_classcut_rule;
+typedef struct pg_classcut pg_classcut;
+int pg_classcut_compile(const pg_classcut_rule* rules, uint32_t n, const pg_cond_col* cols, uint32_t n_cols, const char* const* recall_names,
+                        uint32_t n_recalls, pg_classcut** out);
+int pg_classcut_free(pg_classcut* c);
+int pg_classcut_num_classes(const pg_classcut* c);
+int pg_classcut_reads_recall_name(const pg_classcut* c);
+int pg_classcut_out_cap(const pg_classcut* c, uint32_t cap, uint32_t* out_cap);
+int pg_classcut_masks_host(const pg_classcut* c, uint32_t n, const uint8_t* item_in, const void* const* cols, const uint8_t* source,
+                           const double* score, uint8_t* out_masks);
+int pg_candidates_classcut_host(const pg_classcut* c, uint32_t nq, uint32_t cap, const uint8_t* item_in, const void* const* cols,
+                                const uint64_t* rows, const double* score, const uint8_t* source, const uint32_t* count,
+                                const double* planes_f64, uint32_t n_f64, const uint32_t* source_mask, const float* planes_f32, uint32_t n_f32,
+                                uint64_t* out_rows, double* out_score, uint8_t* out_source, double* out_planes_f64, uint32_t* out_source_mask,
+                                float* out_planes_f32, uint32_t* out_count);
+int pg_classcut_masks_dev(pg_ctx* ctx, pg_classcut* c, const pg_features* fs, uint32_t nq, uint32_t cap, const uint64_t* d_rows,
+                          const double* d_score, const uint8_t* d_source, const uint32_t* d_count, uint8_t* d_out_masks);
+int pg_candidates_classcut_dev(pg_ctx* ctx, pg_classcut* c, const pg_features* fs, uint32_t nq, uint32_t cap, const uint64_t* d_rows,
+                               const double* d_score, const uint8_t* d_source, const uint32_t* d_count, const double* d_planes_f64,
+                               uint32_t n_f64, const uint32_t* d_source_mask, const float* d_planes_f32, uint32_t n_f32, uint64_t* d_out_rows,
+                               double* d_out_score, uint8_t* d_out_source, double* d_out_planes_f64, uint32_t* d_out_source_mask,
+                               float* d_out_planes_f32, uint32_t* d_out_count);
+int pg_candidates_classcut(pg_ctx* ctx, pg_classcut* c, const pg_features* fs, uint32_t n, const uint64_t* rows, const double* score,
+                           const uint8_t* source, uint64_t* out_rows, double* out_score, uint8_t* out_source, uint32_t* out_count);
+
 /* ---- shard group: one process, several GPUs --------------------------------------------------------
  * BASELINE.json configs[4] / SURVEY.md 8e behind the C ABI (a cgo host cannot join a torch.distributed job): the item
  * table in contiguous row ranges [g*N/G, (g+1)*N/G), one context per shard, model weights replicated.  devices[] may

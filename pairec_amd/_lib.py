@@ -55,6 +55,9 @@ EXPORTS = [
     "pg_cond_compile", "pg_cond_free", "pg_cond_num_rules", "pg_cond_num_user_slots", "pg_cond_user_slot_name",
     "pg_cond_user_slot_is_float", "pg_cond_match_host", "pg_boost_scores_host", "pg_item_state_filter_dev", "pg_boost_scores_dev",
     "pg_item_state_filter", "pg_boost_scores",
+    "pg_classcut_compile", "pg_classcut_free", "pg_classcut_num_classes", "pg_classcut_reads_recall_name", "pg_classcut_out_cap",
+    "pg_classcut_masks_host", "pg_candidates_classcut_host", "pg_classcut_masks_dev", "pg_candidates_classcut_dev",
+    "pg_candidates_classcut",
 ]
 
 
@@ -156,6 +159,10 @@ class PgCondRule(C.Structure):
 
 class PgCondCol(C.Structure):
     _fields_ = [("name", C.c_char_p), ("dtype", C.c_int32)]
+
+
+class PgClasscutRule(C.Structure):
+    _fields_ = [("expression", C.c_char_p), ("type", C.c_uint8), ("count", C.c_uint32)]
 
 
 class PgIndexRefreshParams(C.Structure):
@@ -304,6 +311,16 @@ def load():
         "pg_boost_scores_dev": [vp, vp, vp, u32, u32, u32, vp, vp, vp, vp, vp, vp, vp],
         "pg_item_state_filter": [vp, vp, vp, u32, vp, vp, vp, vp, u32, vp, vp, vp, vp],
         "pg_boost_scores": [vp, vp, u32, u32, vp, P(vp), vp, u32, vp, vp, vp],
+        "pg_classcut_compile": [P(PgClasscutRule), u32, P(PgCondCol), u32, P(C.c_char_p), u32, P(vp)],
+        "pg_classcut_free": [vp],
+        "pg_classcut_num_classes": [vp],
+        "pg_classcut_reads_recall_name": [vp],
+        "pg_classcut_out_cap": [vp, u32, P(C.c_uint32)],
+        "pg_classcut_masks_host": [vp, u32, vp, P(vp), vp, vp, vp],
+        "pg_candidates_classcut_host": [vp, u32, u32, vp, P(vp), vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp],
+        "pg_classcut_masks_dev": [vp, vp, vp, u32, u32, vp, vp, vp, vp, vp],
+        "pg_candidates_classcut_dev": [vp, vp, vp, u32, u32, vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp],
+        "pg_candidates_classcut": [vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp],
         "pg_index_refresh": [vp, vp, P(PgIndexRefreshParams)],
         "pg_index_refresh_stats": [vp, P(PgIndexRefreshStats)],
         "pg_index_screen_probe": [vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, vp, vp],

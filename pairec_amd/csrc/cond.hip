@@ -29,12 +29,14 @@
 // Kernels: one lane per candidate.  The lane loads its row, then every referenced column's value (raw bits, <= 16 loads issued
 // before the first use), then walks the terms, which travel as a by-value kernel argument; in lists and expression programs lie
 // in a small device table uploaded once per compiled set and are read with wave-uniform addresses.  The expression walk keeps
-// an 8-deep stack in registers (constant indices only: the top is always slot 0).
+// an 8-deep stack in registers (constant indices only: the top is always slot 0).  The candidate's loads, the pick of a column's
+// value and its reading as float64 are cond_eval.hpp's, shared with classcut.hip.
 //   item_state_filter_kernel   one workgroup per request walks cap in chunks of 1 024: ballot + mbcnt within a wave, per-wave
 //                              counts in LDS (two sets: a wave one chunk ahead writes the other), every lane adds up the counts
 //                              itself, so one barrier per chunk; kept entries move to the front with everything carried.
 //   boost_scores_kernel        256 lanes per workgroup, grid (cap / 256, nq).
 #include "pipeline.hpp"
+#include "cond_eval.hpp"
 #include "expr_prog.hpp"
 
 #include <algorithm>
@@ -45,10 +47,10 @@
 namespace pg {
 namespace {
 
-constexpr uint32_t kCondMaxRules = 8, kCondMaxTerms = 8, kCondMaxCols = 16, kCondMaxSlots = 8, kCondMaxList = 64;
+constexpr uint32_t kCondMaxRules = 8, kCondMaxTerms = 8, kCondMaxSlots = 8, kCondMaxList = 64;      // (kCondMaxCols: cond_eval.hpp)
 constexpr uint32_t kCondMaxExprOps = 64, kCondMaxExprDepth = 8;
 constexpr uint32_t kCondChunk = 1024, kCondWaves = kCondChunk / kWave;
-static_assert(kCondMaxRules == PG_COND_MAX_RULES && kCondMaxTerms == PG_COND_MAX_TERMS && kCondMaxCols == PG_COND_MAX_COLS &&
+static_assert(kCondMaxRules == PG_COND_MAX_RULES && kCondMaxTerms == PG_COND_MAX_TERMS &&
                   kCondMaxSlots == PG_COND_MAX_SLOTS && kCondMaxList == PG_COND_MAX_LIST && kCondMaxExprOps == PG_COND_MAX_EXPR_OPS &&
                   kCondMaxExprDepth == PG_COND_MAX_EXPR_DEPTH,
               "include/pairec_gpu.h repeats these");
@@ -62,7 +64,6 @@ struct CondTerm {                                 // 24 bytes
     uint32_t pad;
 };
 struct CondRule { uint8_t term_off, n_terms; uint16_t prog_off, prog_n, pad; };
-struct CondCol { const void* base; int32_t dtype; int32_t pad; };
 struct CondProgram {                              // what both kernels and the host statement walk
     CondCol cols[kCondMaxCols];                   // the referenced columns (host statement: base = the caller's candidate-aligned array)
     CondTerm terms[kCondMaxRules * kCondMaxTerms];
@@ -73,54 +74,16 @@ struct CondProgram {                              // what both kernels and the h
     uint64_t store_rows;
 };
 
-// the candidate as the evaluator sees it: raw bits of every referenced column (meaningful iff item_in), the request's user slots
-struct CondItem {
-    unsigned long long raw[kCondMaxCols];
-    bool item_in;
-};
+// the request's user slots (the candidate itself: CondItem, cond_eval.hpp)
 struct CondUser {
     const unsigned long long* vals;               // [kCondMaxSlots] bits: int64 or fp64 by the slot's type
     uint32_t present;
 };
 
-// r[k] for a wave-uniform k as a chain of selects over constant indices: the values stay in registers.  (Left to itself the
-// optimiser folds the chain back into one indexed read, which puts the array in scratch; the empty asm keeps the links apart.)
-template <int N>
-__host__ __device__ __forceinline__ unsigned long long cond_pick(const unsigned long long (&r)[N], uint32_t k) {
-    unsigned long long v = r[0];
-#pragma unroll
-    for (int j = 1; j < N; ++j) {
-        v = k == (uint32_t)j ? r[j] : v;
-#if defined(__HIP_DEVICE_COMPILE__)
-        asm volatile("" : "+v"(v));
-#endif
-    }
-    return v;
-}
-__host__ __device__ __forceinline__ double cond_bits_f64(unsigned long long b) {
-    double d;
-    memcpy(&d, &b, 8);
-    return d;
-}
 __host__ __device__ __forceinline__ long long cond_col_i64(const CondProgram& p, const CondItem& it, uint32_t k) {
     const unsigned long long b = cond_pick(it.raw, k);
     return p.cols[k].dtype == PG_F_I32 ? (long long)(int32_t)(uint32_t)b : (long long)b;          // (integer columns: the compiler checked)
 }
-__host__ __device__ __forceinline__ double cond_col_f64(const CondProgram& p, const CondItem& it, uint32_t k) {
-    const unsigned long long b = cond_pick(it.raw, k);
-    switch (p.cols[k].dtype) {
-        case PG_F_I32: return (double)(int32_t)(uint32_t)b;
-        case PG_F_I64: return (double)(long long)b;
-        case PG_F_F32: {
-            const uint32_t w = (uint32_t)b;
-            float f;
-            memcpy(&f, &w, 4);
-            return (double)f;
-        }
-        default: return cond_bits_f64(b);
-    }
-}
-
 // one operator that is not a bool (see the file header for where every answer comes from)
 __host__ __device__ __forceinline__ bool cond_term(const CondProgram& p, const CondTerm& t, const CondItem& it, const CondUser& u) {
     const bool left_in = t.user_left ? ((u.present >> t.left) & 1u) != 0 : it.item_in;
@@ -243,21 +206,6 @@ __host__ __device__ __forceinline__ uint32_t cond_boost(const CondProgram& p, bo
 }
 
 // ---- kernels ---------------------------------------------------------------------------------------------------------------
-// the referenced columns of `row`, every load issued before anything uses one
-__device__ __forceinline__ void cond_load(const CondProgram& p, unsigned long long row, CondItem* it) {
-    it->item_in = row < p.store_rows;
-#pragma unroll
-    for (uint32_t k = 0; k < kCondMaxCols; ++k) {
-        unsigned long long b = 0;
-        if (k < p.n_used && it->item_in) {
-            const int dt = p.cols[k].dtype;
-            if (dt == PG_F_I32 || dt == PG_F_F32) b = ((const uint32_t*)p.cols[k].base)[row];
-            else b = ((const unsigned long long*)p.cols[k].base)[row];
-        }
-        it->raw[k] = b;
-    }
-}
-
 struct FilterArgs {
     CandIn in;
     CandOut out;                                 // (out_cap = cap: the kept entries move to the front of their own list)
@@ -575,20 +523,6 @@ void cond_program(const pg_cond* c, const void* const* declared_base, const long
     p->store_rows = store_rows;
 }
 
-// host statement: the candidate's values from candidate-aligned arrays
-void cond_host_item(const pg_cond* c, const void* const* cols, const uint8_t* item_in, uint32_t i, CondItem* it) {
-    it->item_in = item_in ? item_in[i] != 0 : true;
-    for (uint32_t k = 0; k < kCondMaxCols; ++k) {
-        unsigned long long b = 0;
-        if (k < c->used.size() && it->item_in) {
-            const int d = c->used[k], dt = c->col_dtypes[(size_t)d];
-            if (dt == PG_F_I32 || dt == PG_F_F32) b = ((const uint32_t*)cols[d])[i];
-            else b = ((const unsigned long long*)cols[d])[i];
-        }
-        it->raw[k] = b;
-    }
-}
-
 int cond_host_check(const pg_cond* c, const void* const* cols, const uint64_t* user_vals, const char* who) {
     for (int d : c->used)
         if (!cols || !cols[d]) {
@@ -604,22 +538,9 @@ int cond_host_check(const pg_cond* c, const void* const* cols, const uint64_t* u
 
 // binds the set to a store by name and makes sure its table is on the context's device; caller holds ctx->mu
 int cond_bind_locked(pg_ctx* ctx, pg_cond* c, const pg_features* fs, const char* who, CondProgram* p) {
-    std::vector<const void*> declared(c->col_names.size(), nullptr);
-    for (int d : c->used) {
-        const pg_features::Column* col = nullptr;
-        for (const auto& x : fs->cols)
-            if (x.name == c->col_names[(size_t)d]) { col = &x; break; }
-        if (!col || !col->d) {
-            set_error("%s: column \"%s\" is not a column of the feature store", who, c->col_names[(size_t)d].c_str());
-            return PG_ERR_INVALID;
-        }
-        if (col->dtype != c->col_dtypes[(size_t)d]) {
-            set_error("%s: column \"%s\" has dtype %d in the feature store, the set was compiled for dtype %d", who, col->name.c_str(), col->dtype,
-                      c->col_dtypes[(size_t)d]);
-            return PG_ERR_INVALID;
-        }
-        declared[(size_t)d] = col->d;
-    }
+    std::vector<const void*> declared;
+    int rc;
+    if ((rc = cond_resolve_columns(fs, c->col_names, c->col_dtypes, c->used, who, &declared))) return rc;
     std::lock_guard<std::mutex> table_guard(c->table_mu);
     if (c->device >= 0 && c->device != ctx->device) {
         set_error("%s: the set's table lives on device %d, the context on device %d", who, c->device, ctx->device);
@@ -644,22 +565,6 @@ int cond_bind_locked(pg_ctx* ctx, pg_cond* c, const pg_features* fs, const char*
     }
     cond_program(c, declared.data(), (const long long*)c->d_table, (const Instr*)((const char*)c->d_table + c->progs_off), fs->rows, p);
     return PG_OK;
-}
-
-int cond_check_shape(uint32_t nq, uint32_t cap, const char* who) {
-    PG_REQUIRE(nq >= 1 && nq <= (uint32_t)kMaxQueries, "%s: nq=%u must be in [1,%d]", who, nq, kMaxQueries);
-    if (cap < 1 || cap > kCandMaxCap) {
-        set_error("%s: cap=%u unsupported (1..%u)", who, cap, kCandMaxCap);
-        return PG_ERR_UNSUPPORTED;
-    }
-    return PG_OK;
-}
-
-// [a, a + an) and [b, b + bn) share a byte
-inline bool cond_overlap(const void* a, size_t an, const void* b, size_t bn) {
-    if (!a || !b) return false;
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + bn && y < x + an;
 }
 
 int item_state_filter_locked(pg_ctx* ctx, pg_cond* c, const pg_features* fs, const CandIn& in, const CandOut& out, const uint64_t* d_user_vals,
@@ -739,7 +644,7 @@ int pg_cond_match_host(const pg_cond* c, uint32_t rule, uint32_t n, const uint8_
     const pg::CondUser u{reinterpret_cast<const unsigned long long*>(user_vals), user_present};
     for (uint32_t i = 0; i < n; ++i) {
         pg::CondItem it;
-        pg::cond_host_item(c, cols, item_in, i, &it);
+        pg::cond_host_item(c->used, c->col_dtypes, cols, item_in, i, &it);
         out_match[i] = pg::cond_rule(p, rule, it, u) ? 1 : 0;
     }
     return PG_OK;
@@ -757,7 +662,7 @@ int pg_boost_scores_host(const pg_cond* c, uint32_t filter_all, uint32_t n, cons
     const pg::CondUser u{reinterpret_cast<const unsigned long long*>(user_vals), user_present};
     for (uint32_t i = 0; i < n; ++i) {
         pg::CondItem it;
-        pg::cond_host_item(c, cols, item_in, i, &it);
+        pg::cond_host_item(c->used, c->col_dtypes, cols, item_in, i, &it);
         double s = score[i];
         const uint32_t last = pg::cond_boost(p, filter_all != 0, it, u, &s);
         memcpy(&out_score[i], &s, 8);                    // (moves only: an untouched score keeps its bits)

@@ -15,7 +15,14 @@ enum OpCode : uint32_t { OP_CONST = 0, OP_VAR, OP_ADD, OP_SUB, OP_MUL, OP_DIV, O
                          OP_NEG,    // antlr subset: unary minus
                          OP_FMOD,   // govaluate subset: `%` = math.Mod on float64 (no panic: NaN for a zero divisor)
                          OP_ROUND,  // govaluate subset: round(x) = math.Round (unary)
-                         OP_ROUND2 };  // govaluate subset: round(x, n) = math.Trunc(x * Pow(10, n)) / Pow(10, n) (binary)
+                         OP_ROUND2,  // govaluate subset: round(x, n) = math.Trunc(x * Pow(10, n)) / Pow(10, n) (binary)
+                         // govaluate's boolean subset (classcut.hip only: no other front end emits them, no other evaluator
+                         // meets them).  A bool travels on the value stack as 1.0 / 0.0, an error as a bit beside its slot.
+                         OP_EQ, OP_NE, OP_GT, OP_GE, OP_LT, OP_LE,   // two numbers → bool, IEEE
+                         OP_IN,     // unary: the number == one of the constants [arg & 0xFFFF, + arg >> 16) of the set's list table
+                         OP_SRC,    // push: bit `source` of the mask `arg` (recall_name ==, in; a source >= 32 has no bit)
+                         OP_AND, OP_OR,   // two bools, govaluate's short circuit: the left's error, else its verdict, else the right
+                         OP_NOT };  // unary on a bool
 
 struct Instr {
     uint32_t op;

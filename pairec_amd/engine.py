@@ -339,6 +339,104 @@ def cond_match_host(cond: Cond, cols=None, item_in=None, user=None, rule: int = 
     return cond.match_host(cols, item_in, user, rule, n)
 
 
+class Classcut:
+    """A compiled DiversityAdjustCountFilter (pg_classcut_compile): 1..8 classes, each a govaluate boolean expression over declared
+    item columns, recall_score and recall_name with a quota.  rules: [(expression, TRIM_FIX | TRIM_ACCUMULATE, count)]; cols:
+    [(name, F_I32 | F_I64 | F_F32 | F_F64)]; recall_names: the recalls in fan-in source order.  A host object until a device
+    entry first uses it."""
+
+    def __init__(self, rules, cols=(), recall_names=()):
+        self.L = _lib.load()
+        self.cols = [(str(n), int(d)) for n, d in cols]
+        self.recall_names = [str(n) for n in recall_names]
+        keep = [str(e).encode("utf-8") for e, _, _ in rules]
+        arr = (_lib.PgClasscutRule * max(len(rules), 1))()
+        for i, (_, type_, count) in enumerate(rules):
+            arr[i] = _lib.PgClasscutRule(keep[i], int(type_), int(count))
+        ca = (_lib.PgCondCol * max(len(self.cols), 1))()
+        for i, (n, d) in enumerate(self.cols):
+            keep.append(n.encode("utf-8"))
+            ca[i].name, ca[i].dtype = keep[-1], d
+        names = (C.c_char_p * max(len(self.recall_names), 1))(*[n.encode("utf-8") for n in self.recall_names])
+        h = C.c_void_p()
+        _lib.check(self.L.pg_classcut_compile(arr, len(rules), ca, len(self.cols), names, len(self.recall_names), C.byref(h)))
+        del keep
+        self.h = h
+        self.n_classes = self.L.pg_classcut_num_classes(h)
+        self.reads_recall_name = bool(self.L.pg_classcut_reads_recall_name(h))
+
+    def free(self):
+        if self.h:
+            self.L.pg_classcut_free(self.h)
+            self.h = None
+
+    def out_cap(self, cap: int) -> int:
+        """pg_classcut_out_cap: min(cap, the FIX counts + the largest ACCUMULATE count).  A host function."""
+        out = C.c_uint32()
+        _lib.check(self.L.pg_classcut_out_cap(self.h, int(cap), C.byref(out)))
+        return out.value
+
+    def _host_cols(self, cols, n):
+        """{column name: candidate-aligned values} → (the arrays, kept alive by the caller, and the pointer table)"""
+        arrs = []
+        ptrs = (C.c_void_p * max(len(self.cols), 1))()
+        for i, (name, dt) in enumerate(self.cols):
+            if cols is not None and name in cols:
+                a = np.ascontiguousarray(cols[name], dtype=_F_NP[dt]).reshape(-1)
+                if a.shape[0] != n:
+                    raise ValueError("Classcut: column %r holds %d values for %d candidates" % (name, a.shape[0], n))
+                arrs.append(a)
+                ptrs[i] = a.ctypes.data
+        return arrs, ptrs
+
+    def masks_host(self, score, cols=None, item_in=None, source=None) -> np.ndarray:
+        """pg_classcut_masks_host: n candidates as candidate-aligned arrays (score [n], {column name: [n]}, item_in [n]: 0 = the
+        row is outside the store, source [n]) → [n] uint8, bit c = member of class c."""
+        sc = np.ascontiguousarray(score, dtype=np.float64).reshape(-1)
+        n = sc.shape[0]
+        arrs, ptrs = self._host_cols(cols, n)
+        inn = None if item_in is None else np.ascontiguousarray(item_in, dtype=np.uint8).reshape(-1)
+        src = None if source is None else np.ascontiguousarray(source, dtype=np.uint8).reshape(-1)
+        out = np.zeros(n, dtype=np.uint8)
+        _lib.check(self.L.pg_classcut_masks_host(self.h, n, None if inn is None else _ptr(inn), ptrs, None if src is None else _ptr(src),
+                                                 _ptr(sc), _ptr(out)))
+        del arrs
+        return out
+
+
+def classcut_compile(rules, cols=(), recall_names=()) -> Classcut:
+    """pg_classcut_compile (see Classcut)."""
+    return Classcut(rules, cols, recall_names)
+
+
+def classcut_out_cap(cc: Classcut, cap: int) -> int:
+    """pg_classcut_out_cap (see Classcut.out_cap): a host function, no context, no device."""
+    return cc.out_cap(cap)
+
+
+def classcut_masks_host(cc: Classcut, score, cols=None, item_in=None, source=None) -> np.ndarray:
+    """pg_classcut_masks_host (see Classcut.masks_host): a host function, no context, no device."""
+    return cc.masks_host(score, cols, item_in, source)
+
+
+def candidates_classcut_host(cc: Classcut, rows, score, source=None, count=None, planes_f64=None, source_mask=None, planes_f32=None, cols=None,
+                             item_in=None):
+    """pg_candidates_classcut_host: DiversityAdjustCountFilter on host arrays by the library's host statement (no context, no
+    device); the arrays and the result of Context.candidates_classcut, the columns as candidate-aligned values {name: [nq][cap]}
+    and item_in [nq][cap] in place of the store."""
+    nq, cap, ins, outs, n64, n32 = _cand_arrays("candidates_classcut_host", cc.out_cap, rows, score, source, count, planes_f64, source_mask,
+                                                planes_f32)
+    arrs, ptrs = cc._host_cols(cols, nq * cap)
+    inn = None if item_in is None else np.ascontiguousarray(item_in, dtype=np.uint8).reshape(-1)
+    if inn is not None and inn.shape[0] != nq * cap:
+        raise ValueError("candidates_classcut_host: item_in is [nq][cap]")
+    v = lambda a: None if a is None else _ptr(a)                                     # noqa: E731
+    _lib.check(_lib.load().pg_candidates_classcut_host(cc.h, nq, cap, v(inn), ptrs, v(ins[0]), v(ins[1]), v(ins[2]), v(ins[3]), v(ins[4]), n64,
+                                                       v(ins[5]), v(ins[6]), n32, *[v(a) for a in outs]))
+    del arrs
+    return tuple(outs)
+
+
 def expr_compile_govaluate(source: str) -> "Expr":
     """pg_expr_compile_govaluate: the arithmetic subset of govaluate that BoostScoreSort expressions use."""
     return Expr(source, govaluate=True)
@@ -734,6 +832,55 @@ class Context:
                                           _ptr(vals), present, _ptr(sc), _ptr(out), _ptr(rule)))
         del arrs
         return out, rule
+
+    # ---- DiversityAdjustCountFilter: quotas per expression class ---------------------------------------
+    def classcut_masks_dev(self, cc, fs, nq: int, cap: int, d_rows: int, d_score: int, d_source: int, d_count: int, d_out_masks: int) -> None:
+        """pg_classcut_masks_dev: device addresses (0 = absent) → [nq][cap] uint8, bit c = member of class c.  One launch on the
+        context's stream: synchronize() before reading."""
+        v = lambda p: C.c_void_p(p or None)                                          # noqa: E731
+        _lib.check(self.L.pg_classcut_masks_dev(self.h, cc.h, getattr(fs, "h", fs), nq, cap, v(d_rows), v(d_score), v(d_source), v(d_count),
+                                                v(d_out_masks)))
+
+    def classcut_masks(self, cc, fs, rows, score, source=None, count=None) -> np.ndarray:
+        """the class masks of host arrays rows / score / source [nq][cap], count [nq] (pg_classcut_masks_dev) → [nq][cap] uint8"""
+        nq, cap, ins, _, _, _ = _cand_arrays("classcut_masks", lambda cap: cap, rows, score, source, count, None, None, None)
+        out = np.empty((nq, cap), np.uint8)
+        return self._cand_run(ins[:4], [out], lambda d_in, d_out: self.classcut_masks_dev(cc, fs, nq, cap, d_in[0], d_in[1], d_in[2], d_in[3],
+                                                                                          d_out[0]))[0]
+
+    def candidates_classcut_dev(self, cc, fs, nq: int, cap: int, d_rows: int, d_score: int, d_source: int, d_count: int, d_planes_f64: int,
+                                n_f64: int, d_source_mask: int, d_planes_f32: int, n_f32: int, d_out_rows: int, d_out_score: int,
+                                d_out_source: int, d_out_planes_f64: int, d_out_source_mask: int, d_out_planes_f32: int,
+                                d_out_count: int) -> None:
+        """pg_candidates_classcut_dev: cc a Classcut, fs the store its columns are bound to, everything else device addresses as
+        candidates_trim_dev (0 = absent; an output is required exactly where its input is given), outputs [nq][cc.out_cap(cap)].
+        Enqueued on the context's stream: synchronize() before reading."""
+        v = lambda p: C.c_void_p(p or None)                                          # noqa: E731
+        _lib.check(self.L.pg_candidates_classcut_dev(self.h, cc.h, getattr(fs, "h", fs), nq, cap, v(d_rows), v(d_score), v(d_source),
+                                                     v(d_count), v(d_planes_f64), n_f64, v(d_source_mask), v(d_planes_f32), n_f32,
+                                                     v(d_out_rows), v(d_out_score), v(d_out_source), v(d_out_planes_f64),
+                                                     v(d_out_source_mask), v(d_out_planes_f32), v(d_out_count)))
+
+    def candidates_classcut(self, cc, fs, rows, score, source=None, count=None, planes_f64=None, source_mask=None, planes_f32=None):
+        """DiversityAdjustCountFilter on host arrays (pg_candidates_classcut_dev): the arrays of candidates_trim → (rows, score,
+        source, planes_f64, source_mask, planes_f32, count), [nq][out_cap] each, None where the input was None."""
+        nq, cap, ins, outs, n64, n32 = _cand_arrays("candidates_classcut", cc.out_cap, rows, score, source, count, planes_f64, source_mask,
+                                                    planes_f32)
+        return self._cand_run(ins, outs, lambda d_in, d_out: self.candidates_classcut_dev(
+            cc, fs, nq, cap, d_in[0], d_in[1], d_in[2], d_in[3], d_in[4], n64, d_in[5], d_in[6], n32, *d_out))
+
+    def candidates_classcut_one(self, cc, fs, rows, score, source=None):
+        """pg_candidates_classcut: one request on host arrays (what the host mirror calls) → (rows, score, source | None, count),
+        arrays of cc.out_cap(n) entries"""
+        r = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1)
+        sc = np.ascontiguousarray(score, dtype=np.float64).reshape(-1)
+        src = None if source is None else np.ascontiguousarray(source, dtype=np.uint8).reshape(-1)
+        w = cc.out_cap(r.shape[0]) if r.shape[0] else 0
+        o_r, o_s, o_src, cnt = np.empty(w, np.uint64), np.empty(w, np.float64), None if src is None else np.empty(w, np.uint8), C.c_uint32()
+        _lib.check(self.L.pg_candidates_classcut(self.h, cc.h, getattr(fs, "h", fs), r.shape[0], _ptr(r), _ptr(sc),
+                                                 None if src is None else _ptr(src), _ptr(o_r), _ptr(o_s),
+                                                 None if src is None else _ptr(o_src), C.byref(cnt)))
+        return o_r, o_s, o_src, cnt.value
 
     # ---- sort / expr (context-level ops) ----------------------------------------------------
     def sort_scores(self, scores: np.ndarray, seg_offsets: Optional[Sequence[int]] = None,

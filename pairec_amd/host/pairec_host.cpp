@@ -268,6 +268,59 @@ static std::vector<std::string> str_list(const json::Value& v) {
             if (e.type == json::Value::String) out.push_back(e.str);
     return out;
 }
+// the names a DiversityAdjustCountFilter expression reads besides recall_name / recall_score, appended to *names once each: bare
+// and [bracketed] identifiers that are no keyword, no function call and no accessor (what the compile refuses it names itself)
+static void ClasscutNames(const std::string& e, std::vector<std::string>* names) {
+    auto alpha = [](char c) { return (c >= 'a' && c <= 'z') || (c >= 'A' && c <= 'Z') || c == '_'; };
+    auto digit = [](char c) { return c >= '0' && c <= '9'; };
+    auto add = [&](const std::string& n) {
+        if (n.empty() || n == "recall_name" || n == "recall_score" || n.find('.') != std::string::npos) return;
+        if (std::find(names->begin(), names->end(), n) == names->end()) names->push_back(n);
+    };
+    for (size_t i = 0; i < e.size();) {
+        const char c = e[i];
+        if (c == '\'' || c == '"') {
+            const size_t close = e.find(c, i + 1);
+            i = close == std::string::npos ? e.size() : close + 1;
+        } else if (c == '[') {
+            const size_t close = e.find(']', i + 1);
+            if (close == std::string::npos) return;
+            add(e.substr(i + 1, close - i - 1));
+            i = close + 1;
+        } else if (digit(c) || c == '.') {
+            while (i < e.size() && (digit(e[i]) || alpha(e[i]) || e[i] == '.')) ++i;
+        } else if (alpha(c)) {
+            size_t j = i;
+            while (j < e.size() && (alpha(e[j]) || digit(e[j]) || e[j] == '.')) ++j;
+            const std::string n = e.substr(i, j - i);
+            size_t k = j;
+            while (k < e.size() && (e[k] == ' ' || e[k] == '\t' || e[k] == '\n' || e[k] == '\r')) ++k;
+            const bool keyword = n == "in" || n == "IN" || n == "true" || n == "false", call = k < e.size() && e[k] == '(';
+            if (!keyword && !call) add(n);
+            i = j;
+        } else {
+            ++i;
+        }
+    }
+}
+
+// pg_classcut_compile of a parsed DiversityAdjustCountFilter: its columns declared as the engine holds them (int32)
+static bool CompileClasscut(const GpuFilterConfig& c, pg_classcut** out, std::string* why) {
+    std::vector<pg_classcut_rule> rules(c.Classes.size());
+    for (size_t i = 0; i < rules.size(); ++i) rules[i] = pg_classcut_rule{c.Classes[i].Expression.c_str(), c.Classes[i].Type, c.Classes[i].Count};
+    std::vector<pg_cond_col> cols(c.ClassColumns.size());
+    for (size_t i = 0; i < cols.size(); ++i) cols[i] = pg_cond_col{c.ClassColumns[i].c_str(), PG_F_I32};
+    std::vector<const char*> recalls(c.ClassRecalls.size());
+    for (size_t i = 0; i < recalls.size(); ++i) recalls[i] = c.ClassRecalls[i].c_str();
+    if (recalls.size() > PG_CLASSCUT_MAX_RECALLS) recalls.resize(PG_CLASSCUT_MAX_RECALLS);      // (later recalls have names equal to no literal)
+    if (pg_classcut_compile(rules.data(), (uint32_t)rules.size(), cols.data(), (uint32_t)cols.size(), recalls.data(), (uint32_t)recalls.size(), out) == PG_OK)
+        return true;
+    *why = pg_last_error();
+    const size_t colon = why->find(": ");                                 // (the entry point's name says nothing here)
+    if (colon != std::string::npos) *why = why->substr(colon + 2);
+    return false;
+}
+
 bool RecommendConfig::Parse(const std::string& text, RecommendConfig* out, std::string* err) {
     json::Value root;
     if (!json::Parser(text).Parse(&root, err)) return false;
@@ -499,6 +552,30 @@ bool RecommendConfig::Parse(const std::string& text, RecommendConfig* out, std::
                 const size_t colon = why.find(": ");                     // (the entry point's name says nothing here)
                 if (colon != std::string::npos) why = why.substr(colon + 2);
                 why = c.FilterType + ": " + why;
+            }
+        }
+        else if (c.IsClasscut()) {
+            // NewDiversityAdjustCountFilter (diversity_adjust_count_filter.go:44-66): what pg_classcut_compile refuses is refused here, by name
+            for (const auto& r : out->GpuRecalls) c.ClassRecalls.push_back(r.Name);
+            const auto& confs = fc.at("AdjustCountConfs").arr;
+            for (size_t i = 0; why.empty() && i < confs.size(); ++i) {
+                GpuFilterConfig::ClassConf cl;
+                cl.Expression = confs[i].s("Expression");
+                const double count = confs[i].d("Count");
+                const std::string type = confs[i].s("Type");
+                if (confs[i].at("Count").type != json::Value::Number || count < 0 || count > 4294967295.0 || count != std::floor(count))
+                    why = "Count of class " + std::to_string(i) + " is not a count";
+                else if (type != "fix" && type != "accumulator")
+                    why = "Type \"" + type + "\" of class " + std::to_string(i) + " (the reference serves fix and accumulator)";
+                cl.Count = why.empty() ? (uint32_t)count : 0u;
+                cl.Type = type == "fix" ? PG_TRIM_FIX : PG_TRIM_ACCUMULATE;
+                ClasscutNames(cl.Expression, &c.ClassColumns);
+                c.Classes.push_back(cl);
+            }
+            if (why.empty()) {
+                pg_classcut* set = nullptr;
+                if (!CompileClasscut(c, &set, &why)) why = c.FilterType + ": " + why;
+                else pg_classcut_free(set);
             }
         }
         else if (c.FilterType != "ItemStateFilter") why = "unknown FilterType \"" + c.FilterType + "\" (the device serves ItemStateFilter)";
@@ -1897,6 +1974,50 @@ bool blend_filter(Engine* self, const recconf::GpuFilterConfig& conf, std::vecto
     return true;
 }
 
+// DiversityAdjustCountFilter (filter/diversity_adjust_count_filter.go:75-143) through pg_candidates_classcut: an item becomes its table
+// row (one the table does not know: a row of its own behind the store, every column missing), Item.Score and the index of
+// RetrieveId among the engine's recalls; the kept rows come back in class order and name their items.
+bool classcut_filter(Engine* self, const recconf::GpuFilterConfig& conf, std::vector<module::ItemPtr>* items, std::string* err) {
+    const size_t n = items->size();
+    if (n == 0) return true;
+    auto fail = [&](const std::string& what) { if (err) *err = "DiversityAdjustCountFilter " + conf.Name + ": " + what; return false; };
+    if (n > PG_TRIM_MAX_CAP) return fail(std::to_string(n) + " items (the device serves up to " + std::to_string(PG_TRIM_MAX_CAP) + ")");
+    if (!conf.ClassColumns.empty() && !self->feats) return fail("the engine has no feature columns");
+    for (const auto& name : conf.ClassColumns)
+        if (pg_features_column_index(self->feats, name.c_str()) < 0) return fail("\"" + name + "\" is not a feature column");
+    pg_classcut* set = nullptr;
+    std::string why;
+    if (!recconf::CompileClasscut(conf, &set, &why)) return fail(why);
+    uint32_t out_cap = 0, count = 0;
+    pg_classcut_out_cap(set, (uint32_t)n, &out_cap);
+    const size_t width = std::max<size_t>(out_cap, 1);                      // (every count 0: nothing is kept, the outputs still exist)
+    std::vector<uint64_t> rows(n), out_rows(width);
+    std::vector<double> score(n), out_score(width);
+    std::vector<uint8_t> source(n), out_source(width);
+    std::map<uint64_t, size_t> at;
+    for (size_t i = 0; i < n; ++i) {
+        const module::Item& it = *(*items)[i];
+        uint32_t row;
+        rows[i] = self->RowOfId(it.Id, &row) ? row : self->table_rows + i;
+        if (!at.emplace(rows[i], i).second) {
+            pg_classcut_free(set);
+            return fail("item " + it.Id + " comes twice (the filter runs behind UniqueFilter)");
+        }
+        score[i] = it.Score;
+        const auto r = std::find(conf.ClassRecalls.begin(), conf.ClassRecalls.end(), it.RetrieveId);
+        source[i] = r == conf.ClassRecalls.end() || r - conf.ClassRecalls.begin() >= 0xFF ? 0xFF : (uint8_t)(r - conf.ClassRecalls.begin());
+    }
+    const bool ok = pg_candidates_classcut(self->ctx, set, self->feats, (uint32_t)n, rows.data(), score.data(), source.data(), out_rows.data(),
+                                           out_score.data(), out_source.data(), &count) == PG_OK;
+    why = ok ? std::string() : pg_err("pg_candidates_classcut");
+    pg_classcut_free(set);
+    if (!ok) return fail(why);
+    std::vector<module::ItemPtr> kept(std::min(count, out_cap));
+    for (size_t k = 0; k < kept.size(); ++k) kept[k] = (*items)[at.at(out_rows[k])];
+    items->swap(kept);
+    return true;
+}
+
 struct GpuSSDSort : sort::ISort {                        // sort/ssd_sort.go:110-343 (embedding table = item table)
     Engine* e;
     recconf::SSDSortConfig conf;
@@ -2523,6 +2644,10 @@ bool Engine::ItemStateFilter(const recconf::GpuFilterConfig& conf, const module:
 
 bool Engine::BlendFilter(const recconf::GpuFilterConfig& conf, std::vector<module::ItemPtr>* items, std::string* err) {
     return blend_filter(this, conf, items, err);
+}
+
+bool Engine::ClasscutFilter(const recconf::GpuFilterConfig& conf, std::vector<module::ItemPtr>* items, std::string* err) {
+    return classcut_filter(this, conf, items, err);
 }
 
 bool Engine::Recommend(const std::string& uid, int size, const std::string& scene,

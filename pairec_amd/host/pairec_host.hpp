@@ -156,6 +156,7 @@ struct SortConfig {                        // recconf.go:820-838: Name, SortType
 // pairec_gpu.Filters: FilterType "ItemStateFilter" (filter/item_state_filter.go:47-57) over the engine's feature columns
 // … "SnakeFilter" (filter/snake_filter.go:118-241: AdjustCountConfs[{RecallName, Weight}], RetainNum, SnakeType) and
 // "CompletelyFairCountFilter" (filter/completely_fair_count_filter.go:18-94: RetainNum) through pg_candidates_blend_dev
+// … and "DiversityAdjustCountFilter" (filter/diversity_adjust_count_filter.go:44-143) through pg_candidates_classcut
 struct GpuFilterConfig {
     std::string Name, FilterType, FeatureStore;
     json::Value FilterParams;              // [FilterParamConfig] (recconf.go:884-891)
@@ -164,6 +165,13 @@ struct GpuFilterConfig {
     pg_blend_conf Blend{};
     std::vector<std::string> BlendSources;
     bool IsBlend() const { return FilterType == "SnakeFilter" || FilterType == "CompletelyFairCountFilter"; }
+    // "DiversityAdjustCountFilter" (filter/diversity_adjust_count_filter.go:25-66: AdjustCountConfs[{Expression, Count, Type}]) through
+    // pg_candidates_classcut: the classes as the device takes them, the names their expressions read besides recall_name /
+    // recall_score (columns of the engine's item_features store, by item row) and the recall names in pairec_gpu.Recalls order
+    struct ClassConf { std::string Expression; uint8_t Type = 0; uint32_t Count = 0; };
+    std::vector<ClassConf> Classes;
+    std::vector<std::string> ClassColumns, ClassRecalls;
+    bool IsClasscut() const { return FilterType == "DiversityAdjustCountFilter"; }
 };
 struct FeatureConfig {                      // recconf.go:256-265
     std::string FeatureType, FeatureName, FeatureSource, FeatureValue, FeatureStore, Normalizer, Expression;
@@ -483,9 +491,10 @@ public:
     std::map<std::string, recconf::GpuFilterConfig> gpu_filters;
     bool ItemStateFilter(const recconf::GpuFilterConfig& conf, const module::User* user, std::vector<module::ItemPtr>* items, std::string* err);
     bool BlendFilter(const recconf::GpuFilterConfig& conf, std::vector<module::ItemPtr>* items, std::string* err);   // SnakeFilter, CompletelyFairCountFilter
+    bool ClasscutFilter(const recconf::GpuFilterConfig& conf, std::vector<module::ItemPtr>* items, std::string* err);   // DiversityAdjustCountFilter
     // one pairec_gpu.Filters entry, whatever its FilterType
     bool RunGpuFilter(const recconf::GpuFilterConfig& conf, const module::User* user, std::vector<module::ItemPtr>* items, std::string* err) {
-        return conf.IsBlend() ? BlendFilter(conf, items, err) : ItemStateFilter(conf, user, items, err);
+        return conf.IsBlend() ? BlendFilter(conf, items, err) : conf.IsClasscut() ? ClasscutFilter(conf, items, err) : ItemStateFilter(conf, user, items, err);
     }
     std::map<std::string, std::vector<int32_t>> user_fields;   // uid → dictionary-encoded user categorical features
     pg_model* fm2t = nullptr;                           // FM + two-tower model: rank algorithm "fm2t", and the vector model of the online recall
