@@ -924,6 +924,71 @@ int pg_candidates_blend_host(const pg_blend_conf* conf, uint32_t nq, uint32_t ca
                              uint8_t* out_source, double* out_planes_f64, uint32_t* out_source_mask, float* out_planes_f32,
                              uint32_t* out_count);
 
+/* PriorityAdjustCountFilterV2 on the device (csrc/trim2.hip): the quota filter of a scene whose recalls overlap
+ * (filter/priority_adjust_count_filter_v2.go:39-103, registered in filter/filter.go:148), in the trim's slot between UniqueFilter
+ * and RankService.Rank (service/user_recommend.go:105-137).  An item that several recalls returned counts for every one of them,
+ * under that recall's score (RecallScores, i.e. the fan-in's per-recall score planes and source mask), until one quota takes it;
+ * it then leaves with that recall's name and score.  pg_candidates_trim_dev treats an item as its first recall's only: on
+ * overlapping recalls that is a different answer.
+ *   In        pg_fanin_merge_dev's outputs as they are, in pg_candidates_trim_dev's argument order and optionality: nq <= 256
+ *             requests of cap in [1, PG_TRIM_MAX_CAP] entries; d_rows, d_score, optional d_source, d_count, d_planes_f64
+ *             [n_f64][nq][cap] (planes 0.. are the per-recall scores by source index), d_source_mask, d_planes_f32; at most
+ *             PG_TRIM_MAX_PLANES planes each.  An entry is padding if its row is UINT64_MAX or its position is >= d_count[q];
+ *             padding may sit anywhere, is dropped and never counted.
+ *   Rules     host values, 1 .. PG_TRIM_MAX_RULES of pg_trim_rule {source, type, count} in AdjustCountConfs order: type
+ *             PG_TRIM_FIX or PG_TRIM_ACCUMULATE, source < PG_TRIM_MAX_SOURCES (the fan-in source index RecallName resolves to).
+ *   Answer    DEFINED bit for bit.  "Score order" is pg_sort_scores_dev's: descending, -0.0 equals +0.0, NaN last, ties keep
+ *             input position (the reference shuffles and sorts unstably, :47-52, and iterates a Go map, :66: only the order
+ *             among equal keys is being fixed).
+ *               1. a real entry e is a duplicate iff a mask is given and popcount(mask[e]) > 1 (the reference's
+ *                  len(RecallScores) > 1, :55); otherwise it is a single.
+ *               2. rule c names source s_c; its list L_c holds the singles with source[e] == s_c, keyed d_score[e] (:58,63), and
+ *                  every duplicate with bit s_c of mask[e] set, keyed planes_f64[s_c][e] — also where source[e] == s_c (:66-71:
+ *                  RecallScores[name] is read for every name; it differs from Item.Score only where the first recall held the
+ *                  id twice, unique_filter.go:40-43).  L_c is in score order of its key.  Without d_source the single legal
+ *                  rule owns every entry: each real entry counts as of source s_0.
+ *                  Singles of sources no rule names, and duplicates no named source holds, are dropped.
+ *               3. rules apply in order with acc = 0 and taken empty: limit_c = count_c for PG_TRIM_FIX, max(0, count_c - acc)
+ *                  for PG_TRIM_ACCUMULATE (:86); the picks are the first limit_c entries of L_c that are not in taken, in
+ *                  order — an entry an earlier rule took does not use up a place (the reference deletes it from the map,
+ *                  :80-83,91-93; pg_candidates_classcut_dev's window differs in this); taken gains the picks; an ACCUMULATE
+ *                  rule adds their number to acc (:95), a FIX rule leaves acc alone.
+ *               4. the output is the picks concatenated in rule order.  A pick carries its row, score = its key in L_c, source
+ *                  = s_c (:68-69) and every plane, mask and fp32 plane unchanged; doubles and floats travel as bits.
+ *                  d_out_count[q] = the picks; behind them padding as the trim's: row UINT64_MAX, score -inf, source 0xFF, fp64
+ *                  planes the quiet NaN 0x7FF8000000000000, mask 0, fp32 planes 0.
+ *             Outputs are [nq][out_cap] (planes [n][nq][out_cap]) with out_cap from pg_trim2_out_cap; an output is required
+ *             exactly where its input is given.  Without a mask every entry is a single and the answer equals
+ *             pg_candidates_trim_dev's on the same rules, bit for bit.
+ *   Refused   on the host, the context left usable (PG_ERR_INVALID): no rules; a source named twice (the reference emits its
+ *             singles twice); PG_TRIM_ANY; a source >= PG_TRIM_MAX_SOURCES; an unknown type; a mask without planes covering every
+ *             named source (n_f64 must exceed every named source); more than one source named without d_source; an output
+ *             missing where its input is given; an output that overlaps its input.  ACCUMULATE counts that decrease are legal
+ *             here: V2 compares (i < count, :88) where v1 slices and panics.  More than PG_TRIM_MAX_RULES rules and cap outside
+ *             [1, PG_TRIM_MAX_CAP] are PG_ERR_UNSUPPORTED.
+ *   Width     pg_trim2_out_cap: a pure host function (no context, no device) that validates the rules as above and returns
+ *             out_cap = min(cap, the sum of the FIX counts + the largest ACCUMULATE count), computed in 64 bits: acc never
+ *             exceeds the largest ACCUMULATE count and a position is picked once.
+ *   Host      pg_candidates_trim2_host: the same answer computed on the host over host arrays (no context, no device) — the
+ *             statement the device path is tested against, and the path of a host that holds the merged list already.
+ *   Kernel    one key array per rule (non-members NaN), one segmented score sort over nq x n_rules segments, then one workgroup
+ *             of PG_TRIM_CHUNK lanes per request: rules one after another, each walking its order PG_TRIM_CHUNK positions at a
+ *             time against a bitmap of taken input positions in LDS (an eligible entry's rank from wave ballots and per-wave
+ *             counts), until its picks reach the limit or the order ends.  Every output element is written exactly once.
+ *   Stream    the sort and the launches on the context's stream, no synchronisation (as pg_candidates_trim_dev).
+ * Not served here: AdjustCountConfig's Expression / Weight (V2 does not read them). */
+int pg_trim2_out_cap(const pg_trim_rule* rules, uint32_t n_rules, uint32_t cap, uint32_t* out_cap);
+int pg_candidates_trim2_dev(pg_ctx* ctx, const pg_trim_rule* rules, uint32_t n_rules, uint32_t nq, uint32_t cap, const uint64_t* d_rows,
+                            const double* d_score, const uint8_t* d_source, const uint32_t* d_count, const double* d_planes_f64,
+                            uint32_t n_f64, const uint32_t* d_source_mask, const float* d_planes_f32, uint32_t n_f32, uint64_t* d_out_rows,
+                            double* d_out_score, uint8_t* d_out_source, double* d_out_planes_f64, uint32_t* d_out_source_mask,
+                            float* d_out_planes_f32, uint32_t* d_out_count);
+int pg_candidates_trim2_host(const pg_trim_rule* rules, uint32_t n_rules, uint32_t nq, uint32_t cap, const uint64_t* rows,
+                             const double* score, const uint8_t* source, const uint32_t* count, const double* planes_f64, uint32_t n_f64,
+                             const uint32_t* source_mask, const float* planes_f32, uint32_t n_f32, uint64_t* out_rows, double* out_score,
+                             uint8_t* out_source, double* out_planes_f64, uint32_t* out_source_mask, float* out_planes_f32,
+                             uint32_t* out_count);
+
 /* Refresh: bring an existing index back to its table's current rows KEEPING ITS CENTROIDS — cheap when few
  * rows were written, several times cheaper than pg_index_build when all of them were (nothing is trained).  Nothing changes
  * until it is called: a written table still makes its index stale.
@@ -1086,8 +1151,8 @@ int pg_recommend_candidates_dnn3_dev(pg_ctx* ctx, const pg_table* t, const pg_mo
  *             surviving rows (model scores and everything carried are bit-identical).
  *   Errors    a filtered view is refused (PG_ERR_UNSUPPORTED); PG_ERR_ARITH when either RankScore divides by zero.  The call
  *             returns synchronised.
- * Not served here yet: what pg_recommend_candidates_dnn3_dev does not serve, an FM + two-tower coarse model, the filter's
- * diversity branch (ensureDiversity, DiversityDao) and PriorityAdjustCountFilterV2's Expression / Weight. */
+ * Not served here yet: what pg_recommend_candidates_dnn3_dev does not serve, an FM + two-tower coarse model and the filter's
+ * diversity branch (ensureDiversity, DiversityDao).  (PriorityAdjustCountFilterV2 is pg_candidates_trim2_dev.) */
 int pg_recommend_cascade_dnn3_dev(pg_ctx* ctx, const pg_table* t, const pg_model* m_coarse, const pg_expr* e_coarse,
                                   const char* coarse_var, const pg_model* m_fine, const pg_expr* e_fine, const char* fine_var,
                                   const float* d_user_vecs, uint32_t nq, uint32_t cap, const uint64_t* d_rows, const double* d_score,

@@ -50,6 +50,7 @@ EXPORTS = [
     "pg_fanin_merge_dev", "pg_recommend_candidates_dnn3_dev",
     "pg_trim_out_cap", "pg_candidates_trim_dev", "pg_recommend_cascade_dnn3_dev",
     "pg_blend_out_cap", "pg_candidates_blend_dev", "pg_candidates_blend_host",
+    "pg_trim2_out_cap", "pg_candidates_trim2_dev", "pg_candidates_trim2_host",
     "pg_diversity_rules_host", "pg_diversity_rules_dev", "pg_diversity_rules_features_dev", "pg_diversity_rules",
     "pg_expr_compile_govaluate", "pg_expr_eval_host",
     "pg_cond_compile", "pg_cond_free", "pg_cond_num_rules", "pg_cond_num_user_slots", "pg_cond_user_slot_name",
@@ -289,6 +290,9 @@ def load():
         "pg_recommend_candidates_dnn3_dev": [vp, vp, vp, vp, C.c_char_p, vp, u32, u32, vp, vp, vp, vp, vp, vp],
         "pg_trim_out_cap": [P(PgTrimRule), u32, u32, P(C.c_uint32)],
         "pg_candidates_trim_dev": [vp, P(PgTrimRule), u32, u32, u32, vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp],
+        "pg_trim2_out_cap": [P(PgTrimRule), u32, u32, P(C.c_uint32)],
+        "pg_candidates_trim2_dev": [vp, P(PgTrimRule), u32, u32, u32, vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp],
+        "pg_candidates_trim2_host": [P(PgTrimRule), u32, u32, u32, vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp],
         "pg_blend_out_cap": [P(PgBlendConf), u32, P(C.c_uint32)],
         "pg_candidates_blend_dev": [vp, P(PgBlendConf), u32, u32, vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp],
         "pg_candidates_blend_host": [P(PgBlendConf), u32, u32, vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp],

@@ -1,5 +1,5 @@
 // cand_lists.hpp — the candidate lists of nq requests, stated once for the stages that read and write them: the trim (trim.hip),
-// the blend (blend.hip), the class cut (classcut.hip) and ItemStateFilter (cond.hip); the fan-in (fanin.hip), which makes them, takes the constants
+// the blend (blend.hip), the class cut (classcut.hip), the V2 quota cut (trim2.hip) and ItemStateFilter (cond.hip); the fan-in (fanin.hip), which makes them, takes the constants
 // (DESIGN.md 4.1n).
 //
 // Every array is dense and request-major: an entry is position p < cap of request q, at index q * cap + p; a plane set holds n

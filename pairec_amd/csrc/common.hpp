@@ -84,6 +84,7 @@ enum ScratchSlot : int {
     kSlotCond = 25,          // cond.hip: the one-request entries' staging (pg_item_state_filter, pg_boost_scores: inputs, outputs, the temporary store)
     kSlotBlend = 26,         // blend.hip: segment offsets, per-entry keys and orders, the compacted lists and the pick records
     kSlotClasscut = 27,      // classcut.hip: segment offsets, the score order and the class masks of a cut; the one-request entry's staging behind them
+    kSlotTrim2 = 28,         // trim2.hip: segment offsets, per-rule keys and orders of a V2 quota cut
     kSlotCount
 };
 

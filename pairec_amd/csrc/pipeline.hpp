@@ -120,6 +120,9 @@ int candidates_trim_locked(pg_ctx* ctx, const pg_trim_rule* rules, uint32_t n_ru
 // blend.hip: SnakeFilter / CompletelyFairCountFilter over the same lists (checked by the caller; out.out_cap from pg_blend_out_cap).
 // Caller holds ctx->mu; no synchronisation.
 int candidates_blend_locked(pg_ctx* ctx, const pg_blend_conf* conf, const CandIn& in, const CandOut& out);
+// trim2.hip: PriorityAdjustCountFilterV2 over the same lists (checked by the caller; out.out_cap from pg_trim2_out_cap).  Caller holds
+// ctx->mu; no synchronisation.
+int candidates_trim2_locked(pg_ctx* ctx, const pg_trim_rule* rules, uint32_t n_rules, const CandIn& in, const CandOut& out);
 int rerank_select_locked(pg_ctx* ctx, const RecommendCall& c, uint32_t q0, uint32_t nq, const PostScratch& ps);
 int rerank_run_locked(pg_ctx* ctx, const RecommendCall& c, uint32_t q0, uint32_t nq, const PostScratch& ps);
 

@@ -53,6 +53,15 @@ def trim_out_cap(rules, cap: int) -> int:
     return out.value
 
 
+def trim2_out_cap(rules, cap: int) -> int:
+    """pg_trim2_out_cap: rules = [(source, TRIM_FIX | TRIM_ACCUMULATE, count)] for PriorityAdjustCountFilterV2 → min(cap, the FIX
+    counts + the largest ACCUMULATE count); raises PgError for a rule set the call refuses.  A host function: no context, no
+    device."""
+    out = C.c_uint32()
+    _lib.check(_lib.load().pg_trim2_out_cap(_trim_rules(rules), len(rules), int(cap), C.byref(out)))
+    return out.value
+
+
 BLEND_SNAKE_REFILL, BLEND_SNAKE_SKIP, BLEND_FAIR = 0, 1, 2
 
 
@@ -113,6 +122,17 @@ def candidates_blend_host(conf, rows, score, source=None, count=None, planes_f64
                                                 planes_f64, source_mask, planes_f32)
     v = lambda a: None if a is None else _ptr(a)                                     # noqa: E731
     _lib.check(_lib.load().pg_candidates_blend_host(C.byref(_blend_conf(conf)), nq, cap, v(ins[0]), v(ins[1]), v(ins[2]), v(ins[3]),
+                                                    v(ins[4]), n64, v(ins[5]), v(ins[6]), n32, *[v(a) for a in outs]))
+    return tuple(outs)
+
+
+def candidates_trim2_host(rules, rows, score, source=None, count=None, planes_f64=None, source_mask=None, planes_f32=None):
+    """pg_candidates_trim2_host: PriorityAdjustCountFilterV2 on host arrays by the library's host statement (no context, no
+    device); arguments and result as Context.candidates_trim2."""
+    nq, cap, ins, outs, n64, n32 = _cand_arrays("candidates_trim2_host", lambda cap: trim2_out_cap(rules, cap), rows, score, source, count,
+                                                planes_f64, source_mask, planes_f32)
+    v = lambda a: None if a is None else _ptr(a)                                     # noqa: E731
+    _lib.check(_lib.load().pg_candidates_trim2_host(_trim_rules(rules), len(rules), nq, cap, v(ins[0]), v(ins[1]), v(ins[2]), v(ins[3]),
                                                     v(ins[4]), n64, v(ins[5]), v(ins[6]), n32, *[v(a) for a in outs]))
     return tuple(outs)
 
@@ -670,6 +690,34 @@ class Context:
                                                     planes_f64, source_mask, planes_f32)
         return self._cand_run(ins, outs, lambda d_in, d_out: self.candidates_blend_dev(
             conf, nq, cap, d_in[0], d_in[1], d_in[2], d_in[3], d_in[4], n64, d_in[5], d_in[6], n32, *d_out))
+
+    @staticmethod
+    def trim2_out_cap(rules, cap: int) -> int:
+        """pg_trim2_out_cap: the width of what V2's rules can keep of `cap` entries (validates them; needs no device)."""
+        return trim2_out_cap(rules, cap)
+
+    def candidates_trim2_dev(self, rules, nq: int, cap: int, d_rows: int, d_score: int, d_source: int, d_count: int, d_planes_f64: int,
+                             n_f64: int, d_source_mask: int, d_planes_f32: int, n_f32: int, d_out_rows: int, d_out_score: int,
+                             d_out_source: int, d_out_planes_f64: int, d_out_source_mask: int, d_out_planes_f32: int,
+                             d_out_count: int) -> None:
+        """pg_candidates_trim2_dev: rules = [(source, type, count)], everything else device addresses as candidates_trim_dev (0 =
+        absent; an output is required exactly where its input is given), outputs [nq][trim2_out_cap(rules, cap)].  Enqueued on
+        the context's stream: synchronize() before reading."""
+        arr = _trim_rules(rules)
+        v = lambda p: C.c_void_p(p or None)                                          # noqa: E731
+        _lib.check(self.L.pg_candidates_trim2_dev(self.h, arr, len(rules), nq, cap, v(d_rows), v(d_score), v(d_source), v(d_count),
+                                                  v(d_planes_f64), n_f64, v(d_source_mask), v(d_planes_f32), n_f32, v(d_out_rows),
+                                                  v(d_out_score), v(d_out_source), v(d_out_planes_f64), v(d_out_source_mask),
+                                                  v(d_out_planes_f32), v(d_out_count)))
+
+    def candidates_trim2(self, rules, rows, score, source=None, count=None, planes_f64=None, source_mask=None, planes_f32=None):
+        """PriorityAdjustCountFilterV2 on host arrays (pg_candidates_trim2_dev): the arrays of candidates_trim, planes_f64 the
+        per-recall scores by source index and source_mask the recalls that hold the entry → (rows, score, source, planes_f64,
+        source_mask, planes_f32, count), [nq][out_cap] each, None where the input was None."""
+        nq, cap, ins, outs, n64, n32 = _cand_arrays("candidates_trim2", lambda cap: trim2_out_cap(rules, cap), rows, score, source, count,
+                                                    planes_f64, source_mask, planes_f32)
+        return self._cand_run(ins, outs, lambda d_in, d_out: self.candidates_trim2_dev(
+            rules, nq, cap, d_in[0], d_in[1], d_in[2], d_in[3], d_in[4], n64, d_in[5], d_in[6], n32, *d_out))
 
     def diversity_rules_dev(self, cfg, n_cols: int, nq: int, cap: int, d_count: int, d_dims: int, d_source: int, d_enable: int,
                             d_order: int) -> None:

@@ -578,6 +578,41 @@ bool RecommendConfig::Parse(const std::string& text, RecommendConfig* out, std::
                 else pg_classcut_free(set);
             }
         }
+        else if (c.IsQuota()) {
+            // NewPriorityAdjustCountFilter (priority_adjust_count_filter.go:44-78) / NewPriorityAdjustCountFilterV2
+            // (priority_adjust_count_filter_v2.go:21-30): what pg_trim_out_cap / pg_trim2_out_cap refuse is refused here, by name
+            const bool v2 = c.FilterType == "PriorityAdjustCountFilterV2";
+            for (const auto& r : out->GpuRecalls) c.QuotaSources.push_back(r.Name);
+            for (const char* key : {"EnsureDiversity", "DiversityMinCount", "DiversityDaoConf"})
+                if (!v2 && why.empty() && fc.has(key)) why = std::string(key) + " (the filter's diversity branch is not served on the device)";
+            const auto& confs = fc.at("AdjustCountConfs").arr;
+            if (why.empty() && confs.empty()) why = "AdjustCountConfs is empty";
+            if (why.empty() && confs.size() > PG_TRIM_MAX_RULES)
+                why = std::to_string(confs.size()) + " AdjustCountConfs (the device serves up to " + std::to_string(PG_TRIM_MAX_RULES) + ")";
+            for (size_t i = 0; why.empty() && i < confs.size(); ++i) {
+                const std::string name = confs[i].s("RecallName"), type = confs[i].s("Type");
+                const double count = confs[i].d("Count");
+                const auto at = std::find(c.QuotaSources.begin(), c.QuotaSources.end(), name);
+                if (at == c.QuotaSources.end()) why = "RecallName \"" + name + "\" is no recall of pairec_gpu.Recalls";
+                else if (at - c.QuotaSources.begin() >= PG_TRIM_MAX_SOURCES)
+                    why = "RecallName \"" + name + "\" is recall " + std::to_string(at - c.QuotaSources.begin()) + " (the device serves the first " +
+                          std::to_string(PG_TRIM_MAX_SOURCES) + " recalls)";
+                else if (confs[i].at("Count").type != json::Value::Number || count < 0 || count > 4294967295.0 || count != std::floor(count))
+                    why = "Count of \"" + name + "\" is not a count";
+                else if (type != "fix" && type != "accumulator")
+                    why = "Type \"" + type + "\" of \"" + name + "\" (the reference serves fix and accumulator)";
+                else
+                    c.Quotas.push_back(pg_trim_rule{(uint8_t)(at - c.QuotaSources.begin()), (uint8_t)(type == "fix" ? PG_TRIM_FIX : PG_TRIM_ACCUMULATE),
+                                                    (uint32_t)count});
+            }
+            uint32_t width = 0;
+            if (why.empty() && (v2 ? pg_trim2_out_cap : pg_trim_out_cap)(c.Quotas.data(), (uint32_t)c.Quotas.size(), 1, &width) != PG_OK) {
+                why = pg_last_error();
+                const size_t colon = why.find(": ");                     // (the entry point's name says nothing here)
+                if (colon != std::string::npos) why = why.substr(colon + 2);
+            }
+            if (!why.empty()) why = c.FilterType + ": " + why;
+        }
         else if (c.FilterType != "ItemStateFilter") why = "unknown FilterType \"" + c.FilterType + "\" (the device serves ItemStateFilter)";
         else if (!c.FeatureStore.empty() && c.FeatureStore != "item_features")
             why = "FeatureStore \"" + c.FeatureStore + "\" (the engine holds one store of item columns, \"item_features\")";
@@ -1974,6 +2009,87 @@ bool blend_filter(Engine* self, const recconf::GpuFilterConfig& conf, std::vecto
     return true;
 }
 
+// PriorityAdjustCountFilter (filter/priority_adjust_count_filter.go:80-251, ensureDiversity false) through pg_candidates_trim_dev and
+// PriorityAdjustCountFilterV2 (filter/priority_adjust_count_filter_v2.go:39-103) through pg_candidates_trim2_dev: the items become
+// the arrays a fan-in leaves, exactly as blend_filter builds them, and the kept positions come back in rule order; under V2 an item
+// kept through a rule other than its own source takes that recall's name and score (:68-69).
+bool quota_filter(Engine* self, const recconf::GpuFilterConfig& conf, std::vector<module::ItemPtr>* items, std::string* err) {
+    const size_t n = items->size();
+    if (n == 0) return true;
+    auto fail = [&](const std::string& what) { if (err) *err = conf.FilterType + " " + conf.Name + ": " + what; return false; };
+    if (n > PG_TRIM_MAX_CAP) return fail(std::to_string(n) + " items (the device serves up to " + std::to_string(PG_TRIM_MAX_CAP) + ")");
+    const bool v2 = conf.FilterType == "PriorityAdjustCountFilterV2";
+    std::vector<std::string> names = conf.QuotaSources;
+    if (names.size() > PG_TRIM_MAX_SOURCES) names.resize(PG_TRIM_MAX_SOURCES);
+    const uint32_t n_planes = (uint32_t)std::max<size_t>(names.size(), 1);
+    const uint32_t cap = (uint32_t)n, n_rules = (uint32_t)conf.Quotas.size();
+    uint32_t out_cap = 0;
+    if ((v2 ? pg_trim2_out_cap : pg_trim_out_cap)(conf.Quotas.data(), n_rules, cap, &out_cap) != PG_OK) return fail(pg_last_error());
+    if (out_cap == 0) {                                                       // every count is 0: nothing is kept
+        items->clear();
+        return true;
+    }
+    std::vector<uint64_t> rows(n), out_rows(out_cap);
+    std::vector<double> score(n), out_score(out_cap), planes((size_t)n_planes * n, std::nan(""));
+    std::vector<uint8_t> source(n), out_source(out_cap);
+    std::vector<uint32_t> mask(n);
+    for (size_t i = 0; i < n; ++i) {
+        const module::Item& it = *(*items)[i];
+        const auto at = std::find(names.begin(), names.end(), it.RetrieveId);
+        rows[i] = i;
+        score[i] = it.Score;
+        source[i] = at == names.end() ? 0xFF : (uint8_t)(at - names.begin());        // (what no rule names is dropped)
+        if (it.hasRecallScores && it.RecallScores.size() > 1) {                      // (:55: the names of RecallScores are what counts)
+            for (const auto& kv : it.RecallScores) {
+                const auto r = std::find(names.begin(), names.end(), kv.first);
+                if (r == names.end()) {
+                    mask[i] |= 1u << 31;                                             // (a recall the device does not know: no rule names it)
+                    continue;
+                }
+                mask[i] |= 1u << (r - names.begin());
+                planes[(size_t)(r - names.begin()) * n + i] = kv.second;
+            }
+        } else if (source[i] < n_planes) {
+            mask[i] = 1u << source[i];
+            planes[(size_t)source[i] * n + i] = it.Score;
+        }
+    }
+    const size_t b_in = n * 8, b_out = (size_t)out_cap * 8;
+    // one device buffer: rows | score | planes | mask | source | out rows | out score | out planes | out mask | out source | count
+    const size_t o_score = b_in, o_planes = 2 * b_in, o_mask = o_planes + n_planes * b_in, o_source = o_mask + n * 4;
+    const size_t o_orows = (o_source + n + 255) & ~(size_t)255, o_oscore = o_orows + b_out, o_oplanes = o_oscore + b_out;
+    const size_t o_omask = o_oplanes + n_planes * b_out, o_osource = o_omask + (size_t)out_cap * 4, o_count = (o_osource + out_cap + 255) & ~(size_t)255;
+    void* d = nullptr;
+    if (pg_device_malloc(self->ctx, o_count + 256, &d) != PG_OK) return fail(pg_last_error());
+    char* b = (char*)d;
+    uint32_t count = 0;
+    const bool ok = pg_memcpy_h2d(self->ctx, b, rows.data(), b_in) == PG_OK && pg_memcpy_h2d(self->ctx, b + o_score, score.data(), b_in) == PG_OK &&
+                    pg_memcpy_h2d(self->ctx, b + o_planes, planes.data(), n_planes * b_in) == PG_OK &&
+                    pg_memcpy_h2d(self->ctx, b + o_mask, mask.data(), n * 4) == PG_OK && pg_memcpy_h2d(self->ctx, b + o_source, source.data(), n) == PG_OK &&
+                    (v2 ? pg_candidates_trim2_dev : pg_candidates_trim_dev)(
+                        self->ctx, conf.Quotas.data(), n_rules, 1, cap, (const uint64_t*)b, (const double*)(b + o_score), (const uint8_t*)(b + o_source),
+                        nullptr, (const double*)(b + o_planes), n_planes, (const uint32_t*)(b + o_mask), nullptr, 0, (uint64_t*)(b + o_orows),
+                        (double*)(b + o_oscore), (uint8_t*)(b + o_osource), (double*)(b + o_oplanes), (uint32_t*)(b + o_omask), nullptr,
+                        (uint32_t*)(b + o_count)) == PG_OK &&
+                    pg_synchronize(self->ctx) == PG_OK && pg_memcpy_d2h(self->ctx, out_rows.data(), b + o_orows, b_out) == PG_OK &&
+                    pg_memcpy_d2h(self->ctx, out_score.data(), b + o_oscore, b_out) == PG_OK &&
+                    pg_memcpy_d2h(self->ctx, out_source.data(), b + o_osource, out_cap) == PG_OK &&
+                    pg_memcpy_d2h(self->ctx, &count, b + o_count, 4) == PG_OK;
+    const std::string why = ok ? std::string() : pg_last_error();
+    pg_device_free(self->ctx, d);
+    if (!ok) return fail(why);
+    std::vector<module::ItemPtr> kept(std::min(count, out_cap));
+    for (size_t k = 0; k < kept.size(); ++k) {
+        kept[k] = (*items)[(size_t)out_rows[k]];
+        if (v2 && out_source[k] < names.size()) {                                     // (:68-69; a single's are its own)
+            kept[k]->RetrieveId = names[out_source[k]];
+            kept[k]->Score = out_score[k];
+        }
+    }
+    items->swap(kept);
+    return true;
+}
+
 // DiversityAdjustCountFilter (filter/diversity_adjust_count_filter.go:75-143) through pg_candidates_classcut: an item becomes its table
 // row (one the table does not know: a row of its own behind the store, every column missing), Item.Score and the index of
 // RetrieveId among the engine's recalls; the kept rows come back in class order and name their items.
@@ -2648,6 +2764,10 @@ bool Engine::BlendFilter(const recconf::GpuFilterConfig& conf, std::vector<modul
 
 bool Engine::ClasscutFilter(const recconf::GpuFilterConfig& conf, std::vector<module::ItemPtr>* items, std::string* err) {
     return classcut_filter(this, conf, items, err);
+}
+
+bool Engine::QuotaFilter(const recconf::GpuFilterConfig& conf, std::vector<module::ItemPtr>* items, std::string* err) {
+    return quota_filter(this, conf, items, err);
 }
 
 bool Engine::Recommend(const std::string& uid, int size, const std::string& scene,

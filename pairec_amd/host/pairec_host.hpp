@@ -157,6 +157,7 @@ struct SortConfig {                        // recconf.go:820-838: Name, SortType
 // … "SnakeFilter" (filter/snake_filter.go:118-241: AdjustCountConfs[{RecallName, Weight}], RetainNum, SnakeType) and
 // "CompletelyFairCountFilter" (filter/completely_fair_count_filter.go:18-94: RetainNum) through pg_candidates_blend_dev
 // … and "DiversityAdjustCountFilter" (filter/diversity_adjust_count_filter.go:44-143) through pg_candidates_classcut
+// … and "PriorityAdjustCountFilter" / "PriorityAdjustCountFilterV2" through pg_candidates_trim_dev / pg_candidates_trim2_dev
 struct GpuFilterConfig {
     std::string Name, FilterType, FeatureStore;
     json::Value FilterParams;              // [FilterParamConfig] (recconf.go:884-891)
@@ -172,6 +173,13 @@ struct GpuFilterConfig {
     std::vector<ClassConf> Classes;
     std::vector<std::string> ClassColumns, ClassRecalls;
     bool IsClasscut() const { return FilterType == "DiversityAdjustCountFilter"; }
+    // "PriorityAdjustCountFilter" (filter/priority_adjust_count_filter.go:80-251, without its diversity branch) through
+    // pg_candidates_trim_dev and "PriorityAdjustCountFilterV2" (filter/priority_adjust_count_filter_v2.go:39-103) through
+    // pg_candidates_trim2_dev: AdjustCountConfs[{RecallName, Count, Type}] as the rules the device takes, a RecallName resolved to
+    // the recall's index in pairec_gpu.Recalls, and those recall names in index order
+    std::vector<pg_trim_rule> Quotas;
+    std::vector<std::string> QuotaSources;
+    bool IsQuota() const { return FilterType == "PriorityAdjustCountFilter" || FilterType == "PriorityAdjustCountFilterV2"; }
 };
 struct FeatureConfig {                      // recconf.go:256-265
     std::string FeatureType, FeatureName, FeatureSource, FeatureValue, FeatureStore, Normalizer, Expression;
@@ -492,9 +500,10 @@ public:
     bool ItemStateFilter(const recconf::GpuFilterConfig& conf, const module::User* user, std::vector<module::ItemPtr>* items, std::string* err);
     bool BlendFilter(const recconf::GpuFilterConfig& conf, std::vector<module::ItemPtr>* items, std::string* err);   // SnakeFilter, CompletelyFairCountFilter
     bool ClasscutFilter(const recconf::GpuFilterConfig& conf, std::vector<module::ItemPtr>* items, std::string* err);   // DiversityAdjustCountFilter
+    bool QuotaFilter(const recconf::GpuFilterConfig& conf, std::vector<module::ItemPtr>* items, std::string* err);   // PriorityAdjustCountFilter, PriorityAdjustCountFilterV2
     // one pairec_gpu.Filters entry, whatever its FilterType
     bool RunGpuFilter(const recconf::GpuFilterConfig& conf, const module::User* user, std::vector<module::ItemPtr>* items, std::string* err) {
-        return conf.IsBlend() ? BlendFilter(conf, items, err) : conf.IsClasscut() ? ClasscutFilter(conf, items, err) : ItemStateFilter(conf, user, items, err);
+        return conf.IsBlend() ? BlendFilter(conf, items, err) : conf.IsClasscut() ? ClasscutFilter(conf, items, err) : conf.IsQuota() ? QuotaFilter(conf, items, err) : ItemStateFilter(conf, user, items, err);
     }
     std::map<std::string, std::vector<int32_t>> user_fields;   // uid → dictionary-encoded user categorical features
     pg_model* fm2t = nullptr;                           // FM + two-tower model: rank algorithm "fm2t", and the vector model of the online recall
