@@ -1506,6 +1506,104 @@ int pg_candidates_classcut_dev(pg_ctx* ctx, pg_classcut* c, const pg_features* f
 int pg_candidates_classcut(pg_ctx* ctx, pg_classcut* c, const pg_features* fs, uint32_t n, const uint64_t* rows, const double* score,
                            const uint8_t* source, uint64_t* out_rows, double* out_score, uint8_t* out_source, uint32_t* out_count);
 
+/* MultiRecallMixSort on the device: fixed and random page slots (csrc/mixsort.hip).  The reference's page-shaping
+ * sort behind ItemRankScore (sort/multi_recall_mix_sort.go, sort/mix_sort_strategy.go): every MixSortConfig is a strategy that
+ * claims items by recall name or by a module.FilterParam and puts them at configured positions of the page (fix_position) or at
+ * a random place of each stride (random_position); everything else fills up in order.
+ *   In        one request holds entries 0 .. n-1, n = d_count[q] (cap when d_count is NULL), in the order the previous sort left
+ *             them; an entry's position in that list is its identity (after UniqueFilter ids are unique, so remainItemIterator's
+ *             id map, :180-216, is a "placed" flag per entry).  d_order [nq][cap] uint32 (optional, NULL =
+ *             identity): list entry j is element d_order[q][j] of the [nq][cap] arrays — pg_sort_scores_dev's output and the
+ *             recommend calls' d_out_order plug in as they are.  Per element: d_rows uint64 (binds the condition columns and the
+ *             position columns through a pg_features store; a row >= the store's rows is "missing", as for pg_cond), d_source
+ *             uint8 (the fan-in's numbering; required iff a strategy has a non-zero source mask), user slots as pg_cond takes
+ *             them (d_user_vals [nq][PG_COND_MAX_SLOTS], d_user_present [nq]).  S = max(ctx_size, the compiled size) (:42-45,
+ *             :66-69); ctx_size is one host value per call; 1 <= S <= PG_MIX_MAX_SIZE.
+ *   Answer    DEFINED bit for bit; positions are reported as indices into the [nq][cap] arrays (composed with d_order).
+ *               1. n < S: the answer is the identity, the count n (:71-73).
+ *               2. strategies s = 0 .. n_s-1 in config order.  number_s (mix_sort_strategy.go:121-176): FIX — the number of
+ *                  configured positions, else `number` if > 0, else 0; RANDOM — (int)((double)S * number_rate) if number_rate >
+ *                  0, else `number` if > 0, else 0.  member_s(i): the source bit of entry i is set in the strategy's mask (a
+ *                  source >= 32 never matches), or the strategy has conditions and they hold (:86-107).  Inside pg_cond's subset
+ *                  EvaluateByDomain returns no error, so the break at :95-98 is unreachable.
+ *               3. taken_s = the first number_s entries, in list order, with member_s that no earlier strategy took; D = the first
+ *                  S entries nobody took.  (The reference walks item by item, strategies inside, and stops once all are full,
+ *                  :82-128; taking strategy by strategy gives the same lists.)
+ *               4. result[0 .. S) starts empty.  FIX strategies first, in config order (BuildItems, :137-155): P_s = the
+ *                  configured positions; or, without any and with a position column, for j < min(number_s, |taken_s|) the column's
+ *                  value at taken_s[j] (a missing row counts as -1, utils.ToInt(.., -1)), keeping the values p > 0 in order.
+ *                  idx = 0; for each p in P_s: if p <= S and idx < |taken_s|, result[p-1] = taken_s[idx++].  A later write to a
+ *                  slot replaces the earlier entry, which then is no longer in the result.  (The k-th usable position receives
+ *                  the k-th taken entry, not the entry whose column gave the position: that is the reference.)
+ *               5. RANDOM strategies next, in config order (:178-216): step = S / number_s, start = 0; for the j-th entry of
+ *                  taken_s: stop if no slot of result is empty; end = min(start + draw(q, s, j) % step, S - 1), moved forward
+ *                  cyclically to the first empty slot; the entry goes there; start += step.
+ *                  draw(q, s, j): x = seed[q] + 0x9E3779B97F4A7C15 * (1 + s * 65536 + j) in uint64 arithmetic;
+ *                  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9; x = (x ^ (x >> 27)) * 0x94D049BB133111EB; draw = x ^ (x >> 31) (the
+ *                  splitmix64 finaliser).  d_seed [nq] uint64, NULL = 0.  Go's process-wide math/rand stream is not reproduced;
+ *                  the range and the placement rule are.
+ *               6. D fills the empty slots in ascending slot order (:236-245).
+ *               7. slots still empty receive, in ascending slot order, the entries not in result, in list order (:143-159).
+ *                  Because n >= S there are always enough: the shrinking branch :152-156 is unreachable, |result| = S exactly,
+ *                  without duplicates.
+ *               8. with remain_item every entry not in the result follows in list order (:161-174) and the count is n; otherwise
+ *                  the count is S.  Slots behind the count receive UINT32_MAX.  Every element of d_out_order [nq][cap] and
+ *                  d_out_count [nq] is written exactly once; d_out_order may not overlap d_order.
+ *   Refused   on the host, the context left usable.  PG_ERR_INVALID: a configured position < 1 (the reference indexes items[-1]);
+ *             a RANDOM strategy with number_s > S at the call's S (rand.Intn(0) panics); a negative number / number_rate; a
+ *             source mask without d_source; a position column that is not declared int32 / int64 or is not in the store; an
+ *             unknown strategy type.  PG_ERR_UNSUPPORTED: more than PG_MIX_MAX_STRATEGIES strategies; more than
+ *             PG_MIX_MAX_POSITIONS positions in one strategy; S > PG_MIX_MAX_SIZE; cap outside [1, PG_TRIM_MAX_CAP]; nq > 256;
+ *             whatever pg_cond_compile refuses, under its name.  No strategies is not an error: the answer is D, then the tail.
+ *   host      pg_mix_sort_host: a pure host function (no context, no device), the same answer stated entry by entry over
+ *             candidate-aligned arrays as pg_candidates_classcut_host takes them: cols[d] = the nq * cap values of declared
+ *             column d in its dtype (NULL for columns nothing reads), item_in[i] = 0 for an element outside the store (NULL: all
+ *             inside), source, user_vals [nq][PG_COND_MAX_SLOTS], user_present [nq].  What the kernels are tested against; the
+ *             library falls back to it for nothing.
+ *   Kernels   pg_mix_sort_dev: two launches on the context's stream, no synchronisation (the first device call with a set
+ *             uploads its position table once, synchronously).  A match kernel, one lane per entry: its row, every referenced
+ *             column's raw value (all loads issued before the first use), each strategy's rule and source mask → one byte, bit s
+ *             = member of strategy s.  A mix kernel, one workgroup of 1 024 lanes per request: strategies in turn walk the list
+ *             1 024 entries at a time (rank from wave ballots + per-wave counts; a 2 KB LDS bitmap of taken entries; the walk
+ *             ends in the chunk where the rank reaches number_s), one wave places FIX and RANDOM entries into the page in LDS,
+ *             all lanes fill and write the tail from an "in result" bitmap.  No entry depends on which lane came first.
+ *   Sharing   as pg_cond: several contexts of ONE device may use a set, also concurrently; pg_mix_free waits for that device.
+ *   one       pg_mix_sort: one request on host arrays against a store (upload, run, download, synchronise); n = 0 is an empty
+ *             answer. */
+#define PG_MIX_FIX 1            /* MixStrategy "fix_position" */
+#define PG_MIX_RANDOM 2         /* MixStrategy "random_position" */
+#define PG_MIX_MAX_STRATEGIES 8
+#define PG_MIX_MAX_POSITIONS 256
+#define PG_MIX_MAX_SIZE 4096
+typedef struct {
+    int32_t             type;            /* PG_MIX_FIX | PG_MIX_RANDOM */
+    const int32_t*      positions;       /* FIX: MixSortConfig.Positions, 1-based */
+    uint32_t            n_positions;
+    const char*         position_field;  /* FIX without positions: MixSortConfig.PositionField, a declared int32 / int64 column; NULL or "" = none */
+    int32_t             number;          /* MixSortConfig.Number */
+    double              number_rate;     /* MixSortConfig.NumberRate (RANDOM) */
+    uint32_t            source_mask;     /* bit r = RecallNames holds the fan-in's source r */
+    const pg_cond_term* terms;           /* MixSortConfig.Conditions */
+    uint32_t            n_terms;
+} pg_mix_strategy;
+typedef struct pg_mix pg_mix;
+int pg_mix_compile(const pg_mix_strategy* strategies, uint32_t n, const pg_cond_col* cols, uint32_t n_cols, uint32_t size, uint32_t remain_item,
+                   pg_mix** out);
+int pg_mix_free(pg_mix* m);
+int pg_mix_num_strategies(const pg_mix* m);
+int pg_mix_num_user_slots(const pg_mix* m);
+const char* pg_mix_user_slot_name(const pg_mix* m, int i);
+int pg_mix_user_slot_is_float(const pg_mix* m, int i);
+int pg_mix_sort_host(const pg_mix* m, uint32_t ctx_size, uint32_t nq, uint32_t cap, const uint8_t* item_in, const void* const* cols,
+                     const uint8_t* source, const uint32_t* order, const uint32_t* count, const uint64_t* seed, const uint64_t* user_vals,
+                     const uint32_t* user_present, uint32_t* out_order, uint32_t* out_count);
+int pg_mix_sort_dev(pg_ctx* ctx, pg_mix* m, const pg_features* fs, uint32_t ctx_size, uint32_t nq, uint32_t cap, const uint64_t* d_rows,
+                    const uint8_t* d_source, const uint32_t* d_order, const uint32_t* d_count, const uint64_t* d_seed,
+                    const uint64_t* d_user_vals, const uint32_t* d_user_present, uint32_t* d_out_order, uint32_t* d_out_count);
+int pg_mix_sort(pg_ctx* ctx, pg_mix* m, const pg_features* fs, uint32_t ctx_size, uint32_t n, const uint64_t* rows, const uint8_t* source,
+                const uint32_t* order, uint64_t seed, const uint64_t* user_vals, uint32_t user_present, uint32_t* out_order,
+                uint32_t* out_count);
+
 /* ---- shard group: one process, several GPUs --------------------------------------------------------
  * BASELINE.json configs[4] / SURVEY.md 8e behind the C ABI (a cgo host cannot join a torch.distributed job): the item
  * table in contiguous row ranges [g*N/G, (g+1)*N/G), one context per shard, model weights replicated.  devices[] may

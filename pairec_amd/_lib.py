@@ -59,6 +59,8 @@ EXPORTS = [
     "pg_classcut_compile", "pg_classcut_free", "pg_classcut_num_classes", "pg_classcut_reads_recall_name", "pg_classcut_out_cap",
     "pg_classcut_masks_host", "pg_candidates_classcut_host", "pg_classcut_masks_dev", "pg_candidates_classcut_dev",
     "pg_candidates_classcut",
+    "pg_mix_compile", "pg_mix_free", "pg_mix_num_strategies", "pg_mix_num_user_slots", "pg_mix_user_slot_name", "pg_mix_user_slot_is_float",
+    "pg_mix_sort_host", "pg_mix_sort_dev", "pg_mix_sort",
 ]
 
 
@@ -164,6 +166,12 @@ class PgCondCol(C.Structure):
 
 class PgClasscutRule(C.Structure):
     _fields_ = [("expression", C.c_char_p), ("type", C.c_uint8), ("count", C.c_uint32)]
+
+
+class PgMixStrategy(C.Structure):
+    _fields_ = [("type", C.c_int32), ("positions", C.POINTER(C.c_int32)), ("n_positions", C.c_uint32), ("position_field", C.c_char_p),
+                ("number", C.c_int32), ("number_rate", C.c_double), ("source_mask", C.c_uint32), ("terms", C.POINTER(PgCondTerm)),
+                ("n_terms", C.c_uint32)]
 
 
 class PgIndexRefreshParams(C.Structure):
@@ -325,6 +333,14 @@ def load():
         "pg_classcut_masks_dev": [vp, vp, vp, u32, u32, vp, vp, vp, vp, vp],
         "pg_candidates_classcut_dev": [vp, vp, vp, u32, u32, vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp],
         "pg_candidates_classcut": [vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp],
+        "pg_mix_compile": [P(PgMixStrategy), u32, P(PgCondCol), u32, u32, u32, P(vp)],
+        "pg_mix_free": [vp],
+        "pg_mix_num_strategies": [vp],
+        "pg_mix_num_user_slots": [vp],
+        "pg_mix_user_slot_is_float": [vp, i32],
+        "pg_mix_sort_host": [vp, u32, u32, u32, vp, P(vp), vp, vp, vp, vp, vp, vp, vp, vp],
+        "pg_mix_sort_dev": [vp, vp, vp, u32, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+        "pg_mix_sort": [vp, vp, vp, u32, u32, vp, vp, vp, u64, vp, u32, vp, P(u32)],
         "pg_index_refresh": [vp, vp, P(PgIndexRefreshParams)],
         "pg_index_refresh_stats": [vp, P(PgIndexRefreshStats)],
         "pg_index_screen_probe": [vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, vp, vp],
@@ -445,6 +461,8 @@ def load():
     L.pg_where_column_name.restype = C.c_char_p
     L.pg_cond_user_slot_name.argtypes = [vp, i32]
     L.pg_cond_user_slot_name.restype = C.c_char_p
+    L.pg_mix_user_slot_name.argtypes = [vp, i32]
+    L.pg_mix_user_slot_name.restype = C.c_char_p
     _lib = L
     return L
 

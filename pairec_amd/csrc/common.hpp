@@ -85,6 +85,7 @@ enum ScratchSlot : int {
     kSlotBlend = 26,         // blend.hip: segment offsets, per-entry keys and orders, the compacted lists and the pick records
     kSlotClasscut = 27,      // classcut.hip: segment offsets, the score order and the class masks of a cut; the one-request entry's staging behind them
     kSlotTrim2 = 28,         // trim2.hip: segment offsets, per-rule keys and orders of a V2 quota cut
+    kSlotMix = 29,           // mixsort.hip: the strategy masks and the taken lists of a mix sort; the one-request entry's staging behind them
     kSlotCount
 };
 

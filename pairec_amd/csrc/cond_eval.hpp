@@ -1,10 +1,13 @@
 // cond_eval.hpp — what the per-candidate evaluators over feature-store columns share: cond.hip (FilterParam terms and boost
-// expressions) and classcut.hip (boolean class expressions, 4.1r).  A candidate is its row; the lane loads the
+// expressions), classcut.hip (boolean class expressions, 4.1r) and mixsort.hip (a FilterParam rule per strategy,
+// 4.1t: the compiled pg_cond, its terms and rules and their bind to a store are stated in the second half of this file).  A candidate is its row; the lane loads the
 // raw bits of every referenced column before anything uses one and keeps them in registers; a column is read as float64(value).
 #pragma once
 #include "cand_lists.hpp"
+#include "expr_prog.hpp"
 
 #include <cstring>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -124,6 +127,194 @@ inline bool cond_overlap(const void* a, size_t an, const void* b, size_t bn) {
     if (!a || !b) return false;
     const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
     return x < y + bn && y < x + an;
+}
+
+
+// ---- module.FilterParam compiled: what cond.hip (filter, boost) and mixsort.hip (strategy membership) walk -------------------------
+constexpr uint32_t kCondMaxRules = 8, kCondMaxTerms = 8, kCondMaxSlots = 8, kCondMaxList = 64;      // (kCondMaxCols: cond_eval.hpp)
+constexpr uint32_t kCondMaxExprOps = 64, kCondMaxExprDepth = 8;
+static_assert(kCondMaxRules == PG_COND_MAX_RULES && kCondMaxTerms == PG_COND_MAX_TERMS &&
+                  kCondMaxSlots == PG_COND_MAX_SLOTS && kCondMaxList == PG_COND_MAX_LIST && kCondMaxExprOps == PG_COND_MAX_EXPR_OPS &&
+                  kCondMaxExprDepth == PG_COND_MAX_EXPR_DEPTH,
+              "include/pairec_gpu.h repeats these");
+
+struct CondTerm {                                 // 24 bytes
+    uint8_t op, type, rhs, user_left;             // pg_cond_op, pg_cond_type, pg_cond_rhs; left side: 0 = column `left`, 1 = user slot `left`
+    uint8_t left, rhs_idx, depth, is_and;         // rhs_idx: user slot or referenced column; depth 1: a child of the bool in front
+    union { long long i; double f; } c;           // the constant
+    uint16_t list_off, list_n;                    // in / not_in: values [list_off, list_off + list_n) of the table, ascending
+    uint32_t pad;
+};
+struct CondRule { uint8_t term_off, n_terms; uint16_t prog_off, prog_n, pad; };
+struct CondProgram {                              // what both kernels and the host statement walk
+    CondCol cols[kCondMaxCols];                   // the referenced columns (host statement: base = the caller's candidate-aligned array)
+    CondTerm terms[kCondMaxRules * kCondMaxTerms];
+    CondRule rules[kCondMaxRules];
+    const long long* lists;
+    const Instr* progs;
+    uint32_t n_used, n_rules;
+    uint64_t store_rows;
+};
+
+// the request's user slots (the candidate itself: CondItem, cond_eval.hpp)
+struct CondUser {
+    const unsigned long long* vals;               // [kCondMaxSlots] bits: int64 or fp64 by the slot's type
+    uint32_t present;
+};
+
+__host__ __device__ __forceinline__ long long cond_col_i64(const CondProgram& p, const CondItem& it, uint32_t k) {
+    const unsigned long long b = cond_pick(it.raw, k);
+    return p.cols[k].dtype == PG_F_I32 ? (long long)(int32_t)(uint32_t)b : (long long)b;          // (integer columns: the compiler checked)
+}
+// one operator that is not a bool (see the file header for where every answer comes from)
+__host__ __device__ __forceinline__ bool cond_term(const CondProgram& p, const CondTerm& t, const CondItem& it, const CondUser& u) {
+    const bool left_in = t.user_left ? ((u.present >> t.left) & 1u) != 0 : it.item_in;
+    if (t.op == PG_COND_IS_NULL) return !left_in;
+    if (t.op == PG_COND_IS_NOT_NULL) return left_in;
+    if (!left_in) return t.op == PG_COND_NOT_EQUAL;
+    const bool is_float = t.type == PG_COND_FLOAT;
+    if (t.op == PG_COND_EQUAL || t.op == PG_COND_NOT_EQUAL) {
+        if (is_float) return false;
+    } else if (t.op == PG_COND_IN || t.op == PG_COND_NOT_IN) {
+        if (is_float || t.type == PG_COND_INT64) return false;
+        const long long v = t.user_left ? (long long)u.vals[t.left] : cond_col_i64(p, it, t.left);
+        uint32_t lo = 0, hi = t.list_n;                               // the first value >= v
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (p.lists[t.list_off + mid] < v) lo = mid + 1; else hi = mid;
+        }
+        const bool found = lo < t.list_n && p.lists[t.list_off + lo] == v;
+        return t.op == PG_COND_IN ? found : !found;
+    }
+    // the right-hand side
+    if (t.rhs == PG_COND_RHS_USER && !((u.present >> t.rhs_idx) & 1u)) return t.op == PG_COND_NOT_EQUAL;
+    if (t.rhs == PG_COND_RHS_ITEM && !it.item_in) return t.op == PG_COND_NOT_EQUAL || (t.op >= PG_COND_GREATER && is_float);
+    if (is_float) {
+        const double l = t.user_left ? cond_bits_f64(u.vals[t.left]) : cond_col_f64(p, it, t.left);
+        const double r = t.rhs == PG_COND_RHS_USER ? cond_bits_f64(u.vals[t.rhs_idx])
+                         : t.rhs == PG_COND_RHS_ITEM ? cond_col_f64(p, it, t.rhs_idx) : t.c.f;
+        switch (t.op) {
+            case PG_COND_GREATER: return l > r;
+            case PG_COND_GREATER_THAN: return l >= r;
+            case PG_COND_LESS: return l < r;
+            default: return l <= r;
+        }
+    }
+    const long long l = t.user_left ? (long long)u.vals[t.left] : cond_col_i64(p, it, t.left);
+    const long long r = t.rhs == PG_COND_RHS_USER ? (long long)u.vals[t.rhs_idx] : t.rhs == PG_COND_RHS_ITEM ? cond_col_i64(p, it, t.rhs_idx) : t.c.i;
+    switch (t.op) {
+        case PG_COND_EQUAL: return l == r;
+        case PG_COND_NOT_EQUAL: return l != r;
+        case PG_COND_GREATER: return l > r;
+        case PG_COND_GREATER_THAN: return l >= r;
+        case PG_COND_LESS: return l < r;
+        default: return l <= r;
+    }
+}
+
+// FilterParam.EvaluateByDomain of rule r (filter_op.go:507-540; a bool's children: :1679-1756)
+__host__ __device__ __forceinline__ bool cond_rule(const CondProgram& p, uint32_t r, const CondItem& it, const CondUser& u) {
+    const uint32_t t0 = p.rules[r].term_off, t1 = t0 + p.rules[r].n_terms;
+    bool all = true;
+    uint32_t i = t0;
+    while (i < t1) {
+        const CondTerm& t = p.terms[i];
+        bool v;
+        if (t.op == PG_COND_BOOL) {
+            bool any = false, every = true;
+            for (++i; i < t1 && p.terms[i].depth == 1; ++i) {
+                const bool c = cond_term(p, p.terms[i], it, u);
+                any = any || c;
+                every = every && c;
+            }
+            v = t.is_and ? every : any;
+        } else {
+            v = cond_term(p, t, it, u);
+            ++i;
+        }
+        all = all && v;
+    }
+    return all;
+}
+
+}  // namespace pg
+
+// the compiled object (pg_cond_compile, cond.hip)
+struct pg_cond {
+    bool boost = false;
+    std::vector<std::string> col_names;           // as declared
+    std::vector<int> col_dtypes;
+    std::vector<int> used;                        // referenced columns → declared index (<= kCondMaxCols)
+    std::vector<std::string> slot_names;          // user slots in order of first use
+    std::vector<uint8_t> slot_float;
+    std::vector<pg::CondTerm> terms;
+    std::vector<pg::CondRule> rules;
+    std::vector<long long> lists;
+    std::vector<pg::Instr> progs;
+    // the device table (lists, programs): uploaded at the first device call, owned until pg_cond_free
+    std::mutex table_mu;                          // the upload below: contexts on one device may share a set
+    int device = -1;
+    void* d_table = nullptr;
+    size_t progs_off = 0;
+};
+
+namespace pg {
+
+// the kernel argument / the host statement's program; cols_base[k]: the base of referenced column k
+inline void cond_program(const pg_cond* c, const void* const* declared_base, const long long* lists, const Instr* progs, uint64_t store_rows, CondProgram* p) {
+    memset(p, 0, sizeof *p);
+    for (size_t k = 0; k < c->used.size(); ++k) p->cols[k] = CondCol{declared_base[c->used[k]], c->col_dtypes[(size_t)c->used[k]], 0};
+    std::copy(c->terms.begin(), c->terms.end(), p->terms);
+    std::copy(c->rules.begin(), c->rules.end(), p->rules);
+    p->lists = lists;
+    p->progs = progs;
+    p->n_used = (uint32_t)c->used.size();
+    p->n_rules = (uint32_t)c->rules.size();
+    p->store_rows = store_rows;
+}
+
+inline int cond_host_check(const pg_cond* c, const void* const* cols, const uint64_t* user_vals, const char* who) {
+    for (int d : c->used)
+        if (!cols || !cols[d]) {
+            set_error("%s: the values of column \"%s\" are missing", who, c->col_names[(size_t)d].c_str());
+            return PG_ERR_INVALID;
+        }
+    if (!c->slot_names.empty() && !user_vals) {
+        set_error("%s: the set reads user property \"%s\" but user_vals is NULL", who, c->slot_names[0].c_str());
+        return PG_ERR_INVALID;
+    }
+    return PG_OK;
+}
+
+// binds the set to a store by name and makes sure its table is on the context's device; caller holds ctx->mu
+inline int cond_bind_locked(pg_ctx* ctx, pg_cond* c, const pg_features* fs, const char* who, CondProgram* p) {
+    std::vector<const void*> declared;
+    int rc;
+    if ((rc = cond_resolve_columns(fs, c->col_names, c->col_dtypes, c->used, who, &declared))) return rc;
+    std::lock_guard<std::mutex> table_guard(c->table_mu);
+    if (c->device >= 0 && c->device != ctx->device) {
+        set_error("%s: the set's table lives on device %d, the context on device %d", who, c->device, ctx->device);
+        return PG_ERR_INVALID;
+    }
+    if (c->device < 0) {
+        // once per set: the in lists and the expression programs (the only synchronous step; every later call only launches)
+        const size_t lb = align_up(c->lists.size() * 8), pb = c->progs.size() * sizeof(Instr);
+        void* d = nullptr;
+        PG_HIP(hipMalloc(&d, lb + pb + 256));
+        hipError_t e = hipSuccess;
+        if (!c->lists.empty()) e = hipMemcpy(d, c->lists.data(), c->lists.size() * 8, hipMemcpyHostToDevice);
+        if (e == hipSuccess && pb) e = hipMemcpy((char*)d + lb, c->progs.data(), pb, hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            hipFree(d);
+            set_error("%s: uploading the set's table failed: %s", who, hipGetErrorString(e));
+            return PG_ERR_DEVICE;
+        }
+        c->d_table = d;
+        c->progs_off = lb;
+        c->device = ctx->device;
+    }
+    cond_program(c, declared.data(), (const long long*)c->d_table, (const Instr*)((const char*)c->d_table + c->progs_off), fs->rows, p);
+    return PG_OK;
 }
 
 }  // namespace pg

@@ -457,6 +457,108 @@ def candidates_classcut_host(cc: Classcut, rows, score, source=None, count=None,
     return tuple(outs)
 
 
+MIX_FIX, MIX_RANDOM = 1, 2
+MIX_MAX_STRATEGIES, MIX_MAX_POSITIONS, MIX_MAX_SIZE = 8, 256, 4096
+_MIX_TYPES = {"fix_position": MIX_FIX, "random_position": MIX_RANDOM}
+
+
+class Mix:
+    """A compiled MultiRecallMixSort (pg_mix_compile): 0..8 strategies in config order.  strategies: [MixSortConfig] with the
+    reference's JSON keys {MixStrategy: "fix_position" | "random_position" (or MIX_FIX / MIX_RANDOM), Positions, PositionField,
+    Number, NumberRate, RecallNames, Conditions: [FilterParamConfig]}; a "SourceMask" key gives the fan-in source bits directly,
+    RecallNames are mapped through recall_names (fan-in source order; a name it lacks matches nothing).  cols: [(name, F_*)];
+    strings: {value: dictionary id} for string terms.  A host object until a device entry first uses it."""
+
+    def __init__(self, strategies, cols=(), size: int = 0, remain_item: bool = False, recall_names=(), strings: Optional[dict] = None):
+        self.L = _lib.load()
+        self.cols = [(str(n), int(d)) for n, d in cols]
+        self.size, self.remain_item = int(size), bool(remain_item)
+        self.strings = dict(strings or {})
+        names = [str(n) for n in recall_names]
+        keep = []
+        arr = (_lib.PgMixStrategy * max(len(strategies), 1))()
+        for i, st in enumerate(strategies):
+            ty = st.get("MixStrategy", 0)
+            arr[i].type = _MIX_TYPES.get(ty, 0) if isinstance(ty, str) else int(ty)
+            pos = [int(p) for p in (st.get("Positions") or ())]
+            pa = (C.c_int32 * max(len(pos), 1))(*pos)
+            keep.append(pa)
+            arr[i].positions, arr[i].n_positions = pa, len(pos)
+            keep.append(str(st.get("PositionField", "") or "").encode("utf-8"))
+            arr[i].position_field = keep[-1]
+            arr[i].number = int(st.get("Number", 0) or 0)
+            arr[i].number_rate = float(st.get("NumberRate", 0.0) or 0.0)
+            mask = int(st.get("SourceMask", 0) or 0)
+            for name in st.get("RecallNames") or ():
+                if name in names and names.index(name) < 32:
+                    mask |= 1 << names.index(name)
+            arr[i].source_mask = mask
+            terms = _cond_terms(st.get("Conditions", ()) or (), self.strings, keep)
+            ta = (_lib.PgCondTerm * max(len(terms), 1))(*terms)
+            keep.append(ta)
+            arr[i].terms, arr[i].n_terms = ta, len(terms)
+        ca = (_lib.PgCondCol * max(len(self.cols), 1))()
+        for i, (n, d) in enumerate(self.cols):
+            keep.append(n.encode("utf-8"))
+            ca[i].name, ca[i].dtype = keep[-1], d
+        h = C.c_void_p()
+        _lib.check(self.L.pg_mix_compile(arr, len(strategies), ca, len(self.cols), self.size, 1 if self.remain_item else 0, C.byref(h)))
+        del keep
+        self.h = h
+        self.n_strategies = self.L.pg_mix_num_strategies(h)
+        self.user_slots = [(self.L.pg_mix_user_slot_name(h, i).decode("utf-8"), bool(self.L.pg_mix_user_slot_is_float(h, i)))
+                           for i in range(self.L.pg_mix_num_user_slots(h))]
+
+    def free(self):
+        if self.h:
+            self.L.pg_mix_free(self.h)
+            self.h = None
+
+    pack_user = Cond.pack_user
+
+    def sort_host(self, ctx_size: int, nq: int, cap: int, cols=None, item_in=None, source=None, order=None, count=None, seed=None,
+                  users=None):
+        """pg_mix_sort_host: the answer on host arrays, no context, no device.  cols {name: [nq][cap]} and item_in [nq][cap] stand
+        in for the store (by element); source [nq][cap] u8, order [nq][cap] u32, count [nq] u32, seed [nq] u64, users one
+        {name: value} per request → (out_order [nq][cap] u32, out_count [nq] u32)."""
+        arrs = []
+        ptrs = (C.c_void_p * max(len(self.cols), 1))()
+        for i, (name, dt) in enumerate(self.cols):
+            if cols is not None and name in cols:
+                a = np.ascontiguousarray(cols[name], dtype=_F_NP[dt]).reshape(-1)
+                if a.shape[0] != nq * cap:
+                    raise ValueError("Mix: column %r holds %d values for %d x %d elements" % (name, a.shape[0], nq, cap))
+                arrs.append(a)
+                ptrs[i] = a.ctypes.data
+
+        def arr_(a, dt, n):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=dt).reshape(-1)
+            if a.shape[0] != n:
+                raise ValueError("Mix.sort_host: an array holds %d values, %d expected" % (a.shape[0], n))
+            return a
+        inn, src, ordr = arr_(item_in, np.uint8, nq * cap), arr_(source, np.uint8, nq * cap), arr_(order, np.uint32, nq * cap)
+        cnt, sd = arr_(count, np.uint32, nq), arr_(seed, np.uint64, nq)
+        uv, up = self.pack_user(users if users is not None else [None] * nq)
+        out, oc = np.empty((nq, cap), np.uint32), np.empty(nq, np.uint32)
+        v = lambda a: None if a is None else _ptr(a)                                     # noqa: E731
+        _lib.check(self.L.pg_mix_sort_host(self.h, int(ctx_size), nq, cap, v(inn), ptrs, v(src), v(ordr), v(cnt), v(sd), _ptr(uv), _ptr(up),
+                                           _ptr(out), _ptr(oc)))
+        del arrs
+        return out, oc
+
+
+def mix_compile(strategies, cols=(), size: int = 0, remain_item: bool = False, recall_names=(), strings: Optional[dict] = None) -> Mix:
+    """pg_mix_compile (see Mix)."""
+    return Mix(strategies, cols, size, remain_item, recall_names, strings)
+
+
+def mix_sort_host(mix: Mix, ctx_size: int, nq: int, cap: int, **kw):
+    """pg_mix_sort_host (see Mix.sort_host): a host function, no context, no device."""
+    return mix.sort_host(ctx_size, nq, cap, **kw)
+
+
 def expr_compile_govaluate(source: str) -> "Expr":
     """pg_expr_compile_govaluate: the arithmetic subset of govaluate that BoostScoreSort expressions use."""
     return Expr(source, govaluate=True)
@@ -929,6 +1031,41 @@ class Context:
                                                  None if src is None else _ptr(src), _ptr(o_r), _ptr(o_s),
                                                  None if src is None else _ptr(o_src), C.byref(cnt)))
         return o_r, o_s, o_src, cnt.value
+
+    # ---- MultiRecallMixSort: fixed and random page slots -------------------------------------------------
+    def mix_sort_dev(self, mix, fs, ctx_size: int, nq: int, cap: int, d_rows: int, d_source: int, d_order: int, d_count: int, d_seed: int,
+                     d_user_vals: int, d_user_present: int, d_out_order: int, d_out_count: int) -> None:
+        """pg_mix_sort_dev: device addresses (0 = absent) → d_out_order [nq][cap] u32, d_out_count [nq] u32.  Enqueued on the
+        context's stream: synchronize() before reading."""
+        v = lambda p: C.c_void_p(p or None)                                          # noqa: E731
+        _lib.check(self.L.pg_mix_sort_dev(self.h, mix.h, getattr(fs, "h", fs), int(ctx_size), nq, cap, v(d_rows), v(d_source), v(d_order),
+                                          v(d_count), v(d_seed), v(d_user_vals), v(d_user_present), v(d_out_order), v(d_out_count)))
+
+    def mix_sort(self, mix, fs, ctx_size: int, rows, source=None, order=None, count=None, seed=None, users=None):
+        """MultiRecallMixSort on host arrays (pg_mix_sort_dev): rows [nq][cap] u64, source [nq][cap] u8, order [nq][cap] u32 (the
+        previous sort's order; None = identity), count [nq], seed [nq] u64, users one {name: value} per request →
+        (out_order [nq][cap] u32, out_count [nq] u32)."""
+        r = np.ascontiguousarray(rows, dtype=np.uint64)
+        if r.ndim != 2:
+            raise ValueError("mix_sort: rows is [nq][cap]")
+        nq, cap = r.shape
+        opt = lambda a, dt: None if a is None else np.ascontiguousarray(a, dtype=dt)     # noqa: E731
+        uv, up = mix.pack_user(users if users is not None else [None] * nq)
+        ins = [r, opt(source, np.uint8), opt(order, np.uint32), opt(count, np.uint32), opt(seed, np.uint64), uv, up]
+        outs = [np.empty((nq, cap), np.uint32), np.empty(nq, np.uint32)]
+        return self._cand_run(ins, outs, lambda d_in, d_out: self.mix_sort_dev(mix, fs, ctx_size, nq, cap, *d_in, *d_out))
+
+    def mix_sort_one(self, mix, fs, ctx_size: int, rows, source=None, order=None, seed: int = 0, user=None):
+        """pg_mix_sort: one request on host arrays (what the host mirror calls) → (out_order [n] u32, count)"""
+        r = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1)
+        src = None if source is None else np.ascontiguousarray(source, dtype=np.uint8).reshape(-1)
+        ordr = None if order is None else np.ascontiguousarray(order, dtype=np.uint32).reshape(-1)
+        uv, up = mix.pack_user([user])
+        out, cnt = np.empty(r.shape[0], np.uint32), C.c_uint32()
+        _lib.check(self.L.pg_mix_sort(self.h, mix.h, getattr(fs, "h", fs), int(ctx_size), r.shape[0], _ptr(r), None if src is None else _ptr(src),
+                                      None if ordr is None else _ptr(ordr), int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(uv), int(up[0]), _ptr(out),
+                                      C.byref(cnt)))
+        return out, cnt.value
 
     # ---- sort / expr (context-level ops) ----------------------------------------------------
     def sort_scores(self, scores: np.ndarray, seg_offsets: Optional[Sequence[int]] = None,

@@ -3,6 +3,7 @@
 #include "pairec_host.hpp"
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cerrno>
 #include <cmath>
@@ -258,6 +259,29 @@ bool CheckBoostScoreConf(const json::Value& sc, std::string* why) {
     }
     return true;
 }
+// a MultiRecallMixSort entry that pg_mix_compile accepts; what it refuses is named by key.  Rules with an unknown MixStrategy are
+// skipped, as createMixStrategies skips them (multi_recall_mix_sort.go:47-58).
+bool CheckMixSortConf(const json::Value& sc, std::string* why) {
+    const double size = sc.d("Size");
+    if (size < 0 || size > PG_MIX_MAX_SIZE) { *why = "Size " + json::NumToString(size) + " (0 .. " + std::to_string(PG_MIX_MAX_SIZE) + ")"; return false; }
+    size_t known = 0;
+    for (const auto& r : sc.at("MixSortRules").arr) {
+        const std::string ms = r.s("MixStrategy");
+        if (ms != "fix_position" && ms != "random_position") continue;
+        ++known;
+        if (!CheckFilterParams(r.at("Conditions"), true, why)) { *why = "MixSortRules: Conditions: " + *why; return false; }
+        if (r.d("Number") < 0) { *why = "MixSortRules: a negative Number"; return false; }
+        if (r.d("NumberRate") < 0) { *why = "MixSortRules: a negative NumberRate"; return false; }
+        if (ms == "fix_position") {
+            const auto& pos = r.at("Positions").arr;
+            if (pos.size() > PG_MIX_MAX_POSITIONS) { *why = "MixSortRules: " + std::to_string(pos.size()) + " Positions (at most " + std::to_string(PG_MIX_MAX_POSITIONS) + ")"; return false; }
+            for (const auto& p : pos)
+                if (p.type != json::Value::Number || p.num < 1 || p.num > 2147483647.0) { *why = "MixSortRules: Positions count from 1 (the reference indexes items[-1])"; return false; }
+        }
+    }
+    if (known > PG_MIX_MAX_STRATEGIES) { *why = std::to_string(known) + " MixSortRules (at most " + std::to_string(PG_MIX_MAX_STRATEGIES) + ")"; return false; }
+    return true;
+}
 }  // namespace recconf
 
 namespace recconf {
@@ -510,6 +534,14 @@ bool RecommendConfig::Parse(const std::string& text, RecommendConfig* out, std::
             std::string why;
             if (!CheckBoostScoreConf(sc, &why)) {
                 if (err) *err = "pairec_gpu.Sorts: " + c.Name + ": BoostScoreSort: " + why;
+                return false;
+            }
+        }
+        if (c.SortType == "MultiRecallMixSort") {
+            c.MixConf = sc;
+            std::string why;
+            if (!CheckMixSortConf(sc, &why)) {
+                if (err) *err = "pairec_gpu.Sorts: " + c.Name + ": MultiRecallMixSort: " + why;
                 return false;
             }
         }
@@ -1891,6 +1923,169 @@ struct GpuBoostScoreSort : sort::ISort {
     }
 };
 
+// MultiRecallMixSort (sort/multi_recall_mix_sort.go:62-178) through pg_mix_sort: the items in the order the previous sort left
+// them are the list.  What the conditions read becomes columns of a store of n rows built for the call (item i is row i) — strings
+// dictionary-encoded per call with the conditions' literals, numbers as int64 where every item holds an integer and fp64 otherwise,
+// as GpuBoostScoreSort does; a PositionField becomes an int64 column, -1 where the item lacks it (utils.ToInt(.., -1)).  The
+// RecallNames of all rules are numbered per call and an item's RetrieveId becomes its source.  The seed is Seed + the number of
+// calls this sort has served.  Rules with an unknown MixStrategy are skipped (createMixStrategies, :47-58).  A config
+// pg_mix_compile refuses, an item without a property a condition names or a list over the device's cap leave Data untouched and
+// return the error.
+struct GpuMultiRecallMixSort : sort::ISort {
+    Engine* e;
+    json::Value conf;
+    std::atomic<uint64_t> served{0};
+    GpuMultiRecallMixSort(Engine* eng, json::Value c) : e(eng), conf(std::move(c)) {}
+    bool Sort(sort::SortData* d, std::string* err) override {
+        const size_t n = d->Data.size();
+        const uint64_t call = served.fetch_add(1);
+        if (n == 0) return true;
+        auto fail = [&](const std::string& what) { if (err) *err = "MultiRecallMixSort: " + what; return false; };
+        if (n > PG_TRIM_MAX_CAP) return fail(std::to_string(n) + " items (the device serves up to " + std::to_string(PG_TRIM_MAX_CAP) + ")");
+        std::map<std::string, long long> dict;
+        CondBuild b;
+        b.dict = &dict;
+        std::vector<const json::Value*> rules;
+        for (const auto& r : conf.at("MixSortRules").arr)
+            if (r.s("MixStrategy") == "fix_position" || r.s("MixStrategy") == "random_position") rules.push_back(&r);
+        const size_t ns = rules.size();
+        std::vector<std::vector<pg_cond_term>> terms(ns);
+        std::vector<std::vector<int32_t>> positions(ns);
+        std::vector<pg_mix_strategy> st(ns);
+        std::vector<std::string> names, pos_fields;          // recall names → sources; position columns
+        for (size_t s = 0; s < ns; ++s) {
+            const json::Value& r = *rules[s];
+            memset(&st[s], 0, sizeof st[s]);
+            st[s].type = r.s("MixStrategy") == "fix_position" ? PG_MIX_FIX : PG_MIX_RANDOM;
+            if (!b.build(r.at("Conditions"), 0, &terms[s])) return fail(b.err);
+            st[s].terms = terms[s].data();
+            st[s].n_terms = (uint32_t)terms[s].size();
+            for (const auto& p : r.at("Positions").arr) positions[s].push_back(p.type == json::Value::Number ? (int32_t)p.num : 0);
+            st[s].positions = positions[s].data();
+            st[s].n_positions = (uint32_t)positions[s].size();
+            st[s].number = (int32_t)r.n("Number");
+            st[s].number_rate = r.d("NumberRate");
+            for (const auto& name : recconf::str_list(r.at("RecallNames"))) {
+                auto at = std::find(names.begin(), names.end(), name);
+                if (at == names.end()) {
+                    if (names.size() >= 32) return fail("more than 32 RecallNames among the MixSortRules");
+                    names.push_back(name);
+                    at = names.end() - 1;
+                }
+                st[s].source_mask |= 1u << (at - names.begin());
+            }
+            if (st[s].type == PG_MIX_FIX && positions[s].empty() && !r.s("PositionField").empty()) {
+                st[s].position_field = b.keep("position:" + r.s("PositionField"));      // (its own column: a condition may read the property as a string)
+                if (std::find(pos_fields.begin(), pos_fields.end(), r.s("PositionField")) == pos_fields.end()) pos_fields.push_back(r.s("PositionField"));
+            }
+        }
+        // the columns: what the conditions read, then the position fields
+        const size_t ncond = b.item_names.size(), nc = ncond + pos_fields.size();
+        std::vector<std::vector<long long>> ints(nc);
+        std::vector<std::vector<double>> floats(nc);
+        std::vector<pg_cond_col> cols(nc);
+        std::vector<std::string> col_names(nc);
+        for (size_t c = 0; c < ncond; ++c) {
+            const std::string& name = b.item_names[c];
+            const int kind = b.item_kind[name];
+            if ((kind & 1) && (kind & 2)) return fail("property \"" + name + "\" is read both as a string and as a number");
+            bool whole = true;
+            for (size_t i = 0; i < n; ++i) {
+                const auto p = d->Data[i]->Properties.find(name);
+                if (p == d->Data[i]->Properties.end()) return fail("item " + d->Data[i]->Id + " has no property \"" + name + "\"");
+                if (kind & 1) continue;
+                if (p->second.type != json::Value::Number) return fail("item " + d->Data[i]->Id + ": property \"" + name + "\" is not a number");
+                whole = whole && (p->second.is_int || (p->second.num == std::floor(p->second.num) && std::fabs(p->second.num) < 9e15));
+            }
+            col_names[c] = name;
+            if ((kind & 1) || whole) {
+                ints[c].resize(n);
+                for (size_t i = 0; i < n; ++i) {
+                    const json::Value& v = d->Data[i]->Properties.find(name)->second;
+                    ints[c][i] = (kind & 1) ? b.code(feature::ItemStringProperty(*d->Data[i], name)) : (v.is_int ? v.i : (long long)v.num);
+                }
+                cols[c].dtype = PG_F_I64;
+            } else {
+                floats[c].resize(n);
+                for (size_t i = 0; i < n; ++i) floats[c][i] = d->Data[i]->Properties.find(name)->second.num;
+                cols[c].dtype = PG_F_F64;
+            }
+        }
+        for (size_t k = 0; k < pos_fields.size(); ++k) {
+            const size_t c = ncond + k;
+            col_names[c] = "position:" + pos_fields[k];
+            cols[c].dtype = PG_F_I64;
+            ints[c].assign(n, -1);
+            for (size_t i = 0; i < n; ++i) {
+                const auto p = d->Data[i]->Properties.find(pos_fields[k]);
+                if (p == d->Data[i]->Properties.end()) continue;
+                long long v = -1;
+                double f = 0.0;
+                if (b.constant(p->second, "int", pos_fields[k], &v, &f)) ints[c][i] = v;      // utils.ToInt(.., -1)
+            }
+        }
+        b.err.clear();
+        for (size_t c = 0; c < nc; ++c) cols[c].name = col_names[c].c_str();
+        pg_mix* m = nullptr;
+        const uint32_t size = (uint32_t)std::max<long long>(conf.n("Size"), 0);
+        if (pg_mix_compile(st.data(), (uint32_t)ns, cols.data(), (uint32_t)nc, size, conf.at("RemainItem").b ? 1u : 0u, &m) != PG_OK) return fail(pg_last_error());
+        pg_features* fs = nullptr;
+        std::vector<uint64_t> rows(n);
+        std::vector<uint8_t> source(n);
+        std::vector<uint32_t> out(n);
+        uint32_t count = 0;
+        for (size_t i = 0; i < n; ++i) {
+            rows[i] = i;
+            const auto at = std::find(names.begin(), names.end(), d->Data[i]->RetrieveId);
+            source[i] = at == names.end() ? 0xFF : (uint8_t)(at - names.begin());
+        }
+        uint64_t uv[PG_COND_MAX_SLOTS] = {0};
+        uint32_t present = 0;
+        std::string why;
+        bool ok = true;
+        if (nc) {
+            ok = pg_features_create(e->ctx, n, &fs) == PG_OK;
+            for (size_t c = 0; ok && c < nc; ++c)
+                ok = pg_features_set_column(e->ctx, fs, cols[c].name, cols[c].dtype, cols[c].dtype == PG_F_I64 ? (const void*)ints[c].data() : (const void*)floats[c].data(), 0.0) == PG_OK;
+            if (!ok) why = pg_err("pg_features");
+        }
+        // the user slots (cond_user_slots reads them off a pg_cond; the set answers the same questions)
+        for (int s = 0; ok && s < pg_mix_num_user_slots(m); ++s) {
+            const std::string name = pg_mix_user_slot_name(m, s);
+            if (!d->User) continue;
+            const auto p = d->User->Properties.find(name);
+            if (p == d->User->Properties.end()) continue;
+            const json::Value& v = p->second;
+            if (b.user_kind[name] & 1) {
+                const long long id = b.code(v.type == json::Value::String ? v.str : v.type == json::Value::Number ? json::NumToString(v.num) : std::string());
+                memcpy(&uv[s], &id, 8);
+            } else if (pg_mix_user_slot_is_float(m, s)) {
+                const double f = ToFloat(v, 0.0);
+                memcpy(&uv[s], &f, 8);
+            } else {
+                long long i = 0;
+                double f = 0.0;
+                if (!b.constant(v, "int", name, &i, &f)) { ok = false; why = "user property \"" + name + "\" is not an integer"; break; }
+                memcpy(&uv[s], &i, 8);
+            }
+            present |= 1u << s;
+        }
+        if (ok) {
+            const long long seed = conf.n("Seed");
+            ok = pg_mix_sort(e->ctx, m, fs, (uint32_t)std::max(d->Context ? d->Context->Size : 0, 0), (uint32_t)n, rows.data(), source.data(), nullptr,
+                             (uint64_t)seed + call, uv, present, out.data(), &count) == PG_OK;
+            if (!ok) why = pg_err("pg_mix_sort");
+        }
+        pg_mix_free(m);
+        if (fs) pg_features_destroy(e->ctx, fs);
+        if (!ok) return fail(why);
+        std::vector<module::ItemPtr> page(count);
+        for (uint32_t k = 0; k < count; ++k) page[k] = d->Data[out[k]];
+        d->Data.swap(page);
+        return true;
+    }
+};
+
 // ItemStateFilter (filter/item_state_filter.go:47-57; the DAO's keep, module/item_state_filter_hologres_dao.go:313-357) through
 // pg_item_state_filter over the engine's feature columns: an item whose id the table does not know is the item absent from the
 // state table.  The position rides in the score plane, so the kept items come back by position, in order.
@@ -2692,6 +2887,7 @@ Engine* Engine::Create(const std::string& config_json, std::string* err) {
         else if (sc.SortType == "ItemScore") e->sorts.RegisterSort(sc.Name, std::make_shared<GpuItemScoreSort>(e.get()), nullptr);
         else if (sc.SortType == "DiversityRuleSort") e->sorts.RegisterSort(sc.Name, std::make_shared<GpuDiversityRuleSort>(e.get(), sc.DiversityConf), nullptr);
         else if (sc.SortType == "BoostScoreSort") e->sorts.RegisterSort(sc.Name, std::make_shared<GpuBoostScoreSort>(e.get(), sc.BoostConf), nullptr);
+        else if (sc.SortType == "MultiRecallMixSort") e->sorts.RegisterSort(sc.Name, std::make_shared<GpuMultiRecallMixSort>(e.get(), sc.MixConf), nullptr);
         else { if (err) *err = "pairec_gpu.Sorts: unknown SortType " + sc.SortType; return nullptr; }
     }
     for (const auto& fc : e->config.GpuFilters) e->gpu_filters[fc.Name] = fc;
@@ -3151,6 +3347,7 @@ const char* ph_engine_sort_scored(void* h, const char* sort_name, const char* it
     for (const auto& it : root.arr) {
         auto item = std::make_shared<module::Item>(it.s("id"));
         item->Score = it.d("score");
+        item->RetrieveId = it.s("retrieve_id");
         item->Properties = it.at("properties").obj;
         sd.Data.push_back(item);
     }

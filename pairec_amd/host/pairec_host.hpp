@@ -152,6 +152,9 @@ struct SortConfig {                        // recconf.go:820-838: Name, SortType
     DiversityRuleSortConfig DiversityConf; // pairec_gpu.Sorts entries of SortType DiversityRuleSort only
     json::Value BoostConf;                 // pairec_gpu.Sorts entries of SortType BoostScoreSort only: the entry itself (BoostScoreConditions[]
                                            // {Conditions, Expression}, BoostScoreConditionsFilterAll: recconf.go:843-844,892-895)
+    json::Value MixConf;                   // pairec_gpu.Sorts entries of SortType MultiRecallMixSort only: the entry itself (MixSortRules[]
+                                           // {MixStrategy, Positions, PositionField, Number, NumberRate, RecallNames, Conditions}, RemainItem,
+                                           // Size: recconf.go SortConfig / MixSortConfig; Seed: ours, default 0)
 };
 // pairec_gpu.Filters: FilterType "ItemStateFilter" (filter/item_state_filter.go:47-57) over the engine's feature columns
 // … "SnakeFilter" (filter/snake_filter.go:118-241: AdjustCountConfs[{RecallName, Weight}], RetainNum, SnakeType) and
