@@ -376,7 +376,8 @@ int pg_dpp_ex(pg_ctx* ctx, const pg_table* t, const uint32_t* cand_rows, const d
  * out_idx (capacity n) receives min(topn, n) indices into the candidate list; when the reference would
  * return the items unchanged ("all item score are zeros") it receives 0..n-1 and *out_count = n.
  * out_quality (optional, [n]) receives the normalised quality scores ("ssd_quality_score").
- * PG_ERR_UNSUPPORTED, the context left usable: n > 8192, dim + ensure_pos_similarity > 320, a candidate row outside `t`. */
+ * PG_ERR_UNSUPPORTED, the context left usable: n > 8192, dim + ensure_pos_similarity > 320, a candidate row outside `t`.
+ * SSDSort.Sort / doSort around the window for nq requests on device arrays (the split, the cuts, the gates): pg_ssd_sort_dev. */
 int pg_ssd(pg_ctx* ctx, const pg_table* t, const uint32_t* cand_rows, const double* rel, uint32_t n,
            double gamma, uint32_t topn, uint32_t window, int normalize_emb, int ensure_pos_similarity,
            int norm_quality_score, int use_ssd_star, uint32_t* out_idx, uint32_t* out_count,
@@ -1116,7 +1117,8 @@ int pg_recommend_end(pg_ctx* ctx, pg_ticket* ticket, double* scan_ms);
  *             answer with its scores widened, the three outputs are bit for bit pg_recommend_dnn3_dev's.
  *   Errors    a filtered view is refused (PG_ERR_UNSUPPORTED) as there; PG_ERR_ARITH when the RankScore divides by zero.  The
  *             call returns synchronised.
- * Not served here yet: the coalescer, scenes, the shard group, a DPP stage behind the sort and the _begin / _end ticket form. */
+ * Not served here yet: the coalescer, scenes, the shard group, a DPP stage behind the sort and the _begin / _end ticket form.
+ * (An SSDSort stage behind the sort is pg_ssd_sort_dev: it takes d_out_order, d_out_fused and d_rows as they are.) */
 int pg_recommend_candidates_dnn3_dev(pg_ctx* ctx, const pg_table* t, const pg_model* m, const pg_expr* e, const char* rank_var,
                                      const float* d_user_vecs, uint32_t nq, uint32_t cap, const uint64_t* d_rows,
                                      const double* d_score, const uint32_t* d_count, float* d_out_rank_scores,
@@ -1603,6 +1605,61 @@ int pg_mix_sort_dev(pg_ctx* ctx, pg_mix* m, const pg_features* fs, uint32_t ctx_
 int pg_mix_sort(pg_ctx* ctx, pg_mix* m, const pg_features* fs, uint32_t ctx_size, uint32_t n, const uint64_t* rows, const uint8_t* source,
                 const uint32_t* order, uint64_t seed, const uint64_t* user_vals, uint32_t user_present, uint32_t* out_order,
                 uint32_t* out_count);
+
+/* SSDSort on the device: candidate lists in, re-ranked page out (csrc/ssd.hip).  SSDSort.Sort and doSort around the
+ * sliding window (sort/ssd_sort.go:110-343) for nq requests on device arrays: the ssd_filter_retrieve_ids split, the candidate-count
+ * cut, the min-score-percent cut, the two normalisations with their "all item score are zeros" bail-out, SSDWithSlidingWindow
+ * (:346-486, as pg_ssd) and the backup list behind the picks.  Enqueued on the context's stream; no host synchronisation.
+ *   In        one request holds entries 0 .. n-1, n = d_count[q] (cap when d_count is NULL), in the order the previous sort left
+ *             them: d_order [nq][cap] uint32 (optional, NULL = identity), list entry j is element d_order[q][j] of the [nq][cap]
+ *             arrays — pg_sort_scores_dev's order and d_order / d_out_fused / the rows of pg_recommend_candidates_dnn3_dev plug in
+ *             as they are.  Per element: d_rows uint64 (global rows of t: the embeddings), d_score fp64 (Item.Score), d_source
+ *             uint8 (optional; the fan-in's numbering).  d_enable [nq] uint8 (optional): the sort's Condition gate (:119-128), as
+ *             pg_diversity_rules_dev takes it.  Padding — an entry at or beyond the count, an order value >= cap, a row UINT64_MAX
+ *             or a row outside t — leaves the list first and appears in no output.
+ *             The list is taken to be score-descending already (ItemRankScore ran before).  The stage does NOT re-sort where the
+ *             reference calls sort.Sort (:123, :130, :302): Go's sort.Sort is unstable, so entries of equal score have no defined
+ *             order in the reference; the order that arrives is kept.
+ *   Scalars   gamma; topn (ctx.Size); window (<= 1 means 5, :356-359); normalize_emb, ensure_pos_similarity, use_ssd_star as
+ *             pg_ssd; norm_quality_score 0 / 1 / 2; candidate_count, min_score_percent, abort_run_cnt (0 = off);
+ *             filter_source_mask: bit s set = source s is among FilterRetrieveIds (a source >= 32, or no d_source, matches nothing).
+ *   Answer    per request, DEFINED bit for bit, in this order:
+ *               1. enable == 0, or abort_run_cnt > 0 and the number of real entries <= abort_run_cnt: the list as it is (:119-134).
+ *               2. entries whose source is in filter_source_mask go to `backup`, in order; the rest is `selected` (:156-169).
+ *               3. gamma == 0: `selected` as it is (:304-308).
+ *               4. cuts (:312-331): if (candidate_count > 0 || min_score_percent > 0) and len > topn: with candidate_count > 0 the
+ *                  list is cut to max(topn, candidate_count); with min_score_percent > 0 and still len > topn it is cut at the
+ *                  first idx >= topn with score[idx] / score[0] < min_score_percent — the fp64 quotient as written, so a NaN
+ *                  quotient does not cut.  What a cut removes is gone.
+ *               5. normalisation of the cut list's scores (:366-391), bit for bit orc_ssd_quality: mode 1 = the sequential sum,
+ *                  the mean, stat.PopMeanVariance's ss / comp chains with separate multiply and add, StdScore; mode 2 = min-max
+ *                  from the first and the last entry with eps = 1e-6.  mean == 0 or variance == 0 (mode 1), span == 0 (mode 2):
+ *                  the cut list is the result, unchanged.
+ *               6. SSDWithSlidingWindow over the cut list, T = min(len, topn) picks.
+ *               7. result = the picks (or the unchanged list of 1, 3 or 5), then `backup`.
+ *   Out       d_out_pos [nq][cap] uint32: the result as indices into the [nq][cap] arrays (composed with d_order), UINT32_MAX
+ *             behind the count; d_out_count [nq]; optional d_out_rows [nq][cap] uint64: the rows at those positions, UINT64_MAX
+ *             behind the count; optional d_out_quality [nq][cap] fp64, by INPUT position: the ssd_quality_score of every entry of
+ *             the cut list when mode 1 or 2 ran (not bailed), the quiet NaN everywhere else.  Every output element is written
+ *             exactly once; no output may overlap an input.
+ *   Limits    nq <= PG_SSD_STAGE_MAX_NQ, cap <= PG_SSD_STAGE_MAX_CAP; n_max = candidate_count > 0 ? min(cap, max(topn,
+ *             candidate_count)) : cap, the host-side bound on a request's cut list, <= PG_SSD_STAGE_MAX_N; d1 = t's dim +
+ *             ensure_pos_similarity in {64, 65, 128, 129} and the effective window <= 16 (the batched kernel's shapes).  Anything
+ *             else, a filtered view and a table of >= 2^32 rows: PG_ERR_UNSUPPORTED by name, nothing enqueued.  topn == 0,
+ *             norm_quality_score outside 0..2, nq or cap 0: PG_ERR_INVALID.
+ *   Kernels   a list kernel (one workgroup per request: the split and the renumbering by wave ballots, the cuts, the
+ *             normalisation — mode 1's chains on one lane, by specification sequential), ssd_prepare_kernel and
+ *             ssd_kernel_grid<D1> with a count per request (every request its own workgroups, mailbox and barrier), an epilogue
+ *             kernel (picks → positions, backup, padding, rows, quality).  pg_stats' ssd_grid_calls grows by one per call. */
+#define PG_SSD_STAGE_MAX_NQ 256
+#define PG_SSD_STAGE_MAX_CAP 16384
+#define PG_SSD_STAGE_MAX_N 8192
+int pg_ssd_sort_dev(pg_ctx* ctx, const pg_table* t, uint32_t nq, uint32_t cap, const uint32_t* d_order, const uint64_t* d_rows,
+                    const double* d_score, const uint8_t* d_source, const uint32_t* d_count, const uint8_t* d_enable, double gamma,
+                    uint32_t topn, uint32_t window, int normalize_emb, int ensure_pos_similarity, int norm_quality_score,
+                    int use_ssd_star, uint32_t candidate_count, double min_score_percent, uint32_t abort_run_cnt,
+                    uint32_t filter_source_mask, uint32_t* d_out_pos, uint32_t* d_out_count, uint64_t* d_out_rows,
+                    double* d_out_quality);
 
 /* ---- shard group: one process, several GPUs --------------------------------------------------------
  * BASELINE.json configs[4] / SURVEY.md 8e behind the C ABI (a cgo host cannot join a torch.distributed job): the item

@@ -60,7 +60,7 @@ EXPORTS = [
     "pg_classcut_masks_host", "pg_candidates_classcut_host", "pg_classcut_masks_dev", "pg_candidates_classcut_dev",
     "pg_candidates_classcut",
     "pg_mix_compile", "pg_mix_free", "pg_mix_num_strategies", "pg_mix_num_user_slots", "pg_mix_user_slot_name", "pg_mix_user_slot_is_float",
-    "pg_mix_sort_host", "pg_mix_sort_dev", "pg_mix_sort",
+    "pg_mix_sort_host", "pg_mix_sort_dev", "pg_mix_sort", "pg_ssd_sort_dev",
 ]
 
 
@@ -341,6 +341,8 @@ def load():
         "pg_mix_sort_host": [vp, u32, u32, u32, vp, P(vp), vp, vp, vp, vp, vp, vp, vp, vp],
         "pg_mix_sort_dev": [vp, vp, vp, u32, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp],
         "pg_mix_sort": [vp, vp, vp, u32, u32, vp, vp, vp, u64, vp, u32, vp, P(u32)],
+        "pg_ssd_sort_dev": [vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, C.c_double, u32, u32, i32, i32, i32, i32, u32, C.c_double, u32, u32,
+                            vp, vp, vp, vp],
         "pg_index_refresh": [vp, vp, P(PgIndexRefreshParams)],
         "pg_index_refresh_stats": [vp, P(PgIndexRefreshStats)],
         "pg_index_screen_probe": [vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, vp, vp],

@@ -16,6 +16,8 @@
 // DESIGN.md §5.7): dot = chain_{k asc} fma; norm = sqrt(chain fma); e ∓= p·f as separate multiply and
 // add/subtract (ScaleVec, then floats.Sub/Add); quality = r + (volume·l2).  Bit-identical to
 // oracle/oracle.c:orc_ssd_window.
+//
+// pg_ssd_sort_dev, further down, is SSDSort.Sort / doSort around that window for a batch of candidate lists on device arrays.
 #include "pipeline.hpp"
 #include "bitonic_reg.hpp"
 
@@ -345,30 +347,44 @@ __device__ __forceinline__ void ssd_grid_barrier(uint32_t* counter, uint32_t G, 
 }
 
 // ebuf: [2 parities][G + 1 slots][D1]: slot w = workgroup w's best candidate, slot G = the item leaving the window
-template <int D1>
-__global__ __launch_bounds__(64) void ssd_kernel_grid(const double* __restrict__ Et, uint32_t n,
-                                                      const double* __restrict__ rel_g, double gamma, uint32_t T,
+// RAGGED (pg_ssd_sort_dev): n_req / t_req [requests of the launch] give every request its own candidate count n_q <= n_stride and
+// pick count T_q <= T_stride; every stride (Et, rel, ebuf, out) stays by the launch's n_stride, G and T_stride.  A lane is valid
+// iff j < n_q and the loop ends at T_q.  EVERY workgroup of a request stays in EVERY barrier of that request (the count is
+// gridDim.x for all of them): a workgroup with no valid lane publishes kNone, "nothing", which the reduction already skips.  A
+// request with n_q == 0 or T_q == 0 (the list kernel's "unchanged") returns as a whole before its first barrier — both words are
+// the request's, so the decision is uniform over its workgroups.  The uniform instantiation (pg_ssd, the coalescer) is the
+// kernel as it was.
+template <int D1, bool RAGGED>
+__global__ __launch_bounds__(64) void ssd_kernel_grid(const double* __restrict__ Et, uint32_t n_stride,
+                                                      const double* __restrict__ rel_g, double gamma, uint32_t T_stride,
                                                       uint32_t W, int star, SsdMail* __restrict__ mail,
-                                                      double* __restrict__ ebuf, uint32_t* __restrict__ out) {
+                                                      double* __restrict__ ebuf, uint32_t* __restrict__ out,
+                                                      const uint32_t* __restrict__ n_req, const uint32_t* __restrict__ t_req) {
     __shared__ double e_sel[D1], e_old[D1];
     __shared__ double p_ring[16][64];
     __shared__ uint32_t pick_ring[32];                   // the last picks (W <= 16 back is all that is needed)
     constexpr uint32_t kNone = 0xFFFFFFFFu;
     const uint32_t lane = threadIdx.x, G = gridDim.x, wg = blockIdx.x;
+    uint32_t n = n_stride, T = T_stride;
     {   // request blockIdx.y of a batch: its own embeddings, mailbox (and barrier counter), vector slots, output
         const uint32_t req = blockIdx.y;
-        Et += (size_t)req * n * D1;
-        rel_g += (size_t)req * n;
+        Et += (size_t)req * n_stride * D1;
+        rel_g += (size_t)req * n_stride;
         mail += req;
         ebuf += (size_t)req * 2 * (G + 1) * D1;
-        out += (size_t)req * T;
+        out += (size_t)req * T_stride;
+        if (RAGGED) {
+            n = min(n_req[req], n_stride);
+            T = min(min(t_req[req], T_stride), n);
+            if (n == 0 || T == 0) return;
+        }
     }
     const uint32_t j = wg * 64 + lane;
     const bool valid = j < n;
     const uint32_t jc = valid ? j : n - 1;
     double v[D1];
 #pragma unroll
-    for (int k = 0; k < D1; ++k) v[k] = (Et + (size_t)k * n)[jc];
+    for (int k = 0; k < D1; ++k) v[k] = (Et + (size_t)k * n_stride)[jc];
     const double rel = rel_g[jc];
     bool selected = false;
     uint32_t phase = 0;
@@ -552,10 +568,13 @@ bool ssd_batchable(uint32_t d1, uint32_t window) { return (d1 == 64 || d1 == 65 
 // quality scores (normalised already), d_out [R][T] picks.  R > 1 needs the multi-workgroup kernel's shapes
 // (ssd_batchable): every request is its own set of G single-wave workgroups with its own mailbox and barrier; a launch
 // carries as many requests as are co-resident (4 single-wave workgroups per CU).  The embeddings are rows d_cand of the
-// device array d_tab [tab_rows][dim] (d_cand == nullptr: rows 0..n-1).  Caller holds ctx->mu.
+// device array d_tab [tab_rows][dim] (d_cand == nullptr: rows 0..n-1).  d_n_req / d_t_req [R] (device, a pair, batchable
+// shapes only): request r holds d_n_req[r] <= n candidates and makes d_t_req[r] <= T picks; n and T stay the strides of every
+// array.  Caller holds ctx->mu.
 static int ssd_run_rows_locked(pg_ctx* ctx, const float* d_tab, uint32_t tab_rows, uint32_t dim, const uint32_t* d_cand,
                                const double* d_rel, uint32_t R, uint32_t n, double gamma, uint32_t T, uint32_t window,
-                               int normalize_emb, int ensure_pos_similarity, int use_ssd_star, uint32_t* d_out) {
+                               int normalize_emb, int ensure_pos_similarity, int use_ssd_star, uint32_t* d_out,
+                               const uint32_t* d_n_req = nullptr, const uint32_t* d_t_req = nullptr) {
     if (R == 0 || n == 0 || T == 0) return PG_OK;
     if (window <= 1) window = 5;                          // ssd_sort.go:357-360
     const uint32_t d1 = dim + (ensure_pos_similarity ? 1u : 0u);
@@ -565,7 +584,7 @@ static int ssd_run_rows_locked(pg_ctx* ctx, const float* d_tab, uint32_t tab_row
     // (single requests only).
     const bool known_d1 = d1 == 64 || d1 == 65 || d1 == 128 || d1 == 129;
     const int kind = ssd_batchable(d1, window) ? 2 : ((known_d1 && n <= kSsdRegMaxN) ? 1 : 0);
-    if (R > 1 && kind != 2) {
+    if ((R > 1 || d_n_req) && kind != 2) {
         set_error("ssd: a batch of %u requests needs dim 64 / 128 and a window <= 16 (d1 = %u, window %u)", R, d1, window);
         return PG_ERR_UNSUPPORTED;
     }
@@ -594,13 +613,19 @@ static int ssd_run_rows_locked(pg_ctx* ctx, const float* d_tab, uint32_t tab_row
             SsdMail* mail_r = mail + r0;
             double* ebuf_r = ebuf + (size_t)r0 * 2 * (G + 1) * d1;
             uint32_t* out_r = d_out + (size_t)r0 * T;
+            const uint32_t* n_r = d_n_req ? d_n_req + r0 : nullptr;          // (the per-request words move with everything else)
+            const uint32_t* t_r = d_n_req ? d_t_req + r0 : nullptr;
             const dim3 grid(G, rn);
+#define PG_SSD_GRID(D1)                                                                                                                  \
+    if (d_n_req) ssd_kernel_grid<D1, true><<<grid, 64, 0, ctx->stream>>>(Et_r, n, rel_r, gamma, T, window, use_ssd_star, mail_r, ebuf_r, out_r, n_r, t_r); \
+    else ssd_kernel_grid<D1, false><<<grid, 64, 0, ctx->stream>>>(Et_r, n, rel_r, gamma, T, window, use_ssd_star, mail_r, ebuf_r, out_r, nullptr, nullptr)
             switch (d1) {
-                case 64: ssd_kernel_grid<64><<<grid, 64, 0, ctx->stream>>>(Et_r, n, rel_r, gamma, T, window, use_ssd_star, mail_r, ebuf_r, out_r); break;
-                case 65: ssd_kernel_grid<65><<<grid, 64, 0, ctx->stream>>>(Et_r, n, rel_r, gamma, T, window, use_ssd_star, mail_r, ebuf_r, out_r); break;
-                case 128: ssd_kernel_grid<128><<<grid, 64, 0, ctx->stream>>>(Et_r, n, rel_r, gamma, T, window, use_ssd_star, mail_r, ebuf_r, out_r); break;
-                default: ssd_kernel_grid<129><<<grid, 64, 0, ctx->stream>>>(Et_r, n, rel_r, gamma, T, window, use_ssd_star, mail_r, ebuf_r, out_r); break;
+                case 64: PG_SSD_GRID(64); break;
+                case 65: PG_SSD_GRID(65); break;
+                case 128: PG_SSD_GRID(128); break;
+                default: PG_SSD_GRID(129); break;
             }
+#undef PG_SSD_GRID
         }
         PG_HIP(hipGetLastError());
         return PG_OK;
@@ -675,6 +700,253 @@ static int ssd_one(pg_ctx* ctx, const pg_table* t, const uint32_t* cand_rows, co
     return PG_OK;
 }
 
+
+// ---------------------------------------------------------------------------------------------
+// pg_ssd_sort_dev: SSDSort.Sort / doSort around the window for nq requests on device arrays.  include/pairec_gpu.h
+// states the answer step by step; the numbers of the steps below are its.
+//
+//   ssd_list_kernel      one workgroup of 1 024 lanes per request.  Walks the list 1 024 entries at a time: an entry's rank among
+//                        `selected` and among `backup` from wave ballots + per-wave counts in LDS (two sets, one barrier per
+//                        chunk) and the running counts.  `selected` goes to the front of the request's position map, `backup` to
+//                        its back (reversed), so one [cap] array holds both.  The min-score-percent cut is a block minimum over
+//                        the first failing index.  Mode 1's sum / ss / comp chains are sequential by specification: one lane runs
+//                        them over the scores staged in LDS, 4 096 at a time; all lanes then write the quality.  Leaves n_q, T_q,
+//                        the state, the cut list's local rows (0 behind n_q) and its quality in kSlotSsdStage.
+//   ssd_prepare_kernel, ssd_kernel_grid<D1, true>   as for a coalesced batch, with a count per request.
+//   ssd_epilogue_kernel  one lane per output slot: picks → positions, `backup`, the unchanged lists, the padding, rows, quality.
+// ---------------------------------------------------------------------------------------------
+constexpr uint32_t kStageThreads = 1024, kStageWaves = kStageThreads / 64, kStageChunk = 4096, kStageNone = 0xFFFFFFFFu;
+constexpr uint32_t kStageRerank = 0, kStageUnchanged = 1;
+static_assert(kCandMaxCap == PG_SSD_STAGE_MAX_CAP && kMaxQueries == PG_SSD_STAGE_MAX_NQ, "include/pairec_gpu.h repeats these");
+static_assert(PG_SSD_STAGE_MAX_N == 128 * 64, "SsdMail holds 128 workgroups of 64 candidates");
+
+struct SsdStageArgs {
+    const uint32_t* order;               // [nq][cap] or nullptr
+    const uint64_t* rows;                // [nq][cap] by element
+    const double* score;
+    const uint8_t* source;               // or nullptr
+    const uint32_t* count;               // [nq] or nullptr
+    const uint8_t* enable;               // [nq] or nullptr
+    uint32_t cap, n_max, topn, T, mode, cand_count, abort_cnt, src_mask;
+    double gamma, min_pct;
+    unsigned long long row_offset, tab_rows;
+    // kSlotSsdStage
+    uint32_t* hdr;                       // [nq][4]: len (the cut list, or the unchanged list), T_q, state, |backup|
+    uint32_t* n_req;                     // [nq] what the grid kernel reads: n_q, or 0 for a request that is not re-ranked
+    uint32_t* t_req;                     // [nq] T_q, or 0
+    uint32_t* map;                       // [nq][cap] selected r → element at [r]; backup b → element at [cap - 1 - b]
+    uint32_t* inv;                       // [nq][cap] element → its rank in `selected`, or kStageNone (only with out_quality)
+    uint32_t* cand;                      // [nq][n_max] the cut list's local rows
+    double* qual;                        // [nq][n_max] its quality scores
+    uint32_t* picks;                     // [nq][T]
+    uint32_t* out_pos;
+    uint32_t* out_count;
+    uint64_t* out_rows;                  // or nullptr
+    double* out_quality;                 // or nullptr
+};
+
+// block-wide minimum / sum over one value per lane; every lane receives it.  s: kStageWaves words.
+__device__ __forceinline__ uint32_t stage_block_min(uint32_t v, uint32_t* s) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, o, 64));
+    __syncthreads();                                                 // (s may still be read from the call before)
+    if ((threadIdx.x & 63u) == 0) s[threadIdx.x >> 6] = v;
+    __syncthreads();
+    uint32_t m = s[0];
+#pragma unroll
+    for (uint32_t w = 1; w < kStageWaves; ++w) m = min(m, s[w]);
+    return m;
+}
+__device__ __forceinline__ uint32_t stage_block_sum(uint32_t v, uint32_t* s) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o, 64);
+    __syncthreads();
+    if ((threadIdx.x & 63u) == 0) s[threadIdx.x >> 6] = v;
+    __syncthreads();
+    uint32_t m = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < kStageWaves; ++w) m += s[w];
+    return m;
+}
+
+// list entry j of a request → its element and whether it is a real entry (padding: an order value >= cap, a row outside t)
+__device__ __forceinline__ bool stage_entry(const SsdStageArgs& a, size_t q0, uint32_t j, uint32_t n, uint32_t* elem) {
+    if (j >= n) return false;
+    const uint32_t e = a.order ? a.order[q0 + j] : j;
+    *elem = e;
+    if (e >= a.cap) return false;
+    const unsigned long long row = a.rows[q0 + e];
+    return row >= a.row_offset && row - a.row_offset < a.tab_rows;   // (UINT64_MAX is outside every table)
+}
+
+// Request q = blockIdx.x.
+__global__ __launch_bounds__(kStageThreads) void ssd_list_kernel(SsdStageArgs a) {
+    __shared__ double s_buf[kStageChunk];
+    __shared__ uint32_t s_wcnt[2][2][kStageWaves];
+    __shared__ uint32_t s_red[kStageWaves];
+    __shared__ double s_stat[2];
+    const uint32_t q = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
+    const size_t q0 = (size_t)q * a.cap;
+    const uint32_t n = a.count ? min(a.count[q], a.cap) : a.cap;
+    uint32_t* map = a.map + q0;
+    uint32_t* inv = a.out_quality ? a.inv + q0 : nullptr;
+
+    // 1. the gates: Condition, abort_run_cnt against the number of real entries
+    bool gated = a.enable && a.enable[q] == 0;
+    if (!gated && a.abort_cnt > 0) {
+        uint32_t mine = 0, e;
+        for (uint32_t j = tid; j < n; j += kStageThreads) mine += stage_entry(a, q0, j, n, &e) ? 1u : 0u;
+        gated = stage_block_sum(mine, s_red) <= a.abort_cnt;
+    }
+    const uint32_t src_mask = (gated || !a.source) ? 0u : a.src_mask;
+
+    // 2. the split: ranks among `selected` and among `backup`
+    if (inv) for (uint32_t p = tid; p < a.cap; p += kStageThreads) inv[p] = kStageNone;
+    __syncthreads();
+    uint32_t ns = 0, nb = 0, it = 0;
+    for (uint32_t c0 = 0; c0 < n; c0 += kStageThreads) {
+        uint32_t elem = 0;
+        const bool real = stage_entry(a, q0, c0 + tid, n, &elem);
+        bool bak = false;
+        if (real && src_mask) {
+            const uint32_t src = a.source[q0 + elem];
+            bak = src < 32u && ((src_mask >> src) & 1u) != 0;
+        }
+        const bool sel = real && !bak;
+        const unsigned long long ms = __ballot(sel), mb = __ballot(bak);
+        uint32_t(*wc)[kStageWaves] = s_wcnt[it & 1u];
+        ++it;
+        if (lane == 0) { wc[0][wave] = (uint32_t)__popcll(ms); wc[1][wave] = (uint32_t)__popcll(mb); }
+        __syncthreads();
+        uint32_t below_s = 0, all_s = 0, below_b = 0, all_b = 0;
+#pragma unroll
+        for (uint32_t w = 0; w < kStageWaves; ++w) {
+            const uint32_t cs = wc[0][w], cb = wc[1][w];
+            below_s += w < wave ? cs : 0u;
+            all_s += cs;
+            below_b += w < wave ? cb : 0u;
+            all_b += cb;
+        }
+        const unsigned long long lt = (1ull << lane) - 1ull;
+        if (sel) {
+            const uint32_t r = ns + below_s + (uint32_t)__popcll(ms & lt);      // (r < cap: ranks of distinct list entries)
+            map[r] = elem;
+            if (inv) inv[elem] = r;
+        }
+        if (bak) map[a.cap - 1u - (nb + below_b + (uint32_t)__popcll(mb & lt))] = elem;
+        ns += all_s;
+        nb += all_b;
+    }
+    __syncthreads();                                                 // the map is read below by other lanes than wrote it
+
+    // 3. and 4.: gamma, the cuts
+    uint32_t len = ns, state = kStageUnchanged;
+    const double* score = a.score + q0;
+    if (!gated && a.gamma != 0.0 && ns > 0) {
+        state = kStageRerank;
+        if ((a.cand_count > 0 || a.min_pct > 0.0) && len > a.topn) {
+            if (a.cand_count > 0) len = min(len, max(a.topn, a.cand_count));
+            if (a.min_pct > 0.0 && len > a.topn) {
+                const double top = score[map[0]];
+                uint32_t first = len;
+                for (uint32_t idx = a.topn + tid; idx < len; idx += kStageThreads)
+                    if (score[map[idx]] / top < a.min_pct) { first = idx; break; }      // (a NaN quotient does not cut)
+                len = stage_block_min(first, s_red);
+            }
+        }
+        // 5. the normalisation (len <= n_max by the host's bound)
+        if (a.mode == 1) {
+            double sum = 0.0;
+            for (uint32_t c0 = 0; c0 < len; c0 += kStageChunk) {
+                const uint32_t m = min(kStageChunk, len - c0);
+                for (uint32_t i = tid; i < m; i += kStageThreads) s_buf[i] = score[map[c0 + i]];
+                __syncthreads();
+                if (tid == 0)
+                    for (uint32_t i = 0; i < m; ++i) sum = __dadd_rn(sum, s_buf[i]);
+                __syncthreads();
+            }
+            if (tid == 0) s_stat[0] = sum / (double)len;
+            __syncthreads();
+            const double mean = s_stat[0];
+            double ss = 0.0, comp = 0.0;
+            for (uint32_t c0 = 0; c0 < len; c0 += kStageChunk) {
+                const uint32_t m = min(kStageChunk, len - c0);
+                for (uint32_t i = tid; i < m; i += kStageThreads) s_buf[i] = score[map[c0 + i]];
+                __syncthreads();
+                if (tid == 0)
+                    for (uint32_t i = 0; i < m; ++i) {
+                        const double d = __dsub_rn(s_buf[i], mean);
+                        ss = __dadd_rn(ss, __dmul_rn(d, d));
+                        comp = __dadd_rn(comp, d);
+                    }
+                __syncthreads();
+            }
+            if (tid == 0) s_stat[1] = __dsub_rn(ss, __dmul_rn(comp, comp) / (double)len) / (double)len;
+            __syncthreads();
+            const double variance = s_stat[1];
+            if (mean == 0.0 || variance == 0.0) state = kStageUnchanged;
+            else {
+                const double sd = sqrt(variance);
+                for (uint32_t i = tid; i < len; i += kStageThreads) a.qual[(size_t)q * a.n_max + i] = __dsub_rn(score[map[i]], mean) / sd;
+            }
+        } else if (a.mode == 2) {
+            const double mn = score[map[len - 1u]], span = __dsub_rn(score[map[0]], mn);
+            if (span == 0.0) state = kStageUnchanged;
+            else {
+                const double eps = 1e-6;
+                for (uint32_t i = tid; i < len; i += kStageThreads)
+                    a.qual[(size_t)q * a.n_max + i] = __dadd_rn(__dmul_rn(__dsub_rn(score[map[i]], mn) / span, 1 - eps), eps);
+            }
+        } else {
+            for (uint32_t i = tid; i < len; i += kStageThreads) a.qual[(size_t)q * a.n_max + i] = score[map[i]];
+        }
+    }
+    // what the grid kernel and the epilogue read: rows behind n_q are row 0, so that ssd_prepare_kernel stays inside the table
+    const uint32_t n_q = state == kStageRerank ? len : 0u;
+    for (uint32_t i = tid; i < a.n_max; i += kStageThreads) {
+        a.cand[(size_t)q * a.n_max + i] = i < n_q ? (uint32_t)(a.rows[q0 + map[i]] - a.row_offset) : 0u;
+        if (i >= n_q) a.qual[(size_t)q * a.n_max + i] = 0.0;
+    }
+    if (tid == 0) {
+        const uint32_t T_q = min(len, a.topn);
+        a.hdr[q * 4u + 0] = len;
+        a.hdr[q * 4u + 1] = T_q;
+        a.hdr[q * 4u + 2] = state;
+        a.hdr[q * 4u + 3] = nb;
+        a.n_req[q] = n_q;
+        a.t_req[q] = state == kStageRerank ? T_q : 0u;
+    }
+}
+
+// 7. Request blockIdx.y, output slot (and input position) blockIdx.x * 256 + threadIdx.x.
+__global__ __launch_bounds__(256) void ssd_epilogue_kernel(SsdStageArgs a) {
+    const uint32_t q = blockIdx.y, o = blockIdx.x * 256u + threadIdx.x;
+    if (o >= a.cap) return;
+    const size_t q0 = (size_t)q * a.cap;
+    const uint32_t len = a.hdr[q * 4u + 0], T_q = a.hdr[q * 4u + 1], state = a.hdr[q * 4u + 2], nb = a.hdr[q * 4u + 3];
+    const uint32_t* map = a.map + q0;
+    const uint32_t head = state == kStageRerank ? T_q : len;
+    uint32_t pos = kStageNone;
+    if (o < head) {
+        if (state == kStageRerank) {
+            const uint32_t pk = a.picks[(size_t)q * a.T + o];
+            if (pk < len) pos = map[pk];
+        } else {
+            pos = map[o];
+        }
+    } else if (o - head < nb) {
+        pos = map[a.cap - 1u - (o - head)];
+    }
+    a.out_pos[q0 + o] = pos;
+    if (a.out_rows) a.out_rows[q0 + o] = pos != kStageNone ? a.rows[q0 + pos] : ~0ull;
+    if (a.out_quality) {
+        const uint32_t r = a.inv[q0 + o];
+        const bool has = state == kStageRerank && a.mode != 0 && r < len;
+        a.out_quality[q0 + o] = has ? a.qual[(size_t)q * a.n_max + r] : __longlong_as_double(0x7FF8000000000000ll);
+    }
+    if (o == 0) a.out_count[q] = head + nb;
+}
+
 }  // namespace pg
 
 extern "C" {
@@ -721,6 +993,73 @@ int pg_ssd_emb(pg_ctx* ctx, const float* emb, uint32_t dim, const double* rel, u
     }
     return pg::ssd_one(ctx, nullptr, nullptr, emb, dim, rel, n, gamma, topn, window, normalize_emb, ensure_pos_similarity,
                        norm_quality_score, use_ssd_star, out_idx, out_count, out_quality);
+}
+
+int pg_ssd_sort_dev(pg_ctx* ctx, const pg_table* t, uint32_t nq, uint32_t cap, const uint32_t* d_order, const uint64_t* d_rows,
+                    const double* d_score, const uint8_t* d_source, const uint32_t* d_count, const uint8_t* d_enable, double gamma,
+                    uint32_t topn, uint32_t window, int normalize_emb, int ensure_pos_similarity, int norm_quality_score,
+                    int use_ssd_star, uint32_t candidate_count, double min_score_percent, uint32_t abort_run_cnt,
+                    uint32_t filter_source_mask, uint32_t* d_out_pos, uint32_t* d_out_count, uint64_t* d_out_rows,
+                    double* d_out_quality) {
+    PG_REQUIRE(ctx && t && d_rows && d_score && d_out_pos && d_out_count, "pg_ssd_sort_dev: NULL argument");
+    PG_REQUIRE(nq >= 1 && cap >= 1, "pg_ssd_sort_dev: nq and cap must be at least 1");
+    PG_REQUIRE(topn >= 1, "pg_ssd_sort_dev: topn (ctx.Size) must be at least 1");
+    PG_REQUIRE(norm_quality_score >= 0 && norm_quality_score <= 2, "pg_ssd_sort_dev: norm_quality_score must be 0, 1 or 2");
+    PG_REQUIRE((const void*)d_out_pos != (const void*)d_order && (const void*)d_out_rows != (const void*)d_rows &&
+                   (const void*)d_out_quality != (const void*)d_score, "pg_ssd_sort_dev: an output is its own input (no output may overlap an input)");
+    if (window <= 1) window = 5;                          // ssd_sort.go:356-359
+    const uint32_t d1 = t->dim + (ensure_pos_similarity ? 1u : 0u);
+    const uint32_t n_max = candidate_count > 0 ? std::min(cap, std::max(topn, candidate_count)) : cap;
+    if (nq > PG_SSD_STAGE_MAX_NQ || cap > PG_SSD_STAGE_MAX_CAP) {
+        pg::set_error("pg_ssd_sort_dev: nq=%u / cap=%u unsupported (at most %u requests of %u entries)", nq, cap, PG_SSD_STAGE_MAX_NQ, PG_SSD_STAGE_MAX_CAP);
+        return PG_ERR_UNSUPPORTED;
+    }
+    if (n_max > PG_SSD_STAGE_MAX_N) {
+        pg::set_error("pg_ssd_sort_dev: a request may re-rank up to %u entries (cap %u, topn %u, candidate_count %u): at most %u — set candidate_count",
+                      n_max, cap, topn, candidate_count, PG_SSD_STAGE_MAX_N);
+        return PG_ERR_UNSUPPORTED;
+    }
+    if (!pg::ssd_batchable(d1, window)) {
+        pg::set_error("pg_ssd_sort_dev: dim %u%s / window %u: not a batchable shape (d1 64 / 65 / 128 / 129, window <= 16; pg_ssd serves it per request)",
+                      t->dim, ensure_pos_similarity ? " + 1" : "", window);
+        return PG_ERR_UNSUPPORTED;
+    }
+    if (t->d_row_map) {
+        pg::set_error("pg_ssd_sort_dev: the table is a filtered view (pg_table_view_create) — views serve the recall calls only");
+        return PG_ERR_UNSUPPORTED;
+    }
+    if (t->rows >= (1ull << 32)) {
+        pg::set_error("pg_ssd_sort_dev: tables of 2^32 rows and more are unsupported");
+        return PG_ERR_UNSUPPORTED;
+    }
+    std::lock_guard<std::mutex> g(ctx->mu);
+    PG_HIP(hipSetDevice(ctx->device));
+    pg::TableRead tr(t->rw);
+    pg::SsdStageArgs a{};
+    a.order = d_order; a.rows = d_rows; a.score = d_score; a.source = d_source; a.count = d_count; a.enable = d_enable;
+    a.cap = cap; a.n_max = n_max; a.topn = topn; a.T = std::min(n_max, topn); a.mode = (uint32_t)norm_quality_score;
+    a.cand_count = candidate_count; a.abort_cnt = abort_run_cnt; a.src_mask = filter_source_mask;
+    a.gamma = gamma; a.min_pct = min_score_percent;
+    a.row_offset = t->row_offset; a.tab_rows = t->rows;
+    a.out_pos = d_out_pos; a.out_count = d_out_count; a.out_rows = d_out_rows; a.out_quality = d_out_quality;
+    int rc;
+    if ((rc = pg::scratch_carve(ctx, pg::kSlotSsdStage, [&](pg::Carve& c) {
+            a.hdr = c.take<uint32_t>((size_t)nq * 4);
+            a.n_req = c.take<uint32_t>(nq);
+            a.t_req = c.take<uint32_t>(nq);
+            a.map = c.take<uint32_t>((size_t)nq * cap);
+            a.inv = c.take<uint32_t>(d_out_quality ? (size_t)nq * cap : 0);
+            a.cand = c.take<uint32_t>((size_t)nq * n_max);
+            a.qual = c.take<double>((size_t)nq * n_max);
+            a.picks = c.take<uint32_t>((size_t)nq * a.T);
+        }))) return rc;
+    pg::ssd_list_kernel<<<nq, pg::kStageThreads, 0, ctx->stream>>>(a);
+    PG_HIP(hipGetLastError());
+    if ((rc = pg::ssd_run_rows_locked(ctx, t->d, (uint32_t)t->rows, t->dim, a.cand, a.qual, nq, n_max, gamma, a.T, window, normalize_emb,
+                                      ensure_pos_similarity, use_ssd_star, a.picks, a.n_req, a.t_req))) return rc;
+    pg::ssd_epilogue_kernel<<<dim3((cap + 255) / 256, nq), 256, 0, ctx->stream>>>(a);
+    PG_HIP(hipGetLastError());
+    return PG_OK;
 }
 
 }  // extern "C"

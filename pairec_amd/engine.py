@@ -1067,6 +1067,26 @@ class Context:
                                       C.byref(cnt)))
         return out, cnt.value
 
+    # ---- SSDSort: candidate lists in, re-ranked page out ------------------------------------------------
+    def ssd_sort_dev(self, table, nq: int, cap: int, d_order, d_rows, d_score, d_source, d_count, d_enable, gamma: float, topn: int,
+                     window: int, d_out_pos, d_out_count, d_out_rows=0, d_out_quality=0, normalize_emb: bool = True,
+                     ensure_pos_similarity: bool = True, norm_quality_score: int = 0, use_ssd_star: bool = False,
+                     candidate_count: int = 0, min_score_percent: float = 0.0, abort_run_cnt: int = 0, filter_source_mask: int = 0):
+        """pg_ssd_sort_dev: SSDSort.Sort for nq requests on device arrays.  Every d_* is a torch tensor (anything with
+        .data_ptr()) or a raw device address (0 / None = absent): d_order [nq][cap] u32, d_rows [nq][cap] u64, d_score [nq][cap]
+        f64, d_source [nq][cap] u8, d_count [nq] u32, d_enable [nq] u8; outputs d_out_pos [nq][cap] u32, d_out_count [nq] u32,
+        optional d_out_rows [nq][cap] u64 and d_out_quality [nq][cap] f64 (by input position).  Enqueued on the context's stream:
+        synchronize() before reading.  Returns the outputs that were given, (pos, count[, rows][, quality])."""
+        def v(p):
+            return C.c_void_p((p.data_ptr() if hasattr(p, "data_ptr") else p) or None)
+        _lib.check(self.L.pg_ssd_sort_dev(self.h, getattr(table, "h", table), nq, cap, v(d_order), v(d_rows), v(d_score), v(d_source), v(d_count),
+                                          v(d_enable), float(gamma), int(topn), int(window), int(normalize_emb), int(ensure_pos_similarity),
+                                          int(norm_quality_score), int(use_ssd_star), int(candidate_count), float(min_score_percent),
+                                          int(abort_run_cnt), int(filter_source_mask) & 0xFFFFFFFF, v(d_out_pos), v(d_out_count), v(d_out_rows),
+                                          v(d_out_quality)))
+        absent = lambda p: p is None or (isinstance(p, int) and p == 0)              # noqa: E731
+        return tuple(p for p in (d_out_pos, d_out_count, d_out_rows, d_out_quality) if not absent(p))
+
     # ---- sort / expr (context-level ops) ----------------------------------------------------
     def sort_scores(self, scores: np.ndarray, seg_offsets: Optional[Sequence[int]] = None,
                     descending: bool = True) -> np.ndarray:
