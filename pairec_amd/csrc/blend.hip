@@ -395,32 +395,24 @@ int blend_check_conf(const pg_blend_conf* c, uint32_t cap, uint32_t* out_cap, co
     return PG_OK;
 }
 
-// the checks both entry points share: the conf, nq, the pairs of optional arrays, what a snake needs of them
-int blend_check_call(const pg_blend_conf* c, uint32_t nq, uint32_t cap, const void* rows, const void* score, const void* source,
-                     const void* planes_f64, uint32_t n_f64, const void* mask, const void* planes_f32, uint32_t n_f32, const void* out_rows,
-                     const void* out_score, const void* out_source, const void* out_planes_f64, const void* out_mask,
-                     const void* out_planes_f32, const void* out_count, uint32_t* out_cap, const char* who) {
-    PG_REQUIRE(rows && score && out_rows && out_score && out_count, "%s: NULL argument", who);
-    PG_REQUIRE(nq >= 1 && nq <= (uint32_t)kMaxQueries, "%s: nq=%u must be in [1,%d]", who, nq, kMaxQueries);
+// the checks both entry points share, in the order they fire: the pointers, nq, the conf, the pairs of optional arrays, what a
+// snake needs of them (an output may share memory with its input: the blend does not ask)
+int blend_check_call(const pg_blend_conf* c, uint32_t nq, uint32_t cap, const CandCall& l, uint32_t* out_cap, const char* who) {
     int rc;
-    if ((rc = blend_check_conf(c, cap, out_cap, who))) return rc;
-    if ((rc = cand_lists_check(who, source, planes_f64, n_f64, mask, planes_f32, n_f32, out_source, out_planes_f64, out_mask, out_planes_f32,
-                               kBlendMaxPlanes)))
+    if ((rc = cand_call_required(l, true, who)) || (rc = cand_check_nq(nq, who)) || (rc = blend_check_conf(c, cap, out_cap, who)) ||
+        (rc = cand_lists_check(l, kBlendMaxPlanes, who)))
         return rc;
     if (c->mode != PG_BLEND_FAIR) {
-        PG_REQUIRE(source || c->n_entries == 1, "%s: a snake that names more than one source needs d_source", who);
-        if (mask) {
+        PG_REQUIRE(l.source || c->n_entries == 1, "%s: a snake that names more than one source needs d_source", who);
+        if (l.source_mask) {
             uint32_t need = 0;
             for (uint32_t i = 0; i < c->n_entries; ++i) need = std::max(need, (uint32_t)c->source[i] + 1u);
-            PG_REQUIRE(planes_f64 && n_f64 >= need,
+            PG_REQUIRE(l.planes_f64 && l.n_f64 >= need,
                        "%s: a source mask needs the per-recall score planes of every named source (n_f64 >= %u)", who, need);
         }
     }
     return PG_OK;
 }
-
-// pg_sort_scores_dev's order on the host: descending, -0.0 equal to +0.0, NaN last, ties by input position
-inline bool blend_before(double x, double y) { return x == x && (y != y || x > y); }
 
 // one request of pg_candidates_blend_host → the input positions kept, with the entry (SNAKE) each was picked through
 struct BlendPick {
@@ -439,7 +431,7 @@ void blend_request_host(const pg_blend_conf& c, uint32_t cap, const uint64_t* ro
         for (uint32_t p = 0; p < cap; ++p)
             if (src_of(p) != kBlendNone) real.push_back(p);
         const size_t retain = std::min<size_t>(c.retain_num, real.size());
-        std::stable_sort(real.begin(), real.end(), [&](uint32_t x, uint32_t y) { return blend_before(score[x], score[y]); });
+        std::stable_sort(real.begin(), real.end(), [&](uint32_t x, uint32_t y) { return cand_before(score[x], score[y]); });
         std::vector<uint32_t> by[kBlendMaxSources];
         size_t at[kBlendMaxSources] = {0};
         std::vector<uint32_t> names;
@@ -476,7 +468,7 @@ void blend_request_host(const pg_blend_conf& c, uint32_t cap, const uint64_t* ro
                 lists[i].push_back(p);
             }
         }
-        std::stable_sort(lists[i].begin(), lists[i].end(), [&](uint32_t x, uint32_t y) { return blend_before(key[x], key[y]); });
+        std::stable_sort(lists[i].begin(), lists[i].end(), [&](uint32_t x, uint32_t y) { return cand_before(key[x], key[y]); });
     }
     std::vector<bool> taken(cap, false);
     size_t cur[kBlendMaxSources] = {0};
@@ -563,16 +555,14 @@ int pg_candidates_blend_dev(pg_ctx* ctx, const pg_blend_conf* conf, uint32_t nq,
                             double* d_out_score, uint8_t* d_out_source, double* d_out_planes_f64, uint32_t* d_out_source_mask,
                             float* d_out_planes_f32, uint32_t* d_out_count) {
     PG_REQUIRE(ctx, "pg_candidates_blend_dev: NULL argument");
+    const pg::CandCall l{d_rows, d_score, d_source, d_count, d_planes_f64, n_f64, d_source_mask, d_planes_f32, n_f32, d_out_rows, d_out_score,
+                         d_out_source, d_out_planes_f64, d_out_source_mask, d_out_planes_f32, d_out_count};
     uint32_t out_cap = 0;
     int rc;
-    if ((rc = pg::blend_check_call(conf, nq, cap, d_rows, d_score, d_source, d_planes_f64, n_f64, d_source_mask, d_planes_f32, n_f32,
-                                   d_out_rows, d_out_score, d_out_source, d_out_planes_f64, d_out_source_mask, d_out_planes_f32,
-                                   d_out_count, &out_cap, "pg_candidates_blend_dev")))
-        return rc;
+    if ((rc = pg::blend_check_call(conf, nq, cap, l, &out_cap, "pg_candidates_blend_dev"))) return rc;
     pg::CandIn in;
     pg::CandOut out;
-    pg::cand_lists_bind(nq, cap, out_cap, d_rows, d_score, d_source, d_count, d_planes_f64, n_f64, d_source_mask, d_planes_f32, n_f32,
-                        d_out_rows, d_out_score, d_out_source, d_out_planes_f64, d_out_source_mask, d_out_planes_f32, d_out_count, &in, &out);
+    pg::cand_lists_bind(l, nq, cap, out_cap, &in, &out);
     std::lock_guard<std::mutex> g(ctx->mu);
     PG_HIP(hipSetDevice(ctx->device));
     return pg::candidates_blend_locked(ctx, conf, in, out);
@@ -583,16 +573,14 @@ int pg_candidates_blend_host(const pg_blend_conf* conf, uint32_t nq, uint32_t ca
                              const uint32_t* source_mask, const float* planes_f32, uint32_t n_f32, uint64_t* out_rows, double* out_score,
                              uint8_t* out_source, double* out_planes_f64, uint32_t* out_source_mask, float* out_planes_f32,
                              uint32_t* out_count) {
+    const pg::CandCall l{rows, score, source, count, planes_f64, n_f64, source_mask, planes_f32, n_f32, out_rows, out_score,
+                         out_source, out_planes_f64, out_source_mask, out_planes_f32, out_count};
     uint32_t out_cap = 0;
     int rc;
-    if ((rc = pg::blend_check_call(conf, nq, cap, rows, score, source, planes_f64, n_f64, source_mask, planes_f32, n_f32, out_rows,
-                                   out_score, out_source, out_planes_f64, out_source_mask, out_planes_f32, out_count, &out_cap,
-                                   "pg_candidates_blend_host")))
-        return rc;
+    if ((rc = pg::blend_check_call(conf, nq, cap, l, &out_cap, "pg_candidates_blend_host"))) return rc;
     pg::CandIn in;
     pg::CandOut out;
-    pg::cand_lists_bind(nq, cap, out_cap, rows, score, source, count, planes_f64, n_f64, source_mask, planes_f32, n_f32, out_rows, out_score,
-                        out_source, out_planes_f64, out_source_mask, out_planes_f32, out_count, &in, &out);
+    pg::cand_lists_bind(l, nq, cap, out_cap, &in, &out);
     std::vector<pg::BlendPick> picks;
     for (uint32_t q = 0; q < nq; ++q) {
         const size_t in0 = (size_t)q * cap, out0 = (size_t)q * out_cap;

@@ -143,7 +143,7 @@ __global__ __launch_bounds__(kCcMaskThreads) void classcut_masks_kernel(CcProgra
     if (pos < n_valid && row != kCandPad) {
         CondItem item;
         cond_load(p, row, &item);
-        m = cc_classes(p, item, cond_bits_f64(score[i]), source ? (uint32_t)source[i] : 0xFFu);
+        m = cc_classes(p, item, cand_bits_f64(score[i]), source ? (uint32_t)source[i] : 0xFFu);
     }
     out[i] = (uint8_t)m;
 }
@@ -236,11 +236,7 @@ struct pg_classcut {
     std::vector<double> lists;
     std::vector<pg::Instr> progs;
     bool reads_source = false;                    // an expression reads recall_name
-    // the device table (lists, programs): uploaded at the first device call, owned until pg_classcut_free
-    std::mutex table_mu;                          // the upload below: contexts on one device may share a set
-    int device = -1;
-    void* d_table = nullptr;
-    size_t progs_off = 0;
+    pg::SetTable table;                           // lists | programs
 };
 
 namespace pg {
@@ -729,29 +725,8 @@ int classcut_bind_locked(pg_ctx* ctx, pg_classcut* c, const pg_features* fs, con
         return PG_ERR_INVALID;
     }
     if (fs && (rc = cond_resolve_columns(fs, c->col_names, c->col_dtypes, c->used, who, &declared))) return rc;
-    std::lock_guard<std::mutex> table_guard(c->table_mu);
-    if (c->device >= 0 && c->device != ctx->device) {
-        set_error("%s: the set's table lives on device %d, the context on device %d", who, c->device, ctx->device);
-        return PG_ERR_INVALID;
-    }
-    if (c->device < 0) {
-        // once per set: the in lists and the programs (the only synchronous step; every later call only launches)
-        const size_t lb = align_up(c->lists.size() * 8), pb = c->progs.size() * sizeof(Instr);
-        void* d = nullptr;
-        PG_HIP(hipMalloc(&d, lb + pb + 256));
-        hipError_t e = hipSuccess;
-        if (!c->lists.empty()) e = hipMemcpy(d, c->lists.data(), c->lists.size() * 8, hipMemcpyHostToDevice);
-        if (e == hipSuccess && pb) e = hipMemcpy((char*)d + lb, c->progs.data(), pb, hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            hipFree(d);
-            set_error("%s: uploading the set's table failed: %s", who, hipGetErrorString(e));
-            return PG_ERR_DEVICE;
-        }
-        c->d_table = d;
-        c->progs_off = lb;
-        c->device = ctx->device;
-    }
-    classcut_program(c, declared.data(), (const double*)c->d_table, (const Instr*)((const char*)c->d_table + c->progs_off), fs ? fs->rows : 0, p);
+    if ((rc = c->table.ensure(ctx, who, {{c->lists.data(), c->lists.size() * 8}, {c->progs.data(), c->progs.size() * sizeof(Instr)}}))) return rc;
+    classcut_program(c, declared.data(), c->table.part<double>(0), c->table.part<Instr>(1), fs ? fs->rows : 0, p);
     return PG_OK;
 }
 
@@ -800,9 +775,6 @@ int candidates_classcut_locked(pg_ctx* ctx, pg_classcut* c, const pg_features* f
     return PG_OK;
 }
 
-// pg_sort_scores_dev's order on the host: descending, -0.0 equal to +0.0, NaN last, ties by input position
-inline bool cc_before(double x, double y) { return x == x && (y != y || x > y); }
-
 // one request of pg_candidates_classcut_host: masks [cap] → the input positions kept, in output order
 void classcut_request_host(const pg_classcut* c, uint32_t cap, const uint64_t* rows, const double* score, uint32_t n_valid, const uint8_t* masks,
                            std::vector<uint32_t>* out) {
@@ -810,7 +782,7 @@ void classcut_request_host(const pg_classcut* c, uint32_t cap, const uint64_t* r
     std::vector<uint32_t> real;
     for (uint32_t p = 0; p < n_valid && p < cap; ++p)
         if (rows[p] != kCandPad) real.push_back(p);
-    std::stable_sort(real.begin(), real.end(), [&](uint32_t x, uint32_t y) { return cc_before(score[x], score[y]); });
+    std::stable_sort(real.begin(), real.end(), [&](uint32_t x, uint32_t y) { return cand_before(score[x], score[y]); });
     std::vector<uint8_t> taken(cap, 0);
     uint64_t acc = 0;
     for (size_t r = 0; r < c->rules.size(); ++r) {
@@ -847,14 +819,7 @@ int pg_classcut_compile(const pg_classcut_rule* rules, uint32_t n, const pg_cond
 
 int pg_classcut_free(pg_classcut* c) {
     if (!c) return PG_OK;
-    if (c->d_table) {
-        int cur = 0;
-        hipGetDevice(&cur);
-        hipSetDevice(c->device);
-        hipDeviceSynchronize();                     // (a launch that reads the table may still be in flight)
-        hipFree(c->d_table);
-        hipSetDevice(cur);
-    }
+    c->table.release();
     delete c;
     return PG_OK;
 }
@@ -898,14 +863,12 @@ int pg_candidates_classcut_host(const pg_classcut* c, uint32_t nq, uint32_t cap,
     if ((rc = pg::cond_check_shape(nq, cap, who))) return rc;
     const uint32_t out_cap = pg::classcut_width(c, cap);
     PG_REQUIRE(out_cap == 0 || (out_rows && out_score), "%s: NULL argument", who);
-    if ((rc = pg::cand_lists_check(who, source, planes_f64, n_f64, source_mask, planes_f32, n_f32, out_source, out_planes_f64, out_source_mask,
-                                   out_planes_f32, pg::kCandMaxPlanes)))
-        return rc;
-    if ((rc = pg::classcut_host_check(c, cols, source, who))) return rc;
+    const pg::CandCall l{rows, score, source, count, planes_f64, n_f64, source_mask, planes_f32, n_f32, out_rows, out_score,
+                         out_source, out_planes_f64, out_source_mask, out_planes_f32, out_count};
+    if ((rc = pg::cand_lists_check(l, pg::kCandMaxPlanes, who)) || (rc = pg::classcut_host_check(c, cols, source, who))) return rc;
     pg::CandIn in;
     pg::CandOut out;
-    pg::cand_lists_bind(nq, cap, out_cap, rows, score, source, count, planes_f64, n_f64, source_mask, planes_f32, n_f32, out_rows, out_score,
-                        out_source, out_planes_f64, out_source_mask, out_planes_f32, out_count, &in, &out);
+    pg::cand_lists_bind(l, nq, cap, out_cap, &in, &out);
     pg::CcProgram p;
     pg::classcut_program(c, nullptr, c->lists.data(), c->progs.data(), 0, &p);
     std::vector<uint8_t> masks(cap);
@@ -949,30 +912,22 @@ int pg_candidates_classcut_dev(pg_ctx* ctx, pg_classcut* c, const pg_features* f
                                double* d_out_score, uint8_t* d_out_source, double* d_out_planes_f64, uint32_t* d_out_source_mask,
                                float* d_out_planes_f32, uint32_t* d_out_count) {
     const char* who = "pg_candidates_classcut_dev";
-    PG_REQUIRE(ctx && c && d_rows && d_score && d_out_rows && d_out_score && d_out_count, "%s: NULL argument", who);
+    const pg::CandCall l{d_rows, d_score, d_source, d_count, d_planes_f64, n_f64, d_source_mask, d_planes_f32, n_f32, d_out_rows, d_out_score,
+                         d_out_source, d_out_planes_f64, d_out_source_mask, d_out_planes_f32, d_out_count};
     int rc;
-    if ((rc = pg::cond_check_shape(nq, cap, who))) return rc;
+    if ((rc = pg::cand_call_required(l, ctx && c, who)) || (rc = pg::cond_check_shape(nq, cap, who))) return rc;
     PG_REQUIRE(d_source || !c->reads_source, "%s: an expression reads recall_name: d_source is needed", who);
-    if ((rc = pg::cand_lists_check(who, d_source, d_planes_f64, n_f64, d_source_mask, d_planes_f32, n_f32, d_out_source, d_out_planes_f64,
-                                   d_out_source_mask, d_out_planes_f32, pg::kCandMaxPlanes)))
-        return rc;
     const uint32_t out_cap = pg::classcut_width(c, cap);
-    const size_t e = (size_t)nq * cap, o = (size_t)nq * out_cap;
-    PG_REQUIRE(!pg::cond_overlap(d_rows, e * 8, d_out_rows, o * 8) && !pg::cond_overlap(d_score, e * 8, d_out_score, o * 8) &&
-                   !pg::cond_overlap(d_source, e, d_out_source, o) && !pg::cond_overlap(d_source_mask, e * 4, d_out_source_mask, o * 4) &&
-                   !pg::cond_overlap(d_planes_f64, e * 8 * n_f64, d_out_planes_f64, o * 8 * n_f64) &&
-                   !pg::cond_overlap(d_planes_f32, e * 4 * n_f32, d_out_planes_f32, o * 4 * n_f32),
-               "%s: an output overlaps its input", who);
+    if ((rc = pg::cand_lists_check(l, pg::kCandMaxPlanes, who)) || (rc = pg::cand_call_apart(l, nq, cap, out_cap, who))) return rc;
     pg::CandIn in;
     pg::CandOut out;
-    pg::cand_lists_bind(nq, cap, out_cap, d_rows, d_score, d_source, d_count, d_planes_f64, n_f64, d_source_mask, d_planes_f32, n_f32, d_out_rows,
-                        d_out_score, d_out_source, d_out_planes_f64, d_out_source_mask, d_out_planes_f32, d_out_count, &in, &out);
+    pg::cand_lists_bind(l, nq, cap, out_cap, &in, &out);
     std::lock_guard<std::mutex> g(ctx->mu);
     PG_HIP(hipSetDevice(ctx->device));
     return pg::candidates_classcut_locked(ctx, c, fs, in, out, who);
 }
 
-// ---- one request on host arrays: upload, run, download, synchronise --------------------------------------------------------
+// ---- one request on host arrays (staged_run, cand_lists.hpp) ---------------------------------------------------------------------
 int pg_candidates_classcut(pg_ctx* ctx, pg_classcut* c, const pg_features* fs, uint32_t n, const uint64_t* rows, const double* score,
                            const uint8_t* source, uint64_t* out_rows, double* out_score, uint8_t* out_source, uint32_t* out_count) {
     const char* who = "pg_candidates_classcut";
@@ -993,38 +948,30 @@ int pg_candidates_classcut(pg_ctx* ctx, pg_classcut* c, const pg_features* fs, u
     PG_REQUIRE(out_rows && out_score, "%s: NULL argument", who);
     std::lock_guard<std::mutex> g(ctx->mu);
     PG_HIP(hipSetDevice(ctx->device));
-    uint64_t *d_rows, *d_orows; double *d_score, *d_oscore; uint8_t *d_src, *d_osrc; uint32_t* d_cnt;
-    if ((rc = pg::scratch_carve(ctx, pg::kSlotStaging, [&](pg::Carve& s) {
-            d_rows = s.take<uint64_t>(n);
-            d_score = s.take<double>(n);
-            d_orows = s.take<uint64_t>(out_cap);
-            d_oscore = s.take<double>(out_cap);
-            d_src = s.take<uint8_t>(n);
-            d_osrc = s.take<uint8_t>(out_cap);
-            d_cnt = s.take<uint32_t>(1);
-        }))) return rc;
-    PG_HIP(hipMemcpyAsync(d_rows, rows, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-    PG_HIP(hipMemcpyAsync(d_score, score, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-    if (source) PG_HIP(hipMemcpyAsync(d_src, source, n, hipMemcpyHostToDevice, ctx->stream));
-    pg::CandIn in{};
-    in.rows = d_rows;
-    in.score = reinterpret_cast<const unsigned long long*>(d_score);
-    in.source = source ? d_src : nullptr;
-    in.nq = 1;
-    in.cap = n;
-    pg::CandOut out{};
-    out.rows = d_orows;
-    out.score = reinterpret_cast<unsigned long long*>(d_oscore);
-    out.source = source ? d_osrc : nullptr;
-    out.count = d_cnt;
-    out.out_cap = out_cap;
-    if ((rc = pg::candidates_classcut_locked(ctx, c, fs, in, out, who))) return rc;
-    PG_HIP(hipMemcpyAsync(out_rows, d_orows, (size_t)out_cap * 8, hipMemcpyDeviceToHost, ctx->stream));
-    PG_HIP(hipMemcpyAsync(out_score, d_oscore, (size_t)out_cap * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (source) PG_HIP(hipMemcpyAsync(out_source, d_osrc, out_cap, hipMemcpyDeviceToHost, ctx->stream));
-    PG_HIP(hipMemcpyAsync(out_count, d_cnt, 4, hipMemcpyDeviceToHost, ctx->stream));
-    PG_HIP(hipStreamSynchronize(ctx->stream));
-    return PG_OK;
+    using pg::Staged;
+    enum { kRows, kScore, kOutRows, kOutScore, kSource, kOutSource, kCount };
+    Staged st[] = {{rows, (size_t)n * 8, Staged::kIn},
+                   {score, (size_t)n * 8, Staged::kIn},
+                   {out_rows, (size_t)out_cap * 8, Staged::kOut},
+                   {out_score, (size_t)out_cap * 8, Staged::kOut},
+                   {source, n, Staged::in_if(source)},
+                   {out_source, out_cap, Staged::out_if(source)},
+                   {out_count, 4, Staged::kOut}};
+    return pg::staged_run(ctx, pg::kSlotStaging, st, sizeof st / sizeof *st, false, [&] {
+        pg::CandIn in{};
+        in.rows = st[kRows].at<uint64_t>();
+        in.score = st[kScore].at<unsigned long long>();
+        in.source = source ? st[kSource].at<uint8_t>() : nullptr;
+        in.nq = 1;
+        in.cap = n;
+        pg::CandOut out{};
+        out.rows = st[kOutRows].at<uint64_t>();
+        out.score = st[kOutScore].at<unsigned long long>();
+        out.source = source ? st[kOutSource].at<uint8_t>() : nullptr;
+        out.count = st[kCount].at<uint32_t>();
+        out.out_cap = out_cap;
+        return pg::candidates_classcut_locked(ctx, c, fs, in, out, who);
+    });
 }
 
 }  // extern "C"

@@ -169,7 +169,7 @@ __global__ __launch_bounds__(kBoostThreads) void boost_scores_kernel(CondProgram
         u.present = user_present ? user_present[q] : 0u;
         CondItem item;
         cond_load(p, row, &item);
-        double s = cond_bits_f64(bits);
+        double s = cand_bits_f64(bits);
         last = cond_boost(p, filter_all != 0, item, u, &s);
         memcpy(&bits, &s, 8);                                            // (moves only: an untouched score keeps its bits)
     }
@@ -435,14 +435,7 @@ int pg_cond_compile(const pg_cond_rule* rules, uint32_t n_rules, const pg_cond_c
 
 int pg_cond_free(pg_cond* c) {
     if (!c) return PG_OK;
-    if (c->d_table) {
-        int cur = 0;
-        hipGetDevice(&cur);
-        hipSetDevice(c->device);
-        hipDeviceSynchronize();                     // (a launch that reads the table may still be in flight)
-        hipFree(c->d_table);
-        hipSetDevice(cur);
-    }
+    c->table.release();
     delete c;
     return PG_OK;
 }
@@ -497,24 +490,18 @@ int pg_item_state_filter_dev(pg_ctx* ctx, pg_cond* c, const pg_features* fs, uin
                              const uint64_t* d_user_vals, const uint32_t* d_user_present, uint64_t* d_out_rows, double* d_out_score,
                              uint8_t* d_out_source, double* d_out_planes_f64, uint32_t* d_out_source_mask, float* d_out_planes_f32,
                              uint32_t* d_out_count) {
-    PG_REQUIRE(ctx && c && fs && d_rows && d_score && d_out_rows && d_out_score && d_out_count, "pg_item_state_filter_dev: NULL argument");
-    PG_REQUIRE(!c->boost, "pg_item_state_filter_dev: the set was compiled as a boost rule set");
+    const char* who = "pg_item_state_filter_dev";
+    const pg::CandCall l{d_rows, d_score, d_source, d_count, d_planes_f64, n_f64, d_source_mask, d_planes_f32, n_f32, d_out_rows, d_out_score,
+                         d_out_source, d_out_planes_f64, d_out_source_mask, d_out_planes_f32, d_out_count};
     int rc;
-    if ((rc = pg::cond_check_shape(nq, cap, "pg_item_state_filter_dev"))) return rc;
-    PG_REQUIRE(c->slot_names.empty() || (d_user_vals && d_user_present), "pg_item_state_filter_dev: the set reads user properties: d_user_vals and d_user_present are needed");
-    if ((rc = pg::cand_lists_check("pg_item_state_filter_dev", d_source, d_planes_f64, n_f64, d_source_mask, d_planes_f32, n_f32, d_out_source,
-                                   d_out_planes_f64, d_out_source_mask, d_out_planes_f32, pg::kCandMaxPlanes)))
-        return rc;
-    const size_t e = (size_t)nq * cap;
-    PG_REQUIRE(!pg::cond_overlap(d_rows, e * 8, d_out_rows, e * 8) && !pg::cond_overlap(d_score, e * 8, d_out_score, e * 8) &&
-                   !pg::cond_overlap(d_source, e, d_out_source, e) && !pg::cond_overlap(d_source_mask, e * 4, d_out_source_mask, e * 4) &&
-                   !pg::cond_overlap(d_planes_f64, e * 8 * n_f64, d_out_planes_f64, e * 8 * n_f64) &&
-                   !pg::cond_overlap(d_planes_f32, e * 4 * n_f32, d_out_planes_f32, e * 4 * n_f32),
-               "pg_item_state_filter_dev: an output overlaps its input");
+    if ((rc = pg::cand_call_required(l, ctx && c && fs, who))) return rc;
+    PG_REQUIRE(!c->boost, "%s: the set was compiled as a boost rule set", who);
+    if ((rc = pg::cond_check_shape(nq, cap, who))) return rc;
+    PG_REQUIRE(c->slot_names.empty() || (d_user_vals && d_user_present), "%s: the set reads user properties: d_user_vals and d_user_present are needed", who);
+    if ((rc = pg::cand_lists_check(l, pg::kCandMaxPlanes, who)) || (rc = pg::cand_call_apart(l, nq, cap, cap, who))) return rc;
     pg::CandIn in;
     pg::CandOut out;
-    pg::cand_lists_bind(nq, cap, cap, d_rows, d_score, d_source, d_count, d_planes_f64, n_f64, d_source_mask, d_planes_f32, n_f32, d_out_rows,
-                        d_out_score, d_out_source, d_out_planes_f64, d_out_source_mask, d_out_planes_f32, d_out_count, &in, &out);
+    pg::cand_lists_bind(l, nq, cap, cap, &in, &out);
     std::lock_guard<std::mutex> g(ctx->mu);
     PG_HIP(hipSetDevice(ctx->device));
     return pg::item_state_filter_locked(ctx, c, fs, in, out, d_user_vals, d_user_present);
@@ -533,7 +520,7 @@ int pg_boost_scores_dev(pg_ctx* ctx, pg_cond* c, const pg_features* fs, uint32_t
     return pg::boost_scores_locked(ctx, c, fs, filter_all, nq, cap, d_rows, d_score, d_count, d_user_vals, d_user_present, d_out_score, d_out_rule);
 }
 
-// ---- one request on host arrays: upload, run, download, synchronise --------------------------------------------------------
+// ---- one request on host arrays (staged_run, cand_lists.hpp) ---------------------------------------------------------------------
 int pg_item_state_filter(pg_ctx* ctx, pg_cond* c, const pg_features* fs, uint32_t n, const uint64_t* rows, const double* score, const uint8_t* source,
                          const uint64_t* user_vals, uint32_t user_present, uint64_t* out_rows, double* out_score, uint8_t* out_source,
                          uint32_t* out_count) {
@@ -549,45 +536,28 @@ int pg_item_state_filter(pg_ctx* ctx, pg_cond* c, const pg_features* fs, uint32_
     if ((rc = pg::cond_check_shape(1, n, "pg_item_state_filter"))) return rc;
     std::lock_guard<std::mutex> g(ctx->mu);
     PG_HIP(hipSetDevice(ctx->device));
-    uint64_t *d_rows, *d_orows, *d_uv; double *d_score, *d_oscore; uint8_t *d_src, *d_osrc; uint32_t *d_up, *d_cnt;
-    if ((rc = pg::scratch_carve(ctx, pg::kSlotCond, [&](pg::Carve& s) {
-            d_rows = s.take<uint64_t>(n);
-            d_score = s.take<double>(n);
-            d_orows = s.take<uint64_t>(n);
-            d_oscore = s.take<double>(n);
-            d_src = s.take<uint8_t>(n);
-            d_osrc = s.take<uint8_t>(n);
-            d_uv = s.take<uint64_t>(pg::kCondMaxSlots);
-            d_up = s.take<uint32_t>(1);
-            d_cnt = s.take<uint32_t>(1);
-        }))) return rc;
     uint64_t uv[pg::kCondMaxSlots] = {0};
     if (user_vals) memcpy(uv, user_vals, c->slot_names.size() * 8);
-    PG_HIP(hipMemcpyAsync(d_rows, rows, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-    PG_HIP(hipMemcpyAsync(d_score, score, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-    if (source) PG_HIP(hipMemcpyAsync(d_src, source, n, hipMemcpyHostToDevice, ctx->stream));
-    PG_HIP(hipMemcpyAsync(d_uv, uv, sizeof uv, hipMemcpyHostToDevice, ctx->stream));
-    PG_HIP(hipMemcpyAsync(d_up, &user_present, 4, hipMemcpyHostToDevice, ctx->stream));
-    PG_HIP(hipStreamSynchronize(ctx->stream));       // (uv and user_present are this frame's)
-    pg::CandIn in{};
-    in.rows = d_rows;
-    in.score = reinterpret_cast<const unsigned long long*>(d_score);
-    in.source = source ? d_src : nullptr;
-    in.nq = 1;
-    in.cap = n;
-    pg::CandOut out{};
-    out.rows = d_orows;
-    out.score = reinterpret_cast<unsigned long long*>(d_oscore);
-    out.source = source ? d_osrc : nullptr;
-    out.count = d_cnt;
-    out.out_cap = n;
-    if ((rc = pg::item_state_filter_locked(ctx, c, fs, in, out, d_uv, d_up))) return rc;
-    PG_HIP(hipMemcpyAsync(out_rows, d_orows, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
-    PG_HIP(hipMemcpyAsync(out_score, d_oscore, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (source) PG_HIP(hipMemcpyAsync(out_source, d_osrc, n, hipMemcpyDeviceToHost, ctx->stream));
-    PG_HIP(hipMemcpyAsync(out_count, d_cnt, 4, hipMemcpyDeviceToHost, ctx->stream));
-    PG_HIP(hipStreamSynchronize(ctx->stream));
-    return PG_OK;
+    using pg::Staged;
+    enum { kRows, kScore, kOutRows, kOutScore, kSource, kOutSource, kUserVals, kUserPresent, kCount };
+    Staged st[] = {{rows, (size_t)n * 8, Staged::kIn},      {score, (size_t)n * 8, Staged::kIn},   {out_rows, (size_t)n * 8, Staged::kOut},
+                   {out_score, (size_t)n * 8, Staged::kOut}, {source, n, Staged::in_if(source)},    {out_source, n, Staged::out_if(source)},
+                   {uv, sizeof uv, Staged::kIn},             {&user_present, 4, Staged::kIn},       {out_count, 4, Staged::kOut}};
+    return pg::staged_run(ctx, pg::kSlotCond, st, sizeof st / sizeof *st, true /* uv and user_present are this frame's */, [&] {
+        pg::CandIn in{};
+        in.rows = st[kRows].at<uint64_t>();
+        in.score = st[kScore].at<unsigned long long>();
+        in.source = source ? st[kSource].at<uint8_t>() : nullptr;
+        in.nq = 1;
+        in.cap = n;
+        pg::CandOut out{};
+        out.rows = st[kOutRows].at<uint64_t>();
+        out.score = st[kOutScore].at<unsigned long long>();
+        out.source = source ? st[kOutSource].at<uint8_t>() : nullptr;
+        out.count = st[kCount].at<uint32_t>();
+        out.out_cap = n;
+        return pg::item_state_filter_locked(ctx, c, fs, in, out, st[kUserVals].at<uint64_t>(), st[kUserPresent].at<uint32_t>());
+    });
 }
 
 int pg_boost_scores(pg_ctx* ctx, pg_cond* c, uint32_t filter_all, uint32_t n, const uint8_t* item_in, const void* const* cols,
@@ -602,43 +572,34 @@ int pg_boost_scores(pg_ctx* ctx, pg_cond* c, uint32_t filter_all, uint32_t n, co
     PG_HIP(hipSetDevice(ctx->device));
     // the candidates' values become a store of n rows in scratch: candidate i reads row i, one outside the store row n
     const size_t nu = c->used.size();
-    uint64_t *d_rows, *d_uv; double *d_score, *d_oscore; uint8_t* d_rule; uint32_t* d_up;
-    std::vector<void*> d_col(nu);                     // a column of up to 8-byte values each
-    if ((rc = pg::scratch_carve(ctx, pg::kSlotCond, [&](pg::Carve& s) {
-            d_rows = s.take<uint64_t>(n);
-            d_score = s.take<double>(n);
-            d_oscore = s.take<double>(n);
-            d_rule = s.take<uint8_t>(n);
-            d_uv = s.take<uint64_t>(pg::kCondMaxSlots);
-            d_up = s.take<uint32_t>(1);
-            for (size_t k = 0; k < nu; ++k) d_col[k] = s.bytes((size_t)n * 8);
-        }))) return rc;
     std::vector<uint64_t> rows(n);
     for (uint32_t i = 0; i < n; ++i) rows[i] = !item_in || item_in[i] ? i : n;
     uint64_t uv[pg::kCondMaxSlots] = {0};
     if (user_vals) memcpy(uv, user_vals, c->slot_names.size() * 8);
-    pg_features tmp;                                  // (never owns: the columns point into scratch)
-    tmp.rows = n;
-    for (size_t k = 0; k < nu; ++k) {
-        const int d = c->used[k], dt = c->col_dtypes[(size_t)d];
-        const size_t es = dt == PG_F_I32 || dt == PG_F_F32 ? 4 : 8;
-        PG_HIP(hipMemcpyAsync(d_col[k], cols[d], (size_t)n * es, hipMemcpyHostToDevice, ctx->stream));
-        pg_features::Column col;
-        col.name = c->col_names[(size_t)d];
-        col.dtype = dt;
-        col.d = d_col[k];
-        tmp.cols.push_back(col);
+    using pg::Staged;
+    enum { kRows, kScore, kOutScore, kOutRule, kUserVals, kUserPresent, kCols };
+    std::vector<Staged> st = {{rows.data(), (size_t)n * 8, Staged::kIn},      {score, (size_t)n * 8, Staged::kIn},
+                              {out_score, (size_t)n * 8, Staged::kOut},       {out_rule, n, Staged::out_if(out_rule)},
+                              {uv, sizeof uv, Staged::kIn},                   {&user_present, 4, Staged::kIn}};
+    for (size_t k = 0; k < nu; ++k) {                 // a column of up to 8-byte values each
+        const int dt = c->col_dtypes[(size_t)c->used[k]];
+        st.push_back({cols[c->used[k]], (size_t)n * (dt == PG_F_I32 || dt == PG_F_F32 ? 4 : 8), Staged::kIn, (size_t)n * 8});
     }
-    PG_HIP(hipMemcpyAsync(d_rows, rows.data(), (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-    PG_HIP(hipMemcpyAsync(d_score, score, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-    PG_HIP(hipMemcpyAsync(d_uv, uv, sizeof uv, hipMemcpyHostToDevice, ctx->stream));
-    PG_HIP(hipMemcpyAsync(d_up, &user_present, 4, hipMemcpyHostToDevice, ctx->stream));
-    PG_HIP(hipStreamSynchronize(ctx->stream));       // (rows, uv and user_present are this frame's)
-    if ((rc = pg::boost_scores_locked(ctx, c, &tmp, filter_all, 1, n, d_rows, d_score, nullptr, d_uv, d_up, d_oscore, d_rule))) return rc;
-    PG_HIP(hipMemcpyAsync(out_score, d_oscore, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (out_rule) PG_HIP(hipMemcpyAsync(out_rule, d_rule, n, hipMemcpyDeviceToHost, ctx->stream));
-    PG_HIP(hipStreamSynchronize(ctx->stream));
-    return PG_OK;
+    return pg::staged_run(ctx, pg::kSlotCond, st.data(), st.size(), true /* rows, uv and user_present are this frame's */, [&] {
+        pg_features tmp;                              // (never owns: the columns point into scratch)
+        tmp.rows = n;
+        for (size_t k = 0; k < nu; ++k) {
+            const int d = c->used[k];
+            pg_features::Column col;
+            col.name = c->col_names[(size_t)d];
+            col.dtype = c->col_dtypes[(size_t)d];
+            col.d = st[kCols + k].dev;
+            tmp.cols.push_back(col);
+        }
+        return pg::boost_scores_locked(ctx, c, &tmp, filter_all, 1, n, st[kRows].at<uint64_t>(), st[kScore].at<double>(), nullptr,
+                                       st[kUserVals].at<uint64_t>(), st[kUserPresent].at<uint32_t>(), st[kOutScore].at<double>(),
+                                       st[kOutRule].at<uint8_t>());
+    });
 }
 
 }  // extern "C"

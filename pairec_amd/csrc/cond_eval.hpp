@@ -1,12 +1,17 @@
 // cond_eval.hpp — what the per-candidate evaluators over feature-store columns share: cond.hip (FilterParam terms and boost
 // expressions), classcut.hip (boolean class expressions, 4.1r) and mixsort.hip (a FilterParam rule per strategy,
-// 4.1t: the compiled pg_cond, its terms and rules and their bind to a store are stated in the second half of this file).  A candidate is its row; the lane loads the
-// raw bits of every referenced column before anything uses one and keeps them in registers; a column is read as float64(value).
+// 4.1t).  A candidate is its row; the lane loads the raw bits of every referenced column before anything uses one and keeps
+// them in registers; a column is read as float64(value).
+//
+// In this order: the candidate and its column reads; the by-name binding of a set's columns to a store; SetTable, the device
+// table every compiled set (pg_cond, pg_classcut, pg_mix) owns; FilterParam compiled — the terms and rules, the pg_cond object
+// and its bind to a store — which cond.hip and mixsort.hip walk.
 #pragma once
 #include "cand_lists.hpp"
 #include "expr_prog.hpp"
 
 #include <cstring>
+#include <initializer_list>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -38,11 +43,6 @@ __host__ __device__ __forceinline__ unsigned long long cond_pick(const unsigned 
     }
     return v;
 }
-__host__ __device__ __forceinline__ double cond_bits_f64(unsigned long long b) {
-    double d;
-    memcpy(&d, &b, 8);
-    return d;
-}
 // referenced column k as float64(value); P: a program with cols[kCondMaxCols]
 template <class P>
 __host__ __device__ __forceinline__ double cond_col_f64(const P& p, const CondItem& it, uint32_t k) {
@@ -56,7 +56,7 @@ __host__ __device__ __forceinline__ double cond_col_f64(const P& p, const CondIt
             memcpy(&f, &w, 4);
             return (double)f;
         }
-        default: return cond_bits_f64(b);
+        default: return cand_bits_f64(b);
     }
 }
 
@@ -122,16 +122,62 @@ inline int cond_check_shape(uint32_t nq, uint32_t cap, const char* who) {
     return PG_OK;
 }
 
-// [a, a + an) and [b, b + bn) share a byte
-inline bool cond_overlap(const void* a, size_t an, const void* b, size_t bn) {
-    if (!a || !b) return false;
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + bn && y < x + an;
-}
+// the device table of a compiled set: its lists and programs, uploaded at the first device call and owned until the set is freed
+struct SetTable {
+    struct Part { const void* host; size_t bytes; };
+    std::mutex mu;                                // the upload: contexts on one device may share a set
+    int device = -1;
+    void* d = nullptr;
+    size_t off[2] = {0, 0};                       // where each part begins (256-byte aligned)
+
+    // the parts are on the context's device after this; caller holds ctx->mu.  The first call of a set allocates and uploads
+    // (the only synchronous step; every later call only launches), a context on another device is refused.
+    int ensure(pg_ctx* ctx, const char* who, std::initializer_list<Part> parts) {
+        std::lock_guard<std::mutex> guard(mu);
+        if (device >= 0 && device != ctx->device) {
+            set_error("%s: the set's table lives on device %d, the context on device %d", who, device, ctx->device);
+            return PG_ERR_INVALID;
+        }
+        if (device >= 0) return PG_OK;
+        size_t end = 0, n = 0;
+        for (const Part& p : parts) {
+            off[n++] = end = align_up(end);
+            end += p.bytes;
+        }
+        void* t = nullptr;
+        PG_HIP(hipMalloc(&t, end + 256));
+        hipError_t e = hipSuccess;
+        n = 0;
+        for (const Part& p : parts) {
+            if (e == hipSuccess && p.bytes) e = hipMemcpy((char*)t + off[n], p.host, p.bytes, hipMemcpyHostToDevice);
+            ++n;
+        }
+        if (e != hipSuccess) {
+            hipFree(t);
+            set_error("%s: uploading the set's table failed: %s", who, hipGetErrorString(e));
+            return PG_ERR_DEVICE;
+        }
+        d = t;
+        device = ctx->device;
+        return PG_OK;
+    }
+    template <class T>
+    const T* part(size_t i) const { return (const T*)((const char*)d + off[i]); }
+    void release() {
+        if (!d) return;
+        int cur = 0;
+        hipGetDevice(&cur);
+        hipSetDevice(device);
+        hipDeviceSynchronize();                     // (a launch that reads the table may still be in flight)
+        hipFree(d);
+        hipSetDevice(cur);
+        d = nullptr;
+    }
+};
 
 
 // ---- module.FilterParam compiled: what cond.hip (filter, boost) and mixsort.hip (strategy membership) walk -------------------------
-constexpr uint32_t kCondMaxRules = 8, kCondMaxTerms = 8, kCondMaxSlots = 8, kCondMaxList = 64;      // (kCondMaxCols: cond_eval.hpp)
+constexpr uint32_t kCondMaxRules = 8, kCondMaxTerms = 8, kCondMaxSlots = 8, kCondMaxList = 64;      // (kCondMaxCols: above)
 constexpr uint32_t kCondMaxExprOps = 64, kCondMaxExprDepth = 8;
 static_assert(kCondMaxRules == PG_COND_MAX_RULES && kCondMaxTerms == PG_COND_MAX_TERMS &&
                   kCondMaxSlots == PG_COND_MAX_SLOTS && kCondMaxList == PG_COND_MAX_LIST && kCondMaxExprOps == PG_COND_MAX_EXPR_OPS &&
@@ -156,7 +202,7 @@ struct CondProgram {                              // what both kernels and the h
     uint64_t store_rows;
 };
 
-// the request's user slots (the candidate itself: CondItem, cond_eval.hpp)
+// the request's user slots (the candidate itself: CondItem, above)
 struct CondUser {
     const unsigned long long* vals;               // [kCondMaxSlots] bits: int64 or fp64 by the slot's type
     uint32_t present;
@@ -190,8 +236,8 @@ __host__ __device__ __forceinline__ bool cond_term(const CondProgram& p, const C
     if (t.rhs == PG_COND_RHS_USER && !((u.present >> t.rhs_idx) & 1u)) return t.op == PG_COND_NOT_EQUAL;
     if (t.rhs == PG_COND_RHS_ITEM && !it.item_in) return t.op == PG_COND_NOT_EQUAL || (t.op >= PG_COND_GREATER && is_float);
     if (is_float) {
-        const double l = t.user_left ? cond_bits_f64(u.vals[t.left]) : cond_col_f64(p, it, t.left);
-        const double r = t.rhs == PG_COND_RHS_USER ? cond_bits_f64(u.vals[t.rhs_idx])
+        const double l = t.user_left ? cand_bits_f64(u.vals[t.left]) : cond_col_f64(p, it, t.left);
+        const double r = t.rhs == PG_COND_RHS_USER ? cand_bits_f64(u.vals[t.rhs_idx])
                          : t.rhs == PG_COND_RHS_ITEM ? cond_col_f64(p, it, t.rhs_idx) : t.c.f;
         switch (t.op) {
             case PG_COND_GREATER: return l > r;
@@ -251,11 +297,7 @@ struct pg_cond {
     std::vector<pg::CondRule> rules;
     std::vector<long long> lists;
     std::vector<pg::Instr> progs;
-    // the device table (lists, programs): uploaded at the first device call, owned until pg_cond_free
-    std::mutex table_mu;                          // the upload below: contexts on one device may share a set
-    int device = -1;
-    void* d_table = nullptr;
-    size_t progs_off = 0;
+    pg::SetTable table;                           // lists | programs
 };
 
 namespace pg {
@@ -291,29 +333,8 @@ inline int cond_bind_locked(pg_ctx* ctx, pg_cond* c, const pg_features* fs, cons
     std::vector<const void*> declared;
     int rc;
     if ((rc = cond_resolve_columns(fs, c->col_names, c->col_dtypes, c->used, who, &declared))) return rc;
-    std::lock_guard<std::mutex> table_guard(c->table_mu);
-    if (c->device >= 0 && c->device != ctx->device) {
-        set_error("%s: the set's table lives on device %d, the context on device %d", who, c->device, ctx->device);
-        return PG_ERR_INVALID;
-    }
-    if (c->device < 0) {
-        // once per set: the in lists and the expression programs (the only synchronous step; every later call only launches)
-        const size_t lb = align_up(c->lists.size() * 8), pb = c->progs.size() * sizeof(Instr);
-        void* d = nullptr;
-        PG_HIP(hipMalloc(&d, lb + pb + 256));
-        hipError_t e = hipSuccess;
-        if (!c->lists.empty()) e = hipMemcpy(d, c->lists.data(), c->lists.size() * 8, hipMemcpyHostToDevice);
-        if (e == hipSuccess && pb) e = hipMemcpy((char*)d + lb, c->progs.data(), pb, hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            hipFree(d);
-            set_error("%s: uploading the set's table failed: %s", who, hipGetErrorString(e));
-            return PG_ERR_DEVICE;
-        }
-        c->d_table = d;
-        c->progs_off = lb;
-        c->device = ctx->device;
-    }
-    cond_program(c, declared.data(), (const long long*)c->d_table, (const Instr*)((const char*)c->d_table + c->progs_off), fs->rows, p);
+    if ((rc = c->table.ensure(ctx, who, {{c->lists.data(), c->lists.size() * 8}, {c->progs.data(), c->progs.size() * sizeof(Instr)}}))) return rc;
+    cond_program(c, declared.data(), c->table.part<long long>(0), c->table.part<Instr>(1), fs->rows, p);
     return PG_OK;
 }
 

@@ -21,7 +21,7 @@
 //   output   the result, the untaken entries in order (ballot ranks again), the set-aside entries, UINT32_MAX behind count.
 // The window counts and the keys live in context scratch, written by one lane and read by the workgroup's others only across
 // a __syncthreads: one workgroup stays on one compute unit, whose vector cache serves them all.
-#include "common.hpp"
+#include "cand_lists.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -712,18 +712,13 @@ int pg_diversity_rules(pg_ctx* ctx, const pg_div_config* cfg, uint32_t n, const 
     PG_REQUIRE(order && (dims || c.n_cols == 0), "pg_diversity_rules: NULL argument");
     std::lock_guard<std::mutex> g(ctx->mu);
     PG_HIP(hipSetDevice(ctx->device));
-    int64_t* d_dims; uint8_t* d_src; uint32_t* d_out;
-    if ((rc = pg::scratch_carve(ctx, pg::kSlotStaging, [&](pg::Carve& s) {
-            d_dims = s.take<int64_t>((size_t)c.n_cols * n);
-            d_src = s.take<uint8_t>(n);
-            d_out = s.take<uint32_t>(n);
-        }))) return rc;
-    if (c.n_cols) PG_HIP(hipMemcpyAsync(d_dims, dims, (size_t)c.n_cols * n * 8, hipMemcpyHostToDevice, ctx->stream));
-    if (source) PG_HIP(hipMemcpyAsync(d_src, source, n, hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = pg::div_launch_locked(ctx, c, 1, n, nullptr, d_dims, source ? d_src : nullptr, nullptr, d_out))) return rc;
-    PG_HIP(hipMemcpyAsync(order, d_out, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    PG_HIP(hipStreamSynchronize(ctx->stream));
-    return PG_OK;
+    using pg::Staged;
+    enum { kDims, kSource, kOrder };
+    Staged st[] = {{dims, (size_t)c.n_cols * n * 8, Staged::kIn}, {source, n, Staged::in_if(source)}, {order, (size_t)n * 4, Staged::kOut}};
+    return pg::staged_run(ctx, pg::kSlotStaging, st, sizeof st / sizeof *st, false, [&] {
+        return pg::div_launch_locked(ctx, c, 1, n, nullptr, st[kDims].at<int64_t>(), source ? st[kSource].at<uint8_t>() : nullptr, nullptr,
+                                     st[kOrder].at<uint32_t>());
+    });
 }
 
 }  // extern "C"

@@ -347,10 +347,7 @@ struct pg_mix {
     std::vector<int> col_dtypes;
     pg_cond* cond = nullptr;                          // the strategies' Conditions, one rule per strategy that has any (or nullptr)
     std::vector<int32_t> pos_table;
-    // the device table (configured positions): uploaded at the first device call, owned until pg_mix_free
-    std::mutex table_mu;
-    int device = -1;
-    void* d_table = nullptr;
+    pg::SetTable table;                               // the configured positions
     ~pg_mix() { pg_cond_free(cond); }
 };
 
@@ -516,25 +513,7 @@ int mix_sort_locked(pg_ctx* ctx, pg_mix* m, const pg_features* fs, uint32_t S, c
             o.pos_i64 = col->dtype == PG_F_I64;
         }
     }
-    {
-        std::lock_guard<std::mutex> table_guard(m->table_mu);
-        if (m->device >= 0 && m->device != ctx->device) return mix_refuse(PG_ERR_INVALID, who, "the set's table lives on device %d, the context on device %d", m->device, ctx->device);
-        if (m->device < 0) {
-            // once per set: the configured positions (the only synchronous step; every later call only launches)
-            void* d = nullptr;
-            PG_HIP(hipMalloc(&d, m->pos_table.size() * 4 + 256));
-            if (!m->pos_table.empty()) {
-                const hipError_t e = hipMemcpy(d, m->pos_table.data(), m->pos_table.size() * 4, hipMemcpyHostToDevice);
-                if (e != hipSuccess) {
-                    hipFree(d);
-                    set_error("%s: uploading the set's table failed: %s", who, hipGetErrorString(e));
-                    return PG_ERR_DEVICE;
-                }
-            }
-            m->d_table = d;
-            m->device = ctx->device;
-        }
-    }
+    if ((rc = m->table.ensure(ctx, who, {{m->pos_table.data(), m->pos_table.size() * 4}}))) return rc;
     a.n_st = (uint32_t)m->st.size();
     a.S = S;
     a.remain = m->remain;
@@ -548,7 +527,7 @@ int mix_sort_locked(pg_ctx* ctx, pg_mix* m, const pg_features* fs, uint32_t S, c
     a.seed = reinterpret_cast<const unsigned long long*>(d_seed);
     a.user_vals = reinterpret_cast<const unsigned long long*>(d_user_vals);
     a.user_present = d_user_present;
-    a.pos_table = (const int32_t*)m->d_table;
+    a.pos_table = m->table.part<int32_t>(0);
     if ((rc = scratch_carve(ctx, kSlotMix, [&](Carve& c) {
             a.mask = c.take<uint8_t>((size_t)nq * cap);
             a.taken = c.take<uint32_t>((size_t)nq * off);
@@ -642,14 +621,7 @@ int pg_mix_compile(const pg_mix_strategy* strategies, uint32_t n, const pg_cond_
 
 int pg_mix_free(pg_mix* m) {
     if (!m) return PG_OK;
-    if (m->d_table) {
-        int cur = 0;
-        hipGetDevice(&cur);
-        hipSetDevice(m->device);
-        hipDeviceSynchronize();                     // (a launch that reads the table may still be in flight)
-        hipFree(m->d_table);
-        hipSetDevice(cur);
-    }
+    m->table.release();
     delete m;
     return PG_OK;
 }
@@ -736,14 +708,14 @@ int pg_mix_sort_dev(pg_ctx* ctx, pg_mix* m, const pg_features* fs, uint32_t ctx_
     uint32_t S, number[pg::kMixMaxStrategies] = {0};
     if ((rc = pg::mix_check_call(m, nq, cap, d_source, d_user_vals, d_user_present, who))) return rc;
     if ((rc = pg::mix_numbers(m, ctx_size, who, &S, number))) return rc;
-    PG_REQUIRE(!pg::cond_overlap(d_order, (size_t)nq * cap * 4, d_out_order, (size_t)nq * cap * 4), "pg_mix_sort_dev: d_out_order overlaps d_order");
+    PG_REQUIRE(!pg::cand_overlap(d_order, (size_t)nq * cap * 4, d_out_order, (size_t)nq * cap * 4), "pg_mix_sort_dev: d_out_order overlaps d_order");
     std::lock_guard<std::mutex> g(ctx->mu);
     PG_HIP(hipSetDevice(ctx->device));
     return pg::mix_sort_locked(ctx, m, fs, S, number, nq, cap, d_rows, d_source, d_order, d_count, d_seed, d_user_vals, d_user_present, d_out_order,
                                d_out_count, who);
 }
 
-// ---- one request on host arrays: upload, run, download, synchronise --------------------------------------------------------
+// ---- one request on host arrays (staged_run, cand_lists.hpp) ---------------------------------------------------------------------
 int pg_mix_sort(pg_ctx* ctx, pg_mix* m, const pg_features* fs, uint32_t ctx_size, uint32_t n, const uint64_t* rows, const uint8_t* source,
                 const uint32_t* order, uint64_t seed, const uint64_t* user_vals, uint32_t user_present, uint32_t* out_order,
                 uint32_t* out_count) {
@@ -760,32 +732,23 @@ int pg_mix_sort(pg_ctx* ctx, pg_mix* m, const pg_features* fs, uint32_t ctx_size
     if ((rc = pg::mix_numbers(m, ctx_size, who, &S, number))) return rc;
     std::lock_guard<std::mutex> g(ctx->mu);
     PG_HIP(hipSetDevice(ctx->device));
-    uint64_t *d_rows, *d_uv, *d_seed; uint32_t *d_order, *d_out, *d_up, *d_cnt; uint8_t* d_src;
-    if ((rc = pg::scratch_carve(ctx, pg::kSlotStaging, [&](pg::Carve& s) {
-            d_rows = s.take<uint64_t>(n);
-            d_uv = s.take<uint64_t>(pg::kCondMaxSlots);
-            d_seed = s.take<uint64_t>(1);
-            d_order = s.take<uint32_t>(n);
-            d_out = s.take<uint32_t>(n);
-            d_up = s.take<uint32_t>(1);
-            d_cnt = s.take<uint32_t>(1);
-            d_src = s.take<uint8_t>(n);
-        }))) return rc;
     uint64_t uv[pg::kCondMaxSlots] = {0};
     if (user_vals) memcpy(uv, user_vals, (size_t)pg_mix_num_user_slots(m) * 8);
-    PG_HIP(hipMemcpyAsync(d_rows, rows, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-    if (source) PG_HIP(hipMemcpyAsync(d_src, source, n, hipMemcpyHostToDevice, ctx->stream));
-    if (order) PG_HIP(hipMemcpyAsync(d_order, order, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-    PG_HIP(hipMemcpyAsync(d_uv, uv, sizeof uv, hipMemcpyHostToDevice, ctx->stream));
-    PG_HIP(hipMemcpyAsync(d_seed, &seed, 8, hipMemcpyHostToDevice, ctx->stream));
-    PG_HIP(hipMemcpyAsync(d_up, &user_present, 4, hipMemcpyHostToDevice, ctx->stream));
-    PG_HIP(hipStreamSynchronize(ctx->stream));       // (uv, seed and user_present are this frame's)
-    if ((rc = pg::mix_sort_locked(ctx, m, fs, S, number, 1, n, d_rows, source ? d_src : nullptr, order ? d_order : nullptr, nullptr, d_seed, d_uv, d_up,
-                                  d_out, d_cnt, who))) return rc;
-    PG_HIP(hipMemcpyAsync(out_order, d_out, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    PG_HIP(hipMemcpyAsync(out_count, d_cnt, 4, hipMemcpyDeviceToHost, ctx->stream));
-    PG_HIP(hipStreamSynchronize(ctx->stream));
-    return PG_OK;
+    using pg::Staged;
+    enum { kRows, kUserVals, kSeed, kOrder, kOutOrder, kUserPresent, kCount, kSource };
+    Staged st[] = {{rows, (size_t)n * 8, Staged::kIn},
+                   {uv, sizeof uv, Staged::kIn},
+                   {&seed, 8, Staged::kIn},
+                   {order, (size_t)n * 4, Staged::in_if(order)},
+                   {out_order, (size_t)n * 4, Staged::kOut},
+                   {&user_present, 4, Staged::kIn},
+                   {out_count, 4, Staged::kOut},
+                   {source, n, Staged::in_if(source)}};
+    return pg::staged_run(ctx, pg::kSlotStaging, st, sizeof st / sizeof *st, true /* uv, seed and user_present are this frame's */, [&] {
+        return pg::mix_sort_locked(ctx, m, fs, S, number, 1, n, st[kRows].at<uint64_t>(), source ? st[kSource].at<uint8_t>() : nullptr,
+                                   order ? st[kOrder].at<uint32_t>() : nullptr, nullptr, st[kSeed].at<uint64_t>(), st[kUserVals].at<uint64_t>(),
+                                   st[kUserPresent].at<uint32_t>(), st[kOutOrder].at<uint32_t>(), st[kCount].at<uint32_t>(), who);
+    });
 }
 
 }  // extern "C"

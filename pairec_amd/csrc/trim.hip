@@ -239,19 +239,18 @@ int pg_candidates_trim_dev(pg_ctx* ctx, const pg_trim_rule* rules, uint32_t n_ru
                            uint32_t n_f64, const uint32_t* d_source_mask, const float* d_planes_f32, uint32_t n_f32, uint64_t* d_out_rows,
                            double* d_out_score, uint8_t* d_out_source, double* d_out_planes_f64, uint32_t* d_out_source_mask,
                            float* d_out_planes_f32, uint32_t* d_out_count) {
-    PG_REQUIRE(ctx && d_rows && d_score && d_out_rows && d_out_score && d_out_count, "pg_candidates_trim_dev: NULL argument");
-    PG_REQUIRE(nq >= 1 && nq <= (uint32_t)pg::kMaxQueries, "pg_candidates_trim_dev: nq=%u must be in [1,%d]", nq, pg::kMaxQueries);
+    const char* who = "pg_candidates_trim_dev";
+    const pg::CandCall l{d_rows, d_score, d_source, d_count, d_planes_f64, n_f64, d_source_mask, d_planes_f32, n_f32, d_out_rows, d_out_score,
+                         d_out_source, d_out_planes_f64, d_out_source_mask, d_out_planes_f32, d_out_count};
     uint32_t out_cap = 0;
     int rc;
-    if ((rc = pg::trim_check_rules(rules, n_rules, cap, &out_cap, "pg_candidates_trim_dev"))) return rc;
-    PG_REQUIRE(d_source || rules[0].source == PG_TRIM_ANY, "pg_candidates_trim_dev: rules that name sources need d_source");
-    if ((rc = pg::cand_lists_check("pg_candidates_trim_dev", d_source, d_planes_f64, n_f64, d_source_mask, d_planes_f32, n_f32, d_out_source,
-                                   d_out_planes_f64, d_out_source_mask, d_out_planes_f32, pg::kTrimMaxPlanes)))
+    if ((rc = pg::cand_call_required(l, ctx, who)) || (rc = pg::cand_check_nq(nq, who)) || (rc = pg::trim_check_rules(rules, n_rules, cap, &out_cap, who)))
         return rc;
+    PG_REQUIRE(d_source || rules[0].source == PG_TRIM_ANY, "%s: rules that name sources need d_source", who);
+    if ((rc = pg::cand_lists_check(l, pg::kTrimMaxPlanes, who))) return rc;
     pg::CandIn in;
     pg::CandOut out;
-    pg::cand_lists_bind(nq, cap, out_cap, d_rows, d_score, d_source, d_count, d_planes_f64, n_f64, d_source_mask, d_planes_f32, n_f32,
-                        d_out_rows, d_out_score, d_out_source, d_out_planes_f64, d_out_source_mask, d_out_planes_f32, d_out_count, &in, &out);
+    pg::cand_lists_bind(l, nq, cap, out_cap, &in, &out);
     std::lock_guard<std::mutex> g(ctx->mu);
     PG_HIP(hipSetDevice(ctx->device));
     return pg::candidates_trim_locked(ctx, rules, n_rules, in, out, nullptr);

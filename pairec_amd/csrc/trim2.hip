@@ -179,48 +179,21 @@ int trim2_check_rules(const pg_trim_rule* rules, uint32_t n_rules, uint32_t cap,
     return PG_OK;
 }
 
-// [a, a + an) and [b, b + bn) share a byte
-inline bool trim2_overlap(const void* a, size_t an, const void* b, size_t bn) {
-    if (!a || !b) return false;
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + bn && y < x + an;
-}
-
-// the checks both entry points share: the rules, nq, the pairs of optional arrays, what the mask needs, the overlaps
-int trim2_check_call(const pg_trim_rule* rules, uint32_t n_rules, uint32_t nq, uint32_t cap, const void* rows, const void* score,
-                     const void* source, const void* planes_f64, uint32_t n_f64, const void* mask, const void* planes_f32, uint32_t n_f32,
-                     const void* out_rows, const void* out_score, const void* out_source, const void* out_planes_f64, const void* out_mask,
-                     const void* out_planes_f32, const void* out_count, uint32_t* out_cap, const char* who) {
-    PG_REQUIRE(rows && score && out_rows && out_score && out_count, "%s: NULL argument", who);
-    PG_REQUIRE(nq >= 1 && nq <= (uint32_t)kMaxQueries, "%s: nq=%u must be in [1,%d]", who, nq, kMaxQueries);
+// the checks both entry points share, in the order they fire: the pointers, nq, the rules, the pairs of optional arrays, what
+// the rules and the mask need of them, the overlaps
+int trim2_check_call(const pg_trim_rule* rules, uint32_t n_rules, uint32_t nq, uint32_t cap, const CandCall& l, uint32_t* out_cap, const char* who) {
     int rc;
-    if ((rc = trim2_check_rules(rules, n_rules, cap, out_cap, who))) return rc;
-    if ((rc = cand_lists_check(who, source, planes_f64, n_f64, mask, planes_f32, n_f32, out_source, out_planes_f64, out_mask, out_planes_f32,
-                               kCandMaxPlanes)))
+    if ((rc = cand_call_required(l, true, who)) || (rc = cand_check_nq(nq, who)) || (rc = trim2_check_rules(rules, n_rules, cap, out_cap, who)) ||
+        (rc = cand_lists_check(l, kCandMaxPlanes, who)))
         return rc;
-    PG_REQUIRE(source || n_rules == 1, "%s: rules that name more than one source need d_source", who);
-    if (mask) {
+    PG_REQUIRE(l.source || n_rules == 1, "%s: rules that name more than one source need d_source", who);
+    if (l.source_mask) {
         uint32_t need = 0;
         for (uint32_t r = 0; r < n_rules; ++r) need = std::max(need, (uint32_t)rules[r].source + 1u);
-        PG_REQUIRE(planes_f64 && n_f64 >= need, "%s: a source mask needs the per-recall score planes of every named source (n_f64 >= %u)", who,
+        PG_REQUIRE(l.planes_f64 && l.n_f64 >= need, "%s: a source mask needs the per-recall score planes of every named source (n_f64 >= %u)", who,
                    need);
     }
-    const size_t e = (size_t)nq * cap, o = (size_t)nq * *out_cap;
-    PG_REQUIRE(!trim2_overlap(rows, e * 8, out_rows, o * 8) && !trim2_overlap(score, e * 8, out_score, o * 8) &&
-                   !trim2_overlap(source, e, out_source, o) && !trim2_overlap(mask, e * 4, out_mask, o * 4) &&
-                   !trim2_overlap(planes_f64, e * 8 * n_f64, out_planes_f64, o * 8 * n_f64) &&
-                   !trim2_overlap(planes_f32, e * 4 * n_f32, out_planes_f32, o * 4 * n_f32),
-               "%s: an output overlaps its input", who);
-    return PG_OK;
-}
-
-// pg_sort_scores_dev's order on the host: descending, -0.0 equal to +0.0, NaN last, ties by input position
-inline bool trim2_before(double x, double y) { return x == x && (y != y || x > y); }
-
-inline double trim2_f64(unsigned long long bits) {
-    double d;
-    memcpy(&d, &bits, 8);
-    return d;
+    return cand_call_apart(l, nq, cap, *out_cap, who);
 }
 
 }  // namespace
@@ -275,16 +248,14 @@ int pg_candidates_trim2_dev(pg_ctx* ctx, const pg_trim_rule* rules, uint32_t n_r
                             double* d_out_score, uint8_t* d_out_source, double* d_out_planes_f64, uint32_t* d_out_source_mask,
                             float* d_out_planes_f32, uint32_t* d_out_count) {
     PG_REQUIRE(ctx, "pg_candidates_trim2_dev: NULL argument");
+    const pg::CandCall l{d_rows, d_score, d_source, d_count, d_planes_f64, n_f64, d_source_mask, d_planes_f32, n_f32, d_out_rows, d_out_score,
+                         d_out_source, d_out_planes_f64, d_out_source_mask, d_out_planes_f32, d_out_count};
     uint32_t out_cap = 0;
     int rc;
-    if ((rc = pg::trim2_check_call(rules, n_rules, nq, cap, d_rows, d_score, d_source, d_planes_f64, n_f64, d_source_mask, d_planes_f32, n_f32,
-                                   d_out_rows, d_out_score, d_out_source, d_out_planes_f64, d_out_source_mask, d_out_planes_f32,
-                                   d_out_count, &out_cap, "pg_candidates_trim2_dev")))
-        return rc;
+    if ((rc = pg::trim2_check_call(rules, n_rules, nq, cap, l, &out_cap, "pg_candidates_trim2_dev"))) return rc;
     pg::CandIn in;
     pg::CandOut out;
-    pg::cand_lists_bind(nq, cap, out_cap, d_rows, d_score, d_source, d_count, d_planes_f64, n_f64, d_source_mask, d_planes_f32, n_f32,
-                        d_out_rows, d_out_score, d_out_source, d_out_planes_f64, d_out_source_mask, d_out_planes_f32, d_out_count, &in, &out);
+    pg::cand_lists_bind(l, nq, cap, out_cap, &in, &out);
     std::lock_guard<std::mutex> g(ctx->mu);
     PG_HIP(hipSetDevice(ctx->device));
     return pg::candidates_trim2_locked(ctx, rules, n_rules, in, out);
@@ -295,16 +266,14 @@ int pg_candidates_trim2_host(const pg_trim_rule* rules, uint32_t n_rules, uint32
                              const uint32_t* source_mask, const float* planes_f32, uint32_t n_f32, uint64_t* out_rows, double* out_score,
                              uint8_t* out_source, double* out_planes_f64, uint32_t* out_source_mask, float* out_planes_f32,
                              uint32_t* out_count) {
+    const pg::CandCall l{rows, score, source, count, planes_f64, n_f64, source_mask, planes_f32, n_f32, out_rows, out_score,
+                         out_source, out_planes_f64, out_source_mask, out_planes_f32, out_count};
     uint32_t out_cap = 0;
     int rc;
-    if ((rc = pg::trim2_check_call(rules, n_rules, nq, cap, rows, score, source, planes_f64, n_f64, source_mask, planes_f32, n_f32, out_rows,
-                                   out_score, out_source, out_planes_f64, out_source_mask, out_planes_f32, out_count, &out_cap,
-                                   "pg_candidates_trim2_host")))
-        return rc;
+    if ((rc = pg::trim2_check_call(rules, n_rules, nq, cap, l, &out_cap, "pg_candidates_trim2_host"))) return rc;
     pg::CandIn in;
     pg::CandOut out;
-    pg::cand_lists_bind(nq, cap, out_cap, rows, score, source, count, planes_f64, n_f64, source_mask, planes_f32, n_f32, out_rows, out_score,
-                        out_source, out_planes_f64, out_source_mask, out_planes_f32, out_count, &in, &out);
+    pg::cand_lists_bind(l, nq, cap, out_cap, &in, &out);
     std::vector<uint32_t> list;
     std::vector<double> key(cap);
     std::vector<bool> via_plane(cap), taken(cap);
@@ -320,11 +289,11 @@ int pg_candidates_trim2_host(const pg_trim_rule* rules, uint32_t n_rules, uint32
             for (uint32_t p = 0; p < cap; ++p) {                  // (:58,63,66-71)
                 bool plane;
                 if (!pg::trim2_member(in, in0 + p, p, n_valid, sc, &plane)) continue;
-                key[p] = pg::trim2_f64(pg::trim2_key(in, in0 + p, sc, plane));
+                key[p] = pg::cand_bits_f64(pg::trim2_key(in, in0 + p, sc, plane));
                 via_plane[p] = plane;
                 list.push_back(p);
             }
-            std::stable_sort(list.begin(), list.end(), [&](uint32_t x, uint32_t y) { return pg::trim2_before(key[x], key[y]); });    // (:74)
+            std::stable_sort(list.begin(), list.end(), [&](uint32_t x, uint32_t y) { return pg::cand_before(key[x], key[y]); });    // (:74)
             const uint64_t cnt = rules[c].count;
             const uint64_t limit = rules[c].type == PG_TRIM_FIX ? cnt : (cnt > acc ? cnt - acc : 0);     // (:76-77,86-88)
             uint64_t picks = 0;

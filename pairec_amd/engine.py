@@ -725,12 +725,16 @@ class Context:
         """pg_candidates_trim_dev: rules = [(source, type, count)], everything else device addresses (0 = absent; an output is
         required exactly where its input is given), outputs [nq][trim_out_cap(rules, cap)].  Enqueued on the context's stream:
         synchronize() before reading."""
-        arr = _trim_rules(rules)
+        self._list_call(self.L.pg_candidates_trim_dev, (_trim_rules(rules), len(rules)), nq, cap,
+                        (d_rows, d_score, d_source, d_count, d_planes_f64, n_f64, d_source_mask, d_planes_f32, n_f32, d_out_rows, d_out_score,
+                         d_out_source, d_out_planes_f64, d_out_source_mask, d_out_planes_f32, d_out_count))
+
+    def _list_call(self, fn, lead, nq, cap, lists, before_outputs=()):
+        """fn(context, *lead, nq, cap, the ABI's 16 list arguments): `lists` in candidates_trim_dev's order, device addresses (0 =
+        absent) but for the two plane counts; before_outputs: addresses an entry takes between the inputs and the outputs"""
         v = lambda p: C.c_void_p(p or None)                                          # noqa: E731
-        _lib.check(self.L.pg_candidates_trim_dev(self.h, arr, len(rules), nq, cap, v(d_rows), v(d_score), v(d_source), v(d_count),
-                                                 v(d_planes_f64), n_f64, v(d_source_mask), v(d_planes_f32), n_f32, v(d_out_rows),
-                                                 v(d_out_score), v(d_out_source), v(d_out_planes_f64), v(d_out_source_mask),
-                                                 v(d_out_planes_f32), v(d_out_count)))
+        a = [x if i in (5, 8) else v(x) for i, x in enumerate(lists)]
+        _lib.check(fn(self.h, *lead, nq, cap, *a[:9], *[v(x) for x in before_outputs], *a[9:]))
 
     def candidates_trim(self, rules, rows, score, source=None, count=None, planes_f64=None, source_mask=None, planes_f32=None):
         """Recall quotas / the top-N cut on host arrays (pg_candidates_trim_dev): fanin_merge's rows [nq][cap] u64, score
@@ -778,11 +782,9 @@ class Context:
         """pg_candidates_blend_dev: conf = (mode, retain_num, [(source, weight)]), everything else device addresses as
         candidates_trim_dev (0 = absent; an output is required exactly where its input is given), outputs
         [nq][blend_out_cap(conf, cap)].  Enqueued on the context's stream: synchronize() before reading."""
-        v = lambda p: C.c_void_p(p or None)                                          # noqa: E731
-        _lib.check(self.L.pg_candidates_blend_dev(self.h, C.byref(_blend_conf(conf)), nq, cap, v(d_rows), v(d_score), v(d_source),
-                                                  v(d_count), v(d_planes_f64), n_f64, v(d_source_mask), v(d_planes_f32), n_f32,
-                                                  v(d_out_rows), v(d_out_score), v(d_out_source), v(d_out_planes_f64),
-                                                  v(d_out_source_mask), v(d_out_planes_f32), v(d_out_count)))
+        self._list_call(self.L.pg_candidates_blend_dev, (C.byref(_blend_conf(conf)),), nq, cap,
+                        (d_rows, d_score, d_source, d_count, d_planes_f64, n_f64, d_source_mask, d_planes_f32, n_f32, d_out_rows, d_out_score,
+                         d_out_source, d_out_planes_f64, d_out_source_mask, d_out_planes_f32, d_out_count))
 
     def candidates_blend(self, conf, rows, score, source=None, count=None, planes_f64=None, source_mask=None, planes_f32=None):
         """SnakeFilter / CompletelyFairCountFilter on host arrays (pg_candidates_blend_dev): the arrays of candidates_trim, conf =
@@ -805,12 +807,9 @@ class Context:
         """pg_candidates_trim2_dev: rules = [(source, type, count)], everything else device addresses as candidates_trim_dev (0 =
         absent; an output is required exactly where its input is given), outputs [nq][trim2_out_cap(rules, cap)].  Enqueued on
         the context's stream: synchronize() before reading."""
-        arr = _trim_rules(rules)
-        v = lambda p: C.c_void_p(p or None)                                          # noqa: E731
-        _lib.check(self.L.pg_candidates_trim2_dev(self.h, arr, len(rules), nq, cap, v(d_rows), v(d_score), v(d_source), v(d_count),
-                                                  v(d_planes_f64), n_f64, v(d_source_mask), v(d_planes_f32), n_f32, v(d_out_rows),
-                                                  v(d_out_score), v(d_out_source), v(d_out_planes_f64), v(d_out_source_mask),
-                                                  v(d_out_planes_f32), v(d_out_count)))
+        self._list_call(self.L.pg_candidates_trim2_dev, (_trim_rules(rules), len(rules)), nq, cap,
+                        (d_rows, d_score, d_source, d_count, d_planes_f64, n_f64, d_source_mask, d_planes_f32, n_f32, d_out_rows, d_out_score,
+                         d_out_source, d_out_planes_f64, d_out_source_mask, d_out_planes_f32, d_out_count))
 
     def candidates_trim2(self, rules, rows, score, source=None, count=None, planes_f64=None, source_mask=None, planes_f32=None):
         """PriorityAdjustCountFilterV2 on host arrays (pg_candidates_trim2_dev): the arrays of candidates_trim, planes_f64 the
@@ -840,32 +839,12 @@ class Context:
                                                           v(d_source), v(d_enable), v(d_order)))
         del keep
 
-    def _diversity_run(self, nq, cap, arrays, launch):
-        out = np.empty((nq, cap), dtype=np.uint32)
-        bufs = []
-        try:
-            dev = []
-            for a in arrays:
-                dev.append(self.to_device(a) if a is not None else 0)
-                bufs.append(dev[-1])
-            d_out = self.malloc(max(out.nbytes, 16))
-            bufs.append(d_out)
-            launch(dev, d_out)
-            self.synchronize()
-            if out.nbytes:
-                self.d2h(out, d_out)
-        finally:
-            for b in bufs:
-                if b:
-                    self.free(b)
-        return out
-
     def diversity_rules(self, cfg, dims, count=None, source=None, enable=None) -> np.ndarray:
         """DiversityRuleSort of nq requests on host arrays (pg_diversity_rules_dev): dims [n_cols][nq][cap] int64, count [nq],
         source [nq][cap] uint8, enable [nq] bytes → order [nq][cap] uint32 (UINT32_MAX behind count)."""
         d, n_cols, nq, cap, cnt, src, en = _div_planes(dims, count, source, enable)
-        return self._diversity_run(nq, cap, [cnt, d, src, en], lambda dev, d_out: self.diversity_rules_dev(
-            cfg, n_cols, nq, cap, dev[0], dev[1], dev[2], dev[3], d_out))
+        return self._cand_run([cnt, d, src, en], [np.empty((nq, cap), np.uint32)], lambda dev, d_out: self.diversity_rules_dev(
+            cfg, n_cols, nq, cap, dev[0], dev[1], dev[2], dev[3], d_out[0]))[0]
 
     def diversity_rules_features(self, cfg, fs, col_names, rows, count=None, source=None, enable=None) -> np.ndarray:
         """The same with the dimension columns read from a feature store (pg_diversity_rules_features_dev): rows [nq][cap] uint64."""
@@ -876,8 +855,8 @@ class Context:
         cnt = None if count is None else np.ascontiguousarray(count, dtype=np.uint32)
         src = None if source is None else np.ascontiguousarray(source, dtype=np.uint8)
         en = None if enable is None else np.ascontiguousarray(enable, dtype=np.uint8)
-        return self._diversity_run(nq, cap, [r, cnt, src, en], lambda dev, d_out: self.diversity_rules_features_dev(
-            cfg, fs, list(col_names), nq, cap, dev[0], dev[1], dev[2], dev[3], d_out))
+        return self._cand_run([r, cnt, src, en], [np.empty((nq, cap), np.uint32)], lambda dev, d_out: self.diversity_rules_features_dev(
+            cfg, fs, list(col_names), nq, cap, dev[0], dev[1], dev[2], dev[3], d_out[0]))[0]
 
     def diversity_rules_one(self, cfg, dims, source=None) -> np.ndarray:
         """pg_diversity_rules: one request on host arrays, dims [n_cols][n] int64 → order [n] uint32 (what the host mirror calls)."""
@@ -898,11 +877,9 @@ class Context:
                               d_out_source_mask: int, d_out_planes_f32: int, d_out_count: int) -> None:
         """pg_item_state_filter_dev: device addresses (0 = absent; an output is required exactly where its input is given),
         outputs [nq][cap].  Enqueued on the context's stream: synchronize() before reading."""
-        v = lambda p: C.c_void_p(p or None)                                          # noqa: E731
-        _lib.check(self.L.pg_item_state_filter_dev(self.h, cond.h, getattr(fs, "h", fs), nq, cap, v(d_rows), v(d_score), v(d_source),
-                                                   v(d_count), v(d_planes_f64), n_f64, v(d_source_mask), v(d_planes_f32), n_f32,
-                                                   v(d_user_vals), v(d_user_present), v(d_out_rows), v(d_out_score), v(d_out_source),
-                                                   v(d_out_planes_f64), v(d_out_source_mask), v(d_out_planes_f32), v(d_out_count)))
+        self._list_call(self.L.pg_item_state_filter_dev, (cond.h, getattr(fs, "h", fs)), nq, cap,
+                        (d_rows, d_score, d_source, d_count, d_planes_f64, n_f64, d_source_mask, d_planes_f32, n_f32, d_out_rows, d_out_score,
+                         d_out_source, d_out_planes_f64, d_out_source_mask, d_out_planes_f32, d_out_count), (d_user_vals, d_user_present))
 
     def boost_scores_dev(self, cond, fs, filter_all: bool, nq: int, cap: int, d_rows: int, d_score: int, d_count: int, d_user_vals: int,
                          d_user_present: int, d_out_score: int, d_out_rule: int) -> None:
@@ -939,24 +916,8 @@ class Context:
         nq, cap = r.shape
         cnt = None if count is None else np.ascontiguousarray(count, dtype=np.uint32)
         uv, up = self._cond_user(cond, users, nq)
-        out, rule = np.empty((nq, cap), np.float64), np.empty((nq, cap), np.uint8)
-        bufs = []
-        try:
-            dev = []
-            for a in (r, sc, cnt, uv, up):
-                dev.append(self.to_device(a) if a is not None else 0)
-                bufs.append(dev[-1])
-            d_out, d_rule = self.malloc(max(out.nbytes, 16)), self.malloc(max(rule.nbytes, 16))
-            bufs += [d_out, d_rule]
-            self.boost_scores_dev(cond, fs, filter_all, nq, cap, dev[0], dev[1], dev[2], dev[3], dev[4], d_out, d_rule)
-            self.synchronize()
-            self.d2h(out, d_out)
-            self.d2h(rule, d_rule)
-        finally:
-            for b in bufs:
-                if b:
-                    self.free(b)
-        return out, rule
+        return self._cand_run([r, sc, cnt, uv, up], [np.empty((nq, cap), np.float64), np.empty((nq, cap), np.uint8)],
+                              lambda d_in, d_out: self.boost_scores_dev(cond, fs, filter_all, nq, cap, *d_in, *d_out))
 
     def item_state_filter_one(self, cond, fs, rows, score, source=None, user=None):
         """pg_item_state_filter: one request on host arrays (what the host mirror calls) → (rows [n], score [n], source [n] | None, count)"""
@@ -1005,11 +966,9 @@ class Context:
         """pg_candidates_classcut_dev: cc a Classcut, fs the store its columns are bound to, everything else device addresses as
         candidates_trim_dev (0 = absent; an output is required exactly where its input is given), outputs [nq][cc.out_cap(cap)].
         Enqueued on the context's stream: synchronize() before reading."""
-        v = lambda p: C.c_void_p(p or None)                                          # noqa: E731
-        _lib.check(self.L.pg_candidates_classcut_dev(self.h, cc.h, getattr(fs, "h", fs), nq, cap, v(d_rows), v(d_score), v(d_source),
-                                                     v(d_count), v(d_planes_f64), n_f64, v(d_source_mask), v(d_planes_f32), n_f32,
-                                                     v(d_out_rows), v(d_out_score), v(d_out_source), v(d_out_planes_f64),
-                                                     v(d_out_source_mask), v(d_out_planes_f32), v(d_out_count)))
+        self._list_call(self.L.pg_candidates_classcut_dev, (cc.h, getattr(fs, "h", fs)), nq, cap,
+                        (d_rows, d_score, d_source, d_count, d_planes_f64, n_f64, d_source_mask, d_planes_f32, n_f32, d_out_rows, d_out_score,
+                         d_out_source, d_out_planes_f64, d_out_source_mask, d_out_planes_f32, d_out_count))
 
     def candidates_classcut(self, cc, fs, rows, score, source=None, count=None, planes_f64=None, source_mask=None, planes_f32=None):
         """DiversityAdjustCountFilter on host arrays (pg_candidates_classcut_dev): the arrays of candidates_trim → (rows, score,
