@@ -400,7 +400,13 @@ typedef struct pg_features pg_features;
 typedef enum { PG_F_I32 = 1, PG_F_I64 = 2, PG_F_F32 = 3, PG_F_F64 = 4 } pg_feature_dtype;
 int pg_features_create(pg_ctx* ctx, uint64_t rows, pg_features** out);
 int pg_features_destroy(pg_ctx* ctx, pg_features* fs);
-/* add or replace column `name`; host_values: [rows] of the dtype, or NULL (every row = default) */
+/* add or replace column `name`; host_values: [rows] of the dtype, or NULL (every row = default).
+ * THE STORED DEFAULT: a column has one default, default_value rounded to the column's dtype — (double)(float)default_value for
+ * F32, default_value itself for F64, the integer truncated toward zero for I32 / I64 (-7.9 stores -7).  A NULL fill writes that
+ * value into every row and every reader of a row outside the store (gather_i32, gather_f32, pg_features_eval_dev, the FM item
+ * records, WhereClause / condition readers) sees that value: a row inside a NULL-filled column and a row outside the store read
+ * the same bits.  An I32 / I64 default that is NaN, infinite or outside the dtype's range is PG_ERR_INVALID (the message names
+ * the column), refused before anything is allocated or modified: the store stays as it was. */
 int pg_features_set_column(pg_ctx* ctx, pg_features* fs, const char* name, int dtype,
                            const void* host_values, double default_value);
 int pg_features_column_index(const pg_features* fs, const char* name);   /* -1 if absent */
@@ -409,7 +415,11 @@ int pg_features_num_columns(const pg_features* fs);
 int pg_features_gather_i32_dev(pg_ctx* ctx, const pg_features* fs, const int32_t* col_idx, uint32_t n_cols,
                                const uint32_t* d_rows, uint32_t n, int32_t* d_out);
 /* d_out[i][f] = fmaf((float)value, scale[f], bias[f]) (host arrays [n_cols]; NULL = 1 / 0): dense float
- * inputs with the simplest normalizer fused; richer ones go through pg_expr_* */
+ * inputs with the simplest normalizer fused; richer ones go through pg_expr_*.
+ * DIRECT CONVERSION: (float)value rounds ONCE, to nearest-even — an I32 / I64 value converts to fp32 directly, never through a
+ * double (an int64 beyond 2^53 would round twice: 2^60 + 2^36 + 1 is 0x5D800001, by way of a double 0x5D800000); an F64 value
+ * is (float)double.  Then one fused multiply-add, IEEE throughout: fp32 subnormals are kept (not flushed), an fp64 beyond the
+ * fp32 range is +-inf, NaN stays NaN, -0.0 with no scale and no bias is fmaf(-0, 1, +0) = +0.0. */
 int pg_features_gather_f32_dev(pg_ctx* ctx, const pg_features* fs, const int32_t* col_idx, uint32_t n_cols,
                                const float* scale, const float* bias, const uint32_t* d_rows, uint32_t n,
                                float* d_out);
@@ -1040,7 +1050,11 @@ int pg_index_refresh_stats(const pg_index* ix, pg_index_refresh_stats_t* out);
 int pg_index_screen_probe(pg_ctx* ctx, uint32_t dim, const float* rows, uint32_t n, const float* centroids, uint32_t n_lists,
                           float* out_s, float* out_e);
 /* FM + two-tower rank straight from candidate rows: the model's item field ids are the integer columns
- * item_field_cols[n_item_fields] of `fs` (out-of-vocabulary ids are clamped as in pg_rank_fm2t_dev) */
+ * item_field_cols[n_item_fields] of `fs`.
+ * THE CLAMP ON ITEM IDS: an item field id is the column's value saturated to int32 (as pg_features_gather_i32_dev), then clamped
+ * to [0, vocab - 1] — -1 reads id 0, `vocab` and 2^40 read id vocab - 1.  pg_rank_fm2t_dev (device ids), this call and the item
+ * records (pg_fm2t_item_rows_*) apply the same rule and score an out-of-vocabulary id bit for bit as the clamped id; only the
+ * host entry pg_rank_fm2t, which sees the ids, refuses them (PG_ERR_INVALID names the first). */
 int pg_rank_fm2t_rows_dev(pg_ctx* ctx, const pg_model* m, const pg_features* fs, const int32_t* item_field_cols,
                           const float* d_user_vecs, const int32_t* d_user_field_ids, const uint32_t* d_cand_rows,
                           const uint32_t* d_req_offsets, uint32_t n_req, uint32_t n_items, float* d_out_scores);
@@ -1059,7 +1073,9 @@ int pg_rank_fm2t_rows(pg_ctx* ctx, const pg_model* m, const pg_features* fs, con
  * hold the very values the per-field path reads and the kernel sums them in the same order, so scores are bit-identical
  * to pg_rank_fm2t_rows_dev in both precision modes; candidates outside the store read the columns' defaults as there.
  * After a column changes (pg_features_set_column) or the model's field tables are reloaded, _update re-materialises
- * rows [row0, row0 + nrows); the per-field path stays available for field-table hot-swaps. */
+ * rows [row0, row0 + nrows) and always the defaults' record (nrows = 0 refreshes that alone); a range that does not lie
+ * inside the store — row0 > rows or nrows > rows - row0, a row0 + nrows that wraps included — is PG_ERR_INVALID with nothing
+ * launched.  The per-field path stays available for field-table hot-swaps. */
 typedef struct pg_item_rows pg_item_rows;
 int pg_fm2t_item_rows_build(pg_ctx* ctx, const pg_model* m, const pg_features* fs, const int32_t* item_field_cols,
                             pg_item_rows** out);

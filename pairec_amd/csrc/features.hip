@@ -27,13 +27,16 @@ struct ColDesc {
     double def;
 };
 
-__device__ __forceinline__ double load_as_f64(const ColDesc& c, uint32_t row, uint64_t rows) {
-    if (row >= rows) return c.def;
+// (float)value with ONE rounding: an integer converts to fp32 directly — through a double an int64 beyond 2^53 rounds twice
+// (2^60 + 2^36 + 1 is 0x5D800001 directly, 0x5D800000 by way of the double).  The stored default (pg_features_set_column) is
+// already a value of the column's dtype, exact in the double that carries it.
+__device__ __forceinline__ float load_as_f32(const ColDesc& c, uint32_t row, uint64_t rows) {
+    if (row >= rows) return (float)c.def;
     switch (c.dtype) {
-        case PG_F_I32: return (double)((const int32_t*)c.base)[row];
-        case PG_F_I64: return (double)((const int64_t*)c.base)[row];
-        case PG_F_F32: return (double)((const float*)c.base)[row];
-        default: return ((const double*)c.base)[row];
+        case PG_F_I32: return (float)((const int32_t*)c.base)[row];
+        case PG_F_I64: return (float)((const int64_t*)c.base)[row];
+        case PG_F_F32: return ((const float*)c.base)[row];
+        default: return (float)((const double*)c.base)[row];
     }
 }
 
@@ -61,7 +64,7 @@ __global__ void features_gather_f32_kernel(const ColDesc* __restrict__ cols, uin
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n * F) return;
     const uint32_t i = t / F, f = t % F;
-    const float v = (float)load_as_f64(cols[f], cand[i], rows);
+    const float v = load_as_f32(cols[f], cand[i], rows);
     out[t] = __fmaf_rn(v, scale ? scale[f] : 1.0f, bias ? bias[f] : 0.0f);
 }
 
@@ -197,6 +200,22 @@ int pg_features_set_column(pg_ctx* ctx, pg_features* fs, const char* name, int d
     PG_REQUIRE(ctx && fs && name && name[0], "pg_features_set_column: NULL argument");
     const size_t es = pg::dtype_size(dtype);
     PG_REQUIRE(es != 0, "pg_features_set_column: unknown dtype %d", dtype);
+    // ONE value per default: the default rounded to the column's dtype, kept in a double that holds it exactly — what a NULL
+    // fill stores in every row and what every reader of a row outside the store sees.  An integer default truncates toward
+    // zero; one that no value of the dtype can stand for is refused here, before anything is allocated or modified.
+    double def = default_value;
+    if (dtype == PG_F_F32) {
+        def = (double)(float)default_value;
+    } else if (dtype == PG_F_I32 || dtype == PG_F_I64) {
+        PG_REQUIRE(std::isfinite(default_value), "pg_features_set_column: column \"%s\": default %g is not an integer value", name,
+                   default_value);
+        def = std::trunc(default_value);
+        const double lo = dtype == PG_F_I32 ? -2147483648.0 : -9223372036854775808.0;
+        const double hi = dtype == PG_F_I32 ? 2147483648.0 : 9223372036854775808.0;       // exclusive
+        PG_REQUIRE(def >= lo && def < hi, "pg_features_set_column: column \"%s\": default %g outside the range of %s", name,
+                   default_value, dtype == PG_F_I32 ? "int32" : "int64");
+        def = (double)(int64_t)def;                      // (-0.5 truncates to -0.0: the integer 0 reads back as +0.0)
+    }
     std::lock_guard<std::mutex> g(ctx->mu);
     pg_features::Column* col = nullptr;
     for (auto& c : fs->cols)
@@ -213,7 +232,7 @@ int pg_features_set_column(pg_ctx* ctx, pg_features* fs, const char* name, int d
         col->name = name;
     }
     col->dtype = dtype;
-    col->def = default_value;
+    col->def = def;
     col->version = pg::next_column_version();      // (before the write: a cached filter of the old values never matches again)
     if (!col->d) {
         hipError_t e = hipMalloc(&col->d, fs->rows * es);
@@ -231,10 +250,10 @@ int pg_features_set_column(pg_ctx* ctx, pg_features* fs, const char* name, int d
         std::vector<uint8_t> fill(fs->rows * es);
         for (uint64_t r = 0; r < fs->rows; ++r) {
             switch (dtype) {
-                case PG_F_I32: ((int32_t*)fill.data())[r] = (int32_t)default_value; break;
-                case PG_F_I64: ((int64_t*)fill.data())[r] = (int64_t)default_value; break;
-                case PG_F_F32: ((float*)fill.data())[r] = (float)default_value; break;
-                default: ((double*)fill.data())[r] = default_value;
+                case PG_F_I32: ((int32_t*)fill.data())[r] = (int32_t)def; break;       // (in range: checked above)
+                case PG_F_I64: ((int64_t*)fill.data())[r] = (int64_t)def; break;
+                case PG_F_F32: ((float*)fill.data())[r] = (float)def; break;
+                default: ((double*)fill.data())[r] = def;
             }
         }
         PG_HIP(hipMemcpyAsync(col->d, fill.data(), fs->rows * es, hipMemcpyHostToDevice, ctx->stream));

@@ -779,7 +779,7 @@ int pg_group_table_fill_synthetic(pg_group* g, uint64_t seed, int normalize) {
 
 int pg_group_table_upload(pg_group* g, uint64_t row0, uint64_t nrows, const float* host_rows) {
     PG_REQUIRE(g && g->total_rows && (nrows == 0 || host_rows), "pg_group_table_upload: bad argument");
-    PG_REQUIRE(row0 + nrows <= g->total_rows, "pg_group_table_upload: rows %llu..%llu outside the table",
+    PG_REQUIRE(row0 <= g->total_rows && nrows <= g->total_rows - row0, "pg_group_table_upload: rows %llu..%llu outside the table",
                (unsigned long long)row0, (unsigned long long)(row0 + nrows));
     std::lock_guard<std::mutex> lk(g->mu);
     int rc;

@@ -1854,8 +1854,9 @@ int pg_fm2t_item_rows_build(pg_ctx* ctx, const pg_model* m, const pg_features* f
 
 int pg_fm2t_item_rows_update(pg_ctx* ctx, pg_item_rows* ir, uint64_t row0, uint64_t nrows) {
     PG_REQUIRE(ctx && ir, "pg_fm2t_item_rows_update: NULL argument");
-    PG_REQUIRE(row0 + nrows <= ir->rows, "pg_fm2t_item_rows_update: rows %llu..%llu outside the store", (unsigned long long)row0,
-               (unsigned long long)(row0 + nrows));
+    // (not row0 + nrows <= rows: the sum wraps for a huge row0, and the kernel would write far outside the records)
+    PG_REQUIRE(row0 <= ir->rows && nrows <= ir->rows - row0, "pg_fm2t_item_rows_update: rows %llu + %llu outside the store's %llu",
+               (unsigned long long)row0, (unsigned long long)nrows, (unsigned long long)ir->rows);
     std::lock_guard<std::mutex> g(ctx->mu);
     int rc;
     if ((rc = pg::item_rows_fill_locked(ctx, ir, row0, nrows))) return rc;

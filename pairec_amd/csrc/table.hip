@@ -247,7 +247,7 @@ int pg_table_fill_mixture(pg_ctx* ctx, pg_table* t, uint64_t seed, uint32_t n_ce
 
 int pg_table_upload(pg_ctx* ctx, pg_table* t, uint64_t row0, uint64_t nrows, const float* host_rows) {
     PG_REQUIRE(ctx && t && (nrows == 0 || host_rows), "pg_table_upload: NULL argument");
-    PG_REQUIRE(row0 + nrows <= t->rows, "pg_table_upload: rows [%llu,%llu) outside table of %llu",
+    PG_REQUIRE(row0 <= t->rows && nrows <= t->rows - row0, "pg_table_upload: rows [%llu,%llu) outside table of %llu",   // (row0 + nrows may wrap)
                (unsigned long long)row0, (unsigned long long)(row0 + nrows), (unsigned long long)t->rows);
     std::lock_guard<std::mutex> g(ctx->mu);
     if (nrows == 0) return PG_OK;
@@ -266,7 +266,7 @@ int pg_table_upload(pg_ctx* ctx, pg_table* t, uint64_t row0, uint64_t nrows, con
 
 int pg_table_download(pg_ctx* ctx, const pg_table* t, uint64_t row0, uint64_t nrows, float* host_rows) {
     PG_REQUIRE(ctx && t && (nrows == 0 || host_rows), "pg_table_download: NULL argument");
-    PG_REQUIRE(row0 + nrows <= t->rows, "pg_table_download: rows out of range");
+    PG_REQUIRE(row0 <= t->rows && nrows <= t->rows - row0, "pg_table_download: rows out of range");
     std::lock_guard<std::mutex> g(ctx->mu);
     if (nrows == 0) return PG_OK;
     PG_HIP(hipMemcpyAsync(host_rows, t->d + row0 * t->dim, nrows * (size_t)t->dim * sizeof(float),

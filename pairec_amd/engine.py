@@ -2298,12 +2298,14 @@ class Features:
         r = np.ascontiguousarray(rows, dtype=np.uint32)
         d_r = self.ctx.to_device(r)
         d_o = self.ctx.malloc(max(r.shape[0] * idx.shape[0] * 4, 16))
-        _lib.check(self.ctx.L.pg_features_gather_i32_dev(self.ctx.h, self.h, _ptr(idx), idx.shape[0], d_r,
-                                                         r.shape[0], d_o))
-        out = np.zeros((r.shape[0], idx.shape[0]), dtype=np.int32)
-        self.ctx.d2h(out, d_o)
-        self.ctx.free(d_r)
-        self.ctx.free(d_o)
+        try:                                              # (a refused column must not leak the two buffers)
+            _lib.check(self.ctx.L.pg_features_gather_i32_dev(self.ctx.h, self.h, _ptr(idx), idx.shape[0], d_r,
+                                                             r.shape[0], d_o))
+            out = np.zeros((r.shape[0], idx.shape[0]), dtype=np.int32)
+            self.ctx.d2h(out, d_o)
+        finally:
+            self.ctx.free(d_r)
+            self.ctx.free(d_o)
         return out
 
     def gather_f32(self, names, rows: np.ndarray, scale=None, bias=None) -> np.ndarray:

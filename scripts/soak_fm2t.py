@@ -26,10 +26,16 @@ while time.time() < t_end:
     ids = rng.integers(0, vocab, (n_cat, 8)).astype(np.int32)
     ids[rng.random((n_cat, 8)) < 0.02] = 0
     ids[rng.random((n_cat, 8)) < 0.02] = vocab - 1
+    # ids outside the vocabulary: the columns hold them raw, the two column paths clamp them (saturate to int32, then [0, vocab - 1]);
+    # `ids` keeps the clamped values for the path that is handed its ids (the host entry refuses others) and for the oracle
+    raw = ids.astype(np.int64)
+    out = rng.random((n_cat, 8)) < 0.02
+    raw[out] = rng.choice([-1, -2**31, vocab, vocab + 5, 2**31 - 1, 2**40, -2**40], int(out.sum()))
+    ids = np.clip(np.clip(raw, -2**31, 2**31 - 1), 0, vocab - 1).astype(np.int32)
     feats = pa.Features(ctx, n_cat)
     cols = ["f%d" % f for f in range(8)]
     for f, c in enumerate(cols):
-        feats.set_column(c, pa.F_I32, np.ascontiguousarray(ids[:, f]))
+        feats.set_column(c, pa.F_I64 if f % 2 else pa.F_I32, np.ascontiguousarray(np.clip(raw[:, f], -2**31, 2**31 - 1) if f % 2 == 0 else raw[:, f]))
     for prec in (0, 1, 2):                                   # 2 = PG_PREC_BF16X3, against the fp32 specification (round 5)
         m = pa.RankModel(ctx, pa.MODEL_FM_TWOTOWER, (pa.PREC_F32, pa.PREC_BF16, pa.PREC_BF16X3)[prec], pa.pack_fm2t(fw))
         ir = pa.ItemRows(m, feats, cols)

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import expr_cases as xc
+import features_ref as fr
 import pairec_amd as pa
 from oracle import oracle as o
 from pairec_amd._lib import PgError, check
@@ -317,8 +318,12 @@ def test_features_eval_dev_over_typed_columns(ctx):
             v = (rng.standard_normal(rows) * 10.0).astype(np_type[dtype[1]])
         for t, h in enumerate(hostile[dtype[1]]):               # (each column's edge values on rows of its own: few items are all-NaN)
             v[(7 * c + t) % rows] = h
-        cols[name], defaults[name] = v, (-0.0 if c == 15 else -1.5 * (c + 1))
-        fs.set_column(name, dtype[1], v, default=defaults[name])
+        default = -0.0 if c == 15 else -1.5 * (c + 1)
+        fs.set_column(name, dtype[1], v, default=default)
+        # what a row outside the store reads: the default rounded to the column's dtype (pairec_gpu.h, THE STORED DEFAULT) — an
+        # integer column given -1.5 stores -1
+        cols[name], defaults[name] = v, float(fr.stored_default(dtype[1], default))
+    assert defaults["i32_0"] == -1.0 and defaults["f32_0"] == -4.5 and defaults["f64_3"] == 0.0 and np.signbit(defaults["f64_3"])
     names = list(cols)
     assert len(names) == 16
     r = np.concatenate([rng.permutation(rows), rng.integers(0, rows, n - rows)]).astype(np.uint32)
