@@ -1421,6 +1421,93 @@ int pg_item_state_filter(pg_ctx* ctx, pg_cond* c, const pg_features* fs, uint32_
 int pg_boost_scores(pg_ctx* ctx, pg_cond* c, uint32_t filter_all, uint32_t n, const uint8_t* item_in, const void* const* cols,
                     const uint64_t* user_vals, uint32_t user_present, const double* score, double* out_score, uint8_t* out_rule);
 
+/* DistinctIdSort on the device (csrc/cond.hip): sort/distinct_id_sort.go:52-72 tags every item with a group id —
+ * the DistinctId of the first DistinctIdCondition whose FilterParam matches, else the item's 1-based position (:57) — under one
+ * property name; a later stage (DiversityRuleSort, SSD) reads it as a dimension.  A compiled condition set (not a boost set)
+ * holds the conditions as its rules, in order.
+ *   answer    out_id[q][p] = ids[r] for the first rule r that matches (EvaluateByDomain answers false where it errors, and
+ *             :60 takes err != nil for a non-match), else p + 1; p is the position in the list as given, padding included (a
+ *             list that has been through a filter has none in front of its count).  Padding entries — row UINT64_MAX or
+ *             position >= d_count[q] — get 0.
+ *   dev       pg_distinct_ids_dev: ids is a HOST array of pg_cond_num_rules(c) int64 (it travels as a kernel argument);
+ *             d_rows uint64 [nq][cap], d_count [nq] or NULL, d_user_vals / d_user_present as pg_item_state_filter_dev,
+ *             d_out_id int64 [nq][cap].  nq <= 256, cap <= PG_TRIM_MAX_CAP.  One launch, one lane per candidate, on the context's
+ *             stream, no synchronisation.
+ *   host      pg_distinct_ids_host: a pure host function over candidate-aligned arrays in the shape of pg_boost_scores_host;
+ *             candidate i is position i of one request and none is padding.  What tests compare the kernel with; the
+ *             library falls back to it for nothing.
+ *   one       pg_distinct_ids: pg_distinct_ids_host's arguments through the device (the candidates' own values become a store
+ *             of n rows in context scratch, as pg_boost_scores does).  n = 0 is PG_OK. */
+int pg_distinct_ids_host(const pg_cond* c, const int64_t* ids, uint32_t n, const uint8_t* item_in, const void* const* cols,
+                         const uint64_t* user_vals, uint32_t user_present, int64_t* out_id);
+int pg_distinct_ids_dev(pg_ctx* ctx, pg_cond* c, const pg_features* fs, const int64_t* ids, uint32_t nq, uint32_t cap, const uint64_t* d_rows,
+                        const uint32_t* d_count, const uint64_t* d_user_vals, const uint32_t* d_user_present, int64_t* d_out_id);
+int pg_distinct_ids(pg_ctx* ctx, pg_cond* c, const int64_t* ids, uint32_t n, const uint8_t* item_in, const void* const* cols,
+                    const uint64_t* user_vals, uint32_t user_present, int64_t* out_id);
+
+/* The value cap on the device: DimensionFieldUniqueFilter and one dimension of GroupWeightCountFilter's size limit (DESIGN.md
+ * 4.1u; csrc/dimcap.hip).  DimensionFieldUniqueFilter (filter/dimension_field_unique_filter.go:33-55) keeps the first item of each
+ * value of a property — one video per author, one SKU per spu — and every item whose property is "" (:41-42);
+ * groupWeightDimensionFilter (filter/group_weight_count_filter.go:288-302) keeps the first sizeLimit items of each value of a
+ * dimension, "" standing for the value "__DEFAULT__" (:293-295).
+ *   walk      per request, the real entries in order; padding — row UINT64_MAX or position >= min(d_count[q], cap) — is dropped
+ *             and never counted.
+ *   key       the value of feature-store column conf->column at the entry's row, widened to int64.  PG_F_I32 and PG_F_I64
+ *             columns are served (strings are dictionary ids the caller encoded); a float column is PG_ERR_UNSUPPORTED; a name
+ *             the store does not hold is PG_ERR_INVALID.
+ *   null      an entry whose row is outside the store (row >= the store's rows), or, with has_null set, whose value equals
+ *             null_value: the "" StringProperty returns.  PG_DIMCAP_NULL_KEEP: always kept, never counted (:41-42).
+ *             PG_DIMCAP_NULL_VALUE: one more value of its own, capped like the rest ("__DEFAULT__").
+ *   keep      a non-null entry is kept iff fewer than `limit` earlier entries of its key were kept in this request — that is,
+ *             iff it is among the first `limit` occurrences of its key.  limit = 1 is DimensionFieldUniqueFilter exactly;
+ *             limit > 1 the size limit of one dimension.  Several dimensions are several calls in the caller's order (Go
+ *             walks them in map order: every order is one of its answers).  limit = 0 is PG_ERR_INVALID.
+ *   dev       pg_candidates_dimcap_dev: ONE launch on the context's stream, no synchronisation.  In: the lists as
+ *             pg_candidates_trim_dev takes them (pg_fanin_merge_dev's outputs as they are), nq <= 256, cap in
+ *             [1, PG_TRIM_MAX_CAP], up to PG_TRIM_MAX_PLANES planes a set.  Out [nq][cap]: the kept entries in order with
+ *             everything carried, d_out_count[q], and padding behind the count as pg_item_state_filter_dev pads: UINT64_MAX
+ *             rows, quiet-NaN scores and fp64 planes, source 0xFF, mask 0, fp32 planes 0 — accepted by pg_candidates_trim_dev
+ *             unchanged.  Every output element is written exactly once; an output that overlaps its input is PG_ERR_INVALID
+ *             (the kernel reads a request's inputs after its first output is written).  Checks, in this order: the NULL
+ *             arguments, the conf, nq, cap, the optional arrays' pairing, the overlap, then the column.
+ *   host      pg_candidates_dimcap_host: a pure host function (no context, no device; conf->column is not read) over
+ *             candidate-aligned arrays: keys int64 [nq * cap] the entries' values, item_in [nq * cap] 0 = the row is outside
+ *             the store (NULL: all inside).  The statement the kernel is tested against; the library falls back to it for
+ *             nothing.
+ *   one       pg_candidates_dimcap: rows / score / source of one request on host arrays against a store (upload, run,
+ *             download, synchronise).  n = 0 is PG_OK with count 0.
+ *   Kernel    one workgroup of PG_DIMCAP_CHUNK lanes per request walks cap in chunks.  A lane loads its row, then its value;
+ *             finds or claims the value's slot in an open-addressed table of full 64-bit keys with a kept-count per slot,
+ *             max(2 cap, PG_DIMCAP_MIN_SLOTS) slots, linear probing from
+ *                 ((uint64(key) * 0x9E3779B97F4A7C15 >> 32) * slots) >> 32;
+ *             ranks itself among the lanes of its wave that hold the same slot (one ballot per bit of the slot index); then
+ *             the waves take turns: count + rank < limit keeps, the last lane of a group stores min(count + group, limit).
+ *             Kept entries are compacted by ballot rank and a running base.  No atomic decides an order.  Up to
+ *             PG_DIMCAP_LDS_MAX_CAP the table is LDS (12 bytes a slot: 144 KiB at the boundary), above it context scratch. */
+#define PG_DIMCAP_CHUNK 1024
+#define PG_DIMCAP_MIN_SLOTS 1024
+#define PG_DIMCAP_LDS_MAX_CAP 6144
+typedef enum { PG_DIMCAP_NULL_KEEP = 0, PG_DIMCAP_NULL_VALUE = 1 } pg_dimcap_null_mode;
+typedef struct {
+    const char* column;        /* the feature-store column the key is read from (unused by the host statement) */
+    uint32_t    limit;         /* >= 1 */
+    uint32_t    null_mode;     /* pg_dimcap_null_mode */
+    uint32_t    has_null;      /* != 0: a value equal to null_value is null */
+    int64_t     null_value;
+} pg_dimcap_conf;
+int pg_candidates_dimcap_host(const pg_dimcap_conf* conf, uint32_t nq, uint32_t cap, const int64_t* keys, const uint8_t* item_in,
+                              const uint64_t* rows, const double* score, const uint8_t* source, const uint32_t* count,
+                              const double* planes_f64, uint32_t n_f64, const uint32_t* source_mask, const float* planes_f32, uint32_t n_f32,
+                              uint64_t* out_rows, double* out_score, uint8_t* out_source, double* out_planes_f64, uint32_t* out_source_mask,
+                              float* out_planes_f32, uint32_t* out_count);
+int pg_candidates_dimcap_dev(pg_ctx* ctx, const pg_features* fs, const pg_dimcap_conf* conf, uint32_t nq, uint32_t cap, const uint64_t* d_rows,
+                             const double* d_score, const uint8_t* d_source, const uint32_t* d_count, const double* d_planes_f64,
+                             uint32_t n_f64, const uint32_t* d_source_mask, const float* d_planes_f32, uint32_t n_f32, uint64_t* d_out_rows,
+                             double* d_out_score, uint8_t* d_out_source, double* d_out_planes_f64, uint32_t* d_out_source_mask,
+                             float* d_out_planes_f32, uint32_t* d_out_count);
+int pg_candidates_dimcap(pg_ctx* ctx, const pg_features* fs, const pg_dimcap_conf* conf, uint32_t n, const uint64_t* rows, const double* score,
+                         const uint8_t* source, uint64_t* out_rows, double* out_score, uint8_t* out_source, uint32_t* out_count);
+
 /* DiversityAdjustCountFilter on the device: quotas per expression class (csrc/classcut.hip).  The fourth reference
  * filter of the slot between UniqueFilter and RankService.Rank (service/user_recommend.go:105-137): every AdjustCountConfig gives
  * its quota not to a recall but to the items for which a govaluate expression over the item's features is true

@@ -56,6 +56,8 @@ EXPORTS = [
     "pg_cond_compile", "pg_cond_free", "pg_cond_num_rules", "pg_cond_num_user_slots", "pg_cond_user_slot_name",
     "pg_cond_user_slot_is_float", "pg_cond_match_host", "pg_boost_scores_host", "pg_item_state_filter_dev", "pg_boost_scores_dev",
     "pg_item_state_filter", "pg_boost_scores",
+    "pg_distinct_ids_host", "pg_distinct_ids_dev", "pg_distinct_ids",
+    "pg_candidates_dimcap_host", "pg_candidates_dimcap_dev", "pg_candidates_dimcap",
     "pg_classcut_compile", "pg_classcut_free", "pg_classcut_num_classes", "pg_classcut_reads_recall_name", "pg_classcut_out_cap",
     "pg_classcut_masks_host", "pg_candidates_classcut_host", "pg_classcut_masks_dev", "pg_candidates_classcut_dev",
     "pg_candidates_classcut",
@@ -162,6 +164,11 @@ class PgCondRule(C.Structure):
 
 class PgCondCol(C.Structure):
     _fields_ = [("name", C.c_char_p), ("dtype", C.c_int32)]
+
+
+class PgDimcapConf(C.Structure):
+    _fields_ = [("column", C.c_char_p), ("limit", C.c_uint32), ("null_mode", C.c_uint32), ("has_null", C.c_uint32),
+                ("null_value", C.c_int64)]
 
 
 class PgClasscutRule(C.Structure):
@@ -323,6 +330,12 @@ def load():
         "pg_boost_scores_dev": [vp, vp, vp, u32, u32, u32, vp, vp, vp, vp, vp, vp, vp],
         "pg_item_state_filter": [vp, vp, vp, u32, vp, vp, vp, vp, u32, vp, vp, vp, vp],
         "pg_boost_scores": [vp, vp, u32, u32, vp, P(vp), vp, u32, vp, vp, vp],
+        "pg_distinct_ids_host": [vp, vp, u32, vp, P(vp), vp, u32, vp],
+        "pg_distinct_ids_dev": [vp, vp, vp, vp, u32, u32, vp, vp, vp, vp, vp],
+        "pg_distinct_ids": [vp, vp, vp, u32, vp, P(vp), vp, u32, vp],
+        "pg_candidates_dimcap_host": [P(PgDimcapConf), u32, u32, vp, vp, vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp],
+        "pg_candidates_dimcap_dev": [vp, vp, P(PgDimcapConf), u32, u32, vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp],
+        "pg_candidates_dimcap": [vp, vp, P(PgDimcapConf), u32, vp, vp, vp, vp, vp, vp, vp],
         "pg_classcut_compile": [P(PgClasscutRule), u32, P(PgCondCol), u32, P(C.c_char_p), u32, P(vp)],
         "pg_classcut_free": [vp],
         "pg_classcut_num_classes": [vp],

@@ -1,5 +1,6 @@
 // cand_lists.hpp — the candidate lists of nq requests, stated once for the stages that read and write them: the trim (trim.hip),
-// the blend (blend.hip), the class cut (classcut.hip), the V2 quota cut (trim2.hip) and ItemStateFilter (cond.hip); the fan-in
+// the blend (blend.hip), the class cut (classcut.hip), the V2 quota cut (trim2.hip), ItemStateFilter (cond.hip) and the value
+// cap (dimcap.hip); the fan-in
 // (fanin.hip), which makes them, takes the constants.  Three parts: what the kernels and the host statements
 // move (CandIn / CandOut, cand_carry, cand_pad, the sort order and the bit cast); what an entry point is handed (CandCall) and
 // the checks every stage runs over it, each in its own order; the staging of a one-request call on host arrays (Staged).
@@ -96,6 +97,20 @@ __host__ __device__ __forceinline__ void cand_pad(const CandIn& in, const CandOu
         for (uint32_t f = 0; f < in.n_f64; ++f) out.planes64[f * out_plane + o] = kCandNan;
         for (uint32_t f = 0; f < in.n_f32; ++f) out.planes32[f * out_plane + o] = 0u;
     }
+}
+
+// Accesses of a per-request open-addressed table that lives in LDS or in context scratch (the fan-in's and the value cap's two
+// tiers).  LDS: workgroup scope.  Scratch: every read and write of a slot is an agent-scope atomic, so all of them meet in L2
+// whatever the lanes' L1 holds.
+template <bool kLds, typename T>
+__device__ inline T tab_load(T* p) {
+    if constexpr (kLds) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    else return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+template <bool kLds, typename T>
+__device__ inline void tab_store(T* p, T v) {
+    if constexpr (kLds) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    else __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // ---- an entry point's arguments ---------------------------------------------------------------------------------------------------

@@ -87,6 +87,7 @@ enum ScratchSlot : int {
     kSlotTrim2 = 28,         // trim2.hip: segment offsets, per-rule keys and orders of a V2 quota cut
     kSlotMix = 29,           // mixsort.hip: the strategy masks and the taken lists of a mix sort; the one-request entry's staging behind them
     kSlotSsdStage = 30,      // ssd.hip pg_ssd_sort_dev: per-request counts and states, the position maps, the cut lists' rows and quality, the picks (kSlotWork stays the grid kernel's)
+    kSlotDimcap = 31,        // dimcap.hip: the scratch tier's keys and counts of a value cap; the one-request entry's staging behind them
     kSlotCount
 };
 

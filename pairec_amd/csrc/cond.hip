@@ -36,6 +36,8 @@
 //                              counts in LDS (two sets: a wave one chunk ahead writes the other), every lane adds up the counts
 //                              itself, so one barrier per chunk; kept entries move to the front with everything carried.
 //   boost_scores_kernel        256 lanes per workgroup, grid (cap / 256, nq).
+//   distinct_ids_kernel        the same grid: DistinctIdSort (sort/distinct_id_sort.go:52-72) — the id of the
+//                              first rule that matches, else the entry's position + 1.
 #include "pipeline.hpp"
 #include "cond_eval.hpp"
 #include "expr_prog.hpp"
@@ -175,6 +177,38 @@ __global__ __launch_bounds__(kBoostThreads) void boost_scores_kernel(CondProgram
     }
     out_score[i] = bits;                                                 // padding entries keep their score bits
     if (out_rule) out_rule[i] = (uint8_t)last;
+}
+
+// DistinctIdSort.doSort's inner loop for one item at position pos (distinct_id_sort.go:57-67, every condition under one name):
+// the id of the first rule that matches, else pos + 1 (an evaluation error is cond_rule's false, and :60's err != nil a non-match)
+struct DistinctIds { long long id[kCondMaxRules]; };
+__host__ __device__ __forceinline__ long long cond_distinct_id(const CondProgram& p, const DistinctIds& ids, const CondItem& it, const CondUser& u, uint32_t pos) {
+    for (uint32_t r = 0; r < p.n_rules; ++r)
+        if (cond_rule(p, r, it, u)) return ids.id[r];
+    return (long long)pos + 1;
+}
+
+// Request q = blockIdx.y, positions blockIdx.x * 256 ...
+__global__ __launch_bounds__(kBoostThreads) void distinct_ids_kernel(CondProgram p, DistinctIds ids, const uint64_t* __restrict__ rows,
+                                                                     const uint32_t* __restrict__ count,
+                                                                     const unsigned long long* __restrict__ user_vals,
+                                                                     const uint32_t* __restrict__ user_present, uint32_t cap,
+                                                                     long long* __restrict__ out_id) {
+    const uint32_t q = blockIdx.y, pos = blockIdx.x * kBoostThreads + threadIdx.x;
+    if (pos >= cap) return;
+    const size_t i = (size_t)q * cap + pos;
+    const uint32_t n_valid = count ? min(count[q], cap) : cap;
+    const unsigned long long row = rows[i];
+    long long id = 0;                                                    // padding entries get 0
+    if (pos < n_valid && row != kCandPad) {
+        CondUser u;
+        u.vals = user_vals ? user_vals + (size_t)q * kCondMaxSlots : nullptr;
+        u.present = user_present ? user_present[q] : 0u;
+        CondItem item;
+        cond_load(p, row, &item);
+        id = cond_distinct_id(p, ids, item, u, pos);
+    }
+    out_id[i] = id;
 }
 
 }  // namespace
@@ -415,6 +449,45 @@ int boost_scores_locked(pg_ctx* ctx, pg_cond* c, const pg_features* fs, uint32_t
     return PG_OK;
 }
 
+int distinct_ids_locked(pg_ctx* ctx, pg_cond* c, const pg_features* fs, const int64_t* ids, uint32_t nq, uint32_t cap, const uint64_t* d_rows,
+                        const uint32_t* d_count, const uint64_t* d_user_vals, const uint32_t* d_user_present, int64_t* d_out_id, const char* who) {
+    CondProgram p;
+    int rc;
+    if ((rc = cond_bind_locked(ctx, c, fs, who, &p))) return rc;
+    DistinctIds di{};
+    for (size_t r = 0; r < c->rules.size(); ++r) di.id[r] = ids[r];
+    distinct_ids_kernel<<<dim3((cap + kBoostThreads - 1) / kBoostThreads, nq), kBoostThreads, 0, ctx->stream>>>(
+        p, di, d_rows, d_count, reinterpret_cast<const unsigned long long*>(d_user_vals), d_user_present, cap, reinterpret_cast<long long*>(d_out_id));
+    PG_HIP(hipGetLastError());
+    return PG_OK;
+}
+
+// The one-request entries over the candidates' own values (pg_boost_scores, pg_distinct_ids): the values become a store of n
+// rows in scratch, candidate i reads row i, one outside the store row n.  rows_of: the row ids to stage; stage_cols appends
+// the referenced columns to the staging list (a column of up to 8-byte values each), store_of makes the store over them once
+// staged_run has placed them (it never owns: the columns point into scratch).
+void cond_own_rows(uint32_t n, const uint8_t* item_in, std::vector<uint64_t>* rows) {
+    rows->resize(n);
+    for (uint32_t i = 0; i < n; ++i) (*rows)[i] = !item_in || item_in[i] ? i : n;
+}
+void cond_stage_cols(const pg_cond* c, uint32_t n, const void* const* cols, std::vector<Staged>* st) {
+    for (size_t k = 0; k < c->used.size(); ++k) {
+        const int dt = c->col_dtypes[(size_t)c->used[k]];
+        st->push_back({cols[c->used[k]], (size_t)n * (dt == PG_F_I32 || dt == PG_F_F32 ? 4 : 8), Staged::kIn, (size_t)n * 8});
+    }
+}
+void cond_own_store(const pg_cond* c, uint32_t n, const Staged* staged_cols, pg_features* tmp) {
+    tmp->rows = n;
+    for (size_t k = 0; k < c->used.size(); ++k) {
+        const int d = c->used[k];
+        pg_features::Column col;
+        col.name = c->col_names[(size_t)d];
+        col.dtype = c->col_dtypes[(size_t)d];
+        col.d = staged_cols[k].dev;
+        tmp->cols.push_back(col);
+    }
+}
+
 }  // namespace
 }  // namespace pg
 
@@ -570,10 +643,8 @@ int pg_boost_scores(pg_ctx* ctx, pg_cond* c, uint32_t filter_all, uint32_t n, co
     if ((rc = pg::cond_host_check(c, cols, user_vals, "pg_boost_scores"))) return rc;
     std::lock_guard<std::mutex> g(ctx->mu);
     PG_HIP(hipSetDevice(ctx->device));
-    // the candidates' values become a store of n rows in scratch: candidate i reads row i, one outside the store row n
-    const size_t nu = c->used.size();
-    std::vector<uint64_t> rows(n);
-    for (uint32_t i = 0; i < n; ++i) rows[i] = !item_in || item_in[i] ? i : n;
+    std::vector<uint64_t> rows;
+    pg::cond_own_rows(n, item_in, &rows);
     uint64_t uv[pg::kCondMaxSlots] = {0};
     if (user_vals) memcpy(uv, user_vals, c->slot_names.size() * 8);
     using pg::Staged;
@@ -581,24 +652,75 @@ int pg_boost_scores(pg_ctx* ctx, pg_cond* c, uint32_t filter_all, uint32_t n, co
     std::vector<Staged> st = {{rows.data(), (size_t)n * 8, Staged::kIn},      {score, (size_t)n * 8, Staged::kIn},
                               {out_score, (size_t)n * 8, Staged::kOut},       {out_rule, n, Staged::out_if(out_rule)},
                               {uv, sizeof uv, Staged::kIn},                   {&user_present, 4, Staged::kIn}};
-    for (size_t k = 0; k < nu; ++k) {                 // a column of up to 8-byte values each
-        const int dt = c->col_dtypes[(size_t)c->used[k]];
-        st.push_back({cols[c->used[k]], (size_t)n * (dt == PG_F_I32 || dt == PG_F_F32 ? 4 : 8), Staged::kIn, (size_t)n * 8});
-    }
+    pg::cond_stage_cols(c, n, cols, &st);
     return pg::staged_run(ctx, pg::kSlotCond, st.data(), st.size(), true /* rows, uv and user_present are this frame's */, [&] {
-        pg_features tmp;                              // (never owns: the columns point into scratch)
-        tmp.rows = n;
-        for (size_t k = 0; k < nu; ++k) {
-            const int d = c->used[k];
-            pg_features::Column col;
-            col.name = c->col_names[(size_t)d];
-            col.dtype = c->col_dtypes[(size_t)d];
-            col.d = st[kCols + k].dev;
-            tmp.cols.push_back(col);
-        }
+        pg_features tmp;
+        pg::cond_own_store(c, n, st.data() + kCols, &tmp);
         return pg::boost_scores_locked(ctx, c, &tmp, filter_all, 1, n, st[kRows].at<uint64_t>(), st[kScore].at<double>(), nullptr,
                                        st[kUserVals].at<uint64_t>(), st[kUserPresent].at<uint32_t>(), st[kOutScore].at<double>(),
                                        st[kOutRule].at<uint8_t>());
+    });
+}
+
+// ---- DistinctIdSort ------------------------------------------------------------------------------------------------------------------
+int pg_distinct_ids_host(const pg_cond* c, const int64_t* ids, uint32_t n, const uint8_t* item_in, const void* const* cols,
+                         const uint64_t* user_vals, uint32_t user_present, int64_t* out_id) {
+    PG_REQUIRE(c && ids && (n == 0 || out_id), "pg_distinct_ids_host: NULL argument");
+    PG_REQUIRE(!c->boost, "pg_distinct_ids_host: the set was compiled as a boost rule set");
+    int rc;
+    if (n && (rc = pg::cond_host_check(c, cols, user_vals, "pg_distinct_ids_host"))) return rc;
+    pg::CondProgram p;
+    std::vector<const void*> none(c->col_names.size(), nullptr);
+    pg::cond_program(c, none.data(), c->lists.data(), c->progs.data(), 0, &p);
+    const pg::CondUser u{reinterpret_cast<const unsigned long long*>(user_vals), user_present};
+    pg::DistinctIds di{};
+    for (size_t r = 0; r < c->rules.size(); ++r) di.id[r] = ids[r];
+    for (uint32_t i = 0; i < n; ++i) {
+        pg::CondItem it;
+        pg::cond_host_item(c->used, c->col_dtypes, cols, item_in, i, &it);
+        out_id[i] = pg::cond_distinct_id(p, di, it, u, i);
+    }
+    return PG_OK;
+}
+
+int pg_distinct_ids_dev(pg_ctx* ctx, pg_cond* c, const pg_features* fs, const int64_t* ids, uint32_t nq, uint32_t cap, const uint64_t* d_rows,
+                        const uint32_t* d_count, const uint64_t* d_user_vals, const uint32_t* d_user_present, int64_t* d_out_id) {
+    const char* who = "pg_distinct_ids_dev";
+    PG_REQUIRE(ctx && c && fs && ids && d_rows && d_out_id, "%s: NULL argument", who);
+    PG_REQUIRE(!c->boost, "%s: the set was compiled as a boost rule set", who);
+    int rc;
+    if ((rc = pg::cond_check_shape(nq, cap, who))) return rc;
+    PG_REQUIRE(c->slot_names.empty() || (d_user_vals && d_user_present), "%s: the set reads user properties: d_user_vals and d_user_present are needed", who);
+    std::lock_guard<std::mutex> g(ctx->mu);
+    PG_HIP(hipSetDevice(ctx->device));
+    return pg::distinct_ids_locked(ctx, c, fs, ids, nq, cap, d_rows, d_count, d_user_vals, d_user_present, d_out_id, who);
+}
+
+int pg_distinct_ids(pg_ctx* ctx, pg_cond* c, const int64_t* ids, uint32_t n, const uint8_t* item_in, const void* const* cols,
+                    const uint64_t* user_vals, uint32_t user_present, int64_t* out_id) {
+    const char* who = "pg_distinct_ids";
+    PG_REQUIRE(ctx && c && ids && (n == 0 || out_id), "%s: NULL argument", who);
+    PG_REQUIRE(!c->boost, "%s: the set was compiled as a boost rule set", who);
+    int rc;
+    if (n == 0) return PG_OK;                        // an empty request: nothing to tag
+    if ((rc = pg::cond_check_shape(1, n, who))) return rc;
+    if ((rc = pg::cond_host_check(c, cols, user_vals, who))) return rc;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    PG_HIP(hipSetDevice(ctx->device));
+    std::vector<uint64_t> rows;
+    pg::cond_own_rows(n, item_in, &rows);
+    uint64_t uv[pg::kCondMaxSlots] = {0};
+    if (user_vals) memcpy(uv, user_vals, c->slot_names.size() * 8);
+    using pg::Staged;
+    enum { kRows, kOutId, kUserVals, kUserPresent, kCols };
+    std::vector<Staged> st = {{rows.data(), (size_t)n * 8, Staged::kIn}, {out_id, (size_t)n * 8, Staged::kOut}, {uv, sizeof uv, Staged::kIn},
+                              {&user_present, 4, Staged::kIn}};
+    pg::cond_stage_cols(c, n, cols, &st);
+    return pg::staged_run(ctx, pg::kSlotCond, st.data(), st.size(), true /* rows, uv and user_present are this frame's */, [&] {
+        pg_features tmp;
+        pg::cond_own_store(c, n, st.data() + kCols, &tmp);
+        return pg::distinct_ids_locked(ctx, c, &tmp, ids, 1, n, st[kRows].at<uint64_t>(), nullptr, st[kUserVals].at<uint64_t>(),
+                                       st[kUserPresent].at<uint32_t>(), st[kOutId].at<int64_t>(), who);
     });
 }
 

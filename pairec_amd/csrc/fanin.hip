@@ -103,19 +103,6 @@ __device__ inline uint32_t fanin_source_of(const FaninDesc& d, uint32_t n_src, u
     return s;
 }
 
-// Table accesses of the two tiers.  LDS: workgroup scope.  Scratch: every read and write of a slot is an agent-scope atomic,
-// so all of them meet in L2 whatever the lanes' L1 holds.
-template <bool kLds, typename T>
-__device__ inline T tab_load(T* p) {
-    if constexpr (kLds) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    else return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-template <bool kLds, typename T>
-__device__ inline void tab_store(T* p, T v) {
-    if constexpr (kLds) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    else __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 // the slot that holds `key` (it was inserted: the probe ends)
 template <bool kLds, typename Key>
 __device__ inline uint32_t fanin_find(Key* keys, Key key, uint32_t bits) {

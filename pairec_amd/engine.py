@@ -359,6 +359,51 @@ def cond_match_host(cond: Cond, cols=None, item_in=None, user=None, rule: int = 
     return cond.match_host(cols, item_in, user, rule, n)
 
 
+def distinct_ids_host(cond: Cond, ids, cols=None, item_in=None, user=None, n: Optional[int] = None) -> np.ndarray:
+    """pg_distinct_ids_host: DistinctIdSort's ids of the n candidates of one request, given as Cond.match_host's arguments; ids: one
+    int64 per rule of the set → [n] int64 (the first matching rule's id, else position + 1).  A host function, no device."""
+    di = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+    if di.shape[0] != cond.n_rules:
+        raise ValueError("distinct_ids_host: %d ids for %d rules" % (di.shape[0], cond.n_rules))
+    m, arrs, ptrs, inn, vals, present = cond._host_args(cols, item_in, user)
+    n = m if n is None else n
+    out = np.zeros(n or 0, dtype=np.int64)
+    _lib.check(cond.L.pg_distinct_ids_host(cond.h, _ptr(di), n or 0, None if inn is None else _ptr(inn), ptrs, _ptr(vals), present, _ptr(out)))
+    del arrs
+    return out
+
+
+# ---- the value cap: DimensionFieldUniqueFilter, one dimension of GroupWeightCountFilter's size limit ----
+DIMCAP_NULL_KEEP, DIMCAP_NULL_VALUE = 0, 1
+DIMCAP_CHUNK, DIMCAP_MIN_SLOTS, DIMCAP_LDS_MAX_CAP = 1024, 1024, 6144
+
+
+def _dimcap_conf(conf):
+    """(column, limit, null_mode, null_value | None) → pg_dimcap_conf; the column may be None for the host statement"""
+    column, limit, null_mode, null_value = conf
+    c = _lib.PgDimcapConf()
+    c.column = None if column is None else str(column).encode("utf-8")
+    c.limit, c.null_mode = int(limit), int(null_mode)
+    c.has_null, c.null_value = (0, 0) if null_value is None else (1, int(null_value))
+    return c
+
+
+def candidates_dimcap_host(conf, keys, rows, score, item_in=None, source=None, count=None, planes_f64=None, source_mask=None, planes_f32=None):
+    """pg_candidates_dimcap_host: the value cap on host arrays by the library's host statement (no context, no device); conf =
+    (column | None, limit, DIMCAP_NULL_KEEP | DIMCAP_NULL_VALUE, null_value | None), keys [nq][cap] int64 the entries' values,
+    item_in [nq][cap] 0 = the row is outside the store; the rest and the result as Context.candidates_dimcap."""
+    nq, cap, ins, outs, n64, n32 = _cand_arrays("candidates_dimcap_host", lambda cap: cap, rows, score, source, count, planes_f64,
+                                                source_mask, planes_f32)
+    k = np.ascontiguousarray(keys, dtype=np.int64)
+    inn = None if item_in is None else np.ascontiguousarray(item_in, dtype=np.uint8)
+    if k.shape != (nq, cap) or (inn is not None and inn.shape != (nq, cap)):
+        raise ValueError("candidates_dimcap_host: keys and item_in are [nq][cap]")
+    v = lambda a: None if a is None else _ptr(a)                                     # noqa: E731
+    _lib.check(_lib.load().pg_candidates_dimcap_host(C.byref(_dimcap_conf(conf)), nq, cap, _ptr(k), v(inn), v(ins[0]), v(ins[1]), v(ins[2]),
+                                                     v(ins[3]), v(ins[4]), n64, v(ins[5]), v(ins[6]), n32, *[v(a) for a in outs]))
+    return tuple(outs)
+
+
 class Classcut:
     """A compiled DiversityAdjustCountFilter (pg_classcut_compile): 1..8 classes, each a govaluate boolean expression over declared
     item columns, recall_score and recall_name with a quota.  rules: [(expression, TRIM_FIX | TRIM_ACCUMULATE, count)]; cols:
@@ -943,6 +988,74 @@ class Context:
                                           _ptr(vals), present, _ptr(sc), _ptr(out), _ptr(rule)))
         del arrs
         return out, rule
+
+    # ---- DistinctIdSort and the value cap (DimensionFieldUniqueFilter) ---------------------------------
+    def distinct_ids_dev(self, cond, fs, ids, nq: int, cap: int, d_rows: int, d_count: int, d_user_vals: int, d_user_present: int,
+                         d_out_id: int) -> None:
+        """pg_distinct_ids_dev: ids a HOST array of one int64 per rule, the rest device addresses (0 = absent), d_out_id [nq][cap]
+        int64.  Enqueued on the context's stream: synchronize() before reading."""
+        di = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+        if di.shape[0] != cond.n_rules:
+            raise ValueError("distinct_ids_dev: %d ids for %d rules" % (di.shape[0], cond.n_rules))
+        v = lambda p: C.c_void_p(p or None)                                          # noqa: E731
+        _lib.check(self.L.pg_distinct_ids_dev(self.h, cond.h, getattr(fs, "h", fs), _ptr(di), nq, cap, v(d_rows), v(d_count), v(d_user_vals),
+                                              v(d_user_present), v(d_out_id)))
+
+    def distinct_ids(self, cond, fs, ids, rows, count=None, users=None) -> np.ndarray:
+        """DistinctIdSort's ids on host arrays (pg_distinct_ids_dev): rows [nq][cap] u64, count [nq], users: one {name: value} per
+        request → [nq][cap] int64 (the first matching rule's id, else position + 1; padding 0)."""
+        r = np.ascontiguousarray(rows, dtype=np.uint64)
+        if r.ndim != 2:
+            raise ValueError("distinct_ids: rows is [nq][cap]")
+        nq, cap = r.shape
+        cnt = None if count is None else np.ascontiguousarray(count, dtype=np.uint32)
+        uv, up = self._cond_user(cond, users, nq)
+        return self._cand_run([r, cnt, uv, up], [np.empty((nq, cap), np.int64)],
+                              lambda d_in, d_out: self.distinct_ids_dev(cond, fs, ids, nq, cap, *d_in, *d_out))[0]
+
+    def distinct_ids_one(self, cond, ids, cols=None, item_in=None, user=None, n: Optional[int] = None) -> np.ndarray:
+        """pg_distinct_ids: one request on host arrays, distinct_ids_host's arguments (what the host mirror calls) → [n] int64"""
+        di = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+        if di.shape[0] != cond.n_rules:
+            raise ValueError("distinct_ids_one: %d ids for %d rules" % (di.shape[0], cond.n_rules))
+        m, arrs, ptrs, inn, vals, present = cond._host_args(cols, item_in, user)
+        n = m if n is None else n
+        out = np.zeros(n or 0, dtype=np.int64)
+        _lib.check(self.L.pg_distinct_ids(self.h, cond.h, _ptr(di), n or 0, None if inn is None else _ptr(inn), ptrs, _ptr(vals), present,
+                                          _ptr(out)))
+        del arrs
+        return out
+
+    def candidates_dimcap_dev(self, conf, fs, nq: int, cap: int, d_rows: int, d_score: int, d_source: int, d_count: int, d_planes_f64: int,
+                              n_f64: int, d_source_mask: int, d_planes_f32: int, n_f32: int, d_out_rows: int, d_out_score: int,
+                              d_out_source: int, d_out_planes_f64: int, d_out_source_mask: int, d_out_planes_f32: int,
+                              d_out_count: int) -> None:
+        """pg_candidates_dimcap_dev: conf = (column, limit, DIMCAP_NULL_KEEP | DIMCAP_NULL_VALUE, null_value | None), everything
+        else device addresses as candidates_trim_dev (0 = absent; an output is required exactly where its input is given),
+        outputs [nq][cap].  Enqueued on the context's stream: synchronize() before reading."""
+        self._list_call(self.L.pg_candidates_dimcap_dev, (getattr(fs, "h", fs), C.byref(_dimcap_conf(conf))), nq, cap,
+                        (d_rows, d_score, d_source, d_count, d_planes_f64, n_f64, d_source_mask, d_planes_f32, n_f32, d_out_rows, d_out_score,
+                         d_out_source, d_out_planes_f64, d_out_source_mask, d_out_planes_f32, d_out_count))
+
+    def candidates_dimcap(self, conf, fs, rows, score, source=None, count=None, planes_f64=None, source_mask=None, planes_f32=None):
+        """The value cap on host arrays (pg_candidates_dimcap_dev): the arrays of candidates_trim against the store's column
+        conf[0] → (rows, score, source, planes_f64, source_mask, planes_f32, count), [nq][cap] each, None where the input was
+        None."""
+        nq, cap, ins, outs, n64, n32 = _cand_arrays("candidates_dimcap", lambda cap: cap, rows, score, source, count, planes_f64,
+                                                    source_mask, planes_f32)
+        return self._cand_run(ins, outs, lambda d_in, d_out: self.candidates_dimcap_dev(
+            conf, fs, nq, cap, d_in[0], d_in[1], d_in[2], d_in[3], d_in[4], n64, d_in[5], d_in[6], n32, *d_out))
+
+    def candidates_dimcap_one(self, conf, fs, rows, score, source=None):
+        """pg_candidates_dimcap: one request on host arrays (what the host mirror calls) → (rows [n], score [n], source [n] | None, count)"""
+        r = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1)
+        sc = np.ascontiguousarray(score, dtype=np.float64).reshape(-1)
+        src = None if source is None else np.ascontiguousarray(source, dtype=np.uint8).reshape(-1)
+        o_r, o_s, o_src, cnt = np.empty_like(r), np.empty_like(sc), None if src is None else np.empty_like(src), C.c_uint32()
+        _lib.check(self.L.pg_candidates_dimcap(self.h, getattr(fs, "h", fs), C.byref(_dimcap_conf(conf)), r.shape[0], _ptr(r), _ptr(sc),
+                                               None if src is None else _ptr(src), _ptr(o_r), _ptr(o_s),
+                                               None if src is None else _ptr(o_src), C.byref(cnt)))
+        return o_r, o_s, o_src, cnt.value
 
     # ---- DiversityAdjustCountFilter: quotas per expression class ---------------------------------------
     def classcut_masks_dev(self, cc, fs, nq: int, cap: int, d_rows: int, d_score: int, d_source: int, d_count: int, d_out_masks: int) -> None:

@@ -259,6 +259,28 @@ bool CheckBoostScoreConf(const json::Value& sc, std::string* why) {
     }
     return true;
 }
+// a DistinctIdSort entry (sort/distinct_id_sort.go:17-42).  The reference writes each condition's id under the condition's own
+// DistinctIdName; the device writes one id per item, so one sort serves one name — two names are two sorts, which write the same
+// properties (distinct_id_sort_test.go, "multi distinctid name").
+bool CheckDistinctIdConf(const json::Value& sc, std::string* why) {
+    const auto& conds = sc.at("DistinctIdConditions").arr;
+    if (conds.size() > PG_COND_MAX_RULES) { *why = "more than " + std::to_string(PG_COND_MAX_RULES) + " DistinctIdConditions"; return false; }
+    for (const auto& c : conds) {
+        if (!CheckFilterParams(c.at("Conditions"), true, why)) return false;
+        const json::Value& id = c.at("DistinctId");
+        if (id.type != json::Value::Null && (id.type != json::Value::Number || id.num != std::floor(id.num) || std::fabs(id.num) >= 9e15)) {
+            *why = "DistinctId is not an integer";
+            return false;
+        }
+        auto name_of = [](const json::Value& x) { return x.s("DistinctIdName").empty() ? std::string("__distinct_id__") : x.s("DistinctIdName"); };
+        if (name_of(c) != name_of(conds[0])) {
+            *why = "DistinctIdName \"" + name_of(c) + "\" beside \"" + name_of(conds[0]) +
+                   "\": the device serves one name per sort (declare one DistinctIdSort per name: they write the same properties)";
+            return false;
+        }
+    }
+    return true;
+}
 // a MultiRecallMixSort entry that pg_mix_compile accepts; what it refuses is named by key.  Rules with an unknown MixStrategy are
 // skipped, as createMixStrategies skips them (multi_recall_mix_sort.go:47-58).
 bool CheckMixSortConf(const json::Value& sc, std::string* why) {
@@ -545,6 +567,14 @@ bool RecommendConfig::Parse(const std::string& text, RecommendConfig* out, std::
                 return false;
             }
         }
+        if (c.SortType == "DistinctIdSort") {
+            c.DistinctConf = sc;
+            std::string why;
+            if (!CheckDistinctIdConf(sc, &why)) {
+                if (err) *err = "pairec_gpu.Sorts: " + c.Name + ": DistinctIdSort: " + why;
+                return false;
+            }
+        }
         out->GpuSorts.push_back(c);
     }
     for (const auto& fc : out->UserDefineConfs.at("pairec_gpu").at("Filters").arr) {
@@ -644,6 +674,21 @@ bool RecommendConfig::Parse(const std::string& text, RecommendConfig* out, std::
                 if (colon != std::string::npos) why = why.substr(colon + 2);
             }
             if (!why.empty()) why = c.FilterType + ": " + why;
+        }
+        else if (c.IsDimcap()) {
+            // NewDimensionFieldUniqueFilter (dimension_field_unique_filter.go:17-24) takes any Dimension; an empty one makes every
+            // StringProperty "" and the filter a no-op, which a config never means
+            c.Dimension = fc.s("Dimension");
+            const json::Value& nv = fc.at("NullValue");
+            if (c.Dimension.empty()) why = "DimensionFieldUniqueFilter: Dimension is empty";
+            else if (!c.FeatureStore.empty() && c.FeatureStore != "item_features")
+                why = "FeatureStore \"" + c.FeatureStore + "\" (the engine holds one store of item columns, \"item_features\")";
+            else if (nv.type != json::Value::Null && (nv.type != json::Value::Number || nv.num != std::floor(nv.num) || std::fabs(nv.num) >= 9e15))
+                why = "DimensionFieldUniqueFilter: NullValue is not an integer (the store's columns are integers: the code that stands for \"\")";
+            else if (nv.type == json::Value::Number) {
+                c.HasNullValue = true;
+                c.NullValue = nv.is_int ? nv.i : (long long)nv.num;
+            }
         }
         else if (c.FilterType != "ItemStateFilter") why = "unknown FilterType \"" + c.FilterType + "\" (the device serves ItemStateFilter)";
         else if (!c.FeatureStore.empty() && c.FeatureStore != "item_features")
@@ -1843,7 +1888,98 @@ bool cond_user_slots(pg_cond* c, const module::User* user, CondBuild* b, uint64_
     }
     return true;
 }
+// the item properties a built condition set names, as candidate-aligned columns: strings dictionary-encoded through the build's
+// map, numbers as int64 where every item holds an integer and fp64 otherwise
+struct CondColumns {
+    std::vector<std::vector<long long>> ints;
+    std::vector<std::vector<double>> floats;
+    std::vector<pg_cond_col> cols;              // (the names point into the build's item_names)
+    std::vector<const void*> col_ptr;
+    bool fill(CondBuild* b, const std::vector<module::ItemPtr>& data, std::string* why) {
+        const size_t nc = b->item_names.size(), n = data.size();
+        ints.resize(nc); floats.resize(nc); cols.resize(nc); col_ptr.resize(nc);
+        for (size_t c = 0; c < nc; ++c) {
+            const std::string& name = b->item_names[c];
+            const int kind = b->item_kind[name];
+            if ((kind & 1) && (kind & 2)) { *why = "property \"" + name + "\" is read both as a string and as a number"; return false; }
+            bool whole = true;
+            for (size_t i = 0; i < n; ++i) {
+                const auto p = data[i]->Properties.find(name);
+                if (p == data[i]->Properties.end()) { *why = "item " + data[i]->Id + " has no property \"" + name + "\""; return false; }
+                if (kind & 1) continue;
+                if (p->second.type != json::Value::Number) { *why = "item " + data[i]->Id + ": property \"" + name + "\" is not a number"; return false; }
+                whole = whole && (p->second.is_int || (p->second.num == std::floor(p->second.num) && std::fabs(p->second.num) < 9e15));
+            }
+            cols[c].name = name.c_str();
+            if ((kind & 1) || whole) {
+                ints[c].resize(n);
+                for (size_t i = 0; i < n; ++i) {
+                    const json::Value& v = data[i]->Properties.find(name)->second;
+                    ints[c][i] = (kind & 1) ? b->code(feature::ItemStringProperty(*data[i], name)) : (v.is_int ? v.i : (long long)v.num);
+                }
+                cols[c].dtype = PG_F_I64;
+                col_ptr[c] = ints[c].data();
+            } else {
+                floats[c].resize(n);
+                for (size_t i = 0; i < n; ++i) floats[c][i] = data[i]->Properties.find(name)->second.num;
+                cols[c].dtype = PG_F_F64;
+                col_ptr[c] = floats[c].data();
+            }
+        }
+        return true;
+    }
+};
 }  // namespace
+
+// DistinctIdSort (sort/distinct_id_sort.go:52-72) through pg_distinct_ids: the conditions become the rules of one condition set
+// over the items' own properties, as GpuBoostScoreSort builds them, and the ids come back per item, to be written under the sort's
+// one DistinctIdName.  An item without a named property, a list over the device's cap or a set pg_cond_compile refuses leave the
+// items untouched and return an error, which the caller ignores as it ignores every sort's error.
+struct GpuDistinctIdSort : sort::ISort {
+    Engine* e;
+    json::Value conf;
+    GpuDistinctIdSort(Engine* eng, json::Value c) : e(eng), conf(std::move(c)) {}
+    bool Sort(sort::SortData* d, std::string* err) override {
+        const size_t n = d->Data.size();
+        const auto& conds = conf.at("DistinctIdConditions").arr;
+        if (n == 0 || conds.empty()) return true;                                  // (no condition: the loop at :59 adds nothing)
+        auto fail = [&](const std::string& what) { if (err) *err = "DistinctIdSort: " + what; return false; };
+        if (n > PG_TRIM_MAX_CAP) return fail(std::to_string(n) + " items (the device serves up to " + std::to_string(PG_TRIM_MAX_CAP) + ")");
+        const std::string name = conds[0].s("DistinctIdName").empty() ? "__distinct_id__" : conds[0].s("DistinctIdName");
+        std::map<std::string, long long> dict;
+        CondBuild b;
+        b.dict = &dict;
+        std::vector<std::vector<pg_cond_term>> terms(conds.size());
+        std::vector<pg_cond_rule> rules(conds.size());
+        std::vector<int64_t> ids(conds.size());
+        for (size_t r = 0; r < conds.size(); ++r) {
+            if (!b.build(conds[r].at("Conditions"), 0, &terms[r])) return fail(b.err);
+            rules[r] = pg_cond_rule{terms[r].data(), (uint32_t)terms[r].size(), nullptr};
+            ids[r] = (int64_t)conds[r].n("DistinctId");
+        }
+        CondColumns cc;
+        std::string cerr;
+        if (!cc.fill(&b, d->Data, &cerr)) return fail(cerr);
+        pg_cond* c = nullptr;
+        if (pg_cond_compile(rules.data(), (uint32_t)rules.size(), cc.cols.data(), (uint32_t)cc.cols.size(), 0, &c) != PG_OK) return fail(pg_last_error());
+        uint64_t uv[PG_COND_MAX_SLOTS] = {0};
+        uint32_t present = 0;
+        std::vector<int64_t> out(n);
+        std::string uerr;
+        const bool ok = cond_user_slots(c, d->User, &b, uv, &present, &uerr) &&
+                        pg_distinct_ids(e->ctx, c, ids.data(), (uint32_t)n, nullptr, cc.col_ptr.data(), uv, present, out.data()) == PG_OK;
+        const std::string why = ok ? std::string() : (uerr.empty() ? pg_err("pg_distinct_ids") : uerr);
+        pg_cond_free(c);
+        if (!ok) return fail(why);
+        for (size_t i = 0; i < n; ++i) {
+            json::Value v = json::Value::Num((double)out[i]);
+            v.is_int = true;
+            v.i = out[i];
+            d->Data[i]->Properties[name] = v;
+        }
+        return true;
+    }
+};
 
 struct GpuBoostScoreSort : sort::ISort {
     Engine* e;
@@ -1871,49 +2007,18 @@ struct GpuBoostScoreSort : sort::ISort {
                 if (strcmp(pg_expr_var_name(x, v), "score") != 0) b.item(pg_expr_var_name(x, v), 2);
             pg_expr_free(x);
         }
-        // the columns
-        const size_t nc = b.item_names.size();
-        std::vector<std::vector<long long>> ints(nc);
-        std::vector<std::vector<double>> floats(nc);
-        std::vector<pg_cond_col> cols(nc);
-        std::vector<const void*> col_ptr(nc);
-        for (size_t c = 0; c < nc; ++c) {
-            const std::string& name = b.item_names[c];
-            const int kind = b.item_kind[name];
-            if ((kind & 1) && (kind & 2)) return fail("property \"" + name + "\" is read both as a string and as a number");
-            bool whole = true;
-            for (size_t i = 0; i < n; ++i) {
-                const auto p = d->Data[i]->Properties.find(name);
-                if (p == d->Data[i]->Properties.end()) return fail("item " + d->Data[i]->Id + " has no property \"" + name + "\"");
-                if (kind & 1) continue;
-                if (p->second.type != json::Value::Number) return fail("item " + d->Data[i]->Id + ": property \"" + name + "\" is not a number");
-                whole = whole && (p->second.is_int || (p->second.num == std::floor(p->second.num) && std::fabs(p->second.num) < 9e15));
-            }
-            cols[c].name = name.c_str();
-            if ((kind & 1) || whole) {
-                ints[c].resize(n);
-                for (size_t i = 0; i < n; ++i) {
-                    const json::Value& v = d->Data[i]->Properties.find(name)->second;
-                    ints[c][i] = (kind & 1) ? b.code(feature::ItemStringProperty(*d->Data[i], name)) : (v.is_int ? v.i : (long long)v.num);
-                }
-                cols[c].dtype = PG_F_I64;
-                col_ptr[c] = ints[c].data();
-            } else {
-                floats[c].resize(n);
-                for (size_t i = 0; i < n; ++i) floats[c][i] = d->Data[i]->Properties.find(name)->second.num;
-                cols[c].dtype = PG_F_F64;
-                col_ptr[c] = floats[c].data();
-            }
-        }
+        CondColumns cc;
+        std::string cerr;
+        if (!cc.fill(&b, d->Data, &cerr)) return fail(cerr);
         pg_cond* c = nullptr;
-        if (pg_cond_compile(rules.data(), (uint32_t)rules.size(), cols.data(), (uint32_t)nc, 1, &c) != PG_OK) return fail(pg_last_error());
+        if (pg_cond_compile(rules.data(), (uint32_t)rules.size(), cc.cols.data(), (uint32_t)cc.cols.size(), 1, &c) != PG_OK) return fail(pg_last_error());
         uint64_t uv[PG_COND_MAX_SLOTS] = {0};
         uint32_t present = 0;
         std::vector<double> score(n), out(n);
         for (size_t i = 0; i < n; ++i) score[i] = d->Data[i]->Score;
         std::string uerr;
         const bool ok = cond_user_slots(c, d->User, &b, uv, &present, &uerr) &&
-                        pg_boost_scores(e->ctx, c, conf.at("BoostScoreConditionsFilterAll").b ? 1u : 0u, (uint32_t)n, nullptr, col_ptr.data(), uv, present,
+                        pg_boost_scores(e->ctx, c, conf.at("BoostScoreConditionsFilterAll").b ? 1u : 0u, (uint32_t)n, nullptr, cc.col_ptr.data(), uv, present,
                                         score.data(), out.data(), nullptr) == PG_OK;
         const std::string why = ok ? std::string() : (uerr.empty() ? pg_err("pg_boost_scores") : uerr);
         pg_cond_free(c);
@@ -2122,6 +2227,34 @@ bool item_state_filter(Engine* self, const recconf::GpuFilterConfig& conf, const
     const std::string why = ok ? std::string() : (uerr.empty() ? pg_err("pg_item_state_filter") : uerr);
     pg_cond_free(c);
     if (!ok) return fail(why);
+    std::vector<module::ItemPtr> kept(count);
+    for (uint32_t k = 0; k < count; ++k) kept[k] = (*items)[(size_t)out_pos[k]];
+    items->swap(kept);
+    return true;
+}
+
+// DimensionFieldUniqueFilter (filter/dimension_field_unique_filter.go:33-55) through pg_candidates_dimcap over the engine's feature
+// columns: the first item of each value of the Dimension column is kept; an item whose id the table does not know, or whose
+// value is the configured NullValue, is the item whose StringProperty is "" and is always kept (:41-42).  The position rides in
+// the score plane, as in item_state_filter.
+bool dimension_unique_filter(Engine* self, const recconf::GpuFilterConfig& conf, std::vector<module::ItemPtr>* items, std::string* err) {
+    const size_t n = items->size();
+    if (n == 0) return true;
+    auto fail = [&](const std::string& what) { if (err) *err = "DimensionFieldUniqueFilter " + conf.Name + ": " + what; return false; };
+    if (n > PG_TRIM_MAX_CAP) return fail(std::to_string(n) + " items (the device serves up to " + std::to_string(PG_TRIM_MAX_CAP) + ")");
+    if (!self->feats) return fail("the engine has no feature columns");
+    if (pg_features_column_index(self->feats, conf.Dimension.c_str()) < 0) return fail("\"" + conf.Dimension + "\" is not a feature column");
+    std::vector<uint64_t> rows(n), out_rows(n);
+    std::vector<double> pos(n), out_pos(n);
+    for (size_t i = 0; i < n; ++i) {
+        uint32_t row;
+        rows[i] = self->RowOfId((*items)[i]->Id, &row) ? row : self->table_rows;
+        pos[i] = (double)i;
+    }
+    const pg_dimcap_conf dc{conf.Dimension.c_str(), 1u, PG_DIMCAP_NULL_KEEP, conf.HasNullValue ? 1u : 0u, (int64_t)conf.NullValue};
+    uint32_t count = 0;
+    if (pg_candidates_dimcap(self->ctx, self->feats, &dc, (uint32_t)n, rows.data(), pos.data(), nullptr, out_rows.data(), out_pos.data(), nullptr, &count) != PG_OK)
+        return fail(pg_err("pg_candidates_dimcap"));
     std::vector<module::ItemPtr> kept(count);
     for (uint32_t k = 0; k < count; ++k) kept[k] = (*items)[(size_t)out_pos[k]];
     items->swap(kept);
@@ -2888,6 +3021,7 @@ Engine* Engine::Create(const std::string& config_json, std::string* err) {
         else if (sc.SortType == "DiversityRuleSort") e->sorts.RegisterSort(sc.Name, std::make_shared<GpuDiversityRuleSort>(e.get(), sc.DiversityConf), nullptr);
         else if (sc.SortType == "BoostScoreSort") e->sorts.RegisterSort(sc.Name, std::make_shared<GpuBoostScoreSort>(e.get(), sc.BoostConf), nullptr);
         else if (sc.SortType == "MultiRecallMixSort") e->sorts.RegisterSort(sc.Name, std::make_shared<GpuMultiRecallMixSort>(e.get(), sc.MixConf), nullptr);
+        else if (sc.SortType == "DistinctIdSort") e->sorts.RegisterSort(sc.Name, std::make_shared<GpuDistinctIdSort>(e.get(), sc.DistinctConf), nullptr);
         else { if (err) *err = "pairec_gpu.Sorts: unknown SortType " + sc.SortType; return nullptr; }
     }
     for (const auto& fc : e->config.GpuFilters) e->gpu_filters[fc.Name] = fc;
@@ -2952,6 +3086,9 @@ Engine* Engine::Create(const std::string& config_json, std::string* err) {
 
 bool Engine::ItemStateFilter(const recconf::GpuFilterConfig& conf, const module::User* user, std::vector<module::ItemPtr>* items, std::string* err) {
     return item_state_filter(this, conf, user, items, err);
+}
+bool Engine::DimensionUniqueFilter(const recconf::GpuFilterConfig& conf, std::vector<module::ItemPtr>* items, std::string* err) {
+    return dimension_unique_filter(this, conf, items, err);
 }
 
 bool Engine::BlendFilter(const recconf::GpuFilterConfig& conf, std::vector<module::ItemPtr>* items, std::string* err) {
@@ -3328,7 +3465,7 @@ const char* ph_engine_sort(void* h, const char* sort_name, const char* items_jso
 
 // one registered sort over caller-made items, as ph_engine_sort, with the user's properties (a JSON object or NULL); the answer
 // carries the scores: {"items":[{"item_id","score",…}]}
-const char* ph_engine_sort_scored(void* h, const char* sort_name, const char* items_json, const char* user_json, int size) {
+static const char* engine_sort_user(void* h, const char* sort_name, const char* items_json, const char* user_json, int size, bool with_properties) {
     if (!h) { g_ph_err = "ph_engine_sort_scored: NULL engine"; return nullptr; }
     Engine* e = (Engine*)h;
     json::Value root, uroot;
@@ -3352,7 +3489,36 @@ const char* ph_engine_sort_scored(void* h, const char* sort_name, const char* it
         sd.Data.push_back(item);
     }
     if (!s->Sort(&sd, &err)) { g_ph_err = err; return nullptr; }
-    return items_to_json(sd.Data);
+    if (!with_properties) return items_to_json(sd.Data);
+    // {"items":[{"item_id","properties":{name: number | string}}]}: what a sort that tags its items (DistinctIdSort) leaves in them
+    std::string& o = g_ph_out;
+    o = "{\"items\":[";
+    for (size_t i = 0; i < sd.Data.size(); ++i) {
+        if (i) o += ",";
+        o += "{\"item_id\":";
+        json::Escape(sd.Data[i]->Id, &o);
+        o += ",\"properties\":{";
+        bool first = true;
+        for (const auto& kv : sd.Data[i]->Properties) {
+            if (kv.second.type != json::Value::Number && kv.second.type != json::Value::String) continue;
+            if (!first) o += ",";
+            first = false;
+            json::Escape(kv.first, &o);
+            o += ":";
+            if (kv.second.type == json::Value::String) json::Escape(kv.second.str, &o);
+            else o += kv.second.is_int ? std::to_string(kv.second.i) : json::NumToString(kv.second.num);
+        }
+        o += "}}";
+    }
+    o += "]}";
+    return o.c_str();
+}
+const char* ph_engine_sort_scored(void* h, const char* sort_name, const char* items_json, const char* user_json, int size) {
+    return engine_sort_user(h, sort_name, items_json, user_json, size, false);
+}
+// the same call; the answer carries the items' properties instead of their scores
+const char* ph_engine_sort_props(void* h, const char* sort_name, const char* items_json, const char* user_json, int size) {
+    return engine_sort_user(h, sort_name, items_json, user_json, size, true);
 }
 
 // one pairec_gpu.Filters entry over caller-made items [{"id","score"}, optionally "retrieve_id" and "recall_scores" {recall: score}

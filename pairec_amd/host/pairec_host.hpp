@@ -155,12 +155,15 @@ struct SortConfig {                        // recconf.go:820-838: Name, SortType
     json::Value MixConf;                   // pairec_gpu.Sorts entries of SortType MultiRecallMixSort only: the entry itself (MixSortRules[]
                                            // {MixStrategy, Positions, PositionField, Number, NumberRate, RecallNames, Conditions}, RemainItem,
                                            // Size: recconf.go SortConfig / MixSortConfig; Seed: ours, default 0)
+    json::Value DistinctConf;              // pairec_gpu.Sorts entries of SortType DistinctIdSort only: the entry itself (DistinctIdConditions[]
+                                           // {Conditions, DistinctId, DistinctIdName}: recconf.go SortConfig / DistinctIdCondition)
 };
 // pairec_gpu.Filters: FilterType "ItemStateFilter" (filter/item_state_filter.go:47-57) over the engine's feature columns
 // … "SnakeFilter" (filter/snake_filter.go:118-241: AdjustCountConfs[{RecallName, Weight}], RetainNum, SnakeType) and
 // "CompletelyFairCountFilter" (filter/completely_fair_count_filter.go:18-94: RetainNum) through pg_candidates_blend_dev
 // … and "DiversityAdjustCountFilter" (filter/diversity_adjust_count_filter.go:44-143) through pg_candidates_classcut
 // … and "PriorityAdjustCountFilter" / "PriorityAdjustCountFilterV2" through pg_candidates_trim_dev / pg_candidates_trim2_dev
+// … and "DimensionFieldUniqueFilter" (filter/dimension_field_unique_filter.go:33-55) through pg_candidates_dimcap
 struct GpuFilterConfig {
     std::string Name, FilterType, FeatureStore;
     json::Value FilterParams;              // [FilterParamConfig] (recconf.go:884-891)
@@ -183,6 +186,12 @@ struct GpuFilterConfig {
     std::vector<pg_trim_rule> Quotas;
     std::vector<std::string> QuotaSources;
     bool IsQuota() const { return FilterType == "PriorityAdjustCountFilter" || FilterType == "PriorityAdjustCountFilterV2"; }
+    // "DimensionFieldUniqueFilter" (filter/dimension_field_unique_filter.go:33-55) through pg_candidates_dimcap: Dimension names a
+    // column of the engine's item_features store; NullValue (optional) is the value that stands for the "" StringProperty returns
+    std::string Dimension;
+    bool HasNullValue = false;
+    long long NullValue = 0;
+    bool IsDimcap() const { return FilterType == "DimensionFieldUniqueFilter"; }
 };
 struct FeatureConfig {                      // recconf.go:256-265
     std::string FeatureType, FeatureName, FeatureSource, FeatureValue, FeatureStore, Normalizer, Expression;
@@ -504,9 +513,10 @@ public:
     bool BlendFilter(const recconf::GpuFilterConfig& conf, std::vector<module::ItemPtr>* items, std::string* err);   // SnakeFilter, CompletelyFairCountFilter
     bool ClasscutFilter(const recconf::GpuFilterConfig& conf, std::vector<module::ItemPtr>* items, std::string* err);   // DiversityAdjustCountFilter
     bool QuotaFilter(const recconf::GpuFilterConfig& conf, std::vector<module::ItemPtr>* items, std::string* err);   // PriorityAdjustCountFilter, PriorityAdjustCountFilterV2
+    bool DimensionUniqueFilter(const recconf::GpuFilterConfig& conf, std::vector<module::ItemPtr>* items, std::string* err);   // DimensionFieldUniqueFilter
     // one pairec_gpu.Filters entry, whatever its FilterType
     bool RunGpuFilter(const recconf::GpuFilterConfig& conf, const module::User* user, std::vector<module::ItemPtr>* items, std::string* err) {
-        return conf.IsBlend() ? BlendFilter(conf, items, err) : conf.IsClasscut() ? ClasscutFilter(conf, items, err) : conf.IsQuota() ? QuotaFilter(conf, items, err) : ItemStateFilter(conf, user, items, err);
+        return conf.IsBlend() ? BlendFilter(conf, items, err) : conf.IsClasscut() ? ClasscutFilter(conf, items, err) : conf.IsQuota() ? QuotaFilter(conf, items, err) : conf.IsDimcap() ? DimensionUniqueFilter(conf, items, err) : ItemStateFilter(conf, user, items, err);
     }
     std::map<std::string, std::vector<int32_t>> user_fields;   // uid → dictionary-encoded user categorical features
     pg_model* fm2t = nullptr;                           // FM + two-tower model: rank algorithm "fm2t", and the vector model of the online recall
