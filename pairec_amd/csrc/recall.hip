@@ -434,18 +434,19 @@ struct ScreenArgs {
     const float* nx_rows;     // L2 = 2 (per-row test: g = 2 s_x s_q I - |x|^2 >= C'_q, thr_screen = C'_q, l2_b = 2 s_x s_q): |x|^2 of every row
 };
 
-// Hit records (query halves).  A 32-row x 32-query tile with a suspect in it has, as a rule, exactly one: one lane, one of
-// its 16 accumulators.  Finding the register inside the scan kernel — 16 compare / add-with-carry pairs and a staging
-// loop, issued for the whole wave on behalf of that one lane — cost about as many VALU slots as the reject test itself.
-// Instead the lane parks its 16 accumulators as they are (64 B) with a tag (first row of the block; query column and
-// lane half) in the wave's LDS staging area and moves on: five LDS writes under the hit lanes' exec mask.  Every
+// Hit records (query halves).  A 32-row x 16-query tile with a suspect in it has, as a rule, exactly one: one lane, one of
+// its 8 accumulators (two row halves x 4 registers of v_mfma_i32_16x16x64_i8).  Finding the register inside the scan kernel —
+// compare / add-with-carry pairs and a staging loop, issued for the whole wave on behalf of that one lane — cost about as
+// many VALU slots as the reject test itself.  Instead the lane parks its 8 accumulators as they are (32 B) with a tag (first
+// row of the block; query | lane group << 8) in the wave's LDS staging area and moves on: three LDS writes under the hit
+// lanes' exec mask.  (On the 32x32x32 shape the record was a lane's 16 accumulators + tag, 80 B.)  Every
 // kRecStage records the area is copied to the wave's region of a global record buffer (plain coalesced stores, no
 // atomics, no wait: the stores add to vmcnt, which only makes the ring's counted waits conservative for a moment —
 // loads return in order among themselves).  screen_decode_kernel then does the compares with one record per lane — all
 // 64 lanes busy — and fills the per-query suspect lists that rescore_kernel reads.  (Stores straight from the hit path,
 // without the LDS stage, were measured: 4.35 vs 3.1 ms per pass — with stores in flight in every second block the
 // counted waits over-wait all the time and the ring runs one piece deep.)
-constexpr uint32_t kRecBytes = 80;
+constexpr uint32_t kRecBytes = 48;
 constexpr uint32_t kRecOvfWord = 1 + kMaxQueries + 1;       // rs.overflow[kRecOvfWord]: the overflow was one of the hit-record areas (they can grow: pg_table::rec_scale)
 
 // NQB query blocks of 32; WAVES waves per workgroup.  <=128 queries: 8 waves (2 per SIMD), ring of 4
@@ -454,9 +455,12 @@ constexpr uint32_t kRecOvfWord = 1 + kMaxQueries + 1;       // rs.overflow[kRecO
 // I8: the shadow and the queries are int8 and the bound is an exact int32 dot product on
 // v_mfma_i32_32x32x32_i8 — same issue rate as the bf16 MFMA at twice the k per instruction, over half the
 // bytes per row.
-// QH: query halves — the wave serves NQB x QH query blocks, QH groups of NQB one after the other on the same table
+// QH: query halves — the wave serves NQB x QH query blocks of 32, QH groups of NQB one after the other on the same table
 // block, re-using the accumulators (int8, 256 queries: 2 x 4 blocks in 8 waves — two waves per SIMD, so one
 // wave's test, hit path and DMA issue run under the other's MFMAs; all 128 B-operand registers in the AGPR half).
+// This path runs on v_mfma_i32_16x16x64_i8 — a half is 8 column blocks of 16 queries x 2 row halves — at the same
+// operations per cycle as 32x32x32 and a higher clock under the package power cap (DESIGN.md §4.1a, Appendix A;
+// scripts/micro/mfma_shape_i8.hip): its own A read pattern, DMA rotation, B packing (screen_prep8_kernel) and record.
 // (SPLIT and VAR are kept only so that the kernel's name stays the same)
 template <int DIM, int NQB, int WAVES, int SPLIT = 1, int VAR = 0, bool I8 = false, int QH = 1, int L2 = 0>
 __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void screen_kernel(ScreenArgs a) {
@@ -478,7 +482,9 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void screen_kernel(ScreenArg
     // (query halves: the last two B fragments sit in LDS — 2 KiB for the workgroup — because the allocator wants a
     // few registers of the AGPR half for itself and would otherwise bring two fragments back from scratch per block,
     // behind an s_waitcnt vmcnt(0) that also drains the DMA ring)
-    constexpr int kBLds = QH > 1 ? 2048 : 0;
+    // (query halves, 16x16x64: a lane has 16 query columns, and 16 threshold registers do not fit beside 64 accumulators at
+    // 128 arch registers — the 256 integer thresholds follow the two fragments, eight ds_read_b32 per half under 512 MFMA cycles)
+    constexpr int kBLds = QH > 1 ? 3072 : 0;
     constexpr int kStageBytesW = (kScreenLds - kScanLdsRing - kBLds) / WAVES;
     constexpr int NQT = NQB * QH;                // query blocks of this wave
     static_assert(QH == 1 || PPB == 1, "query halves: one piece per block");
@@ -498,11 +504,14 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void screen_kernel(ScreenArg
     float la[NQT];                                    // L2: A_q
     bool active[NQT];
     char* const b_lds = smem + kScreenLds - kBLds;
+    int* const thr_lds = reinterpret_cast<int*>(b_lds + 2048);
     if constexpr (QH > 1) {
         if (wave == 0) {
             *reinterpret_cast<uint4*>(b_lds + lane * 16) = a.qb16[((NQT - 1) * KS + KS - 2) * 64 + lane];
             *reinterpret_cast<uint4*>(b_lds + 1024 + lane * 16) = a.qb16[((NQT - 1) * KS + KS - 1) * 64 + lane];
         }
+        if (threadIdx.x < (uint32_t)kMaxQueries)      // (inactive columns: never a suspect)
+            thr_lds[threadIdx.x] = threadIdx.x < a.nq ? __float_as_int(a.thr_screen[threadIdx.x]) : 0x7fffffff;
         __syncthreads();
     }
 #pragma unroll
@@ -513,7 +522,8 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void screen_kernel(ScreenArg
             else bfrag[c][ks] = a.qb16[(c * KS + ks) * 64 + lane];
         }
         active[c] = (uint32_t)(c * 32 + i32) < a.nq;
-        if constexpr (I8) thr_s[c] = active[c] ? __float_as_int(a.thr_screen[c * 32 + i32]) : 0x7fffffff;
+        if constexpr (QH > 1) thr_s[c] = 0;                // (query halves: the thresholds are in LDS, by 16-query block)
+        else if constexpr (I8) thr_s[c] = active[c] ? __float_as_int(a.thr_screen[c * 32 + i32]) : 0x7fffffff;
         else thr_s[c] = active[c] ? a.thr_screen[c * 32 + i32] : __builtin_inff();
         eu[c] = (!I8 && active[c]) ? a.eps_unit[c * 32 + i32] : 0.0f;
         if constexpr (L2 != 0) {                      // A_q in la, B_q in eu (L2 = 2: C'_q and 2 s_x s_q; inactive columns: never a suspect)
@@ -531,7 +541,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void screen_kernel(ScreenArg
             else
                 asm volatile("" : "+v"(bfrag[c][ks].x), "+v"(bfrag[c][ks].y), "+v"(bfrag[c][ks].z), "+v"(bfrag[c][ks].w));
         }
-        asm volatile("" : "+v"(thr_s[c]));
+        if (QH == 1) asm volatile("" : "+v"(thr_s[c]));
         if (!I8 || L2) asm volatile("" : "+v"(eu[c]));
         if (L2) asm volatile("" : "+v"(la[c]));
     }
@@ -541,7 +551,11 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void screen_kernel(ScreenArg
     for (int n = 0; n < ND; ++n) {
         const int S = n * 64 + lane;
         const int i = S >> 3, p = S & 7;
-        voff[n] = (uint32_t)(i * DIM * EB + 16 * ((p + (i >> 1)) & 7));      // row i, rotated 16-B quad p
+        // row i, rotated 16-B quad p.  A ds_read_b128 lane group ({0-3, 12-15, 20-27} / {4-11, 16-19, 28-31} of a wave half) must
+        // cover the 64 banks once.  32x32 shapes: the group reads 16 rows at ONE quad — rotate by i >> 1.  16x16x64 (query
+        // halves): it reads rows {0-3, 12-15} at quad q and rows 4-11 at q +- 1 — rotate by i & 6 (row pairs at q - {0, 2, 4, 6,
+        // 0, 2, 4, 6}; with the +-1 of pairs 2-5 all eight differ, where i >> 1 collides two-way: measured, scripts/micro/mfma_shape_i8.hip)
+        voff[n] = (uint32_t)(i * DIM * EB + 16 * ((p + (QH > 1 ? (i & 6) : (i >> 1))) & 7));
     }
     const uint32_t lds_wave_u = __builtin_amdgcn_readfirstlane(
         (uint32_t)(uintptr_t)((__attribute__((address_space(3))) char*)smem) + wave * (NS * kPieceBytes));
@@ -669,6 +683,9 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void screen_kernel(ScreenArg
         char* const rec_lds = smem + kScanLdsRing + wave * kStageBytesW;
         char* const rec_glb = a.rec + (size_t)gw * a.rec_cap * kRecBytes;
         uint32_t rec_st = 0, rec_total = 0;
+        const int r16 = lane & 15, g16 = lane >> 4;
+        const int rot16 = (r16 & 6) * 16;
+        const uint32_t tag16 = (uint32_t)r16 | ((uint32_t)g16 << 8);      // a record's tag word: query | lane group << 8
         auto rec_flush = [&]() {
             if (rec_total + rec_st > a.rec_cap) {
                 // region full (the table's best rows sit together): the staged records go to the shared pool — one returning
@@ -696,10 +713,13 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void screen_kernel(ScreenArg
             const char* nb_src;
             uint32_t nb_dst;
             piece_addr(NS - 1, b + NS - 1, nb_src, nb_dst);
-            const char* slot = lds_ptr + (b % NS) * kPieceBytes + rd_row;
+            // A fragments on v_mfma_i32_16x16x64_i8: q4[2 rh + ks] = row (lane & 15) + 16 rh, bytes 64 ks + 16 (lane >> 4) ..+15
+            // (quad 4 ks + (lane >> 4)); rows 16 apart share a rotation, so the second row half is the first + 2 KiB
+            const char* slot = lds_ptr + (b % NS) * kPieceBytes + r16 * 128;
             f32x4 q4[4];
 #pragma unroll
-            for (int j = 0; j < 4; ++j) q4[j] = *reinterpret_cast<const f32x4*>(slot + (((2 * j + h) * 16 - rd_rot) & 112));
+            for (int j = 0; j < 4; ++j)
+                q4[j] = *reinterpret_cast<const f32x4*>(slot + (((4 * (j & 1) + g16) * 16 - rot16) & 112) + 2048 * (j >> 1));
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int n = 0; n < ND; ++n)
@@ -711,36 +731,47 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void screen_kernel(ScreenArg
             const uint32_t row0 = cur_phys * kPieceRows;
 #pragma unroll
             for (int half = 0; half < QH; ++half) {
-                AccT acc[NQB];
+                // 8 query blocks of 16 x 2 row halves: acc[rh][c][e] = row 16 rh + 4 (lane >> 4) + e, query 16 (8 half + c) + (lane & 15)
+                constexpr int NC = 2 * NQB;
+                i32x4 acc[2][NC];
+                int thr16[NC];
 #pragma unroll
-                for (int c = 0; c < NQB; ++c)
+                for (int c = 0; c < NC; ++c) thr16[c] = thr_lds[(half * NC + c) * 16 + r16];
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) acc[c][r] = 0;
+                for (int ks = 0; ks < 2; ++ks) {
+                    // all 16 accumulators per k-step (an accumulator's second MFMA never waits for its first); a query block's two
+                    // row halves finish together, so its test starts under the MFMAs that remain
 #pragma unroll
-                for (int ksl = 0; ksl < 4; ++ksl)
+                    for (int c = 0; c < NC; ++c)
 #pragma unroll
-                    for (int c = 0; c < NQB; ++c) {
-                        uint4 bq;
-                        if (half * NQB + c == NQT - 1 && ksl >= KS - 2) bq = *reinterpret_cast<const uint4*>(b_lds + (ksl - (KS - 2)) * 1024 + lane * 16);
-                        else bq = bfrag[half * NQB + c][ksl];
-                        acc[c] = __builtin_amdgcn_mfma_i32_32x32x32_i8(__builtin_bit_cast(i32x4, q4[ksl]),
-                                                                       __builtin_bit_cast(i32x4, bq), acc[c], 0, 0, 0);
-                    }
-                uint64_t cmask[NQB];
-                bool hit[NQB];
+                        for (int rh = 0; rh < 2; ++rh) {
+                            constexpr int kLdsFrag = NQT * KS - 2;      // (flat B fragment (16-query block, k-step); the last two: LDS)
+                            const int f = (half * NC + c) * 2 + ks;
+                            uint4 bq;
+                            if (f >= kLdsFrag) bq = *reinterpret_cast<const uint4*>(b_lds + (f - kLdsFrag) * 1024 + lane * 16);
+                            else bq = bfrag[f / KS][f % KS];
+                            const i32x4 c0 = ks == 0 ? i32x4{0, 0, 0, 0} : acc[rh][c];
+                            acc[rh][c] = __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4, q4[2 * rh + ks]),
+                                                                               __builtin_bit_cast(i32x4, bq), c0, 0, 0, 0);
+                        }
+                    if (ks == 0) __builtin_amdgcn_sched_barrier(0);
+                }
+                uint64_t cmask[NC];
+                bool hit[NC];
                 uint64_t any_mask = 0;
 #pragma unroll
-                for (int c = 0; c < NQB; ++c) {
-                    int m = acc[c][0];
+                for (int c = 0; c < NC; ++c) {
+                    // the lane's eight values of a column block belong to ONE query
+                    int m = acc[0][c][0];
 #pragma unroll
-                    for (int r = 1; r < 16; ++r) m = acc[c][r] > m ? acc[c][r] : m;
-                    hit[c] = m >= thr_s[half * NQB + c];
+                    for (int r = 1; r < 8; ++r) m = acc[r >> 2][c][r & 3] > m ? acc[r >> 2][c][r & 3] : m;
+                    hit[c] = m >= thr16[c];
                     cmask[c] = __builtin_amdgcn_ballot_w64(hit[c]);
                     any_mask |= cmask[c];
                 }
                 if (any_mask != 0) {
 #pragma unroll
-                    for (int c = 0; c < NQB; ++c) {
+                    for (int c = 0; c < NC; ++c) {
                         if (cmask[c] == 0) continue;
                         uint64_t pend = cmask[c];
                         bool mine = hit[c];
@@ -752,12 +783,12 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void screen_kernel(ScreenArg
                             const bool take = mine && pre < kRecStage;      // (more than kRecStage hit lanes: in rounds)
                             if (take) {
                                 char* const r = rec_lds + (rec_st + pre) * kRecBytes;
-#pragma unroll
-                                for (int jj = 0; jj < 4; ++jj) {
-                                    const i32x4 v = {acc[c][4 * jj], acc[c][4 * jj + 1], acc[c][4 * jj + 2], acc[c][4 * jj + 3]};
-                                    *reinterpret_cast<i32x4*>(r + 16 * jj) = v;
-                                }
-                                *reinterpret_cast<uint2*>(r + 64) = make_uint2(row0, (uint32_t)((half * NQB + c) * 32 + i32) | ((uint32_t)h << 8));
+                                *reinterpret_cast<i32x4*>(r) = acc[0][c];
+                                *reinterpret_cast<i32x4*>(r + 16) = acc[1][c];
+                                // (opaque: else the 16 tags of a lane are hoisted and live — spilled — across the block loop)
+                                uint32_t tag = tag16;
+                                asm volatile("" : "+v"(tag));
+                                *reinterpret_cast<uint2*>(r + 32) = make_uint2(row0, tag + (uint32_t)((half * NC + c) * 16));
                             }
                             rec_st += n < kRecStage ? n : kRecStage;
                             if (n <= kRecStage) break;
@@ -942,19 +973,22 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void screen_kernel(ScreenArg
 __device__ __forceinline__ uint32_t rec_mask(const char* r, const float* __restrict__ thr_screen, uint32_t row_end, uint32_t& q,
                                              uint32_t& row0h) {
     typedef int i32x4 __attribute__((ext_vector_type(4)));
-    const uint2 tag = *reinterpret_cast<const uint2*>(r + 64);
+    // D of v_mfma_i32_16x16x64_i8: lane l holds column l & 15 (the query), rows 4 (l >> 4) + e in register e = 0..3; the record
+    // is the lane's two row halves (registers rr = 0..3: rows 0-15 of the block, rr = 4..7: rows 16-31) and the tag
+    // (block's first row; query | (l >> 4) << 8)
+    const uint2 tag = *reinterpret_cast<const uint2*>(r + 32);
     q = tag.y & 255u;
-    const uint32_t h = (tag.y >> 8) & 1u;
-    row0h = tag.x + 4 * h;
+    const uint32_t g = (tag.y >> 8) & 3u;
+    row0h = tag.x + 4 * g;
     const int t = __float_as_int(thr_screen[q]);
     uint32_t m = 0;                                        // bit rr: accumulator register rr of the lane is a suspect
 #pragma unroll
-    for (int jj = 0; jj < 4; ++jj) {
+    for (int jj = 0; jj < 2; ++jj) {
         const i32x4 v = *reinterpret_cast<const i32x4*>(r + 16 * jj);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const int rr = 4 * jj + e;
-            if (v[e] >= t && row0h + (rr & 3) + 8 * (rr >> 2) < row_end) m |= 1u << rr;
+            if (v[e] >= t && row0h + (rr & 3) + 16 * (rr >> 2) < row_end) m |= 1u << rr;
         }
     }
     return m;
@@ -966,7 +1000,7 @@ __global__ __launch_bounds__(1024) void screen_decode_kernel(const char* __restr
                                                              uint32_t* __restrict__ susp_cnt, uint32_t* __restrict__ susp,
                                                              uint32_t cap, uint32_t* __restrict__ overflow) {
     __shared__ uint32_t cntq[kMaxQueries], baseq[kMaxQueries], nreg[8];
-    // pass 1 leaves (first row + lane half, query | mask << 16) of every record with a suspect here, pass 2 reads them back
+    // pass 1 leaves (first row + 4 x lane group, query | mask << 16) of every record with a suspect here, pass 2 reads them back
     // (records beyond the buffer — a workgroup of a skewed table — are read from global memory again)
     constexpr uint32_t kKeep = 12288;
     __shared__ uint2 keep[kKeep];
@@ -1014,7 +1048,7 @@ __global__ __launch_bounds__(1024) void screen_decode_kernel(const char* __restr
                     while (m) {
                         const uint32_t rr = __builtin_ctz(m);
                         m &= m - 1;
-                        susp[(uint64_t)q * cap + pos++] = row0h + (rr & 3) + 8 * (rr >> 2);
+                        susp[(uint64_t)q * cap + pos++] = row0h + (rr & 3) + 16 * (rr >> 2);
                     }
                 }
             }
@@ -1231,7 +1265,7 @@ __global__ void screen_thr_kernel(const float* __restrict__ thr, const float* __
 // a single request used to spend 36 us preparing 255 zero queries, a full batch 37 us in one 1024-thread workgroup).
 __global__ __launch_bounds__(128) void screen_prep8_kernel(const float* __restrict__ qpad, uint32_t dim,
                                                             float max_norm, float resid, uint4* __restrict__ qb8,
-                                                            float* __restrict__ eps, float* __restrict__ qscale) {
+                                                            float* __restrict__ eps, float* __restrict__ qscale, uint32_t wide) {
     __shared__ float sq[32];
     const uint32_t tid = threadIdx.x, c = blockIdx.x;
     {
@@ -1274,11 +1308,14 @@ __global__ __launch_bounds__(128) void screen_prep8_kernel(const float* __restri
         }
     }
     __syncthreads();
+    // B fragments, 16 B per lane.  v_mfma_i32_32x32x32_i8: [c][ks][lane] = query 32 c + (lane & 31), bytes 32 ks + 16 (lane >> 5) ..+15.
+    // wide (> 128 queries, dim 128: the query halves run on v_mfma_i32_16x16x64_i8): [c16][ks][lane] = query 16 c16 + (lane & 15),
+    // bytes 64 ks + 16 (lane >> 4) ..+15, two k-steps — this workgroup's 32 queries are blocks c16 = 2 c, 2 c + 1, the same 4 x 64 slots
     const uint32_t KS = dim / 32;
     for (uint32_t i = tid; i < KS * 64; i += blockDim.x) {
-        const uint32_t lane = i & 63, ks = i >> 6;
-        const uint32_t ql = lane & 31;
-        const float* q = qpad + (size_t)(c * 32 + ql) * dim + ks * 32 + 16 * (lane >> 5);
+        const uint32_t lane = i & 63, ks = wide ? (i >> 6) & 1 : i >> 6;
+        const uint32_t ql = wide ? 16 * (i >> 7) + (lane & 15) : lane & 31;
+        const float* q = qpad + (size_t)(c * 32 + ql) * dim + (wide ? ks * 64 + 16 * (lane >> 4) : ks * 32 + 16 * (lane >> 5));
         const float sc = sq[ql];
         uint32_t w[4];
         for (int e = 0; e < 4; ++e) {
@@ -1290,7 +1327,7 @@ __global__ __launch_bounds__(128) void screen_prep8_kernel(const float* __restri
             }
             w[e] = word;
         }
-        qb8[(c * KS + ks) * 64 + lane] = make_uint4(w[0], w[1], w[2], w[3]);
+        qb8[c * KS * 64 + i] = make_uint4(w[0], w[1], w[2], w[3]);      // (= [c][ks][lane], wide: [2 c + (i >> 7)][ks][lane])
     }
 }
 
@@ -2844,7 +2881,7 @@ struct PlanRun {                     // the launches of one plan (helper of reca
                 const uint64_t rsc = t->rec_scale ? t->rec_scale : 1;     // (tables whose batches overflowed these areas got larger ones)
                 uint32_t cap_w = (uint32_t)(((uint64_t)kMaxQueries * j->k * 4 * rsc / rec_waves + 255) / 256 * 256);
                 // (the safe plan's chunk — kCandSlack / 2 rows — with EVERY row a suspect of every query, e.g. a table in ascending
-                //  score order: 8 x 64 records per block, and the blocks of a SIMD's pair of waves split as screen_kernel splits
+                //  score order: 16 query blocks of 16 x 64 lanes = 1024 records per block, and the blocks of a SIMD's pair of waves split as screen_kernel splits
                 //  them — the larger share decides.  Sized for an even split, the early wave's fifth block went to the spill pool,
                 //  which at a small K is small: "overflow in safe mode" on such a table at K = 10, 256 queries.)
                 const uint32_t pairs = (uint32_t)ctx->num_cus * 4u;
@@ -2852,7 +2889,7 @@ struct PlanRun {                     // the launches of one plan (helper of reca
                 const uint32_t es = sa.early_share > 512 ? sa.early_share : 1024 - sa.early_share;
                 uint32_t eb = (uint32_t)(((uint64_t)pb * es + 512) >> 10) + 1;
                 if (eb > pb) eb = pb;
-                const uint32_t floor_w = eb * 512;
+                const uint32_t floor_w = eb * 1024;
                 if (cap_w < floor_w) cap_w = floor_w;
                 // + a spill pool for tables whose best rows sit together: room for all of 256 x 2 K suspects
                 const uint32_t pool_cap = (uint32_t)(((uint64_t)kMaxQueries * j->k * 2 * rsc + kRecPoolSlice - 1) / kRecPoolSlice * kRecPoolSlice);
@@ -3040,7 +3077,8 @@ int recall_job_enqueue(RecallJob* j) {
         if (!r.no_i8) {
             if (t->shadow_is_i8)
                 screen_prep8_kernel<<<j->nq <= 32 ? 1u : (j->nq <= 64 ? 2u : (j->nq <= 128 ? 4u : 8u)), 128, 0, ctx->stream>>>(
-                    rs.qpad, t->dim, t->max_norm, t->resid8, rs.qb16, rs.eps, rs.qscale);     // grid = the scan's NQB x QH
+                    rs.qpad, t->dim, t->max_norm, t->resid8, rs.qb16, rs.eps, rs.qscale,
+                    j->nq > 128 && !j->l2 ? 1u : 0u);     // grid = the scan's NQB x QH; wide: dispatch_screen's query halves
             else
                 screen_prep_kernel<<<(kScreenMaxNQB * (t->dim / 16) * 64 + 255) / 256, 256, 0, ctx->stream>>>(
                     rs.qpad, t->dim, rs.qb16, rs.eps);
