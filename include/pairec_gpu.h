@@ -693,8 +693,9 @@ int pg_i2i_recall_exclude(pg_ctx* ctx, const pg_table* trigger_table, const uint
  * every similarity by the trigger's preference (:179-192), sums the products per distinct item in float64
  * (module/user_collaborative_dao.go:38-51), divides by the largest sum unless Normalization is "off" (:61-68), sorts
  * descending and cuts to RecallCount.  ItemCollaborativeFilterRecall (service/recall/item_collaborative_filter_recall.go:40-90)
- * is the one-trigger case with prefer = 1 and normalize = 0.  RealTimeU2IRecall's trigger-weight expression stays on the host:
- * its output is this call's (trigger_rows, trigger_prefer).
+ * is the one-trigger case with prefer = 1 and normalize = 0.  RealTimeU2IRecall is NOT this call: its DAO keeps the LARGEST
+ * sim * prefer term of an item, un-normalised, where this call sums and normalises — pg_rtu2i_* below serves it, trigger
+ * weights included.
  *   Table     CSR over the LOCAL rows of an item table `t`: offsets uint64[rows + 1], neighbours uint32[pairs] (local rows of
  *             `t`), similarities float[pairs].  The reference parses similarities from text as float64; here they are stored
  *             fp32, like every table of this engine, and widened exactly when used.  `t` must outlive the similarity table,
@@ -747,6 +748,103 @@ int pg_cf_recall(pg_ctx* ctx, const pg_simtable* s, const uint32_t* trigger_rows
 int pg_cf_recall_dev(pg_ctx* ctx, const pg_simtable* s, const uint32_t* d_trigger_rows, const double* d_trigger_prefer,
                      const uint32_t* trigger_offsets, uint32_t nq, uint32_t k, const pg_cf_opts* opts, uint64_t* d_out_rows,
                      double* d_out_scores, uint32_t* out_count);
+
+/* RealTimeU2IRecall on the device (csrc/rtu2i.hip, csrc/cf.hip): the user's latest behaviour events become
+ * weighted trigger items, the triggers are expanded through a similarity table, the largest term of an item is its score.
+ * Reference: service/recall/realtime_u2i_recall.go; RealtimeUser2ItemHologresDao (module/realtime_user2item_hologres_dao.go:
+ * 98-343: GetTriggerInfos, ListItemsByUser) over NewRealtimeUser2ItemBaseDao's config (module/realtime_user2item_dao.go:64-136).
+ *   compile   pg_rtu2i_compile turns a UserTriggerDaoConf into a pg_rtu2i (host only, no context).
+ *             event_names[n_events] is the dictionary that gives events their uint16 codes (code = index).
+ *             event_weight / event_play_time ("click:1;buy:3.5") are parsed as the reference does (:96-120): split on ';', then
+ *             on ':'; a piece without exactly two parts, or whose number strconv.ParseFloat rejects, is skipped; a later piece
+ *             of a name replaces an earlier one; a name outside event_names can never match and is ignored.  A non-empty
+ *             event_weight that yields no pair is PG_ERR_INVALID (the reference panics).  A number ParseFloat reads in a form
+ *             this front end does not (hexadecimal, '_' between digits) is PG_ERR_UNSUPPORTED.  NULL = "".
+ *             weight_expression is the govaluate arithmetic subset of pg_expr_compile_govaluate with the DAO's own function
+ *             table (:23-30), which holds ONLY exp: round(...) is refused by name here, as exp is everywhere else; anything
+ *             outside the subset (comparators, strings, ...) is PG_ERR_UNSUPPORTED, named in the message.  The only variables
+ *             are currentTime and eventTime: any other name is PG_ERR_INVALID, named (in the reference every evaluation would
+ *             fail and every weight would be 0); so is an empty expression (no evaluation yields a number: every weight 0).
+ *             At most 64 operations, stack depth 8.  exp(x) is Go's pure math.Exp restated operation for operation (the
+ *             FreeBSD e_exp.c form; real(cmplx.Exp(complex(x, 0))) = Exp(x) cos(0) = Exp(x)), the same bits on host and device,
+ *             within 1 ulp of libm's exp.  Go's amd64 build uses an assembly Exp, so parity with a Go binary is unpinned, like
+ *             govaluate's: this restatement is the specification (csrc/expr_prog.hpp go_exp, tests/rtu2i_ref.py).
+ *             weight_mode: "sum", "max", or "" / NULL = sum; anything else PG_ERR_INVALID (the reference sums under any name but
+ *             "max").  The effective trigger count T = trigger_count ? trigger_count : limit must lie in 1 .. 256, else
+ *             PG_ERR_UNSUPPORTED.  pg_rtu2i_trigger_count returns T.
+ *   triggers  Request q's events are [event_offsets[q], event_offsets[q + 1]), in the order the reference's SQL returns them
+ *             (ORDER BY timestamp DESC, already cut to Limit by the caller): event_rows uint32 (the local row of the item
+ *             table with `rows` rows, 1 <= rows < 2^32), event_code uint16, event_play_time double (NULL: all zeros, the
+ *             zero value NoUsePlayTimeField leaves), event_time int64; now[q] int64 = currentTime.Unix().  nq <= 256; at
+ *             most 1024 events per request: more is PG_ERR_UNSUPPORTED, the request named, the context left usable.
+ *             The answer is DEFINED, bit for bit (GetTriggerInfos, :259-330):
+ *               - an event whose row is >= rows (UINT32_MAX included) is dropped before anything else;
+ *               - an event whose code has a play-time threshold t is dropped when play_time <= t;
+ *               - weight = w * e (one rounding): w the event's weight, 1 when its code has none or is >= n_events; e the
+ *                 expression over currentTime = (double)now[q], eventTime = (double)event_time;
+ *               - events in the order given: the first surviving event of an item sets its weight; a later one does
+ *                 weight = weight + w_e (sum), or replaces the weight only when w_e > weight (max);
+ *               - an item whose combined weight is not finite is dropped;
+ *               - order: weight descending, then the index of the item's first surviving event ascending (-0.0 ranks as 0.0
+ *                 and keeps its bits); the first T entries are kept.
+ *             out_rows uint32 [nq][T] (padding UINT32_MAX), out_weight double [nq][T] (padding -inf), out_count uint32 [nq].
+ *             With Item2ItemTable == "" the reference returns exactly these items, their weights as scores (:104-112).
+ *             Deviations, all where the reference's own answer is not defined or not useful: an event of an item the engine
+ *             does not hold could take a TriggerCount place in the reference and then match no SQL row; the reference's sort
+ *             is undefined with a NaN in it and the expansion needs finite preferences, hence the dropped non-finite weights;
+ *             the reference's order of equal weights is map iteration and pdqsort order.
+ *             pg_rtu2i_triggers_host is the host statement (no context); pg_rtu2i_triggers takes host arrays;
+ *             pg_rtu2i_triggers_dev device arrays (offsets and now stay host memory) and device outputs.  All return
+ *             synchronised.
+ *   expand    pg_rtu2i_expand[_dev]: arguments, limits and errors of pg_cf_recall[_dev]; opts->normalize is ignored, the
+ *             exclusion lists mean what they mean there.  DEFINED answer: triggers in the order given, entries in stored order,
+ *             term = (double)sim * prefer (one rounding); the first term of an item is its score, a later one replaces it only
+ *             when term > score — ListItemsByUser's descending sort followed by uniqItems (:203-204), the ±0.0 case decided
+ *             by order; no division by the largest score; order, cut, padding, counts, tiers and the 65536-pair report as
+ *             in pg_cf_recall.
+ *   recall    pg_rtu2i_recall[_dev]: events in, out_rows uint64 [nq][k] and out_scores double [nq][k] out (the shape
+ *             pg_fanin_merge_dev takes with score_f64 != 0), out_count optional.  Equal to pg_rtu2i_triggers followed by
+ *             pg_rtu2i_expand over `s` (rows = the rows of its item table), byte for byte; the trigger lists stay in device
+ *             memory and the two kernels follow each other on the stream with no host read-back between them.  _dev: events,
+ *             opts->excl_rows and outputs are device memory; offsets, now and out_count host memory.  Returns synchronised.
+ *   Not served (refused or out of scope): DiversityRules / PropertyFields (DiversityTriggers), the U2I2X2I, BE and
+ *             FeatureStore DAOs, MergeMode "snake", the recall's cache line. */
+typedef struct pg_rtu2i pg_rtu2i;
+typedef struct {
+    const char* weight_expression;
+    const char* event_weight;
+    const char* event_play_time;
+    const char* const* event_names;
+    uint32_t n_events;
+    const char* weight_mode;
+    uint32_t trigger_count;
+    uint32_t limit;
+} pg_rtu2i_conf;
+int pg_rtu2i_compile(const pg_rtu2i_conf* conf, pg_rtu2i** out);
+int pg_rtu2i_free(pg_rtu2i* c);
+int pg_rtu2i_trigger_count(const pg_rtu2i* c);
+int pg_rtu2i_triggers_host(const pg_rtu2i* c, uint64_t rows, const uint32_t* event_rows, const uint16_t* event_code,
+                           const double* event_play_time, const int64_t* event_time, const uint32_t* event_offsets, const int64_t* now,
+                           uint32_t nq, uint32_t* out_rows, double* out_weight, uint32_t* out_count);
+int pg_rtu2i_triggers(pg_ctx* ctx, pg_rtu2i* c, uint64_t rows, const uint32_t* event_rows, const uint16_t* event_code,
+                      const double* event_play_time, const int64_t* event_time, const uint32_t* event_offsets, const int64_t* now,
+                      uint32_t nq, uint32_t* out_rows, double* out_weight, uint32_t* out_count);
+int pg_rtu2i_triggers_dev(pg_ctx* ctx, pg_rtu2i* c, uint64_t rows, const uint32_t* d_event_rows, const uint16_t* d_event_code,
+                          const double* d_event_play_time, const int64_t* d_event_time, const uint32_t* event_offsets,
+                          const int64_t* now, uint32_t nq, uint32_t* d_out_rows, double* d_out_weight, uint32_t* d_out_count);
+int pg_rtu2i_expand(pg_ctx* ctx, const pg_simtable* s, const uint32_t* trigger_rows, const double* trigger_prefer,
+                    const uint32_t* trigger_offsets, uint32_t nq, uint32_t k, const pg_cf_opts* opts, uint64_t* out_rows,
+                    double* out_scores, uint32_t* out_count);
+int pg_rtu2i_expand_dev(pg_ctx* ctx, const pg_simtable* s, const uint32_t* d_trigger_rows, const double* d_trigger_prefer,
+                        const uint32_t* trigger_offsets, uint32_t nq, uint32_t k, const pg_cf_opts* opts, uint64_t* d_out_rows,
+                        double* d_out_scores, uint32_t* out_count);
+int pg_rtu2i_recall(pg_ctx* ctx, pg_rtu2i* c, const pg_simtable* s, const uint32_t* event_rows, const uint16_t* event_code,
+                    const double* event_play_time, const int64_t* event_time, const uint32_t* event_offsets, const int64_t* now,
+                    uint32_t nq, uint32_t k, const pg_cf_opts* opts, uint64_t* out_rows, double* out_scores, uint32_t* out_count);
+int pg_rtu2i_recall_dev(pg_ctx* ctx, pg_rtu2i* c, const pg_simtable* s, const uint32_t* d_event_rows, const uint16_t* d_event_code,
+                        const double* d_event_play_time, const int64_t* d_event_time, const uint32_t* event_offsets,
+                        const int64_t* now, uint32_t nq, uint32_t k, const pg_cf_opts* opts, uint64_t* d_out_rows,
+                        double* d_out_scores, uint32_t* out_count);
 
 /* Fan-in + UniqueFilter on the device (csrc/fanin.hip): the answers of a request's recalls merged into one
  * candidate list without leaving device memory.  RecallService.GetItems (service/recall.go:53-153; the fan-in :126-150) runs

@@ -47,6 +47,8 @@ EXPORTS = [
     "pg_exclude_compact_dev", "pg_recall_topk_exclude", "pg_recall_topk_exclude_dev", "pg_i2i_recall_exclude",
     "pg_coalescer_recall_exclude",
     "pg_simtable_create", "pg_simtable_upload", "pg_simtable_info", "pg_simtable_destroy", "pg_cf_recall", "pg_cf_recall_dev",
+    "pg_rtu2i_compile", "pg_rtu2i_free", "pg_rtu2i_trigger_count", "pg_rtu2i_triggers_host", "pg_rtu2i_triggers", "pg_rtu2i_triggers_dev",
+    "pg_rtu2i_expand", "pg_rtu2i_expand_dev", "pg_rtu2i_recall", "pg_rtu2i_recall_dev",
     "pg_fanin_merge_dev", "pg_recommend_candidates_dnn3_dev",
     "pg_trim_out_cap", "pg_candidates_trim_dev", "pg_recommend_cascade_dnn3_dev",
     "pg_blend_out_cap", "pg_candidates_blend_dev", "pg_candidates_blend_host",
@@ -117,6 +119,12 @@ class PgRecallExcludeOpts(C.Structure):
 
 class PgCfOpts(C.Structure):
     _fields_ = [("normalize", C.c_int), ("excl_rows", C.c_void_p), ("excl_offsets", C.c_void_p)]
+
+
+class PgRtU2IConf(C.Structure):
+    _fields_ = [("weight_expression", C.c_char_p), ("event_weight", C.c_char_p), ("event_play_time", C.c_char_p),
+                ("event_names", C.POINTER(C.c_char_p)), ("n_events", C.c_uint32), ("weight_mode", C.c_char_p),
+                ("trigger_count", C.c_uint32), ("limit", C.c_uint32)]
 
 
 class PgFaninSource(C.Structure):
@@ -301,6 +309,16 @@ def load():
         "pg_simtable_destroy": [vp, vp],
         "pg_cf_recall": [vp, vp, vp, vp, vp, u32, u32, P(PgCfOpts), vp, vp, vp],
         "pg_cf_recall_dev": [vp, vp, vp, vp, vp, u32, u32, P(PgCfOpts), vp, vp, vp],
+        "pg_rtu2i_compile": [P(PgRtU2IConf), P(vp)],
+        "pg_rtu2i_free": [vp],
+        "pg_rtu2i_trigger_count": [vp],
+        "pg_rtu2i_triggers_host": [vp, u64, vp, vp, vp, vp, vp, vp, u32, vp, vp, vp],
+        "pg_rtu2i_triggers": [vp, vp, u64, vp, vp, vp, vp, vp, vp, u32, vp, vp, vp],
+        "pg_rtu2i_triggers_dev": [vp, vp, u64, vp, vp, vp, vp, vp, vp, u32, vp, vp, vp],
+        "pg_rtu2i_expand": [vp, vp, vp, vp, vp, u32, u32, P(PgCfOpts), vp, vp, vp],
+        "pg_rtu2i_expand_dev": [vp, vp, vp, vp, vp, u32, u32, P(PgCfOpts), vp, vp, vp],
+        "pg_rtu2i_recall": [vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, P(PgCfOpts), vp, vp, vp],
+        "pg_rtu2i_recall_dev": [vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, P(PgCfOpts), vp, vp, vp],
         "pg_fanin_merge_dev": [vp, P(PgFaninSource), u32, u32, vp, vp, vp, vp, vp, vp],
         "pg_recommend_candidates_dnn3_dev": [vp, vp, vp, vp, C.c_char_p, vp, u32, u32, vp, vp, vp, vp, vp, vp],
         "pg_trim_out_cap": [P(PgTrimRule), u32, u32, P(C.c_uint32)],

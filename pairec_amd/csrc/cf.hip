@@ -15,9 +15,15 @@
 // trigger's list is spread over the lanes, and a list holds no neighbour twice (pg_simtable_upload refuses it), so no two
 // lanes of one trigger touch one slot.  Every item's additions happen in trigger order with a plain read-modify-write; only
 // the slot's uint32 key is claimed by compare-and-swap.
-#include "common.hpp"
+//
+// RealTimeU2IRecall's expansion (pg_rtu2i_expand, pg_rtu2i_recall) is the same kernel with another reduction: an
+// item keeps the LARGEST of its terms — the first, replaced only by a larger one — and nothing is normalised
+// (module/realtime_user2item_hologres_dao.go:203-204: a descending sort, then uniqItems).  Its triggers may come from rtu2i.hip's
+// trigger kernel: lists at a fixed stride with a device count per request (CfTrigDev), read without a host round trip.
+#include "cf_shared.hpp"
 
 #include <cmath>
+#include <functional>
 
 struct pg_simtable {
     // recalls share this lock, pg_simtable_upload takes it exclusively.  Lock order: ctx->mu, the item table, then this.
@@ -36,7 +42,6 @@ namespace pg {
 namespace {
 
 constexpr uint32_t kCfThreads = 1024;            // one workgroup per request; a list of at most kCfMaxList entries is one entry per lane
-constexpr uint32_t kCfMaxTriggers = 256;
 constexpr uint32_t kCfMaxList = 1024;
 constexpr uint32_t kCfMaxPairs = 65536;          // a request beyond it is reported, never cut
 // LDS tier: 12288 slots of (fp64 accumulator, uint32 key) in two planes = 144 KiB; load factor <= 0.5 serves 6144 pairs.  The
@@ -49,7 +54,6 @@ constexpr size_t kCfTableBytes = (size_t)kCfLdsSlots * 12;
 static_assert((size_t)kCfSortChunk * 16 <= kCfTableBytes, "the sort reuses the table's LDS");
 constexpr size_t kCfLds = kCfTableBytes + kCfMaxTriggers * (8 + 8 + 4) + 64;
 static_assert(kCfLds <= 160 * 1024, "one workgroup's LDS");
-constexpr uint32_t kCfEmpty = 0xFFFFFFFFu;       // never a neighbour: neighbours are < rows <= UINT32_MAX
 constexpr uint32_t kCfMaxDepth = 16384;
 
 struct CfArgs {
@@ -60,7 +64,9 @@ struct CfArgs {
     uint64_t row_offset;
     const uint32_t* trig;
     const double* pref;
-    const uint32_t* trig_off;      // [nq + 1]
+    const uint32_t* trig_off;      // [nq + 1]; NULL: request q's triggers are [q * trig_stride, + min(trig_cnt[q], trig_stride))
+    const uint32_t* trig_cnt;      // [nq] (CfTrigDev: what rtu2i.hip's trigger kernel wrote)
+    uint32_t trig_stride;
     uint32_t lds_max_pairs;
     uint32_t gslots;               // slots of one request's slice of the global tables (a power of two >= 2 min(65536, rows))
     uint32_t* gkeys;               // [nq][gslots]
@@ -76,18 +82,13 @@ struct CfArgs {
     uint32_t* status;              // the smallest request beyond kCfMaxPairs (UINT32_MAX: none)
 };
 
-// (the multiplicative hash of exclude.hip on 32-bit rows, scaled to any slot count: rows that share their low bits, or are
-// multiples of the slot count, spread over the table)
-__device__ inline uint32_t cf_slot(uint32_t row, uint32_t slots) {
-    return (uint32_t)(((uint64_t)(row * 0x9E3779B1u) * slots) >> 32);
-}
-
 __device__ inline bool cf_less(const ulonglong2& a, const ulonglong2& b) { return a.x < b.x || (a.x == b.x && a.y < b.y); }
 
 // The accumulation over one request's staged triggers and the compaction of its occupied slots into cand[0 .. *n_items), in
 // no particular order (the order is made by the sort); *max_bits = the largest positive score's bits.  One body for both
-// tiers: keys / acc are LDS or the request's slice of the global tables, `slots` a multiple of kCfThreads.
-template <bool kLds>
+// tiers: keys / acc are LDS or the request's slice of the global tables, `slots` a multiple of kCfThreads.  kMax: the reduction
+// of pg_rtu2i_expand — a later term replaces the item's score only when it is larger — in place of the sum.
+template <bool kLds, bool kMax>
 __device__ void cf_accumulate(const CfArgs& a, uint32_t* keys, double* acc, uint32_t slots, uint32_t nt, const uint64_t* tb_begin,
                               const double* tb_pref, const uint32_t* tb_len, ulonglong2* cand, uint32_t* n_items,
                               unsigned long long* max_bits) {
@@ -130,7 +131,8 @@ __device__ void cf_accumulate(const CfArgs& a, uint32_t* keys, double* acc, uint
                     break;
                 }
                 if (cur == nb) {
-                    acc[h] = acc[h] + term;
+                    if (!kMax) acc[h] = acc[h] + term;
+                    else if (term > acc[h]) acc[h] = term;
                     break;
                 }
             }
@@ -223,6 +225,7 @@ __device__ inline void cf_pad(const CfArgs& a, uint32_t q, uint32_t from) {
 }
 
 // Request q = blockIdx.x.  trigger_prefer must be finite (the host entry point checks it).
+template <bool kMax>
 __global__ __launch_bounds__(kCfThreads) void cf_recall_kernel(CfArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char cf_lds[];
     uint64_t* tb_begin = reinterpret_cast<uint64_t*>(cf_lds + kCfTableBytes);
@@ -232,8 +235,8 @@ __global__ __launch_bounds__(kCfThreads) void cf_recall_kernel(CfArgs a) {
     uint32_t* n_pairs = reinterpret_cast<uint32_t*>(max_bits + 1);
     uint32_t* n_items = n_pairs + 1;
     const uint32_t q = blockIdx.x, tid = threadIdx.x;
-    const uint32_t t0 = a.trig_off[q];
-    const uint32_t nt = min(a.trig_off[q + 1] - t0, kCfMaxTriggers);
+    const uint32_t t0 = a.trig_off ? a.trig_off[q] : q * a.trig_stride;
+    const uint32_t nt = min(a.trig_off ? a.trig_off[q + 1] - t0 : min(a.trig_cnt[q], a.trig_stride), kCfMaxTriggers);
     if (tid == 0) {
         *max_bits = 0;
         *n_pairs = 0;
@@ -269,13 +272,13 @@ __global__ __launch_bounds__(kCfThreads) void cf_recall_kernel(CfArgs a) {
     if (pairs <= min(a.lds_max_pairs, kCfLdsMaxPairs)) {
         double* acc = reinterpret_cast<double*>(cf_lds);
         uint32_t* keys = reinterpret_cast<uint32_t*>(cf_lds + (size_t)kCfLdsSlots * 8);
-        cf_accumulate<true>(a, keys, acc, kCfLdsSlots, nt, tb_begin, tb_pref, tb_len, cand, n_items, max_bits);
+        cf_accumulate<true, kMax>(a, keys, acc, kCfLdsSlots, nt, tb_begin, tb_pref, tb_len, cand, n_items, max_bits);
     } else {
         uint32_t slots = kCfThreads;
         while (slots < 2 * pairs) slots <<= 1;
         slots = min(slots, a.gslots);                    // (distinct items <= min(pairs, rows) <= gslots / 2 either way)
-        cf_accumulate<false>(a, a.gkeys + (size_t)q * a.gslots, a.gacc + (size_t)q * a.gslots, slots, nt, tb_begin, tb_pref, tb_len,
-                             cand, n_items, max_bits);
+        cf_accumulate<false, kMax>(a, a.gkeys + (size_t)q * a.gslots, a.gacc + (size_t)q * a.gslots, slots, nt, tb_begin, tb_pref, tb_len,
+                                   cand, n_items, max_bits);
     }
     const uint32_t n = min(*n_items, a.cand_cap);
     if (n == 0) {
@@ -338,23 +341,24 @@ __global__ void cf_fill_u64_kernel(uint64_t* __restrict__ p, uint64_t n, uint64_
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) p[i] = v;
 }
 
-// the arguments every form of the recall checks, in this order
+// the arguments every form of the recall checks, in this order (dev_trig: the triggers are a CfTrigDev made by the call itself —
+// no trigger arrays, no offsets)
 int cf_check(const char* who, const pg_ctx* ctx, const pg_simtable* s, const void* trig, const void* pref, const uint32_t* off, uint32_t nq,
-             uint32_t k, const pg_cf_opts* opts, const void* rows, const void* scores, uint32_t* nmax_out) {
-    PG_REQUIRE(ctx && s && off && rows && scores, "%s: NULL argument", who);
+             uint32_t k, const pg_cf_opts* opts, const void* rows, const void* scores, uint32_t* nmax_out, bool dev_trig = false) {
+    PG_REQUIRE(ctx && s && (off || dev_trig) && rows && scores, "%s: NULL argument", who);
     PG_REQUIRE(nq >= 1 && nq <= (uint32_t)kMaxQueries, "%s: nq=%u must be in [1,%d]", who, nq, kMaxQueries);
     if (k < 1 || k > kCfMaxDepth) {
         set_error("%s: k=%u unsupported (1..%u)", who, k, kCfMaxDepth);
         return PG_ERR_UNSUPPORTED;
     }
-    for (uint32_t q = 0; q < nq; ++q) {
+    for (uint32_t q = 0; q < nq && !dev_trig; ++q) {
         PG_REQUIRE(off[q + 1] >= off[q], "%s: trigger_offsets[%u] = %u is below trigger_offsets[%u] = %u", who, q + 1, off[q + 1], q, off[q]);
         if (off[q + 1] - off[q] > kCfMaxTriggers) {
             set_error("%s: request %u has %u triggers (at most %u per request)", who, q, off[q + 1] - off[q], kCfMaxTriggers);
             return PG_ERR_UNSUPPORTED;
         }
     }
-    PG_REQUIRE((trig && pref) || off[nq] == off[0], "%s: NULL argument", who);
+    PG_REQUIRE(dev_trig || (trig && pref) || off[nq] == off[0], "%s: NULL argument", who);
     uint32_t nmax = 0;
     const uint32_t* xo = opts ? opts->excl_offsets : nullptr;
     if (xo) {
@@ -380,10 +384,13 @@ int cf_check(const char* who, const pg_ctx* ctx, const pg_simtable* s, const voi
 
 // The recall of nq requests whose triggers are device memory (indexed by the host offsets `off` as given) into device outputs
 // [nq][k]; lists: host ids (staged here) or device ids, host offsets.  Caller holds ctx->mu, the item table's shared lock and
-// the similarity table's; ends synchronised.
+// the similarity table's; ends synchronised.  max_rule: pg_rtu2i_expand's reduction (no normalisation).  With `off` NULL the
+// triggers are what make_trig describes: it is called once everything of this call is staged and its staging synchronised,
+// right in front of the launch, so what it enqueues (the trigger kernel) and the expansion run back to back on the stream.
 int cf_recall_locked(const char* who, pg_ctx* ctx, const pg_simtable* s, const uint32_t* d_trig, const double* d_pref, const uint32_t* off,
                      uint32_t nq, uint32_t k, int normalize, const uint64_t* excl, bool excl_on_host, const uint32_t* xoff, uint32_t nmax,
-                     uint64_t* d_out_rows, double* d_out_scores, uint32_t* out_count) {
+                     uint64_t* d_out_rows, double* d_out_scores, uint32_t* out_count, bool max_rule = false,
+                     const std::function<int(CfTrigDev*)>& make_trig = nullptr) {
     int rc;
     const uint32_t rows_eff = (uint32_t)std::min<uint64_t>(kCfMaxPairs, s->rows);
     uint32_t gslots = kCfThreads, cand_cap = 1;
@@ -394,7 +401,7 @@ int cf_recall_locked(const char* who, pg_ctx* ctx, const pg_simtable* s, const u
     uint32_t *d_status, *d_off, *d_xoff, *d_keys; uint64_t *d_list, *d_xrows; double *d_acc, *d_xsc; ulonglong2* d_cand; float *d_xidx, *d_oidx;
     if ((rc = scratch_carve(ctx, kSlotCf, [&](Carve& c) {
             d_status = c.take<uint32_t>(1 + (size_t)kMaxQueries);      // ONE region, copied out together: [0] the status word, [1 + q] request q's count
-            d_off = c.take<uint32_t>((size_t)nq + 1);
+            d_off = c.take<uint32_t>(off ? (size_t)nq + 1 : 0);
             d_xoff = c.take<uint32_t>((size_t)nq + 1);
             d_list = c.take<uint64_t>(xtotal);
             d_keys = c.take<uint32_t>((size_t)nq * gslots);
@@ -407,22 +414,26 @@ int cf_recall_locked(const char* who, pg_ctx* ctx, const pg_simtable* s, const u
         }))) return rc;
     uint32_t h_xoff[kMaxQueries + 1];
     PG_HIP(hipMemsetAsync(d_status, 0xFF, 4, ctx->stream));
-    PG_HIP(hipMemcpyAsync(d_off, off, ((size_t)nq + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (off) PG_HIP(hipMemcpyAsync(d_off, off, ((size_t)nq + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
     if (nmax) {
         for (uint32_t q = 0; q <= nq; ++q) h_xoff[q] = excl_on_host ? xoff[q] - xoff[0] : xoff[q];
         PG_HIP(hipMemcpyAsync(d_xoff, h_xoff, ((size_t)nq + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
         if (xtotal) PG_HIP(hipMemcpyAsync(d_list, excl + xoff[0], (size_t)xtotal * 8, hipMemcpyHostToDevice, ctx->stream));
     }
     PG_HIP(hipStreamSynchronize(ctx->stream));           // (the staged offsets live on the callers' frames)
+    CfTrigDev td;
+    if (!off && (rc = make_trig(&td))) return rc;
     CfArgs a;
     a.off = s->d_off;
     a.nbr = s->d_nbr;
     a.sim = s->d_sim;
     a.rows = (uint32_t)s->rows;
     a.row_offset = s->t->row_offset;
-    a.trig = d_trig;
-    a.pref = d_pref;
-    a.trig_off = d_off;
+    a.trig = off ? d_trig : td.d_rows;
+    a.pref = off ? d_pref : td.d_weight;
+    a.trig_off = off ? d_off : nullptr;
+    a.trig_cnt = td.d_count;
+    a.trig_stride = td.stride;
     a.lds_max_pairs = std::min(ctx->knobs.cf_lds_max_pairs, kCfLdsMaxPairs);
     a.gslots = gslots;
     a.gkeys = d_keys;
@@ -436,8 +447,13 @@ int cf_recall_locked(const char* who, pg_ctx* ctx, const pg_simtable* s, const u
     a.out_idx = nmax ? d_xidx : nullptr;
     a.out_count = d_status + 1;
     a.status = d_status;
-    if ((rc = ensure_dyn_lds(ctx, (const void*)cf_recall_kernel, kCfLds))) return rc;
-    cf_recall_kernel<<<nq, kCfThreads, kCfLds, ctx->stream>>>(a);
+    if (max_rule) {
+        if ((rc = ensure_dyn_lds(ctx, (const void*)cf_recall_kernel<true>, kCfLds))) return rc;
+        cf_recall_kernel<true><<<nq, kCfThreads, kCfLds, ctx->stream>>>(a);
+    } else {
+        if ((rc = ensure_dyn_lds(ctx, (const void*)cf_recall_kernel<false>, kCfLds))) return rc;
+        cf_recall_kernel<false><<<nq, kCfThreads, kCfLds, ctx->stream>>>(a);
+    }
     PG_HIP(hipGetLastError());
     if (nmax) {
         // the existing compaction on the row plane; its fp32 score plane carries each entry's index into the fp64 scores
@@ -458,7 +474,7 @@ int cf_recall_locked(const char* who, pg_ctx* ctx, const pg_simtable* s, const u
 }
 
 int cf_entry(const char* who, pg_ctx* ctx, const pg_simtable* s, const uint32_t* trig, const double* pref, const uint32_t* off, uint32_t nq,
-             uint32_t k, const pg_cf_opts* opts, uint64_t* rows, double* scores, uint32_t* out_count, bool host) {
+             uint32_t k, const pg_cf_opts* opts, uint64_t* rows, double* scores, uint32_t* out_count, bool host, bool max_rule = false) {
     int rc;
     uint32_t nmax = 0;
     if ((rc = cf_check(who, ctx, s, trig, pref, off, nq, k, opts, rows, scores, &nmax))) return rc;
@@ -466,7 +482,7 @@ int cf_entry(const char* who, pg_ctx* ctx, const pg_simtable* s, const uint32_t*
     if (host)
         for (uint32_t i = 0; i < total; ++i)
             PG_REQUIRE(std::isfinite(pref[off[0] + i]), "%s: trigger_prefer[%u] is not finite", who, off[0] + i);
-    const int normalize = opts ? opts->normalize : 1;
+    const int normalize = max_rule ? 0 : opts ? opts->normalize : 1;
     std::lock_guard<std::mutex> g(ctx->mu);
     PG_HIP(hipSetDevice(ctx->device));
     TableRead tr(s->t->rw);
@@ -476,7 +492,7 @@ int cf_entry(const char* who, pg_ctx* ctx, const pg_simtable* s, const uint32_t*
                who, (unsigned long long)s->gen, (unsigned long long)gen);
     const uint64_t* excl = opts ? opts->excl_rows : nullptr;
     const uint32_t* xoff = opts ? opts->excl_offsets : nullptr;
-    if (!host) return cf_recall_locked(who, ctx, s, trig, pref, off, nq, k, normalize, excl, false, xoff, nmax, rows, scores, out_count);
+    if (!host) return cf_recall_locked(who, ctx, s, trig, pref, off, nq, k, normalize, excl, false, xoff, nmax, rows, scores, out_count, max_rule);
     // host buffers: triggers and preferences in, rows and scores out, through the staging slot
     uint32_t* d_trig; double *d_pref, *d_sc; uint64_t* d_rows;
     if ((rc = scratch_carve(ctx, kSlotStaging, [&](Carve& c) {
@@ -491,8 +507,62 @@ int cf_entry(const char* who, pg_ctx* ctx, const pg_simtable* s, const uint32_t*
         PG_HIP(hipMemcpyAsync(d_trig, trig + off[0], (size_t)total * 4, hipMemcpyHostToDevice, ctx->stream));
         PG_HIP(hipMemcpyAsync(d_pref, pref + off[0], (size_t)total * 8, hipMemcpyHostToDevice, ctx->stream));
     }
-    rc = cf_recall_locked(who, ctx, s, d_trig, d_pref, h_off, nq, k, normalize, excl, true, xoff, nmax, d_rows, d_sc, out_count);
+    rc = cf_recall_locked(who, ctx, s, d_trig, d_pref, h_off, nq, k, normalize, excl, true, xoff, nmax, d_rows, d_sc, out_count, max_rule);
     if (rc) return rc;
+    PG_HIP(hipMemcpyAsync(rows, d_rows, (size_t)nq * k * 8, hipMemcpyDeviceToHost, ctx->stream));
+    PG_HIP(hipMemcpyAsync(scores, d_sc, (size_t)nq * k * 8, hipMemcpyDeviceToHost, ctx->stream));
+    PG_HIP(hipStreamSynchronize(ctx->stream));
+    return PG_OK;
+}
+
+// RealTimeU2IRecall in one call: the trigger kernel writes each request's trigger list into kSlotRtU2I, the
+// expansion kernel reads it through CfTrigDev; the two launches follow each other on the stream.  host: events in, answer out
+// through the staging slot.
+int rt_recall_entry(const char* who, pg_ctx* ctx, pg_rtu2i* c, const pg_simtable* s, const uint32_t* ev_rows, const uint16_t* ev_code,
+                    const double* ev_pt, const int64_t* ev_time, const uint32_t* ev_off, const int64_t* now, uint32_t nq, uint32_t k,
+                    const pg_cf_opts* opts, uint64_t* rows, double* scores, uint32_t* out_count, bool host) {
+    int rc;
+    uint32_t nmax = 0;
+    PG_REQUIRE(ctx && c && s, "%s: NULL argument", who);
+    if ((rc = rt_check(who, c, s->rows, ev_rows, ev_code, ev_time, ev_off, now, nq))) return rc;
+    if ((rc = cf_check(who, ctx, s, nullptr, nullptr, nullptr, nq, k, opts, rows, scores, &nmax, true))) return rc;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    PG_HIP(hipSetDevice(ctx->device));
+    TableRead tr(s->t->rw);
+    std::shared_lock<std::shared_mutex> sr(s->rw);
+    const uint64_t gen = s->t->generation.load(std::memory_order_relaxed);
+    PG_REQUIRE(gen == s->gen, "%s: the similarity table describes generation %llu of its item table, which is at generation %llu (stale)",
+               who, (unsigned long long)s->gen, (unsigned long long)gen);
+    const uint64_t* excl = opts ? opts->excl_rows : nullptr;
+    const uint32_t* xoff = opts ? opts->excl_offsets : nullptr;
+    const uint32_t total = ev_off[nq] - ev_off[0];
+    uint32_t h_off[kMaxQueries + 1];
+    for (uint32_t q = 0; q <= nq; ++q) h_off[q] = host ? ev_off[q] - ev_off[0] : ev_off[q];
+    uint32_t* d_er = nullptr; uint16_t* d_ec = nullptr; double *d_ep = nullptr, *d_sc = nullptr; int64_t* d_et = nullptr; uint64_t* d_rows = nullptr;
+    if (host) {
+        if ((rc = scratch_carve(ctx, kSlotStaging, [&](Carve& cv) {
+                d_er = cv.take<uint32_t>(total);
+                d_ec = cv.take<uint16_t>(total);
+                d_ep = cv.take<double>(ev_pt ? total : 0);
+                d_et = cv.take<int64_t>(total);
+                d_rows = cv.take<uint64_t>((size_t)nq * k);
+                d_sc = cv.take<double>((size_t)nq * k);
+            }))) return rc;
+        if (total) {
+            PG_HIP(hipMemcpyAsync(d_er, ev_rows + ev_off[0], (size_t)total * 4, hipMemcpyHostToDevice, ctx->stream));
+            PG_HIP(hipMemcpyAsync(d_ec, ev_code + ev_off[0], (size_t)total * 2, hipMemcpyHostToDevice, ctx->stream));
+            if (ev_pt) PG_HIP(hipMemcpyAsync(d_ep, ev_pt + ev_off[0], (size_t)total * 8, hipMemcpyHostToDevice, ctx->stream));
+            PG_HIP(hipMemcpyAsync(d_et, ev_time + ev_off[0], (size_t)total * 8, hipMemcpyHostToDevice, ctx->stream));
+        }
+    }
+    const auto make_trig = [&](CfTrigDev* td) {
+        return rt_triggers_enqueue_locked(who, ctx, c, (uint32_t)s->rows, host ? d_er : ev_rows, host ? d_ec : ev_code,
+                                          host ? (ev_pt ? d_ep : nullptr) : ev_pt, host ? d_et : ev_time, h_off, now, nq, nullptr, nullptr,
+                                          nullptr, td);
+    };
+    rc = cf_recall_locked(who, ctx, s, nullptr, nullptr, nullptr, nq, k, 0, excl, host, xoff, nmax, host ? d_rows : rows, host ? d_sc : scores,
+                          out_count, true, make_trig);
+    if (rc || !host) return rc;
     PG_HIP(hipMemcpyAsync(rows, d_rows, (size_t)nq * k * 8, hipMemcpyDeviceToHost, ctx->stream));
     PG_HIP(hipMemcpyAsync(scores, d_sc, (size_t)nq * k * 8, hipMemcpyDeviceToHost, ctx->stream));
     PG_HIP(hipStreamSynchronize(ctx->stream));
@@ -639,6 +709,33 @@ int pg_cf_recall_dev(pg_ctx* ctx, const pg_simtable* s, const uint32_t* d_trigge
                      double* d_out_scores, uint32_t* out_count) {
     return pg::cf_entry("pg_cf_recall_dev", ctx, s, d_trigger_rows, d_trigger_prefer, trigger_offsets, nq, k, opts, d_out_rows, d_out_scores,
                         out_count, false);
+}
+
+int pg_rtu2i_expand(pg_ctx* ctx, const pg_simtable* s, const uint32_t* trigger_rows, const double* trigger_prefer, const uint32_t* trigger_offsets,
+                    uint32_t nq, uint32_t k, const pg_cf_opts* opts, uint64_t* out_rows, double* out_scores, uint32_t* out_count) {
+    return pg::cf_entry("pg_rtu2i_expand", ctx, s, trigger_rows, trigger_prefer, trigger_offsets, nq, k, opts, out_rows, out_scores, out_count, true,
+                        true);
+}
+
+int pg_rtu2i_expand_dev(pg_ctx* ctx, const pg_simtable* s, const uint32_t* d_trigger_rows, const double* d_trigger_prefer,
+                        const uint32_t* trigger_offsets, uint32_t nq, uint32_t k, const pg_cf_opts* opts, uint64_t* d_out_rows,
+                        double* d_out_scores, uint32_t* out_count) {
+    return pg::cf_entry("pg_rtu2i_expand_dev", ctx, s, d_trigger_rows, d_trigger_prefer, trigger_offsets, nq, k, opts, d_out_rows, d_out_scores,
+                        out_count, false, true);
+}
+
+int pg_rtu2i_recall(pg_ctx* ctx, pg_rtu2i* c, const pg_simtable* s, const uint32_t* event_rows, const uint16_t* event_code,
+                    const double* event_play_time, const int64_t* event_time, const uint32_t* event_offsets, const int64_t* now, uint32_t nq,
+                    uint32_t k, const pg_cf_opts* opts, uint64_t* out_rows, double* out_scores, uint32_t* out_count) {
+    return pg::rt_recall_entry("pg_rtu2i_recall", ctx, c, s, event_rows, event_code, event_play_time, event_time, event_offsets, now, nq, k, opts,
+                               out_rows, out_scores, out_count, true);
+}
+
+int pg_rtu2i_recall_dev(pg_ctx* ctx, pg_rtu2i* c, const pg_simtable* s, const uint32_t* d_event_rows, const uint16_t* d_event_code,
+                        const double* d_event_play_time, const int64_t* d_event_time, const uint32_t* event_offsets, const int64_t* now,
+                        uint32_t nq, uint32_t k, const pg_cf_opts* opts, uint64_t* d_out_rows, double* d_out_scores, uint32_t* out_count) {
+    return pg::rt_recall_entry("pg_rtu2i_recall_dev", ctx, c, s, d_event_rows, d_event_code, d_event_play_time, d_event_time, event_offsets, now, nq,
+                               k, opts, d_out_rows, d_out_scores, out_count, false);
 }
 
 }  // extern "C"

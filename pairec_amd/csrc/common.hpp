@@ -88,6 +88,7 @@ enum ScratchSlot : int {
     kSlotMix = 29,           // mixsort.hip: the strategy masks and the taken lists of a mix sort; the one-request entry's staging behind them
     kSlotSsdStage = 30,      // ssd.hip pg_ssd_sort_dev: per-request counts and states, the position maps, the cut lists' rows and quality, the picks (kSlotWork stays the grid kernel's)
     kSlotDimcap = 31,        // dimcap.hip: the scratch tier's keys and counts of a value cap; the one-request entry's staging behind them
+    kSlotRtU2I = 32,         // rtu2i.hip: the staged event offsets and clocks of a trigger stage; in pg_rtu2i_recall_dev the trigger lists between its two launches (cf.hip's expansion reads them while kSlotCf is its own)
     kSlotCount
 };
 

@@ -641,14 +641,16 @@ struct GvParser {
     pg_expr* e;
     int depth = 0, max_depth = 0, nest = 0;
     std::string err;
-    GvParser(const std::string& src, pg_expr* out) : s(src), e(out) {}
+    uint32_t fns;                                 // GvFunctions: the function table of the front end
+    GvParser(const std::string& src, pg_expr* out, uint32_t functions) : s(src), e(out), fns(functions) {}
+    const char* fn_names() const { return fns == kGvExp ? "exp" : "round"; }
     void ws() { while (i < s.size() && (s[i] == ' ' || s[i] == '\t' || s[i] == '\n' || s[i] == '\r')) ++i; }
     bool fail(const std::string& m) { if (err.empty()) err = m; return false; }
     bool at(const char* t) { ws(); return s.compare(i, strlen(t), t) == 0; }
     void push(uint32_t op, uint32_t arg, double val) {
         e->prog.push_back({op, arg, val});
         if (op == OP_CONST || op == OP_VAR) max_depth = std::max(max_depth, ++depth);
-        else if (op != OP_NEG && op != OP_ROUND) --depth;
+        else if (op != OP_NEG && op != OP_ROUND && op != OP_EXP) --depth;
     }
     uint32_t var(const std::string& name) {
         uint32_t idx = 0;
@@ -709,8 +711,18 @@ struct GvParser {
             i = j;
             ws();
             if (i < s.size() && s[i] == '(') {
-                if (name != "round") return fail("the function \"" + name + "\" is not in the served subset (functions: round)");
+                const bool known = (name == "round" && (fns & kGvRound)) || (name == "exp" && (fns & kGvExp));
+                if (!known) return fail("the function \"" + name + "\" is not in the served subset (functions: " + fn_names() + ")");
                 ++i;
+                if (name == "exp") {
+                    if (!add()) return false;
+                    ws();
+                    if (i < s.size() && s[i] == ',') return fail("exp: wrong number of arguments");
+                    if (i >= s.size() || s[i] != ')') return unexpected("exp: missing ')'");
+                    ++i;
+                    push(OP_EXP, 0, 0.0);
+                    return true;
+                }
                 if (!add()) return false;
                 ws();
                 if (i < s.size() && s[i] == ',') {
@@ -728,7 +740,7 @@ struct GvParser {
                 push(OP_ROUND, 0, 0.0);
                 return true;
             }
-            if (name == "round") return fail("the function \"round\" needs its argument list");
+            if (name == "round" && (fns & kGvRound)) return fail("the function \"round\" needs its argument list");
             push(OP_VAR, var(name), 0.0);
             return true;
         }
@@ -817,6 +829,31 @@ bool expr_run_host(const std::vector<Instr>& prog, const double* vars, double* o
     *out = sp > 0 ? st[sp - 1] : 0.0;
     return ok;
 }
+
+// the parse behind the two govaluate front ends (expr_prog.hpp)
+extern "C++" int gv_compile(const char* who, const char* source, uint32_t functions, pg_expr* e) {
+    e->source = source;
+    bool ok = e->source.size() <= 16384;
+    GvParser p(e->source, e, functions);
+    if (!ok) p.fail("expression too large");
+    if (ok) ok = p.add();
+    if (ok) {
+        p.ws();
+        if (p.i != e->source.size()) ok = p.unexpected("unexpected");
+    }
+    if (!ok) {
+        set_error("%s: %s at byte %zu of '%.200s' — the engine serves the arithmetic subset of govaluate "
+                  "(float64 numbers, names, [names], + - * / %% **, unary minus, parentheses, %s) and refuses the rest rather "
+                  "than evaluate it differently", who, p.err.c_str(), p.i, source, p.fn_names());
+        return PG_ERR_UNSUPPORTED;
+    }
+    if (e->prog.size() > (size_t)kMaxProg || p.max_depth > kMaxStack) {
+        set_error("%s: expression too large (%zu operations, depth %d)", who, e->prog.size(), p.max_depth);
+        return PG_ERR_UNSUPPORTED;
+    }
+    e->max_depth = p.max_depth;
+    return PG_OK;
+}
 }  // namespace pg
 
 int pg_expr_compile_govaluate(const char* source, pg_expr** out) {
@@ -828,27 +865,11 @@ int pg_expr_compile_govaluate(const char* source, pg_expr** out) {
         *out = e;
         return PG_OK;
     }
-    bool ok = e->source.size() <= 16384;
-    pg::GvParser p(e->source, e);
-    if (!ok) p.fail("expression too large");
-    if (ok) ok = p.add();
-    if (ok) {
-        p.ws();
-        if (p.i != e->source.size()) ok = p.unexpected("unexpected");
-    }
-    if (!ok) {
-        pg::set_error("pg_expr_compile_govaluate: %s at byte %zu of '%.200s' — the engine serves the arithmetic subset of govaluate "
-                      "(float64 numbers, names, [names], + - * / %% **, unary minus, parentheses, round) and refuses the rest rather "
-                      "than evaluate it differently", p.err.c_str(), p.i, source);
+    const int rc = pg::gv_compile("pg_expr_compile_govaluate", source, pg::kGvRound, e);
+    if (rc) {
         delete e;
-        return PG_ERR_UNSUPPORTED;
+        return rc;
     }
-    if (e->prog.size() > (size_t)pg::kMaxProg || p.max_depth > pg::kMaxStack) {
-        pg::set_error("pg_expr_compile_govaluate: expression too large (%zu operations, depth %d)", e->prog.size(), p.max_depth);
-        delete e;
-        return PG_ERR_UNSUPPORTED;
-    }
-    e->max_depth = p.max_depth;
     *out = e;
     return PG_OK;
 }

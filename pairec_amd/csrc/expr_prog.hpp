@@ -5,6 +5,7 @@
 
 #include <atomic>
 #include <cmath>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -22,7 +23,8 @@ enum OpCode : uint32_t { OP_CONST = 0, OP_VAR, OP_ADD, OP_SUB, OP_MUL, OP_DIV, O
                          OP_IN,     // unary: the number == one of the constants [arg & 0xFFFF, + arg >> 16) of the set's list table
                          OP_SRC,    // push: bit `source` of the mask `arg` (recall_name ==, in; a source >= 32 has no bit)
                          OP_AND, OP_OR,   // two bools, govaluate's short circuit: the left's error, else its verdict, else the right
-                         OP_NOT };  // unary on a bool
+                         OP_NOT,    // unary on a bool
+                         OP_EXP };  // RealTimeU2I's weight expression only (rtu2i.hip): exp(x) = go_exp (unary); no other front end emits it
 
 struct Instr {
     uint32_t op;
@@ -55,6 +57,12 @@ struct pg_expr {
 };
 
 namespace pg {
+
+// expr.hip: the govaluate arithmetic subset parsed into e (source, prog, vars, max_depth) for the entry point `who`.  The front
+// ends differ only in the function table they hand the parser: pg_expr_compile_govaluate utils.GovaluateFunctions' round,
+// pg_rtu2i_compile the DAO's own table, which holds only exp.  PG_ERR_UNSUPPORTED with the construct named in the message.
+enum GvFunctions : uint32_t { kGvRound = 1u, kGvExp = 2u };
+int gv_compile(const char* who, const char* source, uint32_t functions, pg_expr* e);
 
 // math.Pow as `^` sees it (utils/ast/ast.go:246; Go stdlib math/pow.go, go 1.24 per the reference's go.mod).  Go does not call a
 // libm pow: Pow(x, 1) = x and Pow(x, +-0.5) = Sqrt(x), 1 / Sqrt(x) are exact special cases, and the INTEGER part of the exponent
@@ -100,6 +108,40 @@ __host__ __device__ __forceinline__ double go_pow(double x, double y) {
         return ldexp(a1, (int)ae);
     }
     return pow(x, y);
+}
+
+// math.Exp as the exp() of RealTimeU2IRecall's WeightExpression sees it (module/realtime_user2item_hologres_dao.go:23-30:
+// real(cmplx.Exp(complex(v, 0))) = Exp(v) * cos(0) = Exp(v)).  Go's pure-Go exp (math/exp.go, the FreeBSD e_exp.c form) restated
+// operation for operation: argument reduction x = k ln2 + r with ln2 split in two, a degree-5 rational approximation in r * r,
+// then the scaling by 2^k.  This restatement IS the specification (Go's amd64 build has an assembly Exp, so parity with a Go
+// binary is unpinned, like govaluate's); it differs from libm's exp by at most one unit in the last place.  No product feeds a
+// sum as one fused operation here — host and device give the same bits —, and the scaling is two multiplications by powers of
+// two, the first exact: one rounding, in the subnormal range too (what Go's Ldexp and C's ldexp give).
+__host__ __device__ inline double go_exp(double x) {
+#pragma clang fp contract(off)
+    const double kLn2Hi = 6.93147180369123816490e-01, kLn2Lo = 1.90821492927058770002e-10, kLog2e = 1.44269504088896338700e+00;
+    const double kP1 = 1.66666666666666657415e-01, kP2 = -2.77777777770155933842e-03, kP3 = 6.61375632143793436117e-05,
+                 kP4 = -1.65339022054652515390e-06, kP5 = 4.13813679705723846039e-08;
+    if (x != x || x == __builtin_inf()) return x;
+    if (x == -__builtin_inf()) return 0.0;
+    if (x > 7.09782712893383973096e+02) return __builtin_inf();
+    if (x < -7.45133219101941108420e+02) return 0.0;
+    if (-0x1p-28 < x && x < 0x1p-28) return 1.0 + x;
+    const int k = x < 0.0 ? (int)(kLog2e * x - 0.5) : (int)(kLog2e * x + 0.5);      // (Go's int() truncates, as this cast does)
+    const double kf = (double)k;
+    const double hi = x - kf * kLn2Hi;
+    const double lo = kf * kLn2Lo;
+    const double r = hi - lo;
+    const double t = r * r;
+    const double c = r - t * (kP1 + t * (kP2 + t * (kP3 + t * (kP4 + t * kP5))));
+    const double y = 1.0 - ((lo - (r * c) / (2.0 - c)) - hi);
+    // Ldexp(y, k), k in [-1075, 1024]: both halves of k are exponents of normal numbers
+    const int k1 = k >> 1, k2 = k - k1;
+    const unsigned long long b1 = (unsigned long long)(k1 + 1023) << 52, b2 = (unsigned long long)(k2 + 1023) << 52;
+    double p1, p2;
+    memcpy(&p1, &b1, 8);
+    memcpy(&p2, &b2, 8);
+    return (y * p1) * p2;
 }
 
 // one binary operation of the program; false: the reference panics here (a zero divisor of OP_DIV / OP_MOD)

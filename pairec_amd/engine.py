@@ -1348,6 +1348,77 @@ class Table:
         return counts
 
 
+def _pack_events(rows, codes, play_time, times, now):
+    """one list of events per request → (event_rows u32, event_code u16, event_play_time f64 or None, event_time i64,
+    offsets u32 [nq + 1], now i64 [nq])"""
+    nq = len(rows)
+    if len(codes) != nq or len(times) != nq or len(now) != nq or (play_time is not None and len(play_time) != nq):
+        raise ValueError("events: every request needs its rows, codes, times and clock")
+    er = [np.asarray(a, dtype=np.uint32).reshape(-1) for a in rows]
+    ec = [np.asarray(a, dtype=np.uint16).reshape(-1) for a in codes]
+    et = [np.asarray(a, dtype=np.int64).reshape(-1) for a in times]
+    ep = [np.asarray(a, dtype=np.float64).reshape(-1) for a in play_time] if play_time is not None else None
+    if any(a.shape != b.shape or a.shape != c.shape for a, b, c in zip(er, ec, et)) or (ep and any(a.shape != b.shape for a, b in zip(er, ep))):
+        raise ValueError("events: every event needs a row, a code and a time")
+    off = np.zeros(nq + 1, dtype=np.uint32)
+    off[1:] = np.cumsum([a.shape[0] for a in er])
+
+    def cat(arrs, dt):
+        return np.ascontiguousarray(np.concatenate(arrs)) if nq else np.zeros(0, dtype=dt)
+    return (cat(er, np.uint32), cat(ec, np.uint16), cat(ep, np.float64) if ep is not None else None, cat(et, np.int64), off,
+            np.ascontiguousarray(now, dtype=np.int64))
+
+
+class RtU2I:
+    """RealTimeU2IRecall's UserTriggerDaoConf compiled (pg_rtu2i_compile): the trigger-weight expression, the event weights and
+    play-time thresholds, the weight mode and the trigger count.  event_names gives events their codes (code = index)."""
+
+    def __init__(self, weight_expression: str, event_names=(), event_weight: str = "", event_play_time: str = "", weight_mode: str = "",
+                 trigger_count: int = 0, limit: int = 0):
+        names = (C.c_char_p * max(len(event_names), 1))(*[n.encode() for n in event_names])
+        conf = _lib.PgRtU2IConf(weight_expression.encode(), event_weight.encode(), event_play_time.encode(), names, len(event_names),
+                                weight_mode.encode(), int(trigger_count), int(limit))
+        h = C.c_void_p()
+        _lib.check(_lib.load().pg_rtu2i_compile(C.byref(conf), C.byref(h)))
+        self.h = h
+        self.trigger_count = int(_lib.load().pg_rtu2i_trigger_count(h))
+
+    def free(self):
+        if self.h:
+            _lib.load().pg_rtu2i_free(self.h)
+            self.h = None
+
+    def _out(self, nq):
+        T = self.trigger_count
+        return np.empty((nq, T), dtype=np.uint32), np.empty((nq, T), dtype=np.float64), np.zeros(nq, dtype=np.uint32)
+
+    def triggers_host(self, table_rows: int, rows, codes, play_time, times, now):
+        """pg_rtu2i_triggers_host (no context, no device): rows[q], codes[q], play_time[q] (or play_time None), times[q] = request
+        q's events, newest first; now[q] its clock → (trigger rows [nq][T] u32, weights [nq][T] f64, counts [nq])"""
+        er, ec, ep, et, off, nw = _pack_events(rows, codes, play_time, times, now)
+        o = self._out(len(rows))
+        _lib.check(_lib.load().pg_rtu2i_triggers_host(self.h, int(table_rows), _ptr(er), _ptr(ec), _ptr(ep) if ep is not None else None, _ptr(et),
+                                                     _ptr(off), _ptr(nw), len(rows), _ptr(o[0]), _ptr(o[1]), _ptr(o[2])))
+        return o
+
+    def triggers(self, ctx: "Context", table_rows: int, rows, codes, play_time, times, now):
+        """pg_rtu2i_triggers: triggers_host's arguments and answer, computed on the device"""
+        er, ec, ep, et, off, nw = _pack_events(rows, codes, play_time, times, now)
+        o = self._out(len(rows))
+        _lib.check(ctx.L.pg_rtu2i_triggers(ctx.h, self.h, int(table_rows), _ptr(er), _ptr(ec), _ptr(ep) if ep is not None else None, _ptr(et),
+                                           _ptr(off), _ptr(nw), len(rows), _ptr(o[0]), _ptr(o[1]), _ptr(o[2])))
+        return o
+
+    def triggers_dev(self, ctx: "Context", table_rows: int, d_rows: int, d_codes: int, d_play_time: int, d_times: int, offsets, now,
+                     d_out_rows: int, d_out_weight: int, d_out_count: int):
+        """pg_rtu2i_triggers_dev: events and outputs are device addresses (d_play_time 0: none), offsets and now host arrays"""
+        off = np.ascontiguousarray(offsets, dtype=np.uint32)
+        nw = np.ascontiguousarray(now, dtype=np.int64)
+        _lib.check(ctx.L.pg_rtu2i_triggers_dev(ctx.h, self.h, int(table_rows), C.c_void_p(d_rows), C.c_void_p(d_codes), d_play_time or None,
+                                               C.c_void_p(d_times), _ptr(off), _ptr(nw), off.shape[0] - 1, C.c_void_p(d_out_rows),
+                                               C.c_void_p(d_out_weight), C.c_void_p(d_out_count)))
+
+
 class SimTable:
     """Item-to-item similarity lists over the local rows of `table`, resident in HBM (pg_simtable_*), and the
     collaborative-filter recall over them (pg_cf_recall).  The table must outlive it."""
@@ -1416,6 +1487,78 @@ class SimTable:
         counts = np.zeros(nq, dtype=np.uint32)
         _lib.check(self.ctx.L.pg_cf_recall_dev(self.ctx.h, self.h, C.c_void_p(d_triggers), C.c_void_p(d_prefer), _ptr(off), nq, k,
                                                C.byref(opts), C.c_void_p(d_out_rows), C.c_void_p(d_out_scores), _ptr(counts)))
+        return counts
+
+    def rtu2i_expand(self, triggers, prefer, k: int, lists=None):
+        """RealTimeU2IRecall's expansion (pg_rtu2i_expand): cf_recall's arguments, but an item keeps the LARGEST of its
+        sim * prefer terms and nothing is normalised → (rows [nq][k] uint64 global ids, scores [nq][k] f64, counts [nq])."""
+        nq = len(triggers)
+        if len(prefer) != nq:
+            raise ValueError("rtu2i_expand: %d preference lists for %d requests" % (len(prefer), nq))
+        tr = [np.asarray(t, dtype=np.uint32).reshape(-1) for t in triggers]
+        pf = [np.asarray(p, dtype=np.float64).reshape(-1) for p in prefer]
+        if any(a.shape != b.shape for a, b in zip(tr, pf)):
+            raise ValueError("rtu2i_expand: every trigger needs one preference score")
+        off = np.zeros(nq + 1, dtype=np.uint32)
+        off[1:] = np.cumsum([a.shape[0] for a in tr])
+        trc = np.ascontiguousarray(np.concatenate(tr)) if nq else np.zeros(0, dtype=np.uint32)
+        pfc = np.ascontiguousarray(np.concatenate(pf)) if nq else np.zeros(0, dtype=np.float64)
+        opts = _lib.PgCfOpts(0, None, None)
+        if lists is not None:
+            ids, xoff = _pack_lists(lists, nq)
+            opts.excl_rows, opts.excl_offsets = ids.ctypes.data, xoff.ctypes.data
+        rows = np.empty((nq, k), dtype=np.uint64)
+        scores = np.empty((nq, k), dtype=np.float64)
+        counts = np.zeros(nq, dtype=np.uint32)
+        _lib.check(self.ctx.L.pg_rtu2i_expand(self.ctx.h, self.h, _ptr(trc), _ptr(pfc), _ptr(off), nq, k, C.byref(opts),
+                                              _ptr(rows), _ptr(scores), _ptr(counts)))
+        return rows, scores, counts
+
+    def rtu2i_expand_dev(self, d_triggers: int, d_prefer: int, trigger_offsets, k: int, d_out_rows: int, d_out_scores: int,
+                         d_excl_rows: int = 0, excl_offsets=None):
+        """pg_rtu2i_expand_dev: triggers, preferences, lists and outputs are device addresses, the offsets host arrays → counts"""
+        off = np.ascontiguousarray(trigger_offsets, dtype=np.uint32)
+        nq = off.shape[0] - 1
+        opts = _lib.PgCfOpts(0, None, None)
+        if excl_offsets is not None:
+            xoff = np.ascontiguousarray(excl_offsets, dtype=np.uint32)
+            opts.excl_rows, opts.excl_offsets = d_excl_rows or None, xoff.ctypes.data
+        counts = np.zeros(nq, dtype=np.uint32)
+        _lib.check(self.ctx.L.pg_rtu2i_expand_dev(self.ctx.h, self.h, C.c_void_p(d_triggers), C.c_void_p(d_prefer), _ptr(off), nq, k,
+                                                  C.byref(opts), C.c_void_p(d_out_rows), C.c_void_p(d_out_scores), _ptr(counts)))
+        return counts
+
+    def rtu2i_recall(self, conf: "RtU2I", rows, codes, play_time, times, now, k: int, lists=None):
+        """RealTimeU2IRecall (pg_rtu2i_recall): request q's events rows[q], codes[q], play_time[q] (or play_time None), times[q],
+        newest first, and its clock now[q] → (rows [nq][k] uint64 global ids, scores [nq][k] f64, counts [nq])."""
+        er, ec, ep, et, off, nw = _pack_events(rows, codes, play_time, times, now)
+        nq = len(rows)
+        opts = _lib.PgCfOpts(0, None, None)
+        if lists is not None:
+            ids, xoff = _pack_lists(lists, nq)
+            opts.excl_rows, opts.excl_offsets = ids.ctypes.data, xoff.ctypes.data
+        out_rows = np.empty((nq, k), dtype=np.uint64)
+        scores = np.empty((nq, k), dtype=np.float64)
+        counts = np.zeros(nq, dtype=np.uint32)
+        _lib.check(self.ctx.L.pg_rtu2i_recall(self.ctx.h, conf.h, self.h, _ptr(er), _ptr(ec), _ptr(ep) if ep is not None else None, _ptr(et),
+                                              _ptr(off), _ptr(nw), nq, k, C.byref(opts), _ptr(out_rows), _ptr(scores), _ptr(counts)))
+        return out_rows, scores, counts
+
+    def rtu2i_recall_dev(self, conf: "RtU2I", d_rows: int, d_codes: int, d_play_time: int, d_times: int, offsets, now, k: int,
+                         d_out_rows: int, d_out_scores: int, d_excl_rows: int = 0, excl_offsets=None):
+        """pg_rtu2i_recall_dev: events, lists and outputs are device addresses (d_play_time 0: none), offsets and now host
+        arrays; enqueue-only between its two kernels → counts"""
+        off = np.ascontiguousarray(offsets, dtype=np.uint32)
+        nw = np.ascontiguousarray(now, dtype=np.int64)
+        nq = off.shape[0] - 1
+        opts = _lib.PgCfOpts(0, None, None)
+        if excl_offsets is not None:
+            xoff = np.ascontiguousarray(excl_offsets, dtype=np.uint32)
+            opts.excl_rows, opts.excl_offsets = d_excl_rows or None, xoff.ctypes.data
+        counts = np.zeros(nq, dtype=np.uint32)
+        _lib.check(self.ctx.L.pg_rtu2i_recall_dev(self.ctx.h, conf.h, self.h, C.c_void_p(d_rows), C.c_void_p(d_codes), d_play_time or None,
+                                                  C.c_void_p(d_times), _ptr(off), _ptr(nw), nq, k, C.byref(opts), C.c_void_p(d_out_rows),
+                                                  C.c_void_p(d_out_scores), _ptr(counts)))
         return counts
 
 
