@@ -882,7 +882,11 @@ int pg_rtu2i_recall_dev(pg_ctx* ctx, pg_rtu2i* c, const pg_simtable* s, const ui
  *             LDS, keyed on the 32-bit distance to the request's smallest id; everything else — a larger cap, ids further apart
  *             — uses context scratch with full 64-bit keys (12 B x the power of two >= 2 cap, per request).  Two ids that differ
  *             only above bit 32 are never merged.
- *   Stream    one launch on the context's stream, no synchronisation (pg_synchronize, or any later call that does). */
+ *   Stream    one launch on the context's stream, no synchronisation (pg_synchronize, or any later call that does).  One
+ *             exception, which holds for every `_dev` stage below that says "no synchronisation": a call whose scratch layout
+ *             no longer fits its slot of the context's arena waits for the stream before the slot is freed and reallocated
+ *             (kernels enqueued earlier hold the old address).  Slots grow in whole MiB and never shrink, so a serving loop
+ *             meets this while its shapes still grow, not in steady state ("Stream order is the only fence"). */
 #define PG_FANIN_MAX_SOURCES 8
 #define PG_FANIN_MAX_CAP 16384
 #define PG_FANIN_LDS_MAX_CAP 8192
