@@ -11,7 +11,7 @@
 //            exactly: the K-th best score is thr_q, a lower bound of the final K-th best
 //   scan     the lists that are not in the probe and whose bound reaches thr_q (inclusive), scored exactly; a row joins the
 //            query's candidates when its score reaches the running threshold
-//   select   recall.hip's select / final kernels: the same keys (score totalOrder descending, then row ascending) as the table pass
+//   select   recall_select.hip's select / final kernels: the same keys (score totalOrder descending, then row ascending) as the table pass
 // Every row is scored by recall.hip's rescore_kernel — the specification's k-ascending fmaf chain — so its bits are the table
 // pass's bits; pruning drops only lists whose bound proves that none of their rows can reach thr_q.
 //

@@ -10,6 +10,13 @@
 // step), so a request's scores do not depend on how many other requests share the table pass.
 // Order: score descending (IEEE totalOrder, NaN last), then row ascending, via a 64-bit key.
 //
+// This file: the table pass — its kernels, their launchers (dispatch_scan, dispatch_screen) and the plans that chain them
+// (recall_job_prepare / enqueue / check / finish).  Its siblings, sharing recall_shared.hpp:
+//   recall_select.hip  select_kernel, the final_* kernels, launch_select, final_launch, the top-k merge of per-shard lists
+//   recall_table.hip   what is derived from a table, lazily: shadows, statistics, row norms, the threshold model
+//   recall_filter.hip  row filters, the compaction of the admitted rows, filtered recalls and views
+//   recall_entry.hip   recall_dev_locked, batching, the exclusion lists and the pg_* entry points
+//
 // Kernels
 //   scan_kernel      HBM-bound.  One wave = one 32-row block at a time; rows stream HBM → LDS by
 //                    LDS-DMA (global_load_lds_dwordx4, full 128-B lines, no VGPR staging) through a
@@ -21,13 +28,8 @@
 //                    int8 / bf16 MFMA bounds every row·query score rigorously, pairs whose bound reaches the
 //                    threshold are "suspects"; rescore_kernel scores the suspects exactly from the fp32 rows.
 //                    Up to 256 queries per pass; results identical to scan_kernel's, bit for bit.
-//   select_kernel    per query: radix-select the K-th largest key of the candidates, keep the top
-//                    K, publish the new threshold (any K-th-largest-so-far is a valid lower bound,
-//                    so the result is exact for every data distribution).
-//   final_kernel     per query: bitonic sort of the K survivors in LDS, decode to (row, score).
 #include "common.hpp"
-#include "bitonic_reg.hpp"
-#include "split_sort.hpp"
+#include "recall_shared.hpp"
 
 #include <type_traits>
 
@@ -36,7 +38,7 @@ namespace pg {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int kPieceRows = 32;
+// (kPieceRows = 32: recall_shared.hpp)
 constexpr int kPieceCols = 32;                             // one 128-B line per row
 constexpr int kPieceBytes = kPieceRows * kPieceCols * 4;   // 4 KiB
 constexpr int kPieceDmas = kPieceBytes / 1024;             // LDS-DMA instructions per piece
@@ -48,24 +50,6 @@ constexpr int kScanLdsRing = kScanWaves * kRingSlots * kPieceBytes;   // 128 KiB
 constexpr int kStageCap = 280;                             // staged hits per wave (fills the LDS left by the ring)
 constexpr int kStageBytes = kStageCap * 12 + 512;          // keys + query ids + 64 counters + 64 bases
 constexpr int kScanLds = kScanLdsRing + kScanWaves * kStageBytes;
-
-__device__ __forceinline__ uint32_t f32_ordered_bits(float f) {
-    const uint32_t b = __float_as_uint(f);
-    if (f != f) return 0u;
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ uint64_t topk_key(float score, uint32_t row) {
-    return ((uint64_t)f32_ordered_bits(score) << 32) | (uint64_t)(0xFFFFFFFFu - row);
-}
-__device__ __forceinline__ float key_score(uint64_t key) {
-    const uint32_t ob = (uint32_t)(key >> 32);
-    if (ob == 0u) return __uint_as_float(0x7FC00000u);
-    const uint32_t b = (ob & 0x80000000u) ? (ob & 0x7FFFFFFFu) : ~ob;
-    return __uint_as_float(b);
-}
-__device__ __forceinline__ uint32_t key_row(uint64_t key) {
-    return 0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFu);
-}
 
 struct ScanArgs {
     const float* tab;        // [rows][DIM]
@@ -407,7 +391,6 @@ typedef float f32x8 __attribute__((ext_vector_type(8)));
 
 constexpr int kScreenMaxNQB = 8;                // 8 x 32 = 256 queries per pass at most
 constexpr int kScreenLds = 163840;              // the whole LDS of a CU: ring (128 KiB) + staging (32 KiB)
-constexpr float kScreenEps = 0.008f;
 
 struct ScreenArgs {
     const void* tab16;        // shadow of the table: bf16 (pg_table::d16) or int8 (pg_table::d8)
@@ -1380,448 +1363,6 @@ __global__ void screen_thr8_l2_kernel(const float* __restrict__ thr, const float
     a_out[q] = A;
     b_out[q] = B;
 }
-// smallest |x|^2 of every 32-row block (rows past the table's end do not count)
-// stats[0] += sum over rows of (|x|^2 - the block's smallest), stats[1] += sum of |x|^2: how much the per-block cutoff gives away
-__global__ void block_nxmin_kernel(const float* __restrict__ nx, uint64_t rows, float* __restrict__ out, uint32_t nblocks,
-                                   double* __restrict__ stats) {
-    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
-    double slack = 0.0, sum = 0.0;
-    if (b < nblocks) {
-        float m = __builtin_inff();
-        for (uint32_t i = 0; i < (uint32_t)kPieceRows; ++i) {
-            const uint64_t r = (uint64_t)b * kPieceRows + i;
-            if (r < rows) m = fminf(m, nx[r]);
-        }
-        m = m == m ? m : 0.0f;                       // (a NaN norm: no help from this block)
-        out[b] = m;
-        for (uint32_t i = 0; i < (uint32_t)kPieceRows; ++i) {
-            const uint64_t r = (uint64_t)b * kPieceRows + i;
-            if (r < rows && nx[r] == nx[r] && nx[r] < 1e30f) { slack += (double)nx[r] - (double)m; sum += (double)nx[r]; }
-        }
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-        slack += __shfl_xor(slack, off, 64);
-        sum += __shfl_xor(sum, off, 64);
-    }
-    if ((threadIdx.x & 63) == 0 && sum > 0.0) {
-        atomicAdd(&stats[0], slack);
-        atomicAdd(&stats[1], sum);
-    }
-}
-
-// Table statistics without a shadow (first pass of the int8 build): max |x|, max row L2 norm^2, finiteness.
-template <int DIM>
-__global__ __launch_bounds__(256) void table_stats_kernel(const float* __restrict__ tab, uint64_t rows,
-                                                          float* __restrict__ out_max, uint32_t* __restrict__ out_nonfinite,
-                                                          float* __restrict__ out_absmax, float* __restrict__ out_sumsq) {
-    constexpr int G = DIM / 8;
-    __shared__ float smax[4], samax[4], ssum[4];
-    __shared__ uint32_t sbad[4];
-    const uint64_t n8 = rows * (uint64_t)G;
-    float mx = 0.0f, amx = 0.0f, sum = 0.0f;
-    uint32_t bad = 0;
-    for (uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; g < ((n8 + 63) & ~63ull);
-         g += (uint64_t)gridDim.x * blockDim.x) {
-        float ss = 0.0f;
-        if (g < n8) {
-            const float4 a = reinterpret_cast<const float4*>(tab)[2 * g];
-            const float4 b = reinterpret_cast<const float4*>(tab)[2 * g + 1];
-            ss = a.x * a.x + a.y * a.y + a.z * a.z + a.w * a.w + b.x * b.x + b.y * b.y + b.z * b.z + b.w * b.w;
-            sum += ss;
-            amx = fmaxf(amx, fmaxf(fmaxf(fmaxf(fabsf(a.x), fabsf(a.y)), fmaxf(fabsf(a.z), fabsf(a.w))),
-                                   fmaxf(fmaxf(fabsf(b.x), fabsf(b.y)), fmaxf(fabsf(b.z), fabsf(b.w)))));
-        }
-#pragma unroll
-        for (int off = 1; off < G; off <<= 1) ss += __shfl_xor(ss, off, 64);
-        if (!(ss < 3.0e38f)) bad = 1;
-        mx = fmaxf(mx, ss);
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        mx = fmaxf(mx, __shfl_xor(mx, off, 64));
-        amx = fmaxf(amx, __shfl_xor(amx, off, 64));
-        sum += __shfl_xor(sum, off, 64);
-        bad |= (uint32_t)__shfl_xor((int)bad, off, 64);
-    }
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { smax[w] = mx; samax[w] = amx; ssum[w] = sum; sbad[w] = bad; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        atomicMax(reinterpret_cast<uint32_t*>(out_max), __float_as_uint(fmaxf(fmaxf(smax[0], smax[1]), fmaxf(smax[2], smax[3]))));
-        atomicMax(reinterpret_cast<uint32_t*>(out_absmax),
-                  __float_as_uint(fmaxf(fmaxf(samax[0], samax[1]), fmaxf(samax[2], samax[3]))));
-        if (sbad[0] | sbad[1] | sbad[2] | sbad[3]) atomicOr(out_nonfinite, 1u);
-        atomicAdd(out_sumsq, ssum[0] + ssum[1] + ssum[2] + ssum[3]);     // (statistics only: decides int8 vs bf16)
-    }
-}
-
-// Second pass: the int8 shadow X = clamp(rint(x / s), +-127) and the largest row residual ||x - s X||^2.
-// A thread converts 8 consecutive values (one 8-byte store); DIM/8 neighbouring lanes share a row.
-template <int DIM>
-__global__ __launch_bounds__(256) void table_quant8_kernel(const float* __restrict__ tab, uint64_t rows, float s,
-                                                           int8_t* __restrict__ out8, float* __restrict__ out_resid) {
-    constexpr int G = DIM / 8;
-    __shared__ float smax[4];
-    const uint64_t n8 = rows * (uint64_t)G;
-    const float inv = 1.0f / s;
-    float mx = 0.0f;
-    for (uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; g < ((n8 + 63) & ~63ull);
-         g += (uint64_t)gridDim.x * blockDim.x) {
-        float rs = 0.0f;
-        if (g < n8) {
-            const float4 a = reinterpret_cast<const float4*>(tab)[2 * g];
-            const float4 b = reinterpret_cast<const float4*>(tab)[2 * g + 1];
-            const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-            uint32_t w[2] = {0, 0};
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                int X = __float2int_rn(v[i] * inv);
-                X = X > 127 ? 127 : (X < -127 ? -127 : X);
-                const float r = __fmaf_rn(-s, (float)X, v[i]);
-                rs = __fmaf_rn(r, r, rs);
-                w[i >> 2] |= (uint32_t)(X & 0xff) << (8 * (i & 3));
-            }
-            reinterpret_cast<uint2*>(out8)[g] = make_uint2(w[0], w[1]);
-        }
-#pragma unroll
-        for (int off = 1; off < G; off <<= 1) rs += __shfl_xor(rs, off, 64);
-        mx = fmaxf(mx, rs);
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) smax[w] = mx;
-    __syncthreads();
-    if (threadIdx.x == 0)
-        atomicMax(reinterpret_cast<uint32_t*>(out_resid), __float_as_uint(fmaxf(fmaxf(smax[0], smax[1]), fmaxf(smax[2], smax[3]))));
-}
-
-// Table preparation for the screen, one coalesced pass: the bf16 shadow of the rows (RNE, what
-// v_cvt_pk_bf16_f32 gives) and the statistics the error bound needs — max row L2 norm (upper bound) and
-// finiteness.  A thread converts 8 consecutive values; DIM/8 neighbouring lanes share a row.
-template <int DIM>
-__global__ __launch_bounds__(256) void table_shadow_kernel(const float* __restrict__ tab, uint64_t rows,
-                                                           uint16_t* __restrict__ out16,
-                                                           float* __restrict__ out_max,
-                                                           uint32_t* __restrict__ out_nonfinite,
-                                                           float* __restrict__ out_blk_norm2) {
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
-    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-    constexpr int G = DIM / 8;                       // lanes per row (8 or 16)
-    __shared__ float smax[4];
-    __shared__ uint32_t sbad[4];
-    const uint64_t n8 = rows * (uint64_t)G;          // 8-value groups in the table
-    float mx = 0.0f;
-    uint32_t bad = 0;
-    for (uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; g < ((n8 + 63) & ~63ull);
-         g += (uint64_t)gridDim.x * blockDim.x) {
-        float ss = 0.0f;
-        if (g < n8) {
-            const float4 a = reinterpret_cast<const float4*>(tab)[2 * g];
-            const float4 b = reinterpret_cast<const float4*>(tab)[2 * g + 1];
-            const f32x2 p0 = {a.x, a.y}, p1 = {a.z, a.w}, p2 = {b.x, b.y}, p3 = {b.z, b.w};
-            uint4 o;
-            o.x = __builtin_bit_cast(uint32_t, __builtin_convertvector(p0, bf16x2));
-            o.y = __builtin_bit_cast(uint32_t, __builtin_convertvector(p1, bf16x2));
-            o.z = __builtin_bit_cast(uint32_t, __builtin_convertvector(p2, bf16x2));
-            o.w = __builtin_bit_cast(uint32_t, __builtin_convertvector(p3, bf16x2));
-            reinterpret_cast<uint4*>(out16)[g] = o;
-            ss = a.x * a.x + a.y * a.y + a.z * a.z + a.w * a.w + b.x * b.x + b.y * b.y + b.z * b.z + b.w * b.w;
-        }
-#pragma unroll
-        for (int off = 1; off < G; off <<= 1) ss += __shfl_xor(ss, off, 64);     // the row's sum of squares
-        if (!(ss < 3.0e38f)) bad = 1;                 // NaN, inf or overflow
-        mx = fmaxf(mx, ss);
-        // largest row norm^2 of the 32-row block: a wave holds 64 / G consecutive rows of one block
-        float wm = ss;
-#pragma unroll
-        for (int off = G; off < 64; off <<= 1) wm = fmaxf(wm, __shfl_xor(wm, off, 64));
-        if ((threadIdx.x & 63) == 0 && g < n8)
-            atomicMax(reinterpret_cast<uint32_t*>(out_blk_norm2) + (g / G) / kPieceRows, __float_as_uint(fmaxf(wm, 0.0f)));
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        mx = fmaxf(mx, __shfl_xor(mx, off, 64));
-        bad |= (uint32_t)__shfl_xor((int)bad, off, 64);
-    }
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { smax[w] = mx; sbad[w] = bad; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const float m = fmaxf(fmaxf(smax[0], smax[1]), fmaxf(smax[2], smax[3]));
-        atomicMax(reinterpret_cast<uint32_t*>(out_max), __float_as_uint(m));   // non-negative floats order as uints
-        if (sbad[0] | sbad[1] | sbad[2] | sbad[3]) atomicOr(out_nonfinite, 1u);
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// select: keep the K largest keys of cand_in[q][0..M) in cand_out[q][0..min(M,K)), set cnt, thr.
-// One 1024-thread workgroup per query; 8 radix passes (one byte each) over L2-resident keys.
-// ---------------------------------------------------------------------------------------------
-constexpr uint32_t kSelLdsKeys = 16384;          // candidate lists up to this size are selected in LDS
-
-// Block-wide radix-select helper state lives in LDS; keys come from `src` (LDS or global).
-__global__ __launch_bounds__(1024) void select_kernel(const uint64_t* __restrict__ cand_in,
-                                                      uint64_t* __restrict__ cand_out,
-                                                      uint32_t* __restrict__ cnt,
-                                                      float* __restrict__ thr, uint32_t cap,
-                                                      uint32_t K, int thr_only, uint32_t* __restrict__ cnt_seen) {
-    // thr_only: the lists stay as they are (cand_out is not written, cnt unchanged); the query's threshold rises to the
-    // score of its K-th largest candidate so far — when it has that many (the refinement step of the pilot plan)
-    extern __shared__ __attribute__((aligned(16))) char sel_smem[];
-    uint64_t* const lkeys = reinterpret_cast<uint64_t*>(sel_smem);          // [kSelLdsKeys] when used
-    __shared__ uint32_t hist[256];
-    __shared__ uint32_t s_digit, s_need, s_out, s_cnt;
-    __shared__ unsigned long long s_min, s_max;
-    const uint32_t q = blockIdx.x;
-    const uint64_t* in = cand_in + (uint64_t)q * cap;
-    uint64_t* out = cand_out + (uint64_t)q * cap;
-    uint32_t M = cnt[q];
-    if (threadIdx.x == 0 && cnt_seen) cnt_seen[q] = M;      // (statistics: the candidates collected before K of them are kept)
-    if (M > cap) M = cap;
-    const uint32_t tid = threadIdx.x;
-    if (tid == 0) { s_min = ~0ull; s_max = 0ull; }
-    __syncthreads();
-    const bool in_lds = M <= kSelLdsKeys;
-    // pass 0: stage the keys in LDS (when they fit) and find their range
-    unsigned long long mn = ~0ull, mx = 0ull;
-    for (uint32_t i = tid; i < M; i += 1024) {
-        const uint64_t k = in[i];
-        if (in_lds) lkeys[i] = k;
-        mn = k < mn ? k : mn;
-        mx = k > mx ? k : mx;
-    }
-    // wave-level reduce, then one LDS atomic per wave
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned long long omn = __shfl_xor(mn, off), omx = __shfl_xor(mx, off);
-        mn = omn < mn ? omn : mn;
-        mx = omx > mx ? omx : mx;
-    }
-    if ((tid & 63) == 0) {
-        atomicMin(&s_min, mn);
-        atomicMax(&s_max, mx);
-    }
-    __syncthreads();
-    const uint64_t kmin = s_min, kmax = s_max;
-    const uint64_t* src = in_lds ? lkeys : in;
-    if (M <= K) {
-        if (!thr_only)
-            for (uint32_t i = tid; i < M; i += 1024) out[i] = src[i];
-        if (tid == 0) {
-            if (!thr_only) cnt[q] = M;
-            if (M == K && K > 0) thr[q] = key_score(kmin);     // threshold = score of the smallest key
-        }
-        return;
-    }
-    // radix select of the K-th largest of (key - kmin): only the bits below the span's top bit vary,
-    // so the first digit is already well spread (no single hot histogram bin)
-    const uint64_t span = kmax - kmin;
-    int shift = span ? (63 - __clzll((long long)span)) - 7 : 0;
-    if (shift < 0) shift = 0;
-    uint64_t prefix = 0, mask = 0;              // over (key - kmin)
-    uint32_t need = K;
-    uint32_t bucket = M;
-    while (true) {
-        if (tid < 256) hist[tid] = 0;
-        __syncthreads();
-        for (uint32_t i = tid; i < M; i += 1024) {
-            const uint64_t k = src[i] - kmin;
-            if ((k & mask) == prefix) atomicAdd(&hist[(uint32_t)(k >> shift) & 255u], 1u);
-        }
-        __syncthreads();
-        if (tid < 256) {
-            uint32_t above = 0;
-            for (int d = 255; d > (int)tid; --d) above += hist[d];
-            if (above < need && need <= above + hist[tid]) {
-                s_digit = tid;
-                s_need = need - above;
-                s_cnt = hist[tid];
-            }
-        }
-        __syncthreads();
-        prefix |= (uint64_t)s_digit << shift;
-        mask |= 255ull << shift;
-        need = s_need;
-        bucket = s_cnt;
-        __syncthreads();
-        if (shift == 0 || bucket == 1) break;
-        shift = shift >= 8 ? shift - 8 : 0;
-    }
-    // keys are distinct.  If the selected bucket holds one key, that key is the K-th; otherwise all
-    // digits down to bit 0 were fixed and prefix is the full (key - kmin) of the K-th.
-    if (shift != 0) {
-        if (tid == 0) s_min = 0ull;
-        __syncthreads();
-        for (uint32_t i = tid; i < M; i += 1024) {
-            const uint64_t k = src[i] - kmin;
-            if ((k & mask) == prefix) s_min = k;            // exactly one thread writes
-        }
-        __syncthreads();
-        prefix = s_min;
-    }
-    const uint64_t kth = prefix + kmin;          // exactly K keys are >= kth
-    if (thr_only) {
-        if (tid == 0) thr[q] = key_score(kth);
-        return;
-    }
-    if (tid == 0) s_out = 0;
-    __syncthreads();
-    for (uint32_t i = tid; i < M; i += 1024) {
-        const uint64_t k = src[i];
-        if (k >= kth) out[atomicAdd(&s_out, 1u)] = k;
-    }
-    if (tid == 0) {
-        cnt[q] = K;
-        thr[q] = key_score(kth);
-    }
-}
-
-// final: sort the survivors descending in LDS and decode.  P = pow2 >= n, P*8 bytes of LDS.
-__global__ __launch_bounds__(1024) void final_kernel(const uint64_t* __restrict__ cand,
-                                                     const uint32_t* __restrict__ cnt, uint32_t cap,
-                                                     uint32_t K, uint32_t P, uint64_t row_offset,
-                                                     uint64_t* __restrict__ out_rows,
-                                                     float* __restrict__ out_scores,
-                                                     uint32_t* __restrict__ out_count) {
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    uint64_t* s = reinterpret_cast<uint64_t*>(smem_raw);
-    const uint32_t q = blockIdx.x, tid = threadIdx.x;
-    uint32_t n = cnt[q];
-    if (n > K) n = K;
-    const uint64_t* in = cand + (uint64_t)q * cap;
-    for (uint32_t i = tid; i < P; i += 1024) s[i] = i < n ? in[i] : 0ull;
-    __syncthreads();
-    for (uint32_t k = 2; k <= P; k <<= 1) {
-        for (uint32_t j = k >> 1; j > 0; j >>= 1) {
-            for (uint32_t idx = tid; idx < P; idx += 1024) {
-                const uint32_t ixj = idx ^ j;
-                if (ixj > idx) {
-                    const uint64_t x = s[idx], y = s[ixj];
-                    const bool desc = (idx & k) == 0;
-                    if ((x < y) == desc) {
-                        s[idx] = y;
-                        s[ixj] = x;
-                    }
-                }
-            }
-            __syncthreads();
-        }
-    }
-    for (uint32_t i = tid; i < K; i += 1024) {
-        if (i < n) {
-            out_rows[(uint64_t)q * K + i] = row_offset + key_row(s[i]);
-            out_scores[(uint64_t)q * K + i] = key_score(s[i]);
-        } else {
-            out_rows[(uint64_t)q * K + i] = ~0ull;
-            out_scores[(uint64_t)q * K + i] = -__builtin_inff();
-        }
-    }
-    if (tid == 0 && out_count) out_count[q] = n;
-}
-
-// final for K <= 8192: the register-resident bitonic network (bitonic_reg.hpp) on complemented keys
-__global__ __launch_bounds__(1024) void final_kernel_reg(const uint64_t* __restrict__ cand,
-                                                         const uint32_t* __restrict__ cnt, uint32_t cap,
-                                                         uint32_t K, uint64_t row_offset,
-                                                         uint64_t* __restrict__ out_rows,
-                                                         float* __restrict__ out_scores,
-                                                         uint32_t* __restrict__ out_count) {
-    __shared__ BitonicLds lds;
-    const uint32_t q = blockIdx.x, t = threadIdx.x;
-    uint32_t n = cnt[q];
-    if (n > K) n = K;
-    uint32_t P = 512;
-    while (P < K) P <<= 1;
-    const uint64_t* in = cand + (uint64_t)q * cap;
-    uint64_t k[kBitonicE];
-    uint32_t ix[kBitonicE];
-#pragma unroll
-    for (int u = 0; u < kBitonicE; ++u) {
-        const uint32_t i = t * kBitonicE + u;
-        k[u] = (i < n) ? ~in[i] : ~0ull;               // descending = ascending on the complement; pad last
-        ix[u] = 0;
-    }
-    bitonic_sort_reg<false>(k, ix, P, lds, n);
-#pragma unroll
-    for (int u = 0; u < kBitonicE; ++u) {
-        const uint32_t i = t * kBitonicE + u;
-        if (i < K) {
-            const uint64_t key = ~k[u];
-            if (i < n) {
-                out_rows[(uint64_t)q * K + i] = row_offset + key_row(key);
-                out_scores[(uint64_t)q * K + i] = key_score(key);
-            } else {
-                out_rows[(uint64_t)q * K + i] = ~0ull;
-                out_scores[(uint64_t)q * K + i] = -__builtin_inff();
-            }
-        }
-    }
-    if (t == 0 && out_count) out_count[q] = n;
-}
-
-// final for a handful of queries (K <= 8192): counting ranks instead of a sorting network.  One workgroup sorts a
-// query's 8192-slot network on ONE CU in 48 us whatever the chip is doing; with only a few queries in the call the
-// other 250 CUs are idle, so every 64 candidates get a workgroup of their own: it stages the query's n keys in LDS
-// (broadcast reads), wave p counts the keys above each of its 64 within the p-th quarter, the four counts add up
-// to the candidate's rank — its output position, the keys being distinct.  n^2 / 4 compares per wave: ~6 us at 5 000.
-// EPB candidates per workgroup, 256 / EPB threads each: 16 for one or two queries, 64 beyond.
-template <int EPB>
-__global__ __launch_bounds__(256) void final_rank_kernel(const uint64_t* __restrict__ cand, const uint32_t* __restrict__ cnt,
-                                                         uint32_t cap, uint32_t K, uint64_t row_offset,
-                                                         uint64_t* __restrict__ out_rows, float* __restrict__ out_scores,
-                                                         uint32_t* __restrict__ out_count) {
-    constexpr uint32_t PARTS = 256 / EPB;
-    extern __shared__ __attribute__((aligned(16))) uint64_t rk_keys[];       // [n rounded up to 32]
-    __shared__ uint32_t part[PARTS][EPB];
-    const uint32_t q = blockIdx.y, tid = threadIdx.x;
-    uint32_t n = cnt[q];
-    if (n > K) n = K;
-    // positions past the candidates (fewer than K rows in the table)
-    for (uint32_t i = n + blockIdx.x * 256u + tid; i < K; i += gridDim.x * 256u) {
-        out_rows[(uint64_t)q * K + i] = ~0ull;
-        out_scores[(uint64_t)q * K + i] = -__builtin_inff();
-    }
-    if (blockIdx.x == 0 && tid == 0 && out_count) out_count[q] = n;
-    if (blockIdx.x * (uint32_t)EPB >= n) return;
-    const uint64_t* in = cand + (uint64_t)q * cap;
-    const uint32_t n8 = (n + 31u) & ~31u;
-    for (uint32_t i0 = tid; i0 < n8; i0 += 8u * 256u) {                     // eight independent loads per thread in flight
-        uint64_t kv[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const uint32_t i = i0 + (uint32_t)u * 256u;
-            kv[u] = in[i < n ? i : 0u];
-        }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const uint32_t i = i0 + (uint32_t)u * 256u;
-            if (i < n8) rk_keys[i] = i < n ? kv[u] : 0ull;                  // padding: below every real key
-        }
-    }
-    __syncthreads();
-    const uint32_t el = tid % (uint32_t)EPB, p = tid / (uint32_t)EPB;
-    const uint32_t e = blockIdx.x * (uint32_t)EPB + el;
-    const uint64_t mine = e < n ? rk_keys[e] : ~0ull;
-    const uint32_t chunk = n8 / PARTS;                                     // n8 % 32 == 0: even chunks
-    const uint32_t j0 = p * chunk, j1 = j0 + chunk;
-    uint32_t above = 0;
-    // (unrolled: one wave per SIMD here, so a broadcast read's LDS latency is hidden only by the reads behind it)
-#pragma unroll 4
-    for (uint32_t j = j0; j < j1; j += 2) {
-        const ulonglong2 kk = *reinterpret_cast<const ulonglong2*>(&rk_keys[j]);
-        above += (kk.x > mine) ? 1u : 0u;
-        above += (kk.y > mine) ? 1u : 0u;
-    }
-    part[p][el] = above;
-    __syncthreads();
-    if (p == 0 && e < n) {
-        uint32_t r = 0;
-#pragma unroll
-        for (uint32_t i = 0; i < PARTS; ++i) r += part[i][el];
-        out_rows[(uint64_t)q * K + r] = row_offset + key_row(mine);
-        out_scores[(uint64_t)q * K + r] = key_score(mine);
-    }
-}
 
 // after a refined pilot plan: thr = score of the K-th best candidate kept (select_kernel), thr_ref = the raised threshold
 __global__ void refine_verify_kernel(const float* __restrict__ thr, const float* __restrict__ thr_ref,
@@ -1843,22 +1384,8 @@ __global__ void recall_init_kernel(const float* __restrict__ queries, uint32_t n
     if (i == 0) { *overflow = 0; overflow[kRecOvfWord] = 0; }
 }
 
-// squared-Euclidean recall: |x|^2 of every row and |q|^2 of every query as k-ascending fmaf chains (the specification's), and
-// the sign flip of the scores that come out (-d → d; padding -inf → +inf)
-__global__ void row_norm2_kernel(const float* __restrict__ tab, uint64_t rows, uint32_t dim, float* __restrict__ out) {
-    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= rows) return;
-    const float4* x = reinterpret_cast<const float4*>(tab + r * dim);
-    float s = 0.0f;
-    for (uint32_t c = 0; c < dim / 4; ++c) {
-        const float4 v = x[c];
-        s = __fmaf_rn(v.x, v.x, s);
-        s = __fmaf_rn(v.y, v.y, s);
-        s = __fmaf_rn(v.z, v.z, s);
-        s = __fmaf_rn(v.w, v.w, s);
-    }
-    out[r] = s;
-}
+// squared-Euclidean recall: |q|^2 of every query as a k-ascending fmaf chain (the specification's; |x|^2 of every row:
+// recall_table.hip), and the sign flip of the scores that come out (-d → d; padding -inf → +inf)
 __global__ void query_norm2_kernel(const float* __restrict__ qpad, uint32_t dim, float* __restrict__ out) {
     const uint32_t q = threadIdx.x;
     float s = 0.0f;
@@ -1870,95 +1397,7 @@ __global__ void negate_kernel(float* __restrict__ v, uint64_t n) {
     if (i < n) v[i] = 0.0f - v[i];                     // (a zero distance comes out as +0, padding as +inf)
 }
 
-// merge input lists (global rows, scores) → candidate keys.  Padding entries (row = UINT64_MAX: a shard with fewer
-// than per_list rows) are dropped here, so the keys stay distinct (select_kernel's invariant) and cnt[q] is the number
-// of real candidates.  Input layout: [nq][nlists][per_list] (list_major = 0) or [nlists][nq][per_list] (1: what an
-// all-gather of per-shard [nq][per_list] blocks produces).  cnt must be zero on entry.
-// list l of query q starts at rows + l * row_ls + q * row_qs (scores likewise): covers the query-major layout
-// [nq][nlists][per_list], the list-major one an all-gather produces, and packed per-shard (rows | scores) blocks
-__global__ void merge_keys_kernel(const uint64_t* __restrict__ rows, const float* __restrict__ scores, uint32_t nq,
-                                  uint32_t nlists, uint32_t per_list, size_t row_ls, size_t row_qs, size_t sc_ls, size_t sc_qs,
-                                  uint32_t cap, uint64_t* __restrict__ cand, uint32_t* __restrict__ cnt) {
-    const uint32_t q = blockIdx.y;
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t per_q = nlists * per_list;
-    if (i >= per_q) return;
-    const uint32_t l = i / per_list, j = i - l * per_list;
-    const uint64_t r = rows[l * row_ls + q * row_qs + j];
-    if (r == ~0ull) return;
-    cand[(uint64_t)q * cap + atomicAdd(&cnt[q], 1u)] = topk_key(scores[l * sc_ls + q * sc_qs + j], (uint32_t)r);
-}
-
-// ---------------------------------------------------------------------------------------------
-// Threshold predictor.  A query's scores over the table are a projection of the rows: mean mu.q, variance q'Sq, and —
-// 128 terms each — close to Gaussian, so the K-th best of N rows sits z standard deviations above the mean, with z
-// nearly the same for every query of a workload.  mu and S come from a row sample (with the table's statistics); z is
-// not assumed but OBSERVED: every verified batch reports (K-th best − mu.q) / sigma_q of its queries.  Once the
-// observed z is tight, the first thresholds of a batch are mu.q + (mean z − margin) sigma_q: the pilot sample — two
-// small scan launches, a re-scoring and two selects, 0.35 ms that nothing overlaps — is skipped.  Exactness does
-// not depend on any of this: a threshold that turns out too high leaves a query short of K candidates, which the
-// plan check sees, and the batch re-runs on the pilot plan (and the table stays on it for a while).
-// ---------------------------------------------------------------------------------------------
-// second moments of a row sample: workgroup b walks sample rows b, b + G, ...; thread (ty, tx) of a 16 x 16 grid owns
-// the 8 x 8 patch (i = ty + 16a, j = tx + 16b) of sum x_i x_j; 16 rows are staged per barrier pair
-__global__ __launch_bounds__(256) void pred_moments_kernel(const float* __restrict__ tab, uint64_t rows, uint64_t stride,
-                                                           uint64_t n_sample, float* __restrict__ sum1, float* __restrict__ sum2) {
-    __shared__ float xs[16][128 + 4];
-    const uint32_t tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
-    float acc[8][8];
-#pragma unroll
-    for (int a = 0; a < 8; ++a)
-#pragma unroll
-        for (int b = 0; b < 8; ++b) acc[a][b] = 0.0f;
-    float s1 = 0.0f;                                       // thread t < 128: sum of column t
-    for (uint64_t r0 = (uint64_t)blockIdx.x * 16; r0 < n_sample; r0 += (uint64_t)gridDim.x * 16) {
-        __syncthreads();
-        for (uint32_t e = tid; e < 16 * 32; e += 256) {    // 16 rows x 32 quads
-            const uint32_t rr = e >> 5, qd = e & 31;
-            const uint64_t sr = r0 + rr;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (sr < n_sample) {
-                const uint64_t row = sr * stride < rows ? sr * stride : rows - 1;
-                v = *reinterpret_cast<const float4*>(tab + row * 128 + 4 * qd);
-            }
-            *reinterpret_cast<float4*>(&xs[rr][4 * qd]) = v;
-        }
-        __syncthreads();
-#pragma unroll 4
-        for (int rr = 0; rr < 16; ++rr) {
-            float xi[8], xj[8];
-#pragma unroll
-            for (int a = 0; a < 8; ++a) {
-                xi[a] = xs[rr][ty + 16 * a];
-                xj[a] = xs[rr][tx + 16 * a];
-            }
-#pragma unroll
-            for (int a = 0; a < 8; ++a)
-#pragma unroll
-                for (int b = 0; b < 8; ++b) acc[a][b] = __fmaf_rn(xi[a], xj[b], acc[a][b]);
-            if (tid < 128) s1 += xs[rr][tid];
-        }
-    }
-#pragma unroll
-    for (int a = 0; a < 8; ++a)
-#pragma unroll
-        for (int b = 0; b < 8; ++b) atomicAdd(&sum2[(ty + 16 * a) * 128 + tx + 16 * b], acc[a][b]);
-    if (tid < 128) atomicAdd(&sum1[tid], s1);
-}
-// sums → mean and covariance in place; the observation block behind them is cleared
-__global__ void pred_finish_kernel(float* __restrict__ pred, uint64_t n_sample) {
-    const uint32_t i = blockIdx.x, j = threadIdx.x;        // 128 x 128
-    const float inv = 1.0f / (float)n_sample;
-    const float mi = pred[i] * inv, mj = pred[j] * inv;
-    const float c = pred[128 + i * 128 + j] * inv - mi * mj;
-    pred[128 + i * 128 + j] = c;                           // (the raw column sums pred[0..127] are turned into means by the next launch)
-}
-__global__ void pred_means_kernel(float* __restrict__ pred, uint64_t n_sample) {
-    const uint32_t j = threadIdx.x;
-    if (j < 128) pred[j] = pred[j] / (float)n_sample;
-    if (j < 8) reinterpret_cast<uint32_t*>(pred + 128 + 128 * 128)[j] = 0u;          // n, sum z, sum z^2, min z (doubles)
-    if (j == 0) reinterpret_cast<double*>(pred + 128 + 128 * 128)[3] = 1e300;
-}
+// (the threshold predictor's model and what it is for: recall_table.hip, at pred_moments_kernel)
 // per query: mean mu.q and sigma sqrt(q'Sq) of its scores (one workgroup of 128 threads per query)
 __global__ __launch_bounds__(128) void pred_query_kernel(const float* __restrict__ qpad, const float* __restrict__ pred,
                                                          float* __restrict__ ms, float* __restrict__ thr, float z_lo) {
@@ -2040,22 +1479,6 @@ __global__ void pred_update_kernel(const float* __restrict__ thr, const float* _
     }
 }
 
-int launch_select(pg_ctx* ctx, uint32_t nq, const uint64_t* in, uint64_t* out, uint32_t* cnt, float* thr,
-                         uint32_t cap, uint32_t k, int thr_only, uint32_t* cnt_seen) {
-    constexpr size_t lds = (size_t)kSelLdsKeys * 8;
-    int rc_attr;
-    if ((rc_attr = ensure_dyn_lds(ctx, (const void*)select_kernel, lds))) return rc_attr;
-    select_kernel<<<nq, 1024, lds, ctx->stream>>>(in, out, cnt, thr, cap, k, thr_only, cnt_seen);
-    PG_HIP(hipGetLastError());
-    return PG_OK;
-}
-
-static uint32_t next_pow2(uint32_t x) {
-    uint32_t p = 1;
-    while (p < x) p <<= 1;
-    return p;
-}
-
 template <int DIM, int NQB = 1, bool L2 = false>
 static int launch_scan(pg_ctx* ctx, const ScanArgs& a) {
     int rc_attr;
@@ -2095,7 +1518,6 @@ static int dispatch_scan(pg_ctx* ctx, uint32_t dim, const ScanArgs& a) {
 
 constexpr uint32_t kFirstChunkRows = 32768;
 constexpr uint32_t kRescoreBlocksPerQuery = 16;   // x 256 suspects per block per stride step
-constexpr uint32_t kCandSlack = 1u << 19;      // candidate capacity beyond K per query
 
 int recall_scratch(pg_ctx* ctx, uint32_t dim, uint32_t k, RecallScratch* rs) {
     const uint32_t cap = k + kCandSlack;
@@ -2129,171 +1551,6 @@ int recall_scratch(pg_ctx* ctx, uint32_t dim, uint32_t k, RecallScratch* rs) {
             rs->susp2 = c.take<uint32_t>(lists);
         }))) return rc;
     rs->cap = cap;
-    return PG_OK;
-}
-
-// final as a split sort (split_sort.hpp): descending by candidate key = ascending on the complement, keys distinct
-struct FinalSortPolicy {
-    static constexpr bool kWithIdx = false;
-    const uint64_t* cand;
-    const uint32_t* cnt;
-    uint32_t cap, K;
-    uint64_t row_offset;
-    uint64_t* out_rows;
-    float* out_scores;
-    uint32_t* out_count;
-    __device__ uint32_t count(uint32_t q) const { const uint32_t n = cnt[q]; return n < K ? n : K; }
-    __device__ uint64_t key(uint32_t q, uint32_t i) const { return ~cand[(uint64_t)q * cap + i]; }
-    __device__ void store(uint32_t q, uint32_t rank, uint64_t k, uint32_t) const {
-        out_rows[(uint64_t)q * K + rank] = row_offset + key_row(~k);
-        out_scores[(uint64_t)q * K + rank] = key_score(~k);
-    }
-    // positions past the candidates (fewer than K rows in the table); t = this thread among nt of the list's workgroups
-    __device__ void tail(uint32_t q, uint32_t n, uint32_t t, uint32_t nt) const {
-        for (uint32_t i = n + t; i < K; i += nt) {
-            out_rows[(uint64_t)q * K + i] = ~0ull;
-            out_scores[(uint64_t)q * K + i] = -__builtin_inff();
-        }
-        if (t == 0 && out_count) out_count[q] = n;
-    }
-};
-
-int final_launch(pg_ctx* ctx, const uint64_t* cand, const uint32_t* cnt, uint32_t cap,
-                        uint32_t nq, uint32_t k, uint64_t row_offset, uint64_t* d_out_rows,
-                        float* d_out_scores, uint32_t* d_out_count) {
-    if (!rank_sort_applies(ctx, nq, k, 1.5) && split_sort_applies(ctx, nq, k))
-        return split_sort_launch(ctx, FinalSortPolicy{cand, cnt, cap, k, row_offset, d_out_rows, d_out_scores, d_out_count}, nq, k);
-    if (rank_sort_applies(ctx, nq, k, 1.5)) {
-        const size_t lds = (size_t)((k + 31u) & ~31u) * 8;
-        int rc_attr;
-        if (nq <= 2) {
-            if ((rc_attr = ensure_dyn_lds(ctx, (const void*)final_rank_kernel<16>, lds))) return rc_attr;
-            final_rank_kernel<16><<<dim3((k + 15) / 16, nq), 256, lds, ctx->stream>>>(cand, cnt, cap, k, row_offset, d_out_rows,
-                                                                                      d_out_scores, d_out_count);
-        } else {
-            if ((rc_attr = ensure_dyn_lds(ctx, (const void*)final_rank_kernel<64>, lds))) return rc_attr;
-            final_rank_kernel<64><<<dim3((k + 63) / 64, nq), 256, lds, ctx->stream>>>(cand, cnt, cap, k, row_offset, d_out_rows,
-                                                                                      d_out_scores, d_out_count);
-        }
-        PG_HIP(hipGetLastError());
-        return PG_OK;
-    }
-    if (k <= kBitonicMax) {
-        final_kernel_reg<<<nq, 1024, 0, ctx->stream>>>(cand, cnt, cap, k, row_offset, d_out_rows, d_out_scores,
-                                                       d_out_count);
-        PG_HIP(hipGetLastError());
-        return PG_OK;
-    }
-    const uint32_t P = next_pow2(k < 2 ? 2 : k);
-    const size_t lds = (size_t)P * 8;
-    int rc_attr;
-    if ((rc_attr = ensure_dyn_lds(ctx, (const void*)final_kernel, lds))) return rc_attr;
-    final_kernel<<<nq, 1024, lds, ctx->stream>>>(cand, cnt, cap, k, P, row_offset, d_out_rows,
-                                                 d_out_scores, d_out_count);
-    PG_HIP(hipGetLastError());
-    return PG_OK;
-}
-
-// statistics + shadow of a table (lazily, cached until the next upload / fill): int8 for dim 128 (two passes:
-// statistics, then quantisation with the table's scale), bf16 for dim 64.
-// Tables the screen cannot serve (other dims, no memory for the shadow) keep stats_valid = false.
-static std::mutex g_stats_build_mu;   // a table is shared by the contexts of a device (a coalescer's sibling): one of them builds
-int ensure_table_stats(pg_ctx* ctx, const pg_table* tc) {
-    pg_table* t = const_cast<pg_table*>(tc);          // lazily computed cache
-    std::lock_guard<std::mutex> build_guard(g_stats_build_mu);
-    if (t->stats_valid || t->shadow_failed) return PG_OK;
-    t->i4_ok = t->i4_failed = false;                  // the 4-bit shadow (recall_i4.hip) follows the rows too
-    t->i4m_pairs = 0.0f;
-    t->rec_scale = 0;
-    t->r2_ok = t->r2_failed = false;                  // ... and the residual shadow (recall_r2.hip)
-    t->wide_susp = 0.0f;
-    t->pred_model = false;                            // ... and the threshold model
-    t->prefix_failures = 0;
-    if (t->dim != 64 && t->dim != 128) { t->shadow_failed = true; return PG_OK; }
-    bool i8 = t->dim == 128;
-    void* p;
-    int rc;
-    if ((rc = scratch_reserve(ctx, kSlotStatus, 4096, &p))) return rc;
-    float* d_max = (float*)p + 300;                   // [300] max norm^2, [301] non-finite flag, [302] max |x|, [303] max residual^2, [304] sum of norm^2
-    uint32_t* d_bad = (uint32_t*)p + 301;
-    PG_HIP(hipMemsetAsync(d_max, 0, 20, ctx->stream));
-    const uint32_t grid = (uint32_t)ctx->num_cus * 16;
-    if (i8) {
-        // statistics first: they decide between the two shadows
-        table_stats_kernel<128><<<grid, 256, 0, ctx->stream>>>(t->d, t->rows, d_max, d_bad, d_max + 2, d_max + 4);
-        PG_HIP(hipGetLastError());
-        PG_HIP(hipMemcpyAsync(ctx->h_status + 300, d_max, 20, hipMemcpyDeviceToHost, ctx->stream));
-        PG_HIP(hipStreamSynchronize(ctx->stream));
-        float mx, amx, sumsq;
-        memcpy(&mx, ctx->h_status + 300, 4);
-        memcpy(&amx, ctx->h_status + 302, 4);
-        memcpy(&sumsq, ctx->h_status + 304, 4);
-        t->all_finite = ctx->h_status[301] == 0;
-        t->max_norm = sqrtf(mx) * 1.0001f;
-        t->s8 = fmaxf(amx / 127.0f, 1e-30f);
-        t->resid8 = 0.0f;
-        // One scale for the table only works when the largest element is not far above the typical row: the int8
-        // margin is ~ s8 sqrt(dim / 12) per unit of ||q|| for EVERY row, the bf16 margin 0.008 x the row's own norm.
-        // Heavy tails or outliers (a Student-t table: int8 margin 130 x the bf16 one, every row a suspect, 560 ms per
-        // recall instead of 2.4) go to the bf16 shadow with per-block norms.
-        const float rms_norm = sqrtf(sumsq / (float)(t->rows ? t->rows : 1));
-        if (t->all_finite && t->s8 * sqrtf((float)t->dim / 12.0f) > 4.0f * kScreenEps * rms_norm) i8 = false;
-    }
-    if (i8) {
-        if (!t->d8) {
-            const size_t bytes = (t->rows + 64) * (size_t)t->dim;
-            if (hipMalloc((void**)&t->d8, bytes) != hipSuccess) {
-                (void)hipGetLastError();
-                t->d8 = nullptr;
-                t->shadow_failed = true;              // stay on the exact scan
-                return PG_OK;
-            }
-            PG_HIP(hipMemsetAsync(t->d8 + t->rows * (size_t)t->dim, 0, 64 * (size_t)t->dim, ctx->stream));
-        }
-        if (t->all_finite) {
-            table_quant8_kernel<128><<<grid, 256, 0, ctx->stream>>>(t->d, t->rows, t->s8, t->d8, d_max + 3);
-            PG_HIP(hipGetLastError());
-            PG_HIP(hipMemcpyAsync(ctx->h_status + 303, d_max + 3, 4, hipMemcpyDeviceToHost, ctx->stream));
-            PG_HIP(hipStreamSynchronize(ctx->stream));
-            float r2;
-            memcpy(&r2, ctx->h_status + 303, 4);
-            // (the residuals were accumulated in fp32: a relative 1e-3 and an absolute 1e-6 N cover that)
-            t->resid8 = sqrtf(r2) * 1.001f + 1e-6f * t->max_norm;
-        }
-        t->shadow_is_i8 = true;
-        t->stats_valid = true;
-        return PG_OK;
-    }
-    const size_t n_blk = (size_t)((t->rows + kPieceRows - 1) / kPieceRows) + 2;
-    if (!t->d16) {
-        const size_t bytes = (t->rows + 64) * (size_t)t->dim * 2;
-        if (hipMalloc((void**)&t->d16, bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            t->d16 = nullptr;
-            t->shadow_failed = true;                  // stay on the exact scan
-            return PG_OK;
-        }
-        PG_HIP(hipMemsetAsync(t->d16 + t->rows * (size_t)t->dim, 0, 64 * (size_t)t->dim * 2, ctx->stream));
-    }
-    if (!t->dnorm2 && hipMalloc((void**)&t->dnorm2, n_blk * sizeof(float)) != hipSuccess) {
-        (void)hipGetLastError();
-        t->dnorm2 = nullptr;
-        t->shadow_failed = true;
-        return PG_OK;
-    }
-    PG_HIP(hipMemsetAsync(t->dnorm2, 0, n_blk * sizeof(float), ctx->stream));
-    PG_HIP(hipMemsetAsync(d_max, 0, 8, ctx->stream));
-    if (t->dim == 64) table_shadow_kernel<64><<<grid, 256, 0, ctx->stream>>>(t->d, t->rows, t->d16, d_max, d_bad, t->dnorm2);
-    else table_shadow_kernel<128><<<grid, 256, 0, ctx->stream>>>(t->d, t->rows, t->d16, d_max, d_bad, t->dnorm2);
-    PG_HIP(hipGetLastError());
-    PG_HIP(hipMemcpyAsync(ctx->h_status + 300, d_max, 8, hipMemcpyDeviceToHost, ctx->stream));
-    PG_HIP(hipStreamSynchronize(ctx->stream));
-    float mx;
-    memcpy(&mx, ctx->h_status + 300, 4);
-    t->all_finite = ctx->h_status[301] == 0;
-    t->max_norm = sqrtf(mx) * 1.0001f;
-    t->shadow_is_i8 = false;
-    t->stats_valid = true;
     return PG_OK;
 }
 
@@ -2334,33 +1591,6 @@ __global__ void status_pack_kernel(const uint32_t* __restrict__ overflow, uint32
         out[kI4mStatAt + 3] = s[1][0] + s[1][1] + s[1][2] + s[1][3];
         out[kI4mStatAt + 4] = s[2][0] + s[2][1] + s[2][2] + s[2][3];
     }
-}
-
-// the threshold model of a table (dim 128): mean and covariance of a row sample, built once per generation of the rows
-static int ensure_pred_model(pg_ctx* ctx, const pg_table* tc) {
-    pg_table* t = const_cast<pg_table*>(tc);
-    std::lock_guard<std::mutex> build_guard(g_stats_build_mu);
-    if (t->pred_model) return PG_OK;
-    const size_t bytes = (size_t)(128 + 128 * 128) * 4 + 5 * 8;   // mean | covariance (→ factor) | n, sum, sum2, min, total
-    if (!t->d_pred && hipMalloc((void**)&t->d_pred, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        t->d_pred = nullptr;
-        return PG_OK;                                 // no model: the pilot plan serves
-    }
-    PG_HIP(hipMemsetAsync(t->d_pred, 0, bytes, ctx->stream));
-    const uint64_t n_sample = t->rows < (1u << 20) ? t->rows : (1u << 20);
-    const uint64_t stride = t->rows / n_sample;
-    pred_moments_kernel<<<(uint32_t)ctx->num_cus, 256, 0, ctx->stream>>>(t->d, t->rows, stride, n_sample, t->d_pred, t->d_pred + 128);
-    pred_finish_kernel<<<128, 128, 0, ctx->stream>>>(t->d_pred, n_sample);
-    pred_means_kernel<<<1, 128, 0, ctx->stream>>>(t->d_pred, n_sample);
-    PG_HIP(hipGetLastError());
-    PG_HIP(hipStreamSynchronize(ctx->stream));        // other contexts of the device use the model from their own streams
-    t->pred_model = true;
-    t->pred_k = 0;
-    t->pred_n = t->pred_sum = t->pred_sum2 = t->pred_total = 0.0;
-    t->pred_min = 1e300;
-    t->pred_backoff = 0;
-    return PG_OK;
 }
 
 template <int DIM, int NQB, int WAVES, bool I8 = false, int QH = 1, int L2 = 0>
@@ -2429,218 +1659,6 @@ enum RecallPlan { kPilot = 0, kGrow = 1, kSafe = 2, kPredict = 3 };
 
 static inline uint64_t rs_cap_bound(uint32_t k) { return (uint64_t)k + kCandSlack; }
 
-// rows that pass a recall's filter (one pass over the column: 0.4 GB per 100 M rows)
-__global__ void filter_count_kernel(RowFilter f, uint64_t rows, unsigned long long* __restrict__ out) {
-    unsigned long long n = 0;
-    for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += (uint64_t)gridDim.x * blockDim.x)
-        n += row_filter_pass(f, (uint32_t)r) ? 1u : 0u;
-    for (int off = 32; off > 0; off >>= 1) n += __shfl_xor(n, off, 64);
-    if ((threadIdx.x & 63) == 0 && n) atomicAdd(out, n);
-}
-
-// ---- selective filters: the admitted rows, in row order (stable compaction), gathered into a compact table ----
-constexpr uint32_t kCompactBlockRows = 1024;
-__device__ __forceinline__ bool filter_cmp(int op, long long v, long long val) {
-    switch (op) {
-        case 0: return v > val;
-        case 1: return v >= val;
-        case 2: return v < val;
-        case 3: return v <= val;
-        case 4: return v == val;
-        default: return v != val;
-    }
-}
-// bit i: row r0 + i passes (r0 a multiple of 4: one 16-B load of an int32 column, two of an int64 one, four bits of a bitmap)
-__device__ __forceinline__ uint32_t row_filter_mask4(const RowFilter& f, uint64_t r0, uint64_t rows) {
-    uint32_t m = 0;
-    if (f.dtype == kFilterBits) return (reinterpret_cast<const uint32_t*>(f.col)[r0 >> 5] >> (uint32_t)(r0 & 31u)) & 0xFu;   // (zero bits beyond the rows)
-    if (r0 + 4 <= rows) {
-        if (f.dtype == PG_F_I64) {
-            const longlong2 a = reinterpret_cast<const longlong2*>(reinterpret_cast<const long long*>(f.col) + r0)[0];
-            const longlong2 b = reinterpret_cast<const longlong2*>(reinterpret_cast<const long long*>(f.col) + r0)[1];
-            m = (filter_cmp(f.op, a.x, f.val) ? 1u : 0u) | (filter_cmp(f.op, a.y, f.val) ? 2u : 0u) | (filter_cmp(f.op, b.x, f.val) ? 4u : 0u) |
-                (filter_cmp(f.op, b.y, f.val) ? 8u : 0u);
-        } else {
-            const int4 a = *reinterpret_cast<const int4*>(reinterpret_cast<const int32_t*>(f.col) + r0);
-            m = (filter_cmp(f.op, a.x, f.val) ? 1u : 0u) | (filter_cmp(f.op, a.y, f.val) ? 2u : 0u) | (filter_cmp(f.op, a.z, f.val) ? 4u : 0u) |
-                (filter_cmp(f.op, a.w, f.val) ? 8u : 0u);
-        }
-    } else {
-        for (uint32_t i = 0; i < 4 && r0 + i < rows; ++i) m |= row_filter_pass(f, (uint32_t)(r0 + i)) ? 1u << i : 0u;
-    }
-    return m;
-}
-__global__ __launch_bounds__(256) void filter_block_count_kernel(RowFilter f, uint64_t rows, uint32_t* __restrict__ block_n) {
-    __shared__ uint32_t ws[4];
-    const uint64_t r0 = (uint64_t)blockIdx.x * kCompactBlockRows + threadIdx.x * 4;
-    uint32_t n = r0 < rows ? (uint32_t)__popc(row_filter_mask4(f, r0, rows)) : 0u;
-    for (int off = 32; off > 0; off >>= 1) n += __shfl_xor(n, off, 64);
-    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = n;
-    __syncthreads();
-    if (threadIdx.x == 0) block_n[blockIdx.x] = ws[0] + ws[1] + ws[2] + ws[3];
-}
-// The block counts' exclusive scan in two parallel levels: every group of 1024 counts is scanned in place by a workgroup of its
-// own (its total → group_n[g]); one small workgroup then scans the <= 4096 group totals (grand total → group_n[ngroups]).  A
-// block's offset is block_n[b] + group_n[b / 1024].
-__device__ __forceinline__ uint32_t wg1024_exclusive_scan(uint32_t v, uint32_t* wsum, uint32_t* total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    uint32_t incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t up = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += up;
-    }
-    if (lane == 63) wsum[w] = incl;
-    __syncthreads();
-    uint32_t excl = incl - v, all = 0;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-        if (j < w) excl += wsum[j];
-        all += wsum[j];
-    }
-    *total = all;
-    return excl;
-}
-__global__ __launch_bounds__(1024) void filter_group_scan_kernel(uint32_t* __restrict__ block_n, uint32_t n, uint32_t* __restrict__ group_n) {
-    __shared__ uint32_t wsum[16];
-    const uint32_t i = blockIdx.x * 1024 + threadIdx.x;
-    const uint32_t v = i < n ? block_n[i] : 0u;
-    uint32_t total;
-    const uint32_t excl = wg1024_exclusive_scan(v, wsum, &total);
-    if (i < n) block_n[i] = excl;
-    if (threadIdx.x == 0) group_n[blockIdx.x] = total;
-}
-__global__ __launch_bounds__(1024) void filter_total_scan_kernel(uint32_t* __restrict__ group_n, uint32_t ngroups) {
-    __shared__ uint32_t wsum[16];
-    uint32_t v[4], s = 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const uint32_t i = threadIdx.x * 4 + j;
-        v[j] = i < ngroups ? group_n[i] : 0u;
-        s += v[j];
-    }
-    uint32_t total;
-    uint32_t acc = wg1024_exclusive_scan(s, wsum, &total);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const uint32_t i = threadIdx.x * 4 + j;
-        if (i < ngroups) group_n[i] = acc;
-        acc += v[j];
-    }
-    if (threadIdx.x == 0) group_n[ngroups] = total;
-}
-// ids[block offset + rank inside the block] = row, ranks in row order: a thread takes 4 consecutive rows, a wave 256
-__global__ __launch_bounds__(256) void filter_scatter_kernel(RowFilter f, uint64_t rows, const uint32_t* __restrict__ block_off,
-                                                             const uint32_t* __restrict__ group_off, uint32_t* __restrict__ ids) {
-    __shared__ uint32_t wn[4];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const uint64_t r0 = (uint64_t)blockIdx.x * kCompactBlockRows + threadIdx.x * 4;
-    const uint32_t m = r0 < rows ? row_filter_mask4(f, r0, rows) : 0u;
-    const uint32_t c = (uint32_t)__popc(m);
-    uint32_t incl = c;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t up = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += up;
-    }
-    if (lane == 63) wn[w] = incl;
-    __syncthreads();
-    uint32_t pos = block_off[blockIdx.x] + group_off[blockIdx.x >> 10] + incl - c;
-    for (int j = 0; j < w; ++j) pos += wn[j];
-#pragma unroll
-    for (uint32_t i = 0; i < 4; ++i)
-        if (m & (1u << i)) ids[pos++] = (uint32_t)(r0 + i);
-}
-// compact[i][:] = tab[ids[i]][:] (a wave per row-quad: 16 B per lane)
-__global__ void compact_gather_kernel(const float* __restrict__ tab, const uint32_t* __restrict__ ids, uint32_t n, uint32_t dim,
-                                      float* __restrict__ out) {
-    const uint32_t q4 = dim / 4;
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (uint64_t)n * q4) return;
-    const uint32_t r = (uint32_t)(i / q4), c = (uint32_t)(i % q4);
-    reinterpret_cast<float4*>(out)[i] = reinterpret_cast<const float4*>(tab + (size_t)ids[r] * dim)[c];
-}
-__global__ void compact_gather_nx_kernel(const float* __restrict__ nx, const uint32_t* __restrict__ ids, uint32_t n, float* __restrict__ out) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n + 64) out[i] = i < n ? nx[ids[i]] : 0.0f;
-}
-__global__ void recall_pad_kernel(uint64_t* __restrict__ rows, float* __restrict__ scores, size_t n, bool l2) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) {
-        rows[i] = ~0ull;
-        scores[i] = l2 ? __builtin_inff() : -__builtin_inff();
-    }
-}
-// local rows of the compact table → the table's global row ids (padding stays UINT64_MAX)
-__global__ void compact_map_rows_kernel(uint64_t* __restrict__ rows, uint64_t n, const uint32_t* __restrict__ ids, uint64_t row_offset,
-                                        uint64_t n_ids) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n && rows[i] < n_ids) rows[i] = row_offset + ids[rows[i]];      // (padding, UINT64_MAX, stays)
-}
-
-// Count the rows `f` admits per 1024-row block (one pass over the column) and scan the counts — the scan is also the compaction's
-// map (filter_scatter_kernel); buffers in kSlotFilterCount.  Synchronises the stream (the count comes back to the host).
-int filter_count_locked(pg_ctx* ctx, const RowFilter& f, uint64_t rows, uint32_t** d_blk_out, uint32_t** d_grp_out, uint32_t* cblocks_out,
-                        uint32_t* admitted_out) {
-    const uint32_t cblocks = (uint32_t)((rows + kCompactBlockRows - 1) / kCompactBlockRows);
-    const uint32_t cgroups = (cblocks + 1023) / 1024;
-    if (cgroups > 4096) {
-        set_error("filtered recall: table of %llu rows too large", (unsigned long long)rows);
-        return PG_ERR_UNSUPPORTED;
-    }
-    uint32_t *d_blk, *d_grp; int rc;
-    if ((rc = scratch_carve(ctx, kSlotFilterCount, [&](Carve& c) {
-            d_blk = c.take<uint32_t>(cblocks);
-            d_grp = c.take<uint32_t>((size_t)cgroups + 2);      // the groups' scan, the total behind it
-        }))) return rc;
-    uint32_t admitted = 0;
-    if (cblocks) {
-        filter_block_count_kernel<<<cblocks, 256, 0, ctx->stream>>>(f, rows, d_blk);
-        filter_group_scan_kernel<<<cgroups, 1024, 0, ctx->stream>>>(d_blk, cblocks, d_grp);
-        filter_total_scan_kernel<<<1, 1024, 0, ctx->stream>>>(d_grp, cgroups);
-        PG_HIP(hipGetLastError());
-        PG_HIP(hipMemcpyAsync(&admitted, d_grp + cgroups, 4, hipMemcpyDeviceToHost, ctx->stream));
-        PG_HIP(hipStreamSynchronize(ctx->stream));
-    }
-    *d_blk_out = d_blk;
-    *d_grp_out = d_grp;
-    *cblocks_out = cblocks;
-    *admitted_out = admitted;
-    return PG_OK;
-}
-
-// |x|^2 of every row, for the squared-Euclidean recall (lazily, cached until the next upload / fill; shared by the contexts
-// of a device like the shadows)
-int ensure_table_nx(pg_ctx* ctx, const pg_table* tc) {
-    pg_table* t = const_cast<pg_table*>(tc);
-    std::lock_guard<std::mutex> build_guard(g_stats_build_mu);
-    if (t->nx_valid) return PG_OK;
-    const uint32_t nblocks = (uint32_t)((t->rows + kPieceRows - 1) / kPieceRows);
-    if (!t->d_nx) PG_HIP(hipMalloc((void**)&t->d_nx, (t->rows + 64) * sizeof(float)));
-    if (!t->d_nxmin) PG_HIP(hipMalloc((void**)&t->d_nxmin, ((size_t)nblocks + 64) * sizeof(float)));
-    PG_HIP(hipMemsetAsync(t->d_nx + t->rows, 0, 64 * sizeof(float), ctx->stream));
-    PG_HIP(hipMemsetAsync(t->d_nxmin + nblocks, 0, 64 * sizeof(float), ctx->stream));
-    row_norm2_kernel<<<(uint32_t)((t->rows + 255) / 256), 256, 0, ctx->stream>>>(t->d, t->rows, t->dim, t->d_nx);
-    void* p;
-    int rc;
-    if ((rc = scratch_reserve(ctx, kSlotStatus, 4096, &p))) return rc;
-    double* d_st = reinterpret_cast<double*>((char*)p + 2048);
-    PG_HIP(hipMemsetAsync(d_st, 0, 16, ctx->stream));
-    block_nxmin_kernel<<<(nblocks + 255) / 256, 256, 0, ctx->stream>>>(t->d_nx, t->rows, t->d_nxmin, nblocks, d_st);
-    PG_HIP(hipGetLastError());
-    double h_st[2] = {0.0, 0.0};
-    PG_HIP(hipMemcpyAsync(h_st, d_st, 16, hipMemcpyDeviceToHost, ctx->stream));
-    PG_HIP(hipStreamSynchronize(ctx->stream));
-    // What the per-block cutoff gives away: a row's cutoff sits (|x|^2 - min of its block) / 2 below its own, in inner-product
-    // units whose spread over the table is about |x| |q| / sqrt(dim) ~ mean|x|^2 / sqrt(dim) for queries like the rows.  Normalised
-    // rows: 0.  N(0, 1) rows: 1.5 spreads — then nearly every block holds suspects and the exact scan is the faster pass.
-    const double mean_nx = t->rows ? h_st[1] / (double)t->rows : 0.0;
-    t->l2_slack = mean_nx > 0.0 ? (float)((h_st[0] / (double)t->rows) * 0.5 / (mean_nx / sqrt((double)t->dim))) : 0.0f;
-    if (ctx->knobs.debug_scan) fprintf(stderr, "[pg] squared-Euclidean recall: per-block cutoff slack %.3f score spreads\n", t->l2_slack);
-    t->nx_valid = true;
-    return PG_OK;
-}
-
 int recall_job_prepare(RecallJob* j) {
     pg_ctx* ctx = j->ctx;
     const pg_table* t = j->t;
@@ -2664,8 +1682,7 @@ int recall_job_prepare(RecallJob* j) {
         if ((rc = scratch_reserve(ctx, kSlotStatus, 4096, &p))) return rc;
         unsigned long long* d_n = reinterpret_cast<unsigned long long*>((char*)p + 3072);
         PG_HIP(hipMemsetAsync(d_n, 0, 8, ctx->stream));
-        filter_count_kernel<<<(uint32_t)ctx->num_cus * 8, 256, 0, ctx->stream>>>(j->filter, t->rows, d_n);
-        PG_HIP(hipGetLastError());
+        if ((rc = filter_count_launch(ctx, j->filter, t->rows, d_n))) return rc;
         unsigned long long h_n = 0;
         PG_HIP(hipMemcpyAsync(&h_n, d_n, 8, hipMemcpyDeviceToHost, ctx->stream));
         PG_HIP(hipStreamSynchronize(ctx->stream));
@@ -3183,8 +2200,7 @@ int recall_job_enqueue(RecallJob* j) {
         return rc;
     if (t->d_row_map) {                                // a filtered view answers with its source's row ids
         const uint64_t n = (uint64_t)j->nq * j->k;
-        compact_map_rows_kernel<<<(uint32_t)((n + 255) / 256), 256, 0, ctx->stream>>>(j->d_out_rows, n, t->d_row_map, t->map_offset, t->rows);
-        PG_HIP(hipGetLastError());
+        if ((rc = compact_map_rows_launch(ctx, j->d_out_rows, n, t->d_row_map, t->map_offset, t->rows))) return rc;
     }
     if (j->l2) {                                       // the lists were ranked by -d: the distances go out
         const uint64_t n = (uint64_t)j->nq * j->k;
@@ -3407,223 +2423,6 @@ int recall_patch_failed_locked(RecallJob* j, uint32_t* counts) {
     return PG_OK;
 }
 
-// the whole recall for one batch of queries, verified before it returns; all pointers are device pointers
-int recall_dev_locked(pg_ctx* ctx, const pg_table* t, const float* d_queries, uint32_t nq,
-                      uint32_t k, uint64_t* d_out_rows, float* d_out_scores,
-                      uint32_t* out_count, uint32_t* d_out_count, const RecallOpts& o) {
-    RecallJob j;
-    j.exact_only = o.exact_only;
-    j.no_index = o.no_index;
-    j.skip_pilot = o.skip_pilot;
-    j.l2 = o.l2;
-    if (o.filter) j.filter = *o.filter;
-    j.ctx = ctx;
-    j.t = t;
-    j.d_queries = d_queries;
-    j.nq = nq;
-    j.k = k;
-    j.d_out_rows = d_out_rows;
-    j.d_out_scores = d_out_scores;
-    j.d_out_count = d_out_count;
-    j.h_status = ctx->h_status;
-    j.events = &ctx->ev_pool;
-    int rc;
-    if ((rc = recall_job_prepare(&j))) return rc;
-    uint32_t counts[kMaxQueries];
-    for (;;) {
-        if ((rc = recall_job_enqueue(&j))) return rc;
-        PG_HIP(hipStreamSynchronize(ctx->stream));
-        bool ok = false;
-        if ((rc = recall_job_check(&j, &ok))) return rc;
-        for (uint32_t q = 0; q < nq; ++q) counts[q] = ctx->h_status[1 + q];
-        if (ok) break;
-        if (!j.failed.empty() && j.failed.size() <= kMaxPatchQueries && nq > 1) {
-            // the pilot's threshold was too high for a few queries only: re-run those, not the batch
-            // (the nested calls reuse ctx->h_status: the counts are kept on the stack)
-            if ((rc = recall_patch_failed_locked(&j, counts))) return rc;
-            break;
-        }
-    }
-    if (out_count)
-        for (uint32_t q = 0; q < nq; ++q) out_count[q] = counts[q];
-    recall_job_finish(&j);
-    return PG_OK;
-}
-
-int recall_batches_locked(pg_ctx* ctx, const pg_table* t, const float* d_queries, uint32_t nq, uint32_t k, uint64_t* d_out_rows,
-                          float* d_out_scores, uint32_t* out_count, const RecallOpts& o) {
-    const uint32_t step = o.l2 ? 128u : (uint32_t)kMaxQueries;
-    for (uint32_t q0 = 0; q0 < nq; q0 += step) {
-        const uint32_t n = nq - q0 < step ? nq - q0 : step;
-        const int rc = recall_dev_locked(ctx, t, d_queries + (size_t)q0 * t->dim, n, k, d_out_rows + (size_t)q0 * k,
-                                         d_out_scores + (size_t)q0 * k, out_count ? out_count + q0 : nullptr, nullptr, o);
-        if (rc) return rc;
-    }
-    return PG_OK;
-}
-
-// pg_recall_topk[_l2][_dev]: host, the queries and outputs are host memory (staged through kSlotStaging)
-int recall_entry(const char* who, pg_ctx* ctx, const pg_table* t, const float* q, uint32_t nq, uint32_t k, uint64_t* rows, float* sc,
-                 uint32_t* out_count, bool l2, bool host) {
-    int rc;
-    if ((rc = recall_check(who, ctx, t, q, rows, sc, nq, k, l2))) return rc;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    TableRead tr(t->rw);
-    RecallOpts o;
-    o.l2 = l2;
-    auto run = [&](const float* d_q, uint64_t* d_rows, float* d_sc) {
-        return recall_batches_locked(ctx, t, d_q, nq, k, d_rows, d_sc, out_count, o);
-    };
-    return host ? recall_staged(ctx, t->dim, q, nq, k, rows, sc, run) : run(q, rows, sc);
-}
-
-// ---- recalls with per-request exclusion lists (the kernel: exclude.hip) ----------------------------------------
-// The offsets of nq lists (`extra` more ids join every list: the request's own trigger row): monotone, at most kMaxExclude ids
-// each, k + the longest within the recalls' 16384.
-int exclude_lists_check(const char* who, const uint32_t* off, uint32_t nq, uint32_t k, uint32_t extra, uint32_t* nmax_out) {
-    uint32_t nmax = extra;
-    for (uint32_t q = 0; off && q < nq; ++q) {
-        PG_REQUIRE(off[q + 1] >= off[q], "%s: excl_offsets[%u] = %u is below excl_offsets[%u] = %u", who, q + 1, off[q + 1], q, off[q]);
-        if (off[q + 1] - off[q] > kMaxExclude) {
-            set_error("%s: request %u excludes %u ids (at most %u per request)", who, q, off[q + 1] - off[q], kMaxExclude);
-            return PG_ERR_UNSUPPORTED;
-        }
-        nmax = std::max(nmax, off[q + 1] - off[q] + extra);
-    }
-    if (nmax > kMaxExclude) {
-        set_error("%s: a list of %u ids with the trigger row (at most %u per request)", who, nmax, kMaxExclude);
-        return PG_ERR_UNSUPPORTED;
-    }
-    if ((uint64_t)k + nmax > 16384) {
-        set_error("%s: k=%u plus the longest exclusion list of %u ids exceeds the recalls' depth of 16384", who, k, nmax);
-        return PG_ERR_UNSUPPORTED;
-    }
-    *nmax_out = nmax;
-    return PG_OK;
-}
-
-// One recall of nq device queries at depth k + nmax through `inner` — the plain call's own search — into kSlotRecallExclude, then
-// the compaction into d_rows / d_sc [nq][k].  excl: the lists' ids, host (staged here, off rebased) or device (indexed by off
-// as given); off: host [nq + 1].  nmax = 0: `inner` at k straight into the outputs.  Caller holds ctx->mu and the table's
-// shared lock; ends synchronised (out_count: host [nq] or NULL).
-template <class Inner>
-int recall_exclude_locked(pg_ctx* ctx, uint32_t nq, uint32_t k, uint32_t nmax, bool l2, const uint64_t* excl, bool excl_on_host,
-                          const uint32_t* off, uint64_t* d_rows, float* d_sc, uint32_t* out_count, Inner&& inner) {
-    int rc;
-    uint32_t counts[kMaxQueries];
-    if (nmax == 0) {
-        if ((rc = inner(k, d_rows, d_sc, counts))) return rc;
-        if (out_count) memcpy(out_count, counts, (size_t)nq * 4);
-        return PG_OK;
-    }
-    const uint32_t kx = k + nmax;
-    const uint32_t total = excl_on_host ? off[nq] - off[0] : 0;
-    uint32_t *d_off, *d_cnt; uint64_t *d_list, *d_xrows; float* d_xsc;
-    if ((rc = scratch_carve(ctx, kSlotRecallExclude, [&](Carve& c) {
-            d_off = c.take<uint32_t>((size_t)nq + 1);
-            d_cnt = c.take<uint32_t>(nq);
-            d_list = c.take<uint64_t>(total);
-            d_xrows = c.take<uint64_t>((size_t)nq * kx);
-            d_xsc = c.take<float>((size_t)nq * kx);
-        }))) return rc;
-    uint32_t h_off[kMaxQueries + 1];
-    for (uint32_t q = 0; q <= nq; ++q) h_off[q] = excl_on_host ? off[q] - off[0] : off[q];
-    PG_HIP(hipMemcpyAsync(d_off, h_off, ((size_t)nq + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-    if (total) PG_HIP(hipMemcpyAsync(d_list, excl + off[0], (size_t)total * 8, hipMemcpyHostToDevice, ctx->stream));
-    PG_HIP(hipStreamSynchronize(ctx->stream));          // (h_off lives on this frame, and the inner recall may reuse pageable staging)
-    if ((rc = inner(kx, d_xrows, d_xsc, counts))) return rc;
-    if ((rc = exclude_compact_locked(ctx, d_xrows, d_xsc, nq, kx, excl_on_host ? d_list : excl, d_off, k,
-                                     l2 ? __builtin_inff() : -__builtin_inff(), d_rows, d_sc, d_cnt)))
-        return rc;
-    PG_HIP(hipMemcpyAsync(ctx->h_status, d_cnt, (size_t)nq * 4, hipMemcpyDeviceToHost, ctx->stream));
-    PG_HIP(hipStreamSynchronize(ctx->stream));
-    if (out_count) memcpy(out_count, ctx->h_status, (size_t)nq * 4);
-    return PG_OK;
-}
-
-// the queries of an item-to-item recall arrive as rows of the trigger table: the trigger rows are few, one small
-// device-to-device copy each (coalesced 512-B rows)
-int trigger_fill(pg_ctx* ctx, const pg_table* trigger_table, const uint32_t* trigger_rows, uint32_t n, float* d_q) {
-    const size_t dim = trigger_table->dim;
-    for (uint32_t i = 0; i < n; ++i)
-        PG_HIP(hipMemcpyAsync(d_q + i * dim, trigger_table->d + trigger_rows[i] * dim, dim * 4, hipMemcpyDeviceToDevice, ctx->stream));
-    return PG_OK;
-}
-
-// pg_recall_topk_exclude[_dev]: the checks of the call it extends (pg_recall_topk[_l2][_dev], or pg_recall_topk_where_ex with a
-// clause), then the lists'
-int recall_exclude_entry(const char* who, pg_ctx* ctx, const pg_table* t, const float* q, uint32_t nq, uint32_t k, const uint64_t* excl,
-                         const uint32_t* off, const pg_recall_exclude_opts* opts, uint64_t* rows, float* sc, uint32_t* out_count, bool host) {
-    const int metric = opts ? opts->metric : 0;
-    const pg_features* fs = opts ? opts->fs : nullptr;
-    const pg_where* w = opts ? opts->where : nullptr;
-    PG_REQUIRE((fs != nullptr) == (w != nullptr), "%s: opts->fs and opts->where come together", who);
-    int rc;
-    if (w) {
-        if ((rc = where_clause_check(who, ctx, t, fs, w, metric, q, rows, sc, nq, k))) return rc;
-    } else {
-        PG_REQUIRE(metric == 0 || metric == 1, "%s: metric %d unknown (0 inner product, 1 squared Euclidean)", who, metric);
-        if ((rc = recall_check(who, ctx, t, q, rows, sc, nq, k, metric == 1))) return rc;
-    }
-    PG_REQUIRE(off, "%s: excl_offsets is NULL", who);
-    uint32_t nmax = 0;
-    if ((rc = exclude_lists_check(who, off, nq, k, 0, &nmax))) return rc;
-    PG_REQUIRE(excl || off[nq] == off[0], "%s: excl_rows is NULL", who);
-    std::lock_guard<std::mutex> g(ctx->mu);
-    TableRead tr(t->rw);
-    WhereServe ws;
-    if (w && (rc = where_clause_bind(who, ctx, t, fs, w, &ws))) return rc;
-    pg_index* ix = w ? index_route_where(ctx, t) : nullptr;
-    auto run = [&](const float* d_q, uint64_t* d_rows, float* d_sc) {
-        auto inner = [&](uint32_t kk, uint64_t* r, float* s, uint32_t* counts) {
-            if (!w) {
-                RecallOpts o;
-                o.l2 = metric == 1;
-                return recall_batches_locked(ctx, t, d_q, nq, kk, r, s, counts, o);
-            }
-            return ix ? index_where_locked(ctx, ix, ws.id, ws.f, metric == 1, d_q, nq, kk, r, s, counts)
-                      : recall_where_locked(ctx, t, ws.f, metric, d_q, nq, kk, r, s, counts);
-        };
-        return recall_exclude_locked(ctx, nq, k, nmax, metric == 1, excl, host, off, d_rows, d_sc, out_count, inner);
-    };
-    rc = host ? recall_staged(ctx, t->dim, q, nq, k, rows, sc, run) : run(q, rows, sc);
-    if (rc != PG_OK && w) (void)hipStreamSynchronize(ctx->stream);      // (nothing enqueued reads the bitmap once ws lets go of it)
-    return rc;
-}
-
-int topk_merge_strided_locked(pg_ctx* ctx, const uint64_t* d_rows, const float* d_scores, uint32_t nq, uint32_t nlists,
-                              uint32_t per_list, size_t row_ls, size_t row_qs, size_t sc_ls, size_t sc_qs, uint32_t k,
-                              uint64_t* d_out_rows, float* d_out_scores, uint32_t* d_out_count) {
-    if (nq < 1 || nq > (uint32_t)kMaxQueries) {
-        set_error("topk merge: nq=%u out of range", nq);
-        return PG_ERR_INVALID;
-    }
-    const uint64_t per_q = (uint64_t)nlists * per_list;
-    if (k < 1 || k > 16384 || per_q == 0 || per_q > k + kCandSlack) {
-        set_error("topk merge: unsupported sizes k=%u lists=%u x %u", k, nlists, per_list);
-        return PG_ERR_UNSUPPORTED;
-    }
-    RecallScratch rs;
-    int rc;
-    if ((rc = recall_scratch(ctx, 64, k, &rs))) return rc;
-    PG_HIP(hipMemsetAsync(rs.cnt, 0, sizeof(uint32_t) * kMaxQueries, ctx->stream));
-    dim3 grid((uint32_t)((per_q + 255) / 256), nq);
-    merge_keys_kernel<<<grid, 256, 0, ctx->stream>>>(d_rows, d_scores, nq, nlists, per_list, row_ls, row_qs, sc_ls, sc_qs, rs.cap, rs.cand[0],
-                                                    rs.cnt);
-    PG_HIP(hipGetLastError());
-    if ((rc = launch_select(ctx, nq, rs.cand[0], rs.cand[1], rs.cnt, rs.thr, rs.cap, k, 0))) return rc;
-    return final_launch(ctx, rs.cand[1], rs.cnt, rs.cap, nq, k, 0, d_out_rows, d_out_scores, d_out_count);
-}
-
-// global top-k of nlists per-shard lists per query (identical and deterministic on every shard that runs it)
-int topk_merge_locked(pg_ctx* ctx, const uint64_t* d_rows, const float* d_scores, uint32_t nq, uint32_t nlists,
-                      uint32_t per_list, int list_major, uint32_t k, uint64_t* d_out_rows, float* d_out_scores,
-                      uint32_t* d_out_count) {
-    const size_t ls = list_major ? (size_t)nq * per_list : (size_t)per_list;
-    const size_t qs = list_major ? (size_t)per_list : (size_t)nlists * per_list;
-    return topk_merge_strided_locked(ctx, d_rows, d_scores, nq, nlists, per_list, ls, qs, ls, qs, k, d_out_rows, d_out_scores, d_out_count);
-}
-
 // The exact re-scoring and the squared-Euclidean helpers for callers outside this file (index.hip): the same kernels, so a
 // row scored there carries the bits the table's own pass gives it.
 int rescore_launch(pg_ctx* ctx, uint32_t dim, bool l2, const float* tab, const float* d_queries, const float* thr, const uint32_t* susp,
@@ -3662,340 +2461,4 @@ int negate_launch(pg_ctx* ctx, float* d_v, uint64_t n) {
     return PG_OK;
 }
 
-int where_check(const char* who, const pg_ctx* ctx, const pg_table* t, const pg_features* fs, int column, int op, long long value,
-                int metric, const void* queries, const void* rows, const void* scores, uint32_t nq, uint32_t k, RowFilter* f) {
-    PG_REQUIRE(ctx && t && fs && queries && rows && scores, "%s: NULL argument", who);
-    PG_REQUIRE(nq >= 1 && nq <= (uint32_t)kMaxQueries, "%s: nq=%u must be in [1,%d]", who, nq, kMaxQueries);
-    PG_REQUIRE(t->dim <= 128 || nq <= 32, "%s: dim %u supports at most 32 queries per call", who, t->dim);
-    PG_REQUIRE(column >= 0 && (size_t)column < fs->cols.size(), "%s: column %d out of range", who, column);
-    PG_REQUIRE(op >= 0 && op <= 5, "%s: op %d unknown (0 >, 1 >=, 2 <, 3 <=, 4 ==, 5 !=)", who, op);
-    PG_REQUIRE(metric == 0 || metric == 1, "%s: metric %d unknown (0 inner product, 1 squared Euclidean)", who, metric);
-    PG_REQUIRE(fs->rows >= t->rows, "%s: the feature store holds %llu rows, the table %llu", who, (unsigned long long)fs->rows,
-               (unsigned long long)t->rows);
-    const pg_features::Column& c = fs->cols[(size_t)column];
-    if ((c.dtype != PG_F_I32 && c.dtype != PG_F_I64) || !c.d) {
-        set_error("%s: column \"%s\" must be an int32 / int64 column with values", who, c.name.c_str());
-        return PG_ERR_UNSUPPORTED;
-    }
-    if (k < 1 || k > 16384) {
-        set_error("%s: k=%u unsupported (1..16384)", who, k);
-        return PG_ERR_UNSUPPORTED;
-    }
-    *f = RowFilter();
-    f->col = c.d;
-    f->dtype = c.dtype;
-    f->op = op;
-    f->val = value;
-    return PG_OK;
-}
-
-int where_pad_launch(pg_ctx* ctx, uint64_t* d_rows, float* d_sc, size_t n, bool l2) {
-    recall_pad_kernel<<<(uint32_t)((n + 255) / 256), 256, 0, ctx->stream>>>(d_rows, d_sc, n, l2);
-    PG_HIP(hipGetLastError());
-    return PG_OK;
-}
-
-int recall_where_locked(pg_ctx* ctx, const pg_table* t, RowFilter f, int metric, const float* d_q, uint32_t nq, uint32_t k,
-                        uint64_t* d_rows, float* d_sc, uint32_t* out_count) {
-    int rc;
-    uint32_t *d_blk, *d_grp, cblocks, admitted;
-    if ((rc = filter_count_locked(ctx, f, t->rows, &d_blk, &d_grp, &cblocks, &admitted))) return rc;
-    f.admitted = admitted;
-    if (admitted == 0) {
-        // nothing passes: every slot is padding (row UINT64_MAX, score -inf / distance +inf), every count 0
-        if ((rc = where_pad_launch(ctx, d_rows, d_sc, (size_t)nq * k, metric == 1))) return rc;
-        if (out_count) for (uint32_t q = 0; q < nq; ++q) out_count[q] = 0;
-    } else if (admitted <= (nq <= 4 ? ctx->knobs.where_compact_max_rows / 2 : ctx->knobs.where_compact_max_rows) &&
-               (uint64_t)admitted * ctx->knobs.where_compact_min_ratio <= t->rows &&
-               (metric == 0 || t->dim == 64 || t->dim == 128)) {
-        // A selective filter: the thresholds the scan plans estimate from samples of the table say little about the few rows
-        // that pass (1 % admitted of 100 M rows, 128 queries: 180 ms of re-planned passes).  Gather the admitted rows, in row
-        // order, into a compact table and run the exact scan over that: its rows are the candidates, its row order the tie
-        // order, and the answer's local rows map back through the id list.  (The gather is 1 KB of traffic per admitted row: at
-        // 100 M x 128 the copy wins below ~4 M rows for a lone query — in place 2.2 ms at 4 % — and below ~8 M for 16+ queries.)
-        uint32_t* d_ids;
-        float *d_tab, *d_cnx = nullptr;
-        if ((rc = scratch_carve(ctx, kSlotFilterGather, [&](Carve& c) {
-                d_ids = c.take<uint32_t>((size_t)admitted + 64);
-                d_tab = c.take<float>(((size_t)admitted + 64) * t->dim);
-                if (metric == 1) d_cnx = c.take<float>((size_t)admitted + 64);
-            }))) return rc;
-        filter_scatter_kernel<<<cblocks, 256, 0, ctx->stream>>>(f, t->rows, d_blk, d_grp, d_ids);
-        const uint64_t quads = (uint64_t)admitted * (t->dim / 4);
-        compact_gather_kernel<<<(uint32_t)((quads + 255) / 256), 256, 0, ctx->stream>>>(t->d, d_ids, admitted, t->dim, d_tab);
-        PG_HIP(hipMemsetAsync(d_tab + (size_t)admitted * t->dim, 0, (size_t)64 * t->dim * 4, ctx->stream));
-        pg_table ct;
-        ct.d = d_tab;
-        ct.rows = admitted;
-        ct.dim = t->dim;
-        if (metric == 1) {
-            if ((rc = ensure_table_nx(ctx, t))) return rc;
-            compact_gather_nx_kernel<<<(admitted + 64 + 255) / 256, 256, 0, ctx->stream>>>(t->d_nx, d_ids, admitted, d_cnx);
-            ct.d_nx = d_cnx;
-            ct.nx_valid = true;
-        }
-        PG_HIP(hipGetLastError());
-        RecallOpts o;
-        o.l2 = metric == 1;
-        o.exact_only = true;
-        if ((rc = recall_batches_locked(ctx, &ct, d_q, nq, k, d_rows, d_sc, out_count, o))) return rc;
-        compact_map_rows_kernel<<<(uint32_t)(((size_t)nq * k + 255) / 256), 256, 0, ctx->stream>>>(d_rows, (uint64_t)nq * k, d_ids, t->row_offset, admitted);
-        PG_HIP(hipGetLastError());
-        ct.d = nullptr;
-        ct.d_nx = nullptr;
-    } else {
-        RecallOpts o;
-        o.l2 = metric == 1;
-        o.filter = &f;
-        if ((rc = recall_batches_locked(ctx, t, d_q, nq, k, d_rows, d_sc, out_count, o))) return rc;
-    }
-    return PG_OK;
-}
-
-int view_create_locked(const char* who, pg_ctx* ctx, const pg_table* t, const RowFilter& f, pg_table** out_view) {
-    PG_HIP(hipSetDevice(ctx->device));
-    int rc;
-    uint32_t *d_blk, *d_grp, cblocks, admitted;
-    if ((rc = filter_count_locked(ctx, f, t->rows, &d_blk, &d_grp, &cblocks, &admitted))) return rc;
-    if (admitted == 0) {
-        set_error("%s: no row passes the filter", who);
-        return PG_ERR_EMPTY;
-    }
-    pg_table* v = new pg_table();
-    v->rows = admitted;
-    v->dim = t->dim;
-    v->row_offset = 0;
-    v->map_offset = t->row_offset;
-    hipError_t e = hipMalloc((void**)&v->d, ((size_t)admitted + 64) * t->dim * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&v->d_row_map, ((size_t)admitted + 64) * sizeof(uint32_t));
-    if (e != hipSuccess) {
-        set_error("%s: hipMalloc(%.1f GB) failed: %s", who, (double)admitted * t->dim * 4 / 1e9, hipGetErrorString(e));
-        if (v->d) (void)hipFree(v->d);
-        delete v;
-        return PG_ERR_NOMEM;
-    }
-    filter_scatter_kernel<<<cblocks, 256, 0, ctx->stream>>>(f, t->rows, d_blk, d_grp, v->d_row_map);
-    const uint64_t quads = (uint64_t)admitted * (t->dim / 4);
-    compact_gather_kernel<<<(uint32_t)((quads + 255) / 256), 256, 0, ctx->stream>>>(t->d, v->d_row_map, admitted, t->dim, v->d);
-    PG_HIP(hipGetLastError());
-    PG_HIP(hipMemsetAsync(v->d + (size_t)admitted * t->dim, 0, (size_t)64 * t->dim * sizeof(float), ctx->stream));
-    PG_HIP(hipMemsetAsync(v->d_row_map + admitted, 0, 64 * sizeof(uint32_t), ctx->stream));
-    PG_HIP(hipStreamSynchronize(ctx->stream));
-    *out_view = v;
-    return PG_OK;
-}
-
 }  // namespace pg
-
-extern "C" {
-
-int pg_table_screen_info(pg_ctx* ctx, const pg_table* t, int* out_elem_bytes, float* out_scale, float* out_resid) {
-    PG_REQUIRE(ctx && t, "pg_table_screen_info: NULL argument");
-    std::lock_guard<std::mutex> g(ctx->mu);
-    int rc;
-    if ((rc = pg::ensure_table_stats(ctx, t))) return rc;
-    const bool screened = t->stats_valid && t->all_finite;
-    if (out_elem_bytes) *out_elem_bytes = screened ? (t->shadow_is_i8 ? 1 : 2) : 0;
-    if (out_scale) *out_scale = screened && t->shadow_is_i8 ? t->s8 : 0.0f;
-    if (out_resid) *out_resid = screened && t->shadow_is_i8 ? t->resid8 : 0.0f;
-    return PG_OK;
-}
-
-int pg_recall_topk_dev(pg_ctx* ctx, const pg_table* t, const float* d_queries, uint32_t nq,
-                       uint32_t k, uint64_t* d_out_rows, float* d_out_scores, uint32_t* out_count) {
-    return pg::recall_entry("pg_recall_topk_dev", ctx, t, d_queries, nq, k, d_out_rows, d_out_scores, out_count, false, false);
-}
-
-int pg_recall_topk(pg_ctx* ctx, const pg_table* t, const float* queries, uint32_t nq, uint32_t k,
-                   uint64_t* out_rows, float* out_scores, uint32_t* out_count) {
-    return pg::recall_entry("pg_recall_topk", ctx, t, queries, nq, k, out_rows, out_scores, out_count, false, true);
-}
-
-// HologresVectorRecallV2 (service/recall/hologres_vector_recall_v2.go:23,96-206): "SELECT id, pm_approx_squared_euclidean_distance
-// (emb, $1) as distance … ORDER BY distance LIMIT n" — the K rows of SMALLEST squared Euclidean distance, ascending, the distance
-// as the item's score (:181-189).  Exact here (the reference's Proxima index is approximate): d = fmaf(-2, ip, |x|^2 + |q|^2),
-// every sum a k-ascending fp32 fmaf chain; ties by row ascending; slots beyond the table's rows: row UINT64_MAX, distance +inf.
-int pg_recall_topk_l2_dev(pg_ctx* ctx, const pg_table* t, const float* d_queries, uint32_t nq, uint32_t k, uint64_t* d_out_rows,
-                          float* d_out_dist, uint32_t* out_count) {
-    return pg::recall_entry("pg_recall_topk_l2_dev", ctx, t, d_queries, nq, k, d_out_rows, d_out_dist, out_count, true, false);
-}
-
-int pg_recall_topk_l2(pg_ctx* ctx, const pg_table* t, const float* queries, uint32_t nq, uint32_t k, uint64_t* out_rows,
-                      float* out_dist, uint32_t* out_count) {
-    return pg::recall_entry("pg_recall_topk_l2", ctx, t, queries, nq, k, out_rows, out_dist, out_count, true, true);
-}
-
-// A Hologres vector recall WITH its WhereClause (HologresVectorConf.WhereClause, recconf.go:492-497; the SQL of
-// hologres_vector_recall.go:23 / hologres_vector_recall_v2.go:23 has `FROM table WHERE … ORDER BY distance`), in the shape the
-// device serves: `column OP constant` over an integer feature column keyed by item row (e.g. "create_time > ${time}" with the
-// constant substituted by the caller, as :56-61 does).  metric 0: inner product, descending; 1: squared Euclidean, ascending.
-// Only rows that pass are candidates; out_count[q] = min(k, rows that pass).  Exact, like the unfiltered recalls: the predicate
-// is applied where candidates are made, so the plans' thresholds are thresholds of the filtered top-K.
-int pg_recall_topk_where(pg_ctx* ctx, const pg_table* t, const pg_features* fs, int column, int op, long long value, int metric,
-                         const float* queries, uint32_t nq, uint32_t k, uint64_t* out_rows, float* out_scores, uint32_t* out_count) {
-    pg::RowFilter f;
-    int rc;
-    if ((rc = pg::where_check("pg_recall_topk_where", ctx, t, fs, column, op, value, metric, queries, out_rows, out_scores, nq, k, &f)))
-        return rc;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    pg::TableRead tr(t->rw);
-    pg_index* ix = pg::index_route_where(ctx, t);          // ("index_route_where": the attached index, when it is current)
-    uint32_t counts[pg::kMaxQueries];
-    auto run = [&](const float* d_q, uint64_t* d_rows, float* d_sc) {
-        return ix ? pg::index_where_locked(ctx, ix, pg::WhereId{fs, column, nullptr, 0}, f, metric == 1, d_q, nq, k, d_rows, d_sc, counts)
-                  : pg::recall_where_locked(ctx, t, f, metric, d_q, nq, k, d_rows, d_sc, counts);
-    };
-    if ((rc = pg::recall_staged(ctx, t->dim, queries, nq, k, out_rows, out_scores, run))) return rc;
-    if (out_count) memcpy(out_count, counts, (size_t)nq * 4);
-    return PG_OK;
-}
-
-// A filtered VIEW of a table: the rows `column OP value` admits, in row order, copied into a table of their own whose recalls
-// answer with the source's row ids.  What a Hologres recall with a WhereClause whose constant is fixed when the recall is built
-// (hologres_vector_recall.go:56-61: "${time}" is substituted in the constructor) searches: build the view once per table
-// generation and every recall flavour — pg_recall_topk[_l2][_dev], a coalescer's pg_coalescer_recall[_l2] — serves it at the speed
-// of an unfiltered table of that size (own shadows, statistics and threshold model).  A snapshot: later changes of the source or
-// the column do not reach it.  Ties break by source row, as in pg_recall_topk_where.  Destroyed with pg_table_destroy.
-int pg_table_view_create(pg_ctx* ctx, const pg_table* t, const pg_features* fs, int column, int op, long long value, pg_table** out_view) {
-    PG_REQUIRE(ctx && t && fs && out_view, "pg_table_view_create: NULL argument");
-    PG_REQUIRE(!t->d_row_map, "pg_table_view_create: the source is a view itself");
-    PG_REQUIRE(column >= 0 && (size_t)column < fs->cols.size(), "pg_table_view_create: column %d out of range", column);
-    PG_REQUIRE(op >= 0 && op <= 5, "pg_table_view_create: op %d unknown (0 >, 1 >=, 2 <, 3 <=, 4 ==, 5 !=)", op);
-    PG_REQUIRE(fs->rows >= t->rows, "pg_table_view_create: the feature store holds %llu rows, the table %llu", (unsigned long long)fs->rows,
-               (unsigned long long)t->rows);
-    const pg_features::Column& c = fs->cols[(size_t)column];
-    if ((c.dtype != PG_F_I32 && c.dtype != PG_F_I64) || !c.d) {
-        pg::set_error("pg_table_view_create: column \"%s\" must be an int32 / int64 column with values", c.name.c_str());
-        return PG_ERR_UNSUPPORTED;
-    }
-    pg::RowFilter f;
-    f.col = c.d;
-    f.dtype = c.dtype;
-    f.op = op;
-    f.val = value;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    pg::TableRead tr(t->rw);
-    return pg::view_create_locked("pg_table_view_create", ctx, t, f, out_view);
-}
-
-// I2IVectorRecall (service/recall/item_2_item_vector_racall.go:51-152): the trigger item's own embedding
-// (dao.VectorString(item_id)) is the query of the same inner-product top-K; the trigger is not excluded (the
-// reference's SQL does not exclude it either).
-int pg_i2i_recall(pg_ctx* ctx, const pg_table* trigger_table, const uint32_t* trigger_rows, uint32_t n,
-                  const pg_table* t, uint32_t k, uint64_t* out_rows, float* out_scores, uint32_t* out_count) {
-    PG_REQUIRE(ctx && trigger_table && t && trigger_rows && out_rows && out_scores, "pg_i2i_recall: NULL argument");
-    PG_REQUIRE(trigger_table->dim == t->dim, "pg_i2i_recall: trigger table dim %u != searched table dim %u", trigger_table->dim, t->dim);
-    PG_REQUIRE(!trigger_table->d_row_map, "pg_i2i_recall: the trigger table is a filtered view (trigger rows are rows of the source)");
-    PG_REQUIRE(n >= 1 && n <= (uint32_t)pg::kMaxQueries && (t->dim <= 128 || n <= 32), "pg_i2i_recall: %u trigger items per call unsupported", n);
-    if (k < 1 || k > 16384) {
-        pg::set_error("pg_i2i_recall: k=%u unsupported (1..16384)", k);
-        return PG_ERR_UNSUPPORTED;
-    }
-    for (uint32_t i = 0; i < n; ++i)
-        PG_REQUIRE(trigger_rows[i] < trigger_table->rows, "pg_i2i_recall: trigger row %u outside table of %llu rows", trigger_rows[i],
-                   (unsigned long long)trigger_table->rows);
-    std::lock_guard<std::mutex> g(ctx->mu);
-    pg::TableRead2 tr(t, trigger_table);
-    auto fill = [&](float* d_q) { return pg::trigger_fill(ctx, trigger_table, trigger_rows, n, d_q); };
-    return pg::recall_staged(ctx, t->dim, nullptr, n, k, out_rows, out_scores, [&](const float* d_q, uint64_t* d_rows, float* d_sc) {
-        return pg::recall_dev_locked(ctx, t, d_q, n, k, d_rows, d_sc, out_count, nullptr);
-    }, fill);
-}
-
-int pg_recall_topk_exclude(pg_ctx* ctx, const pg_table* t, const float* queries, uint32_t nq, uint32_t k, const uint64_t* excl_rows,
-                           const uint32_t* excl_offsets, const pg_recall_exclude_opts* opts, uint64_t* out_rows, float* out_scores,
-                           uint32_t* out_count) {
-    return pg::recall_exclude_entry("pg_recall_topk_exclude", ctx, t, queries, nq, k, excl_rows, excl_offsets, opts, out_rows, out_scores,
-                                    out_count, true);
-}
-
-int pg_recall_topk_exclude_dev(pg_ctx* ctx, const pg_table* t, const float* d_queries, uint32_t nq, uint32_t k, const uint64_t* d_excl_rows,
-                               const uint32_t* excl_offsets, const pg_recall_exclude_opts* opts, uint64_t* d_out_rows, float* d_out_scores,
-                               uint32_t* out_count) {
-    return pg::recall_exclude_entry("pg_recall_topk_exclude_dev", ctx, t, d_queries, nq, k, d_excl_rows, excl_offsets, opts, d_out_rows,
-                                    d_out_scores, out_count, false);
-}
-
-// pg_i2i_recall without the items the request has seen — and, with exclude_trigger, without the trigger item itself (the hole
-// pg_i2i_recall documents): its checks in its order, then the lists'
-int pg_i2i_recall_exclude(pg_ctx* ctx, const pg_table* trigger_table, const uint32_t* trigger_rows, uint32_t n, const pg_table* t,
-                          uint32_t k, int exclude_trigger, const uint64_t* excl_rows, const uint32_t* excl_offsets, uint64_t* out_rows,
-                          float* out_scores, uint32_t* out_count) {
-    PG_REQUIRE(ctx && trigger_table && t && trigger_rows && out_rows && out_scores, "pg_i2i_recall_exclude: NULL argument");
-    PG_REQUIRE(trigger_table->dim == t->dim, "pg_i2i_recall_exclude: trigger table dim %u != searched table dim %u", trigger_table->dim, t->dim);
-    PG_REQUIRE(!trigger_table->d_row_map, "pg_i2i_recall_exclude: the trigger table is a filtered view (trigger rows are rows of the source)");
-    PG_REQUIRE(n >= 1 && n <= (uint32_t)pg::kMaxQueries && (t->dim <= 128 || n <= 32), "pg_i2i_recall_exclude: %u trigger items per call unsupported", n);
-    if (k < 1 || k > 16384) {
-        pg::set_error("pg_i2i_recall_exclude: k=%u unsupported (1..16384)", k);
-        return PG_ERR_UNSUPPORTED;
-    }
-    for (uint32_t i = 0; i < n; ++i)
-        PG_REQUIRE(trigger_rows[i] < trigger_table->rows, "pg_i2i_recall_exclude: trigger row %u outside table of %llu rows", trigger_rows[i],
-                   (unsigned long long)trigger_table->rows);
-    PG_REQUIRE(!exclude_trigger || trigger_table == t, "pg_i2i_recall_exclude: exclude_trigger needs the trigger table to be the searched table");
-    PG_REQUIRE(excl_offsets || exclude_trigger, "pg_i2i_recall_exclude: excl_offsets is NULL");
-    uint32_t nmax = 0;
-    int rc;
-    if ((rc = pg::exclude_lists_check("pg_i2i_recall_exclude", excl_offsets, n, k, exclude_trigger ? 1u : 0u, &nmax))) return rc;
-    PG_REQUIRE(excl_rows || !excl_offsets || excl_offsets[n] == excl_offsets[0], "pg_i2i_recall_exclude: excl_rows is NULL");
-    // every request's list with its trigger row behind it
-    std::vector<uint64_t> lists;
-    std::vector<uint32_t> off(n + 1, 0);
-    for (uint32_t i = 0; i < n; ++i) {
-        if (excl_offsets) lists.insert(lists.end(), excl_rows + excl_offsets[i], excl_rows + excl_offsets[i + 1]);
-        if (exclude_trigger) lists.push_back(t->row_offset + trigger_rows[i]);
-        off[i + 1] = (uint32_t)lists.size();
-    }
-    std::lock_guard<std::mutex> g(ctx->mu);
-    pg::TableRead2 tr(t, trigger_table);
-    auto fill = [&](float* d_q) { return pg::trigger_fill(ctx, trigger_table, trigger_rows, n, d_q); };
-    return pg::recall_staged(ctx, t->dim, nullptr, n, k, out_rows, out_scores, [&](const float* d_q, uint64_t* d_rows, float* d_sc) {
-        auto inner = [&](uint32_t kk, uint64_t* r, float* s, uint32_t* counts) { return pg::recall_dev_locked(ctx, t, d_q, n, kk, r, s, counts, nullptr); };
-        return pg::recall_exclude_locked(ctx, n, k, nmax, false, lists.data(), true, off.data(), d_rows, d_sc, out_count, inner);
-    }, fill);
-}
-
-// OnlineVectorRecall (service/recall/online_vector_recall.go:73-155): the model server turns the user's features
-// into the user-tower embedding and answers with its FaissNeighNum nearest items (match_item_scores + item_ids,
-// algorithm/eas/easyrec_response.go:700-734).  Here: user tower of the two-tower model on the device, then the
-// same exact inner-product top-K over the item-embedding table (dim = the towers' output width).
-int pg_online_vector_recall(pg_ctx* ctx, const pg_model* m, const pg_table* item_emb, const float* user_vecs,
-                            uint32_t n_req, uint32_t k, uint64_t* out_rows, float* out_scores, uint32_t* out_count) {
-    PG_REQUIRE(ctx && m && item_emb && user_vecs && out_rows && out_scores, "pg_online_vector_recall: NULL argument");
-    PG_REQUIRE(m->kind == PG_MODEL_FM_TWOTOWER, "pg_online_vector_recall: model is not FM_TWOTOWER");
-    PG_REQUIRE(item_emb->dim == m->to, "pg_online_vector_recall: item-embedding table dim %u != tower output %u", item_emb->dim, m->to);
-    PG_REQUIRE(n_req >= 1 && n_req <= (uint32_t)pg::kMaxQueries, "pg_online_vector_recall: n_req=%u must be in [1,%d]", n_req, pg::kMaxQueries);
-    if (k < 1 || k > 16384) {
-        pg::set_error("pg_online_vector_recall: k=%u unsupported (1..16384)", k);
-        return PG_ERR_UNSUPPORTED;
-    }
-    std::lock_guard<std::mutex> g(ctx->mu);
-    pg::TableRead tr(item_emb->rw);
-    float *d_u, *d_q, *d_sc;
-    uint64_t* d_rows;
-    int rc;
-    const size_t rb = (size_t)n_req * k * 8, sb = (size_t)n_req * k * 4;
-    if ((rc = pg::scratch_carve(ctx, pg::kSlotStaging, [&](pg::Carve& c) {
-            d_u = c.take<float>((size_t)n_req * m->d_user);
-            d_q = c.take<float>((size_t)n_req * m->to);
-            d_rows = c.take<uint64_t>((size_t)n_req * k);
-            d_sc = c.take<float>((size_t)n_req * k);
-        }))) return rc;
-    PG_HIP(hipMemcpyAsync(d_u, user_vecs, (size_t)n_req * m->d_user * 4, hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = pg::fm2t_user_embedding_locked(ctx, m, d_u, n_req, d_q))) return rc;
-    if ((rc = pg::recall_dev_locked(ctx, item_emb, d_q, n_req, k, d_rows, d_sc, out_count, nullptr))) return rc;
-    PG_HIP(hipMemcpyAsync(out_rows, d_rows, rb, hipMemcpyDeviceToHost, ctx->stream));
-    PG_HIP(hipMemcpyAsync(out_scores, d_sc, sb, hipMemcpyDeviceToHost, ctx->stream));
-    PG_HIP(hipStreamSynchronize(ctx->stream));
-    return PG_OK;
-}
-
-int pg_topk_merge_dev(pg_ctx* ctx, const uint64_t* d_rows, const float* d_scores, uint32_t nq,
-                      uint32_t nlists, uint32_t per_list, uint32_t k, uint64_t* d_out_rows,
-                      float* d_out_scores) {
-    PG_REQUIRE(ctx && d_rows && d_scores && d_out_rows && d_out_scores, "pg_topk_merge_dev: NULL argument");
-    std::lock_guard<std::mutex> g(ctx->mu);
-    return pg::topk_merge_locked(ctx, d_rows, d_scores, nq, nlists, per_list, 0, k, d_out_rows, d_out_scores, nullptr);
-}
-
-}  // extern "C"

@@ -120,7 +120,7 @@ __global__ __launch_bounds__(1024) void sort_kernel_reg(const double* __restrict
 }
 
 // A handful of segments of up to 8192 items: ranks by counting, 64 items per workgroup (see final_rank_kernel in
-// recall.hip — the network above keeps one CU busy for 66 us per segment while the rest of the chip idles).
+// recall_select.hip — the network above keeps one CU busy for 66 us per segment while the rest of the chip idles).
 // item i's position = #{j : key_j < key_i} + #{j < i : key_j = key_i}: the same order as the network (ties by index).
 // EPB items per workgroup, 256 / EPB threads per item (each counts within its share of the keys): 16 for one or two
 // segments (a 5 000-item segment then spreads over 313 workgroups), 64 beyond.

@@ -31,7 +31,7 @@ def same_bits(got, want):
 
 def ordered_bits(scores) -> np.ndarray:
     """float32 → uint32 whose unsigned order is the recall's score order: IEEE totalOrder (-inf < ... < -0.0 < +0.0 < ... <
-    +inf) with every NaN below everything (f32_ordered_bits of recall.hip / oracle.c, tail_ord of group.hip)."""
+    +inf) with every NaN below everything (f32_ordered_bits of recall_shared.hpp / oracle.c, tail_ord of group.hip)."""
     s = np.ascontiguousarray(scores, dtype=np.float32)
     b = s.view(np.uint32)
     ob = np.where(b & np.uint32(0x80000000), ~b, b | np.uint32(0x80000000)).astype(np.uint32)

@@ -1,5 +1,5 @@
 """GPU tests of the shard-side exchange calls — the glue kernels of the multi-GPU path (csrc/group.hip, misc.hip, the merge of
-recall.hip) — each against its plain numpy statement in tests/shard_ref.py, bit for bit: rows and slots exact, scores as uint32 /
+recall_select.hip) — each against its plain numpy statement in tests/shard_ref.py, bit for bit: rows and slots exact, scores as uint32 /
 uint64 bits, NaN by NaN-ness.  Every output buffer is filled with a sentinel first (0xA5 bytes) and carries a guard region behind
 the specified extent; whatever the call is not specified to write must still hold the sentinel afterwards.  Refusal cases pass
 only arguments the host checks before anything is launched."""
