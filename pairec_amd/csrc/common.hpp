@@ -19,6 +19,7 @@
 
 #include "../../include/pairec_gpu.h"
 #include "scratch_layout.hpp"
+#include "table_state.hpp"
 
 namespace pg {
 
@@ -68,13 +69,13 @@ enum ScratchSlot : int {
     kSlotGroup = 9,          // group.hip pg_owned_compact_dev: the per-request counts of owned rows
     kSlotRerank = 10,        // pipeline.hip: the re-rank stage's DPP candidates
     kSlotHitRecords = 11,    // recall.hip: the screened pass's record regions
-    kSlotFilterCount = 12,   // recall.hip filter_count_locked: per-block and per-group counts of the rows a filter admits
-    kSlotFilterGather = 13,  // recall.hip: the admitted rows' ids, compacted table and norms of a filtered recall
+    kSlotFilterCount = 12,   // recall_filter.hip filter_count_locked: per-block and per-group counts of the rows a filter admits
+    kSlotFilterGather = 13,  // recall_filter.hip: the admitted rows' ids, compacted table and norms of a filtered recall
     kSlotRankHeads = 14,     // rank_mlp.hip: head partials of the weights-stationary multi-head kernel
     kSlotFuse = 15,          // pipeline.hip pg_fuse_scores_dev: the bound variables and error flags
     kSlotExprVars = 16,      // expr.hip pg_features_eval_dev: the bound variables
     kSlotIndexSearch = 17,   // index.hip: bounds, probe thresholds and list counts of an index recall; rank_mlp.hip: the fp16 split kernel's fallback tile tables (separate calls)
-    kSlotRecallExclude = 18, // recall.hip: the over-fetched answer, lists and counts of a recall with exclusion lists
+    kSlotRecallExclude = 18, // recall_entry.hip: the over-fetched answer, lists and counts of a recall with exclusion lists
     kSlotCf = 19,            // cf.hip: status and counts, staged offsets and lists, the global tier's tables, the items to order, the over-fetched answer
     kSlotFanin = 20,         // fanin.hip: the merge's keys, values and masks
     kSlotTrim = 21,          // trim.hip: segment offsets and the order of a coarse-rank cut
@@ -111,10 +112,10 @@ struct Knobs {
     bool no_screen_i4m = false;    // PG_NO_SCREEN_I4M: batches of 5..64 queries stay on the int8 screen
     uint32_t i4m_min_queries = 1;  // PG_I4M_MIN_QUERIES: smallest batch it serves (below, and for squared-Euclidean recalls and tables without an int8 shadow: recall_i4.hip's vector-ALU screen, exact re-scoring of all its suspects; one query: 1.08 against 1.17 ms per 100 M rows)
     uint32_t i4m_max_queries = 64; // PG_I4M_MAX_QUERIES: largest batch the 4-bit matrix-pipe screen serves (<= kI4mMaxQueries)
-    double i4m_max_lambda = 2.2;   // PG_I4M_MAX_LAMBDA: largest pg_table::lam4 it is used for
+    double i4m_max_lambda = 2.2;   // PG_I4M_MAX_LAMBDA: largest TableDerived::lam4 it is used for
     double i4m_max_pairs = 2.4e7;  // PG_I4M_MAX_PAIRS: ... and the most (row, query) pairs per pass its 4-bit stage may be expected to pass on
     uint32_t i4_min_rows = 1u << 22; // PG_I4_MIN_ROWS: smallest table the 4-bit screen is built for
-    double i4_max_lambda = 1.7;    // PG_I4_MAX_LAMBDA: largest pg_table::lam4 the 4-bit screen is used for
+    double i4_max_lambda = 1.7;    // PG_I4_MAX_LAMBDA: largest TableDerived::lam4 the 4-bit screen is used for
     bool rank_no_ws = false;       // PG_RANK_NO_WS: streaming DNN3 kernel instead of the weights-stationary one
     uint32_t split_sort_max = 96;  // PG_SPLIT_SORT_MAX: up to this many lists (of 1025 … 8192 items, ~450 K items in all) per call are sorted run by run over the chip (split_sort.hpp; 0 = never)
     uint32_t rank_sort_max = 32;   // PG_RANK_SORT_MAX: up to this many lists per call are sorted by counting ranks (0 = never) ...
@@ -133,7 +134,7 @@ struct Knobs {
     bool l2_exact = false;                  // PG_L2_EXACT: squared-Euclidean recalls always on the exact scan (A/B runs)
     uint32_t where_compact_max_rows = 8u << 20;   // PG_WHERE_COMPACT_MAX_ROWS: a filter admitting at most this many rows (half of it for <= 4 queries) ...
     uint32_t where_compact_min_ratio = 8;         // PG_WHERE_COMPACT_MIN_RATIO: ... and at most 1/ratio of the table is served from a compact copy of them
-    double l2_max_slack = 1.0;              // PG_L2_MAX_SLACK: largest pg_table::l2_slack the per-BLOCK cutoff is used for (above: the per-row test)
+    double l2_max_slack = 1.0;              // PG_L2_MAX_SLACK: largest TableDerived::l2_slack the per-BLOCK cutoff is used for (above: the per-row test)
     uint32_t screen_early_share = 604;      // PG_SCREEN_EARLY_SHARE: share (x 1024) of a SIMD's blocks given to its older wave (256-query screen)
     double index_dense_fraction = 0.01;     // PG_INDEX_DENSE_FRACTION: an index recall of nq queries whose (row, query) pairs exceed this x rows x nq^0.6 is served by the table's pass
     uint32_t index_plan_rounds = 2;         // PG_INDEX_PLAN_ROUNDS: expand / rescore / select rounds of an attached index's plan, for the probe and for the scan each
@@ -176,56 +177,9 @@ struct pg_table {
     // report d_row_map[local row] + map_offset — the source's row ids
     uint32_t* d_row_map = nullptr;
     uint64_t map_offset = 0;
-    // lazily computed for the screened recall (invalidated by upload / fill): statistics and the shadow of
-    // the rows that the screen streams instead of the fp32 rows (the exact re-scoring still gathers fp32):
-    //   dim 128: int8, X = rint(x / s8) with ONE scale s8 = max|x| / 127 for the table, [rows + 64][dim] bytes
-    //            — a quarter of the fp32 bytes; resid8 = max over rows of ||x - s8 X||_2 (measured, not assumed)
-    //   dim 64, and dim-128 tables whose value range defeats one int8 scale (heavy tails, outliers): bf16 (RNE of
-    //            every fp32 value), [rows + 64][dim] — half the bytes — plus the largest row norm of every 32-row block
-    bool stats_valid = false;
-    bool all_finite = false;
-    float max_norm = 0.0f;       // upper bound of the rows' L2 norms
-    uint16_t* d16 = nullptr;     // bf16 shadow; allocated on first use, kept across rebuilds
-    float* dnorm2 = nullptr;     // with the bf16 shadow: largest row norm^2 of every 32-row block (the bf16 bound is relative)
-    int8_t* d8 = nullptr;        // int8 shadow; likewise
-    bool shadow_is_i8 = false;   // which of the two the current statistics belong to
-    float s8 = 0.0f;             // int8 scale
-    float resid8 = 0.0f;         // upper bound of the rows' quantisation residual (L2)
-    bool shadow_failed = false;  // allocation failed once: stay on the exact scan
-    float* d_nx = nullptr;       // squared-Euclidean recall: |x|^2 of every row [rows + 64] (lazily, invalidated by upload / fill)
-    float* d_nxmin = nullptr;    // ... and the smallest of every 32-row block (the int8 screen's per-block cutoff under that metric)
-    bool nx_valid = false;
-    float l2_slack = 0.0f;       // mean (|x|^2 - the block's smallest) / 2 in units of the score spread: above Knobs::l2_max_slack the exact scan serves that metric
-    // recall_i4.hip: the 4-bit shadow that the full pass of a small batch streams (dim 128, built on the first such
-    // recall, 68 B per row): nibbles [rows + 64][64 B], one fp32 scale per row, and the bound's measured constants
-    uint8_t* d4 = nullptr;
-    uint32_t* d4s = nullptr;     // row scale (bf16, low half) | row residual bound (bf16, high half)
-    bool i4_ok = false, i4_failed = false;
-    float rho4 = 0.0f;           // max over rows of ||x - x^|| / (s_row sqrt(dim)) (diagnostic)
-    float rmax4 = 0.0f;          // max over rows of ||x - x^|| (upper bound)
-    float lam4 = 0.0f;           // mean residual term in units of the score spread (decides whether the shadow pays)
-    float i4m_pairs = 0.0f;      // recall_i4m.hip: running average of the (row, query) pairs its 4-bit stage lets through, per query
-    // recall_r2.hip: the int8 RESIDUAL shadow (x = s8 X8 + s8r Xr + e2) that the refinement stage of crowded tables gathers beside
-    // the int8 shadow; built the first time the table shows more than Knobs::r2_min_factor screen suspects per answer
-    int8_t* d8r = nullptr;
-    float s8r = 0.0f, resid2 = 0.0f;   // its scale (s8 / 254), the measured upper bound of ||e2||
-    bool r2_ok = false, r2_failed = false;
-    float wide_susp = 0.0f;      // running average of the int8 screen's suspects per query (passes without a 4-bit stage)
-    uint32_t rec_scale = 0;      // recall.hip: the 256-query pass's hit-record areas, x their default size (0 = 1; doubled when a batch overflows them)
-    uint32_t prefix_failures = 0; // batches whose refined thresholds failed verification for most queries (ordered rows): two → no refinement
-    // Threshold predictor (recall.hip, DESIGN.md 4.1, plan 0): a Gaussian model of a query's scores over the rows — mean
-    // vector and covariance from a row sample, built with the statistics — and the quantile z = (K-th best score −
-    // mean) / sigma actually observed for the batches served so far.  Once the observed z is tight, a batch's first
-    // thresholds come from the model instead of a pilot sample.  A hint only: every plan is verified, results are exact.
-    float* d_pred = nullptr;      // [dim] mean | [dim][dim] covariance | 4 doubles: n, sum z, sum z^2, min z
-    bool pred_model = false;      // mean / covariance belong to the current rows
-    uint32_t pred_k = 0;          // the K the observations belong to
-    double pred_n = 0.0, pred_sum = 0.0, pred_sum2 = 0.0, pred_min = 0.0, pred_total = 0.0;   // host copy as of the last verified batch
-    uint32_t pred_backoff = 0;    // batches that stay on the pilot plan after a prediction failed verification
-    uint32_t pred_failures = 0;
-    // screened plans that ended in an overflowing suspect / record / candidate list (rows crowded within the screen's error of
-    // every query's K-th score: DESIGN.md 4.1): after two in a row the table's recalls start on the exact scan for a while
-    uint32_t screen_overflow_streak = 0, screen_backoff = 0;
+    // what is built from the rows and what the plans learn about them (table_state.hpp: lifetimes, update rules, locking)
+    mutable pg::TableDerived derived;
+    mutable pg::TableLearned learned;
 };
 
 // rank model weights resident in HBM (rank_mlp.hip loads them)
@@ -516,7 +470,7 @@ int recall_batches_locked(pg_ctx* ctx, const pg_table* t, const float* d_queries
 int index_plan_prepare(RecallJob* j);
 int index_plan_enqueue(RecallJob* j, uint32_t status_words);
 int index_plan_check(RecallJob* j, bool* ok);
-// recall.hip: the checks of pg_recall_topk_where and pg_index_recall_topk_where, in this order, named after `who` (t: the table
+// recall_filter.hip: the checks of pg_recall_topk_where and pg_index_recall_topk_where, in this order, named after `who` (t: the table
 // searched); on success *f is the filter.  recall_where_locked: its search, never through an index (caller holds ctx->mu and the
 // table's shared lock; device queries and outputs, host counts [nq] or NULL); where_pad_launch: an answer of no admitted row.
 int where_check(const char* who, const pg_ctx* ctx, const pg_table* t, const pg_features* fs, int column, int op, long long value,
@@ -529,7 +483,7 @@ struct WhereId {
     const pg_where* w = nullptr;
     uint64_t epoch = 0;
 };
-// recall.hip: pg_table_view_create behind its checks (caller holds ctx->mu and the table's shared lock; synchronises)
+// recall_filter.hip: pg_table_view_create behind its checks (caller holds ctx->mu and the table's shared lock; synchronises)
 int view_create_locked(const char* who, pg_ctx* ctx, const pg_table* t, const RowFilter& f, pg_table** out_view);
 int recall_where_locked(pg_ctx* ctx, const pg_table* t, RowFilter f, int metric, const float* d_q, uint32_t nq, uint32_t k,
                         uint64_t* d_rows, float* d_sc, uint32_t* out_count);
@@ -587,8 +541,14 @@ int launch_select(pg_ctx* ctx, uint32_t nq, const uint64_t* in, uint64_t* out, u
                   uint32_t cap, uint32_t k, int thr_only = 0, uint32_t* cnt_seen = nullptr);
 int final_launch(pg_ctx* ctx, const uint64_t* cand, const uint32_t* cnt, uint32_t cap, uint32_t nq, uint32_t k,
                  uint64_t row_offset, uint64_t* d_out_rows, float* d_out_scores, uint32_t* d_out_count);
-int ensure_table_stats(pg_ctx* ctx, const pg_table* tc);
-int ensure_table_nx(pg_ctx* ctx, const pg_table* tc);
+// recall_table.hip: the lazy builds of pg_table::derived (each takes g_table_state_mu itself: never call one with it held)
+int ensure_table_stats(pg_ctx* ctx, const pg_table* t);
+int ensure_table_nx(pg_ctx* ctx, const pg_table* t);
+// what the plans learnt about a table, as a copy taken under g_table_state_mu: how pg_table::learned is read (table_state.hpp)
+inline TableLearned table_learned(const pg_table* t) {
+    std::lock_guard<std::mutex> g(g_table_state_mu);
+    return t->learned;
+}
 // recall.hip's exact re-scoring (rescore_kernel) over per-query suspect lists susp[q * scap + i] of local rows, appending the keys of
 // rows whose score reaches thr[q] to cand[q * cap + ...]; the squared-Euclidean |q|^2 chain and the final sign flip (index.hip)
 int rescore_launch(pg_ctx* ctx, uint32_t dim, bool l2, const float* tab, const float* d_queries, const float* thr, const uint32_t* susp,
@@ -598,7 +558,7 @@ int query_norm2_launch(pg_ctx* ctx, const float* d_queries, uint32_t nq, uint32_
 int negate_launch(pg_ctx* ctx, float* d_v, uint64_t n);
 // recall_i4.hip (caller holds ctx->mu)
 constexpr uint32_t kI4MaxQueries = 4;
-int ensure_table_i4(pg_ctx* ctx, const pg_table* tc);
+int ensure_table_i4(pg_ctx* ctx, const pg_table* t);
 int screen4_prep_launch(pg_ctx* ctx, const pg_table* t, const RecallScratch& rs);
 int screen4_launch(pg_ctx* ctx, const pg_table* t, const RecallScratch& rs, uint32_t nq, uint32_t row_begin, uint32_t row_end,
                    uint32_t cap4, const float* l2_nqv = nullptr);
@@ -608,7 +568,7 @@ constexpr uint32_t kI4mMaxQueries = 64;
 constexpr uint32_t kQ4mWords = kI4mMaxQueries * 32 + kI4mMaxQueries * 4 + 4;
 int screen4m_prep_launch(pg_ctx* ctx, const RecallScratch& rs, uint32_t nq);
 // recall_r2.hip (caller holds ctx->mu)
-int ensure_table_r2(pg_ctx* ctx, const pg_table* tc);
+int ensure_table_r2(pg_ctx* ctx, const pg_table* t);
 int rescreen16_prep_launch(pg_ctx* ctx, const pg_table* t, const RecallScratch& rs, uint32_t nq);
 int rescreen16_launch(pg_ctx* ctx, const pg_table* t, const RecallScratch& rs, uint32_t nq);
 int screen4m_launch(pg_ctx* ctx, const pg_table* t, const RecallScratch& rs, uint32_t nq, uint32_t row_begin, uint32_t row_end,

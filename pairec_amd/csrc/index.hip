@@ -1092,7 +1092,7 @@ int index_search(pg_ctx* ctx, const pg_index* ix, const SearchLists& li, const f
             const uint32_t blocks = grid(h_pw ? std::min<uint64_t>(most - (uint64_t)r * scap, scap) : scap);
             int rc3;
             if ((rc3 = rescore_launch(ctx, dim, l2, t->d, d_q, rs.thr, rs.susp, rs.susp_cnt, scap, rs.cnt, rs.cand[cur], rs.overflow, rs.cap,
-                                      nq, (uint32_t)ix->rows /* the gather's bound: the table's rows */, l2 ? t->d_nx : nullptr, l2 ? sb.nqv : nullptr, blocks)))
+                                      nq, (uint32_t)ix->rows /* the gather's bound: the table's rows */, l2 ? t->derived.d_nx : nullptr, l2 ? sb.nqv : nullptr, blocks)))
                 return rc3;
             // (a round without suspects selects the kept list again: the same K keys, the same threshold)
             if ((rc3 = launch_select(ctx, nq, rs.cand[cur], rs.cand[cur ^ 1], rs.cnt, rs.thr, rs.cap, k, 0))) return rc3;

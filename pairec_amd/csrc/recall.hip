@@ -70,7 +70,7 @@ struct ScanArgs {
     uint32_t group_q;        // > 0: blockIdx.y selects a group of group_q queries (of nq in all) — one launch serves
                              // every group of a screened recall's exact seed scan instead of one launch per group
     // squared-Euclidean recall (scan_kernel<…, L2 = true>): a row·query pair is ranked by -d = fmaf(2, ip, -(|x|^2 + |q|^2))
-    const float* nx;         // [rows + 64] |x|^2 of every row (k-ascending fmaf chain; pg_table::d_nx)
+    const float* nx;         // [rows + 64] |x|^2 of every row (k-ascending fmaf chain; TableDerived::d_nx)
     const float* nqv;        // [nq] |q|^2 of every query
     RowFilter filter;        // rows that fail it are no candidates (col = nullptr: none)
 };
@@ -393,7 +393,7 @@ constexpr int kScreenMaxNQB = 8;                // 8 x 32 = 256 queries per pass
 constexpr int kScreenLds = 163840;              // the whole LDS of a CU: ring (128 KiB) + staging (32 KiB)
 
 struct ScreenArgs {
-    const void* tab16;        // shadow of the table: bf16 (pg_table::d16) or int8 (pg_table::d8)
+    const void* tab16;        // shadow of the table: bf16 (TableDerived::d16) or int8 (TableDerived::d8)
     const uint4* qb16;        // [NQB][KS][64] B fragments: 8 bf16 (KS = DIM/16) or 16 int8 (KS = DIM/32) per lane
     const float* thr_screen;  // [256] bf16: thr - eps, rounded down; int8: the same in integer dot units (int32 bits)
     uint32_t* susp_cnt;       // [256] suspects per query of this launch
@@ -401,7 +401,7 @@ struct ScreenArgs {
     uint32_t* overflow;
     uint32_t cap, nq, rb_begin, rb_end, row_end, stride, perm_mul, perm_mod;
     // bf16 only: the bound is relative to the row's norm — eps = eps_unit[q] x (largest row norm of the 32-row block)
-    const float* blk_norm2;   // [blocks] largest row norm^2 per physical 32-row block (pg_table::dnorm2)
+    const float* blk_norm2;   // [blocks] largest row norm^2 per physical 32-row block (TableDerived::dnorm2)
     const float* eps_unit;    // [256] 0.008 ||q|| (inflated); thr_screen then carries thr itself (or -inf)
     // query halves (int8, > 128 queries): hit records instead of staged (row, query) pairs — see kRecBytes
     char* rec;                // [waves][rec_cap] records of kRecBytes: one region per wave of the launch
@@ -412,7 +412,7 @@ struct ScreenArgs {
     uint32_t early_share;     // 8-wave variants: share (x 1024) of a SIMD's blocks that goes to its older wave; 512 = even
     // squared-Euclidean recall on the int8 screen (L2 = true, <= 128 queries): a pair is a suspect iff
     // I >= floor(A_q + B_q * min|x|^2 of the block) - 2, with thr_screen = A_q (float) and l2_b = B_q (screen_thr8_l2_kernel)
-    const float* blk_nxmin;   // [blocks] smallest |x|^2 of every physical 32-row block (pg_table::d_nxmin)
+    const float* blk_nxmin;   // [blocks] smallest |x|^2 of every physical 32-row block (TableDerived::d_nxmin)
     const float* l2_b;        // [256]
     const float* nx_rows;     // L2 = 2 (per-row test: g = 2 s_x s_q I - |x|^2 >= C'_q, thr_screen = C'_q, l2_b = 2 s_x s_q): |x|^2 of every row
 };
@@ -430,7 +430,7 @@ struct ScreenArgs {
 // without the LDS stage, were measured: 4.35 vs 3.1 ms per pass — with stores in flight in every second block the
 // counted waits over-wait all the time and the ring runs one piece deep.)
 constexpr uint32_t kRecBytes = 48;
-constexpr uint32_t kRecOvfWord = 1 + kMaxQueries + 1;       // rs.overflow[kRecOvfWord]: the overflow was one of the hit-record areas (they can grow: pg_table::rec_scale)
+constexpr uint32_t kRecOvfWord = 1 + kMaxQueries + 1;       // rs.overflow[kRecOvfWord]: the overflow was one of the hit-record areas (they can grow: TableLearned::rec_scale)
 
 // NQB query blocks of 32; WAVES waves per workgroup.  <=128 queries: 8 waves (2 per SIMD), ring of 4
 // pieces per wave; 256 queries: the 256 B-operand registers leave room for one wave per SIMD only, so
@@ -1240,7 +1240,7 @@ __global__ void screen_thr_kernel(const float* __restrict__ thr, const float* __
 // product I = sum X_i Q_i exactly.  For the true score s = sum x_i q_i (real arithmetic):
 //     s - s_x s_q I = sum (x_i - x^_i) q_i + sum x^_i (q_i - q^_i)
 //     |s - s_x s_q I| <= ||x - x^|| ||q|| + ||x^|| ||q - q^||  <=  R ||q|| + (N + R) ||q - q^||
-// with R = max row residual (pg_table::resid8, measured when the shadow is built), N = max row norm.  eps_q is
+// with R = max row residual (TableDerived::resid8, measured when the shadow is built), N = max row norm.  eps_q is
 // that bound plus 1e-5 N ||q|| for the rounding of the specification's fp32 fmaf chain (<= 128 * 2^-24 N ||q||).
 // A row can reach thr only if  I >= (thr - eps_q) / (s_x s_q): the screen compares integers.
 // per call: int8 B fragments of the (zero-padded) queries, eps_q and the per-query scale s_q = max|q| / 127
@@ -1707,20 +1707,18 @@ int recall_job_prepare(RecallJob* j) {
     bool screen = j->nq > kn.screen_min && t->dim <= 128 && !kn.recall_exact && !j->exact_only;
     if (screen) {
         if ((rc = ensure_table_stats(ctx, t))) return rc;
-        if (!t->stats_valid || !t->all_finite) screen = false;      // no shadow (dim, memory) or non-finite rows
+        if (!t->derived.stats_valid || !t->derived.all_finite) screen = false;      // no shadow (dim, memory) or non-finite rows
     }
-    if (screen && t->screen_backoff) {                 // this table's screened plans kept overflowing: exact scan for now
-        std::lock_guard<std::mutex> build_guard(g_stats_build_mu);
-        pg_table* tm = const_cast<pg_table*>(t);
-        if (tm->screen_backoff) {
-            tm->screen_backoff--;
-            screen = false;
-        }
+    TableLearned seen;                                 // what the policy below reads of pg_table::learned: one snapshot
+    {
+        std::lock_guard<std::mutex> state_guard(g_table_state_mu);
+        if (screen && t->learned.screen_backed_off()) screen = false;   // this table's screened plans kept overflowing: exact scan for now
+        seen = t->learned;
     }
     // squared Euclidean: the int8 screen with per-block cutoffs for up to 128 queries (dim 128, int8 shadow); else the exact scan
-    if (j->l2 && !(screen && t->dim == 128 && t->shadow_is_i8 && j->nq <= 128 && !kn.l2_exact)) screen = false;
+    if (j->l2 && !(screen && t->dim == 128 && t->derived.shadow_is_i8 && j->nq <= 128 && !kn.l2_exact)) screen = false;
     // rows of (nearly) one norm: one cutoff per 32-row block; beyond: the per-row test (three VALU instructions per bound instead of half a one)
-    j->l2_per_row = j->l2 && screen && t->l2_slack > kn.l2_max_slack;
+    j->l2_per_row = j->l2 && screen && t->derived.l2_slack > kn.l2_max_slack;
     j->screen = screen;
     j->screen4 = j->screen4m = false;
     j->n_plans = 0;
@@ -1763,53 +1761,51 @@ int recall_job_prepare(RecallJob* j) {
         // (measured at 100M x 128, int8 pass 2.1 ms: uniform rows, lambda 0.8: 1.37 / 1.38 / 1.59 / 1.66 ms at 1..4
         // queries; Gaussian rows, lambda 1.3: 1.46 / 1.59 / 1.78 / 2.02 — every query re-scores its own suspects)
         static const double kLamScale[kI4MaxQueries] = {1.0, 1.0, 0.88, 0.7};
-        j->screen4 = t->i4_ok && (double)t->lam4 <= kn.i4_max_lambda * kLamScale[j->nq - 1];
+        j->screen4 = t->derived.i4_ok && (double)t->derived.lam4 <= kn.i4_max_lambda * kLamScale[j->nq - 1];
     }
     // 1 .. 64 queries, inner product, int8 main shadow: the same 4-bit shadow through the matrix pipe, suspects thinned on the int8
     // shadow (recall_i4m.hip) — also for one or two queries (1.08 against the vector screen's 1.17 ms per 100 M rows: its int8 stage
     // re-scores a twentieth of the suspects)
-    if (screen && !j->l2 && t->dim == 128 && t->shadow_is_i8 && j->nq >= kn.i4m_min_queries && j->nq <= kI4mMaxQueries &&
+    if (screen && !j->l2 && t->dim == 128 && t->derived.shadow_is_i8 && j->nq >= kn.i4m_min_queries && j->nq <= kI4mMaxQueries &&
         j->nq <= kn.i4m_max_queries && j->plans[0] == kPilot && !kn.no_screen_i4m && rows >= kn.i4_min_rows) {
         if ((rc = ensure_table_i4(ctx, t))) return rc;
         // every pair the 4-bit stage lets through is one random 128-B read (~35 G/s in rescreen8_kernel): beyond i4m_max_pairs of them per pass
         // the int8 shadow's wider stream is the shorter pass.  The count per query is the table's own running average.
         // (two query blocks: the 4-bit stage is vector-ALU-bound, 1.5 instead of 1.2 ms per 100 M rows — the budget shrinks with the gain)
-        j->screen4m = t->i4_ok && (double)t->lam4 <= kn.i4m_max_lambda &&
-                      (double)t->i4m_pairs * j->nq <= kn.i4m_max_pairs * (j->nq > 32 ? 0.7 : 1.0);
+        j->screen4m = t->derived.i4_ok && (double)t->derived.lam4 <= kn.i4m_max_lambda &&
+                      (double)seen.i4m_pairs * j->nq <= kn.i4m_max_pairs * (j->nq > 32 ? 0.7 : 1.0);
         if (j->screen4m) j->screen4 = false;
     }
     // crowded rows (clustered embeddings: many suspects per answer): the int8 screen's suspects pass a two-digit refinement on the
     // residual shadow before the exact re-scoring (recall_r2.hip); passes with a 4-bit stage have their own int8 stage
     j->stage2 = false;
-    if (screen && !j->l2 && t->dim == 128 && t->shadow_is_i8 && !j->screen4m && !j->screen4 && !kn.no_r2 &&
-        (double)t->wide_susp > kn.r2_min_factor * (double)j->k) {
+    if (screen && !j->l2 && t->dim == 128 && t->derived.shadow_is_i8 && !j->screen4m && !j->screen4 && !kn.no_r2 &&
+        (double)seen.wide_susp > kn.r2_min_factor * (double)j->k) {
         if ((rc = ensure_table_r2(ctx, t))) return rc;
-        j->stage2 = t->r2_ok;
+        j->stage2 = t->derived.r2_ok;
     }
     // the threshold model: observe with every pilot-plan batch of a big int8-screened table; predict once the observed
     // quantile is tight (plan 0)
     j->predict = j->pred_observe = false;
     // (batches of <= 4 queries too: their full pass — the 4-bit shadow's — takes the same float thresholds, and the pilot's five
     //  launches are 0.15 ms of a lone request's 1.45)
-    if (screen && !j->l2 && !j->filter.col && t->dim == 128 && t->shadow_is_i8 && j->plans[0] == kPilot && !j->skip_pilot && !kn.no_predict &&
+    if (screen && !j->l2 && !j->filter.col && t->dim == 128 && t->derived.shadow_is_i8 && j->plans[0] == kPilot && !j->skip_pilot && !kn.no_predict &&
         rows >= kn.predict_min_rows && j->k < rows / 64) {
         if ((rc = ensure_pred_model(ctx, t))) return rc;
-        pg_table* tm = const_cast<pg_table*>(t);
-        std::lock_guard<std::mutex> build_guard(g_stats_build_mu);
-        if (t->pred_model) {
-            if (tm->pred_k != j->k) {                  // the observations belong to one K
-                PG_HIP(hipMemsetAsync(t->d_pred + 128 + 128 * 128, 0, 24, ctx->stream));
-                tm->pred_k = j->k;
-                tm->pred_n = tm->pred_sum = tm->pred_sum2 = 0.0;
-                tm->pred_backoff = 4;                  // (batches already in flight still report the old K's quantiles)
+        std::lock_guard<std::mutex> state_guard(g_table_state_mu);
+        TableLearned& ln = t->learned;
+        if (t->derived.pred_model) {
+            if (ln.pred_k != j->k) {                   // the observations belong to one K
+                PG_HIP(hipMemsetAsync(t->derived.d_pred + 128 + 128 * 128, 0, 24, ctx->stream));
+                ln.pred_change_k(j->k);
             }
             // (a mature model learns nothing from a lone request: its two launches and the 40-byte copy are spared)
-            j->pred_observe = !(j->nq <= (uint32_t)kI4MaxQueries && t->pred_n >= 8192.0);
-            if (tm->pred_backoff > 0) {
-                --tm->pred_backoff;
-            } else if (t->pred_n >= 1024.0) {
-                const double mean = t->pred_sum / t->pred_n;
-                const double var = t->pred_sum2 / t->pred_n - mean * mean;
+            j->pred_observe = !(j->nq <= (uint32_t)kI4MaxQueries && ln.pred_n >= 8192.0);
+            if (ln.pred_backoff > 0) {
+                --ln.pred_backoff;
+            } else if (ln.pred_n >= 1024.0) {
+                const double mean = ln.pred_sum / ln.pred_n;
+                const double var = ln.pred_sum2 / ln.pred_n - mean * mean;
                 const double sd = var > 0.0 ? sqrt(var) : 0.0;
                 // tight enough to beat the sample's own six-sigma margin (a threshold 3 % low in z doubles the rows that reach it)
                 if (mean > 0.5 && sd <= 0.025 * mean) {
@@ -1863,8 +1859,8 @@ struct PlanRun {                     // the launches of one plan (helper of reca
         const uint32_t nq = j->nq;
         if (j->screen && !thr_is_open && !exact_chunks) {
             ScreenArgs sa;
-            sa.tab16 = t->shadow_is_i8 ? (const void*)t->d8 : (const void*)t->d16;
-            sa.blk_norm2 = t->dnorm2;
+            sa.tab16 = t->derived.shadow_is_i8 ? (const void*)t->derived.d8 : (const void*)t->derived.d16;
+            sa.blk_norm2 = t->derived.dnorm2;
             sa.eps_unit = rs.eps;
             sa.qb16 = rs.qb16;
             sa.thr_screen = rs.thr_screen;
@@ -1881,21 +1877,22 @@ struct PlanRun {                     // the launches of one plan (helper of reca
             sa.perm_mod = j->sample_blocks;
             int rc2;
             // > 128 queries on the int8 shadow: the scan leaves hit records, decoded into the suspect lists below
-            const bool records = t->shadow_is_i8 && nq > 128;
+            const bool records = t->derived.shadow_is_i8 && nq > 128;
             sa.rec = nullptr;
             sa.rec_cnt = nullptr;
             sa.rec_cap = 0;
             sa.rec_pool = nullptr;
             sa.rec_pool_cap = sa.rec_waves = 0;
             sa.early_share = records ? ctx->knobs.screen_early_share : ctx->knobs.screen_early_share_narrow;
-            sa.blk_nxmin = j->l2 && !j->l2_per_row ? t->d_nxmin : nullptr;
-            sa.nx_rows = j->l2 && j->l2_per_row ? t->d_nx : nullptr;
+            sa.blk_nxmin = j->l2 && !j->l2_per_row ? t->derived.d_nxmin : nullptr;
+            sa.nx_rows = j->l2 && j->l2_per_row ? t->derived.d_nx : nullptr;
             sa.l2_b = j->l2 ? rs.thr_ref : nullptr;    // (no refinement step under this metric: its buffer carries B_q)
             const uint32_t rec_waves = (uint32_t)ctx->num_cus * 8u;
             if (records) {
                 // a region per wave: four times the share of 256 x K suspects a wave expects, never below the records the safe
                 // plan's bounded chunks can leave in one region
-                const uint64_t rsc = t->rec_scale ? t->rec_scale : 1;     // (tables whose batches overflowed these areas got larger ones)
+                // (tables whose batches overflowed these areas got larger ones.  A fresh snapshot: recall_job_check doubles it and the same plan runs again)
+                const uint64_t rsc = table_learned(t).rec_scale_eff();
                 uint32_t cap_w = (uint32_t)(((uint64_t)kMaxQueries * j->k * 4 * rsc / rec_waves + 255) / 256 * 256);
                 // (the safe plan's chunk — kCandSlack / 2 rows — with EVERY row a suspect of every query, e.g. a table in ascending
                 //  score order: 16 query blocks of 16 x 64 lanes = 1024 records per block, and the blocks of a SIMD's pair of waves split as screen_kernel splits
@@ -1942,19 +1939,19 @@ struct PlanRun {                     // the launches of one plan (helper of reca
                 last_was_i4m = true;
             } else {
                 last_was_i4m = false;
-                if ((rc2 = dispatch_screen(ctx, t->dim, t->shadow_is_i8, sa))) return rc2;
+                if ((rc2 = dispatch_screen(ctx, t->dim, t->derived.shadow_is_i8, sa))) return rc2;
                 if (records) {
                     screen_decode_kernel<<<rec_waves / 8 + sa.rec_pool_cap / kRecPoolSlice, 1024, 0, ctx->stream>>>(
                         sa.rec, sa.rec_cnt, sa.rec_cap, rec_waves, sa.rec_pool, sa.rec_pool_cap, rs.thr_screen, j->rows,
                                                                             rs.susp_cnt, rs.susp, rs.cap, rs.overflow);
                     PG_HIP(hipGetLastError());
                 }
-                j->scan_bytes += (uint64_t)cb * kPieceRows * t->dim * (t->shadow_is_i8 ? 1 : 2);
+                j->scan_bytes += (uint64_t)cb * kPieceRows * t->dim * (t->derived.shadow_is_i8 ? 1 : 2);
             }
             j->scanned_rows += (uint64_t)cb * kPieceRows;
             // exact re-scoring of the launch's suspects → candidate keys (grid.x strides over each list)
             const dim3 rg(i4 ? screen4_rescore_blocks() : kRescoreBlocksPerQuery, nq);
-            const bool r2 = j->stage2 && t->shadow_is_i8 && !i4 && !i4m && !j->l2 && t->dim == 128;
+            const bool r2 = j->stage2 && t->derived.shadow_is_i8 && !i4 && !i4m && !j->l2 && t->dim == 128;
             if (r2) {
                 // crowded rows: the suspects once more with two more digits (recall_r2.hip); what is left goes to the exact re-scoring
                 if ((rc2 = rescreen16_launch(ctx, t, rs, nq))) return rc2;
@@ -1963,7 +1960,7 @@ struct PlanRun {                     // the launches of one plan (helper of reca
                                                                  rs.cnt, rs.cand[cur], rs.overflow, rs.cap, j->rows, nullptr, nullptr, j->filter);
             } else if (j->l2)
                 rescore_kernel<128, true><<<rg, 256, 0, ctx->stream>>>(t->d, rs.qpad, rs.thr, rs.susp, rs.susp_cnt, rs.cap, rs.cnt,
-                                                                       rs.cand[cur], rs.overflow, scap, j->rows, t->d_nx, rs.pred_ms, j->filter);
+                                                                       rs.cand[cur], rs.overflow, scap, j->rows, t->derived.d_nx, rs.pred_ms, j->filter);
             else if (t->dim == 64)
                 rescore_kernel<64><<<rg, 256, 0, ctx->stream>>>(t->d, rs.qpad, rs.thr, rs.susp, rs.susp_cnt, rs.cap,
                                                                 rs.cnt, rs.cand[cur], rs.overflow, scap, j->rows, nullptr, nullptr, j->filter);
@@ -1996,7 +1993,7 @@ struct PlanRun {                     // the launches of one plan (helper of reca
             a.stride = st;
             a.perm_mul = j->perm_mul;
             a.perm_mod = j->sample_blocks;
-            a.nx = j->l2 ? t->d_nx : nullptr;
+            a.nx = j->l2 ? t->derived.d_nx : nullptr;
             a.nqv = j->l2 ? rs.pred_ms : nullptr;
             a.filter = j->filter;
             int rc2;
@@ -2014,10 +2011,10 @@ struct PlanRun {                     // the launches of one plan (helper of reca
         int rc2;
         if ((rc2 = launch_select(ctx, j->nq, rs.cand[cur], rs.cand[cur ^ 1], rs.cnt, rs.thr, rs.cap, kk, 0, rs.cnt_seen))) return rc2;
         if (j->screen && !no_i8 && !(last && !j->l2)) {
-            if (j->l2) screen_thr8_l2_kernel<<<1, kMaxQueries, 0, ctx->stream>>>(rs.thr, rs.eps, rs.qscale, rs.pred_ms, t->s8, t->max_norm,
+            if (j->l2) screen_thr8_l2_kernel<<<1, kMaxQueries, 0, ctx->stream>>>(rs.thr, rs.eps, rs.qscale, rs.pred_ms, t->derived.s8, t->derived.max_norm,
                                                                                 rs.thr_screen, rs.thr_ref, j->l2_per_row ? 1 : 0);
-            else if (t->shadow_is_i8) screen_thr8_kernel<<<1, kMaxQueries, 0, ctx->stream>>>(rs.thr, rs.eps, rs.qscale, t->s8, rs.thr_screen);
-            else screen_thr_kernel<<<1, kMaxQueries, 0, ctx->stream>>>(rs.thr, rs.eps, t->max_norm, rs.thr_screen);
+            else if (t->derived.shadow_is_i8) screen_thr8_kernel<<<1, kMaxQueries, 0, ctx->stream>>>(rs.thr, rs.eps, rs.qscale, t->derived.s8, rs.thr_screen);
+            else screen_thr_kernel<<<1, kMaxQueries, 0, ctx->stream>>>(rs.thr, rs.eps, t->derived.max_norm, rs.thr_screen);
             PG_HIP(hipGetLastError());
         }
         cur ^= 1;
@@ -2028,8 +2025,8 @@ struct PlanRun {                     // the launches of one plan (helper of reca
         int rc2;
         if ((rc2 = launch_select(ctx, j->nq, rs.cand[cur], rs.cand[cur ^ 1], rs.cnt, rs.thr, rs.cap, kk, 1))) return rc2;
         if (j->screen) {
-            if (t->shadow_is_i8) screen_thr8_kernel<<<1, kMaxQueries, 0, ctx->stream>>>(rs.thr, rs.eps, rs.qscale, t->s8, rs.thr_screen);
-            else screen_thr_kernel<<<1, kMaxQueries, 0, ctx->stream>>>(rs.thr, rs.eps, t->max_norm, rs.thr_screen);
+            if (t->derived.shadow_is_i8) screen_thr8_kernel<<<1, kMaxQueries, 0, ctx->stream>>>(rs.thr, rs.eps, rs.qscale, t->derived.s8, rs.thr_screen);
+            else screen_thr_kernel<<<1, kMaxQueries, 0, ctx->stream>>>(rs.thr, rs.eps, t->derived.max_norm, rs.thr_screen);
             PG_HIP(hipGetLastError());
         }
         return PG_OK;
@@ -2092,9 +2089,9 @@ int recall_job_enqueue(RecallJob* j) {
     r.no_i8 = plan == kPredict && j->screen4;
     if (j->screen) {
         if (!r.no_i8) {
-            if (t->shadow_is_i8)
+            if (t->derived.shadow_is_i8)
                 screen_prep8_kernel<<<j->nq <= 32 ? 1u : (j->nq <= 64 ? 2u : (j->nq <= 128 ? 4u : 8u)), 128, 0, ctx->stream>>>(
-                    rs.qpad, t->dim, t->max_norm, t->resid8, rs.qb16, rs.eps, rs.qscale,
+                    rs.qpad, t->dim, t->derived.max_norm, t->derived.resid8, rs.qb16, rs.eps, rs.qscale,
                     j->nq > 128 && !j->l2 ? 1u : 0u);     // grid = the scan's NQB x QH; wide: dispatch_screen's query halves
             else
                 screen_prep_kernel<<<(kScreenMaxNQB * (t->dim / 16) * 64 + 255) / 256, 256, 0, ctx->stream>>>(
@@ -2111,7 +2108,7 @@ int recall_job_enqueue(RecallJob* j) {
     const bool observe = j->pred_observe && (plan == kPilot || plan == kPredict);
     if (observe || plan == kPredict) {
         // mean and sigma of every query's scores; under prediction the same launch writes the first thresholds
-        pred_query_kernel<<<j->nq, 128, 0, ctx->stream>>>(rs.qpad, t->d_pred, rs.pred_ms, plan == kPredict ? rs.thr : nullptr,
+        pred_query_kernel<<<j->nq, 128, 0, ctx->stream>>>(rs.qpad, t->derived.d_pred, rs.pred_ms, plan == kPredict ? rs.thr : nullptr,
                                                           (float)j->z_lo);
         PG_HIP(hipGetLastError());
     }
@@ -2127,7 +2124,7 @@ int recall_job_enqueue(RecallJob* j) {
     if (j->timers) PG_HIP(hipEventRecord((*j->events)[0], ctx->stream));
     if (plan == kPredict && !r.no_i8) {
         // no sample: the first thresholds are the model's (pred_query_kernel above), here in the int8 screen's units
-        screen_thr8_kernel<<<1, kMaxQueries, 0, ctx->stream>>>(rs.thr, rs.eps, rs.qscale, t->s8, rs.thr_screen);
+        screen_thr8_kernel<<<1, kMaxQueries, 0, ctx->stream>>>(rs.thr, rs.eps, rs.qscale, t->derived.s8, rs.thr_screen);
         PG_HIP(hipGetLastError());
     }
     if (plan == kPilot || plan == kPredict) {
@@ -2173,7 +2170,7 @@ int recall_job_enqueue(RecallJob* j) {
         // (not behind a predicted threshold: that one already sits tighter than what a quarter of the table can certify —
         //  rank ~1.1 K against k2's ~1.18 K — so the split would only add a launch boundary)
         const bool refine = j->screen && !j->l2 && !j->screen4 && !kn.no_refine && j->rows >= kn.refine_min_rows && nb_q >= 64 &&
-                            k2 < j->k && t->prefix_failures < 2 && plan != kPredict;
+                            k2 < j->k && table_learned(t).prefix_failures < 2 && plan != kPredict;
         if (refine) {
             if ((rc = r.scan_range(0, nb_q, 1, false, true))) return rc;
             if ((rc = r.refine(k2))) return rc;
@@ -2219,7 +2216,7 @@ int recall_job_enqueue(RecallJob* j) {
     if (observe) {
         // the K-th best scores that came out (rs.thr after the last refresh) as quantiles of the model; queries that
         // failed report 0 items and do not count.  The sums travel to the host with the status words.
-        double* stats = reinterpret_cast<double*>(t->d_pred + 128 + 128 * 128);
+        double* stats = reinterpret_cast<double*>(t->derived.d_pred + 128 + 128 * 128);
         pred_update_kernel<<<1, kMaxQueries, 0, ctx->stream>>>(rs.thr, rs.pred_ms, j->d_count, j->nq, j->k < j->rows ? j->k : j->rows, stats);
         PG_HIP(hipGetLastError());
     }
@@ -2232,7 +2229,7 @@ int recall_job_enqueue(RecallJob* j) {
         // of the refinement stage, [+ 4] the candidates the pass collected (select_kernel notes them before it keeps K)
         const uint32_t* const susp = j->susp_stat ? (r.last_was_i4m ? rs.susp2_cnt : rs.susp_cnt) : nullptr;
         status_pack_kernel<<<1, kMaxQueries, 0, ctx->stream>>>(
-            rs.overflow, j->nq, kRecOvfWord, observe ? reinterpret_cast<const uint32_t*>(t->d_pred + 128 + 128 * 128) : nullptr,
+            rs.overflow, j->nq, kRecOvfWord, observe ? reinterpret_cast<const uint32_t*>(t->derived.d_pred + 128 + 128 * 128) : nullptr,
             j->susp_stat && r.last_was_i4m ? rs.susp2_cnt + kI4mMaxQueries : nullptr, susp, j->susp_stat && r.last_was_r2 ? rs.susp2w_cnt : susp,
             j->susp_stat ? rs.cnt_seen : nullptr, rs.status);
         PG_HIP(hipGetLastError());
@@ -2263,7 +2260,7 @@ int recall_job_check(RecallJob* j, bool* ok_out) {
         uint32_t sc[4] = {0, 0, 0, 0};
         PG_HIP(hipMemcpy(sc, j->rs.susp_cnt, sizeof sc, hipMemcpyDeviceToHost));
         fprintf(stderr, "[pg] plan %d last screened launch: suspects of queries 0-3: %u %u %u %u (K = %u)\n", plan, sc[0], sc[1], sc[2], sc[3], j->k);
-        if (j->t->shadow_is_i8 && j->nq > 128 && scratch_peek(ctx, kSlotHitRecords)) {     // hit records: the fullest wave region, the spill pool
+        if (j->t->derived.shadow_is_i8 && j->nq > 128 && scratch_peek(ctx, kSlotHitRecords)) {     // hit records: the fullest wave region, the spill pool
             const uint32_t waves = (uint32_t)ctx->num_cus * 8u;
             std::vector<uint32_t> rc(waves + 1);
             PG_HIP(hipMemcpy(rc.data(), scratch_peek(ctx, kSlotHitRecords), rc.size() * 4, hipMemcpyDeviceToHost));
@@ -2287,33 +2284,26 @@ int recall_job_check(RecallJob* j, bool* ok_out) {
                 j->failed.push_back(q);
             }
     }
+    // what the verified batch teaches about the table: one locked section, the update rules are TableLearned's members
+    std::lock_guard<std::mutex> state_guard(g_table_state_mu);
+    TableLearned& ln = j->t->learned;
     if (j->observed || plan == kPredict) {
-        pg_table* tm = const_cast<pg_table*>(j->t);
-        std::lock_guard<std::mutex> build_guard(g_stats_build_mu);
-        if (j->observed && tm->pred_k == j->k) {
+        if (j->observed && ln.pred_k == j->k) {
             double st[5];
             memcpy(st, j->h_status + kPredStatsAt, sizeof st);
-            if (st[4] >= tm->pred_total) {              // (two streams report: keep the later snapshot)
-                tm->pred_total = st[4];
-                tm->pred_n = st[0];
-                tm->pred_sum = st[1];
-                tm->pred_sum2 = st[2];
-                tm->pred_min = st[3];
-            }
+            ln.pred_report(st);
         }
-        if (ctx->knobs.debug_scan && tm->pred_n > 0.0) {
-            const double mean = tm->pred_sum / tm->pred_n, var = tm->pred_sum2 / tm->pred_n - mean * mean;
+        if (ctx->knobs.debug_scan && ln.pred_n > 0.0) {
+            const double mean = ln.pred_sum / ln.pred_n, var = ln.pred_sum2 / ln.pred_n - mean * mean;
             fprintf(stderr, "[pg] plan %d %s: threshold model n = %.0f, z mean %.5f sd %.5f min %.5f (z_lo of this job %.5f)\n", plan,
-                    ok ? "held" : "FAILED", tm->pred_n, mean, var > 0 ? sqrt(var) : 0.0, tm->pred_min, j->z_lo);
+                    ok ? "held" : "FAILED", ln.pred_n, mean, var > 0 ? sqrt(var) : 0.0, ln.pred_min, j->z_lo);
         }
         if (plan == kPredict && !ok) {
             // the model's threshold was too high for some query: this table stays on the pilot plan for a while (the
             // whole batch re-runs when more than a handful failed — that must stay rare)
             // and the model starts over: what it learnt no longer describes the queries
-            tm->pred_failures++;
-            tm->pred_backoff = 64u << (tm->pred_failures < 6 ? tm->pred_failures : 6);
-            PG_HIP(hipMemsetAsync(tm->d_pred + 128 + 128 * 128, 0, 24, ctx->stream));
-            tm->pred_n = tm->pred_sum = tm->pred_sum2 = 0.0;
+            ln.pred_failed(true);
+            PG_HIP(hipMemsetAsync(j->t->derived.d_pred + 128 + 128 * 128, 0, 24, ctx->stream));
         }
     }
     if (j->screen) {
@@ -2322,16 +2312,13 @@ int recall_job_check(RecallJob* j, bool* ok_out) {
         // margin of every query's threshold — and the chunked fallback plans would screen the same crowd chunk by chunk (256
         // queries, 40 M such rows: 180 ms shuffled, 790 ms in ascending order, where the exact scan takes 30).  The job's
         // remaining plans run on the exact scan; two such batches in a row and the table's next 64 start there.
-        pg_table* tm = const_cast<pg_table*>(j->t);
-        std::lock_guard<std::mutex> build_guard(g_stats_build_mu);
-        if (j->h_status[0] != 0 && j->h_status[kI4mStatAt + 2] != 0 && (tm->rec_scale ? tm->rec_scale : 1) < ctx->knobs.max_rec_scale) {
+        if (j->h_status[0] != 0 && j->h_status[kI4mStatAt + 2] != 0 && ln.grow_rec_scale(ctx->knobs.max_rec_scale)) {
             // the hit-record areas of the 256-query pass were too small for this table (clustered rows: a query's whole cluster sits
             // within the screen's error of its K-th score — tens of suspects per answer where uniform rows have two): they grow, and
             // the same plan runs again; the table keeps the larger areas
-            tm->rec_scale = tm->rec_scale ? tm->rec_scale * 2 : 2;
             ctx->stats.recall_record_growths++;
             if (j->next_plan > 0) j->next_plan--;
-            if (ctx->knobs.debug_scan) fprintf(stderr, "[pg] plan %d overflowed its hit-record areas: scale -> %u, again\n", plan, tm->rec_scale);
+            if (ctx->knobs.debug_scan) fprintf(stderr, "[pg] plan %d overflowed its hit-record areas: scale -> %u, again\n", plan, ln.rec_scale);
         } else if (j->h_status[0] != 0) {
             ctx->stats.recall_screen_overflows++;
             j->screen = j->screen4 = j->screen4m = j->l2_per_row = false;
@@ -2340,18 +2327,13 @@ int recall_job_check(RecallJob* j, bool* ok_out) {
             //  growing-chunk plans meet a table in ascending order with a flood of candidates per chunk)
             for (int p = 0; p < j->n_plans; ++p)
                 if (j->plans[p] == kPilot && p < j->next_plan) j->next_plan = p;
-            if (++tm->screen_overflow_streak >= 2) tm->screen_backoff = 64;
+            ln.screen_overflowed();
         } else if (ok) {
-            tm->screen_overflow_streak = 0;
+            ln.screen_held();
         }
     }
-    if (j->susp_stat && ok && j->stat_wide) {
-        // (the int8 screen's suspects per query: decides whether the table's passes get the refinement stage)
-        pg_table* tm = const_cast<pg_table*>(j->t);
-        std::lock_guard<std::mutex> build_guard(g_stats_build_mu);
-        const float per_q = (float)j->h_status[kI4mStatAt + 1] / (float)j->nq;
-        tm->wide_susp = tm->wide_susp > 0.0f ? 0.75f * tm->wide_susp + 0.25f * per_q : per_q;
-    }
+    // (the int8 screen's suspects per query: decides whether the table's passes get the refinement stage)
+    if (j->susp_stat && ok && j->stat_wide) ln.note_wide_susp((float)j->h_status[kI4mStatAt + 1] / (float)j->nq);
     if (plan == kPredict && ok && j->susp_stat &&
         (double)j->h_status[kI4mStatAt + 4] > ctx->knobs.predict_max_factor * (double)j->k * j->nq) {
         // The predicted thresholds held but admitted far more than K rows per query as CANDIDATES (exact score >= threshold): on
@@ -2360,12 +2342,9 @@ int recall_job_check(RecallJob* j, bool* ok_out) {
         // answer; the refinement stage cannot reject what really reaches the threshold, while the sample's threshold leaves 7-15
         // suspects of which it keeps one).  Such a table goes back to the pilot plan; the model gets another try after an
         // exponentially growing number of batches.
-        pg_table* tm = const_cast<pg_table*>(j->t);
-        std::lock_guard<std::mutex> build_guard(g_stats_build_mu);
-        tm->pred_failures++;
-        tm->pred_backoff = 64u << (tm->pred_failures < 6 ? tm->pred_failures : 6);
+        ln.pred_failed(false);
         if (ctx->knobs.debug_scan) fprintf(stderr, "[pg] plan %d held with %.1f candidates per answer: pilot plan for the next %u batches\n", plan,
-                                           (double)j->h_status[kI4mStatAt + 4] / j->nq / j->k, tm->pred_backoff);
+                                           (double)j->h_status[kI4mStatAt + 4] / j->nq / j->k, ln.pred_backoff);
     }
     if (j->susp_stat && ok) {
         ctx->stats.recall_rescored += j->h_status[kI4mStatAt + 3];
@@ -2375,17 +2354,15 @@ int recall_job_check(RecallJob* j, bool* ok_out) {
     }
     if (j->screen4m && j->susp_stat && ok) {
         // what the 4-bit stage lets through per query decides up to which batch size it beats the int8 shadow (recall_job_prepare)
-        pg_table* tm = const_cast<pg_table*>(j->t);
-        std::lock_guard<std::mutex> build_guard(g_stats_build_mu);
         const float per_q = (float)j->h_status[kI4mStatAt] / (float)j->nq;
-        tm->i4m_pairs = tm->i4m_pairs > 0.0f ? 0.75f * tm->i4m_pairs + 0.25f * per_q : per_q;
-        if (ctx->knobs.debug_scan) fprintf(stderr, "[pg] plan %d 4-bit stage: %.0f pairs per query (running %.0f)\n", plan, per_q, tm->i4m_pairs);
+        ln.note_i4m_pairs(per_q);
+        if (ctx->knobs.debug_scan) fprintf(stderr, "[pg] plan %d 4-bit stage: %.0f pairs per query (running %.0f)\n", plan, per_q, ln.i4m_pairs);
     }
     if (!ok) ctx->stats.recall_rescans++;
     if (ok && plan == kPredict) ctx->stats.recall_predicted++;
     // a refined threshold that fails verification on most of a batch says the head of the table is not representative
     // (ordered rows): after two such batches the table's recalls stop refining (a hint, not state anyone relies on)
-    if (!ok && (plan == kPilot || plan == kPredict) && j->refined && j->failed.size() > j->nq / 2) const_cast<pg_table*>(j->t)->prefix_failures++;
+    if (!ok && (plan == kPilot || plan == kPredict) && j->refined && j->failed.size() > j->nq / 2) ln.prefix_failures++;
     *ok_out = ok;
     return PG_OK;
 }

@@ -268,9 +268,9 @@ int recall_where_locked(pg_ctx* ctx, const pg_table* t, RowFilter f, int metric,
         ct.dim = t->dim;
         if (metric == 1) {
             if ((rc = ensure_table_nx(ctx, t))) return rc;
-            compact_gather_nx_kernel<<<(admitted + 64 + 255) / 256, 256, 0, ctx->stream>>>(t->d_nx, d_ids, admitted, d_cnx);
-            ct.d_nx = d_cnx;
-            ct.nx_valid = true;
+            compact_gather_nx_kernel<<<(admitted + 64 + 255) / 256, 256, 0, ctx->stream>>>(t->derived.d_nx, d_ids, admitted, d_cnx);
+            ct.derived.d_nx = d_cnx;
+            ct.derived.nx_valid = true;
         }
         PG_HIP(hipGetLastError());
         RecallOpts o;
@@ -279,7 +279,7 @@ int recall_where_locked(pg_ctx* ctx, const pg_table* t, RowFilter f, int metric,
         if ((rc = recall_batches_locked(ctx, &ct, d_q, nq, k, d_rows, d_sc, out_count, o))) return rc;
         if ((rc = compact_map_rows_launch(ctx, d_rows, (uint64_t)nq * k, d_ids, t->row_offset, admitted))) return rc;
         ct.d = nullptr;
-        ct.d_nx = nullptr;
+        ct.derived.d_nx = nullptr;
     } else {
         RecallOpts o;
         o.l2 = metric == 1;

@@ -272,36 +272,32 @@ __global__ __launch_bounds__(256) void table_quant4_kernel(const float* __restri
     }
 }
 
-std::mutex g_i4_build_mu;      // a table is shared by the contexts of a device: one of them builds its shadow
-
 }  // namespace
 
 // the 4-bit shadow of a dim-128 table whose int8 statistics are valid (lazily, on the first small-batch recall)
-int ensure_table_i4(pg_ctx* ctx, const pg_table* tc) {
-    pg_table* t = const_cast<pg_table*>(tc);
-    if (t->i4_ok || t->i4_failed) return PG_OK;
-    std::lock_guard<std::mutex> g(g_i4_build_mu);
-    if (t->i4_ok || t->i4_failed) return PG_OK;
-    if (t->dim != 128 || !t->stats_valid || !t->all_finite) { t->i4_failed = true; return PG_OK; }
+int ensure_table_i4(pg_ctx* ctx, const pg_table* t) {
+    std::lock_guard<std::mutex> state_guard(g_table_state_mu);
+    if (t->derived.i4_ok || t->derived.i4_failed) return PG_OK;
+    if (t->dim != 128 || !t->derived.stats_valid || !t->derived.all_finite) { t->derived.i4_failed = true; return PG_OK; }
     void* p;
     int rc;
     if ((rc = scratch_reserve(ctx, kSlotStatus, 4096, &p))) return rc;
     float* d_st = (float*)p + 320;
-    if (!t->d4) {
-        if (hipMalloc((void**)&t->d4, (t->rows + 64) * (size_t)64) != hipSuccess ||
-            hipMalloc((void**)&t->d4s, (t->rows + 64) * sizeof(uint32_t)) != hipSuccess) {
+    if (!t->derived.d4) {
+        if (hipMalloc((void**)&t->derived.d4, (t->rows + 64) * (size_t)64) != hipSuccess ||
+            hipMalloc((void**)&t->derived.d4s, (t->rows + 64) * sizeof(uint32_t)) != hipSuccess) {
             (void)hipGetLastError();
-            if (t->d4) (void)hipFree(t->d4);
-            t->d4 = nullptr;
-            t->d4s = nullptr;
-            t->i4_failed = true;                       // stay on the int8 screen
+            if (t->derived.d4) (void)hipFree(t->derived.d4);
+            t->derived.d4 = nullptr;
+            t->derived.d4s = nullptr;
+            t->derived.i4_failed = true;                       // stay on the int8 screen
             return PG_OK;
         }
-        PG_HIP(hipMemsetAsync(t->d4 + t->rows * (size_t)64, 0x88, 64 * (size_t)64, ctx->stream));
-        PG_HIP(hipMemsetAsync(t->d4s + t->rows, 0, 64 * sizeof(uint32_t), ctx->stream));
+        PG_HIP(hipMemsetAsync(t->derived.d4 + t->rows * (size_t)64, 0x88, 64 * (size_t)64, ctx->stream));
+        PG_HIP(hipMemsetAsync(t->derived.d4s + t->rows, 0, 64 * sizeof(uint32_t), ctx->stream));
     }
     PG_HIP(hipMemsetAsync(d_st, 0, 12, ctx->stream));
-    table_quant4_kernel<<<(uint32_t)ctx->num_cus * 16, 256, 0, ctx->stream>>>(t->d, t->rows, (uint32_t*)t->d4, t->d4s, d_st);
+    table_quant4_kernel<<<(uint32_t)ctx->num_cus * 16, 256, 0, ctx->stream>>>(t->d, t->rows, (uint32_t*)t->derived.d4, t->derived.d4s, d_st);
     PG_HIP(hipGetLastError());
     PG_HIP(hipMemcpyAsync(ctx->h_status + 320, d_st, 12, hipMemcpyDeviceToHost, ctx->stream));
     PG_HIP(hipStreamSynchronize(ctx->stream));
@@ -309,20 +305,20 @@ int ensure_table_i4(pg_ctx* ctx, const pg_table* tc) {
     memcpy(&rho2, ctx->h_status + 320, 4);
     memcpy(&r2, ctx->h_status + 321, 4);
     memcpy(&lam, ctx->h_status + 322, 4);
-    t->rho4 = sqrtf(rho2);                             // (diagnostic: 0.29 for a uniformly spread rounding error)
-    t->rmax4 = r2 * 1.000001f + 1e-6f * t->max_norm;
+    t->derived.rho4 = sqrtf(rho2);                             // (diagnostic: 0.29 for a uniformly spread rounding error)
+    t->derived.rmax4 = r2 * 1.000001f + 1e-6f * t->derived.max_norm;
     // mean over rows of the residual term in units of the score's spread ||x|| ||q|| / sqrt(dim): how far below the
     // K-th score the 4-bit bound reaches.  Uniform rows: 0.8, Gaussian rows: 1.3 (0.2 % / 0.5 % of the rows become
     // suspects at K / rows = 5e-5); beyond ~1.7 the re-scoring gathers more than the narrower shadow saves.
-    t->lam4 = t->rows ? lam / (float)t->rows * sqrtf((float)t->dim) : 0.0f;
+    t->derived.lam4 = t->rows ? lam / (float)t->rows * sqrtf((float)t->dim) : 0.0f;
     if (ctx->knobs.debug_scan)
-        fprintf(stderr, "[pg] 4-bit shadow: lambda %.3f, max rho %.3f, max residual %.4g (max norm %.4g)\n", t->lam4, t->rho4, t->rmax4, t->max_norm);
-    t->i4_ok = true;
+        fprintf(stderr, "[pg] 4-bit shadow: lambda %.3f, max rho %.3f, max residual %.4g (max norm %.4g)\n", t->derived.lam4, t->derived.rho4, t->derived.rmax4, t->derived.max_norm);
+    t->derived.i4_ok = true;
     return PG_OK;
 }
 
 int screen4_prep_launch(pg_ctx* ctx, const pg_table* t, const RecallScratch& rs) {
-    screen4_prep_kernel<<<1, 256, 0, ctx->stream>>>(rs.qpad, t->max_norm, t->rmax4, rs.q4);
+    screen4_prep_kernel<<<1, 256, 0, ctx->stream>>>(rs.qpad, t->derived.max_norm, t->derived.rmax4, rs.q4);
     PG_HIP(hipGetLastError());
     return PG_OK;
 }
@@ -345,13 +341,13 @@ int screen4_launch(pg_ctx* ctx, const pg_table* t, const RecallScratch& rs, uint
     a.l2c = nullptr;
     if (l2_nqv) {
         float* l2c = reinterpret_cast<float*>(rs.q4 + 4 * 32 + 16);       // behind the queries and their constants
-        screen4_l2_consts_kernel<<<1, 64, 0, ctx->stream>>>(l2_nqv, t->max_norm, l2c);
+        screen4_l2_consts_kernel<<<1, 64, 0, ctx->stream>>>(l2_nqv, t->derived.max_norm, l2c);
         PG_HIP(hipGetLastError());
-        a.nx = t->d_nx;
+        a.nx = t->derived.d_nx;
         a.l2c = l2c;
     }
-    a.d4 = reinterpret_cast<const u32x4*>(t->d4);
-    a.d4s = t->d4s;
+    a.d4 = reinterpret_cast<const u32x4*>(t->derived.d4);
+    a.d4s = t->derived.d4s;
     a.q4 = rs.q4;
     a.thr = rs.thr;
     a.susp_cnt = rs.susp_cnt;
@@ -360,7 +356,7 @@ int screen4_launch(pg_ctx* ctx, const pg_table* t, const RecallScratch& rs, uint
     a.cap4 = cap4;
     a.rows = rows;
     a.row_begin = row_begin;
-    a.h_cap = (t->max_norm + t->rmax4) * 1.000001f;
+    a.h_cap = (t->derived.max_norm + t->derived.rmax4) * 1.000001f;
     // a persistent grid of exactly the resident workgroups (the group walk is interleaved over all waves, so waves
     // that started late would leave a tail); 4 KiB of loads in flight per wave
     static int per_cu[kI4MaxQueries + 1] = {0, 0, 0, 0, 0};

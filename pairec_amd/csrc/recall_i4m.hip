@@ -63,7 +63,7 @@ constexpr uint32_t kQcAt = kI4mMaxQueries * 32;              // words: the per-q
 constexpr uint32_t kKappaAt = kQcAt + kI4mMaxQueries * 4;
 
 struct Screen4mArgs {
-    const char* d4;           // [rows + 64][64 B] nibbles (pg_table::d4)
+    const char* d4;           // [rows + 64][64 B] nibbles (TableDerived::d4)
     const uint32_t* d4s;      // [rows + 64] s_r (bf16, low half) | R_r (bf16, high half)
     const uint32_t* q4m;      // [64][32] int8 queries in plain order | [64][4] {s_q, beta_q, 8 sum(Q) as int bits, -} | kappa
     const float* thr;         // [>= nq] running thresholds
@@ -502,11 +502,11 @@ int screen4m_prep_launch(pg_ctx* ctx, const RecallScratch& rs, uint32_t nq) {
 int screen4m_launch(pg_ctx* ctx, const pg_table* t, const RecallScratch& rs, uint32_t nq, uint32_t row_begin, uint32_t row_end,
                     uint32_t cap1, bool susp2_clean) {
     Screen4mArgs a;
-    a.d4 = reinterpret_cast<const char*>(t->d4);
-    a.d4s = t->d4s;
+    a.d4 = reinterpret_cast<const char*>(t->derived.d4);
+    a.d4s = t->derived.d4s;
     a.q4m = rs.q4m;
     a.thr = rs.thr;
-    a.h_cap = (t->max_norm + t->rmax4) * 1.000001f;
+    a.h_cap = (t->derived.max_norm + t->derived.rmax4) * 1.000001f;
     a.susp_cnt = rs.susp_cnt;
     a.susp = rs.susp;
     a.overflow = rs.overflow;
@@ -532,11 +532,12 @@ int screen4m_launch(pg_ctx* ctx, const pg_table* t, const RecallScratch& rs, uin
     // a wave should walk ~10 chunks of 64 suspects (its gathers run a chunk ahead: a wave with two or three chunks spends its time
     // on the first round trip — 8 queries: 104 us with 256 blocks per query, the 4-bit stage's pass-through known from earlier
     // batches puts it at a quarter of that); never more than the chip holds at once
-    const double pairs = t->i4m_pairs > 0.0f ? (double)t->i4m_pairs : 170000.0;
+    const TableLearned seen = table_learned(t);
+    const double pairs = seen.i4m_pairs > 0.0f ? (double)seen.i4m_pairs : 170000.0;
     uint32_t s2_blocks = (uint32_t)(pairs / 64.0 / 10.0 / 4.0) + 1;
     if (s2_blocks > 2048u / nq) s2_blocks = 2048u / nq;
     if (s2_blocks < 8) s2_blocks = 8;
-    rescreen8_kernel<<<dim3(s2_blocks, nq), 256, 0, ctx->stream>>>(t->d8, rs.q4m, rs.thr_screen, rs.susp, rs.susp_cnt, cap1, (uint32_t)t->rows,
+    rescreen8_kernel<<<dim3(s2_blocks, nq), 256, 0, ctx->stream>>>(t->derived.d8, rs.q4m, rs.thr_screen, rs.susp, rs.susp_cnt, cap1, (uint32_t)t->rows,
                                                              rs.susp2, rs.susp2_cnt, rs.cap, rs.overflow, stat);
     PG_HIP(hipGetLastError());
     return PG_OK;

@@ -245,48 +245,44 @@ __global__ __launch_bounds__(256) void rescreen16_kernel(const int8_t* __restric
     if (cnt) flush();
 }
 
-std::mutex g_r2_build_mu;
-
 }  // namespace
 
 // the residual shadow of an int8-screened dim-128 table (lazily: the first batch after the table showed crowded rows)
-int ensure_table_r2(pg_ctx* ctx, const pg_table* tc) {
-    pg_table* t = const_cast<pg_table*>(tc);
-    if (t->r2_ok || t->r2_failed) return PG_OK;
-    std::lock_guard<std::mutex> g(g_r2_build_mu);
-    if (t->r2_ok || t->r2_failed) return PG_OK;
-    if (t->dim != 128 || !t->stats_valid || !t->all_finite || !t->shadow_is_i8 || !t->d8) { t->r2_failed = true; return PG_OK; }
+int ensure_table_r2(pg_ctx* ctx, const pg_table* t) {
+    std::lock_guard<std::mutex> state_guard(g_table_state_mu);
+    if (t->derived.r2_ok || t->derived.r2_failed) return PG_OK;
+    if (t->dim != 128 || !t->derived.stats_valid || !t->derived.all_finite || !t->derived.shadow_is_i8 || !t->derived.d8) { t->derived.r2_failed = true; return PG_OK; }
     void* p;
     int rc;
     if ((rc = scratch_reserve(ctx, kSlotStatus, 4096, &p))) return rc;
     float* d_st = (float*)p + 340;
-    if (!t->d8r) {
-        if (hipMalloc((void**)&t->d8r, (t->rows + 64) * (size_t)128) != hipSuccess) {
+    if (!t->derived.d8r) {
+        if (hipMalloc((void**)&t->derived.d8r, (t->rows + 64) * (size_t)128) != hipSuccess) {
             (void)hipGetLastError();
-            t->d8r = nullptr;
-            t->r2_failed = true;                       // no memory: the suspects go to the exact re-scoring as before
+            t->derived.d8r = nullptr;
+            t->derived.r2_failed = true;                       // no memory: the suspects go to the exact re-scoring as before
             return PG_OK;
         }
-        PG_HIP(hipMemsetAsync(t->d8r + t->rows * (size_t)128, 0, 64 * (size_t)128, ctx->stream));
+        PG_HIP(hipMemsetAsync(t->derived.d8r + t->rows * (size_t)128, 0, 64 * (size_t)128, ctx->stream));
     }
-    t->s8r = t->s8 / 254.0f;
+    t->derived.s8r = t->derived.s8 / 254.0f;
     PG_HIP(hipMemsetAsync(d_st, 0, 4, ctx->stream));
-    table_quant8r_kernel<<<(uint32_t)ctx->num_cus * 16, 256, 0, ctx->stream>>>(t->d, t->rows, t->s8, t->s8r, t->d8r, d_st);
+    table_quant8r_kernel<<<(uint32_t)ctx->num_cus * 16, 256, 0, ctx->stream>>>(t->d, t->rows, t->derived.s8, t->derived.s8r, t->derived.d8r, d_st);
     PG_HIP(hipGetLastError());
     PG_HIP(hipMemcpyAsync(ctx->h_status + 340, d_st, 4, hipMemcpyDeviceToHost, ctx->stream));
     PG_HIP(hipStreamSynchronize(ctx->stream));
     float r2;
     memcpy(&r2, ctx->h_status + 340, 4);
     // (accumulated in fp32 from fp32 residuals: a relative 1e-2 and an absolute 1e-7 N cover that many times over)
-    t->resid2 = sqrtf(r2) * 1.01f + 1e-7f * t->max_norm;
+    t->derived.resid2 = sqrtf(r2) * 1.01f + 1e-7f * t->derived.max_norm;
     if (ctx->knobs.debug_scan)
-        fprintf(stderr, "[pg] residual shadow: s8r %.4g, max second residual %.4g (first: %.4g)\n", t->s8r, t->resid2, t->resid8);
-    t->r2_ok = true;
+        fprintf(stderr, "[pg] residual shadow: s8r %.4g, max second residual %.4g (first: %.4g)\n", t->derived.s8r, t->derived.resid2, t->derived.resid8);
+    t->derived.r2_ok = true;
     return PG_OK;
 }
 
 int rescreen16_prep_launch(pg_ctx* ctx, const pg_table* t, const RecallScratch& rs, uint32_t nq) {
-    rescreen16_prep_kernel<<<(nq + 63) / 64, 256, 0, ctx->stream>>>(rs.qpad, t->max_norm, t->resid2, rs.q16);
+    rescreen16_prep_kernel<<<(nq + 63) / 64, 256, 0, ctx->stream>>>(rs.qpad, t->derived.max_norm, t->derived.resid2, rs.q16);
     PG_HIP(hipGetLastError());
     return PG_OK;
 }
@@ -294,11 +290,12 @@ int rescreen16_prep_launch(pg_ctx* ctx, const pg_table* t, const RecallScratch& 
 // rs.susp ([nq][rs.cap], counts rs.susp_cnt) -> rs.susp2 ([nq][rs.cap], counts rs.susp2w_cnt, zeroed here)
 int rescreen16_launch(pg_ctx* ctx, const pg_table* t, const RecallScratch& rs, uint32_t nq) {
     PG_HIP(hipMemsetAsync(rs.susp2w_cnt, 0, sizeof(uint32_t) * kMaxQueries, ctx->stream));
-    const double per_q = t->wide_susp > 0.0f ? (double)t->wide_susp : 50000.0;
+    const TableLearned seen = table_learned(t);
+    const double per_q = seen.wide_susp > 0.0f ? (double)seen.wide_susp : 50000.0;
     uint32_t blocks = (uint32_t)(per_q / 64.0 / 10.0 / 4.0) + 1;
     if (blocks > 2048u / nq) blocks = 2048u / nq;
     if (blocks < 4) blocks = 4;
-    rescreen16_kernel<<<dim3(blocks, nq), 256, 0, ctx->stream>>>(t->d8, t->d8r, t->s8, t->s8r, rs.q16, rs.thr, rs.susp, rs.susp_cnt, rs.cap,
+    rescreen16_kernel<<<dim3(blocks, nq), 256, 0, ctx->stream>>>(t->derived.d8, t->derived.d8r, t->derived.s8, t->derived.s8r, rs.q16, rs.thr, rs.susp, rs.susp_cnt, rs.cap,
                                                                 (uint32_t)t->rows, rs.susp2, rs.susp2w_cnt, rs.cap, rs.overflow);
     PG_HIP(hipGetLastError());
     return PG_OK;

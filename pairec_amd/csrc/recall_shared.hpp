@@ -37,12 +37,9 @@ static uint32_t next_pow2(uint32_t x) {
     return p;
 }
 
-// recall_table.hip.  A table is shared by the contexts of a device (a coalescer's sibling), each under its own ctx->mu: this
-// mutex serialises the lazy builds — pg_table's shadows and statistics (stats_valid, shadow_failed, shadow_is_i8, d8, d16, dnorm2,
-// all_finite, max_norm, s8, resid8), its row norms (nx_valid, d_nx, d_nxmin, l2_slack) and its threshold model (pred_model,
-// d_pred) — and every later write of what the plans learn about the table: pred_*, screen_backoff, rec_scale, wide_susp, i4m_pairs.
-extern std::mutex g_stats_build_mu;
-int ensure_pred_model(pg_ctx* ctx, const pg_table* tc);      // builds the threshold model once per generation of the rows (dim 128)
+// recall_table.hip.  What it builds lives in pg_table::derived, what the plans learn from verified batches in pg_table::learned;
+// g_table_state_mu guards both, and `learned` is read through table_learned()'s snapshots only (table_state.hpp, common.hpp).
+int ensure_pred_model(pg_ctx* ctx, const pg_table* t);       // builds the threshold model once per generation of the rows (dim 128)
 // recall_filter.hip (caller holds ctx->mu; one launch each, nothing synchronises): *d_n += the rows of [0, rows) that `filter`
 // admits; d_rows[i] = offset + ids[d_rows[i]] for the n entries below `rows` (local rows of a compact table → the source's)
 int filter_count_launch(pg_ctx* ctx, const RowFilter& filter, uint64_t rows, unsigned long long* d_n);

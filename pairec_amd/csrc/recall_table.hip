@@ -1,7 +1,7 @@
 // recall_table.hip — what the table pass (recall.hip) derives from a table's rows, built lazily on first use and cached until
 // the next upload / fill: the int8 / bf16 shadow and the statistics of the screen's bound (ensure_table_stats), |x|^2 of every
 // row and the per-block minima of the squared-Euclidean recall (ensure_table_nx; service/recall/hologres_vector_recall_v2.go:23)
-// and the threshold predictor's model (ensure_pred_model).  The builds of one table are serialised by g_stats_build_mu.
+// and the threshold predictor's model (ensure_pred_model).  The builds are serialised by g_table_state_mu (table_state.hpp).
 #include "common.hpp"
 #include "recall_shared.hpp"
 
@@ -271,19 +271,13 @@ __global__ void pred_means_kernel(float* __restrict__ pred, uint64_t n_sample) {
 // statistics + shadow of a table (lazily, cached until the next upload / fill): int8 for dim 128 (two passes:
 // statistics, then quantisation with the table's scale), bf16 for dim 64.
 // Tables the screen cannot serve (other dims, no memory for the shadow) keep stats_valid = false.
-std::mutex g_stats_build_mu;   // a table is shared by the contexts of a device (a coalescer's sibling): one of them builds
-int ensure_table_stats(pg_ctx* ctx, const pg_table* tc) {
-    pg_table* t = const_cast<pg_table*>(tc);          // lazily computed cache
-    std::lock_guard<std::mutex> build_guard(g_stats_build_mu);
-    if (t->stats_valid || t->shadow_failed) return PG_OK;
-    t->i4_ok = t->i4_failed = false;                  // the 4-bit shadow (recall_i4.hip) follows the rows too
-    t->i4m_pairs = 0.0f;
-    t->rec_scale = 0;
-    t->r2_ok = t->r2_failed = false;                  // ... and the residual shadow (recall_r2.hip)
-    t->wide_susp = 0.0f;
-    t->pred_model = false;                            // ... and the threshold model
-    t->prefix_failures = 0;
-    if (t->dim != 64 && t->dim != 128) { t->shadow_failed = true; return PG_OK; }
+std::mutex g_table_state_mu;   // table_state.hpp: guards pg_table::derived and pg_table::learned of every table
+int ensure_table_stats(pg_ctx* ctx, const pg_table* t) {
+    std::lock_guard<std::mutex> state_guard(g_table_state_mu);
+    if (t->derived.stats_valid || t->derived.shadow_failed) return PG_OK;
+    t->derived.stats_rebuilt();                       // the 4-bit shadow, the residual shadow and the threshold model follow the rows too
+    t->learned.stats_rebuilt();
+    if (t->dim != 64 && t->dim != 128) { t->derived.shadow_failed = true; return PG_OK; }
     bool i8 = t->dim == 128;
     void* p;
     int rc;
@@ -302,120 +296,115 @@ int ensure_table_stats(pg_ctx* ctx, const pg_table* tc) {
         memcpy(&mx, ctx->h_status + 300, 4);
         memcpy(&amx, ctx->h_status + 302, 4);
         memcpy(&sumsq, ctx->h_status + 304, 4);
-        t->all_finite = ctx->h_status[301] == 0;
-        t->max_norm = sqrtf(mx) * 1.0001f;
-        t->s8 = fmaxf(amx / 127.0f, 1e-30f);
-        t->resid8 = 0.0f;
+        t->derived.all_finite = ctx->h_status[301] == 0;
+        t->derived.max_norm = sqrtf(mx) * 1.0001f;
+        t->derived.s8 = fmaxf(amx / 127.0f, 1e-30f);
+        t->derived.resid8 = 0.0f;
         // One scale for the table only works when the largest element is not far above the typical row: the int8
         // margin is ~ s8 sqrt(dim / 12) per unit of ||q|| for EVERY row, the bf16 margin 0.008 x the row's own norm.
         // Heavy tails or outliers (a Student-t table: int8 margin 130 x the bf16 one, every row a suspect, 560 ms per
         // recall instead of 2.4) go to the bf16 shadow with per-block norms.
         const float rms_norm = sqrtf(sumsq / (float)(t->rows ? t->rows : 1));
-        if (t->all_finite && t->s8 * sqrtf((float)t->dim / 12.0f) > 4.0f * kScreenEps * rms_norm) i8 = false;
+        if (t->derived.all_finite && t->derived.s8 * sqrtf((float)t->dim / 12.0f) > 4.0f * kScreenEps * rms_norm) i8 = false;
     }
     if (i8) {
-        if (!t->d8) {
+        if (!t->derived.d8) {
             const size_t bytes = (t->rows + 64) * (size_t)t->dim;
-            if (hipMalloc((void**)&t->d8, bytes) != hipSuccess) {
+            if (hipMalloc((void**)&t->derived.d8, bytes) != hipSuccess) {
                 (void)hipGetLastError();
-                t->d8 = nullptr;
-                t->shadow_failed = true;              // stay on the exact scan
+                t->derived.d8 = nullptr;
+                t->derived.shadow_failed = true;              // stay on the exact scan
                 return PG_OK;
             }
-            PG_HIP(hipMemsetAsync(t->d8 + t->rows * (size_t)t->dim, 0, 64 * (size_t)t->dim, ctx->stream));
+            PG_HIP(hipMemsetAsync(t->derived.d8 + t->rows * (size_t)t->dim, 0, 64 * (size_t)t->dim, ctx->stream));
         }
-        if (t->all_finite) {
-            table_quant8_kernel<128><<<grid, 256, 0, ctx->stream>>>(t->d, t->rows, t->s8, t->d8, d_max + 3);
+        if (t->derived.all_finite) {
+            table_quant8_kernel<128><<<grid, 256, 0, ctx->stream>>>(t->d, t->rows, t->derived.s8, t->derived.d8, d_max + 3);
             PG_HIP(hipGetLastError());
             PG_HIP(hipMemcpyAsync(ctx->h_status + 303, d_max + 3, 4, hipMemcpyDeviceToHost, ctx->stream));
             PG_HIP(hipStreamSynchronize(ctx->stream));
             float r2;
             memcpy(&r2, ctx->h_status + 303, 4);
             // (the residuals were accumulated in fp32: a relative 1e-3 and an absolute 1e-6 N cover that)
-            t->resid8 = sqrtf(r2) * 1.001f + 1e-6f * t->max_norm;
+            t->derived.resid8 = sqrtf(r2) * 1.001f + 1e-6f * t->derived.max_norm;
         }
-        t->shadow_is_i8 = true;
-        t->stats_valid = true;
+        t->derived.shadow_is_i8 = true;
+        t->derived.stats_valid = true;
         return PG_OK;
     }
     const size_t n_blk = (size_t)((t->rows + kPieceRows - 1) / kPieceRows) + 2;
-    if (!t->d16) {
+    if (!t->derived.d16) {
         const size_t bytes = (t->rows + 64) * (size_t)t->dim * 2;
-        if (hipMalloc((void**)&t->d16, bytes) != hipSuccess) {
+        if (hipMalloc((void**)&t->derived.d16, bytes) != hipSuccess) {
             (void)hipGetLastError();
-            t->d16 = nullptr;
-            t->shadow_failed = true;                  // stay on the exact scan
+            t->derived.d16 = nullptr;
+            t->derived.shadow_failed = true;                  // stay on the exact scan
             return PG_OK;
         }
-        PG_HIP(hipMemsetAsync(t->d16 + t->rows * (size_t)t->dim, 0, 64 * (size_t)t->dim * 2, ctx->stream));
+        PG_HIP(hipMemsetAsync(t->derived.d16 + t->rows * (size_t)t->dim, 0, 64 * (size_t)t->dim * 2, ctx->stream));
     }
-    if (!t->dnorm2 && hipMalloc((void**)&t->dnorm2, n_blk * sizeof(float)) != hipSuccess) {
+    if (!t->derived.dnorm2 && hipMalloc((void**)&t->derived.dnorm2, n_blk * sizeof(float)) != hipSuccess) {
         (void)hipGetLastError();
-        t->dnorm2 = nullptr;
-        t->shadow_failed = true;
+        t->derived.dnorm2 = nullptr;
+        t->derived.shadow_failed = true;
         return PG_OK;
     }
-    PG_HIP(hipMemsetAsync(t->dnorm2, 0, n_blk * sizeof(float), ctx->stream));
+    PG_HIP(hipMemsetAsync(t->derived.dnorm2, 0, n_blk * sizeof(float), ctx->stream));
     PG_HIP(hipMemsetAsync(d_max, 0, 8, ctx->stream));
-    if (t->dim == 64) table_shadow_kernel<64><<<grid, 256, 0, ctx->stream>>>(t->d, t->rows, t->d16, d_max, d_bad, t->dnorm2);
-    else table_shadow_kernel<128><<<grid, 256, 0, ctx->stream>>>(t->d, t->rows, t->d16, d_max, d_bad, t->dnorm2);
+    if (t->dim == 64) table_shadow_kernel<64><<<grid, 256, 0, ctx->stream>>>(t->d, t->rows, t->derived.d16, d_max, d_bad, t->derived.dnorm2);
+    else table_shadow_kernel<128><<<grid, 256, 0, ctx->stream>>>(t->d, t->rows, t->derived.d16, d_max, d_bad, t->derived.dnorm2);
     PG_HIP(hipGetLastError());
     PG_HIP(hipMemcpyAsync(ctx->h_status + 300, d_max, 8, hipMemcpyDeviceToHost, ctx->stream));
     PG_HIP(hipStreamSynchronize(ctx->stream));
     float mx;
     memcpy(&mx, ctx->h_status + 300, 4);
-    t->all_finite = ctx->h_status[301] == 0;
-    t->max_norm = sqrtf(mx) * 1.0001f;
-    t->shadow_is_i8 = false;
-    t->stats_valid = true;
+    t->derived.all_finite = ctx->h_status[301] == 0;
+    t->derived.max_norm = sqrtf(mx) * 1.0001f;
+    t->derived.shadow_is_i8 = false;
+    t->derived.stats_valid = true;
     return PG_OK;
 }
 
 // the threshold model of a table (dim 128): mean and covariance of a row sample, built once per generation of the rows
-int ensure_pred_model(pg_ctx* ctx, const pg_table* tc) {
-    pg_table* t = const_cast<pg_table*>(tc);
-    std::lock_guard<std::mutex> build_guard(g_stats_build_mu);
-    if (t->pred_model) return PG_OK;
+int ensure_pred_model(pg_ctx* ctx, const pg_table* t) {
+    std::lock_guard<std::mutex> state_guard(g_table_state_mu);
+    if (t->derived.pred_model) return PG_OK;
     const size_t bytes = (size_t)(128 + 128 * 128) * 4 + 5 * 8;   // mean | covariance (→ factor) | n, sum, sum2, min, total
-    if (!t->d_pred && hipMalloc((void**)&t->d_pred, bytes) != hipSuccess) {
+    if (!t->derived.d_pred && hipMalloc((void**)&t->derived.d_pred, bytes) != hipSuccess) {
         (void)hipGetLastError();
-        t->d_pred = nullptr;
+        t->derived.d_pred = nullptr;
         return PG_OK;                                 // no model: the pilot plan serves
     }
-    PG_HIP(hipMemsetAsync(t->d_pred, 0, bytes, ctx->stream));
+    PG_HIP(hipMemsetAsync(t->derived.d_pred, 0, bytes, ctx->stream));
     const uint64_t n_sample = t->rows < (1u << 20) ? t->rows : (1u << 20);
     const uint64_t stride = t->rows / n_sample;
-    pred_moments_kernel<<<(uint32_t)ctx->num_cus, 256, 0, ctx->stream>>>(t->d, t->rows, stride, n_sample, t->d_pred, t->d_pred + 128);
-    pred_finish_kernel<<<128, 128, 0, ctx->stream>>>(t->d_pred, n_sample);
-    pred_means_kernel<<<1, 128, 0, ctx->stream>>>(t->d_pred, n_sample);
+    pred_moments_kernel<<<(uint32_t)ctx->num_cus, 256, 0, ctx->stream>>>(t->d, t->rows, stride, n_sample, t->derived.d_pred, t->derived.d_pred + 128);
+    pred_finish_kernel<<<128, 128, 0, ctx->stream>>>(t->derived.d_pred, n_sample);
+    pred_means_kernel<<<1, 128, 0, ctx->stream>>>(t->derived.d_pred, n_sample);
     PG_HIP(hipGetLastError());
     PG_HIP(hipStreamSynchronize(ctx->stream));        // other contexts of the device use the model from their own streams
-    t->pred_model = true;
-    t->pred_k = 0;
-    t->pred_n = t->pred_sum = t->pred_sum2 = t->pred_total = 0.0;
-    t->pred_min = 1e300;
-    t->pred_backoff = 0;
+    t->derived.pred_model = true;
+    t->learned.model_rebuilt();
     return PG_OK;
 }
 
 // |x|^2 of every row, for the squared-Euclidean recall (lazily, cached until the next upload / fill; shared by the contexts
 // of a device like the shadows)
-int ensure_table_nx(pg_ctx* ctx, const pg_table* tc) {
-    pg_table* t = const_cast<pg_table*>(tc);
-    std::lock_guard<std::mutex> build_guard(g_stats_build_mu);
-    if (t->nx_valid) return PG_OK;
+int ensure_table_nx(pg_ctx* ctx, const pg_table* t) {
+    std::lock_guard<std::mutex> state_guard(g_table_state_mu);
+    if (t->derived.nx_valid) return PG_OK;
     const uint32_t nblocks = (uint32_t)((t->rows + kPieceRows - 1) / kPieceRows);
-    if (!t->d_nx) PG_HIP(hipMalloc((void**)&t->d_nx, (t->rows + 64) * sizeof(float)));
-    if (!t->d_nxmin) PG_HIP(hipMalloc((void**)&t->d_nxmin, ((size_t)nblocks + 64) * sizeof(float)));
-    PG_HIP(hipMemsetAsync(t->d_nx + t->rows, 0, 64 * sizeof(float), ctx->stream));
-    PG_HIP(hipMemsetAsync(t->d_nxmin + nblocks, 0, 64 * sizeof(float), ctx->stream));
-    row_norm2_kernel<<<(uint32_t)((t->rows + 255) / 256), 256, 0, ctx->stream>>>(t->d, t->rows, t->dim, t->d_nx);
+    if (!t->derived.d_nx) PG_HIP(hipMalloc((void**)&t->derived.d_nx, (t->rows + 64) * sizeof(float)));
+    if (!t->derived.d_nxmin) PG_HIP(hipMalloc((void**)&t->derived.d_nxmin, ((size_t)nblocks + 64) * sizeof(float)));
+    PG_HIP(hipMemsetAsync(t->derived.d_nx + t->rows, 0, 64 * sizeof(float), ctx->stream));
+    PG_HIP(hipMemsetAsync(t->derived.d_nxmin + nblocks, 0, 64 * sizeof(float), ctx->stream));
+    row_norm2_kernel<<<(uint32_t)((t->rows + 255) / 256), 256, 0, ctx->stream>>>(t->d, t->rows, t->dim, t->derived.d_nx);
     void* p;
     int rc;
     if ((rc = scratch_reserve(ctx, kSlotStatus, 4096, &p))) return rc;
     double* d_st = reinterpret_cast<double*>((char*)p + 2048);
     PG_HIP(hipMemsetAsync(d_st, 0, 16, ctx->stream));
-    block_nxmin_kernel<<<(nblocks + 255) / 256, 256, 0, ctx->stream>>>(t->d_nx, t->rows, t->d_nxmin, nblocks, d_st);
+    block_nxmin_kernel<<<(nblocks + 255) / 256, 256, 0, ctx->stream>>>(t->derived.d_nx, t->rows, t->derived.d_nxmin, nblocks, d_st);
     PG_HIP(hipGetLastError());
     double h_st[2] = {0.0, 0.0};
     PG_HIP(hipMemcpyAsync(h_st, d_st, 16, hipMemcpyDeviceToHost, ctx->stream));
@@ -424,9 +413,9 @@ int ensure_table_nx(pg_ctx* ctx, const pg_table* tc) {
     // units whose spread over the table is about |x| |q| / sqrt(dim) ~ mean|x|^2 / sqrt(dim) for queries like the rows.  Normalised
     // rows: 0.  N(0, 1) rows: 1.5 spreads — then nearly every block holds suspects and the exact scan is the faster pass.
     const double mean_nx = t->rows ? h_st[1] / (double)t->rows : 0.0;
-    t->l2_slack = mean_nx > 0.0 ? (float)((h_st[0] / (double)t->rows) * 0.5 / (mean_nx / sqrt((double)t->dim))) : 0.0f;
-    if (ctx->knobs.debug_scan) fprintf(stderr, "[pg] squared-Euclidean recall: per-block cutoff slack %.3f score spreads\n", t->l2_slack);
-    t->nx_valid = true;
+    t->derived.l2_slack = mean_nx > 0.0 ? (float)((h_st[0] / (double)t->rows) * 0.5 / (mean_nx / sqrt((double)t->dim))) : 0.0f;
+    if (ctx->knobs.debug_scan) fprintf(stderr, "[pg] squared-Euclidean recall: per-block cutoff slack %.3f score spreads\n", t->derived.l2_slack);
+    t->derived.nx_valid = true;
     return PG_OK;
 }
 
@@ -439,10 +428,10 @@ int pg_table_screen_info(pg_ctx* ctx, const pg_table* t, int* out_elem_bytes, fl
     std::lock_guard<std::mutex> g(ctx->mu);
     int rc;
     if ((rc = pg::ensure_table_stats(ctx, t))) return rc;
-    const bool screened = t->stats_valid && t->all_finite;
-    if (out_elem_bytes) *out_elem_bytes = screened ? (t->shadow_is_i8 ? 1 : 2) : 0;
-    if (out_scale) *out_scale = screened && t->shadow_is_i8 ? t->s8 : 0.0f;
-    if (out_resid) *out_resid = screened && t->shadow_is_i8 ? t->resid8 : 0.0f;
+    const bool screened = t->derived.stats_valid && t->derived.all_finite;
+    if (out_elem_bytes) *out_elem_bytes = screened ? (t->derived.shadow_is_i8 ? 1 : 2) : 0;
+    if (out_scale) *out_scale = screened && t->derived.shadow_is_i8 ? t->derived.s8 : 0.0f;
+    if (out_resid) *out_resid = screened && t->derived.shadow_is_i8 ? t->derived.resid8 : 0.0f;
     return PG_OK;
 }
 

@@ -129,6 +129,13 @@ int table_gather_locked(pg_ctx* ctx, const pg_table* t, const uint32_t* d_rows, 
     return PG_OK;
 }
 
+// after every write of the rows (upload / fill), under the writer's exclusive lock, once the write has completed
+static void table_rows_written(pg_table* t) {
+    std::lock_guard<std::mutex> g(g_table_state_mu);
+    t->derived.rows_written();
+    t->learned.rows_written();
+}
+
 }  // namespace pg
 
 extern "C" {
@@ -166,17 +173,12 @@ int pg_table_destroy(pg_ctx* ctx, pg_table* t) {
     if (!t) return PG_OK;
     std::lock_guard<std::mutex> g(ctx->mu);
     PG_HIP(hipStreamSynchronize(ctx->stream));
-    if (t->d) PG_HIP(hipFree(t->d));
-    if (t->d16) PG_HIP(hipFree(t->d16));
-    if (t->d8) PG_HIP(hipFree(t->d8));
-    if (t->d8r) PG_HIP(hipFree(t->d8r));
-    if (t->d4) PG_HIP(hipFree(t->d4));
-    if (t->d4s) PG_HIP(hipFree(t->d4s));
-    if (t->dnorm2) PG_HIP(hipFree(t->dnorm2));
-    if (t->d_pred) PG_HIP(hipFree(t->d_pred));
-    if (t->d_nx) PG_HIP(hipFree(t->d_nx));
-    if (t->d_nxmin) PG_HIP(hipFree(t->d_nxmin));
-    if (t->d_row_map) PG_HIP(hipFree(t->d_row_map));
+    hipError_t e = hipSuccess;
+    const auto free_one = [&e](void* p) { if (p && e == hipSuccess) e = hipFree(p); };
+    free_one(t->d);
+    free_one(t->d_row_map);
+    t->derived.for_each_owned(free_one);
+    PG_HIP(e);
     delete t;
     return PG_OK;
 }
@@ -205,9 +207,7 @@ int pg_table_fill_synthetic(pg_ctx* ctx, pg_table* t, uint64_t seed, int normali
     }
     PG_HIP(hipGetLastError());
     PG_HIP(hipStreamSynchronize(ctx->stream));
-    t->stats_valid = false;
-    t->screen_overflow_streak = t->screen_backoff = 0;
-    t->nx_valid = false;
+    pg::table_rows_written(t);
     return PG_OK;
 }
 
@@ -221,9 +221,7 @@ int pg_table_fill_gaussian(pg_ctx* ctx, pg_table* t, uint64_t seed, float sigma)
                                                                                      (double)sigma);
     PG_HIP(hipGetLastError());
     PG_HIP(hipStreamSynchronize(ctx->stream));
-    t->stats_valid = false;
-    t->screen_overflow_streak = t->screen_backoff = 0;
-    t->nx_valid = false;
+    pg::table_rows_written(t);
     return PG_OK;
 }
 
@@ -239,9 +237,7 @@ int pg_table_fill_mixture(pg_ctx* ctx, pg_table* t, uint64_t seed, uint32_t n_ce
     else pg::table_fill_mixture_kernel<128><<<blocks, 256, 0, ctx->stream>>>(t->d, t->rows, t->row_offset, seed, n_centres, ns);
     PG_HIP(hipGetLastError());
     PG_HIP(hipStreamSynchronize(ctx->stream));
-    t->stats_valid = false;
-    t->screen_overflow_streak = t->screen_backoff = 0;
-    t->nx_valid = false;
+    pg::table_rows_written(t);
     return PG_OK;
 }
 
@@ -258,9 +254,7 @@ int pg_table_upload(pg_ctx* ctx, pg_table* t, uint64_t row0, uint64_t nrows, con
     PG_HIP(hipMemcpyAsync(t->d + row0 * t->dim, host_rows, nrows * (size_t)t->dim * sizeof(float),
                           hipMemcpyHostToDevice, ctx->stream));
     PG_HIP(hipStreamSynchronize(ctx->stream));
-    t->stats_valid = false;
-    t->screen_overflow_streak = t->screen_backoff = 0;
-    t->nx_valid = false;
+    pg::table_rows_written(t);
     return PG_OK;
 }
 
@@ -288,48 +282,9 @@ int pg_table_swap(pg_ctx* ctx, pg_table* a, pg_table* b) {
     std::swap(a->row_offset, b->row_offset);
     std::swap(a->d_row_map, b->d_row_map);
     std::swap(a->map_offset, b->map_offset);
-    std::swap(a->stats_valid, b->stats_valid);
-    std::swap(a->all_finite, b->all_finite);
-    std::swap(a->max_norm, b->max_norm);
-    std::swap(a->d16, b->d16);
-    std::swap(a->d8, b->d8);
-    std::swap(a->dnorm2, b->dnorm2);
-    std::swap(a->shadow_is_i8, b->shadow_is_i8);
-    std::swap(a->s8, b->s8);
-    std::swap(a->resid8, b->resid8);
-    std::swap(a->shadow_failed, b->shadow_failed);
-    std::swap(a->d4, b->d4);
-    std::swap(a->d4s, b->d4s);
-    std::swap(a->i4_ok, b->i4_ok);
-    std::swap(a->i4_failed, b->i4_failed);
-    std::swap(a->rho4, b->rho4);
-    std::swap(a->rmax4, b->rmax4);
-    std::swap(a->lam4, b->lam4);
-    std::swap(a->i4m_pairs, b->i4m_pairs);
-    std::swap(a->rec_scale, b->rec_scale);
-    std::swap(a->d8r, b->d8r);
-    std::swap(a->s8r, b->s8r);
-    std::swap(a->resid2, b->resid2);
-    std::swap(a->r2_ok, b->r2_ok);
-    std::swap(a->r2_failed, b->r2_failed);
-    std::swap(a->wide_susp, b->wide_susp);
-    std::swap(a->prefix_failures, b->prefix_failures);
-    std::swap(a->d_pred, b->d_pred);
-    std::swap(a->d_nx, b->d_nx);
-    std::swap(a->d_nxmin, b->d_nxmin);
-    std::swap(a->l2_slack, b->l2_slack);
-    std::swap(a->nx_valid, b->nx_valid);
-    std::swap(a->pred_model, b->pred_model);
-    std::swap(a->pred_k, b->pred_k);
-    std::swap(a->pred_n, b->pred_n);
-    std::swap(a->pred_sum, b->pred_sum);
-    std::swap(a->pred_sum2, b->pred_sum2);
-    std::swap(a->pred_min, b->pred_min);
-    std::swap(a->pred_total, b->pred_total);
-    std::swap(a->pred_backoff, b->pred_backoff);
-    std::swap(a->pred_failures, b->pred_failures);
-    std::swap(a->screen_overflow_streak, b->screen_overflow_streak);
-    std::swap(a->screen_backoff, b->screen_backoff);
+    std::lock_guard<std::mutex> sg(pg::g_table_state_mu);
+    std::swap(a->derived, b->derived);               // shadows, statistics, model: they travel with the rows ...
+    std::swap(a->learned, b->learned);               // ... and so does what the plans learnt about them
     return PG_OK;
 }
 
