@@ -20,6 +20,7 @@
 #include "../../include/pairec_gpu.h"
 #include "scratch_layout.hpp"
 #include "table_state.hpp"
+#include "rank_model.hpp"     // pg_model
 
 namespace pg {
 
@@ -182,45 +183,7 @@ struct pg_table {
     mutable pg::TableLearned learned;
 };
 
-// rank model weights resident in HBM (rank_mlp.hip loads them)
-struct pg_model {
-    pg_model_kind kind;
-    int prec;
-    uint32_t d_user = 0, d_item = 0, h1 = 0, h2 = 0;           // DNN3
-    uint32_t nuf = 0, nif = 0, k = 0, th = 0, to = 0, vocab = 0;  // two-tower
-    float b3 = 0.f, fm_b = 0.f;
-    uint32_t n_out = 1;     // DNN3: heads on the shared trunk (PG_MODEL_DNN3_MULTI; kind is stored as PG_MODEL_DNN3)
-    float* b3v = nullptr;   // device [n_out] head biases (b3 = b3v[0])
-    // device buffers
-    float* w1u = nullptr;   // [d_user][h1] (DNN3) / uw1 (two-tower), operand-rounded fp32
-    float* b1 = nullptr;    // b1 / ub1
-    float* uw2 = nullptr;   // two-tower user layer 2
-    float* ub2 = nullptr;
-    void* w1p = nullptr;    // packed item-side layer 1
-    void* w2p = nullptr;    // packed layer 2
-    void* w1p_lo = nullptr; // PG_PREC_BF16X3: the lo fragments (inside the w1p / w2p allocations)
-    void* w2p_lo = nullptr;
-    // PG_PREC_F16X2 / PG_PREC_F16: prec is 2 (every BF16X3 buffer above is kept: the fallback) and f16_nprod 2 / 1
-    int f16_nprod = 0;
-    void* h_w1p = nullptr;  // scaled fp16 fragments (rank_2r.hip); the lo planes inside the same allocations
-    void* h_w2p = nullptr;
-    void* h_w1p_lo = nullptr;
-    void* h_w2p_lo = nullptr;
-    float* h_xs = nullptr;  // [kDIN] input-column factors
-    float* h_hs = nullptr;  // [h1] hidden-unit factors
-    unsigned long long* h_stats = nullptr;   // device [2]: tiles taken by the fp16 kernel, tiles re-served in BF16X3
-    mutable uint64_t f16_calls = 0, f16_calls_whole = 0;   // under the context's lock
-    pg_ctx* ctx = nullptr;
-    float* c1_shared = nullptr;   // two-tower: ib1
-    float* b2 = nullptr;
-    float* w3 = nullptr;    // DNN3 head(s): [n_out][h2]
-    float* fields = nullptr;          // two-tower: all field tables, one allocation
-    const float** d_field_emb = nullptr;
-    const float** d_field_lin = nullptr;
-    std::vector<void*> allocs;
-};
-
-// features.hip owns the columns; rank_mlp.hip reads them when it materialises item records
+// features.hip owns the columns; rank_mlp.hip reads them when it fills item records
 struct pg_features {
     uint64_t rows = 0;
     struct Column {
@@ -233,7 +196,7 @@ struct pg_features {
     std::vector<Column> cols;
 };
 
-// materialised item side of an FM + two-tower model (rank_mlp.hip): [rows + 1][kItemRowFloats] fp32
+// materialised item side of an FM + two-tower model (rank_entry.hip builds it, rank_mlp.hip fills it): [rows + 1][kItemRowFloats] fp32
 struct pg_item_rows {
     const pg_model* m = nullptr;
     const pg_features* fs = nullptr;
@@ -586,6 +549,11 @@ int rank_dnn3_dev_locked(pg_ctx* ctx, const pg_model* m, const pg_table* t, cons
                          const uint32_t* d_cand, const uint32_t* d_off, uint32_t n_req, uint32_t n_items,
                          float* d_out, size_t out_stride = 0);
 int fm2t_user_embedding_locked(pg_ctx* ctx, const pg_model* m, const float* d_user, uint32_t n_req, float* d_out);
+// candidates as per-item field ids (d_ifids), or as rows of item records (ir, d_cand)
+int rank_fm2t_dev_locked(pg_ctx* ctx, const pg_model* m, const float* d_user, const int32_t* d_ufids, const int32_t* d_ifids,
+                         const uint32_t* d_off, uint32_t n_req, uint32_t n_items, float* d_out, const pg_item_rows* ir = nullptr,
+                         const uint32_t* d_cand = nullptr);
+int item_rows_fill_locked(pg_ctx* ctx, pg_item_rows* ir, uint64_t row0, uint64_t nrows);
 int rank_fm2t_irows_dev_locked(pg_ctx* ctx, const pg_model* m, const pg_item_rows* ir, const float* d_user, const int32_t* d_ufids,
                                const uint32_t* d_cand, const uint32_t* d_off, uint32_t n_req, uint32_t n_items, float* d_out);
 int rank_fm2t_rows_dev_locked(pg_ctx* ctx, const pg_model* m, const pg_features* fs, const int32_t* item_field_cols,

@@ -48,7 +48,7 @@
 // bf16 MFMA rate and a unit round-off of 2^-11 instead of 2^-8: activations rounded ONCE to fp16 and weights as hi + lo fp16
 // (F16X2, two products per term) or rounded once as well (F16, one product) stay within ~3e-6 / ~4e-6 of the fp32 scores
 // (tests/test_f16_modes_cpu.py is the numpy statement of both).  What fp16 lacks is range, so every operand is scaled by an
-// exact power of two at load time (pg_model_load, rank_mlp.hip):
+// exact power of two at load time (pg_model_load: build_f16_operands, rank_model.hpp):
 //   E_k = floor(log2 max_j |W1[k][j]|)   per input column k of layer 1's item half   (0 for an all-zero row)
 //   F_i = floor(log2 max_j |W2[i][j]|)   per hidden unit i                           (0 for an all-zero row)
 //   "row-normalised units": wn = W * 2^-E (row maximum in [1, 2)), xn_k = x_k * 2^E_k — the products are unchanged.

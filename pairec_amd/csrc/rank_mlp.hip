@@ -906,139 +906,9 @@ static void launch_fm2t_user(pg_ctx* ctx, const pg_model* m, const float* d_user
 }  // namespace pg
 
 // ---------------------------------------------------------------------------------------------
-// host side: model blobs, weight pre-packing, launches
+// host side: launches (the model loader and the entry points are in rank_entry.hip)
 // ---------------------------------------------------------------------------------------------
 namespace pg {
-
-// Pack W[K][N] (row-major, k major) into MFMA B-fragment order, 1 KiB per (n-block, k-group).
-//   bf16: fragment (nbg, ks): lane (j,hk) holds W[ks*16 + 8*hk + e][nbg*32 + j], e = 0..7
-//   f32 : fragment (nbg, g8): lane (j,h)  holds W[g8*8 + 2*st + h][nbg*32 + j], st = 0..3
-//   split bf16 (prec 2): the bf16 layout twice — every hi fragment, then every lo fragment (lo = RNE(w - hi))
-static std::vector<uint8_t> pack_weights(const float* w, uint32_t K, uint32_t N, int prec) {
-    const uint32_t kg = prec ? K / 16 : K / 8;
-    const size_t plane = (size_t)(N / 32) * kg * 1024;
-    std::vector<uint8_t> out(plane * (prec == 2 ? 2 : 1));
-    for (uint32_t nbg = 0; nbg < N / 32; ++nbg)
-        for (uint32_t g = 0; g < kg; ++g) {
-            uint8_t* frag = out.data() + ((size_t)nbg * kg + g) * 1024;
-            for (uint32_t lane = 0; lane < 64; ++lane) {
-                const uint32_t j = lane & 31, hh = lane >> 5;
-                if (prec) {
-                    uint16_t* d = reinterpret_cast<uint16_t*>(frag + lane * 16);
-                    uint16_t* dl = reinterpret_cast<uint16_t*>(frag + plane + lane * 16);
-                    for (uint32_t e = 0; e < 8; ++e) {
-                        const float v = w[(size_t)(g * 16 + 8 * hh + e) * N + nbg * 32 + j];
-                        d[e] = f32_to_bf16_rne(v);
-                        if (prec == 2) dl[e] = f32_to_bf16_rne(v - bf16_to_f32(d[e]));
-                    }
-                } else {
-                    float* d = reinterpret_cast<float*>(frag + lane * 16);
-                    for (uint32_t st = 0; st < 4; ++st)
-                        d[st] = w[(size_t)(g * 8 + 2 * st + hh) * N + nbg * 32 + j];
-                }
-            }
-        }
-    return out;
-}
-
-// PG_PREC_F16X2 / PG_PREC_F16 (rank_2r.hip): the bf16 fragment layout in fp16 — every hi fragment (RNE), then, with two
-// products per term, every lo fragment (lo = RNE(w - hi))
-static std::vector<uint8_t> pack_weights_f16(const float* w, uint32_t K, uint32_t N, int nprod) {
-    const uint32_t kg = K / 16;
-    const size_t plane = (size_t)(N / 32) * kg * 1024;
-    std::vector<uint8_t> out(plane * nprod);
-    for (uint32_t nbg = 0; nbg < N / 32; ++nbg)
-        for (uint32_t g = 0; g < kg; ++g) {
-            uint8_t* frag = out.data() + ((size_t)nbg * kg + g) * 1024;
-            for (uint32_t lane = 0; lane < 64; ++lane) {
-                const uint32_t j = lane & 31, hh = lane >> 5;
-                _Float16 hi[8], lo[8];
-                for (uint32_t e = 0; e < 8; ++e) {
-                    const float v = w[(size_t)(g * 16 + 8 * hh + e) * N + nbg * 32 + j];
-                    hi[e] = (_Float16)v;
-                    lo[e] = (_Float16)(v - (float)hi[e]);
-                }
-                memcpy(frag + lane * 16, hi, 16);
-                if (nprod == 2) memcpy(frag + plane + lane * 16, lo, 16);
-            }
-        }
-    return out;
-}
-
-// floor(log2 max_j |row[j]|), 0 for an all-zero row; false for a non-finite entry
-static bool row_exponent(const float* row, size_t n, int* e) {
-    float mx = 0.0f;
-    for (size_t j = 0; j < n; ++j) {
-        if (!std::isfinite(row[j])) return false;
-        mx = std::max(mx, std::fabs(row[j]));
-    }
-    *e = mx > 0.0f ? std::ilogb(mx) : 0;
-    return true;
-}
-static bool f32_normal_or_zero(float v) { return v == 0.0f || std::isnormal(v); }
-
-// The fp16 modes' operands (the scaling rule is in rank_2r.hip's header): W1's item half [kDIN][h1] and W2 [h1][h2] scaled
-// per row, the activations' factors beside them.  PG_ERR_UNSUPPORTED for weights the rule cannot carry.
-static int build_f16_operands(const float* w1i, const float* w2, uint32_t h1, uint32_t h2, int nprod,
-                              std::vector<uint8_t>* w1p, std::vector<uint8_t>* w2p, std::vector<float>* xs,
-                              std::vector<float>* hs) {
-    auto scale_rows = [&](const float* w, uint32_t K, uint32_t N, int act_bias, std::vector<float>* ws,
-                          std::vector<float>* fs, const char* what) {
-        ws->assign((size_t)K * N, 0.0f);
-        fs->assign(K, 0.0f);
-        for (uint32_t k = 0; k < K; ++k) {
-            int e;
-            if (!row_exponent(w + (size_t)k * N, N, &e)) {
-                set_error("pg_model_load: %s row %u holds a non-finite weight: not representable in an fp16 mode", what, k);
-                return PG_ERR_UNSUPPORTED;
-            }
-            // act_bias: G for x (accumulator scale S comes from the weights), G - S for h1 (whose accumulators carry 2^S)
-            const float f = std::ldexp(1.0f, e + act_bias), g = std::ldexp(1.0f, -e - kH2G + kH2S);
-            bool ok = std::isnormal(f) && std::isnormal(g);
-            for (uint32_t j = 0; j < N && ok; ++j) {
-                const float v = w[(size_t)k * N + j] * g;
-                // (a weight 2^-100 of its row's maximum may vanish: it is under every bound here)
-                ok = std::isfinite(v);
-                (*ws)[(size_t)k * N + j] = v;
-            }
-            if (!ok) {
-                set_error("pg_model_load: %s row %u (largest weight 2^%d) leaves fp32's normal range once scaled for an fp16 mode",
-                          what, k, e);
-                return PG_ERR_UNSUPPORTED;
-            }
-            (*fs)[k] = f;
-        }
-        return PG_OK;
-    };
-    std::vector<float> w1s, w2s;
-    int rc;
-    if ((rc = scale_rows(w1i, kDIN, h1, kH2G, &w1s, xs, "W1 (item half)"))) return rc;
-    if ((rc = scale_rows(w2, h1, h2, kH2G - kH2S, &w2s, hs, "W2"))) return rc;
-    *w1p = pack_weights_f16(w1s.data(), kDIN, h1, nprod);
-    *w2p = pack_weights_f16(w2s.data(), h1, h2, nprod);
-    return PG_OK;
-}
-
-static int upload(pg_ctx* ctx, pg_model* m, const void* src, size_t bytes, void** dst) {
-    void* d = nullptr;
-    hipError_t e = hipMalloc(&d, bytes ? bytes : 16);
-    if (e != hipSuccess) {
-        set_error("pg_model_load: hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
-        return PG_ERR_NOMEM;
-    }
-    m->allocs.push_back(d);
-    if (bytes) PG_HIP(hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, ctx->stream));
-    PG_HIP(hipStreamSynchronize(ctx->stream));
-    *dst = d;
-    return PG_OK;
-}
-
-static std::vector<float> rounded(const float* w, size_t n, int prec) {
-    std::vector<float> o(n);
-    for (size_t i = 0; i < n; ++i) o[i] = round_prec(w[i], prec);
-    return o;
-}
-
 
 struct RankScratch {
     uint32_t *tile_req, *tile_item0, *tile_cnt, *n_tiles, *req_tile0;
@@ -1126,22 +996,7 @@ static int launch_fm2t_mlp(pg_ctx* ctx, const MlpArgs& a, uint32_t grid) {
     }
     return PG_OK;
 }
-// (h1, h2) of DNN3 and (t_h1, t_out, k) of the two-tower model; d_item is 64 or 128 (64: the gathered row is padded
-// with zero columns whose W1 rows are zero), n_item_fields x k = 128, n_user_fields <= 16
-#define PG_DNN3_SHAPES(X) X(128, 128) X(256, 128) X(256, 256) X(512, 256) X(1024, 512)
-#define PG_FM2T_SHAPES(X) X(256, 64, 16) X(256, 64, 32) X(128, 64, 8) X(512, 128, 16)
-static bool dnn3_shape_ok(uint32_t h1, uint32_t h2) {
-#define X(A, B) if (h1 == A && h2 == B) return true;
-    PG_DNN3_SHAPES(X)
-#undef X
-    return false;
-}
-static bool fm2t_shape_ok(uint32_t th, uint32_t to, uint32_t k) {
-#define X(A, B, C) if (th == A && to == B && k == C) return true;
-    PG_FM2T_SHAPES(X)
-#undef X
-    return false;
-}
+// one instance per shape of rank_model.hpp's lists
 static int dispatch_dnn3_mlp(pg_ctx* ctx, const pg_model* m, const MlpArgs& a, uint32_t grid) {
 #define X(A, B)                                                                                          \
     if (m->h1 == A && m->h2 == B)                                                                        \
@@ -1276,10 +1131,10 @@ int rank_dnn3_dev_locked(pg_ctx* ctx, const pg_model* m, const pg_table* t,
     return PG_OK;
 }
 
-static int rank_fm2t_dev_locked(pg_ctx* ctx, const pg_model* m, const float* d_user,
-                                const int32_t* d_ufids, const int32_t* d_ifids, const uint32_t* d_off,
-                                uint32_t n_req, uint32_t n_items, float* d_out, const pg_item_rows* ir = nullptr,
-                                const uint32_t* d_cand = nullptr) {
+int rank_fm2t_dev_locked(pg_ctx* ctx, const pg_model* m, const float* d_user,
+                         const int32_t* d_ufids, const int32_t* d_ifids, const uint32_t* d_off,
+                         uint32_t n_req, uint32_t n_items, float* d_out, const pg_item_rows* ir,
+                         const uint32_t* d_cand) {
     if (n_items == 0 || n_req == 0) return PG_OK;
     // the benchmark's shape over item records: the per-wave pipeline kernel (rank_is.hip), 32-item tiles
     const bool isw = ir && !ctx->knobs.rank_no_ws && fm2t_isw_shape(m->th, m->to, m->k, m->nif, m->prec);
@@ -1430,500 +1285,4 @@ int fm2t_user_embedding_locked(pg_ctx* ctx, const pg_model* m, const float* d_us
     return PG_OK;
 }
 
-static int finish_rank_timing(pg_ctx* ctx) {
-    PG_HIP(hipStreamSynchronize(ctx->stream));
-    if (!ctx->rank_timing_pending) return PG_OK;       // (stage timers off: nothing was recorded, last_rank_ms stays)
-    float ms = 0.f;
-    PG_HIP(hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]));
-    ctx->stats.last_rank_ms = ms;
-    ctx->rank_timing_pending = false;
-    return PG_OK;
-}
-
 }  // namespace pg
-
-extern "C" {
-
-int pg_model_load(pg_ctx* ctx, pg_model_kind kind, pg_prec prec, const void* blob, size_t len,
-                  pg_model** out) {
-    PG_REQUIRE(ctx && blob && out, "pg_model_load: NULL argument");
-    PG_REQUIRE(prec == PG_PREC_F32 || prec == PG_PREC_BF16 || prec == PG_PREC_BF16X3 || prec == PG_PREC_F16X2 || prec == PG_PREC_F16,
-               "pg_model_load: bad precision %d", (int)prec);
-    const int f16_nprod = prec == PG_PREC_F16X2 ? 2 : (prec == PG_PREC_F16 ? 1 : 0);
-    if (f16_nprod && kind == PG_MODEL_FM_TWOTOWER) {
-        pg::set_error("pg_model_load: PG_PREC_F16X2 / PG_PREC_F16 serve PG_MODEL_DNN3 and PG_MODEL_DNN3_MULTI; load a "
-                      "PG_MODEL_FM_TWOTOWER in PG_PREC_BF16X3");
-        return PG_ERR_UNSUPPORTED;
-    }
-    std::lock_guard<std::mutex> g(ctx->mu);
-    PG_HIP(hipSetDevice(ctx->device));
-    const uint8_t* p = (const uint8_t*)blob;
-    pg_model* m = new pg_model();
-    m->kind = kind;
-    // an fp16 mode is the split-bf16 model (its whole-call and per-tile fallback) plus the fp16 operands
-    m->prec = f16_nprod ? (int)PG_PREC_BF16X3 : (int)prec;
-    m->f16_nprod = f16_nprod;
-    m->ctx = ctx;
-    int rc = PG_OK;
-    auto fail = [&](int code) {
-        for (void* a : m->allocs) hipFree(a);
-        delete m;
-        return code;
-    };
-    if (kind == PG_MODEL_DNN3 || kind == PG_MODEL_DNN3_MULTI) {
-        const bool multi = kind == PG_MODEL_DNN3_MULTI;
-        const size_t hb = multi ? 20 : 16;
-        m->kind = PG_MODEL_DNN3;                 // every rank entry point takes it; n_out says how many planes it writes
-        if (len < hb) { pg::set_error("pg_model_load: blob too short"); return fail(PG_ERR_INVALID); }
-        uint32_t hdr[5] = {0, 0, 0, 0, 1};
-        memcpy(hdr, p, hb);
-        m->d_user = hdr[0]; m->d_item = hdr[1]; m->h1 = hdr[2]; m->h2 = hdr[3]; m->n_out = hdr[4];
-        if (m->n_out == 0 || m->n_out > (uint32_t)pg::kMaxHeads) {
-            pg::set_error("pg_model_load: a multi-output DNN3 has 1..%d outputs, the blob says %u", pg::kMaxHeads, m->n_out);
-            return fail(PG_ERR_UNSUPPORTED);
-        }
-        if ((m->d_item != 128 && m->d_item != 64) || !pg::dnn3_shape_ok(m->h1, m->h2) || m->d_user == 0 || m->d_user > 4096) {
-            pg::set_error("pg_model_load: DNN3 shape [%u+%u]->%u->%u->1 unsupported (d_item 64 or 128; hidden widths "
-                          "128-128, 256-128, 256-256, 512-256, 1024-512)", m->d_user, m->d_item, m->h1, m->h2);
-            return fail(PG_ERR_UNSUPPORTED);
-        }
-        const size_t din = (size_t)m->d_user + m->d_item;
-        const size_t need = hb + (din * m->h1 + m->h1 + (size_t)m->h1 * m->h2 + m->h2 + ((size_t)m->h2 + 1) * m->n_out) * 4;
-        if (len != need) { pg::set_error("pg_model_load: DNN3 blob is %zu bytes, expected %zu", len, need); return fail(PG_ERR_INVALID); }
-        const float* w1 = (const float*)(p + hb);
-        const float* b1 = w1 + din * m->h1;
-        const float* w2 = b1 + m->h1;
-        const float* b2 = w2 + (size_t)m->h1 * m->h2;
-        const float* w3 = b2 + m->h2;                      // [h2][n_out] as exported ([in][out]); kept head-major on the device
-        const float* b3 = w3 + (size_t)m->h2 * m->n_out;
-        m->b3 = b3[0];
-        std::vector<float> w3t((size_t)m->n_out * m->h2);
-        for (uint32_t o = 0; o < m->n_out; ++o)
-            for (uint32_t j = 0; j < m->h2; ++j) w3t[(size_t)o * m->h2 + j] = w3[(size_t)j * m->n_out + o];
-        auto w1u = pg::rounded(w1, (size_t)m->d_user * m->h1, m->prec);
-        // the kernel's layer 1 is 128 deep: a 64-wide item row is padded with zero columns, W1 with zero rows
-        std::vector<float> w1i((size_t)pg::kDIN * m->h1, 0.0f);
-        memcpy(w1i.data(), w1 + (size_t)m->d_user * m->h1, (size_t)m->d_item * m->h1 * 4);
-        auto w1p = pg::pack_weights(w1i.data(), pg::kDIN, m->h1, m->prec);
-        auto w2p = pg::pack_weights(w2, m->h1, m->h2, m->prec);
-        if ((rc = pg::upload(ctx, m, w1u.data(), w1u.size() * 4, (void**)&m->w1u))) return fail(rc);
-        if ((rc = pg::upload(ctx, m, b1, m->h1 * 4, (void**)&m->b1))) return fail(rc);
-        if ((rc = pg::upload(ctx, m, w1p.data(), w1p.size(), &m->w1p))) return fail(rc);
-        if ((rc = pg::upload(ctx, m, w2p.data(), w2p.size(), &m->w2p))) return fail(rc);
-        if (m->prec == 2) {                          // split bf16: the lo fragments follow the hi fragments
-            m->w1p_lo = (char*)m->w1p + w1p.size() / 2;
-            m->w2p_lo = (char*)m->w2p + w2p.size() / 2;
-        }
-        if ((rc = pg::upload(ctx, m, b2, m->h2 * 4, (void**)&m->b2))) return fail(rc);
-        if ((rc = pg::upload(ctx, m, w3t.data(), w3t.size() * 4, (void**)&m->w3))) return fail(rc);
-        if ((rc = pg::upload(ctx, m, b3, m->n_out * 4, (void**)&m->b3v))) return fail(rc);
-        if (f16_nprod) {
-            std::vector<uint8_t> hw1, hw2;
-            std::vector<float> xs, hs;
-            const unsigned long long zeros[2] = {0, 0};
-            for (size_t i = 0; i < (len - hb) / 4; ++i)
-                if (!std::isfinite(w1[i])) {
-                    pg::set_error("pg_model_load: the blob holds a non-finite weight (float %zu): not representable in an fp16 mode", i);
-                    return fail(PG_ERR_UNSUPPORTED);
-                }
-            if ((rc = pg::build_f16_operands(w1i.data(), w2, m->h1, m->h2, f16_nprod, &hw1, &hw2, &xs, &hs))) return fail(rc);
-            if ((rc = pg::upload(ctx, m, hw1.data(), hw1.size(), &m->h_w1p))) return fail(rc);
-            if ((rc = pg::upload(ctx, m, hw2.data(), hw2.size(), &m->h_w2p))) return fail(rc);
-            if (f16_nprod == 2) {
-                m->h_w1p_lo = (char*)m->h_w1p + hw1.size() / 2;
-                m->h_w2p_lo = (char*)m->h_w2p + hw2.size() / 2;
-            }
-            if ((rc = pg::upload(ctx, m, xs.data(), xs.size() * 4, (void**)&m->h_xs))) return fail(rc);
-            if ((rc = pg::upload(ctx, m, hs.data(), hs.size() * 4, (void**)&m->h_hs))) return fail(rc);
-            if ((rc = pg::upload(ctx, m, zeros, sizeof zeros, (void**)&m->h_stats))) return fail(rc);
-        }
-    } else if (kind == PG_MODEL_FM_TWOTOWER) {
-        if (len < 32) { pg::set_error("pg_model_load: blob too short"); return fail(PG_ERR_INVALID); }
-        uint32_t hdr[7];
-        memcpy(hdr, p, 28);
-        memcpy(&m->fm_b, p + 28, 4);
-        m->nuf = hdr[0]; m->nif = hdr[1]; m->k = hdr[2]; m->d_user = hdr[3];
-        m->th = hdr[4]; m->to = hdr[5]; m->vocab = hdr[6];
-        if (m->nuf == 0 || m->nuf > 16 || m->nif * m->k != (uint32_t)pg::kDIN || !pg::fm2t_shape_ok(m->th, m->to, m->k) ||
-            m->d_user == 0 || m->d_user > 4096 || m->vocab == 0) {
-            pg::set_error("pg_model_load: two-tower shape unsupported (1..16 user fields; item fields x k = 128 with "
-                          "k = 8, 16 or 32; towers 256-64 (k 16 / 32), 128-64 (k 8), 512-128 (k 16))");
-            return fail(PG_ERR_UNSUPPORTED);
-        }
-        const size_t din = (size_t)m->nif * m->k;
-        const size_t nf = m->nuf + m->nif;
-        const size_t wfl = (size_t)m->d_user * m->th + m->th + (size_t)m->th * m->to + m->to + din * m->th +
-                           m->th + (size_t)m->th * m->to + m->to;
-        const size_t field_fl = nf * ((size_t)m->vocab * m->k + m->vocab);
-        const size_t need = 32 + (wfl + field_fl) * 4;
-        if (len != need) { pg::set_error("pg_model_load: two-tower blob is %zu bytes, expected %zu", len, need); return fail(PG_ERR_INVALID); }
-        const float* uw1 = (const float*)(p + 32);
-        const float* ub1 = uw1 + (size_t)m->d_user * m->th;
-        const float* uw2 = ub1 + m->th;
-        const float* ub2 = uw2 + (size_t)m->th * m->to;
-        const float* iw1 = ub2 + m->to;
-        const float* ib1 = iw1 + din * m->th;
-        const float* iw2 = ib1 + m->th;
-        const float* ib2 = iw2 + (size_t)m->th * m->to;
-        const float* fields = ib2 + m->to;
-        auto ruw1 = pg::rounded(uw1, (size_t)m->d_user * m->th, m->prec);
-        auto ruw2 = pg::rounded(uw2, (size_t)m->th * m->to, m->prec);
-        auto iw1p = pg::pack_weights(iw1, (uint32_t)din, m->th, m->prec);
-        auto iw2p = pg::pack_weights(iw2, m->th, m->to, m->prec);
-        if ((rc = pg::upload(ctx, m, ruw1.data(), ruw1.size() * 4, (void**)&m->w1u))) return fail(rc);
-        if ((rc = pg::upload(ctx, m, ub1, m->th * 4, (void**)&m->b1))) return fail(rc);
-        if ((rc = pg::upload(ctx, m, ruw2.data(), ruw2.size() * 4, (void**)&m->uw2))) return fail(rc);
-        if ((rc = pg::upload(ctx, m, ub2, m->to * 4, (void**)&m->ub2))) return fail(rc);
-        if ((rc = pg::upload(ctx, m, iw1p.data(), iw1p.size(), &m->w1p))) return fail(rc);
-        if ((rc = pg::upload(ctx, m, ib1, m->th * 4, (void**)&m->c1_shared))) return fail(rc);
-        if ((rc = pg::upload(ctx, m, iw2p.data(), iw2p.size(), &m->w2p))) return fail(rc);
-        if (m->prec == 2) {
-            m->w1p_lo = (char*)m->w1p + iw1p.size() / 2;
-            m->w2p_lo = (char*)m->w2p + iw2p.size() / 2;
-        }
-        if ((rc = pg::upload(ctx, m, ib2, m->to * 4, (void**)&m->b2))) return fail(rc);
-        if ((rc = pg::upload(ctx, m, fields, field_fl * 4, (void**)&m->fields))) return fail(rc);
-        std::vector<const float*> pe(nf), pl(nf);
-        for (size_t f = 0; f < nf; ++f) {
-            pe[f] = m->fields + f * ((size_t)m->vocab * m->k + m->vocab);
-            pl[f] = pe[f] + (size_t)m->vocab * m->k;
-        }
-        if ((rc = pg::upload(ctx, m, pe.data(), nf * sizeof(float*), (void**)&m->d_field_emb))) return fail(rc);
-        if ((rc = pg::upload(ctx, m, pl.data(), nf * sizeof(float*), (void**)&m->d_field_lin))) return fail(rc);
-    } else {
-        pg::set_error("pg_model_load: unknown model kind %d", (int)kind);
-        return fail(PG_ERR_INVALID);
-    }
-    *out = m;
-    return PG_OK;
-}
-
-int pg_model_num_outputs(const pg_model* m, uint32_t* out) {
-    PG_REQUIRE(m && out, "pg_model_num_outputs: NULL argument");
-    *out = m->n_out;
-    return PG_OK;
-}
-
-int pg_model_f16_stats(const pg_model* m, uint64_t out[4]) {
-    PG_REQUIRE(m && out, "pg_model_f16_stats: NULL argument");
-    out[0] = out[1] = out[2] = out[3] = 0;
-    if (!m->f16_nprod) return PG_OK;
-    pg_ctx* ctx = m->ctx;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    PG_HIP(hipSetDevice(ctx->device));
-    unsigned long long dev[2] = {0, 0};
-    PG_HIP(hipMemcpyAsync(dev, m->h_stats, sizeof dev, hipMemcpyDeviceToHost, ctx->stream));
-    PG_HIP(hipStreamSynchronize(ctx->stream));
-    out[0] = m->f16_calls;
-    out[1] = dev[0];
-    out[2] = dev[1];
-    out[3] = m->f16_calls_whole;
-    return PG_OK;
-}
-
-int pg_model_destroy(pg_ctx* ctx, pg_model* m) {
-    PG_REQUIRE(ctx, "pg_model_destroy: ctx is NULL");
-    if (!m) return PG_OK;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    PG_HIP(hipStreamSynchronize(ctx->stream));
-    for (void* a : m->allocs) PG_HIP(hipFree(a));
-    delete m;
-    return PG_OK;
-}
-
-int pg_rank_dnn3_dev(pg_ctx* ctx, const pg_model* m, const pg_table* t, const float* d_user_vecs,
-                     const uint32_t* d_cand_rows, const uint32_t* d_req_offsets, uint32_t n_req,
-                     uint32_t n_items, float* d_out_scores) {
-    PG_REQUIRE(ctx && m && t && d_user_vecs && d_cand_rows && d_req_offsets && d_out_scores,
-               "pg_rank_dnn3_dev: NULL argument");
-    PG_REQUIRE(m->kind == PG_MODEL_DNN3, "pg_rank_dnn3_dev: model is not DNN3");
-    PG_REQUIRE(t->dim == m->d_item, "pg_rank_dnn3_dev: table dim %u != model d_item %u", t->dim, m->d_item);
-    PG_REQUIRE(n_req <= 65535, "pg_rank_dnn3_dev: at most 65535 requests per call");
-    std::lock_guard<std::mutex> g(ctx->mu);
-    pg::TableRead tr(t->rw);
-    return pg::rank_dnn3_dev_locked(ctx, m, t, d_user_vecs, d_cand_rows, d_req_offsets, n_req, n_items,
-                                    d_out_scores);
-}
-
-int pg_rank_dnn3(pg_ctx* ctx, const pg_model* m, const pg_table* t, const float* user_vecs,
-                 const uint32_t* cand_rows, const uint32_t* req_offsets, uint32_t n_req,
-                 float* out_scores) {
-    PG_REQUIRE(ctx && m && t && req_offsets, "pg_rank_dnn3: NULL argument");
-    PG_REQUIRE(m->kind == PG_MODEL_DNN3, "pg_rank_dnn3: model is not DNN3");
-    PG_REQUIRE(t->dim == m->d_item, "pg_rank_dnn3: table dim %u != model d_item %u", t->dim, m->d_item);
-    PG_REQUIRE(n_req <= 65535, "pg_rank_dnn3: at most 65535 requests per call");
-    if (n_req == 0) return PG_OK;
-    PG_REQUIRE(req_offsets[0] == 0, "pg_rank_dnn3: req_offsets[0] must be 0");
-    for (uint32_t r = 0; r < n_req; ++r)
-        PG_REQUIRE(req_offsets[r + 1] >= req_offsets[r], "pg_rank_dnn3: req_offsets not monotone at %u", r);
-    const uint32_t n_items = req_offsets[n_req];
-    if (n_items == 0) return PG_OK;
-    PG_REQUIRE(user_vecs && cand_rows && out_scores, "pg_rank_dnn3: NULL argument");
-    for (uint32_t i = 0; i < n_items; ++i)
-        PG_REQUIRE(cand_rows[i] < t->rows, "pg_rank_dnn3: candidate %u row %u outside table of %llu rows", i,
-                   cand_rows[i], (unsigned long long)t->rows);
-    std::lock_guard<std::mutex> g(ctx->mu);
-    pg::TableRead tr(t->rw);
-    float *d_u, *d_s;
-    uint32_t *d_c, *d_o;
-    int rc;
-    const size_t ub = (size_t)n_req * m->d_user * 4, cb = (size_t)n_items * 4, ob = (size_t)(n_req + 1) * 4;
-    const size_t sb = (size_t)n_items * 4 * m->n_out;
-    if ((rc = pg::scratch_carve(ctx, pg::kSlotStaging, [&](pg::Carve& c) {
-            d_u = c.take<float>(ub / 4);
-            d_c = c.take<uint32_t>(cb / 4);
-            d_o = c.take<uint32_t>(ob / 4);
-            d_s = c.take<float>(sb / 4);
-        }))) return rc;
-    PG_HIP(hipMemcpyAsync(d_u, user_vecs, ub, hipMemcpyHostToDevice, ctx->stream));
-    PG_HIP(hipMemcpyAsync(d_c, cand_rows, cb, hipMemcpyHostToDevice, ctx->stream));
-    PG_HIP(hipMemcpyAsync(d_o, req_offsets, ob, hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = pg::rank_dnn3_dev_locked(ctx, m, t, d_u, d_c, d_o, n_req, n_items, d_s))) return rc;
-    PG_HIP(hipMemcpyAsync(out_scores, d_s, sb, hipMemcpyDeviceToHost, ctx->stream));
-    return pg::finish_rank_timing(ctx);
-}
-
-int pg_fm2t_user_embedding_dev(pg_ctx* ctx, const pg_model* m, const float* d_user_vecs, uint32_t n_req, float* d_out) {
-    PG_REQUIRE(ctx && m && (n_req == 0 || (d_user_vecs && d_out)), "pg_fm2t_user_embedding_dev: NULL argument");
-    PG_REQUIRE(m->kind == PG_MODEL_FM_TWOTOWER, "pg_fm2t_user_embedding_dev: model is not FM_TWOTOWER");
-    std::lock_guard<std::mutex> g(ctx->mu);
-    return pg::fm2t_user_embedding_locked(ctx, m, d_user_vecs, n_req, d_out);
-}
-
-int pg_fm2t_user_embedding(pg_ctx* ctx, const pg_model* m, const float* user_vecs, uint32_t n_req, float* out) {
-    PG_REQUIRE(ctx && m && (n_req == 0 || (user_vecs && out)), "pg_fm2t_user_embedding: NULL argument");
-    PG_REQUIRE(m->kind == PG_MODEL_FM_TWOTOWER, "pg_fm2t_user_embedding: model is not FM_TWOTOWER");
-    if (n_req == 0) return PG_OK;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    float *d_u, *d_o;
-    int rc;
-    const size_t ob = (size_t)n_req * m->to * 4;
-    if ((rc = pg::scratch_carve(ctx, pg::kSlotStaging, [&](pg::Carve& c) {
-            d_u = c.take<float>((size_t)n_req * m->d_user);
-            d_o = c.take<float>(ob / 4);
-        }))) return rc;
-    PG_HIP(hipMemcpyAsync(d_u, user_vecs, (size_t)n_req * m->d_user * 4, hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = pg::fm2t_user_embedding_locked(ctx, m, d_u, n_req, d_o))) return rc;
-    PG_HIP(hipMemcpyAsync(out, d_o, ob, hipMemcpyDeviceToHost, ctx->stream));
-    PG_HIP(hipStreamSynchronize(ctx->stream));
-    return PG_OK;
-}
-
-int pg_rank_fm2t_dev(pg_ctx* ctx, const pg_model* m, const float* d_user_vecs,
-                     const int32_t* d_user_field_ids, const int32_t* d_item_field_ids,
-                     const uint32_t* d_req_offsets, uint32_t n_req, uint32_t n_items,
-                     float* d_out_scores) {
-    PG_REQUIRE(ctx && m && d_user_vecs && d_user_field_ids && d_item_field_ids && d_req_offsets && d_out_scores,
-               "pg_rank_fm2t_dev: NULL argument");
-    PG_REQUIRE(m->kind == PG_MODEL_FM_TWOTOWER, "pg_rank_fm2t_dev: model is not FM_TWOTOWER");
-    PG_REQUIRE(n_req <= 65535, "pg_rank_fm2t_dev: at most 65535 requests per call");
-    std::lock_guard<std::mutex> g(ctx->mu);
-    return pg::rank_fm2t_dev_locked(ctx, m, d_user_vecs, d_user_field_ids, d_item_field_ids, d_req_offsets,
-                                    n_req, n_items, d_out_scores);
-}
-
-int pg_rank_fm2t_rows_dev(pg_ctx* ctx, const pg_model* m, const pg_features* fs, const int32_t* item_field_cols,
-                          const float* d_user_vecs, const int32_t* d_user_field_ids, const uint32_t* d_cand_rows,
-                          const uint32_t* d_req_offsets, uint32_t n_req, uint32_t n_items, float* d_out_scores) {
-    PG_REQUIRE(ctx && m && fs && item_field_cols && d_user_vecs && d_user_field_ids && d_cand_rows && d_req_offsets &&
-                   d_out_scores,
-               "pg_rank_fm2t_rows_dev: NULL argument");
-    PG_REQUIRE(m->kind == PG_MODEL_FM_TWOTOWER, "pg_rank_fm2t_rows_dev: model is not FM_TWOTOWER");
-    PG_REQUIRE(n_req <= 65535, "pg_rank_fm2t_rows_dev: at most 65535 requests per call");
-    if (n_items == 0 || n_req == 0) return PG_OK;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    return pg::rank_fm2t_rows_dev_locked(ctx, m, fs, item_field_cols, d_user_vecs, d_user_field_ids, d_cand_rows, d_req_offsets,
-                                         n_req, n_items, d_out_scores);
-}
-
-// host-buffer form of pg_rank_fm2t_rows_dev: what an IAlgorithm.Run of the EasyRec flavour passes — item ids resolved
-// to rows, the per-item "context features" read from the device-resident columns instead of being boxed per request
-int pg_rank_fm2t_rows(pg_ctx* ctx, const pg_model* m, const pg_features* fs, const int32_t* item_field_cols,
-                      const float* user_vecs, const int32_t* user_field_ids, const uint32_t* cand_rows,
-                      const uint32_t* req_offsets, uint32_t n_req, float* out_scores) {
-    PG_REQUIRE(ctx && m && fs && item_field_cols && req_offsets, "pg_rank_fm2t_rows: NULL argument");
-    PG_REQUIRE(m->kind == PG_MODEL_FM_TWOTOWER, "pg_rank_fm2t_rows: model is not FM_TWOTOWER");
-    PG_REQUIRE(n_req <= 65535, "pg_rank_fm2t_rows: at most 65535 requests per call");
-    if (n_req == 0) return PG_OK;
-    PG_REQUIRE(req_offsets[0] == 0, "pg_rank_fm2t_rows: req_offsets[0] must be 0");
-    for (uint32_t r = 0; r < n_req; ++r)
-        PG_REQUIRE(req_offsets[r + 1] >= req_offsets[r], "pg_rank_fm2t_rows: req_offsets not monotone at %u", r);
-    const uint32_t n_items = req_offsets[n_req];
-    if (n_items == 0) return PG_OK;
-    PG_REQUIRE(user_vecs && user_field_ids && cand_rows && out_scores, "pg_rank_fm2t_rows: NULL argument");
-    for (size_t i = 0; i < (size_t)n_req * m->nuf; ++i)
-        PG_REQUIRE(user_field_ids[i] >= 0 && (uint32_t)user_field_ids[i] < m->vocab,
-                   "pg_rank_fm2t_rows: user field id %d outside vocab %u", user_field_ids[i], m->vocab);
-    std::lock_guard<std::mutex> g(ctx->mu);
-    float *d_u, *d_s;
-    int32_t *d_uf, *d_if;
-    uint32_t *d_c, *d_o;
-    int rc;
-    const size_t ub = (size_t)n_req * m->d_user * 4, ufb = (size_t)n_req * m->nuf * 4, cb = (size_t)n_items * 4;
-    const size_t ifb = (size_t)n_items * m->nif * 4, ob = (size_t)(n_req + 1) * 4, sb = (size_t)n_items * 4;
-    if ((rc = pg::scratch_carve(ctx, pg::kSlotStaging, [&](pg::Carve& c) {
-            d_u = c.take<float>(ub / 4);
-            d_uf = c.take<int32_t>(ufb / 4);
-            d_c = c.take<uint32_t>(cb / 4);
-            d_if = c.take<int32_t>(ifb / 4);
-            d_o = c.take<uint32_t>(ob / 4);
-            d_s = c.take<float>(sb / 4);
-        }))) return rc;
-    PG_HIP(hipMemcpyAsync(d_u, user_vecs, ub, hipMemcpyHostToDevice, ctx->stream));
-    PG_HIP(hipMemcpyAsync(d_uf, user_field_ids, ufb, hipMemcpyHostToDevice, ctx->stream));
-    PG_HIP(hipMemcpyAsync(d_c, cand_rows, cb, hipMemcpyHostToDevice, ctx->stream));
-    PG_HIP(hipMemcpyAsync(d_o, req_offsets, ob, hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = pg::features_gather_i32_locked(ctx, fs, item_field_cols, m->nif, d_c, n_items, d_if, "pg_rank_fm2t_rows"))) return rc;
-    if ((rc = pg::rank_fm2t_dev_locked(ctx, m, d_u, d_uf, d_if, d_o, n_req, n_items, d_s))) return rc;
-    PG_HIP(hipMemcpyAsync(out_scores, d_s, sb, hipMemcpyDeviceToHost, ctx->stream));
-    return pg::finish_rank_timing(ctx);
-}
-
-int pg_rank_fm2t(pg_ctx* ctx, const pg_model* m, const float* user_vecs, const int32_t* user_field_ids,
-                 const int32_t* item_field_ids, const uint32_t* req_offsets, uint32_t n_req,
-                 float* out_scores) {
-    PG_REQUIRE(ctx && m && req_offsets, "pg_rank_fm2t: NULL argument");
-    PG_REQUIRE(m->kind == PG_MODEL_FM_TWOTOWER, "pg_rank_fm2t: model is not FM_TWOTOWER");
-    PG_REQUIRE(n_req <= 65535, "pg_rank_fm2t: at most 65535 requests per call");
-    if (n_req == 0) return PG_OK;
-    PG_REQUIRE(req_offsets[0] == 0, "pg_rank_fm2t: req_offsets[0] must be 0");
-    for (uint32_t r = 0; r < n_req; ++r)
-        PG_REQUIRE(req_offsets[r + 1] >= req_offsets[r], "pg_rank_fm2t: req_offsets not monotone at %u", r);
-    const uint32_t n_items = req_offsets[n_req];
-    if (n_items == 0) return PG_OK;
-    PG_REQUIRE(user_vecs && user_field_ids && item_field_ids && out_scores, "pg_rank_fm2t: NULL argument");
-    for (size_t i = 0; i < (size_t)n_req * m->nuf; ++i)
-        PG_REQUIRE(user_field_ids[i] >= 0 && (uint32_t)user_field_ids[i] < m->vocab,
-                   "pg_rank_fm2t: user field id %d outside vocab %u", user_field_ids[i], m->vocab);
-    for (size_t i = 0; i < (size_t)n_items * m->nif; ++i)
-        PG_REQUIRE(item_field_ids[i] >= 0 && (uint32_t)item_field_ids[i] < m->vocab,
-                   "pg_rank_fm2t: item field id %d outside vocab %u", item_field_ids[i], m->vocab);
-    std::lock_guard<std::mutex> g(ctx->mu);
-    float *d_u, *d_s;
-    int32_t *d_uf, *d_if;
-    uint32_t* d_o;
-    int rc;
-    const size_t ub = (size_t)n_req * m->d_user * 4, ufb = (size_t)n_req * m->nuf * 4;
-    const size_t ifb = (size_t)n_items * m->nif * 4, ob = (size_t)(n_req + 1) * 4, sb = (size_t)n_items * 4;
-    if ((rc = pg::scratch_carve(ctx, pg::kSlotStaging, [&](pg::Carve& c) {
-            d_u = c.take<float>(ub / 4);
-            d_uf = c.take<int32_t>(ufb / 4);
-            d_if = c.take<int32_t>(ifb / 4);
-            d_o = c.take<uint32_t>(ob / 4);
-            d_s = c.take<float>(sb / 4);
-        }))) return rc;
-    PG_HIP(hipMemcpyAsync(d_u, user_vecs, ub, hipMemcpyHostToDevice, ctx->stream));
-    PG_HIP(hipMemcpyAsync(d_uf, user_field_ids, ufb, hipMemcpyHostToDevice, ctx->stream));
-    PG_HIP(hipMemcpyAsync(d_if, item_field_ids, ifb, hipMemcpyHostToDevice, ctx->stream));
-    PG_HIP(hipMemcpyAsync(d_o, req_offsets, ob, hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = pg::rank_fm2t_dev_locked(ctx, m, d_u, d_uf, d_if, d_o, n_req, n_items, d_s))) return rc;
-    PG_HIP(hipMemcpyAsync(out_scores, d_s, sb, hipMemcpyDeviceToHost, ctx->stream));
-    return pg::finish_rank_timing(ctx);
-}
-
-int pg_fm2t_item_rows_build(pg_ctx* ctx, const pg_model* m, const pg_features* fs, const int32_t* item_field_cols,
-                            pg_item_rows** out) {
-    PG_REQUIRE(ctx && m && fs && item_field_cols && out, "pg_fm2t_item_rows_build: NULL argument");
-    PG_REQUIRE(m->kind == PG_MODEL_FM_TWOTOWER, "pg_fm2t_item_rows_build: model is not FM_TWOTOWER");
-    PG_REQUIRE(m->nif <= 16 && m->nif * m->k == (uint32_t)pg::kDIN, "pg_fm2t_item_rows_build: unsupported item side (%u fields x %u)", m->nif, m->k);
-    PG_REQUIRE(fs->rows < 0xFFFFFFFEull, "pg_fm2t_item_rows_build: too many rows");
-    std::lock_guard<std::mutex> g(ctx->mu);
-    PG_HIP(hipSetDevice(ctx->device));
-    pg_item_rows* ir = new pg_item_rows();
-    ir->m = m;
-    ir->fs = fs;
-    ir->rows = fs->rows;
-    for (uint32_t f = 0; f < m->nif; ++f) ir->cols[f] = item_field_cols[f];
-    const size_t bytes = (size_t)(fs->rows + 1) * pg::kItemRowFloats * 4;
-    const hipError_t e = hipMalloc((void**)&ir->d, bytes);
-    if (e != hipSuccess) {
-        pg::set_error("pg_fm2t_item_rows_build: hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
-        delete ir;
-        return PG_ERR_NOMEM;
-    }
-    int rc;
-    if ((rc = pg::item_rows_fill_locked(ctx, ir, 0, fs->rows + 1))) {       // + the defaults' record
-        hipFree(ir->d);
-        delete ir;
-        return rc;
-    }
-    PG_HIP(hipStreamSynchronize(ctx->stream));
-    *out = ir;
-    return PG_OK;
-}
-
-int pg_fm2t_item_rows_update(pg_ctx* ctx, pg_item_rows* ir, uint64_t row0, uint64_t nrows) {
-    PG_REQUIRE(ctx && ir, "pg_fm2t_item_rows_update: NULL argument");
-    // (not row0 + nrows <= rows: the sum wraps for a huge row0, and the kernel would write far outside the records)
-    PG_REQUIRE(row0 <= ir->rows && nrows <= ir->rows - row0, "pg_fm2t_item_rows_update: rows %llu + %llu outside the store's %llu",
-               (unsigned long long)row0, (unsigned long long)nrows, (unsigned long long)ir->rows);
-    std::lock_guard<std::mutex> g(ctx->mu);
-    int rc;
-    if ((rc = pg::item_rows_fill_locked(ctx, ir, row0, nrows))) return rc;
-    if ((rc = pg::item_rows_fill_locked(ctx, ir, ir->rows, 1))) return rc;     // the defaults may have changed with the column
-    PG_HIP(hipStreamSynchronize(ctx->stream));
-    return PG_OK;
-}
-
-int pg_fm2t_item_rows_destroy(pg_ctx* ctx, pg_item_rows* ir) {
-    PG_REQUIRE(ctx, "pg_fm2t_item_rows_destroy: NULL context");
-    if (!ir) return PG_OK;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    PG_HIP(hipStreamSynchronize(ctx->stream));
-    if (ir->d) PG_HIP(hipFree(ir->d));
-    delete ir;
-    return PG_OK;
-}
-
-int pg_rank_fm2t_irows_dev(pg_ctx* ctx, const pg_model* m, const pg_item_rows* ir, const float* d_user_vecs,
-                           const int32_t* d_user_field_ids, const uint32_t* d_cand_rows, const uint32_t* d_req_offsets,
-                           uint32_t n_req, uint32_t n_items, float* d_out_scores) {
-    PG_REQUIRE(ctx && m && ir && d_user_vecs && d_user_field_ids && d_cand_rows && d_req_offsets && d_out_scores,
-               "pg_rank_fm2t_irows_dev: NULL argument");
-    PG_REQUIRE(m->kind == PG_MODEL_FM_TWOTOWER && ir->m == m, "pg_rank_fm2t_irows_dev: the item records belong to another model");
-    PG_REQUIRE(n_req <= 65535, "pg_rank_fm2t_irows_dev: at most 65535 requests per call");
-    if (n_items == 0 || n_req == 0) return PG_OK;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    return pg::rank_fm2t_irows_dev_locked(ctx, m, ir, d_user_vecs, d_user_field_ids, d_cand_rows, d_req_offsets, n_req, n_items, d_out_scores);
-}
-
-int pg_rank_fm2t_irows(pg_ctx* ctx, const pg_model* m, const pg_item_rows* ir, const float* user_vecs,
-                       const int32_t* user_field_ids, const uint32_t* cand_rows, const uint32_t* req_offsets, uint32_t n_req,
-                       float* out_scores) {
-    PG_REQUIRE(ctx && m && ir && req_offsets, "pg_rank_fm2t_irows: NULL argument");
-    PG_REQUIRE(m->kind == PG_MODEL_FM_TWOTOWER && ir->m == m, "pg_rank_fm2t_irows: the item records belong to another model");
-    PG_REQUIRE(n_req <= 65535, "pg_rank_fm2t_irows: at most 65535 requests per call");
-    if (n_req == 0) return PG_OK;
-    PG_REQUIRE(req_offsets[0] == 0, "pg_rank_fm2t_irows: req_offsets[0] must be 0");
-    for (uint32_t r = 0; r < n_req; ++r)
-        PG_REQUIRE(req_offsets[r + 1] >= req_offsets[r], "pg_rank_fm2t_irows: req_offsets not monotone at %u", r);
-    const uint32_t n_items = req_offsets[n_req];
-    if (n_items == 0) return PG_OK;
-    PG_REQUIRE(user_vecs && user_field_ids && cand_rows && out_scores, "pg_rank_fm2t_irows: NULL argument");
-    for (size_t i = 0; i < (size_t)n_req * m->nuf; ++i)
-        PG_REQUIRE(user_field_ids[i] >= 0 && (uint32_t)user_field_ids[i] < m->vocab,
-                   "pg_rank_fm2t_irows: user field id %d outside vocab %u", user_field_ids[i], m->vocab);
-    std::lock_guard<std::mutex> g(ctx->mu);
-    float *d_u, *d_s;
-    int32_t* d_uf;
-    uint32_t *d_c, *d_o;
-    int rc;
-    const size_t ub = (size_t)n_req * m->d_user * 4, ufb = (size_t)n_req * m->nuf * 4, cb = (size_t)n_items * 4;
-    const size_t ob = (size_t)(n_req + 1) * 4, sb = (size_t)n_items * 4;
-    if ((rc = pg::scratch_carve(ctx, pg::kSlotStaging, [&](pg::Carve& c) {
-            d_u = c.take<float>(ub / 4);
-            d_uf = c.take<int32_t>(ufb / 4);
-            d_c = c.take<uint32_t>(cb / 4);
-            d_o = c.take<uint32_t>(ob / 4);
-            d_s = c.take<float>(sb / 4);
-        }))) return rc;
-    PG_HIP(hipMemcpyAsync(d_u, user_vecs, ub, hipMemcpyHostToDevice, ctx->stream));
-    PG_HIP(hipMemcpyAsync(d_uf, user_field_ids, ufb, hipMemcpyHostToDevice, ctx->stream));
-    PG_HIP(hipMemcpyAsync(d_c, cand_rows, cb, hipMemcpyHostToDevice, ctx->stream));
-    PG_HIP(hipMemcpyAsync(d_o, req_offsets, ob, hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = pg::rank_fm2t_irows_dev_locked(ctx, m, ir, d_u, d_uf, d_c, d_o, n_req, n_items, d_s))) return rc;
-    PG_HIP(hipMemcpyAsync(out_scores, d_s, sb, hipMemcpyDeviceToHost, ctx->stream));
-    return pg::finish_rank_timing(ctx);
-}
-
-}  // extern "C"

@@ -1,7 +1,9 @@
-// rank_mlp.hpp — what the rank-stage kernels share: operand types, the bf16 rounding used on both sides of
-// the boundary, the kernel argument block and the swizzled LDS operand-tile stores (rank_mlp.hip, rank_ws.hip).
+// rank_mlp.hpp — what the rank-stage kernels share: operand types, the kernel argument block and the swizzled LDS
+// operand-tile stores (rank_mlp.hip, rank_ws.hip); the model's constants and the bf16 rounding used on both sides of
+// the boundary come from rank_model.hpp.
 #pragma once
 #include "common.hpp"
+#include "rank_model.hpp"
 
 #include <cstring>
 
@@ -10,33 +12,6 @@ namespace pg {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-__host__ __device__ __forceinline__ uint16_t f32_to_bf16_rne(float x) {
-    uint32_t b;
-#ifdef __HIP_DEVICE_COMPILE__
-    b = __float_as_uint(x);
-#else
-    memcpy(&b, &x, 4);
-#endif
-    if ((b & 0x7FFFFFFFu) > 0x7F800000u) return (uint16_t)((b >> 16) | 0x0040u);
-    b += 0x7FFFu + ((b >> 16) & 1u);
-    return (uint16_t)(b >> 16);
-}
-__host__ __device__ __forceinline__ float bf16_to_f32(uint16_t v) {
-    uint32_t b = (uint32_t)v << 16;
-#ifdef __HIP_DEVICE_COMPILE__
-    return __uint_as_float(b);
-#else
-    float f;
-    memcpy(&f, &b, 4);
-    return f;
-#endif
-}
-// operand rounding of a precision mode: 0 = fp32, 1 = bf16 (RNE), 2 = split bf16 (x = hi + lo, three MFMA products:
-// nothing is rounded on the scalar side — the mode's specification is the fp32 one)
-__host__ __device__ __forceinline__ float round_prec(float x, int prec) {
-    return prec == 1 ? bf16_to_f32(f32_to_bf16_rne(x)) : x;
-}
 
 // PG_PREC_BF16X3: a pair of fp32 values as two packed bf16 pairs, hi = RNE(x), lo = RNE(x - hi) — x - hi is exact in
 // fp32, so |x - hi - lo| <= 2^-17 |x|; with the weights split the same way, hi*hi + hi*lo + lo*hi leaves a relative
@@ -52,10 +27,8 @@ __device__ __forceinline__ void split_bf16x2(float a, float b, uint32_t& hi, uin
 }
 
 constexpr int kBM = 128;       // items per workgroup tile
-constexpr int kDIN = 128;      // gathered input width
-constexpr int kFmMaxK = 32;        // largest FM embedding width (item fields x width = kDIN)
+constexpr int kFmMaxK = 32;       // largest FM embedding width (item fields x width = kDIN)
 constexpr int kFmUserStride = 1 + 2 * kFmMaxK;   // per-request FM prefix: lin, s[<=32] at +1, q[<=32] at +33
-constexpr int kMaxHeads = 8;           // outputs of a multi-head DNN3
 constexpr int kItemRowFloats = 160;    // a materialised item record: 128 embedding floats + <= 16 linear weights, padded to 5 x 128 B
 
 // the item-field columns of a feature store, by value (kernel argument of the item-record builder)
@@ -197,9 +170,7 @@ bool dnn3_x3_shape(uint32_t h1, uint32_t h2);
 int launch_dnn3_x3(pg_ctx* ctx, uint32_t h1, uint32_t h2, const MlpArgs& a);
 
 // ... and in PG_PREC_F16X2 / PG_PREC_F16 (nprod 2 / 1) — the same body on the fp16 MFMA, operands scaled by exact powers of
-// two, out-of-range tiles listed for the BF16X3 kernel; same shapes as dnn3_x3_shape
-constexpr int kH2G = 11;       // activations: 2^G on top of the row normalisation
-constexpr int kH2S = 23;       // accumulators hold 2^S x the pre-activation; weights carry 2^(S - G)
+// two (kH2G, kH2S), out-of-range tiles listed for the BF16X3 kernel; same shapes as dnn3_x3_shape
 int launch_dnn3_h2(pg_ctx* ctx, uint32_t h1, uint32_t h2, int nprod, const MlpArgs& a);
 
 // rank_is.hip: FM + two-tower over materialised item records for the benchmark's shape (towers 256-64, 8 fields x 16, bf16),

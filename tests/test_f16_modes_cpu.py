@@ -1,6 +1,7 @@
 """PG_PREC_F16X2 / PG_PREC_F16 restated in numpy — the specification the GPU tests of the fp16 rank modes lean on.
 
-The restatement follows pairec_amd/csrc/rank_2r.hip and the load-time scaling in rank_mlp.hip:
+The restatement follows pairec_amd/csrc/rank_2r.hip and the load-time scaling in rank_model.hpp (build_f16_operands, which
+tests/test_rank_model_cpu.py runs on the host):
   E_k = floor(log2 max_j |W1[k][j]|) per item input column, F_i = floor(log2 max_j |W2[i][j]|) per hidden unit (0 for a zero row)
   x'_k = fp16(x_k * 2^(E_k + G))          against  W1[k][:] * 2^(-E_k - G + S)   (accumulators: 2^S * z1, c1 enters * 2^S)
   h'_i = fp16(relu(acc1_i) * 2^(F_i + G - S))  against  W2[i][:] * 2^(-F_i - G + S)   (accumulators: 2^S * z2)

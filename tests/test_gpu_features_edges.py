@@ -1,4 +1,5 @@
-"""The feature store's gathers (csrc/features.hip) and the FM item records (csrc/rank_mlp.hip) at their edges, bit for bit against
+"""The feature store's gathers (csrc/features.hip) and the FM item records (csrc/rank_mlp.hip fills them, rank_entry.hip
+holds their entry points) at their edges, bit for bit against
 tests/features_ref.py (its own known answers: tests/test_features_ref_cpu.py).  The rules under test are stated in
 include/pairec_gpu.h — pg_features_set_column: THE STORED DEFAULT; pg_features_gather_f32_dev: DIRECT CONVERSION;
 pg_rank_fm2t_rows_dev: THE CLAMP ON ITEM IDS; pg_fm2t_item_rows_update: the range check — and in DESIGN.md §5.8.
