@@ -30,6 +30,15 @@
 //   leaves with PG_ERR_TIMEOUT — out of the queue if its request was still waiting there, otherwise it abandons the
 //   request record, which the workers retire when the batch completes.  The inputs of a staged request were copied,
 //   outputs are only ever written by the caller itself, so nothing touches the caller's memory after it returned.
+//
+// Two things this file only uses live elsewhere, each stated once:
+// * WHEN a batch closes — arrival statistics, the "full" rules, the choice among ready queues, the wake-up deadline and the
+//   rejoin hold, with their constants — is coalescer_policy.hpp (no HIP, no clock: tests/coalescer_policy_check.cpp runs it
+//   on hand-made time points).  The workers below keep the locks and the clock and call it for every decision.
+// * WHERE a batch's answers lie in the slot's pinned output image is one layout per flavour (RecallImage, RankImage,
+//   RecommendImage over pipeline.hpp's PageView, DppImage below): alloc_slot sizes the image from it, slot_copy_out writes
+//   through it, the entry points read through it.
+#include "coalescer_policy.hpp"
 #include "pipeline.hpp"
 
 #include <linux/futex.h>
@@ -116,27 +125,33 @@ struct Slot {
     Clock::time_point enqueued;
     std::atomic<uint32_t> pending{0};      // callers that have not copied their slice yet
     bool verified = false;                 // the recall plan of the current batch has been checked (a patched batch is only copied again)
-    // pinned host staging
+    // Every h_* (pinned host) and d_* (device) pointer below comes from pinned() / device(), which record it: free_slot
+    // walks the two lists, so a buffer added to alloc_slot needs no second mention.
+    std::vector<void*> pinned_owned, device_owned;
+    template <class T> hipError_t pinned(T** p, size_t bytes) {
+        const hipError_t e = hipHostMalloc((void**)p, bytes);
+        if (e == hipSuccess) pinned_owned.push_back(*p);
+        return e;
+    }
+    template <class T> hipError_t device(T** p, size_t bytes) {
+        const hipError_t e = hipMalloc((void**)p, bytes);
+        if (e == hipSuccess) device_owned.push_back(*p);
+        return e;
+    }
+    // every flavour: the requests' vectors and field ids, the output image (layouts below)
     float* h_vec = nullptr;                // [rows][vec_w]
-    int32_t* h_ufid = nullptr;             // [rows][ufid_stride]
-    uint32_t* h_qk = nullptr;              // recall: [max_batch] {kind, trigger row} pairs
-    float* h_uq = nullptr;                 // recall: [max_batch][d_user of the query model]
-    uint32_t* h_cand = nullptr;            // rank: concatenated candidate rows
-    uint32_t* h_off = nullptr;             // rank: request offsets
-    char* h_out = nullptr;                 // flavour-specific output image
-    // device
     float* d_vec = nullptr;
+    int32_t* h_ufid = nullptr;             // [rows][ufid_stride]
     int32_t* d_ufid = nullptr;
+    char* h_out = nullptr;                 // flavour-specific output image
+    // recall (and the recall in front of a recommend batch)
+    uint32_t* h_qk = nullptr;              // [max_batch] {kind, trigger row} pairs
     uint32_t* d_qk = nullptr;
+    float* h_uq = nullptr;                 // [max_batch][d_user of the query model]
     float* d_uq = nullptr;
-    float* d_qemb = nullptr;               // recall: the query model's embeddings [max_batch][dim]
-    uint32_t* d_cand = nullptr;
-    uint32_t* d_off = nullptr;
+    float* d_qemb = nullptr;               // the query model's embeddings [max_batch][dim]
     uint64_t* d_rows = nullptr;            // [max_batch][k]
     float* d_recall = nullptr;
-    float* d_rank = nullptr;               // n_algos planes of rank_stride floats
-    double* d_fused = nullptr;
-    uint32_t* d_order = nullptr;
     uint32_t* d_count = nullptr;           // [max_batch]
     // recalls with exclusion lists ("coalescer_max_exclude" > 0): the lists, their offsets, and the job's answer at depth k + max_exclude
     uint64_t* h_xlist = nullptr;           // [max_batch][max_exclude] packed request by request
@@ -145,17 +160,19 @@ struct Slot {
     uint32_t* d_xoff = nullptr;
     uint64_t* d_xrows = nullptr;           // [max_batch][k + max_exclude]
     float* d_xsc = nullptr;
+    // rank
+    uint32_t* h_cand = nullptr;            // concatenated candidate rows
+    uint32_t* d_cand = nullptr;
+    uint32_t* h_off = nullptr;             // request offsets
+    uint32_t* d_off = nullptr;
+    float* d_rank = nullptr;               // n_algos planes of rank_stride floats
+    // recommend
+    double* d_fused = nullptr;
+    uint32_t* d_order = nullptr;
     uint32_t* d_pick = nullptr;            // re-rank: [max_batch][max_top_n]
     uint32_t* d_pick_cnt = nullptr;
-    char* d_page = nullptr;                // recommend: the pages, layout as h_out
-    RecommendCall call;                    // recommend: what was enqueued (the verification may re-run single requests)
-    // a coalescer over a shard group: the step's ticket and its pages (host memory, [max_batch][max_top_n] planes)
-    pg_group_ticket* gticket = nullptr;
-    uint64_t* g_rows = nullptr;
-    float* g_rec = nullptr;
-    float* g_rnk = nullptr;
-    double* g_fus = nullptr;
-    uint32_t* g_cnt = nullptr;
+    char* d_page = nullptr;                // the pages, layout as h_out
+    RecommendCall call;                    // what was enqueued (the verification may re-run single requests)
     // dpp flavour (allocated by the first such batch)
     bool dpp_ready = false;
     uint32_t* h_dcand = nullptr;
@@ -165,8 +182,43 @@ struct Slot {
     double* d_drel = nullptr;
     double* d_dhook = nullptr;
     float* d_demb = nullptr;
-    uint32_t* d_dout = nullptr;            // [items] picks, [max dpp batch] counts behind them
+    uint32_t* d_dout = nullptr;            // the DppImage
     uint32_t* h_dout = nullptr;
+    // a coalescer over a shard group: the step's ticket and its pages (host memory, [max_batch][max_top_n] planes)
+    pg_group_ticket* gticket = nullptr;
+    std::vector<uint64_t> g_rows;
+    std::vector<float> g_rec, g_rnk;
+    std::vector<double> g_fus;
+    std::vector<uint32_t> g_cnt;
+};
+
+// ---- the output image of a batch, per flavour: alloc_slot sizes it, slot_copy_out writes it, the entry points read it ----
+// recall: rows [max_batch][k] u64 | scores [max_batch][k] f32 | counts [max_batch] u32 (byte offsets into h_out)
+struct RecallImage {
+    size_t k, scores, counts, bytes;
+    RecallImage(size_t max_batch, size_t k_) : k(k_), scores(max_batch * k_ * 8), counts(max_batch * k_ * 12), bytes(counts + max_batch * 4) {}
+    const char* rows_of(const char* img, uint32_t q) const { return img + (size_t)q * k * 8; }
+    const char* scores_of(const char* img, uint32_t q) const { return img + scores + (size_t)q * k * 4; }
+    const char* count_of(const char* img, uint32_t q) const { return img + counts + (size_t)q * 4; }
+};
+// rank: head o of the model is plane o, [n_items] f32 each, back to back
+struct RankImage {
+    size_t n_items;
+    size_t plane(uint32_t o) const { return (size_t)o * n_items * 4; }
+    size_t bytes(uint32_t heads) const { return plane(heads); }
+};
+// recommend: the pages (PageView over n_req x page width entries) | counts [max_batch] u32 | pick counts [max_batch] u32
+struct RecommendImage {
+    size_t pages, counts, pick_counts, bytes;
+    RecommendImage(size_t max_batch, size_t max_top_n, int n_planes)
+        : pages(max_batch * max_top_n * page_entry_bytes(std::max(n_planes, 1))), counts(pages), pick_counts(pages + max_batch * 4),
+          bytes(pages + max_batch * 8) {}
+};
+// dpp / ssd: picks [requests][topn] u32 | counts [kMaxQueries] u32 behind item_cap picks (in elements of h_dout / d_dout)
+struct DppImage {
+    size_t counts, elems;
+    explicit DppImage(size_t item_cap) : counts(item_cap), elems(item_cap + kMaxQueries) {}
+    size_t picks_of(uint32_t r, uint32_t topn) const { return (size_t)r * topn; }
 };
 
 inline void futex_wait(std::atomic<uint32_t>* w, uint32_t expect, const timespec* rel_timeout) {
@@ -221,23 +273,7 @@ struct pg_coalescer {
     std::atomic<uint32_t> outstanding{0};            // requests between submit and return (the router's load measure)
     uint32_t k = 0, max_batch = 0, max_wait_us = 0, depth = 0, max_top_n = 0, max_rank_items = 0, timeout_us = 0;
     uint32_t max_exclude = 0;        // the context's "coalescer_max_exclude" at creation: longest list of pg_coalescer_recall_exclude (0: off)
-    // arrival statistics per queue (under mu): a request that arrives at an idle device only waits for company when company is likely —
-    // when the recent inter-arrival gap (EWMA) is below max_wait_us; a lone caller is dispatched at once
-    pg::Clock::time_point last_arrival[pg::kNumQueues];
-    double gap_ewma_us[pg::kNumQueues] = {};
-    bool seen_arrival[pg::kNumQueues] = {};
-    // Rejoin hold (recall-based queues, under mu).  Callers are closed loops (a goroutine blocked in Recall.GetCandidateItems /
-    // IAlgorithm.Run issues its next request when this one returns), so the n callers of a batch that just completed are back
-    // within some tens of microseconds — and a partial batch dispatched the moment the device falls idle splits them from the
-    // requests that waited meanwhile into two cohorts that alternate for ever (32 callers: two batches of ~16, every request
-    // waits for the other cohort's pass: p50 3.2 ms where one batch of 32 takes 1.8).  After a completion the waiting partial
-    // batch is therefore held until those n are back, at most rejoin window (50 + 2 n us); rejoin_score tracks how many came
-    // back in time (open-loop arrivals do not): below one half the hold is off, re-tried every sixteenth completion.
-    pg::Clock::time_point rejoin_until[pg::kNumQueues];
-    size_t rejoin_target[pg::kNumQueues] = {};
-    uint32_t rejoin_n[pg::kNumQueues] = {};
-    double rejoin_score[pg::kNumQueues] = {};
-    uint32_t rejoin_probe[pg::kNumQueues] = {};
+    pg::policy::QueuePolicy policy[pg::kNumQueues];   // arrival statistics and rejoin hold per queue (under mu; rules: coalescer_policy.hpp)
     uint32_t max_rank_reqs = 0, rank_item_cap = 0;
     uint32_t dim = 0, vec_w = 0, ufid_stride = 0, vec_rows = 0;
     uint32_t dpp_item_cap = 0, dpp_max_n = 0, dpp_max_hook = 0;
@@ -270,79 +306,76 @@ int flavour_of(int queue) {
     return (queue == kQRecall || queue == kQRecallL2 || queue == kQRecallEx) ? kRecall : (queue == kQRecommend ? kRecommend : (queue == kQDpp ? kDpp : kRank));
 }
 
-size_t page_bytes(const pg_coalescer* c) { return (size_t)c->max_batch * c->max_top_n * page_entry_bytes(std::max(c->n_planes, 1)); }
+RecallImage recall_image(const pg_coalescer* c) { return RecallImage(c->max_batch, c->k); }
+RecommendImage recommend_image(const pg_coalescer* c) { return RecommendImage(c->max_batch, c->max_top_n, c->n_planes); }
+DppImage dpp_image(const pg_coalescer* c) { return DppImage(c->dpp_item_cap); }
 
 void fail_req(Req* r, int rc, const char* msg) {
     r->rc = rc;
     snprintf(r->err, sizeof r->err, "%s", msg);
 }
 
-// how many DPP requests of `n` candidates one batch takes: bounded by the staging buffers and by the kernel
-// matrices (n^2 doubles per request in the context's scratch: at most 1 GiB of them per batch)
-uint32_t dpp_batch_limit(const pg_coalescer* c, uint32_t n) {
-    uint64_t b = c->dpp_item_cap / std::max(n, 1u);
-    b = std::min<uint64_t>(b, (1ull << 27) / ((uint64_t)n * n));
-    return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(b, kMaxQueries));
-}
+uint32_t dpp_batch_limit(const pg_coalescer* c, uint32_t n) { return policy::dpp_batch_limit(c->dpp_item_cap, n, kMaxQueries); }
 
+// (a failure half-way leaves what was allocated in the slot's lists: the caller frees the partial slot with free_slot)
 int alloc_slot(pg_coalescer* c, Slot* s) {
     if (c->group) {                      // host staging only: the group owns every device buffer
         const size_t np = (size_t)c->max_batch * c->max_top_n;
-        PG_HIP(hipHostMalloc((void**)&s->h_vec, (size_t)c->max_batch * c->dim * 4));
-        s->g_rows = new uint64_t[np];
-        s->g_rec = new float[np];
-        s->g_rnk = new float[np];
-        s->g_fus = new double[np];
-        s->g_cnt = new uint32_t[c->max_batch];
+        PG_HIP(s->pinned(&s->h_vec, (size_t)c->max_batch * c->dim * 4));
+        s->g_rows.resize(np);
+        s->g_rec.resize(np);
+        s->g_rnk.resize(np);
+        s->g_fus.resize(np);
+        s->g_cnt.resize(c->max_batch);
         return PG_OK;
     }
     const size_t nb = c->max_batch, k = c->k;
     const bool rank = c->n_algos > 0;
     PG_HIP(hipEventCreateWithFlags(&s->done, hipEventDisableTiming));
     PG_HIP(hipEventCreateWithFlags(&s->computed, hipEventDisableTiming));
-    PG_HIP(hipHostMalloc((void**)&s->h_vec, (size_t)c->vec_rows * c->vec_w * 4));
-    PG_HIP(hipMalloc((void**)&s->d_vec, (size_t)c->vec_rows * c->vec_w * 4));
-    PG_HIP(hipHostMalloc((void**)&s->h_qk, nb * 8));
-    PG_HIP(hipMalloc((void**)&s->d_qk, nb * 8));
+    PG_HIP(s->pinned(&s->h_vec, (size_t)c->vec_rows * c->vec_w * 4));
+    PG_HIP(s->device(&s->d_vec, (size_t)c->vec_rows * c->vec_w * 4));
+    PG_HIP(s->pinned(&s->h_qk, nb * 8));
+    PG_HIP(s->device(&s->d_qk, nb * 8));
     if (c->ufid_stride) {
-        PG_HIP(hipHostMalloc((void**)&s->h_ufid, (size_t)c->vec_rows * c->ufid_stride * 4));
-        PG_HIP(hipMalloc((void**)&s->d_ufid, (size_t)c->vec_rows * c->ufid_stride * 4));
+        PG_HIP(s->pinned(&s->h_ufid, (size_t)c->vec_rows * c->ufid_stride * 4));
+        PG_HIP(s->device(&s->d_ufid, (size_t)c->vec_rows * c->ufid_stride * 4));
     }
     if (c->query_model) {
-        PG_HIP(hipHostMalloc((void**)&s->h_uq, nb * c->query_model->d_user * 4));
-        PG_HIP(hipMalloc((void**)&s->d_uq, nb * c->query_model->d_user * 4));
-        PG_HIP(hipMalloc((void**)&s->d_qemb, nb * c->dim * 4));
+        PG_HIP(s->pinned(&s->h_uq, nb * c->query_model->d_user * 4));
+        PG_HIP(s->device(&s->d_uq, nb * c->query_model->d_user * 4));
+        PG_HIP(s->device(&s->d_qemb, nb * c->dim * 4));
     }
-    size_t out_bytes = nb * k * 12 + nb * 4;                       // recall image: rows | scores | counts
+    size_t out_bytes = recall_image(c).bytes;                      // the image holds the largest flavour's
     if (rank) {
-        PG_HIP(hipHostMalloc((void**)&s->h_cand, (size_t)c->rank_item_cap * 4));
-        PG_HIP(hipHostMalloc((void**)&s->h_off, ((size_t)c->max_rank_reqs + 1) * 4));
-        PG_HIP(hipMalloc((void**)&s->d_cand, (size_t)c->rank_item_cap * 4));
-        PG_HIP(hipMalloc((void**)&s->d_off, ((size_t)c->max_rank_reqs + 1) * 4));
-        out_bytes = std::max(out_bytes, (size_t)c->rank_item_cap * 4 * c->max_heads);    // (a multi-output model: a plane per head)
+        PG_HIP(s->pinned(&s->h_cand, (size_t)c->rank_item_cap * 4));
+        PG_HIP(s->pinned(&s->h_off, ((size_t)c->max_rank_reqs + 1) * 4));
+        PG_HIP(s->device(&s->d_cand, (size_t)c->rank_item_cap * 4));
+        PG_HIP(s->device(&s->d_off, ((size_t)c->max_rank_reqs + 1) * 4));
+        out_bytes = std::max(out_bytes, RankImage{c->rank_item_cap}.bytes(c->max_heads));     // (a multi-output model: a plane per head)
     }
-    if (c->e) out_bytes = std::max(out_bytes, page_bytes(c) + nb * 8);
-    PG_HIP(hipHostMalloc((void**)&s->h_out, out_bytes));
-    PG_HIP(hipMalloc((void**)&s->d_rows, nb * k * 8));
-    PG_HIP(hipMalloc((void**)&s->d_recall, nb * k * 4));
-    PG_HIP(hipMalloc((void**)&s->d_count, nb * 4));
+    if (c->e) out_bytes = std::max(out_bytes, recommend_image(c).bytes);
+    PG_HIP(s->pinned(&s->h_out, out_bytes));
+    PG_HIP(s->device(&s->d_rows, nb * k * 8));
+    PG_HIP(s->device(&s->d_recall, nb * k * 4));
+    PG_HIP(s->device(&s->d_count, nb * 4));
     if (c->max_exclude) {
         const size_t kx = k + c->max_exclude;
-        PG_HIP(hipHostMalloc((void**)&s->h_xlist, nb * c->max_exclude * 8));
-        PG_HIP(hipHostMalloc((void**)&s->h_xoff, (nb + 1) * 4));
-        PG_HIP(hipMalloc((void**)&s->d_xlist, nb * c->max_exclude * 8));
-        PG_HIP(hipMalloc((void**)&s->d_xoff, (nb + 1) * 4));
-        PG_HIP(hipMalloc((void**)&s->d_xrows, nb * kx * 8));
-        PG_HIP(hipMalloc((void**)&s->d_xsc, nb * kx * 4));
+        PG_HIP(s->pinned(&s->h_xlist, nb * c->max_exclude * 8));
+        PG_HIP(s->pinned(&s->h_xoff, (nb + 1) * 4));
+        PG_HIP(s->device(&s->d_xlist, nb * c->max_exclude * 8));
+        PG_HIP(s->device(&s->d_xoff, (nb + 1) * 4));
+        PG_HIP(s->device(&s->d_xrows, nb * kx * 8));
+        PG_HIP(s->device(&s->d_xsc, nb * kx * 4));
     }
-    if (rank) PG_HIP(hipMalloc((void**)&s->d_rank, (size_t)std::max(c->n_planes, (int)c->max_heads) * c->rank_stride * 4));
+    if (rank) PG_HIP(s->device(&s->d_rank, (size_t)std::max(c->n_planes, (int)c->max_heads) * c->rank_stride * 4));
     if (c->e) {
-        PG_HIP(hipMalloc((void**)&s->d_fused, nb * k * 8));
-        PG_HIP(hipMalloc((void**)&s->d_order, nb * k * 4));
-        PG_HIP(hipMalloc((void**)&s->d_page, page_bytes(c)));
+        PG_HIP(s->device(&s->d_fused, nb * k * 8));
+        PG_HIP(s->device(&s->d_order, nb * k * 4));
+        PG_HIP(s->device(&s->d_page, recommend_image(c).pages));
         if (c->rerank.kind) {
-            PG_HIP(hipMalloc((void**)&s->d_pick, nb * c->max_top_n * 4));
-            PG_HIP(hipMalloc((void**)&s->d_pick_cnt, nb * 4));
+            PG_HIP(s->device(&s->d_pick, nb * c->max_top_n * 4));
+            PG_HIP(s->device(&s->d_pick_cnt, nb * 4));
         }
     }
     return pipe_run_acquire(s->ctx, &s->run);
@@ -353,38 +386,27 @@ int ensure_dpp_buffers(pg_coalescer* c, Slot* s) {
     if (s->dpp_ready) return PG_OK;
     PG_HIP(hipSetDevice(s->ctx->device));
     const size_t items = c->dpp_item_cap;
-    PG_HIP(hipHostMalloc((void**)&s->h_dcand, items * 4));
-    PG_HIP(hipHostMalloc((void**)&s->h_drel, items * 8));
-    PG_HIP(hipMalloc((void**)&s->d_dcand, items * 4));
-    PG_HIP(hipMalloc((void**)&s->d_drel, items * 8));
-    PG_HIP(hipMalloc((void**)&s->d_demb, items * c->dim * 4));
-    PG_HIP(hipMalloc((void**)&s->d_dout, (items + kMaxQueries) * 4));
-    PG_HIP(hipHostMalloc((void**)&s->h_dout, (items + kMaxQueries) * 4));
+    PG_HIP(s->pinned(&s->h_dcand, items * 4));
+    PG_HIP(s->pinned(&s->h_drel, items * 8));
+    PG_HIP(s->device(&s->d_dcand, items * 4));
+    PG_HIP(s->device(&s->d_drel, items * 8));
+    PG_HIP(s->device(&s->d_demb, items * c->dim * 4));
+    PG_HIP(s->device(&s->d_dout, dpp_image(c).elems * 4));
+    PG_HIP(s->pinned(&s->h_dout, dpp_image(c).elems * 4));
     if (c->dpp_max_hook) {
-        PG_HIP(hipHostMalloc((void**)&s->h_dhook, items * c->dpp_max_hook * 8));
-        PG_HIP(hipMalloc((void**)&s->d_dhook, items * c->dpp_max_hook * 8));
+        PG_HIP(s->pinned(&s->h_dhook, items * c->dpp_max_hook * 8));
+        PG_HIP(s->device(&s->d_dhook, items * c->dpp_max_hook * 8));
     }
     s->dpp_ready = true;
     return PG_OK;
 }
 
 void free_slot(pg_coalescer* c, Slot* s) {
-    delete[] s->g_rows;
-    delete[] s->g_rec;
-    delete[] s->g_rnk;
-    delete[] s->g_fus;
-    delete[] s->g_cnt;
     if (s->run) pipe_run_release(s->ctx, s->run);
     if (s->done) hipEventDestroy(s->done);
     if (s->computed) hipEventDestroy(s->computed);
-    for (void* p : {(void*)s->h_vec, (void*)s->h_ufid, (void*)s->h_qk, (void*)s->h_uq, (void*)s->h_cand, (void*)s->h_off, (void*)s->h_out,
-                    (void*)s->h_dcand, (void*)s->h_drel, (void*)s->h_dhook, (void*)s->h_dout, (void*)s->h_xlist, (void*)s->h_xoff})
-        if (p) hipHostFree(p);
-    for (void* p : {(void*)s->d_vec, (void*)s->d_ufid, (void*)s->d_qk, (void*)s->d_uq, (void*)s->d_qemb, (void*)s->d_cand, (void*)s->d_off,
-                    (void*)s->d_rows, (void*)s->d_recall, (void*)s->d_rank, (void*)s->d_fused, (void*)s->d_order, (void*)s->d_count,
-                    (void*)s->d_pick, (void*)s->d_pick_cnt, (void*)s->d_page, (void*)s->d_dcand, (void*)s->d_drel, (void*)s->d_dhook,
-                    (void*)s->d_demb, (void*)s->d_dout, (void*)s->d_xlist, (void*)s->d_xoff, (void*)s->d_xrows, (void*)s->d_xsc})
-        if (p) hipFree(p);
+    for (void* p : s->pinned_owned) hipHostFree(p);
+    for (void* p : s->device_owned) hipFree(p);
     delete s;
 }
 
@@ -408,26 +430,29 @@ int slot_copy_out(pg_coalescer* c, Slot* s) {
     if (fl == kRank) {
         // head o of a multi-output model: plane o of the batch, [n_items] each, back to back in the image
         const uint32_t heads = c->algos[s->queue - kQRank0].m->n_out;
+        const RankImage im{s->n_items};
         for (uint32_t o = 0; o < heads; ++o)
-            PG_HIP(hipMemcpyAsync(s->h_out + (size_t)o * s->n_items * 4, s->d_rank + (size_t)o * c->rank_stride, (size_t)s->n_items * 4,
+            PG_HIP(hipMemcpyAsync(s->h_out + im.plane(o), s->d_rank + (size_t)o * c->rank_stride, (size_t)s->n_items * 4,
                                   hipMemcpyDeviceToHost, c->copy_stream));
     } else if (fl == kRecall) {
+        const RecallImage im = recall_image(c);
         const size_t nk = (size_t)nq * c->k;
         PG_HIP(hipMemcpyAsync(s->h_out, s->d_rows, nk * 8, hipMemcpyDeviceToHost, c->copy_stream));
-        PG_HIP(hipMemcpyAsync(s->h_out + (size_t)c->max_batch * c->k * 8, s->d_recall, nk * 4, hipMemcpyDeviceToHost, c->copy_stream));
+        PG_HIP(hipMemcpyAsync(s->h_out + im.scores, s->d_recall, nk * 4, hipMemcpyDeviceToHost, c->copy_stream));
         if (s->queue == kQRecallEx)            // (the counts after the exclusions: the job's status words count the over-fetched answer)
-            PG_HIP(hipMemcpyAsync(s->h_out + (size_t)c->max_batch * c->k * 12, s->d_count, (size_t)nq * 4, hipMemcpyDeviceToHost, c->copy_stream));
+            PG_HIP(hipMemcpyAsync(s->h_out + im.counts, s->d_count, (size_t)nq * 4, hipMemcpyDeviceToHost, c->copy_stream));
     } else if (fl == kDpp) {
-        const size_t np = (size_t)nq * s->key.topn;
+        const DppImage im = dpp_image(c);
+        const size_t np = im.picks_of(nq, s->key.topn);
         PG_HIP(hipMemcpyAsync(s->h_dout, s->d_dout, np * 4, hipMemcpyDeviceToHost, c->copy_stream));
-        PG_HIP(hipMemcpyAsync(s->h_dout + c->dpp_item_cap, s->d_dout + c->dpp_item_cap, (size_t)nq * 4, hipMemcpyDeviceToHost, c->copy_stream));
+        PG_HIP(hipMemcpyAsync(s->h_dout + im.counts, s->d_dout + im.counts, (size_t)nq * 4, hipMemcpyDeviceToHost, c->copy_stream));
     } else {
+        const RecommendImage im = recommend_image(c);
         const size_t np = (size_t)nq * s->n_items;
         PG_HIP(hipMemcpyAsync(s->h_out, s->d_page, np * page_entry_bytes(c->n_planes), hipMemcpyDeviceToHost, c->copy_stream));
-        PG_HIP(hipMemcpyAsync(s->h_out + page_bytes(c), s->d_count, (size_t)nq * 4, hipMemcpyDeviceToHost, c->copy_stream));
+        PG_HIP(hipMemcpyAsync(s->h_out + im.counts, s->d_count, (size_t)nq * 4, hipMemcpyDeviceToHost, c->copy_stream));
         if (c->rerank.kind)
-            PG_HIP(hipMemcpyAsync(s->h_out + page_bytes(c) + (size_t)c->max_batch * 4, s->d_pick_cnt, (size_t)nq * 4, hipMemcpyDeviceToHost,
-                                  c->copy_stream));
+            PG_HIP(hipMemcpyAsync(s->h_out + im.pick_counts, s->d_pick_cnt, (size_t)nq * 4, hipMemcpyDeviceToHost, c->copy_stream));
     }
     PG_HIP(hipEventRecord(s->done, c->copy_stream));
     return PG_OK;
@@ -527,7 +552,7 @@ int enqueue_dpp_batch(pg_coalescer* c, Slot* s) {
     if (key.has_table && (rc = table_gather_locked(ctx, c->t, s->d_dcand, (uint32_t)items, s->d_demb))) return rc;
     return dpp_run_locked(ctx, key.has_table ? s->d_demb : nullptr, key.hook_dim ? s->d_dhook : nullptr, s->d_drel, R, key.n,
                           key.has_table ? c->dim : 0u, key.hook_dim, key.alpha, key.topn, key.window, key.normalize, key.ensure_pos,
-                          key.has_table, s->d_dout, s->d_dout + c->dpp_item_cap);
+                          key.has_table, s->d_dout, s->d_dout + dpp_image(c).counts);
 }
 
 // Enqueue the slot's batch: inputs host → device, the kernels, the copy-out.  first = false: the recall plan of a
@@ -734,56 +759,30 @@ void dispatcher_main(pg_coalescer* c) {
     std::unique_lock<std::mutex> lk(c->mu);
     while (true) {
         if (c->stop) break;
-        // Which queue goes next?  A batch is ready when it is full, or when nothing is in flight on the device and
-        // its oldest request has waited max_wait_us; among ready queues the one whose head is oldest wins.
-        const bool idle = c->inflight.empty();
-        const auto now = Clock::now();
-        int kind = -1;
-        bool any = false;
-        auto earliest = Clock::time_point::max();
+        // Which queue goes next (policy::choose)?  What the policy sees of every queue: its length, its head, whether it is full
+        policy::QueueView view[kNumQueues];
         for (int f = 0; f < kNumQueues; ++f) {
-            std::deque<Req*>& qf = c->queue[f];
+            const std::deque<Req*>& qf = c->queue[f];
             if (qf.empty()) continue;
-            any = true;
-            bool full;
-            if (f >= kQRank0) {
-                full = qf.size() >= c->max_rank_reqs || c->queue_items[f] >= (uint64_t)c->max_batch * c->k;
-            } else if (f == kQDpp) {
-                full = qf.size() >= dpp_batch_limit(c, qf.front()->key.n);
-            } else {
-                full = qf.size() >= (f == kQRecallL2 ? l2_batch_limit(c) : c->max_batch);
-            }
-            const uint32_t wait_us = c->gap_ewma_us[f] > (double)c->max_wait_us ? 0u : c->max_wait_us;
-            auto deadline = qf.front()->arrived + std::chrono::microseconds(wait_us);
-            // (rejoin hold: everyone the last batch answered is back -> go at once; else not before the window closes)
-            const bool holding = now < c->rejoin_until[f];
-            const bool rejoined = holding && qf.size() >= c->rejoin_target[f];
-            if (rejoined) deadline = now;
-            else if (holding && c->rejoin_until[f] > deadline) deadline = c->rejoin_until[f];
-            // recall-based flavours: a table pass costs the same for 1 query as for 256, so a partial batch only goes out
-            // when the device has nothing to do; rank / DPP launches cost what their items cost, so a partial batch goes out
-            // as soon as its head has waited (a free slot permitting) and pipelines behind the running one
-            const bool per_item = f >= kQRank0 || f == kQDpp;
-            if ((idle || per_item) && deadline < earliest) earliest = deadline;      // (a deadline that time alone will make ready)
-            if ((full || ((idle || per_item) && now >= deadline)) && (kind < 0 || qf.front()->arrived < c->queue[kind].front()->arrived)) kind = f;
+            view[f].len = qf.size();
+            view[f].head_arrived = qf.front()->arrived;
+            view[f].per_item = f >= kQRank0 || f == kQDpp;
+            if (f >= kQRank0) view[f].full = policy::rank_queue_full(qf.size(), c->queue_items[f], c->max_rank_reqs, c->max_batch, c->k);
+            else if (f == kQDpp) view[f].full = policy::dpp_queue_full(qf.size(), c->dpp_item_cap, qf.front()->key.n, kMaxQueries);
+            else view[f].full = policy::recall_queue_full(qf.size(), f == kQRecallL2 ? l2_batch_limit(c) : c->max_batch);
         }
-        if (kind < 0 || c->free_slots.empty()) {
+        const policy::Choice next = policy::choose(view, c->policy, kNumQueues, c->inflight.empty(), Clock::now(), c->max_wait_us, !c->free_slots.empty());
+        if (next.queue < 0) {
             // nothing ready (or `depth` batches already in flight: keep collecting).  A new request, a completion
             // or a released slot wakes us; an idle device additionally at the oldest request's deadline.
-            if (any && kind < 0 && !c->free_slots.empty() && earliest != Clock::time_point::max()) c->cv_dispatch.wait_until(lk, earliest);
+            if (next.timed) c->cv_dispatch.wait_until(lk, next.wake);
             else c->cv_dispatch.wait(lk);
             continue;
         }
+        const int kind = next.queue;
         Slot* s = c->free_slots.front();               // oldest first: consecutive batches alternate between the contexts
         c->free_slots.erase(c->free_slots.begin());
-        if (c->rejoin_n[kind]) {                       // how much of the last batch's callers made it into this one
-            const size_t base = c->rejoin_target[kind] - c->rejoin_n[kind];
-            const size_t have = c->queue[kind].size();
-            const double frac = have <= base ? 0.0 : (have - base >= c->rejoin_n[kind] ? 1.0 : (double)(have - base) / c->rejoin_n[kind]);
-            c->rejoin_score[kind] = 0.8 * c->rejoin_score[kind] + 0.2 * frac;
-            c->rejoin_n[kind] = 0;
-            c->rejoin_until[kind] = Clock::time_point();
-        }
+        c->policy[kind].on_dispatch(c->queue[kind].size());
         take_batch(c, kind, s);
         lk.unlock();
         int rc = kind == kQDpp ? ensure_dpp_buffers(c, s) : PG_OK;
@@ -870,7 +869,7 @@ void completer_main(pg_coalescer* c) {
         }
         if (c->group) {
             // waits for the step, verifies every shard's plan (re-running the step where one failed), assembles the pages
-            rc = pg_group_recommend_end(c->group, s->gticket, s->g_rows, s->g_rec, s->g_rnk, s->g_fus, s->g_cnt);
+            rc = pg_group_recommend_end(c->group, s->gticket, s->g_rows.data(), s->g_rec.data(), s->g_rnk.data(), s->g_fus.data(), s->g_cnt.data());
             s->gticket = nullptr;
             device_fault = rc == PG_ERR_DEVICE;
         }
@@ -887,15 +886,8 @@ void completer_main(pg_coalescer* c) {
         lk.lock();
         c->inflight.pop_front();
         if (!c->group && s->queue < kQRank0 && s->queue != kQDpp && s->n_req && c->inflight.empty() &&
-            c->ctx->knobs.coalescer_rejoin) {
-            const int f = s->queue;
-            const bool on = c->rejoin_score[f] >= 0.5 || (++c->rejoin_probe[f] & 15u) == 0;
-            if (on) {
-                c->rejoin_n[f] = s->n_req;
-                c->rejoin_target[f] = c->queue[f].size() + s->n_req;
-                c->rejoin_until[f] = Clock::now() + std::chrono::microseconds(50 + (int)(c->ctx->knobs.coalescer_rejoin_us_per_caller * s->n_req));
-            }
-        }
+            c->ctx->knobs.coalescer_rejoin)
+            c->policy[s->queue].on_completion(Clock::now(), s->n_req, c->queue[s->queue].size(), c->ctx->knobs.coalescer_rejoin_us_per_caller);
         c->stats.device_ms[(fl == kDpp && s->key.ssd) ? (int)kSsd : fl] += ms;
         if (replanned) c->stats.replans++;
         std::vector<Req*> orphans;
@@ -946,16 +938,7 @@ int submit_and_wait_inner(pg_coalescer* c, Req* r) {
         }
         c->queue[r->queue].push_back(r);
         if (r->queue >= kQRank0) c->queue_items[r->queue] += r->n;
-        const int f = r->queue;
-        if (c->seen_arrival[f]) {
-            double gap = std::chrono::duration<double, std::micro>(r->arrived - c->last_arrival[f]).count();
-            gap = gap < 0.0 ? 0.0 : (gap > 1e5 ? 1e5 : gap);
-            c->gap_ewma_us[f] = 0.75 * c->gap_ewma_us[f] + 0.25 * gap;
-        } else {
-            c->seen_arrival[f] = true;
-            c->gap_ewma_us[f] = 0.0;                   // (the first request waits: nothing is known yet)
-        }
-        c->last_arrival[f] = r->arrived;
+        c->policy[r->queue].on_arrival(r->arrived);
     }
     c->cv_dispatch.notify_one();
     const bool timed = c->timeout_us != 0;
@@ -1026,6 +1009,36 @@ void destroy_partial(pg_coalescer* c) {
     delete c;
 }
 
+// What both creators share.  The batching defaults of a pg_coalescer_config (0 = default; default_batch: what one pass serves):
+void config_defaults(pg_coalescer* c, const pg_coalescer_config* cfg, uint32_t default_batch) {
+    c->max_batch = cfg->max_batch ? cfg->max_batch : default_batch;
+    c->max_wait_us = cfg->max_wait_us ? cfg->max_wait_us : 100;
+    c->depth = cfg->depth ? cfg->depth : 2;
+    c->timeout_us = cfg->timeout_us;
+}
+
+// `depth` slots, alternating between the context and its sibling (where there is one); on failure the caller's destroy_partial
+// frees the slots made so far
+int alloc_slots(pg_coalescer* c) {
+    for (uint32_t i = 0; i < c->depth; ++i) {
+        Slot* s = new Slot();
+        s->id = (int)i;
+        s->ctx = (c->sibling && (i & 1)) ? c->sibling : c->ctx;
+        if (const int rc = alloc_slot(c, s)) {
+            free_slot(c, s);
+            return rc;
+        }
+        c->slots.push_back(s);
+        c->free_slots.push_back(s);
+    }
+    return PG_OK;
+}
+
+void start_workers(pg_coalescer* c) {
+    c->dispatcher = std::thread(dispatcher_main, c);
+    c->completer = std::thread(completer_main, c);
+}
+
 }  // namespace
 }  // namespace pg
 
@@ -1078,44 +1091,56 @@ int pg_coalescer_create_scene(pg_ctx* ctx, const pg_table* t, const pg_scene_con
         PG_REQUIRE(sc->dpp.norm_relevance_score >= 0 && sc->dpp.norm_relevance_score <= 2, "pg_coalescer_create: dpp.norm_relevance_score must be 0, 1 or 2");
     }
     PG_HIP(hipSetDevice(ctx->device));
+    // score planes and their RankScore names: "<algo>" or, per output of a multi-output model, "<algo>_<output>"
+    // (rank_service.go:315-319)
+    int plane0[pg::kMaxAlgos] = {0, 1, 2, 3}, n_planes = 0;
+    uint32_t max_heads = 1;
+    std::vector<std::string> plane_names;
+    for (uint32_t a = 0; a < sc->n_algos; ++a) {
+        const pg_rank_algo& al = sc->algos[a];
+        const uint32_t heads = al.model->n_out;
+        plane0[a] = n_planes;
+        // (for EVERY algorithm, before its names are pushed: a single-output one behind models that already fill the
+        // planes would write past names[] below — ADVICE r4)
+        PG_REQUIRE(n_planes + (int)heads <= pg::kMaxPlanes, "pg_coalescer_create: the scene's models have more than %d outputs together", pg::kMaxPlanes);
+        if (heads > 1) {
+            for (uint32_t o = 0; o < heads; ++o) {
+                // (no names given: "<algo>_0", "<algo>_1", … — enough for a scene that only ranks)
+                const char* on = al.output_names ? al.output_names[o] : nullptr;
+                PG_REQUIRE(!al.output_names || (on && on[0]), "pg_coalescer_create: \"%s\": output %u has no name", al.name, o);
+                plane_names.push_back(std::string(al.name) + "_" + (on ? std::string(on) : std::to_string(o)));
+            }
+        } else {
+            plane_names.push_back(al.name);
+        }
+        n_planes += (int)heads;
+        max_heads = std::max(max_heads, heads);
+    }
+    const char* names[pg::kMaxPlanes] = {nullptr};
+    for (int p_ = 0; p_ < n_planes; ++p_) names[p_] = plane_names[(size_t)p_].c_str();
+    pg::ExprHold binding;            // (no score rewrite may be attached between the binding and the coalescer's own hold)
+    binding.take(sc->rank_score);
+    std::vector<int> var_src;
+    int rc;
+    if (sc->rank_score && (rc = pg::recommend_bind_vars(sc->rank_score, names, n_planes, &var_src, "pg_coalescer_create"))) return rc;
+    uint32_t max_exclude;
+    {
+        std::lock_guard<std::mutex> g(ctx->mu);
+        max_exclude = ctx->knobs.coalescer_max_exclude;
+    }
+    if (max_exclude && cfg->k + max_exclude > 16384) {
+        pg::set_error("pg_coalescer_create: k=%u plus coalescer_max_exclude=%u exceeds the recalls' depth of 16384", cfg->k, max_exclude);
+        return PG_ERR_UNSUPPORTED;
+    }
+    // every check that needs no allocation has passed: from here on the one failure exit is destroy_partial
     pg_coalescer* c = new pg_coalescer();
     c->ctx = ctx;
     c->t = t;
     c->trigger_table = trig;
     c->query_model = sc->query_model;
     c->n_algos = (int)sc->n_algos;
-    // score planes and their RankScore names: "<algo>" or, per output of a multi-output model, "<algo>_<output>"
-    // (rank_service.go:315-319)
-    const char* names[pg::kMaxPlanes] = {nullptr};
     for (int a = 0; a < c->n_algos; ++a) {
-        const uint32_t heads = sc->algos[a].model->n_out;
-        c->plane0[a] = c->n_planes;
-        // (for EVERY algorithm, before its names are pushed: a single-output one behind models that already fill the
-        // planes would write past names[] below — ADVICE r4)
-        if (c->n_planes + (int)heads > pg::kMaxPlanes) {
-            pg::set_error("pg_coalescer_create: the scene's models have more than %d outputs together", pg::kMaxPlanes);
-            delete c;
-            return PG_ERR_INVALID;
-        }
-        if (heads > 1) {
-            for (uint32_t o = 0; o < heads; ++o) {
-                // (no names given: "<algo>_0", "<algo>_1", … — enough for a scene that only ranks)
-                const char* on = sc->algos[a].output_names ? sc->algos[a].output_names[o] : nullptr;
-                if (sc->algos[a].output_names && (!on || !on[0])) {
-                    pg::set_error("pg_coalescer_create: \"%s\": output %u has no name", sc->algos[a].name, o);
-                    delete c;
-                    return PG_ERR_INVALID;
-                }
-                c->plane_names.push_back(std::string(sc->algos[a].name) + "_" + (on ? std::string(on) : std::to_string(o)));
-            }
-        } else {
-            c->plane_names.push_back(sc->algos[a].name);
-        }
-        c->n_planes += (int)heads;
-        c->max_heads = std::max(c->max_heads, heads);
-    }
-    for (int p_ = 0; p_ < c->n_planes; ++p_) names[p_] = c->plane_names[(size_t)p_].c_str();
-    for (int a = 0; a < c->n_algos; ++a) {
+        c->plane0[a] = plane0[a];
         c->algos[a].m = sc->algos[a].model;
         c->algos[a].fs = sc->algos[a].features;
         c->algos[a].irows = sc->algos[a].item_rows;
@@ -1123,33 +1148,20 @@ int pg_coalescer_create_scene(pg_ctx* ctx, const pg_table* t, const pg_scene_con
             for (uint32_t f = 0; f < sc->algos[a].model->nif && f < 16; ++f) c->algos[a].item_field_cols[f] = sc->algos[a].item_field_cols[f];
         c->algo_names[a] = sc->algos[a].name;
     }
+    c->n_planes = n_planes;
+    c->max_heads = max_heads;
+    c->plane_names.swap(plane_names);
     c->e = sc->rank_score;
     c->e_hold.take(c->e);
-    int rc;
-    if (c->e && (rc = pg::recommend_bind_vars(c->e, names, c->n_planes, &c->var_src, "pg_coalescer_create"))) {
-        delete c;
-        return rc;
-    }
+    c->var_src.swap(var_src);
     c->rerank.kind = sc->rerank;
     c->rerank.candidates = sc->rerank_candidates;
     c->rerank.dpp = sc->dpp;
     c->k = cfg->k;
-    {
-        std::lock_guard<std::mutex> g(ctx->mu);
-        c->max_exclude = ctx->knobs.coalescer_max_exclude;
-    }
-    if (c->max_exclude && cfg->k + c->max_exclude > 16384) {
-        pg::set_error("pg_coalescer_create: k=%u plus coalescer_max_exclude=%u exceeds the recalls' depth of 16384", cfg->k, c->max_exclude);
-        delete c;
-        return PG_ERR_UNSUPPORTED;
-    }
-    c->max_batch = cfg->max_batch ? cfg->max_batch : max_q;
-    c->max_wait_us = cfg->max_wait_us ? cfg->max_wait_us : 100;
-    for (double& sc : c->rejoin_score) sc = 1.0;     // (optimistic: callers are closed loops until they show otherwise)
-    c->depth = cfg->depth ? cfg->depth : 2;
+    c->max_exclude = max_exclude;
+    pg::config_defaults(c, cfg, max_q);
     c->max_top_n = max_top_n;
     c->max_rank_items = cfg->max_rank_items ? cfg->max_rank_items : cfg->k;
-    c->timeout_us = cfg->timeout_us;
     c->dim = t->dim;
     c->vec_w = std::max(t->dim, d_user_max);
     c->ufid_stride = nuf_max;
@@ -1174,17 +1186,9 @@ int pg_coalescer_create_scene(pg_ctx* ctx, const pg_table* t, const pg_scene_con
         std::lock_guard<std::mutex> g(ctx->mu);
         c->sibling->knobs = ctx->knobs;
     }
-    for (uint32_t i = 0; i < c->depth; ++i) {
-        pg::Slot* s = new pg::Slot();
-        s->id = (int)i;
-        s->ctx = (c->sibling && (i & 1)) ? c->sibling : ctx;
-        if ((rc = pg::alloc_slot(c, s))) {
-            pg::free_slot(c, s);
-            pg::destroy_partial(c);
-            return rc;
-        }
-        c->slots.push_back(s);
-        c->free_slots.push_back(s);
+    if ((rc = pg::alloc_slots(c))) {
+        pg::destroy_partial(c);
+        return rc;
     }
     // build the table's shadow now rather than inside the first batch
     {
@@ -1194,8 +1198,7 @@ int pg_coalescer_create_scene(pg_ctx* ctx, const pg_table* t, const pg_scene_con
             return rc;
         }
     }
-    c->dispatcher = std::thread(pg::dispatcher_main, c);
-    c->completer = std::thread(pg::completer_main, c);
+    pg::start_workers(c);
     *out = c;
     return PG_OK;
 }
@@ -1244,21 +1247,25 @@ int pg_coalescer_destroy(pg_coalescer* c) {
     return PG_OK;
 }
 
-static int coalescer_recall_common(pg_coalescer* c, pg::Req* r, uint64_t* out_rows, float* out_scores, uint32_t* out_count) {
+// Every recall entry point: queue the request on `queue`, copy its slice out of the batch's RecallImage.  The count is the job's
+// status word of the request — for a recall with exclusions the compacted count in the image (the status words count the
+// over-fetched answer).
+static int coalescer_recall_common(pg_coalescer* c, pg::Req* r, int queue, uint64_t* out_rows, float* out_scores, uint32_t* out_count) {
     if (c->group) {
         delete r;
         pg::set_error("pg_coalescer: a coalescer over a shard group serves pg_coalescer_recommend only");
         return PG_ERR_UNSUPPORTED;
     }
-    r->queue = pg::kQRecall;
+    r->queue = queue;
     int rc;
     if ((rc = pg::submit_and_wait(c, r))) return rc;
     pg::Slot* s = r->slot;
     if (r->rc == PG_OK) {
-        const size_t k = c->k;
-        memcpy(out_rows, s->h_out + (size_t)r->index * k * 8, k * 8);
-        memcpy(out_scores, s->h_out + (size_t)c->max_batch * k * 8 + (size_t)r->index * k * 4, k * 4);
-        if (out_count) *out_count = s->run->h_status[1 + r->index];
+        const pg::RecallImage im = pg::recall_image(c);
+        memcpy(out_rows, im.rows_of(s->h_out, r->index), im.k * 8);
+        memcpy(out_scores, im.scores_of(s->h_out, r->index), im.k * 4);
+        if (out_count && queue == pg::kQRecallEx) memcpy(out_count, im.count_of(s->h_out, r->index), 4);
+        else if (out_count) *out_count = s->run->h_status[1 + r->index];
     }
     return pg::finish_call(c, r);
 }
@@ -1269,40 +1276,22 @@ int pg_coalescer_recall(pg_coalescer* c, const float* query, uint64_t* out_rows,
     pg::Req* r = new pg::Req();
     r->vec = query;
     r->qkind = pg::kVector;
-    return coalescer_recall_common(c, r, out_rows, out_scores, out_count);
+    return coalescer_recall_common(c, r, pg::kQRecall, out_rows, out_scores, out_count);
 }
 
 int pg_coalescer_recall_l2(pg_coalescer* c, const float* query, uint64_t* out_rows, float* out_dist, uint32_t* out_count) {
     PG_REQUIRE(c && query && out_rows && out_dist, "pg_coalescer_recall_l2: NULL argument");
     PG_REQUIRE(c->dim == 64 || c->dim == 128, "pg_coalescer_recall_l2: dim %u unsupported (64 or 128)", c->dim);
-    if (c->group) {
-        pg::set_error("pg_coalescer: a coalescer over a shard group serves pg_coalescer_recommend only");
-        return PG_ERR_UNSUPPORTED;
-    }
     pg::Req* r = new pg::Req();
     r->vec = query;
     r->qkind = pg::kVector;
-    r->queue = pg::kQRecallL2;
-    int rc;
-    if ((rc = pg::submit_and_wait(c, r))) return rc;
-    pg::Slot* s = r->slot;
-    if (r->rc == PG_OK) {
-        const size_t k = c->k;
-        memcpy(out_rows, s->h_out + (size_t)r->index * k * 8, k * 8);
-        memcpy(out_dist, s->h_out + (size_t)c->max_batch * k * 8 + (size_t)r->index * k * 4, k * 4);
-        if (out_count) *out_count = s->run->h_status[1 + r->index];
-    }
-    return pg::finish_call(c, r);
+    return coalescer_recall_common(c, r, pg::kQRecallL2, out_rows, out_dist, out_count);
 }
 
 int pg_coalescer_recall_exclude(pg_coalescer* c, const float* query, const uint64_t* excl_rows, uint32_t n_excl, uint64_t* out_rows,
                                 float* out_scores, uint32_t* out_count) {
     PG_REQUIRE(c && query && out_rows && out_scores && (excl_rows || n_excl == 0), "pg_coalescer_recall_exclude: NULL argument");
-    if (c->group) {
-        pg::set_error("pg_coalescer: a coalescer over a shard group serves pg_coalescer_recommend only");
-        return PG_ERR_UNSUPPORTED;
-    }
-    if (!c->max_exclude || n_excl > c->max_exclude) {
+    if (!c->group && (!c->max_exclude || n_excl > c->max_exclude)) {       // (a group coalescer answers with its own refusal)
         pg::set_error("pg_coalescer_recall_exclude: a list of %u ids; the coalescer was created with coalescer_max_exclude = %u", n_excl, c->max_exclude);
         return PG_ERR_UNSUPPORTED;
     }
@@ -1311,17 +1300,7 @@ int pg_coalescer_recall_exclude(pg_coalescer* c, const float* query, const uint6
     r->qkind = pg::kVector;
     r->excl = excl_rows;
     r->n = n_excl;
-    r->queue = pg::kQRecallEx;
-    int rc;
-    if ((rc = pg::submit_and_wait(c, r))) return rc;
-    pg::Slot* s = r->slot;
-    if (r->rc == PG_OK) {
-        const size_t k = c->k;
-        memcpy(out_rows, s->h_out + (size_t)r->index * k * 8, k * 8);
-        memcpy(out_scores, s->h_out + (size_t)c->max_batch * k * 8 + (size_t)r->index * k * 4, k * 4);
-        if (out_count) memcpy(out_count, s->h_out + (size_t)c->max_batch * k * 12 + (size_t)r->index * 4, 4);
-    }
-    return pg::finish_call(c, r);
+    return coalescer_recall_common(c, r, pg::kQRecallEx, out_rows, out_scores, out_count);
 }
 
 int pg_coalescer_i2i_recall(pg_coalescer* c, uint32_t trigger_row, uint64_t* out_rows, float* out_scores,
@@ -1333,7 +1312,7 @@ int pg_coalescer_i2i_recall(pg_coalescer* c, uint32_t trigger_row, uint64_t* out
     pg::Req* r = new pg::Req();
     r->qkind = pg::kTrigger;
     r->trigger_row = trigger_row;
-    return coalescer_recall_common(c, r, out_rows, out_scores, out_count);
+    return coalescer_recall_common(c, r, pg::kQRecall, out_rows, out_scores, out_count);
 }
 
 int pg_coalescer_online_recall(pg_coalescer* c, const float* user_vec, uint64_t* out_rows, float* out_scores,
@@ -1343,7 +1322,7 @@ int pg_coalescer_online_recall(pg_coalescer* c, const float* user_vec, uint64_t*
     pg::Req* r = new pg::Req();
     r->vec = user_vec;
     r->qkind = pg::kOnline;
-    return coalescer_recall_common(c, r, out_rows, out_scores, out_count);
+    return coalescer_recall_common(c, r, pg::kQRecall, out_rows, out_scores, out_count);
 }
 
 int pg_coalescer_rank(pg_coalescer* c, uint32_t algo, const float* user_vec, const int32_t* user_field_ids,
@@ -1372,9 +1351,11 @@ int pg_coalescer_rank(pg_coalescer* c, uint32_t algo, const float* user_vec, con
     r->n = n;
     int rc;
     if ((rc = pg::submit_and_wait(c, r))) return rc;
-    if (r->rc == PG_OK)                                  // head o: out_scores[o * n ..), from plane o of the batch image
+    if (r->rc == PG_OK) {                                // head o: out_scores[o * n ..), from plane o of the batch image
+        const pg::RankImage im{r->slot->n_items};
         for (uint32_t o = 0; o < m->n_out; ++o)
-            memcpy(out_scores + (size_t)o * n, r->slot->h_out + ((size_t)o * r->slot->n_items + r->item0) * 4, (size_t)n * 4);
+            memcpy(out_scores + (size_t)o * n, r->slot->h_out + im.plane(o) + (size_t)r->item0 * 4, (size_t)n * 4);
+    }
     return pg::finish_call(c, r);
 }
 
@@ -1424,26 +1405,22 @@ static int coalescer_recommend_common(pg_coalescer* c, const float* user_vec, co
     pg::Slot* s = r->slot;
     if (r->rc == PG_OK && c->group) {
         const size_t o = (size_t)r->index * s->n_items;                 // the step's pages are [n_req][batch top_n]
-        memcpy(out_rows, s->g_rows + o, (size_t)top_n * 8);
-        memcpy(out_fused, s->g_fus + o, (size_t)top_n * 8);
-        memcpy(out_recall_scores, s->g_rec + o, (size_t)top_n * 4);
-        memcpy(out_rank_scores, s->g_rnk + o, (size_t)top_n * 4);
+        memcpy(out_rows, s->g_rows.data() + o, (size_t)top_n * 8);
+        memcpy(out_fused, s->g_fus.data() + o, (size_t)top_n * 8);
+        memcpy(out_recall_scores, s->g_rec.data() + o, (size_t)top_n * 4);
+        memcpy(out_rank_scores, s->g_rnk.data() + o, (size_t)top_n * 4);
         if (out_count) *out_count = std::min(top_n, s->g_cnt[r->index]);
     } else if (r->rc == PG_OK) {
         const size_t nq_top = (size_t)s->n_items;                       // page width of the batch's image: planes are [n_req][nq_top]
-        const uint32_t* counts = (const uint32_t*)(s->h_out + pg::page_bytes(c));
-        const uint32_t* pick_counts = counts + c->max_batch;
-        const uint32_t batch = s->n_req;
-        const size_t np = (size_t)batch * nq_top;
-        const uint64_t* p_rows = (const uint64_t*)s->h_out;
-        const double* p_fused = (const double*)(p_rows + np);
-        const float* p_recall = (const float*)(p_fused + np);
-        const float* p_rank = p_recall + np;
+        const pg::RecommendImage im = pg::recommend_image(c);
+        const uint32_t* counts = (const uint32_t*)(s->h_out + im.counts);
+        const uint32_t* pick_counts = (const uint32_t*)(s->h_out + im.pick_counts);
+        const pg::PageView page(s->h_out, (size_t)s->n_req * nq_top);
         const size_t o = (size_t)r->index * nq_top;
-        memcpy(out_rows, p_rows + o, (size_t)top_n * 8);
-        memcpy(out_fused, p_fused + o, (size_t)top_n * 8);
-        memcpy(out_recall_scores, p_recall + o, (size_t)top_n * 4);
-        for (int a = 0; a < rank_planes; ++a) memcpy(out_rank_scores + (size_t)a * top_n, p_rank + (size_t)a * np + o, (size_t)top_n * 4);
+        memcpy(out_rows, page.rows + o, (size_t)top_n * 8);
+        memcpy(out_fused, page.fused + o, (size_t)top_n * 8);
+        memcpy(out_recall_scores, page.recall + o, (size_t)top_n * 4);
+        for (int a = 0; a < rank_planes; ++a) memcpy(out_rank_scores + (size_t)a * top_n, page.rank_plane(a) + o, (size_t)top_n * 4);
         if (out_count) {
             uint32_t cnt = std::min(top_n, counts[r->index]);
             if (c->rerank.kind) cnt = std::min(cnt, pick_counts[r->index]);
@@ -1512,9 +1489,10 @@ int pg_coalescer_dpp(pg_coalescer* c, const uint32_t* cand_rows, const double* r
     if ((rc = pg::submit_and_wait(c, r))) return rc;
     pg::Slot* s = r->slot;
     if (r->rc == PG_OK) {
+        const pg::DppImage im = pg::dpp_image(c);
         const uint32_t topn = s->key.topn;
-        const uint32_t cnt = std::min(topn, s->h_dout[c->dpp_item_cap + r->index]);
-        memcpy(out_idx, s->h_dout + (size_t)r->index * topn, (size_t)cnt * 4);
+        const uint32_t cnt = std::min(topn, s->h_dout[im.counts + r->index]);
+        memcpy(out_idx, s->h_dout + im.picks_of(r->index, topn), (size_t)cnt * 4);
         *out_count = cnt;
     }
     return pg::finish_call(c, r);
@@ -1566,7 +1544,7 @@ int pg_coalescer_ssd(pg_coalescer* c, const uint32_t* cand_rows, const double* r
     pg::Slot* s = r->slot;
     if (r->rc == PG_OK) {
         const uint32_t T = s->key.topn;
-        memcpy(out_idx, s->h_dout + (size_t)r->index * T, (size_t)T * 4);
+        memcpy(out_idx, s->h_dout + pg::dpp_image(c).picks_of(r->index, T), (size_t)T * 4);
         *out_count = T;
     }
     return pg::finish_call(c, r);
@@ -1606,6 +1584,7 @@ int pg_coalescer_create_group(pg_group* g, const pg_expr* e, const char* rank_va
     std::vector<int> src;
     int rc;
     if ((rc = pg::recommend_bind_vars(e, names, 1, &src, "pg_coalescer_create_group"))) return rc;
+    PG_HIP(hipSetDevice(pg_group_ctx(g, 0)->device));
     pg_coalescer* c = new pg_coalescer();
     c->group = g;
     c->gplan = *plan;
@@ -1614,29 +1593,15 @@ int pg_coalescer_create_group(pg_group* g, const pg_expr* e, const char* rank_va
     c->e = e;
     c->e_hold.take(e);
     c->k = plan->k;
-    c->max_batch = cfg->max_batch ? cfg->max_batch : (uint32_t)pg::kMaxQueries;
-    c->max_wait_us = cfg->max_wait_us ? cfg->max_wait_us : 100;
-    for (double& sc : c->rejoin_score) sc = 1.0;     // (optimistic: callers are closed loops until they show otherwise)
-    c->depth = cfg->depth ? cfg->depth : 2;
+    pg::config_defaults(c, cfg, (uint32_t)pg::kMaxQueries);
     c->max_top_n = cfg->max_top_n ? cfg->max_top_n : std::min<uint32_t>(plan->k, 1000);
     if (plan->dpp_candidates && c->max_top_n > plan->dpp_candidates) c->max_top_n = plan->dpp_candidates;   // DPP candidates must not depend on the request
-    c->timeout_us = cfg->timeout_us;
     c->dim = dim;
-    PG_HIP(hipSetDevice(c->ctx->device));
-    for (uint32_t i = 0; i < c->depth; ++i) {
-        pg::Slot* s = new pg::Slot();
-        s->id = (int)i;
-        s->ctx = c->ctx;
-        if ((rc = pg::alloc_slot(c, s))) {
-            pg::free_slot(c, s);
-            pg::destroy_partial(c);
-            return rc;
-        }
-        c->slots.push_back(s);
-        c->free_slots.push_back(s);
+    if ((rc = pg::alloc_slots(c))) {
+        pg::destroy_partial(c);
+        return rc;
     }
-    c->dispatcher = std::thread(pg::dispatcher_main, c);
-    c->completer = std::thread(pg::completer_main, c);
+    pg::start_workers(c);
     *out = c;
     return PG_OK;
 }

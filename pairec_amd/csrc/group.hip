@@ -938,11 +938,7 @@ int pg_group_recommend_end(pg_group* g, pg_group_ticket* tk, uint64_t* out_rows,
         for (uint32_t s_ = 0; s_ < G && !rc; ++s_) {
             const pg::Lane& l = g->sh[s_].lane[L];
             const uint32_t nqs = s_ < nq ? (nq - s_ + G - 1) / G : 0u;
-            const size_t np = (size_t)nqs * top_n;
-            const uint64_t* p_rows = (const uint64_t*)l.h_page;
-            const double* p_fused = (const double*)(p_rows + np);
-            const float* p_recall = (const float*)(p_fused + np);
-            const float* p_rank = p_recall + np;
+            const pg::PageView page(l.h_page, (size_t)nqs * top_n);
             for (uint32_t i = 0; i < nqs; ++i) {
                 const uint32_t q = s_ + i * G;
                 if (l.h_flags[i]) {
@@ -950,10 +946,10 @@ int pg_group_recommend_end(pg_group* g, pg_group_ticket* tk, uint64_t* out_rows,
                     rc = PG_ERR_ARITH;
                     break;
                 }
-                memcpy(out_rows + (size_t)q * top_n, p_rows + (size_t)i * top_n, (size_t)top_n * 8);
-                memcpy(out_fused + (size_t)q * top_n, p_fused + (size_t)i * top_n, (size_t)top_n * 8);
-                memcpy(out_recall_scores + (size_t)q * top_n, p_recall + (size_t)i * top_n, (size_t)top_n * 4);
-                memcpy(out_rank_scores + (size_t)q * top_n, p_rank + (size_t)i * top_n, (size_t)top_n * 4);
+                memcpy(out_rows + (size_t)q * top_n, page.rows + (size_t)i * top_n, (size_t)top_n * 8);
+                memcpy(out_fused + (size_t)q * top_n, page.fused + (size_t)i * top_n, (size_t)top_n * 8);
+                memcpy(out_recall_scores + (size_t)q * top_n, page.recall + (size_t)i * top_n, (size_t)top_n * 4);
+                memcpy(out_rank_scores + (size_t)q * top_n, page.rank + (size_t)i * top_n, (size_t)top_n * 4);
                 if (out_count) out_count[q] = C ? l.h_flags[512 + i] : std::min(top_n, l.h_flags[256 + i]);
             }
         }

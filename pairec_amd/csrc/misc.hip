@@ -117,19 +117,14 @@ int gather_global_rows_launch(hipStream_t st, const pg_table* t, const uint64_t*
     return PG_OK;
 }
 
-size_t page_entry_bytes(int n_algos) { return 20 + 4 * (size_t)n_algos; }
-
 int page_launch(hipStream_t st, const uint32_t* d_order, const uint32_t* d_pick, const uint32_t* d_pick_cnt,
                 const uint64_t* d_rows, const float* d_recall, const float* d_rank, size_t rank_stride, int n_algos,
                 const double* d_fused, uint32_t nq, uint32_t k, uint32_t top_n, char* d_page) {
     const size_t np = (size_t)nq * top_n;
     if (np == 0) return PG_OK;
-    uint64_t* p_rows = (uint64_t*)d_page;
-    double* p_fused = (double*)(p_rows + np);
-    float* p_recall = (float*)(p_fused + np);
-    float* p_rank = p_recall + np;
+    const PageView page(d_page, np);
     page_kernel<<<(uint32_t)((np + 255) / 256), 256, 0, st>>>(d_order, d_pick, d_pick_cnt, d_rows, d_recall, d_rank, rank_stride, n_algos,
-                                                             d_fused, nq, k, top_n, p_rows, p_fused, p_recall, p_rank);
+                                                             d_fused, nq, k, top_n, page.rows, page.fused, page.recall, page.rank);
     PG_HIP(hipGetLastError());
     return PG_OK;
 }

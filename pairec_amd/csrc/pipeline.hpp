@@ -139,8 +139,20 @@ int sorted_head_launch(hipStream_t st, const uint32_t* d_order, const uint64_t* 
 int gather_global_rows_launch(hipStream_t st, const pg_table* t, const uint64_t* d_global_rows, uint32_t n, float* d_out);
 // The page of every request: entry order[q][pick[q][p]] (pick = NULL: p itself) of its list, p < top_n, as planes
 // [nq][top_n]: rows u64 | fused f64 | recall f32 | n_algos x rank f32.  Entries beyond pick_cnt[q] are padding
-// (row = UINT64_MAX, fused = NaN, recall = -inf, rank = 0).
-size_t page_entry_bytes(int n_algos);
+// (row = UINT64_MAX, fused = NaN, recall = -inf, rank = 0).  PageView is that layout, carved from the image's base and
+// np = nq * top_n: page_launch writes through it, the coalescer and the shard group read their host copies through it.
+struct PageView {
+    uint64_t* rows;
+    double* fused;
+    float* recall;
+    float* rank;                     // rank_plane(0)
+    size_t np;
+    PageView(void* base, size_t np_)
+        : rows((uint64_t*)base), fused((double*)(rows + np_)), recall((float*)(fused + np_)), rank(recall + np_), np(np_) {}
+    float* rank_plane(int a) const { return rank + (size_t)a * np; }
+    static constexpr size_t entry_bytes(int n_algos) { return sizeof(uint64_t) + sizeof(double) + sizeof(float) + sizeof(float) * (size_t)n_algos; }
+};
+inline size_t page_entry_bytes(int n_algos) { return PageView::entry_bytes(n_algos); }
 int page_launch(hipStream_t st, const uint32_t* d_order, const uint32_t* d_pick, const uint32_t* d_pick_cnt,
                 const uint64_t* d_rows, const float* d_recall, const float* d_rank, size_t rank_stride, int n_algos,
                 const double* d_fused, uint32_t nq, uint32_t k, uint32_t top_n, char* d_page);
