@@ -686,6 +686,68 @@ int pg_i2i_recall_exclude(pg_ctx* ctx, const pg_table* trigger_table, const uint
                           uint32_t k, int exclude_trigger, const uint64_t* excl_rows, const uint32_t* excl_offsets,
                           uint64_t* out_rows, float* out_scores, uint32_t* out_count);
 
+/* ---- ColdStartRecall (csrc/coldstart.hip, csrc/coldstart_host.hpp) ---------------------------------
+ * ColdStartRecall.GetCandidateItems runs `SELECT pk FROM t WHERE <WhereClause> ORDER BY <OrderBy | random()> LIMIT n`
+ * (module/cold_start_recall_hologres_dao.go:48,76-80,116-153; without a clause every row, cold_start_recall_featurestore_dao.go:
+ * 155-169).  pg_cold turns "the rows a clause admits" into a recall answer on the device, in both orders.
+ *   create    needs no GPU.  w: the compiled clause, BORROWED (the caller may share it with its vector recalls: one bitmap serves
+ *             both) and not to be freed before the pg_cold; NULL = every row of the table.  order_by: NULL, "" or random() in
+ *             any case = the random order; otherwise `column`, `column ASC` or `column DESC` (keywords in any case, one column
+ *             [A-Za-z_][A-Za-z0-9_]*), the name kept and resolved in `fs` at each use.  Anything else — two columns, an
+ *             expression, NULLS FIRST — is PG_ERR_PARSE with the 0-based byte position in pg_last_error() ("... at position N").
+ *   Pool      the rows r < rows whose bit is set in the clause's bitmap (pg_where: bit r & 31 of word r >> 5; a one-comparison
+ *             clause's bitmap is built too).  sel(j) is the j-th admitted row in ascending row order, 0 <= j < A.
+ *   Random    request q with seed[q] (NULL: 0 for every request) gets slot i = row_offset + sel(P(i)), i < min(k, A), where P
+ *             is a keyed bijection of [0, A): b = the smallest even integer >= 2 with 2^b >= A, h = b / 2, mask = 2^h - 1; one
+ *             application on x < 2^b splits (L, R) = (x >> h, x & mask), runs for r = 0 .. 7
+ *                 (L, R) <- (R, L ^ (mix(seed + 0x9E3779B97F4A7C15 * (1 + r * 2^32 + R)) & mask))          (uint64 arithmetic,
+ *             mix = the splitmix64 finaliser of pg_mix_sort's draw) and returns (L << h) | R; P(i) applies it to i and again to
+ *             the result while that is >= A (cycle walking: a bijection returns to [0, A); 2^b < 4 A, so fewer than four
+ *             applications are expected).  Hence: the ids of a request are distinct; with k >= A a request's answer is a
+ *             permutation of the pool; and the answer at depth k is a PREFIX of the answer at any larger depth — over-fetching
+ *             by the longest exclusion list and pg_exclude_compact_dev give the first k unseen items of the same sequence.
+ *             Go's math/rand and Postgres's random() are not reproduced (as with pg_mix_sort's random_position).
+ *   Ordered   key of a row = its column value (I32, I64, F32 or F64) as an order-preserving unsigned integer: integers with the
+ *             sign bit flipped; floats with -0.0 taken as +0.0 and the usual total-order transform, every NaN greater than every
+ *             number and equal to every other NaN (Postgres: first under DESC, last under ASC); F32 orders as its exactly widened
+ *             value.  The answer is the admitted rows by (key ascending or descending, then row ascending) cut to min(k, A): ties
+ *             break by row.  It is the same for every request of the call, computed once, written nq times; seeds are ignored.
+ *   Out       every recall's shape (a pg_fanin_source with score_f64 = 0): out_rows [nq][k] global ids then UINT64_MAX,
+ *             out_scores [nq][k] 0.0f (module.NewItem leaves Score zero) then -inf, out_count[q] (optional) = min(k, A).  A = 0
+ *             is PG_OK with all padding (the reference returns an empty list).
+ *   Limits    1 <= nq <= 256 (else PG_ERR_INVALID), 1 <= k <= 16384 and 1 <= rows < 2^32, no filtered view (PG_ERR_UNSUPPORTED);
+ *             fs must cover the table's rows and hold the clause's columns (pg_where's Binding rules) and the order column, numeric
+ *             with values (PG_ERR_INVALID); fs may be NULL for a random order without a clause.  Refusals are made on the host,
+ *             nothing enqueued, the context left usable.
+ *   host      pg_cold_recall_host states the answer on host arrays (bits NULL = every row; order_col / order_dtype the ordered
+ *             column's values and PG_F_* type, unused for the random order); the device calls reproduce it bit for bit.
+ *   Stream    the pg_cold keeps, per bitmap epoch, the admitted count of every 1 024-row block and its exclusive scan (4 B per
+ *             block) beside a reference to the bitmap.  With both current pg_cold_recall_dev only enqueues on the context's stream
+ *             and reads nothing back — A comes from the bitmap's build (the `_dev` scratch exception of pg_fanin_merge_dev
+ *             applies).  A call that has to build the bitmap or the prefix synchronises the stream, as a pg_where build does; a
+ *             call that REPLACES the kept pair first waits for the whole device, so a kernel enqueued earlier never reads freed
+ *             memory, and an answer enqueued before a column write is the old columns' answer.  Contexts and threads may share a
+ *             pg_cold: builds are serialised.  pg_cold_recall takes host arrays: upload, run, download, synchronise.
+ *             pg_cold_free waits for the device; it must not run while a call uses the pg_cold.
+ *   stats     prefix builds and uses that found it current, device bytes held (prefix; without a clause the all-rows bitmap
+ *             too), the bitmap's epoch (0 without a clause) and the rows it admits. */
+typedef struct pg_cold pg_cold;
+typedef struct {
+    uint64_t prefix_builds, prefix_hits;
+    uint64_t bytes;
+    uint64_t epoch, admitted;
+} pg_cold_stats_t;
+int pg_cold_create(const pg_where* w, const char* order_by, pg_cold** out);
+int pg_cold_free(pg_cold* c);
+int pg_cold_recall_host(const pg_cold* c, const uint32_t* bits, uint64_t rows, uint64_t row_offset, const void* order_col,
+                        int order_dtype, const uint64_t* seed, uint32_t nq, uint32_t k, uint64_t* out_rows, float* out_scores,
+                        uint32_t* out_count);
+int pg_cold_recall_dev(pg_ctx* ctx, const pg_cold* c, const pg_table* t, const pg_features* fs, const uint64_t* d_seed,
+                       uint32_t nq, uint32_t k, uint64_t* d_out_rows, float* d_out_scores, uint32_t* d_out_count);
+int pg_cold_recall(pg_ctx* ctx, const pg_cold* c, const pg_table* t, const pg_features* fs, const uint64_t* seed, uint32_t nq,
+                   uint32_t k, uint64_t* out_rows, float* out_scores, uint32_t* out_count);
+int pg_cold_stats(const pg_cold* c, pg_cold_stats_t* out);
+
 /* Collaborative-filter recall (U2I2I) over a similarity table resident in HBM (csrc/cf.hip).
  * UserCollaborativeFilterRecall.GetCandidateItems (service/recall/user_collaborative_filter_recall.go:31-80) reads the user's
  * trigger items with their preference scores, expands them into their similar-item lists (swing / etrec) with four goroutines

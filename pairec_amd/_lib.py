@@ -65,6 +65,7 @@ EXPORTS = [
     "pg_candidates_classcut",
     "pg_mix_compile", "pg_mix_free", "pg_mix_num_strategies", "pg_mix_num_user_slots", "pg_mix_user_slot_name", "pg_mix_user_slot_is_float",
     "pg_mix_sort_host", "pg_mix_sort_dev", "pg_mix_sort", "pg_ssd_sort_dev",
+    "pg_cold_create", "pg_cold_free", "pg_cold_recall_host", "pg_cold_recall_dev", "pg_cold_recall", "pg_cold_stats",
 ]
 
 
@@ -87,6 +88,11 @@ class PgStats(C.Structure):
 class PgWhereStats(C.Structure):
     _fields_ = [("builds", C.c_uint64), ("hits", C.c_uint64), ("last_build_ms", C.c_double), ("bytes", C.c_uint64),
                 ("epoch", C.c_uint64), ("admitted", C.c_uint64)]
+
+
+class PgColdStats(C.Structure):
+    _fields_ = [("prefix_builds", C.c_uint64), ("prefix_hits", C.c_uint64), ("bytes", C.c_uint64), ("epoch", C.c_uint64),
+                ("admitted", C.c_uint64)]
 
 
 class PgIndexParams(C.Structure):
@@ -299,6 +305,12 @@ def load():
         "pg_where_bits": [vp, vp, vp, C.c_uint64, vp, P(C.c_uint64)],
         "pg_where_stats": [vp, P(PgWhereStats)],
         "pg_exclude_compact_dev": [vp, vp, vp, u32, u32, vp, vp, u32, C.c_float, vp, vp, vp],
+        "pg_cold_create": [vp, C.c_char_p, P(vp)],
+        "pg_cold_free": [vp],
+        "pg_cold_recall_host": [vp, vp, u64, u64, vp, i32, vp, u32, u32, vp, vp, vp],
+        "pg_cold_recall_dev": [vp, vp, vp, vp, vp, u32, u32, vp, vp, vp],
+        "pg_cold_recall": [vp, vp, vp, vp, vp, u32, u32, vp, vp, vp],
+        "pg_cold_stats": [vp, P(PgColdStats)],
         "pg_recall_topk_exclude": [vp, vp, vp, u32, u32, vp, vp, P(PgRecallExcludeOpts), vp, vp, vp],
         "pg_recall_topk_exclude_dev": [vp, vp, vp, u32, u32, vp, vp, P(PgRecallExcludeOpts), vp, vp, vp],
         "pg_i2i_recall_exclude": [vp, vp, vp, u32, vp, u32, i32, vp, vp, vp, vp, vp],

@@ -91,6 +91,7 @@ enum ScratchSlot : int {
     kSlotSsdStage = 30,      // ssd.hip pg_ssd_sort_dev: per-request counts and states, the position maps, the cut lists' rows and quality, the picks (kSlotWork stays the grid kernel's)
     kSlotDimcap = 31,        // dimcap.hip: the scratch tier's keys and counts of a value cap; the one-request entry's staging behind them
     kSlotRtU2I = 32,         // rtu2i.hip: the staged event offsets and clocks of a trigger stage; in pg_rtu2i_recall_dev the trigger lists between its two launches (cf.hip's expansion reads them while kSlotCf is its own)
+    kSlotCold = 33,          // coldstart.hip: the select's threshold state and digit histogram, per-block counts and their scan, the survivors and the ordered list of an ordered pool
     kSlotCount
 };
 
@@ -462,6 +463,10 @@ struct WhereServe {
 int where_clause_check(const char* who, const pg_ctx* ctx, const pg_table* t, const pg_features* fs, const pg_where* w, int metric,
                        const void* queries, const void* rows, const void* scores, uint32_t nq, uint32_t k);
 int where_clause_bind(const char* who, pg_ctx* ctx, const pg_table* t, const pg_features* fs, const pg_where* w, WhereServe* out);
+// where.hip: the clause's BITMAP over `rows` rows of `fs`, a one-comparison clause's too (coldstart.hip: the pool of a
+// ColdStartRecall): its columns resolved with where_resolve's rules, the bitmap built or found current; out->f.admitted is the
+// rows it admits, out->id.epoch its epoch.  Caller holds ctx->mu; a build synchronises.
+int where_bits_bind(const char* who, pg_ctx* ctx, const pg_where* w, const pg_features* fs, uint64_t rows, WhereServe* out);
 // exclude.hip: pg_exclude_compact_dev behind its checks (caller holds ctx->mu; enqueues one kernel, nothing synchronises)
 constexpr uint32_t kMaxExclude = 4096;      // ids in one request's list
 int exclude_compact_locked(pg_ctx* ctx, const uint64_t* d_rows, const float* d_scores, uint32_t nq, uint32_t k_in,

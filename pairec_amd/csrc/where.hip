@@ -669,6 +669,18 @@ int where_clause_bind(const char* who, pg_ctx* ctx, const pg_table* t, const pg_
     return PG_OK;
 }
 
+int where_bits_bind(const char* who, pg_ctx* ctx, const pg_where* w, const pg_features* fs, uint64_t rows, WhereServe* out) {
+    int cols[kMaxCols];
+    int rc;
+    if ((rc = where_resolve(who, w, fs, rows, cols))) return rc;
+    WhereBound b;
+    if ((rc = where_bind(who, ctx, w, fs, rows, cols, true, &b))) return rc;
+    out->f = b.f;
+    out->id = b.id;
+    out->hold = b.hold;
+    return PG_OK;
+}
+
 }  // namespace pg
 
 extern "C" {

@@ -1950,6 +1950,80 @@ class Where:
         return rows, scores, counts
 
 
+class ColdStart:
+    """ColdStartRecall (pg_cold_*): the rows a clause admits as a recall answer — a keyed uniform sample per request (order_by
+    None, "" or "random()") or the head of the pool by one column ("create_time DESC").  `where` is borrowed (None: every row of
+    the table) and must outlive this object; creating needs no GPU."""
+
+    def __init__(self, where: Optional[Where] = None, order_by: Optional[str] = None):
+        self.L = _lib.load()
+        self.where = where
+        h = C.c_void_p()
+        _lib.check(self.L.pg_cold_create(where.h if where is not None else None,
+                                         order_by.encode("utf-8") if order_by is not None else None, C.byref(h)))
+        self.h = h
+
+    def free(self):
+        if self.h:
+            self.L.pg_cold_free(self.h)
+            self.h = None
+
+    @staticmethod
+    def _seeds(seed, nq: int):
+        if seed is None:
+            return None
+        s = np.ascontiguousarray(seed, dtype=np.uint64)
+        if s.shape != (nq,):
+            raise ValueError("ColdStart: one seed per request")
+        return s
+
+    def recall_host(self, rows: int, nq: int, k: int, bits: Optional[np.ndarray] = None, order_col: Optional[np.ndarray] = None,
+                    seed=None, row_offset: int = 0):
+        """The host statement (pg_cold_recall_host): bits = the clause's bitmap over `rows` rows (Where.eval_host; None: every
+        row), order_col = the ordered column's values (int32 / int64 / float32 / float64) → (rows [nq][k] u64, scores [nq][k]
+        f32, counts [nq] u32)."""
+        b = None if bits is None else np.ascontiguousarray(bits, dtype=np.uint32)
+        if b is not None and b.shape[0] < (rows + 31) // 32:
+            raise ValueError("ColdStart.recall_host: the bitmap is shorter than the rows")
+        oc, dt = None, 0
+        if order_col is not None:
+            oc = np.ascontiguousarray(order_col)
+            dts = [d for d, t in _F_NP.items() if oc.dtype == t]
+            if not dts or oc.shape != (rows,):
+                raise TypeError("ColdStart.recall_host: the order column is one int32 / int64 / float32 / float64 value per row")
+            dt = dts[0]
+        s = self._seeds(seed, nq)
+        out_r = np.empty((nq, k), dtype=np.uint64)
+        out_s = np.empty((nq, k), dtype=np.float32)
+        cnt = np.empty(nq, dtype=np.uint32)
+        _lib.check(self.L.pg_cold_recall_host(self.h, _ptr(b) if b is not None else None, rows, row_offset,
+                                              _ptr(oc) if oc is not None else None, dt, _ptr(s) if s is not None else None, nq, k,
+                                              _ptr(out_r), _ptr(out_s), _ptr(cnt)))
+        return out_r, out_s, cnt
+
+    def recall_dev(self, ctx: "Context", table: "Table", feats: Optional["Features"], d_seed: int, nq: int, k: int, d_out_rows: int,
+                   d_out_scores: int, d_out_count: int = 0) -> None:
+        """pg_cold_recall_dev: device addresses (d_seed 0 = seed 0 for every request), enqueued on the context's stream."""
+        _lib.check(self.L.pg_cold_recall_dev(ctx.h, self.h, table.h, feats.h if feats is not None else None, C.c_void_p(d_seed or None),
+                                             nq, k, C.c_void_p(d_out_rows or None), C.c_void_p(d_out_scores or None),
+                                             C.c_void_p(d_out_count or None)))
+
+    def recall(self, ctx: "Context", table: "Table", feats: Optional["Features"], nq: int, k: int, seed=None):
+        """pg_cold_recall on host arrays → (rows [nq][k] u64, scores [nq][k] f32, counts [nq] u32)"""
+        s = self._seeds(seed, nq)
+        out_r = np.empty((max(nq, 1), max(k, 1)), dtype=np.uint64)
+        out_s = np.empty((max(nq, 1), max(k, 1)), dtype=np.float32)
+        cnt = np.empty(max(nq, 1), dtype=np.uint32)
+        _lib.check(self.L.pg_cold_recall(ctx.h, self.h, table.h, feats.h if feats is not None else None,
+                                         _ptr(s) if s is not None else None, nq, k, _ptr(out_r), _ptr(out_s), _ptr(cnt)))
+        return out_r, out_s, cnt
+
+    def stats(self) -> dict:
+        st = _lib.PgColdStats()
+        _lib.check(self.L.pg_cold_stats(self.h, C.byref(st)))
+        return {name: getattr(st, name) for name, _ in st._fields_}
+
+
 class Expr:
     """Compiled RankConfig.RankScore expression (utils/ast replacement)."""
 
