@@ -75,7 +75,7 @@ enum ScratchSlot : int {
     kSlotRankHeads = 14,     // rank_mlp.hip: head partials of the weights-stationary multi-head kernel
     kSlotFuse = 15,          // pipeline.hip pg_fuse_scores_dev: the bound variables and error flags
     kSlotExprVars = 16,      // expr.hip pg_features_eval_dev: the bound variables
-    kSlotIndexSearch = 17,   // index.hip: bounds, probe thresholds and list counts of an index recall; rank_mlp.hip: the fp16 split kernel's fallback tile tables (separate calls)
+    kSlotIndexSearch = 17,   // index_search.hip: bounds, probe thresholds and list counts of an index recall; rank_mlp.hip: the fp16 split kernel's fallback tile tables (separate calls)
     kSlotRecallExclude = 18, // recall_entry.hip: the over-fetched answer, lists and counts of a recall with exclusion lists
     kSlotCf = 19,            // cf.hip: status and counts, staged offsets and lists, the global tier's tables, the items to order, the over-fetched answer
     kSlotFanin = 20,         // fanin.hip: the merge's keys, values and masks
@@ -327,7 +327,7 @@ struct RecallScratch {
     uint32_t* cnt_seen;      // [kMaxQueries] the candidates each query had collected when the last select kept K of them
 };
 constexpr uint32_t kRecallStatusWords = 640;
-constexpr uint32_t kIndexStatAt = 260;      // an index plan's words in a job's status block ([0, 1 + nq) as every plan's; index.hip)
+constexpr uint32_t kIndexStatAt = 260;      // an index plan's words in a job's status block ([0, 1 + nq) as every plan's; index.hip, IndexPlanWords in index_shared.hpp)
 // A predicate over an integer feature column that restricts a recall's candidates (HologresVectorConf.WhereClause of the
 // reference, hologres_vector_recall.go:49-62, in the one shape the device serves: `column OP constant`).  Rows that fail it
 // never become candidates — it is applied where candidates are made (exact re-scoring, the exact scan's hit path), so every
@@ -356,7 +356,7 @@ __host__ __device__ inline bool row_filter_pass(const RowFilter& f, uint32_t row
     }
 }
 
-struct IndexServe;   // index.hip: an attached index's serving counters and switch (outlives the index while a job holds it)
+struct IndexServe;   // index_serve.hpp: an attached index's serving counters and switch (outlives the index while a job holds it)
 struct RecallJob {
     // set by the caller
     pg_ctx* ctx = nullptr;
@@ -518,7 +518,7 @@ inline TableLearned table_learned(const pg_table* t) {
     return t->learned;
 }
 // recall.hip's exact re-scoring (rescore_kernel) over per-query suspect lists susp[q * scap + i] of local rows, appending the keys of
-// rows whose score reaches thr[q] to cand[q * cap + ...]; the squared-Euclidean |q|^2 chain and the final sign flip (index.hip)
+// rows whose score reaches thr[q] to cand[q * cap + ...]; the squared-Euclidean |q|^2 chain and the final sign flip (index_search.hip)
 int rescore_launch(pg_ctx* ctx, uint32_t dim, bool l2, const float* tab, const float* d_queries, const float* thr, const uint32_t* susp,
                    const uint32_t* susp_cnt, uint32_t scap, uint32_t* cnt, uint64_t* cand, uint32_t* overflow, uint32_t cap, uint32_t nq,
                    uint32_t n_rows, const float* nx, const float* nqv, uint32_t blocks);

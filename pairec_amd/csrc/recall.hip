@@ -2400,7 +2400,7 @@ int recall_patch_failed_locked(RecallJob* j, uint32_t* counts) {
     return PG_OK;
 }
 
-// The exact re-scoring and the squared-Euclidean helpers for callers outside this file (index.hip): the same kernels, so a
+// The exact re-scoring and the squared-Euclidean helpers for callers outside this file (index_search.hip): the same kernels, so a
 // row scored there carries the bits the table's own pass gives it.
 int rescore_launch(pg_ctx* ctx, uint32_t dim, bool l2, const float* tab, const float* d_queries, const float* thr, const uint32_t* susp,
                    const uint32_t* susp_cnt, uint32_t scap, uint32_t* cnt, uint64_t* cand, uint32_t* overflow, uint32_t cap, uint32_t nq,

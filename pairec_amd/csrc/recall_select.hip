@@ -6,7 +6,7 @@
 //   final_kernel     per query: bitonic sort of the K survivors in LDS, decode to (row, score); final_kernel_reg,
 //                    final_rank_kernel and the split sort (FinalSortPolicy) are its faster forms, chosen by final_launch.
 //   merge_keys_kernel + select + final: the global top-k of per-shard lists (topk_merge_*_locked, pg_topk_merge_dev).
-// Called by the table pass (recall.hip) and by index.hip, group.hip, exclude.hip and cf.hip.
+// Called by the table pass (recall.hip) and by index_search.hip, group.hip, exclude.hip and cf.hip.
 #include "common.hpp"
 #include "recall_shared.hpp"
 #include "bitonic_reg.hpp"

@@ -1,6 +1,6 @@
 // Compound WhereClauses: `pg_where`, a predicate over the integer columns of a feature store, compiled on the
 // host from the SQL text a Hologres recall carries (HologresVectorConf.WhereClause, recconf.go:492-497) and evaluated on the
-// device into a row bitmap that every consumer of a RowFilter reads (recall.hip, recall_filter.hip, index.hip).
+// device into a row bitmap that every consumer of a RowFilter reads (recall.hip, recall_filter.hip, index_where.hip).
 //
 //   expr  := and ( OR and )*
 //   and   := unary ( AND unary )*

@@ -1,4 +1,4 @@
-"""The exact IVF index's bound, restated in numpy (index.hip: radius_kernel, cnorm_kernel, bound_kernel; all fp64, every
+"""The exact IVF index's bound, restated in numpy (index_build.hip: radius_kernel, cnorm_kernel; index_search.hip: bound_kernel; all fp64, every
 table-side input rounded up to fp32 first), and adversarial lists to test it on.  Shared by tests/test_index_cpu.py (the formula
 dominates every chain score) and tests/test_gpu_index_bounds.py (the device's state equals the formula)."""
 import numpy as np
@@ -12,7 +12,7 @@ def _up32(v):
 
 
 def _cnorm(c):
-    """||c_L|| as the build measures it (index.hip: cnorm_kernel): fp64, a 2^-40 relative margin, rounded up to fp32"""
+    """||c_L|| as the build measures it (index_build.hip: cnorm_kernel): fp64, a 2^-40 relative margin, rounded up to fp32"""
     return float(_up32(np.sqrt(np.sum(c.astype(np.float64) ** 2)) * (1 + 2.0 ** -40)))
 
 

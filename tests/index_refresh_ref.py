@@ -1,4 +1,4 @@
-"""pg_index_refresh restated in numpy: the assignment rule (index.hip: assign_kernel, through the oracle's
+"""pg_index_refresh restated in numpy: the assignment rule (index_build.hip: assign_kernel, through the oracle's
 fmaf chains), the index arrays the build's steps 3-5 give for a set of centroids and rows, and the matrix-pipe screen of
 index_assign.hip with its bound e(x, L).  Shared by tests/test_index_refresh_cpu.py (the bound dominates |screen - rule| inside
 its range, the survivor counts of the GPU tests' tables) and tests/test_gpu_index_refresh.py (the device's arrays equal the rule)."""
