@@ -1873,6 +1873,108 @@ int pg_mix_sort(pg_ctx* ctx, pg_mix* m, const pg_features* fs, uint32_t ctx_size
                 const uint32_t* order, uint64_t seed, const uint64_t* user_vals, uint32_t user_present, uint32_t* out_order,
                 uint32_t* out_count);
 
+/* TrafficControlSort's macro control on the device (csrc/traffic.hip, csrc/traffic_host.hpp).  The reference's
+ * sort (sort/traffic_control_sort.go) splits per request into a controller — PIDController.compute / setMeasurement,
+ * computeMacroControlAlpha, filterValidControllers: a handful of scalars per target, driven by wall-clock time and remote traffic
+ * counters, which stay on the host and hand over ONE number per target and request, alpha — and the re-ranking: macroControl
+ * (:204-364), computeDeltaRank (:555-589) and the closing position sort (:160-181), N items x T targets, which is this stage.
+ *   In        one request holds entries 0 .. n-1, n = d_count[q] (cap when d_count is NULL); d_order [nq][cap] uint32 (optional,
+ *             NULL = identity): list entry j is element d_order[q][j] of the [nq][cap] arrays, as for pg_mix_sort_dev.  Per element:
+ *             d_score fp64 (Item.Score), d_member uint8: bit t set = isControlledItem(controller_t, item) — the output of
+ *             pg_classcut_masks_dev over a set whose class expressions are the targets' item expressions plugs in as it is (its
+ *             counts are ignored; hence at most 8 targets); a target without an item expression has its bit on every entry.
+ *             d_alpha [nq][T] fp64: the controller's output for that request; 0 = the target is off for this request (filtered
+ *             out, returned 0, timed out).  An order value >= cap is PG_ERR_INVALID where the host can see it (the host statement
+ *             and the one-request call); on the device it is padding as in pg_ssd_sort_dev: the entry leaves the list first and
+ *             appears in no output.  Scalars per call: ctx_size (ctx.Size), page_no (the page_number parameter, clamped to >= 1
+ *             by the caller as :294-297 does), gamma, beta, eta (PidGamma, PidBeta, PidEta: 1.0, 1.0, 1.6 by default, :269-282).
+ *   Answer    DEFINED bit for bit.
+ *               0. The list is taken to be score-descending already: the stage does not redo :114's unstable sort.Sort and keeps the
+ *                  order that arrives (the rule and the reason of pg_ssd_sort_dev).  i is the list index, origin_i = i + 1 and
+ *                  control_id_i starts at i + 1 (:115-118).
+ *               1. n = 0, T = 0 or every alpha of the request 0: the identity (:131-135, :208-211), control_id_i = i + 1,
+ *                  new_pos_i = i + 1.  (The steps below give exactly that; nothing is a special case.)
+ *               2. goint(x): Go's float64 -> int on amd64 — truncation toward zero for -2^63 < x < 2^63, INT64_MIN for NaN and
+ *                  everything else.  All integer arithmetic behind it is wrapping int64 (in sigmoid, INT64_MIN - 5000 wraps
+ *                  positive and returns 1; in step 6, ctx_size + goint(NaN) is hugely negative).
+ *               3. Tables (:45-66), built once with the host's libm (pg_traffic_table reads them; the device receives them by
+ *                  upload and never computes them): positionWeight[i] = exp(-0.01 * i) for i < 500 and the literal 0.006737946999
+ *                  beyond, expTable[i] = exp(i / 1000.0), tanhTable[i] = tanh(i / 1000.0), sigmoidTable[i] = 1 / (1 + exp(10 -
+ *                  (i / 1000.0 + 5.0))).
+ *               4. Scores and sums (:217-256): s_i = score_i with 0.0 replaced by 1e-8; maxScore = s_0; itemScore_0 = math.E (the
+ *                  constant, not exp(1.0)), itemScore_i = expTable[clamp(goint(s_i / maxScore * 1000), 0, 999)] for i > 0;
+ *                  w_i = s_i * posWeight_i; total = sum of w_i; sum_t = sum of w_i over the entries with bit t, for the targets
+ *                  with alpha_t != 0.  Both run sequentially in list order from 0.0 (the reference's chains; fp64 addition is not
+ *                  associative).  weight_t = sum_t / total if target t received at least one addition, else 0.0 (the map has no
+ *                  key); the division as written, so it may be NaN or +-Inf.
+ *               5. Uplift scaling (:284-291): for alpha_t > 0, alpha_t *= 1.0 + gamma * tanh_tab(beta * weight_t), with
+ *                  tanh_tab(x) = tanhTable[clamp(goint(x * 1000), 0, 2999)] (:942-950).  Every product and sum is its own
+ *                  operation (no fused multiply-add).
+ *               6. Per entry i (:332-356), targets t in ascending index, final = 0.0.  (The reference walks a Go map; only the last
+ *                  bit of `final` and the control id of an entry two targets uplift depend on that order.  Ascending is the
+ *                  definition.)  Skip t if bit t is clear or alpha_t (as step 5 left it) == 0.
+ *                    alpha_t < 0 (pull down): rho = eta * (1.0 - tanh_tab(weight_t)); delta = alpha_t * sigmoid_tab(double(i), rho);
+ *                      sigmoid_tab(x, rho): idx = goint(rho * x * 1000.0) - 5000; idx < 0 uses entry 0, idx >= 10000 returns 1.0,
+ *                      otherwise sigmoidTable[idx] (:952-960).
+ *                    otherwise (uplift; a NaN alpha lands here, as in Go): delta = alpha_t * itemScore_i; start = ctx_size, and if
+ *                      page_no > 1, start += goint((weight_t - 0.3) * 10 * double(ctx_size)); if i > start and delta >= 1.0:
+ *                      PG_TRAFFIC_PERCENT sets control_id_i = -target_id, PG_TRAFFIC_QUANTITY sets it to 0 if it is > 0.
+ *                    final += delta.
+ *                  Behind the targets: if final != 0.0 and control_id_i == 0 and final < 1.0, control_id_i = origin_i (:350-356).
+ *               7. Positions (:160-180): new_pos_i = final != 0.0 ? double(i + 1) - final : double(i + 1).  A NaN new_pos is
+ *                  reported as the quiet NaN 0x7FF8000000000000 (IEEE 754 leaves a NaN's sign and payload to the hardware).
+ *               8. Order (:181, ItemRankSlice :924-934): ascending new_pos (-0.0 equal to +0.0), ties by origin position; a NaN
+ *                  new_pos sorts behind every number, NaNs among themselves by origin.  (The reference's comparator is no order
+ *                  there: this is a definition.)  The count is n.
+ *   Outputs   d_out_order [nq][cap] uint32: indices into the [nq][cap] arrays (composed with d_order), UINT32_MAX behind the count;
+ *             d_out_count [nq]; optional d_out_control_id [nq][cap] int32 (__traffic_control_id__) by input element, 0 for an
+ *             element that is no entry of the list; optional d_out_new_pos [nq][cap] fp64 (_NEW_POSITION_) by input element, the
+ *             quiet NaN 0x7FF8000000000000 for such an element.  Every element of every output is written exactly once (d_order
+ *             names no element twice).  An output that overlaps an input or another output is PG_ERR_INVALID.
+ *   Refused   pg_traffic_compile, by name, nothing allocated: more than PG_TRAFFIC_MAX_TARGETS targets or an unknown control type
+ *             (PG_ERR_UNSUPPORTED); target_id == INT32_MIN, whose negation overflows (PG_ERR_INVALID).  No targets compiles: the
+ *             answer is the identity.  A call, on the host, the context left usable: nq = 0, ctx_size == 0, page_no == 0, a
+ *             missing score / member / alpha while T > 0 (PG_ERR_INVALID); nq > 256, cap outside [1, PG_TRIM_MAX_CAP]
+ *             (PG_ERR_UNSUPPORTED).
+ *   host      pg_traffic_sort_host: a pure host function (no context, no device), the answer entry by entry; what the kernels are
+ *             tested against, the library falls back to it for nothing.  out_control_id / out_new_pos may be NULL.
+ *   Kernels   pg_traffic_sort_dev: enqueued on the context's stream, no synchronisation (the first device call with a set uploads
+ *             the four tables once, synchronously).  A control kernel, one workgroup of PG_TRIM_CHUNK lanes per request: lanes walk
+ *             the list a chunk at a time, compact it (wave ballots), stage w_i and the member byte in LDS; lanes 0 .. T of the
+ *             first wave each run one sequential chain over the chunk (lane 0 total, lane 1 + t sum_t and its "received an
+ *             addition" flag); one lane per target then finishes weight_t, the scaled alpha, rho and the page-2 start; all lanes
+ *             do steps 6 and 7 from the tables in global memory (116 KB, read-only, data-dependent addresses: they stay in L2)
+ *             and write new_pos and control_id by element and new_pos in list order as the sort key.  The order is the segmented
+ *             score sort of pg_sort_scores_dev, ascending: its ties-keep-input-order and NaN-last rules are step 8's.  A compose
+ *             kernel maps the sorted positions to elements and writes the UINT32_MAX tail and the counts.
+ *   Sharing   as pg_mix: several contexts of ONE device may use a set, also concurrently; pg_traffic_free waits for that device.
+ *   one       pg_traffic_sort: one request of n entries on host arrays (upload, run, download, synchronise); alpha [T]; n = 0 is an
+ *             empty answer.
+ *   Not here  microControl (:592-704), sampleControlTargetsByScore (:502-545), the controller and the isControlledBy* filters. */
+#define PG_TRAFFIC_MAX_TARGETS 8
+#define PG_TRAFFIC_PERCENT  1   /* task.ControlType "Percent" */
+#define PG_TRAFFIC_QUANTITY 2   /* anything else */
+typedef struct {
+    int32_t target_id;          /* strconv.Atoi(TrafficControlTargetId) */
+    int32_t control_type;       /* PG_TRAFFIC_PERCENT | PG_TRAFFIC_QUANTITY */
+} pg_traffic_target;
+typedef struct pg_traffic pg_traffic;
+int pg_traffic_compile(const pg_traffic_target* targets, uint32_t n, pg_traffic** out);
+int pg_traffic_free(pg_traffic* m);
+int pg_traffic_num_targets(const pg_traffic* m);
+/* entries [first, first + n) of table `which`: 0 positionWeight[500], 1 expTable[1000], 2 tanhTable[3000], 3 sigmoidTable[10000] */
+int pg_traffic_table(int which, uint32_t first, uint32_t n, double* out);
+int pg_traffic_sort_host(const pg_traffic* m, uint32_t ctx_size, uint32_t page_no, double gamma, double beta, double eta, uint32_t nq,
+                         uint32_t cap, const double* score, const uint8_t* member, const uint32_t* order, const uint32_t* count,
+                         const double* alpha, uint32_t* out_order, uint32_t* out_count, int32_t* out_control_id, double* out_new_pos);
+int pg_traffic_sort_dev(pg_ctx* ctx, pg_traffic* m, uint32_t ctx_size, uint32_t page_no, double gamma, double beta, double eta,
+                        uint32_t nq, uint32_t cap, const double* d_score, const uint8_t* d_member, const uint32_t* d_order,
+                        const uint32_t* d_count, const double* d_alpha, uint32_t* d_out_order, uint32_t* d_out_count,
+                        int32_t* d_out_control_id, double* d_out_new_pos);
+int pg_traffic_sort(pg_ctx* ctx, pg_traffic* m, uint32_t ctx_size, uint32_t page_no, double gamma, double beta, double eta, uint32_t n,
+                    const double* score, const uint8_t* member, const uint32_t* order, const double* alpha, uint32_t* out_order,
+                    uint32_t* out_count, int32_t* out_control_id, double* out_new_pos);
+
 /* SSDSort on the device: candidate lists in, re-ranked page out (csrc/ssd.hip).  SSDSort.Sort and doSort around the
  * sliding window (sort/ssd_sort.go:110-343) for nq requests on device arrays: the ssd_filter_retrieve_ids split, the candidate-count
  * cut, the min-score-percent cut, the two normalisations with their "all item score are zeros" bail-out, SSDWithSlidingWindow

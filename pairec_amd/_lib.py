@@ -65,6 +65,8 @@ EXPORTS = [
     "pg_candidates_classcut",
     "pg_mix_compile", "pg_mix_free", "pg_mix_num_strategies", "pg_mix_num_user_slots", "pg_mix_user_slot_name", "pg_mix_user_slot_is_float",
     "pg_mix_sort_host", "pg_mix_sort_dev", "pg_mix_sort", "pg_ssd_sort_dev",
+    "pg_traffic_compile", "pg_traffic_free", "pg_traffic_num_targets", "pg_traffic_table", "pg_traffic_sort_host", "pg_traffic_sort_dev",
+    "pg_traffic_sort",
     "pg_cold_create", "pg_cold_free", "pg_cold_recall_host", "pg_cold_recall_dev", "pg_cold_recall", "pg_cold_stats",
 ]
 
@@ -193,6 +195,10 @@ class PgMixStrategy(C.Structure):
     _fields_ = [("type", C.c_int32), ("positions", C.POINTER(C.c_int32)), ("n_positions", C.c_uint32), ("position_field", C.c_char_p),
                 ("number", C.c_int32), ("number_rate", C.c_double), ("source_mask", C.c_uint32), ("terms", C.POINTER(PgCondTerm)),
                 ("n_terms", C.c_uint32)]
+
+
+class PgTrafficTarget(C.Structure):
+    _fields_ = [("target_id", C.c_int32), ("control_type", C.c_int32)]
 
 
 class PgIndexRefreshParams(C.Structure):
@@ -384,6 +390,13 @@ def load():
         "pg_mix_sort_host": [vp, u32, u32, u32, vp, P(vp), vp, vp, vp, vp, vp, vp, vp, vp],
         "pg_mix_sort_dev": [vp, vp, vp, u32, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp],
         "pg_mix_sort": [vp, vp, vp, u32, u32, vp, vp, vp, u64, vp, u32, vp, P(u32)],
+        "pg_traffic_compile": [P(PgTrafficTarget), u32, P(vp)],
+        "pg_traffic_free": [vp],
+        "pg_traffic_num_targets": [vp],
+        "pg_traffic_table": [i32, u32, u32, vp],
+        "pg_traffic_sort_host": [vp, u32, u32, C.c_double, C.c_double, C.c_double, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+        "pg_traffic_sort_dev": [vp, vp, u32, u32, C.c_double, C.c_double, C.c_double, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+        "pg_traffic_sort": [vp, vp, u32, u32, C.c_double, C.c_double, C.c_double, u32, vp, vp, vp, vp, vp, P(u32), vp, vp],
         "pg_ssd_sort_dev": [vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, C.c_double, u32, u32, i32, i32, i32, i32, u32, C.c_double, u32, u32,
                             vp, vp, vp, vp],
         "pg_index_refresh": [vp, vp, P(PgIndexRefreshParams)],

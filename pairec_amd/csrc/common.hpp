@@ -92,6 +92,7 @@ enum ScratchSlot : int {
     kSlotDimcap = 31,        // dimcap.hip: the scratch tier's keys and counts of a value cap; the one-request entry's staging behind them
     kSlotRtU2I = 32,         // rtu2i.hip: the staged event offsets and clocks of a trigger stage; in pg_rtu2i_recall_dev the trigger lists between its two launches (cf.hip's expansion reads them while kSlotCf is its own)
     kSlotCold = 33,          // coldstart.hip: the select's threshold state and digit histogram, per-block counts and their scan, the survivors and the ordered list of an ordered pool
+    kSlotTraffic = 34,       // traffic.hip: the position keys, the compacted lists, the keys' order, the list lengths and the segment offsets of a traffic control sort
     kSlotCount
 };
 

@@ -604,6 +604,80 @@ def mix_sort_host(mix: Mix, ctx_size: int, nq: int, cap: int, **kw):
     return mix.sort_host(ctx_size, nq, cap, **kw)
 
 
+TRAFFIC_PERCENT, TRAFFIC_QUANTITY = 1, 2
+TRAFFIC_MAX_TARGETS = 8
+_TRAFFIC_TABLES = (500, 1000, 3000, 10000)
+
+
+def traffic_table(which: int) -> np.ndarray:
+    """pg_traffic_table: the whole of table `which` — 0 positionWeight[500], 1 expTable[1000], 2 tanhTable[3000],
+    3 sigmoidTable[10000] — as the library built it (float64)."""
+    if not 0 <= int(which) < len(_TRAFFIC_TABLES):
+        raise ValueError("traffic_table: table %r (0 .. 3)" % (which,))
+    out = np.empty(_TRAFFIC_TABLES[int(which)], np.float64)
+    _lib.check(_lib.load().pg_traffic_table(int(which), 0, out.shape[0], _ptr(out)))
+    return out
+
+
+class Traffic:
+    """A compiled TrafficControlSort target set (pg_traffic_compile): 0..8 targets in config order.  targets: [{TrafficControlTargetId
+    (an integer or its decimal string, strconv.Atoi), ControlType: "Percent" (or TRAFFIC_PERCENT) | anything else (TRAFFIC_QUANTITY)}]
+    or (target_id, control_type) pairs.  A host object until a device entry first uses it."""
+
+    def __init__(self, targets):
+        self.L = _lib.load()
+        arr = (_lib.PgTrafficTarget * max(len(targets), 1))()
+        for i, t in enumerate(targets):
+            if isinstance(t, dict):
+                tid, ty = t.get("TrafficControlTargetId", 0), t.get("ControlType", TRAFFIC_QUANTITY)
+            else:
+                tid, ty = t
+            if isinstance(ty, str):
+                ty = TRAFFIC_PERCENT if ty == "Percent" else TRAFFIC_QUANTITY
+            arr[i].target_id, arr[i].control_type = int(tid), int(ty)
+        h = C.c_void_p()
+        _lib.check(self.L.pg_traffic_compile(arr, len(targets), C.byref(h)))
+        self.h = h
+        self.n_targets = self.L.pg_traffic_num_targets(h)
+
+    def free(self):
+        if self.h:
+            self.L.pg_traffic_free(self.h)
+            self.h = None
+
+    def sort_host(self, ctx_size: int, nq: int, cap: int, score=None, member=None, order=None, count=None, alpha=None, page_no: int = 1,
+                  gamma: float = 1.0, beta: float = 1.0, eta: float = 1.6, want_control_id: bool = True, want_new_pos: bool = True):
+        """pg_traffic_sort_host: the answer on host arrays, no context, no device.  score [nq][cap] f64, member [nq][cap] u8, order
+        [nq][cap] u32, count [nq] u32, alpha [nq][T] f64 → (out_order [nq][cap] u32, out_count [nq] u32, control_id [nq][cap] i32
+        | None, new_pos [nq][cap] f64 | None)."""
+        def arr_(a, dt, n):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=dt).reshape(-1)
+            if a.shape[0] != n:
+                raise ValueError("Traffic.sort_host: an array holds %d values, %d expected" % (a.shape[0], n))
+            return a
+        sc, mem, ordr = arr_(score, np.float64, nq * cap), arr_(member, np.uint8, nq * cap), arr_(order, np.uint32, nq * cap)
+        cnt, al = arr_(count, np.uint32, nq), arr_(alpha, np.float64, nq * self.n_targets)
+        out, oc = np.empty((nq, cap), np.uint32), np.empty(nq, np.uint32)
+        cid = np.empty((nq, cap), np.int32) if want_control_id else None
+        pos = np.empty((nq, cap), np.float64) if want_new_pos else None
+        v = lambda a: None if a is None else _ptr(a)                                     # noqa: E731
+        _lib.check(self.L.pg_traffic_sort_host(self.h, int(ctx_size), int(page_no), float(gamma), float(beta), float(eta), nq, cap, v(sc),
+                                               v(mem), v(ordr), v(cnt), v(al), _ptr(out), _ptr(oc), v(cid), v(pos)))
+        return out, oc, cid, pos
+
+
+def traffic_compile(targets) -> Traffic:
+    """pg_traffic_compile (see Traffic)."""
+    return Traffic(targets)
+
+
+def traffic_sort_host(traffic: Traffic, ctx_size: int, nq: int, cap: int, **kw):
+    """pg_traffic_sort_host (see Traffic.sort_host): a host function, no context, no device."""
+    return traffic.sort_host(ctx_size, nq, cap, **kw)
+
+
 def expr_compile_govaluate(source: str) -> "Expr":
     """pg_expr_compile_govaluate: the arithmetic subset of govaluate that BoostScoreSort expressions use."""
     return Expr(source, govaluate=True)
@@ -1138,6 +1212,46 @@ class Context:
                                       None if ordr is None else _ptr(ordr), int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(uv), int(up[0]), _ptr(out),
                                       C.byref(cnt)))
         return out, cnt.value
+
+    # ---- TrafficControlSort: the macro control's re-ranking ----------------------------------------------
+    def traffic_sort_dev(self, traffic, ctx_size: int, nq: int, cap: int, d_score: int, d_member: int, d_order: int, d_count: int, d_alpha: int,
+                         d_out_order: int, d_out_count: int, d_out_control_id: int = 0, d_out_new_pos: int = 0, page_no: int = 1,
+                         gamma: float = 1.0, beta: float = 1.0, eta: float = 1.6) -> None:
+        """pg_traffic_sort_dev: device addresses (0 = absent) → d_out_order [nq][cap] u32, d_out_count [nq] u32, d_out_control_id
+        [nq][cap] i32, d_out_new_pos [nq][cap] f64.  Enqueued on the context's stream: synchronize() before reading."""
+        v = lambda p: C.c_void_p(p or None)                                          # noqa: E731
+        _lib.check(self.L.pg_traffic_sort_dev(self.h, traffic.h, int(ctx_size), int(page_no), float(gamma), float(beta), float(eta), nq, cap,
+                                              v(d_score), v(d_member), v(d_order), v(d_count), v(d_alpha), v(d_out_order), v(d_out_count),
+                                              v(d_out_control_id), v(d_out_new_pos)))
+
+    def traffic_sort(self, traffic, ctx_size: int, score, member, alpha, order=None, count=None, page_no: int = 1, gamma: float = 1.0,
+                     beta: float = 1.0, eta: float = 1.6):
+        """TrafficControlSort's macro control on host arrays (pg_traffic_sort_dev): score [nq][cap] f64, member [nq][cap] u8, alpha
+        [nq][T] f64, order [nq][cap] u32 (None = identity), count [nq] → (out_order [nq][cap] u32, out_count [nq] u32, control_id
+        [nq][cap] i32, new_pos [nq][cap] f64)."""
+        sc = np.ascontiguousarray(score, dtype=np.float64)
+        if sc.ndim != 2:
+            raise ValueError("traffic_sort: score is [nq][cap]")
+        nq, cap = sc.shape
+        opt = lambda a, dt: None if a is None else np.ascontiguousarray(a, dtype=dt)     # noqa: E731
+        ins = [sc, opt(member, np.uint8), opt(order, np.uint32), opt(count, np.uint32), opt(alpha, np.float64)]
+        outs = [np.empty((nq, cap), np.uint32), np.empty(nq, np.uint32), np.empty((nq, cap), np.int32), np.empty((nq, cap), np.float64)]
+        return self._cand_run(ins, outs, lambda d_in, d_out: self.traffic_sort_dev(traffic, ctx_size, nq, cap, *d_in, *d_out, page_no=page_no,
+                                                                                    gamma=gamma, beta=beta, eta=eta))
+
+    def traffic_sort_one(self, traffic, ctx_size: int, score, member, alpha, order=None, page_no: int = 1, gamma: float = 1.0, beta: float = 1.0,
+                         eta: float = 1.6):
+        """pg_traffic_sort: one request on host arrays (what the host mirror calls) → (out_order [n] u32, count, control_id [n] i32,
+        new_pos [n] f64)"""
+        sc = np.ascontiguousarray(score, dtype=np.float64).reshape(-1)
+        mem = np.ascontiguousarray(member, dtype=np.uint8).reshape(-1)
+        al = np.ascontiguousarray(alpha, dtype=np.float64).reshape(-1)
+        ordr = None if order is None else np.ascontiguousarray(order, dtype=np.uint32).reshape(-1)
+        n = sc.shape[0]
+        out, cnt, cid, pos = np.empty(n, np.uint32), C.c_uint32(), np.empty(n, np.int32), np.empty(n, np.float64)
+        _lib.check(self.L.pg_traffic_sort(self.h, traffic.h, int(ctx_size), int(page_no), float(gamma), float(beta), float(eta), n, _ptr(sc),
+                                          _ptr(mem), None if ordr is None else _ptr(ordr), _ptr(al), _ptr(out), C.byref(cnt), _ptr(cid), _ptr(pos)))
+        return out, cnt.value, cid, pos
 
     # ---- SSDSort: candidate lists in, re-ranked page out ------------------------------------------------
     def ssd_sort_dev(self, table, nq: int, cap: int, d_order, d_rows, d_score, d_source, d_count, d_enable, gamma: float, topn: int,

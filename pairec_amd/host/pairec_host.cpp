@@ -367,6 +367,53 @@ static bool CompileClasscut(const GpuFilterConfig& c, pg_classcut** out, std::st
     return false;
 }
 
+// The targets of a pairec_gpu.Sorts TrafficControlSort entry as pg_traffic_compile takes them, and their ItemExpressions as one
+// classcut set (class c is target class_target[c]; a target without an expression has no class: it controls every item).  What
+// pg_traffic_compile or pg_classcut_compile refuse is named by key.  *set stays NULL when no target has an expression.
+static bool CompileTrafficConf(const json::Value& sc, std::vector<pg_traffic_target>* targets, pg_classcut** set, std::vector<int>* class_target,
+                               std::vector<std::string>* columns, std::string* why) {
+    const auto& ts = sc.at("Targets").arr;
+    if (ts.size() > PG_TRAFFIC_MAX_TARGETS) {
+        *why = std::to_string(ts.size()) + " Targets (the device serves up to " + std::to_string(PG_TRAFFIC_MAX_TARGETS) + ")";
+        return false;
+    }
+    GpuFilterConfig cc;
+    for (size_t t = 0; t < ts.size(); ++t) {
+        const json::Value& id = ts[t].at("TrafficControlTargetId");
+        long long v = 0;
+        if (id.type == json::Value::Number) v = id.is_int ? id.i : (long long)id.num;
+        else if (id.type == json::Value::String) {
+            char* end = nullptr;
+            v = strtoll(id.str.c_str(), &end, 10);
+            if (id.str.empty() || *end) { *why = "Targets[" + std::to_string(t) + "]: TrafficControlTargetId \"" + id.str + "\" is not an integer (strconv.Atoi)"; return false; }
+        } else { *why = "Targets[" + std::to_string(t) + "]: no TrafficControlTargetId"; return false; }
+        if (v <= -2147483648LL || v > 2147483647LL) { *why = "Targets[" + std::to_string(t) + "]: TrafficControlTargetId outside int32"; return false; }
+        targets->push_back(pg_traffic_target{(int32_t)v, ts[t].s("ControlType") == "Percent" ? PG_TRAFFIC_PERCENT : PG_TRAFFIC_QUANTITY});
+        if (ts[t].has("Alpha") && ts[t].at("Alpha").type != json::Value::Number) { *why = "Targets[" + std::to_string(t) + "]: Alpha is not a number"; return false; }
+        const std::string expr = ts[t].s("ItemExpression");
+        if (expr.empty()) continue;
+        GpuFilterConfig::ClassConf cl;
+        cl.Expression = expr;
+        cl.Type = PG_TRIM_FIX;
+        cl.Count = 1;                                                    // (the counts are ignored: only the masks are read)
+        ClasscutNames(expr, &cc.ClassColumns);
+        cc.Classes.push_back(cl);
+        class_target->push_back((int)t);
+    }
+    pg_traffic* m = nullptr;
+    if (pg_traffic_compile(targets->data(), (uint32_t)targets->size(), &m) != PG_OK) {
+        *why = pg_last_error();
+        return false;
+    }
+    pg_traffic_free(m);
+    *columns = cc.ClassColumns;
+    *set = nullptr;
+    if (cc.Classes.empty()) return true;
+    if (CompileClasscut(cc, set, why)) return true;
+    *why = "ItemExpression: " + *why;
+    return false;
+}
+
 bool RecommendConfig::Parse(const std::string& text, RecommendConfig* out, std::string* err) {
     json::Value root;
     if (!json::Parser(text).Parse(&root, err)) return false;
@@ -566,6 +613,19 @@ bool RecommendConfig::Parse(const std::string& text, RecommendConfig* out, std::
                 if (err) *err = "pairec_gpu.Sorts: " + c.Name + ": MultiRecallMixSort: " + why;
                 return false;
             }
+        }
+        if (c.SortType == "TrafficControlSort") {
+            c.TrafficConf = sc;
+            std::string why;
+            std::vector<pg_traffic_target> targets;
+            std::vector<int> class_target;
+            std::vector<std::string> columns;
+            pg_classcut* set = nullptr;
+            if (!CompileTrafficConf(sc, &targets, &set, &class_target, &columns, &why)) {
+                if (err) *err = "pairec_gpu.Sorts: " + c.Name + ": TrafficControlSort: " + why;
+                return false;
+            }
+            pg_classcut_free(set);
         }
         if (c.SortType == "DistinctIdSort") {
             c.DistinctConf = sc;
@@ -2191,6 +2251,130 @@ struct GpuMultiRecallMixSort : sort::ISort {
     }
 };
 
+// TrafficControlSort's macro control (sort/traffic_control_sort.go:91-185, :204-364) through pg_traffic_sort.  The PID controller
+// itself — traffic counters, wall-clock time, PIDController.compute — is the Go side's job and hands over one alpha per target; the
+// mirror has no traffic service, so a target's alpha is its config constant Alpha until Engine::SetTrafficAlpha replaces it.  The
+// items are put in score order first (:114), each becomes its table row (one the table does not know: a row of its own behind the
+// store, every column missing), the targets' ItemExpressions run as one classcut set over the engine's item_features store
+// (pg_classcut_masks_dev) and its masks are the members; a target without an expression controls every item.  page_number is the
+// request parameter (default 1, :294-297); PidGamma / PidBeta / PidEta default to 1.0 / 1.0 / 1.6 (:269-282) and an experiment
+// parameter pid_gamma / pid_beta / pid_eta overrides them.  The items leave in the new order with __traffic_control_id__,
+// _ORIGIN_POSITION_ and _NEW_POSITION_ set.  An error leaves Data in score order and returns it.
+struct GpuTrafficControlSort : sort::ISort {
+    Engine* e;
+    json::Value conf;
+    std::mutex mu;                                       // alphas
+    std::vector<std::string> ids;                        // TrafficControlTargetId as written
+    std::vector<double> alphas;
+    GpuTrafficControlSort(Engine* eng, json::Value c) : e(eng), conf(std::move(c)) {
+        for (const auto& t : conf.at("Targets").arr) {
+            const json::Value& id = t.at("TrafficControlTargetId");
+            ids.push_back(id.type == json::Value::String ? id.str : std::to_string(id.is_int ? id.i : (long long)id.num));
+            alphas.push_back(t.d("Alpha"));
+        }
+    }
+    bool SetAlpha(const std::string& target_id, double alpha) {
+        std::lock_guard<std::mutex> g(mu);
+        const auto at = std::find(ids.begin(), ids.end(), target_id);
+        if (at == ids.end()) return false;
+        alphas[(size_t)(at - ids.begin())] = alpha;
+        return true;
+    }
+    bool Sort(sort::SortData* d, std::string* err) override {
+        const size_t n = d->Data.size();
+        if (n == 0) return true;
+        auto fail = [&](const std::string& what) { if (err) *err = "TrafficControlSort: " + what; return false; };
+        if (n > PG_TRIM_MAX_CAP) return fail(std::to_string(n) + " items (the device serves up to " + std::to_string(PG_TRIM_MAX_CAP) + ")");
+        if (!sort_items(e, d, true, err)) return false;
+        std::vector<pg_traffic_target> targets;
+        std::vector<int> class_target;
+        std::vector<std::string> columns;
+        pg_classcut* set = nullptr;
+        std::string why;
+        if (!recconf::CompileTrafficConf(conf, &targets, &set, &class_target, &columns, &why)) return fail(why);
+        const size_t T = targets.size();
+        std::vector<double> alpha;
+        {
+            std::lock_guard<std::mutex> g(mu);
+            alpha = alphas;
+        }
+        std::vector<uint8_t> member(n, 0);
+        bool ok = true;
+        if (set) {
+            if (!columns.empty() && !e->feats) { ok = false; why = "the engine has no feature columns"; }
+            for (size_t c = 0; ok && c < columns.size(); ++c)
+                if (pg_features_column_index(e->feats, columns[c].c_str()) < 0) { ok = false; why = "\"" + columns[c] + "\" is not a feature column"; }
+            std::vector<uint64_t> rows(n);
+            std::vector<double> score(n);
+            for (size_t i = 0; i < n; ++i) {
+                uint32_t row;
+                rows[i] = e->RowOfId(d->Data[i]->Id, &row) ? row : e->table_rows + i;
+                score[i] = d->Data[i]->Score;
+            }
+            void *d_rows = nullptr, *d_score = nullptr, *d_masks = nullptr;
+            std::vector<uint8_t> masks(n, 0);
+            if (ok) {
+                ok = pg_device_malloc(e->ctx, n * 8, &d_rows) == PG_OK && pg_device_malloc(e->ctx, n * 8, &d_score) == PG_OK &&
+                     pg_device_malloc(e->ctx, n, &d_masks) == PG_OK && pg_memcpy_h2d(e->ctx, d_rows, rows.data(), n * 8) == PG_OK &&
+                     pg_memcpy_h2d(e->ctx, d_score, score.data(), n * 8) == PG_OK &&
+                     pg_classcut_masks_dev(e->ctx, set, e->feats, 1, (uint32_t)n, (const uint64_t*)d_rows, (const double*)d_score, nullptr, nullptr,
+                                           (uint8_t*)d_masks) == PG_OK &&
+                     pg_memcpy_d2h(e->ctx, masks.data(), d_masks, n) == PG_OK;
+                if (!ok) why = pg_err("pg_classcut_masks_dev");
+            }
+            for (void* p : {d_rows, d_score, d_masks})
+                if (p) pg_device_free(e->ctx, p);
+            pg_classcut_free(set);
+            for (size_t i = 0; ok && i < n; ++i)
+                for (size_t c = 0; c < class_target.size(); ++c)
+                    if ((masks[i] >> c) & 1u) member[i] |= (uint8_t)(1u << class_target[c]);
+        }
+        if (!ok) return fail(why);
+        for (size_t t = 0; t < T; ++t)
+            if (conf.at("Targets").arr[t].s("ItemExpression").empty())
+                for (size_t i = 0; i < n; ++i) member[i] |= (uint8_t)(1u << t);
+        const context::RecommendContext none;
+        const context::RecommendContext& cx = d->Context ? *d->Context : none;
+        long long page_no = 1;
+        {
+            const auto p = cx.Param.find("page_number");                     // utils.ToInt(ctx.GetParameter("page_number"), 1)
+            if (p != cx.Param.end()) {
+                if (p->second.type == json::Value::Number) page_no = p->second.is_int ? p->second.i : (long long)p->second.num;
+                else if (p->second.type == json::Value::String) { char* end = nullptr; const long long v = strtoll(p->second.str.c_str(), &end, 10); if (!p->second.str.empty() && !*end) page_no = v; }
+            }
+            if (page_no < 1) page_no = 1;
+            if (page_no > 0xFFFFFFFFLL) page_no = 0xFFFFFFFFLL;
+        }
+        const double gamma = cx.GetFloat("pid_gamma", conf.has("PidGamma") ? conf.d("PidGamma") : 1.0);
+        const double beta = cx.GetFloat("pid_beta", conf.has("PidBeta") ? conf.d("PidBeta") : 1.0);
+        const double eta = cx.GetFloat("pid_eta", conf.has("PidEta") ? conf.d("PidEta") : 1.6);
+        const int size = d->Context ? d->Context->Size : 10;
+        if (size < 1) return fail("the page size (ctx.Size) is " + std::to_string(size));
+        std::vector<double> score(n), new_pos(n);
+        for (size_t i = 0; i < n; ++i) score[i] = d->Data[i]->Score;
+        std::vector<uint32_t> out(n);
+        std::vector<int32_t> control(n);
+        uint32_t count = 0;
+        pg_traffic* m = nullptr;
+        if (pg_traffic_compile(targets.data(), (uint32_t)T, &m) != PG_OK) return fail(pg_last_error());
+        ok = pg_traffic_sort(e->ctx, m, (uint32_t)size, (uint32_t)page_no, gamma, beta, eta, (uint32_t)n, score.data(), member.data(), nullptr, alpha.data(),
+                             out.data(), &count, control.data(), new_pos.data()) == PG_OK;
+        if (!ok) why = pg_err("pg_traffic_sort");
+        pg_traffic_free(m);
+        if (!ok) return fail(why);
+        auto integer = [](long long v) { json::Value x = json::Value::Num((double)v); x.is_int = true; x.i = v; return x; };
+        for (size_t i = 0; i < n; ++i) {
+            d->Data[i]->Properties["__traffic_control_id__"] = integer(control[i]);
+            d->Data[i]->Properties["_ORIGIN_POSITION_"] = integer((long long)i + 1);
+            d->Data[i]->Properties["_NEW_POSITION_"] = new_pos[i] == (double)(i + 1) ? integer((long long)i + 1) : json::Value::Num(new_pos[i]);
+        }
+        std::vector<module::ItemPtr> page(count);
+        for (uint32_t k = 0; k < count; ++k) page[k] = d->Data[out[k]];
+        d->Data.swap(page);
+        return true;
+    }
+};
+
 // ItemStateFilter (filter/item_state_filter.go:47-57; the DAO's keep, module/item_state_filter_hologres_dao.go:313-357) through
 // pg_item_state_filter over the engine's feature columns: an item whose id the table does not know is the item absent from the
 // state table.  The position rides in the score plane, so the kept items come back by position, in order.
@@ -3021,6 +3205,7 @@ Engine* Engine::Create(const std::string& config_json, std::string* err) {
         else if (sc.SortType == "DiversityRuleSort") e->sorts.RegisterSort(sc.Name, std::make_shared<GpuDiversityRuleSort>(e.get(), sc.DiversityConf), nullptr);
         else if (sc.SortType == "BoostScoreSort") e->sorts.RegisterSort(sc.Name, std::make_shared<GpuBoostScoreSort>(e.get(), sc.BoostConf), nullptr);
         else if (sc.SortType == "MultiRecallMixSort") e->sorts.RegisterSort(sc.Name, std::make_shared<GpuMultiRecallMixSort>(e.get(), sc.MixConf), nullptr);
+        else if (sc.SortType == "TrafficControlSort") e->sorts.RegisterSort(sc.Name, std::make_shared<GpuTrafficControlSort>(e.get(), sc.TrafficConf), nullptr);
         else if (sc.SortType == "DistinctIdSort") e->sorts.RegisterSort(sc.Name, std::make_shared<GpuDistinctIdSort>(e.get(), sc.DistinctConf), nullptr);
         else { if (err) *err = "pairec_gpu.Sorts: unknown SortType " + sc.SortType; return nullptr; }
     }
@@ -3093,6 +3278,13 @@ bool Engine::DimensionUniqueFilter(const recconf::GpuFilterConfig& conf, std::ve
 
 bool Engine::BlendFilter(const recconf::GpuFilterConfig& conf, std::vector<module::ItemPtr>* items, std::string* err) {
     return blend_filter(this, conf, items, err);
+}
+
+bool Engine::SetTrafficAlpha(const std::string& sort_name, const std::string& target_id, double alpha, std::string* err) {
+    auto s = std::dynamic_pointer_cast<GpuTrafficControlSort>(sorts.Get(sort_name));
+    if (!s) { if (err) *err = "TrafficControlSort:not find, name:" + sort_name; return false; }
+    if (!s->SetAlpha(target_id, alpha)) { if (err) *err = "TrafficControlSort " + sort_name + ": no target \"" + target_id + "\""; return false; }
+    return true;
 }
 
 bool Engine::ClasscutFilter(const recconf::GpuFilterConfig& conf, std::vector<module::ItemPtr>* items, std::string* err) {
@@ -3394,6 +3586,15 @@ int ph_engine_set_feature_column(void* h, const char* name, const int32_t* value
     const int rc = pg_features_set_column(e->ctx, e->feats, name, PG_F_I32, values, 0.0);
     if (rc != PG_OK) g_ph_err = pg_last_error();
     return rc;
+}
+
+// the alpha of one target of a pairec_gpu.Sorts TrafficControlSort entry from the next request on (the PID controller's output:
+// the Go side computes it and hands it over)
+int ph_engine_set_traffic_alpha(void* h, const char* sort_name, const char* target_id, double alpha) {
+    if (!h || !sort_name || !target_id) { g_ph_err = "ph_engine_set_traffic_alpha: NULL argument"; return -1; }
+    std::string err;
+    if (!((Engine*)h)->SetTrafficAlpha(sort_name, target_id, alpha, &err)) { g_ph_err = err; return -1; }
+    return 0;
 }
 
 int ph_set_user_fields(void* h, const char* uid, const int32_t* ids, int n) {

@@ -155,6 +155,9 @@ struct SortConfig {                        // recconf.go:820-838: Name, SortType
     json::Value MixConf;                   // pairec_gpu.Sorts entries of SortType MultiRecallMixSort only: the entry itself (MixSortRules[]
                                            // {MixStrategy, Positions, PositionField, Number, NumberRate, RecallNames, Conditions}, RemainItem,
                                            // Size: recconf.go SortConfig / MixSortConfig; Seed: ours, default 0)
+    json::Value TrafficConf;               // pairec_gpu.Sorts entries of SortType TrafficControlSort only: the entry itself (Targets[]
+                                           // {TrafficControlTargetId, ControlType, ItemExpression, Alpha}, PidGamma, PidBeta, PidEta: the
+                                           // controller's outputs as constants — the mirror has no traffic service)
     json::Value DistinctConf;              // pairec_gpu.Sorts entries of SortType DistinctIdSort only: the entry itself (DistinctIdConditions[]
                                            // {Conditions, DistinctId, DistinctIdName}: recconf.go SortConfig / DistinctIdCondition)
 };
@@ -511,6 +514,8 @@ public:
     std::map<std::string, recconf::GpuFilterConfig> gpu_filters;
     bool ItemStateFilter(const recconf::GpuFilterConfig& conf, const module::User* user, std::vector<module::ItemPtr>* items, std::string* err);
     bool BlendFilter(const recconf::GpuFilterConfig& conf, std::vector<module::ItemPtr>* items, std::string* err);   // SnakeFilter, CompletelyFairCountFilter
+    // a TrafficControlSort target's alpha from now on (the controller's output; the config's Alpha until then)
+    bool SetTrafficAlpha(const std::string& sort_name, const std::string& target_id, double alpha, std::string* err);
     bool ClasscutFilter(const recconf::GpuFilterConfig& conf, std::vector<module::ItemPtr>* items, std::string* err);   // DiversityAdjustCountFilter
     bool QuotaFilter(const recconf::GpuFilterConfig& conf, std::vector<module::ItemPtr>* items, std::string* err);   // PriorityAdjustCountFilter, PriorityAdjustCountFilterV2
     bool DimensionUniqueFilter(const recconf::GpuFilterConfig& conf, std::vector<module::ItemPtr>* items, std::string* err);   // DimensionFieldUniqueFilter
