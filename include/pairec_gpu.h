@@ -2333,6 +2333,41 @@ int pg_hbm_read_probe(pg_ctx* ctx, const pg_table* t, int reps, double* out_gbps
  * quantisation step s (x ~ s X, X in [-127,127]), *out_resid = max over rows of ||x - s X||_2 as measured —
  * the two table-side terms of the screen's error bound; 0 otherwise.  Any out pointer may be NULL. */
 int pg_table_screen_info(pg_ctx* ctx, const pg_table* t, int* out_elem_bytes, float* out_scale, float* out_resid);
+/* Diagnostics of a table's derived state (what the screens' error bounds are made of).  Read-only with
+ * respect to answers: both build and read exactly what a recall would build and stream.
+ *   info     builds the parts of `parts` (PG_DERIVED_*) that are not built yet, through the functions the recall calls and in
+ *            its order (the statistics and the main shadow first, always), and reports the scalars.  A part that cannot exist
+ *            for this table says so in its flag and is no error: i4 / r2 / pred on dim != 128 or a non-finite table, r2 and
+ *            pred on a bf16 main shadow, nx on a dim other than 64 / 128.  Flags and values of parts never asked for report
+ *            the table's current state.  elem_bytes as pg_table_screen_info.
+ *   read     copies elements [first, first + n) of one array (PG_DERIVED_ARR_*) to host memory.  Lengths, in elements:
+ *            I8 [rows + 64][dim] int8; BF16 [rows + 64][dim] u16; BLKNORM2 [ceil(rows / 32)] f32 (with the bf16 shadow);
+ *            I4 [rows + 64][16] u32; I4S [rows + 64] u32 (scale bf16 low half | residual bound bf16 high half);
+ *            I8R [rows + 64][128] int8; NX [rows + 64] f32; NXMIN [ceil(rows / 32)] f32; PRED [128 + 128 * 128] f32 followed
+ *            by 5 doubles, counted as 128 + 128 * 128 + 10 four-byte elements.  The 64 padding rows are readable (the
+ *            streaming kernels read them).  PG_ERR_INVALID on a NULL argument, an unknown array, a range outside the array
+ *            or an array that is not built (ask info first). */
+enum {
+    PG_DERIVED_STATS = 1, PG_DERIVED_I4 = 2, PG_DERIVED_R2 = 4, PG_DERIVED_NX = 8, PG_DERIVED_PRED = 16
+};
+enum {
+    PG_DERIVED_ARR_I8 = 0, PG_DERIVED_ARR_BF16 = 1, PG_DERIVED_ARR_BLKNORM2 = 2, PG_DERIVED_ARR_I4 = 3, PG_DERIVED_ARR_I4S = 4,
+    PG_DERIVED_ARR_I8R = 5, PG_DERIVED_ARR_NX = 6, PG_DERIVED_ARR_NXMIN = 7, PG_DERIVED_ARR_PRED = 8
+};
+typedef struct {
+    int32_t elem_bytes, all_finite;            /* main shadow: 0 / 1 / 2; rows all finite with norm^2 < 3e38 */
+    float max_norm, s8, resid8;                /* >= max ||x||; int8 scale; >= max ||x - s8 X8|| (int8 shadow only) */
+    int32_t i4_ok;
+    float rho4, rmax4, lam4;
+    int32_t r2_ok;
+    float s8r, resid2;
+    int32_t nx_valid;
+    float l2_slack;
+    int32_t pred_model;
+    uint64_t pred_n_sample, pred_stride;       /* the model's sample: rows min(s * stride, rows - 1), s < n_sample */
+} pg_table_derived_t;
+int pg_table_derived_info(pg_ctx* ctx, const pg_table* t, uint32_t parts, pg_table_derived_t* out);
+int pg_table_derived_read(pg_ctx* ctx, const pg_table* t, int which, uint64_t first, uint64_t n, void* out);
 
 #ifdef __cplusplus
 }

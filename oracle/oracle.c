@@ -104,6 +104,16 @@ uint64_t orc_topk_key(float score, uint32_t row) {
     return ((uint64_t)f32_ordered_bits(score) << 32) | (uint64_t)(0xFFFFFFFFu - row);
 }
 
+void orc_row_norm2(const float* table, uint64_t nrows, uint32_t dim, float* out) {
+    /* |x|^2 of every row: the chain the squared-Euclidean recall below uses for nx */
+    for (uint64_t r = 0; r < nrows; ++r) {
+        const float* x = table + (size_t)r * dim;
+        float nx = 0.0f;
+        for (uint32_t c = 0; c < dim; ++c) nx = fmaf(x[c], x[c], nx);
+        out[r] = nx;
+    }
+}
+
 void orc_dot_scores(const float* table, uint64_t nrows, uint32_t dim, const float* queries,
                     uint32_t nq, float* out, int threads) {
     /* transpose queries to [dim][nq] so the q loop vectorises; each (row,q) is still its own

@@ -32,6 +32,8 @@ void orc_synth_uniform(uint64_t seed, uint64_t n, float scale, float* out);
 
 /* ---- recall: inner-product top-K (vector_recall.go:70-102, hologres_vector_recall.go:23) --- */
 uint64_t orc_topk_key(float score, uint32_t row);
+/* |x|^2 of every row as a k-ascending fmaf chain (the nx of orc_recall_topk_l2) */
+void orc_row_norm2(const float* table, uint64_t nrows, uint32_t dim, float* out);
 void orc_dot_scores(const float* table, uint64_t nrows, uint32_t dim, const float* queries,
                     uint32_t nq, float* out /* [nq][nrows] */, int threads);
 /* exact top-K (score desc by IEEE total order, row asc) of rows [0,nrows); out_rows are

@@ -50,6 +50,8 @@ def lib():
         L.orc_topk_key.restype = u64
         L.orc_topk_key.argtypes = [C.c_float, u32]
         L.orc_dot_scores.argtypes = [f32p, u64, u32, f32p, u32, f32p, i32]
+        L.orc_row_norm2.argtypes = [f32p, u64, u32, f32p]
+        L.orc_row_norm2.restype = None
         L.orc_recall_topk.restype = u32
         L.orc_recall_topk.argtypes = [f32p, u64, u32, u64, f32p, u32, u32, C.POINTER(u64), f32p, i32]
         L.orc_recall_topk_l2.restype = u32
@@ -130,6 +132,14 @@ def dot_scores(table: np.ndarray, queries: np.ndarray, threads: int = 0) -> np.n
     out = np.empty((queries.shape[0], table.shape[0]), dtype=np.float32)
     lib().orc_dot_scores(_f32p(table), table.shape[0], table.shape[1], _f32p(queries),
                          queries.shape[0], _f32p(out), threads)
+    return out
+
+
+def row_norm2(table: np.ndarray) -> np.ndarray:
+    """|x|^2 of every row as the k-ascending fp32 fmaf chain (the squared-Euclidean recall's nx)"""
+    table = np.ascontiguousarray(table, dtype=np.float32)
+    out = np.empty(table.shape[0], dtype=np.float32)
+    lib().orc_row_norm2(_f32p(table), table.shape[0], table.shape[1], _f32p(out))
     return out
 
 

@@ -21,7 +21,7 @@ EXPORTS = [
     "pg_rank_fm2t", "pg_rank_fm2t_dev", "pg_expr_compile", "pg_expr_free", "pg_expr_num_vars", "pg_expr_set_score_rewrites", "pg_expr_compile_typed", "pg_expr_is_antlr", "pg_fuse_scores_dev",
     "pg_expr_var_name", "pg_expr_eval", "pg_expr_eval_dev", "pg_sort_scores", "pg_sort_scores_dev",
     "pg_dpp", "pg_stats", "pg_last_scan_kernel_ms", "pg_rows_to_local_dev", "pg_widen_f32_dev",
-    "pg_hbm_read_probe", "pg_table_screen_info", "pg_ssd", "pg_ssd_emb", "pg_features_create", "pg_features_destroy", "pg_features_set_column",
+    "pg_hbm_read_probe", "pg_table_screen_info", "pg_table_derived_info", "pg_table_derived_read", "pg_ssd", "pg_ssd_emb", "pg_features_create", "pg_features_destroy", "pg_features_set_column",
     "pg_features_column_index", "pg_features_num_columns", "pg_features_gather_i32_dev",
     "pg_features_gather_f32_dev", "pg_rank_fm2t_rows_dev", "pg_rank_fm2t_rows", "pg_recommend_dnn3_dev", "pg_set_option",
     "pg_table_fill_gaussian", "pg_table_fill_mixture", "pg_group_exchange_stats", "pg_dpp_ex", "pg_i2i_recall", "pg_online_vector_recall", "pg_fm2t_user_embedding",
@@ -119,6 +119,19 @@ class PgIndexServingStats(C.Structure):
 class PgIndexWhereStats(C.Structure):
     _fields_ = [("builds", C.c_uint64), ("hits", C.c_uint64), ("evictions", C.c_uint64), ("entries", C.c_uint64),
                 ("bytes", C.c_uint64)]
+
+
+class PgTableDerived(C.Structure):
+    _fields_ = [("elem_bytes", C.c_int32), ("all_finite", C.c_int32), ("max_norm", C.c_float), ("s8", C.c_float),
+                ("resid8", C.c_float), ("i4_ok", C.c_int32), ("rho4", C.c_float), ("rmax4", C.c_float), ("lam4", C.c_float),
+                ("r2_ok", C.c_int32), ("s8r", C.c_float), ("resid2", C.c_float), ("nx_valid", C.c_int32), ("l2_slack", C.c_float),
+                ("pred_model", C.c_int32), ("pred_n_sample", C.c_uint64), ("pred_stride", C.c_uint64)]
+
+
+# pg_table_derived_info's parts and pg_table_derived_read's arrays (PG_DERIVED_*, PG_DERIVED_ARR_*)
+DERIVED_STATS, DERIVED_I4, DERIVED_R2, DERIVED_NX, DERIVED_PRED = 1, 2, 4, 8, 16
+DERIVED_ALL = 31
+DERIVED_ARRAYS = {"i8": 0, "bf16": 1, "blknorm2": 2, "i4": 3, "i4s": 4, "i8r": 5, "nx": 6, "nxmin": 7, "pred": 8}
 
 
 class PgRecallExcludeOpts(C.Structure):
@@ -498,6 +511,8 @@ def load():
         "pg_last_scan_kernel_ms": [vp, P(C.c_double), P(u64)],
         "pg_hbm_read_probe": [vp, vp, i32, P(C.c_double)],
         "pg_table_screen_info": [vp, vp, P(C.c_int), P(C.c_float), P(C.c_float)],
+        "pg_table_derived_info": [vp, vp, u32, P(PgTableDerived)],
+        "pg_table_derived_read": [vp, vp, i32, u64, u64, vp],
     }
     missing = [n for n in EXPORTS if not hasattr(L, n)]
     if missing:

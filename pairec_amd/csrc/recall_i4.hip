@@ -234,25 +234,38 @@ __global__ __launch_bounds__(256) void table_quant4_kernel(const float* __restri
         // row of values below 7e-30 rounds to them and its residual says so): recall_i4m.hip divides by it
         const float s = bf16_up(fmaxf(amax / 7.0f, 1e-30f));
         const float inv = 1.0f / s;
-        float rs = 0.0f;
+        float r[8], ra = 0.0f;
         uint32_t word = 0;
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             int X = __float2int_rn(v[i] * inv);
             X = X > 7 ? 7 : (X < -7 ? -7 : X);
-            const float r = __fmaf_rn(-s, (float)X, v[i]);
-            rs = __fmaf_rn(r, r, rs);
+            r[i] = __fmaf_rn(-s, (float)X, v[i]);
+            ra = fmaxf(ra, fabsf(r[i]));
             word |= (uint32_t)(X + 8) << (8 * (i & 3) + 4 * (i >> 2));
         }
         if (g < n8) out4[g] = word;
+        // ||r|| = ra sqrt(sum (r / ra)^2), ra the row's largest |r|: the squares of a row of tiny values (5e-31: below the scale's
+        // floor, all nibbles zero) underflow in fp32 and the row's bound came out as the bare 1e-30.  Scaled, the largest term is
+        // exactly 1 and whatever still underflows is below 2^-75 of it.
+#pragma unroll
+        for (int off = 1; off < G; off <<= 1) ra = fmaxf(ra, __shfl_xor(ra, off, 64));
+        const float rq = ra > 0.0f ? ra : 1.0f;
+        float rs = 0.0f;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const float q = r[i] / rq;
+            rs = __fmaf_rn(q, q, rs);
+        }
 #pragma unroll
         for (int off = 1; off < G; off <<= 1) rs += __shfl_xor(rs, off, 64);
         if (g < n8 && (g % G) == 0) {
             // (the residual was accumulated in fp32: a relative 1e-3 covers that, as for the int8 shadow)
-            const float R = bf16_up(sqrtf(rs) * 1.001f + 1e-30f);
+            const float R = bf16_up(ra * sqrtf(rs) * 1.001f + 1e-30f);
             out_scale[g / G] = (__float_as_uint(s) >> 16) | (__float_as_uint(R) & 0xffff0000u);
             if (ss > 0.0f) lam += R / sqrtf(ss);
-            rho_mx = fmaxf(rho_mx, s > 1e-18f ? rs / (s * s * (float)DIM) : 0.0f);
+            const float t = ra / s;
+            rho_mx = fmaxf(rho_mx, s > 1e-18f ? t * t * rs / (float)DIM : 0.0f);
             r_mx = fmaxf(r_mx, R);
         }
     }

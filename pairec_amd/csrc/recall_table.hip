@@ -15,11 +15,16 @@ __global__ void block_nxmin_kernel(const float* __restrict__ nx, uint64_t rows, 
     double slack = 0.0, sum = 0.0;
     if (b < nblocks) {
         float m = __builtin_inff();
+        bool nan = false;                            // (fminf skips a NaN: it has to be seen separately)
         for (uint32_t i = 0; i < (uint32_t)kPieceRows; ++i) {
             const uint64_t r = (uint64_t)b * kPieceRows + i;
-            if (r < rows) m = fminf(m, nx[r]);
+            if (r < rows) {
+                const float v = nx[r];
+                nan |= v != v;
+                m = fminf(m, v);
+            }
         }
-        m = m == m ? m : 0.0f;                       // (a NaN norm: no help from this block)
+        m = nan ? 0.0f : m;                          // (a NaN norm: no help from this block)
         out[b] = m;
         for (uint32_t i = 0; i < (uint32_t)kPieceRows; ++i) {
             const uint64_t r = (uint64_t)b * kPieceRows + i;
@@ -365,6 +370,12 @@ int ensure_table_stats(pg_ctx* ctx, const pg_table* t) {
     return PG_OK;
 }
 
+// the threshold model's row sample: rows min(s * stride, rows - 1), s < n_sample
+static inline void pred_sample(uint64_t rows, uint64_t* n_sample, uint64_t* stride) {
+    *n_sample = rows < (1u << 20) ? rows : (1u << 20);
+    *stride = rows / *n_sample;
+}
+
 // the threshold model of a table (dim 128): mean and covariance of a row sample, built once per generation of the rows
 int ensure_pred_model(pg_ctx* ctx, const pg_table* t) {
     std::lock_guard<std::mutex> state_guard(g_table_state_mu);
@@ -376,8 +387,8 @@ int ensure_pred_model(pg_ctx* ctx, const pg_table* t) {
         return PG_OK;                                 // no model: the pilot plan serves
     }
     PG_HIP(hipMemsetAsync(t->derived.d_pred, 0, bytes, ctx->stream));
-    const uint64_t n_sample = t->rows < (1u << 20) ? t->rows : (1u << 20);
-    const uint64_t stride = t->rows / n_sample;
+    uint64_t n_sample, stride;
+    pred_sample(t->rows, &n_sample, &stride);
     pred_moments_kernel<<<(uint32_t)ctx->num_cus, 256, 0, ctx->stream>>>(t->d, t->rows, stride, n_sample, t->derived.d_pred, t->derived.d_pred + 128);
     pred_finish_kernel<<<128, 128, 0, ctx->stream>>>(t->derived.d_pred, n_sample);
     pred_means_kernel<<<1, 128, 0, ctx->stream>>>(t->derived.d_pred, n_sample);
@@ -432,6 +443,76 @@ int pg_table_screen_info(pg_ctx* ctx, const pg_table* t, int* out_elem_bytes, fl
     if (out_elem_bytes) *out_elem_bytes = screened ? (t->derived.shadow_is_i8 ? 1 : 2) : 0;
     if (out_scale) *out_scale = screened && t->derived.shadow_is_i8 ? t->derived.s8 : 0.0f;
     if (out_resid) *out_resid = screened && t->derived.shadow_is_i8 ? t->derived.resid8 : 0.0f;
+    return PG_OK;
+}
+
+// Diagnostics of a table's derived state.  Lock order as table_state.hpp prescribes for a reader of `derived`: ctx->mu, the
+// table's shared lock, then (inside the ensure_* calls) g_table_state_mu; what is read afterwards was built by those calls.
+int pg_table_derived_info(pg_ctx* ctx, const pg_table* t, uint32_t parts, pg_table_derived_t* out) {
+    PG_REQUIRE(ctx && t && out, "pg_table_derived_info: NULL argument");
+    const uint32_t known = PG_DERIVED_STATS | PG_DERIVED_I4 | PG_DERIVED_R2 | PG_DERIVED_NX | PG_DERIVED_PRED;
+    PG_REQUIRE((parts & ~known) == 0, "pg_table_derived_info: unknown parts 0x%x", parts);
+    std::lock_guard<std::mutex> g(ctx->mu);
+    pg::TableRead tr(t->rw);
+    int rc;
+    if ((rc = pg::ensure_table_stats(ctx, t))) return rc;     // always first: it is what resets the parts below after a write
+    const pg::TableDerived& d = t->derived;
+    const bool screened = d.stats_valid && d.all_finite;
+    if ((parts & PG_DERIVED_I4) && (rc = pg::ensure_table_i4(ctx, t))) return rc;
+    if ((parts & PG_DERIVED_R2) && (rc = pg::ensure_table_r2(ctx, t))) return rc;
+    if ((parts & PG_DERIVED_NX) && (t->dim == 64 || t->dim == 128) && (rc = pg::ensure_table_nx(ctx, t))) return rc;
+    // (the recall builds the model for int8-screened dim-128 tables only: the kernels assume 128 columns)
+    if ((parts & PG_DERIVED_PRED) && t->dim == 128 && screened && d.shadow_is_i8 && (rc = pg::ensure_pred_model(ctx, t))) return rc;
+    memset(out, 0, sizeof(*out));
+    out->elem_bytes = screened ? (d.shadow_is_i8 ? 1 : 2) : 0;
+    out->all_finite = d.stats_valid && d.all_finite ? 1 : 0;
+    out->max_norm = d.stats_valid ? d.max_norm : 0.0f;
+    out->s8 = screened && d.shadow_is_i8 ? d.s8 : 0.0f;
+    out->resid8 = screened && d.shadow_is_i8 ? d.resid8 : 0.0f;
+    out->i4_ok = d.i4_ok ? 1 : 0;
+    if (d.i4_ok) { out->rho4 = d.rho4; out->rmax4 = d.rmax4; out->lam4 = d.lam4; }
+    out->r2_ok = d.r2_ok ? 1 : 0;
+    if (d.r2_ok) { out->s8r = d.s8r; out->resid2 = d.resid2; }
+    out->nx_valid = d.nx_valid ? 1 : 0;
+    if (d.nx_valid) out->l2_slack = d.l2_slack;
+    out->pred_model = d.pred_model ? 1 : 0;
+    if (d.pred_model) pg::pred_sample(t->rows, &out->pred_n_sample, &out->pred_stride);
+    return PG_OK;
+}
+
+int pg_table_derived_read(pg_ctx* ctx, const pg_table* t, int which, uint64_t first, uint64_t n, void* out) {
+    PG_REQUIRE(ctx && t && (n == 0 || out), "pg_table_derived_read: NULL argument");
+    std::lock_guard<std::mutex> g(ctx->mu);
+    pg::TableRead tr(t->rw);
+    const pg::TableDerived& d = t->derived;
+    const void* src = nullptr;
+    uint64_t len = 0, esz = 0;
+    bool built = false;
+    {
+        // a write since the last build invalidates everything (ensure_table_stats has not yet reset the later parts' flags)
+        std::lock_guard<std::mutex> sg(pg::g_table_state_mu);
+        const bool cur = d.stats_valid, screened = cur && d.all_finite;
+        const uint64_t padded = t->rows + 64, nblk = (t->rows + pg::kPieceRows - 1) / pg::kPieceRows;
+        switch (which) {
+            case PG_DERIVED_ARR_I8: src = d.d8; len = padded * t->dim; esz = 1; built = screened && d.shadow_is_i8; break;
+            case PG_DERIVED_ARR_BF16: src = d.d16; len = padded * t->dim; esz = 2; built = screened && !d.shadow_is_i8; break;
+            case PG_DERIVED_ARR_BLKNORM2: src = d.dnorm2; len = nblk; esz = 4; built = screened && !d.shadow_is_i8; break;
+            case PG_DERIVED_ARR_I4: src = d.d4; len = padded * 16; esz = 4; built = cur && d.i4_ok; break;
+            case PG_DERIVED_ARR_I4S: src = d.d4s; len = padded; esz = 4; built = cur && d.i4_ok; break;
+            case PG_DERIVED_ARR_I8R: src = d.d8r; len = padded * 128; esz = 1; built = cur && d.r2_ok; break;
+            case PG_DERIVED_ARR_NX: src = d.d_nx; len = padded; esz = 4; built = d.nx_valid; break;
+            case PG_DERIVED_ARR_NXMIN: src = d.d_nxmin; len = nblk; esz = 4; built = d.nx_valid; break;
+            case PG_DERIVED_ARR_PRED: src = d.d_pred; len = 128 + 128 * 128 + 10; esz = 4; built = cur && d.pred_model; break;
+            default: break;
+        }
+    }
+    PG_REQUIRE(esz != 0, "pg_table_derived_read: unknown array %d", which);
+    PG_REQUIRE(built && src, "pg_table_derived_read: array %d is not built (pg_table_derived_info builds it)", which);
+    PG_REQUIRE(first <= len && n <= len - first, "pg_table_derived_read: elements [%llu,+%llu) outside array %d of %llu",
+               (unsigned long long)first, (unsigned long long)n, which, (unsigned long long)len);
+    if (n == 0) return PG_OK;
+    PG_HIP(hipMemcpyAsync(out, (const char*)src + first * esz, n * esz, hipMemcpyDeviceToHost, ctx->stream));
+    PG_HIP(hipStreamSynchronize(ctx->stream));
     return PG_OK;
 }
 

@@ -1316,6 +1316,32 @@ class Table:
         _lib.check(self.ctx.L.pg_table_screen_info(self.ctx.h, self.h, C.byref(eb), C.byref(sc), C.byref(rs)))
         return eb.value, sc.value, rs.value
 
+    _DERIVED_DTYPES = {"i8": np.int8, "bf16": np.uint16, "blknorm2": np.float32, "i4": np.uint32, "i4s": np.uint32, "i8r": np.int8,
+                       "nx": np.float32, "nxmin": np.float32, "pred": np.uint32}
+
+    def derived_info(self, parts: int = _lib.DERIVED_ALL) -> dict:
+        """pg_table_derived_info: builds the asked parts (_lib.DERIVED_*) that are not built yet and returns the scalars of the
+        table's derived state as a dict (field names of pg_table_derived_t)."""
+        out = _lib.PgTableDerived()
+        _lib.check(self.ctx.L.pg_table_derived_info(self.ctx.h, self.h, int(parts), C.byref(out)))
+        return {n: getattr(out, n) for n, _ in _lib.PgTableDerived._fields_}
+
+    def derived_len(self, which: str) -> int:
+        """elements of one derived array (pg_table_derived_read's layouts)"""
+        padded, nblk = self.rows + 64, (self.rows + 31) // 32
+        return {"i8": padded * self.dim, "bf16": padded * self.dim, "blknorm2": nblk, "i4": padded * 16, "i4s": padded,
+                "i8r": padded * 128, "nx": padded, "nxmin": nblk, "pred": 128 + 128 * 128 + 10}[which]
+
+    def derived_read(self, which: str, first: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """pg_table_derived_read: elements [first, first + n) of one derived array (a name of _lib.DERIVED_ARRAYS; n = None: to
+        the array's end, padding rows included) as a flat numpy array; "pred" comes as uint32 words (f32 mean and covariance,
+        then 5 doubles)."""
+        if n is None:
+            n = self.derived_len(which) - first
+        out = np.empty(max(int(n), 0), dtype=self._DERIVED_DTYPES[which])
+        _lib.check(self.ctx.L.pg_table_derived_read(self.ctx.h, self.h, _lib.DERIVED_ARRAYS[which], int(first), int(n), _ptr(out)))
+        return out
+
     def fill_synthetic(self, seed: int, normalize: bool = True):
         _lib.check(self.ctx.L.pg_table_fill_synthetic(self.ctx.h, self.h, seed, int(normalize)))
 
