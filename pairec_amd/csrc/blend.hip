@@ -14,14 +14,15 @@
 //                   position; no loop over retain;
 //   SNAKE   keys    one key array per config entry (members: the score or the recall's plane; everything else NaN), sorted as
 //                   nq x n_entries segments;
-//           compact each entry's order to its members, in order (ballot + mbcnt + per-wave counts): the sort cannot tell a
+//           compact each entry's order to its members, in order (block_rank.hpp's chunk_rank): the sort cannot tell a
 //                   non-member from a member with a NaN key; the head of every list is kept in LDS as uint16;
 //           walk    one wave, a (round, entry) step at a time, 64 list entries per look: ballot the untaken ones against a bitmap
-//                   of input positions in LDS, take by mbcnt, mark, record {position, entry} at the running output position;
+//                   of input positions in LDS, take by wave_rank, mark, record {position, entry} at the running output position;
 //           gather  the whole workgroup, from the pick records;
 //   pad     the slots behind the kept entries.
 // pg_candidates_blend_host states the same answer on host arrays with plain containers; the tests hold the device to it.
 #include "pipeline.hpp"
+#include "block_rank.hpp"
 
 #include <algorithm>
 #include <vector>
@@ -92,7 +93,7 @@ __global__ __launch_bounds__(kBlendThreads) void blend_snake_kernel(BlendArgs a)
     __shared__ uint16_t head[kBlendMaxSources][kBlendLdsList];
     __shared__ uint32_t taken[kBlendMaxCap / 32];
     __shared__ uint32_t llen[kBlendMaxSources], cur[kBlendMaxSources];
-    __shared__ uint32_t wcnt[2][kBlendWaves];
+    __shared__ uint32_t wcnt[2 * kBlendWaves];
     __shared__ uint32_t total_s;
     const uint32_t q = blockIdx.x, tid = threadIdx.x, wave = tid / kWave, lane = tid & (kWave - 1);
     const uint32_t cap = a.in.cap, out_cap = a.out.out_cap, n_e = a.n_entries;
@@ -121,24 +122,16 @@ __global__ __launch_bounds__(kBlendThreads) void blend_snake_kernel(BlendArgs a)
                     mem = s != kBlendNone && blend_member(a, in0, pos, s, si, &own);
                 }
             }
-            uint32_t* wc = wcnt[it & 1u];                        // (two sets of counts: a wave ahead by one chunk writes the other one)
-            const unsigned long long m = __ballot(mem);
-            const uint32_t before = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-            if (lane == 0) wc[wave] = (uint32_t)__popcll(m);
-            __syncthreads();
+            uint32_t r, total;
+            chunk_rank<kBlendWaves>(mem, wcnt, it, &r, &total);
             if (mem) {
-                uint32_t rank = llen[i] + before;
-                for (uint32_t w = 0; w < wave; ++w) rank += wc[w];
+                const uint32_t rank = llen[i] + r;
                 a.lists[l0 + rank] = pos;                        // (rank < cap: ranks count distinct positions of the order)
                 if (rank < kBlendLdsList) head[i][rank] = (uint16_t)pos;
             }
             __syncthreads();
             // (the length moves between this chunk's reads and the next chunk's, which lie behind its barrier)
-            if (tid == 0) {
-                uint32_t s = 0;
-                for (uint32_t w = 0; w < kBlendWaves; ++w) s += wc[w];
-                llen[i] += s;
-            }
+            if (tid == 0) llen[i] += total;
         }
     }
     __syncthreads();
@@ -164,9 +157,8 @@ __global__ __launch_bounds__(kBlendThreads) void blend_snake_kernel(BlendArgs a)
                     uint32_t pos = 0;
                     if (have) pos = c + lane < kBlendLdsList ? (uint32_t)head[i][c + lane] : a.lists[l0 + c + lane];
                     const bool fresh = have && !((taken[pos >> 5] >> (pos & 31u)) & 1u);
-                    const unsigned long long m = __ballot(fresh);
-                    const uint32_t nf = (uint32_t)__popcll(m);
-                    const uint32_t before = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+                    uint32_t nf;
+                    const uint32_t before = wave_rank(fresh, &nf);
                     uint32_t used = n, np = nf;
                     bool take = fresh;
                     if (a.skip) {
@@ -315,7 +307,7 @@ __global__ __launch_bounds__(kBlendThreads) void blend_fair_kernel(BlendArgs a) 
         uint32_t before = 0;
         for (uint32_t r = 0; r < kBlendMaxSources; ++r) {
             const unsigned long long m = __ballot(s == r);
-            if (s == r) before = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+            if (s == r) before = ballot_rank(m);
             if (lane == 0) wc[r][wave] = (uint32_t)__popcll(m);
         }
         __syncthreads();

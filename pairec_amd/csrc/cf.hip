@@ -21,6 +21,7 @@
 // (module/realtime_user2item_hologres_dao.go:203-204: a descending sort, then uniqItems).  Its triggers may come from rtu2i.hip's
 // trigger kernel: lists at a fixed stride with a device count per request (CfTrigDev), read without a host round trip.
 #include "cf_shared.hpp"
+#include "block_rank.hpp"
 
 #include <cmath>
 #include <functional>
@@ -145,7 +146,7 @@ __device__ void cf_accumulate(const CfArgs& a, uint32_t* keys, double* acc, uint
         const bool occ = key != kCfEmpty;
         const unsigned long long m = __ballot(occ);
         if (m == 0) continue;
-        const uint32_t before = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+        const uint32_t before = ballot_rank(m);
         const int leader = __ffsll((long long)m) - 1;
         uint32_t base = 0;
         if (occ && before == 0) base = atomicAdd(n_items, (uint32_t)__popcll(m));

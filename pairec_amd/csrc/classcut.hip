@@ -17,13 +17,14 @@
 //   cut kernel    one workgroup of 1 024 lanes per request over the trim's score order.  Classes run one after another (limit_c
 //                 needs the picks of the classes before it); inside a class the order is walked 1 024 positions at a time: a
 //                 member's rank = the running count + the members in the waves before it (per-wave counts in LDS) + those in the
-//                 lanes before it (ballot + mbcnt); it is in the window iff rank < limit_c and picked iff its bit in a 2 KB LDS
+//                 lanes before it (block_rank.hpp's wave_rank); it is in the window iff rank < limit_c and picked iff its bit in a 2 KB LDS
 //                 bitmap of input positions is clear; picks get base + their prefix count and set their bit.  The walk of a
 //                 class ends with the chunk in which the rank reaches the limit.  Whatever steers the walk is the same in every
 //                 lane: it comes out of LDS behind a barrier.
 // pg_classcut_masks_host / pg_candidates_classcut_host state the same answer on host arrays with plain containers.
 #include "pipeline.hpp"
 #include "cond_eval.hpp"
+#include "block_rank.hpp"
 #include "expr_prog.hpp"
 
 #include <algorithm>
@@ -180,9 +181,9 @@ __global__ __launch_bounds__(kCcChunk) void candidates_classcut_kernel(CutArgs a
                 pos = a.order[in0 + i];
                 if (pos < cap) member = ((a.masks[in0 + pos] >> c) & 1u) != 0;
             }
-            const unsigned long long mm = __ballot(member);
-            const uint32_t mbefore = __builtin_amdgcn_mbcnt_hi((uint32_t)(mm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mm, 0u));
-            if (lane == 0) wmem[wave] = (uint32_t)__popcll(mm);
+            uint32_t n_mem;
+            const uint32_t mbefore = wave_rank(member, &n_mem);
+            if (lane == 0) wmem[wave] = n_mem;
             __syncthreads();                                          // (also: the picks' bits of the chunk before are set)
             uint32_t mbelow = 0, mtotal = 0;
 #pragma unroll
@@ -193,9 +194,9 @@ __global__ __launch_bounds__(kCcChunk) void candidates_classcut_kernel(CutArgs a
             }
             // the window: the class's first `limit` members; a place an earlier pick holds is used up all the same
             const bool pick = member && rank_run + mbelow + mbefore < limit && !((taken[pos >> 5] >> (pos & 31u)) & 1u);
-            const unsigned long long pm = __ballot(pick);
-            const uint32_t pbefore = __builtin_amdgcn_mbcnt_hi((uint32_t)(pm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)pm, 0u));
-            if (lane == 0) wpick[wave] = (uint32_t)__popcll(pm);
+            uint32_t n_pick;
+            const uint32_t pbefore = wave_rank(pick, &n_pick);
+            if (lane == 0) wpick[wave] = n_pick;
             __syncthreads();                                          // (every lane has read wmem and its bit of taken)
             uint32_t pbelow = 0, ptotal = 0;
 #pragma unroll

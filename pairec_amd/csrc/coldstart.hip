@@ -12,6 +12,7 @@
 //            by per-block counts and a scan — and the order of the <= k survivors by split_sort.hpp's runs and merge (up to
 //            8 192 of them; counting ranks above).
 #include "common.hpp"
+#include "block_rank.hpp"
 #include "coldstart_host.hpp"
 #include "split_sort.hpp"
 
@@ -52,29 +53,7 @@ struct pg_cold {
 namespace pg {
 namespace {
 
-// ---- block-wide exclusive scan (256 threads; ws: 4 words of LDS) ---------------------------------------------------------
-template <class T>
-__device__ inline T block_excl_scan(T v, T* total, T* ws) {
-    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-    T inc = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const T o = __shfl_up(inc, off, 64);
-        if (lane >= (uint32_t)off) inc += o;
-    }
-    if (lane == 63u) ws[wv] = inc;
-    __syncthreads();
-    T base = 0, tot = 0;
-#pragma unroll
-    for (uint32_t i = 0; i < 4; ++i) {
-        const T x = ws[i];
-        if (i < wv) base += x;
-        tot += x;
-    }
-    __syncthreads();                     // (ws may be written again)
-    *total = tot;
-    return base + inc - v;
-}
+constexpr uint32_t kColdWaves = 256 / kWave;                                         // every kernel here: 256 lanes; a scan's ws: 4 elements of LDS
 
 // ---- exclusive scan of n elements in place: chunk sums, their scan by one workgroup, the chunks -----------------------------
 template <class T>
@@ -85,7 +64,7 @@ __global__ __launch_bounds__(256) void scan_sums_kernel(const T* __restrict__ in
 #pragma unroll
     for (uint32_t j = 0; j < 4; ++j) s += i0 + j < n ? in[i0 + j] : (T)0;
     T total;
-    (void)block_excl_scan(s, &total, ws);
+    (void)block_excl_scan<kColdWaves>(s, ws, &total);
     if (threadIdx.x == 0) sums[blockIdx.x] = total;
 }
 template <class T>
@@ -96,9 +75,10 @@ __global__ __launch_bounds__(256) void scan_top_kernel(T* __restrict__ sums, uin
         const uint32_t i = base + threadIdx.x;
         const T v = i < m ? sums[i] : (T)0;
         T total;
-        const T ex = block_excl_scan(v, &total, ws);
+        const T ex = block_excl_scan<kColdWaves>(v, ws, &total);
         if (i < m) sums[i] = carry + ex;
         carry += total;
+        __syncthreads();                                      // (the next round's scan writes ws again)
     }
 }
 template <class T>
@@ -112,7 +92,7 @@ __global__ __launch_bounds__(256) void scan_apply_kernel(T* __restrict__ io, uin
         s += v[j];
     }
     T total;
-    T ex = block_excl_scan(s, &total, ws) + sums[blockIdx.x];
+    T ex = block_excl_scan<kColdWaves>(s, ws, &total) + sums[blockIdx.x];
 #pragma unroll
     for (uint32_t j = 0; j < 4; ++j) {
         if (i0 + j < n) io[i0 + j] = ex;
@@ -271,7 +251,7 @@ __global__ __launch_bounds__(256) void cold_pick_kernel(uint32_t* __restrict__ h
     hist[tid] = 0;                                            // (the next pass's)
     const uint32_t rem = st->remaining;
     uint32_t total;
-    const uint32_t ex = block_excl_scan(c, &total, ws);       // (its barriers stand between every lane's read of the state and the write)
+    const uint32_t ex = block_excl_scan<kColdWaves>(c, ws, &total);  // (its barrier stands between every lane's read of the state and the write)
     if (c && ex < rem && rem <= ex + c) {
         st->prefix |= (unsigned long long)tid << shift;
         st->remaining = rem - ex;
@@ -291,7 +271,7 @@ __global__ __launch_bounds__(256) void cold_tile_count_kernel(const uint32_t* __
     for (uint32_t j = 0; j < 4; ++j)
         if ((nib >> j) & 1u) v += key[j] < T ? (1ull << 32) : key[j] == T ? 1ull : 0ull;
     unsigned long long total;
-    (void)block_excl_scan(v, &total, ws);
+    (void)block_excl_scan<kColdWaves>(v, ws, &total);
     if (threadIdx.x == 0) counts[blockIdx.x] = total;
 }
 // scan: the tile counts' exclusive scan.  The better rows fill [0, kk - t) in row order, the first t rows of the threshold key
@@ -311,7 +291,7 @@ __global__ __launch_bounds__(256) void cold_collect_kernel(const uint32_t* __res
     for (uint32_t j = 0; j < 4; ++j)
         if ((nib >> j) & 1u) v += key[j] < T ? (1ull << 32) : key[j] == T ? 1ull : 0ull;
     unsigned long long total;
-    const unsigned long long at = scan[blockIdx.x] + block_excl_scan(v, &total, ws);
+    const unsigned long long at = scan[blockIdx.x] + block_excl_scan<kColdWaves>(v, ws, &total);
     uint32_t bpos = (uint32_t)(at >> 32), tpos = (uint32_t)at;
     const uint32_t n_better = kk - min(t_take, kk);
 #pragma unroll

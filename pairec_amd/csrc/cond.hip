@@ -32,14 +32,14 @@
 // an 8-deep stack in registers (constant indices only: the top is always slot 0).  The candidate's loads, the pick of a column's
 // value and its reading as float64 are cond_eval.hpp's, shared with classcut.hip; the compiled object, its terms and rules
 // (CondProgram, cond_term, cond_rule) and their bind to a store are stated there too, shared with mixsort.hip.
-//   item_state_filter_kernel   one workgroup per request walks cap in chunks of 1 024: ballot + mbcnt within a wave, per-wave
-//                              counts in LDS (two sets: a wave one chunk ahead writes the other), every lane adds up the counts
-//                              itself, so one barrier per chunk; kept entries move to the front with everything carried.
+//   item_state_filter_kernel   one workgroup per request walks cap in chunks of 1 024 (block_rank.hpp's chunk_rank: one barrier
+//                              per chunk); kept entries move to the front with everything carried.
 //   boost_scores_kernel        256 lanes per workgroup, grid (cap / 256, nq).
 //   distinct_ids_kernel        the same grid: DistinctIdSort (sort/distinct_id_sort.go:52-72) — the id of the
 //                              first rule that matches, else the entry's position + 1.
 #include "pipeline.hpp"
 #include "cond_eval.hpp"
+#include "block_rank.hpp"
 #include "expr_prog.hpp"
 
 #include <algorithm>
@@ -113,8 +113,8 @@ struct FilterArgs {
 
 // Request q = blockIdx.x.
 __global__ __launch_bounds__(kCondChunk) void item_state_filter_kernel(CondProgram p, FilterArgs a) {
-    __shared__ uint32_t wcnt[2][kCondWaves];
-    const uint32_t q = blockIdx.x, tid = threadIdx.x, wave = tid / kWave, lane = tid & (kWave - 1);
+    __shared__ uint32_t wcnt[2 * kCondWaves];
+    const uint32_t q = blockIdx.x, tid = threadIdx.x;
     const size_t q0 = (size_t)q * a.in.cap;
     const uint32_t n_valid = cand_n_valid(a.in, q);
     CondUser u;
@@ -132,19 +132,9 @@ __global__ __launch_bounds__(kCondChunk) void item_state_filter_kernel(CondProgr
                 keep = cond_rule(p, 0, item, u);
             }
         }
-        const unsigned long long m = __ballot(keep);
-        const uint32_t before = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-        uint32_t* wc = wcnt[it & 1u];
-        if (lane == 0) wc[wave] = (uint32_t)__popcll(m);
-        __syncthreads();
-        uint32_t below = 0, total = 0;
-#pragma unroll
-        for (uint32_t w = 0; w < kCondWaves; ++w) {
-            const uint32_t c = wc[w];
-            below += w < wave ? c : 0u;
-            total += c;
-        }
-        if (keep) cand_carry(a.in, a.out, q0 + pos, q0 + run + below + before, true);      // (run + below + before <= pos < cap)
+        uint32_t r, total;
+        chunk_rank<kCondWaves>(keep, wcnt, it, &r, &total);
+        if (keep) cand_carry(a.in, a.out, q0 + pos, q0 + run + r, true);                   // (run + r <= pos < cap)
         run += total;
     }
     cand_pad(a.in, a.out, q, run + tid, kCondChunk, kCandNan);          // padding behind the count

@@ -18,11 +18,12 @@
 //   count    the waves of the chunk in turn (a barrier between two): a lane reads its slot's count, is kept iff count + rank <
 //            limit, and the last peer stores min(count + group, limit).  Waves in position order, lanes in position order
 //            within the wave: no atomic decides an order;
-//   compact  kept entries move to the front by ballot rank + per-wave counts in LDS + a running base, as ItemStateFilter's do
-//            (cond.hip), with everything carried (cand_carry).
+//   compact  kept entries move to the front by block_rank.hpp's chunk_rank + a running base, with everything carried
+//            (cand_carry).
 // Two tiers by cap alone: up to kDimcapLdsMaxCap the table is dynamic LDS (12 bytes per slot, 2 cap slots: 144 KiB at the
 // boundary), above it the request's slice of kSlotDimcap, every access an agent-scope atomic as the fan-in's scratch tier.
 #include "cand_lists.hpp"
+#include "block_rank.hpp"
 
 #include <unordered_map>
 
@@ -60,7 +61,7 @@ struct DimcapArgs {
 template <bool kLds>
 __global__ __launch_bounds__(kDimcapChunk) void dimcap_kernel(DimcapArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char dimcap_lds[];
-    __shared__ uint32_t wcnt[2][kDimcapWaves];
+    __shared__ uint32_t wcnt[2 * kDimcapWaves];
     const uint32_t q = blockIdx.x, tid = threadIdx.x, wave = tid / kWave, lane = tid & (kWave - 1);
     const uint32_t slots = a.slots, limit = a.limit;
     unsigned long long* keys;
@@ -137,19 +138,9 @@ __global__ __launch_bounds__(kDimcapChunk) void dimcap_kernel(DimcapArgs a) {
             __syncthreads();
         }
         // compact
-        const unsigned long long m = __ballot(keep);
-        const uint32_t before = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-        uint32_t* wc = wcnt[it & 1u];                                // (two sets: a wave one chunk ahead writes the other)
-        if (lane == 0) wc[wave] = (uint32_t)__popcll(m);
-        __syncthreads();
-        uint32_t below = 0, total = 0;
-#pragma unroll
-        for (uint32_t w = 0; w < kDimcapWaves; ++w) {
-            const uint32_t c = wc[w];
-            below += w < wave ? c : 0u;
-            total += c;
-        }
-        if (keep) cand_carry(a.in, a.out, q0 + pos, q0 + run + below + before, true);      // (run + below + before <= pos < cap)
+        uint32_t r, total;
+        chunk_rank<kDimcapWaves>(keep, wcnt, it, &r, &total);
+        if (keep) cand_carry(a.in, a.out, q0 + pos, q0 + run + r, true);                   // (run + r <= pos < cap)
         run += total;
     }
     cand_pad(a.in, a.out, q, run + tid, kDimcapChunk, kCandNan);      // padding behind the count

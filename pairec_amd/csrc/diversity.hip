@@ -7,8 +7,8 @@
 // is defined bit for bit in include/pairec_gpu.h; div_host_one below states it on the host, the kernel reproduces it.
 //
 // One workgroup per request, every decision taken by all lanes alike from what lies in LDS:
-//   compact  the entries that are not set aside, in order (wave ballots + per-wave counts, as trim.hip's walk); the set-aside
-//            ones behind them, reversed;
+//   compact  the entries that are not set aside, in order (block_rank.hpp's wave_rank + per-wave counts of both flags behind
+//            one barrier); the set-aside ones behind them, reversed;
 //   keys     per rule, an entry's value becomes the smallest position that holds an equal tuple: an open-addressed table in the
 //            request's slice of context scratch whose slots hold positions — two entries share a slot iff their TUPLES are equal,
 //            compared column by column; every access of a slot is an agent-scope atomic (fanin.hip's scratch tier);
@@ -18,10 +18,11 @@
 //            last window - 1 results (window), both kept current by one lane per rule after every pick; ballots + a scan of the
 //            waves' masks give the first eligible entry (which fixes the explore bound) and the first passing one; (largest w,
 //            first position) travels packed in one 64-bit maximum;
-//   output   the result, the untaken entries in order (ballot ranks again), the set-aside entries, UINT32_MAX behind count.
+//   output   the result, the untaken entries in order (block_rank.hpp's chunk_rank), the set-aside entries, UINT32_MAX behind count.
 // The window counts and the keys live in context scratch, written by one lane and read by the workgroup's others only across
 // a __syncthreads: one workgroup stays on one compute unit, whose vector cache serves them all.
 #include "cand_lists.hpp"
+#include "block_rank.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -132,7 +133,7 @@ __global__ __launch_bounds__(kDivThreads) void diversity_rules_kernel(DivArgs a)
     __shared__ uint8_t exb[kDivMaxN];            // bit e: exclusion rule e's terms hold for kept entry j
     __shared__ uint32_t taken[kDivMaxN / 32];
     __shared__ unsigned long long welig[2][kDivWaves], wpass[kDivWaves], wbest[kDivWaves];
-    __shared__ uint32_t wcnt[2][2][kDivWaves];
+    __shared__ uint32_t wcnt[2][2][kDivWaves];   // [flag][set][wave]: the compaction's two flags; the output's walk uses flag 0's sets
     __shared__ uint32_t tail_key[kDivMaxRules], tail_run[kDivMaxRules];
     __shared__ uint32_t exm_s;                   // the exclusion rules that name the position being filled
     const uint32_t q = blockIdx.x, tid = threadIdx.x, wave = tid / kWave, lane = tid & (kWave - 1);
@@ -154,15 +155,16 @@ __global__ __launch_bounds__(kDivThreads) void diversity_rules_kernel(DivArgs a)
                 sa = s < 32u && ((a.c.exclude_mask >> s) & 1u);
                 keep = !sa;
             }
-            const unsigned long long mk = __ballot(keep), ms = __ballot(sa);
+            uint32_t nk, ns;                     // (two flags, one barrier: chunk_rank's steps, the counts side by side)
+            const uint32_t rk = wave_rank(keep, &nk), rs = wave_rank(sa, &ns);
             if (lane == 0) {
-                wcnt[it & 1u][0][wave] = (uint32_t)__popcll(mk);
-                wcnt[it & 1u][1][wave] = (uint32_t)__popcll(ms);
+                wcnt[0][it & 1u][wave] = nk;
+                wcnt[1][it & 1u][wave] = ns;
             }
             __syncthreads();
             uint32_t bk = 0, bs = 0, tk = 0, ts = 0;
             for (uint32_t w = 0; w < kDivWaves; ++w) {
-                const uint32_t ck = wcnt[it & 1u][0][w], cs = wcnt[it & 1u][1][w];
+                const uint32_t ck = wcnt[0][it & 1u][w], cs = wcnt[1][it & 1u][w];
                 if (w < wave) {
                     bk += ck;
                     bs += cs;
@@ -170,9 +172,8 @@ __global__ __launch_bounds__(kDivThreads) void diversity_rules_kernel(DivArgs a)
                 tk += ck;
                 ts += cs;
             }
-            const unsigned long long below = (1ull << lane) - 1ull;
-            if (keep) cpos[m + bk + (uint32_t)__popcll(mk & below)] = (uint16_t)p;
-            if (sa) cpos[n - 1u - (n_sa + bs + (uint32_t)__popcll(ms & below))] = (uint16_t)p;
+            if (keep) cpos[m + bk + rk] = (uint16_t)p;
+            if (sa) cpos[n - 1u - (n_sa + bs + rs)] = (uint16_t)p;
             m += tk;
             n_sa += ts;
         }
@@ -346,16 +347,9 @@ __global__ __launch_bounds__(kDivThreads) void diversity_rules_kernel(DivArgs a)
     for (uint32_t c0 = 0; c0 < m; c0 += kDivChunk, ++it) {
         const uint32_t j = c0 + tid;
         const bool left = j < m && !((taken[j >> 5] >> (j & 31u)) & 1u);
-        const unsigned long long ml = __ballot(left);
-        if (lane == 0) wcnt[it & 1u][0][wave] = (uint32_t)__popcll(ml);
-        __syncthreads();
-        uint32_t off = 0, total = 0;
-        for (uint32_t w = 0; w < kDivWaves; ++w) {
-            const uint32_t cw = wcnt[it & 1u][0][w];
-            if (w < wave) off += cw;
-            total += cw;
-        }
-        if (left) order[base + off + (uint32_t)__popcll(ml & ((1ull << lane) - 1ull))] = cpos[j];
+        uint32_t r, total;
+        chunk_rank<kDivWaves>(left, wcnt[0][0], it, &r, &total);
+        if (left) order[base + r] = cpos[j];
         base += total;
     }
     for (uint32_t t = tid; t < n - m; t += kDivThreads) order[m + t] = cpos[n - 1u - t];

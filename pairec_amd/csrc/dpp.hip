@@ -14,6 +14,7 @@
 // gonum's Dgemm-by-axpy does on amd64, and is bit-identical to oracle/oracle.c given the same L.
 #include "pipeline.hpp"
 #include "bitonic_reg.hpp"
+#include "block_rank.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -608,9 +609,9 @@ __global__ __launch_bounds__(64) void dpp_greedy_wave_kernel(const double* __res
             for (int s = 0; s < EPL; ++s) {
                 const uint32_t n = (uint32_t)s * 64u + lane;
                 const bool cand = n < N && !sel[s];
-                const uint64_t m = __builtin_amdgcn_ballot_w64(cand);
-                const uint32_t before = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-                const uint32_t room = topn - ny, cnt = (uint32_t)__popcll(m);
+                uint32_t cnt;
+                const uint32_t before = wave_rank(cand, &cnt);
+                const uint32_t room = topn - ny;
                 if (cand && before < room) {
                     out[done + ny + before] = n;
                     sel[s] = true;

@@ -7,6 +7,7 @@
 // not in a list of n ids lie within the first k + n entries of that order.  One ordinary pass at depth k + max n (recall.hip)
 // holds every request's exact answer; this file's kernel cuts it out, order preserved, without a sort.
 #include "common.hpp"
+#include "block_rank.hpp"
 
 namespace pg {
 namespace {
@@ -23,7 +24,7 @@ __device__ inline uint32_t excl_slot(unsigned long long id) { return (uint32_t)(
 
 // Request q = blockIdx.x: out[q][j] = the j-th entry of in[q][0 .. k_in) that is neither padding (row UINT64_MAX) nor in the
 // request's list, j < k_out; the slots behind the kept entries are padding.  Chunks of kExclThreads entries in order: a
-// membership test per lane, the lane's place from the wave's ballot and the counts of the waves before it, and a running base.
+// membership test per lane, the lane's place from block_rank.hpp's chunk_rank, and a running base.
 // The walk ends with the chunk that fills k_out, so an empty list reads the head only (and builds no set).
 __global__ __launch_bounds__(kExclThreads) void exclude_compact_kernel(const uint64_t* __restrict__ rows, const float* __restrict__ scores,
                                                                       uint32_t k_in, const uint64_t* __restrict__ excl,
@@ -32,7 +33,7 @@ __global__ __launch_bounds__(kExclThreads) void exclude_compact_kernel(const uin
                                                                       uint32_t* __restrict__ out_count) {
     extern __shared__ __attribute__((aligned(16))) unsigned long long excl_set[];      // [kExclSetSlots], then wave counts [2][kExclWaves]
     uint32_t* wcnt = reinterpret_cast<uint32_t*>(excl_set + kExclSetSlots);
-    const uint32_t q = blockIdx.x, tid = threadIdx.x, wave = tid / kWave;
+    const uint32_t q = blockIdx.x, tid = threadIdx.x;
     const uint32_t e0 = excl_off[q];
     // (a longer list breaks the caller's precondition: its first kMaxExclude ids count — the set keeps empty slots, every probe ends)
     const uint32_t n = min(excl_off[q + 1] - e0, kMaxExclude);
@@ -72,18 +73,9 @@ __global__ __launch_bounds__(kExclThreads) void exclude_compact_kernel(const uin
                 if (cur == id || cur == kExclEmpty) break;
             }
         }
-        const unsigned long long m = __ballot(keep);
-        const uint32_t before = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-        uint32_t* wc = wcnt + (it & 1u) * kExclWaves;        // (two sets of counts: a wave ahead by one chunk writes the other one)
-        if ((tid & (kWave - 1)) == 0) wc[wave] = (uint32_t)__popcll(m);
-        __syncthreads();
-        uint32_t off = base, total = 0;
-        for (uint32_t w = 0; w < kExclWaves; ++w) {
-            const uint32_t cw = wc[w];
-            if (w < wave) off += cw;
-            total += cw;
-        }
-        const uint32_t dst = off + before;
+        uint32_t r, total;
+        chunk_rank<kExclWaves>(keep, wcnt, it, &r, &total);
+        const uint32_t dst = base + r;
         if (keep && dst < k_out) {
             out_rows[dst] = id;
             out_bits[dst] = bits;

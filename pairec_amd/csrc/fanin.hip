@@ -10,7 +10,7 @@
 // Order-preserving dedup needs more than membership, and nothing here depends on which lane gets anywhere first:
 //   insert   every entry claims its id's slot and takes atomicMin(slot value, its position in the concatenation);
 //   walk     an entry is a first occurrence iff the slot holds its own position; chunks of kFaninChunk positions in order, first
-//            occurrences compacted by wave ballot + mbcnt and a running base (exclude.hip's walk) — each leaves its OUTPUT SLOT
+//            occurrences compacted by block_rank.hpp's chunk_rank and a running base — each leaves its OUTPUT SLOT
 //            in the table;
 //   planes   per source, every entry takes atomicMax(slot value, (source + 1, index in the source, output slot)) — later sources
 //            outrank earlier ones, so nothing is reset — and the entry that finds its own value back is its source's LAST
@@ -20,6 +20,7 @@
 // table in LDS, keyed on the 32-bit distance to the request's smallest id (8 B per slot: 16384 slots = 128 KiB); everything
 // else uses the request's slice of context scratch with full 64-bit keys.  Either way two ids that differ anywhere are two ids.
 #include "cand_lists.hpp"
+#include "block_rank.hpp"
 
 #include <type_traits>
 
@@ -120,7 +121,7 @@ __device__ void fanin_run(const FaninArgs& a, const FaninDesc& d, uint32_t q, ty
     typedef typename std::conditional<kLds, uint32_t, unsigned long long>::type Key;
     typedef typename std::conditional<kLds, uint8_t, uint32_t>::type Mask;
     constexpr Key kEmpty = (Key)~(Key)0;         // never a key: the LDS tier's distances are < 2^32 - 1, padding is never inserted
-    const uint32_t tid = threadIdx.x, wave = tid / kWave;
+    const uint32_t tid = threadIdx.x;
     const uint32_t bits = a.slot_bits, slots = 1u << bits, smask = slots - 1u, cap = a.cap, n_src = a.n_src;
     const bool want_planes = a.out_planes || a.out_mask;
     for (uint32_t i = tid; i < slots; i += kFaninThreads) {
@@ -168,19 +169,10 @@ __device__ void fanin_run(const FaninArgs& a, const FaninDesc& d, uint32_t q, ty
                 first = tab_load<kLds>(&val[h]) == p;
             }
         }
-        const unsigned long long m = __ballot(first);
-        const uint32_t before = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-        uint32_t* wc = wcnt + (it & 1u) * kFaninWaves;       // (two sets of counts: a wave ahead by one chunk writes the other one)
-        if ((tid & (kWave - 1)) == 0) wc[wave] = (uint32_t)__popcll(m);
-        __syncthreads();
-        uint32_t off = base, total = 0;
-        for (uint32_t w = 0; w < kFaninWaves; ++w) {
-            const uint32_t cw = wc[w];
-            if (w < wave) off += cw;
-            total += cw;
-        }
+        uint32_t r, total;
+        chunk_rank<kFaninWaves>(first, wcnt, it, &r, &total);
         if (first) {
-            const uint32_t dst = off + before;               // (< cap: at most one first occurrence per position)
+            const uint32_t dst = base + r;                   // (< cap: at most one first occurrence per position)
             const size_t at = (size_t)q * d.k[s] + j;
             out_rows[dst] = id;
             out_score[dst] = (a.f64_mask >> s) & 1u ? reinterpret_cast<const unsigned long long*>(d.scores[s])[at]

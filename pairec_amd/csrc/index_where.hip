@@ -1,6 +1,7 @@
 // index_where.hip — the lists of an exact IVF index restricted to the rows a filter admits: built on the
 // device, kept per index in a small LRU cache whose policy is index_serve.hpp's.  The search over them is index.hip's.
 #include "index_shared.hpp"
+#include "block_rank.hpp"
 
 #include <hipcub/hipcub.hpp>
 
@@ -33,11 +34,14 @@ __global__ __launch_bounds__(256) void where_lists_kernel(const uint32_t* __rest
         const uint32_t p = p0 + threadIdx.x;
         const uint32_t row = p < e ? perm[p] : 0u;
         const bool pass = p < e && ((bits[row >> 5] >> (row & 31)) & 1u);
-        const uint64_t m = __builtin_amdgcn_ballot_w64(pass);
-        if (lane == 0) wsum[w] = (uint32_t)__popcll(m);
+        // (block_rank.hpp's wave_rank only: one set of counts and a barrier behind the reads — chunk_rank's two sets would
+        // double this kernel's LDS words)
+        uint32_t n_w;
+        const uint32_t before = wave_rank(pass, &n_w);
+        if (lane == 0) wsum[w] = n_w;
         __syncthreads();
         if (!COUNT && pass) {
-            uint32_t pos = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+            uint32_t pos = base + before;
             for (int j = 0; j < w; ++j) pos += wsum[j];
             perm_f[pos] = row;
         }

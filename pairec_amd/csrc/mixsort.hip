@@ -12,8 +12,8 @@
 //   mix_match_kernel   one lane per list entry: its element (through d_order), its row, every referenced column's raw value (all
 //                      loads issued before the first use, cond_eval.hpp), then per strategy the source-mask test ORed with the
 //                      strategy's FilterParam rule → one byte, bit s = member of strategy s.  256 lanes, grid (cap / 256, nq).
-//   mix_sort_kernel    one workgroup of 1 024 lanes per request.  Strategies in turn walk the list 1 024 entries at a time: ballot
-//                      + mbcnt in a wave, per-wave counts in LDS (two sets, one barrier per chunk) and the running count give a
+//   mix_sort_kernel    one workgroup of 1 024 lanes per request.  Strategies in turn walk the list 1 024 entries at a time:
+//                      block_rank.hpp's chunk_rank (one barrier per chunk; all walks share one counter) and the running count give a
 //                      member its rank; a 2 KB LDS bitmap records taken entries; the walk ends in the chunk where the rank reaches
 //                      number_s.  The taken lists (and, for a position column, the entries' column values) go to global scratch.
 //                      Wave 0 then places FIX and RANDOM entries into the page in LDS: it reads lists and positions 64 at a time
@@ -24,6 +24,7 @@
 //                      tail is one more ranked walk.  Nothing depends on which lane came first.
 #include "pipeline.hpp"
 #include "cond_eval.hpp"
+#include "block_rank.hpp"
 
 #include <algorithm>
 #include <cstdarg>
@@ -106,26 +107,6 @@ __global__ __launch_bounds__(kMixMatchThreads) void mix_match_kernel(CondProgram
 __device__ __forceinline__ bool mix_bit(const uint32_t* bm, uint32_t j) { return ((bm[j >> 5] >> (j & 31u)) & 1u) != 0; }
 __device__ __forceinline__ void mix_set(uint32_t* bm, uint32_t j) { atomicOr(&bm[j >> 5], 1u << (j & 31u)); }
 
-// the rank of a lane's flag among the flags of the workgroup's chunk, and their number; one barrier; `it` picks the set of counts
-__device__ __forceinline__ void mix_rank(bool flag, uint32_t (*wcnt)[kMixWaves], uint32_t* it, uint32_t wave, uint32_t lane, uint32_t* rank,
-                                         uint32_t* total) {
-    const unsigned long long m = __ballot(flag);
-    const uint32_t before = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-    uint32_t* wc = wcnt[*it & 1u];
-    ++*it;
-    if (lane == 0) wc[wave] = (uint32_t)__popcll(m);
-    __syncthreads();
-    uint32_t below = 0, all = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < kMixWaves; ++w) {
-        const uint32_t c = wc[w];
-        below += w < wave ? c : 0u;
-        all += c;
-    }
-    *rank = below + before;
-    *total = all;
-}
-
 // wave 0: the first empty slot from `end` on, cyclically; free = the lane's empty slots; at least one slot of the page is empty
 __device__ __forceinline__ uint32_t mix_first_empty(unsigned long long free, uint32_t end, uint32_t lane) {
     const uint32_t el = end >> 6;
@@ -146,7 +127,7 @@ __global__ __launch_bounds__(kMixChunk) void mix_sort_kernel(MixArgs a) {
     __shared__ uint32_t s_res[kMixMaxSize];                          // the page: list entries, kMixEmpty for an empty slot
     __shared__ uint32_t s_empty[kMixMaxSize];                        // the empty slots after FIX and RANDOM, ascending
     __shared__ uint32_t s_taken[kCandMaxCap / 32], s_inres[kCandMaxCap / 32];
-    __shared__ uint32_t s_wcnt[2][kMixWaves];
+    __shared__ uint32_t s_wcnt[2 * kMixWaves];
     __shared__ uint32_t s_cnt[kMixMaxStrategies];                    // |taken_s|
     const uint32_t q = blockIdx.x, tid = threadIdx.x, wave = tid / kWave, lane = tid & (kWave - 1);
     const size_t q0 = (size_t)q * a.cap;
@@ -174,7 +155,7 @@ __global__ __launch_bounds__(kMixChunk) void mix_sort_kernel(MixArgs a) {
             const uint32_t j = c0 + tid;
             const bool mem = j < n && ((mask[j] >> s) & 1u) != 0 && !mix_bit(s_taken, j);
             uint32_t r, total;
-            mix_rank(mem, s_wcnt, &it, wave, lane, &r, &total);
+            chunk_rank<kMixWaves>(mem, s_wcnt, it++, &r, &total);
             r += run;
             if (mem && r < st.number) {
                 mix_set(s_taken, j);
@@ -265,7 +246,7 @@ __global__ __launch_bounds__(kMixChunk) void mix_sort_kernel(MixArgs a) {
         const bool empty = slot < S && e == kMixEmpty;
         if (slot < S && !empty) mix_set(s_inres, e);
         uint32_t r, total;
-        mix_rank(empty, s_wcnt, &it, wave, lane, &r, &total);
+        chunk_rank<kMixWaves>(empty, s_wcnt, it++, &r, &total);
         if (empty) s_empty[n_e + r] = slot;
         n_e += total;
     }
@@ -277,7 +258,7 @@ __global__ __launch_bounds__(kMixChunk) void mix_sort_kernel(MixArgs a) {
         const uint32_t j = c0 + tid;
         const bool free = j < n && !mix_bit(s_taken, j);
         uint32_t r, total;
-        mix_rank(free, s_wcnt, &it, wave, lane, &r, &total);
+        chunk_rank<kMixWaves>(free, s_wcnt, it++, &r, &total);
         r += d_run;
         if (free && r < n_e) {
             s_res[s_empty[r]] = j;
@@ -295,7 +276,7 @@ __global__ __launch_bounds__(kMixChunk) void mix_sort_kernel(MixArgs a) {
         const uint32_t j = c0 + tid;
         const bool left = j < n && !mix_bit(s_inres, j);
         uint32_t r, total;
-        mix_rank(left, s_wcnt, &it, wave, lane, &r, &total);
+        chunk_rank<kMixWaves>(left, s_wcnt, it++, &r, &total);
         r += r_run;
         if (left && r < need) {
             s_res[s_empty[d_run + r]] = j;
@@ -316,7 +297,7 @@ __global__ __launch_bounds__(kMixChunk) void mix_sort_kernel(MixArgs a) {
             const uint32_t j = c0 + tid;
             const bool left = j < n && !mix_bit(s_inres, j);
             uint32_t r, total;
-            mix_rank(left, s_wcnt, &it, wave, lane, &r, &total);
+            chunk_rank<kMixWaves>(left, s_wcnt, it++, &r, &total);
             if (left && cnt_out + r < a.cap) out[cnt_out + r] = ord ? ord[j] : j;      // (cnt_out + r < n <= cap)
             cnt_out += total;
         }

@@ -5,6 +5,7 @@
 // pg_table_view_create).  The filter inside the table pass itself is recall.hip's; compound clauses are where.hip's.
 #include "common.hpp"
 #include "recall_shared.hpp"
+#include "block_rank.hpp"
 
 namespace pg {
 
@@ -61,31 +62,12 @@ __global__ __launch_bounds__(256) void filter_block_count_kernel(RowFilter f, ui
 // The block counts' exclusive scan in two parallel levels: every group of 1024 counts is scanned in place by a workgroup of its
 // own (its total → group_n[g]); one small workgroup then scans the <= 4096 group totals (grand total → group_n[ngroups]).  A
 // block's offset is block_n[b] + group_n[b / 1024].
-__device__ __forceinline__ uint32_t wg1024_exclusive_scan(uint32_t v, uint32_t* wsum, uint32_t* total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    uint32_t incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t up = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += up;
-    }
-    if (lane == 63) wsum[w] = incl;
-    __syncthreads();
-    uint32_t excl = incl - v, all = 0;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-        if (j < w) excl += wsum[j];
-        all += wsum[j];
-    }
-    *total = all;
-    return excl;
-}
 __global__ __launch_bounds__(1024) void filter_group_scan_kernel(uint32_t* __restrict__ block_n, uint32_t n, uint32_t* __restrict__ group_n) {
     __shared__ uint32_t wsum[16];
     const uint32_t i = blockIdx.x * 1024 + threadIdx.x;
     const uint32_t v = i < n ? block_n[i] : 0u;
     uint32_t total;
-    const uint32_t excl = wg1024_exclusive_scan(v, wsum, &total);
+    const uint32_t excl = block_excl_scan<16>(v, wsum, &total);
     if (i < n) block_n[i] = excl;
     if (threadIdx.x == 0) group_n[blockIdx.x] = total;
 }
@@ -99,7 +81,7 @@ __global__ __launch_bounds__(1024) void filter_total_scan_kernel(uint32_t* __res
         s += v[j];
     }
     uint32_t total;
-    uint32_t acc = wg1024_exclusive_scan(s, wsum, &total);
+    uint32_t acc = block_excl_scan<16>(s, wsum, &total);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const uint32_t i = threadIdx.x * 4 + j;
@@ -112,20 +94,10 @@ __global__ __launch_bounds__(1024) void filter_total_scan_kernel(uint32_t* __res
 __global__ __launch_bounds__(256) void filter_scatter_kernel(RowFilter f, uint64_t rows, const uint32_t* __restrict__ block_off,
                                                              const uint32_t* __restrict__ group_off, uint32_t* __restrict__ ids) {
     __shared__ uint32_t wn[4];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const uint64_t r0 = (uint64_t)blockIdx.x * kCompactBlockRows + threadIdx.x * 4;
     const uint32_t m = r0 < rows ? row_filter_mask4(f, r0, rows) : 0u;
-    const uint32_t c = (uint32_t)__popc(m);
-    uint32_t incl = c;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t up = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += up;
-    }
-    if (lane == 63) wn[w] = incl;
-    __syncthreads();
-    uint32_t pos = block_off[blockIdx.x] + group_off[blockIdx.x >> 10] + incl - c;
-    for (int j = 0; j < w; ++j) pos += wn[j];
+    uint32_t total;
+    uint32_t pos = block_off[blockIdx.x] + group_off[blockIdx.x >> 10] + block_excl_scan<4>((uint32_t)__popc(m), wn, &total);
 #pragma unroll
     for (uint32_t i = 0; i < 4; ++i)
         if (m & (1u << i)) ids[pos++] = (uint32_t)(r0 + i);

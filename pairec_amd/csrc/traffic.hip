@@ -7,7 +7,7 @@
 //   traffic_control_kernel  one workgroup of 1 024 lanes per request.  It resolves the request's alphas first: with every one 0 the
 //                           passes below only compact the list and write the identity.  Pass 1 walks the list 1 024 entries at a time: a lane takes
 //                           entry j, its element (through d_order) and, when that is an element of the arrays, its rank among the
-//                           chunk's such entries (ballot + mbcnt in a wave, per-wave counts in LDS) — its list index i — then
+//                           chunk's such entries (block_rank.hpp's chunk_rank) — its list index i — then
 //                           s_i and w_i = s_i * posWeight_i; w_i and the member byte go to LDS at the rank, the element to the
 //                           compacted list in scratch, its bit into the "is an entry" bitmap.  Lanes 0 .. T of wave 0 then each
 //                           run ONE sequential chain over the chunk's staged values: lane 0 `total`, lane 1 + t `sum_t` and its
@@ -21,6 +21,7 @@
 //                           NaN sorts last, which is step 8; the padding keys sit behind every entry's key, NaN or not.
 //   traffic_compose_kernel  sorted list index → element through the compacted list; UINT32_MAX behind the count; the counts.
 #include "pipeline.hpp"
+#include "block_rank.hpp"
 #include "cond_eval.hpp"      // SetTable
 #include "traffic_host.hpp"
 
@@ -61,7 +62,7 @@ __global__ __launch_bounds__(kTrafficChunk) void traffic_control_kernel(TrafficA
     __shared__ __attribute__((aligned(16))) double s_w[kTrafficChunk];   // the chunk's w_i, by rank
     __shared__ __attribute__((aligned(16))) uint8_t s_m[kTrafficChunk];  // ... and member bytes
     __shared__ uint32_t s_isentry[kCandMaxCap / 32];                   // bit e: element e is an entry of the list
-    __shared__ uint32_t s_wcnt[2][kTrafficWaves];
+    __shared__ uint32_t s_wcnt[2 * kTrafficWaves];
     __shared__ double s_max;                                           // maxScore = s_0
     __shared__ TrafficTarget s_tg[kTrafficMaxTargets];
     const uint32_t q = blockIdx.x, tid = threadIdx.x, wave = tid / kWave, lane = tid & (kWave - 1);
@@ -88,25 +89,14 @@ __global__ __launch_bounds__(kTrafficChunk) void traffic_control_kernel(TrafficA
         const uint32_t j = c0 + tid;
         const uint32_t elem = j < n ? (ord ? ord[j] : j) : a.cap;
         const bool valid = elem < a.cap;                               // (an order value outside the arrays leaves the list)
-        const unsigned long long m = __ballot(valid);
-        const uint32_t before = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-        uint32_t* wc = s_wcnt[it & 1u];
-        ++it;
-        if (lane == 0) wc[wave] = (uint32_t)__popcll(m);
-        __syncthreads();                                               // also: the chains are done with the previous chunk's s_w / s_m
-        uint32_t below = 0, cnt = 0;
-#pragma unroll
-        for (uint32_t w = 0; w < kTrafficWaves; ++w) {
-            const uint32_t c = wc[w];
-            below += w < wave ? c : 0u;
-            cnt += c;
-        }
+        uint32_t r, cnt;                                               // (r < cnt <= 1 024 where valid)
+        chunk_rank<kTrafficWaves>(valid, s_wcnt, it++, &r, &cnt);      // its barrier also: the chains are done with the previous chunk's s_w / s_m
         if (live && tid >= cnt && tid < ((cnt + 7u) & ~7u)) {          // the chains read whole groups of eight slots
             s_w[tid] = -0.0;
             s_m[tid] = 0;
         }
         if (valid) {
-            const uint32_t r = below + before, i = run + r;            // r < cnt <= 1 024, i < n <= cap
+            const uint32_t i = run + r;                                // i < n <= cap
             elems[i] = elem;
             atomicOr(&s_isentry[elem >> 5], 1u << (elem & 31u));
             if (live) {

@@ -10,10 +10,12 @@
 //   count   real entries per class (order does not matter: wave ballots added up in LDS);
 //   plan    one lane turns the rules and the counts into each class's take and output base;
 //   walk    the sorted order in chunks of kTrimChunk positions: an entry's rank within its class = the class's running count +
-//           the entries of its class in the waves before it (per-wave class counts in LDS) + those in the lanes before it
-//           (ballot + mbcnt), as exclude.hip's walk; a rank below the class's take is written at base[class] + rank;
+//           the entries of its class in the waves before it (per-wave class counts in LDS, two sets as block_rank.hpp's
+//           chunk_rank keeps them) + those in the lanes before it (its ballot_rank); a rank below the class's take is written
+//           at base[class] + rank;
 //   pad     the slots behind the takes.
 #include "pipeline.hpp"
+#include "block_rank.hpp"
 
 #include <algorithm>
 
@@ -111,7 +113,7 @@ __global__ __launch_bounds__(kTrimThreads) void candidates_trim_kernel(TrimArgs 
         uint32_t before = 0;
         for (uint32_t r = 0; r < n_rules; ++r) {
             const unsigned long long m = __ballot(c == r);
-            if (c == r) before = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+            if (c == r) before = ballot_rank(m);
             if (lane == 0) wc[r][wave] = (uint32_t)__popcll(m);
         }
         __syncthreads();

@@ -12,13 +12,14 @@
 //   cut     one workgroup per request, rules one after another (a rule's limit and the taken entries need the rules before):
 //           inside a rule the rule's order kTrim2Chunk positions at a time; a lane is eligible iff its position is a member
 //           (recomputed from source / mask: the sort cannot tell a non-member from a member with a NaN key) and its bit in the
-//           LDS bitmap of input positions is clear; its rank = the rule's picks so far + the eligibles of the waves before
-//           (per-wave counts in LDS) + those of the lanes before (ballot + mbcnt); rank < limit: written at base + rank, bit set.
+//           LDS bitmap of input positions is clear; its rank = the rule's picks so far + its rank among the chunk's eligibles
+//           (block_rank.hpp's chunk_rank); rank < limit: written at base + rank, bit set.
 //           A rule's walk ends with the chunk in which its picks reach the limit, or with the order — never at a chunk without an
 //           eligible entry: an earlier rule may have taken the first kTrim2Chunk members of this one's list;
 //   pad     the slots behind the picks.
 // pg_candidates_trim2_host states the same answer on host arrays with plain containers; the tests hold the device to it.
 #include "pipeline.hpp"
+#include "block_rank.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -79,8 +80,8 @@ __global__ __launch_bounds__(256) void trim2_keys_kernel(Trim2Args a, unsigned l
 // cut: request q = blockIdx.x.
 __global__ __launch_bounds__(kTrim2Chunk) void candidates_trim2_kernel(Trim2Args a) {
     __shared__ uint32_t taken[kCandMaxCap / 32];                     // one bit per input position: an earlier pick
-    __shared__ uint32_t wcnt[2][kTrim2Waves];                        // a chunk's eligible entries per wave
-    const uint32_t q = blockIdx.x, tid = threadIdx.x, wave = tid / kWave, lane = tid & (kWave - 1);
+    __shared__ uint32_t wcnt[2 * kTrim2Waves];                       // a chunk's eligible entries per wave
+    const uint32_t q = blockIdx.x, tid = threadIdx.x;
     const uint32_t cap = a.in.cap, out_cap = a.out.out_cap, n_rules = a.n_rules;
     const size_t in0 = (size_t)q * cap, out0 = (size_t)q * out_cap;
     const uint32_t n_valid = cand_n_valid(a.in, q);
@@ -102,19 +103,9 @@ __global__ __launch_bounds__(kTrim2Chunk) void candidates_trim2_kernel(Trim2Args
                 if (pos < cap)
                     elig = trim2_member(a.in, in0 + pos, pos, n_valid, sc, &plane) && !((taken[pos >> 5] >> (pos & 31u)) & 1u);
             }
-            uint32_t* wc = wcnt[it & 1u];                            // (two sets of counts: a wave ahead by one chunk writes the other one)
-            const unsigned long long m = __ballot(elig);
-            const uint32_t before = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-            if (lane == 0) wc[wave] = (uint32_t)__popcll(m);
-            __syncthreads();
-            uint32_t below = 0, total = 0;
-#pragma unroll
-            for (uint32_t w = 0; w < kTrim2Waves; ++w) {
-                const uint32_t n = wc[w];
-                below += w < wave ? n : 0u;
-                total += n;
-            }
-            const uint32_t rank = picks + below + before;
+            uint32_t r, total;
+            chunk_rank<kTrim2Waves>(elig, wcnt, it, &r, &total);
+            const uint32_t rank = picks + r;
             if (elig && rank < limit) {
                 const uint32_t dst = base + rank;
                 if (dst < out_cap) {                                 // (always: pg_trim2_out_cap's bound)
