@@ -60,8 +60,8 @@ struct Scratch {
 enum ScratchSlot : int {
     kSlotRows = 0,           // table.hip: the row ids of a gather from host rows; rank_mlp.hip: fm2t rows' gathered field ids (separate entry points, neither calls the other)
     kSlotHostStage = 1,      // table.hip: the gathered rows on their way to the host; features.hip: column descriptors and pointers of a gather (separate entry points)
-    kSlotRecallSmall = 2,    // recall.hip recall_scratch: padded queries, thresholds, counts, screen fragments, status words
-    kSlotRecallCand = 3,     // recall.hip recall_scratch: the candidate and suspect lists
+    kSlotRecallSmall = 2,    // recall_plan.hip recall_scratch: padded queries, thresholds, counts, screen fragments, status words
+    kSlotRecallCand = 3,     // recall_plan.hip recall_scratch: the candidate and suspect lists
     kSlotStatus = 4,         // 4096 bytes of status words (expr, misc, recall, recall_i4, recall_r2): each user writes, copies out and synchronises inside one step of its call
     kSlotStaging = 5,        // staging of every host-buffer entry point (rank, recall, sort, dpp, ssd, expr, cf, index, diversity): one per call under ctx->mu, synchronised before it returns
     kSlotRankTiles = 6,      // rank_mlp.hip: tile table + request partials
@@ -69,7 +69,7 @@ enum ScratchSlot : int {
     kSlotPipe = 8,           // pipeline.hip post_scratch: the recommend pipeline's intermediates
     kSlotGroup = 9,          // group.hip pg_owned_compact_dev: the per-request counts of owned rows
     kSlotRerank = 10,        // pipeline.hip: the re-rank stage's DPP candidates
-    kSlotHitRecords = 11,    // recall.hip: the screened pass's record regions
+    kSlotHitRecords = 11,    // recall_plan.hip: the screened pass's record regions
     kSlotFilterCount = 12,   // recall_filter.hip filter_count_locked: per-block and per-group counts of the rows a filter admits
     kSlotFilterGather = 13,  // recall_filter.hip: the admitted rows' ids, compacted table and norms of a filtered recall
     kSlotRankHeads = 14,     // rank_mlp.hip: head partials of the weights-stationary multi-head kernel
@@ -297,7 +297,7 @@ struct TableWrite {
     }
 };
 
-// ---- recall.hip: a recall whose plans are enqueued without host synchronisation and verified later --------
+// ---- recall_plan.hip: a recall whose plans are enqueued without host synchronisation and verified later --------
 struct RecallScratch {
     float* qpad;
     float* thr;
@@ -408,7 +408,7 @@ struct RecallJob {
     const pg_index* ix = nullptr;
     std::shared_ptr<IndexServe> ix_serve;
 };
-constexpr int kIndexPlan = 100;             // the plan id of an attached index's plan (recall.hip's own plans are 0 .. 3)
+constexpr int kIndexPlan = 100;             // the plan id of an attached index's plan (recall_plan.hip's own plans are 0 .. 3)
 constexpr size_t kMaxPatchQueries = 8;
 // All four: caller holds ctx->mu.  prepare may synchronise once (a table's statistics / shadow on first use).
 int recall_job_prepare(RecallJob* j);
@@ -519,10 +519,11 @@ inline TableLearned table_learned(const pg_table* t) {
     return t->learned;
 }
 // recall.hip's exact re-scoring (rescore_kernel) over per-query suspect lists susp[q * scap + i] of local rows, appending the keys of
-// rows whose score reaches thr[q] to cand[q * cap + ...]; the squared-Euclidean |q|^2 chain and the final sign flip (index_search.hip)
+// rows whose score reaches thr[q] to cand[q * cap + ...]; the squared-Euclidean |q|^2 chain and the final sign flip — for the plans
+// (recall_plan.hip) and index_search.hip.  blocks = 0: the table pass's own grid; rows that fail `filter` are no candidates
 int rescore_launch(pg_ctx* ctx, uint32_t dim, bool l2, const float* tab, const float* d_queries, const float* thr, const uint32_t* susp,
                    const uint32_t* susp_cnt, uint32_t scap, uint32_t* cnt, uint64_t* cand, uint32_t* overflow, uint32_t cap, uint32_t nq,
-                   uint32_t n_rows, const float* nx, const float* nqv, uint32_t blocks);
+                   uint32_t n_rows, const float* nx, const float* nqv, uint32_t blocks, const RowFilter& filter = RowFilter());
 int query_norm2_launch(pg_ctx* ctx, const float* d_queries, uint32_t nq, uint32_t dim, float* d_out);
 int negate_launch(pg_ctx* ctx, float* d_v, uint64_t n);
 // recall_i4.hip (caller holds ctx->mu)

@@ -10,8 +10,9 @@
 // step), so a request's scores do not depend on how many other requests share the table pass.
 // Order: score descending (IEEE totalOrder, NaN last), then row ascending, via a 64-bit key.
 //
-// This file: the table pass — its kernels, their launchers (dispatch_scan, dispatch_screen) and the plans that chain them
-// (recall_job_prepare / enqueue / check / finish).  Its siblings, sharing recall_shared.hpp:
+// This file: the table pass — its kernels and their launchers (dispatch_scan, screen_launch, rescore_launch, ...), which own the
+// choice of an instantiation and its grid.  Its siblings, sharing recall_shared.hpp:
+//   recall_plan.hip    the plans that chain the launches (recall_job_prepare / enqueue / check / finish); their arithmetic: recall_plan_math.hpp
 //   recall_select.hip  select_kernel, the final_* kernels, launch_select, final_launch, the top-k merge of per-shard lists
 //   recall_table.hip   what is derived from a table, lazily: shadows, statistics, row norms, the threshold model
 //   recall_filter.hip  row filters, the compaction of the admitted rows, filtered recalls and views
@@ -38,7 +39,7 @@ namespace pg {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// (kPieceRows = 32: recall_shared.hpp)
+// (kPieceRows = 32: recall_plan_math.hpp)
 constexpr int kPieceCols = 32;                             // one 128-B line per row
 constexpr int kPieceBytes = kPieceRows * kPieceCols * 4;   // 4 KiB
 constexpr int kPieceDmas = kPieceBytes / 1024;             // LDS-DMA instructions per piece
@@ -51,29 +52,6 @@ constexpr int kStageCap = 280;                             // staged hits per wa
 constexpr int kStageBytes = kStageCap * 12 + 512;          // keys + query ids + 64 counters + 64 bases
 constexpr int kScanLds = kScanLdsRing + kScanWaves * kStageBytes;
 
-struct ScanArgs {
-    const float* tab;        // [rows][DIM]
-    const float* qpad;       // [32][DIM] queries, zero-padded
-    const float* thr;        // [32] running thresholds
-    uint32_t* cnt;           // [32] candidate counts
-    uint64_t* cand;          // [32][cap] candidate keys
-    uint32_t* overflow;      // set to 1 if any list overflowed
-    uint32_t cap;
-    uint32_t nq;
-    uint32_t nq_launch;      // queries of the call (selects the 32- or 64-query kernel)
-    uint32_t rb_begin;       // first 32-row block of this launch
-    uint32_t rb_end;         // one past the last block
-    uint32_t row_end;        // rows >= row_end are ignored (table end)
-    uint32_t stride;         // 1 = every block; S > 1 = pilot sample: logical block L reads table
-                             // block sample_block(L, ...)
-    uint32_t perm_mul, perm_mod;   // pilot sample order: slot = L * perm_mul mod perm_mod
-    uint32_t group_q;        // > 0: blockIdx.y selects a group of group_q queries (of nq in all) — one launch serves
-                             // every group of a screened recall's exact seed scan instead of one launch per group
-    // squared-Euclidean recall (scan_kernel<…, L2 = true>): a row·query pair is ranked by -d = fmaf(2, ip, -(|x|^2 + |q|^2))
-    const float* nx;         // [rows + 64] |x|^2 of every row (k-ascending fmaf chain; TableDerived::d_nx)
-    const float* nqv;        // [nq] |q|^2 of every query
-    RowFilter filter;        // rows that fail it are no candidates (col = nullptr: none)
-};
 
 // Pilot sample: logical block L of a stride-S launch is table block slot*S + jitter(slot), where
 // slot = L*mul mod n_slots is a fixed permutation of the n_slots sample slots (mul coprime with
@@ -389,35 +367,10 @@ __global__ __launch_bounds__(64 * kScanWaves, 2) void scan_kernel(ScanArgs a) {
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x8 __attribute__((ext_vector_type(8)));
 
-constexpr int kScreenMaxNQB = 8;                // 8 x 32 = 256 queries per pass at most
 constexpr int kScreenLds = 163840;              // the whole LDS of a CU: ring (128 KiB) + staging (32 KiB)
 
-struct ScreenArgs {
-    const void* tab16;        // shadow of the table: bf16 (TableDerived::d16) or int8 (TableDerived::d8)
-    const uint4* qb16;        // [NQB][KS][64] B fragments: 8 bf16 (KS = DIM/16) or 16 int8 (KS = DIM/32) per lane
-    const float* thr_screen;  // [256] bf16: thr - eps, rounded down; int8: the same in integer dot units (int32 bits)
-    uint32_t* susp_cnt;       // [256] suspects per query of this launch
-    uint32_t* susp;           // [256][cap] suspect rows (passed the screen; re-scored by rescore_kernel)
-    uint32_t* overflow;
-    uint32_t cap, nq, rb_begin, rb_end, row_end, stride, perm_mul, perm_mod;
-    // bf16 only: the bound is relative to the row's norm — eps = eps_unit[q] x (largest row norm of the 32-row block)
-    const float* blk_norm2;   // [blocks] largest row norm^2 per physical 32-row block (TableDerived::dnorm2)
-    const float* eps_unit;    // [256] 0.008 ||q|| (inflated); thr_screen then carries thr itself (or -inf)
-    // query halves (int8, > 128 queries): hit records instead of staged (row, query) pairs — see kRecBytes
-    char* rec;                // [waves][rec_cap] records of kRecBytes: one region per wave of the launch
-    uint32_t* rec_cnt;        // [waves] records in each region (zeroed per launch); [waves]: records in the spill pool
-    uint32_t rec_cap;
-    char* rec_pool;           // [rec_pool_cap] records: where a wave whose region is full puts its staged records
-    uint32_t rec_pool_cap, rec_waves;
-    uint32_t early_share;     // 8-wave variants: share (x 1024) of a SIMD's blocks that goes to its older wave; 512 = even
-    // squared-Euclidean recall on the int8 screen (L2 = true, <= 128 queries): a pair is a suspect iff
-    // I >= floor(A_q + B_q * min|x|^2 of the block) - 2, with thr_screen = A_q (float) and l2_b = B_q (screen_thr8_l2_kernel)
-    const float* blk_nxmin;   // [blocks] smallest |x|^2 of every physical 32-row block (TableDerived::d_nxmin)
-    const float* l2_b;        // [256]
-    const float* nx_rows;     // L2 = 2 (per-row test: g = 2 s_x s_q I - |x|^2 >= C'_q, thr_screen = C'_q, l2_b = 2 s_x s_q): |x|^2 of every row
-};
-
-// Hit records (query halves).  A 32-row x 16-query tile with a suspect in it has, as a rule, exactly one: one lane, one of
+// (ScanArgs, ScreenArgs: recall_shared.hpp)
+// Hit records (query halves; kRecBytes = 48, recall_plan_math.hpp).  A 32-row x 16-query tile with a suspect in it has, as a rule, exactly one: one lane, one of
 // its 8 accumulators (two row halves x 4 registers of v_mfma_i32_16x16x64_i8).  Finding the register inside the scan kernel —
 // compare / add-with-carry pairs and a staging loop, issued for the whole wave on behalf of that one lane — cost about as
 // many VALU slots as the reject test itself.  Instead the lane parks its 8 accumulators as they are (32 B) with a tag (first
@@ -429,8 +382,6 @@ struct ScreenArgs {
 // 64 lanes busy — and fills the per-query suspect lists that rescore_kernel reads.  (Stores straight from the hit path,
 // without the LDS stage, were measured: 4.35 vs 3.1 ms per pass — with stores in flight in every second block the
 // counted waits over-wait all the time and the ring runs one piece deep.)
-constexpr uint32_t kRecBytes = 48;
-constexpr uint32_t kRecOvfWord = 1 + kMaxQueries + 1;       // rs.overflow[kRecOvfWord]: the overflow was one of the hit-record areas (they can grow: TableLearned::rec_scale)
 
 // NQB query blocks of 32; WAVES waves per workgroup.  <=128 queries: 8 waves (2 per SIMD), ring of 4
 // pieces per wave; 256 queries: the 256 B-operand registers leave room for one wave per SIMD only, so
@@ -976,7 +927,6 @@ __device__ __forceinline__ uint32_t rec_mask(const char* r, const float* __restr
     }
     return m;
 }
-constexpr uint32_t kRecPoolSlice = 8192;       // records of the spill pool per decode workgroup
 __global__ __launch_bounds__(1024) void screen_decode_kernel(const char* __restrict__ rec, const uint32_t* __restrict__ rec_cnt,
                                                              uint32_t rec_cap, uint32_t rec_waves, const char* __restrict__ rec_pool,
                                                              uint32_t rec_pool_cap, const float* __restrict__ thr_screen, uint32_t row_end,
@@ -1364,25 +1314,6 @@ __global__ void screen_thr8_l2_kernel(const float* __restrict__ thr, const float
     b_out[q] = B;
 }
 
-// after a refined pilot plan: thr = score of the K-th best candidate kept (select_kernel), thr_ref = the raised threshold
-__global__ void refine_verify_kernel(const float* __restrict__ thr, const float* __restrict__ thr_ref,
-                                     uint32_t* __restrict__ count, uint32_t nq) {
-    const uint32_t q = threadIdx.x;
-    if (q < nq && !(thr[q] >= thr_ref[q])) count[q] = 0u;
-}
-
-__global__ void recall_init_kernel(const float* __restrict__ queries, uint32_t nq, uint32_t dim,
-                                   float* __restrict__ qpad, float* __restrict__ thr,
-                                   uint32_t* __restrict__ cnt, uint32_t* __restrict__ overflow) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < kMaxQueries * dim) qpad[i] = (i / dim) < nq ? queries[i] : 0.0f;
-    if (i < kMaxQueries) {
-        thr[i] = -__builtin_inff();
-        cnt[i] = 0;
-        cnt[kMaxQueries + i] = 0;                          // susp_cnt (RecallScratch: right behind cnt)
-    }
-    if (i == 0) { *overflow = 0; overflow[kRecOvfWord] = 0; }
-}
 
 // squared-Euclidean recall: |q|^2 of every query as a k-ascending fmaf chain (the specification's; |x|^2 of every row:
 // recall_table.hip), and the sign flip of the scores that come out (-d → d; padding -inf → +inf)
@@ -1395,88 +1326,6 @@ __global__ void query_norm2_kernel(const float* __restrict__ qpad, uint32_t dim,
 __global__ void negate_kernel(float* __restrict__ v, uint64_t n) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) v[i] = 0.0f - v[i];                     // (a zero distance comes out as +0, padding as +inf)
-}
-
-// (the threshold predictor's model and what it is for: recall_table.hip, at pred_moments_kernel)
-// per query: mean mu.q and sigma sqrt(q'Sq) of its scores (one workgroup of 128 threads per query)
-__global__ __launch_bounds__(128) void pred_query_kernel(const float* __restrict__ qpad, const float* __restrict__ pred,
-                                                         float* __restrict__ ms, float* __restrict__ thr, float z_lo) {
-    __shared__ float qs[128];
-    __shared__ double red[2][2];
-    const uint32_t q = blockIdx.x, t = threadIdx.x;
-    qs[t] = qpad[(size_t)q * 128 + t];
-    __syncthreads();
-    const float* S = pred + 128;
-    float sq = 0.0f;
-    for (int i = 0; i < 128; ++i) sq = __fmaf_rn(S[i * 128 + t], qs[i], sq);          // (S q)_t: S symmetric, column t coalesced
-    double v = (double)sq * (double)qs[t], m = (double)pred[t] * (double)qs[t];
-    for (int off = 32; off > 0; off >>= 1) {
-        v += __shfl_xor(v, off, 64);
-        m += __shfl_xor(m, off, 64);
-    }
-    if ((t & 63) == 0) { red[t >> 6][0] = v; red[t >> 6][1] = m; }
-    __syncthreads();
-    if (t == 0) {
-        const double var = red[0][0] + red[1][0], mean = red[0][1] + red[1][1];
-        const float m = (float)mean, sg = var > 0.0 ? (float)sqrt(var) : 0.0f;
-        ms[2 * q] = m;
-        ms[2 * q + 1] = sg;
-        if (thr) {
-            // first threshold from the model: mean + z_lo sigma, rounded down; anything odd → +inf, which leaves the query
-            // without candidates: the plan check then sends the batch to the pilot plan.  (Query columns >= nq keep the
-            // -inf recall_init_kernel gave them.)
-            float t = __fmaf_rn(z_lo, sg, m);
-            t = t - fabsf(t) * 1e-6f;
-            if (!(sg > 0.0f) || !(t == t) || fabsf(t) > 1e30f) t = __builtin_inff();
-            thr[q] = t;
-        }
-    }
-}
-// after a verified-to-be pass: fold the batch's observed quantiles into the table's statistics (queries that came up
-// short of K, or whose model sigma is 0, do not count), then they travel to the host with the status words
-__global__ void pred_update_kernel(const float* __restrict__ thr, const float* __restrict__ ms, const uint32_t* __restrict__ cnt,
-                                   uint32_t nq, uint32_t k, double* __restrict__ stats) {
-    const uint32_t q = threadIdx.x;
-    double z = 0.0, z2 = 0.0, n = 0.0, mn = 1e300;
-    if (q < nq && cnt[q] >= k && ms[2 * q + 1] > 0.0f) {
-        const float t = thr[q];
-        if (t == t && fabsf(t) < 1e30f) {
-            z = ((double)t - (double)ms[2 * q]) / (double)ms[2 * q + 1];
-            z2 = z * z;
-            n = 1.0;
-            mn = z;
-        }
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-        z += __shfl_xor(z, off, 64);
-        z2 += __shfl_xor(z2, off, 64);
-        n += __shfl_xor(n, off, 64);
-        const double o = __shfl_xor(mn, off, 64);
-        mn = o < mn ? o : mn;
-    }
-    if ((q & 63) == 0 && n > 0.0) {
-        atomicAdd(&stats[4], n);                       // observations ever (orders the host's snapshots; never decays)
-        atomicAdd(&stats[0], n);
-        atomicAdd(&stats[1], z);
-        atomicAdd(&stats[2], z2);
-        // (min via compare-and-swap on the bit pattern: the values are positive in every workload this is for, and a
-        //  stale minimum only makes the margin more careful)
-        unsigned long long* a = reinterpret_cast<unsigned long long*>(&stats[3]);
-        unsigned long long old = *a;
-        while (__longlong_as_double((long long)old) > mn) {
-            const unsigned long long seen = atomicCAS(a, old, (unsigned long long)__double_as_longlong(mn));
-            if (seen == old) break;
-            old = seen;
-        }
-    }
-    // a sliding window in effect: past 2^17 observations the sums halve, so a drifting query population moves the
-    // model within ~100 batches (the halving may race another stream's add and drop it: these are statistics)
-    __syncthreads();
-    if (q == 0 && stats[0] >= 131072.0) {
-        stats[0] *= 0.5;
-        stats[1] *= 0.5;
-        stats[2] *= 0.5;
-    }
 }
 
 template <int DIM, int NQB = 1, bool L2 = false>
@@ -1493,7 +1342,7 @@ static int launch_scan(pg_ctx* ctx, const ScanArgs& a) {
     return PG_OK;
 }
 
-static int dispatch_scan(pg_ctx* ctx, uint32_t dim, const ScanArgs& a) {
+int dispatch_scan(pg_ctx* ctx, uint32_t dim, const ScanArgs& a) {
     const bool wide = a.nq_launch > 32;          // two 32-query column blocks
     if (a.nx) {                                   // squared-Euclidean recall
         if (dim == 64) return wide ? launch_scan<64, 2, true>(ctx, a) : launch_scan<64, 1, true>(ctx, a);
@@ -1514,83 +1363,6 @@ static int dispatch_scan(pg_ctx* ctx, uint32_t dim, const ScanArgs& a) {
     }
     set_error("recall: dim=%u unsupported", dim);
     return PG_ERR_UNSUPPORTED;
-}
-
-constexpr uint32_t kFirstChunkRows = 32768;
-constexpr uint32_t kRescoreBlocksPerQuery = 16;   // x 256 suspects per block per stride step
-
-int recall_scratch(pg_ctx* ctx, uint32_t dim, uint32_t k, RecallScratch* rs) {
-    const uint32_t cap = k + kCandSlack;
-    int rc;
-    // the small regions stay packed as they always were (alignment = the element's own), but for the 64-byte fragment loads
-    if ((rc = scratch_carve(ctx, kSlotRecallSmall, [&](Carve& c) {
-            rs->qpad = c.take<float>((size_t)kMaxQueries * dim);
-            rs->qb16 = c.take<uint4>((size_t)kScreenMaxNQB * (dim / 16) * 64, 16);
-            rs->thr = c.take<float>(kMaxQueries, 4);
-            rs->eps = c.take<float>(kMaxQueries, 4);
-            rs->thr_screen = c.take<float>(kMaxQueries, 4);
-            rs->cnt = c.take<uint32_t>(kMaxQueries, 4);
-            rs->susp_cnt = c.take<uint32_t>(kMaxQueries, 4);
-            rs->overflow = c.take<uint32_t>(64 + kMaxQueries, 4);      // ONE region: the overflow word, the valid counts [kMaxQueries] right behind it (+ 1), padding
-            rs->qscale = c.take<float>(kMaxQueries, 4);
-            rs->q4 = c.take<uint32_t>(160, 4);                         // 4 x 128 B + 4 x 16 B
-            rs->thr_ref = c.take<float>(kMaxQueries, 4);
-            rs->pred_ms = c.take<float>(2 * (size_t)kMaxQueries, 4);
-            rs->susp2_cnt = c.take<uint32_t>(kI4mMaxQueries + 2, 4);   // + two statistics words
-            rs->q4m = c.take<uint32_t>(kQ4mWords, 64);                 // (16-byte fragment loads)
-            rs->q16 = c.take<uint32_t>((size_t)kMaxQueries * (2 * 32 + 4), 64);   // [256][32] Qh | [256][32] Ql | [256][4]
-            rs->susp2w_cnt = c.take<uint32_t>(kMaxQueries + 2, 4);
-            rs->status = c.take<uint32_t>(kRecallStatusWords + kMaxQueries, 64);  // ONE region, copied out together: the status words, then cnt_seen
-            rs->cnt_seen = rs->status + kRecallStatusWords;
-        }))) return rc;
-    const size_t lists = (size_t)kMaxQueries * cap;
-    if ((rc = scratch_carve(ctx, kSlotRecallCand, [&](Carve& c) {
-            rs->cand[0] = c.take<uint64_t>(lists);
-            rs->cand[1] = c.take<uint64_t>(lists);
-            rs->susp = c.take<uint32_t>(lists);
-            rs->susp2 = c.take<uint32_t>(lists);
-        }))) return rc;
-    rs->cap = cap;
-    return PG_OK;
-}
-
-// a job's status block, packed on the device by status_pack_kernel and copied to the host in ONE piece: [0] overflow flag,
-// [1 + q] valid count of query q, then
-constexpr uint32_t kPredStatsAt = 260;        // words [260, 270): the table's observation sums (five doubles)
-constexpr uint32_t kI4mStatAt = 272;          // [272] the (row, query) pairs the 4-bit stage of a mid-batch pass let through,
-                                              // [+1] suspects of the full pass's last launch, [+2] a hit-record area overflowed,
-                                              // [+3] pairs that reached the exact re-scoring, [+4] candidates the pass collected
-constexpr uint32_t kStatusCopyWords = kI4mStatAt + 5;
-static_assert(kStatusCopyWords <= 300 && kStatusCopyWords <= kRecallStatusWords, "the status block ends in front of the words other calls keep in ctx->h_status");
-// (an index plan has none of the words above: its own twelve take their place, index.hip)
-static_assert(kIndexStatAt > kMaxQueries && kIndexStatAt + 12 <= kStatusCopyWords, "an index plan's status words");
-
-// (launched <<<1, kMaxQueries>>>; null pointers = words that stay zero)
-__global__ void status_pack_kernel(const uint32_t* __restrict__ overflow, uint32_t nq, uint32_t rec_ovf_word,
-                                   const uint32_t* __restrict__ pred_stats, const uint32_t* __restrict__ pairs_word,
-                                   const uint32_t* __restrict__ susp, const uint32_t* __restrict__ rescored,
-                                   const uint32_t* __restrict__ cand_seen, uint32_t* __restrict__ out) {
-    const uint32_t t = threadIdx.x;
-    uint32_t v1 = (susp && t < nq) ? susp[t] : 0u, v3 = (rescored && t < nq) ? rescored[t] : 0u, v4 = (cand_seen && t < nq) ? cand_seen[t] : 0u;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        v1 += __shfl_xor(v1, off, 64);
-        v3 += __shfl_xor(v3, off, 64);
-        v4 += __shfl_xor(v4, off, 64);
-    }
-    __shared__ uint32_t s[3][4];
-    if ((t & 63) == 0) { s[0][t >> 6] = v1; s[1][t >> 6] = v3; s[2][t >> 6] = v4; }
-    out[1 + t] = t < nq ? overflow[1 + t] : 0u;
-    if (t < 10) out[kPredStatsAt + t] = pred_stats ? pred_stats[t] : 0u;
-    __syncthreads();
-    if (t == 0) {
-        out[0] = overflow[0];
-        out[kI4mStatAt] = pairs_word ? *pairs_word : 0u;
-        out[kI4mStatAt + 1] = s[0][0] + s[0][1] + s[0][2] + s[0][3];
-        out[kI4mStatAt + 2] = overflow[rec_ovf_word];
-        out[kI4mStatAt + 3] = s[1][0] + s[1][1] + s[1][2] + s[1][3];
-        out[kI4mStatAt + 4] = s[2][0] + s[2][1] + s[2][2] + s[2][3];
-    }
 }
 
 template <int DIM, int NQB, int WAVES, bool I8 = false, int QH = 1, int L2 = 0>
@@ -1636,788 +1408,57 @@ static int dispatch_screen(pg_ctx* ctx, uint32_t dim, bool i8, const ScreenArgs&
     return launch_screen<128, 4, 8>(ctx, a);
 }
 
-// ---------------------------------------------------------------------------------------------
-// One recall = one batch of queries against one table (one table pass when the first plan holds).
-// Plans, tried in order until one completes without overflowing a candidate list:
-//  pilot — the threshold comes from a jittered 1/S block sample (its K'-th best score, K' chosen six
-//          sigma above the expected rank K/S, so it is below the true K-th best except with
-//          negligible probability), then ONE full-rate pass over the whole table collects every row
-//          at or above it.  Verified exactly: if a query ends with fewer than min(K, rows)
-//          candidates the sample lied and the next plan runs.  ~1.5 K candidates per query instead
-//          of K ln(rows/32768) for the growing-chunk plan.  On big tables the pass is split after its first
-//          quarter and the thresholds are raised to the k2-th best candidate found so far (a 16x larger sample:
-//          ~1.2 K candidates per query for the rest); the raised threshold is verified against the K-th best
-//          score that comes out.  Batches of <= 4 queries stream the 4-bit shadow instead (recall_i4.hip).
-//  grow  — geometric chunks, threshold refreshed after each (small tables, and the fallback).
-//  safe  — bounded chunks that cannot overflow (adversarially ordered tables).
-// A plan is ENQUEUED as a whole (no host synchronisation inside it) and VERIFIED afterwards from a few status
-// words copied to pinned host memory: recall_dev_locked synchronises right away, the device-resident pipelines
-// (pipeline.hip) defer the check to the end of the whole request batch, so the rank / fusion / sort stages of a
-// batch are queued behind its recall without the GPU ever waiting for the host.
-// ---------------------------------------------------------------------------------------------
-enum RecallPlan { kPilot = 0, kGrow = 1, kSafe = 2, kPredict = 3 };
-
-static inline uint64_t rs_cap_bound(uint32_t k) { return (uint64_t)k + kCandSlack; }
-
-int recall_job_prepare(RecallJob* j) {
-    pg_ctx* ctx = j->ctx;
-    const pg_table* t = j->t;
-    const Knobs& kn = ctx->knobs;
+int screen_launch(pg_ctx* ctx, uint32_t dim, bool i8, const ScreenArgs& a) {
     int rc;
-    if (j->l2) {
-        if (t->dim != 64 && t->dim != 128) {
-            set_error("recall (squared Euclidean): dim=%u unsupported (64 or 128)", t->dim);
-            return PG_ERR_UNSUPPORTED;
-        }
-        if ((rc = ensure_table_nx(ctx, t))) return rc;
+    if ((rc = dispatch_screen(ctx, dim, i8, a))) return rc;
+    if (a.rec) {
+        screen_decode_kernel<<<a.rec_waves / 8 + a.rec_pool_cap / kRecPoolSlice, 1024, 0, ctx->stream>>>(
+            a.rec, a.rec_cnt, a.rec_cap, a.rec_waves, a.rec_pool, a.rec_pool_cap, a.thr_screen, a.row_end, a.susp_cnt, a.susp, a.cap, a.overflow);
+        PG_HIP(hipGetLastError());
     }
-    j->table_gen = t->generation.load(std::memory_order_relaxed);
-    j->rows_qualified = (uint32_t)t->rows;
-    if (j->filter.col && j->filter.admitted >= 0) {
-        j->rows_qualified = (uint32_t)j->filter.admitted;
-    } else if (j->filter.col) {
-        // how many rows the filter admits: the plan check needs it (a filtered list may rightly be shorter than K), and the
-        // pilot plan is only worth its launches when the sample holds enough of them
-        void* p;
-        if ((rc = scratch_reserve(ctx, kSlotStatus, 4096, &p))) return rc;
-        unsigned long long* d_n = reinterpret_cast<unsigned long long*>((char*)p + 3072);
-        PG_HIP(hipMemsetAsync(d_n, 0, 8, ctx->stream));
-        if ((rc = filter_count_launch(ctx, j->filter, t->rows, d_n))) return rc;
-        unsigned long long h_n = 0;
-        PG_HIP(hipMemcpyAsync(&h_n, d_n, 8, hipMemcpyDeviceToHost, ctx->stream));
-        PG_HIP(hipStreamSynchronize(ctx->stream));
-        j->rows_qualified = (uint32_t)h_n;
-        j->filter.admitted = (long long)h_n;      // (the re-run of a failed query does not count again)
-    }
-    if ((rc = recall_scratch(ctx, t->dim, j->k, &j->rs))) return rc;
-    j->d_count = j->rs.overflow + 1;              // status words in one block: one device → host copy
-    j->rows = (uint32_t)t->rows;
-    j->nblocks = (j->rows + kPieceRows - 1) / kPieceRows;
-    j->scan_ms = j->total_ms = 0.0;
-    j->scanned_rows = 0;
-    j->scan_bytes = 0;
-    j->scan_launches = 0;
-    j->next_plan = 0;
-    j->enqueued_plan = -1;
-    j->failed.clear();
-
-    // Policy: finite tables of dim <= 128 use the screened scan (int8 or bf16 filter + exact re-scoring) for every
-    // batch size (knobs.screen_min = 0), HBM-bound up to 128 queries per pass; everything else rides the exact
-    // fp32-MFMA scan in groups of <= 64 queries, one launch per group.
-    bool screen = j->nq > kn.screen_min && t->dim <= 128 && !kn.recall_exact && !j->exact_only;
-    if (screen) {
-        if ((rc = ensure_table_stats(ctx, t))) return rc;
-        if (!t->derived.stats_valid || !t->derived.all_finite) screen = false;      // no shadow (dim, memory) or non-finite rows
-    }
-    TableLearned seen;                                 // what the policy below reads of pg_table::learned: one snapshot
-    {
-        std::lock_guard<std::mutex> state_guard(g_table_state_mu);
-        if (screen && t->learned.screen_backed_off()) screen = false;   // this table's screened plans kept overflowing: exact scan for now
-        seen = t->learned;
-    }
-    // squared Euclidean: the int8 screen with per-block cutoffs for up to 128 queries (dim 128, int8 shadow); else the exact scan
-    if (j->l2 && !(screen && t->dim == 128 && t->derived.shadow_is_i8 && j->nq <= 128 && !kn.l2_exact)) screen = false;
-    // rows of (nearly) one norm: one cutoff per 32-row block; beyond: the per-row test (three VALU instructions per bound instead of half a one)
-    j->l2_per_row = j->l2 && screen && t->derived.l2_slack > kn.l2_max_slack;
-    j->screen = screen;
-    j->screen4 = j->screen4m = false;
-    j->n_plans = 0;
-    j->stride = 1;
-    j->sample_blocks = 0;
-    j->k_pilot = 0;
-    j->perm_mul = 1;
-    const uint32_t rows = j->rows;
-    const uint32_t full_blocks = rows / kPieceRows;           // the sample only uses whole blocks
-    // 1/96 of the blocks: with the refinement step of the pilot plan (below) the sample's threshold only serves the
-    // first quarter of the full pass, so a thinner, cheaper sample wins (256 requests: 291 vs 286 M items/s at 1/64,
-    // 261 M at 1/32; before the refinement 1/64 was best)
-    uint32_t want = full_blocks / 96;
-    // >= 1M sample rows, but never more than an eighth of the table: small tables are launch-bound, and the pilot's
-    // three scan launches beat the growing-chunk plan's nine (1M x 64, K = 200: 0.31 -> 0.13 ms per recall)
-    const uint32_t floor_blocks = full_blocks / 8 < 32768 ? full_blocks / 8 : 32768;
-    if (want < floor_blocks) want = floor_blocks;
-    if (kn.pilot_fraction > 0.0) want = (uint32_t)(full_blocks * kn.pilot_fraction);
-    j->stride = want ? full_blocks / want : 1;
-    if (j->stride >= 2 && !kn.no_pilot) {
-        j->sample_blocks = full_blocks / j->stride;
-        const double m = (double)j->k * ((double)j->sample_blocks * kPieceRows / (double)rows);
-        j->k_pilot = (uint32_t)ceil(m + ctx->knobs.pilot_sigmas * sqrt(m) + 8.0);
-        // (a filter thins the sample by its selectivity: the sample must still hold 4 K' admitted rows)
-        const double admitted = rows ? (double)j->rows_qualified / (double)rows : 1.0;
-        if ((double)j->k_pilot * 4.0 <= (double)j->sample_blocks * kPieceRows * admitted) j->plans[j->n_plans++] = kPilot;
-        j->perm_mul = 2654435761u % j->sample_blocks;          // golden-ratio step, made coprime below
-        if (j->perm_mul < 2) j->perm_mul = 1;
-        auto gcd = [](uint32_t x, uint32_t y) { while (y) { const uint32_t r = x % y; x = y; y = r; } return x; };
-        while (gcd(j->perm_mul, j->sample_blocks) != 1) ++j->perm_mul;
-    }
-    j->plans[j->n_plans++] = kGrow;
-    j->plans[j->n_plans++] = kSafe;
-    if (j->skip_pilot && j->plans[0] == kPilot) j->next_plan = 1;    // the re-run of a query a sampled threshold failed
-    static_assert(kIndexPlan != kPilot && kIndexPlan != kGrow && kIndexPlan != kSafe && kIndexPlan != kPredict, "plan ids");
-    // small batches: the pilot plan's full pass is HBM-bound on the shadow it streams — use the 4-bit one (recall_i4.hip)
-    if (screen && t->dim == 128 && j->nq <= kI4MaxQueries && j->plans[0] == kPilot && !kn.no_screen_i4 &&
-        rows >= kn.i4_min_rows && (uint64_t)kMaxQueries * rs_cap_bound(j->k) / kI4MaxQueries < 0xFFFFFFFFull) {
-        if ((rc = ensure_table_i4(ctx, t))) return rc;
-        // (measured at 100M x 128, int8 pass 2.1 ms: uniform rows, lambda 0.8: 1.37 / 1.38 / 1.59 / 1.66 ms at 1..4
-        // queries; Gaussian rows, lambda 1.3: 1.46 / 1.59 / 1.78 / 2.02 — every query re-scores its own suspects)
-        static const double kLamScale[kI4MaxQueries] = {1.0, 1.0, 0.88, 0.7};
-        j->screen4 = t->derived.i4_ok && (double)t->derived.lam4 <= kn.i4_max_lambda * kLamScale[j->nq - 1];
-    }
-    // 1 .. 64 queries, inner product, int8 main shadow: the same 4-bit shadow through the matrix pipe, suspects thinned on the int8
-    // shadow (recall_i4m.hip) — also for one or two queries (1.08 against the vector screen's 1.17 ms per 100 M rows: its int8 stage
-    // re-scores a twentieth of the suspects)
-    if (screen && !j->l2 && t->dim == 128 && t->derived.shadow_is_i8 && j->nq >= kn.i4m_min_queries && j->nq <= kI4mMaxQueries &&
-        j->nq <= kn.i4m_max_queries && j->plans[0] == kPilot && !kn.no_screen_i4m && rows >= kn.i4_min_rows) {
-        if ((rc = ensure_table_i4(ctx, t))) return rc;
-        // every pair the 4-bit stage lets through is one random 128-B read (~35 G/s in rescreen8_kernel): beyond i4m_max_pairs of them per pass
-        // the int8 shadow's wider stream is the shorter pass.  The count per query is the table's own running average.
-        // (two query blocks: the 4-bit stage is vector-ALU-bound, 1.5 instead of 1.2 ms per 100 M rows — the budget shrinks with the gain)
-        j->screen4m = t->derived.i4_ok && (double)t->derived.lam4 <= kn.i4m_max_lambda &&
-                      (double)seen.i4m_pairs * j->nq <= kn.i4m_max_pairs * (j->nq > 32 ? 0.7 : 1.0);
-        if (j->screen4m) j->screen4 = false;
-    }
-    // crowded rows (clustered embeddings: many suspects per answer): the int8 screen's suspects pass a two-digit refinement on the
-    // residual shadow before the exact re-scoring (recall_r2.hip); passes with a 4-bit stage have their own int8 stage
-    j->stage2 = false;
-    if (screen && !j->l2 && t->dim == 128 && t->derived.shadow_is_i8 && !j->screen4m && !j->screen4 && !kn.no_r2 &&
-        (double)seen.wide_susp > kn.r2_min_factor * (double)j->k) {
-        if ((rc = ensure_table_r2(ctx, t))) return rc;
-        j->stage2 = t->derived.r2_ok;
-    }
-    // the threshold model: observe with every pilot-plan batch of a big int8-screened table; predict once the observed
-    // quantile is tight (plan 0)
-    j->predict = j->pred_observe = false;
-    // (batches of <= 4 queries too: their full pass — the 4-bit shadow's — takes the same float thresholds, and the pilot's five
-    //  launches are 0.15 ms of a lone request's 1.45)
-    if (screen && !j->l2 && !j->filter.col && t->dim == 128 && t->derived.shadow_is_i8 && j->plans[0] == kPilot && !j->skip_pilot && !kn.no_predict &&
-        rows >= kn.predict_min_rows && j->k < rows / 64) {
-        if ((rc = ensure_pred_model(ctx, t))) return rc;
-        std::lock_guard<std::mutex> state_guard(g_table_state_mu);
-        TableLearned& ln = t->learned;
-        if (t->derived.pred_model) {
-            if (ln.pred_k != j->k) {                   // the observations belong to one K
-                PG_HIP(hipMemsetAsync(t->derived.d_pred + 128 + 128 * 128, 0, 24, ctx->stream));
-                ln.pred_change_k(j->k);
-            }
-            // (a mature model learns nothing from a lone request: its two launches and the 40-byte copy are spared)
-            j->pred_observe = !(j->nq <= (uint32_t)kI4MaxQueries && ln.pred_n >= 8192.0);
-            if (ln.pred_backoff > 0) {
-                --ln.pred_backoff;
-            } else if (ln.pred_n >= 1024.0) {
-                const double mean = ln.pred_sum / ln.pred_n;
-                const double var = ln.pred_sum2 / ln.pred_n - mean * mean;
-                const double sd = var > 0.0 ? sqrt(var) : 0.0;
-                // tight enough to beat the sample's own six-sigma margin (a threshold 3 % low in z doubles the rows that reach it)
-                if (mean > 0.5 && sd <= 0.025 * mean) {
-                    j->predict = true;
-                    j->z_lo = mean - kn.predict_sigmas * sd - 0.002 * mean;
-                    for (int i = j->n_plans; i > 0; --i) j->plans[i] = j->plans[i - 1];
-                    j->plans[0] = kPredict;
-                    j->n_plans++;
-                }
-            }
-        }
-    }
-    // a table with an attached index: its plan goes in front of everything above (index.hip; the plans above stay as they are
-    // and serve the batch when it does not hold)
-    return index_plan_prepare(j);
+    return PG_OK;
 }
 
-namespace {
-struct PlanRun {                     // the launches of one plan (helper of recall_job_enqueue)
-    RecallJob* j;
-    pg_ctx* ctx;
-    const pg_table* t;
-    RecallScratch& rs;
-    uint32_t n_ev = 0;
-    int cur = 0;
-    bool susp2_clean = false;        // screen4m_prep_kernel left the mid-batch pass's second counters at zero (same)
-    bool susp_clean = true;          // recall_init_kernel left the suspect counters at zero: the plan's first screened launch skips its memset
-    bool no_i8 = false;              // the plan launches no int8 / bf16 screen (thresholds predicted, full pass on the 4-bit shadow):
-                                     // its integer-unit thresholds are not needed
-    bool last_full_screened = false; // the plan's last scan launch was a screened one ...
-    bool last_was_i4m = false;       // ... of the mid-batch kind (its survivors are counted in susp2_cnt)
-    bool last_was_r2 = false;        // ... followed by the refinement stage (its survivors are counted in susp2w_cnt)
-    bool exact_chunks = false;       // every chunk on the exact scan: the safe plan of a FILTERED recall.  Its thresholds stay open until K
-                                     // admitted rows were seen — under a selective filter, for many chunks — and a screened chunk with open
-                                     // thresholds makes every row a suspect of every query: the hit-record regions are sized for the bounded
-                                     // chunk spread evenly over the waves, the waves' shares are not even.  The exact scan stages admitted
-                                     // rows only, at most the chunk's rows per query.
-
-    explicit PlanRun(RecallJob* job) : j(job), ctx(job->ctx), t(job->t), rs(job->rs) {}
-
-    // one scan launch over logical blocks [rb, rb+cb) of a stride-`st` view, bracketed by HIP events:
-    // their sum is the per-pass duration of the dominant kernel that bench.py prices against HBM
-    int scan_range(uint32_t rb, uint32_t cb, uint32_t st, bool thr_is_open, bool allow_i4 = false) {
-        std::vector<hipEvent_t>& pool = *j->events;
-        while (pool.size() < 2 * (size_t)(n_ev + 1)) {
-            hipEvent_t e;
-            PG_HIP(hipEventCreate(&e));
-            pool.push_back(e);
-        }
-        if (j->timers) PG_HIP(hipEventRecord(pool[2 * n_ev], ctx->stream));
-        const uint32_t nq = j->nq;
-        if (j->screen && !thr_is_open && !exact_chunks) {
-            ScreenArgs sa;
-            sa.tab16 = t->derived.shadow_is_i8 ? (const void*)t->derived.d8 : (const void*)t->derived.d16;
-            sa.blk_norm2 = t->derived.dnorm2;
-            sa.eps_unit = rs.eps;
-            sa.qb16 = rs.qb16;
-            sa.thr_screen = rs.thr_screen;
-            sa.susp_cnt = rs.susp_cnt;
-            sa.susp = rs.susp;
-            sa.overflow = rs.overflow;
-            sa.cap = rs.cap;
-            sa.nq = nq;
-            sa.rb_begin = rb;
-            sa.rb_end = rb + cb;
-            sa.row_end = j->rows;
-            sa.stride = st;
-            sa.perm_mul = j->perm_mul;
-            sa.perm_mod = j->sample_blocks;
-            int rc2;
-            // > 128 queries on the int8 shadow: the scan leaves hit records, decoded into the suspect lists below
-            const bool records = t->derived.shadow_is_i8 && nq > 128;
-            sa.rec = nullptr;
-            sa.rec_cnt = nullptr;
-            sa.rec_cap = 0;
-            sa.rec_pool = nullptr;
-            sa.rec_pool_cap = sa.rec_waves = 0;
-            sa.early_share = records ? ctx->knobs.screen_early_share : ctx->knobs.screen_early_share_narrow;
-            sa.blk_nxmin = j->l2 && !j->l2_per_row ? t->derived.d_nxmin : nullptr;
-            sa.nx_rows = j->l2 && j->l2_per_row ? t->derived.d_nx : nullptr;
-            sa.l2_b = j->l2 ? rs.thr_ref : nullptr;    // (no refinement step under this metric: its buffer carries B_q)
-            const uint32_t rec_waves = (uint32_t)ctx->num_cus * 8u;
-            if (records) {
-                // a region per wave: four times the share of 256 x K suspects a wave expects, never below the records the safe
-                // plan's bounded chunks can leave in one region
-                // (tables whose batches overflowed these areas got larger ones.  A fresh snapshot: recall_job_check doubles it and the same plan runs again)
-                const uint64_t rsc = table_learned(t).rec_scale_eff();
-                uint32_t cap_w = (uint32_t)(((uint64_t)kMaxQueries * j->k * 4 * rsc / rec_waves + 255) / 256 * 256);
-                // (the safe plan's chunk — kCandSlack / 2 rows — with EVERY row a suspect of every query, e.g. a table in ascending
-                //  score order: 16 query blocks of 16 x 64 lanes = 1024 records per block, and the blocks of a SIMD's pair of waves split as screen_kernel splits
-                //  them — the larger share decides.  Sized for an even split, the early wave's fifth block went to the spill pool,
-                //  which at a small K is small: "overflow in safe mode" on such a table at K = 10, 256 queries.)
-                const uint32_t pairs = (uint32_t)ctx->num_cus * 4u;
-                const uint32_t pb = (kCandSlack / 2 / kPieceRows + pairs - 1) / pairs;
-                const uint32_t es = sa.early_share > 512 ? sa.early_share : 1024 - sa.early_share;
-                uint32_t eb = (uint32_t)(((uint64_t)pb * es + 512) >> 10) + 1;
-                if (eb > pb) eb = pb;
-                const uint32_t floor_w = eb * 1024;
-                if (cap_w < floor_w) cap_w = floor_w;
-                // + a spill pool for tables whose best rows sit together: room for all of 256 x 2 K suspects
-                const uint32_t pool_cap = (uint32_t)(((uint64_t)kMaxQueries * j->k * 2 * rsc + kRecPoolSlice - 1) / kRecPoolSlice * kRecPoolSlice);
-                if ((rc2 = scratch_carve(ctx, kSlotHitRecords, [&](Carve& c) {
-                        sa.rec_cnt = c.take<uint32_t>((size_t)rec_waves + 1);
-                        sa.rec = (char*)c.bytes(((size_t)rec_waves * cap_w + pool_cap) * kRecBytes);      // the wave regions, then the spill pool
-                    }))) return rc2;
-                sa.rec_cap = cap_w;
-                sa.rec_pool = sa.rec + (size_t)rec_waves * cap_w * kRecBytes;
-                sa.rec_pool_cap = pool_cap;
-                sa.rec_waves = rec_waves;
-                PG_HIP(hipMemsetAsync(sa.rec_cnt, 0, (size_t)(rec_waves + 1) * 4, ctx->stream));
-            }
-            if (!susp_clean) PG_HIP(hipMemsetAsync(rs.susp_cnt, 0, sizeof(uint32_t) * kMaxQueries, ctx->stream));
-            susp_clean = false;
-            last_full_screened = true;
-            last_was_r2 = false;
-            // the full pass of a small batch streams the 4-bit shadow; its few suspect lists share the whole buffer
-            // (whole 64-row groups: a range starts on an even block and ends on one or at the table's end)
-            const bool i4 = j->screen4 && allow_i4 && st == 1 && (rb & 1) == 0 && (((rb + cb) & 1) == 0 || rb + cb == j->nblocks);
-            const bool i4m = j->screen4m && allow_i4 && st == 1 && (rb & 1) == 0 && (((rb + cb) & 1) == 0 || rb + cb == j->nblocks);
-            const uint32_t scap = i4 ? rs.cap * (uint32_t)(kMaxQueries / kI4MaxQueries) : rs.cap;
-            const uint64_t r_begin = (uint64_t)rb * kPieceRows;
-            const uint64_t r_end = (uint64_t)(rb + cb) * kPieceRows < j->rows ? (uint64_t)(rb + cb) * kPieceRows : j->rows;
-            if (i4) {
-                if ((rc2 = screen4_launch(ctx, t, rs, nq, (uint32_t)r_begin, (uint32_t)r_end, scap, j->l2 ? rs.pred_ms : nullptr))) return rc2;
-                j->scan_bytes += (r_end - r_begin) * (j->l2 ? 72 : 68);      // (squared Euclidean: + the row's |x|^2)
-            } else if (i4m) {
-                // stage-1 suspects share the whole buffer ([nq][4 cap]); what passes the int8 stage lands in susp2 ([nq][cap])
-                if ((rc2 = screen4m_launch(ctx, t, rs, nq, (uint32_t)r_begin, (uint32_t)r_end, rs.cap * (uint32_t)(kMaxQueries / kI4mMaxQueries), susp2_clean))) return rc2;
-                susp2_clean = false;
-                j->scan_bytes += (r_end - r_begin) * 68;
-                last_was_i4m = true;
-            } else {
-                last_was_i4m = false;
-                if ((rc2 = dispatch_screen(ctx, t->dim, t->derived.shadow_is_i8, sa))) return rc2;
-                if (records) {
-                    screen_decode_kernel<<<rec_waves / 8 + sa.rec_pool_cap / kRecPoolSlice, 1024, 0, ctx->stream>>>(
-                        sa.rec, sa.rec_cnt, sa.rec_cap, rec_waves, sa.rec_pool, sa.rec_pool_cap, rs.thr_screen, j->rows,
-                                                                            rs.susp_cnt, rs.susp, rs.cap, rs.overflow);
-                    PG_HIP(hipGetLastError());
-                }
-                j->scan_bytes += (uint64_t)cb * kPieceRows * t->dim * (t->derived.shadow_is_i8 ? 1 : 2);
-            }
-            j->scanned_rows += (uint64_t)cb * kPieceRows;
-            // exact re-scoring of the launch's suspects → candidate keys (grid.x strides over each list)
-            const dim3 rg(i4 ? screen4_rescore_blocks() : kRescoreBlocksPerQuery, nq);
-            const bool r2 = j->stage2 && t->derived.shadow_is_i8 && !i4 && !i4m && !j->l2 && t->dim == 128;
-            if (r2) {
-                // crowded rows: the suspects once more with two more digits (recall_r2.hip); what is left goes to the exact re-scoring
-                if ((rc2 = rescreen16_launch(ctx, t, rs, nq))) return rc2;
-                last_was_r2 = true;
-                rescore_kernel<128><<<rg, 256, 0, ctx->stream>>>(t->d, rs.qpad, rs.thr, rs.susp2, rs.susp2w_cnt, rs.cap,
-                                                                 rs.cnt, rs.cand[cur], rs.overflow, rs.cap, j->rows, nullptr, nullptr, j->filter);
-            } else if (j->l2)
-                rescore_kernel<128, true><<<rg, 256, 0, ctx->stream>>>(t->d, rs.qpad, rs.thr, rs.susp, rs.susp_cnt, rs.cap, rs.cnt,
-                                                                       rs.cand[cur], rs.overflow, scap, j->rows, t->derived.d_nx, rs.pred_ms, j->filter);
-            else if (t->dim == 64)
-                rescore_kernel<64><<<rg, 256, 0, ctx->stream>>>(t->d, rs.qpad, rs.thr, rs.susp, rs.susp_cnt, rs.cap,
-                                                                rs.cnt, rs.cand[cur], rs.overflow, scap, j->rows, nullptr, nullptr, j->filter);
-            else if (i4m)
-                rescore_kernel<128><<<rg, 256, 0, ctx->stream>>>(t->d, rs.qpad, rs.thr, rs.susp2, rs.susp2_cnt, rs.cap,
-                                                                 rs.cnt, rs.cand[cur], rs.overflow, rs.cap, j->rows, nullptr, nullptr, j->filter);
-            else
-                rescore_kernel<128><<<rg, 256, 0, ctx->stream>>>(t->d, rs.qpad, rs.thr, rs.susp, rs.susp_cnt, rs.cap,
-                                                                 rs.cnt, rs.cand[cur], rs.overflow, scap, j->rows, nullptr, nullptr, j->filter);
-            PG_HIP(hipGetLastError());
-        } else {
-            last_full_screened = false;
-            // exact scan (the first chunk of a screened recall too: its threshold is still -inf,
-            // every row is a candidate and there is nothing to screen) in groups of <= 64 queries,
-            // one launch; blockIdx.y walks the groups
-            ScanArgs a;
-            a.tab = t->d;
-            a.qpad = rs.qpad;
-            a.thr = rs.thr;
-            a.cnt = rs.cnt;
-            a.cand = rs.cand[cur];
-            a.overflow = rs.overflow;
-            a.cap = rs.cap;
-            a.nq = nq;
-            a.group_q = nq > (uint32_t)kMaxQueriesExact ? (uint32_t)kMaxQueriesExact : 0u;
-            a.nq_launch = a.group_q ? a.group_q : nq;
-            a.rb_begin = rb;
-            a.rb_end = rb + cb;
-            a.row_end = j->rows;
-            a.stride = st;
-            a.perm_mul = j->perm_mul;
-            a.perm_mod = j->sample_blocks;
-            a.nx = j->l2 ? t->derived.d_nx : nullptr;
-            a.nqv = j->l2 ? rs.pred_ms : nullptr;
-            a.filter = j->filter;
-            int rc2;
-            if ((rc2 = dispatch_scan(ctx, t->dim, a))) return rc2;
-            j->scan_bytes += (uint64_t)cb * kPieceRows * t->dim * 4;
-            j->scanned_rows += (uint64_t)cb * kPieceRows;
-        }
-        if (j->timers) PG_HIP(hipEventRecord(pool[2 * n_ev + 1], ctx->stream));
-        ++n_ev;
-        return PG_OK;
-    }
-    // keep the best `kk` candidates per query, refresh the thresholds, swap the ping-pong lists
-    // last: no launch screens against these thresholds any more (the screen's integer cutoffs are not derived)
-    int refresh(uint32_t kk, bool last = false) {
-        int rc2;
-        if ((rc2 = launch_select(ctx, j->nq, rs.cand[cur], rs.cand[cur ^ 1], rs.cnt, rs.thr, rs.cap, kk, 0, rs.cnt_seen))) return rc2;
-        if (j->screen && !no_i8 && !(last && !j->l2)) {
-            if (j->l2) screen_thr8_l2_kernel<<<1, kMaxQueries, 0, ctx->stream>>>(rs.thr, rs.eps, rs.qscale, rs.pred_ms, t->derived.s8, t->derived.max_norm,
-                                                                                rs.thr_screen, rs.thr_ref, j->l2_per_row ? 1 : 0);
-            else if (t->derived.shadow_is_i8) screen_thr8_kernel<<<1, kMaxQueries, 0, ctx->stream>>>(rs.thr, rs.eps, rs.qscale, t->derived.s8, rs.thr_screen);
-            else screen_thr_kernel<<<1, kMaxQueries, 0, ctx->stream>>>(rs.thr, rs.eps, t->derived.max_norm, rs.thr_screen);
-            PG_HIP(hipGetLastError());
-        }
-        cur ^= 1;
-        return PG_OK;
-    }
-    // raise the thresholds to every query's kk-th best candidate so far (lists untouched)
-    int refine(uint32_t kk) {
-        int rc2;
-        if ((rc2 = launch_select(ctx, j->nq, rs.cand[cur], rs.cand[cur ^ 1], rs.cnt, rs.thr, rs.cap, kk, 1))) return rc2;
-        if (j->screen) {
-            if (t->derived.shadow_is_i8) screen_thr8_kernel<<<1, kMaxQueries, 0, ctx->stream>>>(rs.thr, rs.eps, rs.qscale, t->derived.s8, rs.thr_screen);
-            else screen_thr_kernel<<<1, kMaxQueries, 0, ctx->stream>>>(rs.thr, rs.eps, t->derived.max_norm, rs.thr_screen);
-            PG_HIP(hipGetLastError());
-        }
-        return PG_OK;
-    }
-    // geometric chunks over `nb` logical blocks of a stride-`st` view, keeping the best `kk`
-    int grow_scan(uint32_t nb, uint32_t st, uint32_t kk, double growth, bool safe) {
-        uint32_t rb = 0;
-        while (rb < nb) {
-            uint32_t chunk_rows;
-            if (rb == 0) {
-                // every row of the first chunk becomes a candidate of every query: keep it just large
-                // enough to seed a meaningful threshold (8 x kk rows, 2048..32768)
-                chunk_rows = next_pow2(8 * kk);
-                if (chunk_rows < 2048) chunk_rows = 2048;
-                if (chunk_rows > kFirstChunkRows || chunk_rows < kk) chunk_rows = kFirstChunkRows;
-            } else {
-                // chunk = (growth-1) x rows seen: every chunk stages ≈ (growth-1)*kk candidates per query
-                const uint64_t grow = (uint64_t)((double)rb * kPieceRows * (growth - 1.0));
-                chunk_rows = grow > 0xFFFFFFE0ull ? 0xFFFFFFE0u : (uint32_t)grow;
-            }
-            if (safe && chunk_rows > kCandSlack / 2) chunk_rows = kCandSlack / 2;
-            uint32_t cb = chunk_rows / kPieceRows;
-            if (cb > nb - rb) cb = nb - rb;
-            int rc2;
-            if ((rc2 = scan_range(rb, cb, st, rb == 0))) return rc2;
-            rb += cb;
-            if ((rc2 = refresh(kk))) return rc2;
-        }
-        return PG_OK;
-    }
-};
-}  // namespace
-
-int recall_job_enqueue(RecallJob* j) {
-    pg_ctx* ctx = j->ctx;
-    const pg_table* t = j->t;
-    const Knobs& kn = ctx->knobs;
-    if (j->next_plan >= j->n_plans) {
-        set_error("recall: candidate overflow in safe mode (internal error)");
-        return PG_ERR_DEVICE;
-    }
-    const int plan = j->plans[j->next_plan];
-    int rc;
-    // another call on this context may have grown the scratch arenas since recall_job_prepare (a re-plan reaches
-    // here long after it): fetch the pointers again rather than trust the cached ones
-    if ((rc = recall_scratch(ctx, t->dim, j->k, &j->rs))) return rc;
-    j->d_count = j->rs.overflow + 1;
-    if (plan == kIndexPlan) return index_plan_enqueue(j, kStatusCopyWords);
-    PlanRun r(j);
-    RecallScratch& rs = j->rs;
-    recall_init_kernel<<<(kMaxQueries * t->dim + 255) / 256, 256, 0, ctx->stream>>>(
-        j->d_queries, j->nq, t->dim, rs.qpad, rs.thr, rs.cnt, rs.overflow);
+int screen_prep_launch(pg_ctx* ctx, const pg_table* t, const RecallScratch& rs, uint32_t nq, bool wide) {
+    if (t->derived.shadow_is_i8)
+        screen_prep8_kernel<<<nq <= 32 ? 1u : (nq <= 64 ? 2u : (nq <= 128 ? 4u : 8u)), 128, 0, ctx->stream>>>(
+            rs.qpad, t->dim, t->derived.max_norm, t->derived.resid8, rs.qb16, rs.eps, rs.qscale,
+            wide ? 1u : 0u);     // grid = the scan's NQB x QH; wide: dispatch_screen's query halves
+    else
+        screen_prep_kernel<<<(kScreenMaxNQB * (t->dim / 16) * 64 + 255) / 256, 256, 0, ctx->stream>>>(
+            rs.qpad, t->dim, rs.qb16, rs.eps);
     PG_HIP(hipGetLastError());
-    if (j->l2) {
-        query_norm2_kernel<<<1, kMaxQueries, 0, ctx->stream>>>(rs.qpad, t->dim, rs.pred_ms);      // (the threshold model is off: its buffer is free)
-        PG_HIP(hipGetLastError());
-    }
-    // thresholds predicted and the full pass on the 4-bit shadow: the plan launches no int8 screen, so neither the int8 query
-    // fragments nor the integer-unit thresholds are needed (two launches less in front of a lone request, two behind)
-    r.no_i8 = plan == kPredict && j->screen4;
-    if (j->screen) {
-        if (!r.no_i8) {
-            if (t->derived.shadow_is_i8)
-                screen_prep8_kernel<<<j->nq <= 32 ? 1u : (j->nq <= 64 ? 2u : (j->nq <= 128 ? 4u : 8u)), 128, 0, ctx->stream>>>(
-                    rs.qpad, t->dim, t->derived.max_norm, t->derived.resid8, rs.qb16, rs.eps, rs.qscale,
-                    j->nq > 128 && !j->l2 ? 1u : 0u);     // grid = the scan's NQB x QH; wide: dispatch_screen's query halves
-            else
-                screen_prep_kernel<<<(kScreenMaxNQB * (t->dim / 16) * 64 + 255) / 256, 256, 0, ctx->stream>>>(
-                    rs.qpad, t->dim, rs.qb16, rs.eps);
-            PG_HIP(hipGetLastError());
-        }
-        if (j->screen4 && (rc = screen4_prep_launch(ctx, t, rs))) return rc;
-        if (j->screen4m) {
-            if ((rc = screen4m_prep_launch(ctx, rs, j->nq))) return rc;
-            r.susp2_clean = true;
-        }
-        if (j->stage2 && (rc = rescreen16_prep_launch(ctx, t, rs, j->nq))) return rc;
-    }
-    const bool observe = j->pred_observe && (plan == kPilot || plan == kPredict);
-    if (observe || plan == kPredict) {
-        // mean and sigma of every query's scores; under prediction the same launch writes the first thresholds
-        pred_query_kernel<<<j->nq, 128, 0, ctx->stream>>>(rs.qpad, t->derived.d_pred, rs.pred_ms, plan == kPredict ? rs.thr : nullptr,
-                                                          (float)j->z_lo);
-        PG_HIP(hipGetLastError());
-    }
-    while (j->events->size() < 2) {
-        hipEvent_t e;
-        PG_HIP(hipEventCreate(&e));
-        j->events->push_back(e);
-    }
-    bool refined = false;
-    // events 0/1 of the pool bracket the whole plan; PlanRun's launches use the pairs after them
-    r.n_ev = 1;
-    j->timers = !ctx->timers_off;
-    if (j->timers) PG_HIP(hipEventRecord((*j->events)[0], ctx->stream));
-    if (plan == kPredict && !r.no_i8) {
-        // no sample: the first thresholds are the model's (pred_query_kernel above), here in the int8 screen's units
-        screen_thr8_kernel<<<1, kMaxQueries, 0, ctx->stream>>>(rs.thr, rs.eps, rs.qscale, t->derived.s8, rs.thr_screen);
-        PG_HIP(hipGetLastError());
-    }
-    if (plan == kPilot || plan == kPredict) {
-      if (plan == kPilot) {
-        // The sample itself is streamed in two launches when it is screened: a seed of `seed_rows` rows
-        // (exact, every row a candidate) whose m0-th best score becomes the threshold of ONE screened
-        // launch over the rest of the sample; m0 is chosen so that fewer than K' sample rows reaching
-        // that threshold has probability < 1e-9 (Poisson tail of seed hits among the sample's top K');
-        // should it happen anyway, select_kernel leaves the threshold at -inf, the full pass overflows
-        // and the next plan takes over.  (Measured against geometric chunks over the sample: 1.0 → 0.7 ms.)
-        const uint32_t seed_rows = kn.seed_rows;
-        const uint64_t sample_rows = (uint64_t)j->sample_blocks * kPieceRows;
-        if (j->screen && kn.pilot_growth <= 0.0 && sample_rows > 8ull * seed_rows && j->k_pilot < seed_rows / 4) {
-            const double mu = (double)seed_rows * (double)j->k_pilot / (double)sample_rows;
-            uint32_t m0 = 1;
-            for (double term = exp(-mu), cdf = term; 1.0 - cdf > 1e-9 && m0 < seed_rows; ++m0) {
-                term *= mu / (double)m0;          // P(X = m0)
-                cdf += term;                      // P(X <= m0)  →  loop ends with P(X >= m0+1) <= 1e-9
-            }
-            ++m0;
-            const uint32_t sb = seed_rows / kPieceRows;
-            if ((rc = r.scan_range(0, sb, j->stride, true))) return rc;
-            if ((rc = r.refresh(m0))) return rc;
-            if ((rc = r.scan_range(sb, j->sample_blocks - sb, j->stride, false))) return rc;
-            if ((rc = r.refresh(j->k_pilot))) return rc;
-        } else {
-            // geometric chunks over the sample (exact scan, or pilot_growth set: A/B runs)
-            if ((rc = r.grow_scan(j->sample_blocks, j->stride, j->k_pilot, kn.pilot_growth > 0.0 ? kn.pilot_growth : 8.0, false))) return rc;
-        }
-      }
-        if (plan == kPilot) PG_HIP(hipMemsetAsync(rs.cnt, 0, sizeof(uint32_t) * kMaxQueries, ctx->stream));    // (kPredict: still zero from recall_init_kernel)
-        // The sample's threshold is deliberately low (K' = m + 6 sqrt(m) + 8 of a 1/64 sample: ~1.8 K rows reach it where K
-        // are needed), and every row that reaches it costs a suspect's hit path and an exact re-scoring — a quarter of
-        // the 256-query pass.  After the first quarter of the table the candidates found so far ARE a 16x larger sample:
-        // their k2-th best (k2 from the same formula) is a much tighter threshold for the other three quarters.  A
-        // contiguous prefix is not a random sample: if the prefix holds more than its share of the best rows the raised
-        // threshold can exceed the true K-th score — which is CHECKED after the pass (refine_verify_kernel: the K-th
-        // best score that came out must reach the raised threshold), and such a query is re-run like one whose sample
-        // threshold was too high.  Randomly ordered rows fail with the sample's own probability (six sigma).
-        const uint32_t nb_q = (j->nblocks / 4) & ~1u;      // (even: the 4-bit screens walk whole 64-row pieces)
-        const double m2 = (double)j->k * 0.25;
-        const uint32_t k2 = (uint32_t)ceil(m2 + kn.pilot_sigmas * sqrt(m2) + 8.0);
-        // (not behind a predicted threshold: that one already sits tighter than what a quarter of the table can certify —
-        //  rank ~1.1 K against k2's ~1.18 K — so the split would only add a launch boundary)
-        const bool refine = j->screen && !j->l2 && !j->screen4 && !kn.no_refine && j->rows >= kn.refine_min_rows && nb_q >= 64 &&
-                            k2 < j->k && table_learned(t).prefix_failures < 2 && plan != kPredict;
-        if (refine) {
-            if ((rc = r.scan_range(0, nb_q, 1, false, true))) return rc;
-            if ((rc = r.refine(k2))) return rc;
-            PG_HIP(hipMemcpyAsync(rs.thr_ref, rs.thr, sizeof(float) * kMaxQueries, hipMemcpyDeviceToDevice, ctx->stream));
-            refined = true;
-            if ((rc = r.scan_range(nb_q, j->nblocks - nb_q, 1, false, true))) return rc;
-        } else if ((rc = r.scan_range(0, j->nblocks, 1, false, true))) {
-            return rc;
-        }
-        // (statistics: the candidates the full pass collected, before the select keeps K of each list — a predicted threshold that
-        //  admits many times K is no use to the table, recall_job_check)
-        // (select_kernel notes them in rs.cnt_seen)
-        if ((rc = r.refresh(j->k, true))) return rc;
-    } else {
-        // measured: growth 4 is best for the exact scan, 2 for the screened scan whose re-scoring
-        // gathers 512 B per staged candidate
-        r.exact_chunks = plan == kSafe && j->filter.col;
-        const double growth = kn.chunk_growth > 1.0 ? kn.chunk_growth : (j->screen && !r.exact_chunks ? 2.0 : 4.0);
-        if ((rc = r.grow_scan(j->nblocks, 1, j->k, growth, plan == kSafe))) return rc;
-    }
-    if (j->timers) PG_HIP(hipEventRecord((*j->events)[1], ctx->stream));
-    if ((rc = final_launch(ctx, rs.cand[r.cur], rs.cnt, rs.cap, j->nq, j->k, t->row_offset, j->d_out_rows,
-                           j->d_out_scores, j->d_count)))
-        return rc;
-    if (t->d_row_map) {                                // a filtered view answers with its source's row ids
-        const uint64_t n = (uint64_t)j->nq * j->k;
-        if ((rc = compact_map_rows_launch(ctx, j->d_out_rows, n, t->d_row_map, t->map_offset, t->rows))) return rc;
-    }
-    if (j->l2) {                                       // the lists were ranked by -d: the distances go out
-        const uint64_t n = (uint64_t)j->nq * j->k;
-        negate_kernel<<<(uint32_t)((n + 255) / 256), 256, 0, ctx->stream>>>(j->d_out_scores, n);
-        PG_HIP(hipGetLastError());
-    }
-    if (refined) {
-        // Two thresholds were in force during the full pass, so "K candidates were found" no longer proves that none
-        // of the true top K was rejected: the raised one must not exceed the K-th best score that came out — then at
-        // least K rows reach it, and every row it rejected is below K rows that were kept.  A query that fails reports
-        // zero items, which the plan check reads as "re-run this query" (the same path as a sample threshold that
-        // turned out too high).
-        refine_verify_kernel<<<1, kMaxQueries, 0, ctx->stream>>>(rs.thr, rs.thr_ref, j->d_count, j->nq);
-        PG_HIP(hipGetLastError());
-    }
-    if (observe) {
-        // the K-th best scores that came out (rs.thr after the last refresh) as quantiles of the model; queries that
-        // failed report 0 items and do not count.  The sums travel to the host with the status words.
-        double* stats = reinterpret_cast<double*>(t->derived.d_pred + 128 + 128 * 128);
-        pred_update_kernel<<<1, kMaxQueries, 0, ctx->stream>>>(rs.thr, rs.pred_ms, j->d_count, j->nq, j->k < j->rows ? j->k : j->rows, stats);
-        PG_HIP(hipGetLastError());
-    }
-    j->susp_stat = j->screen && (plan == kPilot || plan == kPredict) && r.last_full_screened;
-    j->stat_wide = j->susp_stat && !r.last_was_i4m;
-    {
-        // the status words in one block, one copy (they were six copies and two sums of their own: ~40 us of a small batch's step):
-        // [kI4mStatAt] the pairs a mid-batch pass's 4-bit stage let through (zero otherwise), [+ 1] the suspects its int8 stage / the
-        // int8 screen handed on in the full pass's last launch, [+ 3] what reached the exact re-scoring: the same, or the survivors
-        // of the refinement stage, [+ 4] the candidates the pass collected (select_kernel notes them before it keeps K)
-        const uint32_t* const susp = j->susp_stat ? (r.last_was_i4m ? rs.susp2_cnt : rs.susp_cnt) : nullptr;
-        status_pack_kernel<<<1, kMaxQueries, 0, ctx->stream>>>(
-            rs.overflow, j->nq, kRecOvfWord, observe ? reinterpret_cast<const uint32_t*>(t->derived.d_pred + 128 + 128 * 128) : nullptr,
-            j->susp_stat && r.last_was_i4m ? rs.susp2_cnt + kI4mMaxQueries : nullptr, susp, j->susp_stat && r.last_was_r2 ? rs.susp2w_cnt : susp,
-            j->susp_stat ? rs.cnt_seen : nullptr, rs.status);
-        PG_HIP(hipGetLastError());
-    }
-    if (j->d_out_count)
-        PG_HIP(hipMemcpyAsync(j->d_out_count, j->d_count, 4 * j->nq, hipMemcpyDeviceToDevice, ctx->stream));
-    PG_HIP(hipMemcpyAsync(j->h_status, rs.status, 4 * (size_t)kStatusCopyWords, hipMemcpyDeviceToHost, ctx->stream));
-    j->n_ev = r.n_ev;
-    j->refined = refined;
-    j->enqueued_plan = plan;
-    j->observed = observe;
-    j->next_plan++;
     return PG_OK;
 }
 
-int recall_job_check(RecallJob* j, bool* ok_out) {
-    pg_ctx* ctx = j->ctx;
-    const int plan = j->enqueued_plan;
-    float ms = 0.f;
-    if (j->timers) PG_HIP(hipEventElapsedTime(&ms, (*j->events)[0], (*j->events)[1]));
-    j->total_ms += ms;
-    for (uint32_t i = 1; j->timers && i < j->n_ev; ++i) {
-        PG_HIP(hipEventElapsedTime(&ms, (*j->events)[2 * i], (*j->events)[2 * i + 1]));
-        j->scan_ms += ms;
-        if (ctx->knobs.debug_scan) fprintf(stderr, "[pg] plan %d scan launch %u: %.3f ms\n", plan, i - 1, ms);
-    }
-    if (ctx->knobs.debug_scan && j->screen) {          // suspects of the last screened launch vs K (developer aid)
-        uint32_t sc[4] = {0, 0, 0, 0};
-        PG_HIP(hipMemcpy(sc, j->rs.susp_cnt, sizeof sc, hipMemcpyDeviceToHost));
-        fprintf(stderr, "[pg] plan %d last screened launch: suspects of queries 0-3: %u %u %u %u (K = %u)\n", plan, sc[0], sc[1], sc[2], sc[3], j->k);
-        if (j->t->derived.shadow_is_i8 && j->nq > 128 && scratch_peek(ctx, kSlotHitRecords)) {     // hit records: the fullest wave region, the spill pool
-            const uint32_t waves = (uint32_t)ctx->num_cus * 8u;
-            std::vector<uint32_t> rc(waves + 1);
-            PG_HIP(hipMemcpy(rc.data(), scratch_peek(ctx, kSlotHitRecords), rc.size() * 4, hipMemcpyDeviceToHost));
-            uint32_t mx = 0;
-            uint64_t sum = 0;
-            for (uint32_t w = 0; w < waves; ++w) { mx = rc[w] > mx ? rc[w] : mx; sum += rc[w]; }
-            fprintf(stderr, "[pg] plan %d last screened launch: hit records %llu in wave regions (fullest %u), %u in the spill pool\n", plan,
-                    (unsigned long long)sum, mx, rc[waves]);
-        }
-    }
-    j->scan_launches += j->n_ev - 1;
-    if (plan == kIndexPlan) return index_plan_check(j, ok_out);
-    bool ok = j->h_status[0] == 0;
-    j->failed.clear();
-    if (ok && (plan == kPilot || plan == kPredict)) {
-        const uint32_t have = j->filter.col ? j->rows_qualified : j->rows;
-        const uint32_t want = j->k < have ? j->k : have;
-        for (uint32_t q = 0; q < j->nq; ++q)
-            if (j->h_status[1 + q] != want) {
-                ok = false;
-                j->failed.push_back(q);
-            }
-    }
-    // what the verified batch teaches about the table: one locked section, the update rules are TableLearned's members
-    std::lock_guard<std::mutex> state_guard(g_table_state_mu);
-    TableLearned& ln = j->t->learned;
-    if (j->observed || plan == kPredict) {
-        if (j->observed && ln.pred_k == j->k) {
-            double st[5];
-            memcpy(st, j->h_status + kPredStatsAt, sizeof st);
-            ln.pred_report(st);
-        }
-        if (ctx->knobs.debug_scan && ln.pred_n > 0.0) {
-            const double mean = ln.pred_sum / ln.pred_n, var = ln.pred_sum2 / ln.pred_n - mean * mean;
-            fprintf(stderr, "[pg] plan %d %s: threshold model n = %.0f, z mean %.5f sd %.5f min %.5f (z_lo of this job %.5f)\n", plan,
-                    ok ? "held" : "FAILED", ln.pred_n, mean, var > 0 ? sqrt(var) : 0.0, ln.pred_min, j->z_lo);
-        }
-        if (plan == kPredict && !ok) {
-            // the model's threshold was too high for some query: this table stays on the pilot plan for a while (the
-            // whole batch re-runs when more than a handful failed — that must stay rare)
-            // and the model starts over: what it learnt no longer describes the queries
-            ln.pred_failed(true);
-            PG_HIP(hipMemsetAsync(j->t->derived.d_pred + 128 + 128 * 128, 0, 24, ctx->stream));
-        }
-    }
-    if (j->screen) {
-        // A screened plan that OVERFLOWED (not: a threshold a few queries' lists fell short of) says the rows crowd within the
-        // screen's error of the K-th scores — nearly collinear rows and queries along them: 1 % of 40 M rows within the int8
-        // margin of every query's threshold — and the chunked fallback plans would screen the same crowd chunk by chunk (256
-        // queries, 40 M such rows: 180 ms shuffled, 790 ms in ascending order, where the exact scan takes 30).  The job's
-        // remaining plans run on the exact scan; two such batches in a row and the table's next 64 start there.
-        if (j->h_status[0] != 0 && j->h_status[kI4mStatAt + 2] != 0 && ln.grow_rec_scale(ctx->knobs.max_rec_scale)) {
-            // the hit-record areas of the 256-query pass were too small for this table (clustered rows: a query's whole cluster sits
-            // within the screen's error of its K-th score — tens of suspects per answer where uniform rows have two): they grow, and
-            // the same plan runs again; the table keeps the larger areas
-            ctx->stats.recall_record_growths++;
-            if (j->next_plan > 0) j->next_plan--;
-            if (ctx->knobs.debug_scan) fprintf(stderr, "[pg] plan %d overflowed its hit-record areas: scale -> %u, again\n", plan, ln.rec_scale);
-        } else if (j->h_status[0] != 0) {
-            ctx->stats.recall_screen_overflows++;
-            j->screen = j->screen4 = j->screen4m = j->l2_per_row = false;
-            j->pred_observe = false;
-            // (... starting over at the pilot plan: on the exact scan the sample's threshold is as good as anywhere, while the
-            //  growing-chunk plans meet a table in ascending order with a flood of candidates per chunk)
-            for (int p = 0; p < j->n_plans; ++p)
-                if (j->plans[p] == kPilot && p < j->next_plan) j->next_plan = p;
-            ln.screen_overflowed();
-        } else if (ok) {
-            ln.screen_held();
-        }
-    }
-    // (the int8 screen's suspects per query: decides whether the table's passes get the refinement stage)
-    if (j->susp_stat && ok && j->stat_wide) ln.note_wide_susp((float)j->h_status[kI4mStatAt + 1] / (float)j->nq);
-    if (plan == kPredict && ok && j->susp_stat &&
-        (double)j->h_status[kI4mStatAt + 4] > ctx->knobs.predict_max_factor * (double)j->k * j->nq) {
-        // The predicted thresholds held but admitted far more than K rows per query as CANDIDATES (exact score >= threshold): on
-        // clustered rows the model's margin — a few per cent of the distance between a query's mean score and its K-th best — is
-        // many times the spread of the scores inside the query's cluster, every member of which then is a true candidate (20 per
-        // answer; the refinement stage cannot reject what really reaches the threshold, while the sample's threshold leaves 7-15
-        // suspects of which it keeps one).  Such a table goes back to the pilot plan; the model gets another try after an
-        // exponentially growing number of batches.
-        ln.pred_failed(false);
-        if (ctx->knobs.debug_scan) fprintf(stderr, "[pg] plan %d held with %.1f candidates per answer: pilot plan for the next %u batches\n", plan,
-                                           (double)j->h_status[kI4mStatAt + 4] / j->nq / j->k, ln.pred_backoff);
-    }
-    if (j->susp_stat && ok) {
-        ctx->stats.recall_rescored += j->h_status[kI4mStatAt + 3];
-        ctx->stats.recall_suspects += j->h_status[kI4mStatAt + 1];
-        ctx->stats.recall_suspect_queries += j->nq;
-        ctx->stats.recall_i4m_pairs += j->h_status[kI4mStatAt];
-    }
-    if (j->screen4m && j->susp_stat && ok) {
-        // what the 4-bit stage lets through per query decides up to which batch size it beats the int8 shadow (recall_job_prepare)
-        const float per_q = (float)j->h_status[kI4mStatAt] / (float)j->nq;
-        ln.note_i4m_pairs(per_q);
-        if (ctx->knobs.debug_scan) fprintf(stderr, "[pg] plan %d 4-bit stage: %.0f pairs per query (running %.0f)\n", plan, per_q, ln.i4m_pairs);
-    }
-    if (!ok) ctx->stats.recall_rescans++;
-    if (ok && plan == kPredict) ctx->stats.recall_predicted++;
-    // a refined threshold that fails verification on most of a batch says the head of the table is not representative
-    // (ordered rows): after two such batches the table's recalls stop refining (a hint, not state anyone relies on)
-    if (!ok && (plan == kPilot || plan == kPredict) && j->refined && j->failed.size() > j->nq / 2) ln.prefix_failures++;
-    *ok_out = ok;
+int screen_thr_launch(pg_ctx* ctx, const pg_table* t, const RecallScratch& rs, bool l2, bool l2_per_row) {
+    if (l2) screen_thr8_l2_kernel<<<1, kMaxQueries, 0, ctx->stream>>>(rs.thr, rs.eps, rs.qscale, rs.pred_ms, t->derived.s8, t->derived.max_norm,
+                                                                      rs.thr_screen, rs.thr_ref, l2_per_row ? 1 : 0);
+    else if (t->derived.shadow_is_i8) screen_thr8_kernel<<<1, kMaxQueries, 0, ctx->stream>>>(rs.thr, rs.eps, rs.qscale, t->derived.s8, rs.thr_screen);
+    else screen_thr_kernel<<<1, kMaxQueries, 0, ctx->stream>>>(rs.thr, rs.eps, t->derived.max_norm, rs.thr_screen);
+    PG_HIP(hipGetLastError());
     return PG_OK;
 }
 
-void recall_job_finish(RecallJob* j) {
-    pg_ctx* ctx = j->ctx;
-    ctx->stats.recall_calls++;
-    ctx->stats.recall_rows_scanned += j->scanned_rows;
-    if (j->timers) {                                   // (a batch without stage timers leaves the last direct call's figures)
-        ctx->stats.last_recall_ms = j->total_ms;
-        ctx->last_scan_ms = j->scan_ms;
-    }
-    ctx->last_scan_launches = j->scan_launches;
-    ctx->last_scan_bytes = j->scan_bytes;              // bytes the scan launches streamed (fp32 rows, int8 / bf16 / 4-bit shadow)
-}
-
-int recall_patch_failed_locked(RecallJob* j, uint32_t* counts) {
-    pg_ctx* ctx = j->ctx;
-    const std::vector<uint32_t> failed = j->failed;
-    RecallOpts o;
-    o.skip_pilot = true;
-    o.l2 = j->l2;
-    o.filter = j->filter.col ? &j->filter : nullptr;
-    o.exact_only = j->exact_only;
-    o.no_index = j->no_index;
-    for (uint32_t q : failed) {
-        uint32_t cnt = 0;
-        int rc;
-        if ((rc = recall_dev_locked(ctx, j->t, j->d_queries + (size_t)q * j->t->dim, 1, j->k, j->d_out_rows + (size_t)q * j->k,
-                                    j->d_out_scores + (size_t)q * j->k, &cnt, j->d_out_count ? j->d_out_count + q : nullptr, o)))
-            return rc;
-        counts[q] = cnt;
-    }
-    j->failed.clear();
-    return PG_OK;
-}
-
-// The exact re-scoring and the squared-Euclidean helpers for callers outside this file (index_search.hip): the same kernels, so a
-// row scored there carries the bits the table's own pass gives it.
+// The exact re-scoring and the squared-Euclidean helpers, for the plans and for index_search.hip: the same kernels, so a
+// row scored there carries the bits the table's own pass gives it.  blocks = 0: the table pass's own grid.
+constexpr uint32_t kRescoreBlocksPerQuery = 16;   // x 256 suspects per block per stride step
 int rescore_launch(pg_ctx* ctx, uint32_t dim, bool l2, const float* tab, const float* d_queries, const float* thr, const uint32_t* susp,
                    const uint32_t* susp_cnt, uint32_t scap, uint32_t* cnt, uint64_t* cand, uint32_t* overflow, uint32_t cap, uint32_t nq,
-                   uint32_t n_rows, const float* nx, const float* nqv, uint32_t blocks) {
-    const dim3 g(blocks, nq);
+                   uint32_t n_rows, const float* nx, const float* nqv, uint32_t blocks, const RowFilter& filter) {
+    const dim3 g(blocks ? blocks : kRescoreBlocksPerQuery, nq);
     if (l2 && dim == 64)
-        rescore_kernel<64, true><<<g, 256, 0, ctx->stream>>>(tab, d_queries, thr, susp, susp_cnt, cap, cnt, cand, overflow, scap, n_rows, nx, nqv);
+        rescore_kernel<64, true><<<g, 256, 0, ctx->stream>>>(tab, d_queries, thr, susp, susp_cnt, cap, cnt, cand, overflow, scap, n_rows, nx, nqv, filter);
     else if (l2 && dim == 128)
-        rescore_kernel<128, true><<<g, 256, 0, ctx->stream>>>(tab, d_queries, thr, susp, susp_cnt, cap, cnt, cand, overflow, scap, n_rows, nx, nqv);
+        rescore_kernel<128, true><<<g, 256, 0, ctx->stream>>>(tab, d_queries, thr, susp, susp_cnt, cap, cnt, cand, overflow, scap, n_rows, nx, nqv, filter);
     else if (!l2 && dim == 64)
-        rescore_kernel<64><<<g, 256, 0, ctx->stream>>>(tab, d_queries, thr, susp, susp_cnt, cap, cnt, cand, overflow, scap, n_rows);
+        rescore_kernel<64><<<g, 256, 0, ctx->stream>>>(tab, d_queries, thr, susp, susp_cnt, cap, cnt, cand, overflow, scap, n_rows, nullptr, nullptr, filter);
     else if (!l2 && dim == 128)
-        rescore_kernel<128><<<g, 256, 0, ctx->stream>>>(tab, d_queries, thr, susp, susp_cnt, cap, cnt, cand, overflow, scap, n_rows);
+        rescore_kernel<128><<<g, 256, 0, ctx->stream>>>(tab, d_queries, thr, susp, susp_cnt, cap, cnt, cand, overflow, scap, n_rows, nullptr, nullptr, filter);
     else if (!l2 && dim == 192)
-        rescore_kernel<192><<<g, 256, 0, ctx->stream>>>(tab, d_queries, thr, susp, susp_cnt, cap, cnt, cand, overflow, scap, n_rows);
+        rescore_kernel<192><<<g, 256, 0, ctx->stream>>>(tab, d_queries, thr, susp, susp_cnt, cap, cnt, cand, overflow, scap, n_rows, nullptr, nullptr, filter);
     else if (!l2 && dim == 256)
-        rescore_kernel<256><<<g, 256, 0, ctx->stream>>>(tab, d_queries, thr, susp, susp_cnt, cap, cnt, cand, overflow, scap, n_rows);
+        rescore_kernel<256><<<g, 256, 0, ctx->stream>>>(tab, d_queries, thr, susp, susp_cnt, cap, cnt, cand, overflow, scap, n_rows, nullptr, nullptr, filter);
     else {
         set_error("rescore: dim=%u unsupported%s", dim, l2 ? " (squared Euclidean: 64 or 128)" : "");
         return PG_ERR_UNSUPPORTED;

@@ -1,5 +1,5 @@
 // recall_entry.hip — the recalls as their callers see them: one verified batch of queries (recall_dev_locked: the plans of
-// recall.hip, enqueued, synchronised and checked), batches of batches, host staging, per-request exclusion lists, and the pg_*
+// recall_plan.hip, enqueued, synchronised and checked), batches of batches, host staging, per-request exclusion lists, and the pg_*
 // entry points of VectorRecall (service/recall/vector_recall.go:88-102), HologresVectorRecallV2
 // (hologres_vector_recall_v2.go:23,96-206), I2IVectorRecall (item_2_item_vector_racall.go:51-152) and OnlineVectorRecall
 // (online_vector_recall.go:73-155).  Host code only: every kernel is behind a function of common.hpp.

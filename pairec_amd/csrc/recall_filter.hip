@@ -129,7 +129,7 @@ __global__ void compact_map_rows_kernel(uint64_t* __restrict__ rows, uint64_t n,
     if (i < n && rows[i] < n_ids) rows[i] = row_offset + ids[rows[i]];      // (padding, UINT64_MAX, stays)
 }
 
-// the two kernels of this file that the plans of recall.hip launch (declared in recall_shared.hpp)
+// the two kernels of this file that the plans of recall_plan.hip launch (declared in recall_shared.hpp)
 int filter_count_launch(pg_ctx* ctx, const RowFilter& filter, uint64_t rows, unsigned long long* d_n) {
     filter_count_kernel<<<(uint32_t)ctx->num_cus * 8, 256, 0, ctx->stream>>>(filter, rows, d_n);
     PG_HIP(hipGetLastError());

@@ -51,7 +51,7 @@ struct TableDerived {
     int8_t* d8r = nullptr;
     float s8r = 0.0f, resid2 = 0.0f;   // its scale (s8 / 254), the measured upper bound of ||e2||
     bool r2_ok = false, r2_failed = false;
-    // Threshold predictor (recall.hip, built by recall_table.hip; DESIGN.md 4.1, plan 0): a Gaussian model of a query's scores over the rows — mean
+    // Threshold predictor (recall_plan.hip, built by recall_table.hip; DESIGN.md 4.1, plan 0): a Gaussian model of a query's scores over the rows — mean
     // vector and covariance from a row sample, built with the statistics — and the quantile z = (K-th best score −
     // mean) / sigma actually observed for the batches served so far (TableLearned::pred_*).  Once the observed z is tight, a
     // batch's first thresholds come from the model instead of a pilot sample.  A hint only: every plan is verified, results are exact.
@@ -72,7 +72,7 @@ struct TableDerived {
 struct TableLearned {
     float i4m_pairs = 0.0f;      // recall_i4m.hip: running average of the (row, query) pairs its 4-bit stage lets through, per query
     float wide_susp = 0.0f;      // running average of the int8 screen's suspects per query (passes without a 4-bit stage)
-    uint32_t rec_scale = 0;      // recall.hip: the 256-query pass's hit-record areas, x their default size (0 = 1; doubled when a batch overflows them)
+    uint32_t rec_scale = 0;      // recall_plan.hip: the 256-query pass's hit-record areas, x their default size (0 = 1; doubled when a batch overflows them)
     uint32_t prefix_failures = 0; // batches whose refined thresholds failed verification for most queries (ordered rows): two → no refinement
     uint32_t pred_k = 0;          // the K the threshold model's observations belong to
     double pred_n = 0.0, pred_sum = 0.0, pred_sum2 = 0.0, pred_min = 0.0, pred_total = 0.0;   // host copy as of the last verified batch

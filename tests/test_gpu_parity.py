@@ -714,7 +714,7 @@ def test_recall_adversarial_order(ctx):
 
 def test_recall_threshold_refinement_any_row_order(ctx):
     """The pilot plan raises its threshold after the first quarter of the full pass to the k2-th best candidate found
-    so far (csrc/recall.hip).  A contiguous prefix is not a random sample: forced on for a small table, with the rows
+    so far (csrc/recall_plan.hip).  A contiguous prefix is not a random sample: forced on for a small table, with the rows
     ordered so that the prefix holds none, all, or a disproportionate share of the best rows — results must be exact
     for every order, and for the random order no plan may fail."""
     rng = np.random.default_rng(41)
@@ -755,7 +755,7 @@ def test_recall_threshold_refinement_any_row_order(ctx):
 
 
 def test_recall_hit_records_with_every_lane_hit(ctx):
-    """The hit-record path of the > 128-query int8 screen (csrc/recall.hip, kRecBytes) under data that fills whole tiles
+    """The hit-record path of the > 128-query int8 screen (csrc/recall.hip at "Hit records"; kRecBytes: recall_plan_math.hpp) under data that fills whole tiles
     with suspects: zero queries (threshold 0: every row of every tile is a suspect of that query — more hit lanes per
     tile than the wave's LDS stage holds, regions and spill pool overflow, the plan falls back), blocks of identical rows
     (ties by row id inside one tile), a ragged row count (the last block's rows past the end must not be emitted).
@@ -784,7 +784,7 @@ def test_recall_hit_records_with_every_lane_hit(ctx):
 
 def test_recall_hit_records_spill_pool_on_a_table_whose_best_rows_sit_together(ctx, capfd):
     """More than 128 queries on the int8 shadow: the scan parks hit records (a lane's 16 accumulators + a tag) in a region
-    per wave and screen_decode_kernel turns them into the suspect lists (csrc/recall.hip, kRecBytes).  Rows of three times
+    per wave and screen_decode_kernel turns them into the suspect lists (csrc/recall.hip at "Hit records"; kRecBytes: recall_plan_math.hpp).  Rows of three times
     the norm packed into a few thousand rows: every query's best rows — and nearly all suspects — fall into a handful of
     wave regions, which overflow into the shared spill pool.  Answers must be exact, without a fallback to another plan."""
     rng = np.random.default_rng(77)
@@ -1672,7 +1672,7 @@ def test_recommend_one_call_equals_the_stages(ctx):
 
 def test_recall_threshold_model_predicts_then_backs_off_on_queries_it_does_not_describe(ctx):
     """After 1024 observed queries of one K the screening threshold comes from the table's threshold model instead of
-    the pilot sample (csrc/recall.hip): mean + z * sd of the query's score distribution, z learnt from
+    the pilot sample (csrc/recall_plan.hip): mean + z * sd of the query's score distribution, z learnt from
     the K-th best scores of verified batches.  Exactness never depends on it — a threshold that leaves fewer than K
     candidates fails the same verification as a sampled one.  Forced on for a small table: (1) it takes over and the
     answers stay the oracle's; (2) queries along a two-valued column, whose K-th best score sits far below what the

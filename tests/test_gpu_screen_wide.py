@@ -156,7 +156,7 @@ def test_dense_hits_zero_query_and_heavy_ties(ctx):
 def test_dense_hits_table_in_ascending_score_order(ctx):
     """Every later row beats every earlier one for every query, K = 10, 256 queries: each bounded chunk of the last plan makes
     every row a suspect of every query — 16 column blocks x 64 lanes = 1 024 records per 32-row block, which the per-wave
-    regions are sized for (recall.hip, floor_w)."""
+    regions are sized for (recall_plan_math.hpp, floor_w)."""
     rng = np.random.default_rng(1605)
     n = 150_000
     v = unit_rows(rng, 1)[0]
