@@ -498,6 +498,14 @@ def test_edge_cases(ctx, world):
         v_det = v.recall_topk(q[:8], k)
     same(w_att, w_det)
     same(v_att, v_det)
+    # ... and both equal the oracle on the admitted rows (2 M rows: two scan groups of the filter's block counts)
+    ids = np.flatnonzero(np.arange(N) % 3 == 1)
+    assert v.rows == ids.size
+    frow, fsc = o.recall_topk(tab[ids], q[:8], k)
+    frow = ids[frow.astype(np.int64)].astype(np.uint64)
+    for got in (w_att, v_att):
+        like_oracle(got, frow, fsc)
+        assert got[2].tolist() == [k] * 8
     v.destroy()
     feats.destroy()
 
