@@ -112,7 +112,8 @@ int pg_synchronize(pg_ctx* ctx);
  * more written rows than this share of the table are refreshed in full; a table's write log is dropped past it too); for
  * coalescers created afterwards "coalescer_max_exclude" (default 0, 0..4096: the longest list pg_coalescer_recall_exclude takes;
  * a value outside the range is PG_ERR_INVALID); for pg_cf_recall "cf_lds_max_pairs" (default and largest value 6144: a request
- * of at most this many (trigger, neighbour) pairs keeps its table in LDS, a larger one in global memory; 0 = always global);
+ * of at most this many (trigger, neighbour) pairs keeps its table in LDS, a larger one in global memory; 0 = always global;
+ * pg_x2i_recall reads the same knob for its (X, item) pairs and cuts it to 5120, what its smaller LDS table serves);
  * for pg_fanin_merge_dev "fanin_lds_max_cap" (default and largest value 8192 = PG_FANIN_LDS_MAX_CAP: a merge of at most this
  * many candidates per request keeps its table in LDS, a larger one in context scratch; 0 = always scratch).
  * value is parsed as a number. */
@@ -869,8 +870,8 @@ int pg_cf_recall_dev(pg_ctx* ctx, const pg_simtable* s, const uint32_t* d_trigge
  *             pg_rtu2i_expand over `s` (rows = the rows of its item table), byte for byte; the trigger lists stay in device
  *             memory and the two kernels follow each other on the stream with no host read-back between them.  _dev: events,
  *             opts->excl_rows and outputs are device memory; offsets, now and out_count host memory.  Returns synchronised.
- *   Not served (refused or out of scope): DiversityRules / PropertyFields (DiversityTriggers), the U2I2X2I, BE and
- *             FeatureStore DAOs, MergeMode "snake", the recall's cache line. */
+ *   Not served (refused or out of scope): DiversityRules / PropertyFields (DiversityTriggers), the BE and FeatureStore DAOs,
+ *             MergeMode "snake", the recall's cache line.  The U2I2X2I DAO is pg_rtu2i_x_recall below. */
 typedef struct pg_rtu2i pg_rtu2i;
 typedef struct {
     const char* weight_expression;
@@ -907,6 +908,109 @@ int pg_rtu2i_recall_dev(pg_ctx* ctx, pg_rtu2i* c, const pg_simtable* s, const ui
                         const double* d_event_play_time, const int64_t* d_event_time, const uint32_t* event_offsets,
                         const int64_t* now, uint32_t nq, uint32_t k, const pg_cf_opts* opts, uint64_t* d_out_rows,
                         double* d_out_scores, uint32_t* out_count);
+
+/* U2I2X2I recall over an X table resident in HBM (csrc/x2i.hip, csrc/x2i_host.hpp): trigger items -> their X
+ * values (category, author, tag list) -> the items listed under each X.  UserCollaborativeFilterRecall and RealTimeU2IRecall
+ * switch to this two-hop form as soon as a config names Item2XTable and X2ItemTable (NewUserCollaborativeDao,
+ * module/user_collaborative_dao.go:24-26).  Both DAOs (module/user_collaborative_u2i2x2i_hologres_dao.go:73-348,
+ * module/realtime_user2item_u2i2x2i_hologres_dao.go:94-270) split every trigger item's xKey on XDelimiter and add the trigger's
+ * preference to each X (xPreferScoreMap[x] += prefer, :196-211 / :161-175), walk the X2ItemTable row "id:score,id:score,..." of
+ * every distinct X, skip the ids that are trigger items (:311-315 / :242-246) and give every other entry the score xPrefer[x],
+ * times the entry's score if it has one.  The collaborative DAO sums the entries of an item in float64 and divides by the
+ * largest sum unless Normalization is "off" (mergeUserCollaborativeItemsResult, user_collaborative_dao.go:38-68); the realtime
+ * DAO sorts descending and keeps an item's first, largest entry (uniqItems, :262-263) and normalises nothing.  The order of the
+ * reference's float64 additions depends on goroutines and map iteration, and it has no test or golden vector for either DAO:
+ * the definition below fixes one order, and parity is against this restatement (reference parity unpinned, as for top-K).
+ *   Table     two CSR structures over the LOCAL rows of an item table `t` and n_x X values, which the caller numbers
+ *             0 .. n_x - 1 (its dictionary, as it numbers items by row): item -> X: offsets uint64[rows + 1], x_ids uint32[];
+ *             X -> items: offsets uint64[n_x + 1], item_rows uint32[] (local rows of `t`), scores float[].  Scores are stored
+ *             fp32 and widened exactly when used; an entry without a score in the reference is stored as 1.0 (prefer * 1.0 has
+ *             prefer's bits).  1 <= n_x < 2^32 - 1; `t` must outlive the X table, must not be a view and holds fewer than
+ *             2^32 - 1 rows.  Keys never uploaded have empty lists.
+ *   upload    pg_xtable_upload_item2x appends the X lists of `nrows` consecutive rows from row0, pg_xtable_upload_x2item the
+ *             item lists of `nx` consecutive X from x0; each side ascending and append-only (the first key at or behind the end
+ *             of the side's previous upload; keys skipped keep empty lists); offsets[n + 1] index the call's own arrays.
+ *             PG_ERR_INVALID, the table left as it was, for offsets that descend, an item's X list longer than 64, an X's item
+ *             list longer than 1024, an x id >= n_x, an item row >= rows, a non-finite score, or an id twice in one list
+ *             (duplicate-free lists are what makes the sums deterministic without floating-point atomics; the reference's "a
+ *             category appears several times" is across items, and that is served).  Synchronous; recalls of other contexts
+ *             wait.  Lock order: the context, the item table, then the X table.
+ *   stale     the table records t's generation at create: after pg_table_swap (or any other write) of `t` a recall returns
+ *             PG_ERR_INVALID with a message that names both generations.
+ *   recall    request q's triggers are trigger_rows / trigger_prefer [trigger_offsets[q] .. trigger_offsets[q + 1]) (local rows
+ *             of `t`; at most 256 per request — the collaborative DAO's shuffle cut of more than 200 triggers is the
+ *             caller's — nq <= 256, 1 <= k <= 16384; errors as pg_cf_recall).  The answer is DEFINED, bit for bit:
+ *               - hop 1: triggers in the order given, within a trigger its X list in stored order; the first trigger that
+ *                 names an X sets xPrefer[x] = prefer, every later one does xPrefer[x] = xPrefer[x] + prefer; a trigger row of
+ *                 UINT32_MAX or >= rows contributes nothing; a trigger that occurs twice contributes twice (a deviation from the
+ *                 SQL IN, which returns a row once: the caller's trigger map makes triggers distinct); the request's distinct
+ *                 X stand in order of first appearance; an X whose summed preference is not finite is dropped before hop 2
+ *                 (the reference's sort is undefined with NaN or Inf in it: pg_rtu2i_triggers' rule);
+ *               - hop 2: the X in that order, within an X its item list in stored order; an item that is ANY of the request's
+ *                 trigger rows is skipped — it takes no part in the sums and never counts towards the maximum;
+ *                 term = xPrefer[x] * (double)score (one rounding); sum rule: the first term of an item is its score, every
+ *                 later one does score = score + term; max rule: a later term replaces the score only when term > score;
+ *               - sum rule only: m = the largest score, found with > from 0; with normalize != 0 and m > 0 every score
+ *                 becomes score / m;
+ *               - order: score descending, then local row ascending (-0.0 ranks as 0.0 and keeps its bits); out_rows are
+ *                 global ids, the first k of that order; padding UINT64_MAX / -inf; out_count[q] = the valid count; a request
+ *                 with no triggers, no X, or nothing but trigger items answers 0.
+ *             Never cut silently: a request that reaches more than 1024 distinct X (counted before the non-finite ones are
+ *             dropped), or whose X lists (those of the X kept for hop 2, skipped trigger items included) hold more than 65536
+ *             (X, item) pairs in all, makes the call return PG_ERR_UNSUPPORTED; the message names the smallest such request and
+ *             the limit it broke (the X limit is tested first); that request answers 0, the other requests' outputs and
+ *             counts are written, the context stays usable.  trigger_prefer must be finite: the host-array forms check it
+ *             (PG_ERR_INVALID), for pg_x2i_recall_dev it is a precondition.
+ *   opts      NULL = {1, 0, NULL, NULL}.  normalize as in pg_cf_opts; max_rule != 0: the realtime DAO's reduction, normalize
+ *             ignored; excl_rows / excl_offsets: per-request exclusion lists with the meaning, limits and errors they have in
+ *             pg_cf_recall (global ids, at most 4096 per request, k + the longest list <= 16384).
+ *   tiers     a request of at most min("cf_lds_max_pairs", 5120) pairs keeps its item table in LDS — this kernel's table has
+ *             10240 slots, 2048 fewer than pg_cf_recall's, because the staged X (up to 1024) live in LDS beside it; above, in
+ *             the request's slice of context scratch.  Both tiers give the same bits.
+ *   _dev      trigger_rows, trigger_prefer, opts->excl_rows and the outputs are device memory; both offset arrays and
+ *             out_count (optional) are host memory.  Both forms return synchronised.
+ *   _host     pg_x2i_recall_host is the host statement over host CSR arrays (no context, no HIP): the same arguments, limits,
+ *             errors and bits; the CSR is held to what the uploads accept (PG_ERR_INVALID otherwise).
+ *   rtu2i     pg_rtu2i_x_recall[_dev]: the events of pg_rtu2i_recall[_dev], a pg_xtable in place of the pg_simtable; max_rule is
+ *             forced on.  Equal to pg_rtu2i_triggers (rows = the rows of the item table) followed by pg_x2i_recall with
+ *             max_rule = 1, byte for byte; the trigger lists stay in device memory and the two kernels follow each other on
+ *             the stream with no host read-back between them.
+ *   Memory    scratch of about 40 B x min(65536, rows) per request of the batch (the global tier's tables and the items to
+ *             order: 0.7 GB for 256 requests on a table of >= 65536 rows), in a slot of its own, kept by the context.
+ *   Not served: the shuffle cut of more than 200 triggers, string X values and ids (the caller holds the dictionaries),
+ *             "null" or empty ids in an X row, the BE and FeatureStore DAOs. */
+typedef struct pg_xtable pg_xtable;
+typedef struct {
+    int normalize;                 /* != 0: divide by the largest score when it is positive (sum rule only) */
+    int max_rule;                  /* != 0: an item keeps its largest term; normalize is ignored */
+    const uint64_t* excl_rows;     /* with excl_offsets: per-request exclusion lists; both NULL = none */
+    const uint32_t* excl_offsets;  /* host [nq + 1] */
+} pg_x2i_opts;
+int pg_xtable_create(pg_ctx* ctx, const pg_table* t, uint32_t n_x, pg_xtable** out);
+int pg_xtable_upload_item2x(pg_ctx* ctx, pg_xtable* s, uint64_t row0, uint64_t nrows, const uint64_t* offsets, const uint32_t* x_ids);
+int pg_xtable_upload_x2item(pg_ctx* ctx, pg_xtable* s, uint32_t x0, uint32_t nx, const uint64_t* offsets, const uint32_t* item_rows,
+                            const float* scores);
+/* any of the outputs may be NULL; generation = the item table's generation the lists belong to */
+int pg_xtable_info(const pg_xtable* s, uint64_t* rows, uint32_t* n_x, uint64_t* i2x_pairs, uint64_t* x2i_pairs, uint64_t* generation);
+int pg_xtable_destroy(pg_ctx* ctx, pg_xtable* s);
+int pg_x2i_recall(pg_ctx* ctx, const pg_xtable* s, const uint32_t* trigger_rows, const double* trigger_prefer,
+                  const uint32_t* trigger_offsets, uint32_t nq, uint32_t k, const pg_x2i_opts* opts, uint64_t* out_rows,
+                  double* out_scores, uint32_t* out_count);
+int pg_x2i_recall_dev(pg_ctx* ctx, const pg_xtable* s, const uint32_t* d_trigger_rows, const double* d_trigger_prefer,
+                      const uint32_t* trigger_offsets, uint32_t nq, uint32_t k, const pg_x2i_opts* opts, uint64_t* d_out_rows,
+                      double* d_out_scores, uint32_t* out_count);
+int pg_x2i_recall_host(uint64_t rows, uint64_t row_offset, uint32_t n_x, const uint64_t* i2x_off, const uint32_t* i2x_ids,
+                       const uint64_t* x2i_off, const uint32_t* x2i_rows, const float* x2i_scores, const uint32_t* trigger_rows,
+                       const double* trigger_prefer, const uint32_t* trigger_offsets, uint32_t nq, uint32_t k,
+                       const pg_x2i_opts* opts, uint64_t* out_rows, double* out_scores, uint32_t* out_count);
+int pg_rtu2i_x_recall(pg_ctx* ctx, pg_rtu2i* c, const pg_xtable* s, const uint32_t* event_rows, const uint16_t* event_code,
+                      const double* event_play_time, const int64_t* event_time, const uint32_t* event_offsets, const int64_t* now,
+                      uint32_t nq, uint32_t k, const pg_x2i_opts* opts, uint64_t* out_rows, double* out_scores,
+                      uint32_t* out_count);
+int pg_rtu2i_x_recall_dev(pg_ctx* ctx, pg_rtu2i* c, const pg_xtable* s, const uint32_t* d_event_rows, const uint16_t* d_event_code,
+                          const double* d_event_play_time, const int64_t* d_event_time, const uint32_t* event_offsets,
+                          const int64_t* now, uint32_t nq, uint32_t k, const pg_x2i_opts* opts, uint64_t* d_out_rows,
+                          double* d_out_scores, uint32_t* out_count);
 
 /* Fan-in + UniqueFilter on the device (csrc/fanin.hip): the answers of a request's recalls merged into one
  * candidate list without leaving device memory.  RecallService.GetItems (service/recall.go:53-153; the fan-in :126-150) runs

@@ -68,6 +68,8 @@ EXPORTS = [
     "pg_traffic_compile", "pg_traffic_free", "pg_traffic_num_targets", "pg_traffic_table", "pg_traffic_sort_host", "pg_traffic_sort_dev",
     "pg_traffic_sort",
     "pg_cold_create", "pg_cold_free", "pg_cold_recall_host", "pg_cold_recall_dev", "pg_cold_recall", "pg_cold_stats",
+    "pg_xtable_create", "pg_xtable_upload_item2x", "pg_xtable_upload_x2item", "pg_xtable_info", "pg_xtable_destroy",
+    "pg_x2i_recall", "pg_x2i_recall_dev", "pg_x2i_recall_host", "pg_rtu2i_x_recall", "pg_rtu2i_x_recall_dev",
 ]
 
 
@@ -140,6 +142,10 @@ class PgRecallExcludeOpts(C.Structure):
 
 class PgCfOpts(C.Structure):
     _fields_ = [("normalize", C.c_int), ("excl_rows", C.c_void_p), ("excl_offsets", C.c_void_p)]
+
+
+class PgX2iOpts(C.Structure):
+    _fields_ = [("normalize", C.c_int), ("max_rule", C.c_int), ("excl_rows", C.c_void_p), ("excl_offsets", C.c_void_p)]
 
 
 class PgRtU2IConf(C.Structure):
@@ -350,6 +356,16 @@ def load():
         "pg_rtu2i_expand_dev": [vp, vp, vp, vp, vp, u32, u32, P(PgCfOpts), vp, vp, vp],
         "pg_rtu2i_recall": [vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, P(PgCfOpts), vp, vp, vp],
         "pg_rtu2i_recall_dev": [vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, P(PgCfOpts), vp, vp, vp],
+        "pg_xtable_create": [vp, vp, u32, P(vp)],
+        "pg_xtable_upload_item2x": [vp, vp, u64, u64, vp, vp],
+        "pg_xtable_upload_x2item": [vp, vp, u32, u32, vp, vp, vp],
+        "pg_xtable_info": [vp, P(u64), P(u32), P(u64), P(u64), P(u64)],
+        "pg_xtable_destroy": [vp, vp],
+        "pg_x2i_recall": [vp, vp, vp, vp, vp, u32, u32, P(PgX2iOpts), vp, vp, vp],
+        "pg_x2i_recall_dev": [vp, vp, vp, vp, vp, u32, u32, P(PgX2iOpts), vp, vp, vp],
+        "pg_x2i_recall_host": [u64, u64, u32, vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, P(PgX2iOpts), vp, vp, vp],
+        "pg_rtu2i_x_recall": [vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, P(PgX2iOpts), vp, vp, vp],
+        "pg_rtu2i_x_recall_dev": [vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, P(PgX2iOpts), vp, vp, vp],
         "pg_fanin_merge_dev": [vp, P(PgFaninSource), u32, u32, vp, vp, vp, vp, vp, vp],
         "pg_recommend_candidates_dnn3_dev": [vp, vp, vp, vp, C.c_char_p, vp, u32, u32, vp, vp, vp, vp, vp, vp],
         "pg_trim_out_cap": [P(PgTrimRule), u32, u32, P(C.c_uint32)],

@@ -93,6 +93,7 @@ enum ScratchSlot : int {
     kSlotRtU2I = 32,         // rtu2i.hip: the staged event offsets and clocks of a trigger stage; in pg_rtu2i_recall_dev the trigger lists between its two launches (cf.hip's expansion reads them while kSlotCf is its own)
     kSlotCold = 33,          // coldstart.hip: the select's threshold state and digit histogram, per-block counts and their scan, the survivors and the ordered list of an ordered pool
     kSlotTraffic = 34,       // traffic.hip: the position keys, the compacted lists, the keys' order, the list lengths and the segment offsets of a traffic control sort
+    kSlotX2i = 35,           // x2i.hip: cf.hip's layout for a U2I2X2I recall — status and counts, staged offsets and lists, the global tier's tables, the items to order, the over-fetched answer (pg_rtu2i_x_recall's trigger lists are in kSlotRtU2I meanwhile)
     kSlotCount
 };
 

@@ -1702,6 +1702,153 @@ class SimTable:
         return counts
 
 
+def _pack_triggers(who, triggers, prefer):
+    """per-request trigger rows and preference scores → (rows uint32, prefer f64, offsets uint32 [nq + 1])"""
+    nq = len(triggers)
+    if len(prefer) != nq:
+        raise ValueError("%s: %d preference lists for %d requests" % (who, len(prefer), nq))
+    tr = [np.asarray(t, dtype=np.uint32).reshape(-1) for t in triggers]
+    pf = [np.asarray(p, dtype=np.float64).reshape(-1) for p in prefer]
+    if any(a.shape != b.shape for a, b in zip(tr, pf)):
+        raise ValueError("%s: every trigger needs one preference score" % who)
+    off = np.zeros(nq + 1, dtype=np.uint32)
+    off[1:] = np.cumsum([a.shape[0] for a in tr])
+    trc = np.ascontiguousarray(np.concatenate(tr)) if nq else np.zeros(0, dtype=np.uint32)
+    pfc = np.ascontiguousarray(np.concatenate(pf)) if nq else np.zeros(0, dtype=np.float64)
+    return trc, pfc, off
+
+
+def _x2i_opts(nq, normalize, max_rule, lists):
+    """pg_x2i_opts of host lists, and what must stay alive beside it"""
+    opts = _lib.PgX2iOpts(int(bool(normalize)), int(bool(max_rule)), None, None)
+    keep = None
+    if lists is not None:
+        keep = _pack_lists(lists, nq)
+        opts.excl_rows, opts.excl_offsets = keep[0].ctypes.data, keep[1].ctypes.data
+    return opts, keep
+
+
+def x2i_recall_host(rows: int, row_offset: int, n_x: int, i2x_off, i2x_ids, x2i_off, x2i_rows, x2i_scores, triggers, prefer, k: int,
+                    normalize: bool = True, max_rule: bool = False, lists=None):
+    """pg_x2i_recall_host: the host statement of the U2I2X2I recall over host CSR arrays (no context, no device)
+    → (rows [nq][k] uint64 global ids, scores [nq][k] f64, counts [nq])."""
+    nq = len(triggers)
+    trc, pfc, off = _pack_triggers("x2i_recall_host", triggers, prefer)
+    io = np.ascontiguousarray(i2x_off, dtype=np.uint64)
+    ii = np.ascontiguousarray(i2x_ids, dtype=np.uint32)
+    xo = np.ascontiguousarray(x2i_off, dtype=np.uint64)
+    xr = np.ascontiguousarray(x2i_rows, dtype=np.uint32)
+    xs = np.ascontiguousarray(x2i_scores, dtype=np.float32)
+    if io.shape[0] != rows + 1 or xo.shape[0] != n_x + 1 or xr.shape != xs.shape or int(io.max()) > ii.shape[0] or int(xo.max()) > xr.shape[0]:
+        raise ValueError("x2i_recall_host: the offsets must have rows + 1 / n_x + 1 entries and index their arrays")
+    opts, keep = _x2i_opts(nq, normalize, max_rule, lists)
+    out_rows = np.empty((nq, k), dtype=np.uint64)
+    scores = np.empty((nq, k), dtype=np.float64)
+    counts = np.zeros(nq, dtype=np.uint32)
+    _lib.check(_lib.load().pg_x2i_recall_host(int(rows), int(row_offset), int(n_x), _ptr(io), _ptr(ii), _ptr(xo), _ptr(xr), _ptr(xs), _ptr(trc),
+                                              _ptr(pfc), _ptr(off), nq, k, C.byref(opts), _ptr(out_rows), _ptr(scores), _ptr(counts)))
+    return out_rows, scores, counts
+
+
+class XTable:
+    """Item -> X and X -> item lists over the local rows of `table` and n_x X values (category, author, tag: the caller's
+    dictionary codes), resident in HBM (pg_xtable_*), and the U2I2X2I recall over them (pg_x2i_recall).  The table must outlive it."""
+
+    def __init__(self, ctx: Context, table: Table, n_x: int):
+        self.ctx, self.table = ctx, table
+        h = C.c_void_p()
+        _lib.check(ctx.L.pg_xtable_create(ctx.h, table.h, int(n_x), C.byref(h)))
+        self.h = h
+
+    def destroy(self):
+        if self.h:
+            _lib.check(self.ctx.L.pg_xtable_destroy(self.ctx.h, self.h))
+            self.h = None
+
+    def info(self) -> dict:
+        rows, n_x, ip, xp, gen = C.c_uint64(), C.c_uint32(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _lib.check(self.ctx.L.pg_xtable_info(self.h, C.byref(rows), C.byref(n_x), C.byref(ip), C.byref(xp), C.byref(gen)))
+        return {"rows": rows.value, "n_x": n_x.value, "i2x_pairs": ip.value, "x2i_pairs": xp.value, "generation": gen.value}
+
+    def upload_item2x(self, offsets, x_ids, row0: int = 0):
+        """append the X lists of len(offsets) - 1 consecutive rows from row0: row row0 + i has the X x_ids[offsets[i]:offsets[i + 1]]"""
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        ids = np.ascontiguousarray(x_ids, dtype=np.uint32)
+        if off.shape[0] < 1 or ids.ndim != 1 or int(off.max()) > ids.shape[0]:
+            raise ValueError("XTable.upload_item2x: offsets must index x_ids")
+        _lib.check(self.ctx.L.pg_xtable_upload_item2x(self.ctx.h, self.h, int(row0), off.shape[0] - 1, _ptr(off), _ptr(ids)))
+
+    def upload_x2item(self, offsets, item_rows, scores, x0: int = 0):
+        """append the item lists of len(offsets) - 1 consecutive X from x0: X x0 + i lists the local rows
+        item_rows[offsets[i]:offsets[i + 1]] with the scores scores[...] (1.0 where the reference's entry has none)"""
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        it = np.ascontiguousarray(item_rows, dtype=np.uint32)
+        sc = np.ascontiguousarray(scores, dtype=np.float32)
+        if off.shape[0] < 1 or it.shape != sc.shape or it.ndim != 1 or int(off.max()) > it.shape[0]:
+            raise ValueError("XTable.upload_x2item: offsets must index item_rows / scores of one length")
+        _lib.check(self.ctx.L.pg_xtable_upload_x2item(self.ctx.h, self.h, int(x0), off.shape[0] - 1, _ptr(off), _ptr(it), _ptr(sc)))
+
+    def x2i_recall(self, triggers, prefer, k: int, normalize: bool = True, max_rule: bool = False, lists=None):
+        """U2I2X2I: triggers[q] / prefer[q] = request q's trigger rows and preference scores; max_rule: the realtime DAO's
+        reduction (an item keeps its largest term, nothing normalised); lists[q] = the global row ids request q has seen.
+        → (rows [nq][k] uint64 global ids, scores [nq][k] f64, counts [nq]); the outputs of the other requests are
+        kept in self.last when a request is beyond a limit (PgError -4)."""
+        nq = len(triggers)
+        trc, pfc, off = _pack_triggers("x2i_recall", triggers, prefer)
+        opts, keep = _x2i_opts(nq, normalize, max_rule, lists)
+        rows = np.empty((nq, k), dtype=np.uint64)
+        scores = np.empty((nq, k), dtype=np.float64)
+        counts = np.zeros(nq, dtype=np.uint32)
+        self.last = (rows, scores, counts)
+        _lib.check(self.ctx.L.pg_x2i_recall(self.ctx.h, self.h, _ptr(trc), _ptr(pfc), _ptr(off), nq, k, C.byref(opts),
+                                            _ptr(rows), _ptr(scores), _ptr(counts)))
+        return rows, scores, counts
+
+    def x2i_recall_dev(self, d_triggers: int, d_prefer: int, trigger_offsets, k: int, d_out_rows: int, d_out_scores: int,
+                       normalize: bool = True, max_rule: bool = False, d_excl_rows: int = 0, excl_offsets=None):
+        """pg_x2i_recall_dev: triggers, preferences, lists and outputs are device addresses, the offsets host arrays → counts"""
+        off = np.ascontiguousarray(trigger_offsets, dtype=np.uint32)
+        nq = off.shape[0] - 1
+        opts = _lib.PgX2iOpts(int(bool(normalize)), int(bool(max_rule)), None, None)
+        if excl_offsets is not None:
+            xoff = np.ascontiguousarray(excl_offsets, dtype=np.uint32)
+            opts.excl_rows, opts.excl_offsets = d_excl_rows or None, xoff.ctypes.data
+        counts = np.zeros(nq, dtype=np.uint32)
+        _lib.check(self.ctx.L.pg_x2i_recall_dev(self.ctx.h, self.h, C.c_void_p(d_triggers), C.c_void_p(d_prefer), _ptr(off), nq, k,
+                                                C.byref(opts), C.c_void_p(d_out_rows), C.c_void_p(d_out_scores), _ptr(counts)))
+        return counts
+
+    def rtu2i_x_recall(self, conf: "RtU2I", rows, codes, play_time, times, now, k: int, lists=None):
+        """RealTimeU2IRecall over the X table (pg_rtu2i_x_recall): SimTable.rtu2i_recall's events, expanded through the two hops
+        with the max rule → (rows [nq][k] uint64 global ids, scores [nq][k] f64, counts [nq])."""
+        er, ec, ep, et, off, nw = _pack_events(rows, codes, play_time, times, now)
+        nq = len(rows)
+        opts, keep = _x2i_opts(nq, False, True, lists)
+        out_rows = np.empty((nq, k), dtype=np.uint64)
+        scores = np.empty((nq, k), dtype=np.float64)
+        counts = np.zeros(nq, dtype=np.uint32)
+        _lib.check(self.ctx.L.pg_rtu2i_x_recall(self.ctx.h, conf.h, self.h, _ptr(er), _ptr(ec), _ptr(ep) if ep is not None else None, _ptr(et),
+                                                _ptr(off), _ptr(nw), nq, k, C.byref(opts), _ptr(out_rows), _ptr(scores), _ptr(counts)))
+        return out_rows, scores, counts
+
+    def rtu2i_x_recall_dev(self, conf: "RtU2I", d_rows: int, d_codes: int, d_play_time: int, d_times: int, offsets, now, k: int,
+                           d_out_rows: int, d_out_scores: int, d_excl_rows: int = 0, excl_offsets=None):
+        """pg_rtu2i_x_recall_dev: events, lists and outputs are device addresses (d_play_time 0: none), offsets and now host
+        arrays; enqueue-only between its two kernels → counts"""
+        off = np.ascontiguousarray(offsets, dtype=np.uint32)
+        nw = np.ascontiguousarray(now, dtype=np.int64)
+        nq = off.shape[0] - 1
+        opts = _lib.PgX2iOpts(0, 1, None, None)
+        if excl_offsets is not None:
+            xoff = np.ascontiguousarray(excl_offsets, dtype=np.uint32)
+            opts.excl_rows, opts.excl_offsets = d_excl_rows or None, xoff.ctypes.data
+        counts = np.zeros(nq, dtype=np.uint32)
+        _lib.check(self.ctx.L.pg_rtu2i_x_recall_dev(self.ctx.h, conf.h, self.h, C.c_void_p(d_rows), C.c_void_p(d_codes), d_play_time or None,
+                                                    C.c_void_p(d_times), _ptr(off), _ptr(nw), nq, k, C.byref(opts), C.c_void_p(d_out_rows),
+                                                    C.c_void_p(d_out_scores), _ptr(counts)))
+        return counts
+
+
 class Index:
     """Exact IVF-partitioned index over a table (pg_index_*): the same results as the table's own recalls, bit for bit, with
     the lists that provably cannot reach a query's K-th score skipped.  The table must outlive the index."""
