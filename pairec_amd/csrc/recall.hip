@@ -817,7 +817,9 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void screen_kernel(ScreenArg
 #pragma unroll
             for (int c = 0; c < NQB; ++c) cut[c] = thr_s[c];
         } else {
-            const float nb = sqrtf(a.blk_norm2[cur_phys]) * 1.0002f;
+            // (the floor: a block of rows whose fp32 squares underflow reports a norm of zero, and components below 2^-126 keep an
+            //  absolute 2^-134 in bf16, not a relative 2^-9 — such a block gets the margin of a row of norm kScreenNormFloor)
+            const float nb = fmaxf(sqrtf(a.blk_norm2[cur_phys]), kScreenNormFloor) * 1.0002f;
 #pragma unroll
             for (int c = 0; c < NQB; ++c) {
                 const float v = __fmaf_rn(-eu[c], nb, thr_s[c]);

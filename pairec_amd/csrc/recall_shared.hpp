@@ -27,6 +27,10 @@ __device__ __forceinline__ uint32_t key_row(uint64_t key) {
 }
 
 constexpr float kScreenEps = 0.008f;
+// The bf16 screen's margin is kScreenEps ||q|| x the largest row norm of the block, read from an fp32 sum of squares.  Below this
+// norm that sum is not to be trusted — d squares that underflow lose up to d 2^-126 = 1.5e-36 of it, 1.5e-4 of 1e-32, which the
+// 1.0002 on the norm still covers; a sum of 1e-40 can have lost everything — and the screen takes the floor instead.
+constexpr float kScreenNormFloor = 1e-16f;
 static_assert(kRecQueries == (uint32_t)kMaxQueries, "recall_plan_math.hpp sizes the hit-record areas for kMaxQueries queries");
 
 // ---- the table pass (recall.hip) as the plans (recall_plan.hip) see it: the arguments of a launch and the launchers.  A launcher

@@ -1156,17 +1156,19 @@ def test_sort_split_over_the_chip(ctx):
     cases = ([5000], [8192], [1025, 0, 1, 511, 512, 513], [8192, 5000, 1536, 1537, 2, 4097, 8191, 1024],
              [5000] * 32, [3000 + 17 * i for i in range(96)], [8192] * 3 + [1] * 50)
     ctx.set_option("rank_sort_max", 0)
-    for sizes in cases:
-        segs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint32)
-        s = _sort_corner_scores(rng, segs, 1 if len(sizes) > 1 else None)
-        if len(sizes) == 1:
-            s[500:530] = 0.5                                   # equal scores across the first run boundary
-            s[1000:2100] = np.nan                              # NaN items across two boundaries
-        _check_sort(ctx, s, segs, sizes, "split")
-    before = ctx.stats().sort_split_calls
-    ctx.sort_scores(rng.random(5000), descending=True)
-    assert ctx.stats().sort_split_calls == before + 1
-    ctx.set_option("rank_sort_max", 32)
+    try:
+        for sizes in cases:
+            segs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint32)
+            s = _sort_corner_scores(rng, segs, 1 if len(sizes) > 1 else None)
+            if len(sizes) == 1:
+                s[500:530] = 0.5                                   # equal scores across the first run boundary
+                s[1000:2100] = np.nan                              # NaN items across two boundaries
+            _check_sort(ctx, s, segs, sizes, "split")
+        before = ctx.stats().sort_split_calls
+        ctx.sort_scores(rng.random(5000), descending=True)
+        assert ctx.stats().sort_split_calls == before + 1
+    finally:
+        ctx.set_option("rank_sort_max", 32)
     ctx.sort_scores(rng.random(5000), descending=True)          # one list of 5 000: counting is the shorter launch
     assert ctx.stats().sort_split_calls == before + 1
     ctx.sort_scores(rng.random(8 * 5000), np.arange(9, dtype=np.uint32) * 5000, descending=True)
