@@ -1776,6 +1776,97 @@ int pg_candidates_dimcap_dev(pg_ctx* ctx, const pg_features* fs, const pg_dimcap
 int pg_candidates_dimcap(pg_ctx* ctx, const pg_features* fs, const pg_dimcap_conf* conf, uint32_t n, const uint64_t* rows, const double* score,
                          const uint8_t* source, uint64_t* out_rows, double* out_score, uint8_t* out_source, uint32_t* out_count);
 
+/* User2ItemExposureBloomFilter on the device (csrc/bloom.hip, csrc/bloom_host.hpp).  The reference keeps one Bloom
+ * bitset per user in Redis (filter/user_item_exposure_bloom_filter.go; filter/bloomfilter/bloom.go, redis_bitset.go): Exists runs
+ * over the candidates before rank and drops the ones it finds (user_item_exposure_bloom_filter.go:92-98), Add (logHistory) runs
+ * over the returned page after the request.  Here a user's bitset is a slot of m bits in HBM, whatever the length of the history.
+ *   Hash      bloom.go:67-96 hashes a value to k locations through the user's HashFunc; the one it shows is bloom_test.go:13-29:
+ *             location j of key bytes d = murmur3_x86_32(d, seed_j) % m (spaolacci/murmur3 New32WithSeed), the seeds the primes
+ *             of bloom_test.go:14.  That hash is served, with configurable seeds.
+ *   Test      Exists is true when all k bits are set (redis_bitset.go:46-108); Set sets the k bits (redis_bitset.go:31-44).
+ *   Bits      bit N of a slot is Redis's bit N: byte N >> 3, mask 0x80 >> (N & 7).  pg_bloom_slot_write takes the raw value of a
+ *             user's Redis key as it is, pg_bloom_slot_read returns what can be written back.
+ *   estimate  pg_bloom_estimate restates EstimateParameters (bloom.go:40-45): m = ceil(n ln p / ln(1 / 2^ln 2)), k = uint(ln 2 m / n
+ *             + 0.5); PG_ERR_INVALID for n = 0 or p outside (0, 1).  A host function.
+ *   keys      pg_bloom_keys holds the bytes each item-table row is hashed by — what the user's GenerateFilterValue returns,
+ *             normally the item id string: offsets uint64 [rows + 1] into bytes.  Validated on the host, uploaded once: NULL
+ *             arguments and offsets that descend are PG_ERR_INVALID, a key longer than PG_BLOOM_MAX_KEY bytes PG_ERR_UNSUPPORTED.
+ *             A zero-length key is a key and hashes as murmur of nothing.  pg_bloom_keys_create_decimal builds the decimal text
+ *             of each id (strconv.Itoa, bloom_test.go:49-51) and goes through the same upload.
+ *   filter    pg_bloom_create: 1 <= m <= 2^32 - 1, 1 <= k <= PG_BLOOM_MAX_K (else PG_ERR_INVALID); seeds [k], NULL = the first k
+ *             primes; n_slots >= 1 bitsets of m bits at a 256-byte-aligned stride (pg_bloom_info's bytes per slot), zeroed.  The
+ *             mapping from a user to a slot is the host's, as the Redis key is in the reference.
+ *   slots     pg_bloom_slot_write: n <= ceil(m / 8) Redis-order bytes, the rest of the slot zeroed; bits at or above m in the last
+ *             byte are ignored and read back as 0.  pg_bloom_slot_read: n <= ceil(m / 8) bytes.  pg_bloom_slot_clear.  All three
+ *             synchronise; a slot >= n_slots or an n above ceil(m / 8) is PG_ERR_INVALID.
+ *   device    pg_bloom_exists_dev / pg_bloom_filter_dev / pg_bloom_add_dev: enqueued on the context's stream, no synchronisation,
+ *             nq <= 256, cap <= PG_TRIM_MAX_CAP.  d_slots [nq]: the slot of each request, PG_BLOOM_NO_SLOT = a user without
+ *             history; a slot >= n_slots is treated as PG_BLOOM_NO_SLOT and reads or writes nothing.  A padding entry (row
+ *             UINT64_MAX, or a position at or behind d_count[q]) is never kept and never added.  A row outside the key store has
+ *             no key: its Exists is false, so it is kept, and Add skips it.
+ *               exists   d_out_exists uint8 [nq][cap]: 1 where all k bits are set; padding positions 0.
+ *               filter   pg_item_state_filter_dev's argument list with b, keys, d_slots in place of the condition set, the feature
+ *                        store and the user values, its checks in its order, its outputs: the entries whose Exists is false, in
+ *                        order, with everything carried, d_out_count[q], padding behind the count as that stage pads.  With
+ *                        PG_BLOOM_NO_SLOT the real entries come out bit for bit as they went in.  Two launches.
+ *               add      sets the k bits of every real entry in its request's slot (atomic ORs on 32-bit words: two requests
+ *                        of one call may name one slot).  Stream order is the only fence: an add followed by a filter on the
+ *                        same stream sees the added bits.
+ *   one       pg_bloom_filter / pg_bloom_add / pg_bloom_exists: one request on host arrays (upload, run, download, synchronise);
+ *             n = 0 is an empty answer.
+ *   host      pg_bloom_*_host: the same answers over host arrays — bitsets [n_slots][ceil(m / 8)] Redis bytes, the keys as
+ *             offsets + bytes — with the same checks; no context, no device.  pg_bloom_murmur3_host is the hash itself.  They are
+ *             what tests compare the kernels with; the library falls back to them for nothing.
+ *   Kernels   probe: one lane per candidate, grid (cap / 256, nq); the lane loads its key, mixes each 4-byte block once for all
+ *             seeds, folds and finalises per seed, issues its k word loads together and writes one keep ballot per wave into
+ *             context scratch.  compaction: one workgroup per request walks the ballots (block_rank.hpp, cand_carry, cand_pad).
+ *             add: the probe's grid and arithmetic, then atomic ORs.
+ *   Not here  RedisBloomFilter (BF.MADD, RedisBloom's own hash); rotation (bloom_rotation.go: a host that rotates holds several
+ *             pg_bloom objects, adds to all and tests the active one); keys longer than PG_BLOOM_MAX_KEY bytes. */
+#define PG_BLOOM_MAX_KEY 64
+#define PG_BLOOM_MAX_K 16
+#define PG_BLOOM_NO_SLOT 0xFFFFFFFFu
+typedef struct pg_bloom pg_bloom;
+typedef struct pg_bloom_keys pg_bloom_keys;
+int pg_bloom_estimate(uint64_t n, double p, uint64_t* m, uint32_t* k);
+int pg_bloom_murmur3_host(const uint8_t* bytes, uint64_t n, uint32_t seed, uint32_t* out);
+int pg_bloom_keys_create(pg_ctx* ctx, uint64_t rows, const uint64_t* offsets, const uint8_t* bytes, pg_bloom_keys** out);
+int pg_bloom_keys_create_decimal(pg_ctx* ctx, uint64_t rows, const int64_t* ids, pg_bloom_keys** out);
+int pg_bloom_keys_free(pg_ctx* ctx, pg_bloom_keys* keys);
+int pg_bloom_create(pg_ctx* ctx, uint64_t m, uint32_t k, const uint32_t* seeds, uint32_t n_slots, pg_bloom** out);
+int pg_bloom_free(pg_ctx* ctx, pg_bloom* b);
+int pg_bloom_info(const pg_bloom* b, uint64_t* m, uint32_t* k, uint32_t* n_slots, uint64_t* slot_bytes);
+int pg_bloom_slot_write(pg_ctx* ctx, pg_bloom* b, uint32_t slot, const uint8_t* bytes, uint64_t n);
+int pg_bloom_slot_read(pg_ctx* ctx, const pg_bloom* b, uint32_t slot, uint8_t* bytes, uint64_t n);
+int pg_bloom_slot_clear(pg_ctx* ctx, pg_bloom* b, uint32_t slot);
+int pg_bloom_exists_dev(pg_ctx* ctx, const pg_bloom* b, const pg_bloom_keys* keys, uint32_t nq, uint32_t cap, const uint64_t* d_rows,
+                        const uint32_t* d_count, const uint32_t* d_slots, uint8_t* d_out_exists);
+int pg_bloom_filter_dev(pg_ctx* ctx, const pg_bloom* b, const pg_bloom_keys* keys, uint32_t nq, uint32_t cap, const uint64_t* d_rows,
+                        const double* d_score, const uint8_t* d_source, const uint32_t* d_count, const double* d_planes_f64, uint32_t n_f64,
+                        const uint32_t* d_source_mask, const float* d_planes_f32, uint32_t n_f32, const uint32_t* d_slots,
+                        uint64_t* d_out_rows, double* d_out_score, uint8_t* d_out_source, double* d_out_planes_f64,
+                        uint32_t* d_out_source_mask, float* d_out_planes_f32, uint32_t* d_out_count);
+int pg_bloom_add_dev(pg_ctx* ctx, pg_bloom* b, const pg_bloom_keys* keys, uint32_t nq, uint32_t cap, const uint64_t* d_rows,
+                     const uint32_t* d_count, const uint32_t* d_slots);
+int pg_bloom_exists(pg_ctx* ctx, const pg_bloom* b, const pg_bloom_keys* keys, uint32_t n, const uint64_t* rows, uint32_t slot,
+                    uint8_t* out_exists);
+int pg_bloom_filter(pg_ctx* ctx, const pg_bloom* b, const pg_bloom_keys* keys, uint32_t n, const uint64_t* rows, const double* score,
+                    const uint8_t* source, uint32_t slot, uint64_t* out_rows, double* out_score, uint8_t* out_source, uint32_t* out_count);
+int pg_bloom_add(pg_ctx* ctx, pg_bloom* b, const pg_bloom_keys* keys, uint32_t n, const uint64_t* rows, uint32_t slot);
+int pg_bloom_exists_host(uint64_t m, uint32_t k, const uint32_t* seeds, uint32_t n_slots, const uint8_t* bitsets, uint64_t key_rows,
+                         const uint64_t* key_offsets, const uint8_t* key_bytes, uint32_t nq, uint32_t cap, const uint64_t* rows,
+                         const uint32_t* count, const uint32_t* slots, uint8_t* out_exists);
+int pg_bloom_add_host(uint64_t m, uint32_t k, const uint32_t* seeds, uint32_t n_slots, uint8_t* bitsets, uint64_t key_rows,
+                      const uint64_t* key_offsets, const uint8_t* key_bytes, uint32_t nq, uint32_t cap, const uint64_t* rows,
+                      const uint32_t* count, const uint32_t* slots);
+int pg_bloom_filter_host(uint64_t m, uint32_t k, const uint32_t* seeds, uint32_t n_slots, const uint8_t* bitsets, uint64_t key_rows,
+                         const uint64_t* key_offsets, const uint8_t* key_bytes, uint32_t nq, uint32_t cap, const uint64_t* rows,
+                         const double* score, const uint8_t* source, const uint32_t* count, const double* planes_f64, uint32_t n_f64,
+                         const uint32_t* source_mask, const float* planes_f32, uint32_t n_f32, const uint32_t* slots, uint64_t* out_rows,
+                         double* out_score, uint8_t* out_source, double* out_planes_f64, uint32_t* out_source_mask, float* out_planes_f32,
+                         uint32_t* out_count);
+int pg_bloom_slot_write_host(uint64_t m, uint32_t n_slots, uint8_t* bitsets, uint32_t slot, const uint8_t* bytes, uint64_t n);
+
 /* DiversityAdjustCountFilter on the device: quotas per expression class (csrc/classcut.hip).  The fourth reference
  * filter of the slot between UniqueFilter and RankService.Rank (service/user_recommend.go:105-137): every AdjustCountConfig gives
  * its quota not to a recall but to the items for which a govaluate expression over the item's features is true

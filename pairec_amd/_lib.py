@@ -70,6 +70,10 @@ EXPORTS = [
     "pg_cold_create", "pg_cold_free", "pg_cold_recall_host", "pg_cold_recall_dev", "pg_cold_recall", "pg_cold_stats",
     "pg_xtable_create", "pg_xtable_upload_item2x", "pg_xtable_upload_x2item", "pg_xtable_info", "pg_xtable_destroy",
     "pg_x2i_recall", "pg_x2i_recall_dev", "pg_x2i_recall_host", "pg_rtu2i_x_recall", "pg_rtu2i_x_recall_dev",
+    "pg_bloom_estimate", "pg_bloom_murmur3_host", "pg_bloom_keys_create", "pg_bloom_keys_create_decimal", "pg_bloom_keys_free",
+    "pg_bloom_create", "pg_bloom_free", "pg_bloom_info", "pg_bloom_slot_write", "pg_bloom_slot_read", "pg_bloom_slot_clear",
+    "pg_bloom_exists_dev", "pg_bloom_filter_dev", "pg_bloom_add_dev", "pg_bloom_exists", "pg_bloom_filter", "pg_bloom_add",
+    "pg_bloom_exists_host", "pg_bloom_add_host", "pg_bloom_filter_host", "pg_bloom_slot_write_host",
 ]
 
 
@@ -366,6 +370,28 @@ def load():
         "pg_x2i_recall_host": [u64, u64, u32, vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, P(PgX2iOpts), vp, vp, vp],
         "pg_rtu2i_x_recall": [vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, P(PgX2iOpts), vp, vp, vp],
         "pg_rtu2i_x_recall_dev": [vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, P(PgX2iOpts), vp, vp, vp],
+        "pg_bloom_estimate": [u64, C.c_double, P(u64), P(u32)],
+        "pg_bloom_murmur3_host": [vp, u64, u32, P(u32)],
+        "pg_bloom_keys_create": [vp, u64, vp, vp, P(vp)],
+        "pg_bloom_keys_create_decimal": [vp, u64, vp, P(vp)],
+        "pg_bloom_keys_free": [vp, vp],
+        "pg_bloom_create": [vp, u64, u32, vp, u32, P(vp)],
+        "pg_bloom_free": [vp, vp],
+        "pg_bloom_info": [vp, P(u64), P(u32), P(u32), P(u64)],
+        "pg_bloom_slot_write": [vp, vp, u32, vp, u64],
+        "pg_bloom_slot_read": [vp, vp, u32, vp, u64],
+        "pg_bloom_slot_clear": [vp, vp, u32],
+        "pg_bloom_exists_dev": [vp, vp, vp, u32, u32, vp, vp, vp, vp],
+        "pg_bloom_filter_dev": [vp, vp, vp, u32, u32, vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp],
+        "pg_bloom_add_dev": [vp, vp, vp, u32, u32, vp, vp, vp],
+        "pg_bloom_exists": [vp, vp, vp, u32, vp, u32, vp],
+        "pg_bloom_filter": [vp, vp, vp, u32, vp, vp, vp, u32, vp, vp, vp, vp],
+        "pg_bloom_add": [vp, vp, vp, u32, vp, u32],
+        "pg_bloom_exists_host": [u64, u32, vp, u32, vp, u64, vp, vp, u32, u32, vp, vp, vp, vp],
+        "pg_bloom_add_host": [u64, u32, vp, u32, vp, u64, vp, vp, u32, u32, vp, vp, vp],
+        "pg_bloom_filter_host": [u64, u32, vp, u32, vp, u64, vp, vp, u32, u32, vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, vp, vp,
+                                 vp, vp, vp],
+        "pg_bloom_slot_write_host": [u64, u32, vp, u32, vp, u64],
         "pg_fanin_merge_dev": [vp, P(PgFaninSource), u32, u32, vp, vp, vp, vp, vp, vp],
         "pg_recommend_candidates_dnn3_dev": [vp, vp, vp, vp, C.c_char_p, vp, u32, u32, vp, vp, vp, vp, vp, vp],
         "pg_trim_out_cap": [P(PgTrimRule), u32, u32, P(C.c_uint32)],

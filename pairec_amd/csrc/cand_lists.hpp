@@ -1,6 +1,6 @@
 // cand_lists.hpp — the candidate lists of nq requests, stated once for the stages that read and write them: the trim (trim.hip),
-// the blend (blend.hip), the class cut (classcut.hip), the V2 quota cut (trim2.hip), ItemStateFilter (cond.hip) and the value
-// cap (dimcap.hip); the fan-in
+// the blend (blend.hip), the class cut (classcut.hip), the V2 quota cut (trim2.hip), ItemStateFilter (cond.hip), the value
+// cap (dimcap.hip) and the exposure Bloom filter (bloom.hip); the fan-in
 // (fanin.hip), which makes them, takes the constants.  Three parts: what the kernels and the host statements
 // move (CandIn / CandOut, cand_carry, cand_pad, the sort order and the bit cast); what an entry point is handed (CandCall) and
 // the checks every stage runs over it, each in its own order; the staging of a one-request call on host arrays (Staged).

@@ -1131,6 +1131,85 @@ class Context:
                                                None if src is None else _ptr(o_src), C.byref(cnt)))
         return o_r, o_s, o_src, cnt.value
 
+    # ---- User2ItemExposureBloomFilter -----------------------------------------------------------------------
+    def bloom_exists_dev(self, bloom, keys, nq: int, cap: int, d_rows: int, d_count: int, d_slots: int, d_out_exists: int) -> None:
+        """pg_bloom_exists_dev: device addresses (d_count 0 = absent), d_out_exists [nq][cap] uint8.  Enqueued on the context's
+        stream: synchronize() before reading."""
+        v = lambda p: C.c_void_p(p or None)                                          # noqa: E731
+        _lib.check(self.L.pg_bloom_exists_dev(self.h, bloom.h, keys.h, nq, cap, v(d_rows), v(d_count), v(d_slots), v(d_out_exists)))
+
+    def bloom_add_dev(self, bloom, keys, nq: int, cap: int, d_rows: int, d_count: int, d_slots: int) -> None:
+        """pg_bloom_add_dev: device addresses (d_count 0 = absent).  Enqueued on the context's stream."""
+        v = lambda p: C.c_void_p(p or None)                                          # noqa: E731
+        _lib.check(self.L.pg_bloom_add_dev(self.h, bloom.h, keys.h, nq, cap, v(d_rows), v(d_count), v(d_slots)))
+
+    def bloom_filter_dev(self, bloom, keys, nq: int, cap: int, d_rows: int, d_score: int, d_source: int, d_count: int, d_planes_f64: int,
+                         n_f64: int, d_source_mask: int, d_planes_f32: int, n_f32: int, d_slots: int, d_out_rows: int, d_out_score: int,
+                         d_out_source: int, d_out_planes_f64: int, d_out_source_mask: int, d_out_planes_f32: int, d_out_count: int) -> None:
+        """pg_bloom_filter_dev: device addresses as item_state_filter_dev (0 = absent; an output is required exactly where its
+        input is given), d_slots [nq] uint32, outputs [nq][cap].  Enqueued on the context's stream: synchronize() before reading."""
+        self._list_call(self.L.pg_bloom_filter_dev, (bloom.h, keys.h), nq, cap,
+                        (d_rows, d_score, d_source, d_count, d_planes_f64, n_f64, d_source_mask, d_planes_f32, n_f32, d_out_rows, d_out_score,
+                         d_out_source, d_out_planes_f64, d_out_source_mask, d_out_planes_f32, d_out_count), (d_slots,))
+
+    @staticmethod
+    def _bloom_lists(who, rows, slots, count):
+        r = np.ascontiguousarray(rows, dtype=np.uint64)
+        if r.ndim != 2:
+            raise ValueError("%s: rows is [nq][cap]" % who)
+        sl = np.ascontiguousarray(slots, dtype=np.uint32)
+        cnt = None if count is None else np.ascontiguousarray(count, dtype=np.uint32)
+        if sl.shape != (r.shape[0],) or (cnt is not None and cnt.shape != sl.shape):
+            raise ValueError("%s: slots and count are [nq]" % who)
+        return r, sl, cnt
+
+    def bloom_exists(self, bloom, keys, rows, slots, count=None) -> np.ndarray:
+        """Exists on host arrays (pg_bloom_exists_dev): rows [nq][cap] u64, slots [nq] u32 (BLOOM_NO_SLOT: no history), count [nq]
+        → [nq][cap] uint8"""
+        r, sl, cnt = self._bloom_lists("bloom_exists", rows, slots, count)
+        nq, cap = r.shape
+        return self._cand_run([r, cnt, sl], [np.empty((nq, cap), np.uint8)],
+                              lambda d_in, d_out: self.bloom_exists_dev(bloom, keys, nq, cap, d_in[0], d_in[1], d_in[2], d_out[0]))[0]
+
+    def bloom_add(self, bloom, keys, rows, slots, count=None) -> None:
+        """Add on host arrays (pg_bloom_add_dev), synchronised"""
+        r, sl, cnt = self._bloom_lists("bloom_add", rows, slots, count)
+        nq, cap = r.shape
+        self._cand_run([r, cnt, sl], [], lambda d_in, d_out: self.bloom_add_dev(bloom, keys, nq, cap, d_in[0], d_in[1], d_in[2]))
+
+    def bloom_filter(self, bloom, keys, slots, rows, score, source=None, count=None, planes_f64=None, source_mask=None, planes_f32=None):
+        """The exposure filter on host arrays (pg_bloom_filter_dev): the arrays of candidates_trim, slots [nq] u32 → (rows, score,
+        source, planes_f64, source_mask, planes_f32, count), [nq][cap] each, None where the input was None."""
+        nq, cap, ins, outs, n64, n32 = _cand_arrays("bloom_filter", lambda cap: cap, rows, score, source, count, planes_f64, source_mask,
+                                                    planes_f32)
+        sl = np.ascontiguousarray(slots, dtype=np.uint32)
+        if sl.shape != (nq,):
+            raise ValueError("bloom_filter: slots is [nq]")
+        return self._cand_run(ins + [sl], outs, lambda d_in, d_out: self.bloom_filter_dev(
+            bloom, keys, nq, cap, d_in[0], d_in[1], d_in[2], d_in[3], d_in[4], n64, d_in[5], d_in[6], n32, d_in[7], *d_out))
+
+    def bloom_exists_one(self, bloom, keys, rows, slot: int) -> np.ndarray:
+        """pg_bloom_exists: one request on host arrays → [n] uint8"""
+        r = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1)
+        out = np.empty(r.shape[0], dtype=np.uint8)
+        _lib.check(self.L.pg_bloom_exists(self.h, bloom.h, keys.h, r.shape[0], _ptr(r), int(slot), _ptr(out)))
+        return out
+
+    def bloom_add_one(self, bloom, keys, rows, slot: int) -> None:
+        """pg_bloom_add: one request on host arrays (logHistory over the returned page)"""
+        r = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1)
+        _lib.check(self.L.pg_bloom_add(self.h, bloom.h, keys.h, r.shape[0], _ptr(r), int(slot)))
+
+    def bloom_filter_one(self, bloom, keys, rows, score, slot: int, source=None):
+        """pg_bloom_filter: one request on host arrays → (rows [n], score [n], source [n] | None, count)"""
+        r = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1)
+        sc = np.ascontiguousarray(score, dtype=np.float64).reshape(-1)
+        src = None if source is None else np.ascontiguousarray(source, dtype=np.uint8).reshape(-1)
+        o_r, o_s, o_src, cnt = np.empty_like(r), np.empty_like(sc), None if src is None else np.empty_like(src), C.c_uint32()
+        _lib.check(self.L.pg_bloom_filter(self.h, bloom.h, keys.h, r.shape[0], _ptr(r), _ptr(sc), None if src is None else _ptr(src), int(slot),
+                                          _ptr(o_r), _ptr(o_s), None if src is None else _ptr(o_src), C.byref(cnt)))
+        return o_r, o_s, o_src, cnt.value
+
     # ---- DiversityAdjustCountFilter: quotas per expression class ---------------------------------------
     def classcut_masks_dev(self, cc, fs, nq: int, cap: int, d_rows: int, d_score: int, d_source: int, d_count: int, d_out_masks: int) -> None:
         """pg_classcut_masks_dev: device addresses (0 = absent) → [nq][cap] uint8, bit c = member of class c.  One launch on the
@@ -2235,6 +2314,154 @@ class Where:
             r_, s_, c_ = rows[s:e], scores[s:e], counts[s:e]
             _lib.check(fn(ctx.h, over, feats.h, self.h, 1 if l2 else 0, _ptr(q[s:e]), e - s, k, _ptr(r_), _ptr(s_), _ptr(c_)))
         return rows, scores, counts
+
+
+BLOOM_MAX_KEY, BLOOM_MAX_K, BLOOM_NO_SLOT = 64, 16, 0xFFFFFFFF
+
+
+def bloom_estimate(n: int, p: float) -> Tuple[int, int]:
+    """pg_bloom_estimate: EstimateParameters (bloom.go:40-45) → (m, k).  A host function: no context, no device."""
+    m, k = C.c_uint64(), C.c_uint32()
+    _lib.check(_lib.load().pg_bloom_estimate(int(n), float(p), C.byref(m), C.byref(k)))
+    return m.value, k.value
+
+
+def bloom_murmur3_host(data: bytes, seed: int = 0) -> int:
+    """pg_bloom_murmur3_host: murmur3_x86_32 of the bytes with a seed."""
+    out = C.c_uint32()
+    a = np.frombuffer(bytes(data), dtype=np.uint8)
+    _lib.check(_lib.load().pg_bloom_murmur3_host(_ptr(a) if a.size else None, a.size, int(seed) & 0xFFFFFFFF, C.byref(out)))
+    return out.value
+
+
+def bloom_pack_keys(keys):
+    """a sequence of bytes objects → (offsets uint64 [rows + 1], bytes uint8): what pg_bloom_keys_create and the host statements take"""
+    off = np.zeros(len(keys) + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([len(k) for k in keys], dtype=np.uint64)
+    return off, np.frombuffer(b"".join(bytes(k) for k in keys), dtype=np.uint8).copy()
+
+
+def _bloom_host_args(who, m, k, seeds, bitsets, key_offsets, key_bytes, rows, count, slots):
+    bs = np.ascontiguousarray(bitsets, dtype=np.uint8)
+    if bs.ndim != 2:
+        raise ValueError("%s: bitsets is [n_slots][ceil(m / 8)] bytes" % who)
+    sd = None if seeds is None else np.ascontiguousarray(seeds, dtype=np.uint32)
+    if sd is not None and sd.shape != (k,):
+        raise ValueError("%s: one seed per hash" % who)
+    ko, kb = np.ascontiguousarray(key_offsets, dtype=np.uint64), np.ascontiguousarray(key_bytes, dtype=np.uint8)
+    r = np.ascontiguousarray(rows, dtype=np.uint64)
+    if r.ndim != 2:
+        raise ValueError("%s: rows is [nq][cap]" % who)
+    cnt = None if count is None else np.ascontiguousarray(count, dtype=np.uint32)
+    sl = np.ascontiguousarray(slots, dtype=np.uint32)
+    if sl.shape != (r.shape[0],) or (cnt is not None and cnt.shape != sl.shape):
+        raise ValueError("%s: slots and count are [nq]" % who)
+    return bs, sd, ko, kb, r, cnt, sl
+
+
+def bloom_exists_host(m: int, k: int, seeds, bitsets, key_offsets, key_bytes, rows, slots, count=None) -> np.ndarray:
+    """pg_bloom_exists_host: bitsets [n_slots][ceil(m / 8)] Redis bytes, the keys as bloom_pack_keys gives them, rows [nq][cap],
+    slots [nq] → [nq][cap] uint8.  No context, no device."""
+    bs, sd, ko, kb, r, cnt, sl = _bloom_host_args("bloom_exists_host", m, k, seeds, bitsets, key_offsets, key_bytes, rows, count, slots)
+    out = np.empty(r.shape, dtype=np.uint8)
+    v = lambda a: None if a is None else _ptr(a)                                     # noqa: E731
+    _lib.check(_lib.load().pg_bloom_exists_host(int(m), int(k), v(sd), bs.shape[0], _ptr(bs), ko.shape[0] - 1, _ptr(ko), _ptr(kb), r.shape[0],
+                                                r.shape[1], _ptr(r), v(cnt), _ptr(sl), _ptr(out)))
+    return out
+
+
+def bloom_add_host(m: int, k: int, seeds, bitsets: np.ndarray, key_offsets, key_bytes, rows, slots, count=None) -> None:
+    """pg_bloom_add_host: sets the bits in `bitsets` (a C-contiguous uint8 array [n_slots][ceil(m / 8)]) in place."""
+    if not (isinstance(bitsets, np.ndarray) and bitsets.dtype == np.uint8 and bitsets.flags.c_contiguous and bitsets.flags.writeable):
+        raise TypeError("bloom_add_host: bitsets is a writable C-contiguous uint8 array")
+    bs, sd, ko, kb, r, cnt, sl = _bloom_host_args("bloom_add_host", m, k, seeds, bitsets, key_offsets, key_bytes, rows, count, slots)
+    v = lambda a: None if a is None else _ptr(a)                                     # noqa: E731
+    _lib.check(_lib.load().pg_bloom_add_host(int(m), int(k), v(sd), bs.shape[0], _ptr(bs), ko.shape[0] - 1, _ptr(ko), _ptr(kb), r.shape[0],
+                                             r.shape[1], _ptr(r), v(cnt), _ptr(sl)))
+
+
+def bloom_filter_host(m: int, k: int, seeds, bitsets, key_offsets, key_bytes, slots, rows, score, source=None, count=None, planes_f64=None,
+                      source_mask=None, planes_f32=None):
+    """pg_bloom_filter_host: the filter on host arrays by the library's host statement; the lists and the result as
+    Context.bloom_filter."""
+    nq, cap, ins, outs, n64, n32 = _cand_arrays("bloom_filter_host", lambda cap: cap, rows, score, source, count, planes_f64, source_mask,
+                                                planes_f32)
+    bs, sd, ko, kb, r, cnt, sl = _bloom_host_args("bloom_filter_host", m, k, seeds, bitsets, key_offsets, key_bytes, ins[0], ins[3], slots)
+    v = lambda a: None if a is None else _ptr(a)                                     # noqa: E731
+    _lib.check(_lib.load().pg_bloom_filter_host(int(m), int(k), v(sd), bs.shape[0], _ptr(bs), ko.shape[0] - 1, _ptr(ko), _ptr(kb), nq, cap,
+                                                v(ins[0]), v(ins[1]), v(ins[2]), v(ins[3]), v(ins[4]), n64, v(ins[5]), v(ins[6]), n32, _ptr(sl),
+                                                *[v(a) for a in outs]))
+    return tuple(outs)
+
+
+def bloom_slot_write_host(m: int, bitsets: np.ndarray, slot: int, data) -> None:
+    """pg_bloom_slot_write_host: pg_bloom_slot_write on a host bitset array [n_slots][ceil(m / 8)], in place."""
+    if not (isinstance(bitsets, np.ndarray) and bitsets.dtype == np.uint8 and bitsets.flags.c_contiguous and bitsets.ndim == 2):
+        raise TypeError("bloom_slot_write_host: bitsets is a C-contiguous uint8 array [n_slots][ceil(m / 8)]")
+    d = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+    _lib.check(_lib.load().pg_bloom_slot_write_host(int(m), bitsets.shape[0], _ptr(bitsets), int(slot), _ptr(d) if d.size else None, d.size))
+
+
+class BloomKeys:
+    """pg_bloom_keys: the bytes each item-table row is hashed by (the item id string), uploaded once.  keys: a sequence of bytes
+    objects, or ids=[...] for the decimal text of integer ids."""
+
+    def __init__(self, ctx: "Context", keys=None, ids=None):
+        self.ctx, self.L = ctx, ctx.L
+        h = C.c_void_p()
+        if ids is not None:
+            a = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+            _lib.check(self.L.pg_bloom_keys_create_decimal(ctx.h, a.shape[0], _ptr(a) if a.size else None, C.byref(h)))
+            self.rows = a.shape[0]
+        else:
+            off, data = bloom_pack_keys(keys)
+            _lib.check(self.L.pg_bloom_keys_create(ctx.h, off.shape[0] - 1, _ptr(off), _ptr(data) if data.size else None, C.byref(h)))
+            self.rows = off.shape[0] - 1
+        self.h = h
+
+    def free(self):
+        if self.h:
+            _lib.check(self.L.pg_bloom_keys_free(self.ctx.h, self.h))
+            self.h = None
+
+
+class Bloom:
+    """pg_bloom: n_slots Bloom bitsets of m bits in HBM, k murmur3 hashes per key (seeds None: the first k primes)."""
+
+    def __init__(self, ctx: "Context", m: int, k: int, n_slots: int, seeds=None):
+        self.ctx, self.L = ctx, ctx.L
+        sd = None if seeds is None else np.ascontiguousarray(seeds, dtype=np.uint32)
+        if sd is not None and sd.shape != (k,):
+            raise ValueError("Bloom: one seed per hash")
+        h = C.c_void_p()
+        _lib.check(self.L.pg_bloom_create(ctx.h, int(m), int(k), _ptr(sd) if sd is not None else None, int(n_slots), C.byref(h)))
+        self.h = h
+        self.m, self.k, self.n_slots = int(m), int(k), int(n_slots)
+        self.nbytes = (self.m + 7) // 8
+
+    def free(self):
+        if self.h:
+            _lib.check(self.L.pg_bloom_free(self.ctx.h, self.h))
+            self.h = None
+
+    def info(self) -> dict:
+        m, k, n, b = C.c_uint64(), C.c_uint32(), C.c_uint32(), C.c_uint64()
+        _lib.check(self.L.pg_bloom_info(self.h, C.byref(m), C.byref(k), C.byref(n), C.byref(b)))
+        return {"m": m.value, "k": k.value, "n_slots": n.value, "slot_bytes": b.value}
+
+    def slot_write(self, slot: int, data) -> None:
+        """pg_bloom_slot_write: up to ceil(m / 8) Redis-order bytes (a user's Redis value as it is); the rest of the slot is zeroed"""
+        d = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+        _lib.check(self.L.pg_bloom_slot_write(self.ctx.h, self.h, int(slot), _ptr(d) if d.size else None, d.size))
+
+    def slot_read(self, slot: int, n: Optional[int] = None) -> np.ndarray:
+        """pg_bloom_slot_read → the slot's first n (default: all ceil(m / 8)) Redis-order bytes"""
+        out = np.empty(self.nbytes if n is None else int(n), dtype=np.uint8)
+        _lib.check(self.L.pg_bloom_slot_read(self.ctx.h, self.h, int(slot), _ptr(out) if out.size else None, out.size))
+        return out
+
+    def slot_clear(self, slot: int) -> None:
+        _lib.check(self.L.pg_bloom_slot_clear(self.ctx.h, self.h, int(slot)))
 
 
 class ColdStart:
