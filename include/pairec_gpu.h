@@ -1012,6 +1012,97 @@ int pg_rtu2i_x_recall_dev(pg_ctx* ctx, pg_rtu2i* c, const pg_xtable* s, const ui
                           const int64_t* now, uint32_t nq, uint32_t k, const pg_x2i_opts* opts, uint64_t* d_out_rows,
                           double* d_out_scores, uint32_t* out_count);
 
+/* List recall over a hot table resident in HBM (csrc/hot.hip, csrc/hot_host.hpp): UserGroupHotRecall,
+ * UserGlobalHotRecall and UserTopicRecall as one primitive with three modes.  UserGroupHotRecall
+ * (module/user_group_hot_recall_hologres_dao.go:47-140) expands the user's trigger id into one or several trigger_ids, reads each
+ * one's item_ids row — entries "id", "id:source" or "id:source:score" —, concatenates them, sorts by score descending and cuts to
+ * RecallCount.  UserGlobalHotRecall (module/user_global_hot_recall_hologres_dao.go:50-149) reads one list of the same entries,
+ * gives an entry without a score rand.Float64(), and sorts and cuts only a list longer than RecallCount (:144-148).
+ * UserTopicRecall (module/user_topic_mysql_dao.go:58-138) gives each of the user's topics int(value / total * RecallCount)
+ * places and concatenates the heads of the topics' article lists in stored order.  The reference's sort.Sort is unstable and
+ * its draws are Go's math/rand stream: the definition below fixes the ties and the draws, and parity is against this
+ * restatement (reference parity unpinned, as for top-K).
+ *   Table     a CSR over n_triggers trigger indices, which the caller numbers 0 .. n_triggers - 1 (its dictionary of trigger_id /
+ *             topic strings, as it numbers items by row) and the LOCAL rows of an item table `t`: offsets uint64[n_triggers + 1],
+ *             item_rows uint32[], scores double[] (utils.ToFloat yields float64, and hot scores are counts that fp32 would merge
+ *             into ties), source uint8[]: bits 0-6 = an index into the caller's RetrieveId dictionary, 0 = the recall's own name
+ *             (the one-part form, or an empty second part); PG_HOT_UNSCORED (bit 7) set = the entry carries no score (the one-
+ *             and two-part forms).  1 <= n_triggers < 2^32 - 1; `t` must outlive the hot table and must not be a view.  Triggers
+ *             never uploaded have empty lists.
+ *   upload    pg_hottable_upload appends the lists of `ntrig` consecutive triggers from trig0, ascending and append-only (trig0 at
+ *             or behind the end of the previous upload; triggers skipped keep empty lists); offsets[ntrig + 1] index the call's
+ *             own arrays.  PG_ERR_INVALID, the table left as it was, for offsets that descend, a list longer than
+ *             PG_HOT_MAX_ENTRIES, an item row >= rows, a non-finite score, a source of 0xFF (the output padding), an entry marked
+ *             unscored whose score is not 0, or a table of 2^40 entries.  A row twice in a list is allowed: the reference keeps
+ *             duplicates and nothing here accumulates.  Synchronous: it waits for everything enqueued on the device first.  Lock
+ *             order: the context, the item table, then the hot table.
+ *   stale     the table records t's generation at create: after pg_table_swap (or any other write) of `t` a recall returns
+ *             PG_ERR_INVALID with a message that names both generations.
+ *   recall    request q's triggers are triggers [trigger_offsets[q] .. trigger_offsets[q + 1]) (trigger_value beside them, read
+ *             in PG_HOT_TOPIC only, else it may be NULL).  The answer is DEFINED, bit for bit:
+ *               - concatenation: the request's triggers in the order given, within a trigger its entries in stored order;
+ *                 position p counts from 0 over it, n is its length.  A trigger of UINT32_MAX or >= n_triggers contributes
+ *                 nothing (a trigger_id without a row); a trigger given twice contributes twice.
+ *               - scores: a scored entry has its stored score, bits preserved (-0.0, subnormals).  An unscored entry has 0.0 in
+ *                 PG_HOT_GROUP and PG_HOT_TOPIC (module.NewItem), and in PG_HOT_GLOBAL the draw
+ *                 u(q, p) = (double)(x >> 11) * 2^-53, x = the splitmix64 finaliser — x ^= x >> 30, x *= 0xBF58476D1CE4E5B9,
+ *                 x ^= x >> 27, x *= 0x94D049BB133111EB, x ^= x >> 31, as pg_mix_sort's draw — of
+ *                 seed[q] + 0x9E3779B97F4A7C15 * (1 + p) in uint64 arithmetic (seed NULL = 0).
+ *               - order: score descending, then p ascending; -0.0 ranks as 0.0.
+ *               - PG_HOT_GROUP: always ordered, then cut to min(k, n).
+ *               - PG_HOT_GLOBAL: with n <= k the concatenation as stored, draws included, not sorted; with n > k the order
+ *                 above, cut to k.
+ *               - PG_HOT_TOPIC: never sorted.  v_j = trigger_value[j], 0 taken as 0.5 (:75-77); total = their sequential fp64
+ *                 sum in trigger order over ALL the request's triggers, absent ones included (the reference counts a topic it
+ *                 later finds no articles for); take_j = (int64)((v_j / total) * (double)k) — two roundings, truncation;
+ *                 trigger j contributes its first min(take_j, len_j) entries; the concatenation is cut to k.  The random pick
+ *                 of TopicNum topics (:94-100) is the caller's.
+ *               - out_rows [nq][k]: row_offset + local row, then UINT64_MAX; out_scores [nq][k]: fp64, then -inf; out_source
+ *                 [nq][k]: bits 0-6 of the entry's source, then PG_HOT_PAD_SOURCE; out_count[q] = min(k, n) (TOPIC: of the cut
+ *                 concatenation).  Rows and scores are a pg_fanin_source with score_f64 = 1.
+ *   Limits    1 <= nq <= 256 and a known mode (else PG_ERR_INVALID); at most 256 triggers per request and 1 <= k <= 16384
+ *             (PG_ERR_UNSUPPORTED); n <= PG_HOT_MAX_ENTRIES per request: beyond it the call is refused with PG_ERR_UNSUPPORTED
+ *             naming the smallest such request.  PG_HOT_TOPIC: every value finite and >= 0, else PG_ERR_INVALID naming request
+ *             and trigger.  Every refusal is made on the host — the table keeps a host copy of its offsets — with nothing
+ *             enqueued and the context left usable.
+ *   _dev      triggers, trigger_value and trigger_offsets are HOST memory (user features, at most 256 per request; staged with
+ *             one copy on the context's stream); d_seed (NULL = 0) and the outputs are device memory, d_out_source and
+ *             d_out_count optional.  Enqueue-only on the context's stream, one launch, no synchronisation (the scratch-growth
+ *             exception of pg_fanin_merge_dev applies).
+ *   pg_hot_recall  host arrays throughout (seed [nq] or NULL): upload, run, download, synchronise.
+ *   _host     pg_hot_recall_host is the host statement over host CSR arrays (no context, no HIP): the same arguments, limits,
+ *             errors and bits; the CSR is held to what the upload accepts (PG_ERR_INVALID otherwise).
+ *   Kernel    one workgroup of 1024 lanes per request; a request of at most 8192 padded entries orders its 16-byte records
+ *             in LDS, a longer one in its slice of context scratch (16 B x the padded count); TOPIC, and GLOBAL with n <= k,
+ *             write straight from the gather.  Both tiers give the same bits.
+ *   Not here  exclusion lists (the reference filters after the recall: pg_bloom_filter_dev and the count filters take the
+ *             answer); the per-entry source through pg_fanin_merge_dev (the fan-in attributes a list to one source; the plane
+ *             is the caller's); the feature-store, tablestore and Redis DAO variants' text formats; ContextItemRecall. */
+#define PG_HOT_GROUP 0
+#define PG_HOT_GLOBAL 1
+#define PG_HOT_TOPIC 2
+#define PG_HOT_MAX_ENTRIES 65536u
+#define PG_HOT_UNSCORED 0x80u
+#define PG_HOT_PAD_SOURCE 0xFFu
+typedef struct pg_hottable pg_hottable;
+int pg_hottable_create(pg_ctx* ctx, const pg_table* t, uint32_t n_triggers, pg_hottable** out);
+int pg_hottable_upload(pg_ctx* ctx, pg_hottable* h, uint32_t trig0, uint32_t ntrig, const uint64_t* offsets, const uint32_t* item_rows,
+                       const double* scores, const uint8_t* source);
+/* any of the outputs may be NULL; generation = the item table's generation the lists belong to */
+int pg_hottable_info(const pg_hottable* h, uint64_t* rows, uint32_t* n_triggers, uint64_t* pairs, uint32_t* triggers_uploaded,
+                     uint64_t* generation);
+int pg_hottable_destroy(pg_ctx* ctx, pg_hottable* h);
+int pg_hot_recall_dev(pg_ctx* ctx, const pg_hottable* h, int mode, const uint32_t* triggers, const double* trigger_value,
+                      const uint32_t* trigger_offsets, const uint64_t* d_seed, uint32_t nq, uint32_t k, uint64_t* d_out_rows,
+                      double* d_out_scores, uint8_t* d_out_source, uint32_t* d_out_count);
+int pg_hot_recall(pg_ctx* ctx, const pg_hottable* h, int mode, const uint32_t* triggers, const double* trigger_value,
+                  const uint32_t* trigger_offsets, const uint64_t* seed, uint32_t nq, uint32_t k, uint64_t* out_rows,
+                  double* out_scores, uint8_t* out_source, uint32_t* out_count);
+int pg_hot_recall_host(uint64_t rows, uint64_t row_offset, uint32_t n_triggers, const uint64_t* offsets, const uint32_t* item_rows,
+                       const double* scores, const uint8_t* source, int mode, const uint32_t* triggers, const double* trigger_value,
+                       const uint32_t* trigger_offsets, const uint64_t* seed, uint32_t nq, uint32_t k, uint64_t* out_rows,
+                       double* out_scores, uint8_t* out_source, uint32_t* out_count);
+
 /* Fan-in + UniqueFilter on the device (csrc/fanin.hip): the answers of a request's recalls merged into one
  * candidate list without leaving device memory.  RecallService.GetItems (service/recall.go:53-153; the fan-in :126-150) runs
  * every recall of the scene's category and concatenates what they return; UniqueFilter (filter/unique_filter.go:26-49) dedups

@@ -74,6 +74,8 @@ EXPORTS = [
     "pg_bloom_create", "pg_bloom_free", "pg_bloom_info", "pg_bloom_slot_write", "pg_bloom_slot_read", "pg_bloom_slot_clear",
     "pg_bloom_exists_dev", "pg_bloom_filter_dev", "pg_bloom_add_dev", "pg_bloom_exists", "pg_bloom_filter", "pg_bloom_add",
     "pg_bloom_exists_host", "pg_bloom_add_host", "pg_bloom_filter_host", "pg_bloom_slot_write_host",
+    "pg_hottable_create", "pg_hottable_upload", "pg_hottable_info", "pg_hottable_destroy",
+    "pg_hot_recall_dev", "pg_hot_recall", "pg_hot_recall_host",
 ]
 
 
@@ -392,6 +394,13 @@ def load():
         "pg_bloom_filter_host": [u64, u32, vp, u32, vp, u64, vp, vp, u32, u32, vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, vp, vp,
                                  vp, vp, vp],
         "pg_bloom_slot_write_host": [u64, u32, vp, u32, vp, u64],
+        "pg_hottable_create": [vp, vp, u32, P(vp)],
+        "pg_hottable_upload": [vp, vp, u32, u32, vp, vp, vp, vp],
+        "pg_hottable_info": [vp, P(u64), P(u32), P(u64), P(u32), P(u64)],
+        "pg_hottable_destroy": [vp, vp],
+        "pg_hot_recall_dev": [vp, vp, C.c_int, vp, vp, vp, vp, u32, u32, vp, vp, vp, vp],
+        "pg_hot_recall": [vp, vp, C.c_int, vp, vp, vp, vp, u32, u32, vp, vp, vp, vp],
+        "pg_hot_recall_host": [u64, u64, u32, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, u32, u32, vp, vp, vp, vp],
         "pg_fanin_merge_dev": [vp, P(PgFaninSource), u32, u32, vp, vp, vp, vp, vp, vp],
         "pg_recommend_candidates_dnn3_dev": [vp, vp, vp, vp, C.c_char_p, vp, u32, u32, vp, vp, vp, vp, vp, vp],
         "pg_trim_out_cap": [P(PgTrimRule), u32, u32, P(C.c_uint32)],

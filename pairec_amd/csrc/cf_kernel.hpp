@@ -1,18 +1,18 @@
 // cf_kernel.hpp — the device code that cf.hip (U2I2I, RealTimeU2I's expansion: DESIGN.md 4.1l, 4.1v) and x2i.hip (U2I2X2I: 4.1y)
 // run: the keyed fp64 reduction of staged lists in an open-addressed table (cf_accumulate), the sort records and their bitonic
 // sort through LDS (cf_finish, cf_sort), the cut and the padding, and the two small kernels of the exclusion path and the
-// uploads.  One workgroup of kCfThreads lanes per request.  Included by those two files only.
+// uploads.  One workgroup of kCfThreads lanes per request.  Included by those two files only; the sort itself is cf_sort.hpp's,
+// which hot.hip (list recall: 4.1aa) includes alone.
 #pragma once
 #include "cf_shared.hpp"
 #include "block_rank.hpp"
+#include "cf_sort.hpp"
 
 namespace pg {
 namespace {
 
-constexpr uint32_t kCfThreads = 1024;            // one workgroup per request; a list of at most kCfMaxList entries is one entry per lane
 constexpr uint32_t kCfMaxList = 1024;
 constexpr uint32_t kCfMaxPairs = 65536;          // a request beyond it is reported, never cut
-constexpr uint32_t kCfSortChunk = 8192;          // 16-byte sort records ordered in LDS at a time (128 KiB, the table's bytes reused)
 constexpr uint32_t kCfMaxDepth = 16384;
 
 struct CfArgs {
@@ -40,8 +40,6 @@ struct CfArgs {
     uint32_t* out_count;           // [nq]
     uint32_t* status;              // the smallest request beyond kCfMaxPairs (UINT32_MAX: none)
 };
-
-__device__ inline bool cf_less(const ulonglong2& a, const ulonglong2& b) { return a.x < b.x || (a.x == b.x && a.y < b.y); }
 
 // what cf_accumulate asks before an entry may claim a slot: cf.hip keeps every entry, x2i.hip drops the request's own triggers
 struct CfNoSkip {
@@ -130,55 +128,6 @@ __device__ void cf_accumulate(const CfArgs& a, uint32_t* keys, double* acc, uint
     // (positive doubles order as their bits)
     if ((tid & (kWave - 1)) == 0 && lmax > 0.0) atomicMax(max_bits, (unsigned long long)__double_as_longlong(lmax));
     __syncthreads();
-}
-
-// g[base .. base + n) through LDS: the bitonic network's steps of the merges k_lo .. k_hi whose partner distance is below n
-// (n a power of two <= kCfSortChunk; directions follow the global index).
-__device__ void cf_sort_lds(ulonglong2* g, ulonglong2* s, uint32_t base, uint32_t n, uint32_t k_lo, uint32_t k_hi) {
-    const uint32_t tid = threadIdx.x;
-    for (uint32_t i = tid; i < n; i += kCfThreads) s[i] = g[base + i];
-    __syncthreads();
-    for (uint32_t k = k_lo; k <= k_hi && k; k <<= 1) {
-        for (uint32_t j = min(k >> 1, n >> 1); j > 0; j >>= 1) {
-            for (uint32_t p = tid; p < (n >> 1); p += kCfThreads) {
-                const uint32_t i = ((p & ~(j - 1)) << 1) | (p & (j - 1)), l = i | j;
-                const bool up = ((base + i) & k) == 0;
-                const ulonglong2 x = s[i], y = s[l];
-                if (cf_less(y, x) == up) {
-                    s[i] = y;
-                    s[l] = x;
-                }
-            }
-            __syncthreads();
-        }
-    }
-    for (uint32_t i = tid; i < n; i += kCfThreads) g[base + i] = s[i];
-    __syncthreads();
-}
-
-// ascending sort of g[0 .. n), n a power of two: chunks of kCfSortChunk in LDS, the wider steps in place
-__device__ void cf_sort(ulonglong2* g, ulonglong2* s, uint32_t n) {
-    const uint32_t tid = threadIdx.x;
-    if (n <= kCfSortChunk) {
-        cf_sort_lds(g, s, 0, n, 2, n);
-        return;
-    }
-    for (uint32_t base = 0; base < n; base += kCfSortChunk) cf_sort_lds(g, s, base, kCfSortChunk, 2, kCfSortChunk);
-    for (uint32_t k = kCfSortChunk << 1; k <= n; k <<= 1) {
-        for (uint32_t j = k >> 1; j >= kCfSortChunk; j >>= 1) {
-            for (uint32_t p = tid; p < (n >> 1); p += kCfThreads) {
-                const uint32_t i = ((p & ~(j - 1)) << 1) | (p & (j - 1)), l = i | j;
-                const bool up = (i & k) == 0;
-                const ulonglong2 x = g[i], y = g[l];
-                if (cf_less(y, x) == up) {
-                    g[i] = y;
-                    g[l] = x;
-                }
-            }
-            __syncthreads();
-        }
-        for (uint32_t base = 0; base < n; base += kCfSortChunk) cf_sort_lds(g, s, base, kCfSortChunk, k, k);
-    }
 }
 
 __device__ inline void cf_pad(const CfArgs& a, uint32_t q, uint32_t from) {

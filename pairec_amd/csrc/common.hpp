@@ -95,6 +95,7 @@ enum ScratchSlot : int {
     kSlotTraffic = 34,       // traffic.hip: the position keys, the compacted lists, the keys' order, the list lengths and the segment offsets of a traffic control sort
     kSlotX2i = 35,           // x2i.hip: cf.hip's layout for a U2I2X2I recall — status and counts, staged offsets and lists, the global tier's tables, the items to order, the over-fetched answer (pg_rtu2i_x_recall's trigger lists are in kSlotRtU2I meanwhile)
     kSlotBloom = 36,         // bloom.hip: the probe's keep ballots of a Bloom filter call; the one-request entries' staging behind them
+    kSlotHot = 37,           // hot.hip: the staged trigger offsets, sizes, ids and quotas of a list recall, behind them the sort records of the requests too long to order in LDS
     kSlotCount
 };
 

@@ -1210,6 +1210,51 @@ class Context:
                                           _ptr(o_r), _ptr(o_s), None if src is None else _ptr(o_src), C.byref(cnt)))
         return o_r, o_s, o_src, cnt.value
 
+    # ---- UserGroupHot / GlobalHot / Topic recalls: list recall over a hot table ----------------------------
+    def hottable_create(self, table: "Table", n_triggers: int) -> "HotTable":
+        """pg_hottable_create: an empty hot table of n_triggers trigger indices over the local rows of `table`"""
+        return HotTable(self, table, n_triggers)
+
+    def hottable_upload(self, hot: "HotTable", offsets, item_rows, scores, source, trig0: int = 0) -> None:
+        """pg_hottable_upload: append the lists of len(offsets) - 1 consecutive triggers from trig0; trigger trig0 + i lists the
+        local rows item_rows[offsets[i]:offsets[i + 1]] with scores[...] (float64) and source[...] (uint8: bits 0-6 the
+        RetrieveId index, HOT_UNSCORED = the entry carries no score and its score is 0)"""
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        it = np.ascontiguousarray(item_rows, dtype=np.uint32)
+        sc = np.ascontiguousarray(scores, dtype=np.float64)
+        src = np.ascontiguousarray(source, dtype=np.uint8)
+        if off.ndim != 1 or off.shape[0] < 1 or it.ndim != 1 or it.shape != sc.shape or it.shape != src.shape or int(off.max()) > it.shape[0]:
+            raise ValueError("hottable_upload: offsets must index item_rows / scores / source of one length")
+        _lib.check(self.L.pg_hottable_upload(self.h, hot.h, int(trig0), off.shape[0] - 1, _ptr(off), _ptr(it), _ptr(sc), _ptr(src)))
+
+    def hottable_info(self, hot: "HotTable") -> dict:
+        rows, nt, pairs, up, gen = C.c_uint64(), C.c_uint32(), C.c_uint64(), C.c_uint32(), C.c_uint64()
+        _lib.check(self.L.pg_hottable_info(hot.h, C.byref(rows), C.byref(nt), C.byref(pairs), C.byref(up), C.byref(gen)))
+        return {"rows": rows.value, "n_triggers": nt.value, "pairs": pairs.value, "triggers_uploaded": up.value, "generation": gen.value}
+
+    def hot_recall_dev(self, hot: "HotTable", mode: int, triggers, k: int, d_out_rows: int, d_out_scores: int, d_out_source: int = 0,
+                       d_out_count: int = 0, values=None, d_seed: int = 0) -> None:
+        """pg_hot_recall_dev: triggers[q] = request q's trigger indices and values[q] their topic values (HOT_TOPIC only) are host
+        lists; d_seed [nq] uint64 (0 = absent) and the outputs [nq][k] / [nq] are device addresses (source and count optional).
+        One launch on the context's stream: synchronize() before reading."""
+        tr, vals, off = _pack_hot_triggers("hot_recall_dev", mode, triggers, values)
+        v = lambda p: C.c_void_p(p or None)                                          # noqa: E731
+        _lib.check(self.L.pg_hot_recall_dev(self.h, hot.h, int(mode), _ptr(tr), None if vals is None else _ptr(vals), _ptr(off), v(d_seed),
+                                            off.shape[0] - 1, int(k), v(d_out_rows), v(d_out_scores), v(d_out_source), v(d_out_count)))
+
+    def hot_recall(self, hot: "HotTable", mode: int, triggers, k: int, values=None, seed=None):
+        """pg_hot_recall on host arrays → (rows [nq][k] uint64 global ids, scores [nq][k] f64, source [nq][k] uint8, counts [nq])"""
+        tr, vals, off = _pack_hot_triggers("hot_recall", mode, triggers, values)
+        nq = off.shape[0] - 1
+        sd = None if seed is None else np.ascontiguousarray(seed, dtype=np.uint64).reshape(-1)
+        if sd is not None and sd.shape[0] != nq:
+            raise ValueError("hot_recall: one seed per request")
+        rows, scores = np.empty((nq, k), np.uint64), np.empty((nq, k), np.float64)
+        source, counts = np.empty((nq, k), np.uint8), np.zeros(nq, np.uint32)
+        _lib.check(self.L.pg_hot_recall(self.h, hot.h, int(mode), _ptr(tr), None if vals is None else _ptr(vals), _ptr(off),
+                                        None if sd is None else _ptr(sd), nq, int(k), _ptr(rows), _ptr(scores), _ptr(source), _ptr(counts)))
+        return rows, scores, source, counts
+
     # ---- DiversityAdjustCountFilter: quotas per expression class ---------------------------------------
     def classcut_masks_dev(self, cc, fs, nq: int, cap: int, d_rows: int, d_score: int, d_source: int, d_count: int, d_out_masks: int) -> None:
         """pg_classcut_masks_dev: device addresses (0 = absent) → [nq][cap] uint8, bit c = member of class c.  One launch on the
@@ -1926,6 +1971,79 @@ class XTable:
                                                     C.c_void_p(d_times), _ptr(off), _ptr(nw), nq, k, C.byref(opts), C.c_void_p(d_out_rows),
                                                     C.c_void_p(d_out_scores), _ptr(counts)))
         return counts
+
+
+HOT_GROUP, HOT_GLOBAL, HOT_TOPIC = 0, 1, 2
+HOT_MAX_ENTRIES, HOT_UNSCORED, HOT_PAD_SOURCE = 65536, 0x80, 0xFF
+
+
+def _pack_hot_triggers(who, mode, triggers, values):
+    """per-request trigger indices (and topic values) → (triggers uint32, values f64 | None, offsets uint32 [nq + 1])"""
+    nq = len(triggers)
+    tr = [np.asarray(t, dtype=np.uint32).reshape(-1) for t in triggers]
+    off = np.zeros(nq + 1, dtype=np.uint32)
+    off[1:] = np.cumsum([a.shape[0] for a in tr])
+    trc = np.ascontiguousarray(np.concatenate(tr)) if nq else np.zeros(0, dtype=np.uint32)
+    vals = None
+    if values is not None:
+        if len(values) != nq:
+            raise ValueError("%s: %d value lists for %d requests" % (who, len(values), nq))
+        vs = [np.asarray(v, dtype=np.float64).reshape(-1) for v in values]
+        if any(a.shape != b.shape for a, b in zip(tr, vs)):
+            raise ValueError("%s: every trigger needs one value" % who)
+        vals = np.ascontiguousarray(np.concatenate(vs)) if nq else np.zeros(0, dtype=np.float64)
+    elif mode == HOT_TOPIC and trc.size:
+        raise ValueError("%s: HOT_TOPIC needs the triggers' values" % who)
+    if trc.size == 0:                                    # (an address to pass: nothing is read through it)
+        trc = np.zeros(1, dtype=np.uint32)
+        vals = None if vals is None else np.zeros(1, dtype=np.float64)
+    return trc, vals, off
+
+
+def hot_recall_host(rows: int, row_offset: int, offsets, item_rows, scores, source, mode: int, triggers, k: int, values=None, seed=None):
+    """pg_hot_recall_host: the host statement of the list recall over host CSR arrays (no context, no device); offsets
+    [n_triggers + 1] → (rows [nq][k] uint64 global ids, scores [nq][k] f64, source [nq][k] uint8, counts [nq])."""
+    tr, vals, off = _pack_hot_triggers("hot_recall_host", mode, triggers, values)
+    nq = off.shape[0] - 1
+    to = np.ascontiguousarray(offsets, dtype=np.uint64)
+    it = np.ascontiguousarray(item_rows, dtype=np.uint32)
+    sc = np.ascontiguousarray(scores, dtype=np.float64)
+    src = np.ascontiguousarray(source, dtype=np.uint8)
+    if to.ndim != 1 or to.shape[0] < 2 or it.ndim != 1 or it.shape != sc.shape or it.shape != src.shape or int(to.max()) > it.shape[0]:
+        raise ValueError("hot_recall_host: offsets [n_triggers + 1] must index item_rows / scores / source of one length")
+    sd = None if seed is None else np.ascontiguousarray(seed, dtype=np.uint64).reshape(-1)
+    if sd is not None and sd.shape[0] != nq:
+        raise ValueError("hot_recall_host: one seed per request")
+    out_rows, out_scores = np.empty((nq, k), np.uint64), np.empty((nq, k), np.float64)
+    out_source, counts = np.empty((nq, k), np.uint8), np.zeros(nq, np.uint32)
+    _lib.check(_lib.load().pg_hot_recall_host(int(rows), int(row_offset), to.shape[0] - 1, _ptr(to), _ptr(it) if it.size else None,
+                                              _ptr(sc) if it.size else None, _ptr(src) if it.size else None, int(mode), _ptr(tr),
+                                              None if vals is None else _ptr(vals), _ptr(off), None if sd is None else _ptr(sd), nq, int(k),
+                                              _ptr(out_rows), _ptr(out_scores), _ptr(out_source), _ptr(counts)))
+    return out_rows, out_scores, out_source, counts
+
+
+class HotTable:
+    """Hot lists over n_triggers trigger indices (trigger ids, topics: the caller's dictionary codes) and the local rows of
+    `table`, resident in HBM (pg_hottable_*), for the UserGroupHot / UserGlobalHot / UserTopic recalls (Context.hot_recall).  The
+    table must outlive it."""
+
+    def __init__(self, ctx: Context, table: Table, n_triggers: int):
+        self.ctx, self.table = ctx, table
+        h = C.c_void_p()
+        _lib.check(ctx.L.pg_hottable_create(ctx.h, table.h, int(n_triggers), C.byref(h)))
+        self.h = h
+
+    def destroy(self):
+        if self.h:
+            _lib.check(self.ctx.L.pg_hottable_destroy(self.ctx.h, self.h))
+            self.h = None
+
+    def upload(self, offsets, item_rows, scores, source, trig0: int = 0) -> None:
+        self.ctx.hottable_upload(self, offsets, item_rows, scores, source, trig0)
+
+    def info(self) -> dict:
+        return self.ctx.hottable_info(self)
 
 
 class Index:
