@@ -70,7 +70,7 @@ typedef enum {
  *                  Refused at load (PG_ERR_UNSUPPORTED): PG_MODEL_FM_TWOTOWER; a non-finite weight; a scaled weight or
  *                  scale factor outside fp32's normal range. */
 typedef enum { PG_PREC_F32 = 0, PG_PREC_BF16 = 1, PG_PREC_BF16X3 = 2, PG_PREC_F16X2 = 3, PG_PREC_F16 = 4 } pg_prec;
-typedef enum { PG_MODEL_DNN3 = 1, PG_MODEL_FM_TWOTOWER = 2, PG_MODEL_DNN3_MULTI = 3 } pg_model_kind;
+typedef enum { PG_MODEL_DNN3 = 1, PG_MODEL_FM_TWOTOWER = 2, PG_MODEL_DNN3_MULTI = 3, PG_MODEL_DIN = 4 } pg_model_kind;
 
 const char* pg_last_error(void);
 const char* pg_version(void);
@@ -249,6 +249,42 @@ int pg_rank_dnn3(pg_ctx* ctx, const pg_model* m, const pg_table* t, const float*
 int pg_rank_dnn3_dev(pg_ctx* ctx, const pg_model* m, const pg_table* t, const float* d_user_vecs,
                      const uint32_t* d_cand_rows, const uint32_t* d_req_offsets, uint32_t n_req,
                      uint32_t n_items, float* d_out_scores);
+
+/* ---- rank: DIN — attention of every candidate over the user's behaviour sequence (PG_MODEL_DIN) ------------------------------
+ *   Replaces  the remote DIN the reference feeds a user's behaviour sequence to: Feature_Type_Sequence (module/feature_dao.go:19,
+ *             94-134: SequenceLength, SequenceName, SequenceEvent of recconf/recconf.go:202-212, loaded per store by
+ *             feature_hologres_dao.go, feature_be_dao.go, feature_tablestore_dao.go, feature_featurestore_dao.go), scored by the
+ *             model of TEST_TORCHREC_DIN_TOKEN (algorithm/eas/easyrec_predict_test.go).  The sequence's items are rows of the table
+ *             the candidates come from: request r's sequence is seq_rows[seq_offsets[r] .. seq_offsets[r+1]), most recent
+ *             SequenceLength <= PG_DIN_MAX_SEQ kept by the caller.
+ *   Model     per candidate row e (64 wide) and sequence rows s_0 .. s_{L-1}:
+ *               z_l = [ e | s_l | e - s_l | e * s_l ]  (256)      a_l = wa2 . relu( Wa' z_l + ba ) + ba2   (no softmax, as in DIN)
+ *               pooled = sum_l a_l s_l  (64)       score_o = DNN3 trunk on [ user | e | pooled ], heads as PG_MODEL_DNN3_MULTI
+ *   Blob      u32 d_user, d_item (= 64), h1, h2, n_out (1..8), att_h (16 or 32);
+ *             Wa[4 x 64][att_h] (row blocks e, s, e - s, e * s); ba[att_h]; wa2[att_h]; ba2;
+ *             w1[d_user + 128][h1] (rows: user, e, pooled); b1; w2[h1][h2]; b2; w3[h2][n_out]; b3[n_out]
+ *             — little-endian fp32, every matrix [in][out]; (h1, h2) as PG_MODEL_DNN3.  tools/pack_model.py builds it.
+ *   Precision PG_PREC_F32, PG_PREC_BF16, PG_PREC_BF16X3 (its attention is the F32 form).  PG_PREC_BF16 rounds the candidate row and
+ *             the per-position operand s_l Wp + Wq once each (RNE); everything after the matrix product is fp32.
+ *   Masking   positions past PG_DIN_MAX_SEQ and a sequence row >= the table's rows contribute nothing (a user's history may name
+ *             items the table no longer holds); a candidate row >= the table's rows reads the last row, as pg_rank_dnn3_dev's
+ *             gather does; an empty sequence gives pooled = 0: the model is then the DNN3 of w1's user and e rows.
+ *   Output    as pg_rank_dnn3: out_scores[o * n_items + i], one plane per head.
+ *   Refused   pg_model_load: PG_PREC_F16X2 / PG_PREC_F16, d_item != 64, att_h outside {16, 32}, an unknown (h1, h2), n_out
+ *             outside 1..8 (PG_ERR_UNSUPPORTED); a blob of another length (PG_ERR_INVALID).  pg_rank_din (PG_ERR_INVALID, on the
+ *             host, the context left usable): a sequence longer than PG_DIN_MAX_SEQ, offsets that descend or do not start at 0, a
+ *             table whose dim is not 64, a model of another kind; pg_rank_dnn3[_dev] refuse a PG_MODEL_DIN the same way.
+ *             pg_rank_din_dev cannot see the lengths: it uses the first PG_DIN_MAX_SEQ rows of a longer sequence; offsets that
+ *             are not monotone are a precondition there.
+ *   Not here  the coalescer and the pg_recommend_* pipelines (pg_coalescer_create_scene refuses the model); sequence dimension
+ *             fields (SequenceDimFields); 128-wide tables (layer 1 would be 256 deep); softmax or Dice activation units; the fp16
+ *             precisions. */
+#define PG_DIN_MAX_SEQ 64
+int pg_rank_din(pg_ctx* ctx, const pg_model* m, const pg_table* t, const float* user_vecs, const uint32_t* seq_rows,
+                const uint32_t* seq_offsets, const uint32_t* cand_rows, const uint32_t* req_offsets, uint32_t n_req, float* out_scores);
+int pg_rank_din_dev(pg_ctx* ctx, const pg_model* m, const pg_table* t, const float* d_user_vecs, const uint32_t* d_seq_rows,
+                    const uint32_t* d_seq_offsets, const uint32_t* d_cand_rows, const uint32_t* d_req_offsets, uint32_t n_req,
+                    uint32_t n_items, float* d_out_scores);
 /* FM + two-tower: user_field_ids [n_req][n_user_fields], item_field_ids [n_items][n_item_fields] */
 int pg_rank_fm2t(pg_ctx* ctx, const pg_model* m, const float* user_vecs,
                  const int32_t* user_field_ids, const int32_t* item_field_ids,

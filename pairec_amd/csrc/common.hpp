@@ -58,7 +58,7 @@ struct Scratch {
 // The arena's slots.  A slot's contents are valid until the next reserve of the same slot on this context; users that share a
 // slot are stages that never hold it at the same time on the context's one stream.  The values are only array positions.
 enum ScratchSlot : int {
-    kSlotRows = 0,           // table.hip: the row ids of a gather from host rows; rank_mlp.hip: fm2t rows' gathered field ids (separate entry points, neither calls the other)
+    kSlotRows = 0,           // table.hip: the row ids of a gather from host rows; rank_mlp.hip: fm2t rows' gathered field ids; rank_entry.hip: pg_rank_din's staged sequence rows and offsets (separate entry points, none calls another)
     kSlotHostStage = 1,      // table.hip: the gathered rows on their way to the host; features.hip: column descriptors and pointers of a gather (separate entry points)
     kSlotRecallSmall = 2,    // recall_plan.hip recall_scratch: padded queries, thresholds, counts, screen fragments, status words
     kSlotRecallCand = 3,     // recall_plan.hip recall_scratch: the candidate and suspect lists
@@ -96,6 +96,7 @@ enum ScratchSlot : int {
     kSlotX2i = 35,           // x2i.hip: cf.hip's layout for a U2I2X2I recall — status and counts, staged offsets and lists, the global tier's tables, the items to order, the over-fetched answer (pg_rtu2i_x_recall's trigger lists are in kSlotRtU2I meanwhile)
     kSlotBloom = 36,         // bloom.hip: the probe's keep ballots of a Bloom filter call; the one-request entries' staging behind them
     kSlotHot = 37,           // hot.hip: the staged trigger offsets, sizes, ids and quotas of a list recall, behind them the sort records of the requests too long to order in LDS
+    kSlotDin = 38,           // rank_din.hip: the staged rows [e | pooled], the identity candidate list, a run's offsets and its tile table (scratch_layout.hpp kDinRunItems bounds it; kSlotRankTiles stays the trunk's)
     kSlotCount
 };
 
@@ -558,6 +559,10 @@ int topk_merge_locked(pg_ctx* ctx, const uint64_t* d_rows, const float* d_scores
 int rank_dnn3_dev_locked(pg_ctx* ctx, const pg_model* m, const pg_table* t, const float* d_user,
                          const uint32_t* d_cand, const uint32_t* d_off, uint32_t n_req, uint32_t n_items,
                          float* d_out, size_t out_stride = 0);
+// rank_din.hip: a PG_MODEL_DIN — attention pooling over each request's sequence rows, then the call above over the staged rows
+int rank_din_dev_locked(pg_ctx* ctx, const pg_model* m, const pg_table* t, const float* d_user, const uint32_t* d_seq_rows,
+                        const uint32_t* d_seq_off, const uint32_t* d_cand, const uint32_t* d_off, uint32_t n_req, uint32_t n_items,
+                        float* d_out);
 int fm2t_user_embedding_locked(pg_ctx* ctx, const pg_model* m, const float* d_user, uint32_t n_req, float* d_out);
 // candidates as per-item field ids (d_ifids), or as rows of item records (ir, d_cand)
 int rank_fm2t_dev_locked(pg_ctx* ctx, const pg_model* m, const float* d_user, const int32_t* d_ufids, const int32_t* d_ifids,

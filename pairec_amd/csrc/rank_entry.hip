@@ -197,6 +197,56 @@ int pg_rank_dnn3(pg_ctx* ctx, const pg_model* m, const pg_table* t, const float*
         });
 }
 
+int pg_rank_din_dev(pg_ctx* ctx, const pg_model* m, const pg_table* t, const float* d_user_vecs, const uint32_t* d_seq_rows,
+                    const uint32_t* d_seq_offsets, const uint32_t* d_cand_rows, const uint32_t* d_req_offsets, uint32_t n_req,
+                    uint32_t n_items, float* d_out_scores) {
+    // (d_seq_rows may be NULL: every sequence empty)
+    PG_REQUIRE(ctx && m && t && d_user_vecs && d_seq_offsets && d_cand_rows && d_req_offsets && d_out_scores, "pg_rank_din_dev: NULL argument");
+    PG_REQUIRE(m->kind == PG_MODEL_DIN, "pg_rank_din_dev: model is not DIN");
+    PG_REQUIRE(t->dim == m->d_item && t->rows >= 1, "pg_rank_din_dev: table dim %u != model d_item %u (or no rows)", t->dim, m->d_item);
+    PG_REQUIRE(n_req <= 65535, "pg_rank_din_dev: at most 65535 requests per call");
+    std::lock_guard<std::mutex> g(ctx->mu);
+    pg::TableRead tr(t->rw);
+    return pg::rank_din_dev_locked(ctx, m, t, d_user_vecs, d_seq_rows, d_seq_offsets, d_cand_rows, d_req_offsets, n_req, n_items,
+                                   d_out_scores);
+}
+
+int pg_rank_din(pg_ctx* ctx, const pg_model* m, const pg_table* t, const float* user_vecs, const uint32_t* seq_rows,
+                const uint32_t* seq_offsets, const uint32_t* cand_rows, const uint32_t* req_offsets, uint32_t n_req, float* out_scores) {
+    PG_REQUIRE(ctx && m && t && req_offsets, "pg_rank_din: NULL argument");
+    PG_REQUIRE(m->kind == PG_MODEL_DIN, "pg_rank_din: model is not DIN");
+    PG_REQUIRE(t->dim == m->d_item && t->rows >= 1, "pg_rank_din: table dim %u != model d_item %u (or no rows)", t->dim, m->d_item);
+    PG_REQUIRE(n_req == 0 || seq_offsets, "pg_rank_din: NULL argument");
+    uint32_t n_seq = 0;
+    if (n_req && n_req <= 65535) {
+        PG_REQUIRE(seq_offsets[0] == 0, "pg_rank_din: seq_offsets[0] must be 0");
+        for (uint32_t r = 0; r < n_req; ++r) {
+            PG_REQUIRE(seq_offsets[r + 1] >= seq_offsets[r], "pg_rank_din: seq_offsets not monotone at %u", r);
+            PG_REQUIRE(seq_offsets[r + 1] - seq_offsets[r] <= PG_DIN_MAX_SEQ, "pg_rank_din: request %u has a sequence of %u rows, at most %d",
+                       r, seq_offsets[r + 1] - seq_offsets[r], PG_DIN_MAX_SEQ);
+        }
+        n_seq = seq_offsets[n_req];
+        PG_REQUIRE(n_seq == 0 || seq_rows, "pg_rank_din: NULL argument");
+    }
+    // the sequences are staged in kSlotRows: their rows (a dummy word when there are none), then the n_req + 1 offsets
+    static const uint32_t no_rows[1] = {0};
+    const pg::HostIn in[] = {{user_vecs, false, m->d_user, 4}, {cand_rows, true, 1, 4}};
+    return pg::rank_from_host(
+        "pg_rank_din", ctx, m, t, in, nullptr, req_offsets, n_req, out_scores, pg::no_check,
+        [&](void* const* d, const uint32_t* d_off, uint32_t n_items, float* d_scores) -> int {
+            // (ragged, so not among rank_from_host's fixed-width inputs; kSlotDin may grow under rank_din_dev_locked)
+            uint32_t *d_sr, *d_so;
+            int rc;
+            if ((rc = pg::scratch_carve(ctx, pg::kSlotRows, [&](pg::Carve& c) {
+                    d_sr = c.take<uint32_t>(n_seq ? n_seq : 1);
+                    d_so = c.take<uint32_t>((size_t)n_req + 1);
+                }))) return rc;
+            PG_HIP(hipMemcpyAsync(d_sr, n_seq ? seq_rows : no_rows, (size_t)(n_seq ? n_seq : 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+            PG_HIP(hipMemcpyAsync(d_so, seq_offsets, ((size_t)n_req + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+            return pg::rank_din_dev_locked(ctx, m, t, (const float*)d[0], d_sr, d_so, (const uint32_t*)d[1], d_off, n_req, n_items, d_scores);
+        });
+}
+
 int pg_fm2t_user_embedding_dev(pg_ctx* ctx, const pg_model* m, const float* d_user_vecs, uint32_t n_req, float* d_out) {
     PG_REQUIRE(ctx && m && (n_req == 0 || (d_user_vecs && d_out)), "pg_fm2t_user_embedding_dev: NULL argument");
     PG_REQUIRE(m->kind == PG_MODEL_FM_TWOTOWER, "pg_fm2t_user_embedding_dev: model is not FM_TWOTOWER");

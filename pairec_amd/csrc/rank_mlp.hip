@@ -696,9 +696,9 @@ struct TileTableArgs {
     uint32_t blocks;                                       // 0: no table in this launch
 };
 
-static int build_tiles_launch(pg_ctx* ctx, const uint32_t* d_off, uint32_t n_req, uint32_t max_tiles, uint32_t tile_items,
-                              uint32_t* tile_req, uint32_t* tile_item0, uint32_t* tile_cnt, uint32_t* n_tiles,
-                              uint32_t* req_tile0) {
+int build_tiles_launch(pg_ctx* ctx, const uint32_t* d_off, uint32_t n_req, uint32_t max_tiles, uint32_t tile_items,
+                       uint32_t* tile_req, uint32_t* tile_item0, uint32_t* tile_cnt, uint32_t* n_tiles,
+                       uint32_t* req_tile0) {
     if (n_req <= kTilesLdsReqs)
         build_tiles_wide_kernel<<<(max_tiles + 255) / 256, 256, 0, ctx->stream>>>(d_off, n_req, tile_req, tile_item0, tile_cnt,
                                                                                   n_tiles, req_tile0, tile_items);

@@ -154,6 +154,11 @@ __device__ __forceinline__ void store_h_quad(char* tile, int row, int col, float
     }
 }
 
+// rank_mlp.hip: the tile table of a call — tile -> (request, first item, count), tiles of `tile_items` candidates cut per
+// request; arrays of max_tiles >= n_items / tile_items + n_req entries, req_tile0 [n_req] (rank_din.hip tiles its runs with it)
+int build_tiles_launch(pg_ctx* ctx, const uint32_t* d_off, uint32_t n_req, uint32_t max_tiles, uint32_t tile_items,
+                       uint32_t* tile_req, uint32_t* tile_item0, uint32_t* tile_cnt, uint32_t* n_tiles, uint32_t* req_tile0);
+
 // rank_ws.hip: the weights-stationary DNN3 kernel (bf16); `a` describes 64-item tiles
 constexpr int kWsItems = 64;
 int launch_dnn3_ws(pg_ctx* ctx, const MlpArgs& a);

@@ -50,6 +50,15 @@ struct pg_model {
     mutable uint64_t f16_calls = 0, f16_calls_whole = 0;   // under the context's lock
     pg_ctx* ctx = nullptr;
     float* c1_shared = nullptr;   // two-tower: ib1
+    // PG_MODEL_DIN: the activation unit folded for rank_din.hip (fold_din_attention), fp32 [d_item][att_h] each; the trunk's
+    // members above are a DNN3's whose item half is the 128 rows [e | pooled] of w1
+    uint32_t att_h = 0;
+    float* att_wq = nullptr;
+    float* att_wk = nullptr;
+    float* att_wp = nullptr;
+    float* att_ba = nullptr;    // [att_h]
+    float* att_wa2 = nullptr;   // [att_h]
+    float att_ba2 = 0.f;
     float* b2 = nullptr;
     float* w3 = nullptr;    // DNN3 head(s): [n_out][h2]
     float* fields = nullptr;          // two-tower: all field tables, one allocation
@@ -62,6 +71,7 @@ namespace pg {
 
 constexpr int kDIN = 128;      // gathered input width
 constexpr int kMaxHeads = 8;   // outputs of a multi-head DNN3
+constexpr int kDinD = 64;      // PG_MODEL_DIN: item width (the trunk's gathered input is [e | pooled] = kDIN)
 // PG_PREC_F16X2 / PG_PREC_F16 (the scaling rule is in rank_2r.hip's header)
 constexpr int kH2G = 11;       // activations: 2^G on top of the row normalisation
 constexpr int kH2S = 23;       // accumulators hold 2^S x the pre-activation; weights carry 2^(S - G)
@@ -168,6 +178,8 @@ struct BlobLayout {
     // two-tower: the user tower, the item tower, then per field [vocab][k] embeddings and [vocab] linear weights
     size_t uw1 = 0, ub1 = 0, uw2 = 0, ub2 = 0, iw1 = 0, ib1 = 0, iw2 = 0, ib2 = 0, fields = 0;
     size_t field_floats = 0;      // floats of all field tables together
+    // DIN, in front of the DNN3 arrays: Wa [4 x 64][att_h] (row blocks e, s, e - s, e * s), ba [att_h], wa2 [att_h], ba2
+    size_t wa = 0, ba = 0, wa2 = 0, ba2 = 0;
 };
 
 // What `blob` says as a model of `kind` in `prec`: the dimensions (and kind, prec, f16_nprod, b3, fm_b) into *m, the arrays'
@@ -179,6 +191,9 @@ inline int parse_model_blob(int kind, int prec, const void* blob, size_t len, pg
     if (f16_nprod && kind == PG_MODEL_FM_TWOTOWER)
         return refuse(why, PG_ERR_UNSUPPORTED, "pg_model_load: PG_PREC_F16X2 / PG_PREC_F16 serve PG_MODEL_DNN3 and PG_MODEL_DNN3_MULTI; load a "
                                                "PG_MODEL_FM_TWOTOWER in PG_PREC_BF16X3");
+    if (f16_nprod && kind == PG_MODEL_DIN)
+        return refuse(why, PG_ERR_UNSUPPORTED, "pg_model_load: PG_PREC_F16X2 / PG_PREC_F16 serve PG_MODEL_DNN3 and PG_MODEL_DNN3_MULTI; load a "
+                                               "PG_MODEL_DIN in PG_PREC_F32, PG_PREC_BF16 or PG_PREC_BF16X3");
     const uint8_t* p = (const uint8_t*)blob;
     // an fp16 mode is the split-bf16 model (its whole-call and per-tile fallback) plus the fp16 operands
     m->prec = f16_nprod ? (int)PG_PREC_BF16X3 : prec;
@@ -211,6 +226,34 @@ inline int parse_model_blob(int kind, int prec, const void* blob, size_t len, pg
                 if (!std::isfinite(w[i]))
                     return refuse(why, PG_ERR_UNSUPPORTED, "pg_model_load: the blob holds a non-finite weight (float %zu): not representable in an fp16 mode", i);
         }
+    } else if (kind == PG_MODEL_DIN) {
+        m->kind = PG_MODEL_DIN;
+        if (len < 24) return refuse(why, PG_ERR_INVALID, "pg_model_load: blob too short");
+        uint32_t hdr[6];
+        memcpy(hdr, p, 24);
+        m->d_user = hdr[0]; m->d_item = hdr[1]; m->h1 = hdr[2]; m->h2 = hdr[3]; m->n_out = hdr[4]; m->att_h = hdr[5];
+        if (m->n_out == 0 || m->n_out > (uint32_t)kMaxHeads)
+            return refuse(why, PG_ERR_UNSUPPORTED, "pg_model_load: a DIN has 1..%d outputs, the blob says %u", kMaxHeads, m->n_out);
+        if (m->d_item != (uint32_t)kDinD || (m->att_h != 16 && m->att_h != 32) || !dnn3_shape_ok(m->h1, m->h2) || m->d_user == 0 ||
+            m->d_user > 4096)
+            return refuse(why, PG_ERR_UNSUPPORTED, "pg_model_load: DIN shape [%u+2x%u]->%u->%u, attention width %u unsupported (d_item 64; "
+                                                   "attention width 16 or 32; hidden widths 128-128, 256-128, 256-256, 512-256, 1024-512)",
+                          m->d_user, m->d_item, m->h1, m->h2, m->att_h);
+        const size_t att = (size_t)4 * kDinD * m->att_h + 2 * m->att_h + 1, din = (size_t)m->d_user + 2 * kDinD;
+        const size_t need = 24 + (att + din * m->h1 + m->h1 + (size_t)m->h1 * m->h2 + m->h2 + ((size_t)m->h2 + 1) * m->n_out) * 4;
+        if (len != need) return refuse(why, PG_ERR_INVALID, "pg_model_load: DIN blob is %zu bytes, expected %zu", len, need);
+        lay->wa = 24;
+        lay->ba = lay->wa + (size_t)4 * kDinD * m->att_h * 4;
+        lay->wa2 = lay->ba + (size_t)m->att_h * 4;
+        lay->ba2 = lay->wa2 + (size_t)m->att_h * 4;
+        lay->w1 = lay->ba2 + 4;
+        lay->b1 = lay->w1 + din * m->h1 * 4;
+        lay->w2 = lay->b1 + (size_t)m->h1 * 4;
+        lay->b2 = lay->w2 + (size_t)m->h1 * m->h2 * 4;
+        lay->w3 = lay->b2 + (size_t)m->h2 * 4;
+        lay->b3 = lay->w3 + (size_t)m->h2 * m->n_out * 4;
+        memcpy(&m->att_ba2, p + lay->ba2, 4);
+        memcpy(&m->b3, p + lay->b3, 4);
     } else if (kind == PG_MODEL_FM_TWOTOWER) {
         m->kind = PG_MODEL_FM_TWOTOWER;
         if (len < 32) return refuse(why, PG_ERR_INVALID, "pg_model_load: blob too short");
@@ -357,6 +400,20 @@ inline std::vector<float> rounded(const float* w, size_t n, int prec) {
     return o;
 }
 
+// PG_MODEL_DIN: the activation unit's first layer Wa = [We; Ws; Wd; Wp] ([4 x 64][att_h], input [e | s | e - s | e * s]) folded
+// so that no per-pair operand is formed:  Wa' z = (We + Wd)' e + (Ws - Wd)' s + Wp' (e * s)  =  Wq' e + Wk' s + Wp' (e * s).
+// Each output [64][att_h], fp32 sums of fp32 weights (nothing is rounded here in any precision: rank_din.hip rounds the
+// operand it builds from them, once).
+inline void fold_din_attention(const float* wa, uint32_t att_h, std::vector<float>* wq, std::vector<float>* wk, std::vector<float>* wp) {
+    const size_t n = (size_t)kDinD * att_h;
+    const float *we = wa, *ws = wa + n, *wd = wa + 2 * n, *wpp = wa + 3 * n;
+    wq->resize(n); wk->resize(n); wp->assign(wpp, wpp + n);
+    for (size_t i = 0; i < n; ++i) {
+        (*wq)[i] = we[i] + wd[i];
+        (*wk)[i] = ws[i] - wd[i];
+    }
+}
+
 // ---- what goes to the device ---------------------------------------------------------------------------------------------
 // One allocation of a loaded model: `bytes` from `src` (the blob, or a buffer ModelUploads owns) into a device buffer whose
 // address *dst receives; `lo`: the member that points at the second half of that buffer (the lo fragments of split operands).
@@ -390,14 +447,25 @@ inline int model_uploads(pg_model* m, const BlobLayout& lay, const void* blob, M
         up->packed.push_back(std::move(v));
         add(dst, up->packed.back().data(), up->packed.back().size(), lo);
     };
-    if (m->kind == PG_MODEL_DNN3) {
+    if (m->kind == PG_MODEL_DNN3 || m->kind == PG_MODEL_DIN) {
         const float *w1 = at(lay.w1), *w2 = at(lay.w2), *w3 = at(lay.w3);
+        // a DIN's trunk is a DNN3 over the staged rows [e | pooled]: the item half of w1 is those 128 rows
+        const uint32_t item_rows = m->kind == PG_MODEL_DIN ? 2 * m->d_item : m->d_item;
+        if (m->kind == PG_MODEL_DIN) {
+            std::vector<float> wq, wk, wp;
+            fold_din_attention(at(lay.wa), m->att_h, &wq, &wk, &wp);
+            add_floats(&m->att_wq, std::move(wq));
+            add_floats(&m->att_wk, std::move(wk));
+            add_floats(&m->att_wp, std::move(wp));
+            add(&m->att_ba, at(lay.ba), (size_t)m->att_h * 4);
+            add(&m->att_wa2, at(lay.wa2), (size_t)m->att_h * 4);
+        }
         std::vector<float> w3t((size_t)m->n_out * m->h2);          // kept head-major on the device
         for (uint32_t o = 0; o < m->n_out; ++o)
             for (uint32_t j = 0; j < m->h2; ++j) w3t[(size_t)o * m->h2 + j] = w3[(size_t)j * m->n_out + o];
         // the kernel's layer 1 is 128 deep: a 64-wide item row is padded with zero columns, W1 with zero rows
         std::vector<float> w1i((size_t)kDIN * m->h1, 0.0f);
-        memcpy(w1i.data(), w1 + (size_t)m->d_user * m->h1, (size_t)m->d_item * m->h1 * 4);
+        memcpy(w1i.data(), w1 + (size_t)m->d_user * m->h1, (size_t)item_rows * m->h1 * 4);
         void** const split = m->prec == 2 ? &m->w1p_lo : nullptr;   // split bf16: the lo fragments follow the hi fragments
         add_floats(&m->w1u, rounded(w1, (size_t)m->d_user * m->h1, m->prec));
         add(&m->b1, at(lay.b1), (size_t)m->h1 * 4);

@@ -1,8 +1,16 @@
 // scratch_layout.hpp — the one round-up and the carving cursor of the scratch arena (host only, no HIP dependency).
 #pragma once
 #include <cstddef>
+#include <cstdint>
 
 namespace pg {
+
+// kSlotDin (rank_din.hip): candidates of one run of a PG_MODEL_DIN call.  The slot holds at most this many staged rows of
+// 512 B (64 MiB) and as many identity indices, whatever the call's size.  A larger call is served in successive runs of this
+// many CANDIDATES — cut by candidate index, not by request: each run has its own offsets (the call's, clamped to the run and
+// rebased) and is tiled on its own, so a request that straddles a boundary is attended and ranked in both runs, each with
+// the request's whole sequence and user vector, and its scores land where one run would have put them.
+constexpr uint32_t kDinRunItems = 1u << 17;
 
 // x rounded up to a multiple of a (a power of two); 256 bytes is the arena's default region alignment
 inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) & ~(a - 1); }

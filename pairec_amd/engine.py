@@ -14,7 +14,8 @@ import numpy as np
 from . import _lib
 
 PREC_F32, PREC_BF16, PREC_BF16X3, PREC_F16X2, PREC_F16 = 0, 1, 2, 3, 4
-MODEL_DNN3, MODEL_FM_TWOTOWER, MODEL_DNN3_MULTI = 1, 2, 3
+MODEL_DNN3, MODEL_FM_TWOTOWER, MODEL_DNN3_MULTI, MODEL_DIN = 1, 2, 3, 4
+DIN_MAX_SEQ = 64
 MAX_QUERIES = 256         # per table pass (32 when dim > 128)
 
 
@@ -2222,6 +2223,21 @@ def pack_dnn3_multi(w1, b1, w2, b2, w3, b3, d_user: int) -> bytes:
             np.ascontiguousarray(b2, dtype=np.float32).tobytes() + w3.tobytes() + b3.tobytes())
 
 
+def pack_din(wa, ba, wa2, ba2, w1, b1, w2, b2, w3, b3, d_user: int) -> bytes:
+    """PG_MODEL_DIN blob (include/pairec_gpu.h): the activation unit wa [4 x 64][att_h] (row blocks e, s, e - s, e * s), ba, wa2
+    [att_h], ba2; then the trunk as pack_dnn3_multi with w1 [d_user + 128][h1] (rows: user, e, pooled)."""
+    f = lambda a: np.ascontiguousarray(a, dtype=np.float32)   # noqa: E731
+    wa, w1, w2 = f(wa), f(w1), f(w2)
+    att_h, h1, h2 = wa.shape[1], w1.shape[1], w2.shape[1]
+    b3 = f(b3).reshape(-1)
+    w3 = f(w3).reshape(h2, b3.shape[0])
+    d_item = wa.shape[0] // 4
+    assert wa.shape[0] == 4 * d_item and w1.shape[0] == d_user + 2 * d_item
+    return (struct.pack("<6I", d_user, d_item, h1, h2, b3.shape[0], att_h) + wa.tobytes() + f(ba).tobytes() + f(wa2).tobytes() +
+            struct.pack("<f", float(ba2)) + w1.tobytes() + f(b1).tobytes() + w2.tobytes() + f(b2).tobytes() + w3.tobytes() +
+            b3.tobytes())
+
+
 def pack_fm2t(w) -> bytes:
     """w: object with the attributes of oracle.Fm2tWeights (duck-typed; no oracle import here)."""
     parts = [struct.pack("<7If", w.nuf, w.nif, w.k, w.d_user, w.t_h1, w.t_out, w.vocab, w.fm_b)]
@@ -2276,6 +2292,28 @@ class RankModel:
         _lib.check(self.ctx.L.pg_rank_dnn3_dev(self.ctx.h, self.h, table.h, C.c_void_p(d_user_vecs),
                                                C.c_void_p(d_cand_rows), C.c_void_p(d_req_offsets),
                                                n_req, n_items, C.c_void_p(d_out)))
+
+    def rank_din(self, table: Table, user_vecs: np.ndarray, seqs: Sequence[np.ndarray], cand_rows: np.ndarray,
+                 req_offsets: Sequence[int]) -> np.ndarray:
+        """MODEL_DIN: seqs[r] = the rows of `table` in request r's behaviour sequence (at most DIN_MAX_SEQ; may be empty).
+        scores [n_items], or [n_out][n_items] for several heads."""
+        u = np.ascontiguousarray(user_vecs, dtype=np.float32)
+        c = np.ascontiguousarray(cand_rows, dtype=np.uint32)
+        ro = np.ascontiguousarray(req_offsets, dtype=np.uint32)
+        so = np.zeros(len(seqs) + 1, dtype=np.uint32)
+        np.cumsum([len(s) for s in seqs], out=so[1:])
+        sr = np.ascontiguousarray(np.concatenate([np.asarray(s, dtype=np.uint32).reshape(-1) for s in seqs] + [np.zeros(0, np.uint32)]))
+        assert so.shape[0] == ro.shape[0], "one sequence per request"
+        out = np.empty((self.n_out, c.shape[0]), dtype=np.float32)
+        _lib.check(self.ctx.L.pg_rank_din(self.ctx.h, self.h, table.h, _ptr(u), _ptr(sr), _ptr(so), _ptr(c), _ptr(ro),
+                                          ro.shape[0] - 1, _ptr(out)))
+        return out[0] if self.n_out == 1 else out
+
+    def rank_din_dev(self, table: Table, d_user_vecs: int, d_seq_rows: int, d_seq_offsets: int, d_cand_rows: int,
+                     d_req_offsets: int, n_req: int, n_items: int, d_out: int):
+        _lib.check(self.ctx.L.pg_rank_din_dev(self.ctx.h, self.h, table.h, C.c_void_p(d_user_vecs), C.c_void_p(d_seq_rows),
+                                              C.c_void_p(d_seq_offsets), C.c_void_p(d_cand_rows), C.c_void_p(d_req_offsets),
+                                              n_req, n_items, C.c_void_p(d_out)))
 
     def rank_fm2t(self, user_vecs, user_field_ids, item_field_ids, req_offsets) -> np.ndarray:
         u = np.ascontiguousarray(user_vecs, dtype=np.float32)

@@ -14,6 +14,10 @@ Input: an .npz whose arrays are the layers' kernels exactly as a framework saves
       w1 [d_user + d_item][h1]   b1 [h1]   w2 [h1][h2]   b2 [h2]   w3 [h2] or [h2][1]   b3 scalar or [1]
   DNN3, several outputs on one trunk (probs_ctr / probs_cvr …: EasyrecResponse.multiValModule, easyrec_response.go:35-70):
       … w3 [h2][n_out]   b3 [n_out]        (n_out 2..8; the algorithm's "Outputs" list names them in this order)
+  DIN (PG_MODEL_DIN: attention of each candidate over the user's behaviour sequence, pooled, then the trunk above on
+  [user || item_row || pooled]; chosen when the file holds `wa`):
+      wa [4*64][att_h] (row blocks e, s, e-s, e*s; att_h 16 or 32)   ba [att_h]   wa2 [att_h] or [att_h][1]   ba2 scalar
+      w1 [d_user + 128][h1] (rows: user, item row, pooled)   b1, w2, b2 as above   w3 [h2] or [h2][n_out]   b3 [n_out]
   --d-user N says where the user half of w1 ends (or an integer array `d_user` inside the file); d_item = the table's dim
   (64 or 128).  --map w1=dense/kernel,b1=dense/bias,… renames arrays.  Supported hidden shapes: see the header.
 
@@ -26,7 +30,7 @@ import sys
 import numpy as np
 
 DNN3_SHAPES = {(128, 128), (256, 128), (256, 256), (512, 256), (1024, 512)}
-KIND_DNN3, KIND_DNN3_MULTI = 1, 3
+KIND_DNN3, KIND_DNN3_MULTI, KIND_DIN = 1, 3, 4
 
 
 def _f32(a, shape=None, what=""):
@@ -76,6 +80,22 @@ def pack_dnn3_arrays(w1, b1, w2, b2, w3, b3, d_user):
     return KIND_DNN3_MULTI, blob
 
 
+def pack_din_arrays(wa, ba, wa2, ba2, w1, b1, w2, b2, w3, b3, d_user):
+    """→ (KIND_DIN, blob): the activation unit's arrays in front of the trunk's, the trunk checked as a 128-wide DNN3."""
+    wa = np.asarray(wa)
+    if wa.ndim != 2 or wa.shape[0] != 256 or wa.shape[1] not in (16, 32):
+        raise ValueError("wa has shape %s, expected [256][att_h] with att_h 16 or 32 (a 64-wide item table)" % (tuple(wa.shape),))
+    att_h = wa.shape[1]
+    kind, trunk = pack_dnn3_arrays(w1, b1, w2, b2, w3, b3, d_user)
+    d_user_, d_item, h1, h2 = struct.unpack("<4I", trunk[:16])
+    if d_item != 128:
+        raise ValueError("w1 has %d rows behind the user's %d: a DIN's are 128 (item row, pooled)" % (d_item, d_user_))
+    n_out = 1 if kind == KIND_DNN3 else struct.unpack("<I", trunk[16:20])[0]
+    att = (_f32(wa, what="wa").tobytes() + _f32(np.reshape(ba, -1), (att_h,), "ba").tobytes() +
+           _f32(np.reshape(wa2, -1), (att_h,), "wa2").tobytes() + _f32(np.reshape(ba2, -1), (1,), "ba2").tobytes())
+    return KIND_DIN, struct.pack("<6I", d_user_, 64, h1, h2, n_out, att_h) + att + trunk[16 if kind == KIND_DNN3 else 20:]
+
+
 def pack_npz(path_or_mapping, d_user=None, rename=None):
     """Load the arrays (an .npz path or a mapping name → array) and pack them; → (kind, blob, description)."""
     z = np.load(path_or_mapping) if isinstance(path_or_mapping, (str, bytes)) else path_or_mapping
@@ -88,11 +108,15 @@ def pack_npz(path_or_mapping, d_user=None, rename=None):
         return z[key]
     if d_user is None:
         d_user = int(np.asarray(get("d_user")).reshape(-1)[0])
-    kind, blob = pack_dnn3_arrays(get("w1"), get("b1"), get("w2"), get("b2"), get("w3"), get("b3"), d_user)
+    trunk = [get(n) for n in ("w1", "b1", "w2", "b2", "w3", "b3")]
+    if rename.get("wa", "wa") in z:
+        kind, blob = pack_din_arrays(get("wa"), get("ba"), get("wa2"), get("ba2"), *trunk, d_user)
+    else:
+        kind, blob = pack_dnn3_arrays(*trunk, d_user)
     w1, w2 = get("w1"), get("w2")
-    n_out = 1 if kind == KIND_DNN3 else int(np.asarray(get("b3")).size)
-    desc = "%s [%d+%d]-%d-%d-%d, %d bytes" % ("PG_MODEL_DNN3" if kind == KIND_DNN3 else "PG_MODEL_DNN3_MULTI", d_user,
-                                              w1.shape[0] - d_user, w1.shape[1], w2.shape[1], n_out, len(blob))
+    n_out = int(np.asarray(get("b3")).size)
+    desc = "%s [%d+%d]-%d-%d-%d, %d bytes" % ({KIND_DNN3: "PG_MODEL_DNN3", KIND_DNN3_MULTI: "PG_MODEL_DNN3_MULTI", KIND_DIN: "PG_MODEL_DIN"}[kind],
+                                              d_user, w1.shape[0] - d_user, w1.shape[1], w2.shape[1], n_out, len(blob))
     return kind, blob, desc
 
 
