@@ -70,7 +70,7 @@ typedef enum {
  *                  Refused at load (PG_ERR_UNSUPPORTED): PG_MODEL_FM_TWOTOWER; a non-finite weight; a scaled weight or
  *                  scale factor outside fp32's normal range. */
 typedef enum { PG_PREC_F32 = 0, PG_PREC_BF16 = 1, PG_PREC_BF16X3 = 2, PG_PREC_F16X2 = 3, PG_PREC_F16 = 4 } pg_prec;
-typedef enum { PG_MODEL_DNN3 = 1, PG_MODEL_FM_TWOTOWER = 2, PG_MODEL_DNN3_MULTI = 3, PG_MODEL_DIN = 4 } pg_model_kind;
+typedef enum { PG_MODEL_DNN3 = 1, PG_MODEL_FM_TWOTOWER = 2, PG_MODEL_DNN3_MULTI = 3, PG_MODEL_DIN = 4, PG_MODEL_MMOE = 5 } pg_model_kind;
 
 const char* pg_last_error(void);
 const char* pg_version(void);
@@ -285,6 +285,39 @@ int pg_rank_din(pg_ctx* ctx, const pg_model* m, const pg_table* t, const float* 
 int pg_rank_din_dev(pg_ctx* ctx, const pg_model* m, const pg_table* t, const float* d_user_vecs, const uint32_t* d_seq_rows,
                     const uint32_t* d_seq_offsets, const uint32_t* d_cand_rows, const uint32_t* d_req_offsets, uint32_t n_req,
                     uint32_t n_items, float* d_out_scores);
+
+/* ---- rank: MMoE — gated experts and one tower per task (PG_MODEL_MMOE) ---------------------------------------------------------
+ *   Replaces  the remote multi-task model behind the reference's multi-valued answers: EasyrecResponse.multiValModule
+ *             (algorithm/eas/easyrec_response.go:35-70) returns one score list per output (probs_ctr, probs_cvr, ...), and
+ *             service/rank/rank_service.go:315-319 writes each back as <algo>_<output> (the job_rec_rank_8_x_probs_ctr properties of
+ *             web/complex_type_features_test.go).  PG_MODEL_DNN3_MULTI serves the shared-bottom form of such a model; this kind
+ *             serves the multi-gate mixture of experts.
+ *   Model     per candidate row e (d_item wide) of request r with user vector u, x = [ u | e ], E experts, T tasks:
+ *               a_k = relu( We_k' x + be_k )                 k = 0..E-1, h_e wide
+ *               g_t = softmax_k( Wg_t' x + bg_t )            t = 0..T-1, E wide, max-subtracted
+ *               m_t = sum_k g_t[k] a_k                       h_e wide
+ *               score_t = sigmoid( wo_t . relu( Wt_t' m_t + bt_t ) + bo_t )
+ *   Blob      u32 d_user (1..4096), d_item (64 or 128), n_expert, h_e ((2,128), (4,64), (4,128) or (8,64)), n_task (1..4),
+ *             h_t (32 or 64); We[E][d_user + d_item][h_e]; be[E][h_e]; Wg[T][d_user + d_item][E]; bg[T][E]; Wt[T][h_e][h_t];
+ *             bt[T][h_t]; wo[T][h_t]; bo[T] — little-endian fp32, every matrix [in][out].  tools/pack_model.py builds it.
+ *   Precision PG_PREC_BF16: the candidate row, every weight matrix and each m_t are rounded once (RNE) from their fp32 values; the
+ *             user half, the accumulation, the biases, relu, the softmax, the mix, the head dot and the sigmoid are fp32.
+ *             PG_PREC_BF16X3: exactly those operands split into hi + lo, three products per term, nothing else rounded; the
+ *             gate logits alone take a three-way split (the operands' fp32 values exactly), since the softmax exponentiates
+ *             them.
+ *   Output    as a multi-head model: out_scores[t * n_items + i], one plane per task; pg_model_num_outputs() = n_task.  A
+ *             candidate row >= the table's rows reads the last row in pg_rank_mmoe_dev, as pg_rank_dnn3_dev's gather does;
+ *             pg_rank_mmoe validates its rows as pg_rank_dnn3 does.
+ *   Refused   pg_model_load: a shape outside the lists above; PG_PREC_F32, PG_PREC_F16X2, PG_PREC_F16 (PG_ERR_UNSUPPORTED); a blob
+ *             of another length (PG_ERR_INVALID).  pg_rank_mmoe[_dev] (PG_ERR_INVALID, on the host, the context left usable): a
+ *             model of another kind, a table whose dim is not d_item.  pg_rank_dnn3[_dev], pg_rank_din[_dev] and
+ *             pg_coalescer_create_scene refuse a PG_MODEL_MMOE the same way.
+ *   Not here  PG_PREC_F32 and the fp16 precisions; two-layer experts or towers; PLE, ESMM and DBMTL; the coalescer and the
+ *             pg_recommend_* pipelines; E x h_e beyond 512. */
+int pg_rank_mmoe(pg_ctx* ctx, const pg_model* m, const pg_table* t, const float* user_vecs, const uint32_t* cand_rows,
+                 const uint32_t* req_offsets, uint32_t n_req, float* out_scores);
+int pg_rank_mmoe_dev(pg_ctx* ctx, const pg_model* m, const pg_table* t, const float* d_user_vecs, const uint32_t* d_cand_rows,
+                     const uint32_t* d_req_offsets, uint32_t n_req, uint32_t n_items, float* d_out_scores);
 /* FM + two-tower: user_field_ids [n_req][n_user_fields], item_field_ids [n_items][n_item_fields] */
 int pg_rank_fm2t(pg_ctx* ctx, const pg_model* m, const float* user_vecs,
                  const int32_t* user_field_ids, const int32_t* item_field_ids,

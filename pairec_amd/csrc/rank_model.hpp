@@ -59,6 +59,14 @@ struct pg_model {
     float* att_ba = nullptr;    // [att_h]
     float* att_wa2 = nullptr;   // [att_h]
     float att_ba2 = 0.f;
+    // PG_MODEL_MMOE (rank_mmoe.hip; pack_mmoe below): n_out = n_task; the tasks padded to mm_tp = 2 or 4
+    uint32_t n_expert = 0, h_e = 0, h_t = 0, mm_tp = 0;
+    float* mm_wu = nullptr;     // [d_user][32 + E h_e]: the user rows of Wg and We, columns in accumulator-row order
+    float* mm_bu = nullptr;     // [32 + E h_e]: bg and be in that order
+    void* mm_rec = nullptr;     // the gate record, then one record per step of 16 hidden units, in MFMA fragment order
+    float* mm_bt = nullptr;     // [mm_tp][h_t]
+    float* mm_wo = nullptr;     // [mm_tp][h_t]
+    float* mm_bo = nullptr;     // [mm_tp]
     float* b2 = nullptr;
     float* w3 = nullptr;    // DNN3 head(s): [n_out][h2]
     float* fields = nullptr;          // two-tower: all field tables, one allocation
@@ -83,6 +91,14 @@ constexpr int kH2S = 23;       // accumulators hold 2^S x the pre-activation; we
 inline bool dnn3_shape_ok(uint32_t h1, uint32_t h2) {
 #define X(A, B) if (h1 == A && h2 == B) return true;
     PG_DNN3_SHAPES(X)
+#undef X
+    return false;
+}
+// (n_expert, h_e) of an MMoE: E h_e = 256 or 512 layer-1 rows
+#define PG_MMOE_SHAPES(X) X(2, 128) X(4, 64) X(4, 128) X(8, 64)
+inline bool mmoe_shape_ok(uint32_t ne, uint32_t he) {
+#define X(A, B) if (ne == A && he == B) return true;
+    PG_MMOE_SHAPES(X)
 #undef X
     return false;
 }
@@ -180,6 +196,9 @@ struct BlobLayout {
     size_t field_floats = 0;      // floats of all field tables together
     // DIN, in front of the DNN3 arrays: Wa [4 x 64][att_h] (row blocks e, s, e - s, e * s), ba [att_h], wa2 [att_h], ba2
     size_t wa = 0, ba = 0, wa2 = 0, ba2 = 0;
+    // MMoE: We [E][d_user + d_item][h_e], be [E][h_e], Wg [T][d_user + d_item][E], bg [T][E], Wt [T][h_e][h_t], bt [T][h_t],
+    // wo [T][h_t], bo [T]
+    size_t we = 0, be = 0, wg = 0, bg = 0, wt = 0, bt = 0, wo = 0, bo = 0;
 };
 
 // What `blob` says as a model of `kind` in `prec`: the dimensions (and kind, prec, f16_nprod, b3, fm_b) into *m, the arrays'
@@ -194,6 +213,8 @@ inline int parse_model_blob(int kind, int prec, const void* blob, size_t len, pg
     if (f16_nprod && kind == PG_MODEL_DIN)
         return refuse(why, PG_ERR_UNSUPPORTED, "pg_model_load: PG_PREC_F16X2 / PG_PREC_F16 serve PG_MODEL_DNN3 and PG_MODEL_DNN3_MULTI; load a "
                                                "PG_MODEL_DIN in PG_PREC_F32, PG_PREC_BF16 or PG_PREC_BF16X3");
+    if (kind == PG_MODEL_MMOE && prec != PG_PREC_BF16 && prec != PG_PREC_BF16X3)
+        return refuse(why, PG_ERR_UNSUPPORTED, "pg_model_load: a PG_MODEL_MMOE is served in PG_PREC_BF16 and PG_PREC_BF16X3 (precision %d asked)", prec);
     const uint8_t* p = (const uint8_t*)blob;
     // an fp16 mode is the split-bf16 model (its whole-call and per-tile fallback) plus the fp16 operands
     m->prec = f16_nprod ? (int)PG_PREC_BF16X3 : prec;
@@ -254,6 +275,27 @@ inline int parse_model_blob(int kind, int prec, const void* blob, size_t len, pg
         lay->b3 = lay->w3 + (size_t)m->h2 * m->n_out * 4;
         memcpy(&m->att_ba2, p + lay->ba2, 4);
         memcpy(&m->b3, p + lay->b3, 4);
+    } else if (kind == PG_MODEL_MMOE) {
+        m->kind = PG_MODEL_MMOE;
+        if (len < 24) return refuse(why, PG_ERR_INVALID, "pg_model_load: blob too short");
+        uint32_t hdr[6];
+        memcpy(hdr, p, 24);
+        m->d_user = hdr[0]; m->d_item = hdr[1]; m->n_expert = hdr[2]; m->h_e = hdr[3]; m->n_out = hdr[4]; m->h_t = hdr[5];
+        if ((m->d_item != 128 && m->d_item != 64) || !mmoe_shape_ok(m->n_expert, m->h_e) || m->n_out == 0 || m->n_out > 4 ||
+            (m->h_t != 32 && m->h_t != 64) || m->d_user == 0 || m->d_user > 4096)
+            return refuse(why, PG_ERR_UNSUPPORTED, "pg_model_load: MMoE shape [%u+%u] -> %u experts x %u -> %u towers x %u unsupported (d_item 64 or "
+                                                   "128; experts x width 2x128, 4x64, 4x128, 8x64; 1..4 tasks; tower width 32 or 64)",
+                          m->d_user, m->d_item, m->n_expert, m->h_e, m->n_out, m->h_t);
+        m->mm_tp = m->n_out <= 2 ? 2 : 4;
+        const size_t din = (size_t)m->d_user + m->d_item, E = m->n_expert, he = m->h_e, T = m->n_out, ht = m->h_t;
+        const size_t nf[8] = {E * din * he, E * he, T * din * E, T * E, T * he * ht, T * ht, T * ht, T};
+        size_t* const at[8] = {&lay->we, &lay->be, &lay->wg, &lay->bg, &lay->wt, &lay->bt, &lay->wo, &lay->bo};
+        size_t need = 24;
+        for (int i = 0; i < 8; ++i) {
+            *at[i] = need;
+            need += nf[i] * 4;
+        }
+        if (len != need) return refuse(why, PG_ERR_INVALID, "pg_model_load: MMoE blob is %zu bytes, expected %zu", len, need);
     } else if (kind == PG_MODEL_FM_TWOTOWER) {
         m->kind = PG_MODEL_FM_TWOTOWER;
         if (len < 32) return refuse(why, PG_ERR_INVALID, "pg_model_load: blob too short");
@@ -414,6 +456,90 @@ inline void fold_din_attention(const float* wa, uint32_t att_h, std::vector<floa
     }
 }
 
+// PG_MODEL_MMOE: where rank_mmoe.hip wants each weight.  Candidates sit on the MFMA column axis, so a lane (item, half hk) holds
+// rows p = (r & 3) + 8 (r >> 2) + 4 hk, r = 0..15, of a 32-row accumulator block; mmoe_slot gives (hk, r) of row p.
+//   gate block (one):          slot G = 16 hk + r is logit (task G / E, expert G % E), zero rows from task T on: a lane half holds
+//                              whole tasks (16 % E = 0)
+//   layer 1, step s, block b:  slot q = 16 b + r of the step's 8 E slots per half is (expert q % E, hidden unit 16 s + 8 hk + q / E):
+//                              a lane holds all E experts of 8 consecutive hidden units, exactly the 8 k-values it supplies as the
+//                              tower product's B operand for the step's 16-deep slice
+// Column order of wu / bu (and of a request's c1): the 32 gate rows, then rows (s, b, p) ascending.
+inline void mmoe_slot(uint32_t p, uint32_t* hk, uint32_t* r) {
+    *hk = (p >> 2) & 1;
+    *r = (p & 3) + 4 * (p >> 3);
+}
+struct MmoePacked {
+    std::vector<float> wu, bu, bt, wo, bo;
+    std::vector<uint8_t> rec;
+};
+// (split bf16: the gate record carries THREE planes — hi, mid, lo = the weight's 24 bits exactly — because a logit is an exponent:
+//  two planes leave 2^-18 of a +-80 logit, which the softmax turns into 5e-7 of a score)
+constexpr size_t mmoe_gate_bytes(uint32_t d_item, int prec) { return (size_t)(d_item / 16) * (prec == 2 ? 3 : 1) * 1024; }
+constexpr size_t mmoe_step_bytes(uint32_t d_item, uint32_t E, uint32_t tp, uint32_t ht, int prec) {
+    return ((size_t)(E / 2) * (d_item / 16) + tp * ht / 32) * (prec == 2 ? 2 : 1) * 1024;
+}
+// Records in fragment order (1 KiB per fragment: lane l's 8 bf16 at 16 l; split bf16: the lo fragment follows its hi fragment, in
+// the gate record the mid and the lo fragment):
+//   gate record:    fragment ks          lane (p, hk') = Wg row (slot of p), item columns 16 ks + 8 hk' + 0..7
+//   step record s:  fragment b KS + ks   lane (p, hk') = We row (s, b, slot of p), the same columns;
+//                   then fragment tb = t h_t / 32 + hb: lane (i, hk') = Wt_t[16 s + 8 hk' + 0..7][32 hb + i]
+inline void pack_mmoe(const pg_model* m, const float* we, const float* be, const float* wg, const float* bg, const float* wt,
+                      const float* bt, const float* wo, const float* bo, MmoePacked* o) {
+    const uint32_t du = m->d_user, D = m->d_item, din = du + D, E = m->n_expert, he = m->h_e, T = m->n_out, ht = m->h_t, TP = m->mm_tp;
+    const uint32_t KS = D / 16, EB = E / 2, S = he / 16, NC = 32 + E * he, PL = m->prec == 2 ? 2 : 1, HB = ht / 32;
+    const size_t gbytes = mmoe_gate_bytes(D, m->prec), sbytes = mmoe_step_bytes(D, E, TP, ht, m->prec);
+    o->wu.assign((size_t)du * NC, 0.0f);
+    o->bu.assign(NC, 0.0f);
+    o->rec.assign(gbytes + S * sbytes, 0);
+    o->bt.assign((size_t)TP * ht, 0.0f);
+    o->wo.assign((size_t)TP * ht, 0.0f);
+    o->bo.assign(TP, 0.0f);
+    memcpy(o->bt.data(), bt, (size_t)T * ht * 4);
+    memcpy(o->wo.data(), wo, (size_t)T * ht * 4);
+    memcpy(o->bo.data(), bo, (size_t)T * 4);
+    // 8 consecutive k-values of one lane of fragment `frag` (of the record at `rec`)
+    auto put = [&](uint8_t* rec, uint32_t frag, uint32_t lane, const float* v, uint32_t planes) {
+        uint16_t* const d = reinterpret_cast<uint16_t*>(rec + (size_t)frag * planes * 1024 + lane * 16);
+        for (uint32_t e = 0; e < 8; ++e) {
+            float rest = v[e];
+            for (uint32_t pl = 0; pl < planes; ++pl) {
+                d[512 * pl + e] = f32_to_bf16_rne(rest);
+                rest -= bf16_to_f32(d[512 * pl + e]);       // (exact)
+            }
+        }
+    };
+    // one row of the big product: input-major column `col` of W ([din][ncol]) into column `c` of wu / bu and row p of `frag0 + ks`
+    auto row = [&](uint8_t* rec, uint32_t frag0, uint32_t planes, uint32_t p, uint32_t c, const float* W, uint32_t ncol, uint32_t col, float bias) {
+        for (uint32_t k = 0; k < du; ++k) o->wu[(size_t)k * NC + c] = round_prec(W[(size_t)k * ncol + col], m->prec);
+        o->bu[c] = bias;
+        for (uint32_t ks = 0; ks < KS; ++ks)
+            for (uint32_t hh = 0; hh < 2; ++hh) {
+                float v[8];
+                for (uint32_t e = 0; e < 8; ++e) v[e] = W[(size_t)(du + ks * 16 + 8 * hh + e) * ncol + col];
+                put(rec, frag0 + ks, hh * 32 + p, v, planes);
+            }
+    };
+    for (uint32_t p = 0; p < 32; ++p) {
+        uint32_t hk, r;
+        mmoe_slot(p, &hk, &r);
+        const uint32_t G = 16 * hk + r, t = G / E, k = G % E;
+        if (t < T) row(o->rec.data(), 0, PL == 2 ? 3 : 1, p, p, wg + (size_t)t * din * E, E, k, bg[t * E + k]);
+        for (uint32_t s = 0; s < S; ++s)
+            for (uint32_t b = 0; b < EB; ++b) {
+                const uint32_t q = 16 * b + r, x = q % E, j = 16 * s + 8 * hk + q / E;
+                row(o->rec.data() + gbytes + s * sbytes, b * KS, PL, p, 32 + (s * EB + b) * 32 + p, we + (size_t)x * din * he, he, j, be[x * he + j]);
+            }
+    }
+    for (uint32_t s = 0; s < S; ++s)
+        for (uint32_t t = 0; t < T; ++t)
+            for (uint32_t hb = 0; hb < HB; ++hb)
+                for (uint32_t lane = 0; lane < 64; ++lane) {
+                    float v[8];
+                    for (uint32_t e = 0; e < 8; ++e) v[e] = wt[((size_t)t * he + 16 * s + 8 * (lane >> 5) + e) * ht + 32 * hb + (lane & 31)];
+                    put(o->rec.data() + gbytes + s * sbytes, EB * KS + t * HB + hb, lane, v, PL);
+                }
+}
+
 // ---- what goes to the device ---------------------------------------------------------------------------------------------
 // One allocation of a loaded model: `bytes` from `src` (the blob, or a buffer ModelUploads owns) into a device buffer whose
 // address *dst receives; `lo`: the member that points at the second half of that buffer (the lo fragments of split operands).
@@ -447,7 +573,16 @@ inline int model_uploads(pg_model* m, const BlobLayout& lay, const void* blob, M
         up->packed.push_back(std::move(v));
         add(dst, up->packed.back().data(), up->packed.back().size(), lo);
     };
-    if (m->kind == PG_MODEL_DNN3 || m->kind == PG_MODEL_DIN) {
+    if (m->kind == PG_MODEL_MMOE) {
+        MmoePacked pk;
+        pack_mmoe(m, at(lay.we), at(lay.be), at(lay.wg), at(lay.bg), at(lay.wt), at(lay.bt), at(lay.wo), at(lay.bo), &pk);
+        add_floats(&m->mm_wu, std::move(pk.wu));
+        add_floats(&m->mm_bu, std::move(pk.bu));
+        add_packed(&m->mm_rec, std::move(pk.rec), nullptr);
+        add_floats(&m->mm_bt, std::move(pk.bt));
+        add_floats(&m->mm_wo, std::move(pk.wo));
+        add_floats(&m->mm_bo, std::move(pk.bo));
+    } else if (m->kind == PG_MODEL_DNN3 || m->kind == PG_MODEL_DIN) {
         const float *w1 = at(lay.w1), *w2 = at(lay.w2), *w3 = at(lay.w3);
         // a DIN's trunk is a DNN3 over the staged rows [e | pooled]: the item half of w1 is those 128 rows
         const uint32_t item_rows = m->kind == PG_MODEL_DIN ? 2 * m->d_item : m->d_item;

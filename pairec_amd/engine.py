@@ -14,7 +14,7 @@ import numpy as np
 from . import _lib
 
 PREC_F32, PREC_BF16, PREC_BF16X3, PREC_F16X2, PREC_F16 = 0, 1, 2, 3, 4
-MODEL_DNN3, MODEL_FM_TWOTOWER, MODEL_DNN3_MULTI, MODEL_DIN = 1, 2, 3, 4
+MODEL_DNN3, MODEL_FM_TWOTOWER, MODEL_DNN3_MULTI, MODEL_DIN, MODEL_MMOE = 1, 2, 3, 4, 5
 DIN_MAX_SEQ = 64
 MAX_QUERIES = 256         # per table pass (32 when dim > 128)
 
@@ -2238,6 +2238,18 @@ def pack_din(wa, ba, wa2, ba2, w1, b1, w2, b2, w3, b3, d_user: int) -> bytes:
             b3.tobytes())
 
 
+def pack_mmoe(we, be, wg, bg, wt, bt, wo, bo, d_user: int) -> bytes:
+    """PG_MODEL_MMOE blob (include/pairec_gpu.h): experts we [E][d_user + d_item][h_e], be [E][h_e]; gates wg [T][d_user + d_item][E],
+    bg [T][E]; towers wt [T][h_e][h_t], bt [T][h_t], wo [T][h_t], bo [T]."""
+    f = lambda a: np.ascontiguousarray(a, dtype=np.float32)   # noqa: E731
+    we, wg, wt = f(we), f(wg), f(wt)
+    (n_e, din, h_e), (n_t, _, h_t) = we.shape, wt.shape
+    assert wg.shape == (n_t, din, n_e) and wt.shape[1] == h_e and f(be).shape == (n_e, h_e) and f(bg).shape == (n_t, n_e)
+    assert f(bt).shape == (n_t, h_t) and f(wo).shape == (n_t, h_t) and f(bo).reshape(-1).shape == (n_t,)
+    return (struct.pack("<6I", d_user, din - d_user, n_e, h_e, n_t, h_t) + we.tobytes() + f(be).tobytes() + wg.tobytes() + f(bg).tobytes() +
+            wt.tobytes() + f(bt).tobytes() + f(wo).tobytes() + f(bo).tobytes())
+
+
 def pack_fm2t(w) -> bytes:
     """w: object with the attributes of oracle.Fm2tWeights (duck-typed; no oracle import here)."""
     parts = [struct.pack("<7If", w.nuf, w.nif, w.k, w.d_user, w.t_h1, w.t_out, w.vocab, w.fm_b)]
@@ -2314,6 +2326,19 @@ class RankModel:
         _lib.check(self.ctx.L.pg_rank_din_dev(self.ctx.h, self.h, table.h, C.c_void_p(d_user_vecs), C.c_void_p(d_seq_rows),
                                               C.c_void_p(d_seq_offsets), C.c_void_p(d_cand_rows), C.c_void_p(d_req_offsets),
                                               n_req, n_items, C.c_void_p(d_out)))
+
+    def rank_mmoe(self, table: Table, user_vecs: np.ndarray, cand_rows: np.ndarray, req_offsets: Sequence[int]) -> np.ndarray:
+        """MODEL_MMOE: scores [n_items] for one task, [n_task][n_items] for several (one plane per task)."""
+        u = np.ascontiguousarray(user_vecs, dtype=np.float32)
+        c = np.ascontiguousarray(cand_rows, dtype=np.uint32)
+        ro = np.ascontiguousarray(req_offsets, dtype=np.uint32)
+        out = np.empty((self.n_out, c.shape[0]), dtype=np.float32)
+        _lib.check(self.ctx.L.pg_rank_mmoe(self.ctx.h, self.h, table.h, _ptr(u), _ptr(c), _ptr(ro), ro.shape[0] - 1, _ptr(out)))
+        return out[0] if self.n_out == 1 else out
+
+    def rank_mmoe_dev(self, table: Table, d_user_vecs: int, d_cand_rows: int, d_req_offsets: int, n_req: int, n_items: int, d_out: int):
+        _lib.check(self.ctx.L.pg_rank_mmoe_dev(self.ctx.h, self.h, table.h, C.c_void_p(d_user_vecs), C.c_void_p(d_cand_rows),
+                                               C.c_void_p(d_req_offsets), n_req, n_items, C.c_void_p(d_out)))
 
     def rank_fm2t(self, user_vecs, user_field_ids, item_field_ids, req_offsets) -> np.ndarray:
         u = np.ascontiguousarray(user_vecs, dtype=np.float32)

@@ -18,6 +18,10 @@ Input: an .npz whose arrays are the layers' kernels exactly as a framework saves
   [user || item_row || pooled]; chosen when the file holds `wa`):
       wa [4*64][att_h] (row blocks e, s, e-s, e*s; att_h 16 or 32)   ba [att_h]   wa2 [att_h] or [att_h][1]   ba2 scalar
       w1 [d_user + 128][h1] (rows: user, item row, pooled)   b1, w2, b2 as above   w3 [h2] or [h2][n_out]   b3 [n_out]
+  MMoE (PG_MODEL_MMOE: E gated experts and one tower per task; chosen when the file holds `we`):
+      we [E][d_user + d_item][h_e]   be [E][h_e]   wg [T][d_user + d_item][E]   bg [T][E]
+      wt [T][h_e][h_t]   bt [T][h_t]   wo [T][h_t] or [T][h_t][1]   bo [T]
+      ((E, h_e) one of (2,128) (4,64) (4,128) (8,64); T 1..4; h_t 32 or 64; task t is the algorithm's t-th "Outputs" name)
   --d-user N says where the user half of w1 ends (or an integer array `d_user` inside the file); d_item = the table's dim
   (64 or 128).  --map w1=dense/kernel,b1=dense/bias,… renames arrays.  Supported hidden shapes: see the header.
 
@@ -30,7 +34,8 @@ import sys
 import numpy as np
 
 DNN3_SHAPES = {(128, 128), (256, 128), (256, 256), (512, 256), (1024, 512)}
-KIND_DNN3, KIND_DNN3_MULTI, KIND_DIN = 1, 3, 4
+KIND_DNN3, KIND_DNN3_MULTI, KIND_DIN, KIND_MMOE = 1, 3, 4, 5
+MMOE_SHAPES = {(2, 128), (4, 64), (4, 128), (8, 64)}
 
 
 def _f32(a, shape=None, what=""):
@@ -96,6 +101,26 @@ def pack_din_arrays(wa, ba, wa2, ba2, w1, b1, w2, b2, w3, b3, d_user):
     return KIND_DIN, struct.pack("<6I", d_user_, 64, h1, h2, n_out, att_h) + att + trunk[16 if kind == KIND_DNN3 else 20:]
 
 
+def pack_mmoe_arrays(we, be, wg, bg, wt, bt, wo, bo, d_user):
+    """→ (KIND_MMOE, blob, description)"""
+    we, wt = np.asarray(we), np.asarray(wt)
+    if we.ndim != 3 or wt.ndim != 3:
+        raise ValueError("we / wt must be 3-D: [E][in][h_e] and [T][h_e][h_t] (one [in][out] kernel per expert / task)")
+    (n_e, din, h_e), (n_t, _, h_t) = we.shape, wt.shape
+    d_user = int(d_user)
+    d_item = din - d_user
+    if not 1 <= d_user <= 4096 or d_item not in (64, 128):
+        raise ValueError("we has %d input rows: with d_user = %d the item half is %d wide (the table's dim: 64 or 128)" % (din, d_user, d_item))
+    if (n_e, h_e) not in MMOE_SHAPES or not 1 <= n_t <= 4 or h_t not in (32, 64):
+        raise ValueError("%d experts x %d, %d towers x %d have no kernel (experts: %s; 1..4 tasks; tower width 32 or 64)" %
+                         (n_e, h_e, n_t, h_t, sorted(MMOE_SHAPES)))
+    parts = [_f32(we, what="we"), _f32(be, (n_e, h_e), "be"), _f32(wg, (n_t, din, n_e), "wg"), _f32(bg, (n_t, n_e), "bg"),
+             _f32(wt, (n_t, h_e, h_t), "wt"), _f32(bt, (n_t, h_t), "bt"), _f32(np.reshape(wo, (n_t, -1)), (n_t, h_t), "wo"),
+             _f32(np.reshape(bo, -1), (n_t,), "bo")]
+    blob = struct.pack("<6I", d_user, d_item, n_e, h_e, n_t, h_t) + b"".join(a.tobytes() for a in parts)
+    return KIND_MMOE, blob, "PG_MODEL_MMOE [%d+%d] -> %d experts x %d -> %d towers x %d, %d bytes" % (d_user, d_item, n_e, h_e, n_t, h_t, len(blob))
+
+
 def pack_npz(path_or_mapping, d_user=None, rename=None):
     """Load the arrays (an .npz path or a mapping name → array) and pack them; → (kind, blob, description)."""
     z = np.load(path_or_mapping) if isinstance(path_or_mapping, (str, bytes)) else path_or_mapping
@@ -108,6 +133,8 @@ def pack_npz(path_or_mapping, d_user=None, rename=None):
         return z[key]
     if d_user is None:
         d_user = int(np.asarray(get("d_user")).reshape(-1)[0])
+    if rename.get("we", "we") in z:
+        return pack_mmoe_arrays(*[get(n) for n in ("we", "be", "wg", "bg", "wt", "bt", "wo", "bo")], d_user)
     trunk = [get(n) for n in ("w1", "b1", "w2", "b2", "w3", "b3")]
     if rename.get("wa", "wa") in z:
         kind, blob = pack_din_arrays(get("wa"), get("ba"), get("wa2"), get("ba2"), *trunk, d_user)
