@@ -70,7 +70,7 @@ typedef enum {
  *                  Refused at load (PG_ERR_UNSUPPORTED): PG_MODEL_FM_TWOTOWER; a non-finite weight; a scaled weight or
  *                  scale factor outside fp32's normal range. */
 typedef enum { PG_PREC_F32 = 0, PG_PREC_BF16 = 1, PG_PREC_BF16X3 = 2, PG_PREC_F16X2 = 3, PG_PREC_F16 = 4 } pg_prec;
-typedef enum { PG_MODEL_DNN3 = 1, PG_MODEL_FM_TWOTOWER = 2, PG_MODEL_DNN3_MULTI = 3, PG_MODEL_DIN = 4, PG_MODEL_MMOE = 5 } pg_model_kind;
+typedef enum { PG_MODEL_DNN3 = 1, PG_MODEL_FM_TWOTOWER = 2, PG_MODEL_DNN3_MULTI = 3, PG_MODEL_DIN = 4, PG_MODEL_MMOE = 5, PG_MODEL_DCN = 6 } pg_model_kind;
 
 const char* pg_last_error(void);
 const char* pg_version(void);
@@ -318,6 +318,38 @@ int pg_rank_mmoe(pg_ctx* ctx, const pg_model* m, const pg_table* t, const float*
                  const uint32_t* req_offsets, uint32_t n_req, float* out_scores);
 int pg_rank_mmoe_dev(pg_ctx* ctx, const pg_model* m, const pg_table* t, const float* d_user_vecs, const uint32_t* d_cand_rows,
                      const uint32_t* d_req_offsets, uint32_t n_req, uint32_t n_items, float* d_out_scores);
+
+/* ---- rank: DCN-v2 — explicit feature crosses under a DNN3 head (PG_MODEL_DCN) -----------------------------------------------------
+ *   Replaces  a remote ranking model whose backbone is a deep & cross network: the reference ships requests to PAI-EAS EasyRec
+ *             models (algorithm/eas, EasModel.Run) and carries no model arithmetic of its own; DCN-v2 is one of that zoo's stock
+ *             backbones.  The four other kinds interact [user | item] features only implicitly, through relu layers.
+ *   Model     stacked, full-rank cross matrices; per candidate row e (d_item wide) of request r with user vector u:
+ *               x_0     = [ u | e ]                                   D = d_user + d_item
+ *               x_{l+1} = x_0 * ( Wc_l' x_l + bc_l ) + x_l            l = 0 .. L-1   (* element-wise)
+ *               h1 = relu( W1' x_L + b1 )      h2 = relu( W2' h1 + b2 )
+ *               score_o = sigmoid( w3[:, o] . h2 + b3[o] )            o = 0 .. n_out-1
+ *   Blob      u32 d_user (1 .. 256 - d_item), d_item (64 or 128), n_cross (1..3), h1, h2 (128-128 or 256-128), n_out (1..4);
+ *             Wc[L][D][D]; bc[L][D]; w1[D][h1]; b1[h1]; w2[h1][h2]; b2[h2]; w3[h2][n_out]; b3[n_out] — little-endian fp32, every
+ *             matrix [in][out], input rows user first, then item.  The loader pads D with zero rows and columns to 128, 192 or
+ *             256 (a zero coordinate of x_0 stays zero through every cross layer).  tools/pack_model.py builds it.
+ *   Precision PG_PREC_BF16: rounded once (RNE) are the candidate row as layer 0's operand, every weight matrix (user rows
+ *             included), and x_l (l >= 1), x_L and h1 as matrix operands; u and the per-request user half of layer 0, the
+ *             accumulation, the biases, x_0 and x_l in the element-wise product and the residual, relu, the head dot and the
+ *             sigmoid are fp32.  PG_PREC_BF16X3: exactly those operands split into hi + lo, three products per term, nothing
+ *             else rounded.
+ *   Output    as a multi-head model: out_scores[o * n_items + i], one plane per head; pg_model_num_outputs() = n_out.  A
+ *             candidate row >= the table's rows reads the last row in pg_rank_dcn_dev, as pg_rank_dnn3_dev's gather does;
+ *             pg_rank_dcn validates its rows as pg_rank_dnn3 does.
+ *   Refused   pg_model_load: a shape outside the lists above; PG_PREC_F32, PG_PREC_F16X2, PG_PREC_F16 (PG_ERR_UNSUPPORTED); a blob
+ *             of another length (PG_ERR_INVALID).  pg_rank_dcn[_dev] (PG_ERR_INVALID, on the host, the context left usable): a
+ *             model of another kind, a table whose dim is not d_item.  pg_rank_dnn3[_dev], pg_rank_din[_dev], pg_rank_mmoe[_dev]
+ *             and pg_coalescer_create[_scene] refuse a PG_MODEL_DCN the same way.
+ *   Not here  low-rank and mixture cross layers; the parallel (cross || deep) structure; DCN-v1's vector cross; PG_PREC_F32 and
+ *             the fp16 precisions; the coalescer and the pg_recommend_* pipelines; D > 256. */
+int pg_rank_dcn(pg_ctx* ctx, const pg_model* m, const pg_table* t, const float* user_vecs, const uint32_t* cand_rows,
+                const uint32_t* req_offsets, uint32_t n_req, float* out_scores);
+int pg_rank_dcn_dev(pg_ctx* ctx, const pg_model* m, const pg_table* t, const float* d_user_vecs, const uint32_t* d_cand_rows,
+                    const uint32_t* d_req_offsets, uint32_t n_req, uint32_t n_items, float* d_out_scores);
 /* FM + two-tower: user_field_ids [n_req][n_user_fields], item_field_ids [n_items][n_item_fields] */
 int pg_rank_fm2t(pg_ctx* ctx, const pg_model* m, const float* user_vecs,
                  const int32_t* user_field_ids, const int32_t* item_field_ids,

@@ -98,6 +98,7 @@ enum ScratchSlot : int {
     kSlotHot = 37,           // hot.hip: the staged trigger offsets, sizes, ids and quotas of a list recall, behind them the sort records of the requests too long to order in LDS
     kSlotDin = 38,           // rank_din.hip: the staged rows [e | pooled], the identity candidate list, a run's offsets and its tile table (scratch_layout.hpp kDinRunItems bounds it; kSlotRankTiles stays the trunk's)
     kSlotMmoe = 39,          // rank_mmoe.hip: the tile table and the requests' user halves c1 of a PG_MODEL_MMOE call
+    kSlotDcn = 40,           // rank_dcn.hip: the tile table and the requests' user halves c0 (and x_0's user columns) of a PG_MODEL_DCN call
     kSlotCount
 };
 
@@ -567,6 +568,9 @@ int rank_din_dev_locked(pg_ctx* ctx, const pg_model* m, const pg_table* t, const
 // rank_mmoe.hip: a PG_MODEL_MMOE — gated experts and task towers, n_task planes of n_items scores
 int rank_mmoe_dev_locked(pg_ctx* ctx, const pg_model* m, const pg_table* t, const float* d_user, const uint32_t* d_cand,
                          const uint32_t* d_off, uint32_t n_req, uint32_t n_items, float* d_out);
+// rank_dcn.hip: a PG_MODEL_DCN — cross layers and a DNN3 head, n_out planes of n_items scores
+int rank_dcn_dev_locked(pg_ctx* ctx, const pg_model* m, const pg_table* t, const float* d_user, const uint32_t* d_cand,
+                        const uint32_t* d_off, uint32_t n_req, uint32_t n_items, float* d_out);
 int fm2t_user_embedding_locked(pg_ctx* ctx, const pg_model* m, const float* d_user, uint32_t n_req, float* d_out);
 // candidates as per-item field ids (d_ifids), or as rows of item records (ir, d_cand)
 int rank_fm2t_dev_locked(pg_ctx* ctx, const pg_model* m, const float* d_user, const int32_t* d_ufids, const int32_t* d_ifids,

@@ -67,6 +67,12 @@ struct pg_model {
     float* mm_bt = nullptr;     // [mm_tp][h_t]
     float* mm_wo = nullptr;     // [mm_tp][h_t]
     float* mm_bo = nullptr;     // [mm_tp]
+    // PG_MODEL_DCN (rank_dcn.hip; pack_dcn below): n_cross layers over x_0 padded to dc_dp columns, item columns first; the
+    // head's b1, b2, w3 ([n_out][h2]) and b3v are the members a DNN3 uses
+    uint32_t n_cross = 0, dc_dp = 0;
+    float* dc_wu = nullptr;     // [d_user][dc_dp]: the user rows of Wc_0 in the operand precision, columns in the kernel's order
+    float* dc_bc = nullptr;     // [n_cross][dc_dp]: the cross biases in that order
+    void* dc_rec = nullptr;     // every matrix as records of one 32-wide input block each, in MFMA fragment order
     float* b2 = nullptr;
     float* w3 = nullptr;    // DNN3 head(s): [n_out][h2]
     float* fields = nullptr;          // two-tower: all field tables, one allocation
@@ -101,6 +107,13 @@ inline bool mmoe_shape_ok(uint32_t ne, uint32_t he) {
     PG_MMOE_SHAPES(X)
 #undef X
     return false;
+}
+// PG_MODEL_DCN: D = d_user + d_item is padded to one of these widths (zero rows and columns: a zero coordinate of x_0 stays zero
+// through every cross layer); the head is a DNN3's 128-128 or 256-128
+constexpr uint32_t dcn_padded(uint32_t d) { return d <= 128 ? 128 : (d <= 192 ? 192 : 256); }
+inline bool dcn_shape_ok(uint32_t du, uint32_t di, uint32_t L, uint32_t h1, uint32_t h2, uint32_t n_out) {
+    return (di == 64 || di == 128) && du >= 1 && du + di <= 256 && L >= 1 && L <= 3 && (h1 == 128 || h1 == 256) && h2 == 128 && n_out >= 1 &&
+           n_out <= 4;
 }
 inline bool fm2t_shape_ok(uint32_t th, uint32_t to, uint32_t k) {
 #define X(A, B, C) if (th == A && to == B && k == C) return true;
@@ -199,6 +212,8 @@ struct BlobLayout {
     // MMoE: We [E][d_user + d_item][h_e], be [E][h_e], Wg [T][d_user + d_item][E], bg [T][E], Wt [T][h_e][h_t], bt [T][h_t],
     // wo [T][h_t], bo [T]
     size_t we = 0, be = 0, wg = 0, bg = 0, wt = 0, bt = 0, wo = 0, bo = 0;
+    // DCN, in front of the DNN3 arrays (w1 is [d_user + d_item][h1]): Wc [L][D][D], bc [L][D]
+    size_t wc = 0, bc = 0;
 };
 
 // What `blob` says as a model of `kind` in `prec`: the dimensions (and kind, prec, f16_nprod, b3, fm_b) into *m, the arrays'
@@ -215,6 +230,8 @@ inline int parse_model_blob(int kind, int prec, const void* blob, size_t len, pg
                                                "PG_MODEL_DIN in PG_PREC_F32, PG_PREC_BF16 or PG_PREC_BF16X3");
     if (kind == PG_MODEL_MMOE && prec != PG_PREC_BF16 && prec != PG_PREC_BF16X3)
         return refuse(why, PG_ERR_UNSUPPORTED, "pg_model_load: a PG_MODEL_MMOE is served in PG_PREC_BF16 and PG_PREC_BF16X3 (precision %d asked)", prec);
+    if (kind == PG_MODEL_DCN && prec != PG_PREC_BF16 && prec != PG_PREC_BF16X3)
+        return refuse(why, PG_ERR_UNSUPPORTED, "pg_model_load: a PG_MODEL_DCN is served in PG_PREC_BF16 and PG_PREC_BF16X3 (precision %d asked)", prec);
     const uint8_t* p = (const uint8_t*)blob;
     // an fp16 mode is the split-bf16 model (its whole-call and per-tile fallback) plus the fp16 operands
     m->prec = f16_nprod ? (int)PG_PREC_BF16X3 : prec;
@@ -296,6 +313,27 @@ inline int parse_model_blob(int kind, int prec, const void* blob, size_t len, pg
             need += nf[i] * 4;
         }
         if (len != need) return refuse(why, PG_ERR_INVALID, "pg_model_load: MMoE blob is %zu bytes, expected %zu", len, need);
+    } else if (kind == PG_MODEL_DCN) {
+        m->kind = PG_MODEL_DCN;
+        if (len < 24) return refuse(why, PG_ERR_INVALID, "pg_model_load: blob too short");
+        uint32_t hdr[6];
+        memcpy(hdr, p, 24);
+        m->d_user = hdr[0]; m->d_item = hdr[1]; m->n_cross = hdr[2]; m->h1 = hdr[3]; m->h2 = hdr[4]; m->n_out = hdr[5];
+        if (!dcn_shape_ok(m->d_user, m->d_item, m->n_cross, m->h1, m->h2, m->n_out))
+            return refuse(why, PG_ERR_UNSUPPORTED, "pg_model_load: DCN shape [%u+%u], %u cross layers -> %u -> %u -> %u outputs unsupported (d_item 64 "
+                                                   "or 128; d_user + d_item <= 256; 1..3 cross layers; hidden widths 128-128, 256-128; 1..4 outputs)",
+                          m->d_user, m->d_item, m->n_cross, m->h1, m->h2, m->n_out);
+        m->dc_dp = dcn_padded(m->d_user + m->d_item);
+        const size_t D = (size_t)m->d_user + m->d_item, L = m->n_cross;
+        const size_t nf[8] = {L * D * D, L * D, D * m->h1, m->h1, (size_t)m->h1 * m->h2, m->h2, (size_t)m->h2 * m->n_out, m->n_out};
+        size_t* const at[8] = {&lay->wc, &lay->bc, &lay->w1, &lay->b1, &lay->w2, &lay->b2, &lay->w3, &lay->b3};
+        size_t need = 24;
+        for (int i = 0; i < 8; ++i) {
+            *at[i] = need;
+            need += nf[i] * 4;
+        }
+        if (len != need) return refuse(why, PG_ERR_INVALID, "pg_model_load: DCN blob is %zu bytes, expected %zu", len, need);
+        memcpy(&m->b3, p + lay->b3, 4);
     } else if (kind == PG_MODEL_FM_TWOTOWER) {
         m->kind = PG_MODEL_FM_TWOTOWER;
         if (len < 32) return refuse(why, PG_ERR_INVALID, "pg_model_load: blob too short");
@@ -540,6 +578,69 @@ inline void pack_mmoe(const pg_model* m, const float* we, const float* be, const
                 }
 }
 
+// PG_MODEL_DCN: where rank_dcn.hip wants each weight.  The kernel's feature order g = 0 .. dc_dp - 1 puts the item columns first,
+// then the user columns, then the zero padding (dcn_source: g's index in the blob's [user | item] order).  Candidates sit on the
+// MFMA column axis and a lane (item, half hk) keeps a 32-feature block of x_l, of a bias or of an accumulator as 16 registers:
+// register r is feature 16 (r >> 3) + 8 hk + (r & 7) of the block — registers 0..7 and 8..15 are exactly the 8 k-values the lane
+// supplies as the next product's B operand for the block's two 16-deep slices.  Since the accumulator puts row p of a block in
+// (hk, r) = mmoe_slot(p), output row p of a block is made feature dcn_row(p) of it: only the OUTPUT columns of a matrix are
+// permuted, its input rows and every vector stay in feature order.
+inline uint32_t dcn_row(uint32_t p) {
+    uint32_t hk, r;
+    mmoe_slot(p, &hk, &r);
+    return 16 * (r >> 3) + 8 * hk + (r & 7);
+}
+inline int dcn_source(uint32_t g, uint32_t du, uint32_t di) { return g < di ? (int)(du + g) : (g < du + di ? (int)(g - di) : -1); }
+// a record: the two k-slices of one 32-wide input block against every 32-row output block (out / 32 fragments per slice)
+constexpr size_t dcn_rec_bytes(uint32_t out, int prec) { return (size_t)2 * (out / 32) * (prec == 2 ? 2 : 1) * 1024; }
+struct DcnPacked {
+    std::vector<float> wu, bc;
+    std::vector<uint8_t> rec;
+};
+// Records in the order the kernel consumes them: layer 0 (item input blocks only: the user half is c0), layers 1 .. L-1, w1, w2.
+// Fragment s (out / 32) + b of a record (1 KiB; split bf16: its lo fragment follows): lane (p, hk') = input features
+// 32 kb + 16 s + 8 hk' + 0..7, output feature 32 b + dcn_row(p).
+inline void pack_dcn(const pg_model* m, const float* wc, const float* bc, const float* w1, const float* w2, DcnPacked* o) {
+    const uint32_t du = m->d_user, di = m->d_item, D = du + di, DP = m->dc_dp, L = m->n_cross, h1 = m->h1, h2 = m->h2;
+    const uint32_t PL = m->prec == 2 ? 2 : 1;
+    o->wu.assign((size_t)du * DP, 0.0f);
+    o->bc.assign((size_t)L * DP, 0.0f);
+    for (uint32_t g = 0; g < DP; ++g) {
+        const int c = dcn_source(g, du, di);
+        if (c < 0) continue;
+        for (uint32_t k = 0; k < du; ++k) o->wu[(size_t)k * DP + g] = round_prec(wc[(size_t)k * D + c], m->prec);
+        for (uint32_t l = 0; l < L; ++l) o->bc[(size_t)l * DP + g] = bc[(size_t)l * D + c];
+    }
+    // W [.][ncol]: its first nkb 32-wide input blocks against `out` output features; cross_in / cross_out: that side is in the
+    // kernel's feature order (dcn_source), otherwise in the blob's
+    auto matrix = [&](const float* W, uint32_t ncol, uint32_t nkb, uint32_t out, bool cross_in, bool cross_out) {
+        const uint32_t NBO = out / 32;
+        const size_t at = o->rec.size(), rb = dcn_rec_bytes(out, m->prec);
+        o->rec.resize(at + nkb * rb, 0);
+        for (uint32_t kb = 0; kb < nkb; ++kb)
+            for (uint32_t s = 0; s < 2; ++s)
+                for (uint32_t b = 0; b < NBO; ++b)
+                    for (uint32_t lane = 0; lane < 64; ++lane) {
+                        const uint32_t go = 32 * b + dcn_row(lane & 31);
+                        const int col = cross_out ? dcn_source(go, du, di) : (int)go;
+                        uint16_t* const d = reinterpret_cast<uint16_t*>(o->rec.data() + at + kb * rb + (size_t)(s * NBO + b) * PL * 1024 + lane * 16);
+                        for (uint32_t e = 0; e < 8; ++e) {
+                            const uint32_t gi = 32 * kb + 16 * s + 8 * (lane >> 5) + e;
+                            const int row = cross_in ? dcn_source(gi, du, di) : (int)gi;
+                            float rest = row < 0 || col < 0 ? 0.0f : W[(size_t)row * ncol + col];
+                            for (uint32_t pl = 0; pl < PL; ++pl) {
+                                d[512 * pl + e] = f32_to_bf16_rne(rest);
+                                rest -= bf16_to_f32(d[512 * pl + e]);       // (exact)
+                            }
+                        }
+                    }
+    };
+    o->rec.clear();
+    for (uint32_t l = 0; l < L; ++l) matrix(wc + (size_t)l * D * D, D, l ? DP / 32 : di / 32, DP, true, true);
+    matrix(w1, h1, DP / 32, h1, true, false);
+    matrix(w2, h2, h1 / 32, h2, false, false);
+}
+
 // ---- what goes to the device ---------------------------------------------------------------------------------------------
 // One allocation of a loaded model: `bytes` from `src` (the blob, or a buffer ModelUploads owns) into a device buffer whose
 // address *dst receives; `lo`: the member that points at the second half of that buffer (the lo fragments of split operands).
@@ -573,7 +674,21 @@ inline int model_uploads(pg_model* m, const BlobLayout& lay, const void* blob, M
         up->packed.push_back(std::move(v));
         add(dst, up->packed.back().data(), up->packed.back().size(), lo);
     };
-    if (m->kind == PG_MODEL_MMOE) {
+    if (m->kind == PG_MODEL_DCN) {
+        DcnPacked pk;
+        pack_dcn(m, at(lay.wc), at(lay.bc), at(lay.w1), at(lay.w2), &pk);
+        const float* w3 = at(lay.w3);
+        std::vector<float> w3t((size_t)m->n_out * m->h2);          // head-major, as a DNN3's
+        for (uint32_t o = 0; o < m->n_out; ++o)
+            for (uint32_t j = 0; j < m->h2; ++j) w3t[(size_t)o * m->h2 + j] = w3[(size_t)j * m->n_out + o];
+        add_floats(&m->dc_wu, std::move(pk.wu));
+        add_floats(&m->dc_bc, std::move(pk.bc));
+        add_packed(&m->dc_rec, std::move(pk.rec), nullptr);
+        add(&m->b1, at(lay.b1), (size_t)m->h1 * 4);
+        add(&m->b2, at(lay.b2), (size_t)m->h2 * 4);
+        add_floats(&m->w3, std::move(w3t));
+        add(&m->b3v, at(lay.b3), (size_t)m->n_out * 4);
+    } else if (m->kind == PG_MODEL_MMOE) {
         MmoePacked pk;
         pack_mmoe(m, at(lay.we), at(lay.be), at(lay.wg), at(lay.bg), at(lay.wt), at(lay.bt), at(lay.wo), at(lay.bo), &pk);
         add_floats(&m->mm_wu, std::move(pk.wu));

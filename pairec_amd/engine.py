@@ -14,7 +14,7 @@ import numpy as np
 from . import _lib
 
 PREC_F32, PREC_BF16, PREC_BF16X3, PREC_F16X2, PREC_F16 = 0, 1, 2, 3, 4
-MODEL_DNN3, MODEL_FM_TWOTOWER, MODEL_DNN3_MULTI, MODEL_DIN, MODEL_MMOE = 1, 2, 3, 4, 5
+MODEL_DNN3, MODEL_FM_TWOTOWER, MODEL_DNN3_MULTI, MODEL_DIN, MODEL_MMOE, MODEL_DCN = 1, 2, 3, 4, 5, 6
 DIN_MAX_SEQ = 64
 MAX_QUERIES = 256         # per table pass (32 when dim > 128)
 
@@ -2250,6 +2250,20 @@ def pack_mmoe(we, be, wg, bg, wt, bt, wo, bo, d_user: int) -> bytes:
             wt.tobytes() + f(bt).tobytes() + f(wo).tobytes() + f(bo).tobytes())
 
 
+def pack_dcn(wc, bc, w1, b1, w2, b2, w3, b3, d_user: int) -> bytes:
+    """PG_MODEL_DCN blob (include/pairec_gpu.h): cross layers wc [L][D][D], bc [L][D] over x_0 = [user | item], D = d_user + d_item;
+    head w1 [D][h1], b1, w2 [h1][h2], b2, w3 [h2] or [h2][n_out], b3 [n_out]."""
+    f = lambda a: np.ascontiguousarray(a, dtype=np.float32)   # noqa: E731
+    wc, w1, w2 = f(wc), f(w1), f(w2)
+    (n_l, d, _), h1, h2 = wc.shape, w1.shape[1], w2.shape[1]
+    w3 = f(w3).reshape(h2, -1)
+    n_out = w3.shape[1]
+    assert wc.shape == (n_l, d, d) and f(bc).shape == (n_l, d) and w1.shape == (d, h1) and w2.shape == (h1, h2)
+    assert f(b1).shape == (h1,) and f(b2).shape == (h2,) and f(b3).reshape(-1).shape == (n_out,)
+    return (struct.pack("<6I", d_user, d - d_user, n_l, h1, h2, n_out) + wc.tobytes() + f(bc).tobytes() + w1.tobytes() + f(b1).tobytes() +
+            w2.tobytes() + f(b2).tobytes() + w3.tobytes() + f(b3).tobytes())
+
+
 def pack_fm2t(w) -> bytes:
     """w: object with the attributes of oracle.Fm2tWeights (duck-typed; no oracle import here)."""
     parts = [struct.pack("<7If", w.nuf, w.nif, w.k, w.d_user, w.t_h1, w.t_out, w.vocab, w.fm_b)]
@@ -2338,6 +2352,19 @@ class RankModel:
 
     def rank_mmoe_dev(self, table: Table, d_user_vecs: int, d_cand_rows: int, d_req_offsets: int, n_req: int, n_items: int, d_out: int):
         _lib.check(self.ctx.L.pg_rank_mmoe_dev(self.ctx.h, self.h, table.h, C.c_void_p(d_user_vecs), C.c_void_p(d_cand_rows),
+                                               C.c_void_p(d_req_offsets), n_req, n_items, C.c_void_p(d_out)))
+
+    def rank_dcn(self, table: Table, user_vecs: np.ndarray, cand_rows: np.ndarray, req_offsets: Sequence[int]) -> np.ndarray:
+        """MODEL_DCN: scores [n_items] for one output, [n_out][n_items] for several (one plane per head)."""
+        u = np.ascontiguousarray(user_vecs, dtype=np.float32)
+        c = np.ascontiguousarray(cand_rows, dtype=np.uint32)
+        ro = np.ascontiguousarray(req_offsets, dtype=np.uint32)
+        out = np.empty((self.n_out, c.shape[0]), dtype=np.float32)
+        _lib.check(self.ctx.L.pg_rank_dcn(self.ctx.h, self.h, table.h, _ptr(u), _ptr(c), _ptr(ro), ro.shape[0] - 1, _ptr(out)))
+        return out[0] if self.n_out == 1 else out
+
+    def rank_dcn_dev(self, table: Table, d_user_vecs: int, d_cand_rows: int, d_req_offsets: int, n_req: int, n_items: int, d_out: int):
+        _lib.check(self.ctx.L.pg_rank_dcn_dev(self.ctx.h, self.h, table.h, C.c_void_p(d_user_vecs), C.c_void_p(d_cand_rows),
                                                C.c_void_p(d_req_offsets), n_req, n_items, C.c_void_p(d_out)))
 
     def rank_fm2t(self, user_vecs, user_field_ids, item_field_ids, req_offsets) -> np.ndarray:

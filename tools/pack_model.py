@@ -22,6 +22,10 @@ Input: an .npz whose arrays are the layers' kernels exactly as a framework saves
       we [E][d_user + d_item][h_e]   be [E][h_e]   wg [T][d_user + d_item][E]   bg [T][E]
       wt [T][h_e][h_t]   bt [T][h_t]   wo [T][h_t] or [T][h_t][1]   bo [T]
       ((E, h_e) one of (2,128) (4,64) (4,128) (8,64); T 1..4; h_t 32 or 64; task t is the algorithm's t-th "Outputs" name)
+  DCN-v2 (PG_MODEL_DCN: stacked full-rank cross layers x_{l+1} = x_0 * (Wc_l' x_l + bc_l) + x_l, then the trunk above on x_L;
+  chosen when the file holds `wc`):
+      wc [L][D][D] (D = d_user + d_item <= 256; L 1..3)   bc [L][D]
+      w1 [D][h1]   b1, w2, b2 as above ((h1, h2) 128-128 or 256-128)   w3 [h2] or [h2][n_out]   b3 [n_out] (n_out 1..4)
   --d-user N says where the user half of w1 ends (or an integer array `d_user` inside the file); d_item = the table's dim
   (64 or 128).  --map w1=dense/kernel,b1=dense/bias,… renames arrays.  Supported hidden shapes: see the header.
 
@@ -34,8 +38,9 @@ import sys
 import numpy as np
 
 DNN3_SHAPES = {(128, 128), (256, 128), (256, 256), (512, 256), (1024, 512)}
-KIND_DNN3, KIND_DNN3_MULTI, KIND_DIN, KIND_MMOE = 1, 3, 4, 5
+KIND_DNN3, KIND_DNN3_MULTI, KIND_DIN, KIND_MMOE, KIND_DCN = 1, 3, 4, 5, 6
 MMOE_SHAPES = {(2, 128), (4, 64), (4, 128), (8, 64)}
+DCN_HEADS = {(128, 128), (256, 128)}
 
 
 def _f32(a, shape=None, what=""):
@@ -121,6 +126,27 @@ def pack_mmoe_arrays(we, be, wg, bg, wt, bt, wo, bo, d_user):
     return KIND_MMOE, blob, "PG_MODEL_MMOE [%d+%d] -> %d experts x %d -> %d towers x %d, %d bytes" % (d_user, d_item, n_e, h_e, n_t, h_t, len(blob))
 
 
+def pack_dcn_arrays(wc, bc, w1, b1, w2, b2, w3, b3, d_user):
+    """→ (KIND_DCN, blob, description)"""
+    wc, w1, w2 = np.asarray(wc), np.asarray(w1), np.asarray(w2)
+    if wc.ndim != 3 or wc.shape[1] != wc.shape[2] or w1.ndim != 2 or w2.ndim != 2:
+        raise ValueError("wc must be [L][D][D] (one square [in][out] kernel per cross layer), w1 and w2 2-D")
+    (n_l, d, _), h1, h2 = wc.shape, w1.shape[1], w2.shape[1]
+    d_user = int(d_user)
+    d_item = d - d_user
+    if d_user < 1 or d_item not in (64, 128) or d > 256:
+        raise ValueError("wc is %d wide: with d_user = %d the item half is %d wide (the table's dim: 64 or 128; at most 256 in all)" % (d, d_user, d_item))
+    w3 = np.reshape(w3, (h2, -1))
+    n_out = w3.shape[1]
+    if not 1 <= n_l <= 3 or (h1, h2) not in DCN_HEADS or not 1 <= n_out <= 4:
+        raise ValueError("%d cross layers, head %d-%d, %d outputs have no kernel (1..3 layers; heads: %s; 1..4 outputs)" %
+                         (n_l, h1, h2, n_out, sorted(DCN_HEADS)))
+    parts = [_f32(wc, what="wc"), _f32(bc, (n_l, d), "bc"), _f32(w1, (d, h1), "w1"), _f32(b1, (h1,), "b1"), _f32(w2, (h1, h2), "w2"),
+             _f32(b2, (h2,), "b2"), _f32(w3, what="w3"), _f32(np.reshape(b3, -1), (n_out,), "b3")]
+    blob = struct.pack("<6I", d_user, d_item, n_l, h1, h2, n_out) + b"".join(a.tobytes() for a in parts)
+    return KIND_DCN, blob, "PG_MODEL_DCN [%d+%d], %d cross layers -> %d -> %d -> %d, %d bytes" % (d_user, d_item, n_l, h1, h2, n_out, len(blob))
+
+
 def pack_npz(path_or_mapping, d_user=None, rename=None):
     """Load the arrays (an .npz path or a mapping name → array) and pack them; → (kind, blob, description)."""
     z = np.load(path_or_mapping) if isinstance(path_or_mapping, (str, bytes)) else path_or_mapping
@@ -136,6 +162,8 @@ def pack_npz(path_or_mapping, d_user=None, rename=None):
     if rename.get("we", "we") in z:
         return pack_mmoe_arrays(*[get(n) for n in ("we", "be", "wg", "bg", "wt", "bt", "wo", "bo")], d_user)
     trunk = [get(n) for n in ("w1", "b1", "w2", "b2", "w3", "b3")]
+    if rename.get("wc", "wc") in z:
+        return pack_dcn_arrays(get("wc"), get("bc"), *trunk, d_user)
     if rename.get("wa", "wa") in z:
         kind, blob = pack_din_arrays(get("wa"), get("ba"), get("wa2"), get("ba2"), *trunk, d_user)
     else:
