@@ -70,7 +70,7 @@ typedef enum {
  *                  Refused at load (PG_ERR_UNSUPPORTED): PG_MODEL_FM_TWOTOWER; a non-finite weight; a scaled weight or
  *                  scale factor outside fp32's normal range. */
 typedef enum { PG_PREC_F32 = 0, PG_PREC_BF16 = 1, PG_PREC_BF16X3 = 2, PG_PREC_F16X2 = 3, PG_PREC_F16 = 4 } pg_prec;
-typedef enum { PG_MODEL_DNN3 = 1, PG_MODEL_FM_TWOTOWER = 2, PG_MODEL_DNN3_MULTI = 3, PG_MODEL_DIN = 4, PG_MODEL_MMOE = 5, PG_MODEL_DCN = 6 } pg_model_kind;
+typedef enum { PG_MODEL_DNN3 = 1, PG_MODEL_FM_TWOTOWER = 2, PG_MODEL_DNN3_MULTI = 3, PG_MODEL_DIN = 4, PG_MODEL_MMOE = 5, PG_MODEL_DCN = 6, PG_MODEL_MHA = 8 /* 7 is kept unassigned: pg_model_load refuses it as unknown */ } pg_model_kind;
 
 const char* pg_last_error(void);
 const char* pg_version(void);
@@ -350,6 +350,46 @@ int pg_rank_dcn(pg_ctx* ctx, const pg_model* m, const pg_table* t, const float* 
                 const uint32_t* req_offsets, uint32_t n_req, float* out_scores);
 int pg_rank_dcn_dev(pg_ctx* ctx, const pg_model* m, const pg_table* t, const float* d_user_vecs, const uint32_t* d_cand_rows,
                     const uint32_t* d_req_offsets, uint32_t n_req, uint32_t n_items, float* d_out_scores);
+
+/* ---- rank: MHA — multi-head softmax target attention over the user's behaviour sequence (PG_MODEL_MHA) ---------------------------
+ *   Replaces  the remote sequence rankers the reference feeds a behaviour sequence to (Feature_Type_Sequence, SequenceLength of
+ *             recconf/recconf.go:202-212, with no bound of 64 on it): EasyRec's BST and multi-head target-attention blocks, long-
+ *             history models.  The sequence is passed as pg_rank_din's: request r's is seq_rows[seq_offsets[r] .. seq_offsets[r+1]),
+ *             rows of the table the candidates come from, up to PG_MHA_MAX_SEQ of them.
+ *   Model     per candidate row e (64 wide), valid sequence rows s_0 .. s_{L-1}, H = n_head heads of d_h = d_att / H columns:
+ *               q = Wq' e + bq      K_l = Wk' s_l      V_l = Wv' s_l + bv                                     (d_att each)
+ *               per head h:  a_l = q_h . K_lh / sqrt(d_h)    p = softmax over the valid l (max-subtracted)    o_h = sum_l p_l V_lh
+ *               pooled = Wo' [ o_0 | .. | o_{H-1} ]  (64)    score_o = DNN3 trunk on [ user | e | pooled ], heads as PG_MODEL_DNN3_MULTI
+ *             (no bk: q . bk is the same for every l and cancels in the softmax; no bo: b1 absorbs it)
+ *   Blob      u32 d_user, d_item (= 64), h1, h2, n_out (1..8), d_att, n_head — (d_att, n_head) one of (64,1) (64,2) (128,2) (128,4);
+ *             Wq[64][d_att]; bq[d_att]; Wk[64][d_att]; Wv[64][d_att]; bv[d_att]; Wo[d_att][64];
+ *             w1[d_user + 128][h1] (rows: user, e, pooled); b1; w2[h1][h2]; b2; w3[h2][n_out]; b3[n_out]
+ *             — little-endian fp32, every matrix [in][out]; (h1, h2) as PG_MODEL_DNN3.  tools/pack_model.py builds it.
+ *   Precision PG_PREC_F32, PG_PREC_BF16, PG_PREC_BF16X3 (its attention is the F32 form, in which nothing is rounded).  PG_PREC_BF16
+ *             rounds once (RNE): e as Wq's operand, and Wq; q as the logit product's operand; K and V as stored; the unnormalised
+ *             p = exp(a - m) as the P.V operand; the normalised o as Wo's operand, and Wo.  Kept fp32: the K/V projection itself,
+ *             every accumulation, the running max m, the exponent, the running sum l (it sums the unrounded p), the rescale and
+ *             1 / l, pooled as staged.
+ *   Masking   the valid positions are the first min(len, PG_MHA_MAX_SEQ) entries of the sequence whose row is below the table's row
+ *             count.  An entry that names a row the table no longer holds is LEFT OUT of the softmax (it is not a zero key: a
+ *             zero key would still take weight).  No valid position gives pooled = 0: the model is then the DNN3 of w1's user and
+ *             e rows.  A candidate row >= the table's rows reads the last row, as pg_rank_dnn3_dev's gather does.
+ *   Output    as pg_rank_dnn3: out_scores[o * n_items + i], one plane per head.
+ *   Refused   pg_model_load: PG_PREC_F16X2 / PG_PREC_F16, d_item != 64, a (d_att, n_head) outside the list, an unknown (h1, h2),
+ *             n_out outside 1..8 (PG_ERR_UNSUPPORTED); a blob of another length (PG_ERR_INVALID).  pg_rank_mha (PG_ERR_INVALID, on
+ *             the host, the context left usable): a sequence longer than PG_MHA_MAX_SEQ, offsets that descend or do not start at
+ *             0, a table whose dim is not 64, a model of another kind.  pg_rank_mha_dev cannot see the lengths: it uses the first
+ *             PG_MHA_MAX_SEQ entries of a longer sequence (a call of more than 256 requests reads its request offsets back to
+ *             cut its runs).  pg_rank_dnn3[_dev], pg_rank_din[_dev], pg_rank_mmoe[_dev], pg_rank_dcn[_dev] and
+ *             pg_coalescer_create[_scene] refuse a PG_MODEL_MHA.
+ *   Not here  position embeddings; BST's self-attention among the sequence items and its feed-forward block; d_h = 16; 128-wide
+ *             tables; sequence dimension fields (SequenceDimFields); the coalescer and the pg_recommend_* pipelines. */
+#define PG_MHA_MAX_SEQ 512
+int pg_rank_mha(pg_ctx* ctx, const pg_model* m, const pg_table* t, const float* user_vecs, const uint32_t* seq_rows,
+                const uint32_t* seq_offsets, const uint32_t* cand_rows, const uint32_t* req_offsets, uint32_t n_req, float* out_scores);
+int pg_rank_mha_dev(pg_ctx* ctx, const pg_model* m, const pg_table* t, const float* d_user_vecs, const uint32_t* d_seq_rows,
+                    const uint32_t* d_seq_offsets, const uint32_t* d_cand_rows, const uint32_t* d_req_offsets, uint32_t n_req,
+                    uint32_t n_items, float* d_out_scores);
 /* FM + two-tower: user_field_ids [n_req][n_user_fields], item_field_ids [n_items][n_item_fields] */
 int pg_rank_fm2t(pg_ctx* ctx, const pg_model* m, const float* user_vecs,
                  const int32_t* user_field_ids, const int32_t* item_field_ids,

@@ -99,6 +99,7 @@ enum ScratchSlot : int {
     kSlotDin = 38,           // rank_din.hip: the staged rows [e | pooled], the identity candidate list, a run's offsets and its tile table (scratch_layout.hpp kDinRunItems bounds it; kSlotRankTiles stays the trunk's)
     kSlotMmoe = 39,          // rank_mmoe.hip: the tile table and the requests' user halves c1 of a PG_MODEL_MMOE call
     kSlotDcn = 40,           // rank_dcn.hip: the tile table and the requests' user halves c0 (and x_0's user columns) of a PG_MODEL_DCN call
+    kSlotMha = 41,           // rank_mha.hip: kSlotDin's layout for a PG_MODEL_MHA run, behind it the run's n_valid and K/V records (scratch_layout.hpp kDinRunItems and kMhaRunReqs bound it)
     kSlotCount
 };
 
@@ -565,6 +566,11 @@ int rank_dnn3_dev_locked(pg_ctx* ctx, const pg_model* m, const pg_table* t, cons
 int rank_din_dev_locked(pg_ctx* ctx, const pg_model* m, const pg_table* t, const float* d_user, const uint32_t* d_seq_rows,
                         const uint32_t* d_seq_off, const uint32_t* d_cand, const uint32_t* d_off, uint32_t n_req, uint32_t n_items,
                         float* d_out);
+// rank_mha.hip: a PG_MODEL_MHA — softmax attention over each request's sequence rows, then rank_dnn3_dev_locked over the staged
+// rows; h_off (the offsets on the host) may be NULL for a call of at most kMhaRunReqs requests
+int rank_mha_dev_locked(pg_ctx* ctx, const pg_model* m, const pg_table* t, const float* d_user, const uint32_t* d_seq_rows,
+                        const uint32_t* d_seq_off, const uint32_t* d_cand, const uint32_t* d_off, const uint32_t* h_off,
+                        uint32_t n_req, uint32_t n_items, float* d_out);
 // rank_mmoe.hip: a PG_MODEL_MMOE — gated experts and task towers, n_task planes of n_items scores
 int rank_mmoe_dev_locked(pg_ctx* ctx, const pg_model* m, const pg_table* t, const float* d_user, const uint32_t* d_cand,
                          const uint32_t* d_off, uint32_t n_req, uint32_t n_items, float* d_out);

@@ -280,6 +280,10 @@ __global__ void din_run_kernel(const uint32_t* __restrict__ off, uint32_t n_req,
     if (i < hi - lo) ident[i] = i;
 }
 
+void din_run_launch(pg_ctx* ctx, const uint32_t* d_off, uint32_t n_req, uint32_t lo, uint32_t hi, uint32_t* loc_off, uint32_t* ident) {
+    din_run_kernel<<<(std::max(hi - lo, n_req + 1) + 255) / 256, 256, 0, ctx->stream>>>(d_off, n_req, lo, hi, loc_off, ident);
+}
+
 template <int BF16, int ATT_H>
 static int launch_din_attn(pg_ctx* ctx, const DinArgs& a, uint32_t grid) {
     constexpr size_t lds = din_lds_bytes(BF16, ATT_H);
@@ -336,7 +340,7 @@ int rank_din_dev_locked(pg_ctx* ctx, const pg_model* m, const pg_table* t, const
         TimersScope quiet(ctx, false);
         for (uint32_t lo = 0; lo < n_items; lo += kDinRunItems) {
             const uint32_t n = std::min(kDinRunItems, n_items - lo);
-            din_run_kernel<<<(std::max(n, n_req + 1) + 255) / 256, 256, 0, ctx->stream>>>(d_off, n_req, lo, lo + n, loc_off, ident);
+            din_run_launch(ctx, d_off, n_req, lo, lo + n, loc_off, ident);
             PG_HIP(hipGetLastError());
             if ((rc = build_tiles_launch(ctx, loc_off, n_req, max_tiles, kBM, tile_req, tile_item0, tile_cnt, n_tiles, req_tile0))) return rc;
             a.cand_rows = d_cand + lo;

@@ -247,6 +247,65 @@ int pg_rank_din(pg_ctx* ctx, const pg_model* m, const pg_table* t, const float* 
         });
 }
 
+int pg_rank_mha_dev(pg_ctx* ctx, const pg_model* m, const pg_table* t, const float* d_user_vecs, const uint32_t* d_seq_rows,
+                    const uint32_t* d_seq_offsets, const uint32_t* d_cand_rows, const uint32_t* d_req_offsets, uint32_t n_req,
+                    uint32_t n_items, float* d_out_scores) {
+    // (d_seq_rows may be NULL: every sequence empty)
+    PG_REQUIRE(ctx && m && t && d_user_vecs && d_seq_offsets && d_cand_rows && d_req_offsets && d_out_scores, "pg_rank_mha_dev: NULL argument");
+    PG_REQUIRE(m->kind == PG_MODEL_MHA, "pg_rank_mha_dev: model is not MHA");
+    PG_REQUIRE(t->dim == m->d_item && t->rows >= 1, "pg_rank_mha_dev: table dim %u != model d_item %u (or no rows)", t->dim, m->d_item);
+    PG_REQUIRE(n_req <= 65535, "pg_rank_mha_dev: at most 65535 requests per call");
+    std::lock_guard<std::mutex> g(ctx->mu);
+    pg::TableRead tr(t->rw);
+    // runs of at most kMhaRunReqs requests are cut on the host: a larger call's offsets are read back first
+    std::vector<uint32_t> h_off;
+    if (n_req > pg::kMhaRunReqs && n_items) {
+        h_off.resize((size_t)n_req + 1);
+        PG_HIP(hipMemcpyAsync(h_off.data(), d_req_offsets, h_off.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+        PG_HIP(hipStreamSynchronize(ctx->stream));
+        PG_REQUIRE(h_off[0] == 0 && h_off[n_req] == n_items, "pg_rank_mha_dev: the offsets do not span the %u candidates", n_items);
+        for (uint32_t r = 0; r < n_req; ++r) PG_REQUIRE(h_off[r + 1] >= h_off[r], "pg_rank_mha_dev: req_offsets not monotone at %u", r);
+    }
+    return pg::rank_mha_dev_locked(ctx, m, t, d_user_vecs, d_seq_rows, d_seq_offsets, d_cand_rows, d_req_offsets,
+                                   h_off.empty() ? nullptr : h_off.data(), n_req, n_items, d_out_scores);
+}
+
+int pg_rank_mha(pg_ctx* ctx, const pg_model* m, const pg_table* t, const float* user_vecs, const uint32_t* seq_rows,
+                const uint32_t* seq_offsets, const uint32_t* cand_rows, const uint32_t* req_offsets, uint32_t n_req, float* out_scores) {
+    PG_REQUIRE(ctx && m && t && req_offsets, "pg_rank_mha: NULL argument");
+    PG_REQUIRE(m->kind == PG_MODEL_MHA, "pg_rank_mha: model is not MHA");
+    PG_REQUIRE(t->dim == m->d_item && t->rows >= 1, "pg_rank_mha: table dim %u != model d_item %u (or no rows)", t->dim, m->d_item);
+    PG_REQUIRE(n_req == 0 || seq_offsets, "pg_rank_mha: NULL argument");
+    uint32_t n_seq = 0;
+    if (n_req && n_req <= 65535) {
+        PG_REQUIRE(seq_offsets[0] == 0, "pg_rank_mha: seq_offsets[0] must be 0");
+        for (uint32_t r = 0; r < n_req; ++r) {
+            PG_REQUIRE(seq_offsets[r + 1] >= seq_offsets[r], "pg_rank_mha: seq_offsets not monotone at %u", r);
+            PG_REQUIRE(seq_offsets[r + 1] - seq_offsets[r] <= PG_MHA_MAX_SEQ, "pg_rank_mha: request %u has a sequence of %u rows, at most %d",
+                       r, seq_offsets[r + 1] - seq_offsets[r], PG_MHA_MAX_SEQ);
+        }
+        n_seq = seq_offsets[n_req];
+        PG_REQUIRE(n_seq == 0 || seq_rows, "pg_rank_mha: NULL argument");
+    }
+    // the sequences are staged in kSlotRows as pg_rank_din's: their rows (a dummy word when there are none), then the offsets
+    static const uint32_t no_rows[1] = {0};
+    const pg::HostIn in[] = {{user_vecs, false, m->d_user, 4}, {cand_rows, true, 1, 4}};
+    return pg::rank_from_host(
+        "pg_rank_mha", ctx, m, t, in, nullptr, req_offsets, n_req, out_scores, pg::no_check,
+        [&](void* const* d, const uint32_t* d_off, uint32_t n_items, float* d_scores) -> int {
+            uint32_t *d_sr, *d_so;
+            int rc;
+            if ((rc = pg::scratch_carve(ctx, pg::kSlotRows, [&](pg::Carve& c) {
+                    d_sr = c.take<uint32_t>(n_seq ? n_seq : 1);
+                    d_so = c.take<uint32_t>((size_t)n_req + 1);
+                }))) return rc;
+            PG_HIP(hipMemcpyAsync(d_sr, n_seq ? seq_rows : no_rows, (size_t)(n_seq ? n_seq : 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+            PG_HIP(hipMemcpyAsync(d_so, seq_offsets, ((size_t)n_req + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+            return pg::rank_mha_dev_locked(ctx, m, t, (const float*)d[0], d_sr, d_so, (const uint32_t*)d[1], d_off, req_offsets, n_req, n_items,
+                                           d_scores);
+        });
+}
+
 int pg_rank_mmoe_dev(pg_ctx* ctx, const pg_model* m, const pg_table* t, const float* d_user_vecs, const uint32_t* d_cand_rows,
                      const uint32_t* d_req_offsets, uint32_t n_req, uint32_t n_items, float* d_out_scores) {
     PG_REQUIRE(ctx && m && t && d_user_vecs && d_cand_rows && d_req_offsets && d_out_scores, "pg_rank_mmoe_dev: NULL argument");

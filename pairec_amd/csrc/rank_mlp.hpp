@@ -159,6 +159,10 @@ __device__ __forceinline__ void store_h_quad(char* tile, int row, int col, float
 int build_tiles_launch(pg_ctx* ctx, const uint32_t* d_off, uint32_t n_req, uint32_t max_tiles, uint32_t tile_items,
                        uint32_t* tile_req, uint32_t* tile_item0, uint32_t* tile_cnt, uint32_t* n_tiles, uint32_t* req_tile0);
 
+// rank_din.hip: a run's own offsets (the call's, clamped to the run's candidates [lo, hi) and rebased) into loc_off [n_req + 1] and
+// the identity candidate list into ident [hi - lo] (rank_mha.hip cuts its runs with it)
+void din_run_launch(pg_ctx* ctx, const uint32_t* d_off, uint32_t n_req, uint32_t lo, uint32_t hi, uint32_t* loc_off, uint32_t* ident);
+
 // rank_ws.hip: the weights-stationary DNN3 kernel (bf16); `a` describes 64-item tiles
 constexpr int kWsItems = 64;
 int launch_dnn3_ws(pg_ctx* ctx, const MlpArgs& a);

@@ -73,6 +73,15 @@ struct pg_model {
     float* dc_wu = nullptr;     // [d_user][dc_dp]: the user rows of Wc_0 in the operand precision, columns in the kernel's order
     float* dc_bc = nullptr;     // [n_cross][dc_dp]: the cross biases in that order
     void* dc_rec = nullptr;     // every matrix as records of one 32-wide input block each, in MFMA fragment order
+    // PG_MODEL_MHA (rank_mha.hip; pack_mha below): mh_heads heads over mh_datt attention columns; the trunk's members are a DNN3's
+    // whose item half is the 128 rows [e | pooled] of w1, as a DIN's
+    uint32_t mh_datt = 0, mh_heads = 0;
+    void* mh_wq = nullptr;      // Wq [64][d_att] in MFMA fragment order (bf16 or fp32), output columns in mha_row order
+    float* mh_bq = nullptr;     // [d_att] in that order
+    float* mh_wk = nullptr;     // [64][d_att] fp32, feature order
+    float* mh_wv = nullptr;     // [64][d_att] fp32, output columns in mha_row order
+    float* mh_bv = nullptr;     // [d_att] in that order
+    void* mh_wo = nullptr;      // Wo [d_att][64] in MFMA fragment order, input rows in feature order
     float* b2 = nullptr;
     float* w3 = nullptr;    // DNN3 head(s): [n_out][h2]
     float* fields = nullptr;          // two-tower: all field tables, one allocation
@@ -114,6 +123,14 @@ constexpr uint32_t dcn_padded(uint32_t d) { return d <= 128 ? 128 : (d <= 192 ? 
 inline bool dcn_shape_ok(uint32_t du, uint32_t di, uint32_t L, uint32_t h1, uint32_t h2, uint32_t n_out) {
     return (di == 64 || di == 128) && du >= 1 && du + di <= 256 && L >= 1 && L <= 3 && (h1 == 128 || h1 == 256) && h2 == 128 && n_out >= 1 &&
            n_out <= 4;
+}
+// (d_att, n_head) of a PG_MODEL_MHA: head widths 32 and 64
+#define PG_MHA_SHAPES(X) X(64, 1) X(64, 2) X(128, 2) X(128, 4)
+inline bool mha_shape_ok(uint32_t datt, uint32_t heads) {
+#define X(A, B) if (datt == A && heads == B) return true;
+    PG_MHA_SHAPES(X)
+#undef X
+    return false;
 }
 inline bool fm2t_shape_ok(uint32_t th, uint32_t to, uint32_t k) {
 #define X(A, B, C) if (th == A && to == B && k == C) return true;
@@ -214,6 +231,8 @@ struct BlobLayout {
     size_t we = 0, be = 0, wg = 0, bg = 0, wt = 0, bt = 0, wo = 0, bo = 0;
     // DCN, in front of the DNN3 arrays (w1 is [d_user + d_item][h1]): Wc [L][D][D], bc [L][D]
     size_t wc = 0, bc = 0;
+    // MHA, in front of the DNN3 arrays: Wq [64][d_att], bq [d_att], Wk [64][d_att], Wv [64][d_att], bv [d_att], Wo [d_att][64]
+    size_t a_wq = 0, a_bq = 0, a_wk = 0, a_wv = 0, a_bv = 0, a_wo = 0;
 };
 
 // What `blob` says as a model of `kind` in `prec`: the dimensions (and kind, prec, f16_nprod, b3, fm_b) into *m, the arrays'
@@ -228,6 +247,9 @@ inline int parse_model_blob(int kind, int prec, const void* blob, size_t len, pg
     if (f16_nprod && kind == PG_MODEL_DIN)
         return refuse(why, PG_ERR_UNSUPPORTED, "pg_model_load: PG_PREC_F16X2 / PG_PREC_F16 serve PG_MODEL_DNN3 and PG_MODEL_DNN3_MULTI; load a "
                                                "PG_MODEL_DIN in PG_PREC_F32, PG_PREC_BF16 or PG_PREC_BF16X3");
+    if (f16_nprod && kind == PG_MODEL_MHA)
+        return refuse(why, PG_ERR_UNSUPPORTED, "pg_model_load: PG_PREC_F16X2 / PG_PREC_F16 serve PG_MODEL_DNN3 and PG_MODEL_DNN3_MULTI; load a "
+                                               "PG_MODEL_MHA in PG_PREC_F32, PG_PREC_BF16 or PG_PREC_BF16X3");
     if (kind == PG_MODEL_MMOE && prec != PG_PREC_BF16 && prec != PG_PREC_BF16X3)
         return refuse(why, PG_ERR_UNSUPPORTED, "pg_model_load: a PG_MODEL_MMOE is served in PG_PREC_BF16 and PG_PREC_BF16X3 (precision %d asked)", prec);
     if (kind == PG_MODEL_DCN && prec != PG_PREC_BF16 && prec != PG_PREC_BF16X3)
@@ -291,6 +313,30 @@ inline int parse_model_blob(int kind, int prec, const void* blob, size_t len, pg
         lay->w3 = lay->b2 + (size_t)m->h2 * 4;
         lay->b3 = lay->w3 + (size_t)m->h2 * m->n_out * 4;
         memcpy(&m->att_ba2, p + lay->ba2, 4);
+        memcpy(&m->b3, p + lay->b3, 4);
+    } else if (kind == PG_MODEL_MHA) {
+        m->kind = PG_MODEL_MHA;
+        if (len < 28) return refuse(why, PG_ERR_INVALID, "pg_model_load: blob too short");
+        uint32_t hdr[7];
+        memcpy(hdr, p, 28);
+        m->d_user = hdr[0]; m->d_item = hdr[1]; m->h1 = hdr[2]; m->h2 = hdr[3]; m->n_out = hdr[4]; m->mh_datt = hdr[5]; m->mh_heads = hdr[6];
+        if (m->n_out == 0 || m->n_out > (uint32_t)kMaxHeads)
+            return refuse(why, PG_ERR_UNSUPPORTED, "pg_model_load: an MHA has 1..%d outputs, the blob says %u", kMaxHeads, m->n_out);
+        if (m->d_item != (uint32_t)kDinD || !mha_shape_ok(m->mh_datt, m->mh_heads) || !dnn3_shape_ok(m->h1, m->h2) || m->d_user == 0 ||
+            m->d_user > 4096)
+            return refuse(why, PG_ERR_UNSUPPORTED, "pg_model_load: MHA shape [%u+2x%u]->%u->%u, d_att %u in %u heads unsupported (d_item 64; (d_att, heads) "
+                                                   "(64,1) (64,2) (128,2) (128,4); hidden widths 128-128, 256-128, 256-256, 512-256, 1024-512)",
+                          m->d_user, m->d_item, m->h1, m->h2, m->mh_datt, m->mh_heads);
+        const size_t da = m->mh_datt, din = (size_t)m->d_user + 2 * kDinD;
+        const size_t nf[12] = {kDinD * da, da, kDinD * da, kDinD * da, da, da * kDinD, din * m->h1, m->h1, (size_t)m->h1 * m->h2, m->h2,
+                               (size_t)m->h2 * m->n_out, m->n_out};
+        size_t* const at[12] = {&lay->a_wq, &lay->a_bq, &lay->a_wk, &lay->a_wv, &lay->a_bv, &lay->a_wo, &lay->w1, &lay->b1, &lay->w2, &lay->b2, &lay->w3, &lay->b3};
+        size_t need = 28;
+        for (int i = 0; i < 12; ++i) {
+            *at[i] = need;
+            need += nf[i] * 4;
+        }
+        if (len != need) return refuse(why, PG_ERR_INVALID, "pg_model_load: MHA blob is %zu bytes, expected %zu", len, need);
         memcpy(&m->b3, p + lay->b3, 4);
     } else if (kind == PG_MODEL_MMOE) {
         m->kind = PG_MODEL_MMOE;
@@ -641,6 +687,41 @@ inline void pack_dcn(const pg_model* m, const float* wc, const float* bc, const 
     matrix(w2, h2, h1 / 32, h2, false, false);
 }
 
+// PG_MODEL_MHA: where rank_mha.hip wants each weight.  Candidates sit on the MFMA column axis and a lane (candidate, half hk) holds
+// rows p = (r & 3) + 8 (r >> 2) + 4 hk of a 32-row accumulator block, (hk, r) = mmoe_slot(p).  mha_row(p) is the feature of the
+// block that row p is made to hold, so that register r is the feature the lane supplies as the next product's B operand: in the
+// BF16 form 16 (r >> 3) + 8 hk + (r & 7) (dcn_row: registers 0..7 and 8..15 are the two 16-deep slices), in the F32 form 2 r + hk
+// (register r is step r of the 2-deep MFMA).  Permuted by it, within each 32-wide block and so within each head: the OUTPUT columns
+// of Wq (and bq), whose accumulators meet K in feature order in the logit product, and the output columns of Wv (and bv), whose
+// P.V accumulators meet Wo's input rows in feature order.  Wk and Wo keep the blob's order.  Nothing is scaled here: the kernel
+// applies log2(e) / sqrt(d_h) inside the exponent, so Wq is rounded (BF16 form) from the blob's value.
+inline uint32_t mha_row(uint32_t p, bool bf16) {
+    uint32_t hk, r;
+    mmoe_slot(p, &hk, &r);
+    return bf16 ? 16 * (r >> 3) + 8 * hk + (r & 7) : 2 * r + hk;
+}
+struct MhaPacked {
+    std::vector<float> bq, wv, bv;
+    std::vector<uint8_t> wq, wo;
+};
+inline void pack_mha(const pg_model* m, const float* wq, const float* bq, const float* wv, const float* bv, const float* wo, MhaPacked* o) {
+    const uint32_t da = m->mh_datt;
+    const bool bf16 = m->prec == 1;         // split bf16 (prec 2) runs the F32 attention in front of its trunk
+    std::vector<float> wqp((size_t)kDinD * da);
+    o->bq.resize(da); o->bv.resize(da); o->wv.resize((size_t)kDinD * da);
+    for (uint32_t c = 0; c < da; ++c) {
+        const uint32_t src = (c & ~31u) + mha_row(c & 31u, bf16);
+        o->bq[c] = bq[src];
+        o->bv[c] = bv[src];
+        for (uint32_t k = 0; k < (uint32_t)kDinD; ++k) {
+            wqp[(size_t)k * da + c] = wq[(size_t)k * da + src];
+            o->wv[(size_t)k * da + c] = wv[(size_t)k * da + src];
+        }
+    }
+    o->wq = pack_weights(wqp.data(), kDinD, da, bf16 ? 1 : 0);
+    o->wo = pack_weights(wo, da, kDinD, bf16 ? 1 : 0);
+}
+
 // ---- what goes to the device ---------------------------------------------------------------------------------------------
 // One allocation of a loaded model: `bytes` from `src` (the blob, or a buffer ModelUploads owns) into a device buffer whose
 // address *dst receives; `lo`: the member that points at the second half of that buffer (the lo fragments of split operands).
@@ -697,10 +778,20 @@ inline int model_uploads(pg_model* m, const BlobLayout& lay, const void* blob, M
         add_floats(&m->mm_bt, std::move(pk.bt));
         add_floats(&m->mm_wo, std::move(pk.wo));
         add_floats(&m->mm_bo, std::move(pk.bo));
-    } else if (m->kind == PG_MODEL_DNN3 || m->kind == PG_MODEL_DIN) {
+    } else if (m->kind == PG_MODEL_DNN3 || m->kind == PG_MODEL_DIN || m->kind == PG_MODEL_MHA) {
         const float *w1 = at(lay.w1), *w2 = at(lay.w2), *w3 = at(lay.w3);
-        // a DIN's trunk is a DNN3 over the staged rows [e | pooled]: the item half of w1 is those 128 rows
-        const uint32_t item_rows = m->kind == PG_MODEL_DIN ? 2 * m->d_item : m->d_item;
+        // a DIN's or an MHA's trunk is a DNN3 over the staged rows [e | pooled]: the item half of w1 is those 128 rows
+        const uint32_t item_rows = m->kind == PG_MODEL_DNN3 ? m->d_item : 2 * m->d_item;
+        if (m->kind == PG_MODEL_MHA) {
+            MhaPacked pk;
+            pack_mha(m, at(lay.a_wq), at(lay.a_bq), at(lay.a_wv), at(lay.a_bv), at(lay.a_wo), &pk);
+            add_packed(&m->mh_wq, std::move(pk.wq), nullptr);
+            add_floats(&m->mh_bq, std::move(pk.bq));
+            add(&m->mh_wk, at(lay.a_wk), (size_t)kDinD * m->mh_datt * 4);
+            add_floats(&m->mh_wv, std::move(pk.wv));
+            add_floats(&m->mh_bv, std::move(pk.bv));
+            add_packed(&m->mh_wo, std::move(pk.wo), nullptr);
+        }
         if (m->kind == PG_MODEL_DIN) {
             std::vector<float> wq, wk, wp;
             fold_din_attention(at(lay.wa), m->att_h, &wq, &wk, &wp);

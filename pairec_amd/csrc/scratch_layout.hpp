@@ -11,6 +11,9 @@ namespace pg {
 // rebased) and is tiled on its own, so a request that straddles a boundary is attended and ranked in both runs, each with
 // the request's whole sequence and user vector, and its scores land where one run would have put them.
 constexpr uint32_t kDinRunItems = 1u << 17;
+// kSlotMha (rank_mha.hip): a run of a PG_MODEL_MHA call is cut the same way and also covers at most this many REQUESTS, whose
+// projected keys and values (512 positions x d_att x 2 x 4 B at most each) it keeps: 128 MiB at most beside the staged rows.
+constexpr uint32_t kMhaRunReqs = 256;
 
 // x rounded up to a multiple of a (a power of two); 256 bytes is the arena's default region alignment
 inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) & ~(a - 1); }

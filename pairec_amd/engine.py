@@ -14,8 +14,9 @@ import numpy as np
 from . import _lib
 
 PREC_F32, PREC_BF16, PREC_BF16X3, PREC_F16X2, PREC_F16 = 0, 1, 2, 3, 4
-MODEL_DNN3, MODEL_FM_TWOTOWER, MODEL_DNN3_MULTI, MODEL_DIN, MODEL_MMOE, MODEL_DCN = 1, 2, 3, 4, 5, 6
+MODEL_DNN3, MODEL_FM_TWOTOWER, MODEL_DNN3_MULTI, MODEL_DIN, MODEL_MMOE, MODEL_DCN, MODEL_MHA = 1, 2, 3, 4, 5, 6, 8
 DIN_MAX_SEQ = 64
+MHA_MAX_SEQ = 512
 MAX_QUERIES = 256         # per table pass (32 when dim > 128)
 
 
@@ -2264,6 +2265,21 @@ def pack_dcn(wc, bc, w1, b1, w2, b2, w3, b3, d_user: int) -> bytes:
             w2.tobytes() + f(b2).tobytes() + w3.tobytes() + f(b3).tobytes())
 
 
+def pack_mha(wq, bq, wk, wv, bv, wo, w1, b1, w2, b2, w3, b3, d_user: int, n_head: int) -> bytes:
+    """PG_MODEL_MHA blob (include/pairec_gpu.h): the projections wq, wk, wv [64][d_att], bq, bv [d_att], wo [d_att][64] of n_head
+    heads; then the trunk as pack_dnn3_multi with w1 [d_user + 128][h1] (rows: user, e, pooled)."""
+    f = lambda a: np.ascontiguousarray(a, dtype=np.float32)   # noqa: E731
+    wq, wk, wv, wo, w1, w2 = f(wq), f(wk), f(wv), f(wo), f(w1), f(w2)
+    (d_item, d_att), h1, h2 = wq.shape, w1.shape[1], w2.shape[1]
+    b3 = f(b3).reshape(-1)
+    w3 = f(w3).reshape(h2, b3.shape[0])
+    assert wk.shape == wq.shape and wv.shape == wq.shape and wo.shape == (d_att, d_item) and w1.shape[0] == d_user + 2 * d_item
+    assert f(bq).shape == (d_att,) and f(bv).shape == (d_att,)
+    return (struct.pack("<7I", d_user, d_item, h1, h2, b3.shape[0], d_att, n_head) + wq.tobytes() + f(bq).tobytes() + wk.tobytes() +
+            wv.tobytes() + f(bv).tobytes() + wo.tobytes() + w1.tobytes() + f(b1).tobytes() + w2.tobytes() + f(b2).tobytes() +
+            w3.tobytes() + b3.tobytes())
+
+
 def pack_fm2t(w) -> bytes:
     """w: object with the attributes of oracle.Fm2tWeights (duck-typed; no oracle import here)."""
     parts = [struct.pack("<7If", w.nuf, w.nif, w.k, w.d_user, w.t_h1, w.t_out, w.vocab, w.fm_b)]
@@ -2323,6 +2339,14 @@ class RankModel:
                  req_offsets: Sequence[int]) -> np.ndarray:
         """MODEL_DIN: seqs[r] = the rows of `table` in request r's behaviour sequence (at most DIN_MAX_SEQ; may be empty).
         scores [n_items], or [n_out][n_items] for several heads."""
+        return self._rank_seqs(self.ctx.L.pg_rank_din, table, user_vecs, seqs, cand_rows, req_offsets)
+
+    def rank_mha(self, table: Table, user_vecs: np.ndarray, seqs: Sequence[np.ndarray], cand_rows: np.ndarray,
+                 req_offsets: Sequence[int]) -> np.ndarray:
+        """MODEL_MHA: as rank_din, sequences of at most MHA_MAX_SEQ rows."""
+        return self._rank_seqs(self.ctx.L.pg_rank_mha, table, user_vecs, seqs, cand_rows, req_offsets)
+
+    def _rank_seqs(self, entry, table, user_vecs, seqs, cand_rows, req_offsets) -> np.ndarray:
         u = np.ascontiguousarray(user_vecs, dtype=np.float32)
         c = np.ascontiguousarray(cand_rows, dtype=np.uint32)
         ro = np.ascontiguousarray(req_offsets, dtype=np.uint32)
@@ -2331,13 +2355,18 @@ class RankModel:
         sr = np.ascontiguousarray(np.concatenate([np.asarray(s, dtype=np.uint32).reshape(-1) for s in seqs] + [np.zeros(0, np.uint32)]))
         assert so.shape[0] == ro.shape[0], "one sequence per request"
         out = np.empty((self.n_out, c.shape[0]), dtype=np.float32)
-        _lib.check(self.ctx.L.pg_rank_din(self.ctx.h, self.h, table.h, _ptr(u), _ptr(sr), _ptr(so), _ptr(c), _ptr(ro),
-                                          ro.shape[0] - 1, _ptr(out)))
+        _lib.check(entry(self.ctx.h, self.h, table.h, _ptr(u), _ptr(sr), _ptr(so), _ptr(c), _ptr(ro), ro.shape[0] - 1, _ptr(out)))
         return out[0] if self.n_out == 1 else out
 
     def rank_din_dev(self, table: Table, d_user_vecs: int, d_seq_rows: int, d_seq_offsets: int, d_cand_rows: int,
                      d_req_offsets: int, n_req: int, n_items: int, d_out: int):
         _lib.check(self.ctx.L.pg_rank_din_dev(self.ctx.h, self.h, table.h, C.c_void_p(d_user_vecs), C.c_void_p(d_seq_rows),
+                                              C.c_void_p(d_seq_offsets), C.c_void_p(d_cand_rows), C.c_void_p(d_req_offsets),
+                                              n_req, n_items, C.c_void_p(d_out)))
+
+    def rank_mha_dev(self, table: Table, d_user_vecs: int, d_seq_rows: int, d_seq_offsets: int, d_cand_rows: int,
+                     d_req_offsets: int, n_req: int, n_items: int, d_out: int):
+        _lib.check(self.ctx.L.pg_rank_mha_dev(self.ctx.h, self.h, table.h, C.c_void_p(d_user_vecs), C.c_void_p(d_seq_rows),
                                               C.c_void_p(d_seq_offsets), C.c_void_p(d_cand_rows), C.c_void_p(d_req_offsets),
                                               n_req, n_items, C.c_void_p(d_out)))
 

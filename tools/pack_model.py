@@ -26,6 +26,11 @@ Input: an .npz whose arrays are the layers' kernels exactly as a framework saves
   chosen when the file holds `wc`):
       wc [L][D][D] (D = d_user + d_item <= 256; L 1..3)   bc [L][D]
       w1 [D][h1]   b1, w2, b2 as above ((h1, h2) 128-128 or 256-128)   w3 [h2] or [h2][n_out]   b3 [n_out] (n_out 1..4)
+  MHA (PG_MODEL_MHA: multi-head softmax attention of each candidate over the user's behaviour sequence of up to 512 rows, pooled
+  through wo, then the trunk above on [user || item_row || pooled]; chosen when the file holds `wq`):
+      wq [64][d_att]   bq [d_att]   wk [64][d_att]   wv [64][d_att]   bv [d_att]   wo [d_att][64]   n_head (integer array, or --n-head)
+      ((d_att, n_head) one of (64,1) (64,2) (128,2) (128,4); a key bias cancels in the softmax and an output bias belongs in b1)
+      w1 [d_user + 128][h1] (rows: user, item row, pooled)   b1, w2, b2 as above   w3 [h2] or [h2][n_out]   b3 [n_out]
   --d-user N says where the user half of w1 ends (or an integer array `d_user` inside the file); d_item = the table's dim
   (64 or 128).  --map w1=dense/kernel,b1=dense/bias,… renames arrays.  Supported hidden shapes: see the header.
 
@@ -38,9 +43,10 @@ import sys
 import numpy as np
 
 DNN3_SHAPES = {(128, 128), (256, 128), (256, 256), (512, 256), (1024, 512)}
-KIND_DNN3, KIND_DNN3_MULTI, KIND_DIN, KIND_MMOE, KIND_DCN = 1, 3, 4, 5, 6
+KIND_DNN3, KIND_DNN3_MULTI, KIND_DIN, KIND_MMOE, KIND_DCN, KIND_MHA = 1, 3, 4, 5, 6, 8
 MMOE_SHAPES = {(2, 128), (4, 64), (4, 128), (8, 64)}
 DCN_HEADS = {(128, 128), (256, 128)}
+MHA_SHAPES = {(64, 1), (64, 2), (128, 2), (128, 4)}
 
 
 def _f32(a, shape=None, what=""):
@@ -106,6 +112,23 @@ def pack_din_arrays(wa, ba, wa2, ba2, w1, b1, w2, b2, w3, b3, d_user):
     return KIND_DIN, struct.pack("<6I", d_user_, 64, h1, h2, n_out, att_h) + att + trunk[16 if kind == KIND_DNN3 else 20:]
 
 
+def pack_mha_arrays(wq, bq, wk, wv, bv, wo, n_head, w1, b1, w2, b2, w3, b3, d_user):
+    """→ (KIND_MHA, blob): the attention's arrays in front of the trunk's, the trunk checked as a 128-wide DNN3."""
+    wq, n_head = np.asarray(wq), int(n_head)
+    if wq.ndim != 2 or wq.shape[0] != 64 or (wq.shape[1], n_head) not in MHA_SHAPES:
+        raise ValueError("wq has shape %s with %d heads, expected [64][d_att] with (d_att, n_head) one of %s (a 64-wide item table)" %
+                         (tuple(wq.shape), n_head, sorted(MHA_SHAPES)))
+    d_att = wq.shape[1]
+    kind, trunk = pack_dnn3_arrays(w1, b1, w2, b2, w3, b3, d_user)
+    d_user_, d_item, h1, h2 = struct.unpack("<4I", trunk[:16])
+    if d_item != 128:
+        raise ValueError("w1 has %d rows behind the user's %d: an MHA's are 128 (item row, pooled)" % (d_item, d_user_))
+    n_out = 1 if kind == KIND_DNN3 else struct.unpack("<I", trunk[16:20])[0]
+    att = b"".join(a.tobytes() for a in (_f32(wq, what="wq"), _f32(np.reshape(bq, -1), (d_att,), "bq"), _f32(wk, (64, d_att), "wk"),
+                                         _f32(wv, (64, d_att), "wv"), _f32(np.reshape(bv, -1), (d_att,), "bv"), _f32(wo, (d_att, 64), "wo")))
+    return KIND_MHA, struct.pack("<7I", d_user_, 64, h1, h2, n_out, d_att, n_head) + att + trunk[16 if kind == KIND_DNN3 else 20:]
+
+
 def pack_mmoe_arrays(we, be, wg, bg, wt, bt, wo, bo, d_user):
     """→ (KIND_MMOE, blob, description)"""
     we, wt = np.asarray(we), np.asarray(wt)
@@ -147,7 +170,7 @@ def pack_dcn_arrays(wc, bc, w1, b1, w2, b2, w3, b3, d_user):
     return KIND_DCN, blob, "PG_MODEL_DCN [%d+%d], %d cross layers -> %d -> %d -> %d, %d bytes" % (d_user, d_item, n_l, h1, h2, n_out, len(blob))
 
 
-def pack_npz(path_or_mapping, d_user=None, rename=None):
+def pack_npz(path_or_mapping, d_user=None, rename=None, n_head=None):
     """Load the arrays (an .npz path or a mapping name → array) and pack them; → (kind, blob, description)."""
     z = np.load(path_or_mapping) if isinstance(path_or_mapping, (str, bytes)) else path_or_mapping
     rename = rename or {}
@@ -164,13 +187,17 @@ def pack_npz(path_or_mapping, d_user=None, rename=None):
     trunk = [get(n) for n in ("w1", "b1", "w2", "b2", "w3", "b3")]
     if rename.get("wc", "wc") in z:
         return pack_dcn_arrays(get("wc"), get("bc"), *trunk, d_user)
-    if rename.get("wa", "wa") in z:
+    if rename.get("wq", "wq") in z:
+        if n_head is None:
+            n_head = int(np.asarray(get("n_head")).reshape(-1)[0])
+        kind, blob = pack_mha_arrays(*[get(n) for n in ("wq", "bq", "wk", "wv", "bv", "wo")], n_head, *trunk, d_user)
+    elif rename.get("wa", "wa") in z:
         kind, blob = pack_din_arrays(get("wa"), get("ba"), get("wa2"), get("ba2"), *trunk, d_user)
     else:
         kind, blob = pack_dnn3_arrays(*trunk, d_user)
     w1, w2 = get("w1"), get("w2")
     n_out = int(np.asarray(get("b3")).size)
-    desc = "%s [%d+%d]-%d-%d-%d, %d bytes" % ({KIND_DNN3: "PG_MODEL_DNN3", KIND_DNN3_MULTI: "PG_MODEL_DNN3_MULTI", KIND_DIN: "PG_MODEL_DIN"}[kind],
+    desc = "%s [%d+%d]-%d-%d-%d, %d bytes" % ({KIND_DNN3: "PG_MODEL_DNN3", KIND_DNN3_MULTI: "PG_MODEL_DNN3_MULTI", KIND_DIN: "PG_MODEL_DIN", KIND_MHA: "PG_MODEL_MHA"}[kind],
                                               d_user, w1.shape[0] - d_user, w1.shape[1], w2.shape[1], n_out, len(blob))
     return kind, blob, desc
 
@@ -179,12 +206,13 @@ def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("npz")
     ap.add_argument("--d-user", type=int, default=None)
+    ap.add_argument("--n-head", type=int, default=None, help="PG_MODEL_MHA: the number of heads (or an integer array n_head in the file)")
     ap.add_argument("--map", default="", help="w1=dense/kernel,b1=dense/bias,…")
     ap.add_argument("--out", required=True)
     a = ap.parse_args(argv)
     rename = dict(kv.split("=", 1) for kv in a.map.split(",") if kv)
     try:
-        kind, blob, desc = pack_npz(a.npz, a.d_user, rename)
+        kind, blob, desc = pack_npz(a.npz, a.d_user, rename, a.n_head)
     except (KeyError, ValueError) as e:
         sys.stderr.write("pack_model: %s\n" % e)
         return 2
