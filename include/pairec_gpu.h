@@ -70,7 +70,7 @@ typedef enum {
  *                  Refused at load (PG_ERR_UNSUPPORTED): PG_MODEL_FM_TWOTOWER; a non-finite weight; a scaled weight or
  *                  scale factor outside fp32's normal range. */
 typedef enum { PG_PREC_F32 = 0, PG_PREC_BF16 = 1, PG_PREC_BF16X3 = 2, PG_PREC_F16X2 = 3, PG_PREC_F16 = 4 } pg_prec;
-typedef enum { PG_MODEL_DNN3 = 1, PG_MODEL_FM_TWOTOWER = 2, PG_MODEL_DNN3_MULTI = 3, PG_MODEL_DIN = 4, PG_MODEL_MMOE = 5, PG_MODEL_DCN = 6, PG_MODEL_MHA = 8 /* 7 is kept unassigned: pg_model_load refuses it as unknown */ } pg_model_kind;
+typedef enum { PG_MODEL_DNN3 = 1, PG_MODEL_FM_TWOTOWER = 2, PG_MODEL_DNN3_MULTI = 3, PG_MODEL_DIN = 4, PG_MODEL_MMOE = 5, PG_MODEL_DCN = 6, PG_MODEL_MHA = 8, PG_MODEL_PLE = 9 /* 7 is kept unassigned: pg_model_load refuses it as unknown */ } pg_model_kind;
 
 const char* pg_last_error(void);
 const char* pg_version(void);
@@ -312,12 +312,53 @@ int pg_rank_din_dev(pg_ctx* ctx, const pg_model* m, const pg_table* t, const flo
  *             of another length (PG_ERR_INVALID).  pg_rank_mmoe[_dev] (PG_ERR_INVALID, on the host, the context left usable): a
  *             model of another kind, a table whose dim is not d_item.  pg_rank_dnn3[_dev], pg_rank_din[_dev] and
  *             pg_coalescer_create_scene refuse a PG_MODEL_MMOE the same way.
- *   Not here  PG_PREC_F32 and the fp16 precisions; two-layer experts or towers; PLE, ESMM and DBMTL; the coalescer and the
+ *   Not here  PG_PREC_F32 and the fp16 precisions; two-layer experts or towers (PLE is PG_MODEL_PLE; ESMM and DBMTL chains are products of a multi-head model's planes); the coalescer and the
  *             pg_recommend_* pipelines; E x h_e beyond 512. */
 int pg_rank_mmoe(pg_ctx* ctx, const pg_model* m, const pg_table* t, const float* user_vecs, const uint32_t* cand_rows,
                  const uint32_t* req_offsets, uint32_t n_req, float* out_scores);
 int pg_rank_mmoe_dev(pg_ctx* ctx, const pg_model* m, const pg_table* t, const float* d_user_vecs, const uint32_t* d_cand_rows,
                      const uint32_t* d_req_offsets, uint32_t n_req, uint32_t n_items, float* d_out_scores);
+
+/* ---- rank: PLE — one or two levels of task and shared experts under task towers (PG_MODEL_PLE) ---------------------------------
+ *   Replaces  the remote multi-task model behind the reference's multi-valued answers, as PG_MODEL_MMOE does (algorithm/eas/
+ *             easyrec_response.go:35-70, service/rank/rank_service.go:315-319), where that model is a progressive layered
+ *             extraction (Tang et al., RecSys 2020): the usual successor of an MMoE once tasks fight over shared experts.  ESMM and
+ *             DBMTL-style chains need no kind of their own at inference: a multi-head model returns their planes and RankScore
+ *             multiplies them.
+ *   Model     per candidate row e (d_item wide) of request r with user vector u, x = [ u | e ]; T tasks, groups g = 0..T (group
+ *             t < T belongs to task t and has E_t experts, group T is shared and has E_s); x0_g = x; level l = 1..n_level:
+ *               a_{g,k} = relu( We_{g,k}' x^{l-1}_g + be_{g,k} )                     h_e wide, k over the group's experts
+ *               task t:  z = Wg_t' x^{l-1}_t + bg_t  over [ a_{t,0..E_t-1}, a_{T,0..E_s-1} ]   (E_t + E_s logits, this order)
+ *                        x^l_t = sum softmax(z)[k] a_k                               max-subtracted
+ *               shared (l < n_level only):  z = Wg_T' x^{l-1}_T + bg_T  over [ a_{0,*}, .., a_{T-1,*}, a_{T,*} ]   (T E_t + E_s logits)
+ *                        x^l_T = sum softmax(z)[k] a_k
+ *               score_t = sigmoid( wo_t . relu( Wt_t' x^{n_level}_t + bt_t ) + bo_t )
+ *   Blob      u32 d_user (1..4096), d_item (64 or 128), n_task (1..3), e_task (1 or 2), e_shared (1 or 2), h_e (64; 128 with one
+ *             level), n_level (1 or 2), h_t (32 or 64), with (T E_t + E_s) h_e <= 512.  Then per level, in = d_user + d_item at
+ *             level 1 and h_e at level 2: We_t[T][E_t][in][h_e]; We_s[E_s][in][h_e]; be_t[T][E_t][h_e]; be_s[E_s][h_e];
+ *             Wg_t[T][in][E_t + E_s]; bg_t[T][E_t + E_s]; and below the last level only Wg_s[in][T E_t + E_s]; bg_s[T E_t + E_s].
+ *             Then Wt[T][h_e][h_t]; bt[T][h_t]; wo[T][h_t]; bo[T] — little-endian fp32, every matrix [in][out].
+ *             tools/pack_model.py builds it.
+ *   Precision PG_PREC_BF16: the candidate row, every weight matrix, each x^1_g as the second level's operand and each x^{n_level}_t
+ *             as its tower's operand are rounded once (RNE) from their fp32 values; the user half, the accumulation, the biases,
+ *             relu, the softmax, the mixes, the head dot and the sigmoid are fp32.  PG_PREC_BF16X3: exactly those operands split
+ *             into hi + lo, three products per term, nothing else rounded.  Gate logits are exponents: the first level's take a
+ *             three-way split as an MMoE's; the second level's are fp32 fma chains over x^1_t (unrounded in BF16X3, the rounded
+ *             operand in BF16) and the gate weights in the operand precision.  In a two-level BF16X3 model the first level's
+ *             expert products take the three-way split as well (six products per term, the operands' fp32 values exactly): the
+ *             second level's gates exponentiate what they produce.
+ *   Output    as PG_MODEL_MMOE: out_scores[t * n_items + i], one plane per task; pg_model_num_outputs() = n_task.  A candidate row
+ *             >= the table's rows reads the last row in pg_rank_ple_dev; pg_rank_ple validates its rows as pg_rank_dnn3 does.
+ *   Refused   pg_model_load: a shape outside the lists above; PG_PREC_F32, PG_PREC_F16X2, PG_PREC_F16 (PG_ERR_UNSUPPORTED); a blob
+ *             of another length (PG_ERR_INVALID).  pg_rank_ple[_dev] (PG_ERR_INVALID, on the host, the context left usable): a
+ *             model of another kind, a table whose dim is not d_item.  Every other rank entry point and
+ *             pg_coalescer_create[_scene] refuse a PG_MODEL_PLE the same way.
+ *   Not here  three or more levels; per-level or per-group expert counts and widths; PG_PREC_F32 and the fp16 precisions; the
+ *             coalescer and the pg_recommend_* pipelines.  No shape of the lists above fell out: none needs scratch. */
+int pg_rank_ple(pg_ctx* ctx, const pg_model* m, const pg_table* t, const float* user_vecs, const uint32_t* cand_rows,
+                const uint32_t* req_offsets, uint32_t n_req, float* out_scores);
+int pg_rank_ple_dev(pg_ctx* ctx, const pg_model* m, const pg_table* t, const float* d_user_vecs, const uint32_t* d_cand_rows,
+                    const uint32_t* d_req_offsets, uint32_t n_req, uint32_t n_items, float* d_out_scores);
 
 /* ---- rank: DCN-v2 — explicit feature crosses under a DNN3 head (PG_MODEL_DCN) -----------------------------------------------------
  *   Replaces  a remote ranking model whose backbone is a deep & cross network: the reference ships requests to PAI-EAS EasyRec

@@ -336,6 +336,36 @@ int pg_rank_mmoe(pg_ctx* ctx, const pg_model* m, const pg_table* t, const float*
         });
 }
 
+int pg_rank_ple_dev(pg_ctx* ctx, const pg_model* m, const pg_table* t, const float* d_user_vecs, const uint32_t* d_cand_rows,
+                     const uint32_t* d_req_offsets, uint32_t n_req, uint32_t n_items, float* d_out_scores) {
+    PG_REQUIRE(ctx && m && t && d_user_vecs && d_cand_rows && d_req_offsets && d_out_scores, "pg_rank_ple_dev: NULL argument");
+    PG_REQUIRE(m->kind == PG_MODEL_PLE, "pg_rank_ple_dev: model is not PLE");
+    PG_REQUIRE(t->dim == m->d_item && t->rows >= 1, "pg_rank_ple_dev: table dim %u != model d_item %u (or no rows)", t->dim, m->d_item);
+    PG_REQUIRE(n_req <= 65535, "pg_rank_ple_dev: at most 65535 requests per call");
+    std::lock_guard<std::mutex> g(ctx->mu);
+    pg::TableRead tr(t->rw);
+    return pg::rank_ple_dev_locked(ctx, m, t, d_user_vecs, d_cand_rows, d_req_offsets, n_req, n_items, d_out_scores);
+}
+
+int pg_rank_ple(pg_ctx* ctx, const pg_model* m, const pg_table* t, const float* user_vecs, const uint32_t* cand_rows,
+                 const uint32_t* req_offsets, uint32_t n_req, float* out_scores) {
+    PG_REQUIRE(ctx && m && t && req_offsets, "pg_rank_ple: NULL argument");
+    PG_REQUIRE(m->kind == PG_MODEL_PLE, "pg_rank_ple: model is not PLE");
+    PG_REQUIRE(t->dim == m->d_item, "pg_rank_ple: table dim %u != model d_item %u", t->dim, m->d_item);
+    const pg::HostIn in[] = {{user_vecs, false, m->d_user, 4}, {cand_rows, true, 1, 4}};
+    return pg::rank_from_host(
+        "pg_rank_ple", ctx, m, t, in, nullptr, req_offsets, n_req, out_scores,
+        [&](uint32_t n_items) -> int {
+            for (uint32_t i = 0; i < n_items; ++i)
+                PG_REQUIRE(cand_rows[i] < t->rows, "pg_rank_ple: candidate %u row %u outside table of %llu rows", i, cand_rows[i],
+                           (unsigned long long)t->rows);
+            return PG_OK;
+        },
+        [&](void* const* d, const uint32_t* d_off, uint32_t n_items, float* d_scores) {
+            return pg::rank_ple_dev_locked(ctx, m, t, (const float*)d[0], (const uint32_t*)d[1], d_off, n_req, n_items, d_scores);
+        });
+}
+
 int pg_rank_dcn_dev(pg_ctx* ctx, const pg_model* m, const pg_table* t, const float* d_user_vecs, const uint32_t* d_cand_rows,
                      const uint32_t* d_req_offsets, uint32_t n_req, uint32_t n_items, float* d_out_scores) {
     PG_REQUIRE(ctx && m && t && d_user_vecs && d_cand_rows && d_req_offsets && d_out_scores, "pg_rank_dcn_dev: NULL argument");

@@ -154,6 +154,66 @@ __device__ __forceinline__ void store_h_quad(char* tile, int row, int col, float
     }
 }
 
+// ---- what the kernels with candidates on the MFMA column axis share (rank_mmoe.hip, rank_ple.hip) --------------------------------
+// acc += A' B with A the fragment at `frag` (split: its lo fragment 1 KiB on) and B = bh (+ bl)
+template <int NP>
+__device__ __forceinline__ f32x16 mmoe_mac(const char* frag, int lane, bf16x8 bh, bf16x8 bl, f32x16 acc) {
+    const bf16x8 ah = *reinterpret_cast<const bf16x8*>(frag + lane * 16);
+    if constexpr (NP == 3) {
+        const bf16x8 al = *reinterpret_cast<const bf16x8*>(frag + 1024 + lane * 16);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc, 0, 0, 0);
+    }
+    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc, 0, 0, 0);
+}
+
+// the three-way form: A in three planes (hi, mid, lo at `frag`, + 1 KiB, + 2 KiB), B = b1 + b2 + b3, the six products down to
+// 2^-16 of the leading one, smallest first: (a3 b1 + a1 b3 + a2 b2) + (a2 b1 + a1 b2) + a1 b1
+__device__ __forceinline__ f32x16 mmoe_mac6(const char* frag, int lane, bf16x8 b1, bf16x8 b2, bf16x8 b3, f32x16 acc) {
+    const bf16x8 a3 = *reinterpret_cast<const bf16x8*>(frag + 2048 + lane * 16);
+    const bf16x8 a2 = *reinterpret_cast<const bf16x8*>(frag + 1024 + lane * 16);
+    const bf16x8 a1 = *reinterpret_cast<const bf16x8*>(frag + lane * 16);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3, b1, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b3, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b2, acc, 0, 0, 0);
+    return mmoe_mac<3>(frag, lane, b1, b2, acc);
+}
+
+// 8 fp32 values as a B-operand register group: rounded (NP 1) or split into hi and lo (NP 3)
+template <int NP>
+__device__ __forceinline__ void mmoe_operand(const float* v, bf16x8& hi, bf16x8& lo) {
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    uint32_t ph[4], pl[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        if constexpr (NP == 3) {
+            split_bf16x2(v[2 * i], v[2 * i + 1], ph[i], pl[i]);
+        } else {
+            typedef float f32x2 __attribute__((ext_vector_type(2)));
+            typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+            ph[i] = pl[i] = __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2){v[2 * i], v[2 * i + 1]}, bf16x2));   // v_cvt_pk_bf16_f32 (RNE); lo is not read
+        }
+    }
+    lo = __builtin_bit_cast(bf16x8, (u32x4){pl[0], pl[1], pl[2], pl[3]});
+    hi = __builtin_bit_cast(bf16x8, (u32x4){ph[0], ph[1], ph[2], ph[3]});
+}
+
+// the lane's 16 rows of a 32-row block of a per-row fp32 vector: rows 8 q + 4 hk + 0..3 are one float4 (p = base + 4 hk)
+__device__ __forceinline__ f32x16 mmoe_rows16(const float* p) {
+    f32x16 v;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const float4 c = *reinterpret_cast<const float4*>(p + 8 * q);
+        v[4 * q + 0] = c.x; v[4 * q + 1] = c.y; v[4 * q + 2] = c.z; v[4 * q + 3] = c.w;
+    }
+    return v;
+}
+
+// rank_mmoe.hip: c1[r][c] = chain(bu[c]; u[r][k] * wu[k][c], k ascending) for n_req requests — the user half of every row of a
+// product over x = [u | e], hoisted out of the per-candidate kernel
+int mmoe_user_partial_launch(pg_ctx* ctx, const float* d_user, uint32_t n_req, uint32_t du, const float* wu, const float* bu, uint32_t nc,
+                             float* c1);
+
 // rank_mlp.hip: the tile table of a call — tile -> (request, first item, count), tiles of `tile_items` candidates cut per
 // request; arrays of max_tiles >= n_items / tile_items + n_req entries, req_tile0 [n_req] (rank_din.hip tiles its runs with it)
 int build_tiles_launch(pg_ctx* ctx, const uint32_t* d_off, uint32_t n_req, uint32_t max_tiles, uint32_t tile_items,

@@ -80,49 +80,14 @@ __global__ void mmoe_user_partial_kernel(const float* __restrict__ user, uint32_
     c1[(size_t)r * nc + c] = acc;
 }
 
+int mmoe_user_partial_launch(pg_ctx* ctx, const float* d_user, uint32_t n_req, uint32_t du, const float* wu, const float* bu, uint32_t nc,
+                             float* c1) {
+    mmoe_user_partial_kernel<<<dim3(n_req, (nc + 255) / 256), 256, 0, ctx->stream>>>(d_user, du, wu, bu, nc, c1);
+    PG_HIP(hipGetLastError());
+    return PG_OK;
+}
+
 constexpr int mmoe_nbuf(int gate_bytes, int step_bytes) { return gate_bytes + 2 * step_bytes <= 128 * 1024 ? 2 : 1; }
-
-// acc += A' B with A the fragment at `frag` (split: its lo fragment 1 KiB on) and B = bh (+ bl)
-template <int NP>
-__device__ __forceinline__ f32x16 mmoe_mac(const char* frag, int lane, bf16x8 bh, bf16x8 bl, f32x16 acc) {
-    const bf16x8 ah = *reinterpret_cast<const bf16x8*>(frag + lane * 16);
-    if constexpr (NP == 3) {
-        const bf16x8 al = *reinterpret_cast<const bf16x8*>(frag + 1024 + lane * 16);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc, 0, 0, 0);
-    }
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc, 0, 0, 0);
-}
-
-// 8 fp32 values as a B-operand register group: rounded (NP 1) or split into hi and lo (NP 3)
-template <int NP>
-__device__ __forceinline__ void mmoe_operand(const float* v, bf16x8& hi, bf16x8& lo) {
-    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-    uint32_t ph[4], pl[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        if constexpr (NP == 3) {
-            split_bf16x2(v[2 * i], v[2 * i + 1], ph[i], pl[i]);
-        } else {
-            typedef float f32x2 __attribute__((ext_vector_type(2)));
-            typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-            ph[i] = pl[i] = __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2){v[2 * i], v[2 * i + 1]}, bf16x2));   // v_cvt_pk_bf16_f32 (RNE); lo is not read
-        }
-    }
-    lo = __builtin_bit_cast(bf16x8, (u32x4){pl[0], pl[1], pl[2], pl[3]});
-    hi = __builtin_bit_cast(bf16x8, (u32x4){ph[0], ph[1], ph[2], ph[3]});
-}
-
-// the lane's 16 rows of a 32-row block of a per-row fp32 vector: rows 8 q + 4 hk + 0..3 are one float4 (p = base + 4 hk)
-__device__ __forceinline__ f32x16 mmoe_rows16(const float* p) {
-    f32x16 v;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const float4 c = *reinterpret_cast<const float4*>(p + 8 * q);
-        v[4 * q + 0] = c.x; v[4 * q + 1] = c.y; v[4 * q + 2] = c.z; v[4 * q + 3] = c.w;
-    }
-    return v;
-}
 
 template <int NP, int D, int E, int TP, int HT>
 __global__ __launch_bounds__(256) void mmoe_kernel(MmoeArgs a) {
@@ -334,8 +299,7 @@ int rank_mmoe_dev_locked(pg_ctx* ctx, const pg_model* m, const pg_table* t, cons
     const bool timed = !ctx->timers_off;
     if (timed) PG_HIP(hipEventRecord(ctx->ev[2], ctx->stream));
     if ((rc = build_tiles_launch(ctx, d_off, n_req, max_tiles, kBM, tile_req, tile_item0, tile_cnt, n_tiles, req_tile0))) return rc;
-    mmoe_user_partial_kernel<<<dim3(n_req, (nc + 255) / 256), 256, 0, ctx->stream>>>(d_user, m->d_user, m->mm_wu, m->mm_bu, nc, c1);
-    PG_HIP(hipGetLastError());
+    if ((rc = mmoe_user_partial_launch(ctx, d_user, n_req, m->d_user, m->mm_wu, m->mm_bu, nc, c1))) return rc;
     MmoeArgs a{};
     a.tile_req = tile_req;
     a.tile_item0 = tile_item0;

@@ -67,6 +67,11 @@ struct pg_model {
     float* mm_bt = nullptr;     // [mm_tp][h_t]
     float* mm_wo = nullptr;     // [mm_tp][h_t]
     float* mm_bo = nullptr;     // [mm_tp]
+    // PG_MODEL_PLE (rank_ple.hip; pack_ple below): n_out = n_task, e_task / e_shared experts per task / shared group, h_e, h_t as
+    // above; mm_wu / mm_bu ([32 + 32 pl_nrec1]), mm_rec and mm_bt / mm_wo / mm_bo ([3][h_t], [3]) hold what they hold for an MMoE
+    uint32_t e_task = 0, e_shared = 0, n_level = 0, pl_nrec1 = 0;
+    float* pl_be2 = nullptr;    // [pl_nrec1][32]: the second level's expert biases in accumulator-row order, record by record
+    float* pl_bg2 = nullptr;    // [3][4]: the second level's task-gate biases in gate-slot order
     // PG_MODEL_DCN (rank_dcn.hip; pack_dcn below): n_cross layers over x_0 padded to dc_dp columns, item columns first; the
     // head's b1, b2, w3 ([n_out][h2]) and b3v are the members a DNN3 uses
     uint32_t n_cross = 0, dc_dp = 0;
@@ -116,6 +121,11 @@ inline bool mmoe_shape_ok(uint32_t ne, uint32_t he) {
     PG_MMOE_SHAPES(X)
 #undef X
     return false;
+}
+// PG_MODEL_PLE: T task groups of E_t experts and a shared group of E_s, in one or two extraction levels
+inline bool ple_shape_ok(uint32_t du, uint32_t di, uint32_t T, uint32_t et, uint32_t es, uint32_t he, uint32_t nl, uint32_t ht) {
+    return (di == 64 || di == 128) && du >= 1 && du <= 4096 && T >= 1 && T <= 3 && (et == 1 || et == 2) && (es == 1 || es == 2) &&
+           (nl == 1 || nl == 2) && (he == 64 || (he == 128 && nl == 1)) && (ht == 32 || ht == 64) && (T * et + es) * he <= 512;
 }
 // PG_MODEL_DCN: D = d_user + d_item is padded to one of these widths (zero rows and columns: a zero coordinate of x_0 stays zero
 // through every cross layer); the head is a DNN3's 128-128 or 256-128
@@ -233,7 +243,12 @@ struct BlobLayout {
     size_t wc = 0, bc = 0;
     // MHA, in front of the DNN3 arrays: Wq [64][d_att], bq [d_att], Wk [64][d_att], Wv [64][d_att], bv [d_att], Wo [d_att][64]
     size_t a_wq = 0, a_bq = 0, a_wk = 0, a_wv = 0, a_bv = 0, a_wo = 0;
+    // PLE, per level l (in = d_user + d_item at level 1, h_e at level 2): We_t [T][E_t][in][h_e], We_s [E_s][in][h_e], be_t [T][E_t][h_e],
+    // be_s [E_s][h_e], Wg_t [T][in][E_t + E_s], bg_t [T][E_t + E_s] and, below the last level only, Wg_s [in][T E_t + E_s],
+    // bg_s [T E_t + E_s]; then wt, bt, wo, bo as an MMoE's
+    size_t ple[2][8] = {};
 };
+enum { kPleWeT, kPleWeS, kPleBeT, kPleBeS, kPleWgT, kPleBgT, kPleWgS, kPleBgS };
 
 // What `blob` says as a model of `kind` in `prec`: the dimensions (and kind, prec, f16_nprod, b3, fm_b) into *m, the arrays'
 // offsets into *lay.  PG_OK, or the refusal in *why.
@@ -252,6 +267,8 @@ inline int parse_model_blob(int kind, int prec, const void* blob, size_t len, pg
                                                "PG_MODEL_MHA in PG_PREC_F32, PG_PREC_BF16 or PG_PREC_BF16X3");
     if (kind == PG_MODEL_MMOE && prec != PG_PREC_BF16 && prec != PG_PREC_BF16X3)
         return refuse(why, PG_ERR_UNSUPPORTED, "pg_model_load: a PG_MODEL_MMOE is served in PG_PREC_BF16 and PG_PREC_BF16X3 (precision %d asked)", prec);
+    if (kind == PG_MODEL_PLE && prec != PG_PREC_BF16 && prec != PG_PREC_BF16X3)
+        return refuse(why, PG_ERR_UNSUPPORTED, "pg_model_load: a PG_MODEL_PLE is served in PG_PREC_BF16 and PG_PREC_BF16X3 (precision %d asked)", prec);
     if (kind == PG_MODEL_DCN && prec != PG_PREC_BF16 && prec != PG_PREC_BF16X3)
         return refuse(why, PG_ERR_UNSUPPORTED, "pg_model_load: a PG_MODEL_DCN is served in PG_PREC_BF16 and PG_PREC_BF16X3 (precision %d asked)", prec);
     const uint8_t* p = (const uint8_t*)blob;
@@ -359,6 +376,37 @@ inline int parse_model_blob(int kind, int prec, const void* blob, size_t len, pg
             need += nf[i] * 4;
         }
         if (len != need) return refuse(why, PG_ERR_INVALID, "pg_model_load: MMoE blob is %zu bytes, expected %zu", len, need);
+    } else if (kind == PG_MODEL_PLE) {
+        m->kind = PG_MODEL_PLE;
+        if (len < 32) return refuse(why, PG_ERR_INVALID, "pg_model_load: blob too short");
+        uint32_t hdr[8];
+        memcpy(hdr, p, 32);
+        m->d_user = hdr[0]; m->d_item = hdr[1]; m->n_out = hdr[2]; m->e_task = hdr[3]; m->e_shared = hdr[4]; m->h_e = hdr[5]; m->n_level = hdr[6];
+        m->h_t = hdr[7];
+        if (!ple_shape_ok(m->d_user, m->d_item, m->n_out, m->e_task, m->e_shared, m->h_e, m->n_level, m->h_t))
+            return refuse(why, PG_ERR_UNSUPPORTED, "pg_model_load: PLE shape [%u+%u] -> %u levels of %u x %u task and %u shared experts x %u -> towers x %u "
+                                                   "unsupported (d_item 64 or 128; 1..3 tasks; 1 or 2 experts per group; width 64, or 128 with one level; "
+                                                   "1 or 2 levels; tower width 32 or 64; all experts x width <= 512)",
+                          m->d_user, m->d_item, m->n_level, m->n_out, m->e_task, m->e_shared, m->h_e, m->h_t);
+        m->pl_nrec1 = (m->h_e / 16) * (m->n_out + 1);
+        const size_t T = m->n_out, Et = m->e_task, Es = m->e_shared, he = m->h_e, ht = m->h_t;
+        size_t need = 32;
+        for (uint32_t l = 0; l < m->n_level; ++l) {
+            const size_t in = l ? he : (size_t)m->d_user + m->d_item, last = l + 1 == m->n_level;
+            const size_t nf[8] = {T * Et * in * he, Es * in * he, T * Et * he, Es * he, T * in * (Et + Es), T * (Et + Es),
+                                  last ? 0 : in * (T * Et + Es), last ? 0 : T * Et + Es};
+            for (int i = 0; i < 8; ++i) {
+                lay->ple[l][i] = need;
+                need += nf[i] * 4;
+            }
+        }
+        const size_t nf[4] = {T * he * ht, T * ht, T * ht, T};
+        size_t* const at[4] = {&lay->wt, &lay->bt, &lay->wo, &lay->bo};
+        for (int i = 0; i < 4; ++i) {
+            *at[i] = need;
+            need += nf[i] * 4;
+        }
+        if (len != need) return refuse(why, PG_ERR_INVALID, "pg_model_load: PLE blob is %zu bytes, expected %zu", len, need);
     } else if (kind == PG_MODEL_DCN) {
         m->kind = PG_MODEL_DCN;
         if (len < 24) return refuse(why, PG_ERR_INVALID, "pg_model_load: blob too short");
@@ -552,6 +600,17 @@ inline void mmoe_slot(uint32_t p, uint32_t* hk, uint32_t* r) {
     *hk = (p >> 2) & 1;
     *r = (p & 3) + 4 * (p >> 3);
 }
+// 8 consecutive k-values of one lane of fragment `frag` of the record at `rec`, in `planes` bf16 planes (hi, then what is left)
+inline void frag_put(uint8_t* rec, uint32_t frag, uint32_t lane, const float* v, uint32_t planes) {
+    uint16_t* const d = reinterpret_cast<uint16_t*>(rec + (size_t)frag * planes * 1024 + lane * 16);
+    for (uint32_t e = 0; e < 8; ++e) {
+        float rest = v[e];
+        for (uint32_t pl = 0; pl < planes; ++pl) {
+            d[512 * pl + e] = f32_to_bf16_rne(rest);
+            rest -= bf16_to_f32(d[512 * pl + e]);       // (exact)
+        }
+    }
+}
 struct MmoePacked {
     std::vector<float> wu, bu, bt, wo, bo;
     std::vector<uint8_t> rec;
@@ -581,17 +640,6 @@ inline void pack_mmoe(const pg_model* m, const float* we, const float* be, const
     memcpy(o->bt.data(), bt, (size_t)T * ht * 4);
     memcpy(o->wo.data(), wo, (size_t)T * ht * 4);
     memcpy(o->bo.data(), bo, (size_t)T * 4);
-    // 8 consecutive k-values of one lane of fragment `frag` (of the record at `rec`)
-    auto put = [&](uint8_t* rec, uint32_t frag, uint32_t lane, const float* v, uint32_t planes) {
-        uint16_t* const d = reinterpret_cast<uint16_t*>(rec + (size_t)frag * planes * 1024 + lane * 16);
-        for (uint32_t e = 0; e < 8; ++e) {
-            float rest = v[e];
-            for (uint32_t pl = 0; pl < planes; ++pl) {
-                d[512 * pl + e] = f32_to_bf16_rne(rest);
-                rest -= bf16_to_f32(d[512 * pl + e]);       // (exact)
-            }
-        }
-    };
     // one row of the big product: input-major column `col` of W ([din][ncol]) into column `c` of wu / bu and row p of `frag0 + ks`
     auto row = [&](uint8_t* rec, uint32_t frag0, uint32_t planes, uint32_t p, uint32_t c, const float* W, uint32_t ncol, uint32_t col, float bias) {
         for (uint32_t k = 0; k < du; ++k) o->wu[(size_t)k * NC + c] = round_prec(W[(size_t)k * ncol + col], m->prec);
@@ -600,7 +648,7 @@ inline void pack_mmoe(const pg_model* m, const float* we, const float* be, const
             for (uint32_t hh = 0; hh < 2; ++hh) {
                 float v[8];
                 for (uint32_t e = 0; e < 8; ++e) v[e] = W[(size_t)(du + ks * 16 + 8 * hh + e) * ncol + col];
-                put(rec, frag0 + ks, hh * 32 + p, v, planes);
+                frag_put(rec, frag0 + ks, hh * 32 + p, v, planes);
             }
     };
     for (uint32_t p = 0; p < 32; ++p) {
@@ -620,8 +668,146 @@ inline void pack_mmoe(const pg_model* m, const float* we, const float* be, const
                 for (uint32_t lane = 0; lane < 64; ++lane) {
                     float v[8];
                     for (uint32_t e = 0; e < 8; ++e) v[e] = wt[((size_t)t * he + 16 * s + 8 * (lane >> 5) + e) * ht + 32 * hb + (lane & 31)];
-                    put(o->rec.data() + gbytes + s * sbytes, EB * KS + t * HB + hb, lane, v, PL);
+                    frag_put(o->rec.data() + gbytes + s * sbytes, EB * KS + t * HB + hb, lane, v, PL);
                 }
+}
+
+// PG_MODEL_PLE: where rank_ple.hip wants each weight.  Candidates sit on the MFMA column axis as for an MMoE, a lane (item, half hk)
+// holding rows p of a 32-row accumulator block in registers r, (hk, r) = mmoe_slot(p).  Group positions: task t at t, the shared
+// group at 3, whatever T is.
+//   gate block (one, level 1):  half 0, slot r = 4 t + c: task t's logit over its own expert c (c < 2) or shared expert c - 2; half 1,
+//                               slot r: the shared gate's logit over task r / 2's expert r % 2 (r < 6) or shared expert r - 6.  Rows
+//                               of experts the model does not have stay zero; the kernel masks them (ple_task_mask, ple_shared_mask)
+//   an expert block:            slot r = 8 k + u of half hk is (expert k of the group, hidden unit 16 s + 8 hk + u): a lane holds both
+//                               experts of 8 consecutive hidden units, the 8 k-values it supplies to the next product's 16-deep slice s
+// Records (ple_rec1_bytes each at level 1, ple_rec2_bytes at level 2), in the order the kernel consumes them: level 1, then level 2; in a level step s = 0 .. h_e / 16 - 1;
+// in a step the shared group, then task 0 .. T - 1.  A record's fragments (1 KiB each; split bf16: the lo fragment follows its hi):
+//   level 1:  fragment ks < d_item / 16: lane (p, hk') = We1 row (slot of p), item columns 16 ks + 8 hk' + 0..7 (split bf16 under a
+//             second level: hi, mid and lo fragments, ple_l1_planes)
+//   level 2:  fragment ks < 4:           lane (p, hk') = We2 row (slot of p), inputs 16 ks + 8 hk' + 0..7 of the group's x1
+//   last level, a task's record:  then fragment hb < h_t / 32: lane (i, hk') = Wt_t[16 s + 8 hk' + 0..7][32 hb + i]
+// In front of the records the gate record (as an MMoE's: three planes in split bf16) and, with two levels, the second level's task
+// gates for the fp32 chains: float4 [3][64] = Wg2_t[j][own 0, own 1, shared 0, shared 1] in the operand precision.
+// Column order of wu / bu (and of a request's c1): the 32 gate rows, then 32 rows per level-1 record.
+// (split bf16, two levels: level 1's expert fragments carry THREE planes as the gate record does — level 2's gates exponentiate
+//  what those experts produce, and the 2^-18 a two-way split leaves of x1 showed as 3e-7 of a score under +-80 logits)
+constexpr uint32_t ple_l1_planes(uint32_t n_level, int prec) { return prec == 2 ? (n_level == 2 ? 3 : 2) : 1; }
+constexpr size_t ple_rec1_bytes(uint32_t d_item, uint32_t n_level, uint32_t ht, int prec) {
+    return (size_t)(d_item / 16 + (n_level == 1 ? ht / 32 : 0)) * ple_l1_planes(n_level, prec) * 1024;
+}
+constexpr size_t ple_rec2_bytes(uint32_t ht, int prec) { return (size_t)(4 + ht / 32) * (prec == 2 ? 2 : 1) * 1024; }
+constexpr size_t ple_gate_bytes(uint32_t d_item, uint32_t n_level, int prec) {
+    return mmoe_gate_bytes(d_item, prec) + (n_level == 2 ? 3 * 64 * 16 : 0);
+}
+constexpr uint32_t ple_task_mask(uint32_t et, uint32_t es) { return (et == 2 ? 3u : 1u) | (es == 2 ? 12u : 4u); }
+constexpr uint32_t ple_shared_mask(uint32_t T, uint32_t et, uint32_t es) {
+    uint32_t m = (es == 2 ? 3u : 1u) << 6;
+    for (uint32_t t = 0; t < T; ++t) m |= (et == 2 ? 3u : 1u) << (2 * t);
+    return m;
+}
+struct PlePacked {
+    std::vector<float> wu, bu, be2, bg2, bt, wo, bo;
+    std::vector<uint8_t> rec;
+};
+inline void pack_ple(const pg_model* m, const uint8_t* blob, const BlobLayout& lay, PlePacked* o) {
+    const uint32_t du = m->d_user, D = m->d_item, din = du + D, T = m->n_out, Et = m->e_task, Es = m->e_shared, he = m->h_e, ht = m->h_t;
+    const uint32_t NL = m->n_level, KS = D / 16, S = he / 16, HB = ht / 32, PL = m->prec == 2 ? 2 : 1, NR1 = m->pl_nrec1, NC = 32 + 32 * NR1;
+    const size_t gfrag = mmoe_gate_bytes(D, m->prec), gbytes = ple_gate_bytes(D, NL, m->prec);
+    const size_t rb1 = ple_rec1_bytes(D, NL, ht, m->prec), rb2 = ple_rec2_bytes(ht, m->prec);
+    const uint32_t P1 = ple_l1_planes(NL, m->prec);
+    auto arr = [&](uint32_t l, int i) { return (const float*)(blob + lay.ple[l][i]); };
+    const float* const wt = (const float*)(blob + lay.wt);
+    o->wu.assign((size_t)du * NC, 0.0f);
+    o->bu.assign(NC, 0.0f);
+    o->rec.assign(gbytes + NR1 * (rb1 + (NL == 2 ? rb2 : 0)), 0);
+    auto record = [&](uint32_t l, uint32_t ri) { return o->rec.data() + gbytes + (l ? NR1 * rb1 + ri * rb2 : ri * rb1); };
+    o->be2.assign(NL == 2 ? (size_t)NR1 * 32 : 32, 0.0f);
+    o->bg2.assign(12, 0.0f);
+    o->bt.assign((size_t)3 * ht, 0.0f);
+    o->wo.assign((size_t)3 * ht, 0.0f);
+    o->bo.assign(3, 0.0f);
+    memcpy(o->bt.data(), blob + lay.bt, (size_t)T * ht * 4);
+    memcpy(o->wo.data(), blob + lay.wo, (size_t)T * ht * 4);
+    memcpy(o->bo.data(), blob + lay.bo, (size_t)T * 4);
+    // one row of a level-1 product: column `col` of W ([din][ncol]) into column c of wu / bu and row p of fragments frag0 + ks
+    auto row1 = [&](uint8_t* rec, uint32_t planes, uint32_t p, uint32_t c, const float* W, uint32_t ncol, uint32_t col, float bias) {
+        for (uint32_t k = 0; k < du; ++k) o->wu[(size_t)k * NC + c] = round_prec(W[(size_t)k * ncol + col], m->prec);
+        o->bu[c] = bias;
+        for (uint32_t ks = 0; ks < KS; ++ks)
+            for (uint32_t hh = 0; hh < 2; ++hh) {
+                float v[8];
+                for (uint32_t e = 0; e < 8; ++e) v[e] = W[(size_t)(du + ks * 16 + 8 * hh + e) * ncol + col];
+                frag_put(rec, ks, hh * 32 + p, v, planes);
+            }
+    };
+    // group g's (T: the shared group's) expert k of level l: its matrix [in][h_e] and bias [h_e], or null
+    auto expert = [&](uint32_t l, uint32_t g, uint32_t k, const float** W, const float** b) {
+        const size_t in = l ? he : din;
+        if (k >= (g < T ? Et : Es)) return false;
+        const size_t x = g < T ? (size_t)g * Et + k : k;
+        *W = arr(l, g < T ? kPleWeT : kPleWeS) + x * in * he;
+        *b = arr(l, g < T ? kPleBeT : kPleBeS) + x * he;
+        return true;
+    };
+    for (uint32_t p = 0; p < 32; ++p) {
+        uint32_t hk, r;
+        mmoe_slot(p, &hk, &r);
+        // the level-1 gate block
+        if (hk == 0 && r < 4 * T) {
+            const uint32_t t = r / 4, c = r % 4, n = Et + Es;
+            if (c < 2 ? c < Et : c - 2 < Es) {
+                const uint32_t col = c < 2 ? c : Et + c - 2;
+                row1(o->rec.data(), PL == 2 ? 3 : 1, p, p, arr(0, kPleWgT) + (size_t)t * din * n, n, col, arr(0, kPleBgT)[t * n + col]);
+            }
+        }
+        if (hk == 1 && r < 8 && NL == 2) {
+            const uint32_t n = T * Et + Es;
+            const bool ok = r < 6 ? (r / 2 < T && r % 2 < Et) : r - 6 < Es;
+            const uint32_t col = r < 6 ? (r / 2) * Et + r % 2 : T * Et + r - 6;
+            if (ok) row1(o->rec.data(), PL == 2 ? 3 : 1, p, p, arr(0, kPleWgS), n, col, arr(0, kPleBgS)[col]);
+        }
+        // the expert blocks of both levels
+        for (uint32_t l = 0; l < NL; ++l)
+            for (uint32_t s = 0; s < S; ++s)
+                for (uint32_t gi = 0; gi <= T; ++gi) {
+                    const uint32_t g = gi ? gi - 1 : T, ri = s * (T + 1) + gi, j = 16 * s + 8 * hk + (r & 7);
+                    uint8_t* const rec = record(l, ri);
+                    const float *W = nullptr, *b = nullptr;
+                    if (!expert(l, g, r >> 3, &W, &b)) continue;
+                    if (l == 0) {
+                        row1(rec, P1, p, 32 + 32 * ri + p, W, he, j, b[j]);
+                        continue;
+                    }
+                    o->be2[(size_t)ri * 32 + p] = b[j];
+                    for (uint32_t ks = 0; ks < 4; ++ks)
+                        for (uint32_t hh = 0; hh < 2; ++hh) {
+                            float v[8];
+                            for (uint32_t e = 0; e < 8; ++e) v[e] = W[(size_t)(ks * 16 + 8 * hh + e) * he + j];
+                            frag_put(rec, ks, hh * 32 + p, v, PL);
+                        }
+                }
+    }
+    // the towers' slices behind the last level's task records
+    for (uint32_t s = 0; s < S; ++s)
+        for (uint32_t t = 0; t < T; ++t)
+            for (uint32_t hb = 0; hb < HB; ++hb)
+                for (uint32_t lane = 0; lane < 64; ++lane) {
+                    float v[8];
+                    for (uint32_t e = 0; e < 8; ++e) v[e] = wt[((size_t)t * he + 16 * s + 8 * (lane >> 5) + e) * ht + 32 * hb + (lane & 31)];
+                    frag_put(record(NL - 1, s * (T + 1) + 1 + t), (NL == 2 ? 4 : KS) + hb, lane, v, PL);
+                }
+    // the second level's task gates: fp32 chains in the kernel, so plain floats in the operand precision
+    if (NL == 2) {
+        float* const g2 = reinterpret_cast<float*>(o->rec.data() + gfrag);
+        const uint32_t n = Et + Es;
+        for (uint32_t t = 0; t < T; ++t)
+            for (uint32_t c = 0; c < 4; ++c) {
+                if (!(c < 2 ? c < Et : c - 2 < Es)) continue;
+                const uint32_t col = c < 2 ? c : Et + c - 2;
+                for (uint32_t j = 0; j < 64; ++j) g2[(t * 64 + j) * 4 + c] = round_prec(arr(1, kPleWgT)[((size_t)t * he + j) * n + col], m->prec);
+                o->bg2[t * 4 + c] = arr(1, kPleBgT)[t * n + col];
+            }
+    }
 }
 
 // PG_MODEL_DCN: where rank_dcn.hip wants each weight.  The kernel's feature order g = 0 .. dc_dp - 1 puts the item columns first,
@@ -775,6 +961,17 @@ inline int model_uploads(pg_model* m, const BlobLayout& lay, const void* blob, M
         add_floats(&m->mm_wu, std::move(pk.wu));
         add_floats(&m->mm_bu, std::move(pk.bu));
         add_packed(&m->mm_rec, std::move(pk.rec), nullptr);
+        add_floats(&m->mm_bt, std::move(pk.bt));
+        add_floats(&m->mm_wo, std::move(pk.wo));
+        add_floats(&m->mm_bo, std::move(pk.bo));
+    } else if (m->kind == PG_MODEL_PLE) {
+        PlePacked pk;
+        pack_ple(m, p, lay, &pk);
+        add_floats(&m->mm_wu, std::move(pk.wu));
+        add_floats(&m->mm_bu, std::move(pk.bu));
+        add_packed(&m->mm_rec, std::move(pk.rec), nullptr);
+        add_floats(&m->pl_be2, std::move(pk.be2));
+        add_floats(&m->pl_bg2, std::move(pk.bg2));
         add_floats(&m->mm_bt, std::move(pk.bt));
         add_floats(&m->mm_wo, std::move(pk.wo));
         add_floats(&m->mm_bo, std::move(pk.bo));

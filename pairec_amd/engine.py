@@ -14,7 +14,7 @@ import numpy as np
 from . import _lib
 
 PREC_F32, PREC_BF16, PREC_BF16X3, PREC_F16X2, PREC_F16 = 0, 1, 2, 3, 4
-MODEL_DNN3, MODEL_FM_TWOTOWER, MODEL_DNN3_MULTI, MODEL_DIN, MODEL_MMOE, MODEL_DCN, MODEL_MHA = 1, 2, 3, 4, 5, 6, 8
+MODEL_DNN3, MODEL_FM_TWOTOWER, MODEL_DNN3_MULTI, MODEL_DIN, MODEL_MMOE, MODEL_DCN, MODEL_MHA, MODEL_PLE = 1, 2, 3, 4, 5, 6, 8, 9
 DIN_MAX_SEQ = 64
 MHA_MAX_SEQ = 512
 MAX_QUERIES = 256         # per table pass (32 when dim > 128)
@@ -2251,6 +2251,29 @@ def pack_mmoe(we, be, wg, bg, wt, bt, wo, bo, d_user: int) -> bytes:
             wt.tobytes() + f(bt).tobytes() + f(wo).tobytes() + f(bo).tobytes())
 
 
+def pack_ple(levels, wt, bt, wo, bo, d_user: int) -> bytes:
+    """PG_MODEL_PLE blob (include/pairec_gpu.h).  levels: one mapping per extraction level (1 or 2) with we_t [T][E_t][in][h_e],
+    we_s [E_s][in][h_e], be_t [T][E_t][h_e], be_s [E_s][h_e], wg_t [T][in][E_t + E_s], bg_t [T][E_t + E_s] and, in every level but
+    the last, wg_s [in][T E_t + E_s], bg_s [T E_t + E_s]; in = d_user + d_item at level 1, h_e at level 2.  Towers wt [T][h_e][h_t],
+    bt [T][h_t], wo [T][h_t], bo [T]."""
+    f = lambda a: np.ascontiguousarray(a, dtype=np.float32)   # noqa: E731
+    wt = f(wt)
+    n_t, h_e, h_t = wt.shape
+    (_, e_t, din, _), e_s = f(levels[0]["we_t"]).shape, f(levels[0]["we_s"]).shape[0]
+    parts = [struct.pack("<8I", d_user, din - d_user, n_t, e_t, e_s, h_e, len(levels), h_t)]
+    for l, lv in enumerate(levels):
+        n_in, last = (h_e if l else din), l + 1 == len(levels)
+        shapes = {"we_t": (n_t, e_t, n_in, h_e), "we_s": (e_s, n_in, h_e), "be_t": (n_t, e_t, h_e), "be_s": (e_s, h_e),
+                  "wg_t": (n_t, n_in, e_t + e_s), "bg_t": (n_t, e_t + e_s)}
+        if not last:
+            shapes.update({"wg_s": (n_in, n_t * e_t + e_s), "bg_s": (n_t * e_t + e_s,)})
+        for name, shape in shapes.items():
+            assert f(lv[name]).shape == shape, (l, name, f(lv[name]).shape, shape)
+            parts.append(f(lv[name]).tobytes())
+    assert f(bt).shape == (n_t, h_t) and f(wo).shape == (n_t, h_t) and f(bo).reshape(-1).shape == (n_t,)
+    return b"".join(parts + [wt.tobytes(), f(bt).tobytes(), f(wo).tobytes(), f(bo).tobytes()])
+
+
 def pack_dcn(wc, bc, w1, b1, w2, b2, w3, b3, d_user: int) -> bytes:
     """PG_MODEL_DCN blob (include/pairec_gpu.h): cross layers wc [L][D][D], bc [L][D] over x_0 = [user | item], D = d_user + d_item;
     head w1 [D][h1], b1, w2 [h1][h2], b2, w3 [h2] or [h2][n_out], b3 [n_out]."""
@@ -2382,6 +2405,19 @@ class RankModel:
     def rank_mmoe_dev(self, table: Table, d_user_vecs: int, d_cand_rows: int, d_req_offsets: int, n_req: int, n_items: int, d_out: int):
         _lib.check(self.ctx.L.pg_rank_mmoe_dev(self.ctx.h, self.h, table.h, C.c_void_p(d_user_vecs), C.c_void_p(d_cand_rows),
                                                C.c_void_p(d_req_offsets), n_req, n_items, C.c_void_p(d_out)))
+
+    def rank_ple(self, table: Table, user_vecs: np.ndarray, cand_rows: np.ndarray, req_offsets: Sequence[int]) -> np.ndarray:
+        """MODEL_PLE: scores [n_items] for one task, [n_task][n_items] for several (one plane per task)."""
+        u = np.ascontiguousarray(user_vecs, dtype=np.float32)
+        c = np.ascontiguousarray(cand_rows, dtype=np.uint32)
+        ro = np.ascontiguousarray(req_offsets, dtype=np.uint32)
+        out = np.empty((self.n_out, c.shape[0]), dtype=np.float32)
+        _lib.check(self.ctx.L.pg_rank_ple(self.ctx.h, self.h, table.h, _ptr(u), _ptr(c), _ptr(ro), ro.shape[0] - 1, _ptr(out)))
+        return out[0] if self.n_out == 1 else out
+
+    def rank_ple_dev(self, table: Table, d_user_vecs: int, d_cand_rows: int, d_req_offsets: int, n_req: int, n_items: int, d_out: int):
+        _lib.check(self.ctx.L.pg_rank_ple_dev(self.ctx.h, self.h, table.h, C.c_void_p(d_user_vecs), C.c_void_p(d_cand_rows),
+                                              C.c_void_p(d_req_offsets), n_req, n_items, C.c_void_p(d_out)))
 
     def rank_dcn(self, table: Table, user_vecs: np.ndarray, cand_rows: np.ndarray, req_offsets: Sequence[int]) -> np.ndarray:
         """MODEL_DCN: scores [n_items] for one output, [n_out][n_items] for several (one plane per head)."""

@@ -22,6 +22,11 @@ Input: an .npz whose arrays are the layers' kernels exactly as a framework saves
       we [E][d_user + d_item][h_e]   be [E][h_e]   wg [T][d_user + d_item][E]   bg [T][E]
       wt [T][h_e][h_t]   bt [T][h_t]   wo [T][h_t] or [T][h_t][1]   bo [T]
       ((E, h_e) one of (2,128) (4,64) (4,128) (8,64); T 1..4; h_t 32 or 64; task t is the algorithm's t-th "Outputs" name)
+  PLE (PG_MODEL_PLE: one or two extraction levels of T task groups and a shared group of experts; chosen when the file holds
+  `we1_t`; level l = 1, 2 — level 2's arrays only in a two-level model, wg{l}_s / bg{l}_s only below the last level):
+      we{l}_t [T][E_t][in][h_e]   we{l}_s [E_s][in][h_e]   be{l}_t [T][E_t][h_e]   be{l}_s [E_s][h_e]   (in = d_user + d_item, then h_e)
+      wg{l}_t [T][in][E_t + E_s]   bg{l}_t [T][E_t + E_s]   wg{l}_s [in][T E_t + E_s]   bg{l}_s [T E_t + E_s]
+      wt, bt, wo, bo as an MMoE's   (T 1..3; E_t, E_s 1 or 2; h_e 64, or 128 with one level; h_t 32 or 64)
   DCN-v2 (PG_MODEL_DCN: stacked full-rank cross layers x_{l+1} = x_0 * (Wc_l' x_l + bc_l) + x_l, then the trunk above on x_L;
   chosen when the file holds `wc`):
       wc [L][D][D] (D = d_user + d_item <= 256; L 1..3)   bc [L][D]
@@ -43,7 +48,7 @@ import sys
 import numpy as np
 
 DNN3_SHAPES = {(128, 128), (256, 128), (256, 256), (512, 256), (1024, 512)}
-KIND_DNN3, KIND_DNN3_MULTI, KIND_DIN, KIND_MMOE, KIND_DCN, KIND_MHA = 1, 3, 4, 5, 6, 8
+KIND_DNN3, KIND_DNN3_MULTI, KIND_DIN, KIND_MMOE, KIND_DCN, KIND_MHA, KIND_PLE = 1, 3, 4, 5, 6, 8, 9
 MMOE_SHAPES = {(2, 128), (4, 64), (4, 128), (8, 64)}
 DCN_HEADS = {(128, 128), (256, 128)}
 MHA_SHAPES = {(64, 1), (64, 2), (128, 2), (128, 4)}
@@ -149,6 +154,33 @@ def pack_mmoe_arrays(we, be, wg, bg, wt, bt, wo, bo, d_user):
     return KIND_MMOE, blob, "PG_MODEL_MMOE [%d+%d] -> %d experts x %d -> %d towers x %d, %d bytes" % (d_user, d_item, n_e, h_e, n_t, h_t, len(blob))
 
 
+def pack_ple_arrays(levels, wt, bt, wo, bo, d_user):
+    """levels: per extraction level a mapping we_t, we_s, be_t, be_s, wg_t, bg_t (and wg_s, bg_s below the last) → (KIND_PLE, blob, description)"""
+    wt, we_t, we_s = np.asarray(wt), np.asarray(levels[0]["we_t"]), np.asarray(levels[0]["we_s"])
+    if wt.ndim != 3 or we_t.ndim != 4 or we_s.ndim != 3:
+        raise ValueError("we1_t / we1_s / wt must be [T][E_t][in][h_e], [E_s][in][h_e] and [T][h_e][h_t]")
+    (n_t, e_t, din, h_e), e_s, h_t, n_l, d_user = we_t.shape, we_s.shape[0], wt.shape[2], len(levels), int(d_user)
+    d_item = din - d_user
+    if not 1 <= d_user <= 4096 or d_item not in (64, 128):
+        raise ValueError("we1_t has %d input rows: with d_user = %d the item half is %d wide (the table's dim: 64 or 128)" % (din, d_user, d_item))
+    if (not 1 <= n_t <= 3 or e_t not in (1, 2) or e_s not in (1, 2) or n_l not in (1, 2) or h_e not in ((64, 128) if n_l == 1 else (64,)) or
+            h_t not in (32, 64) or (n_t * e_t + e_s) * h_e > 512):
+        raise ValueError("%d levels of %d x %d task and %d shared experts x %d, towers x %d have no kernel (1..3 tasks; 1 or 2 experts per group; "
+                         "width 64, or 128 with one level; tower width 32 or 64; all experts x width <= 512)" % (n_l, n_t, e_t, e_s, h_e, h_t))
+    parts = []
+    for l, lv in enumerate(levels):
+        n_in, n = (h_e if l else din), "%d_" % (l + 1)
+        parts += [_f32(lv["we_t"], (n_t, e_t, n_in, h_e), "we" + n + "t"), _f32(lv["we_s"], (e_s, n_in, h_e), "we" + n + "s"),
+                  _f32(lv["be_t"], (n_t, e_t, h_e), "be" + n + "t"), _f32(lv["be_s"], (e_s, h_e), "be" + n + "s"),
+                  _f32(lv["wg_t"], (n_t, n_in, e_t + e_s), "wg" + n + "t"), _f32(lv["bg_t"], (n_t, e_t + e_s), "bg" + n + "t")]
+        if l + 1 < n_l:
+            parts += [_f32(lv["wg_s"], (n_in, n_t * e_t + e_s), "wg" + n + "s"), _f32(np.reshape(lv["bg_s"], -1), (n_t * e_t + e_s,), "bg" + n + "s")]
+    parts += [_f32(wt, (n_t, h_e, h_t), "wt"), _f32(bt, (n_t, h_t), "bt"), _f32(np.reshape(wo, (n_t, -1)), (n_t, h_t), "wo"), _f32(np.reshape(bo, -1), (n_t,), "bo")]
+    blob = struct.pack("<8I", d_user, d_item, n_t, e_t, e_s, h_e, n_l, h_t) + b"".join(a.tobytes() for a in parts)
+    return KIND_PLE, blob, "PG_MODEL_PLE [%d+%d] -> %d levels of %d x %d + %d experts x %d -> %d towers x %d, %d bytes" % (
+        d_user, d_item, n_l, n_t, e_t, e_s, h_e, n_t, h_t, len(blob))
+
+
 def pack_dcn_arrays(wc, bc, w1, b1, w2, b2, w3, b3, d_user):
     """→ (KIND_DCN, blob, description)"""
     wc, w1, w2 = np.asarray(wc), np.asarray(w1), np.asarray(w2)
@@ -182,6 +214,11 @@ def pack_npz(path_or_mapping, d_user=None, rename=None, n_head=None):
         return z[key]
     if d_user is None:
         d_user = int(np.asarray(get("d_user")).reshape(-1)[0])
+    if rename.get("we1_t", "we1_t") in z:
+        n_l = 2 if rename.get("we2_t", "we2_t") in z else 1
+        levels = [{k: get("%s%d_%s" % (k[:2], l + 1, k[3])) for k in ("we_t", "we_s", "be_t", "be_s", "wg_t", "bg_t") + (("wg_s", "bg_s") if l + 1 < n_l else ())}
+                  for l in range(n_l)]
+        return pack_ple_arrays(levels, *[get(n) for n in ("wt", "bt", "wo", "bo")], d_user)
     if rename.get("we", "we") in z:
         return pack_mmoe_arrays(*[get(n) for n in ("we", "be", "wg", "bg", "wt", "bt", "wo", "bo")], d_user)
     trunk = [get(n) for n in ("w1", "b1", "w2", "b2", "w3", "b3")]
