@@ -70,7 +70,7 @@ typedef enum {
  *                  Refused at load (PG_ERR_UNSUPPORTED): PG_MODEL_FM_TWOTOWER; a non-finite weight; a scaled weight or
  *                  scale factor outside fp32's normal range. */
 typedef enum { PG_PREC_F32 = 0, PG_PREC_BF16 = 1, PG_PREC_BF16X3 = 2, PG_PREC_F16X2 = 3, PG_PREC_F16 = 4 } pg_prec;
-typedef enum { PG_MODEL_DNN3 = 1, PG_MODEL_FM_TWOTOWER = 2, PG_MODEL_DNN3_MULTI = 3, PG_MODEL_DIN = 4, PG_MODEL_MMOE = 5, PG_MODEL_DCN = 6, PG_MODEL_MHA = 8, PG_MODEL_PLE = 9 /* 7 is kept unassigned: pg_model_load refuses it as unknown */ } pg_model_kind;
+typedef enum { PG_MODEL_DNN3 = 1, PG_MODEL_FM_TWOTOWER = 2, PG_MODEL_DNN3_MULTI = 3, PG_MODEL_DIN = 4, PG_MODEL_MMOE = 5, PG_MODEL_DCN = 6, PG_MODEL_MHA = 8, PG_MODEL_PLE = 9, PG_MODEL_GBDT = 10 /* 7 is kept unassigned: pg_model_load refuses it as unknown */ } pg_model_kind;
 
 const char* pg_last_error(void);
 const char* pg_version(void);
@@ -1605,6 +1605,47 @@ int pg_rank_fm2t_rows_dev(pg_ctx* ctx, const pg_model* m, const pg_features* fs,
 int pg_rank_fm2t_rows(pg_ctx* ctx, const pg_model* m, const pg_features* fs, const int32_t* item_field_cols,
                       const float* user_vecs, const int32_t* user_field_ids, const uint32_t* cand_rows,
                       const uint32_t* req_offsets, uint32_t n_req, float* out_scores);
+
+/* ---- rank: GBDT — a forest of complete binary trees over user and item feature values (PG_MODEL_GBDT) --------------------------
+ *   Replaces  the remote PS-SMART model behind the reference's PMML processor (algorithm/eas/model.go:22,39-41, pmml_request.go,
+ *             pmml_response.go:10-45, pssmartResponseFunc in client.go:61): the reference ships one feature map per item and reads
+ *             back a score and a label; here the forest is resident and an item's features are the typed columns of `fs`.  The
+ *             host mirror decodes the reply as before (PssmartScore); its "label 0 -> 1 - score" flip stays there.
+ *   Model     per candidate i of request r:  x = [ user_feats[r][0 .. n_user_feat) | column item_cols[k] at cand_rows[i], k = 0 ..
+ *             n_item_feat - 1 ], every value fp32.  An item value is the column's value converted to fp32 once (int32, int64,
+ *             float32, float64, as pg_features_gather_f32_dev with no scale); a row >= the store's rows reads the column default.
+ *             Tree t = 0 .. n_tree - 1 is a complete binary tree of depth d: nodes n = 0 .. 2^d - 2 with children 2n + 1, 2n + 2.
+ *             At a node with feature f and threshold thr go left iff x[f] < thr (fp32 compare); a NaN x[f] goes left iff the
+ *             node's missing-left bit is set.  After d steps the leaf is leaf[t][n - (2^d - 1)].
+ *               margin = (double)base + sum_t (double)leaf_t      an fp64 chain in ascending tree order: the specification
+ *               objective 1 (identity):  score = (float)margin
+ *               objective 0 (logistic):  score = (float)(1 / (1 + exp(-margin))), fp64, exp as Go's math.Exp restated
+ *                                        (csrc/expr_prog.hpp go_exp), rounded once to fp32
+ *   Blob      u32 n_user_feat (0..64), n_item_feat (0..64; the sum >= 1), n_tree (1..4096), depth (1..8), objective (0 | 1);
+ *             f32 base; then per tree u32 node[2^d - 1] (bits 0..6 the feature's index in x, bit 31 missing goes left),
+ *             f32 thr[2^d - 1], f32 leaf[2^d] — little-endian.  pa.pack_gbdt / tools/pack_model.py build it from pointer trees.
+ *   Precision PG_PREC_F32 only; objective 1 is bit-defined by the lines above, objective 0 up to the one fp32 rounding.
+ *   Output    out_scores[i]; pg_model_num_outputs() = 1.
+ *   Refused   pg_model_load (PG_ERR_UNSUPPORTED): any other precision; a shape outside the ranges above; a feature index >=
+ *             n_user_feat + n_item_feat; a NaN threshold; a non-finite leaf or base.  A blob of another length: PG_ERR_INVALID.
+ *             pg_rank_gbdt[_dev] (PG_ERR_INVALID, on the host, the context left usable): a model of another kind, a column index
+ *             outside the store; pg_rank_gbdt also offsets that descend or do not start at 0.  A candidate row past the store is
+ *             legal: an item without the feature.  Every other rank entry point and pg_coalescer_create[_scene] refuse a
+ *             PG_MODEL_GBDT.  pg_rank_gbdt_dev does not synchronise with the host: the column descriptors travel as kernel
+ *             arguments.  user_feats may be NULL when n_user_feat is 0.
+ *   Not here  multi-class and multi-output forests; categorical (set-membership) splits; trees deeper than 8 (leaf-wise LightGBM);
+ *             more than 64 + 64 features; the coalescer and the pg_recommend_* pipelines.
+ * The kernel streams the forest through LDS in chunks of PG_GBDT_CHUNK_BYTES: PG_GBDT_CHUNK_BYTES / (12 << depth) whole trees.  A
+ * workgroup takes a tile of 64 candidates of one request; in a call of at least PG_GBDT_WIDE_ITEMS candidates over at most 80
+ * features, PG_GBDT_WIDE_TILE.  Neither changes a score. */
+#define PG_GBDT_CHUNK_BYTES 24576
+#define PG_GBDT_WIDE_ITEMS 131072
+#define PG_GBDT_WIDE_TILE 256
+int pg_rank_gbdt(pg_ctx* ctx, const pg_model* m, const pg_features* fs, const int32_t* item_cols, const float* user_feats,
+                 const uint32_t* cand_rows, const uint32_t* req_offsets, uint32_t n_req, float* out_scores);
+int pg_rank_gbdt_dev(pg_ctx* ctx, const pg_model* m, const pg_features* fs, const int32_t* item_cols, const float* d_user_feats,
+                     const uint32_t* d_cand_rows, const uint32_t* d_req_offsets, uint32_t n_req, uint32_t n_items,
+                     float* d_out_scores);
 
 /* ---- materialised item records (FM + two-tower) ---------------------------------------------------------------
  * An item's field ids are static per item (the columns of `fs`), so the item side of model `m` can be laid out once, at

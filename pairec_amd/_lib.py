@@ -17,7 +17,7 @@ EXPORTS = [
     "pg_device_free", "pg_memcpy_h2d", "pg_memcpy_d2h", "pg_table_create", "pg_table_destroy",
     "pg_table_fill_synthetic", "pg_table_upload", "pg_table_download", "pg_table_swap",
     "pg_table_info", "pg_table_gather", "pg_recall_topk", "pg_recall_topk_dev", "pg_recall_topk_l2", "pg_recall_topk_l2_dev", "pg_recall_topk_where", "pg_table_view_create",
-    "pg_topk_merge_dev", "pg_model_load", "pg_model_destroy", "pg_model_num_outputs", "pg_model_f16_stats", "pg_rank_dnn3", "pg_rank_dnn3_dev", "pg_rank_din", "pg_rank_din_dev", "pg_rank_mmoe", "pg_rank_mmoe_dev", "pg_rank_ple", "pg_rank_ple_dev", "pg_rank_dcn", "pg_rank_dcn_dev", "pg_rank_mha", "pg_rank_mha_dev",
+    "pg_topk_merge_dev", "pg_model_load", "pg_model_destroy", "pg_model_num_outputs", "pg_model_f16_stats", "pg_rank_dnn3", "pg_rank_dnn3_dev", "pg_rank_din", "pg_rank_din_dev", "pg_rank_mmoe", "pg_rank_mmoe_dev", "pg_rank_ple", "pg_rank_ple_dev", "pg_rank_gbdt", "pg_rank_gbdt_dev", "pg_rank_dcn", "pg_rank_dcn_dev", "pg_rank_mha", "pg_rank_mha_dev",
     "pg_rank_fm2t", "pg_rank_fm2t_dev", "pg_expr_compile", "pg_expr_free", "pg_expr_num_vars", "pg_expr_set_score_rewrites", "pg_expr_compile_typed", "pg_expr_is_antlr", "pg_fuse_scores_dev",
     "pg_expr_var_name", "pg_expr_eval", "pg_expr_eval_dev", "pg_sort_scores", "pg_sort_scores_dev",
     "pg_dpp", "pg_stats", "pg_last_scan_kernel_ms", "pg_rows_to_local_dev", "pg_widen_f32_dev",
@@ -139,6 +139,9 @@ class PgTableDerived(C.Structure):
 # pg_table_derived_info's parts and pg_table_derived_read's arrays (PG_DERIVED_*, PG_DERIVED_ARR_*)
 DERIVED_STATS, DERIVED_I4, DERIVED_R2, DERIVED_NX, DERIVED_PRED = 1, 2, 4, 8, 16
 DERIVED_ALL = 31
+# PG_GBDT_*: rank_gbdt.hip streams a forest in chunks of this many bytes (whole trees of 12 << depth bytes each) and takes tiles of
+# 64 candidates, or GBDT_WIDE_TILE in a call of at least GBDT_WIDE_ITEMS candidates
+GBDT_CHUNK_BYTES, GBDT_WIDE_ITEMS, GBDT_WIDE_TILE = 24576, 131072, 256
 DERIVED_ARRAYS = {"i8": 0, "bf16": 1, "blknorm2": 2, "i4": 3, "i4s": 4, "i8r": 5, "nx": 6, "nxmin": 7, "pred": 8}
 
 
@@ -479,6 +482,8 @@ def load():
         "pg_rank_mmoe_dev": [vp, vp, vp, vp, vp, vp, u32, u32, vp],
         "pg_rank_ple": [vp, vp, vp, vp, vp, vp, u32, vp],
         "pg_rank_ple_dev": [vp, vp, vp, vp, vp, vp, u32, u32, vp],
+        "pg_rank_gbdt": [vp, vp, vp, vp, vp, vp, vp, u32, vp],
+        "pg_rank_gbdt_dev": [vp, vp, vp, vp, vp, vp, vp, u32, u32, vp],
         "pg_rank_dcn": [vp, vp, vp, vp, vp, vp, u32, vp],
         "pg_rank_dcn_dev": [vp, vp, vp, vp, vp, vp, u32, u32, vp],
         "pg_rank_mha": [vp, vp, vp, vp, vp, vp, vp, vp, u32, vp],

@@ -101,6 +101,7 @@ enum ScratchSlot : int {
     kSlotDcn = 40,           // rank_dcn.hip: the tile table and the requests' user halves c0 (and x_0's user columns) of a PG_MODEL_DCN call
     kSlotMha = 41,           // rank_mha.hip: kSlotDin's layout for a PG_MODEL_MHA run, behind it the run's n_valid and K/V records (scratch_layout.hpp kDinRunItems and kMhaRunReqs bound it)
     kSlotPle = 42,           // rank_ple.hip: the tile table and the requests' user halves c1 of a PG_MODEL_PLE call
+    kSlotGbdt = 43,          // rank_gbdt.hip: the tile table of a PG_MODEL_GBDT call
     kSlotCount
 };
 
@@ -578,6 +579,10 @@ int rank_mmoe_dev_locked(pg_ctx* ctx, const pg_model* m, const pg_table* t, cons
 // rank_ple.hip: a PG_MODEL_PLE — one or two levels of task and shared experts under task towers, n_task planes of n_items scores
 int rank_ple_dev_locked(pg_ctx* ctx, const pg_model* m, const pg_table* t, const float* d_user, const uint32_t* d_cand,
                         const uint32_t* d_off, uint32_t n_req, uint32_t n_items, float* d_out);
+// rank_gbdt.hip: a PG_MODEL_GBDT — a forest over the request's user features and the candidates' columns item_cols of fs (checked
+// by the caller), n_items scores
+int rank_gbdt_dev_locked(pg_ctx* ctx, const pg_model* m, const pg_features* fs, const int32_t* item_cols, const float* d_user,
+                         const uint32_t* d_cand, const uint32_t* d_off, uint32_t n_req, uint32_t n_items, float* d_out);
 // rank_dcn.hip: a PG_MODEL_DCN — cross layers and a DNN3 head, n_out planes of n_items scores
 int rank_dcn_dev_locked(pg_ctx* ctx, const pg_model* m, const pg_table* t, const float* d_user, const uint32_t* d_cand,
                         const uint32_t* d_off, uint32_t n_req, uint32_t n_items, float* d_out);

@@ -11,7 +11,7 @@
 // Numeric columns only (int32 / int64 / float32 / float64, the PBFeature scalar kinds); string features are
 // dictionary-encoded to integer ids by the host before upload.  The "simple normalizer" on the float path is
 // value*scale + bias in fp32 (one fmaf); anything richer goes through the expression evaluator (pg_expr_*).
-#include "common.hpp"
+#include "feature_cols.hpp"
 
 #include <cmath>
 #include <cstring>
@@ -19,26 +19,6 @@
 #include <vector>
 
 namespace pg {
-
-struct ColDesc {
-    const void* base;
-    int32_t dtype;
-    int32_t pad;
-    double def;
-};
-
-// (float)value with ONE rounding: an integer converts to fp32 directly — through a double an int64 beyond 2^53 rounds twice
-// (2^60 + 2^36 + 1 is 0x5D800001 directly, 0x5D800000 by way of the double).  The stored default (pg_features_set_column) is
-// already a value of the column's dtype, exact in the double that carries it.
-__device__ __forceinline__ float load_as_f32(const ColDesc& c, uint32_t row, uint64_t rows) {
-    if (row >= rows) return (float)c.def;
-    switch (c.dtype) {
-        case PG_F_I32: return (float)((const int32_t*)c.base)[row];
-        case PG_F_I64: return (float)((const int64_t*)c.base)[row];
-        case PG_F_F32: return ((const float*)c.base)[row];
-        default: return (float)((const double*)c.base)[row];
-    }
-}
 
 // out[i][f] = int32 view of integer column f at rows[i] (int64 values saturate; default for absent rows)
 __global__ void features_gather_i32_kernel(const ColDesc* __restrict__ cols, uint32_t F, uint64_t rows,

@@ -366,6 +366,41 @@ int pg_rank_ple(pg_ctx* ctx, const pg_model* m, const pg_table* t, const float* 
         });
 }
 
+// a GBDT call's columns: indices inside the store (the descriptors are read under the lock, in rank_gbdt_dev_locked)
+static int gbdt_check_cols(const char* who, const pg_model* m, const pg_features* fs, const int32_t* item_cols) {
+    PG_REQUIRE(m->gb_ni == 0 || item_cols, "%s: NULL argument", who);
+    for (uint32_t f = 0; f < m->gb_ni; ++f)
+        PG_REQUIRE(item_cols[f] >= 0 && (size_t)item_cols[f] < fs->cols.size(), "%s: column index %d out of range (%zu columns)", who,
+                   item_cols[f], fs->cols.size());
+    return PG_OK;
+}
+
+int pg_rank_gbdt_dev(pg_ctx* ctx, const pg_model* m, const pg_features* fs, const int32_t* item_cols, const float* d_user_feats,
+                     const uint32_t* d_cand_rows, const uint32_t* d_req_offsets, uint32_t n_req, uint32_t n_items, float* d_out_scores) {
+    PG_REQUIRE(ctx && m && fs && d_cand_rows && d_req_offsets && d_out_scores, "pg_rank_gbdt_dev: NULL argument");
+    PG_REQUIRE(m->kind == PG_MODEL_GBDT, "pg_rank_gbdt_dev: model is not GBDT");
+    PG_REQUIRE(m->gb_nu == 0 || d_user_feats, "pg_rank_gbdt_dev: NULL argument");
+    PG_REQUIRE(n_req <= 65535, "pg_rank_gbdt_dev: at most 65535 requests per call");
+    std::lock_guard<std::mutex> g(ctx->mu);
+    int rc;
+    if ((rc = gbdt_check_cols("pg_rank_gbdt_dev", m, fs, item_cols))) return rc;
+    return pg::rank_gbdt_dev_locked(ctx, m, fs, item_cols, d_user_feats, d_cand_rows, d_req_offsets, n_req, n_items, d_out_scores);
+}
+
+int pg_rank_gbdt(pg_ctx* ctx, const pg_model* m, const pg_features* fs, const int32_t* item_cols, const float* user_feats,
+                 const uint32_t* cand_rows, const uint32_t* req_offsets, uint32_t n_req, float* out_scores) {
+    PG_REQUIRE(ctx && m && fs && req_offsets, "pg_rank_gbdt: NULL argument");
+    PG_REQUIRE(m->kind == PG_MODEL_GBDT, "pg_rank_gbdt: model is not GBDT");
+    // (a candidate row past the store is an item without the feature: no range check on the rows)
+    const pg::HostIn in[] = {{user_feats, false, m->gb_nu, 4, m->gb_nu != 0}, {cand_rows, true, 1, 4}};
+    return pg::rank_from_host(
+        "pg_rank_gbdt", ctx, m, nullptr, in, nullptr, req_offsets, n_req, out_scores,
+        [&](uint32_t) -> int { return gbdt_check_cols("pg_rank_gbdt", m, fs, item_cols); },
+        [&](void* const* d, const uint32_t* d_off, uint32_t n_items, float* d_scores) {
+            return pg::rank_gbdt_dev_locked(ctx, m, fs, item_cols, (const float*)d[0], (const uint32_t*)d[1], d_off, n_req, n_items, d_scores);
+        });
+}
+
 int pg_rank_dcn_dev(pg_ctx* ctx, const pg_model* m, const pg_table* t, const float* d_user_vecs, const uint32_t* d_cand_rows,
                      const uint32_t* d_req_offsets, uint32_t n_req, uint32_t n_items, float* d_out_scores) {
     PG_REQUIRE(ctx && m && t && d_user_vecs && d_cand_rows && d_req_offsets && d_out_scores, "pg_rank_dcn_dev: NULL argument");

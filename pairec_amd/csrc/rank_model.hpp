@@ -87,6 +87,10 @@ struct pg_model {
     float* mh_wv = nullptr;     // [64][d_att] fp32, output columns in mha_row order
     float* mh_bv = nullptr;     // [d_att] in that order
     void* mh_wo = nullptr;      // Wo [d_att][64] in MFMA fragment order, input rows in feature order
+    // PG_MODEL_GBDT (rank_gbdt.hip; pack_gbdt below): gb_ntree complete trees of depth gb_depth over gb_nu user + gb_ni item features
+    uint32_t gb_nu = 0, gb_ni = 0, gb_ntree = 0, gb_depth = 0, gb_obj = 0;
+    float gb_base = 0.f;
+    void* gb_forest = nullptr;  // whole chunks of kGbdtChunkBytes, tree records back to back (gbdt_tree_bytes each)
     float* b2 = nullptr;
     float* w3 = nullptr;    // DNN3 head(s): [n_out][h2]
     float* fields = nullptr;          // two-tower: all field tables, one allocation
@@ -141,6 +145,18 @@ inline bool mha_shape_ok(uint32_t datt, uint32_t heads) {
     PG_MHA_SHAPES(X)
 #undef X
     return false;
+}
+// PG_MODEL_GBDT: the forest streams through LDS in chunks of whole trees.  A tree's record is 2^d node slots of 8 bytes (slot
+// 2^d - 1 unused) and 2^d leaves: 12 << d bytes, so a chunk holds 2^(11 - d) trees exactly — 8 at depth 8, 1024 at depth 1.
+constexpr uint32_t kGbdtChunkBytes = PG_GBDT_CHUNK_BYTES;
+constexpr uint32_t kGbdtMaxFeat = 64, kGbdtMaxTrees = 4096, kGbdtMaxDepth = 8;
+// candidates per workgroup tile: one wave, or four in a call of at least PG_GBDT_WIDE_ITEMS candidates whose feature rows leave
+// the two chunk buffers room (kGbdtWideMaxFeat rows of 1 KiB beside 48 KiB)
+constexpr uint32_t kGbdtTile = 64, kGbdtWideTile = PG_GBDT_WIDE_TILE, kGbdtWideItems = PG_GBDT_WIDE_ITEMS, kGbdtWideMaxFeat = 80;
+constexpr uint32_t gbdt_tree_bytes(uint32_t depth) { return 12u << depth; }
+constexpr uint32_t gbdt_chunk_trees(uint32_t depth) { return kGbdtChunkBytes / gbdt_tree_bytes(depth); }
+inline bool gbdt_shape_ok(uint32_t nu, uint32_t ni, uint32_t nt, uint32_t d, uint32_t obj) {
+    return nu <= kGbdtMaxFeat && ni <= kGbdtMaxFeat && nu + ni >= 1 && nt >= 1 && nt <= kGbdtMaxTrees && d >= 1 && d <= kGbdtMaxDepth && obj <= 1;
 }
 inline bool fm2t_shape_ok(uint32_t th, uint32_t to, uint32_t k) {
 #define X(A, B, C) if (th == A && to == B && k == C) return true;
@@ -247,6 +263,8 @@ struct BlobLayout {
     // be_s [E_s][h_e], Wg_t [T][in][E_t + E_s], bg_t [T][E_t + E_s] and, below the last level only, Wg_s [in][T E_t + E_s],
     // bg_s [T E_t + E_s]; then wt, bt, wo, bo as an MMoE's
     size_t ple[2][8] = {};
+    // GBDT: tree t at gb_trees + t * gb_tree_bytes: u32 node[2^d - 1], f32 thr[2^d - 1], f32 leaf[2^d]
+    size_t gb_trees = 0, gb_tree_bytes = 0;
 };
 enum { kPleWeT, kPleWeS, kPleBeT, kPleBeS, kPleWgT, kPleBgT, kPleWgS, kPleBgS };
 
@@ -269,6 +287,8 @@ inline int parse_model_blob(int kind, int prec, const void* blob, size_t len, pg
         return refuse(why, PG_ERR_UNSUPPORTED, "pg_model_load: a PG_MODEL_MMOE is served in PG_PREC_BF16 and PG_PREC_BF16X3 (precision %d asked)", prec);
     if (kind == PG_MODEL_PLE && prec != PG_PREC_BF16 && prec != PG_PREC_BF16X3)
         return refuse(why, PG_ERR_UNSUPPORTED, "pg_model_load: a PG_MODEL_PLE is served in PG_PREC_BF16 and PG_PREC_BF16X3 (precision %d asked)", prec);
+    if (kind == PG_MODEL_GBDT && prec != PG_PREC_F32)
+        return refuse(why, PG_ERR_UNSUPPORTED, "pg_model_load: a PG_MODEL_GBDT is served in PG_PREC_F32 (precision %d asked)", prec);
     if (kind == PG_MODEL_DCN && prec != PG_PREC_BF16 && prec != PG_PREC_BF16X3)
         return refuse(why, PG_ERR_UNSUPPORTED, "pg_model_load: a PG_MODEL_DCN is served in PG_PREC_BF16 and PG_PREC_BF16X3 (precision %d asked)", prec);
     const uint8_t* p = (const uint8_t*)blob;
@@ -407,6 +427,41 @@ inline int parse_model_blob(int kind, int prec, const void* blob, size_t len, pg
             need += nf[i] * 4;
         }
         if (len != need) return refuse(why, PG_ERR_INVALID, "pg_model_load: PLE blob is %zu bytes, expected %zu", len, need);
+    } else if (kind == PG_MODEL_GBDT) {
+        m->kind = PG_MODEL_GBDT;
+        if (len < 24) return refuse(why, PG_ERR_INVALID, "pg_model_load: blob too short");
+        uint32_t hdr[5];
+        memcpy(hdr, p, 20);
+        memcpy(&m->gb_base, p + 20, 4);
+        m->gb_nu = hdr[0]; m->gb_ni = hdr[1]; m->gb_ntree = hdr[2]; m->gb_depth = hdr[3]; m->gb_obj = hdr[4];
+        m->n_out = 1;
+        if (!gbdt_shape_ok(m->gb_nu, m->gb_ni, m->gb_ntree, m->gb_depth, m->gb_obj))
+            return refuse(why, PG_ERR_UNSUPPORTED, "pg_model_load: GBDT shape [%u+%u] features, %u trees of depth %u, objective %u unsupported (0..64 "
+                                                   "user and 0..64 item features, at least one; 1..4096 trees; depth 1..8; objective 0 or 1)",
+                          m->gb_nu, m->gb_ni, m->gb_ntree, m->gb_depth, m->gb_obj);
+        const size_t nn = ((size_t)1 << m->gb_depth) - 1, nl = nn + 1;
+        lay->gb_trees = 24;
+        lay->gb_tree_bytes = (2 * nn + nl) * 4;
+        const size_t need = 24 + m->gb_ntree * lay->gb_tree_bytes;
+        if (len != need) return refuse(why, PG_ERR_INVALID, "pg_model_load: GBDT blob is %zu bytes, expected %zu", len, need);
+        if (!std::isfinite(m->gb_base)) return refuse(why, PG_ERR_UNSUPPORTED, "pg_model_load: the GBDT's base score is not finite");
+        for (uint32_t t = 0; t < m->gb_ntree; ++t) {
+            const uint8_t* const tr = p + lay->gb_trees + t * lay->gb_tree_bytes;
+            for (size_t n = 0; n < nn; ++n) {
+                uint32_t w;
+                float thr;
+                memcpy(&w, tr + n * 4, 4);
+                memcpy(&thr, tr + (nn + n) * 4, 4);
+                if ((w & 0x7Fu) >= m->gb_nu + m->gb_ni)
+                    return refuse(why, PG_ERR_UNSUPPORTED, "pg_model_load: GBDT tree %u node %zu splits on feature %u of %u", t, n, w & 0x7Fu, m->gb_nu + m->gb_ni);
+                if (thr != thr) return refuse(why, PG_ERR_UNSUPPORTED, "pg_model_load: GBDT tree %u node %zu has a NaN threshold", t, n);
+            }
+            for (size_t l = 0; l < nl; ++l) {
+                float v;
+                memcpy(&v, tr + (2 * nn + l) * 4, 4);
+                if (!std::isfinite(v)) return refuse(why, PG_ERR_UNSUPPORTED, "pg_model_load: GBDT tree %u leaf %zu is not finite", t, l);
+            }
+        }
     } else if (kind == PG_MODEL_DCN) {
         m->kind = PG_MODEL_DCN;
         if (len < 24) return refuse(why, PG_ERR_INVALID, "pg_model_load: blob too short");
@@ -908,6 +963,33 @@ inline void pack_mha(const pg_model* m, const float* wq, const float* bq, const 
     o->wo = pack_weights(wo, da, kDinD, bf16 ? 1 : 0);
 }
 
+// PG_MODEL_GBDT: the forest as rank_gbdt.hip walks it.  Tree t's record (gbdt_tree_bytes) sits at byte t * gbdt_tree_bytes of the
+// buffer, so chunk c is bytes [c, c + 1) * kGbdtChunkBytes; the last chunk is zero-filled behind the last tree.  A record is the
+// blob's tree with every level REVERSED: heap index m (root 1) has its left child at 2m + 1 and its right child at 2m, so the walk
+// shifts the compare's outcome in.  Node slot m - 1 at 8 (m - 1) = { word, thr } — one 8-byte LDS read per visit —, slot 2^d - 1
+// unused, then the leaves at 8 << d, reversed as well.  word: the feature index in bits 0..6 (the walk multiplies the low 24
+// bits by the feature rows' pitch) and the missing-left flag in bits 30 AND 31: word >> 30 is then the NaN class mask.
+inline std::vector<uint8_t> pack_gbdt(const pg_model* m, const uint8_t* trees, size_t blob_tree_bytes) {
+    const uint32_t d = m->gb_depth, tpc = gbdt_chunk_trees(d), nn = (1u << d) - 1, nl = nn + 1;
+    const size_t rec = gbdt_tree_bytes(d);
+    std::vector<uint8_t> out((size_t)((m->gb_ntree + tpc - 1) / tpc) * kGbdtChunkBytes, 0);
+    for (uint32_t t = 0; t < m->gb_ntree; ++t) {
+        const uint8_t* const src = trees + t * blob_tree_bytes;
+        uint8_t* const dst = out.data() + t * rec;
+        for (uint32_t s = 0; s < d; ++s)
+            for (uint32_t o = 0; o < (1u << s); ++o) {
+                const uint32_t n = (1u << s) - 1 + o, slot = (2u << s) - 2 - o;      // blob node n -> heap index 2^s + (2^s - 1 - o), less 1
+                uint32_t w;
+                memcpy(&w, src + 4 * n, 4);
+                w = (w & 0x7Fu) | ((w >> 31) * 0xC0000000u);
+                memcpy(dst + 8 * slot, &w, 4);
+                memcpy(dst + 8 * slot + 4, src + 4 * (nn + n), 4);
+            }
+        for (uint32_t l = 0; l < nl; ++l) memcpy(dst + 8 * (size_t)nl + 4 * (nl - 1 - l), src + 4 * (size_t)(2 * nn + l), 4);
+    }
+    return out;
+}
+
 // ---- what goes to the device ---------------------------------------------------------------------------------------------
 // One allocation of a loaded model: `bytes` from `src` (the blob, or a buffer ModelUploads owns) into a device buffer whose
 // address *dst receives; `lo`: the member that points at the second half of that buffer (the lo fragments of split operands).
@@ -955,6 +1037,8 @@ inline int model_uploads(pg_model* m, const BlobLayout& lay, const void* blob, M
         add(&m->b2, at(lay.b2), (size_t)m->h2 * 4);
         add_floats(&m->w3, std::move(w3t));
         add(&m->b3v, at(lay.b3), (size_t)m->n_out * 4);
+    } else if (m->kind == PG_MODEL_GBDT) {
+        add_packed(&m->gb_forest, pack_gbdt(m, p + lay.gb_trees, lay.gb_tree_bytes), nullptr);
     } else if (m->kind == PG_MODEL_MMOE) {
         MmoePacked pk;
         pack_mmoe(m, at(lay.we), at(lay.be), at(lay.wg), at(lay.bg), at(lay.wt), at(lay.bt), at(lay.wo), at(lay.bo), &pk);

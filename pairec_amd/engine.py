@@ -14,7 +14,8 @@ import numpy as np
 from . import _lib
 
 PREC_F32, PREC_BF16, PREC_BF16X3, PREC_F16X2, PREC_F16 = 0, 1, 2, 3, 4
-MODEL_DNN3, MODEL_FM_TWOTOWER, MODEL_DNN3_MULTI, MODEL_DIN, MODEL_MMOE, MODEL_DCN, MODEL_MHA, MODEL_PLE = 1, 2, 3, 4, 5, 6, 8, 9
+MODEL_DNN3, MODEL_FM_TWOTOWER, MODEL_DNN3_MULTI, MODEL_DIN, MODEL_MMOE, MODEL_DCN, MODEL_MHA, MODEL_PLE, MODEL_GBDT = 1, 2, 3, 4, 5, 6, 8, 9, 10
+GBDT_CHUNK_BYTES, GBDT_WIDE_ITEMS, GBDT_WIDE_TILE = _lib.GBDT_CHUNK_BYTES, _lib.GBDT_WIDE_ITEMS, _lib.GBDT_WIDE_TILE   # rank_gbdt.hip's chunk and tiles
 DIN_MAX_SEQ = 64
 MHA_MAX_SEQ = 512
 MAX_QUERIES = 256         # per table pass (32 when dim > 128)
@@ -2274,6 +2275,49 @@ def pack_ple(levels, wt, bt, wo, bo, d_user: int) -> bytes:
     return b"".join(parts + [wt.tobytes(), f(bt).tobytes(), f(wo).tobytes(), f(bo).tobytes()])
 
 
+def gbdt_chunk_trees(depth: int) -> int:
+    """whole trees per LDS chunk of rank_gbdt.hip at this depth"""
+    return GBDT_CHUNK_BYTES // (12 << depth)
+
+
+def pack_gbdt(trees, n_user_feat: int, n_item_feat: int, base: float, objective: int, le: bool = False) -> bytes:
+    """PG_MODEL_GBDT blob (include/pairec_gpu.h) from pointer trees as an xgboost / PS-SMART dump gives them: per tree a mapping of
+    arrays feature, threshold, left, right, missing_left, value over its nodes, node 0 the root, a leaf a node with left < 0.  Every
+    tree becomes a complete tree of the forest's depth (at least 1, at most 8): a leaf reached early is copied into every leaf
+    beneath it, over nodes with feature 0 and threshold +inf.  le: the splits are PMML lessOrEqual ones — x <= thr is x < the next
+    fp32 above thr.  objective 0: logistic, 1: identity."""
+    def levels(t):
+        """the pointer node under every slot of each level of tree t, until all are leaves"""
+        left, right = np.asarray(trees[t]["left"], dtype=np.int64), np.asarray(trees[t]["right"], dtype=np.int64)
+        cur, out = np.zeros(1, dtype=np.int64), []
+        while True:
+            out.append(cur)
+            inner = left[cur] >= 0
+            if not inner.any():
+                return out
+            if len(out) > 8:
+                raise ValueError("pack_gbdt: tree %d is deeper than 8" % t)
+            cur = np.stack([np.where(inner, left[cur], cur), np.where(inner, right[cur], cur)], axis=1).reshape(-1)
+    depth = max([1] + [len(levels(t)) - 1 for t in range(len(trees))])
+    parts = [struct.pack("<5If", n_user_feat, n_item_feat, len(trees), depth, objective, base)]
+    for t, tr in enumerate(trees):
+        feat, miss = np.asarray(tr["feature"], dtype=np.int64), np.asarray(tr["missing_left"], dtype=np.int64)
+        thr, val = np.asarray(tr["threshold"], dtype=np.float32), np.asarray(tr["value"], dtype=np.float32)
+        left = np.asarray(tr["left"], dtype=np.int64)
+        if le:
+            thr = np.nextafter(thr, np.float32(np.inf))
+        lv = levels(t)
+        while len(lv) <= depth:                     # a shallow tree: its leaves stay under their own slots
+            lv.append(np.repeat(lv[-1], 2))
+        cur = np.concatenate(lv[:depth])
+        inner = left[cur] >= 0
+        if np.any(inner & ((feat[cur] < 0) | (feat[cur] >= n_user_feat + n_item_feat))):
+            raise ValueError("pack_gbdt: tree %d splits on a feature outside 0..%d" % (t, n_user_feat + n_item_feat - 1))
+        word = np.where(inner, feat[cur] | ((miss[cur] != 0).astype(np.int64) << 31), 0).astype(np.uint32)
+        parts += [word.tobytes(), np.where(inner, thr[cur], np.float32(np.inf)).astype(np.float32).tobytes(), val[lv[depth]].tobytes()]
+    return b"".join(parts)
+
+
 def pack_dcn(wc, bc, w1, b1, w2, b2, w3, b3, d_user: int) -> bytes:
     """PG_MODEL_DCN blob (include/pairec_gpu.h): cross layers wc [L][D][D], bc [L][D] over x_0 = [user | item], D = d_user + d_item;
     head w1 [D][h1], b1, w2 [h1][h2], b2, w3 [h2] or [h2][n_out], b3 [n_out]."""
@@ -2418,6 +2462,23 @@ class RankModel:
     def rank_ple_dev(self, table: Table, d_user_vecs: int, d_cand_rows: int, d_req_offsets: int, n_req: int, n_items: int, d_out: int):
         _lib.check(self.ctx.L.pg_rank_ple_dev(self.ctx.h, self.h, table.h, C.c_void_p(d_user_vecs), C.c_void_p(d_cand_rows),
                                               C.c_void_p(d_req_offsets), n_req, n_items, C.c_void_p(d_out)))
+
+    def rank_gbdt(self, feats: "Features", item_cols, user_feats: np.ndarray, cand_rows: np.ndarray, req_offsets: Sequence[int]) -> np.ndarray:
+        """MODEL_GBDT: scores [n_items].  item_cols: the n_item_feat columns of `feats` (names or indices) behind the model's item
+        features; user_feats [n_req][n_user_feat]; a candidate row past the store reads the columns' defaults."""
+        cols = feats._cols(item_cols)
+        u = np.ascontiguousarray(user_feats, dtype=np.float32)
+        c = np.ascontiguousarray(cand_rows, dtype=np.uint32)
+        ro = np.ascontiguousarray(req_offsets, dtype=np.uint32)
+        out = np.empty(c.shape[0], dtype=np.float32)
+        _lib.check(self.ctx.L.pg_rank_gbdt(self.ctx.h, self.h, feats.h, _ptr(cols), _ptr(u), _ptr(c), _ptr(ro), ro.shape[0] - 1, _ptr(out)))
+        return out
+
+    def rank_gbdt_dev(self, feats: "Features", item_cols, d_user_feats: int, d_cand_rows: int, d_req_offsets: int, n_req: int, n_items: int,
+                      d_out: int):
+        cols = feats._cols(item_cols)
+        _lib.check(self.ctx.L.pg_rank_gbdt_dev(self.ctx.h, self.h, feats.h, _ptr(cols), C.c_void_p(d_user_feats), C.c_void_p(d_cand_rows),
+                                               C.c_void_p(d_req_offsets), n_req, n_items, C.c_void_p(d_out)))
 
     def rank_dcn(self, table: Table, user_vecs: np.ndarray, cand_rows: np.ndarray, req_offsets: Sequence[int]) -> np.ndarray:
         """MODEL_DCN: scores [n_items] for one output, [n_out][n_items] for several (one plane per head)."""

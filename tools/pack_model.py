@@ -36,6 +36,11 @@ Input: an .npz whose arrays are the layers' kernels exactly as a framework saves
       wq [64][d_att]   bq [d_att]   wk [64][d_att]   wv [64][d_att]   bv [d_att]   wo [d_att][64]   n_head (integer array, or --n-head)
       ((d_att, n_head) one of (64,1) (64,2) (128,2) (128,4); a key bias cancels in the softmax and an output bias belongs in b1)
       w1 [d_user + 128][h1] (rows: user, item row, pooled)   b1, w2, b2 as above   w3 [h2] or [h2][n_out]   b3 [n_out]
+  GBDT (PG_MODEL_GBDT: a PS-SMART / xgboost forest; chosen when the file holds `tree_ptr`).  Pointer trees, every array the
+  concatenation over trees, tree t's nodes at [tree_ptr[t], tree_ptr[t + 1]) with its root first and child indices local to it:
+      feature, threshold, left, right (left < 0: a leaf), missing_left, value   tree_ptr [n_tree + 1]
+      n_user_feat, n_item_feat, base, objective (0 logistic, 1 identity), le (optional, 1: PMML lessOrEqual splits) as scalars
+      (trees at most 8 deep; a feature indexes [user features | item columns]; no --d-user)
   --d-user N says where the user half of w1 ends (or an integer array `d_user` inside the file); d_item = the table's dim
   (64 or 128).  --map w1=dense/kernel,b1=dense/bias,… renames arrays.  Supported hidden shapes: see the header.
 
@@ -48,7 +53,7 @@ import sys
 import numpy as np
 
 DNN3_SHAPES = {(128, 128), (256, 128), (256, 256), (512, 256), (1024, 512)}
-KIND_DNN3, KIND_DNN3_MULTI, KIND_DIN, KIND_MMOE, KIND_DCN, KIND_MHA, KIND_PLE = 1, 3, 4, 5, 6, 8, 9
+KIND_DNN3, KIND_DNN3_MULTI, KIND_DIN, KIND_MMOE, KIND_DCN, KIND_MHA, KIND_PLE, KIND_GBDT = 1, 3, 4, 5, 6, 8, 9, 10
 MMOE_SHAPES = {(2, 128), (4, 64), (4, 128), (8, 64)}
 DCN_HEADS = {(128, 128), (256, 128)}
 MHA_SHAPES = {(64, 1), (64, 2), (128, 2), (128, 4)}
@@ -202,6 +207,45 @@ def pack_dcn_arrays(wc, bc, w1, b1, w2, b2, w3, b3, d_user):
     return KIND_DCN, blob, "PG_MODEL_DCN [%d+%d], %d cross layers -> %d -> %d -> %d, %d bytes" % (d_user, d_item, n_l, h1, h2, n_out, len(blob))
 
 
+def pack_gbdt_trees(trees, n_user, n_item, base, objective, le=False):
+    """trees: per tree a mapping feature, threshold, left, right, missing_left, value → (KIND_GBDT, blob, description); every tree
+    completed to the forest's depth — an early leaf copied beneath itself, over nodes (feature 0, threshold +inf)"""
+    def levels(t):
+        left, right = np.asarray(trees[t]["left"], dtype=np.int64), np.asarray(trees[t]["right"], dtype=np.int64)
+        cur, out = np.zeros(1, dtype=np.int64), []
+        while True:
+            out.append(cur)
+            inner = left[cur] >= 0
+            if not inner.any():
+                return out
+            if len(out) > 8:
+                raise ValueError("tree %d is deeper than 8" % t)
+            cur = np.stack([np.where(inner, left[cur], cur), np.where(inner, right[cur], cur)], axis=1).reshape(-1)
+    if not (0 <= n_user <= 64 and 0 <= n_item <= 64 and n_user + n_item >= 1 and 1 <= len(trees) <= 4096 and objective in (0, 1)):
+        raise ValueError("%d + %d features, %d trees, objective %d have no kernel (0..64 + 0..64 features, 1..4096 trees, objective 0 or 1)" %
+                         (n_user, n_item, len(trees), objective))
+    depth = max([1] + [len(levels(t)) - 1 for t in range(len(trees))])
+    parts = [struct.pack("<5If", n_user, n_item, len(trees), depth, objective, base)]
+    for t, tr in enumerate(trees):
+        feat, miss, left = (np.asarray(tr[k], dtype=np.int64) for k in ("feature", "missing_left", "left"))
+        thr = np.asarray(tr["threshold"], dtype=np.float32)
+        if le:
+            thr = np.nextafter(thr, np.float32(np.inf))
+        lv = levels(t)
+        while len(lv) <= depth:
+            lv.append(np.repeat(lv[-1], 2))
+        cur = np.concatenate(lv[:depth])
+        inner = left[cur] >= 0
+        if np.any(inner & ((feat[cur] < 0) | (feat[cur] >= n_user + n_item))):
+            raise ValueError("tree %d splits on a feature outside 0..%d" % (t, n_user + n_item - 1))
+        if np.any(np.isnan(thr[cur][inner])):
+            raise ValueError("tree %d has a NaN threshold" % t)
+        parts += [np.where(inner, feat[cur] | ((miss[cur] != 0).astype(np.int64) << 31), 0).astype(np.uint32).tobytes(),
+                  np.where(inner, thr[cur], np.float32(np.inf)).astype(np.float32).tobytes(), _f32(np.asarray(tr["value"])[lv[depth]], what="value").tobytes()]
+    blob = b"".join(parts)
+    return KIND_GBDT, blob, "PG_MODEL_GBDT [%d+%d] features, %d trees of depth %d, objective %d, %d bytes" % (n_user, n_item, len(trees), depth, objective, len(blob))
+
+
 def pack_npz(path_or_mapping, d_user=None, rename=None, n_head=None):
     """Load the arrays (an .npz path or a mapping name → array) and pack them; → (kind, blob, description)."""
     z = np.load(path_or_mapping) if isinstance(path_or_mapping, (str, bytes)) else path_or_mapping
@@ -212,6 +256,13 @@ def pack_npz(path_or_mapping, d_user=None, rename=None, n_head=None):
         if key not in z:
             raise KeyError("array \"%s\" not in the file (have: %s)" % (key, ", ".join(sorted(z.keys()))))
         return z[key]
+    if rename.get("tree_ptr", "tree_ptr") in z:
+        ptr = np.asarray(get("tree_ptr"), dtype=np.int64)
+        names = ("feature", "threshold", "left", "right", "missing_left", "value")
+        trees = [{k: np.asarray(get(k))[ptr[t]:ptr[t + 1]] for k in names} for t in range(len(ptr) - 1)]
+        scalar = lambda n: np.asarray(get(n)).reshape(-1)[0]   # noqa: E731
+        return pack_gbdt_trees(trees, int(scalar("n_user_feat")), int(scalar("n_item_feat")), float(scalar("base")), int(scalar("objective")),
+                               bool(scalar("le")) if rename.get("le", "le") in z else False)
     if d_user is None:
         d_user = int(np.asarray(get("d_user")).reshape(-1)[0])
     if rename.get("we1_t", "we1_t") in z:
