@@ -70,7 +70,7 @@ typedef enum {
  *                  Refused at load (PG_ERR_UNSUPPORTED): PG_MODEL_FM_TWOTOWER; a non-finite weight; a scaled weight or
  *                  scale factor outside fp32's normal range. */
 typedef enum { PG_PREC_F32 = 0, PG_PREC_BF16 = 1, PG_PREC_BF16X3 = 2, PG_PREC_F16X2 = 3, PG_PREC_F16 = 4 } pg_prec;
-typedef enum { PG_MODEL_DNN3 = 1, PG_MODEL_FM_TWOTOWER = 2, PG_MODEL_DNN3_MULTI = 3, PG_MODEL_DIN = 4, PG_MODEL_MMOE = 5, PG_MODEL_DCN = 6, PG_MODEL_MHA = 8, PG_MODEL_PLE = 9, PG_MODEL_GBDT = 10 /* 7 is kept unassigned: pg_model_load refuses it as unknown */ } pg_model_kind;
+typedef enum { PG_MODEL_DNN3 = 1, PG_MODEL_FM_TWOTOWER = 2, PG_MODEL_DNN3_MULTI = 3, PG_MODEL_DIN = 4, PG_MODEL_MMOE = 5, PG_MODEL_DCN = 6, PG_MODEL_MHA = 8, PG_MODEL_PLE = 9, PG_MODEL_GBDT = 10, PG_MODEL_MIND = 11 /* 7 is kept unassigned: pg_model_load refuses it as unknown */ } pg_model_kind;
 
 const char* pg_last_error(void);
 const char* pg_version(void);
@@ -186,6 +186,59 @@ int pg_i2i_recall(pg_ctx* ctx, const pg_table* trigger_table, const uint32_t* tr
  * embedding (pg_fm2t_user_embedding), `item_emb` the item-tower outputs as a table of dim t_out. */
 int pg_online_vector_recall(pg_ctx* ctx, const pg_model* m, const pg_table* item_emb, const float* user_vecs,
                             uint32_t n_req, uint32_t k, uint64_t* out_rows, float* out_scores, uint32_t* out_count);
+/* ---- recall: MIND — a multi-interest user model by capsule routing, and its multi-interest recall (PG_MODEL_MIND) ---------------
+ *   Replaces  the remote EasyRec MIND model behind a multi-interest recall: OnlineHologresVectorRecall splits the model's answer
+ *             on "|" into several user embeddings, gives every one RecallCount / parts rows and appends the lists
+ *             (service/recall/online_hologres_vector_recall.go:186-223); the realtime-embedding trigger reads `user_interests`
+ *             and per-interest neighbour lists of DimLength interests x DimSize neighbours
+ *             (service/recall/berecall/user_realtime_embedding_mind_trigger.go:80-139, algorithm/eas/easyrec_response.go:374-466,
+ *             EasyrecUserRealtimeEmbeddingMindResponse), which be_x2i_recall.go:183-204 feeds on.
+ *   Model     per request, over the user vector u (d_user) and the VALID sequence rows s_0 .. s_{n-1} of the 64-wide seq_table:
+ *               u^_j  = S' s_j                                              (64 -> 64)
+ *               b_kj  = b0[k][j]                 k = 0 .. K-1               (the fixed routing-logit init of the blob)
+ *               for it = 1 .. n_iter:
+ *                   w_kj = softmax over k of b_.j                           (max-subtracted)
+ *                   z_k  = sum_j w_kj u^_j
+ *                   v_k  = z_k |z_k|^2 / ((1 + |z_k|^2) sqrt(|z_k|^2 + 1e-9))                    (squash)
+ *                   if it < n_iter:  b_kj += v_k . u^_j
+ *               h_k        = relu(Wc' v_k + Wu' u + b1)                     (h1)
+ *               interest_k = W2' h_k + b2                                   (d_out)
+ *               if normalize:  interest_k /= sqrt(|interest_k|^2 + 1e-12)
+ *             With n = 0 every z_k and v_k is 0 and the K interests are one function of u: the model's answer, not an error.
+ *   Blob      u32 d_user (1..1024), d_out (64 | 128), n_interest K (1..8), n_iter (1..4), h1 (128 | 256), normalize (0 | 1);
+ *             then fp32, every matrix [in][out]: S[64][64], b0[K][PG_MIND_MAX_SEQ], Wc[64][h1], Wu[d_user][h1], b1[h1],
+ *             W2[h1][d_out], b2[d_out] — little-endian.  pa.pack_mind / tools/pack_model.py build it.
+ *   Precision PG_PREC_F32 only: nothing is rounded below fp32 (the summation orders: DESIGN.md 5).
+ *   Masking   the valid rows are the first min(len, PG_MIND_MAX_SEQ) entries of the request's sequence whose row is below the
+ *             table's row count, compacted in order (PG_MODEL_MHA's rule); j is the compacted position.
+ *   Output    pg_mind_interests: out_interests[n_req][K][d_out].  pg_mind_recall: every interest is one query of the exact
+ *             inner-product recall (pg_recall_topk) over item_emb at depth floor(k / K); a request's K lists are appended in
+ *             interest order — out_rows / out_scores [n_req][K][k / K], out_count[n_req * K] — and nothing is deduplicated
+ *             (UniqueFilter or the fan-in does that).  Requests are served floor(256 / K) per table pass.
+ *             pg_model_num_outputs() = K.
+ *   Refused   pg_model_load (PG_ERR_UNSUPPORTED): any other precision, a header field outside the lists above, a non-finite
+ *             weight; a blob of another length: PG_ERR_INVALID.  The four calls (PG_ERR_INVALID, on the host, the context left
+ *             usable): a model of another kind, seq_table dim != 64, item_emb dim != d_out, n_req outside 1..256, k < K or
+ *             k / K > 16384; the host forms also offsets that descend or do not start at 0 and a sequence longer than
+ *             PG_MIND_MAX_SEQ (the _dev forms cannot see the lengths and use the first PG_MIND_MAX_SEQ entries).  Every rank
+ *             entry point, pg_online_vector_recall, pg_fm2t_* and pg_coalescer_create[_scene] refuse a PG_MODEL_MIND.
+ *             pg_mind_interests_dev only enqueues; pg_mind_recall_dev ends synchronised (out_count is host memory, as
+ *             pg_recall_topk_dev's) and keeps the interests in the context's staging slot.  seq_rows may be NULL when every
+ *             sequence is empty.
+ *   Not here  the dynamic interest number (K by the log of the length); label-aware attention (training only); position
+ *             embeddings; 128-wide sequence tables; bf16 forms; the coalescer and the pg_recommend_* pipelines; the squared-
+ *             Euclidean, filtered and excluded variants of the recall. */
+#define PG_MIND_MAX_SEQ 256
+int pg_mind_interests(pg_ctx* ctx, const pg_model* m, const pg_table* seq_table, const float* user_vecs, const uint32_t* seq_rows,
+                      const uint32_t* seq_offsets, uint32_t n_req, float* out_interests);
+int pg_mind_interests_dev(pg_ctx* ctx, const pg_model* m, const pg_table* seq_table, const float* d_user_vecs,
+                          const uint32_t* d_seq_rows, const uint32_t* d_seq_offsets, uint32_t n_req, float* d_out_interests);
+int pg_mind_recall(pg_ctx* ctx, const pg_model* m, const pg_table* seq_table, const pg_table* item_emb, const float* user_vecs,
+                   const uint32_t* seq_rows, const uint32_t* seq_offsets, uint32_t n_req, uint32_t k, uint64_t* out_rows,
+                   float* out_scores, uint32_t* out_count);
+int pg_mind_recall_dev(pg_ctx* ctx, const pg_model* m, const pg_table* seq_table, const pg_table* item_emb, const float* d_user_vecs,
+                       const uint32_t* d_seq_rows, const uint32_t* d_seq_offsets, uint32_t n_req, uint32_t k, uint64_t* d_out_rows,
+                       float* d_out_scores, uint32_t* out_count);
 /* merge `nlists` sorted/unsorted (row,score) lists of `per_list` entries per query into the global
  * top-k (multi-GPU: the lists are the all-gathered per-shard results).  Layout [nq][nlists][per_list]. */
 int pg_topk_merge_dev(pg_ctx* ctx, const uint64_t* d_rows, const float* d_scores, uint32_t nq,

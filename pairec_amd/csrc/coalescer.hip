@@ -1062,6 +1062,7 @@ int pg_coalescer_create_scene(pg_ctx* ctx, const pg_table* t, const pg_scene_con
         PG_REQUIRE(al.model->kind != PG_MODEL_DIN, "pg_coalescer_create: \"%s\" is a PG_MODEL_DIN: a coalescer's requests carry no behaviour sequence (pg_rank_din)", al.name);
         PG_REQUIRE(al.model->kind != PG_MODEL_PLE, "pg_coalescer_create: \"%s\" is a PG_MODEL_PLE: a coalescer serves DNN3 and two-tower models (pg_rank_ple)", al.name);
         PG_REQUIRE(al.model->kind != PG_MODEL_GBDT, "pg_coalescer_create: \"%s\" is a PG_MODEL_GBDT: a coalescer serves DNN3 and two-tower models (pg_rank_gbdt)", al.name);
+        PG_REQUIRE(al.model->kind != PG_MODEL_MIND, "pg_coalescer_create: \"%s\" is a PG_MODEL_MIND: a coalescer serves DNN3 and two-tower models (pg_mind_recall)", al.name);
         PG_REQUIRE(al.model->kind != PG_MODEL_MMOE, "pg_coalescer_create: \"%s\" is a PG_MODEL_MMOE: a coalescer serves DNN3 and two-tower models (pg_rank_mmoe)", al.name);
         PG_REQUIRE(al.model->kind != PG_MODEL_MHA, "pg_coalescer_create: \"%s\" is a PG_MODEL_MHA: a coalescer's requests carry no behaviour sequence (pg_rank_mha)", al.name);
         PG_REQUIRE(al.model->kind != PG_MODEL_DCN, "pg_coalescer_create: \"%s\" is a PG_MODEL_DCN: a coalescer serves DNN3 and two-tower models (pg_rank_dcn)", al.name);

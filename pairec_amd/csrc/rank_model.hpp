@@ -91,6 +91,9 @@ struct pg_model {
     uint32_t gb_nu = 0, gb_ni = 0, gb_ntree = 0, gb_depth = 0, gb_obj = 0;
     float gb_base = 0.f;
     void* gb_forest = nullptr;  // whole chunks of kGbdtChunkBytes, tree records back to back (gbdt_tree_bytes each)
+    // PG_MODEL_MIND (mind.hip): n_out = K interests of mi_dout columns after mi_iter routing iterations; d_user and h1 as a DNN3's
+    uint32_t mi_dout = 0, mi_iter = 0, mi_norm = 0;
+    float* mi_w = nullptr;      // the blob's arrays as they stand, array i at float MindLayout::at[i]
     float* b2 = nullptr;
     float* w3 = nullptr;    // DNN3 head(s): [n_out][h2]
     float* fields = nullptr;          // two-tower: all field tables, one allocation
@@ -157,6 +160,23 @@ constexpr uint32_t gbdt_tree_bytes(uint32_t depth) { return 12u << depth; }
 constexpr uint32_t gbdt_chunk_trees(uint32_t depth) { return kGbdtChunkBytes / gbdt_tree_bytes(depth); }
 inline bool gbdt_shape_ok(uint32_t nu, uint32_t ni, uint32_t nt, uint32_t d, uint32_t obj) {
     return nu <= kGbdtMaxFeat && ni <= kGbdtMaxFeat && nu + ni >= 1 && nt >= 1 && nt <= kGbdtMaxTrees && d >= 1 && d <= kGbdtMaxDepth && obj <= 1;
+}
+// PG_MODEL_MIND: where the blob's arrays S, b0, Wc, Wu, b1, W2, b2 start, in floats behind the 24-byte header, and their sum
+constexpr uint32_t kMindSeq = PG_MIND_MAX_SEQ, kMindD = 64, kMindMaxK = 8;
+enum { kMindS, kMindB0, kMindWc, kMindWu, kMindB1, kMindW2, kMindB2, kMindArrays };
+struct MindLayout {
+    size_t at[kMindArrays], floats;
+    MindLayout(uint32_t d_user, uint32_t d_out, uint32_t K, uint32_t h1) {
+        const size_t n[kMindArrays] = {(size_t)kMindD * kMindD, (size_t)K * kMindSeq, (size_t)kMindD * h1, (size_t)d_user * h1, h1, (size_t)h1 * d_out, d_out};
+        floats = 0;
+        for (int i = 0; i < kMindArrays; ++i) {
+            at[i] = floats;
+            floats += n[i];
+        }
+    }
+};
+inline bool mind_shape_ok(uint32_t du, uint32_t dout, uint32_t K, uint32_t it, uint32_t h1, uint32_t norm) {
+    return du >= 1 && du <= 1024 && (dout == 64 || dout == 128) && K >= 1 && K <= kMindMaxK && it >= 1 && it <= 4 && (h1 == 128 || h1 == 256) && norm <= 1;
 }
 inline bool fm2t_shape_ok(uint32_t th, uint32_t to, uint32_t k) {
 #define X(A, B, C) if (th == A && to == B && k == C) return true;
@@ -291,6 +311,8 @@ inline int parse_model_blob(int kind, int prec, const void* blob, size_t len, pg
         return refuse(why, PG_ERR_UNSUPPORTED, "pg_model_load: a PG_MODEL_GBDT is served in PG_PREC_F32 (precision %d asked)", prec);
     if (kind == PG_MODEL_DCN && prec != PG_PREC_BF16 && prec != PG_PREC_BF16X3)
         return refuse(why, PG_ERR_UNSUPPORTED, "pg_model_load: a PG_MODEL_DCN is served in PG_PREC_BF16 and PG_PREC_BF16X3 (precision %d asked)", prec);
+    if (kind == PG_MODEL_MIND && prec != PG_PREC_F32)
+        return refuse(why, PG_ERR_UNSUPPORTED, "pg_model_load: a PG_MODEL_MIND is served in PG_PREC_F32 (precision %d asked)", prec);
     const uint8_t* p = (const uint8_t*)blob;
     // an fp16 mode is the split-bf16 model (its whole-call and per-tile fallback) plus the fp16 operands
     m->prec = f16_nprod ? (int)PG_PREC_BF16X3 : prec;
@@ -461,6 +483,23 @@ inline int parse_model_blob(int kind, int prec, const void* blob, size_t len, pg
                 memcpy(&v, tr + (2 * nn + l) * 4, 4);
                 if (!std::isfinite(v)) return refuse(why, PG_ERR_UNSUPPORTED, "pg_model_load: GBDT tree %u leaf %zu is not finite", t, l);
             }
+        }
+    } else if (kind == PG_MODEL_MIND) {
+        m->kind = PG_MODEL_MIND;
+        if (len < 24) return refuse(why, PG_ERR_INVALID, "pg_model_load: blob too short");
+        uint32_t hdr[6];
+        memcpy(hdr, p, 24);
+        m->d_user = hdr[0]; m->mi_dout = hdr[1]; m->n_out = hdr[2]; m->mi_iter = hdr[3]; m->h1 = hdr[4]; m->mi_norm = hdr[5];
+        if (!mind_shape_ok(m->d_user, m->mi_dout, m->n_out, m->mi_iter, m->h1, m->mi_norm))
+            return refuse(why, PG_ERR_UNSUPPORTED, "pg_model_load: MIND shape d_user %u, d_out %u, %u interests, %u iterations, h1 %u, normalize %u "
+                                                   "unsupported (d_user 1..1024; d_out 64 or 128; 1..8 interests; 1..4 iterations; h1 128 or 256; "
+                                                   "normalize 0 or 1)", m->d_user, m->mi_dout, m->n_out, m->mi_iter, m->h1, m->mi_norm);
+        const size_t nfl = MindLayout(m->d_user, m->mi_dout, m->n_out, m->h1).floats;
+        if (len != 24 + nfl * 4) return refuse(why, PG_ERR_INVALID, "pg_model_load: MIND blob is %zu bytes, expected %zu", len, 24 + nfl * 4);
+        for (size_t i = 0; i < nfl; ++i) {
+            float v;
+            memcpy(&v, p + 24 + i * 4, 4);
+            if (!std::isfinite(v)) return refuse(why, PG_ERR_UNSUPPORTED, "pg_model_load: the MIND blob holds a non-finite weight (float %zu)", i);
         }
     } else if (kind == PG_MODEL_DCN) {
         m->kind = PG_MODEL_DCN;
@@ -1039,6 +1078,8 @@ inline int model_uploads(pg_model* m, const BlobLayout& lay, const void* blob, M
         add(&m->b3v, at(lay.b3), (size_t)m->n_out * 4);
     } else if (m->kind == PG_MODEL_GBDT) {
         add_packed(&m->gb_forest, pack_gbdt(m, p + lay.gb_trees, lay.gb_tree_bytes), nullptr);
+    } else if (m->kind == PG_MODEL_MIND) {         // [in][out] is the order the kernel reads: the arrays go up as they are
+        add(&m->mi_w, p + 24, MindLayout(m->d_user, m->mi_dout, m->n_out, m->h1).floats * 4);
     } else if (m->kind == PG_MODEL_MMOE) {
         MmoePacked pk;
         pack_mmoe(m, at(lay.we), at(lay.be), at(lay.wg), at(lay.bg), at(lay.wt), at(lay.bt), at(lay.wo), at(lay.bo), &pk);

@@ -14,10 +14,11 @@ import numpy as np
 from . import _lib
 
 PREC_F32, PREC_BF16, PREC_BF16X3, PREC_F16X2, PREC_F16 = 0, 1, 2, 3, 4
-MODEL_DNN3, MODEL_FM_TWOTOWER, MODEL_DNN3_MULTI, MODEL_DIN, MODEL_MMOE, MODEL_DCN, MODEL_MHA, MODEL_PLE, MODEL_GBDT = 1, 2, 3, 4, 5, 6, 8, 9, 10
+MODEL_DNN3, MODEL_FM_TWOTOWER, MODEL_DNN3_MULTI, MODEL_DIN, MODEL_MMOE, MODEL_DCN, MODEL_MHA, MODEL_PLE, MODEL_GBDT, MODEL_MIND = 1, 2, 3, 4, 5, 6, 8, 9, 10, 11
 GBDT_CHUNK_BYTES, GBDT_WIDE_ITEMS, GBDT_WIDE_TILE = _lib.GBDT_CHUNK_BYTES, _lib.GBDT_WIDE_ITEMS, _lib.GBDT_WIDE_TILE   # rank_gbdt.hip's chunk and tiles
 DIN_MAX_SEQ = 64
 MHA_MAX_SEQ = 512
+MIND_MAX_SEQ = 256
 MAX_QUERIES = 256         # per table pass (32 when dim > 128)
 
 
@@ -2347,6 +2348,26 @@ def pack_mha(wq, bq, wk, wv, bv, wo, w1, b1, w2, b2, w3, b3, d_user: int, n_head
             w3.tobytes() + b3.tobytes())
 
 
+def pack_mind(S, b0, Wc, Wu, b1, W2, b2, n_iter: int, normalize) -> bytes:
+    """PG_MODEL_MIND blob (include/pairec_gpu.h): S [64][64], the routing-logit init b0 [K][MIND_MAX_SEQ], Wc [64][h1], Wu [d_user][h1],
+    b1 [h1], W2 [h1][d_out], b2 [d_out] — every matrix [in][out].  ValueError for shapes the header does not list."""
+    f = lambda a: np.ascontiguousarray(a, dtype=np.float32)   # noqa: E731
+    S, b0, Wc, Wu, b1, W2, b2 = f(S), f(b0), f(Wc), f(Wu), f(b1).reshape(-1), f(W2), f(b2).reshape(-1)
+    if S.shape != (64, 64) or b0.ndim != 2 or b0.shape[1] != MIND_MAX_SEQ or not 1 <= b0.shape[0] <= 8:
+        raise ValueError("pack_mind: S is [64][64] and b0 [1..8][%d], got %s and %s" % (MIND_MAX_SEQ, S.shape, b0.shape))
+    if Wc.ndim != 2 or Wc.shape[0] != 64 or Wc.shape[1] not in (128, 256):
+        raise ValueError("pack_mind: Wc is [64][128 or 256], got %s" % (Wc.shape,))
+    h1 = Wc.shape[1]
+    if Wu.ndim != 2 or Wu.shape[1] != h1 or not 1 <= Wu.shape[0] <= 1024 or b1.shape != (h1,):
+        raise ValueError("pack_mind: Wu is [1..1024][%d] and b1 [%d], got %s and %s" % (h1, h1, Wu.shape, b1.shape))
+    if W2.ndim != 2 or W2.shape[0] != h1 or W2.shape[1] not in (64, 128) or b2.shape != (W2.shape[1],):
+        raise ValueError("pack_mind: W2 is [%d][64 or 128] and b2 as wide, got %s and %s" % (h1, W2.shape, b2.shape))
+    if not 1 <= int(n_iter) <= 4:
+        raise ValueError("pack_mind: 1..4 routing iterations, got %d" % n_iter)
+    return (struct.pack("<6I", Wu.shape[0], W2.shape[1], b0.shape[0], int(n_iter), h1, 1 if normalize else 0) + S.tobytes() + b0.tobytes() +
+            Wc.tobytes() + Wu.tobytes() + b1.tobytes() + W2.tobytes() + b2.tobytes())
+
+
 def pack_fm2t(w) -> bytes:
     """w: object with the attributes of oracle.Fm2tWeights (duck-typed; no oracle import here)."""
     parts = [struct.pack("<7If", w.nuf, w.nif, w.k, w.d_user, w.t_h1, w.t_out, w.vocab, w.fm_b)]
@@ -2524,6 +2545,54 @@ class RankModel:
         _lib.check(self.ctx.L.pg_online_vector_recall(self.ctx.h, self.h, item_emb.h, _ptr(u), n, k, _ptr(rows),
                                                       _ptr(scores), _ptr(counts)))
         return rows, scores, counts
+
+    def _mind_shape(self):
+        """(d_out, K) of a MODEL_MIND, from the blob's header"""
+        hdr = struct.unpack("<6I", self._blob_head[:24])
+        return hdr[1], hdr[2]
+
+    @staticmethod
+    def _mind_seqs(seqs):
+        so = np.zeros(len(seqs) + 1, dtype=np.uint32)
+        np.cumsum([len(s) for s in seqs], out=so[1:])
+        return np.ascontiguousarray(np.concatenate([np.asarray(s, dtype=np.uint32).reshape(-1) for s in seqs] + [np.zeros(0, np.uint32)])), so
+
+    def mind_interests(self, seq_table: Table, user_vecs: np.ndarray, seqs: Sequence[np.ndarray]) -> np.ndarray:
+        """MODEL_MIND: seqs[r] = the rows of `seq_table` in request r's behaviour sequence (at most MIND_MAX_SEQ; may be empty);
+        → interests [n_req][K][d_out]."""
+        d_out, K = self._mind_shape()
+        u = np.ascontiguousarray(user_vecs, dtype=np.float32)
+        sr, so = self._mind_seqs(seqs)
+        out = np.empty((len(seqs), K, d_out), dtype=np.float32)
+        _lib.check(self.ctx.L.pg_mind_interests(self.ctx.h, self.h, seq_table.h, _ptr(u), _ptr(sr), _ptr(so), len(seqs), _ptr(out)))
+        return out
+
+    def mind_interests_dev(self, seq_table: Table, d_user_vecs: int, d_seq_rows: int, d_seq_offsets: int, n_req: int, d_out: int):
+        """enqueue only: d_out receives [n_req][K][d_out]; a sequence's first MIND_MAX_SEQ entries count"""
+        _lib.check(self.ctx.L.pg_mind_interests_dev(self.ctx.h, self.h, seq_table.h, C.c_void_p(d_user_vecs), C.c_void_p(d_seq_rows),
+                                                    C.c_void_p(d_seq_offsets), n_req, C.c_void_p(d_out)))
+
+    def mind_recall(self, seq_table: Table, item_emb: Table, user_vecs: np.ndarray, seqs: Sequence[np.ndarray], k: int):
+        """MODEL_MIND: every interest recalls k // K rows of item_emb → (rows, scores [n_req][K][k // K], counts [n_req][K]);
+        a request's lists are appended in interest order, nothing deduplicated."""
+        _, K = self._mind_shape()
+        u = np.ascontiguousarray(user_vecs, dtype=np.float32)
+        sr, so = self._mind_seqs(seqs)
+        n, kd = len(seqs), max(k // K, 0)
+        rows, scores = np.empty((n, K, kd), dtype=np.uint64), np.empty((n, K, kd), dtype=np.float32)
+        counts = np.zeros((n, K), dtype=np.uint32)
+        _lib.check(self.ctx.L.pg_mind_recall(self.ctx.h, self.h, seq_table.h, item_emb.h, _ptr(u), _ptr(sr), _ptr(so), n, k, _ptr(rows),
+                                             _ptr(scores), _ptr(counts)))
+        return rows, scores, counts
+
+    def mind_recall_dev(self, seq_table: Table, item_emb: Table, d_user_vecs: int, d_seq_rows: int, d_seq_offsets: int, n_req: int, k: int,
+                        d_out_rows: int, d_out_scores: int) -> np.ndarray:
+        """device pointers in and out ([n_req][K][k // K]); → counts [n_req][K] (the call ends synchronised)"""
+        counts = np.zeros((n_req, self._mind_shape()[1]), dtype=np.uint32)
+        _lib.check(self.ctx.L.pg_mind_recall_dev(self.ctx.h, self.h, seq_table.h, item_emb.h, C.c_void_p(d_user_vecs), C.c_void_p(d_seq_rows),
+                                                 C.c_void_p(d_seq_offsets), n_req, k, C.c_void_p(d_out_rows), C.c_void_p(d_out_scores),
+                                                 _ptr(counts)))
+        return counts
 
     def rank_fm2t_rows(self, feats: "Features", item_field_names, user_vecs, user_field_ids, cand_rows,
                        req_offsets) -> np.ndarray:

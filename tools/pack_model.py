@@ -41,6 +41,10 @@ Input: an .npz whose arrays are the layers' kernels exactly as a framework saves
       feature, threshold, left, right (left < 0: a leaf), missing_left, value   tree_ptr [n_tree + 1]
       n_user_feat, n_item_feat, base, objective (0 logistic, 1 identity), le (optional, 1: PMML lessOrEqual splits) as scalars
       (trees at most 8 deep; a feature indexes [user features | item columns]; no --d-user)
+  MIND (PG_MODEL_MIND: a multi-interest user model, the behaviour sequence routed into K capsules; chosen when the file holds
+  `routing_init`):
+      s [64][64]   routing_init [K][256] (the fixed routing-logit init; K 1..8)   wc [64][h1]   wu [d_user][h1]   b1 [h1]
+      w2 [h1][d_out]   b2 [d_out]   n_iter (1..4) and normalize (0 | 1) as scalars   (h1 128 or 256; d_out 64 or 128; no --d-user)
   --d-user N says where the user half of w1 ends (or an integer array `d_user` inside the file); d_item = the table's dim
   (64 or 128).  --map w1=dense/kernel,b1=dense/bias,… renames arrays.  Supported hidden shapes: see the header.
 
@@ -53,7 +57,7 @@ import sys
 import numpy as np
 
 DNN3_SHAPES = {(128, 128), (256, 128), (256, 256), (512, 256), (1024, 512)}
-KIND_DNN3, KIND_DNN3_MULTI, KIND_DIN, KIND_MMOE, KIND_DCN, KIND_MHA, KIND_PLE, KIND_GBDT = 1, 3, 4, 5, 6, 8, 9, 10
+KIND_DNN3, KIND_DNN3_MULTI, KIND_DIN, KIND_MMOE, KIND_DCN, KIND_MHA, KIND_PLE, KIND_GBDT, KIND_MIND = 1, 3, 4, 5, 6, 8, 9, 10, 11
 MMOE_SHAPES = {(2, 128), (4, 64), (4, 128), (8, 64)}
 DCN_HEADS = {(128, 128), (256, 128)}
 MHA_SHAPES = {(64, 1), (64, 2), (128, 2), (128, 4)}
@@ -246,6 +250,22 @@ def pack_gbdt_trees(trees, n_user, n_item, base, objective, le=False):
     return KIND_GBDT, blob, "PG_MODEL_GBDT [%d+%d] features, %d trees of depth %d, objective %d, %d bytes" % (n_user, n_item, len(trees), depth, objective, len(blob))
 
 
+def pack_mind_arrays(s, b0, wc, wu, b1, w2, b2, n_iter, normalize):
+    """→ (KIND_MIND, blob, description); every matrix [in][out]"""
+    b0, wc, wu, w2 = np.asarray(b0), np.asarray(wc), np.asarray(wu), np.asarray(w2)
+    if b0.ndim != 2 or wc.ndim != 2 or wu.ndim != 2 or w2.ndim != 2:
+        raise ValueError("routing_init, wc, wu and w2 are matrices")
+    K, h1, d_user, d_out = b0.shape[0], wc.shape[1], wu.shape[0], w2.shape[1]
+    if not (1 <= K <= 8 and h1 in (128, 256) and 1 <= d_user <= 1024 and d_out in (64, 128) and 1 <= n_iter <= 4 and normalize in (0, 1)):
+        raise ValueError("%d interests, h1 %d, d_user %d, d_out %d, %d iterations, normalize %d have no kernel (1..8 interests; h1 128 or 256; "
+                         "d_user 1..1024; d_out 64 or 128; 1..4 iterations; normalize 0 or 1)" % (K, h1, d_user, d_out, n_iter, normalize))
+    parts = [_f32(s, (64, 64), "s"), _f32(b0, (K, 256), "routing_init"), _f32(wc, (64, h1), "wc"), _f32(wu, (d_user, h1), "wu"),
+             _f32(np.asarray(b1).reshape(-1), (h1,), "b1"), _f32(w2, (h1, d_out), "w2"), _f32(np.asarray(b2).reshape(-1), (d_out,), "b2")]
+    blob = struct.pack("<6I", d_user, d_out, K, n_iter, h1, normalize) + b"".join(p.tobytes() for p in parts)
+    return KIND_MIND, blob, "PG_MODEL_MIND d_user %d, %d interests of %d, %d iterations, h1 %d, normalize %d, %d bytes" % (
+        d_user, K, d_out, n_iter, h1, normalize, len(blob))
+
+
 def pack_npz(path_or_mapping, d_user=None, rename=None, n_head=None):
     """Load the arrays (an .npz path or a mapping name → array) and pack them; → (kind, blob, description)."""
     z = np.load(path_or_mapping) if isinstance(path_or_mapping, (str, bytes)) else path_or_mapping
@@ -263,6 +283,9 @@ def pack_npz(path_or_mapping, d_user=None, rename=None, n_head=None):
         scalar = lambda n: np.asarray(get(n)).reshape(-1)[0]   # noqa: E731
         return pack_gbdt_trees(trees, int(scalar("n_user_feat")), int(scalar("n_item_feat")), float(scalar("base")), int(scalar("objective")),
                                bool(scalar("le")) if rename.get("le", "le") in z else False)
+    if rename.get("routing_init", "routing_init") in z:
+        scalar = lambda n: int(np.asarray(get(n)).reshape(-1)[0])   # noqa: E731
+        return pack_mind_arrays(*[get(n) for n in ("s", "routing_init", "wc", "wu", "b1", "w2", "b2")], scalar("n_iter"), scalar("normalize"))
     if d_user is None:
         d_user = int(np.asarray(get("d_user")).reshape(-1)[0])
     if rename.get("we1_t", "we1_t") in z:
